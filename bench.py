@@ -21,7 +21,12 @@ touches the GPU) and relays rank 0's line.
 At EVERY N one extra leg runs the SAME global problem (48^3 x 96, all 25 slots, N_ev = --strong-nev), unpartitioned at N = 1 and on the
 T-then-Z process grid otherwise, and reports it at the top level (`strong_scaling`): the speedup of the partitioned path from 1 to N GPUs.
 
-After the timed region (not part of `value`; skipped with --no-extra) the other legs of the path are measured too and
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs of the last step if
+--dump-outputs DIR is given, and the line.  Everything else it measures or checks runs only with --full: the read-bandwidth
+probe (`probe_GBps`), the CPU baseline (`cpu_baseline`, not with --no-cpu-baseline), the detail file, the strong-scaling and
+partitioned legs above and the extra legs below (not with --no-extra).
+
+With --full, after the timed region (not part of `value`) the other legs of the path are measured too and
 reported under `also_measured`, each with its own roofline block, timed by HIP events inside the driver
 (mugiq_hip_loop_set_profiling):
   N = 1 : the configs[2] job on its per-GPU lattice at the metric's N_ev = 400 (48.48.24.24, 8 entries x lengths 1..3,
@@ -34,7 +39,7 @@ reported under `also_measured`, each with its own roofline block, timed by HIP e
           before the wait, boundary tiles after; halo bytes, transfer time and the interior / boundary split are reported.
           N = 4 and 8 run the metric's own 48^3 x 96, N_ev = 400 (204 / 102 GB of eigenvectors per GPU).
 
-Usage: python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+Usage: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]        (N>1: launched by torch.distributed.run)
 """
 import argparse
 import hashlib
@@ -66,6 +71,10 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the probe, the CPU baseline and the extra legs, and write the detail file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the loop traces of the last timed step as DIR/<name>.npy (rank 0; a fixed, seeded sample of sites)")
     ap.add_argument("--lattice", type=int, nargs=4, default=[32, 32, 32, 32], help="LOCAL lattice per GPU (x y z t)")
     ap.add_argument("--nev", type=int, default=200)
     ap.add_argument("--precision", type=int, default=8, choices=[4, 8])
@@ -75,8 +84,8 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline budget (rank 0, N=1 only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true",
-                    help="only the headline (use this under `rocprofv3 --stats`: the extra legs launch the headline kernel with "
-                         "other shapes and would blur its per-kernel average)")
+                    help="with --full: no extra legs (a plain run has none either: use one under `rocprofv3 --stats`, the extra legs "
+                         "launch the headline kernel with other shapes and would blur its per-kernel average)")
     ap.add_argument("--extra", default="", help="comma list restricting the extra legs: displaced,forced,strong,mg,cfg3 (N=1) / strong,partitioned,native (N>1)")
     ap.add_argument("--displaced-nev", type=int, default=400, help="eigenvectors of the displaced extra legs (configs[2]: 400 = 102 GB; 100 for a quick run)")
     ap.add_argument("--strong-nev", type=int, default=48, help="eigenvectors of the strong-scaling leg (48^3 x 96 on every N; 48 fit one GPU "
@@ -93,7 +102,10 @@ def parse():
     ap.add_argument("--strong-grid", type=int, nargs=4, default=None)
     ap.add_argument("--detail-file", default="", help="where the full record (every leg, per-phase times, per-kernel rooflines) goes; "
                                                       "default gpurun_out/bench_detail_n<N>.json")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 # ---- synthetic inputs -------------------------------------------------------------------------
@@ -845,6 +857,27 @@ def extra_native(hip, device, a, world, rank, backend):
     return out
 
 
+# ---- outputs of the timed path ---------------------------------------------------------------------------------------------
+DUMP_SITES = 65536             # sites of the stored sample: 16 MB in fp64
+DUMP_SEED = 20240611
+
+
+def dump_outputs(loop, V, out_dir):
+    """What a caller of the timed path receives -- the 16 loop traces of every site, [16][2 parity][volumeCB] -- written as
+    DIR/loop_sample.npy: [16][S][re, im] at a fixed, seeded sample of S sites (sorted even-odd site indices), and
+    DIR/loop_gamma_stats.npy: [16][sum re, sum im, l2 norm] over ALL sites.  float64 for fp64 loops, float32 for fp32."""
+    rdt = np.float64 if loop.dtype == torch.complex128 else np.float32
+    S = min(DUMP_SITES, V)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(V, S, replace=False))
+    g = loop.view(16, V)
+    sample = torch.view_as_real(g.index_select(1, torch.from_numpy(idx).to(loop.device))).cpu().numpy()
+    w = g.to(torch.complex128)
+    stats = torch.stack([w.real.sum(1), w.imag.sum(1), torch.linalg.vector_norm(w, dim=1)], dim=1).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loop_sample.npy"), sample.astype(rdt))
+    np.save(os.path.join(out_dir, "loop_gamma_stats.npy"), stats.astype(rdt))
+
+
 # ---- main --------------------------------------------------------------------------------------------------------------
 def self_launch(a):
     """`python bench.py --gpus N` typed without a launcher: start the N ranks as CHILDREN (python -m torch.distributed.run)
@@ -936,18 +969,21 @@ def main():
     elapsed, kern_ms = float(t[0]), float(t[1])
     ms_per_step = elapsed * 1e3 / a.steps
     value = world * V / (ms_per_step * 1e-3)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(loop, V, a.dump_outputs)                            # `loop` holds the last timed step's traces
 
-    # what this device streams right now: a pure 16-B/lane non-temporal read of the SAME eigenvector buffer, same process,
-    # straight after the timed region (tells a slow kernel from slow memory when a box runs off the usual numbers)
-    probe_ms = []
-    for r in range(6):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        hip.probeReadBandwidth(big, 1)
-        e1.record()
-        torch.cuda.synchronize()
-        probe_ms.append(e0.elapsed_time(e1))
-    probe_gbs = big.numel() * big.element_size() / (float(np.median(probe_ms[1:])) * 1e-3) / 1e9
+    if a.full:
+        # what this device streams right now: a pure 16-B/lane non-temporal read of the SAME eigenvector buffer, same process,
+        # straight after the timed region (tells a slow kernel from slow memory when a box runs off the usual numbers)
+        probe_ms = []
+        for r in range(6):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            hip.probeReadBandwidth(big, 1)
+            e1.record()
+            torch.cuda.synchronize()
+            probe_ms.append(e0.elapsed_time(e1))
+        probe_gbs = big.numel() * big.element_size() / (float(np.median(probe_ms[1:])) * 1e-3) / 1e9
 
     alg_bytes = V * (nev * 24 * B + 32 * lprec)      # per site N_ev*24*B read + 32*B written
     achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
@@ -980,15 +1016,16 @@ def main():
                      "kernel_ms_stats": {"min": float(step_ms.min()), "median": float(np.median(step_ms)), "max": float(step_ms.max()),
                                          "mean": float(step_ms.mean()), "n": int(a.steps),
                                          "note": "per-launch HIP event times of the timed steps on rank 0; kernel_ms = their median "
-                                                 "(max over ranks)"},
-                     "probe_GBps": probe_gbs, "frac_of_probe": achieved / probe_gbs,
-                     "probe_note": "probe = read_probe_kernel, 16-B non-temporal loads over the same eigenvector buffer, same process, "
-                                   "right after the timed region (median of 5)"},
+                                                 "(max over ranks)"}},
     }
+    if a.full:
+        out["roofline"].update({"probe_GBps": probe_gbs, "frac_of_probe": achieved / probe_gbs,
+                                "probe_note": "probe = read_probe_kernel, 16-B non-temporal loads over the same eigenvector buffer, same process, "
+                                              "right after the timed region (median of 5)"})
     if world > 1:
         out["backend"] = backend
         out["nccl_ranks"] = dist.get_world_size() if backend == "nccl" else 0   # ranks RCCL saw (0: rehearsal over another backend)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         base, cpu_loop, S = cpu_baseline(fields, sig, X, prec, order, a.cpu_seconds)
         # the same sample on the GPU result: the checker agrees with what was just timed
         g = loop.view(16, 2, V // 2)[:, :, :S].reshape(-1).cpu().numpy()
@@ -1008,17 +1045,19 @@ def main():
             if not printed.is_set():
                 printed.set()
                 if rank == 0:
-                    try:
-                        os.makedirs(os.path.dirname(os.path.abspath(detail_path)), exist_ok=True)
-                        with open(detail_path, "w") as f:
-                            json.dump(out, f, indent=1)
-                        where = detail_path
-                    except OSError as e:
-                        where = "not written: %s" % e
+                    where = None                                    # a plain run writes no detail file unless --detail-file asks
+                    if a.full or a.detail_file:
+                        try:
+                            os.makedirs(os.path.dirname(os.path.abspath(detail_path)), exist_ok=True)
+                            with open(detail_path, "w") as f:
+                                json.dump(out, f, indent=1)
+                            where = detail_path
+                        except OSError as e:
+                            where = "not written: %s" % e
                     sys.stdout.write(compact_line(out, where) + "\n")       # the LAST stdout line, and the only one starting with {"metric"
                     sys.stdout.flush()
 
-    if not a.no_extra:
+    if a.full and not a.no_extra:
         del fields, big, loop
         torch.cuda.empty_cache()
         want = [w for w in a.extra.split(",") if w]

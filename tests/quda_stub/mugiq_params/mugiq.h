@@ -1,7 +1,6 @@
 // STUB (tests/quda_stub/README.md): stands where MuGiq's include/mugiq.h stands in a real build -- a MugiqLoopParam with the
 // member names include/mugiq_hip_operators.hpp mirrors (declaration order is irrelevant to the adapter, which reads them by name)
-// and the declaration of the five-argument computeLoop.  Where /root/reference is mounted the syntax test uses the reference's own
-// header instead of this one (it needs nothing of QUDA beyond three parameter-struct names).
+// and the declaration of the five-argument computeLoop.
 #pragma once
 #include <string>
 #include <vector>

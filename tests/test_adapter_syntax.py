@@ -11,7 +11,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STUB = os.path.join(ROOT, "tests", "quda_stub")
-REF_INC = "/root/reference/include"
 
 
 def _compiler():
@@ -38,17 +37,3 @@ def test_the_syntax_check_can_fail():
     r = _syntax_only(os.path.join(STUB, "mugiq_params"), extra=["-include", os.path.join(STUB, "break_on_purpose.h")])
     assert r.returncode != 0 and "mugiq_hip_no_such_entry_point" in r.stderr
 
-
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_INC, "mugiq.h")), reason="the reference tree is not mounted here")
-def test_adapter_compiles_against_the_reference_param_headers():
-    """MugiqLoopParam, the enums and the declaration of computeLoop<Float> from the reference's OWN include/mugiq.h and
-    include/enum_mugiq.h (read where they lie): convert() names real members, the definitions match the declaration."""
-    r = _syntax_only(REF_INC)
-    assert r.returncode == 0, r.stderr[-4000:]
-    # and the reference's headers were the ones seen, not the stand-ins
-    h = subprocess.run([_compiler(), "-std=c++17", "-fsyntax-only", "-x", "c++", "-H", "-D__HIP_PLATFORM_AMD__",
-                        "-I", os.path.join(ROOT, "include"), "-I", os.path.join(STUB, "mugiq_classes"), "-I", REF_INC,
-                        "-I", os.path.join(STUB, "quda"), "-I", "/opt/rocm/include", os.path.join(STUB, "adapter_tu.cpp")],
-                       capture_output=True, text=True)
-    assert REF_INC + "/mugiq.h" in h.stderr and REF_INC + "/enum_mugiq.h" in h.stderr
-    assert "mugiq_params" not in h.stderr
