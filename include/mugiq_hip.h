@@ -252,6 +252,21 @@ int mugiq_hip_displaced_loop_contraction_fused_carry(void *loopData_d, int loopP
                                                      const void *ghostLayers_d, int layers, int region,
                                                      void *ultraLocalSlot_d, int *carried, void *stream);
 
+/* Two-sided form (new): the same contraction with separate LEFT and RIGHT vector sets,
+ *   loopData_d[slot i][tid + V*iG] += sum_n (1/sigma_n) vL_n^dag(x) G(iG) W_k(x) vR_n(x +- k mu),
+ * e.g. the deflated stochastic part of a disconnected loop (vL = gamma5 xi_r, vR = phi_r: INTEGRATION.md).  The signature of
+ * the _carry call with eVecL_h / eVecR_h in place of eVecs_h (same geometry, precision and order); the ghost layers are those of
+ * the RIGHT set (the only one that is displaced), the ultra-local slot is sum_n (1/sigma_n) vL_n^dag G vR_n.  It runs on the
+ * matrix-pipe tile (csrc/fused_mfma_kernel.h, two-sided form) only: MUGIQ_HIP_ERROR_UNSUPPORTED where that tile does not take the
+ * entry (lengths > 8 or not ascending, a partitioned x axis, no tile geometry for the extent) -- then the caller displaces vR step
+ * by step (mugiq_hip_perform_covariant_displacement_vector) and contracts with mugiq_hip_perform_loop_contraction_batched. */
+int mugiq_hip_displaced_loop_contraction_fused_two_sided(void *loopData_d, int loopPrecision,
+                                                         const MugiqHipSpinorField *eVecL_h, const MugiqHipSpinorField *eVecR_h,
+                                                         const double *sigma_h, int nVec, const void *const *pathLinkFields_h,
+                                                         const int *kValues_h, int nK, int dispDir, int dispSign,
+                                                         const int commDim[4], const void *ghostLayers_d, int layers, int region,
+                                                         void *ultraLocalSlot_d, int *carried, void *stream);
+
 /* ---- a8  Fourier phase matrix -------------------------------------------------------------------------- */
 /* createPhaseMatrixGPU<Float>(phaseMatrix_d, momMatrix_h, locV3, Nmom, FTSign, localL, totalL)
  * lib/contract_wrappers.cu:50-77, kernel lib/mugiq_util_kernels.cu:3-35.  commCoord[4] replaces QUDA's
@@ -504,6 +519,14 @@ typedef struct MugiqHipLoop_s MugiqHipLoop;
  * The descriptors are copied; the eigenvector memory stays the caller's. */
 int mugiq_hip_loop_create(MugiqHipLoop **loop, const MugiqHipLoopParam *param, const MugiqHipSpinorField *eVecs_h,
                           const double *eVals_sigma_h, int nEv, const MugiqHipComm *comm, void *stream);
+/* Two-sided loops (new): sum_r (1/sigma_r) vL_r^dag(x) G [D^k vR_r](x) for every entry, with separate left (eVecsL_h) and right
+ * (eVecsR_h, the displaced set) vectors of the same geometry, precision and order; fine-level vectors only.  Output pipeline (G -> g5 G
+ * reorder, momentum projection, HDF5 tree) as for mugiq_hip_loop_create.  No entry is reflected from its opposite-sign partner
+ * (mugiq_hip_loop_entry_derived_from is -1 for all), only the right set travels in halos, and halo face layers are packed by
+ * their own kernels.  For M^-1 ~ sum_r w_r phi_r xi_r^dag pass eVecsR = phi_r, eVecsL = g5 xi_r, sigma_r = 1 / w_r. */
+int mugiq_hip_loop_create_two_sided(MugiqHipLoop **loop, const MugiqHipLoopParam *param, const MugiqHipSpinorField *eVecsL_h,
+                                    const MugiqHipSpinorField *eVecsR_h, const double *sigma_h, int n, const MugiqHipComm *comm,
+                                    void *stream);
 /* The same with eigsolve->useMGenv && eigsolve->computeCoarse (lib/loop_mugiq.cpp:42,482; configs[4]): the
  * eigenvectors are COARSE fields and are prolonged with `transfer` (mugiq_hip_prolongate_batched) -- once, not once
  * per displacement entry; without displacement entries the ultra-local loop runs through
@@ -530,6 +553,15 @@ int mugiq_hip_loop_get_entry(const MugiqHipLoop *loop, int id, int out6[6]);
 /* After mugiq_hip_loop_compute: the entry that entry `id` was reflected from (see mugiq_hip_reflect_displaced_loop), or
  * -1 if it was computed from the eigenvectors; -2 for a bad handle / index. */
 int mugiq_hip_loop_entry_derived_from(const MugiqHipLoop *loop, int id);
+/* After mugiq_hip_loop_compute: how entry `id` was produced (one-sided and two-sided loops alike), or -1 for a bad handle / index or
+ * before the first compute. */
+#define MUGIQ_HIP_ENTRY_KERNEL_REFLECTED 0    /* derived from its opposite-sign partner (position or momentum space) */
+#define MUGIQ_HIP_ENTRY_KERNEL_MFMA_COLUMN 1  /* matrix-pipe tile, column tile (mu = y, z, t; csrc/fused_mfma_kernel.h) */
+#define MUGIQ_HIP_ENTRY_KERNEL_MFMA_ROW 2     /* matrix-pipe tile, row tile (mu = x) */
+#define MUGIQ_HIP_ENTRY_KERNEL_VECTOR_TILE 3  /* LDS-tiled vector kernels (csrc/fused_tile.hip, csrc/fused_tile16.hip) */
+#define MUGIQ_HIP_ENTRY_KERNEL_STREAMING 4    /* the streaming fused kernel (csrc/fused.hip) */
+#define MUGIQ_HIP_ENTRY_KERNEL_STEPWISE 5     /* one displacement + one contraction per step (BASIC plan and its fallbacks) */
+int mugiq_hip_loop_get_entry_kernel(const MugiqHipLoop *loop, int id);
 /* After mugiq_hip_loop_compute: the displacement entry whose pass over the eigenvectors also produced the ultra-local loop
  * (mugiq_hip_displaced_loop_contraction_fused_carry), or -1 if the ultra-local loop took a pass of its own. */
 int mugiq_hip_loop_ultra_local_carrier(const MugiqHipLoop *loop);

@@ -340,6 +340,23 @@ public:
       check(st);
     }
   }
+  // Two-sided loops (mugiq_hip_loop_create_two_sided): sum_r (1/sigma_r) vL_r^dag G [D^k vR_r] with the left set eVecsLeft and the
+  // right (displaced) set eVecsRight, fine-level fields of one geometry, precision and order (the stochastic remainder)
+  Loop_Mugiq(MugiqLoopParam *lp, const std::vector<ColorSpinorField> &eVecsLeft, const std::vector<ColorSpinorField> &eVecsRight,
+             const std::vector<double> &sigma, const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+    if (eVecsRight.empty() || eVecsLeft.size() != eVecsRight.size() || eVecsRight.size() != sigma.size())
+      throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "Loop_Mugiq(two-sided): eVecsLeft / eVecsRight / sigma size mismatch");
+    checkField<Float, fieldOrder>(&eVecsRight[0], "Loop_Mugiq");
+    checkField<Float, fieldOrder>(&eVecsLeft[0], "Loop_Mugiq");
+    CParam c;
+    fill(c, lp, comm, stream);
+    const int st = mugiq_hip_loop_create_two_sided(&h_, &c.p, eVecsLeft.data(), eVecsRight.data(), sigma.data(), (int)eVecsRight.size(),
+                                                   comm, stream);
+    if (st) {
+      mugiq_hip_free_extended_gauge(&ownGauge_);
+      check(st);
+    }
+  }
   // eigsolve->useMGenv && eigsolve->computeCoarse (lib/loop_mugiq.cpp:42,277-319,482): coarse eigenvectors on the coarsest
   // level of the hierarchy + mg_env->transfer[0 .. nCoarseLevels)
   Loop_Mugiq(MugiqLoopParam *lp, const std::vector<MugiqHipCoarseField> &coarseEvecs, const std::vector<double> &eVals_sigma,
@@ -372,6 +389,7 @@ public:
     return i;
   }
   MugiqHipLoop *handle() { return h_; }
+  int entryKernel(int id) const { return mugiq_hip_loop_get_entry_kernel(h_, id); }  // MUGIQ_HIP_ENTRY_KERNEL_* of the last compute
   const std::complex<Float> *dataPos_d() const { return static_cast<const std::complex<Float> *>(mugiq_hip_loop_data_pos_d(h_)); }
   const std::complex<Float> *dataPos() { return static_cast<const std::complex<Float> *>(mugiq_hip_loop_data_pos_h(h_)); }
   const std::complex<Float> *dataMom_bcast() const { return static_cast<const std::complex<Float> *>(mugiq_hip_loop_data_mom_bcast_h(h_)); }

@@ -84,6 +84,10 @@ SIGNATURES = {
                                                                         ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), _I4,
                                                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, _I4, _VP,
                                                                         ctypes.c_int, ctypes.c_int, _VP, _I4, _VP]),
+    "mugiq_hip_displaced_loop_contraction_fused_two_sided": (ctypes.c_int, [_VP, ctypes.c_int, _SP, _SP, ctypes.POINTER(ctypes.c_double),
+                                                                            ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), _I4,
+                                                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, _I4, _VP,
+                                                                            ctypes.c_int, ctypes.c_int, _VP, _I4, _VP]),
     "mugiq_hip_perform_covariant_displacement_vector": (ctypes.c_int, [_SP, _SP, _GP, ctypes.c_int, ctypes.c_int,
                                                                        _I4, _VP]),
     "mugiq_hip_pack_face": (ctypes.c_int, [_VP, _SP, ctypes.c_int, ctypes.c_int, _VP]),
@@ -137,12 +141,15 @@ SIGNATURES = {
     "mugiq_hip_loop_create_coarse": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _VP, ctypes.POINTER(CoarseDesc),
                                                     ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.POINTER(TransferDesc),
                                                     ctypes.c_int, _VP, _VP]),
+    "mugiq_hip_loop_create_two_sided": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _VP, _SP, _SP, ctypes.POINTER(ctypes.c_double),
+                                                       ctypes.c_int, _VP, _VP]),
     "mugiq_hip_loop_compute": (ctypes.c_int, [_VP]),
     "mugiq_hip_loop_get_info": (ctypes.c_int, [_VP, _VP]),
     "mugiq_hip_loop_set_profiling": (ctypes.c_int, [_VP, ctypes.c_int]),
     "mugiq_hip_loop_get_phases": (ctypes.c_int, [_VP, _VP, ctypes.c_int]),
     "mugiq_hip_loop_get_entry": (ctypes.c_int, [_VP, ctypes.c_int, _I4]),
     "mugiq_hip_loop_entry_derived_from": (ctypes.c_int, [_VP, ctypes.c_int]),
+    "mugiq_hip_loop_get_entry_kernel": (ctypes.c_int, [_VP, ctypes.c_int]),
     "mugiq_hip_loop_ultra_local_carrier": (ctypes.c_int, [_VP]),
     "mugiq_hip_loop_halos_packed_in_entry": (ctypes.c_int, [_VP]),
     "mugiq_hip_loop_data_pos_d": (_VP, [_VP]),

@@ -270,29 +270,33 @@ int tile_entry(void *loop_d, const MugiqHipSpinorField *ev, const double *sigma,
                int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers, int region, hipStream_t stream,
                void *ultra_d, int *carried);
 
-// fourth generation: the same tile in an axial gauge on the fp64 matrix pipe (any storage type, ascending lengths up to 8), csrc/fused_mfma.hip
-bool mfma_tile_applicable(const MugiqHipSpinorField &ev, int dir, const int *kvals, int nK, int partitioned, bool gaugeGiven);
-int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
-                    const int *kvals, int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers, int region,
-                    hipStream_t stream, void *ultra_d, int *carried);
+// (fourth generation, the matrix-pipe tile of csrc/fused_mfma.hip: internal.h)
 
 template <typename F, typename A, int ORDER>
 static int fused_entry(void *loop_d, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
                        const int *kvals, int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers,
-                       int region, hipStream_t stream, void *ultra_d, int *carried) {
+                       int region, hipStream_t stream, void *ultra_d, int *carried, const MugiqHipSpinorField *evL, int *kernel) {
   if (carried) *carried = 0;
   {
     int kmax = 0;
     for (int i = 0; i < nK; i++) kmax = kvals[i] > kmax ? kvals[i] : kmax;
     // (every storage type: the tile converts on the way into LDS and works in double; float slots are rounded once, on the way out)
-    if (mfma_tile_applicable(ev[0], dir, kvals, nK, partitioned, axial_gauge_hint_matches(E_d[0], dir, sign, kmax)))
-      return mfma_tile_entry(loop_d, (int)sizeof(A), ev, sigma, nVec, E_d, kvals, nK, dir, sign, partitioned, ghost_d, layers, region, stream, ultra_d, carried);
+    if (mfma_tile_applicable(ev[0], dir, kvals, nK, partitioned, axial_gauge_hint_matches(E_d[0], dir, sign, kmax), evL != nullptr)) {
+      *kernel = dir == 0 ? MUGIQ_HIP_ENTRY_KERNEL_MFMA_ROW : MUGIQ_HIP_ENTRY_KERNEL_MFMA_COLUMN;
+      return mfma_tile_entry(loop_d, (int)sizeof(A), ev, sigma, nVec, E_d, kvals, nK, dir, sign, partitioned, ghost_d, layers, region, stream, ultra_d, carried, evL);
+    }
+    if (evL)  // (no two-sided form of the vector tiles or of the streaming kernel)
+      return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "mugiq_hip_displaced_loop_contraction_fused_two_sided: the matrix-pipe tile does not take this entry "
+                       "(direction %d, lengths %d .. %d, partitioned %d, precision %d, order %d): use the step-by-step sequence", dir, kvals[0], kvals[nK - 1],
+                       partitioned, ev[0].precision, ev[0].field_order);
+    *kernel = MUGIQ_HIP_ENTRY_KERNEL_VECTOR_TILE;
     const bool gen2 = tile_applicable(ev[0], dir, kmax, ev[0].precision, partitioned);
     if (tile16_applicable(ev[0], dir, kmax, ev[0].precision, partitioned, gen2))
       return tile16_entry<F, A, ORDER>(loop_d, ev, sigma, nVec, E_d, kvals, nK, dir, sign, partitioned, ghost_d, layers, region, stream);
     if (gen2)
       return tile_entry<F, A, ORDER>(loop_d, ev, sigma, nVec, E_d, kvals, nK, dir, sign, partitioned, ghost_d, layers, region, stream, ultra_d, carried);
   }
+  *kernel = MUGIQ_HIP_ENTRY_KERNEL_STREAMING;
   // the streaming kernel has no interior / boundary split: when the dimension is partitioned it counts as boundary
   const int overwrite = (region & MUGIQ_HIP_REGION_OVERWRITE) ? 1 : 0;
   region &= 0xff;
@@ -387,14 +391,17 @@ int mugiq_hip_pack_face_layers(void *faces_d, const MugiqHipSpinorField *eVecs_h
   return pack_layers<float, 4>(faces_d, eVecs_h, nVec, dim, high, layers, s);
 }
 
-int mugiq_hip_displaced_loop_contraction_fused_carry(void *loopData_d, int loopPrecision, const MugiqHipSpinorField *eVecs_h,
-                                                     const double *sigma_h, int nVec, const void *const *pathLinkFields_h,
-                                                     const int *kValues_h, int nK, int dispDir, int dispSign,
-                                                     const int commDim[4], const void *ghostLayers_d, int layers, int region,
-                                                     void *ultraLocalSlot_d, int *carried, void *stream) {
+}  // extern "C"
+
+int mugiq::fused_contraction(void *loopData_d, int loopPrecision, const MugiqHipSpinorField *eVecL_h, const MugiqHipSpinorField *eVecs_h,
+                             const double *sigma_h, int nVec, const void *const *pathLinkFields_h, const int *kValues_h, int nK, int dispDir,
+                             int dispSign, const int commDim[4], const void *ghostLayers_d, int layers, int region, void *ultraLocalSlot_d,
+                             int *carried, void *stream, int *kernel) {
   if (int dbg_ = mugiq::debug_poison_lds_if_asked(static_cast<hipStream_t>(stream))) return dbg_;
   if (carried) *carried = 0;
-  const char *who = "mugiq_hip_displaced_loop_contraction_fused";
+  int kernelDummy = 0;
+  if (!kernel) kernel = &kernelDummy;
+  const char *who = eVecL_h ? "mugiq_hip_displaced_loop_contraction_fused_two_sided" : "mugiq_hip_displaced_loop_contraction_fused";
   MUGIQ_REQUIRE((region & 0xff) == MUGIQ_HIP_REGION_ALL || (region & 0xff) == MUGIQ_HIP_REGION_INTERIOR || (region & 0xff) == MUGIQ_HIP_REGION_BOUNDARY,
                 "%s: invalid region %d", who, region);
   MUGIQ_REQUIRE((region & ~(0xff | MUGIQ_HIP_REGION_OVERWRITE)) == 0, "%s: invalid region flags %d", who, region);
@@ -407,6 +414,10 @@ int mugiq_hip_displaced_loop_contraction_fused_carry(void *loopData_d, int loopP
     if (st) return st;
     MUGIQ_REQUIRE(same_geometry(eVecs_h[n], eVecs_h[0]), "%s: eigenvector %d differs in geometry from eigenvector 0", who, n);
     MUGIQ_REQUIRE(sigma_h[n] != 0.0, "%s: sigma[%d] is zero", who, n);
+    if (eVecL_h) {
+      if (int st = validate_spinor(&eVecL_h[n], who, "eVecL")) return st;
+      MUGIQ_REQUIRE(same_geometry(eVecL_h[n], eVecs_h[0]), "%s: left vector %d differs in precision, order or geometry from right vector 0", who, n);
+    }
   }
   const int part = commDim ? (commDim[dispDir] != 0) : 0;
   int kmax = 0;
@@ -428,7 +439,7 @@ int mugiq_hip_displaced_loop_contraction_fused_carry(void *loopData_d, int loopP
                 "%s: loop precision %d with field precision %d is not supported", who, loopPrecision, p);
 #define MUGIQ_FUSED_GO(F, A, O)                                                                                                 \
   return fused_entry<F, A, O>(loopData_d, eVecs_h, sigma_h, nVec, pathLinkFields_h, kValues_h, nK, dispDir, dispSign, part,   \
-                              ghostLayers_d, layers, region, s, ultraLocalSlot_d, carried)
+                              ghostLayers_d, layers, region, s, ultraLocalSlot_d, carried, eVecL_h, kernel)
   if (p == 8 && o == 2) MUGIQ_FUSED_GO(double, double, 2);
   if (p == 8 && o == 4) MUGIQ_FUSED_GO(double, double, 4);
   if (loopPrecision == 8 && o == 2) MUGIQ_FUSED_GO(float, double, 2);
@@ -436,6 +447,28 @@ int mugiq_hip_displaced_loop_contraction_fused_carry(void *loopData_d, int loopP
   if (o == 2) MUGIQ_FUSED_GO(float, float, 2);
   MUGIQ_FUSED_GO(float, float, 4);
 #undef MUGIQ_FUSED_GO
+}
+
+extern "C" {
+
+int mugiq_hip_displaced_loop_contraction_fused_carry(void *loopData_d, int loopPrecision, const MugiqHipSpinorField *eVecs_h,
+                                                     const double *sigma_h, int nVec, const void *const *pathLinkFields_h,
+                                                     const int *kValues_h, int nK, int dispDir, int dispSign,
+                                                     const int commDim[4], const void *ghostLayers_d, int layers, int region,
+                                                     void *ultraLocalSlot_d, int *carried, void *stream) {
+  return fused_contraction(loopData_d, loopPrecision, nullptr, eVecs_h, sigma_h, nVec, pathLinkFields_h, kValues_h, nK, dispDir, dispSign, commDim,
+                           ghostLayers_d, layers, region, ultraLocalSlot_d, carried, stream, nullptr);
+}
+
+int mugiq_hip_displaced_loop_contraction_fused_two_sided(void *loopData_d, int loopPrecision, const MugiqHipSpinorField *eVecL_h,
+                                                         const MugiqHipSpinorField *eVecR_h, const double *sigma_h, int nVec,
+                                                         const void *const *pathLinkFields_h, const int *kValues_h, int nK, int dispDir,
+                                                         int dispSign, const int commDim[4], const void *ghostLayers_d, int layers,
+                                                         int region, void *ultraLocalSlot_d, int *carried, void *stream) {
+  if (carried) *carried = 0;
+  MUGIQ_REQUIRE(eVecL_h != nullptr, "mugiq_hip_displaced_loop_contraction_fused_two_sided: NULL argument");
+  return fused_contraction(loopData_d, loopPrecision, eVecL_h, eVecR_h, sigma_h, nVec, pathLinkFields_h, kValues_h, nK, dispDir, dispSign, commDim,
+                           ghostLayers_d, layers, region, ultraLocalSlot_d, carried, stream, nullptr);
 }
 
 int mugiq_hip_displaced_loop_contraction_fused_region(void *loopData_d, int loopPrecision, const MugiqHipSpinorField *eVecs_h,

@@ -200,7 +200,8 @@ template <typename F> __global__ __launch_bounds__(64) void axial_gauge_from_lin
 
 // The tile geometry for an entry: the first TJ of {8, 12, 4} that divides the extent and keeps TJ + Kmax within the staged
 // positions of its line count (MUGIQ_HIP_MFMA_TJ = 4 | 8 | 12 fixes it); 0 = none.
-static int mfma_tile_tj(int extent, int kmax, int nSlots = kMT_MaxSlots, bool partitioned = true, bool reduced = false) {
+// (two-sided: 8 or 4 only -- a 12-position left image next to the right one exceeds the LDS of a workgroup)
+static int mfma_tile_tj(int extent, int kmax, int nSlots = kMT_MaxSlots, bool partitioned = true, bool reduced = false, bool two = false) {
   int want = 0;
   if (const char *e = getenv("MUGIQ_HIP_MFMA_TJ")) want = atoi(e);
   // 12 x 16 sites (1 + K/12 units staged per site) where it keeps its registers -- three groups per wave: up to three slots -- and the
@@ -210,6 +211,7 @@ static int mfma_tile_tj(int extent, int kmax, int nSlots = kMT_MaxSlots, bool pa
   for (int tj : {first, 8, 12, 4}) {
     if (want && tj != want) continue;
     if (reduced && tj == 4) continue;  // (storage types other than fp64 FLOAT2 come with the 16-line tiles only)
+    if (two && tj == 12) continue;
     if (extent % tj != 0 || tj + kmax > (tj == 4 ? 8 : 16)) continue;
     return tj;
   }
@@ -219,15 +221,16 @@ static int mfma_tile_tj(int extent, int kmax, int nSlots = kMT_MaxSlots, bool pa
 // mu = x: R whole rows per workgroup of W waves, G = 2 | 3 groups of 4 sites per wave: R X0 = 16 G W sites.  Two workgroups of 8
 // waves per CU where the rows allow, else one of 16 (MUGIQ_HIP_MFMA_ROW_WAVES = 8 | 16 fixes it).
 static bool mfma_reduced(const MugiqHipSpinorField &ev) { return !(ev.precision == 8 && ev.field_order == 2); }
-static bool mfma_row_geometry(const MugiqHipSpinorField &ev, int *groups, int *rows, int *waves) {
+static bool mfma_row_geometry(const MugiqHipSpinorField &ev, int *groups, int *rows, int *waves, bool two = false) {
   const int epr = ev.X[0] / 2, nRows = ev.volumeCB / epr;
   if (epr % 4 != 0) return false;
   int want = 0;
   if (const char *e = getenv("MUGIQ_HIP_MFMA_ROW_WAVES")) want = atoi(e);
   for (int w : {8, 16}) {  // (X0 = 48, N_ev 200, spill-free kernels: two workgroups of 8 waves per CU 13.1 ms per entry, one of 16 13.6)
     if (want && w != want) continue;
-    if (mfma_reduced(ev) && w != 8) continue;  // (... and with the 8-wave row tile only)
+    if ((mfma_reduced(ev) || two) && w != 8) continue;  // (... and with the 8-wave row tile only; so are the two-sided tiles)
     for (int g : {3, 2}) {
+      if (two && mfma_reduced(ev) && g != 2) continue;  // (two-sided, storage other than fp64 FLOAT2: 3 groups per wave spill)
       if ((2 * g * w) % epr != 0) continue;
       const int r = 2 * g * w / epr;
       if (nRows % r != 0 || r * 8 * (epr + kMT_MaxLength / 2) > 64 * w) continue;
@@ -244,7 +247,7 @@ static bool mfma_row_geometry(const MugiqHipSpinorField &ev, int *groups, int *r
 // Can the axial-gauge tile take this entry?  fp64 FLOAT2 storage and loops, mu = y, z, t, lengths 1 .. Kmax (the gauge is
 // built from W_1 .. W_Kmax).  MUGIQ_HIP_TILE_MFMA = 0 switches it off (the vector tiles of csrc/fused_tile.hip /
 // fused_tile16.hip take over).
-bool mfma_tile_applicable(const MugiqHipSpinorField &ev, int dir, const int *kvals, int nK, int partitioned, bool gaugeGiven) {
+bool mfma_tile_applicable(const MugiqHipSpinorField &ev, int dir, const int *kvals, int nK, int partitioned, bool gaugeGiven, bool two) {
   if (const char *e = getenv("MUGIQ_HIP_TILE_MFMA"))
     if (atoi(e) == 0) return false;
   if (const char *e = getenv("MUGIQ_HIP_FUSED_TILE"))
@@ -268,12 +271,18 @@ bool mfma_tile_applicable(const MugiqHipSpinorField &ev, int dir, const int *kva
     if (const char *e = getenv("MUGIQ_HIP_MFMA_ROW"))
       if (atoi(e) == 0) return false;
     if (2 * (int64_t)ev.parity_offset >= (1LL << 28)) return false;  // (the row tile keeps 32-bit BYTE offsets)
-    return !partitioned && mfma_row_geometry(ev, &g, &r, &w);
+    return !partitioned && mfma_row_geometry(ev, &g, &r, &w, two);
   }
-  return mfma_tile_tj(ev.X[dir], kmax, kMT_MaxSlots, true, mfma_reduced(ev)) != 0;
+  return mfma_tile_tj(ev.X[dir], kmax, kMT_MaxSlots, true, mfma_reduced(ev), two) != 0;
 }
 
 static int launch_mfma_tile(const MTileArgs &a, int precision, int order, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream) {
+  if (a.VL) {  // two-sided
+    if (precision == 8 && order == 2) return launch_mfma_tile_two_d2(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
+    if (precision == 8) return launch_mfma_tile_two_d4(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
+    if (order == 2) return launch_mfma_tile_two_f2(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
+    return launch_mfma_tile_two_f4(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
+  }
   if (precision == 8 && order == 2) return launch_mfma_tile_t<double, 2, true>(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
   if (precision == 8) return launch_mfma_tile_d4(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
   if (order == 2) return launch_mfma_tile_f2(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
@@ -402,16 +411,19 @@ int build_axial_gauge_from_links(void *G_d, const MugiqHipSpinorField &ev, const
 }
 
 // ultra_d != NULL: also produce the ultra-local loop (k = 0) into ultra_d as one more slot; *carried says whether that
-// happened (only a launch over the whole lattice may: see csrc/fused_tile.hip)
+// happened (only a launch over the whole lattice may: see csrc/fused_tile.hip).  evL != NULL: the two-sided tile, evL the left set
+// and ev the right (displaced) one
 int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
                     const int *kvals, int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers, int region,
-                    hipStream_t stream, void *ultra_d, int *carried) {
-  const size_t ptr_bytes = sizeof(void *) * (size_t)nVec;
+                    hipStream_t stream, void *ultra_d, int *carried, const MugiqHipSpinorField *evL) {
+  const bool two = evL != nullptr;
+  const size_t ptr_bytes = sizeof(void *) * (size_t)nVec * (two ? 2 : 1);
   std::vector<unsigned char> host(ptr_bytes + sizeof(double) * (size_t)nVec);
   const void **hl = reinterpret_cast<const void **>(host.data());
   double *hs = reinterpret_cast<double *>(host.data() + ptr_bytes);
   for (int n = 0; n < nVec; n++) {
     hl[n] = ev[n].data;
+    if (two) hl[nVec + n] = evL[n].data;
     hs[n] = 1.0 / sigma[n];
   }
   void *dev = nullptr;
@@ -422,6 +434,8 @@ int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *
   a.outFloat = loopPrecision == 4;
   if (carried) *carried = 0;
   a.L = reinterpret_cast<const void *const *>(dev);
+  a.VL = two ? a.L + nVec : nullptr;
+  a.leftBufElems = 0;
   a.inv_sigma = reinterpret_cast<const double *>(static_cast<unsigned char *>(dev) + ptr_bytes);
   a.nVec = nVec;
   long long strideMu = 1;
@@ -443,13 +457,14 @@ int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *
   int tj = 0, rowGroups = 0, rowWaves = 0;
   a.rowsPerTile = a.rowChunk = 0;
   if (dir == 0) {
-    MUGIQ_REQUIRE(mfma_row_geometry(ev[0], &rowGroups, &a.rowsPerTile, &rowWaves), "mfma tile: no row geometry for X0 = %d (internal)", ev[0].X[0]);
+    MUGIQ_REQUIRE(mfma_row_geometry(ev[0], &rowGroups, &a.rowsPerTile, &rowWaves, two), "mfma tile: no row geometry for X0 = %d (internal)", ev[0].X[0]);
     a.rowChunk = (a.rowsPerTile * (ev[0].X[0] / 2 + kMT_MaxLength / 2) + 12) / 16 * 16 + 4;  // > R (X0/2 + 4) (the entry behind the rows holds the zero of the padded operand lanes), and 4 mod 16 entries: 16 banks of phase per component
     MUGIQ_REQUIRE(24 * a.rowChunk <= (rowWaves == 8 ? kMT_BufElems / 2 : kMT_BufElems), "mfma tile: row image of %d entries per chunk does not fit (internal)", a.rowChunk);
+    if (two) a.leftBufElems = 24 * a.rowChunk;  // (the left image has the layout of the right one)
     ultra_d = nullptr;  // (the row tile takes no fourth slot)
     tj = ev[0].X[0];    // one "tile" along mu
   } else {
-    tj = mfma_tile_tj(ev[0].X[dir], kvals[nK - 1], kMT_MaxSlots, true, mfma_reduced(ev[0]));
+    tj = mfma_tile_tj(ev[0].X[dir], kvals[nK - 1], kMT_MaxSlots, true, mfma_reduced(ev[0]), two);
     MUGIQ_REQUIRE(tj != 0, "mfma tile: no tile geometry for extent %d, lengths up to %d (internal)", ev[0].X[dir], kvals[nK - 1]);
   }
   const int nJT = ev[0].X[dir] / tj;
@@ -472,7 +487,7 @@ int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *
   // k0 .. k1 stages the TJ + k1 positions its sites and their shifted partners live on
   for (int first = 0, ns = 0; first < nK; first += ns) {
     const bool takesUltra = ultra_d && first == 0;
-    const int room = dir == 0 ? kMT_MaxSlots - 1 : kMT_MaxSlots;  // (the row tile has no four-slot instance)
+    const int room = two ? mt_two_max_slots(dir, !mfma_reduced(ev[0])) : dir == 0 ? kMT_MaxSlots - 1 : kMT_MaxSlots;  // (the row tile has no four-slot instance)
     const int slotsLeft = nK - first + (takesUltra ? 1 : 0), launchesLeft = (slotsLeft + room - 1) / room;
     ns = (slotsLeft + launchesLeft - 1) / launchesLeft - (takesUltra ? 1 : 0);  // evenly: 1 .. 8 with the ultra-local loop = 3 + 3 + 3 slots
     a.kmax = kvals[first + ns - 1];
@@ -492,14 +507,15 @@ int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *
     // the tile of THIS launch (its slots and the positions it stages; the gauge does not depend on it)
     int tjL = tj, nJTL = nJT;
     if (dir != 0) {
-      const int t2 = mfma_tile_tj(ev[0].X[dir], a.kmax, nSlots, partitioned != 0, mfma_reduced(ev[0]));
+      const int t2 = mfma_tile_tj(ev[0].X[dir], a.kmax, nSlots, partitioned != 0, mfma_reduced(ev[0]), two);
       if (t2) tjL = t2;
       nJTL = ev[0].X[dir] / tjL;
+      if (two) a.leftBufElems = mt_left_buf_elems(tjL);
     }
     // region 0: everything | 1: tiles whose shifted reads stay inside the local lattice | 2: tiles that read ghost layers
     // (the split is by the ENTRY's longest length, so that the interior and the boundary launch of a slot cover complementary tiles)
     a.nPack = 0;
-    if (dir == 0 && first == 0 && g_pack.n > 0 && !g_pack.taken && ev[0].X[1] % a.rowsPerTile == 0) {  // the first launch of the entry packs
+    if (!two && dir == 0 && first == 0 && g_pack.n > 0 && !g_pack.taken && ev[0].X[1] % a.rowsPerTile == 0) {  // the first launch of the entry packs
       a.nPack = g_pack.n;
       for (int i = 0; i < g_pack.n; i++) {
         const int fcb = ev[0].volumeCB / ev[0].X[g_pack.t[i].dim];

@@ -22,11 +22,18 @@ constexpr int kMT_MaxPack = 4;   // face-layer targets a row-tile launch can fil
 constexpr int kMT_Chunk = 68;     // complex elements per chunk: 64 + 4 of bank phase
 constexpr int kMT_Chunks = 4 * 12;  // chunks of a tile buffer: 64 / LN positions each, 12 components, <= 4 * 64 / LN staged positions
 constexpr int kMT_BufElems = kMT_Chunks * kMT_Chunk;
+constexpr size_t kMT_MaxLds = 160 * 1024;  // LDS of one workgroup (gfx950)
+// two-sided column tiles: one buffer of the left image holds the TJ own positions (TJ / (64 / LN) position chunks of 12 components)
+constexpr int mt_left_buf_elems(int tj) { return tj / (64 / (tj == 4 ? 32 : 16)) * 12 * kMT_Chunk; }
+// slots per two-sided launch that compile without scratch (128 VGPRs): 3 on the fp64 FLOAT2 column tiles, else 2
+constexpr int mt_two_max_slots(int dir, bool full) { return dir != 0 && full ? 3 : 2; }
 
 struct MTileArgs {
   void *out[kMT_MaxSlots];  // Cplx<double> | Cplx<float> (outFloat)
   int outFloat;
-  const void *const *L;
+  const void *const *L;    // the eigenvectors staged at TJ + kmax positions (two-sided: the RIGHT set, vR)
+  const void *const *VL;   // two-sided only: the LEFT set vL, staged at the TJ own positions (row tile: the rows' own sites)
+  int leftBufElems;        // two-sided only: complex elements of one buffer of the left image (behind the two right buffers)
   const double *inv_sigma;
   int nVec;
   int X[4];
@@ -79,11 +86,17 @@ __host__ __device__ inline void mt_line(int cid, int H, int strideMu, int J, int
 // parities; R X0 = 128 | 192 sites, TJ = 0 and LN = 16 * groups per wave in the template) and there is no halo at all: the
 // positions past the end of the row (sign +) or before its start (sign -) are the row's own first / last sites, staged a
 // second time with the continued gauge g(J + l) | g(-l).  LDS image: chunk (parity, component) = [row][X0/2 + 2] complex.
-template <int DIR, int SIGN, int NS, int TJ, int LN, bool PACK = false, typename F = double, int ORDER = 2>
+//
+// TWO (two-sided loops, sum_n vL_n^dag G [D^k vR_n] / sigma_n): the right set is staged as above (a.L, ghost layers included); the left
+// set (a.VL) only at the tile's own positions, by the staging threads of those positions, with the same g, into a left image of its
+// own (two buffers of a.leftBufElems behind the two right buffers).  The V operand is read from the left image, P from the right one;
+// the ultra-local slot (k = 0) pairs the two images at the same site.
+template <int DIR, int SIGN, int NS, int TJ, int LN, bool PACK = false, typename F = double, int ORDER = 2, bool TWO = false>
 __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile_displaced_contract_kernel(MTileArgs a) {
   // F, ORDER: the eigenvectors' storage (double | float; FLOAT2 | FLOAT4).  They are converted on their way into LDS; the tile images, the
   // gauge and the products are double whatever the storage, the slots double or float (a.outFloat)
   static_assert(!PACK || (std::is_same<F, double>::value && ORDER == 2), "face layers are written on the way for fp64 FLOAT2 only");
+  static_assert(!(PACK && TWO), "two-sided tiles write no face layers");
   // element k = 3 spin + colour of checkerboard entry x in a field body of stride `stride` (complex elements from the parity base)
   auto fieldOff = [](int k, int x, int stride) { return ORDER == 2 ? k * stride + x : (((k >> 1) * stride + x) << 1) + (k & 1); };  // 4 waves per SIMD: <= 128 VGPRs
   constexpr bool kRow = DIR == 0;
@@ -124,6 +137,8 @@ __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile
   const int compStride = kRow ? a.rowChunk : kMT_Chunk;  // distance of two components in the LDS image
   constexpr int bufElems = kWaves == 8 ? kMT_BufElems / 2 : kMT_BufElems;  // one tile buffer (two 8-wave workgroups share a CU's LDS)
   bool commits = stages;
+  bool commitsL = false;  // (TWO) this thread stages the left vector at an own position, into wIdxL of the left image
+  int wIdxL = 0;
   // (row tile, PACK) this thread's (component << 20) | entry within the (y, x) plane of a face, or -1; everything else of the pack
   // addressing is per workgroup (its rows share z and t) and is told to the compiler to be: scalar registers, scalar arithmetic
   int pkAB = -1;
@@ -165,6 +180,8 @@ __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile
     for (int c = 0; c < 3; c++) offC[c] = (int)((int64_t)par * a.parity_offset + fieldOff(3 * spin + c, rowG * EPR + (js >> 1), a.stride));
     wIdx = (parity * 12 + 3 * spin) * a.rowChunk + row * EPRX + mm;
     commits = valid;
+    commitsL = TWO && valid && mm >= rOff && mm < rOff + EPR;  // (the same layout as the right image; own positions only)
+    wIdxL = wIdx;
     sByte = (unsigned)soff * (unsigned)sizeof(Cplx<F>);  // (< 2^32: mfma_tile_applicable)
     if constexpr (PACK) {  // the R rows of a workgroup share z and t (X1 % R == 0, checked by the launcher)
       const int m = mm - rOff;  // a real position of the row (not a continued one): this thread owns the site
@@ -198,6 +215,11 @@ __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile
       for (int c = 0; c < 3; c++) offC[c] = (int)((int64_t)par * a.parity_offset + fieldOff(3 * sspin + c, base + j * a.strideMu, a.stride));
     }
     wIdx = ((spp / kPPC) * 12 + 3 * sspin) * kMT_Chunk + (spp % kPPC) * kMT_Cols + sline;
+    if constexpr (TWO) {  // own positions: [0, TJ) of the window (sign +) | [kmax, kmax + TJ) (sign -); never a ghost site
+      const int lp = (SIGN == MUGIQ_HIP_DISP_SIGN_PLUS) ? spp : spp - a.kmax;
+      commitsL = lp >= 0 && lp < kMT_TJ;
+      wIdxL = commitsL ? ((lp / kPPC) * 12 + 3 * sspin) * kMT_Chunk + (lp % kPPC) * kMT_Cols + sline : 0;
+    }
   }
   const Cplx<F> *ghostBase = reinterpret_cast<const Cplx<F> *>(a.ghost);
 
@@ -222,7 +244,7 @@ __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile
       continue;
     }
     const int gid = wave * kMT_Groups + gi, gpos = gid / kGP, gline = 4 * (gid % kGP) + b;
-    vIdx[gi] = elemIdx((SIGN == MUGIQ_HIP_DISP_SIGN_PLUS) ? gpos : a.kmax + gpos, gline);
+    vIdx[gi] = elemIdx(TWO ? gpos : ((SIGN == MUGIQ_HIP_DISP_SIGN_PLUS) ? gpos : a.kmax + gpos), gline);  // (TWO: the left image)
 #pragma unroll
     for (int s = 0; s < NS; s++) pIdx[gi][s] = elemIdx((SIGN == MUGIQ_HIP_DISP_SIGN_PLUS) ? gpos + a.k[s] : a.kmax + gpos - a.k[s], gline);
   }
@@ -230,7 +252,10 @@ __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile
   // image -- no commit ever writes there -- that holds 0 in BOTH buffers (the right operand may hold anything finite in its padded
   // lanes: its addresses point at real data)
   const int zeroCell = kRow ? a.rowChunk - 1 : 64;
-  if (t < 2) tileBase[(size_t)t * bufElems + zeroCell] = Cplx<double>{0.0, 0.0};
+  // (TWO: the left operand comes from the left image, whose two buffers follow the right ones)
+  Cplx<double> *leftBase = TWO ? tileBase + (size_t)2 * bufElems : tileBase;
+  const size_t leftBuf = TWO ? (size_t)a.leftBufElems : (size_t)bufElems;
+  if (t < 2) leftBase[(size_t)t * leftBuf + zeroCell] = Cplx<double>{0.0, 0.0};
 #pragma unroll
   for (int gi = 0; gi < kMT_Groups; gi++)
     if (hi == 3) vIdx[gi] = zeroCell;
@@ -244,7 +269,9 @@ __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile
   typedef double vec2 __attribute__((ext_vector_type(2)));
   typedef F vecF __attribute__((ext_vector_type(2)));  // one complex number of the storage type
   vecF stageA[3], stageB[3];
+  vecF stageL[3];  // (TWO) the left vector n_ + 1, fetched one step ahead (a second set of registers for a deeper pipeline spills)
 #define MUGIQ_MT_BODY(n_) static_cast<const Cplx<F> *>(as_constant(a.L)[n_])
+#define MUGIQ_MT_BODYL(n_) (TWO ? static_cast<const Cplx<F> *>(as_constant(a.VL)[n_]) : nullptr)
 #define MUGIQ_MT_SIGMA(n_) as_constant(a.inv_sigma)[n_]
   // this thread's three colours of eigenvector n_ (unconditional for the staging waves: a known number of loads in flight)
 #define MUGIQ_MT_FETCH(bodyExpr_, n_, stage)                                                                           \
@@ -293,6 +320,36 @@ __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile
       }                                                                                                                \
     }                                                                                                                  \
   }
+  // (TWO) this thread's three colours of the left vector at its own site (the offsets of the right one: never a ghost site)
+#define MUGIQ_MT_FETCH_L(bodyExpr_, stage)                                                                             \
+  {                                                                                                                    \
+    if constexpr (TWO) {                                                                                               \
+      if (kRow || commitsL) {                                                                                          \
+        const Cplx<F> *bl_ = (bodyExpr_);                                                                              \
+        if constexpr (ORDER == 2 && kRow) {                                                                            \
+          const char *b_ = reinterpret_cast<const char *>(bl_);                                                        \
+          _Pragma("unroll") for (int c = 0; c < 3; c++) stage[c] = *as_global(reinterpret_cast<const vecF *>(b_ + (int64_t)c * a.stride * (int64_t)sizeof(Cplx<F>) + (uint64_t)sByte)); \
+        } else if constexpr (ORDER == 2) {                                                                             \
+          _Pragma("unroll") for (int c = 0; c < 3; c++) stage[c] = *as_global(reinterpret_cast<const vecF *>(bl_ + soff + (int64_t)c * a.stride)); \
+        } else {                                                                                                       \
+          _Pragma("unroll") for (int c = 0; c < 3; c++) stage[c] = *as_global(reinterpret_cast<const vecF *>(bl_ + offC[c])); \
+        }                                                                                                              \
+      }                                                                                                                \
+    }                                                                                                                  \
+  }
+#define MUGIQ_MT_COMMIT_L(stage, buf_)                                                                                 \
+  {                                                                                                                    \
+    if constexpr (TWO) {                                                                                               \
+      if (commitsL) {                                                                                                  \
+        Cplx<double> *dst_ = (buf_) + wIdxL;                                                                           \
+        _Pragma("unroll") for (int i = 0; i < 3; i++) {                                                                \
+          Cplx<double> r{0.0, 0.0};                                                                                    \
+          _Pragma("unroll") for (int j = 0; j < 3; j++) cmadd(r, g[i * 3 + j], Cplx<double>{(double)stage[j].x, (double)stage[j].y}); \
+          dst_[i * compStride] = r;                                                                                    \
+        }                                                                                                              \
+      }                                                                                                                \
+    }                                                                                                                  \
+  }
 #define MUGIQ_MT_BARRIER()                              \
   {                                                     \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
@@ -300,12 +357,12 @@ __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile
     asm volatile("" ::: "memory");                      \
   }
   // the products of one eigenvector (scaled by s_) on the tile buffer tile_
-#define MUGIQ_MT_COMPUTE(tile_, s_)                                                                                    \
+#define MUGIQ_MT_COMPUTE(tile_, ltile_, s_)                                                                            \
   {                                                                                                                    \
-    const Cplx<double> *tile = tile_;                                                                                  \
+    const Cplx<double> *tile = tile_, *ltile = ltile_;                                                                 \
     const double sc = (s_);                                                                                            \
     _Pragma("unroll") for (int gi = 0; gi < kMT_Groups; gi++) {                                                        \
-      const Cplx<double> v = tile[vIdx[gi]];                                                                           \
+      const Cplx<double> v = ltile[vIdx[gi]];                                                                          \
       const double VR = sc * v.re, VI = sc * v.im;                                                                     \
       _Pragma("unroll") for (int s = 0; s < NS; s++) {                                                                 \
         const Cplx<double> p = tile[pIdx[gi][s]];                                                                      \
@@ -322,27 +379,36 @@ __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile
 #define MUGIQ_MT_STEP(n_, stage, GUARD)                                                                                \
   {                                                                                                                    \
     const double sNow = sigPre;                                                                                        \
-    const Cplx<F> *bodyNow = bodyPre;                                                                                  \
+    const Cplx<F> *bodyNow = bodyPre, *bodyNowL = bodyPreL;                                                            \
     {                                                                                                                  \
       const int nb_ = (n_) + 4 < a.nVec ? (n_) + 4 : a.nVec - 1, ns_ = (n_) + 1 < a.nVec ? (n_) + 1 : a.nVec - 1;      \
       bodyPre = MUGIQ_MT_BODY(nb_);                                                                                    \
+      bodyPreL = MUGIQ_MT_BODYL((n_) + 3 < a.nVec ? (n_) + 3 : a.nVec - 1);                                            \
       sigPre = MUGIQ_MT_SIGMA(ns_);                                                                                    \
     }                                                                                                                  \
     __builtin_amdgcn_sched_barrier(0);                                                                                 \
-    if (GUARD == 0 || (n_) + 1 < a.nVec) MUGIQ_MT_COMMIT(stage, tileBase + (size_t)(((n_) + 1) & 1) * bufElems, (n_) + 1)        \
+    if (GUARD == 0 || (n_) + 1 < a.nVec) {                                                                             \
+      MUGIQ_MT_COMMIT(stage, tileBase + (size_t)(((n_) + 1) & 1) * bufElems, (n_) + 1)                                 \
+      MUGIQ_MT_COMMIT_L(stageL, leftBase + (size_t)(((n_) + 1) & 1) * leftBuf) /* (left n_ + 1, fetched last step) */  \
+    }                                                                                                                  \
+    if (GUARD == 0 || (n_) + 2 < a.nVec) MUGIQ_MT_FETCH_L(bodyNowL, stageL) /* (left: n_ + 2) */                       \
     if (GUARD == 0 || (n_) + 3 < a.nVec) MUGIQ_MT_FETCH(bodyNow, (n_) + 3, stage)                                      \
-    MUGIQ_MT_COMPUTE(tileBase + (size_t)((n_) & 1) * bufElems, sNow)                                                   \
+    MUGIQ_MT_COMPUTE(tileBase + (size_t)((n_) & 1) * bufElems, leftBase + (size_t)((n_) & 1) * leftBuf, sNow)          \
     MUGIQ_MT_BARRIER()                                                                                                 \
   }
   // prologue: eigenvector 0 -> buffer 0; eigenvectors 1 and 2 in flight (clamped, unconditional)
   {
     const int last = a.nVec - 1;
     MUGIQ_MT_FETCH(MUGIQ_MT_BODY(0), 0, stageB)
+    MUGIQ_MT_FETCH_L(MUGIQ_MT_BODYL(0), stageL)
     MUGIQ_MT_COMMIT(stageB, tileBase, 0)
+    MUGIQ_MT_COMMIT_L(stageL, leftBase)
     MUGIQ_MT_FETCH(MUGIQ_MT_BODY((1 < last ? 1 : last)), (1 < last ? 1 : last), stageA)
+    MUGIQ_MT_FETCH_L(MUGIQ_MT_BODYL((1 < last ? 1 : last)), stageL)
     MUGIQ_MT_FETCH(MUGIQ_MT_BODY((2 < last ? 2 : last)), (2 < last ? 2 : last), stageB)
   }
   const Cplx<F> *bodyPre = MUGIQ_MT_BODY(a.nVec > 3 ? 3 : a.nVec - 1);
+  const Cplx<F> *bodyPreL = MUGIQ_MT_BODYL(a.nVec > 2 ? 2 : a.nVec - 1);  // (the left vector fetched by the first step)
   double sigPre = MUGIQ_MT_SIGMA(0);
   MUGIQ_MT_BARRIER()
   int n = 0;
@@ -357,8 +423,11 @@ __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile
 #undef MUGIQ_MT_STEP
 #undef MUGIQ_MT_COMPUTE
 #undef MUGIQ_MT_COMMIT
+#undef MUGIQ_MT_COMMIT_L
 #undef MUGIQ_MT_FETCH
+#undef MUGIQ_MT_FETCH_L
 #undef MUGIQ_MT_BODY
+#undef MUGIQ_MT_BODYL
 #undef MUGIQ_MT_SIGMA
 
   // ---- epilogue: lane 16 be + 4 b + al holds element (be, al) of the spin matrix of site b.  Slot by slot through LDS (the
@@ -431,12 +500,18 @@ __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile
 #undef MUGIQ_MFMA_NEGA
 
 // F, ORDER: the eigenvectors' storage.  FULL: every tile geometry and the face-layer packing (fp64 FLOAT2); else the 16-line column tiles
-// and the 8-wave row tile only (a sixth of the instances per storage type).
-template <typename F, int ORDER, bool FULL>
+// and the 8-wave row tile only (a sixth of the instances per storage type).  TWO: the two-sided tile (a.VL = the left set; no 12-position
+// column tile -- its two images would not fit the LDS of a workgroup -- and no face layers)
+template <typename F, int ORDER, bool FULL, bool TWO = false>
 inline int launch_mfma_tile_t(MTileArgs a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream) {
   const int ln = tj == 4 ? 32 : 16;
   const size_t bufElems = dir == 0 && rowWaves == 8 ? kMT_BufElems / 2 : kMT_BufElems;
-  const size_t shmem = std::max(2 * bufElems, (size_t)16 * (dir == 0 ? 4 * rowGroups * rowWaves : tj * ln)) * sizeof(Cplx<double>);
+  const size_t imageElems = 2 * bufElems + (TWO ? 2 * (size_t)a.leftBufElems : 0);
+  const size_t shmem = std::max(imageElems, (size_t)16 * (dir == 0 ? 4 * rowGroups * rowWaves : tj * ln)) * sizeof(Cplx<double>);
+  if (TWO) {
+    MUGIQ_REQUIRE(a.VL != nullptr && a.nPack == 0 && (dir == 0 || tj != 12) && (dir != 0 || (rowWaves == 8 && (FULL || rowGroups == 2))) && ns <= mt_two_max_slots(dir, FULL) && shmem <= kMT_MaxLds,
+                  "mfma tile: two-sided geometry %d / %d waves / %d slots / %d pack targets / %zu bytes of LDS not built (internal)", tj, rowWaves, ns, a.nPack, shmem);
+  }
   const unsigned nblocks = dir == 0 ? (unsigned)(a.numCols / a.rowsPerTile) : (unsigned)(((a.numCols + ln - 1) / ln) * a.jtCount);
   a.blockOrder = 2;
   if (const char *e = getenv("MUGIQ_HIP_TILE_ORDER")) a.blockOrder = atoi(e) & 2;
@@ -448,29 +523,29 @@ inline int launch_mfma_tile_t(MTileArgs a, int dir, int sign, int ns, int tj, in
 #define MUGIQ_MT_ROW(S, N)                                                                                             \
   {                                                                                                                    \
     if (rowWaves == 8) {                                                                                               \
-      if (rowGroups == 3) MUGIQ_MT_LAUNCH_P(0, S, N, 8, 48) else MUGIQ_MT_LAUNCH_P(0, S, N, 8, 32)                     \
-    } else if constexpr (FULL) {                                                                                       \
+      if (rowGroups == 3) { if constexpr (!TWO || FULL) MUGIQ_MT_LAUNCH_P(0, S, N, 8, 48) } else MUGIQ_MT_LAUNCH_P(0, S, N, 8, 32) \
+    } else if constexpr (FULL && !TWO) {                                                                               \
       if (rowGroups == 3) MUGIQ_MT_LAUNCH_P(0, S, N, 16, 48) else MUGIQ_MT_LAUNCH_P(0, S, N, 16, 32)                   \
     }                                                                                                                  \
   }
 #define MUGIQ_MT_ROWCASE(S)                                                                                            \
   case (S):                                                                                                            \
-    if (ns == 1) MUGIQ_MT_ROW(S, 1) else if (ns == 2) MUGIQ_MT_ROW(S, 2) else MUGIQ_MT_ROW(S, 3)                       \
+    if (ns == 1) MUGIQ_MT_ROW(S, 1) else if (ns == 2) MUGIQ_MT_ROW(S, 2) else if constexpr (!TWO) MUGIQ_MT_ROW(S, 3)   \
     break;
 #define MUGIQ_MT_LAUNCH(D, S, N)                                                                                       \
   {                                                                                                                    \
-    if (tj == 12) MUGIQ_MT_LAUNCH_(D, S, N, 12, 16) else if (tj == 8) MUGIQ_MT_LAUNCH_(D, S, N, 8, 16) else if constexpr (FULL) MUGIQ_MT_LAUNCH_(D, S, N, 4, 32) \
+    if (tj == 8) MUGIQ_MT_LAUNCH_(D, S, N, 8, 16) else if (tj == 12) { if constexpr (!TWO) MUGIQ_MT_LAUNCH_(D, S, N, 12, 16) } else if constexpr (FULL) MUGIQ_MT_LAUNCH_(D, S, N, 4, 32) \
   }
 #define MUGIQ_MT_LAUNCH_(D, S, N, T, LL)                                                                               \
   {                                                                                                                    \
-    auto kern = mfma_tile_displaced_contract_kernel<D, S, N, T, LL, false, F, ORDER>;                                  \
+    auto kern = mfma_tile_displaced_contract_kernel<D, S, N, T, LL, false, F, ORDER, TWO>;                             \
     MUGIQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
     hipLaunchKernelGGL(kern, grid, block, shmem, stream, a);                                                           \
   }
 #define MUGIQ_MT_LAUNCH_P(D, S, N, T, LL)                                                                              \
   {                                                                                                                    \
-    auto kern = mfma_tile_displaced_contract_kernel<D, S, N, T, LL, false, F, ORDER>;                                  \
-    if constexpr (FULL) {                                                                                              \
+    auto kern = mfma_tile_displaced_contract_kernel<D, S, N, T, LL, false, F, ORDER, TWO>;                             \
+    if constexpr (FULL && !TWO) {                                                                                      \
       if (a.nPack > 0) kern = mfma_tile_displaced_contract_kernel<D, S, N, T, LL, FULL, F, ORDER>;                     \
     }                                                                                                                  \
     MUGIQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
@@ -478,7 +553,7 @@ inline int launch_mfma_tile_t(MTileArgs a, int dir, int sign, int ns, int tj, in
   }
 #define MUGIQ_MT_CASE(D, S)                                                                                            \
   case (D)*2 + (S):                                                                                                    \
-    if (ns == 1) MUGIQ_MT_LAUNCH(D, S, 1) else if (ns == 2) MUGIQ_MT_LAUNCH(D, S, 2) else if (ns == 3) MUGIQ_MT_LAUNCH(D, S, 3) else MUGIQ_MT_LAUNCH(D, S, 4) \
+    if (ns == 1) MUGIQ_MT_LAUNCH(D, S, 1) else if (ns == 2) MUGIQ_MT_LAUNCH(D, S, 2) else if (ns == 3) { if constexpr (!TWO || FULL) MUGIQ_MT_LAUNCH(D, S, 3) } else if constexpr (!TWO) MUGIQ_MT_LAUNCH(D, S, 4) \
     break;
   switch (dir * 2 + sign) {
     MUGIQ_MT_ROWCASE(0) MUGIQ_MT_ROWCASE(1)
@@ -500,5 +575,10 @@ inline int launch_mfma_tile_t(MTileArgs a, int dir, int sign, int ns, int tj, in
 int launch_mfma_tile_d4(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
 int launch_mfma_tile_f2(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
 int launch_mfma_tile_f4(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
+// the two-sided tiles, one translation unit per storage type (fused_mfma_two.hip: fp64 FLOAT2; fused_mfma_two_d4 / _f2 / _f4.hip)
+int launch_mfma_tile_two_d2(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
+int launch_mfma_tile_two_d4(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
+int launch_mfma_tile_two_f2(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
+int launch_mfma_tile_two_f4(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
 
 }  // namespace mugiq

@@ -1,0 +1,8 @@
+// The two-sided matrix-pipe tile (csrc/fused_mfma_kernel.h, TWO) for fp64 FLOAT4 eigenvectors: 8 x 16 column tiles, 8-wave row tile.
+#include "fused_mfma_kernel.h"
+
+namespace mugiq {
+int launch_mfma_tile_two_d4(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream) {
+  return launch_mfma_tile_t<double, 4, false, true>(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
+}
+}  // namespace mugiq

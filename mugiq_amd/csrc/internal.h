@@ -64,6 +64,19 @@ struct EntryPackTarget {
   int layers;
   int fromVec;  // eigenvectors fromVec .. nVec - 1 (the ones before went out packed by mugiq_hip_pack_face_layers)
 };
+// The matrix-pipe tile (fourth generation, any storage type, ascending lengths up to 8).  two: the two-sided tile (left set evL != NULL
+// in mfma_tile_entry; no 12-position column tile, 8-wave row tile only)
+bool mfma_tile_applicable(const MugiqHipSpinorField &ev, int dir, const int *kvals, int nK, int partitioned, bool gaugeGiven, bool two = false);
+int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
+                    const int *kvals, int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers, int region,
+                    hipStream_t stream, void *ultra_d, int *carried, const MugiqHipSpinorField *evL = nullptr);
+// csrc/fused.hip: what mugiq_hip_displaced_loop_contraction_fused_carry (eVecL_h = NULL) and ..._fused_two_sided do, and which kernel
+// did it (*kernel = MUGIQ_HIP_ENTRY_KERNEL_*; may be NULL).  The two-sided form runs on the matrix-pipe tile only: where that does not
+// apply it fails with MUGIQ_HIP_ERROR_UNSUPPORTED (the driver checks mfma_tile_applicable first and takes the step-by-step sequence)
+int fused_contraction(void *loopData_d, int loopPrecision, const MugiqHipSpinorField *eVecL_h, const MugiqHipSpinorField *eVecR_h,
+                      const double *sigma_h, int nVec, const void *const *pathLinkFields_h, const int *kValues_h, int nK, int dispDir,
+                      int dispSign, const int commDim[4], const void *ghostLayers_d, int layers, int region, void *ultraLocalSlot_d,
+                      int *carried, void *stream, int *kernel);
 int entry_pack_capacity(const MugiqHipSpinorField &ev, const int *kvals, int nK);
 void set_entry_pack_hint(const EntryPackTarget *targets, int n);  // (NULL, 0) clears it
 bool entry_pack_taken();

@@ -51,12 +51,17 @@ struct MugiqHipLoop_s {
   std::vector<std::string> dispEntry, dispString;
   std::vector<int> dispStart, dispStop, nLoopPerEntry, nLoopOffset, dispDir, dispSign;
   std::vector<int> derivedFrom;  // per entry: the entry it was reflected from in the last compute, or -1
+  std::vector<int> entryKernel;  // per entry: MUGIQ_HIP_ENTRY_KERNEL_* of the last compute, or -1
   int nDispEntries = 0, nLoop = 0, nData = 0;
   std::string fnameMom, fnamePos;
   bool writeMom = false, writePos = false;
   // ---- inputs
   std::vector<MugiqHipSpinorField> eVecs;
   std::vector<double> sigma;
+  // two-sided loops (mugiq_hip_loop_create_two_sided): eVecs is the right (displaced) set, eVecsL the left one; no reflected entries
+  bool twoSided = false;
+  std::vector<MugiqHipSpinorField> eVecsL;
+  const MugiqHipSpinorField *left() const { return twoSided ? eVecsL.data() : eVecs.data(); }
   int nEv = 0, precision = 8, order = 2;
   int loopPrecision = 8;  // precision of the loop buffers / FT (= precision, or 8 over fp32 fields: mixed mode)
   MugiqHipGaugeField gauge;
@@ -251,6 +256,7 @@ static int entry_basic(MugiqHipLoop *lp, int id, void *slot0) {
     if ((st = scratch_alloc(lp, &recv_d, fb, false))) return st;
   }
   const size_t slotBytes = (size_t)lp->nElemPosLocPerLoop * lp->loopBytes();
+  lp->entryKernel[id] = MUGIQ_HIP_ENTRY_KERNEL_STEPWISE;
   for (int n = 0; n < lp->nEv; n++) {  // lib/loop_mugiq.cpp:478
     MugiqHipSpinorField cur = lp->eVecs[n];
     int dispCount = 0;
@@ -262,7 +268,7 @@ static int entry_basic(MugiqHipLoop *lp, int id, void *slot0) {
       cur = *dst;
       if (idisp >= lp->dispStart[id] && idisp <= lp->dispStop[id]) {  // :491-496
         void *slot = static_cast<char *>(slot0) + slotBytes * dispCount;
-        if ((st = mugiq_hip_perform_loop_contraction_batched_mixed(slot, lp->loopPrecision, &lp->eVecs[n], &cur, &lp->sigma[n], 1,
+        if ((st = mugiq_hip_perform_loop_contraction_batched_mixed(slot, lp->loopPrecision, lp->left() + n, &cur, &lp->sigma[n], 1,
                                                                    lp->stream)))
           return st;
         dispCount++;
@@ -298,6 +304,7 @@ static int entry_stepwise_blocked(MugiqHipLoop *lp, int id, void *slot0) {
   const size_t slotBytes = (size_t)lp->nElemPosLocPerLoop * lp->loopBytes();
   const int high = (sign == MUGIQ_HIP_DISP_SIGN_PLUS) ? 0 : 1;  // sign +: my LOW face feeds the backward neighbour
   std::vector<MugiqHipSpinorField> cur(nb);
+  lp->entryKernel[id] = MUGIQ_HIP_ENTRY_KERNEL_STEPWISE;
   for (int n0 = 0; n0 < lp->nEv; n0 += nb) {
     const int nv = std::min(nb, lp->nEv - n0);
     for (int i = 0; i < nv; i++) cur[i] = lp->eVecs[n0 + i];
@@ -315,7 +322,7 @@ static int entry_stepwise_blocked(MugiqHipLoop *lp, int id, void *slot0) {
       }
       if (idisp >= start) {
         void *slot = static_cast<char *>(slot0) + slotBytes * (size_t)(idisp - start);
-        if ((st = mugiq_hip_perform_loop_contraction_batched_mixed(slot, lp->loopPrecision, &lp->eVecs[n0], cur.data(), &lp->sigma[n0], nv,
+        if ((st = mugiq_hip_perform_loop_contraction_batched_mixed(slot, lp->loopPrecision, lp->left() + n0, cur.data(), &lp->sigma[n0], nv,
                                                                    lp->stream)))
           return st;
       }
@@ -354,6 +361,19 @@ static size_t halo_bytes(const MugiqHipLoop *lp, int id) {
 
 static int reflection_source(const MugiqHipLoop *lp, int id);
 
+// Does the OPT plan take entry `id` step by step (entry_stepwise_blocked)?  A length past the nearest neighbour of a partitioned
+// direction; for two-sided loops also every entry the two-sided matrix-pipe tile does not take (lengths > 8, a partitioned x axis, no
+// tile geometry).  (The driver builds the axial gauge itself where the lengths do not start at 1: gaugeGiven.)
+static bool entry_stepwise(const MugiqHipLoop *lp, int id) {
+  const int dir = lp->dispDir[id];
+  const bool part = lp->commDim[dir] != 0;
+  if (part && lp->dispStop[id] > lp->localL[dir]) return true;
+  if (!lp->twoSided) return false;
+  std::vector<int> kv;
+  for (int k = lp->dispStart[id]; k <= lp->dispStop[id]; k++) kv.push_back(k);
+  return !mfma_tile_applicable(lp->eVecs[0], dir, kv.data(), (int)kv.size(), part ? 1 : 0, true, true);
+}
+
 // The OPT plan: which entries are reflected from which (derivedFrom), and which of the computed entries along partitioned axes
 // get their eigenvector halo posted AHEAD, at the start of the compute (ahead[id] = 1).  The ghost-layer buffers posted ahead
 // may take a quarter of the device memory.  The rule must not depend on anything that can differ between ranks (such as the
@@ -371,7 +391,7 @@ static int plan_opt(MugiqHipLoop *lp, std::vector<char> &ahead) {
     if (atoi(e) == 0) budget = 0;
   for (int id = 0; id < lp->nDispEntries; id++) {
     const int dir = lp->dispDir[id];
-    if (lp->derivedFrom[id] >= 0 || !lp->commDim[dir] || lp->dispStop[id] > lp->localL[dir]) continue;
+    if (lp->derivedFrom[id] >= 0 || !lp->commDim[dir] || entry_stepwise(lp, id)) continue;
     const size_t bytes = halo_bytes(lp, id);
     if (2 * bytes > budget) continue;  // this entry exchanges eigenvector blocks of <= 4 GiB inside its own turn instead
     budget -= 2 * bytes;
@@ -577,7 +597,17 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) 
   int st;
   // a displacement longer than the local extent of a partitioned dimension reaches past the nearest neighbour: the
   // multi-layer halo cannot serve it, the step-by-step sequence (one face per step) can
-  if (part && stop > lp->localL[dir]) return entry_stepwise_blocked(lp, id, slot0);
+  if (entry_stepwise(lp, id)) return entry_stepwise_blocked(lp, id, slot0);
+  const MugiqHipSpinorField *evL = lp->twoSided ? lp->eVecsL.data() : nullptr;  // (two-sided: the left set of the tile)
+  int kernel = -1;
+  struct KernelRecord {  // what produced the entry, on every way out
+    MugiqHipLoop *lp;
+    int id;
+    int *k;
+    ~KernelRecord() {
+      if (*k >= 0) lp->entryKernel[id] = *k;
+    }
+  } kernelRecord{lp, id, &kernel};
   std::vector<MugiqHipSpinorField> Elocal;
   const bool ahead = part && lp->halo[id].posted;
   std::vector<int> kv;
@@ -612,9 +642,9 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) 
     int ph;
     if (part_sel != 2) {
       ph = phase_begin(lp, MUGIQ_HIP_PHASE_ENTRY_INTERIOR, id, lp->stream);
-      if ((st = mugiq_hip_displaced_loop_contraction_fused_region(slot0, lp->loopPrecision, lp->eVecs.data(), lp->sigma.data(), lp->nEv,
-                                                                  links.data(), kv.data(), (int)kv.size(), dir, sign, lp->commDim,
-                                                                  h.grecv, stop, MUGIQ_HIP_REGION_INTERIOR | MUGIQ_HIP_REGION_OVERWRITE, lp->stream)))
+      if ((st = fused_contraction(slot0, lp->loopPrecision, evL, lp->eVecs.data(), lp->sigma.data(), lp->nEv, links.data(), kv.data(),
+                                  (int)kv.size(), dir, sign, lp->commDim, h.grecv, stop, MUGIQ_HIP_REGION_INTERIOR | MUGIQ_HIP_REGION_OVERWRITE,
+                                  nullptr, nullptr, lp->stream, &kernel)))
         return st;
       phase_end(lp, ph, lp->stream);
     }
@@ -627,9 +657,9 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) 
       MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->stream, h.evBlock[b], 0));
       phase_end(lp, ph, lp->stream);
       ph = phase_begin(lp, MUGIQ_HIP_PHASE_ENTRY_BOUNDARY, id, lp->stream);
-      st = mugiq_hip_displaced_loop_contraction_fused_region(slot0, lp->loopPrecision, &lp->eVecs[n0], &lp->sigma[n0], nv, links.data(), kv.data(),
-                                                             (int)kv.size(), dir, sign, lp->commDim, static_cast<char *>(h.grecv) + perVec * n0, stop,
-                                                             MUGIQ_HIP_REGION_BOUNDARY | (b == 0 ? MUGIQ_HIP_REGION_OVERWRITE : 0), lp->stream);
+      st = fused_contraction(slot0, lp->loopPrecision, evL ? evL + n0 : nullptr, &lp->eVecs[n0], &lp->sigma[n0], nv, links.data(), kv.data(),
+                             (int)kv.size(), dir, sign, lp->commDim, static_cast<char *>(h.grecv) + perVec * n0, stop,
+                             MUGIQ_HIP_REGION_BOUNDARY | (b == 0 ? MUGIQ_HIP_REGION_OVERWRITE : 0), nullptr, nullptr, lp->stream, &kernel);
       phase_end(lp, ph, lp->stream);
       if (st) return st;
     }
@@ -679,9 +709,9 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) 
       // (one block here: nb = nEv.)  The first such entry also takes the ultra-local loop along, if the kernel has room
       int carried = 0;
       void *ultra = (lp->carryUltra && !lp->ultraCarried && nb == lp->nEv) ? lp->dataPos_d : nullptr;
-      if ((st = mugiq_hip_displaced_loop_contraction_fused_carry(slot0, lp->loopPrecision, &lp->eVecs[n0], &lp->sigma[n0], nv,
-                                                                 links.data(), kv.data(), (int)kv.size(), dir, sign, lp->commDim,
-                                                                 nullptr, 0, MUGIQ_HIP_REGION_ALL | ow, ultra, &carried, lp->stream)))
+      if ((st = fused_contraction(slot0, lp->loopPrecision, evL ? evL + n0 : nullptr, &lp->eVecs[n0], &lp->sigma[n0], nv, links.data(),
+                                  kv.data(), (int)kv.size(), dir, sign, lp->commDim, nullptr, 0, MUGIQ_HIP_REGION_ALL | ow, ultra, &carried,
+                                  lp->stream, &kernel)))
         return st;
       if (carried) {
         lp->ultraCarried = true;
@@ -702,18 +732,18 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) 
     phase_end(lp, ph, lp->commStream);
     MUGIQ_CHECK_HIP(hipEventRecord(lp->evHalo, lp->commStream));
     ph = phase_begin(lp, MUGIQ_HIP_PHASE_ENTRY_INTERIOR, id, lp->stream);
-    if ((st = mugiq_hip_displaced_loop_contraction_fused_region(slot0, lp->loopPrecision, &lp->eVecs[n0], &lp->sigma[n0], nv,
-                                                                links.data(), kv.data(), (int)kv.size(), dir, sign, lp->commDim,
-                                                                grecv, stop, MUGIQ_HIP_REGION_INTERIOR | ow, lp->stream)))
+    if ((st = fused_contraction(slot0, lp->loopPrecision, evL ? evL + n0 : nullptr, &lp->eVecs[n0], &lp->sigma[n0], nv, links.data(),
+                                kv.data(), (int)kv.size(), dir, sign, lp->commDim, grecv, stop, MUGIQ_HIP_REGION_INTERIOR | ow, nullptr, nullptr,
+                                lp->stream, &kernel)))
       return st;
     phase_end(lp, ph, lp->stream);
     ph = phase_begin(lp, MUGIQ_HIP_PHASE_HALO_WAIT, id, lp->stream);
     MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->stream, lp->evHalo, 0));
     phase_end(lp, ph, lp->stream);
     ph = phase_begin(lp, MUGIQ_HIP_PHASE_ENTRY_BOUNDARY, id, lp->stream);
-    if ((st = mugiq_hip_displaced_loop_contraction_fused_region(slot0, lp->loopPrecision, &lp->eVecs[n0], &lp->sigma[n0], nv,
-                                                                links.data(), kv.data(), (int)kv.size(), dir, sign, lp->commDim,
-                                                                grecv, stop, MUGIQ_HIP_REGION_BOUNDARY | ow, lp->stream)))
+    if ((st = fused_contraction(slot0, lp->loopPrecision, evL ? evL + n0 : nullptr, &lp->eVecs[n0], &lp->sigma[n0], nv, links.data(),
+                                kv.data(), (int)kv.size(), dir, sign, lp->commDim, grecv, stop, MUGIQ_HIP_REGION_BOUNDARY | ow, nullptr, nullptr,
+                                lp->stream, &kernel)))
       return st;
     phase_end(lp, ph, lp->stream);
   }
@@ -723,6 +753,7 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) 
 // Reflected entries (csrc/reflect.hip): entry `id` can be derived from an entry `jd` computed earlier in this run if jd
 // has the same direction, the opposite sign and covers id's lengths.  Returns the source entry or -1.
 static int reflection_source(const MugiqHipLoop *lp, int id) {
+  if (lp->twoSided) return -1;  // (L^-(x) = eta conj L^+(x - k mu) rests on the left and right vectors being the same)
   if (const char *e = getenv("MUGIQ_HIP_REFLECT"))
     if (atoi(e) == 0) return -1;
   // a length that reaches past the nearest neighbour cannot be served by one halo of the source slot
@@ -741,6 +772,7 @@ static int entry_reflected(MugiqHipLoop *lp, int id, int jd, void *slot0) {
   const char *src0 = static_cast<const char *>(lp->dataPos_d) + slotBytes * (size_t)lp->nLoopOffset[jd];
   const int faceCB = lp->volumeCB / lp->localL[dir];
   int st;
+  lp->entryKernel[id] = MUGIQ_HIP_ENTRY_KERNEL_REFLECTED;
   // a length that reaches past the nearest neighbour cannot be served by one halo: nothing is written, the caller
   // computes the entry from the eigenvectors
   if (part && lp->dispStop[id] > lp->localL[dir]) return -1;
@@ -962,17 +994,22 @@ int mugiq_hip_parse_displace_entry_string(const char *entry_string, int max_entr
   return n;
 }
 
-int mugiq_hip_loop_create(MugiqHipLoop **out, const MugiqHipLoopParam *p, const MugiqHipSpinorField *eVecs_h,
-                          const double *eVals_sigma_h, int nEv, const MugiqHipComm *comm, void *stream) {
-  const char *who = "Loop_Mugiq";
+// eVecsL_h != NULL: a two-sided loop (mugiq_hip_loop_create_two_sided), eVecs_h the right set
+static int loop_create(MugiqHipLoop **out, const MugiqHipLoopParam *p, const MugiqHipSpinorField *eVecs_h, const double *eVals_sigma_h, int nEv,
+                       const MugiqHipComm *comm, void *stream, const MugiqHipSpinorField *eVecsL_h) {
+  const char *who = eVecsL_h ? "Loop_Mugiq(two-sided)" : "Loop_Mugiq";
   MUGIQ_REQUIRE(out && p && eVecs_h && eVals_sigma_h, "%s: NULL argument", who);
   MUGIQ_REQUIRE(nEv >= 1, "%s: nEv = %d must be >= 1", who, nEv);
   *out = nullptr;
   int st;
   for (int n = 0; n < nEv; n++) {
-    if ((st = validate_spinor(&eVecs_h[n], who, "eVecs"))) return st;
+    if ((st = validate_spinor(&eVecs_h[n], who, eVecsL_h ? "eVecsR" : "eVecs"))) return st;
     MUGIQ_REQUIRE(same_geometry(eVecs_h[n], eVecs_h[0]), "%s: eigenvector %d differs in precision, order or geometry from eVecs[0]", who, n);
     MUGIQ_REQUIRE(eVals_sigma_h[n] != 0.0, "%s: eVals_sigma[%d] is zero", who, n);
+    if (eVecsL_h) {
+      if ((st = validate_spinor(&eVecsL_h[n], who, "eVecsL"))) return st;
+      MUGIQ_REQUIRE(same_geometry(eVecsL_h[n], eVecs_h[0]), "%s: left vector %d differs in precision, order or geometry from the right vectors", who, n);
+    }
   }
   MugiqHipLoop *lp = new MugiqHipLoop_s();
   auto fail = [&](int code) {
@@ -981,6 +1018,10 @@ int mugiq_hip_loop_create(MugiqHipLoop **out, const MugiqHipLoopParam *p, const 
   };
   lp->stream = static_cast<hipStream_t>(stream);
   lp->eVecs.assign(eVecs_h, eVecs_h + nEv);
+  if (eVecsL_h) {
+    lp->twoSided = true;
+    lp->eVecsL.assign(eVecsL_h, eVecsL_h + nEv);
+  }
   lp->sigma.assign(eVals_sigma_h, eVals_sigma_h + nEv);
   lp->nEv = nEv;
   lp->precision = eVecs_h[0].precision;
@@ -1067,6 +1108,7 @@ int mugiq_hip_loop_create(MugiqHipLoop **out, const MugiqHipLoopParam *p, const 
       lp->dispDir.push_back(dir);
       lp->dispSign.push_back(sign);
       lp->derivedFrom.push_back(-1);
+      lp->entryKernel.push_back(-1);
     }
     lp->nLoop += 1;  // Don't forget ultra-local case!!
     if (lp->nDispEntries > 0) {
@@ -1134,6 +1176,17 @@ int mugiq_hip_loop_create(MugiqHipLoop **out, const MugiqHipLoopParam *p, const 
   if (lp->haveGauge && (st = reserve_plan_buffers(lp))) return fail(st);
   *out = lp;
   return MUGIQ_HIP_SUCCESS;
+}
+
+int mugiq_hip_loop_create(MugiqHipLoop **out, const MugiqHipLoopParam *p, const MugiqHipSpinorField *eVecs_h,
+                          const double *eVals_sigma_h, int nEv, const MugiqHipComm *comm, void *stream) {
+  return loop_create(out, p, eVecs_h, eVals_sigma_h, nEv, comm, stream, nullptr);
+}
+
+int mugiq_hip_loop_create_two_sided(MugiqHipLoop **out, const MugiqHipLoopParam *p, const MugiqHipSpinorField *eVecsL_h,
+                                    const MugiqHipSpinorField *eVecsR_h, const double *sigma_h, int n, const MugiqHipComm *comm, void *stream) {
+  MUGIQ_REQUIRE(eVecsL_h && eVecsR_h, "Loop_Mugiq(two-sided): NULL argument");
+  return loop_create(out, p, eVecsR_h, sigma_h, n, comm, stream, eVecsL_h);
 }
 
 // Loop_Mugiq with eigsolve->useMGenv && eigsolve->computeCoarse (lib/loop_mugiq.cpp:42,482): the eigenvectors live on
@@ -1242,6 +1295,7 @@ int mugiq_hip_loop_compute(MugiqHipLoop *lp) {
   lp->eventsUsed = 0;
   lp->carryUltra = lp->ultraCarried = false;
   lp->ultraCarrier = -1;
+  std::fill(lp->entryKernel.begin(), lp->entryKernel.end(), -1);
   const auto tWall0 = std::chrono::steady_clock::now();
   if (lp->coarseMode && lp->levelVecs.size() > 1) {
     // coarsest level -> level 1 through the upper transfer operators (lib/loop_mugiq.cpp:306-311), all eigenvectors per launch
@@ -1342,6 +1396,7 @@ int mugiq_hip_loop_compute(MugiqHipLoop *lp) {
     if (id == -1 && !basic && lp->carryUltra && lp->ultraCarried) return MUGIQ_HIP_SUCCESS;  // produced by a displaced entry's pass
     if (id >= 0 && !basic && lp->momReflect && lp->derivedFrom[id] >= 0) {   // derived in momentum space; position space on request
       lp->posReflectPending = true;
+      lp->entryKernel[id] = MUGIQ_HIP_ENTRY_KERNEL_REFLECTED;
       return MUGIQ_HIP_SUCCESS;
     }
     long long bufOffset;
@@ -1357,7 +1412,7 @@ int mugiq_hip_loop_compute(MugiqHipLoop *lp) {
     // cudaMemset :476 -- needed where kernels accumulate into the slots: the ultra-local loop, the BASIC plan, and an OPT
     // entry that falls back to the step-by-step sequence (length beyond the neighbour).  Reflected entries and the fused
     // displaced contraction write every site of their slots (MUGIQ_HIP_REGION_OVERWRITE).
-    const bool stepByStep = id >= 0 && lp->commDim[lp->dispDir[id]] && lp->dispStop[id] > lp->localL[lp->dispDir[id]];
+    const bool stepByStep = id >= 0 && entry_stepwise(lp, id);
     if (id == -1 || basic || (lp->derivedFrom[id] < 0 && stepByStep)) MUGIQ_CHECK_HIP(hipMemsetAsync(slot0, 0, bufByteSize, lp->stream));
     const bool reflected = id >= 0 && !basic && lp->derivedFrom[id] >= 0;
     const bool split = id >= 0 && !basic && !reflected && !stepByStep && lp->commDim[lp->dispDir[id]];  // entry_fused opens its own phases
@@ -1373,10 +1428,10 @@ int mugiq_hip_loop_compute(MugiqHipLoop *lp) {
     } else if (id == -1) {
       if (basic) {
         for (int n = 0; n < lp->nEv && !st; n++)  // :501-502
-          st = mugiq_hip_perform_loop_contraction_batched_mixed(slot0, lp->loopPrecision, &lp->eVecs[n], &lp->eVecs[n], &lp->sigma[n], 1,
+          st = mugiq_hip_perform_loop_contraction_batched_mixed(slot0, lp->loopPrecision, lp->left() + n, &lp->eVecs[n], &lp->sigma[n], 1,
                                                                 lp->stream);
       } else {
-        st = mugiq_hip_perform_loop_contraction_batched_mixed(slot0, lp->loopPrecision, lp->eVecs.data(), lp->eVecs.data(),
+        st = mugiq_hip_perform_loop_contraction_batched_mixed(slot0, lp->loopPrecision, lp->left(), lp->eVecs.data(),
                                                               lp->sigma.data(), lp->nEv, lp->stream);
       }
     } else {
@@ -1435,7 +1490,7 @@ int mugiq_hip_loop_compute(MugiqHipLoop *lp) {
   // MUGIQ_HIP_PACK_IN_ENTRY = 0: pack kernels for everything.
   std::vector<EntryPackTarget> packTargets;
   lp->halosPackedInEntry = 0;
-  if (postHalos && earlyEntry >= 0 && lp->dispDir[earlyEntry] == 0 && lp->loopPrecision == lp->precision) {
+  if (postHalos && earlyEntry >= 0 && lp->dispDir[earlyEntry] == 0 && lp->loopPrecision == lp->precision && !lp->twoSided) {  // (two-sided: pack kernels)
     std::vector<int> kv;
     for (int k = lp->dispStart[earlyEntry]; k <= lp->dispStop[earlyEntry]; k++) kv.push_back(k);
     const int room = entry_pack_capacity(lp->eVecs[0], kv.data(), (int)kv.size());
@@ -1573,6 +1628,11 @@ int mugiq_hip_loop_get_entry(const MugiqHipLoop *lp, int id, int out6[6]) {
 int mugiq_hip_loop_ultra_local_carrier(const MugiqHipLoop *lp) { return (lp && lp->computed) ? lp->ultraCarrier : -1; }
 
 int mugiq_hip_loop_halos_packed_in_entry(const MugiqHipLoop *lp) { return (lp && lp->computed) ? lp->halosPackedInEntry : -1; }
+
+int mugiq_hip_loop_get_entry_kernel(const MugiqHipLoop *lp, int id) {
+  if (!lp || !lp->computed || id < 0 || id >= lp->nDispEntries) return -1;
+  return lp->entryKernel[id];
+}
 
 int mugiq_hip_loop_entry_derived_from(const MugiqHipLoop *lp, int id) {
   if (!lp || id < 0 || id >= lp->nDispEntries) return -2;

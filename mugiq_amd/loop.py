@@ -9,7 +9,7 @@ import torch
 
 from . import _lib
 from .comm import device_bytes
-from .fields import GaugeField, desc_array, coarse_desc_array, transfer_desc_array
+from .fields import GaugeField, SpinorField, desc_array, coarse_desc_array, transfer_desc_array
 
 LOOP_CALC_TYPE_BLAS, LOOP_CALC_TYPE_OPT_KERNEL, LOOP_CALC_TYPE_BASIC_KERNEL = 0, 1, 2   # include/enum_mugiq.h:35-41
 
@@ -132,9 +132,19 @@ class Loop_Mugiq:
     """Loop_Mugiq<Float, order>(loopParams, eigsolve): Float/order come from the eigenvector fields;
     `eVecs` / `eVals_sigma` are what the reference reads out of Eigsolve_Mugiq (lib/loop_mugiq.cpp:442,479)."""
 
-    def __init__(self, loopParams, eVecs, eVals_sigma, comm=None, transfer=None):
+    def __init__(self, loopParams, eVecs, eVals_sigma, comm=None, transfer=None, eVecsLeft=None):
         """`transfer` given: eVecs are CoarseField eigenvectors (eigsolve->computeCoarse) prolonged with it; a list
-        [finest, level 1 -> 2, ...] for an MG hierarchy with several coarse levels (eVecs on the coarsest one)."""
+        [finest, level 1 -> 2, ...] for an MG hierarchy with several coarse levels (eVecs on the coarsest one).
+        `eVecsLeft` given: a two-sided loop sum_r (1/sigma_r) vL_r^dag G [D^k vR_r] (mugiq_hip_loop_create_two_sided) with the left
+        vectors eVecsLeft and the right (displaced) vectors eVecs, fine-level SpinorFields of one geometry, precision and order;
+        eVals_sigma are the sigma_r (the stochastic remainder with eVecs = phi_r, eVecsLeft = g5 xi_r)."""
+        if eVecsLeft is not None:
+            if transfer is not None:
+                raise _lib.MugiqHipError("Loop_Mugiq(two-sided): coarse (MG) vectors and transfers are not supported, fine-level vectors only")
+            if not all(isinstance(v, SpinorField) for v in list(eVecs) + list(eVecsLeft)):
+                raise _lib.MugiqHipError("Loop_Mugiq(two-sided): both vector sets must be fine-level SpinorFields")
+            if len(eVecsLeft) != len(eVecs):
+                raise _lib.MugiqHipError("Loop_Mugiq(two-sided): %d left and %d right vectors" % (len(eVecsLeft), len(eVecs)))
         lib = _lib.load()
         self._keep = []
         self._params, self._transfer = loopParams, transfer
@@ -173,7 +183,12 @@ class Loop_Mugiq:
         c = comm.c_struct() if comm is not None else None
         self._handle = ctypes.c_void_p()
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if transfer is None:
+        self.eVecsLeft = list(eVecsLeft) if eVecsLeft is not None else None
+        if eVecsLeft is not None:
+            _lib.check(lib.mugiq_hip_loop_create_two_sided(ctypes.byref(self._handle), ctypes.byref(p), desc_array(self.eVecsLeft),
+                                                           desc_array(self.eVecs), sg, len(self.eVecs),
+                                                           ctypes.byref(c) if c is not None else None, stream))
+        elif transfer is None:
             _lib.check(lib.mugiq_hip_loop_create(ctypes.byref(self._handle), ctypes.byref(p), desc_array(self.eVecs), sg,
                                                  len(self.eVecs), ctypes.byref(c) if c is not None else None, stream))
         elif isinstance(transfer, (list, tuple)):
@@ -244,6 +259,10 @@ class Loop_Mugiq:
         """After computeCoarseLoop: the entry that entry `idx` was reflected from (opposite sign, same direction and
         lengths), or -1 if it was computed from the eigenvectors."""
         return int(_lib.load().mugiq_hip_loop_entry_derived_from(self._handle, int(idx)))
+
+    def entryKernel(self, idx):
+        """After computeCoarseLoop: how entry `idx` was produced (ENTRY_KERNEL_* of mugiq_amd.operators), or -1."""
+        return int(_lib.load().mugiq_hip_loop_get_entry_kernel(self._handle, int(idx)))
 
     def ultraLocalCarrier(self):
         """After computeCoarseLoop: the entry whose pass over the eigenvectors also produced the ultra-local loop, or -1."""

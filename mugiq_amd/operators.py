@@ -18,6 +18,9 @@ DispDir = {"x": 0, "y": 1, "z": 2, "t": 3}          # include/enum_mugiq.h:72-78
 DispSignMinus, DispSignPlus = 0, 1                   # include/enum_mugiq.h:81-85
 LOOP_FT_SIGN_MINUS, LOOP_FT_SIGN_PLUS = -1, 1        # include/enum_mugiq.h:28-33
 DisplaceFlagArray = ["+x", "-x", "+y", "-y", "+z", "-z", "+t", "-t"]   # include/displace.h:21
+REGION_ALL, REGION_INTERIOR, REGION_BOUNDARY, REGION_OVERWRITE = 0, 1, 2, 0x100   # MUGIQ_HIP_REGION_* (include/mugiq_hip.h)
+# mugiq_hip_loop_get_entry_kernel: how an entry of the last compute was produced (MUGIQ_HIP_ENTRY_KERNEL_*)
+ENTRY_KERNEL_REFLECTED, ENTRY_KERNEL_MFMA_COLUMN, ENTRY_KERNEL_MFMA_ROW, ENTRY_KERNEL_VECTOR_TILE, ENTRY_KERNEL_STREAMING, ENTRY_KERNEL_STEPWISE = range(6)
 
 
 def _stream():
@@ -203,6 +206,26 @@ def displacedLoopContractionFused(loopData_d, eVecs, sigmas, pathLinkFields, kVa
     _lib.check(_lib.load().mugiq_hip_displaced_loop_contraction_fused_mixed(
         loopData_d.data_ptr(), _prec_of(loopData_d), d, sg, n, links, kv, nk, int(dispDir), int(dispSign), _lib.int4(commDim),
         ghostLayers_d.data_ptr() if ghostLayers_d is not None else None, int(layers), _stream()))
+
+
+def displacedLoopContractionFusedTwoSided(loopData_d, eVecsLeft, eVecsRight, sigmas, pathLinkFields, kValues, dispDir, dispSign,
+                                          commDim=(0, 0, 0, 0), ghostLayers_d=None, layers=0, region=REGION_ALL, ultraLocalSlot_d=None):
+    """Two-sided form: loop slot i += sum_n (1/sigma_n) vL_n^dag G W_k vR_n(x +- k mu), k = kValues[i]; the ghost layers are those of
+    the right set.  Runs on the matrix-pipe tile only (MugiqHipError where it does not take the entry).  Returns whether the
+    ultra-local slot (sum_n (1/sigma_n) vL_n^dag G vR_n) was carried."""
+    n, nk = len(eVecsRight), len(kValues)
+    if len(eVecsLeft) != n:
+        raise _lib.MugiqHipError("two-sided contraction: %d left and %d right vectors" % (len(eVecsLeft), n))
+    sg = (ctypes.c_double * n)(*[float(s) for s in sigmas])
+    links = (ctypes.c_void_p * nk)(*[f.data.data_ptr() for f in pathLinkFields])
+    kv = (ctypes.c_int * nk)(*[int(k) for k in kValues])
+    carried = ctypes.c_int(0)
+    _lib.check(_lib.load().mugiq_hip_displaced_loop_contraction_fused_two_sided(
+        loopData_d.data_ptr(), _prec_of(loopData_d), desc_array(eVecsLeft), desc_array(eVecsRight), sg, n, links, kv, nk, int(dispDir),
+        int(dispSign), _lib.int4(commDim), ghostLayers_d.data_ptr() if ghostLayers_d is not None else None, int(layers), int(region),
+        ultraLocalSlot_d.data_ptr() if ultraLocalSlot_d is not None else None, ctypes.byref(carried) if ultraLocalSlot_d is not None else None,
+        _stream()))
+    return bool(carried.value)
 
 
 def probeReadBandwidth(buf, nonTemporal=False):

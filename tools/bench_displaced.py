@@ -24,6 +24,7 @@ ap.add_argument("--plans", default="opt,basic")
 ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--ab-tile", action="store_true", help="alternate MUGIQ_HIP_FUSED_TILE=0/1 in one process (interleaved rounds)")
 ap.add_argument("--momproj", type=int, default=-1, help="also run the momentum projection for all p^2 <= this (whole pipeline)")
+ap.add_argument("--two-sided", action="store_true", help="two-sided loops: a second random set as the left vectors (Loop_Mugiq eVecsLeft)")
 ap.add_argument("--ab-env", default=None, help="NAME=v1,v2,...: alternate an environment knob of the library in one process")
 a = ap.parse_args()
 
@@ -57,6 +58,16 @@ q = _gs(m)
 q = q.reshape(4, 2, vcb, 9).permute(1, 0, 3, 2).contiguous()          # [parity][dir][row*3+col][x_cb]
 g.data.copy_(q.reshape(-1).to(cdt))
 sig = 0.01 + 0.002 * np.arange(a.nev)
+left = None
+if a.two_sided:
+    bigL = torch.empty(a.nev * per, dtype=cdt, device="cuda")
+    left = []
+    for n in range(a.nev):
+        v = bigL[n * per:(n + 1) * per]
+        w = torch.complex(torch.randn(per, dtype=torch.float64, device="cuda"), torch.randn(per, dtype=torch.float64, device="cuda"))
+        w /= torch.linalg.vector_norm(w)
+        v.copy_(w.to(cdt))
+        left.append(hip.SpinorField(X, a.precision, a.order, data=v))
 B = a.precision
 res = {}
 if a.ab_env:
@@ -107,12 +118,12 @@ for plan in a.plans.split(","):
         r = int(np.sqrt(a.momproj)) + 1
         moms = [[x, y, z] for x in range(-r, r + 1) for y in range(-r, r + 1) for z in range(-r, r + 1) if x * x + y * y + z * z <= a.momproj]
         prm.doMomProj, prm.momMatrix, prm.Nmom, prm.FTSign = True, moms, len(moms), -1
-    loop = hip.Loop_Mugiq(prm, fields, sig)
+    loop = hip.Loop_Mugiq(prm, fields, sig, eVecsLeft=left)
     times = []
     for r in range(a.reps):
         if a.momproj >= 0 and r > 0:          # performMomentumProjection may run once per Loop_Mugiq (as in the reference)
             loop.close()
-            loop = hip.Loop_Mugiq(prm, fields, sig)
+            loop = hip.Loop_Mugiq(prm, fields, sig, eVecsLeft=left)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         loop.computeCoarseLoop()
@@ -122,8 +133,11 @@ for plan in a.plans.split(","):
     # algorithmic bytes of the whole job in the fused formulation: ultra-local (N_ev*24B + 32B) per site, plus per
     # displaced slot N_ev*24B (shifted vector) + per entry N_ev*24B (v(x), shared by the entry's slots) + 32B out
     alg = V * (a.nev * 24 * B + 32 * B) + V * (nslots * (a.nev * 24 * B + 32 * B + 18 * B) + loop.nDispEntries * a.nev * 24 * B)
+    if a.two_sided:  # the left set is read too: once for the ultra-local loop, once per entry (at the tile's own sites)
+        alg += V * (1 + loop.nDispEntries) * a.nev * 24 * B
     t = min(times)
     res[plan] = {"seconds": t, "sites_per_s_all_slots": V / t, "nLoop": loop.nLoop, "algorithmic_GB": alg / 1e9,
-                 "effective_GBps_vs_fused_algorithmic": alg / t / 1e9}
+                 "effective_GBps_vs_fused_algorithmic": alg / t / 1e9,
+                 "entry_kernels": [loop.entryKernel(i) for i in range(loop.nDispEntries)]}
     loop.close()
-print(json.dumps({"lattice": X, "nev": a.nev, "entries": a.entries, "results": res}))
+print(json.dumps({"lattice": X, "nev": a.nev, "entries": a.entries, "two_sided": a.two_sided, "results": res}))
