@@ -466,6 +466,20 @@ int mugiq_hip_rccl_relay_plan(int rank, const int grid[4], int dim, int dir, siz
  * per-stream workspace. */
 int mugiq_hip_exchange_ghost_vec(const MugiqHipSpinorField *v, const MugiqHipComm *comm, void *stream);
 
+/* ---- low-mode deflation of solutions (new; the step between the host's solver and a two-sided loop) ---------- */
+/* dst_r <- dst_r - sum_n v_n sigma_n^-1 c_nr,  c_nr = sum_x v_n(x)^dag G src_r(x),  G = g5 (gamma5 != 0) or 1.
+ * sigma_h NULL: sigma = 1 (with gamma5 = 0 and dst == src this is the orthogonal projector 1 - V V^dag).
+ * overlaps_h (optional, [nEv][nVec] complex double): c_nr, global, identical on every rank.
+ * comm NULL: one domain.  src may alias dst.
+ * dst_h / src_h: nVec descriptors of one precision (4 | 8), which may differ from the eigenvectors'; order, geometry, stride and
+ * parity offset as the eigenvectors'; nParity = 2.  The sums are taken in fp64 in a fixed order (bitwise reproducible); fp32 dst
+ * are rounded once.  Cross-rank sum: comm->reduce_space, gather_time, a fixed-order sum on the root, bcast (every rank calls).
+ * Blocking: with one domain (comm NULL or size 1) and overlaps_h NULL the call is stream-ordered and does not block the host;
+ * otherwise it synchronises `stream` once, when the overlaps leave the device (and again after the global ones are back). */
+int mugiq_hip_deflate_low_modes(const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec,
+                                const MugiqHipSpinorField *eVecs_h, const double *sigma_h, int nEv, int gamma5,
+                                double *overlaps_h, const MugiqHipComm *comm, void *stream);
+
 /* What Displace asks of QUDA's ColorSpinorField for its auxiliary vector (lib/displace.cpp:26-30: ColorSpinorField::Create
  * with QUDA_ZERO_FIELD_CREATE and setPrecision(coarsePrec_); :42,:50-51: operator=; :59: blas::zero), for hosts that do not
  * manage device memory themselves.  alloc: geometry, order, stride of `like`, `precision` (0 = like's), zeroed; ghost zones
@@ -619,6 +633,10 @@ int mugiq_hip_loop_write_hdf5(MugiqHipLoop *loop);
 int mugiq_hip_write_loops_hdf5_mom(const char *filename, const void *dataMom_bcast_h, int precision, int Nmom,
                                    const int *momMatrix, int nDispEntries, const char *const *disp_str,
                                    const int *disp_start, const int *disp_stop, int locT, int totT);
+/* mugiq_hip_deflate_low_modes with the eigenvectors, sigma, comm and stream of a one-sided fine-level loop object.
+ * MUGIQ_HIP_ERROR_UNSUPPORTED for two-sided and coarse (MG) loop objects. */
+int mugiq_hip_loop_deflate(MugiqHipLoop *loop, const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h,
+                           int nVec, int gamma5, double *overlaps_h);
 /* Loop_Mugiq::~Loop_Mugiq */
 int mugiq_hip_loop_destroy(MugiqHipLoop *loop);
 

@@ -82,6 +82,19 @@ inline void performLoopContractionBatched(std::complex<Float> *loopData_d, const
   check(mugiq_hip_perform_loop_contraction_batched(loopData_d, eVecL.data(), eVecR.data(), sigma.data(), (int)eVecL.size(), stream));
 }
 
+// dst_r <- dst_r - sum_n v_n sigma_n^-1 v_n^dag G src_r, G = g5 | 1 (mugiq_hip_deflate_low_modes; new).  sigma empty: sigma = 1;
+// overlaps != nullptr receives c_nr as [nEv][nVec] (resized).  dst may be src.
+inline void deflateLowModes(const std::vector<ColorSpinorField> &dst, const std::vector<ColorSpinorField> &src,
+                            const std::vector<ColorSpinorField> &eVecs, const std::vector<double> &sigma = {}, bool gamma5 = true,
+                            std::vector<std::complex<double>> *overlaps = nullptr, const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (src.empty() || dst.size() != src.size() || eVecs.empty() || (!sigma.empty() && sigma.size() != eVecs.size()))
+    throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "deflateLowModes: size mismatch");
+  if (overlaps) overlaps->assign(eVecs.size() * src.size(), std::complex<double>(0.0, 0.0));
+  check(mugiq_hip_deflate_low_modes(dst.data(), src.data(), (int)src.size(), eVecs.data(), sigma.empty() ? nullptr : sigma.data(),
+                                    (int)eVecs.size(), gamma5 ? 1 : 0, overlaps ? reinterpret_cast<double *>(overlaps->data()) : nullptr,
+                                    comm, stream));
+}
+
 // lib/contract_wrappers.cu:133-156
 template <typename Float>
 inline void convertIdxOrder_mapGamma(std::complex<Float> *dataPosMP_d, const std::complex<Float> *dataPos_d, int nData, int nLoop,
@@ -270,6 +283,7 @@ public:
 // `eVecs` / `eVals_sigma` are what the reference reads from Eigsolve_Mugiq as a friend (lib/loop_mugiq.cpp:442,479).
 template <typename Float, int fieldOrder> class Loop_Mugiq {
   MugiqHipLoop *h_ = nullptr;
+  int nEv_ = 0;  // eigenvectors of a one-sided fine-level loop (what deflate reads); 0 for the other forms
   GaugeField ownGauge_{};  // Displace::gaugeField when built here from loopParams.gauge[4]
 
   // everything the C parameter block points into, alive for the duration of the create call
@@ -334,6 +348,7 @@ public:
     checkField<Float, fieldOrder>(&eVecs[0], "Loop_Mugiq");
     CParam c;
     fill(c, lp, comm, stream);
+    nEv_ = (int)eVecs.size();
     const int st = mugiq_hip_loop_create(&h_, &c.p, eVecs.data(), eVals_sigma.data(), (int)eVecs.size(), comm, stream);
     if (st) {
       mugiq_hip_free_extended_gauge(&ownGauge_);
@@ -389,6 +404,14 @@ public:
     return i;
   }
   MugiqHipLoop *handle() { return h_; }
+  // deflateLowModes with this loop's eigenvectors, sigma, comm and stream (one-sided fine-level loops; mugiq_hip_loop_deflate)
+  void deflate(const std::vector<ColorSpinorField> &dst, const std::vector<ColorSpinorField> &src, bool gamma5 = true,
+               std::vector<std::complex<double>> *overlaps = nullptr) {
+    if (src.empty() || dst.size() != src.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "Loop_Mugiq::deflate: size mismatch");
+    if (overlaps) overlaps->assign((size_t)nEv_ * src.size(), std::complex<double>(0.0, 0.0));
+    check(mugiq_hip_loop_deflate(h_, dst.data(), src.data(), (int)src.size(), gamma5 ? 1 : 0,
+                                 overlaps ? reinterpret_cast<double *>(overlaps->data()) : nullptr));
+  }
   int entryKernel(int id) const { return mugiq_hip_loop_get_entry_kernel(h_, id); }  // MUGIQ_HIP_ENTRY_KERNEL_* of the last compute
   const std::complex<Float> *dataPos_d() const { return static_cast<const std::complex<Float> *>(mugiq_hip_loop_data_pos_d(h_)); }
   const std::complex<Float> *dataPos() { return static_cast<const std::complex<Float> *>(mugiq_hip_loop_data_pos_h(h_)); }

@@ -127,6 +127,8 @@ SIGNATURES = {
     "mugiq_hip_displaced_loop_contraction_fused": (ctypes.c_int, [_VP, _SP, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
                                                                   ctypes.POINTER(ctypes.c_void_p), _I4, ctypes.c_int,
                                                                   ctypes.c_int, ctypes.c_int, _I4, _VP, ctypes.c_int, _VP]),
+    "mugiq_hip_deflate_low_modes": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _SP, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int,
+                                                   ctypes.POINTER(ctypes.c_double), _VP, _VP]),
     "mugiq_hip_prolongate_batched": (ctypes.c_int, [_SP, ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),
     "mugiq_hip_prolongate_contract_batched": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(CoarseDesc), ctypes.POINTER(ctypes.c_double),
                                                              ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),
@@ -144,6 +146,7 @@ SIGNATURES = {
     "mugiq_hip_loop_create_two_sided": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _VP, _SP, _SP, ctypes.POINTER(ctypes.c_double),
                                                        ctypes.c_int, _VP, _VP]),
     "mugiq_hip_loop_compute": (ctypes.c_int, [_VP]),
+    "mugiq_hip_loop_deflate": (ctypes.c_int, [_VP, _SP, _SP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "mugiq_hip_loop_get_info": (ctypes.c_int, [_VP, _VP]),
     "mugiq_hip_loop_set_profiling": (ctypes.c_int, [_VP, ctypes.c_int]),
     "mugiq_hip_loop_get_phases": (ctypes.c_int, [_VP, _VP, ctypes.c_int]),

@@ -77,6 +77,10 @@ int fused_contraction(void *loopData_d, int loopPrecision, const MugiqHipSpinorF
                       const double *sigma_h, int nVec, const void *const *pathLinkFields_h, const int *kValues_h, int nK, int dispDir,
                       int dispSign, const int commDim[4], const void *ghostLayers_d, int layers, int region, void *ultraLocalSlot_d,
                       int *carried, void *stream, int *kernel);
+// csrc/deflate.hip: mugiq_hip_deflate_low_modes with the caller's name in the messages (mugiq_hip_loop_deflate passes the loop's set)
+int deflate_low_modes(const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int nVec, const MugiqHipSpinorField *ev,
+                      const double *sigma, int nEv, int gamma5, double *overlaps_h, const MugiqHipComm *comm, hipStream_t stream,
+                      const char *who);
 int entry_pack_capacity(const MugiqHipSpinorField &ev, const int *kvals, int nK);
 void set_entry_pack_hint(const EntryPackTarget *targets, int n);  // (NULL, 0) clears it
 bool entry_pack_taken();

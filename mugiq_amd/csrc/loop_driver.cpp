@@ -1629,6 +1629,17 @@ int mugiq_hip_loop_ultra_local_carrier(const MugiqHipLoop *lp) { return (lp && l
 
 int mugiq_hip_loop_halos_packed_in_entry(const MugiqHipLoop *lp) { return (lp && lp->computed) ? lp->halosPackedInEntry : -1; }
 
+int mugiq_hip_loop_deflate(MugiqHipLoop *lp, const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec, int gamma5,
+                           double *overlaps_h) {
+  const char *who = "Loop_Mugiq::deflate";
+  MUGIQ_REQUIRE(lp != nullptr, "%s: loop is NULL", who);
+  if (lp->twoSided || lp->coarseMode)
+    return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "%s: only one-sided loop objects over fine-level eigenvectors hold a low-mode set (%s)", who,
+                     lp->twoSided ? "two-sided loop" : "coarse (MG) eigenvectors");
+  return deflate_low_modes(dst_h, src_h, nVec, lp->eVecs.data(), lp->sigma.data(), lp->nEv, gamma5, overlaps_h,
+                           lp->haveComm ? &lp->comm : nullptr, lp->stream, who);
+}
+
 int mugiq_hip_loop_get_entry_kernel(const MugiqHipLoop *lp, int id) {
   if (!lp || !lp->computed || id < 0 || id >= lp->nDispEntries) return -1;
   return lp->entryKernel[id];

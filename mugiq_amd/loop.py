@@ -288,6 +288,16 @@ class Loop_Mugiq:
         lib.mugiq_hip_loop_get_phases(self._handle, ctypes.cast(buf, ctypes.c_void_p), n)
         return [{"kind": PHASE_NAMES[b.kind], "entry": b.entry, "ms": b.ms, "bytes": b.bytes} for b in buf]
 
+    def deflate(self, dst, src, gamma5=True, overlaps=False):
+        """deflateLowModes with this loop's eigenvectors, sigmas, comm and stream (mugiq_hip_loop_deflate): one-sided fine-level loops only
+        (MugiqHipError, status 2 = UNSUPPORTED, for two-sided and coarse loop objects).  Returns the [nEv][nVec] overlaps if asked."""
+        from .operators import _deflate_args, _overlap_buffer, _overlap_array
+        dst, src, dd, ds = _deflate_args(dst, src)
+        nEv, nVec = len(self.eVecs), len(src)
+        buf = _overlap_buffer(overlaps, nEv, nVec)
+        _lib.check(_lib.load().mugiq_hip_loop_deflate(self._handle, dd, ds, nVec, int(bool(gamma5)), buf))
+        return _overlap_array(buf, nEv, nVec) if overlaps else None
+
     def computeCoarseLoop(self):
         """lib/loop_mugiq.cpp:439-525"""
         _lib.check(_lib.load().mugiq_hip_loop_compute(self._handle))

@@ -228,6 +228,39 @@ def displacedLoopContractionFusedTwoSided(loopData_d, eVecsLeft, eVecsRight, sig
     return bool(carried.value)
 
 
+def _deflate_args(dst, src):
+    dst, src = list(dst), list(src)
+    if len(dst) != len(src) or not dst:
+        raise _lib.MugiqHipError("deflateLowModes: %d dst and %d src vectors (need the same number, at least one)" % (len(dst), len(src)))
+    return dst, src, desc_array(dst), desc_array(src)
+
+
+def _overlap_buffer(overlaps, nEv, nVec):
+    return (ctypes.c_double * (2 * nEv * nVec))() if overlaps else None
+
+
+def _overlap_array(buf, nEv, nVec):
+    return np.array(buf).view(np.complex128).reshape(nEv, nVec)
+
+
+def deflateLowModes(dst, src, eVecs, sigmas=None, gamma5=True, comm=None, overlaps=False):
+    """dst_r <- dst_r - sum_n v_n sigma_n^-1 c_nr,  c_nr = sum_x v_n(x)^dag G src_r(x),  G = g5 (gamma5) or 1  (mugiq_hip_deflate_low_modes).
+    sigmas None: sigma = 1.  dst may be src (the same SpinorField objects).  comm: a GridComm (None = one domain).
+    overlaps=True returns c as a [nEv][nVec] complex128 array (global, identical on every rank) and synchronises the stream;
+    otherwise the call is stream-ordered on one domain and returns None."""
+    dst, src, dd, ds = _deflate_args(dst, src)
+    ev = list(eVecs)
+    nEv, nVec = len(ev), len(src)
+    sg = (ctypes.c_double * nEv)(*[float(s) for s in sigmas]) if sigmas is not None else None
+    if sigmas is not None and len(sigmas) != nEv:
+        raise _lib.MugiqHipError("deflateLowModes: %d sigmas for %d eigenvectors" % (len(sigmas), nEv))
+    c = comm.c_struct() if comm is not None else None
+    buf = _overlap_buffer(overlaps, nEv, nVec)
+    _lib.check(_lib.load().mugiq_hip_deflate_low_modes(dd, ds, nVec, desc_array(ev), sg, nEv, int(bool(gamma5)), buf,
+                                                       ctypes.cast(ctypes.byref(c), ctypes.c_void_p) if c is not None else None, _stream()))
+    return _overlap_array(buf, nEv, nVec) if overlaps else None
+
+
 def probeReadBandwidth(buf, nonTemporal=False):
     """Enqueue one streaming read of `buf` (a torch tensor); time it with events for the device's achievable GB/s."""
     _lib.check(_lib.load().mugiq_hip_probe_read_bandwidth(buf.data_ptr(), buf.numel() * buf.element_size(), int(nonTemporal), _stream()))
