@@ -153,3 +153,29 @@ def test_cpp_deflate_mirror_compiles(tmp_path):
     r = subprocess.run([cc, "-std=c++17", "-fsyntax-only", "-x", "c++", "-D__HIP_PLATFORM_AMD__", "-Wall", "-I", os.path.join(ROOT, "include"),
                         "-I", "/opt/rocm/include", str(tu)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-4000:]
+
+
+def test_deflate_random_sweep_reaches_its_regimes():
+    """The cases of test_deflate_random_shapes (default seed count) reach what the sweep is there for, by the restated geometry of
+    deflate_low_modes (deflate_workers.deflate_geometry): several 64-eigenvector blocks with a partial last one, several segments per
+    pass-1 chunk with empty chunks behind the last one with work, every right-hand-side block width, several blocks in one call,
+    FLOAT4 with a partial last segment, every storage combination, and dst aliasing src for some r only.  (A partial last chunk is
+    not asked for: nSeg is a multiple of 12, so it needs segsPerChunk = 5 or more, i.e. fields far past the sweep's 32k sites.)"""
+    import deflate_workers as w
+    seen = set()
+    for seed in range(w.DEFAULT_SEEDS):
+        c = w.random_deflate_case(8000 + seed)
+        g = w.deflate_geometry(c["X"], c["order"], c["nev"], c["nvec"])
+        seen |= {k for k, v in g.items() if v is True}
+        seen |= {("RB", rb) for rb in g["RBs"]} | {("storage", c["pe"], c["order"], c["ps"])}
+        if len(g["RBs"]) > 1:
+            seen.add("multi_block")
+        if c["order"] == 4 and g["partial_last_segment"]:
+            seen.add("float4_partial_segment")
+        if 0 < len(c["alias"]) < c["nvec"]:
+            seen.add("mixed_alias")
+        if not c["overlaps"]:
+            seen.add("stream_ordered")
+    want = {"partial_last_block", "multi_segment", "empty_chunks", "multi_block", "float4_partial_segment", "mixed_alias",
+            "stream_ordered"} | {("RB", rb) for rb in (4, 8, 12, 16)} | {("storage",) + s for s in w.STORAGE}
+    assert want <= seen, sorted(map(str, want - seen))

@@ -1,6 +1,7 @@
 """GPU tests of low-mode deflation, dst_r <- dst_r - sum_n v_n sigma_n^-1 v_n^dag G src_r (mugiq_hip_deflate_low_modes,
 mugiq_hip_loop_deflate): every storage combination against numpy with NaN-filled pads, aliasing, determinism, process grids, the loop
 method, and the complete-basis pin of the whole low-mode + deflated-stochastic recipe of INTEGRATION.md."""
+import os
 import re
 
 import numpy as np
@@ -258,3 +259,64 @@ def test_complete_basis_pins_the_deflated_recipe(hip):
     scale = np.max(np.abs(Minv))
     for f in fx2:
         assert np.max(np.abs(f.get_logical())) < 1e-11 * scale
+
+
+@pytest.mark.parametrize("seed", range(int(os.environ.get("MUGIQ_TEST_SEEDS", deflate_workers.DEFAULT_SEEDS))))   # MUGIQ_TEST_SEEDS=N widens the sweep
+def test_deflate_random_shapes(hip, seed, record_max):
+    """Seeded random calls (deflate_workers.random_deflate_case: every storage combination, lattices up to 32k sites with several
+    segments per pass-1 chunk and empty chunks, N_ev past one and two 64-eigenvector blocks, every right-hand-side block width, NaN pads,
+    gamma5 on / off, sigma none or of both signs, a random subset of dst aliasing src, stream-ordered calls without overlaps) against
+    numpy matrix products: overlaps to 1e-12, dst to 1e-12 (fp64) / 1e-5 (fp32) of its largest element, dst pads bitwise unchanged,
+    src untouched where it is not aliased."""
+    c = deflate_workers.random_deflate_case(8000 + seed)
+    X, pe, order, ps, nev, nvec, pad = c["X"], c["pe"], c["order"], c["ps"], c["nev"], c["nvec"], c["pad"]
+    rng = np.random.default_rng(500 + seed)
+    ce, cs = (np.complex128 if pe == 8 else np.complex64), (np.complex128 if ps == 8 else np.complex64)
+    fe = [_field(hip, X, pe, order, _rand(rng, X, ce), pad) for _ in range(nev)]
+    Vm = np.stack([f.get_logical().astype(np.complex128).reshape(-1) for f in fe])          # [n][(p, x, s, c)]
+    src = [_rand(rng, X, cs) for _ in range(nvec)]
+    fs = [_field(hip, X, ps, order, v, pad) for v in src]
+    fd = [fs[r] if r in c["alias"] else _field(hip, X, ps, order, _rand(rng, X, cs), pad) for r in range(nvec)]
+    Dm = np.stack([f.get_logical().astype(np.complex128).reshape(-1) for f in fd])
+    g = np.tile(np.repeat(G5, 3), X[0] * X[1] * X[2] * X[3]) if c["gamma5"] else 1.0
+    C = Vm.conj() @ (g * np.stack([v.reshape(-1) for v in src])).T                           # V^dag (G S), [n][r]
+    sg = None if c["sigma"] is None else np.asarray(c["sigma"])
+    want = Dm - (C / (1.0 if sg is None else sg[:, None])).T @ Vm
+    pads = [_bits(f.data[_pad_mask(f)]).clone() for f in fd] if pad else None
+    kept = {r: _bits(fs[r].data).clone() for r in range(nvec) if r not in c["alias"]}
+    ov = hip.deflateLowModes(fd, fs, fe, c["sigma"], gamma5=c["gamma5"], overlaps=c["overlaps"])
+    if c["overlaps"]:
+        e = rel_err(ov, C)
+        record_max("deflate_sweep_overlaps", e)
+        assert e < 1e-12, (c, e)
+    else:
+        assert ov is None
+        torch.cuda.synchronize()
+    tol = 1e-12 if ps == 8 else 1e-5
+    tag = "fp64" if ps == 8 else "fp32"
+    for r in range(nvec):
+        got = fd[r].get_logical().astype(np.complex128).reshape(-1)
+        assert np.all(np.isfinite(got)), (c, r)
+        e = np.max(np.abs(got - want[r])) / np.max(np.abs(want[r]))
+        record_max("deflate_sweep_dst_%s" % tag, e)
+        assert e < tol, (c, r, e)
+        if pad:
+            assert torch.equal(_bits(fd[r].data[_pad_mask(fd[r])]), pads[r]), "pad of dst %d changed" % r
+        if r in kept:
+            assert torch.equal(_bits(fs[r].data), kept[r]), "src %d changed" % r
+
+
+@pytest.mark.parametrize("seed", [1, 4, 10, 13])
+def test_deflate_random_shapes_poisoned_lds(hip, seed, monkeypatch, record_max):
+    """Seeds of the sweep with several segments per pass-1 chunk, under NaN-filled LDS."""
+    monkeypatch.setenv("MUGIQ_HIP_DEBUG_POISON_LDS", "1")
+    test_deflate_random_shapes(hip, seed, record_max)
+
+
+def test_deflate_process_grid_many_modes_padded(tmp_path):
+    """2 ranks (t split), N_ev = 70 (two 64-eigenvector blocks, the last partial) and NaN-filled stride pads: local results equal the
+    single-domain numpy result, the overlaps are bitwise identical on both ranks."""
+    prefix = str(tmp_path / "ov")
+    mp.spawn(deflate_workers.deflate_worker, args=(2, free_port(), (1, 1, 1, 2), (4, 4, 8, 8), prefix, 70, 5, 7, 33), nprocs=2, join=True)
+    ovs = [np.load("%s_%d.npy" % (prefix, r)) for r in range(2)]
+    assert np.array_equal(ovs[1], ovs[0])

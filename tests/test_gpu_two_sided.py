@@ -2,6 +2,7 @@
 mugiq_hip_displaced_loop_contraction_fused_two_sided, the driver (mugiq_hip_loop_create_two_sided, OPT and BASIC plans), its
 consistency with the one-sided engine, the complete-basis pin of the documented gamma5 recipe, and process grids / forced
 partitioning.  Expected values come from the oracle's primitives (covariant_displacement, loop_contract, the reorder, the phases)."""
+import os
 import re
 
 import numpy as np
@@ -17,15 +18,15 @@ from util import orc, random_gauge_lex, random_spinor_lex, sigmas, momenta_p2_le
 pytestmark = pytest.mark.gpu
 
 
-def _problem(hip, X, nev, prec, order, seed):
+def _problem(hip, X, nev, prec, order, seed, pad=0, gpad=0):
     rng = np.random.default_rng(seed)
     cdt = np.complex128 if prec == 8 else np.complex64
     rnd = lambda: orc.lex_to_eo(random_spinor_lex(rng, X), X).astype(cdt).astype(np.complex128)
     vR, vL = [rnd() for _ in range(nev)], [rnd() for _ in range(nev)]
     Uo = orc.extended_gauge_from_global(random_gauge_lex(rng, X), (0, 0, 0, 0), (1, 1, 1, 1), (0, 0, 0, 0)).astype(cdt).astype(np.complex128)
-    fR = [hip.SpinorField(X, prec, order).set_logical(v) for v in vR]
-    fL = [hip.SpinorField(X, prec, order).set_logical(v) for v in vL]
-    U = hip.GaugeField(X, (0, 0, 0, 0), prec).set_logical(Uo)
+    fR = [hip.SpinorField(X, prec, order, pad=pad).set_logical(v) for v in vR]
+    fL = [hip.SpinorField(X, prec, order, pad=pad).set_logical(v) for v in vL]
+    U = hip.GaugeField(X, (0, 0, 0, 0), prec, pad=gpad).set_logical(Uo)
     return vL, vR, Uo, fL, fR, U
 
 
@@ -56,14 +57,15 @@ def _path_links(hip, X, prec, U, dirn, sign, kmax):
     return E
 
 
-STORAGE = [(8, 2, 8), (8, 4, 8), (4, 2, 4), (4, 4, 4), (4, 2, 8), (4, 4, 8)]   # (eigenvector precision, order, loop precision)
+STORAGE = two_sided_workers.STORAGE   # (eigenvector precision, order, loop precision)
 
 
-def _check_fused_cases(hip, monkeypatch, X, nev, prec, order, lprec, seed, cases_by_tj):
+def _check_fused_cases(hip, monkeypatch, X, nev, prec, order, lprec, seed, cases_by_tj, pad=0, gpad=0, record=None):
     """Every (name, lengths) of cases_by_tj[tj] through the two-sided C entry point with MUGIQ_HIP_MFMA_TJ = tj (None: the default
     choice), against the oracle: the displaced slots accumulated into a non-zero buffer, the ultra-local slot where it was carried,
-    and INTERIOR + BOUNDARY written with OVERWRITE over garbage."""
-    vL, vR, Uo, fL, fR, U = _problem(hip, X, nev, prec, order, seed)
+    and INTERIOR + BOUNDARY written with OVERWRITE over garbage.  pad / gpad: spinor / gauge stride pads; record(err): called with
+    every error measured."""
+    vL, vR, Uo, fL, fR, U = _problem(hip, X, nev, prec, order, seed, pad, gpad)
     sg = sigmas(nev)
     V = int(np.prod(X))
     tol = 1e-13 if prec == 8 else 1e-5                     # (fp32 storage: links and vectors rounded to fp32, loops in fp64 or fp32)
@@ -75,16 +77,18 @@ def _check_fused_cases(hip, monkeypatch, X, nev, prec, order, lprec, seed, cases
             monkeypatch.setenv("MUGIQ_HIP_MFMA_TJ", tj)
         for name, lengths in cases:
             dirn, sign = orc.parse_displacement(name)
-            E = _path_links(hip, X, prec, U, dirn, sign, max(lengths))
+            E = _path_links(hip, X, prec, U, dirn, sign, max(lengths))   # (path-link fields: FLOAT2, pad 0, whatever the vectors' pad)
             links = [E[k] for k in lengths]
             ref = _ref_slots(vL, vR, sg, Uo, X, dirn, sign, lengths)
             out = torch.full((len(lengths) * 16 * V,), 3.0, dtype=cdt, device="cuda")   # accumulated into
             ultra = torch.full((16 * V,), 3.0, dtype=cdt, device="cuda")
             carried = hip.displacedLoopContractionFusedTwoSided(out, fL, fR, sg, links, lengths, dirn, sign, ultraLocalSlot_d=ultra)
             tag = (tj, name, lengths)
-            assert rel_err(out.cpu().numpy() - 3.0, ref[16 * V:]) < tol, tag
+            errs = [rel_err(out.cpu().numpy() - 3.0, ref[16 * V:])]
+            assert errs[-1] < tol, (tag, errs[-1])
             if carried:
-                assert rel_err(ultra.cpu().numpy() - 3.0, ref[:16 * V]) < tol, tag
+                errs.append(rel_err(ultra.cpu().numpy() - 3.0, ref[:16 * V]))
+                assert errs[-1] < tol, (tag, errs[-1])
             else:
                 assert torch.all(ultra == 3.0), tag
             if (prec, order) == (8, 2) and dirn >= 1 and len(lengths) < 3:
@@ -93,7 +97,10 @@ def _check_fused_cases(hip, monkeypatch, X, nev, prec, order, lprec, seed, cases
             split = torch.full_like(out, 5.0)
             for r in (hip.REGION_INTERIOR, hip.REGION_BOUNDARY):
                 hip.displacedLoopContractionFusedTwoSided(split, fL, fR, sg, links, lengths, dirn, sign, region=r | hip.REGION_OVERWRITE)
-            assert rel_err(split.cpu().numpy(), ref[16 * V:]) < tol, tag
+            errs.append(rel_err(split.cpu().numpy(), ref[16 * V:]))
+            assert errs[-1] < tol, (tag, errs[-1])
+            if record:
+                record(max(errs))
     monkeypatch.delenv("MUGIQ_HIP_MFMA_TJ", raising=False)
     return fL, fR, sg, U, cdt, V
 
@@ -322,3 +329,90 @@ def test_two_sided_partitioned_runs(grid, force, G, tmp_path):
         per = 16 * int(np.prod(G))
         diff = [float(np.max(np.abs(a["pos"][i * per:(i + 1) * per] - b["pos"][i * per:(i + 1) * per]))) for i in range(len(a["pos"]) // per)]
         assert np.array_equal(a["pos"], b["pos"]) and np.array_equal(a["mom"], b["mom"]), diff
+
+
+def _storage_tag(prec, lprec):
+    return "fp64" if prec == 8 else ("fp32" if lprec == 4 else "mixed")
+
+
+@pytest.mark.parametrize("seed", range(int(os.environ.get("MUGIQ_TEST_SEEDS", two_sided_workers.DEFAULT_SEEDS))))   # MUGIQ_TEST_SEEDS=N widens the sweep
+def test_two_sided_random_shapes(hip, seed, monkeypatch, record_max):
+    """Seeded random two-sided loops (two_sided_workers.random_two_sided_case: extents 2 to 24, every storage type, N_ev 1 to 9, padded
+    spinor and gauge strides, lengths past the extent and past 8, start > stop, both FT signs) through the OPT plan -- and on every
+    fourth seed the BASIC plan -- against the two-sided reference in position and momentum space; every entry reports the kernel the
+    restated decision of the driver predicts (two_sided_workers.two_sided_entry_kernel)."""
+    for var in ("MUGIQ_HIP_MFMA_TJ", "MUGIQ_HIP_MFMA_ROW_WAVES", "MUGIQ_HIP_TILE_MFMA", "MUGIQ_HIP_MFMA_ROW", "MUGIQ_HIP_MFMA_STORAGE"):
+        monkeypatch.delenv(var, raising=False)
+    c = two_sided_workers.random_two_sided_case(5000 + seed)
+    X, prec, order, lprec, nev = c["X"], c["prec"], c["order"], c["lprec"], c["nev"]
+    vL, vR, Uo, fL, fR, U = _problem(hip, X, nev, prec, order, 900 + seed, c["pad"], c["gpad"])
+    sg = sigmas(nev)
+    _, s, a, b = orc.parse_disp_entry_string(c["entry"])
+    moms = momenta_p2_le(2)
+    cprm, pos, mom = two_sided_workers.two_sided_reference(orc, X, vL, vR, sg, Uo, (s, a, b), moms, c["FTSign"])
+    tol = 1e-12 if prec == 8 else 1e-5
+    tag = _storage_tag(prec, lprec)
+    want = [getattr(hip, "ENTRY_KERNEL_" + k) for k, _ in two_sided_workers.predicted_entry_kernels(c)]
+    for calc in ["opt"] + (["basic"] if seed % 4 == 0 else []):
+        kind = hip.LOOP_CALC_TYPE_OPT_KERNEL if calc == "opt" else hip.LOOP_CALC_TYPE_BASIC_KERNEL
+        prm = hip.MugiqLoopParam(gauge=U, calcType=kind, FTSign=c["FTSign"], doMomProj=True, loopPrecision=lprec)
+        prm.set_displace_entry_string(c["entry"])
+        prm.momMatrix, prm.Nmom = [list(m) for m in moms], len(moms)
+        loop = hip.Loop_Mugiq(prm, fR, sg, eVecsLeft=fL)
+        loop.computeCoarseLoop()
+        err, err_mom = rel_err(loop.dataPos_d.cpu().numpy(), pos), rel_err(loop.dataMom_bcast, mom)
+        kinds = [loop.entryKernel(i) for i in range(len(s))]
+        loop.close()
+        record_max("two_sided_sweep_pos_%s" % tag, err)
+        record_max("two_sided_sweep_mom_%s" % tag, err_mom)
+        assert err < tol and err_mom < tol, (c, calc, err, err_mom)
+        assert kinds == (want if calc == "opt" else [hip.ENTRY_KERNEL_STEPWISE] * len(s)), (c, calc, kinds, want)
+
+
+@pytest.mark.parametrize("seed", [0, 1, 11, 16])
+def test_two_sided_random_shapes_poisoned_lds(hip, seed, monkeypatch, record_max):
+    """Seeds of the sweep with padded strides and column and row tile entries, with the LDS of every CU filled with NaN patterns before
+    each call: a read of a cell nothing wrote shows up."""
+    monkeypatch.setenv("MUGIQ_HIP_DEBUG_POISON_LDS", "1")
+    test_two_sided_random_shapes(hip, seed, monkeypatch, record_max)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_fused_two_sided_random_tile_cases(hip, seed, monkeypatch, record_max):
+    """Random tile-eligible shapes (two_sided_workers.random_tile_case: one axis a multiple of 8, padded fields, N_ev 1 | 2 | 4 | 5 | 9,
+    lengths 1 .. kmax) through the two-sided C entry point: what the restated decision says the tile takes matches the oracle
+    (INTERIOR + BOUNDARY with OVERWRITE == ALL, the carried ultra-local slot); what it says the tile refuses raises MugiqHipError."""
+    monkeypatch.delenv("MUGIQ_HIP_MFMA_TJ", raising=False)
+    c = two_sided_workers.random_tile_case(6000 + seed)
+    X, prec, order, lprec = c["X"], c["prec"], c["order"], c["lprec"]
+    take, refuse = [], []
+    for name, lengths in c["cases"]:
+        k, _ = two_sided_workers.two_sided_entry_kernel(X, prec, order, "xyzt".index(name[1]), 1, max(lengths), c["pad"])
+        (refuse if k == "STEPWISE" else take).append((name, lengths))
+    rec = lambda e: record_max("two_sided_tile_sweep_%s" % _storage_tag(prec, lprec), e)
+    fL, fR, sg, U, cdt, V = _check_fused_cases(hip, monkeypatch, X, c["nev"], prec, order, lprec, 61 + seed, {None: take}, c["pad"], c["gpad"], rec)
+    for name, lengths in refuse:
+        dirn, sign = orc.parse_displacement(name)
+        E = _path_links(hip, X, prec, U, dirn, sign, max(lengths))
+        out = torch.zeros(len(lengths) * 16 * V, dtype=cdt, device="cuda")
+        with pytest.raises(hip.MugiqHipError):
+            hip.displacedLoopContractionFusedTwoSided(out, fL, fR, sg, [E[k] for k in lengths], lengths, dirn, sign)
+
+
+@pytest.mark.parametrize("seed", range(4))
+def test_two_sided_random_partitioned(seed, tmp_path, monkeypatch):
+    """Seeded random jobs (two_sided_workers.random_partitioned_case: storage, N_ev, pads, entries along x, z and t, some past the local
+    extent) with forced partitioning of z and t on one rank: equal to the single-domain reference, and bit for bit equal to the
+    unforced run of the same job in the same process.  Both runs build the axial gauge of every tile entry from the path links
+    (MUGIQ_HIP_GAUGE_FROM_LINKS=0): by default an entry along an axis that is not partitioned takes it from the gauge field, whose
+    link products are associated in another order, so its displaced slots agree with the partitioned run to rounding only."""
+    monkeypatch.setenv("MUGIQ_HIP_GAUGE_FROM_LINKS", "0")             # (inherited by the spawned process)
+    c = two_sided_workers.random_partitioned_case(7000 + seed)
+    mp.spawn(two_sided_workers.two_sided_worker, args=(1, free_port(), (1, 1, 1, 1), (0, 0, 1, 1), 1, c["G"], c["prec"], c["order"], "",
+                                                       False, c["disp"], c["nev"], c["pad"], c["gpad"], 40 + seed, True), nprocs=1, join=True)
+
+
+def test_two_sided_two_ranks_padded(tmp_path):
+    """2 ranks (t split) with padded spinor and gauge strides and N_ev = 5: equal to the single-domain reference."""
+    mp.spawn(two_sided_workers.two_sided_worker, args=(2, free_port(), (1, 1, 1, 2), (0, 0, 0, 0), 1, (4, 4, 8, 8), 8, 2, "", False, None,
+                                                       5, 6, 10, 77), nprocs=2, join=True)

@@ -81,3 +81,34 @@ def test_cpp_two_sided_overload_compiles(tmp_path):
     r = subprocess.run([cc, "-std=c++17", "-fsyntax-only", "-x", "c++", "-D__HIP_PLATFORM_AMD__", "-Wall", "-I", os.path.join(ROOT, "include"),
                         "-I", "/opt/rocm/include", str(tu)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-4000:]
+
+
+def test_two_sided_random_sweep_reaches_both_tiles_and_every_refusal():
+    """The cases of test_two_sided_random_shapes (default seed count), through the restated decision of the driver
+    (two_sided_workers.two_sided_entry_kernel): several column-tile entries, several of them along axes of extent 16 or 24, several
+    row-tile entries, and step-by-step entries for every reason (length past 8, past the extent, no tile geometry, reduced storage on a
+    row shape without a row tile); N_ev <= 4 and padded strides occur."""
+    import collections
+    import two_sided_workers as w
+    n = collections.Counter()
+    for seed in range(w.DEFAULT_SEEDS):
+        c = w.random_two_sided_case(5000 + seed)
+        for e, (kind, reason) in zip(c["entry"].split(";"), w.predicted_entry_kernels(c)):
+            n[kind] += 1
+            n[reason] += 1
+            if kind == "MFMA_COLUMN" and c["X"]["xyzt".index(e[1])] >= 16:
+                n["column_16_24"] += 1
+        n["nev<=4"] += c["nev"] <= 4
+        n["padded"] += c["pad"] > 0
+    assert n["MFMA_COLUMN"] >= 12 and n["column_16_24"] >= 8 and n["MFMA_ROW"] >= 6, n
+    for reason in ("kmax>8", "kmax>extent", "no geometry", "reduced row", "nev<=4", "padded"):
+        assert n[reason] >= 1, (reason, n)
+
+
+def test_two_sided_decision_restatement_matches_known_cases():
+    """Spot checks of the restated decision against the kernels the fixed-shape GPU tests assert"""
+    import two_sided_workers as w
+    k = lambda X, p, o, d, a, b: w.two_sided_entry_kernel(X, p, o, d, a, b)[0]
+    assert k((24, 8, 8, 8), 8, 2, 0, 1, 3) == "MFMA_ROW" and k((24, 8, 8, 8), 4, 4, 0, 1, 3) == "STEPWISE"
+    assert k((8, 8, 8, 16), 8, 2, 2, 1, 8) == "MFMA_COLUMN" and k((8, 8, 8, 16), 8, 2, 1, 1, 9) == "STEPWISE"
+    assert k((4, 4, 2, 4), 8, 2, 3, 1, 2) == "MFMA_COLUMN" and k((4, 4, 2, 2), 8, 2, 2, 1, 1) == "STEPWISE"
