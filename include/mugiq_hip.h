@@ -210,7 +210,11 @@ int mugiq_hip_pack_loop_layers(void *layers_d, const void *slot_d, const int loc
  * Slots are 16*V complex apart.  If commDim[dispDir] != 0, ghostLayers_d holds `layers` >= max k face layers
  * of every eigenvector received from the neighbour the displacement points to, laid out as
  * mugiq_hip_pack_face_layers writes them (sign +: the forward neighbour's LOW layers; sign -: the backward
- * neighbour's HIGH layers). */
+ * neighbour's HIGH layers).
+ * Links need not be unitary: the result is that of the links as stored.  The matrix-pipe tile (the default kernel) is exact only
+ * where the axial gauge built from W_1 .. W_kmax is, g^dag g = 1; these calls build that gauge, reduce
+ * max |g^dag g - 1| over it and take the tile only below 1e-12 (fp64 storage) / 4e-6 (fp32), else the vector tiles.  The check reads
+ * the deviation back to the host: a call that may take the tile synchronises `stream` once. */
 int mugiq_hip_displaced_loop_contraction_fused(void *loopData_d, const MugiqHipSpinorField *eVecs_h,
                                                const double *sigma_h, int nVec, const void *const *pathLinkFields_h,
                                                const int *kValues_h, int nK, int dispDir, int dispSign,
@@ -258,7 +262,8 @@ int mugiq_hip_displaced_loop_contraction_fused_carry(void *loopData_d, int loopP
  * the _carry call with eVecL_h / eVecR_h in place of eVecs_h (same geometry, precision and order); the ghost layers are those of
  * the RIGHT set (the only one that is displaced), the ultra-local slot is sum_n (1/sigma_n) vL_n^dag G vR_n.  It runs on the
  * matrix-pipe tile (csrc/fused_mfma_kernel.h, two-sided form) only: MUGIQ_HIP_ERROR_UNSUPPORTED where that tile does not take the
- * entry (lengths > 8 or not ascending, a partitioned x axis, no tile geometry for the extent) -- then the caller displaces vR step
+ * entry (lengths > 8 or not ascending, a partitioned x axis, no tile geometry for the extent, links whose axial gauge is not unitary
+ * to the tolerance of the one-sided calls) -- then the caller displaces vR step
  * by step (mugiq_hip_perform_covariant_displacement_vector) and contracts with mugiq_hip_perform_loop_contraction_batched. */
 int mugiq_hip_displaced_loop_contraction_fused_two_sided(void *loopData_d, int loopPrecision,
                                                          const MugiqHipSpinorField *eVecL_h, const MugiqHipSpinorField *eVecR_h,
@@ -530,7 +535,12 @@ typedef struct MugiqHipLoop_s MugiqHipLoop;
 /* Loop_Mugiq::Loop_Mugiq(loopParams, eigsolve)  lib/loop_mugiq.cpp:6-59: takes what the class reads from
  * Eigsolve_Mugiq as a friend -- eVecs[0..nEv) and eVals_sigma[0..nEv) (lib/loop_mugiq.cpp:442,479) -- sets up
  * LoopComputeParam, allocates the data buffers, creates the phase matrix.  comm may be NULL (single process).
- * The descriptors are copied; the eigenvector memory stays the caller's. */
+ * The descriptors are copied; the eigenvector memory stays the caller's.
+ * Links need not be unitary (anisotropy-rescaled, smeared and not re-projected, fp32 links in fp64 storage).  At create and at the
+ * start of every OPT compute a pre-pass over the gauge field (one thread per line, per direction with entries: about 0.13 ms per
+ * direction at 48x48x24x24, and one host synchronisation) measures how far the axial gauge of each direction is from unitary; the
+ * flags are summed over all ranks through the comm callbacks, so every rank decides alike.  Directions above the tolerance take the
+ * vector tiles (one-sided) or the step-by-step sequence (two-sided) instead of the matrix-pipe tile. */
 int mugiq_hip_loop_create(MugiqHipLoop **loop, const MugiqHipLoopParam *param, const MugiqHipSpinorField *eVecs_h,
                           const double *eVals_sigma_h, int nEv, const MugiqHipComm *comm, void *stream);
 /* Two-sided loops (new): sum_r (1/sigma_r) vL_r^dag(x) G [D^k vR_r](x) for every entry, with separate left (eVecsL_h) and right
@@ -602,6 +612,7 @@ int mugiq_hip_loop_halos_packed_in_entry(const MugiqHipLoop *loop);
 #define MUGIQ_HIP_PHASE_TOTAL_WALL 13          /* host wall time of the whole mugiq_hip_loop_compute call (always the last phase) */
 #define MUGIQ_HIP_PHASE_MOMENTUM_REFLECT 15     /* host: reflected entries derived on the gathered momentum-space array (wall time) */
 #define MUGIQ_HIP_PHASE_SCRATCH_ALLOC 14       /* host: hipMalloc of scratch / halo buffers the pool did not hold yet (wall time, bytes) */
+#define MUGIQ_HIP_PHASE_AXIAL_CHECK 16         /* OPT plan: the unitarity pre-pass of the axial-gauge tile (kernels, one host read, the cross-rank sum) */
 typedef struct MugiqHipLoopPhase_s {
   int kind;     /* MUGIQ_HIP_PHASE_* */
   int entry;    /* displacement entry the phase belongs to, or -1 */

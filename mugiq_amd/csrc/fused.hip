@@ -281,14 +281,32 @@ static int fused_entry(void *loop_d, const MugiqHipSpinorField *ev, const double
     int kmax = 0;
     for (int i = 0; i < nK; i++) kmax = kvals[i] > kmax ? kvals[i] : kmax;
     // (every storage type: the tile converts on the way into LDS and works in double; float slots are rounded once, on the way out)
-    if (mfma_tile_applicable(ev[0], dir, kvals, nK, partitioned, axial_gauge_hint_matches(E_d[0], dir, sign, kmax), evL != nullptr)) {
+    const bool hinted = axial_gauge_hint_matches(E_d[0], dir, sign, kmax);
+    const int verdict = axial_tile_verdict();
+    bool tile = verdict != 0 && mfma_tile_applicable(ev[0], dir, kvals, nK, partitioned, hinted, evL != nullptr);
+    // the link fields of a hinted call are the gauge buffer: no other kernel may read them (the driver decides before it builds one)
+    if (hinted && !tile)
+      return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "fused contraction: an axial gauge stands in for the links of direction %d, but the "
+                       "matrix-pipe tile does not take the entry (internal)", dir);
+    void *checkedGauge = nullptr;
+    if (tile && verdict < 0 && !hinted) {  // free call: the tile only where the gauge of these links is unitary
+      double dev = 0.0;
+      if (int st = build_axial_gauge_checked(&checkedGauge, &dev, ev[0], E_d, kmax, dir, sign, stream)) return st;
+      tile = dev <= axial_gauge_tolerance(ev[0].precision);
+    }
+    if (tile) {
       *kernel = dir == 0 ? MUGIQ_HIP_ENTRY_KERNEL_MFMA_ROW : MUGIQ_HIP_ENTRY_KERNEL_MFMA_COLUMN;
-      return mfma_tile_entry(loop_d, (int)sizeof(A), ev, sigma, nVec, E_d, kvals, nK, dir, sign, partitioned, ghost_d, layers, region, stream, ultra_d, carried, evL);
+      if (!checkedGauge)
+        return mfma_tile_entry(loop_d, (int)sizeof(A), ev, sigma, nVec, E_d, kvals, nK, dir, sign, partitioned, ghost_d, layers, region, stream, ultra_d, carried, evL);
+      set_axial_gauge_hint(checkedGauge, E_d[0], dir, sign, kmax);  // (the gauge just built and checked; no second build)
+      const int st = mfma_tile_entry(loop_d, (int)sizeof(A), ev, sigma, nVec, E_d, kvals, nK, dir, sign, partitioned, ghost_d, layers, region, stream, ultra_d, carried, evL);
+      set_axial_gauge_hint(nullptr, nullptr, -1, -1, 0);
+      return st;
     }
     if (evL)  // (no two-sided form of the vector tiles or of the streaming kernel)
       return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "mugiq_hip_displaced_loop_contraction_fused_two_sided: the matrix-pipe tile does not take this entry "
-                       "(direction %d, lengths %d .. %d, partitioned %d, precision %d, order %d): use the step-by-step sequence", dir, kvals[0], kvals[nK - 1],
-                       partitioned, ev[0].precision, ev[0].field_order);
+                       "(direction %d, lengths %d .. %d, partitioned %d, precision %d, order %d, or links that are not unitary): use the step-by-step "
+                       "sequence", dir, kvals[0], kvals[nK - 1], partitioned, ev[0].precision, ev[0].field_order);
     *kernel = MUGIQ_HIP_ENTRY_KERNEL_VECTOR_TILE;
     const bool gen2 = tile_applicable(ev[0], dir, kmax, ev[0].precision, partitioned);
     if (tile16_applicable(ev[0], dir, kmax, ev[0].precision, partitioned, gen2))

@@ -32,6 +32,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 #include <vector>
 
@@ -39,8 +40,30 @@ namespace mugiq {
 
 // ---- the axial gauge of one (direction, sign) from the path-link fields E_k = W_k (FLOAT2, pad 0; component 3 j + i of
 // E_k(x) is W_k(x)[i][j]): one thread per line, sequential along the line
+// ---- unitarity of the axial gauge.  W_k(x) v(x + k mu) = g(x)^dag [g v](x + k mu) needs g^dag g = 1; with links that are not unitary
+// (anisotropy-rescaled, smeared and not re-projected, fp32 links in fp64 storage) the tile's error is (g(x)^dag g(x) - 1) W_k(x).
+// mt_deviation: max_ab |(g^dag g - 1)_ab|.  Maxima go into a device word as the bits of a non-negative double (they order like the
+// values); a NaN stays NaN, and no threshold passes it.
+__device__ inline double mt_deviation(const Cplx<double> g[9]) {
+  double d = 0.0;
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int b = 0; b < 3; b++) {
+      Cplx<double> s{a == b ? -1.0 : 0.0, 0.0};
+#pragma unroll
+      for (int m = 0; m < 3; m++) cmadd_conj(s, g[m * 3 + a], g[m * 3 + b]);
+      const double e = sqrt(s.re * s.re + s.im * s.im);
+      d = (e > d || e != e) ? e : d;
+    }
+  return d;
+}
+__device__ inline void mt_worse(double &worst, double d) { worst = (d > worst || d != d) ? d : worst; }
+__device__ inline void mt_report(unsigned long long *out, double worst) { atomicMax(out, (unsigned long long)__double_as_longlong(worst)); }
+
 template <typename F> struct AxialArgs {
   Cplx<double> *G;
+  unsigned long long *dev;  // != NULL: also the largest deviation of the gauge built (mt_deviation)
   const Cplx<F> *E[kMT_MaxLength];  // E_1 .. E_kmax (storage precision; the gauge itself is kept in double)
   int kmax, sign, J, strideMu, H, numCols, volumeCB;
   int rowMode, X1, X2;  // mu = x: line = x row `cid`, site j <-> (parity p0 ^ (j & 1), entry cid J/2 + j/2); G is [9][row][position]
@@ -87,6 +110,11 @@ template <typename F> __global__ __launch_bounds__(64) void axial_gauge_kernel(A
     for (int c = 0; c < 9; c++) a.G[a.rowMode ? ((int64_t)c * a.numCols + cid) * Jext + jext : ((int64_t)c * Jext + jext) * a.numCols + cid] = g[c];
   };
   auto site_xcb = [&](int j) { return a.rowMode ? base + (j >> 1) : base + j * a.strideMu; };
+  double worst = 0.0;
+  auto store_checked = [&](int jext, const Cplx<double> g[9]) {
+    store(jext, g);
+    if (a.dev) mt_worse(worst, mt_deviation(g));
+  };
   Cplx<double> g[9], w[9], t[9];
 #pragma unroll
   for (int c = 0; c < 9; c++) g[c] = Cplx<double>{c % 4 == 0 ? 1.0 : 0.0, 0.0};
@@ -94,7 +122,7 @@ template <typename F> __global__ __launch_bounds__(64) void axial_gauge_kernel(A
   if (a.sign == MUGIQ_HIP_DISP_SIGN_MINUS) {  // g(-l) = W^-_l(x_0)
     for (int l = 1; l <= a.kmax; l++) {
       mt_load_w(w, a.E[l - 1], p0, site_xcb(0), a.volumeCB);
-      store(a.kmax - l, w);
+      store_checked(a.kmax - l, w);
     }
   }
   for (int j = 0; j < a.J; j++) {
@@ -105,13 +133,13 @@ template <typename F> __global__ __launch_bounds__(64) void axial_gauge_kernel(A
 #pragma unroll
       for (int c = 0; c < 9; c++) g[c] = t[c];
     }
-    store(j + off, g);
+    store_checked(j + off, g);
     if (a.sign == MUGIQ_HIP_DISP_SIGN_PLUS) {
       if (j == a.J - 1) {  // g(J + l) = g(J - 1) W_{l+1}(x_{J-1})
         for (int l = 0; l < a.kmax; l++) {
           mt_load_w(w, a.E[l], par, x_cb, a.volumeCB);
           mt_mul3<false>(t, g, w);
-          store(a.J + l, t);
+          store_checked(a.J + l, t);
         }
       } else {  // g(j + 1) = g(j) W_1(x_j)
         mt_load_w(w, a.E[0], par, x_cb, a.volumeCB);
@@ -121,6 +149,7 @@ template <typename F> __global__ __launch_bounds__(64) void axial_gauge_kernel(A
       }
     }
   }
+  if (a.dev) mt_report(a.dev, worst);
 }
 
 // ---- the same gauge straight from the gauge field, for a direction that is NOT partitioned (the local line is the global, periodic
@@ -326,6 +355,12 @@ void set_entry_pack_hint(const EntryPackTarget *targets, int n) {
 }
 bool entry_pack_taken() { return g_pack.taken; }
 
+namespace {
+thread_local int g_verdict = -1;
+}  // namespace
+void set_axial_tile_verdict(int allowed) { g_verdict = allowed; }
+int axial_tile_verdict() { return g_verdict; }
+
 void set_axial_gauge_hint(const void *G_d, const void *E1_d, int dir, int sign, int kmax) {
   g_hint.G = G_d;
   g_hint.E1 = E1_d;
@@ -343,9 +378,11 @@ bool axial_gauge_hint_matches(const void *E0_d, int dir, int sign, int kmax) {
 }
 
 template <typename F>
-static int build_axial_gauge_t(void *G_d, const MugiqHipSpinorField &ev, const void *const *E_d, int kmax, int dir, int sign, hipStream_t stream) {
+static int build_axial_gauge_t(void *G_d, const MugiqHipSpinorField &ev, const void *const *E_d, int kmax, int dir, int sign, hipStream_t stream,
+                               unsigned long long *dev_d) {
   AxialArgs<F> g;
   g.G = static_cast<Cplx<double> *>(G_d);
+  g.dev = dev_d;
   for (int l = 0; l < kMT_MaxLength; l++) g.E[l] = static_cast<const Cplx<F> *>(E_d[l < kmax ? l : 0]);
   long long strideMu = 1;
   for (int d = 0; d < dir; d++) strideMu *= ev.X[d];
@@ -365,8 +402,138 @@ static int build_axial_gauge_t(void *G_d, const MugiqHipSpinorField &ev, const v
 }
 // (the path-link fields are FLOAT2, pad 0, in the eigenvectors' precision)
 int build_axial_gauge(void *G_d, const MugiqHipSpinorField &ev, const void *const *E_d, int kmax, int dir, int sign, hipStream_t stream) {
-  return ev.precision == 8 ? build_axial_gauge_t<double>(G_d, ev, E_d, kmax, dir, sign, stream)
-                           : build_axial_gauge_t<float>(G_d, ev, E_d, kmax, dir, sign, stream);
+  return ev.precision == 8 ? build_axial_gauge_t<double>(G_d, ev, E_d, kmax, dir, sign, stream, nullptr)
+                           : build_axial_gauge_t<float>(G_d, ev, E_d, kmax, dir, sign, stream, nullptr);
+}
+
+double axial_gauge_tolerance(int precision) { return precision == 8 ? 1e-12 : 4e-6; }
+
+static double deviation_from_bits(unsigned long long b) {
+  double d;
+  std::memcpy(&d, &b, sizeof d);
+  return d;
+}
+
+// The free fused call: the gauge from the links of the call into the stream's workspace, and its largest deviation (host-blocking)
+int build_axial_gauge_checked(void **G_out, double *deviation, const MugiqHipSpinorField &ev, const void *const *E_d, int kmax, int dir, int sign,
+                              hipStream_t stream) {
+  const size_t gb = (size_t)9 * (ev.X[dir] + kmax) * (size_t)(2 * ev.volumeCB / ev.X[dir]) * sizeof(Cplx<double>);
+  void *ws = nullptr;
+  int st = stream_workspace(&ws, gb + 256, stream);
+  if (st) return st;
+  unsigned long long *dev_d = reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + gb);
+  MUGIQ_CHECK_HIP(hipMemsetAsync(dev_d, 0, sizeof *dev_d, stream));
+  st = ev.precision == 8 ? build_axial_gauge_t<double>(ws, ev, E_d, kmax, dir, sign, stream, dev_d)
+                         : build_axial_gauge_t<float>(ws, ev, E_d, kmax, dir, sign, stream, dev_d);
+  if (st) return st;
+  unsigned long long bits = 0;
+  MUGIQ_CHECK_HIP(hipMemcpyAsync(&bits, dev_d, sizeof bits, hipMemcpyDeviceToHost, stream));
+  MUGIQ_CHECK_HIP(hipStreamSynchronize(stream));
+  *G_out = ws;
+  *deviation = deviation_from_bits(bits);
+  return MUGIQ_HIP_SUCCESS;
+}
+
+// ---- the driver's pre-pass: D_mu = max over the lines of direction mu and the positions -reach .. J + reach - 1 of mt_deviation(g), with
+// g(j + 1) = g(j) U_mu(x_j), g(0) = 1 (the recurrence of axial_gauge_from_links_kernel; a periodic line wraps, a partitioned one stops where
+// the border of the extended field ends -- the neighbour's own pre-pass covers its links).  One thread per line.
+template <typename F> struct DeviationArgs {
+  const Cplx<F> *U;
+  int64_t Upo;
+  int Ustride;
+  int X[4], R[4];
+  int dir, fwd, bwd, periodic, numLines;
+  unsigned long long *out;
+};
+template <typename F> __global__ __launch_bounds__(64) void axial_deviation_kernel(DeviationArgs<F> a) {
+  const int cid = blockIdx.x * 64 + threadIdx.x;
+  const bool line = cid < a.numLines;  // (every lane stays for the wave's reduction below)
+  int c0[4], XE[4];
+  for (int d = 0, r = cid; d < 4; d++) {
+    XE[d] = a.X[d] + 2 * a.R[d];
+    if (d == a.dir) {
+      c0[d] = 0;
+    } else {
+      c0[d] = r % a.X[d];
+      r /= a.X[d];
+    }
+  }
+  const int J = a.X[a.dir];
+  auto load_u = [&](Cplx<double> u[9], int j) {
+    int c[4];
+#pragma unroll
+    for (int d = 0; d < 4; d++) c[d] = d == a.dir ? (a.periodic ? ((j % J) + J) % J : j) : c0[d];
+    const int par = (c[0] + c[1] + c[2] + c[3]) & 1;  // (borders are even: the extended parity is the interior one)
+#pragma unroll
+    for (int d = 0; d < 4; d++) c[d] += a.R[d];
+    const Cplx<F> *q = a.U + (int64_t)par * a.Upo + (int64_t)(a.dir * 9) * a.Ustride + (lex_index(c, XE) >> 1);
+#pragma unroll
+    for (int e = 0; e < 9; e++) {
+      const Cplx<F> v = q[(int64_t)e * a.Ustride];
+      u[e] = Cplx<double>{(double)v.re, (double)v.im};
+    }
+  };
+  Cplx<double> g[9], u[9], t[9];
+  double worst = 0.0;
+  for (int pass = 0; pass < 2; pass++) {  // g(1) .. g(fwd), then g(-1) .. g(-bwd)
+#pragma unroll
+    for (int c = 0; c < 9; c++) g[c] = Cplx<double>{c % 4 == 0 ? 1.0 : 0.0, 0.0};
+    const int n = !line ? 0 : pass == 0 ? a.fwd : a.bwd;
+    for (int l = 0; l < n; l++) {
+      load_u(u, pass == 0 ? l : -1 - l);
+      if (pass == 0) mt_mul3<false>(t, g, u);
+      else mt_mul3<true>(t, g, u);
+#pragma unroll
+      for (int c = 0; c < 9; c++) g[c] = t[c];
+      mt_worse(worst, mt_deviation(g));
+    }
+  }
+  for (int m = 32; m >= 1; m >>= 1) mt_worse(worst, __shfl_xor(worst, m, 64));  // one atomic per wave, not one per line
+  if (threadIdx.x == 0) mt_report(a.out, worst);
+}
+
+template <typename F>
+static int launch_axial_deviation(unsigned long long *out_d, const MugiqHipGaugeField &U, int dir, int reach, int partitioned, hipStream_t stream) {
+  DeviationArgs<F> a;
+  a.U = static_cast<const Cplx<F> *>(U.data);
+  a.Upo = U.parity_offset;
+  a.Ustride = U.stride;
+  long long lines = 1;
+  for (int d = 0; d < 4; d++) {
+    a.X[d] = U.X[d];
+    a.R[d] = U.R[d];
+    if (d != dir) lines *= U.X[d];
+  }
+  a.dir = dir;
+  a.periodic = !partitioned;
+  const int J = U.X[dir];
+  a.fwd = partitioned ? std::min(J + reach - 1, J + U.R[dir]) : J + reach - 1;  // (g(j + 1) needs the link at j)
+  a.bwd = partitioned ? std::min(reach, U.R[dir]) : reach;
+  a.numLines = (int)lines;
+  a.out = out_d;
+  hipLaunchKernelGGL(axial_deviation_kernel<F>, dim3((unsigned)((lines + 63) / 64)), dim3(64), 0, stream, a);
+  MUGIQ_CHECK_HIP(hipGetLastError());
+  return MUGIQ_HIP_SUCCESS;
+}
+
+int axial_line_deviation(double D[4], const MugiqHipGaugeField &U, const int reach[4], const int partitioned[4], hipStream_t stream) {
+  void *ws = nullptr;
+  int st = stream_workspace(&ws, 4 * sizeof(unsigned long long), stream);
+  if (st) return st;
+  unsigned long long *out_d = static_cast<unsigned long long *>(ws);
+  MUGIQ_CHECK_HIP(hipMemsetAsync(out_d, 0, 4 * sizeof(unsigned long long), stream));
+  for (int d = 0; d < 4; d++) {
+    if (reach[d] <= 0) continue;
+    const int r = std::min(reach[d], kMT_MaxLength);  // (longer entries never take the tile)
+    st = U.precision == 8 ? launch_axial_deviation<double>(out_d + d, U, d, r, partitioned[d], stream)
+                          : launch_axial_deviation<float>(out_d + d, U, d, r, partitioned[d], stream);
+    if (st) return st;
+  }
+  unsigned long long bits[4] = {0, 0, 0, 0};
+  MUGIQ_CHECK_HIP(hipMemcpyAsync(bits, out_d, sizeof bits, hipMemcpyDeviceToHost, stream));
+  MUGIQ_CHECK_HIP(hipStreamSynchronize(stream));
+  for (int d = 0; d < 4; d++) D[d] = deviation_from_bits(bits[d]);
+  return MUGIQ_HIP_SUCCESS;
 }
 
 template <typename F>

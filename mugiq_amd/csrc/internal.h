@@ -51,6 +51,18 @@ int build_axial_gauge(void *G_d, const MugiqHipSpinorField &ev, const void *cons
 bool axial_gauge_from_links_possible(const MugiqHipSpinorField &ev, const MugiqHipGaugeField &U, int kmax, int dir, int sign);
 int build_axial_gauge_from_links(void *G_d, const MugiqHipSpinorField &ev, const MugiqHipGaugeField &U, int kmax, int dir, int sign, hipStream_t stream);
 void set_axial_gauge_hint(const void *G_d, const void *E1_d, int dir, int sign, int kmax);
+// The tile is exact only where g^dag g = 1.  axial_gauge_tolerance: the largest deviation max |g^dag g - 1| it is taken with
+// (per storage precision).  axial_line_deviation: the driver's pre-pass, D[mu] over the lines of the local gauge field out to reach[mu]
+// positions past both ends (reach 0: D = 0, not looked at); blocks the host once.  build_axial_gauge_checked: the free fused call's
+// gauge from its links, built into the stream's workspace, with its deviation; blocks the host once.
+double axial_gauge_tolerance(int precision);
+int axial_line_deviation(double D[4], const MugiqHipGaugeField &U, const int reach[4], const int partitioned[4], hipStream_t stream);
+int build_axial_gauge_checked(void **G_out, double *deviation, const MugiqHipSpinorField &ev, const void *const *E_d, int kmax, int dir, int sign,
+                              hipStream_t stream);
+// The driver's tile decision for the fused calls it makes (per host thread, like the hint): 1 the tile may be taken (the pre-pass passed),
+// 0 it may not (the vector tiles take the entry), -1 no decision (a free call: fused_entry checks the gauge of W_1 .. W_kmax itself)
+void set_axial_tile_verdict(int allowed);
+int axial_tile_verdict();
 bool axial_gauge_hint_matches(const void *E0_d, int dir, int sign, int kmax);  // E0_d: the first link field of the call
 
 // Face layers packed by a mu = x entry on its way through the eigenvectors (csrc/fused_mfma.hip, row tile): the driver hands the

@@ -66,6 +66,10 @@ struct MugiqHipLoop_s {
   int loopPrecision = 8;  // precision of the loop buffers / FT (= precision, or 8 over fp32 fields: mixed mode)
   MugiqHipGaugeField gauge;
   bool haveGauge = false;
+  // the axial-gauge tile along mu only where the gauge of the lines of mu is unitary (check_axial_gauge, once per compute; the same on
+  // every rank).  axialDev: this rank's D_mu of the last check
+  bool axialOk[4] = {true, true, true, true};
+  double axialDev[4] = {0, 0, 0, 0};
   MugiqHipComm comm;
   bool haveComm = false;
   int commDim[4] = {0, 0, 0, 0};
@@ -361,6 +365,42 @@ static size_t halo_bytes(const MugiqHipLoop *lp, int id) {
 
 static int reflection_source(const MugiqHipLoop *lp, int id);
 
+// The tile decision per direction: the pre-pass D_mu of csrc/fused_mfma.hip against axial_gauge_tolerance.  The gauge field belongs
+// to the caller and may change between computes, so it runs at the start of every OPT compute (and at create, for the pool
+// reservation).  Every rank must take the same decision -- the path-link face exchanges and the halos posted ahead depend on it --
+// so the per-direction "not unitary" flags are summed over all ranks (reduce_space, gather_time, bcast, as the momentum projection).
+static int check_axial_gauge(MugiqHipLoop *lp) {
+  int reach[4] = {0, 0, 0, 0};
+  for (int id = 0; id < lp->nDispEntries; id++) reach[lp->dispDir[id]] = std::max(reach[lp->dispDir[id]], lp->dispStop[id]);
+  int st = axial_line_deviation(lp->axialDev, lp->gauge, reach, lp->commDim, lp->stream);
+  if (st) return st;
+  const double tau = axial_gauge_tolerance(lp->precision);
+  std::vector<double> bad(4), space(4, 0.0), sum(4, 0.0);
+  for (int d = 0; d < 4; d++) bad[d] = lp->axialDev[d] <= tau ? 0.0 : 1.0;  // (a NaN is not unitary)
+  if (lp->haveComm && lp->comm.size > 1) {
+    std::vector<double> gathered(4 * (size_t)lp->comm.grid[3], 0.0);
+    if ((st = lp->comm.reduce_space(lp->comm.ctx, bad.data(), space.data(), 4, 8)))
+      return set_error(MUGIQ_HIP_ERROR_HIP, "axial-gauge check: reduce_space callback failed with status %d", st);
+    if ((st = lp->comm.gather_time(lp->comm.ctx, space.data(), gathered.data(), 4, 8)))
+      return set_error(MUGIQ_HIP_ERROR_HIP, "axial-gauge check: gather_time callback failed with status %d", st);
+    for (int t = 0; t < lp->comm.grid[3]; t++)
+      for (int d = 0; d < 4; d++) sum[d] += gathered[(size_t)t * 4 + d];
+    if ((st = lp->comm.bcast(lp->comm.ctx, sum.data(), 4, 8)))
+      return set_error(MUGIQ_HIP_ERROR_HIP, "axial-gauge check: bcast callback failed with status %d", st);
+  } else {
+    sum = bad;
+  }
+  for (int d = 0; d < 4; d++) lp->axialOk[d] = sum[d] == 0.0;
+  return MUGIQ_HIP_SUCCESS;
+}
+
+// The one place the driver asks whether the axial-gauge tile may take entry `id`; where it may not, no axial gauge is built or
+// reserved, and the fused calls take the vector tiles (one-sided) or the entry goes step by step (two-sided)
+static bool entry_tile_allowed(const MugiqHipLoop *lp, int id) { return lp->axialOk[lp->dispDir[id]]; }
+static size_t entry_gauge_bytes(const MugiqHipLoop *lp, int id, const std::vector<int> &kv, int partitioned) {
+  return entry_tile_allowed(lp, id) ? axial_gauge_bytes(lp->eVecs[0], lp->dispDir[id], kv.data(), (int)kv.size(), partitioned) : 0;
+}
+
 // Does the OPT plan take entry `id` step by step (entry_stepwise_blocked)?  A length past the nearest neighbour of a partitioned
 // direction; for two-sided loops also every entry the two-sided matrix-pipe tile does not take (lengths > 8, a partitioned x axis, no
 // tile geometry).  (The driver builds the axial gauge itself where the lengths do not start at 1: gaugeGiven.)
@@ -371,7 +411,7 @@ static bool entry_stepwise(const MugiqHipLoop *lp, int id) {
   if (!lp->twoSided) return false;
   std::vector<int> kv;
   for (int k = lp->dispStart[id]; k <= lp->dispStop[id]; k++) kv.push_back(k);
-  return !mfma_tile_applicable(lp->eVecs[0], dir, kv.data(), (int)kv.size(), part ? 1 : 0, true, true);
+  return !entry_tile_allowed(lp, id) || !mfma_tile_applicable(lp->eVecs[0], dir, kv.data(), (int)kv.size(), part ? 1 : 0, true, true);
 }
 
 // The OPT plan: which entries are reflected from which (derivedFrom), and which of the computed entries along partitioned axes
@@ -421,8 +461,10 @@ static bool self_neighbour_alias(const MugiqHipLoop *lp, int dir) {
 
 static int reserve_plan_buffers(MugiqHipLoop *lp) {
   if (lp->calcType == MUGIQ_HIP_LOOP_CALC_TYPE_BASIC_KERNEL || lp->nDispEntries == 0) return MUGIQ_HIP_SUCCESS;
+  int st = check_axial_gauge(lp);
+  if (st) return st;
   std::vector<char> ahead;
-  int st = plan_opt(lp, ahead);
+  st = plan_opt(lp, ahead);
   if (st) return st;
   const size_t fieldB = (size_t)24 * lp->volumeCB * lp->cplxBytes();  // a FLOAT2 pad-0 path-link field
   bool anyAhead = false;
@@ -433,7 +475,7 @@ static int reserve_plan_buffers(MugiqHipLoop *lp) {
     {  // the entry's axial gauge (csrc/fused_mfma.hip), where that tile takes the entry
       std::vector<int> kv;
       for (int k = lp->dispStart[id]; k <= lp->dispStop[id]; k++) kv.push_back(k);
-      gb = axial_gauge_bytes(lp->eVecs[0], lp->dispDir[id], kv.data(), (int)kv.size(), 1);
+      gb = entry_gauge_bytes(lp, id, kv, 1);
     }
     if (!(gb && axial_gauge_from_links_possible(lp->eVecs[0], lp->gauge, lp->dispStop[id], lp->dispDir[id], lp->dispSign[id]))) {
       // (prepare_halo: the gauge from the extended gauge field where its border reaches far enough -- then no link fields)
@@ -454,7 +496,7 @@ static int reserve_plan_buffers(MugiqHipLoop *lp) {
         std::vector<int> kv;
         for (int k = lp->dispStart[id]; k <= lp->dispStop[id]; k++) kv.push_back(k);
         const bool direct = axial_gauge_from_links_possible(lp->eVecs[0], lp->gauge, lp->dispStop[id], lp->dispDir[id], lp->dispSign[id]);
-        const size_t gb = direct ? axial_gauge_bytes(lp->eVecs[0], lp->dispDir[id], kv.data(), (int)kv.size(), 0) : 0;
+        const size_t gb = direct ? entry_gauge_bytes(lp, id, kv, 0) : 0;
         if (gb) {  // (entry_fused: the gauge straight from the gauge field, no link fields)
           if ((st = pool_reserve(lp, gb))) return st;
         } else {
@@ -491,7 +533,7 @@ static int prepare_halo(MugiqHipLoop *lp, int id) {
   {  // the entry is launched once for its interior tiles and once per halo block for its boundary tiles: one gauge for all of them
     std::vector<int> kv;
     for (int k = lp->dispStart[id]; k <= lp->dispStop[id]; k++) kv.push_back(k);
-    const size_t gb = axial_gauge_bytes(lp->eVecs[0], lp->dispDir[id], kv.data(), (int)kv.size(), 1);
+    const size_t gb = entry_gauge_bytes(lp, id, kv, 1);
     h.axialGauge = nullptr;
     h.E.clear();
     if (gb && axial_gauge_from_links_possible(lp->eVecs[0], lp->gauge, lp->dispStop[id], lp->dispDir[id], lp->dispSign[id])) {
@@ -608,6 +650,10 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) 
       if (*k >= 0) lp->entryKernel[id] = *k;
     }
   } kernelRecord{lp, id, &kernel};
+  struct VerdictScope {  // the fused calls below take the tile only if the pre-pass allowed it (cleared on every way out)
+    explicit VerdictScope(bool allowed) { set_axial_tile_verdict(allowed ? 1 : 0); }
+    ~VerdictScope() { set_axial_tile_verdict(-1); }
+  } verdictScope(entry_tile_allowed(lp, id));
   std::vector<MugiqHipSpinorField> Elocal;
   const bool ahead = part && lp->halo[id].posted;
   std::vector<int> kv;
@@ -617,7 +663,7 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) 
   // (MUGIQ_HIP_GAUGE_FROM_LINKS = 0: build them and the gauge from them, as for the partitioned directions)
   void *directGauge = nullptr;
   if (!part && axial_gauge_from_links_possible(lp->eVecs[0], lp->gauge, stop, dir, sign)) {
-    const size_t gb = axial_gauge_bytes(lp->eVecs[0], dir, kv.data(), (int)kv.size(), 0);
+    const size_t gb = entry_gauge_bytes(lp, id, kv, 0);
     if (gb) {
       if ((st = scratch_alloc(lp, &directGauge, gb, false))) return st;
       if ((st = build_axial_gauge_from_links(directGauge, lp->eVecs[0], lp->gauge, stop, dir, sign, lp->stream))) return st;
@@ -677,7 +723,7 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) 
     set_axial_gauge_hint(directGauge, links[0], dir, sign, stop);
     gaugeScope.on = true;
   } else if (start > 1) {
-    const size_t gb = axial_gauge_bytes(lp->eVecs[0], dir, kv.data(), (int)kv.size(), part ? 1 : 0);
+    const size_t gb = entry_gauge_bytes(lp, id, kv, part ? 1 : 0);
     if (gb) {
       void *G = nullptr;
       std::vector<const void *> lk;
@@ -1328,6 +1374,11 @@ int mugiq_hip_loop_compute(MugiqHipLoop *lp) {
     }
   } else {
     lp->halo.resize(lp->nDispEntries);
+    if (lp->nDispEntries > 0) {
+      const int ph = phase_begin(lp, MUGIQ_HIP_PHASE_AXIAL_CHECK, -1, lp->stream);
+      if ((st = check_axial_gauge(lp))) return st;
+      phase_end(lp, ph, lp->stream);
+    }
     std::vector<char> ahead;
     if ((st = plan_opt(lp, ahead))) return st;
     bool any = false;
@@ -1493,7 +1544,7 @@ int mugiq_hip_loop_compute(MugiqHipLoop *lp) {
   if (postHalos && earlyEntry >= 0 && lp->dispDir[earlyEntry] == 0 && lp->loopPrecision == lp->precision && !lp->twoSided) {  // (two-sided: pack kernels)
     std::vector<int> kv;
     for (int k = lp->dispStart[earlyEntry]; k <= lp->dispStop[earlyEntry]; k++) kv.push_back(k);
-    const int room = entry_pack_capacity(lp->eVecs[0], kv.data(), (int)kv.size());
+    const int room = entry_tile_allowed(lp, earlyEntry) ? entry_pack_capacity(lp->eVecs[0], kv.data(), (int)kv.size()) : 0;
     if (room > 0 && !(st = prepare_halos())) {
       for (int id = 0; id < lp->nDispEntries && (int)packTargets.size() < room; id++) {
         MugiqHipLoop::HaloPost &h = lp->halo[id];
