@@ -275,33 +275,31 @@ int tile_entry(void *loop_d, const MugiqHipSpinorField *ev, const double *sigma,
 template <typename F, typename A, int ORDER>
 static int fused_entry(void *loop_d, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
                        const int *kvals, int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers,
-                       int region, hipStream_t stream, void *ultra_d, int *carried, const MugiqHipSpinorField *evL, int *kernel) {
+                       int region, hipStream_t stream, void *ultra_d, int *carried, const MugiqHipSpinorField *evL, int *kernel,
+                       const FusedEntryPlan *plan) {
   if (carried) *carried = 0;
   {
+    const FusedEntryPlan p = plan ? *plan : FusedEntryPlan{};
     int kmax = 0;
     for (int i = 0; i < nK; i++) kmax = kvals[i] > kmax ? kvals[i] : kmax;
     // (every storage type: the tile converts on the way into LDS and works in double; float slots are rounded once, on the way out)
-    const bool hinted = axial_gauge_hint_matches(E_d[0], dir, sign, kmax);
-    const int verdict = axial_tile_verdict();
-    bool tile = verdict != 0 && mfma_tile_applicable(ev[0], dir, kvals, nK, partitioned, hinted, evL != nullptr);
-    // the link fields of a hinted call are the gauge buffer: no other kernel may read them (the driver decides before it builds one)
-    if (hinted && !tile)
-      return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "fused contraction: an axial gauge stands in for the links of direction %d, but the "
+    const void *gauge = p.axialGauge;
+    bool tile = p.tile != 0 && mfma_tile_applicable(ev[0], dir, kvals, nK, partitioned, gauge != nullptr, evL != nullptr);
+    // a call with the caller's gauge may come without link fields: no other kernel may take it (the driver decides before it builds one)
+    if (gauge && !tile)
+      return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "fused contraction: an axial gauge was built for direction %d, but the "
                        "matrix-pipe tile does not take the entry (internal)", dir);
-    void *checkedGauge = nullptr;
-    if (tile && verdict < 0 && !hinted) {  // free call: the tile only where the gauge of these links is unitary
+    if (tile && p.tile < 0 && !gauge) {  // free call: the tile only where the gauge of these links is unitary (and then on that gauge)
+      void *checkedGauge = nullptr;
       double dev = 0.0;
       if (int st = build_axial_gauge_checked(&checkedGauge, &dev, ev[0], E_d, kmax, dir, sign, stream)) return st;
       tile = dev <= axial_gauge_tolerance(ev[0].precision);
+      gauge = checkedGauge;
     }
     if (tile) {
       *kernel = dir == 0 ? MUGIQ_HIP_ENTRY_KERNEL_MFMA_ROW : MUGIQ_HIP_ENTRY_KERNEL_MFMA_COLUMN;
-      if (!checkedGauge)
-        return mfma_tile_entry(loop_d, (int)sizeof(A), ev, sigma, nVec, E_d, kvals, nK, dir, sign, partitioned, ghost_d, layers, region, stream, ultra_d, carried, evL);
-      set_axial_gauge_hint(checkedGauge, E_d[0], dir, sign, kmax);  // (the gauge just built and checked; no second build)
-      const int st = mfma_tile_entry(loop_d, (int)sizeof(A), ev, sigma, nVec, E_d, kvals, nK, dir, sign, partitioned, ghost_d, layers, region, stream, ultra_d, carried, evL);
-      set_axial_gauge_hint(nullptr, nullptr, -1, -1, 0);
-      return st;
+      return mfma_tile_entry(loop_d, (int)sizeof(A), ev, sigma, nVec, E_d, kvals, nK, dir, sign, partitioned, ghost_d, layers, region, stream,
+                             ultra_d, carried, evL, gauge, p.pack, p.nPack, p.packed);
     }
     if (evL)  // (no two-sided form of the vector tiles or of the streaming kernel)
       return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "mugiq_hip_displaced_loop_contraction_fused_two_sided: the matrix-pipe tile does not take this entry "
@@ -414,7 +412,7 @@ int mugiq_hip_pack_face_layers(void *faces_d, const MugiqHipSpinorField *eVecs_h
 int mugiq::fused_contraction(void *loopData_d, int loopPrecision, const MugiqHipSpinorField *eVecL_h, const MugiqHipSpinorField *eVecs_h,
                              const double *sigma_h, int nVec, const void *const *pathLinkFields_h, const int *kValues_h, int nK, int dispDir,
                              int dispSign, const int commDim[4], const void *ghostLayers_d, int layers, int region, void *ultraLocalSlot_d,
-                             int *carried, void *stream, int *kernel) {
+                             int *carried, void *stream, int *kernel, const FusedEntryPlan *plan) {
   if (int dbg_ = mugiq::debug_poison_lds_if_asked(static_cast<hipStream_t>(stream))) return dbg_;
   if (carried) *carried = 0;
   int kernelDummy = 0;
@@ -424,7 +422,8 @@ int mugiq::fused_contraction(void *loopData_d, int loopPrecision, const MugiqHip
                 "%s: invalid region %d", who, region);
   MUGIQ_REQUIRE((region & ~(0xff | MUGIQ_HIP_REGION_OVERWRITE)) == 0, "%s: invalid region flags %d", who, region);
   MUGIQ_REQUIRE(ultraLocalSlot_d == nullptr || carried != nullptr, "%s: ultraLocalSlot_d given without `carried` (the caller could not tell whether the slot was produced)", who);
-  MUGIQ_REQUIRE(loopData_d && eVecs_h && sigma_h && pathLinkFields_h && kValues_h, "%s: NULL argument", who);
+  const bool gaugeGiven = plan && plan->axialGauge;  // (the driver's gauge: the link fields are not read)
+  MUGIQ_REQUIRE(loopData_d && eVecs_h && sigma_h && (pathLinkFields_h || gaugeGiven) && kValues_h, "%s: NULL argument", who);
   MUGIQ_REQUIRE(nVec >= 1 && nK >= 1, "%s: nVec = %d, nK = %d must be >= 1", who, nVec, nK);
   MUGIQ_REQUIRE(dispDir >= 0 && dispDir < 4 && (dispSign == 0 || dispSign == 1), "%s: Got invalid dispDir and/or dispSign.", who);
   for (int n = 0; n < nVec; n++) {
@@ -441,7 +440,7 @@ int mugiq::fused_contraction(void *loopData_d, int loopPrecision, const MugiqHip
   int kmax = 0;
   for (int i = 0; i < nK; i++) {
     MUGIQ_REQUIRE(kValues_h[i] >= 1, "%s: displacement length %d must be >= 1", who, kValues_h[i]);
-    MUGIQ_REQUIRE(pathLinkFields_h[i] != nullptr, "%s: pathLinkFields_h[%d] is NULL", who, i);
+    MUGIQ_REQUIRE(gaugeGiven || pathLinkFields_h[i] != nullptr, "%s: pathLinkFields_h[%d] is NULL", who, i);
     if (kValues_h[i] > kmax) kmax = kValues_h[i];
   }
   if (part && (region & 0xff) != MUGIQ_HIP_REGION_INTERIOR) {
@@ -457,7 +456,7 @@ int mugiq::fused_contraction(void *loopData_d, int loopPrecision, const MugiqHip
                 "%s: loop precision %d with field precision %d is not supported", who, loopPrecision, p);
 #define MUGIQ_FUSED_GO(F, A, O)                                                                                                 \
   return fused_entry<F, A, O>(loopData_d, eVecs_h, sigma_h, nVec, pathLinkFields_h, kValues_h, nK, dispDir, dispSign, part,   \
-                              ghostLayers_d, layers, region, s, ultraLocalSlot_d, carried, eVecL_h, kernel)
+                              ghostLayers_d, layers, region, s, ultraLocalSlot_d, carried, eVecL_h, kernel, plan)
   if (p == 8 && o == 2) MUGIQ_FUSED_GO(double, double, 2);
   if (p == 8 && o == 4) MUGIQ_FUSED_GO(double, double, 4);
   if (loopPrecision == 8 && o == 2) MUGIQ_FUSED_GO(float, double, 2);
@@ -475,7 +474,7 @@ int mugiq_hip_displaced_loop_contraction_fused_carry(void *loopData_d, int loopP
                                                      const int commDim[4], const void *ghostLayers_d, int layers, int region,
                                                      void *ultraLocalSlot_d, int *carried, void *stream) {
   return fused_contraction(loopData_d, loopPrecision, nullptr, eVecs_h, sigma_h, nVec, pathLinkFields_h, kValues_h, nK, dispDir, dispSign, commDim,
-                           ghostLayers_d, layers, region, ultraLocalSlot_d, carried, stream, nullptr);
+                           ghostLayers_d, layers, region, ultraLocalSlot_d, carried, stream, nullptr, nullptr);
 }
 
 int mugiq_hip_displaced_loop_contraction_fused_two_sided(void *loopData_d, int loopPrecision, const MugiqHipSpinorField *eVecL_h,
@@ -486,7 +485,7 @@ int mugiq_hip_displaced_loop_contraction_fused_two_sided(void *loopData_d, int l
   if (carried) *carried = 0;
   MUGIQ_REQUIRE(eVecL_h != nullptr, "mugiq_hip_displaced_loop_contraction_fused_two_sided: NULL argument");
   return fused_contraction(loopData_d, loopPrecision, eVecL_h, eVecR_h, sigma_h, nVec, pathLinkFields_h, kValues_h, nK, dispDir, dispSign, commDim,
-                           ghostLayers_d, layers, region, ultraLocalSlot_d, carried, stream, nullptr);
+                           ghostLayers_d, layers, region, ultraLocalSlot_d, carried, stream, nullptr, nullptr);
 }
 
 int mugiq_hip_displaced_loop_contraction_fused_region(void *loopData_d, int loopPrecision, const MugiqHipSpinorField *eVecs_h,

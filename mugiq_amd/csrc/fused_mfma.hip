@@ -318,26 +318,8 @@ static int launch_mfma_tile(const MTileArgs &a, int precision, int order, int di
   return launch_mfma_tile_f4(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
 }
 
-namespace {
-struct AxialHint {
-  const void *G = nullptr, *E1 = nullptr;
-  int dir = -1, sign = -1, kmax = 0;
-};
-thread_local AxialHint g_hint;
-}  // namespace
-
-namespace {
-struct PackHint {
-  int n = 0;
-  bool taken = false;
-  EntryPackTarget t[kMT_MaxPack];
-};
-thread_local PackHint g_pack;
-}  // namespace
-
-// Face layers the next mu = x entry of this host thread writes on its way through the eigenvectors (see MTileArgs::pack).
-// entry_pack_capacity: how many targets such an entry can take (0: it cannot -- not the row tile, or rows of a workgroup would
-// straddle a z / t coordinate); entry_pack_taken: did the entry launched since the last set_entry_pack_hint do it?
+// Face layers a mu = x entry writes on its way through the eigenvectors (see MTileArgs::pack).  entry_pack_capacity: how many
+// targets such an entry can take (0: it cannot -- not the row tile, or rows of a workgroup would straddle a z / t coordinate)
 int entry_pack_capacity(const MugiqHipSpinorField &ev, const int *kvals, int nK) {
   if (const char *e = getenv("MUGIQ_HIP_PACK_IN_ENTRY"))
     if (atoi(e) == 0) return 0;
@@ -348,33 +330,10 @@ int entry_pack_capacity(const MugiqHipSpinorField &ev, const int *kvals, int nK)
   if ((int64_t)ev.X[1] * (ev.X[0] / 2) >= (1 << 20)) return 0;  // (face entry within its (z | t) slice: 20 bits in the kernel)
   return kMT_MaxPack;
 }
-void set_entry_pack_hint(const EntryPackTarget *targets, int n) {
-  g_pack.n = targets ? std::min(n, kMT_MaxPack) : 0;
-  g_pack.taken = false;
-  for (int i = 0; i < g_pack.n; i++) g_pack.t[i] = targets[i];
-}
-bool entry_pack_taken() { return g_pack.taken; }
-
-namespace {
-thread_local int g_verdict = -1;
-}  // namespace
-void set_axial_tile_verdict(int allowed) { g_verdict = allowed; }
-int axial_tile_verdict() { return g_verdict; }
-
-void set_axial_gauge_hint(const void *G_d, const void *E1_d, int dir, int sign, int kmax) {
-  g_hint.G = G_d;
-  g_hint.E1 = E1_d;
-  g_hint.dir = dir;
-  g_hint.sign = sign;
-  g_hint.kmax = kmax;
-}
 
 size_t axial_gauge_bytes(const MugiqHipSpinorField &ev, int dir, const int *kvals, int nK, int partitioned) {
   if (!mfma_tile_applicable(ev, dir, kvals, nK, partitioned, true)) return 0;
   return (size_t)9 * (ev.X[dir] + kvals[nK - 1]) * (size_t)(2 * ev.volumeCB / ev.X[dir]) * sizeof(Cplx<double>);
-}
-bool axial_gauge_hint_matches(const void *E0_d, int dir, int sign, int kmax) {
-  return g_hint.G && g_hint.E1 == E0_d && g_hint.dir == dir && g_hint.sign == sign && g_hint.kmax == kmax;
 }
 
 template <typename F>
@@ -582,7 +541,9 @@ int build_axial_gauge_from_links(void *G_d, const MugiqHipSpinorField &ev, const
 // and ev the right (displaced) one
 int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
                     const int *kvals, int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers, int region,
-                    hipStream_t stream, void *ultra_d, int *carried, const MugiqHipSpinorField *evL) {
+                    hipStream_t stream, void *ultra_d, int *carried, const MugiqHipSpinorField *evL, const void *G_d,
+                    const EntryPackTarget *pack, int nPack, bool *packed) {
+  MUGIQ_REQUIRE(nPack <= kMT_MaxPack && (nPack == 0 || packed), "mfma tile: %d pack targets (internal)", nPack);
   const bool two = evL != nullptr;
   const size_t ptr_bytes = sizeof(void *) * (size_t)nVec * (two ? 2 : 1);
   std::vector<unsigned char> host(ptr_bytes + sizeof(double) * (size_t)nVec);
@@ -639,10 +600,10 @@ int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *
   region &= 0xff;
   if (region != MUGIQ_HIP_REGION_ALL) ultra_d = nullptr;
   a.kmaxG = kvals[nK - 1];  // (mfma_tile_applicable: ascending; 1 .. nK unless the caller's gauge is at hand)
-  // the axial gauge of this (direction, sign): the caller's, if it has built one from these links; else rebuilt into the stream's
-  // workspace (one pass over W_1)
-  if (axial_gauge_hint_matches(E_d[0], dir, sign, a.kmaxG)) {
-    a.G = static_cast<const Cplx<double> *>(g_hint.G);
+  // the axial gauge of this (direction, sign): the caller's, if it has built one; else rebuilt into the stream's workspace (one
+  // pass over W_1)
+  if (G_d) {
+    a.G = static_cast<const Cplx<double> *>(G_d);
   } else {
     MUGIQ_REQUIRE(a.kmaxG == nK, "mfma tile: lengths %d .. %d without the caller's axial gauge (internal)", kvals[0], a.kmaxG);
     void *gbuf = nullptr;
@@ -682,19 +643,19 @@ int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *
     // region 0: everything | 1: tiles whose shifted reads stay inside the local lattice | 2: tiles that read ghost layers
     // (the split is by the ENTRY's longest length, so that the interior and the boundary launch of a slot cover complementary tiles)
     a.nPack = 0;
-    if (!two && dir == 0 && first == 0 && g_pack.n > 0 && !g_pack.taken && ev[0].X[1] % a.rowsPerTile == 0) {  // the first launch of the entry packs
-      a.nPack = g_pack.n;
-      for (int i = 0; i < g_pack.n; i++) {
-        const int fcb = ev[0].volumeCB / ev[0].X[g_pack.t[i].dim];
-        a.pack[i].base = static_cast<Cplx<double> *>(g_pack.t[i].out_d);
-        a.pack[i].dim = g_pack.t[i].dim;
-        a.pack[i].high = g_pack.t[i].high;
-        a.pack[i].layers = g_pack.t[i].layers;
-        a.pack[i].from = g_pack.t[i].fromVec;
+    if (!two && dir == 0 && first == 0 && nPack > 0 && !*packed && ev[0].X[1] % a.rowsPerTile == 0) {  // the first launch of the entry packs
+      a.nPack = nPack;
+      for (int i = 0; i < nPack; i++) {
+        const int fcb = ev[0].volumeCB / ev[0].X[pack[i].dim];
+        a.pack[i].base = static_cast<Cplx<double> *>(pack[i].out_d);
+        a.pack[i].dim = pack[i].dim;
+        a.pack[i].high = pack[i].high;
+        a.pack[i].layers = pack[i].layers;
+        a.pack[i].from = pack[i].fromVec;
         a.pack[i].faceCB = fcb;
-        a.pack[i].vecStride = (int64_t)g_pack.t[i].layers * 24 * fcb;
+        a.pack[i].vecStride = (int64_t)pack[i].layers * 24 * fcb;
       }
-      g_pack.taken = true;
+      *packed = true;
     }
     a.jtBegin = 0;
     a.jtCount = nJTL;

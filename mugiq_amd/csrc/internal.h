@@ -40,17 +40,16 @@ int fill_identity_links(const MugiqHipSpinorField *f, hipStream_t stream);  // d
 // MUGIQ_HIP_DEBUG_POISON_LDS=1 (test aid): every compute entry point of the C ABI first overwrites the LDS of all CUs with NaN bit
 // patterns (mugiq_hip_debug_poison_lds), so that a kernel reading a cell it never wrote shows it in its result.
 int debug_poison_lds_if_asked(hipStream_t stream);
-// csrc/fused_mfma.hip.  The axial gauge of a (direction, sign) is rebuilt by every launch of the matrix-pipe tile (one pass over
-// W_1, 0.2 ms) -- unless the caller, who launches the same entry several times (the driver: interior tiles, then the boundary tiles
-// block by block), has built it once and says so: axial_gauge_bytes = 0 where that tile does not apply; the hint is per host
-// thread, names the W_1 field it was built from, and is cleared with G_d = NULL.
+// csrc/fused_mfma.hip.  The axial gauge of a (direction, sign) is rebuilt by every call of the matrix-pipe tile (one pass over
+// W_1, 0.2 ms) -- unless the caller, who calls the same entry several times (the driver: interior tiles, then the boundary tiles
+// block by block), has built it once and hands it over (FusedEntryPlan::axialGauge): axial_gauge_bytes = 0 where that tile does
+// not apply.
 size_t axial_gauge_bytes(const MugiqHipSpinorField &ev, int dir, const int *kvals, int nK, int partitioned);
 int build_axial_gauge(void *G_d, const MugiqHipSpinorField &ev, const void *const *E_d, int kmax, int dir, int sign, hipStream_t stream);
 // ... straight from the gauge field (no path-link fields needed at all): along a direction that is not partitioned, or as far as the border
 // of the extended field reaches along a partitioned one
 bool axial_gauge_from_links_possible(const MugiqHipSpinorField &ev, const MugiqHipGaugeField &U, int kmax, int dir, int sign);
 int build_axial_gauge_from_links(void *G_d, const MugiqHipSpinorField &ev, const MugiqHipGaugeField &U, int kmax, int dir, int sign, hipStream_t stream);
-void set_axial_gauge_hint(const void *G_d, const void *E1_d, int dir, int sign, int kmax);
 // The tile is exact only where g^dag g = 1.  axial_gauge_tolerance: the largest deviation max |g^dag g - 1| it is taken with
 // (per storage precision).  axial_line_deviation: the driver's pre-pass, D[mu] over the lines of the local gauge field out to reach[mu]
 // positions past both ends (reach 0: D = 0, not looked at); blocks the host once.  build_axial_gauge_checked: the free fused call's
@@ -59,16 +58,11 @@ double axial_gauge_tolerance(int precision);
 int axial_line_deviation(double D[4], const MugiqHipGaugeField &U, const int reach[4], const int partitioned[4], hipStream_t stream);
 int build_axial_gauge_checked(void **G_out, double *deviation, const MugiqHipSpinorField &ev, const void *const *E_d, int kmax, int dir, int sign,
                               hipStream_t stream);
-// The driver's tile decision for the fused calls it makes (per host thread, like the hint): 1 the tile may be taken (the pre-pass passed),
-// 0 it may not (the vector tiles take the entry), -1 no decision (a free call: fused_entry checks the gauge of W_1 .. W_kmax itself)
-void set_axial_tile_verdict(int allowed);
-int axial_tile_verdict();
-bool axial_gauge_hint_matches(const void *E0_d, int dir, int sign, int kmax);  // E0_d: the first link field of the call
 
 // Face layers packed by a mu = x entry on its way through the eigenvectors (csrc/fused_mfma.hip, row tile): the driver hands the
 // targets of the halos it is about to post to the entry that runs first, instead of launching mugiq_hip_pack_face_layers beside it
-// (the pack kernels and a tile kernel that fills every CU's registers and LDS take turns, they do not overlap).  Per host thread,
-// like the axial-gauge hint.  Layout of out_d: [nVec][layers][parity][12][faceCB], what mugiq_hip_pack_face_layers writes.
+// (the pack kernels and a tile kernel that fills every CU's registers and LDS take turns, they do not overlap).
+// Layout of out_d: [nVec][layers][parity][12][faceCB], what mugiq_hip_pack_face_layers writes.
 struct EntryPackTarget {
   void *out_d;
   int dim;     // 2 | 3
@@ -76,26 +70,36 @@ struct EntryPackTarget {
   int layers;
   int fromVec;  // eigenvectors fromVec .. nVec - 1 (the ones before went out packed by mugiq_hip_pack_face_layers)
 };
+// What the driver tells the fused calls of one entry that the public C call cannot express (NULL plan: a free call)
+struct FusedEntryPlan {
+  int tile = -1;                     // 1 the tile may be taken (the driver's pre-pass passed), 0 it may not (the vector tiles take the entry),
+                                     // -1 no decision (a free call: fused_entry checks the gauge of W_1 .. W_kmax itself)
+  const void *axialGauge = nullptr;  // the gauge the caller built for (dir, sign, kmax of the call): the tile must take the call, and the
+                                     // link fields are not read (pathLinkFields_h may be NULL)
+  const EntryPackTarget *pack = nullptr;  // face layers for the first launch of the row tile to write (at most entry_pack_capacity)
+  int nPack = 0;
+  bool *packed = nullptr;  // with pack: set once a launch has taken the targets (later calls of the entry leave them alone)
+};
 // The matrix-pipe tile (fourth generation, any storage type, ascending lengths up to 8).  two: the two-sided tile (left set evL != NULL
-// in mfma_tile_entry; no 12-position column tile, 8-wave row tile only)
+// in mfma_tile_entry; no 12-position column tile, 8-wave row tile only).  G_d: the axial gauge of the call (NULL: built here from
+// E_d); pack / nPack / packed: as in FusedEntryPlan
 bool mfma_tile_applicable(const MugiqHipSpinorField &ev, int dir, const int *kvals, int nK, int partitioned, bool gaugeGiven, bool two = false);
 int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
                     const int *kvals, int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers, int region,
-                    hipStream_t stream, void *ultra_d, int *carried, const MugiqHipSpinorField *evL = nullptr);
+                    hipStream_t stream, void *ultra_d, int *carried, const MugiqHipSpinorField *evL, const void *G_d,
+                    const EntryPackTarget *pack, int nPack, bool *packed);
 // csrc/fused.hip: what mugiq_hip_displaced_loop_contraction_fused_carry (eVecL_h = NULL) and ..._fused_two_sided do, and which kernel
 // did it (*kernel = MUGIQ_HIP_ENTRY_KERNEL_*; may be NULL).  The two-sided form runs on the matrix-pipe tile only: where that does not
 // apply it fails with MUGIQ_HIP_ERROR_UNSUPPORTED (the driver checks mfma_tile_applicable first and takes the step-by-step sequence)
 int fused_contraction(void *loopData_d, int loopPrecision, const MugiqHipSpinorField *eVecL_h, const MugiqHipSpinorField *eVecR_h,
                       const double *sigma_h, int nVec, const void *const *pathLinkFields_h, const int *kValues_h, int nK, int dispDir,
                       int dispSign, const int commDim[4], const void *ghostLayers_d, int layers, int region, void *ultraLocalSlot_d,
-                      int *carried, void *stream, int *kernel);
+                      int *carried, void *stream, int *kernel, const FusedEntryPlan *plan);
 // csrc/deflate.hip: mugiq_hip_deflate_low_modes with the caller's name in the messages (mugiq_hip_loop_deflate passes the loop's set)
 int deflate_low_modes(const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int nVec, const MugiqHipSpinorField *ev,
                       const double *sigma, int nEv, int gamma5, double *overlaps_h, const MugiqHipComm *comm, hipStream_t stream,
                       const char *who);
 int entry_pack_capacity(const MugiqHipSpinorField &ev, const int *kvals, int nK);
-void set_entry_pack_hint(const EntryPackTarget *targets, int n);  // (NULL, 0) clears it
-bool entry_pack_taken();
 }  // namespace mugiq
 #include <vector>
 namespace mugiq {

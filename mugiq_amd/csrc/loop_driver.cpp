@@ -401,6 +401,36 @@ static size_t entry_gauge_bytes(const MugiqHipLoop *lp, int id, const std::vecto
   return entry_tile_allowed(lp, id) ? axial_gauge_bytes(lp->eVecs[0], lp->dispDir[id], kv.data(), (int)kv.size(), partitioned) : 0;
 }
 
+// The links of entry `id` for its fused calls: its axial gauge *G (csrc/fused_mfma.hip; NULL: none built here) and the path-link fields
+// W_0 .. W_stop in E (empty: not needed).  ahead: the entry's halo is posted (prepare_halo); the pool reservation of
+// reserve_plan_buffers follows these conditions.
+static int build_entry_links(MugiqHipLoop *lp, int id, bool ahead, void **G, std::vector<MugiqHipSpinorField> &E) {
+  const int dir = lp->dispDir[id], sign = lp->dispSign[id], stop = lp->dispStop[id];
+  const bool part = lp->commDim[dir] != 0;
+  std::vector<int> kv;
+  for (int k = lp->dispStart[id]; k <= stop; k++) kv.push_back(k);
+  const size_t gb = entry_gauge_bytes(lp, id, kv, part ? 1 : 0);
+  *G = nullptr;
+  E.clear();
+  int st;
+  // Straight from the gauge field (W_1 = U_mu, the continued positions are the wrapped sites -- or, along a partitioned direction, the
+  // neighbour's links in the border of the extended field): no path-link fields, and none of their face exchanges.  (A partitioned
+  // entry whose halo is not posted ahead builds them all the same; MUGIQ_HIP_GAUGE_FROM_LINKS = 0: every entry does.)
+  if (gb && (ahead || !part) && axial_gauge_from_links_possible(lp->eVecs[0], lp->gauge, stop, dir, sign)) {
+    if ((st = scratch_alloc(lp, G, gb, false))) return st;
+    return build_axial_gauge_from_links(*G, lp->eVecs[0], lp->gauge, stop, dir, sign, lp->stream);
+  }
+  if ((st = build_path_links(lp, id, E))) return st;  // compute stream: the entry's kernels read them there
+  // ... else from W_1 .. W_stop: once for all launches of a posted entry (interior tiles, then the boundary tiles block by block), and
+  // where the lengths do not start at 1 ("-x:3": the links of the call, W_start .. W_stop, do not hold W_1).  Otherwise every fused
+  // call builds its own from its links.
+  if (!gb || !(ahead || lp->dispStart[id] > 1)) return MUGIQ_HIP_SUCCESS;
+  std::vector<const void *> lk;
+  for (int k = 1; k <= stop; k++) lk.push_back(E[k].data);
+  if ((st = scratch_alloc(lp, G, gb, false))) return st;
+  return build_axial_gauge(*G, lp->eVecs[0], lk.data(), stop, dir, sign, lp->stream);
+}
+
 // Does the OPT plan take entry `id` step by step (entry_stepwise_blocked)?  A length past the nearest neighbour of a partitioned
 // direction; for two-sided loops also every entry the two-sided matrix-pipe tile does not take (lengths > 8, a partitioned x axis, no
 // tile geometry).  (The driver builds the axial gauge itself where the lengths do not start at 1: gaugeGiven.)
@@ -478,7 +508,7 @@ static int reserve_plan_buffers(MugiqHipLoop *lp) {
       gb = entry_gauge_bytes(lp, id, kv, 1);
     }
     if (!(gb && axial_gauge_from_links_possible(lp->eVecs[0], lp->gauge, lp->dispStop[id], lp->dispDir[id], lp->dispSign[id]))) {
-      // (prepare_halo: the gauge from the extended gauge field where its border reaches far enough -- then no link fields)
+      // (build_entry_links: the gauge from the extended gauge field where its border reaches far enough -- then no link fields)
       for (int k = 0; k <= lp->dispStop[id]; k++)
         if ((st = pool_reserve(lp, fieldB))) return st;  // E_0 .. E_stop, held until the entry has run
       if ((st = pool_reserve(lp, faceB)) || (st = pool_reserve(lp, faceB))) return st;
@@ -497,7 +527,7 @@ static int reserve_plan_buffers(MugiqHipLoop *lp) {
         for (int k = lp->dispStart[id]; k <= lp->dispStop[id]; k++) kv.push_back(k);
         const bool direct = axial_gauge_from_links_possible(lp->eVecs[0], lp->gauge, lp->dispStop[id], lp->dispDir[id], lp->dispSign[id]);
         const size_t gb = direct ? entry_gauge_bytes(lp, id, kv, 0) : 0;
-        if (gb) {  // (entry_fused: the gauge straight from the gauge field, no link fields)
+        if (gb) {  // (build_entry_links: the gauge straight from the gauge field, no link fields)
           if ((st = pool_reserve(lp, gb))) return st;
         } else {
           for (int k = 0; k <= lp->dispStop[id]; k++)
@@ -530,26 +560,7 @@ static int prepare_halo(MugiqHipLoop *lp, int id) {
     MUGIQ_CHECK_HIP(hipEventCreateWithFlags(&h.evPacked, hipEventDisableTiming));
     MUGIQ_CHECK_HIP(hipEventCreateWithFlags(&h.evHalo, hipEventDisableTiming));
   }
-  {  // the entry is launched once for its interior tiles and once per halo block for its boundary tiles: one gauge for all of them
-    std::vector<int> kv;
-    for (int k = lp->dispStart[id]; k <= lp->dispStop[id]; k++) kv.push_back(k);
-    const size_t gb = entry_gauge_bytes(lp, id, kv, 1);
-    h.axialGauge = nullptr;
-    h.E.clear();
-    if (gb && axial_gauge_from_links_possible(lp->eVecs[0], lp->gauge, lp->dispStop[id], lp->dispDir[id], lp->dispSign[id])) {
-      // the neighbour's links of the continued positions are in the border of the extended gauge field: no path-link fields (and
-      // none of their face exchanges) for this entry
-      if ((st = scratch_alloc(lp, &h.axialGauge, gb, false))) return st;
-      if ((st = build_axial_gauge_from_links(h.axialGauge, lp->eVecs[0], lp->gauge, lp->dispStop[id], lp->dispDir[id], lp->dispSign[id], lp->stream))) return st;
-    } else if ((st = build_path_links(lp, id, h.E))) {  // compute stream: the entry's kernels read them there
-      return st;
-    } else if (gb) {
-      std::vector<const void *> lk;
-      for (int k = 1; k <= lp->dispStop[id]; k++) lk.push_back(h.E[k].data);
-      if ((st = scratch_alloc(lp, &h.axialGauge, gb, false))) return st;
-      if ((st = build_axial_gauge(h.axialGauge, lp->eVecs[0], lk.data(), lp->dispStop[id], lp->dispDir[id], lp->dispSign[id], lp->stream))) return st;
-    }
-  }
+  if ((st = build_entry_links(lp, id, true, &h.axialGauge, h.E))) return st;
   h.selfAlias = self_neighbour_alias(lp, lp->dispDir[id]);
   if ((st = scratch_alloc(lp, &h.grecv, bytes, false))) return st;
   if (h.selfAlias) h.gsend = h.grecv;
@@ -631,8 +642,9 @@ static int send_halo_block(MugiqHipLoop *lp, int b, bool grouped, int which = -1
 // ---- the fused plan -------------------------------------------------------------------------------------------
 // part_sel: 0 = the whole entry; for an entry whose halo was posted ahead 1 = the interior tiles only, 2 = the boundary tiles
 // only (the driver runs the interiors of ALL such entries before the first boundary: nothing then waits for a halo while there
-// is still work that needs none)
-static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) {
+// is still work that needs none).  pack / nPack / packed: face layers of posted halos for the entry to write (FusedEntryPlan)
+static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0, const EntryPackTarget *pack = nullptr, int nPack = 0,
+                       bool *packed = nullptr) {
   const int dir = lp->dispDir[id], sign = lp->dispSign[id];
   const bool part = lp->commDim[dir] != 0;
   const int stop = lp->dispStop[id], start = lp->dispStart[id];
@@ -650,48 +662,31 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) 
       if (*k >= 0) lp->entryKernel[id] = *k;
     }
   } kernelRecord{lp, id, &kernel};
-  struct VerdictScope {  // the fused calls below take the tile only if the pre-pass allowed it (cleared on every way out)
-    explicit VerdictScope(bool allowed) { set_axial_tile_verdict(allowed ? 1 : 0); }
-    ~VerdictScope() { set_axial_tile_verdict(-1); }
-  } verdictScope(entry_tile_allowed(lp, id));
-  std::vector<MugiqHipSpinorField> Elocal;
   const bool ahead = part && lp->halo[id].posted;
   std::vector<int> kv;
   for (int k = start; k <= stop; k++) kv.push_back(k);
-  // A direction that is not partitioned and an entry the matrix-pipe tile takes: its axial gauge comes straight from the gauge field
-  // (W_1 = U_mu, the continued positions are the wrapped sites) and the path-link fields W_1 .. W_stop are not built at all
-  // (MUGIQ_HIP_GAUGE_FROM_LINKS = 0: build them and the gauge from them, as for the partitioned directions)
-  void *directGauge = nullptr;
-  if (!part && axial_gauge_from_links_possible(lp->eVecs[0], lp->gauge, stop, dir, sign)) {
-    const size_t gb = entry_gauge_bytes(lp, id, kv, 0);
-    if (gb) {
-      if ((st = scratch_alloc(lp, &directGauge, gb, false))) return st;
-      if ((st = build_axial_gauge_from_links(directGauge, lp->eVecs[0], lp->gauge, stop, dir, sign, lp->stream))) return st;
-    }
-  }
-  if (!ahead && !directGauge && (st = build_path_links(lp, id, Elocal))) return st;
-  std::vector<MugiqHipSpinorField> &E = ahead ? lp->halo[id].E : Elocal;
-  std::vector<const void *> links;
-  // (with the gauge at hand the fused call never looks at the link fields: the gauge buffer stands in, and names the hint)
-  if (ahead && E.empty()) directGauge = lp->halo[id].axialGauge;  // (prepare_halo took the gauge from the gauge field: no link fields)
-  for (int k = start; k <= stop; k++) links.push_back(directGauge ? directGauge : E[k].data);
-  if (part && lp->halo[id].posted) {
+  // the entry's gauge and link fields: built here, or by prepare_halo when its halo was posted ahead
+  void *gauge = nullptr;
+  std::vector<MugiqHipSpinorField> Elocal;
+  if (!ahead && (st = build_entry_links(lp, id, false, &gauge, Elocal))) return st;
+  const std::vector<MugiqHipSpinorField> &E = ahead ? lp->halo[id].E : Elocal;
+  std::vector<const void *> links;  // W_start .. W_stop (none: the gauge came straight from the gauge field)
+  for (int k = start; k <= stop && !E.empty(); k++) links.push_back(E[k].data);
+  // the tile only if the pre-pass allowed it
+  const FusedEntryPlan plan{entry_tile_allowed(lp, id) ? 1 : 0, ahead ? lp->halo[id].axialGauge : gauge, pack, nPack, packed};
+  auto fused = [&](int n0, int nv, const void *ghost, int region, void *ultra, int *carried) {
+    return fused_contraction(slot0, lp->loopPrecision, evL ? evL + n0 : nullptr, &lp->eVecs[n0], &lp->sigma[n0], nv,
+                             links.empty() ? nullptr : links.data(), kv.data(), (int)kv.size(), dir, sign, lp->commDim, ghost, ghost ? stop : 0,
+                             region, ultra, carried, lp->stream, &kernel, &plan);
+  };
+  if (ahead) {
     // the halo of all eigenvectors was posted at the start of the compute: interior tiles, then (once it has landed) the
     // boundary tiles
     MugiqHipLoop::HaloPost &h = lp->halo[id];
-    struct HintScope {  // the entry's own axial gauge for the launches below (cleared on every way out)
-      HintScope(const MugiqHipLoop::HaloPost &h, const std::vector<const void *> &links, int dir, int sign, int kmax) {
-        if (h.axialGauge) set_axial_gauge_hint(h.axialGauge, links[0], dir, sign, kmax);
-      }
-      ~HintScope() { set_axial_gauge_hint(nullptr, nullptr, -1, -1, 0); }
-    } hintScope(h, links, dir, sign, stop);
     int ph;
     if (part_sel != 2) {
       ph = phase_begin(lp, MUGIQ_HIP_PHASE_ENTRY_INTERIOR, id, lp->stream);
-      if ((st = fused_contraction(slot0, lp->loopPrecision, evL, lp->eVecs.data(), lp->sigma.data(), lp->nEv, links.data(), kv.data(),
-                                  (int)kv.size(), dir, sign, lp->commDim, h.grecv, stop, MUGIQ_HIP_REGION_INTERIOR | MUGIQ_HIP_REGION_OVERWRITE,
-                                  nullptr, nullptr, lp->stream, &kernel)))
-        return st;
+      if ((st = fused(0, lp->nEv, h.grecv, MUGIQ_HIP_REGION_INTERIOR | MUGIQ_HIP_REGION_OVERWRITE, nullptr, nullptr))) return st;
       phase_end(lp, ph, lp->stream);
     }
     if (part_sel == 1) return MUGIQ_HIP_SUCCESS;
@@ -703,36 +698,12 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) 
       MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->stream, h.evBlock[b], 0));
       phase_end(lp, ph, lp->stream);
       ph = phase_begin(lp, MUGIQ_HIP_PHASE_ENTRY_BOUNDARY, id, lp->stream);
-      st = fused_contraction(slot0, lp->loopPrecision, evL ? evL + n0 : nullptr, &lp->eVecs[n0], &lp->sigma[n0], nv, links.data(), kv.data(),
-                             (int)kv.size(), dir, sign, lp->commDim, static_cast<char *>(h.grecv) + perVec * n0, stop,
-                             MUGIQ_HIP_REGION_BOUNDARY | (b == 0 ? MUGIQ_HIP_REGION_OVERWRITE : 0), nullptr, nullptr, lp->stream, &kernel);
+      st = fused(n0, nv, static_cast<char *>(h.grecv) + perVec * n0, MUGIQ_HIP_REGION_BOUNDARY | (b == 0 ? MUGIQ_HIP_REGION_OVERWRITE : 0),
+                 nullptr, nullptr);
       phase_end(lp, ph, lp->stream);
       if (st) return st;
     }
     return MUGIQ_HIP_SUCCESS;
-  }
-  // Lengths that do not start at 1 ("-x:3"): the matrix-pipe tile cannot build its axial gauge from the links of the call (W_start ..
-  // W_stop), the driver can (it holds W_1 .. W_stop) and says so for the launches below.
-  struct GaugeScope {
-    bool on = false;
-    ~GaugeScope() {
-      if (on) set_axial_gauge_hint(nullptr, nullptr, -1, -1, 0);
-    }
-  } gaugeScope;
-  if (directGauge) {
-    set_axial_gauge_hint(directGauge, links[0], dir, sign, stop);
-    gaugeScope.on = true;
-  } else if (start > 1) {
-    const size_t gb = entry_gauge_bytes(lp, id, kv, part ? 1 : 0);
-    if (gb) {
-      void *G = nullptr;
-      std::vector<const void *> lk;
-      for (int k = 1; k <= stop; k++) lk.push_back(E[k].data);
-      if ((st = scratch_alloc(lp, &G, gb, false))) return st;
-      if ((st = build_axial_gauge(G, lp->eVecs[0], lk.data(), stop, dir, sign, lp->stream))) return st;
-      set_axial_gauge_hint(G, links[0], dir, sign, stop);
-      gaugeScope.on = true;
-    }
   }
   // eigenvector blocks: bounded by the ghost-layer buffers when the dimension is partitioned
   int nb = lp->nEv;
@@ -755,10 +726,7 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) 
       // (one block here: nb = nEv.)  The first such entry also takes the ultra-local loop along, if the kernel has room
       int carried = 0;
       void *ultra = (lp->carryUltra && !lp->ultraCarried && nb == lp->nEv) ? lp->dataPos_d : nullptr;
-      if ((st = fused_contraction(slot0, lp->loopPrecision, evL ? evL + n0 : nullptr, &lp->eVecs[n0], &lp->sigma[n0], nv, links.data(),
-                                  kv.data(), (int)kv.size(), dir, sign, lp->commDim, nullptr, 0, MUGIQ_HIP_REGION_ALL | ow, ultra, &carried,
-                                  lp->stream, &kernel)))
-        return st;
+      if ((st = fused(n0, nv, nullptr, MUGIQ_HIP_REGION_ALL | ow, ultra, &carried))) return st;
       if (carried) {
         lp->ultraCarried = true;
         lp->ultraCarrier = id;
@@ -778,19 +746,13 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0) 
     phase_end(lp, ph, lp->commStream);
     MUGIQ_CHECK_HIP(hipEventRecord(lp->evHalo, lp->commStream));
     ph = phase_begin(lp, MUGIQ_HIP_PHASE_ENTRY_INTERIOR, id, lp->stream);
-    if ((st = fused_contraction(slot0, lp->loopPrecision, evL ? evL + n0 : nullptr, &lp->eVecs[n0], &lp->sigma[n0], nv, links.data(),
-                                kv.data(), (int)kv.size(), dir, sign, lp->commDim, grecv, stop, MUGIQ_HIP_REGION_INTERIOR | ow, nullptr, nullptr,
-                                lp->stream, &kernel)))
-      return st;
+    if ((st = fused(n0, nv, grecv, MUGIQ_HIP_REGION_INTERIOR | ow, nullptr, nullptr))) return st;
     phase_end(lp, ph, lp->stream);
     ph = phase_begin(lp, MUGIQ_HIP_PHASE_HALO_WAIT, id, lp->stream);
     MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->stream, lp->evHalo, 0));
     phase_end(lp, ph, lp->stream);
     ph = phase_begin(lp, MUGIQ_HIP_PHASE_ENTRY_BOUNDARY, id, lp->stream);
-    if ((st = fused_contraction(slot0, lp->loopPrecision, evL ? evL + n0 : nullptr, &lp->eVecs[n0], &lp->sigma[n0], nv, links.data(),
-                                kv.data(), (int)kv.size(), dir, sign, lp->commDim, grecv, stop, MUGIQ_HIP_REGION_BOUNDARY | ow, nullptr, nullptr,
-                                lp->stream, &kernel)))
-      return st;
+    if ((st = fused(n0, nv, grecv, MUGIQ_HIP_REGION_BOUNDARY | ow, nullptr, nullptr))) return st;
     phase_end(lp, ph, lp->stream);
   }
   return MUGIQ_HIP_SUCCESS;
@@ -1443,7 +1405,7 @@ int mugiq_hip_loop_compute(MugiqHipLoop *lp) {
     pendingBoundary.clear();
     return MUGIQ_HIP_SUCCESS;
   };
-  auto run_one = [&](int id, bool holdScratch = false) -> int {
+  auto run_one = [&](int id, bool holdScratch = false, const std::vector<EntryPackTarget> &pack = {}, bool *packed = nullptr) -> int {
     if (id == -1 && !basic && lp->carryUltra && lp->ultraCarried) return MUGIQ_HIP_SUCCESS;  // produced by a displaced entry's pass
     if (id >= 0 && !basic && lp->momReflect && lp->derivedFrom[id] >= 0) {   // derived in momentum space; position space on request
       lp->posReflectPending = true;
@@ -1491,7 +1453,7 @@ int mugiq_hip_loop_compute(MugiqHipLoop *lp) {
       else if (split && lp->halo[id].posted) {
         st = entry_fused(lp, id, slot0, 1);  // interior tiles now; the boundary tiles once every entry's interior is through
         pendingBoundary.push_back(id);
-      } else st = entry_fused(lp, id, slot0);
+      } else st = entry_fused(lp, id, slot0, 0, pack.data(), (int)pack.size(), packed);
       // No host synchronisation between entries: every user of this entry's scratch is ordered on lp->stream (the halo
       // stream's part was waited for by the boundary kernels), so the next entry may take the buffers over at once.
       // The exception is the entry that runs BEFORE the halos are posted: the pack and halo streams start from an event
@@ -1560,10 +1522,8 @@ int mugiq_hip_loop_compute(MugiqHipLoop *lp) {
       } else {
         st = send_halo_block(lp, 0, grouped, 0);  // first blocks that are packed by their kernels: on their way before the entry starts
         if (!st) {
-          set_entry_pack_hint(packTargets.data(), (int)packTargets.size());
-          st = run_one(earlyEntry, true);
-          const bool taken = entry_pack_taken();
-          set_entry_pack_hint(nullptr, 0);
+          bool taken = false;
+          st = run_one(earlyEntry, true, packTargets, &taken);
           if (!st && taken) lp->halosPackedInEntry = (int)packTargets.size();
           if (!st && !taken) st = set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "computeCoarseLoop: entry %d was to write the face layers of the posted halos and did not (internal)", earlyEntry);
         }
