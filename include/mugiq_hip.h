@@ -37,7 +37,8 @@ typedef enum MugiqHipStatus_e {
   MUGIQ_HIP_ERROR_INVALID_ARGUMENT = 1, /* precondition the reference checks with errorQuda */
   MUGIQ_HIP_ERROR_UNSUPPORTED = 2,
   MUGIQ_HIP_ERROR_HIP = 3,              /* a HIP runtime call failed (reference: checkCudaError) */
-  MUGIQ_HIP_ERROR_NO_DEVICE = 4
+  MUGIQ_HIP_ERROR_NO_DEVICE = 4,
+  MUGIQ_HIP_ERROR_NOT_CONVERGED = 5     /* mugiq_hip_wilson_solve: maxIter reached; the outputs are filled all the same */
 } MugiqHipStatus;
 
 /* Values are those of QudaPrecision / QudaFieldOrder so an adapter can pass them through. */
@@ -484,6 +485,63 @@ int mugiq_hip_exchange_ghost_vec(const MugiqHipSpinorField *v, const MugiqHipCom
 int mugiq_hip_deflate_low_modes(const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec,
                                 const MugiqHipSpinorField *eVecs_h, const double *sigma_h, int nEv, int gamma5,
                                 double *overlaps_h, const MugiqHipComm *comm, void *stream);
+
+/* ==== the Wilson operator, the eigenpair check and a deflated CG (csrc/wilson.hip) ============================================ */
+/* MuGiqEigOperator, include/enum_mugiq.h:22-25 (values identical), plus H = g5 M, which the reference does not have */
+#define MUGIQ_HIP_EIG_OPERATOR_M 0
+#define MUGIQ_HIP_EIG_OPERATOR_MDAG 1
+#define MUGIQ_HIP_EIG_OPERATOR_MDAGM 2
+#define MUGIQ_HIP_EIG_OPERATOR_MMDAG 3
+#define MUGIQ_HIP_EIG_OPERATOR_H 4
+
+/* Stands in for QUDA's DiracM / DiracMdag / DiracMdagM / DiracMMdag on a Wilson Dirac operator, as Eigsolve_Mugiq applies it
+ * ((*mat)(w, v), lib/eigsolve_mugiq.cpp:301): dst_i = scale * A src_i, i < nVec, A one of the forms above of the UNIMPROVED Wilson
+ * operator in kappa normalisation
+ *   M psi(x) = psi(x) - kappa sum_mu [ (1 - g_mu) U_mu(x) psi(x+mu) + (1 + g_mu) U_mu^dag(x-mu) psi(x-mu) ],
+ *   g_x, g_y, g_z, g_t = Gamma_1, Gamma_2, Gamma_4, Gamma_8 of mugiq_hip_get_gamma_tables ("g1" .. "g4"), g5 = Gamma_15.
+ * No clover term, no twisted mass, no even-odd preconditioning.  Links are applied as stored (boundary phases and anisotropy are
+ * the host's business; they need not be unitary), the contract of mugiq_hip_perform_covariant_displacement_vector; the gauge
+ * precision (4 | 8) is independent of the spinors'.  `scale`: e.g. the reference's 0.25 / kappa^2 for QUDA_MASS_NORMALIZATION (:302).
+ * dst_h / src_h: nVec descriptors each, one precision, order, geometry, stride and parity offset; no dst may overlap any src.
+ * Arithmetic in the fields' precision; pads are neither read into a result nor written.
+ * comm NULL: one domain.  Otherwise commDim[d] = (comm->grid[d] > 1 || comm->partitioned[d]) as for the displacement: the off-face
+ * neighbour comes from src->ghost[d][0 | 1] (required), which this call fills itself through comm->sendrecv (one transfer group per
+ * block of 8 vectors), the link at x - mu from the border of the extended gauge field: R[d] >= 1 there, MUGIQ_HIP_ERROR_INVALID_ARGUMENT
+ * otherwise.  MdagM / MMdag are two applications with a halo exchange of the intermediate, which lives in the per-stream workspace. */
+int mugiq_hip_wilson_apply(const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec, const MugiqHipGaugeField *gauge,
+                           double kappa, int opType, double scale, const MugiqHipComm *comm, void *stream);
+
+/* Eigsolve_Mugiq::computeEvals, lib/eigsolve_mugiq.cpp:289-315, restated literally for A = the form opType of the operator above:
+ *   w = A v_n (times 0.25 / kappa^2 if massNormalization);  lambda_n = v_n^dag w / ||v_n||;  r_n = ||lambda_n v_n - w||
+ * -- the division is by ||v||, not ||v||^2, as in the reference (:303; the two agree for normalised vectors only).
+ * lambda_h[nEv] complex double (re, im), residual_h[nEv]; sigma_h[nEv] = sqrt(Re lambda) for MdagM / MMdag (:309-312), = Re lambda
+ * WITH its sign for H (what a two-sided loop needs), untouched (may be NULL) for M and Mdag.
+ * The eigenvectors (any storage) are only read, ghost zones included.  Inner products and norms in fp64, summed in a fixed order
+ * and over the ranks as mugiq_hip_deflate_low_modes does: identical on every rank, bitwise reproducible.  Work memory: 24 vectors
+ * of the eigenvectors' storage in the per-stream workspace, whatever nEv.  Blocks the host (two reads per block of 8 vectors). */
+int mugiq_hip_compute_evals(const MugiqHipSpinorField *eVecs_h, int nEv, const MugiqHipGaugeField *gauge, double kappa, int opType,
+                            int massNormalization, double *lambda_h, double *residual_h, double *sigma_h, const MugiqHipComm *comm,
+                            void *stream);
+
+/* Eigsolve_Mugiq::projectVector, lib/eigsolve_mugiq.cpp:340-348: out = sum_i v_i <v_i, in>, on the overlap and update kernels of
+ * mugiq_hip_deflate_low_modes.  out, in: fp64, one layout (the eigenvectors' order, geometry, stride, parity offset), not aliased. */
+int mugiq_hip_project_vector(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in, const MugiqHipSpinorField *eVecs_h, int nEv,
+                             const MugiqHipComm *comm, void *stream);
+
+/* Stands in for the invertQuda call the deflated recipe needs ("Two-sided loops"): x_r = M^-1 b_r, r < nVec, by CG on
+ * M^dag M x = M^dag b.  A correctness-first solver for that recipe and for tests -- plain CG in fp64, no preconditioner, two host
+ * reads per iteration -- not a rival of a multigrid solve.
+ * nEv > 0: the start vector is the low-mode part x0 = sum_n v_n sigma_n^-1 (v_n^dag g5 b) with (v_n, sigma_n) eigenpairs of
+ * H = g5 M (eigenvectors of any storage, layout as x and b); nEv = 0: x0 = 0.  Right-hand sides advance in blocks of 8 through the
+ * batched operator, each with its own scalars; a converged one is no longer touched.  Stops when ||M^dag b - M^dag M x|| <=
+ * tol ||M^dag b|| (recursive residual); iters_out[r] = iterations taken, relres_out[r] = the TRUE ||b - M x|| / ||b||, recomputed
+ * with one more application (0 for b = 0, which returns x = 0 in 0 iterations).  MUGIQ_HIP_ERROR_NOT_CONVERGED if a right-hand side
+ * reaches maxIter first: x and both outputs are filled all the same.
+ * x_h, b_h: fp64, one layout, no x overlapping any b; they need no ghost zones.  All scalars come from fixed-order fp64 sums
+ * (and the cross-rank sum of the deflation): two runs give identical bits and iteration counts.  Work memory: 32 fp64 vectors. */
+int mugiq_hip_wilson_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                           double kappa, const MugiqHipSpinorField *eVecs_h, const double *sigma_h, int nEv, double tol, int maxIter,
+                           int *iters_out, double *relres_out, const MugiqHipComm *comm, void *stream);
 
 /* What Displace asks of QUDA's ColorSpinorField for its auxiliary vector (lib/displace.cpp:26-30: ColorSpinorField::Create
  * with QUDA_ZERO_FIELD_CREATE and setPrecision(coarsePrec_); :42,:50-51: operator=; :59: blas::zero), for hosts that do not

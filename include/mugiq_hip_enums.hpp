@@ -7,6 +7,14 @@
 #define MUGIQ_INVALID_ENUM INT_MIN
 // include/enum_mugiq.h:28-97 (values identical)
 typedef enum LoopFTSign_s { LOOP_FT_SIGN_MINUS = -1, LOOP_FT_SIGN_PLUS = 1, LOOP_FT_SIGN_INVALID = MUGIQ_INVALID_ENUM } LoopFTSign;
+// include/enum_mugiq.h:22-25 (MUGIQ_HIP_EIG_OPERATOR_* of mugiq_hip.h; H = g5 M, value 4, is this library's extension and has no name here)
+typedef enum MuGiqEigOperator_s {
+  MUGIQ_EIG_OPERATOR_M,
+  MUGIQ_EIG_OPERATOR_Mdag,
+  MUGIQ_EIG_OPERATOR_MdagM,
+  MUGIQ_EIG_OPERATOR_MMdag,
+  MUGIQ_EIG_OPERATOR_INVALID = MUGIQ_INVALID_ENUM
+} MuGiqEigOperator;
 typedef enum LoopCalcType_s {
   LOOP_CALC_TYPE_BLAS,
   LOOP_CALC_TYPE_OPT_KERNEL,

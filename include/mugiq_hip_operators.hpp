@@ -95,6 +95,95 @@ inline void deflateLowModes(const std::vector<ColorSpinorField> &dst, const std:
                                     comm, stream));
 }
 
+// ---- the Wilson operator and what Eigsolve_Mugiq does with it (csrc/wilson.hip; new) -------------------------------------------
+// MuGiqEigOperator of include/enum_mugiq.h:22-25 comes from the enums header; H = g5 M is this library's extension
+constexpr int EIG_OPERATOR_H = MUGIQ_HIP_EIG_OPERATOR_H;
+// dst_i = scale * A src_i (mugiq_hip_wilson_apply): stands in for (*mat)(w, v) of lib/eigsolve_mugiq.cpp:301
+inline void wilsonApply(const std::vector<ColorSpinorField> &dst, const std::vector<ColorSpinorField> &src, const GaugeField &gauge, double kappa,
+                        int opType = MUGIQ_HIP_EIG_OPERATOR_M, double scale = 1.0, const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (src.empty() || dst.size() != src.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "wilsonApply: size mismatch");
+  check(mugiq_hip_wilson_apply(dst.data(), src.data(), (int)src.size(), &gauge, kappa, opType, scale, comm, stream));
+}
+// Eigsolve_Mugiq::computeEvals, lib/eigsolve_mugiq.cpp:289-315 (sigma: sqrt(Re lambda) for MdagM / MMdag, Re lambda for H, empty otherwise)
+inline void computeEvals(const std::vector<ColorSpinorField> &eVecs, const GaugeField &gauge, double kappa, int opType, bool massNormalization,
+                         std::vector<std::complex<double>> &lambda, std::vector<double> &residual, std::vector<double> &sigma,
+                         const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (eVecs.empty()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "computeEvals: no eigenvectors");
+  lambda.assign(eVecs.size(), std::complex<double>(0.0, 0.0));
+  residual.assign(eVecs.size(), 0.0);
+  sigma.assign(eVecs.size(), 0.0);
+  check(mugiq_hip_compute_evals(eVecs.data(), (int)eVecs.size(), &gauge, kappa, opType, massNormalization ? 1 : 0,
+                                reinterpret_cast<double *>(lambda.data()), residual.data(), sigma.data(), comm, stream));
+  if (opType == MUGIQ_HIP_EIG_OPERATOR_M || opType == MUGIQ_HIP_EIG_OPERATOR_MDAG) sigma.clear();
+}
+// Eigsolve_Mugiq::projectVector, lib/eigsolve_mugiq.cpp:340-348
+inline void projectVector(ColorSpinorField &out, ColorSpinorField &in, const std::vector<ColorSpinorField> &eVecs, const MugiqHipComm *comm = nullptr,
+                          void *stream = nullptr) {
+  if (eVecs.empty()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "projectVector: no eigenvectors");
+  check(mugiq_hip_project_vector(&out, &in, eVecs.data(), (int)eVecs.size(), comm, stream));
+}
+// x_r = M^-1 b_r by CG on the normal equations from the low-mode start (mugiq_hip_wilson_solve).  Returns false where a right-hand
+// side did not reach tol within maxIter (x, iters and relres are filled all the same); every other failure throws.
+inline bool wilsonSolve(const std::vector<ColorSpinorField> &x, const std::vector<ColorSpinorField> &b, const GaugeField &gauge, double kappa,
+                        const std::vector<ColorSpinorField> &eVecs, const std::vector<double> &sigma, double tol, int maxIter,
+                        std::vector<int> &iters, std::vector<double> &relres, const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (b.empty() || x.size() != b.size() || sigma.size() != eVecs.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "wilsonSolve: size mismatch");
+  iters.assign(b.size(), 0);
+  relres.assign(b.size(), 0.0);
+  const int st = mugiq_hip_wilson_solve(x.data(), b.data(), (int)b.size(), &gauge, kappa, eVecs.empty() ? nullptr : eVecs.data(),
+                                        eVecs.empty() ? nullptr : sigma.data(), (int)eVecs.size(), tol, maxIter, iters.data(), relres.data(), comm,
+                                        stream);
+  if (st == MUGIQ_HIP_ERROR_NOT_CONVERGED) return false;
+  check(st);
+  return true;
+}
+// The members of the reference's Eigsolve_Mugiq (include/eigsolve_mugiq.h) that work on eigenvectors somebody else computed
+class Eigsolve_Mugiq {
+public:
+  Eigsolve_Mugiq(std::vector<ColorSpinorField> eVecs, const GaugeField &gauge, double kappa, int opType, const MugiqHipComm *comm = nullptr,
+                 bool massNormalization = false, void *stream = nullptr)
+      : eVecs_(std::move(eVecs)), gauge_(gauge), kappa_(kappa), opType_(opType), comm_(comm), mass_(massNormalization), stream_(stream),
+        eVals_quda_(eVecs_.size()) {}
+  void computeEvals() { mugiq_hip::computeEvals(eVecs_, gauge_, kappa_, opType_, mass_, eVals_, evals_res_, eVals_sigma_, comm_, stream_); }
+  // lib/eigsolve_mugiq.cpp:317-337, the two line formats character for character (the interface contract of its log)
+  void printEvals(FILE *out = stdout) const {
+    if (comm_ && comm_->rank != 0) return;
+    fprintf(out, "\nEigsolve_Mugiq - Eigenvalues:\n");
+    for (size_t i = 0; i < eVals_.size(); i++)
+      fprintf(out, "Mugiq-Quda: Eval[%04d] = %+.16e %+.16e , %+.16e %+.16e , Residual = %+.16e\n", (int)i, eVals_[i].real(), eVals_[i].imag(),
+              eVals_quda_[i].real(), eVals_quda_[i].imag(), evals_res_[i]);
+    if (opType_ == MUGIQ_HIP_EIG_OPERATOR_MDAGM || opType_ == MUGIQ_HIP_EIG_OPERATOR_MMDAG) {
+      fprintf(out, "\n");
+      for (size_t i = 0; i < eVals_sigma_.size(); i++) fprintf(out, "Mugiq-Quda: Sigma[%04d] = %+.16e\n", (int)i, eVals_sigma_[i]);
+    }
+  }
+  void projectVector(ColorSpinorField &out, ColorSpinorField &in) { mugiq_hip::projectVector(out, in, eVecs_, comm_, stream_); }
+  // M^-1 b; with opType H the eigenpairs (sigma of computeEvals) deflate the start vector
+  bool solve(const std::vector<ColorSpinorField> &x, const std::vector<ColorSpinorField> &b, double tol, int maxIter, std::vector<int> &iters,
+             std::vector<double> &relres) {
+    const bool defl = opType_ == MUGIQ_HIP_EIG_OPERATOR_H && eVals_sigma_.size() == eVecs_.size();
+    static const std::vector<ColorSpinorField> none;
+    static const std::vector<double> noSigma;
+    return wilsonSolve(x, b, gauge_, kappa_, defl ? eVecs_ : none, defl ? eVals_sigma_ : noSigma, tol, maxIter, iters, relres, comm_, stream_);
+  }
+  std::vector<ColorSpinorField> &getEvecs() { return eVecs_; }
+  std::vector<std::complex<double>> *getEvals() { return &eVals_; }
+  std::vector<std::complex<double>> *getEvalsQuda() { return &eVals_quda_; }
+  std::vector<double> *getEvalsRes() { return &evals_res_; }
+  std::vector<double> *getEvalsSigma() { return &eVals_sigma_; }
+
+private:
+  std::vector<ColorSpinorField> eVecs_;
+  GaugeField gauge_;
+  double kappa_;
+  int opType_;
+  const MugiqHipComm *comm_;
+  bool mass_;
+  void *stream_;
+  std::vector<std::complex<double>> eVals_, eVals_quda_;
+  std::vector<double> evals_res_, eVals_sigma_;
+};
+
 // lib/contract_wrappers.cu:133-156
 template <typename Float>
 inline void convertIdxOrder_mapGamma(std::complex<Float> *dataPosMP_d, const std::complex<Float> *dataPos_d, int nData, int nLoop,

@@ -431,6 +431,12 @@ void computeLoop(QudaMultigridParam mgParams, QudaEigParam QudaEigParams, MugiqL
   eigsolve->computeEvecs();
   eigsolve->computeEvals();
   eigsolve->printEvals();
+  // The same check on the device, against the gauge field the LOOP will use (for an unimproved Wilson operator): a mismatch of gauge
+  // field, gamma basis, boundary phase or even-odd convention between QUDA and this library shows as residuals of order one here
+  // instead of as a silently wrong loop.  With ev = describe(*eigsolve->getEvecs()[i]) for every i and gauge = the extended field:
+  //   std::vector<double> lambda(2 * nEv), res(nEv), sigma(nEv);
+  //   mugiq_hip_compute_evals(ev.data(), nEv, &gauge, invParams->kappa, eigParams->diracType,
+  //                           invParams->mass_normalization == QUDA_MASS_NORMALIZATION, lambda.data(), res.data(), sigma.data(), &comm, stream);
   const QudaPrecision ePrec = eigsolve->getEvecs()[0]->Precision();
   if (!((ePrec == QUDA_SINGLE_PRECISION && sizeof(Float) == 4) || (ePrec == QUDA_DOUBLE_PRECISION && sizeof(Float) == 8)))
     errorQuda("Missmatch between eigenvector precision %d and templated precision %zu\n", static_cast<int>(ePrec), sizeof(Float));

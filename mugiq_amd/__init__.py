@@ -24,5 +24,9 @@ from .loop import (  # noqa: E402
 )
 from .comm import GridComm, RcclComm  # noqa: E402
 from .displace import Displace, DISPLACE_TYPE_COVARIANT  # noqa: E402
+from .eigsolve import (  # noqa: E402
+    Eigsolve_Mugiq, wilsonApply, computeEvals, projectVector, wilsonSolve, SolveInfo,
+    MUGIQ_EIG_OPERATOR_M, MUGIQ_EIG_OPERATOR_Mdag, MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H,
+)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -129,6 +129,12 @@ SIGNATURES = {
                                                                   ctypes.c_int, ctypes.c_int, _I4, _VP, ctypes.c_int, _VP]),
     "mugiq_hip_deflate_low_modes": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _SP, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int,
                                                    ctypes.POINTER(ctypes.c_double), _VP, _VP]),
+    "mugiq_hip_wilson_apply": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, ctypes.c_double, ctypes.c_int, ctypes.c_double, _VP, _VP]),
+    "mugiq_hip_compute_evals": (ctypes.c_int, [_SP, ctypes.c_int, _GP, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                               ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _VP, _VP]),
+    "mugiq_hip_project_vector": (ctypes.c_int, [_SP, _SP, _SP, ctypes.c_int, _VP, _VP]),
+    "mugiq_hip_wilson_solve": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, ctypes.c_double, _SP, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+                                              ctypes.c_double, ctypes.c_int, _I4, ctypes.POINTER(ctypes.c_double), _VP, _VP]),
     "mugiq_hip_prolongate_batched": (ctypes.c_int, [_SP, ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),
     "mugiq_hip_prolongate_contract_batched": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(CoarseDesc), ctypes.POINTER(ctypes.c_double),
                                                              ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),

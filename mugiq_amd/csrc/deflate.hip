@@ -262,6 +262,8 @@ bool same_layout(const MugiqHipSpinorField &a, const MugiqHipSpinorField &b) {
          a.X[0] == b.X[0] && a.X[1] == b.X[1] && a.X[2] == b.X[2] && a.X[3] == b.X[3];
 }
 
+}  // namespace
+
 int sum_over_ranks(const MugiqHipComm *comm, std::vector<double> &c) {
   // the order of the momentum projection (loop_driver.cpp): reduce over space, gather over time, fixed-order sum on the root, bcast
   const size_t n = c.size();
@@ -278,8 +280,6 @@ int sum_over_ranks(const MugiqHipComm *comm, std::vector<double> &c) {
   c.swap(sum);
   return MUGIQ_HIP_SUCCESS;
 }
-
-}  // namespace
 
 int deflate_low_modes(const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int nVec, const MugiqHipSpinorField *ev,
                       const double *sigma, int nEv, int gamma5, double *overlaps_h, const MugiqHipComm *comm, hipStream_t stream,

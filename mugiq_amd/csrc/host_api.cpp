@@ -28,8 +28,8 @@ int set_error(int status, const char *fmt, ...) {
 namespace {
 struct StreamArena {
   std::mutex mtx;  // serialises the users of THIS arena (two host threads must not drive one stream anyway)
-  void *tab = nullptr, *ws = nullptr;
-  size_t tabCap = 0, wsCap = 0;
+  void *tab = nullptr, *ws = nullptr, *op = nullptr;
+  size_t tabCap = 0, wsCap = 0, opCap = 0;
   // two pinned staging buffers, used in turn: an upload waits for the upload TWO calls back to have left its buffer -- not for
   // the previous one, which sits on the stream behind the previous call's kernel and would make every call a host sync
   void *pinned[2] = {nullptr, nullptr};
@@ -85,6 +85,16 @@ int stream_workspace(void **ptr, size_t bytes, hipStream_t stream) {
   return MUGIQ_HIP_SUCCESS;
 }
 
+int stream_operator_workspace(void **ptr, size_t bytes, hipStream_t stream) {
+  int dev = 0, st = current_device(&dev);
+  if (st) return st;
+  StreamArena &a = arena_of(dev, stream);
+  std::lock_guard<std::mutex> lock(a.mtx);
+  if ((st = arena_reserve(&a.op, &a.opCap, bytes, 256, stream))) return st;
+  *ptr = a.op;
+  return MUGIQ_HIP_SUCCESS;
+}
+
 int upload_table(void **dev_out, const void *host, size_t bytes, hipStream_t stream) {
   int dev = 0, st = current_device(&dev);
   if (st) return st;
@@ -126,6 +136,7 @@ int release_stream_scratch(hipStream_t stream) {
     std::lock_guard<std::mutex> lock(a.mtx);
     if (a.tab) (void)hipFree(a.tab);
     if (a.ws) (void)hipFree(a.ws);
+    if (a.op) (void)hipFree(a.op);
     for (int i = 0; i < 2; i++) {
       if (a.pinned[i]) (void)hipHostFree(a.pinned[i]);
       if (a.staged[i]) (void)hipEventDestroy(a.staged[i]);

@@ -33,6 +33,9 @@ int set_error(int status, const char *fmt, ...);
 int stream_scratch(void **ptr, size_t bytes, hipStream_t stream);
 int stream_workspace(void **ptr, size_t bytes, hipStream_t stream);
 int upload_table(void **dev, const void *host, size_t bytes, hipStream_t stream);
+// a third buffer of the arena, for the Wilson operator (csrc/wilson.hip): intermediate and solver vectors that must survive the
+// calls of the deflation and halo code in between, which use stream_workspace themselves
+int stream_operator_workspace(void **ptr, size_t bytes, hipStream_t stream);
 int release_stream_scratch(hipStream_t stream);
 size_t eo_dft_x_lds_bytes(int precision, const int localL[4], int nPx, int *redOffsetElems);  // momproj.hip
 int eo_dft_x_time_chunk(int precision, const int localL[4], int nPx);                            // momproj.hip: 0 = the fused x step does not apply
@@ -104,6 +107,9 @@ int entry_pack_capacity(const MugiqHipSpinorField &ev, const int *kvals, int nK)
 #include <vector>
 namespace mugiq {
 bool momenta_negation_table(const int *mom, int Nmom, std::vector<int> &neg);  // reflect_mom.cpp
+// csrc/deflate.hip: c <- the sum of c over all ranks, in the fixed order of the momentum projection (reduce over space, gather over
+// time, rank-ordered sum on the root, bcast): identical bits on every rank
+int sum_over_ranks(const MugiqHipComm *comm, std::vector<double> &c);
 
 // ---- address spaces ---------------------------------------------------------------------------------------------
 // Pointers fetched from a device-side table (eigenvector bodies) have no known address space, so hipcc emits

@@ -1,0 +1,155 @@
+"""The Wilson operator on the device and what Eigsolve_Mugiq does with it (lib/eigsolve_mugiq.cpp:289-348 of the reference):
+computeEvals / printEvals / projectVector, plus a CG on the normal equations started from the low-mode part (csrc/wilson.hip).
+
+The operator is the unimproved Wilson operator in kappa normalisation (no clover term, no twisted mass); see mugiq_hip_wilson_apply
+in include/mugiq_hip.h for the formula and the gamma convention.
+"""
+import collections
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from .fields import SpinorField, desc_array
+
+# MuGiqEigOperator (include/enum_mugiq.h:22-25 of the reference, values identical) and the extension H = g5 M
+MUGIQ_EIG_OPERATOR_M, MUGIQ_EIG_OPERATOR_Mdag, MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H = range(5)
+STATUS_NOT_CONVERGED = 5  # MUGIQ_HIP_ERROR_NOT_CONVERGED
+
+SolveInfo = collections.namedtuple("SolveInfo", "iters relres converged")
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _comm_ptr(comm, keep):
+    if comm is None:
+        return None
+    c = comm.c_struct()
+    keep.append(c)
+    return ctypes.cast(ctypes.byref(c), ctypes.c_void_p)
+
+
+def _alloc_ghosts(fields, comm):
+    if comm is None:
+        return
+    for d in range(4):
+        if comm.comm_dim_partitioned(d):
+            for f in fields:
+                f.alloc_ghost(d, 0), f.alloc_ghost(d, 1)
+
+
+def wilsonApply(dst, src, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_M, scale=1.0, comm=None):
+    """dst_i = scale * A src_i for lists of SpinorFields (mugiq_hip_wilson_apply); the halo exchange of src is part of the call."""
+    dst, src = list(dst), list(src)
+    if len(dst) != len(src) or not src:
+        raise _lib.MugiqHipError("wilsonApply: %d dst and %d src vectors (need the same number, at least one)" % (len(dst), len(src)))
+    _alloc_ghosts(src, comm)
+    keep = []
+    g = gauge.desc()
+    _lib.check(_lib.load().mugiq_hip_wilson_apply(desc_array(dst), desc_array(src), len(src), ctypes.byref(g), float(kappa), int(opType),
+                                                  float(scale), _comm_ptr(comm, keep), _stream()))
+
+
+def computeEvals(eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, massNormalization=False, comm=None):
+    """(lambda[nEv] complex, residual[nEv], sigma[nEv] or None) of mugiq_hip_compute_evals."""
+    ev = list(eVecs)
+    n = len(ev)
+    lam = (ctypes.c_double * (2 * n))()
+    res = (ctypes.c_double * n)()
+    sig = (ctypes.c_double * n)()
+    keep = []
+    g = gauge.desc()
+    _lib.check(_lib.load().mugiq_hip_compute_evals(desc_array(ev), n, ctypes.byref(g), float(kappa), int(opType), int(bool(massNormalization)),
+                                                   lam, res, sig, _comm_ptr(comm, keep), _stream()))
+    has_sigma = int(opType) in (MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H)
+    return np.array(lam).view(np.complex128).copy(), np.array(res), (np.array(sig) if has_sigma else None)
+
+
+def projectVector(out, inp, eVecs, comm=None):
+    """out = sum_i v_i <v_i, in>   (lib/eigsolve_mugiq.cpp:340-348; mugiq_hip_project_vector)"""
+    ev = list(eVecs)
+    do, di = out.desc(), inp.desc()
+    keep = []
+    _lib.check(_lib.load().mugiq_hip_project_vector(ctypes.byref(do), ctypes.byref(di), desc_array(ev), len(ev), _comm_ptr(comm, keep), _stream()))
+
+
+def wilsonSolve(b, gauge, kappa, eVecs=(), sigmas=(), tol=1e-10, maxIter=1000, comm=None, x=None, allow_unconverged=False):
+    """x_r = M^-1 b_r by CG on the normal equations, started from the low-mode part when eigenpairs (v_n, sigma_n) of H = g5 M are
+    given (mugiq_hip_wilson_solve).  Returns (x, SolveInfo(iters, relres, converged)); x: new fp64 fields laid out like b unless
+    given.  A right-hand side that does not reach tol within maxIter raises MugiqHipError (status 5) unless allow_unconverged."""
+    b = list(b)
+    if not b:
+        raise _lib.MugiqHipError("wilsonSolve: no right-hand side")
+    if x is None:
+        x = [SpinorField(f.X, 8, f.order, f.stride - f.volumeCB, device=f.device) for f in b]
+    x = list(x)
+    ev, n = list(eVecs), len(b)
+    if len(sigmas) != len(ev):
+        raise _lib.MugiqHipError("wilsonSolve: %d sigmas for %d eigenvectors" % (len(sigmas), len(ev)))
+    if len(x) != n:
+        raise _lib.MugiqHipError("wilsonSolve: %d x and %d b vectors" % (len(x), n))
+    sg = (ctypes.c_double * max(len(ev), 1))(*[float(s) for s in sigmas])
+    iters = (ctypes.c_int * n)()
+    relres = (ctypes.c_double * n)()
+    keep = []
+    g = gauge.desc()
+    lib = _lib.load()
+    st = lib.mugiq_hip_wilson_solve(desc_array(x), desc_array(b), n, ctypes.byref(g), float(kappa), desc_array(ev) if ev else None,
+                                    sg if ev else None, len(ev), float(tol), int(maxIter), iters, relres, _comm_ptr(comm, keep), _stream())
+    if st != 0 and not (st == STATUS_NOT_CONVERGED and allow_unconverged):
+        _lib.check(st)
+    return x, SolveInfo(np.array(iters), np.array(relres), st == 0)
+
+
+def format_evals(evals, evals_quda, residuals, sigmas=None):
+    """The lines of Eigsolve_Mugiq::printEvals (lib/eigsolve_mugiq.cpp:325-333), character for character."""
+    lines = ["", "Eigsolve_Mugiq - Eigenvalues:"]
+    for i, (e, q, r) in enumerate(zip(evals, evals_quda, residuals)):
+        e, q = complex(e), complex(q)
+        lines.append("Mugiq-Quda: Eval[%04d] = %+.16e %+.16e , %+.16e %+.16e , Residual = %+.16e" % (i, e.real, e.imag, q.real, q.imag, r))
+    if sigmas is not None:
+        lines.append("")
+        for i, s in enumerate(sigmas):
+            lines.append("Mugiq-Quda: Sigma[%04d] = %+.16e" % (i, s))
+    return lines
+
+
+class Eigsolve_Mugiq:
+    """The part of the reference's Eigsolve_Mugiq that runs on eigenvectors somebody else computed: eVecs (SpinorFields), the gauge
+    field they belong to, kappa and the form of the operator they are eigenvectors of.  evals_quda: what the eigensolver reported
+    (printed beside the recomputed values; zero if not given)."""
+
+    def __init__(self, eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, comm=None, massNormalization=False, evals_quda=None):
+        self.eVecs, self.gauge, self.kappa, self.opType, self.comm = list(eVecs), gauge, float(kappa), int(opType), comm
+        self.massNormalization = bool(massNormalization)
+        n = len(self.eVecs)
+        self.eVals_quda = np.zeros(n, np.complex128) if evals_quda is None else np.asarray(evals_quda, np.complex128)
+        self.eVals, self.evals_res, self.eVals_sigma = np.zeros(n, np.complex128), np.zeros(n), None
+
+    def computeEvals(self):
+        self.eVals, self.evals_res, self.eVals_sigma = computeEvals(self.eVecs, self.gauge, self.kappa, self.opType, self.massNormalization,
+                                                                     self.comm)
+        return self.eVals, self.evals_res, self.eVals_sigma
+
+    def printEvals(self, file=None):
+        sig = self.eVals_sigma if self.opType in (MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag) else None
+        lines = format_evals(self.eVals, self.eVals_quda, self.evals_res, sig)
+        if self.comm is None or getattr(self.comm, "rank", 0) == 0:   # printfQuda: rank 0 only
+            print("\n".join(lines), file=file)
+        return lines
+
+    def projectVector(self, out, inp):
+        projectVector(out, inp, self.eVecs, self.comm)
+
+    def solve(self, b, tol=1e-10, maxIter=1000, sigmas=None, x=None, allow_unconverged=False):
+        """M^-1 b.  With opType H the eigenvectors (and sigmas, default: the computeEvals ones) deflate the start vector."""
+        ev, sg = (), ()
+        if self.opType == MUGIQ_EIG_OPERATOR_H:
+            sg = self.eVals_sigma if sigmas is None else sigmas
+            if sg is None:
+                raise _lib.MugiqHipError("Eigsolve_Mugiq.solve: no sigmas (call computeEvals first or pass them)")
+            ev = self.eVecs
+        return wilsonSolve(b, self.gauge, self.kappa, ev, sg, tol, maxIter, self.comm, x, allow_unconverged)

@@ -180,6 +180,7 @@ class Loop_Mugiq:
         self.eVecs = list(eVecs)
         sg = (ctypes.c_double * len(self.eVecs))(*[float(s) for s in eVals_sigma])
         self.comm = comm
+        self.eVals_sigma = [float(s) for s in eVals_sigma]
         c = comm.c_struct() if comm is not None else None
         self._handle = ctypes.c_void_p()
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -297,6 +298,21 @@ class Loop_Mugiq:
         buf = _overlap_buffer(overlaps, nEv, nVec)
         _lib.check(_lib.load().mugiq_hip_loop_deflate(self._handle, dd, ds, nVec, int(bool(gamma5)), buf))
         return _overlap_array(buf, nEv, nVec) if overlaps else None
+
+    def solve(self, b, kappa, tol=1e-10, maxIter=1000, x=None, allow_unconverged=False):
+        """x_r = M^-1 b_r (wilsonSolve) with this loop's gauge field, comm and stream, started from the low-mode part of its
+        eigenvectors and sigmas, which must be eigenpairs of H = g5 M at this kappa.  Returns the list x; the iteration counts and true
+        residuals are kept in self.lastSolve.  Errors as Loop_Mugiq.deflate: status 1 (INVALID_ARGUMENT) for a loop object created
+        without a gauge field, status 2 (UNSUPPORTED) for two-sided and coarse loop objects.  The recipe then reads
+        x = low.solve(xi, kappa); low.deflate(x, xi); Loop_Mugiq(prm, eVecs=x, eVals_sigma=..., eVecsLeft=g5xi)."""
+        from .eigsolve import wilsonSolve
+        if self.eVecsLeft is not None or self._transfer is not None:
+            raise _lib.MugiqHipError("status 2: Loop_Mugiq.solve: two-sided and coarse (MG) loop objects are not supported")
+        if self._params.gauge is None:
+            raise _lib.MugiqHipError("status 1: Loop_Mugiq.solve: the loop object was created without a gauge field")
+        x, self.lastSolve = wilsonSolve(b, self._params.gauge, kappa, self.eVecs, self.eVals_sigma, tol, maxIter, self.comm, x,
+                                        allow_unconverged)
+        return x
 
     def computeCoarseLoop(self):
         """lib/loop_mugiq.cpp:439-525"""

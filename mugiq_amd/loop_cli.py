@@ -110,6 +110,10 @@ def build_parser():
     ap.add_argument("--field-order", type=int, choices=[2, 4], default=None, help="QUDA field order of the eigenvectors (default: FLOAT2 for double, FLOAT4 for single)")
     ap.add_argument("--n-ev", type=int, default=4, help="number of (synthetic) eigenvectors")
     ap.add_argument("--seed", type=int, default=777)
+    ap.add_argument("--kappa", type=float, default=0.12, help="hopping parameter of the Wilson operator (--check-evals)")
+    ap.add_argument("--check-evals", action="store_true",
+                    help="print the printEvals lines (lambda = v^dag MdagM v / ||v||, residual, sigma) of the eigenvectors the loop runs on; "
+                         "needs the gauge field of a displaced loop")
     add_loop_option_mugiq(ap)
     return ap
 
@@ -172,6 +176,13 @@ def main(argv=None):
     if args.loop_prec == "double":
         prm.loopPrecision = 8
 
+    if args.check_evals:
+        from .eigsolve import Eigsolve_Mugiq, MUGIQ_EIG_OPERATOR_MdagM
+        if gauge is None:
+            raise SystemExit("--check-evals needs a gauge field: set --loop-do-nonlocal yes and --displace-entry-string")
+        es = Eigsolve_Mugiq(fields, gauge, args.kappa, MUGIQ_EIG_OPERATOR_MdagM, comm)
+        es.computeEvals()
+        es.printEvals(file=sys.stderr)
     loop = Loop_Mugiq(prm, fields, sigma, comm)
     if rank == 0:
         loop.printLoopComputeParams(lambda line: print(line, file=sys.stderr))
