@@ -325,6 +325,31 @@ int mugiq_hip_convert_and_project_slots(void *dataMom_d, const void *dataPos_d, 
                                         const int *momMatrix_h, int Nmom, int FTSign, const int localL[4], const int totalL[4],
                                         const int commCoord[4], int precision, void *workspace_d, size_t workspace_bytes, void *stream);
 
+/* How the fused reorder + x step of the two calls above is dispatched for a shape (new; host only, no device work): the decisions
+ * the launcher itself takes, through the same helper.  Same validation and the same environment switches (MUGIQ_HIP_EO_MFMA,
+ * MUGIQ_HIP_EO_TILES_PER_WG) as the compute calls; nData = 16 * (number of slots projected). */
+#define MUGIQ_HIP_PROJECT_FORM_GENERAL 0   /* eo_dft_x_kernel: any Lx, one tile per workgroup, tiles cut along t */
+#define MUGIQ_HIP_PROJECT_FORM_PIPELINED 1 /* eo_dft_x_pipelined_kernel: a workgroup walks tilesPerWg tiles, prefetching the next */
+#define MUGIQ_HIP_PROJECT_FORM_MFMA 2      /* eo_dft_x_mfma_kernel<nks, mb>: the same walk, sums on the fp64 matrix pipe */
+typedef struct MugiqHipProjectPlan_s {
+  int form;          /* MUGIQ_HIP_PROJECT_FORM_* */
+  int nks, mb;       /* matrix pipe: k-steps per wave (Lx / 8) and 16-row blocks per tile; 0 otherwise */
+  int nPx;           /* distinct p_x of the momentum list */
+  int tChunk;        /* time slices per tile */
+  int nChunks;       /* tiles per y pair: ceil(Lt / tChunk) */
+  int lastChunk;     /* time slices of the last chunk (< tChunk: ragged, general form only) */
+  int tiles;         /* (Ly / 2) * nChunks */
+  int tilesPerWg;    /* consecutive tiles a workgroup walks (1 in the general form) */
+  int workgroupsX;   /* ceil(tiles / tilesPerWg): grid.x (grid.y = Lz, grid.z = nData) */
+  int rowPasses;     /* passes of 64 rows over a full tile (2 tChunk rows) */
+  int pxPasses;      /* passes of 8 distinct p_x */
+  int stagingPieces; /* 64-entry pieces of a run of Lx checkerboard entries (general form: > 1 for Lx > 64) */
+  int redOffset;     /* complex elements from the tile to the partial-sum area (0: in the tile's place) */
+  long long ldsBytes;/* dynamic LDS of the x-step kernel */
+} MugiqHipProjectPlan;
+int mugiq_hip_convert_and_project_plan(const int *momMatrix_h, int Nmom, const int localL[4], int nData, int precision,
+                                       MugiqHipProjectPlan *out);
+
 /* Reflected displacement entries in momentum space (new; host arrays only, no device work).  With L^-_k(x) = eta conj(L^+_k(x - k mu))
  * (mugiq_hip_reflect_displaced_loop), the Fourier transform of the derived slot follows from that of its source slot:
  *   dst(p, ig, t) = eta(15-ig) exp(-+ i FTSign 2 pi p_mu k / totalL[mu]) conj( src(-p, ig, t) )      mu = x, y, z

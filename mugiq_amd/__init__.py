@@ -11,11 +11,12 @@ from .fields import SpinorField, GaugeField, CoarseField, Transfer, FLOAT2, FLOA
 from .operators import (  # noqa: E402
     copyGammaCoeffStructToSymbol, copyGammaMapStructToSymbol, gammaTables, GammaName,
     performLoopContraction, performLoopContractionBatched, performCovariantDisplacementVector, packFace, exchangeGhostVec,
-    createPhaseMatrixGPU, convertIdxOrder_mapGamma, momentumProjection, momentumProjectionSeparable, convertAndProject, packFaceLayers, displacedLoopContractionFused, displacedLoopContractionFusedTwoSided, reflectDisplacedLoop, packLoopLayers, probeReadBandwidth, prolongateEvecs, prolongateCoarseEvecs, prolongateContractBatched,
+    createPhaseMatrixGPU, convertIdxOrder_mapGamma, momentumProjection, momentumProjectionSeparable, convertAndProject, convertAndProjectSlots, convertAndProjectPlan, packFaceLayers, displacedLoopContractionFused, displacedLoopContractionFusedTwoSided, reflectDisplacedLoop, packLoopLayers, probeReadBandwidth, prolongateEvecs, prolongateCoarseEvecs, prolongateContractBatched,
     deflateLowModes,
     DispDir, DispSignMinus, DispSignPlus, LOOP_FT_SIGN_MINUS, LOOP_FT_SIGN_PLUS, DisplaceFlagArray,
     REGION_ALL, REGION_INTERIOR, REGION_BOUNDARY, REGION_OVERWRITE, ENTRY_KERNEL_REFLECTED, ENTRY_KERNEL_MFMA_COLUMN, ENTRY_KERNEL_MFMA_ROW,
     ENTRY_KERNEL_VECTOR_TILE, ENTRY_KERNEL_STREAMING, ENTRY_KERNEL_STEPWISE,
+    PROJECT_FORM_GENERAL, PROJECT_FORM_PIPELINED, PROJECT_FORM_MFMA,
 )
 from ._lib import MugiqHipError, LIB_PATH  # noqa: E402
 from .loop import (  # noqa: E402

@@ -49,6 +49,13 @@ class TransferDesc(ctypes.Structure):
                 ("spinBlockSize", ctypes.c_int), ("X", ctypes.c_int * 4), ("stride", ctypes.c_int), ("parity_offset", ctypes.c_int64)]
 
 
+class ProjectPlan(ctypes.Structure):
+    """MugiqHipProjectPlan (include/mugiq_hip.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("form", "nks", "mb", "nPx", "tChunk", "nChunks", "lastChunk", "tiles", "tilesPerWg",
+                                            "workgroupsX", "rowPasses", "pxPasses", "stagingPieces", "redOffset")] + \
+               [("ldsBytes", ctypes.c_longlong)]
+
+
 _I4 = ctypes.POINTER(ctypes.c_int)
 _VP = ctypes.c_void_p
 _SP = ctypes.POINTER(SpinorDesc)
@@ -119,6 +126,7 @@ SIGNATURES = {
                                                      ctypes.c_int, _VP, ctypes.c_size_t, _VP]),
     "mugiq_hip_convert_and_project_slots": (ctypes.c_int, [_VP, _VP, ctypes.c_int, _I4, ctypes.c_int, _I4, ctypes.c_int, ctypes.c_int, _I4, _I4, _I4,
                                                            ctypes.c_int, _VP, ctypes.c_size_t, _VP]),
+    "mugiq_hip_convert_and_project_plan": (ctypes.c_int, [_I4, ctypes.c_int, _I4, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ProjectPlan)]),
     "mugiq_hip_reflect_momentum_space": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _I4, ctypes.c_int, _I4, ctypes.c_int, ctypes.c_int,
                                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "mugiq_hip_pack_face_layers": (ctypes.c_int, [_VP, _SP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP]),

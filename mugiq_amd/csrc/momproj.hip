@@ -546,6 +546,62 @@ int eo_dft_x_time_chunk(int precision, const int localL[4], int nPx) {
   return (localL[3] + nChunks - 1) / nChunks;
 }
 
+// the instantiations of eo_dft_x_mfma_kernel<NKS, MB>: every pair the conditions of plan_eo_dft_x can produce (Lx = 24, 32, 48
+// or 64; 17 to 64 rows).  <6,4> and <8,4> are not among them: with Lx = 48 or 64 a run fills a wave, so the pipelined staging
+// (4 waves x kEoLd loads) covers at most 24 time slices = 48 rows.
+#define MUGIQ_EO_MFMA_INSTANCES(CASE) \
+  CASE(3, 2) CASE(3, 3) CASE(3, 4) CASE(4, 2) CASE(4, 3) CASE(4, 4) CASE(6, 2) CASE(6, 3) CASE(8, 2) CASE(8, 3)
+
+// Every decision of the fused reorder + x step for one shape: kernel form, compile-time parameters, tiling, passes, LDS.  The
+// launcher and mugiq_hip_convert_and_project_plan both go through it, so what the query reports is what runs.
+static int plan_eo_dft_x(int precision, const int localL[4], int nPx, int nData, MugiqHipProjectPlan &p) {
+  const int tChunk = eo_dft_x_time_chunk(precision, localL, nPx);
+  MUGIQ_REQUIRE(tChunk >= 1 && localL[2] <= 65535 && nData <= 65535, "performMomentumProjection: lattice too large for the fused reorder + x step");
+  int Lc[4] = {localL[0], localL[1], localL[2], tChunk};
+  p.ldsBytes = (long long)eo_dft_x_lds_bytes(precision, Lc, nPx, &p.redOffset);
+  p.nPx = nPx;
+  p.tChunk = tChunk;
+  p.nChunks = (localL[3] + tChunk - 1) / tChunk;
+  p.lastChunk = localL[3] - (p.nChunks - 1) * tChunk;
+  p.tiles = (localL[1] / kEoYG) * p.nChunks;
+  p.pxPasses = (nPx + kEoCh - 1) / kEoCh;
+  p.rowPasses = (kEoYG * tChunk + 63) / 64;
+  // the pipelined forms walk tiles = (y pair, chunk of time slices): whole time slabs when they fit the LDS, else even chunks
+  const int run = kEoYG * localL[0] / 2;
+  p.stagingPieces = (run + 63) / 64;
+  const bool pipelined = p.lastChunk == tChunk && run <= 64 && (2 * tChunk + 64 / run - 1) / (64 / run) <= 4 * kEoLd;
+  // the sums on the matrix pipe where it applies (fp64; one pass: <= 64 rows, <= 8 distinct p_x; Lx = 24, 32, 48 or 64):
+  // 1.95 ms against 2.06 ms for the vector form at 48.48.24.24 x 25 slots (profiles/r02_eo_dft_x_kernel_stats_*.csv);
+  // MUGIQ_HIP_EO_MFMA = 0 keeps the vector form
+  bool mfma = true;
+  if (const char *m = getenv("MUGIQ_HIP_EO_MFMA")) mfma = atoi(m) != 0;
+  const int mfmaKs = localL[0] / 8, mfmaMb = (kEoYG * tChunk + 15) / 16;
+  mfma = mfma && precision == 8 && pipelined && kEoYG * tChunk <= 64 && nPx <= 8 && localL[0] % 8 == 0 &&
+         (mfmaKs == 3 || mfmaKs == 4 || mfmaKs == 6 || mfmaKs == 8) && mfmaMb >= 2;
+  p.form = mfma ? MUGIQ_HIP_PROJECT_FORM_MFMA : (pipelined ? MUGIQ_HIP_PROJECT_FORM_PIPELINED : MUGIQ_HIP_PROJECT_FORM_GENERAL);
+  p.nks = mfma ? mfmaKs : 0;
+  p.mb = mfma ? mfmaMb : 0;
+  if (mfma) {  // a pair the conditions allow and the list lacks is an error, not an unwritten output
+    bool instantiated = false;
+#define MUGIQ_EO_MFMA_CASE(K_, M_) instantiated = instantiated || (mfmaKs == K_ && mfmaMb == M_);
+    MUGIQ_EO_MFMA_INSTANCES(MUGIQ_EO_MFMA_CASE)
+#undef MUGIQ_EO_MFMA_CASE
+    MUGIQ_REQUIRE(instantiated, "performMomentumProjection: no eo_dft_x_mfma_kernel<%d,%d> for localL = %d %d %d %d, %d p_x", mfmaKs,
+                  mfmaMb, localL[0], localL[1], localL[2], localL[3], nPx);
+  }
+  p.tilesPerWg = 1;
+  if (pipelined) {
+    // about 32 workgroups per CU (8 rounds of 4): enough to balance, few enough to amortise the pipeline fill
+    const long long slabs = (long long)localL[2] * nData;
+    int perWg = (int)((slabs * p.tiles + 8191) / 8192);
+    perWg = perWg < 1 ? 1 : (perWg > p.tiles ? p.tiles : perWg);
+    if (const char *t = getenv("MUGIQ_HIP_EO_TILES_PER_WG")) perWg = std::max(1, std::min(p.tiles, atoi(t)));
+    p.tilesPerWg = perWg;
+  }
+  p.workgroupsX = (p.tiles + p.tilesPerWg - 1) / p.tilesPerWg;
+  return MUGIQ_HIP_SUCCESS;
+}
+
 // the plan: distinct p_x, distinct (p_x, p_y) pairs, and the tables of the three steps
 struct SeparablePlan {
   std::vector<int> px, py, pz;             // distinct values
@@ -702,11 +758,12 @@ static int launch_separable(void *C, const void *A, const void *dataPosEO, int n
   int firstStep = 0;
   if (dataPosEO != nullptr) {  // step x straight from the even-odd buffer (A, the reordered copy, is not needed)
     EoDftArgs<F> e;
-    const int tChunk = eo_dft_x_time_chunk((int)sizeof(F), localL, (int)P.px.size());
-    MUGIQ_REQUIRE(tChunk >= 1 && localL[2] <= 65535 && nData <= 65535, "performMomentumProjection: lattice too large for the fused reorder + x step");
-    int Lc[4] = {localL[0], localL[1], localL[2], tChunk};
-    const size_t shmem = eo_dft_x_lds_bytes((int)sizeof(F), Lc, (int)P.px.size(), &e.redOffset);
-    e.tChunk = tChunk;
+    MugiqHipProjectPlan xp;
+    if (int st = plan_eo_dft_x((int)sizeof(F), localL, (int)P.px.size(), nData, xp)) return st;
+    const size_t shmem = (size_t)xp.ldsBytes;
+    e.redOffset = xp.redOffset;
+    e.tChunk = xp.tChunk;
+    e.tilesPerWg = xp.tilesPerWg;
     e.in = static_cast<const Cplx<F> *>(dataPosEO);
     e.out = t1;
     e.ph = ph_d + phXT;
@@ -720,42 +777,18 @@ static int launch_separable(void *C, const void *A, const void *dataPosEO, int n
     e.nPx = (int)P.px.size();
     e.M = M;
     e.slotMap = slotMap_h ? int_d + slotOff : nullptr;
-    // the pipelined forms walk tiles = (y pair, chunk of time slices): whole time slabs when they fit the LDS, else even chunks
-    const int nCh = localL[3] % tChunk == 0 ? localL[3] / tChunk : 0;
-    const int run = kEoYG * localL[0] / 2, tiles = (localL[1] / kEoYG) * std::max(nCh, 1);
-    const bool pipelined = nCh >= 1 && run <= 64 && (2 * tChunk + 64 / run - 1) / (64 / run) <= 4 * kEoLd;
-    // the sums on the matrix pipe where it applies (fp64; one pass: <= 64 rows, <= 8 distinct p_x; Lx = 24, 32, 48 or 64):
-    // 1.95 ms against 2.06 ms for the vector form at 48.48.24.24 x 25 slots (profiles/r02_eo_dft_x_kernel_stats_*.csv);
-    // MUGIQ_HIP_EO_MFMA = 0 keeps the vector form
-    bool mfma = true;
-    if (const char *m = getenv("MUGIQ_HIP_EO_MFMA")) mfma = atoi(m) != 0;
-    const int mfmaKs = localL[0] / 8, mfmaMb = (kEoYG * tChunk + 15) / 16;
-    mfma = mfma && sizeof(F) == 8 && pipelined && kEoYG * tChunk <= 64 && (int)P.px.size() <= 8 && localL[0] % 8 == 0 &&
-           (mfmaKs == 3 || mfmaKs == 4 || mfmaKs == 6 || mfmaKs == 8) && mfmaMb >= 2;
-    if (pipelined) {
-      // about 32 workgroups per CU (8 rounds of 4): enough to balance, few enough to amortise the pipeline fill
-      const long long slabs = (long long)localL[2] * nData;
-      int perWg = (int)((slabs * tiles + 8191) / 8192);
-      perWg = perWg < 1 ? 1 : (perWg > tiles ? tiles : perWg);
-      if (const char *t = getenv("MUGIQ_HIP_EO_TILES_PER_WG")) perWg = std::max(1, std::min(tiles, atoi(t)));
-      e.tilesPerWg = perWg;
+    const dim3 grid(xp.workgroupsX, localL[2], nData);
+    if (xp.form == MUGIQ_HIP_PROJECT_FORM_MFMA) {
       if constexpr (sizeof(F) == 8) {
-        if (mfma) {
-          const dim3 grid((tiles + perWg - 1) / perWg, localL[2], nData);
 #define MUGIQ_EO_MFMA_CASE(K_, M_) \
-  if (mfmaKs == K_ && mfmaMb == M_) hipLaunchKernelGGL((eo_dft_x_mfma_kernel<K_, M_>), grid, dim3(256), shmem, stream, e);
-          MUGIQ_EO_MFMA_CASE(3, 2) MUGIQ_EO_MFMA_CASE(3, 3) MUGIQ_EO_MFMA_CASE(3, 4) MUGIQ_EO_MFMA_CASE(4, 2) MUGIQ_EO_MFMA_CASE(4, 3)
-          MUGIQ_EO_MFMA_CASE(4, 4) MUGIQ_EO_MFMA_CASE(6, 2) MUGIQ_EO_MFMA_CASE(6, 3) MUGIQ_EO_MFMA_CASE(6, 4) MUGIQ_EO_MFMA_CASE(8, 2)
-          MUGIQ_EO_MFMA_CASE(8, 3) MUGIQ_EO_MFMA_CASE(8, 4)
+  if (xp.nks == K_ && xp.mb == M_) hipLaunchKernelGGL((eo_dft_x_mfma_kernel<K_, M_>), grid, dim3(256), shmem, stream, e);
+        MUGIQ_EO_MFMA_INSTANCES(MUGIQ_EO_MFMA_CASE)  // plan_eo_dft_x has checked that one of them matches
 #undef MUGIQ_EO_MFMA_CASE
-        }
       }
-      if (!mfma)
-        hipLaunchKernelGGL((eo_dft_x_pipelined_kernel<F>), dim3((tiles + perWg - 1) / perWg, localL[2], nData), dim3(256), shmem, stream, e);
+    } else if (xp.form == MUGIQ_HIP_PROJECT_FORM_PIPELINED) {
+      hipLaunchKernelGGL((eo_dft_x_pipelined_kernel<F>), grid, dim3(256), shmem, stream, e);
     } else {
-      e.tilesPerWg = 1;
-      const int nChunks = (localL[3] + tChunk - 1) / tChunk;
-      hipLaunchKernelGGL((eo_dft_x_kernel<F>), dim3((localL[1] / kEoYG) * nChunks, localL[2], nData), dim3(256), shmem, stream, e);
+      hipLaunchKernelGGL((eo_dft_x_kernel<F>), grid, dim3(256), shmem, stream, e);
     }
     MUGIQ_CHECK_HIP(hipGetLastError());
     firstStep = 1;
@@ -858,11 +891,10 @@ int mugiq_hip_momentum_projection_separable(void *dataMom_d, const void *dataPos
   return launch_separable<float>(dataMom_d, dataPosMP_d, nullptr, nData, momMatrix_h, Nmom, FTSign, localL, totalL, commCoord, locT * nData, ws, s);
 }
 
-int mugiq_hip_convert_and_project(void *dataMom_d, const void *dataPos_d, int nData, int nLoop, const int *momMatrix_h, int Nmom, int FTSign,
-                                  const int localL[4], const int totalL[4], const int commCoord[4], int precision, void *workspace_d,
-                                  size_t workspace_bytes, void *stream) {
-  const char *who = "performMomentumProjection";
-  MUGIQ_REQUIRE(dataMom_d && dataPos_d && momMatrix_h && localL && totalL, "%s: NULL argument", who);
+// what mugiq_hip_convert_and_project requires of its host arguments (shared with the plan query)
+static int check_convert_and_project(const char *who, int nData, int nLoop, const int *momMatrix_h, int Nmom, int FTSign, const int localL[4],
+                                     const int totalL[4], int precision) {
+  MUGIQ_REQUIRE(momMatrix_h && localL && totalL, "%s: NULL argument", who);
   MUGIQ_REQUIRE(nData == nLoop * 16 && nLoop >= 1, "%s: This function assumes that nData = nLoop * NGamma", who);  // lib/contract_wrappers.cu:138
   MUGIQ_REQUIRE(precision == 4 || precision == 8, "%s: Precision not supported!", who);
   MUGIQ_REQUIRE(Nmom >= 1 && (FTSign == 1 || FTSign == -1), "%s: Nmom = %d, FTSign = %d", who, Nmom, FTSign);
@@ -872,6 +904,27 @@ int mugiq_hip_convert_and_project(void *dataMom_d, const void *dataPos_d, int nD
     vol *= localL[d];
   }
   MUGIQ_REQUIRE(vol < (1LL << 31) && (long long)localL[3] * nData < (1LL << 31), "%s: local volume overflows int", who);
+  return MUGIQ_HIP_SUCCESS;
+}
+
+int mugiq_hip_convert_and_project_plan(const int *momMatrix_h, int Nmom, const int localL[4], int nData, int precision,
+                                       MugiqHipProjectPlan *out) {
+  const char *who = "performMomentumProjection";
+  MUGIQ_REQUIRE(out, "%s: NULL argument", who);
+  memset(out, 0, sizeof(*out));
+  if (int st = check_convert_and_project(who, nData, nData / 16, momMatrix_h, Nmom, 1, localL, localL, precision)) return st;
+  SeparablePlan P;
+  build_plan(momMatrix_h, Nmom, P);
+  return plan_eo_dft_x(precision, localL, (int)P.px.size(), nData, *out);
+}
+
+int mugiq_hip_convert_and_project(void *dataMom_d, const void *dataPos_d, int nData, int nLoop, const int *momMatrix_h, int Nmom, int FTSign,
+                                  const int localL[4], const int totalL[4], const int commCoord[4], int precision, void *workspace_d,
+                                  size_t workspace_bytes, void *stream) {
+  if (int dbg_ = mugiq::debug_poison_lds_if_asked(static_cast<hipStream_t>(stream))) return dbg_;
+  const char *who = "performMomentumProjection";
+  MUGIQ_REQUIRE(dataMom_d && dataPos_d, "%s: NULL argument", who);
+  if (int st = check_convert_and_project(who, nData, nLoop, momMatrix_h, Nmom, FTSign, localL, totalL, precision)) return st;
   const int locT = localL[3];
   const size_t need = mugiq_hip_momentum_projection_separable_workspace(momMatrix_h, Nmom, localL, locT, nData, precision);
   void *ws = workspace_d;

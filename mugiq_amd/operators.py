@@ -20,6 +20,8 @@ LOOP_FT_SIGN_MINUS, LOOP_FT_SIGN_PLUS = -1, 1        # include/enum_mugiq.h:28-3
 DisplaceFlagArray = ["+x", "-x", "+y", "-y", "+z", "-z", "+t", "-t"]   # include/displace.h:21
 REGION_ALL, REGION_INTERIOR, REGION_BOUNDARY, REGION_OVERWRITE = 0, 1, 2, 0x100   # MUGIQ_HIP_REGION_* (include/mugiq_hip.h)
 # mugiq_hip_loop_get_entry_kernel: how an entry of the last compute was produced (MUGIQ_HIP_ENTRY_KERNEL_*)
+# mugiq_hip_convert_and_project_plan: the kernel form of the fused reorder + x step (MUGIQ_HIP_PROJECT_FORM_*)
+PROJECT_FORM_GENERAL, PROJECT_FORM_PIPELINED, PROJECT_FORM_MFMA = range(3)
 ENTRY_KERNEL_REFLECTED, ENTRY_KERNEL_MFMA_COLUMN, ENTRY_KERNEL_MFMA_ROW, ENTRY_KERNEL_VECTOR_TILE, ENTRY_KERNEL_STREAMING, ENTRY_KERNEL_STEPWISE = range(6)
 
 
@@ -158,6 +160,29 @@ def convertAndProject(dataMom_d, dataPos_d, nData, nLoop, momMatrix, FTSign, loc
     _lib.check(_lib.load().mugiq_hip_convert_and_project(
         dataMom_d.data_ptr(), dataPos_d.data_ptr(), int(nData), int(nLoop), mom.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n_mom,
         int(FTSign), _lib.int4(localL), _lib.int4(totalL), _lib.int4(commCoord), _prec_of(dataPos_d), None, 0, _stream()))
+
+
+def convertAndProjectSlots(dataMom_d, dataPos_d, nLoop, slots, momMatrix, FTSign, localL, totalL, commCoord=(0, 0, 0, 0)):
+    """convertAndProject for the loop slots `slots` only: their rows of dataMom_d ([locT*16*nLoop x Nmom]) are written, the rows of
+    the other slots keep what they held (see mugiq_hip_convert_and_project_slots)."""
+    mom = np.ascontiguousarray(np.asarray(momMatrix, dtype=np.int32).reshape(-1))
+    sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+    n_mom = mom.size // 3
+    assert dataMom_d.numel() >= localL[3] * 16 * nLoop * n_mom and dataMom_d.dtype == dataPos_d.dtype
+    _lib.check(_lib.load().mugiq_hip_convert_and_project_slots(
+        dataMom_d.data_ptr(), dataPos_d.data_ptr(), int(nLoop), sl.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), int(sl.size),
+        mom.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n_mom, int(FTSign), _lib.int4(localL), _lib.int4(totalL), _lib.int4(commCoord),
+        _prec_of(dataPos_d), None, 0, _stream()))
+
+
+def convertAndProjectPlan(momMatrix, localL, nData, precision):
+    """How convertAndProject dispatches its fused reorder + x step for this shape, as a dict of the MugiqHipProjectPlan members
+    (see mugiq_hip_convert_and_project_plan).  Host only: no GPU is touched; raises MugiqHipError where the compute call would."""
+    mom = np.ascontiguousarray(np.asarray(momMatrix, dtype=np.int32).reshape(-1))
+    plan = _lib.ProjectPlan()
+    _lib.check(_lib.load().mugiq_hip_convert_and_project_plan(
+        mom.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), mom.size // 3, _lib.int4(localL), int(nData), int(precision), ctypes.byref(plan)))
+    return {n: int(getattr(plan, n)) for n, _ in plan._fields_}
 
 
 def packFaceLayers(faces_d, eVecs, dim, high, layers):
