@@ -511,7 +511,7 @@ int mugiq_hip_deflate_low_modes(const MugiqHipSpinorField *dst_h, const MugiqHip
                                 const MugiqHipSpinorField *eVecs_h, const double *sigma_h, int nEv, int gamma5,
                                 double *overlaps_h, const MugiqHipComm *comm, void *stream);
 
-/* ==== the Wilson operator, the eigenpair check and a deflated CG (csrc/wilson.hip) ============================================ */
+/* ==== the Wilson and Wilson-clover operators, the eigenpair check and a deflated CG (csrc/wilson.hip, csrc/clover.hip) ========= */
 /* MuGiqEigOperator, include/enum_mugiq.h:22-25 (values identical), plus H = g5 M, which the reference does not have */
 #define MUGIQ_HIP_EIG_OPERATOR_M 0
 #define MUGIQ_HIP_EIG_OPERATOR_MDAG 1
@@ -524,7 +524,8 @@ int mugiq_hip_deflate_low_modes(const MugiqHipSpinorField *dst_h, const MugiqHip
  * operator in kappa normalisation
  *   M psi(x) = psi(x) - kappa sum_mu [ (1 - g_mu) U_mu(x) psi(x+mu) + (1 + g_mu) U_mu^dag(x-mu) psi(x-mu) ],
  *   g_x, g_y, g_z, g_t = Gamma_1, Gamma_2, Gamma_4, Gamma_8 of mugiq_hip_get_gamma_tables ("g1" .. "g4"), g5 = Gamma_15.
- * No clover term, no twisted mass, no even-odd preconditioning.  Links are applied as stored (boundary phases and anisotropy are
+ * The clover term is added by mugiq_hip_wilson_clover_apply below; no twisted mass, no even-odd preconditioning.
+ * Links are applied as stored (boundary phases and anisotropy are
  * the host's business; they need not be unitary), the contract of mugiq_hip_perform_covariant_displacement_vector; the gauge
  * precision (4 | 8) is independent of the spinors'.  `scale`: e.g. the reference's 0.25 / kappa^2 for QUDA_MASS_NORMALIZATION (:302).
  * dst_h / src_h: nVec descriptors each, one precision, order, geometry, stride and parity offset; no dst may overlap any src.
@@ -567,6 +568,67 @@ int mugiq_hip_project_vector(const MugiqHipSpinorField *out, const MugiqHipSpino
 int mugiq_hip_wilson_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
                            double kappa, const MugiqHipSpinorField *eVecs_h, const double *sigma_h, int nEv, double tol, int maxIter,
                            int *iters_out, double *relres_out, const MugiqHipComm *comm, void *stream);
+
+/* ---- the clover term (new; the reference's tests load one through loadCloverQuda before anything else) ------------------------------
+ * With gamma matrices and g5 as above, sign and normalisation of Luescher-Sint-Sommer-Weisz:
+ *   M_clov psi(x) = A(x) psi(x) - kappa sum_mu [ (1 - g_mu) U_mu(x) psi(x+mu) + (1 + g_mu) U_mu^dag(x-mu) psi(x-mu) ]
+ *   A(x)       = 1 + i coeff sum_{mu<nu} sigma_{mu nu} (x) Fhat_{mu nu}(x),     coeff = kappa * c_sw  (QUDA's clover_coeff)
+ *   sigma_mn   = (i/2) [g_m, g_n]
+ *   Fhat_mn(x) = (1/8) (Q_mn(x) - Q_mn(x)^dag)                                   (no trace removed)
+ *   Q_mn(x)    =   U_m(x)       U_n(x+m)       U_m^dag(x+n)  U_n^dag(x)
+ *                + U_n(x)       U_m^dag(x-m+n) U_n^dag(x-m)  U_m(x-m)
+ *                + U_m^dag(x-m) U_n^dag(x-m-n) U_m(x-m-n)    U_n(x-n)
+ *                + U_n^dag(x-n) U_m(x-n)       U_n(x+m-n)    U_m^dag(x)
+ * Links are used as stored: U^dag is the conjugate transpose, not the inverse, and links need not be unitary; boundary phases and
+ * anisotropy stay the host's business, as for the hopping term.  g5 is diagonal, so A commutes with it and is block diagonal: two
+ * Hermitian 6 x 6 blocks per site, block 0 on spins 0, 1 and block 1 on spins 2, 3, index inside a block i = spin_local*3 + colour.
+ * Hence M_clov^dag = g5 M_clov g5, and every form of the operator below works as for the unimproved one.
+ *
+ * MugiqHipCloverField: local sites only (the term is site-local: no border, no halo).  Packed storage, 72 reals per site, as 36 PAIRS
+ * of reals of `precision`; pair p of (parity, x_cb) is at pair index
+ *   parity*parity_offset + p*stride + x_cb                    (a wavefront's loads of one pair coalesce)
+ * with, for block b = 0 | 1:
+ *   p = 18*b + q,     q = 0, 1, 2:    (A_{2q,2q}, A_{2q+1,2q+1})         the real diagonal, two entries to a pair
+ *   p = 18*b + 3 + l, l = i*(i-1)/2 + j, 0 <= j < i < 6:  (Re A_ij, Im A_ij)   the strictly-lower triangle, row by row:
+ *                     (1,0) (2,0) (2,1) (3,0) (3,1) (3,2) (4,0) .. (4,3) (5,0) .. (5,4);    A_ji = conj(A_ij).
+ * A host that has its own clover term fills the buffer itself; the supported route is mugiq_hip_compute_clover. */
+typedef struct MugiqHipCloverField_s {
+  void *data;
+  int precision;         /* 4 | 8; must equal the gauge precision of the operator call it is passed to */
+  int X[4];              /* local dims, all even */
+  int volumeCB;
+  int stride;            /* volumeCB + pad */
+  int64_t parity_offset; /* pairs between the two parities, >= 36*stride */
+} MugiqHipCloverField;
+
+/* bytes of a pad-0 field: volumeCB * 36 pairs * 2 parities * 2 reals */
+size_t mugiq_hip_clover_bytes(const int X[4], int precision);
+/* allocate (zeroed, pad 0) and describe; release with mugiq_hip_free_clover */
+int mugiq_hip_alloc_clover(MugiqHipCloverField *clover, const int X[4], int precision);
+int mugiq_hip_free_clover(MugiqHipCloverField *clover);
+/* Fill `clover` with A(x) of the definition above from the border-extended gauge field (either precision; fp64 arithmetic whatever the
+ * storages, rounded once on the store).  One lattice site per lane, one plane at a time.  Links are addressed as by the stencil, always
+ * in the extended field: R[d] >= 1 supplies x +- m across a face and the edge and corner regions supply the diagonal neighbours
+ * x-m+n, x+m-n, x-m-n (mugiq_hip_create_extended_gauge fills them); R[d] = 0 wraps.  A partitioned dimension (comm, as for
+ * mugiq_hip_wilson_apply) with R[d] = 0 is MUGIQ_HIP_ERROR_INVALID_ARGUMENT.  No communication of its own.  Pads are not written. */
+int mugiq_hip_compute_clover(const MugiqHipCloverField *clover, const MugiqHipGaugeField *gauge, double coeff, const MugiqHipComm *comm,
+                             void *stream);
+
+/* mugiq_hip_wilson_apply, mugiq_hip_compute_evals and mugiq_hip_wilson_solve for M_clov: each is its twin plus `clover`.  clover NULL:
+ * the unimproved operator, through the same code as the twin (identical bits).  Otherwise its geometry must be the spinors', its
+ * precision the gauge field's (the operator's precision), stride >= volumeCB, parity_offset >= 36*stride: MUGIQ_HIP_ERROR_INVALID_ARGUMENT
+ * if not.  The term is applied inside the one stencil kernel (the accumulators start as A psi instead of psi), in the spinors' precision.
+ * For the solver, (v_n, sigma_n) are eigenpairs of H = g5 M_clov. */
+int mugiq_hip_wilson_clover_apply(const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec, const MugiqHipGaugeField *gauge,
+                                  const MugiqHipCloverField *clover, double kappa, int opType, double scale, const MugiqHipComm *comm,
+                                  void *stream);
+int mugiq_hip_compute_evals_clover(const MugiqHipSpinorField *eVecs_h, int nEv, const MugiqHipGaugeField *gauge,
+                                   const MugiqHipCloverField *clover, double kappa, int opType, int massNormalization, double *lambda_h,
+                                   double *residual_h, double *sigma_h, const MugiqHipComm *comm, void *stream);
+int mugiq_hip_wilson_clover_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                                  const MugiqHipCloverField *clover, double kappa, const MugiqHipSpinorField *eVecs_h, const double *sigma_h,
+                                  int nEv, double tol, int maxIter, int *iters_out, double *relres_out, const MugiqHipComm *comm,
+                                  void *stream);
 
 /* What Displace asks of QUDA's ColorSpinorField for its auxiliary vector (lib/displace.cpp:26-30: ColorSpinorField::Create
  * with QUDA_ZERO_FIELD_CREATE and setPrecision(coarsePrec_); :42,:50-51: operator=; :59: blas::zero), for hosts that do not

@@ -137,14 +137,83 @@ inline bool wilsonSolve(const std::vector<ColorSpinorField> &x, const std::vecto
   check(st);
   return true;
 }
+// ---- the clover term (csrc/clover.hip; new): a device field the holder owns, and the three calls above for the Wilson-clover operator ----
+class CloverField {
+public:
+  CloverField(const int X[4], int precision) { check(mugiq_hip_alloc_clover(&f_, X, precision)); }
+  ~CloverField() { mugiq_hip_free_clover(&f_); }
+  CloverField(const CloverField &) = delete;
+  CloverField &operator=(const CloverField &) = delete;
+  // A(x) from the border-extended links; coeff = kappa * c_sw (QUDA's clover_coeff).  The gauge precision of the operator calls must be
+  // this field's.
+  void compute(const GaugeField &gauge, double coeff, const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+    check(mugiq_hip_compute_clover(&f_, &gauge, coeff, comm, stream));
+  }
+  const MugiqHipCloverField *desc() const { return &f_; }
+  static size_t bytes(const int X[4], int precision) { return mugiq_hip_clover_bytes(X, precision); }
+
+private:
+  MugiqHipCloverField f_{};
+};
+inline void wilsonApply(const std::vector<ColorSpinorField> &dst, const std::vector<ColorSpinorField> &src, const GaugeField &gauge,
+                        const CloverField &clover, double kappa, int opType = MUGIQ_HIP_EIG_OPERATOR_M, double scale = 1.0,
+                        const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (src.empty() || dst.size() != src.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "wilsonApply: size mismatch");
+  check(mugiq_hip_wilson_clover_apply(dst.data(), src.data(), (int)src.size(), &gauge, clover.desc(), kappa, opType, scale, comm, stream));
+}
+namespace detail {
+// clover NULL: the unimproved operator
+inline void computeEvals(const std::vector<ColorSpinorField> &eVecs, const GaugeField &gauge, const MugiqHipCloverField *clover, double kappa,
+                         int opType, bool massNormalization, std::vector<std::complex<double>> &lambda, std::vector<double> &residual,
+                         std::vector<double> &sigma, const MugiqHipComm *comm, void *stream) {
+  if (eVecs.empty()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "computeEvals: no eigenvectors");
+  lambda.assign(eVecs.size(), std::complex<double>(0.0, 0.0));
+  residual.assign(eVecs.size(), 0.0);
+  sigma.assign(eVecs.size(), 0.0);
+  check(mugiq_hip_compute_evals_clover(eVecs.data(), (int)eVecs.size(), &gauge, clover, kappa, opType, massNormalization ? 1 : 0,
+                                       reinterpret_cast<double *>(lambda.data()), residual.data(), sigma.data(), comm, stream));
+  if (opType == MUGIQ_HIP_EIG_OPERATOR_M || opType == MUGIQ_HIP_EIG_OPERATOR_MDAG) sigma.clear();
+}
+inline bool wilsonSolve(const std::vector<ColorSpinorField> &x, const std::vector<ColorSpinorField> &b, const GaugeField &gauge,
+                        const MugiqHipCloverField *clover, double kappa, const std::vector<ColorSpinorField> &eVecs, const std::vector<double> &sigma,
+                        double tol, int maxIter, std::vector<int> &iters, std::vector<double> &relres, const MugiqHipComm *comm, void *stream) {
+  if (b.empty() || x.size() != b.size() || sigma.size() != eVecs.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "wilsonSolve: size mismatch");
+  iters.assign(b.size(), 0);
+  relres.assign(b.size(), 0.0);
+  const int st = mugiq_hip_wilson_clover_solve(x.data(), b.data(), (int)b.size(), &gauge, clover, kappa, eVecs.empty() ? nullptr : eVecs.data(),
+                                               eVecs.empty() ? nullptr : sigma.data(), (int)eVecs.size(), tol, maxIter, iters.data(),
+                                               relres.data(), comm, stream);
+  if (st == MUGIQ_HIP_ERROR_NOT_CONVERGED) return false;
+  check(st);
+  return true;
+}
+}  // namespace detail
+inline void computeEvals(const std::vector<ColorSpinorField> &eVecs, const GaugeField &gauge, const CloverField &clover, double kappa, int opType,
+                         bool massNormalization, std::vector<std::complex<double>> &lambda, std::vector<double> &residual,
+                         std::vector<double> &sigma, const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  detail::computeEvals(eVecs, gauge, clover.desc(), kappa, opType, massNormalization, lambda, residual, sigma, comm, stream);
+}
+// (v_n, sigma_n): eigenpairs of H = g5 M_clov
+inline bool wilsonSolve(const std::vector<ColorSpinorField> &x, const std::vector<ColorSpinorField> &b, const GaugeField &gauge,
+                        const CloverField &clover, double kappa, const std::vector<ColorSpinorField> &eVecs, const std::vector<double> &sigma,
+                        double tol, int maxIter, std::vector<int> &iters, std::vector<double> &relres, const MugiqHipComm *comm = nullptr,
+                        void *stream = nullptr) {
+  return detail::wilsonSolve(x, b, gauge, clover.desc(), kappa, eVecs, sigma, tol, maxIter, iters, relres, comm, stream);
+}
 // The members of the reference's Eigsolve_Mugiq (include/eigsolve_mugiq.h) that work on eigenvectors somebody else computed
 class Eigsolve_Mugiq {
 public:
+  // the Wilson-clover operator: `clover` must outlive the object
+  Eigsolve_Mugiq(std::vector<ColorSpinorField> eVecs, const GaugeField &gauge, const CloverField &clover, double kappa, int opType,
+                 const MugiqHipComm *comm = nullptr, bool massNormalization = false, void *stream = nullptr)
+      : Eigsolve_Mugiq(std::move(eVecs), gauge, kappa, opType, comm, massNormalization, stream) {
+    clover_ = clover.desc();
+  }
   Eigsolve_Mugiq(std::vector<ColorSpinorField> eVecs, const GaugeField &gauge, double kappa, int opType, const MugiqHipComm *comm = nullptr,
                  bool massNormalization = false, void *stream = nullptr)
       : eVecs_(std::move(eVecs)), gauge_(gauge), kappa_(kappa), opType_(opType), comm_(comm), mass_(massNormalization), stream_(stream),
         eVals_quda_(eVecs_.size()) {}
-  void computeEvals() { mugiq_hip::computeEvals(eVecs_, gauge_, kappa_, opType_, mass_, eVals_, evals_res_, eVals_sigma_, comm_, stream_); }
+  void computeEvals() { detail::computeEvals(eVecs_, gauge_, clover_, kappa_, opType_, mass_, eVals_, evals_res_, eVals_sigma_, comm_, stream_); }
   // lib/eigsolve_mugiq.cpp:317-337, the two line formats character for character (the interface contract of its log)
   void printEvals(FILE *out = stdout) const {
     if (comm_ && comm_->rank != 0) return;
@@ -164,7 +233,8 @@ public:
     const bool defl = opType_ == MUGIQ_HIP_EIG_OPERATOR_H && eVals_sigma_.size() == eVecs_.size();
     static const std::vector<ColorSpinorField> none;
     static const std::vector<double> noSigma;
-    return wilsonSolve(x, b, gauge_, kappa_, defl ? eVecs_ : none, defl ? eVals_sigma_ : noSigma, tol, maxIter, iters, relres, comm_, stream_);
+    return detail::wilsonSolve(x, b, gauge_, clover_, kappa_, defl ? eVecs_ : none, defl ? eVals_sigma_ : noSigma, tol, maxIter, iters, relres, comm_,
+                               stream_);
   }
   std::vector<ColorSpinorField> &getEvecs() { return eVecs_; }
   std::vector<std::complex<double>> *getEvals() { return &eVals_; }
@@ -175,6 +245,7 @@ public:
 private:
   std::vector<ColorSpinorField> eVecs_;
   GaugeField gauge_;
+  const MugiqHipCloverField *clover_ = nullptr;  // NULL: the unimproved operator
   double kappa_;
   int opType_;
   const MugiqHipComm *comm_;

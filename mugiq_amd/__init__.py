@@ -7,7 +7,7 @@ from . import _lib
 
 _lib.load()
 
-from .fields import SpinorField, GaugeField, CoarseField, Transfer, FLOAT2, FLOAT4  # noqa: E402
+from .fields import SpinorField, GaugeField, CloverField, CoarseField, Transfer, FLOAT2, FLOAT4  # noqa: E402
 from .operators import (  # noqa: E402
     copyGammaCoeffStructToSymbol, copyGammaMapStructToSymbol, gammaTables, GammaName,
     performLoopContraction, performLoopContractionBatched, performCovariantDisplacementVector, packFace, exchangeGhostVec,

@@ -37,6 +37,16 @@ class GaugeDesc(ctypes.Structure):
                 ("parity_offset", ctypes.c_int64)]
 
 
+class CloverDesc(ctypes.Structure):
+    """MugiqHipCloverField (include/mugiq_hip.h)."""
+    _fields_ = [("data", ctypes.c_void_p),
+                ("precision", ctypes.c_int),
+                ("X", ctypes.c_int * 4),
+                ("volumeCB", ctypes.c_int),
+                ("stride", ctypes.c_int),
+                ("parity_offset", ctypes.c_int64)]
+
+
 class CoarseDesc(ctypes.Structure):
     """MugiqHipCoarseField (include/mugiq_hip.h)."""
     _fields_ = [("data", ctypes.c_void_p), ("precision", ctypes.c_int), ("nSpin", ctypes.c_int), ("nColor", ctypes.c_int),
@@ -60,6 +70,7 @@ _I4 = ctypes.POINTER(ctypes.c_int)
 _VP = ctypes.c_void_p
 _SP = ctypes.POINTER(SpinorDesc)
 _GP = ctypes.POINTER(GaugeDesc)
+_CP = ctypes.POINTER(CloverDesc)
 
 # name -> (restype, argtypes); every symbol include/mugiq_hip.h declares
 SIGNATURES = {
@@ -143,6 +154,16 @@ SIGNATURES = {
     "mugiq_hip_project_vector": (ctypes.c_int, [_SP, _SP, _SP, ctypes.c_int, _VP, _VP]),
     "mugiq_hip_wilson_solve": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, ctypes.c_double, _SP, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
                                               ctypes.c_double, ctypes.c_int, _I4, ctypes.POINTER(ctypes.c_double), _VP, _VP]),
+    "mugiq_hip_clover_bytes": (ctypes.c_size_t, [_I4, ctypes.c_int]),
+    "mugiq_hip_alloc_clover": (ctypes.c_int, [_CP, _I4, ctypes.c_int]),
+    "mugiq_hip_free_clover": (ctypes.c_int, [_CP]),
+    "mugiq_hip_compute_clover": (ctypes.c_int, [_CP, _GP, ctypes.c_double, _VP, _VP]),
+    "mugiq_hip_wilson_clover_apply": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.c_int, ctypes.c_double, _VP, _VP]),
+    "mugiq_hip_compute_evals_clover": (ctypes.c_int, [_SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                      ctypes.POINTER(ctypes.c_double), _VP, _VP]),
+    "mugiq_hip_wilson_clover_solve": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, _SP, ctypes.POINTER(ctypes.c_double),
+                                                     ctypes.c_int, ctypes.c_double, ctypes.c_int, _I4, ctypes.POINTER(ctypes.c_double), _VP, _VP]),
     "mugiq_hip_prolongate_batched": (ctypes.c_int, [_SP, ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),
     "mugiq_hip_prolongate_contract_batched": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(CoarseDesc), ctypes.POINTER(ctypes.c_double),
                                                              ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),

@@ -103,6 +103,11 @@ int deflate_low_modes(const MugiqHipSpinorField *dst, const MugiqHipSpinorField 
                       const double *sigma, int nEv, int gamma5, double *overlaps_h, const MugiqHipComm *comm, hipStream_t stream,
                       const char *who);
 int entry_pack_capacity(const MugiqHipSpinorField &ev, const int *kvals, int nK);
+// csrc/wilson.hip: the gauge field of an operator call against the local dims X and the partitioned axes; comm -> part[4]
+int check_gauge(const MugiqHipGaugeField *U, const int X[4], const int part[4], const char *who);
+int check_comm(const MugiqHipComm *comm, int part[4], bool needSums, const char *who);
+// csrc/clover.hip: descriptor bounds; X != NULL: and the geometry of the fields it is applied to
+int validate_clover(const MugiqHipCloverField *C, const int X[4], int volumeCB, const char *who);
 }  // namespace mugiq
 #include <vector>
 namespace mugiq {

@@ -1,8 +1,9 @@
-// The unimproved Wilson operator on the fields this library already holds, and what rests on it: the eigenpair check of
+// The Wilson and Wilson-clover operators on the fields this library already holds, and what rests on them: the eigenpair check of
 // Eigsolve_Mugiq::computeEvals (lib/eigsolve_mugiq.cpp:289-315), projectVector (:340-348) and a CG on the normal equations started
-// from the low-mode part.  Clover and twisted-mass terms, even-odd preconditioning and mixed precision are out of scope.
+// from the low-mode part.  Twisted-mass terms, the inverse clover term, even-odd preconditioning and mixed precision are out of scope.
 //
-//   M psi(x) = psi(x) - kappa sum_mu [ (1 - g_mu) U_mu(x) psi(x+mu) + (1 + g_mu) U_mu^dag(x-mu) psi(x-mu) ]
+//   M psi(x) = A(x) psi(x) - kappa sum_mu [ (1 - g_mu) U_mu(x) psi(x+mu) + (1 + g_mu) U_mu^dag(x-mu) psi(x-mu) ]
+//   A = 1 (Wilson) | the clover term of a MugiqHipCloverField (csrc/clover.hip): two Hermitian 6 x 6 blocks per site, which commute with g5
 //   g_x, g_y, g_z, g_t = Gamma_1, Gamma_2, Gamma_4, Gamma_8 of the library's table, g5 = Gamma_15 = diag(1, 1, -1, -1)
 //
 // Links are applied as stored (boundary phases, anisotropy: the host's business; no unitarity assumed).  M^dag = g5 M g5 is the same
@@ -14,7 +15,9 @@
 // first two).  NB results (24 reals each) stay in registers across the hops; the diagonal term, kappa, g5 and the overall scale
 // are folded in, nothing is written per direction.  NB = 4 for fp64 and 8 for fp32 fields: 192 accumulator registers either way,
 // which with the link, one neighbour spinor and the index arithmetic fits the 512 registers a lane of a 2-wave workgroup may use
-// without scratch (checked with -Rpass-analysis=kernel-resource-usage; DESIGN.md section 12).
+// without scratch (checked with -Rpass-analysis=kernel-resource-usage; DESIGN.md section 4.5).
+// CLOVER: the accumulators start as A(x) psi_v(x) instead of psi_v(x).  One packed block (36 reals) is loaded at a time and applied to the
+// NB vectors; it is dead before the hops start.  A is Hermitian and commutes with g5, so the dagger and gamma5 flags need nothing more.
 #include "internal.h"
 
 #include <algorithm>
@@ -176,9 +179,61 @@ __device__ inline void wilson_hop(Cplx<F> (&acc)[NB][12], const WilsonPtrs<NB> &
   }
 }
 
-template <typename F, int ORDER, typename FG, int NB>
+// the clover field of a launch (nothing for the unimproved operator)
+template <bool CLOVER> struct CloverArg {};
+template <> struct CloverArg<true> {
+  const void *data;
+  int stride;
+  int64_t po;
+};
+
+// acc_v <- A(x) acc_v: block b of the packed field (3 pairs of diagonal reals, 15 strictly-lower entries, row by row) on spins 2b, 2b + 1
+template <typename F, typename FG, int NB>
+__device__ inline void clover_apply(Cplx<F> (&acc)[NB][12], const CloverArg<true> &C, int pty, int x_cb, int nv) {
+  typedef FG cvec2 __attribute__((ext_vector_type(2)));
+  const MUGIQ_GLOBAL cvec2 *p = as_global(reinterpret_cast<const cvec2 *>(C.data)) + pty * C.po + x_cb;
+#pragma unroll
+  for (int b = 0; b < 2; b++) {
+    F d[6];
+    Cplx<F> l[15];
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+      const cvec2 t = p[(int64_t)(b * 18 + q) * C.stride];
+      d[2 * q] = (F)t.x;
+      d[2 * q + 1] = (F)t.y;
+    }
+#pragma unroll
+    for (int k = 0; k < 15; k++) {
+      const cvec2 t = p[(int64_t)(b * 18 + 3 + k) * C.stride];
+      l[k] = Cplx<F>{(F)t.x, (F)t.y};
+    }
+#pragma unroll
+    for (int v = 0; v < NB; v++) {
+      if (v < nv) {
+        Cplx<F> in[6], out[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+          in[i] = acc[v][b * 6 + i];
+          out[i] = Cplx<F>{d[i] * in[i].re, d[i] * in[i].im};
+        }
+#pragma unroll
+        for (int i = 1; i < 6; i++)
+#pragma unroll
+          for (int j = 0; j < i; j++) {
+            const Cplx<F> a = l[i * (i - 1) / 2 + j];  // A_ij; A_ji = conj(A_ij)
+            cmadd(out[i], a, in[j]);
+            cmadd_conj(out[j], a, in[i]);
+          }
+#pragma unroll
+        for (int i = 0; i < 6; i++) acc[v][b * 6 + i] = out[i];
+      }
+    }
+  }
+}
+
+template <typename F, int ORDER, typename FG, int NB, bool CLOVER>
 __global__ __launch_bounds__(kWilsonThreads) void wilson_kernel(WilsonPtrs<NB> P, const FG *U, WilsonGeom g, int nv, F kappa, F scale,
-                                                                int dagger, int gamma5) {
+                                                                int dagger, int gamma5, CloverArg<CLOVER> C) {
   const int site = blockIdx.x * kWilsonThreads + threadIdx.x;
   if (site >= 2 * g.volumeCB) return;
   const int pty = site >= g.volumeCB ? 1 : 0;
@@ -189,6 +244,7 @@ __global__ __launch_bounds__(kWilsonThreads) void wilson_kernel(WilsonPtrs<NB> P
 #pragma unroll
   for (int v = 0; v < NB; v++)
     if (v < nv) load12<F, ORDER>(acc[v], P.src[v], g.stride, g.po, pty, x_cb);
+  if constexpr (CLOVER) clover_apply<F, FG, NB>(acc, C, pty, x_cb, nv);
   const F sgn = dagger ? F(-1) : F(1), mk = -kappa;
   wilson_hop<F, ORDER, FG, NB, 0, 1>(acc, P, U, g, coord, pty, nv, mk, sgn);
   wilson_hop<F, ORDER, FG, NB, 0, 0>(acc, P, U, g, coord, pty, nv, mk, sgn);
@@ -380,6 +436,7 @@ struct OpContext {
   hipStream_t stream;
   unsigned char *send;  // kOpBlock * ghost_bytes
   const char *who;
+  const MugiqHipCloverField *clover = nullptr;  // NULL: the unimproved operator
 };
 
 bool same_layout(const MugiqHipSpinorField &a, const MugiqHipSpinorField &b) {
@@ -390,13 +447,15 @@ void span_of(const MugiqHipSpinorField &f, uintptr_t *a, uintptr_t *b) {
   *b = *a + (uintptr_t)(f.parity_offset + (int64_t)12 * f.stride) * 2 * f.precision;
 }
 
-int check_gauge(const MugiqHipGaugeField *U, const MugiqHipSpinorField &ref, const int part[4], const char *who) {
+}  // namespace
+
+int check_gauge(const MugiqHipGaugeField *U, const int X[4], const int part[4], const char *who) {
   MUGIQ_REQUIRE(U != nullptr && U->data != nullptr, "%s: gauge field is NULL", who);
   MUGIQ_REQUIRE(U->precision == 4 || U->precision == 8, "%s: gauge precision %d", who, U->precision);
   long long volEx = 1;
   int sumR = 0;
   for (int d = 0; d < 4; d++) {
-    MUGIQ_REQUIRE(U->X[d] == ref.X[d], "%s: gauge X[%d] = %d differs from the spinor's %d", who, d, U->X[d], ref.X[d]);
+    MUGIQ_REQUIRE(U->X[d] == X[d], "%s: gauge X[%d] = %d differs from the spinor's %d", who, d, U->X[d], X[d]);
     MUGIQ_REQUIRE(U->R[d] >= 0, "%s: gauge R[%d] = %d is negative", who, d, U->R[d]);
     MUGIQ_REQUIRE(!part[d] || U->R[d] >= 1, "%s: dimension %d is partitioned but the gauge field has no border along it (R = 0)", who, d);
     volEx *= U->X[d] + 2 * U->R[d];
@@ -416,6 +475,17 @@ int check_comm(const MugiqHipComm *comm, int part[4], bool needSums, const char 
     MUGIQ_REQUIRE(!any || comm->sendrecv != nullptr, "%s: comm->sendrecv is NULL", who);
     MUGIQ_REQUIRE(!(needSums && comm->size > 1) || (comm->reduce_space && comm->gather_time && comm->bcast), "%s: a comm callback is NULL", who);
   }
+  return MUGIQ_HIP_SUCCESS;
+}
+
+namespace {
+
+// the clover field of an operator call (NULL: none): geometry of the spinors, precision of the gauge field
+int check_clover(const MugiqHipCloverField *C, const MugiqHipSpinorField &ref, const MugiqHipGaugeField *U, const char *who) {
+  if (C == nullptr) return MUGIQ_HIP_SUCCESS;
+  if (int st = validate_clover(C, ref.X, ref.volumeCB, who)) return st;
+  MUGIQ_REQUIRE(C->precision == U->precision, "%s: clover precision %d differs from the gauge precision %d (the operator's precision)", who,
+                C->precision, U->precision);
   return MUGIQ_HIP_SUCCESS;
 }
 
@@ -444,7 +514,7 @@ int exchange_block(const OpContext &c, const MugiqHipSpinorField *f, int n) {
   return MUGIQ_HIP_SUCCESS;
 }
 
-template <typename F, int ORDER, typename FG>
+template <typename F, int ORDER, typename FG, bool CLOVER>
 int launch_stencil(const OpContext &c, const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int n, int dagger, int gamma5, double scale) {
   constexpr int NB = wilson_nb<F>();
   WilsonGeom g;
@@ -461,6 +531,8 @@ int launch_stencil(const OpContext &c, const MugiqHipSpinorField *dst, const Mug
   g.po = s0.parity_offset;
   g.gstride = c.U->stride;
   g.gpo = c.U->parity_offset;
+  CloverArg<CLOVER> C;
+  if constexpr (CLOVER) C = CloverArg<true>{c.clover->data, c.clover->stride, c.clover->parity_offset};
   const dim3 grid((2 * s0.volumeCB + kWilsonThreads - 1) / kWilsonThreads), block(kWilsonThreads);
   for (int v0 = 0; v0 < n; v0 += NB) {
     const int nv = std::min(NB, n - v0);
@@ -472,8 +544,8 @@ int launch_stencil(const OpContext &c, const MugiqHipSpinorField *dst, const Mug
       for (int d = 0; d < 4; d++)
         for (int b = 0; b < 2; b++) P.ghost[v][d][b] = src[w].ghost[d][b];
     }
-    hipLaunchKernelGGL((wilson_kernel<F, ORDER, FG, NB>), grid, block, 0, c.stream, P, static_cast<const FG *>(c.U->data), g, nv, (F)c.kappa,
-                       (F)scale, dagger, gamma5);
+    hipLaunchKernelGGL((wilson_kernel<F, ORDER, FG, NB, CLOVER>), grid, block, 0, c.stream, P, static_cast<const FG *>(c.U->data), g, nv,
+                       (F)c.kappa, (F)scale, dagger, gamma5, C);
     MUGIQ_CHECK_HIP(hipGetLastError());
   }
   return MUGIQ_HIP_SUCCESS;
@@ -485,10 +557,15 @@ int apply_simple(const OpContext &c, const MugiqHipSpinorField *dst, const Mugiq
   int st = exchange_block(c, src, n);
   if (st) return st;
   const int prec = src[0].precision, order = src[0].field_order, gp = c.U->precision;
+  const bool clover = c.clover != nullptr;  // its precision is the gauge field's (check_clover)
 #define MUGIQ_WILSON_CASE(P_, O_, F_)                                                                      \
-  if (prec == P_ && order == O_)                                                                           \
-    return gp == 8 ? launch_stencil<F_, O_, double>(c, dst, src, n, dagger, gamma5, scale)                 \
-                   : launch_stencil<F_, O_, float>(c, dst, src, n, dagger, gamma5, scale);
+  if (prec == P_ && order == O_) {                                                                         \
+    if (clover)                                                                                            \
+      return gp == 8 ? launch_stencil<F_, O_, double, true>(c, dst, src, n, dagger, gamma5, scale)         \
+                     : launch_stencil<F_, O_, float, true>(c, dst, src, n, dagger, gamma5, scale);         \
+    return gp == 8 ? launch_stencil<F_, O_, double, false>(c, dst, src, n, dagger, gamma5, scale)          \
+                   : launch_stencil<F_, O_, float, false>(c, dst, src, n, dagger, gamma5, scale);          \
+  }
   MUGIQ_WILSON_CASE(8, 2, double)
   MUGIQ_WILSON_CASE(8, 4, double)
   MUGIQ_WILSON_CASE(4, 2, float)
@@ -600,10 +677,9 @@ int check_vector_set(const MugiqHipSpinorField *f, int n, const char *who, const
 
 using namespace mugiq;
 
-extern "C" {
-
-int mugiq_hip_wilson_apply(const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec, const MugiqHipGaugeField *gauge,
-                           double kappa, int opType, double scale, const MugiqHipComm *comm, void *stream) {
+// the three operator entries, for both operators (clover NULL: the unimproved one)
+static int wilson_apply_impl(const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec, const MugiqHipGaugeField *gauge,
+                             const MugiqHipCloverField *clover, double kappa, int opType, double scale, const MugiqHipComm *comm, void *stream) {
   const char *who = "wilsonApply";
   MUGIQ_REQUIRE(dst_h != nullptr && src_h != nullptr, "%s: NULL argument", who);
   MUGIQ_REQUIRE(nVec >= 1, "%s: nVec = %d must be >= 1", who, nVec);
@@ -622,7 +698,8 @@ int mugiq_hip_wilson_apply(const MugiqHipSpinorField *dst_h, const MugiqHipSpino
     }
   }
   if ((st = check_comm(comm, part, false, who))) return st;
-  if ((st = check_gauge(gauge, src_h[0], part, who))) return st;
+  if ((st = check_gauge(gauge, src_h[0].X, part, who))) return st;
+  if ((st = check_clover(clover, src_h[0], gauge, who))) return st;
   for (int d = 0; d < 4; d++)
     for (int i = 0; part[d] && i < nVec; i++)
       MUGIQ_REQUIRE(src_h[i].ghost[d][0] != nullptr && src_h[i].ghost[d][1] != nullptr,
@@ -635,7 +712,7 @@ int mugiq_hip_wilson_apply(const MugiqHipSpinorField *dst_h, const MugiqHipSpino
   const size_t tmpB = normal_op(opType) ? (size_t)kOpBlock * (body_bytes(src_h[0], prec) + ghost_bytes(src_h[0], prec, part)) : 0;
   void *ws = nullptr;
   if ((st = stream_operator_workspace(&ws, sendB + tmpB + 256, s))) return st;
-  OpContext c{gauge, comm, {part[0], part[1], part[2], part[3]}, kappa, s, static_cast<unsigned char *>(ws), who};
+  OpContext c{gauge, comm, {part[0], part[1], part[2], part[3]}, kappa, s, static_cast<unsigned char *>(ws), who, clover};
   MugiqHipSpinorField tmp[kOpBlock];
   unsigned char *cur = c.send + sendB;
   if (tmpB) carve_fields(&cur, src_h[0], prec, part, kOpBlock, tmp);
@@ -644,9 +721,9 @@ int mugiq_hip_wilson_apply(const MugiqHipSpinorField *dst_h, const MugiqHipSpino
   return MUGIQ_HIP_SUCCESS;
 }
 
-int mugiq_hip_compute_evals(const MugiqHipSpinorField *eVecs_h, int nEv, const MugiqHipGaugeField *gauge, double kappa, int opType,
-                            int massNormalization, double *lambda_h, double *residual_h, double *sigma_h, const MugiqHipComm *comm,
-                            void *stream) {
+static int compute_evals_impl(const MugiqHipSpinorField *eVecs_h, int nEv, const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover,
+                              double kappa, int opType, int massNormalization, double *lambda_h, double *residual_h, double *sigma_h,
+                              const MugiqHipComm *comm, void *stream) {
   const char *who = "computeEvals";
   MUGIQ_REQUIRE(eVecs_h != nullptr && lambda_h != nullptr && residual_h != nullptr, "%s: NULL argument", who);
   MUGIQ_REQUIRE(nEv >= 1, "%s: nEv = %d must be >= 1", who, nEv);
@@ -657,7 +734,8 @@ int mugiq_hip_compute_evals(const MugiqHipSpinorField *eVecs_h, int nEv, const M
   int st, part[4];
   if ((st = check_vector_set(eVecs_h, nEv, who, "eVecs"))) return st;
   if ((st = check_comm(comm, part, true, who))) return st;
-  if ((st = check_gauge(gauge, eVecs_h[0], part, who))) return st;
+  if ((st = check_gauge(gauge, eVecs_h[0].X, part, who))) return st;
+  if ((st = check_clover(clover, eVecs_h[0], gauge, who))) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
   // work memory: 3 blocks of kOpBlock vectors of the eigenvectors' storage (a copy with ghost zones, w = A v, the intermediate of a
@@ -668,7 +746,7 @@ int mugiq_hip_compute_evals(const MugiqHipSpinorField *eVecs_h, int nEv, const M
   const size_t fieldB = body_bytes(e0, prec) + ghost_bytes(e0, prec, part);
   void *ws = nullptr;
   if ((st = stream_operator_workspace(&ws, sendB + 3 * kOpBlock * fieldB + reduction_bytes(e0) + 256, s))) return st;
-  OpContext c{gauge, comm, {part[0], part[1], part[2], part[3]}, kappa, s, static_cast<unsigned char *>(ws), who};
+  OpContext c{gauge, comm, {part[0], part[1], part[2], part[3]}, kappa, s, static_cast<unsigned char *>(ws), who, clover};
   MugiqHipSpinorField vc[kOpBlock], w[kOpBlock], tmp[kOpBlock];
   unsigned char *cur = c.send + sendB;
   carve_fields(&cur, e0, prec, part, kOpBlock, vc);
@@ -706,6 +784,8 @@ int mugiq_hip_compute_evals(const MugiqHipSpinorField *eVecs_h, int nEv, const M
   return MUGIQ_HIP_SUCCESS;
 }
 
+extern "C" {
+
 int mugiq_hip_project_vector(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in, const MugiqHipSpinorField *eVecs_h, int nEv,
                              const MugiqHipComm *comm, void *stream) {
   const char *who = "projectVector";
@@ -725,9 +805,11 @@ int mugiq_hip_project_vector(const MugiqHipSpinorField *out, const MugiqHipSpino
   return deflate_low_modes(out, in, 1, eVecs_h, minusOne.data(), nEv, 0, nullptr, comm, s, who);
 }
 
-int mugiq_hip_wilson_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
-                           double kappa, const MugiqHipSpinorField *eVecs_h, const double *sigma_h, int nEv, double tol, int maxIter,
-                           int *iters_out, double *relres_out, const MugiqHipComm *comm, void *stream) {
+}  // extern "C"
+
+static int wilson_solve_impl(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                             const MugiqHipCloverField *clover, double kappa, const MugiqHipSpinorField *eVecs_h, const double *sigma_h, int nEv,
+                             double tol, int maxIter, int *iters_out, double *relres_out, const MugiqHipComm *comm, void *stream) {
   const char *who = "wilsonSolve";
   MUGIQ_REQUIRE(x_h != nullptr && b_h != nullptr && iters_out != nullptr && relres_out != nullptr, "%s: NULL argument", who);
   MUGIQ_REQUIRE(nVec >= 1, "%s: nVec = %d must be >= 1", who, nVec);
@@ -754,7 +836,8 @@ int mugiq_hip_wilson_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorF
   }
   if (nEv && (st = check_vector_set(eVecs_h, nEv, who, "eVecs"))) return st;
   if ((st = check_comm(comm, part, true, who))) return st;
-  if ((st = check_gauge(gauge, b_h[0], part, who))) return st;
+  if ((st = check_gauge(gauge, b_h[0].X, part, who))) return st;
+  if ((st = check_clover(clover, b_h[0], gauge, who))) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
   // work memory: r, p, t = M p, q = M^dag t for a block of kOpBlock right-hand sides (fp64, with ghost zones), whatever nVec
@@ -763,7 +846,7 @@ int mugiq_hip_wilson_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorF
   const size_t fieldB = body_bytes(b0, 8) + ghost_bytes(b0, 8, part);
   void *ws = nullptr;
   if ((st = stream_operator_workspace(&ws, sendB + 4 * kOpBlock * fieldB + reduction_bytes(b0) + 256, s))) return st;
-  OpContext c{gauge, comm, {part[0], part[1], part[2], part[3]}, kappa, s, static_cast<unsigned char *>(ws), who};
+  OpContext c{gauge, comm, {part[0], part[1], part[2], part[3]}, kappa, s, static_cast<unsigned char *>(ws), who, clover};
   MugiqHipSpinorField r[kOpBlock], p[kOpBlock], t[kOpBlock], q[kOpBlock];
   unsigned char *cur = c.send + sendB;
   carve_fields(&cur, b0, 8, part, kOpBlock, r);
@@ -877,6 +960,41 @@ int mugiq_hip_wilson_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorF
     return set_error(MUGIQ_HIP_ERROR_NOT_CONVERGED, "%s: not every right-hand side reached tol = %g within maxIter = %d (x, iters_out, relres_out are filled)",
                      who, tol, maxIter);
   return MUGIQ_HIP_SUCCESS;
+}
+
+extern "C" {
+
+int mugiq_hip_wilson_apply(const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec, const MugiqHipGaugeField *gauge,
+                           double kappa, int opType, double scale, const MugiqHipComm *comm, void *stream) {
+  return wilson_apply_impl(dst_h, src_h, nVec, gauge, nullptr, kappa, opType, scale, comm, stream);
+}
+int mugiq_hip_wilson_clover_apply(const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec, const MugiqHipGaugeField *gauge,
+                                  const MugiqHipCloverField *clover, double kappa, int opType, double scale, const MugiqHipComm *comm,
+                                  void *stream) {
+  return wilson_apply_impl(dst_h, src_h, nVec, gauge, clover, kappa, opType, scale, comm, stream);
+}
+
+int mugiq_hip_compute_evals(const MugiqHipSpinorField *eVecs_h, int nEv, const MugiqHipGaugeField *gauge, double kappa, int opType,
+                            int massNormalization, double *lambda_h, double *residual_h, double *sigma_h, const MugiqHipComm *comm,
+                            void *stream) {
+  return compute_evals_impl(eVecs_h, nEv, gauge, nullptr, kappa, opType, massNormalization, lambda_h, residual_h, sigma_h, comm, stream);
+}
+int mugiq_hip_compute_evals_clover(const MugiqHipSpinorField *eVecs_h, int nEv, const MugiqHipGaugeField *gauge,
+                                   const MugiqHipCloverField *clover, double kappa, int opType, int massNormalization, double *lambda_h,
+                                   double *residual_h, double *sigma_h, const MugiqHipComm *comm, void *stream) {
+  return compute_evals_impl(eVecs_h, nEv, gauge, clover, kappa, opType, massNormalization, lambda_h, residual_h, sigma_h, comm, stream);
+}
+
+int mugiq_hip_wilson_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                           double kappa, const MugiqHipSpinorField *eVecs_h, const double *sigma_h, int nEv, double tol, int maxIter,
+                           int *iters_out, double *relres_out, const MugiqHipComm *comm, void *stream) {
+  return wilson_solve_impl(x_h, b_h, nVec, gauge, nullptr, kappa, eVecs_h, sigma_h, nEv, tol, maxIter, iters_out, relres_out, comm, stream);
+}
+int mugiq_hip_wilson_clover_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                                  const MugiqHipCloverField *clover, double kappa, const MugiqHipSpinorField *eVecs_h, const double *sigma_h,
+                                  int nEv, double tol, int maxIter, int *iters_out, double *relres_out, const MugiqHipComm *comm,
+                                  void *stream) {
+  return wilson_solve_impl(x_h, b_h, nVec, gauge, clover, kappa, eVecs_h, sigma_h, nEv, tol, maxIter, iters_out, relres_out, comm, stream);
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 """The Wilson operator on the device and what Eigsolve_Mugiq does with it (lib/eigsolve_mugiq.cpp:289-348 of the reference):
 computeEvals / printEvals / projectVector, plus a CG on the normal equations started from the low-mode part (csrc/wilson.hip).
 
-The operator is the unimproved Wilson operator in kappa normalisation (no clover term, no twisted mass); see mugiq_hip_wilson_apply
-in include/mugiq_hip.h for the formula and the gamma convention.
+The operator is the Wilson operator in kappa normalisation, unimproved or -- with clover=CloverField -- Wilson-clover (no twisted
+mass); see mugiq_hip_wilson_apply and MugiqHipCloverField in include/mugiq_hip.h for the formulas and the gamma convention.
 """
 import collections
 import ctypes
@@ -41,20 +41,33 @@ def _alloc_ghosts(fields, comm):
                 f.alloc_ghost(d, 0), f.alloc_ghost(d, 1)
 
 
-def wilsonApply(dst, src, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_M, scale=1.0, comm=None):
-    """dst_i = scale * A src_i for lists of SpinorFields (mugiq_hip_wilson_apply); the halo exchange of src is part of the call."""
+def _clover_ptr(clover, keep):
+    if clover is None:
+        return None
+    d = clover.desc()
+    keep.append(d)
+    return ctypes.byref(d)
+
+
+def wilsonApply(dst, src, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_M, scale=1.0, comm=None, clover=None):
+    """dst_i = scale * A src_i for lists of SpinorFields (mugiq_hip_wilson_apply); the halo exchange of src is part of the call.
+    clover: a CloverField of the gauge field's precision for the Wilson-clover operator (mugiq_hip_wilson_clover_apply)."""
     dst, src = list(dst), list(src)
     if len(dst) != len(src) or not src:
         raise _lib.MugiqHipError("wilsonApply: %d dst and %d src vectors (need the same number, at least one)" % (len(dst), len(src)))
     _alloc_ghosts(src, comm)
     keep = []
     g = gauge.desc()
+    if clover is not None:
+        _lib.check(_lib.load().mugiq_hip_wilson_clover_apply(desc_array(dst), desc_array(src), len(src), ctypes.byref(g), _clover_ptr(clover, keep),
+                                                             float(kappa), int(opType), float(scale), _comm_ptr(comm, keep), _stream()))
+        return
     _lib.check(_lib.load().mugiq_hip_wilson_apply(desc_array(dst), desc_array(src), len(src), ctypes.byref(g), float(kappa), int(opType),
                                                   float(scale), _comm_ptr(comm, keep), _stream()))
 
 
-def computeEvals(eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, massNormalization=False, comm=None):
-    """(lambda[nEv] complex, residual[nEv], sigma[nEv] or None) of mugiq_hip_compute_evals."""
+def computeEvals(eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, massNormalization=False, comm=None, clover=None):
+    """(lambda[nEv] complex, residual[nEv], sigma[nEv] or None) of mugiq_hip_compute_evals (clover: ..._clover, the Wilson-clover operator)."""
     ev = list(eVecs)
     n = len(ev)
     lam = (ctypes.c_double * (2 * n))()
@@ -62,8 +75,12 @@ def computeEvals(eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, massNorma
     sig = (ctypes.c_double * n)()
     keep = []
     g = gauge.desc()
-    _lib.check(_lib.load().mugiq_hip_compute_evals(desc_array(ev), n, ctypes.byref(g), float(kappa), int(opType), int(bool(massNormalization)),
-                                                   lam, res, sig, _comm_ptr(comm, keep), _stream()))
+    if clover is not None:
+        _lib.check(_lib.load().mugiq_hip_compute_evals_clover(desc_array(ev), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), int(opType),
+                                                              int(bool(massNormalization)), lam, res, sig, _comm_ptr(comm, keep), _stream()))
+    else:
+        _lib.check(_lib.load().mugiq_hip_compute_evals(desc_array(ev), n, ctypes.byref(g), float(kappa), int(opType), int(bool(massNormalization)),
+                                                       lam, res, sig, _comm_ptr(comm, keep), _stream()))
     has_sigma = int(opType) in (MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H)
     return np.array(lam).view(np.complex128).copy(), np.array(res), (np.array(sig) if has_sigma else None)
 
@@ -76,9 +93,9 @@ def projectVector(out, inp, eVecs, comm=None):
     _lib.check(_lib.load().mugiq_hip_project_vector(ctypes.byref(do), ctypes.byref(di), desc_array(ev), len(ev), _comm_ptr(comm, keep), _stream()))
 
 
-def wilsonSolve(b, gauge, kappa, eVecs=(), sigmas=(), tol=1e-10, maxIter=1000, comm=None, x=None, allow_unconverged=False):
+def wilsonSolve(b, gauge, kappa, eVecs=(), sigmas=(), tol=1e-10, maxIter=1000, comm=None, x=None, allow_unconverged=False, clover=None):
     """x_r = M^-1 b_r by CG on the normal equations, started from the low-mode part when eigenpairs (v_n, sigma_n) of H = g5 M are
-    given (mugiq_hip_wilson_solve).  Returns (x, SolveInfo(iters, relres, converged)); x: new fp64 fields laid out like b unless
+    given (mugiq_hip_wilson_solve; with clover, M is the Wilson-clover operator: mugiq_hip_wilson_clover_solve).  Returns (x, SolveInfo(iters, relres, converged)); x: new fp64 fields laid out like b unless
     given.  A right-hand side that does not reach tol within maxIter raises MugiqHipError (status 5) unless allow_unconverged."""
     b = list(b)
     if not b:
@@ -97,8 +114,13 @@ def wilsonSolve(b, gauge, kappa, eVecs=(), sigmas=(), tol=1e-10, maxIter=1000, c
     keep = []
     g = gauge.desc()
     lib = _lib.load()
-    st = lib.mugiq_hip_wilson_solve(desc_array(x), desc_array(b), n, ctypes.byref(g), float(kappa), desc_array(ev) if ev else None,
-                                    sg if ev else None, len(ev), float(tol), int(maxIter), iters, relres, _comm_ptr(comm, keep), _stream())
+    if clover is not None:
+        st = lib.mugiq_hip_wilson_clover_solve(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa),
+                                               desc_array(ev) if ev else None, sg if ev else None, len(ev), float(tol), int(maxIter), iters,
+                                               relres, _comm_ptr(comm, keep), _stream())
+    else:
+        st = lib.mugiq_hip_wilson_solve(desc_array(x), desc_array(b), n, ctypes.byref(g), float(kappa), desc_array(ev) if ev else None,
+                                        sg if ev else None, len(ev), float(tol), int(maxIter), iters, relres, _comm_ptr(comm, keep), _stream())
     if st != 0 and not (st == STATUS_NOT_CONVERGED and allow_unconverged):
         _lib.check(st)
     return x, SolveInfo(np.array(iters), np.array(relres), st == 0)
@@ -120,10 +142,11 @@ def format_evals(evals, evals_quda, residuals, sigmas=None):
 class Eigsolve_Mugiq:
     """The part of the reference's Eigsolve_Mugiq that runs on eigenvectors somebody else computed: eVecs (SpinorFields), the gauge
     field they belong to, kappa and the form of the operator they are eigenvectors of.  evals_quda: what the eigensolver reported
-    (printed beside the recomputed values; zero if not given)."""
+    (printed beside the recomputed values; zero if not given).  clover: the CloverField of a Wilson-clover operator (None: Wilson)."""
 
-    def __init__(self, eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, comm=None, massNormalization=False, evals_quda=None):
+    def __init__(self, eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, comm=None, massNormalization=False, evals_quda=None, clover=None):
         self.eVecs, self.gauge, self.kappa, self.opType, self.comm = list(eVecs), gauge, float(kappa), int(opType), comm
+        self.clover = clover
         self.massNormalization = bool(massNormalization)
         n = len(self.eVecs)
         self.eVals_quda = np.zeros(n, np.complex128) if evals_quda is None else np.asarray(evals_quda, np.complex128)
@@ -131,7 +154,7 @@ class Eigsolve_Mugiq:
 
     def computeEvals(self):
         self.eVals, self.evals_res, self.eVals_sigma = computeEvals(self.eVecs, self.gauge, self.kappa, self.opType, self.massNormalization,
-                                                                     self.comm)
+                                                                     self.comm, self.clover)
         return self.eVals, self.evals_res, self.eVals_sigma
 
     def printEvals(self, file=None):
@@ -152,4 +175,4 @@ class Eigsolve_Mugiq:
             if sg is None:
                 raise _lib.MugiqHipError("Eigsolve_Mugiq.solve: no sigmas (call computeEvals first or pass them)")
             ev = self.eVecs
-        return wilsonSolve(b, self.gauge, self.kappa, ev, sg, tol, maxIter, self.comm, x, allow_unconverged)
+        return wilsonSolve(b, self.gauge, self.kappa, ev, sg, tol, maxIter, self.comm, x, allow_unconverged, self.clover)

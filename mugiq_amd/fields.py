@@ -176,6 +176,82 @@ class GaugeField:
         return self
 
 
+def clover_lower_index(i, j):
+    """Position of entry (i, j), i > j, of a 6 x 6 block among its 15 strictly-lower ones (row by row); see MugiqHipCloverField."""
+    return i * (i - 1) // 2 + j
+
+
+class CloverField:
+    """The clover term A(x) of the Wilson-clover operator on the local sites: two Hermitian 6 x 6 blocks per site, packed as 36 pairs
+    of reals (MugiqHipCloverField in mugiq_hip.h).  The buffer is a complex tensor: one element = one pair."""
+
+    def __init__(self, X, precision=8, pad=0, device="cuda"):
+        self.X = tuple(int(x) for x in X)
+        assert all(x > 0 and x % 2 == 0 for x in self.X), "local dims must be even"
+        self.precision = int(precision)
+        self.volumeCB = int(np.prod(self.X)) // 2
+        self.stride = self.volumeCB + int(pad)
+        self.parity_offset = 36 * self.stride
+        self.device = torch.device(device)
+        self.data = torch.zeros(2 * self.parity_offset, dtype=_cdtype(precision), device=self.device)
+
+    def desc(self):
+        d = _lib.CloverDesc()
+        d.data = self.data.data_ptr()
+        d.precision = self.precision
+        for i in range(4):
+            d.X[i] = self.X[i]
+        d.volumeCB, d.stride, d.parity_offset = self.volumeCB, self.stride, self.parity_offset
+        return d
+
+    def compute(self, gauge, coeff, comm=None):
+        """Fill the field from the border-extended gauge field (mugiq_hip_compute_clover); coeff = kappa * c_sw.  comm: the GridComm
+        whose partitioned dimensions the gauge field must have a border along."""
+        d, g = self.desc(), gauge.desc()
+        c = comm.c_struct() if comm is not None else None
+        _lib.check(_lib.load().mugiq_hip_compute_clover(
+            ctypes.byref(d), ctypes.byref(g), float(coeff), ctypes.cast(ctypes.byref(c), ctypes.c_void_p) if c is not None else None,
+            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return self
+
+    def _pair_index(self):
+        """pair index of (parity, x_cb, block, pair p of the block): [2, volumeCB, 2, 18]"""
+        p = np.arange(2).reshape(2, 1, 1, 1)
+        x = np.arange(self.volumeCB).reshape(1, -1, 1, 1)
+        b = np.arange(2).reshape(1, 1, 2, 1)
+        q = np.arange(18).reshape(1, 1, 1, 18)
+        return p * self.parity_offset + (b * 18 + q) * self.stride + x
+
+    def set_logical(self, A):
+        """A: dense blocks [2, volumeCB, 2, 6, 6] complex (parity, x_cb, block, row, column).  The real part of the diagonal and the
+        strictly-lower triangle are stored; the upper triangle is implied (A is Hermitian)."""
+        A = np.asarray(A)
+        assert A.shape == (2, self.volumeCB, 2, 6, 6)
+        pairs = np.zeros((2, self.volumeCB, 2, 18), dtype=np.complex128)
+        for q in range(3):
+            pairs[..., q] = A[..., 2 * q, 2 * q].real + 1j * A[..., 2 * q + 1, 2 * q + 1].real
+        for i in range(1, 6):
+            for j in range(i):
+                pairs[..., 3 + clover_lower_index(i, j)] = A[..., i, j]
+        buf = self.data.cpu().numpy()                                                       # pads stay as they are
+        buf[self._pair_index()] = pairs.astype(buf.dtype)
+        self.data.copy_(torch.from_numpy(buf))
+        return self
+
+    def get_logical(self):
+        """dense blocks [2, volumeCB, 2, 6, 6] complex"""
+        pairs = self.data.cpu().numpy()[self._pair_index()]
+        A = np.zeros((2, self.volumeCB, 2, 6, 6), dtype=pairs.dtype)
+        for q in range(3):
+            A[..., 2 * q, 2 * q] = pairs[..., q].real
+            A[..., 2 * q + 1, 2 * q + 1] = pairs[..., q].imag
+        for i in range(1, 6):
+            for j in range(i):
+                A[..., i, j] = pairs[..., 3 + clover_lower_index(i, j)]
+                A[..., j, i] = np.conj(A[..., i, j])
+        return A
+
+
 class CoarseField:
     """Coarse-grid colour-spinor (nSpin 2, nColor n_vec) in FLOAT2 order: a coarse eigenvector of the MG path."""
 

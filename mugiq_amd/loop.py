@@ -299,9 +299,9 @@ class Loop_Mugiq:
         _lib.check(_lib.load().mugiq_hip_loop_deflate(self._handle, dd, ds, nVec, int(bool(gamma5)), buf))
         return _overlap_array(buf, nEv, nVec) if overlaps else None
 
-    def solve(self, b, kappa, tol=1e-10, maxIter=1000, x=None, allow_unconverged=False):
+    def solve(self, b, kappa, tol=1e-10, maxIter=1000, x=None, allow_unconverged=False, clover=None):
         """x_r = M^-1 b_r (wilsonSolve) with this loop's gauge field, comm and stream, started from the low-mode part of its
-        eigenvectors and sigmas, which must be eigenpairs of H = g5 M at this kappa.  Returns the list x; the iteration counts and true
+        eigenvectors and sigmas, which must be eigenpairs of H = g5 M at this kappa (M the Wilson-clover operator with clover=CloverField).  Returns the list x; the iteration counts and true
         residuals are kept in self.lastSolve.  Errors as Loop_Mugiq.deflate: status 1 (INVALID_ARGUMENT) for a loop object created
         without a gauge field, status 2 (UNSUPPORTED) for two-sided and coarse loop objects.  The recipe then reads
         x = low.solve(xi, kappa); low.deflate(x, xi); Loop_Mugiq(prm, eVecs=x, eVals_sigma=..., eVecsLeft=g5xi)."""
@@ -311,7 +311,7 @@ class Loop_Mugiq:
         if self._params.gauge is None:
             raise _lib.MugiqHipError("status 1: Loop_Mugiq.solve: the loop object was created without a gauge field")
         x, self.lastSolve = wilsonSolve(b, self._params.gauge, kappa, self.eVecs, self.eVals_sigma, tol, maxIter, self.comm, x,
-                                        allow_unconverged)
+                                        allow_unconverged, clover)
         return x
 
     def computeCoarseLoop(self):

@@ -111,6 +111,9 @@ def build_parser():
     ap.add_argument("--n-ev", type=int, default=4, help="number of (synthetic) eigenvectors")
     ap.add_argument("--seed", type=int, default=777)
     ap.add_argument("--kappa", type=float, default=0.12, help="hopping parameter of the Wilson operator (--check-evals)")
+    ap.add_argument("--dslash-type", choices=["wilson", "clover"], default="wilson",
+                    help="operator of --check-evals (QUDA --dslash-type): wilson, or clover = Wilson-clover with the term computed from the links")
+    ap.add_argument("--clover-coeff", type=float, default=0.1, help="kappa * c_sw of the clover term (QUDA --clover-coeff)")
     ap.add_argument("--check-evals", action="store_true",
                     help="print the printEvals lines (lambda = v^dag MdagM v / ||v||, residual, sigma) of the eigenvectors the loop runs on; "
                          "needs the gauge field of a displaced loop")
@@ -180,7 +183,11 @@ def main(argv=None):
         from .eigsolve import Eigsolve_Mugiq, MUGIQ_EIG_OPERATOR_MdagM
         if gauge is None:
             raise SystemExit("--check-evals needs a gauge field: set --loop-do-nonlocal yes and --displace-entry-string")
-        es = Eigsolve_Mugiq(fields, gauge, args.kappa, MUGIQ_EIG_OPERATOR_MdagM, comm)
+        clover = None
+        if args.dslash_type == "clover":
+            from . import CloverField
+            clover = CloverField(gauge.X, gauge.precision).compute(gauge, args.clover_coeff, comm)
+        es = Eigsolve_Mugiq(fields, gauge, args.kappa, MUGIQ_EIG_OPERATOR_MdagM, comm, clover=clover)
         es.computeEvals()
         es.printEvals(file=sys.stderr)
     loop = Loop_Mugiq(prm, fields, sigma, comm)

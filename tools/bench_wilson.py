@@ -2,7 +2,10 @@
 it: eight mugiq_hip_perform_covariant_displacement_vector calls per vector plus torch for the (1 -+ g_mu) sums, on the same buffers,
 the two alternated in one process.  Also the cost of the eigenpair check (mugiq_hip_compute_evals) per eigenvector.
 
-    python tools/bench_wilson.py [--lattice 32 32 32 32] [--nvec 8] [--reps 20] [--nev 200] [--no-composed] [--no-evals]
+    python tools/bench_wilson.py [--lattice 32 32 32 32] [--nvec 8] [--reps 20] [--nev 200] [--no-composed] [--no-evals] [--clover]
+
+--clover: also the Wilson-clover M (mugiq_hip_wilson_clover_apply), alternated with the unimproved M in the same loop, and one
+mugiq_hip_compute_clover; the packed term adds 576 B per site and launch (fp64), 2112 -> 2688 B at four vectors a launch: 1.27 x.
 
 Counted bytes of the fused kernel per site and vector (fp64): 192 (source, if the neighbours hit in cache) + 1152 / nVec-per-block
 (links) + 192 (result); one JSON line."""
@@ -29,6 +32,8 @@ def main():
     ap.add_argument("--kappa", type=float, default=0.12)
     ap.add_argument("--no-composed", action="store_true")
     ap.add_argument("--no-evals", action="store_true")
+    ap.add_argument("--clover", action="store_true", help="time the Wilson-clover M beside the unimproved one, and compute_clover")
+    ap.add_argument("--clover-coeff", type=float, default=0.15)
     a = ap.parse_args()
     X = tuple(a.lattice)
     V, vcb = int(np.prod(X)), int(np.prod(X)) // 2
@@ -55,6 +60,14 @@ def main():
     def fused():
         hip.wilsonApply(dst, src, gauge, a.kappa)
 
+    clover, t_setup = None, []
+    if a.clover:
+        clover = hip.CloverField(X, 8)
+        dstc = [hip.SpinorField(X, 8, 2) for _ in range(a.nvec)]
+
+    def fused_clover():
+        hip.wilsonApply(dstc, src, gauge, a.kappa, clover=clover)
+
     def composed():
         for s, o in zip(src, ref):
             acc = view(s).clone()
@@ -72,9 +85,15 @@ def main():
         torch.cuda.synchronize()
         return t0.elapsed_time(t1)
 
-    tf, tc = [], []
+    if a.clover:
+        t_setup = [timed(lambda: clover.compute(gauge, a.clover_coeff)) for _ in range(3)]
+    tf, tc, tcl = [], [], []
     for i in range(a.warmup + a.reps):
         f = timed(fused)
+        if a.clover:
+            cl = timed(fused_clover)
+            if i >= a.warmup:
+                tcl.append(cl)
         c = None if a.no_composed else timed(composed)
         if i >= a.warmup:
             tf.append(f)
@@ -87,6 +106,11 @@ def main():
            "fused_ms_max": round(max(tf), 4), "TBps_on_528B": round(bytes_model / med / 1e9, 3),
            "frac_of_8TBps_on_528B": round(bytes_model / med / 1e9 / 8.0, 3), "TBps_on_block_count": round(bytes_block / med / 1e9, 3),
            "GFLOPs_1320_per_site": round(1320.0 * V * a.nvec / med / 1e6, 1)}
+    if a.clover:
+        mcl = statistics.median(tcl)
+        res.update({"clover_ms_median": round(mcl, 4), "clover_ms_min": round(min(tcl), 4), "clover_ms_max": round(max(tcl), 4),
+                    "clover_over_wilson": round(mcl / med, 3), "clover_over_wilson_byte_model": round((2112 + 576) / 2112, 3),
+                    "compute_clover_ms_first": round(t_setup[0], 3), "compute_clover_ms": round(min(t_setup[1:]), 3)})
     if not a.no_composed:
         mc = statistics.median(tc)
         res.update({"composed_ms_median": round(mc, 3), "composed_ms_min": round(min(tc), 3), "composed_ms_max": round(max(tc), 3),
