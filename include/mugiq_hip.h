@@ -738,6 +738,42 @@ int mugiq_hip_loop_ultra_local_carrier(const MugiqHipLoop *loop);
  * through the eigenvectors, instead of by mugiq_hip_pack_face_layers beside it (fp64 FLOAT2, first entry along x on the row tile,
  * z / t partitioned; MUGIQ_HIP_PACK_IN_ENTRY=0 switches it off).  0: none; -1: bad handle / nothing computed yet. */
 int mugiq_hip_loop_halos_packed_in_entry(const MugiqHipLoop *loop);
+/* The plan of a compute (new; host only, no device work): what mugiq_hip_loop_compute does with every displacement entry, through
+ * the function the driver itself plans with (csrc/loop_plan.cpp), under the same environment switches.  param as for
+ * mugiq_hip_loop_create (param->gauge: precision and R only); eVec: the geometry of the eigenvectors; comm may be NULL, its
+ * callbacks are not called; axialOk[mu]: the outcome of the unitarity pre-pass along mu; deviceBytes: the device's total memory.
+ * No data pointer is read. */
+#define MUGIQ_HIP_LOOP_ROUTE_REFLECTED 0 /* derived from its opposite-sign partner */
+#define MUGIQ_HIP_LOOP_ROUTE_STEPWISE 1  /* one displacement + one contraction per step */
+#define MUGIQ_HIP_LOOP_ROUTE_FUSED 2     /* the fused displaced contraction */
+#define MUGIQ_HIP_LOOP_PLAN_MAX_ENTRIES 64
+#define MUGIQ_HIP_LOOP_PLAN_MAX_BUFFERS 512
+typedef struct MugiqHipLoopEntryPlan_s {
+  int derivedFrom;         /* the entry it is reflected from, or -1 */
+  int route;               /* MUGIQ_HIP_LOOP_ROUTE_* */
+  int part, high;          /* its direction is partitioned; the face it sends (0 low, 1 high) */
+  int kStart, nK;          /* its lengths kStart .. kStart + nK - 1 */
+  int tile;                /* the matrix-pipe tile may take it (the pre-pass along its direction passed) */
+  int gaugeFromField;      /* its axial gauge is built straight from the gauge field: no path-link fields */
+  int nLinkFields;         /* path-link fields W_0 .. W_stop it builds (0 | stop + 1) */
+  int buildGaugeFromLinks; /* the driver builds its axial gauge from those fields, once for all its launches */
+  int ahead, selfAlias;    /* its halo is posted at the start of the compute; the neighbour is the rank itself and nothing is sent */
+  int nBlocks, blockN;     /* the blocks of eigenvectors it is processed (ahead: its halo travels) in */
+  int needsMemset;         /* its slots are accumulated into */
+  int entryPacksFrom;      /* >= 0: the entry that runs first writes its face layers from this eigenvector on; -1: pack kernels */
+  long long faceBytes, haloBytes, perVecHaloBytes, gaugeBytes;
+} MugiqHipLoopEntryPlan;
+typedef struct MugiqHipLoopPlan_s {
+  int nEntries, nOrder, nPackTargets, nReserve;
+  int earlyEntry; /* the entry that runs before the halos are packed, or -2 */
+  int carryUltra, momReflect, grouped;
+  int order[MUGIQ_HIP_LOOP_PLAN_MAX_ENTRIES + 1];     /* -1: the ultra-local loop */
+  int packTargets[MUGIQ_HIP_LOOP_PLAN_MAX_ENTRIES];   /* the posted entries whose face layers earlyEntry writes */
+  long long reserve[MUGIQ_HIP_LOOP_PLAN_MAX_BUFFERS]; /* buffers reserved when the loop object is created, in order */
+  MugiqHipLoopEntryPlan entry[MUGIQ_HIP_LOOP_PLAN_MAX_ENTRIES];
+} MugiqHipLoopPlan;
+int mugiq_hip_loop_plan(const MugiqHipLoopParam *param, const MugiqHipSpinorField *eVec, int nEv, int twoSided, int coarseMode,
+                        const MugiqHipComm *comm, const int axialOk[4], size_t deviceBytes, MugiqHipLoopPlan *out);
 /* Phase timing of a compute (measurement aid; off by default).  When switched on, mugiq_hip_loop_compute brackets each
  * phase with a pair of HIP events on the stream the phase runs on and, after its final synchronisation, reports the
  * device time between them.  Phases of different streams overlap in time (that is the point of the halo stream). */

@@ -66,6 +66,23 @@ class ProjectPlan(ctypes.Structure):
                [("ldsBytes", ctypes.c_longlong)]
 
 
+LOOP_PLAN_MAX_ENTRIES, LOOP_PLAN_MAX_BUFFERS = 64, 512
+
+
+class LoopEntryPlan(ctypes.Structure):
+    """MugiqHipLoopEntryPlan (include/mugiq_hip.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("derivedFrom", "route", "part", "high", "kStart", "nK", "tile", "gaugeFromField", "nLinkFields",
+                                            "buildGaugeFromLinks", "ahead", "selfAlias", "nBlocks", "blockN", "needsMemset", "entryPacksFrom")] + \
+               [(n, ctypes.c_longlong) for n in ("faceBytes", "haloBytes", "perVecHaloBytes", "gaugeBytes")]
+
+
+class LoopPlan(ctypes.Structure):
+    """MugiqHipLoopPlan (include/mugiq_hip.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("nEntries", "nOrder", "nPackTargets", "nReserve", "earlyEntry", "carryUltra", "momReflect", "grouped")] + \
+               [("order", ctypes.c_int * (LOOP_PLAN_MAX_ENTRIES + 1)), ("packTargets", ctypes.c_int * LOOP_PLAN_MAX_ENTRIES),
+                ("reserve", ctypes.c_longlong * LOOP_PLAN_MAX_BUFFERS), ("entry", LoopEntryPlan * LOOP_PLAN_MAX_ENTRIES)]
+
+
 _I4 = ctypes.POINTER(ctypes.c_int)
 _VP = ctypes.c_void_p
 _SP = ctypes.POINTER(SpinorDesc)
@@ -181,6 +198,7 @@ SIGNATURES = {
     "mugiq_hip_loop_create_two_sided": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _VP, _SP, _SP, ctypes.POINTER(ctypes.c_double),
                                                        ctypes.c_int, _VP, _VP]),
     "mugiq_hip_loop_compute": (ctypes.c_int, [_VP]),
+    "mugiq_hip_loop_plan": (ctypes.c_int, [_VP, _SP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _I4, ctypes.c_size_t, ctypes.POINTER(LoopPlan)]),
     "mugiq_hip_loop_deflate": (ctypes.c_int, [_VP, _SP, _SP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "mugiq_hip_loop_get_info": (ctypes.c_int, [_VP, _VP]),
     "mugiq_hip_loop_set_profiling": (ctypes.c_int, [_VP, ctypes.c_int]),

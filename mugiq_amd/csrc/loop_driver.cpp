@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "loop_plan.h"
 
 namespace mugiq {
 
@@ -50,7 +51,6 @@ struct MugiqHipLoop_s {
   long long locV4 = 1, locV3 = 1, totV3 = 1;
   std::vector<std::string> dispEntry, dispString;
   std::vector<int> dispStart, dispStop, nLoopPerEntry, nLoopOffset, dispDir, dispSign;
-  std::vector<int> derivedFrom;  // per entry: the entry it was reflected from in the last compute, or -1
   std::vector<int> entryKernel;  // per entry: MUGIQ_HIP_ENTRY_KERNEL_* of the last compute, or -1
   int nDispEntries = 0, nLoop = 0, nData = 0;
   std::string fnameMom, fnamePos;
@@ -65,7 +65,6 @@ struct MugiqHipLoop_s {
   int nEv = 0, precision = 8, order = 2;
   int loopPrecision = 8;  // precision of the loop buffers / FT (= precision, or 8 over fp32 fields: mixed mode)
   MugiqHipGaugeField gauge;
-  bool haveGauge = false;
   // the axial-gauge tile along mu only where the gauge of the lines of mu is unitary (check_axial_gauge, once per compute; the same on
   // every rank).  axialDev: this rank's D_mu of the last check
   bool axialOk[4] = {true, true, true, true};
@@ -84,13 +83,14 @@ struct MugiqHipLoop_s {
   void *dataPos_d = nullptr, *dataPosMP_d = nullptr, *dataMom_d = nullptr, *phaseMatrix_d = nullptr;
   void *dataPos = nullptr, *dataMom_h = nullptr, *dataMom = nullptr, *dataMom_bcast = nullptr;
   bool dataPosCopied = false, dataPosPinned = false, momProjDone = false, computed = false;
-  // OPT plan: the ultra-local loop rides along with one displaced entry when the tiled kernel has room for it (see
+  LoopPlan plan;  // csrc/loop_plan.cpp: made at create for the pool reservation, and again at the start of every compute
+  // plan.carryUltra: the ultra-local loop rides along with one displaced entry when the tiled kernel has room for it (see
   // mugiq_hip_displaced_loop_contraction_fused_carry); ultraCarried says whether an entry of this compute has produced it
-  bool carryUltra = false, ultraCarried = false;
+  bool ultraCarried = false;
   int ultraCarrier = -1;  // the entry that took it along in the last compute, or -1
-  // OPT plan, momentum-space output: reflected entries are derived on the gathered momentum-space array (csrc/reflect_mom.cpp)
-  // and exist in position space only once somebody asks for dataPos (posReflectPending: not materialised yet)
-  bool momReflect = false, posReflectPending = false;
+  // plan.momReflect: reflected entries are derived on the gathered momentum-space array (csrc/reflect_mom.cpp) and exist in
+  // position space only once somebody asks for dataPos (posReflectPending: not materialised yet)
+  bool posReflectPending = false;
   // ---- MG coarse path (eigsolve->computeCoarse): coarse eigenvectors + one Transfer level (lib/loop_mugiq.cpp:277-319,482)
   bool coarseMode = false;
   std::vector<MugiqHipCoarseField> coarseVecs;
@@ -111,21 +111,14 @@ struct MugiqHipLoop_s {
     bool inUse;
   };
   std::vector<PoolBuf> pool;
-  std::vector<void *> scratch;  // pool buffers handed out for the current entry (returned by free_scratch)
-  // halos posted ahead of their entry (OPT plan): the eigenvector layers of every partitioned entry are packed and sent
+  std::vector<void *> scratch;  // pool buffers handed out for the current entry (release_buffers / hold_scratch)
+  // halos posted ahead of their entry (plan.entry[id].ahead): the eigenvector layers of every partitioned entry are packed and sent
   // at the start of the compute, the entries of unpartitioned directions run while they travel
   struct HaloPost {
-    void *gsend = nullptr, *grecv = nullptr;
-    hipEvent_t evPacked = nullptr, evHalo = nullptr;
+    void *gsend = nullptr, *grecv = nullptr;  // (the same buffer where the plan says selfAlias)
     // the halo travels in blocks of eigenvectors: evPackedBlk[b] (pack stream) / evBlock[b] (halo stream: block b has landed)
     std::vector<hipEvent_t> evPackedBlk, evBlock;
-    int nBlocks = 0, blockN = 0;
-    bool posted = false;
-    int entryPacksFrom = -1;     // >= 0: the face layers of eigenvectors entryPacksFrom .. are written by the entry that runs first, on its
-                                 // way through the eigenvectors (csrc/fused_mfma.hip, row tile); -1: by mugiq_hip_pack_face_layers
-    void *axialGauge = nullptr;  // the axial gauge of the entry, built once for all its launches (csrc/fused_mfma.hip), or NULL
-    bool selfAlias = false;  // the neighbour is this rank itself (an axis of extent 1 under forced partitioning): the face layers are
-                             // packed straight into the ghost buffer, no send buffer and no message (MUGIQ_HIP_SELF_HALO_COPY=1: keep them)
+    void *axialGauge = nullptr;          // the axial gauge of the entry, built once for all its launches (csrc/fused_mfma.hip), or NULL
     std::vector<MugiqHipSpinorField> E;  // path-link fields built ahead (their small face exchanges go first)
   };
   std::vector<HaloPost> halo;   // per displacement entry
@@ -192,7 +185,7 @@ static void phases_resolve(MugiqHipLoop *lp) {
     }
 }
 
-// scratch from the loop's pool (best fit among the free buffers, else a new allocation); returned by free_scratch
+// scratch from the loop's pool (best fit among the free buffers, else a new allocation); returned by release_buffers
 static int scratch_alloc(MugiqHipLoop *lp, void **p, size_t bytes, bool zero) {
   int best = -1;
   for (size_t i = 0; i < lp->pool.size(); i++)
@@ -232,33 +225,59 @@ static int make_scratch_field(MugiqHipLoop *lp, MugiqHipSpinorField *f, int orde
   return MUGIQ_HIP_SUCCESS;
 }
 
-// exchangeGhostVec for ONE face: the face the displacement (dir, sign) reads (lib/contract_wrappers.cu:166-169
-// exchanges all partitioned dims in both directions).
-static int exchange_face(MugiqHipLoop *lp, MugiqHipSpinorField *src, int dir, int sign, void *send_d, void *recv_d) {
-  const int high = (sign == MUGIQ_HIP_DISP_SIGN_PLUS) ? 0 : 1;  // sign +: my LOW face feeds the backward neighbour
-  int st = mugiq_hip_pack_face(send_d, src, dir, high, lp->stream);
-  if (st) return st;
-  const size_t bytes = (size_t)24 * (lp->volumeCB / lp->localL[dir]) * lp->cplxBytes();
-  st = lp->comm.sendrecv(lp->comm.ctx, send_d, recv_d, bytes, dir, high ? +1 : -1, lp->stream);
-  if (st) return set_error(MUGIQ_HIP_ERROR_HIP, "halo sendrecv callback failed with status %d", st);
-  src->ghost[dir][sign == MUGIQ_HIP_DISP_SIGN_PLUS ? 1 : 0] = recv_d;
+// buffers back into the pool (the streams that used them have been synchronised, or order the next user behind them)
+static void release_buffers(MugiqHipLoop *lp, std::vector<void *> &bufs) {
+  for (void *p : bufs)
+    for (auto &b : lp->pool)
+      if (b.ptr == p) b.inUse = false;
+  bufs.clear();
+}
+// ... or kept until the compute ends: what outlives the entries processed in between
+static void hold_scratch(MugiqHipLoop *lp) {
+  lp->held.insert(lp->held.end(), lp->scratch.begin(), lp->scratch.end());
+  lp->scratch.clear();
+}
+
+// the position-space slots of entry `id` (-1: the ultra-local loop)
+static void *entry_slot(const MugiqHipLoop *lp, int id) {
+  return static_cast<char *>(lp->dataPos_d) + (size_t)lp->nElemPosLocPerLoop * (id < 0 ? 0 : lp->nLoopOffset[id]) * lp->loopBytes();
+}
+
+// one message along `dir`: the face `high` (0: my LOW face, which feeds the backward neighbour) out, the opposite ghost zone in
+static int halo_sendrecv(MugiqHipLoop *lp, const void *send_d, void *recv_d, size_t bytes, int dir, int high, hipStream_t stream) {
+  const int st = lp->comm.sendrecv(lp->comm.ctx, send_d, recv_d, bytes, dir, high ? +1 : -1, stream);
+  return st ? set_error(MUGIQ_HIP_ERROR_HIP, "halo sendrecv callback failed with status %d", st) : MUGIQ_HIP_SUCCESS;
+}
+
+// the send and receive buffers of the single faces of a partitioned entry (NULL along an unpartitioned direction)
+static int face_buffers(MugiqHipLoop *lp, const EntryPlan &e, size_t nFaces, void **send_d, void **recv_d) {
+  *send_d = *recv_d = nullptr;
+  if (!e.part) return MUGIQ_HIP_SUCCESS;
+  int st = scratch_alloc(lp, send_d, (size_t)e.faceBytes * nFaces, false);
+  return st ? st : scratch_alloc(lp, recv_d, (size_t)e.faceBytes * nFaces, false);
+}
+
+// exchangeGhostVec for ONE face: the face entry `id` reads (lib/contract_wrappers.cu:166-169 exchanges all partitioned dims in both
+// directions).
+static int exchange_face(MugiqHipLoop *lp, int id, MugiqHipSpinorField *src, void *send_d, void *recv_d) {
+  const EntryPlan &e = lp->plan.entry[id];
+  const int dir = lp->dispDir[id];
+  int st = mugiq_hip_pack_face(send_d, src, dir, e.high, lp->stream);
+  if (st || (st = halo_sendrecv(lp, send_d, recv_d, (size_t)e.faceBytes, dir, e.high, lp->stream))) return st;
+  src->ghost[dir][1 - e.high] = recv_d;
   return MUGIQ_HIP_SUCCESS;
 }
 
 // ---- the reference's own plan: one displacement + one contraction launch per eigenvector and step -----------
 static int entry_basic(MugiqHipLoop *lp, int id, void *slot0) {
+  const EntryPlan &e = lp->plan.entry[id];
   const int dir = lp->dispDir[id], sign = lp->dispSign[id];
-  const bool part = lp->commDim[dir] != 0;
   MugiqHipSpinorField aux[2];
   int st;
   for (int i = 0; i < 2; i++)
     if ((st = make_scratch_field(lp, &aux[i], lp->order, false, true))) return st;  // fully written by every displacement
-  void *send_d = nullptr, *recv_d = nullptr;
-  if (part) {
-    const size_t fb = (size_t)24 * (lp->volumeCB / lp->localL[dir]) * lp->cplxBytes();
-    if ((st = scratch_alloc(lp, &send_d, fb, false))) return st;
-    if ((st = scratch_alloc(lp, &recv_d, fb, false))) return st;
-  }
+  void *send_d, *recv_d;
+  if ((st = face_buffers(lp, e, 1, &send_d, &recv_d))) return st;
   const size_t slotBytes = (size_t)lp->nElemPosLocPerLoop * lp->loopBytes();
   lp->entryKernel[id] = MUGIQ_HIP_ENTRY_KERNEL_STEPWISE;
   for (int n = 0; n < lp->nEv; n++) {  // lib/loop_mugiq.cpp:478
@@ -266,7 +285,7 @@ static int entry_basic(MugiqHipLoop *lp, int id, void *slot0) {
     int dispCount = 0;
     for (int idisp = 1; idisp <= lp->dispStop[id]; idisp++) {  // :489
       MugiqHipSpinorField *dst = &aux[idisp & 1];
-      if (part && (st = exchange_face(lp, &cur, dir, sign, send_d, recv_d))) return st;
+      if (e.part && (st = exchange_face(lp, id, &cur, send_d, recv_d))) return st;
       if ((st = mugiq_hip_perform_covariant_displacement_vector(dst, &cur, &lp->gauge, dir, sign, lp->commDim, lp->stream)))
         return st;  // Displace::doVectorDisplacement, lib/displace.cpp:55-67
       cur = *dst;
@@ -282,17 +301,15 @@ static int entry_basic(MugiqHipLoop *lp, int id, void *slot0) {
   return MUGIQ_HIP_SUCCESS;
 }
 
-// The same sequence for a block of eigenvectors at a time (OPT plan, displacement longer than the local extent of a
-// partitioned dimension: the multi-layer halo cannot reach past the nearest neighbour, single steps can): per step ONE
-// message carries the faces of all eigenvectors of the block and ONE contraction launch takes the whole block, instead of
-// one exchange and one launch per eigenvector and step (thousands of small messages at configs[2] sizes).
+// The same sequence for a block of eigenvectors at a time (OPT plan, route "step by step": the multi-layer halo cannot reach past the
+// nearest neighbour, single steps can): per step ONE message carries the faces of all eigenvectors of the block and ONE contraction
+// launch takes the whole block, instead of one exchange and one launch per eigenvector and step (thousands of small messages at
+// configs[2] sizes).
 static int entry_stepwise_blocked(MugiqHipLoop *lp, int id, void *slot0) {
+  const EntryPlan &e = lp->plan.entry[id];
   const int dir = lp->dispDir[id], sign = lp->dispSign[id], start = lp->dispStart[id], stop = lp->dispStop[id];
-  const bool part = lp->commDim[dir] != 0;
-  const size_t fieldB = (size_t)2 * lp->eVecs[0].parity_offset * lp->cplxBytes();
-  const size_t faceB = (size_t)24 * (lp->volumeCB / lp->localL[dir]) * lp->cplxBytes();
-  const size_t budget = (size_t)8 << 30;  // two auxiliary fields per eigenvector of the block
-  const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)lp->nEv, budget / (2 * fieldB)));
+  const size_t faceB = (size_t)e.faceBytes;
+  const int nb = e.blockN;
   int st;
   std::vector<MugiqHipSpinorField> aux[2];
   for (int h = 0; h < 2; h++) {
@@ -300,26 +317,21 @@ static int entry_stepwise_blocked(MugiqHipLoop *lp, int id, void *slot0) {
     for (int i = 0; i < nb; i++)
       if ((st = make_scratch_field(lp, &aux[h][i], lp->order, false, true))) return st;  // fully written by every displacement
   }
-  void *gsend = nullptr, *grecv = nullptr;
-  if (part) {
-    if ((st = scratch_alloc(lp, &gsend, faceB * nb, false))) return st;
-    if ((st = scratch_alloc(lp, &grecv, faceB * nb, false))) return st;
-  }
+  void *gsend, *grecv;
+  if ((st = face_buffers(lp, e, nb, &gsend, &grecv))) return st;
   const size_t slotBytes = (size_t)lp->nElemPosLocPerLoop * lp->loopBytes();
-  const int high = (sign == MUGIQ_HIP_DISP_SIGN_PLUS) ? 0 : 1;  // sign +: my LOW face feeds the backward neighbour
   std::vector<MugiqHipSpinorField> cur(nb);
   lp->entryKernel[id] = MUGIQ_HIP_ENTRY_KERNEL_STEPWISE;
   for (int n0 = 0; n0 < lp->nEv; n0 += nb) {
     const int nv = std::min(nb, lp->nEv - n0);
     for (int i = 0; i < nv; i++) cur[i] = lp->eVecs[n0 + i];
     for (int idisp = 1; idisp <= stop; idisp++) {
-      if (part) {
-        if ((st = mugiq_hip_pack_face_layers(gsend, cur.data(), nv, dir, high, 1, lp->stream))) return st;
-        st = lp->comm.sendrecv(lp->comm.ctx, gsend, grecv, faceB * nv, dir, high ? +1 : -1, lp->stream);
-        if (st) return set_error(MUGIQ_HIP_ERROR_HIP, "halo sendrecv callback failed with status %d", st);
+      if (e.part) {
+        if ((st = mugiq_hip_pack_face_layers(gsend, cur.data(), nv, dir, e.high, 1, lp->stream))) return st;
+        if ((st = halo_sendrecv(lp, gsend, grecv, faceB * nv, dir, e.high, lp->stream))) return st;
       }
       for (int i = 0; i < nv; i++) {
-        if (part) cur[i].ghost[dir][sign == MUGIQ_HIP_DISP_SIGN_PLUS ? 1 : 0] = static_cast<char *>(grecv) + faceB * i;
+        if (e.part) cur[i].ghost[dir][1 - e.high] = static_cast<char *>(grecv) + faceB * i;
         MugiqHipSpinorField *dst = &aux[idisp & 1][i];
         if ((st = mugiq_hip_perform_covariant_displacement_vector(dst, &cur[i], &lp->gauge, dir, sign, lp->commDim, lp->stream))) return st;
         cur[i] = *dst;
@@ -334,36 +346,6 @@ static int entry_stepwise_blocked(MugiqHipLoop *lp, int id, void *slot0) {
   }
   return MUGIQ_HIP_SUCCESS;
 }
-
-// path-ordered link products W_k as E_k = D^k E_0, E_0(x)(s,c) = delta_sc, s < 3 (scratch fields; k = 0 .. stop)
-static int build_path_links(MugiqHipLoop *lp, int id, std::vector<MugiqHipSpinorField> &E) {
-  const int dir = lp->dispDir[id], sign = lp->dispSign[id], stop = lp->dispStop[id];
-  const bool part = lp->commDim[dir] != 0;
-  int st;
-  E.assign(stop + 1, MugiqHipSpinorField());
-  for (int k = 0; k <= stop; k++)
-    if ((st = make_scratch_field(lp, &E[k], 2, false))) return st;  // every site of E_k is written below
-  if ((st = fill_identity_links(&E[0], lp->stream))) return st;
-  void *send_d = nullptr, *recv_d = nullptr;
-  if (part) {
-    const size_t fb = (size_t)24 * (lp->volumeCB / lp->localL[dir]) * lp->cplxBytes();
-    if ((st = scratch_alloc(lp, &send_d, fb, false))) return st;
-    if ((st = scratch_alloc(lp, &recv_d, fb, false))) return st;
-  }
-  for (int k = 1; k <= stop; k++) {
-    if (part && (st = exchange_face(lp, &E[k - 1], dir, sign, send_d, recv_d))) return st;
-    if ((st = mugiq_hip_perform_covariant_displacement_vector(&E[k], &E[k - 1], &lp->gauge, dir, sign, lp->commDim, lp->stream)))
-      return st;
-  }
-  return MUGIQ_HIP_SUCCESS;
-}
-
-// bytes of the multi-layer eigenvector halo of entry `id` (one direction): `stop` face layers of all eigenvectors
-static size_t halo_bytes(const MugiqHipLoop *lp, int id) {
-  return (size_t)lp->dispStop[id] * 24 * (size_t)(lp->volumeCB / lp->localL[lp->dispDir[id]]) * lp->cplxBytes() * (size_t)lp->nEv;
-}
-
-static int reflection_source(const MugiqHipLoop *lp, int id);
 
 // The tile decision per direction: the pre-pass D_mu of csrc/fused_mfma.hip against axial_gauge_tolerance.  The gauge field belongs
 // to the caller and may change between computes, so it runs at the start of every OPT compute (and at create, for the pool
@@ -394,147 +376,36 @@ static int check_axial_gauge(MugiqHipLoop *lp) {
   return MUGIQ_HIP_SUCCESS;
 }
 
-// The one place the driver asks whether the axial-gauge tile may take entry `id`; where it may not, no axial gauge is built or
-// reserved, and the fused calls take the vector tiles (one-sided) or the entry goes step by step (two-sided)
-static bool entry_tile_allowed(const MugiqHipLoop *lp, int id) { return lp->axialOk[lp->dispDir[id]]; }
-static size_t entry_gauge_bytes(const MugiqHipLoop *lp, int id, const std::vector<int> &kv, int partitioned) {
-  return entry_tile_allowed(lp, id) ? axial_gauge_bytes(lp->eVecs[0], lp->dispDir[id], kv.data(), (int)kv.size(), partitioned) : 0;
-}
-
-// The links of entry `id` for its fused calls: its axial gauge *G (csrc/fused_mfma.hip; NULL: none built here) and the path-link fields
-// W_0 .. W_stop in E (empty: not needed).  ahead: the entry's halo is posted (prepare_halo); the pool reservation of
-// reserve_plan_buffers follows these conditions.
-static int build_entry_links(MugiqHipLoop *lp, int id, bool ahead, void **G, std::vector<MugiqHipSpinorField> &E) {
-  const int dir = lp->dispDir[id], sign = lp->dispSign[id], stop = lp->dispStop[id];
-  const bool part = lp->commDim[dir] != 0;
-  std::vector<int> kv;
-  for (int k = lp->dispStart[id]; k <= stop; k++) kv.push_back(k);
-  const size_t gb = entry_gauge_bytes(lp, id, kv, part ? 1 : 0);
-  *G = nullptr;
-  E.clear();
-  int st;
-  // Straight from the gauge field (W_1 = U_mu, the continued positions are the wrapped sites -- or, along a partitioned direction, the
-  // neighbour's links in the border of the extended field): no path-link fields, and none of their face exchanges.  (A partitioned
-  // entry whose halo is not posted ahead builds them all the same; MUGIQ_HIP_GAUGE_FROM_LINKS = 0: every entry does.)
-  if (gb && (ahead || !part) && axial_gauge_from_links_possible(lp->eVecs[0], lp->gauge, stop, dir, sign)) {
-    if ((st = scratch_alloc(lp, G, gb, false))) return st;
-    return build_axial_gauge_from_links(*G, lp->eVecs[0], lp->gauge, stop, dir, sign, lp->stream);
+// The plan of the next compute (csrc/loop_plan.cpp) from the loop object as it stands: after check_axial_gauge where there are entries
+// to displace.  The ghost-layer buffers posted ahead may take a quarter of the device's TOTAL memory, the same on every rank.
+static int make_plan(MugiqHipLoop *lp) {
+  LoopPlanInput in;
+  in.nEntries = lp->nDispEntries, in.nLoop = lp->nLoop;
+  in.dir = lp->dispDir.data(), in.sign = lp->dispSign.data(), in.start = lp->dispStart.data(), in.stop = lp->dispStop.data();
+  in.ev = &lp->eVecs[0], in.nEv = lp->nEv, in.precision = lp->precision, in.loopPrecision = lp->loopPrecision;
+  in.twoSided = lp->twoSided, in.coarseMode = lp->coarseMode;
+  in.gauge = &lp->gauge;
+  in.haveComm = lp->haveComm, in.groupCallbacks = lp->haveComm && lp->comm.group_begin && lp->comm.group_end;
+  for (int d = 0; d < 4; d++) in.commDim[d] = lp->commDim[d], in.grid[d] = lp->haveComm ? lp->comm.grid[d] : 1, in.axialOk[d] = lp->axialOk[d];
+  in.momMatrix = lp->momMatrix.data(), in.Nmom = lp->Nmom, in.doMomProj = lp->doMomProj, in.momProjDone = lp->momProjDone;
+  in.calcType = lp->calcType;
+  if (lp->calcType != MUGIQ_HIP_LOOP_CALC_TYPE_BASIC_KERNEL && lp->nDispEntries > 0) {
+    size_t freeB = 0;
+    MUGIQ_CHECK_HIP(hipMemGetInfo(&freeB, &in.deviceBytes));
   }
-  if ((st = build_path_links(lp, id, E))) return st;  // compute stream: the entry's kernels read them there
-  // ... else from W_1 .. W_stop: once for all launches of a posted entry (interior tiles, then the boundary tiles block by block), and
-  // where the lengths do not start at 1 ("-x:3": the links of the call, W_start .. W_stop, do not hold W_1).  Otherwise every fused
-  // call builds its own from its links.
-  if (!gb || !(ahead || lp->dispStart[id] > 1)) return MUGIQ_HIP_SUCCESS;
-  std::vector<const void *> lk;
-  for (int k = 1; k <= stop; k++) lk.push_back(E[k].data);
-  if ((st = scratch_alloc(lp, G, gb, false))) return st;
-  return build_axial_gauge(*G, lp->eVecs[0], lk.data(), stop, dir, sign, lp->stream);
-}
-
-// Does the OPT plan take entry `id` step by step (entry_stepwise_blocked)?  A length past the nearest neighbour of a partitioned
-// direction; for two-sided loops also every entry the two-sided matrix-pipe tile does not take (lengths > 8, a partitioned x axis, no
-// tile geometry).  (The driver builds the axial gauge itself where the lengths do not start at 1: gaugeGiven.)
-static bool entry_stepwise(const MugiqHipLoop *lp, int id) {
-  const int dir = lp->dispDir[id];
-  const bool part = lp->commDim[dir] != 0;
-  if (part && lp->dispStop[id] > lp->localL[dir]) return true;
-  if (!lp->twoSided) return false;
-  std::vector<int> kv;
-  for (int k = lp->dispStart[id]; k <= lp->dispStop[id]; k++) kv.push_back(k);
-  return !entry_tile_allowed(lp, id) || !mfma_tile_applicable(lp->eVecs[0], dir, kv.data(), (int)kv.size(), part ? 1 : 0, true, true);
-}
-
-// The OPT plan: which entries are reflected from which (derivedFrom), and which of the computed entries along partitioned axes
-// get their eigenvector halo posted AHEAD, at the start of the compute (ahead[id] = 1).  The ghost-layer buffers posted ahead
-// may take a quarter of the device memory.  The rule must not depend on anything that can differ between ranks (such as the
-// memory free right now): every rank has to take the same decision, or the transfers would not pair up.
-static int plan_opt(MugiqHipLoop *lp, std::vector<char> &ahead) {
-  ahead.assign(lp->nDispEntries, 0);
-  for (int id = 0; id < lp->nDispEntries; id++) {
-    lp->derivedFrom[id] = -1;  // entries after `id` are still -1 here: reflection_source only looks at jd < id
-    lp->derivedFrom[id] = reflection_source(lp, id);
-  }
-  size_t freeB = 0, totalB = 0;
-  MUGIQ_CHECK_HIP(hipMemGetInfo(&freeB, &totalB));
-  size_t budget = totalB / 4;
-  if (const char *e = getenv("MUGIQ_HIP_HALO_AHEAD"))
-    if (atoi(e) == 0) budget = 0;
-  for (int id = 0; id < lp->nDispEntries; id++) {
-    const int dir = lp->dispDir[id];
-    if (lp->derivedFrom[id] >= 0 || !lp->commDim[dir] || entry_stepwise(lp, id)) continue;
-    const size_t bytes = halo_bytes(lp, id);
-    if (2 * bytes > budget) continue;  // this entry exchanges eigenvector blocks of <= 4 GiB inside its own turn instead
-    budget -= 2 * bytes;
-    ahead[id] = 1;
-  }
+  lp->plan = make_loop_plan(in);
   return MUGIQ_HIP_SUCCESS;
 }
 
-// a buffer of `bytes` into the pool, free for scratch_alloc to hand out (hipMalloc of multi-GB buffers costs ~40 ms per GB: the
-// driver maps and clears the pages -- so what the plan is known to need is allocated when the loop object is built, like the
-// reference's allocateDataMemory, lib/loop_mugiq.cpp:101-158, not inside the first compute)
-static int pool_reserve(MugiqHipLoop *lp, size_t bytes) {
-  void *q = nullptr;
-  MUGIQ_CHECK_HIP(hipMalloc(&q, bytes ? bytes : 16));
-  lp->pool.push_back({q, bytes, false});
-  return MUGIQ_HIP_SUCCESS;
-}
-
-// An axis of extent 1 that is partitioned all the same (MugiqHipComm.partitioned): this rank is its own forward and backward
-// neighbour, the "message" would be a device copy of what the pack kernel has just written.  Pack into the ghost buffer instead.
-static bool self_neighbour_alias(const MugiqHipLoop *lp, int dir) {
-  if (!lp->haveComm || lp->comm.grid[dir] != 1) return false;
-  if (const char *e = getenv("MUGIQ_HIP_SELF_HALO_COPY"))
-    if (atoi(e) != 0) return false;
-  return true;
-}
-
+// The buffers the plan will hold for the halos it posts ahead (the large allocations of a partitioned run), into the pool, free for
+// scratch_alloc to hand out: allocated when the loop object is built, like the reference's allocateDataMemory
+// (lib/loop_mugiq.cpp:101-158), not inside the first compute
 static int reserve_plan_buffers(MugiqHipLoop *lp) {
-  if (lp->calcType == MUGIQ_HIP_LOOP_CALC_TYPE_BASIC_KERNEL || lp->nDispEntries == 0) return MUGIQ_HIP_SUCCESS;
-  int st = check_axial_gauge(lp);
-  if (st) return st;
-  std::vector<char> ahead;
-  st = plan_opt(lp, ahead);
-  if (st) return st;
-  const size_t fieldB = (size_t)24 * lp->volumeCB * lp->cplxBytes();  // a FLOAT2 pad-0 path-link field
-  bool anyAhead = false;
-  for (int id = 0; id < lp->nDispEntries; id++) {
-    if (!ahead[id]) continue;
-    const size_t faceB = (size_t)24 * (lp->volumeCB / lp->localL[lp->dispDir[id]]) * lp->cplxBytes();
-    size_t gb = 0;
-    {  // the entry's axial gauge (csrc/fused_mfma.hip), where that tile takes the entry
-      std::vector<int> kv;
-      for (int k = lp->dispStart[id]; k <= lp->dispStop[id]; k++) kv.push_back(k);
-      gb = entry_gauge_bytes(lp, id, kv, 1);
-    }
-    if (!(gb && axial_gauge_from_links_possible(lp->eVecs[0], lp->gauge, lp->dispStop[id], lp->dispDir[id], lp->dispSign[id]))) {
-      // (build_entry_links: the gauge from the extended gauge field where its border reaches far enough -- then no link fields)
-      for (int k = 0; k <= lp->dispStop[id]; k++)
-        if ((st = pool_reserve(lp, fieldB))) return st;  // E_0 .. E_stop, held until the entry has run
-      if ((st = pool_reserve(lp, faceB)) || (st = pool_reserve(lp, faceB))) return st;
-    }
-    if ((st = pool_reserve(lp, halo_bytes(lp, id)))) return st;
-    if (!self_neighbour_alias(lp, lp->dispDir[id]) && (st = pool_reserve(lp, halo_bytes(lp, id)))) return st;
-    if (gb && (st = pool_reserve(lp, gb))) return st;
-    anyAhead = true;
+  for (size_t bytes : lp->plan.reserve) {
+    void *q = nullptr;
+    MUGIQ_CHECK_HIP(hipMalloc(&q, bytes ? bytes : 16));
+    lp->pool.push_back({q, bytes, false});
   }
-  // the entry that runs before the halos are posted keeps its link fields out of the pool until the compute ends (see
-  // mugiq_hip_loop_compute): they come on top of what the posted entries hold
-  if (anyAhead)
-    for (int id = 0; id < lp->nDispEntries; id++)
-      if (lp->derivedFrom[id] < 0 && !lp->commDim[lp->dispDir[id]]) {
-        std::vector<int> kv;
-        for (int k = lp->dispStart[id]; k <= lp->dispStop[id]; k++) kv.push_back(k);
-        const bool direct = axial_gauge_from_links_possible(lp->eVecs[0], lp->gauge, lp->dispStop[id], lp->dispDir[id], lp->dispSign[id]);
-        const size_t gb = direct ? entry_gauge_bytes(lp, id, kv, 0) : 0;
-        if (gb) {  // (build_entry_links: the gauge straight from the gauge field, no link fields)
-          if ((st = pool_reserve(lp, gb))) return st;
-        } else {
-          for (int k = 0; k <= lp->dispStop[id]; k++)
-            if ((st = pool_reserve(lp, fieldB))) return st;
-        }
-        break;
-      }
   return MUGIQ_HIP_SUCCESS;
 }
 
@@ -549,93 +420,75 @@ static int ensure_comm_stream(MugiqHipLoop *lp) {
   return MUGIQ_HIP_SUCCESS;
 }
 
-// Halo of entry `id` posted ahead, step 1: link fields (their small face exchanges happen here, at once), ghost buffers for
-// ALL eigenvectors, and the cut into blocks of eigenvectors the halo travels in.  (Whether an entry is posted ahead is
-// plan_opt's decision.)
-static int prepare_halo(MugiqHipLoop *lp, int id) {
-  const size_t bytes = halo_bytes(lp, id);
+// The links of a fused entry `id`, as its plan says: its axial gauge *G (csrc/fused_mfma.hip; NULL: none built here) straight from
+// the gauge field (W_1 = U_mu, the continued positions are the wrapped sites -- or, along a partitioned direction, the neighbour's
+// links in the border of the extended field), or the path-link fields E_k = D^k E_0, E_0(x)(s,c) = delta_sc, s < 3, k = 0 .. stop
+// (with their face exchanges), and where the plan asks for it the gauge from them.
+static int build_entry_links(MugiqHipLoop *lp, int id, void **G, std::vector<MugiqHipSpinorField> &E) {
+  const EntryPlan &e = lp->plan.entry[id];
+  const int dir = lp->dispDir[id], sign = lp->dispSign[id], stop = lp->dispStop[id];
+  *G = nullptr;
+  E.assign(e.nLinkFields, MugiqHipSpinorField());
   int st;
-  MugiqHipLoop::HaloPost &h = lp->halo[id];
-  if (!h.evPacked) {
-    MUGIQ_CHECK_HIP(hipEventCreateWithFlags(&h.evPacked, hipEventDisableTiming));
-    MUGIQ_CHECK_HIP(hipEventCreateWithFlags(&h.evHalo, hipEventDisableTiming));
+  if (e.gaugeFromField) {
+    if ((st = scratch_alloc(lp, G, (size_t)e.gaugeBytes, false))) return st;
+    return build_axial_gauge_from_links(*G, lp->eVecs[0], lp->gauge, stop, dir, sign, lp->stream);
   }
-  if ((st = build_entry_links(lp, id, true, &h.axialGauge, h.E))) return st;
-  h.selfAlias = self_neighbour_alias(lp, lp->dispDir[id]);
-  if ((st = scratch_alloc(lp, &h.grecv, bytes, false))) return st;
-  if (h.selfAlias) h.gsend = h.grecv;
-  else if ((st = scratch_alloc(lp, &h.gsend, bytes, false))) return st;
-  // all of these outlive the entries processed in between: move them from the per-entry list to the held list
-  for (void *q : lp->scratch) lp->held.push_back(q);
-  lp->scratch.clear();
-  // Blocks of about 2 GiB (at most 8): the first block is on its way after a fraction of the packing, and the boundary tiles
-  // of the first blocks run while the last ones still travel -- with ONE message the transfer could not start before all
-  // face layers were packed (12 ms at configs[2]) and no boundary tile before the last byte had landed.  MUGIQ_HIP_HALO_BLOCKS
-  // fixes the number (1 = the single message of round 2).
-  int nb = (int)std::min<size_t>(8, std::max<size_t>(1, (bytes + ((size_t)1 << 31) - 1) >> 31));
-  if (h.selfAlias) nb = 1;  // nothing travels: one block, one launch of the boundary tiles
-  if (const char *e = getenv("MUGIQ_HIP_HALO_BLOCKS")) nb = std::max(1, std::min(64, atoi(e)));
-  nb = std::min(nb, lp->nEv);
-  h.blockN = (lp->nEv + nb - 1) / nb;
-  h.nBlocks = (lp->nEv + h.blockN - 1) / h.blockN;
-  while ((int)h.evBlock.size() < h.nBlocks) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    MUGIQ_CHECK_HIP(hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-    MUGIQ_CHECK_HIP(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-    h.evPackedBlk.push_back(e0);
-    h.evBlock.push_back(e1);
+  for (auto &Ek : E)
+    if ((st = make_scratch_field(lp, &Ek, 2, false))) return st;  // every site of E_k is written below
+  if ((st = fill_identity_links(&E[0], lp->stream))) return st;
+  void *send_d, *recv_d;
+  if ((st = face_buffers(lp, e, 1, &send_d, &recv_d))) return st;
+  for (int k = 1; k <= stop; k++) {  // compute stream: the entry's kernels read them there
+    if (e.part && (st = exchange_face(lp, id, &E[k - 1], send_d, recv_d))) return st;
+    if ((st = mugiq_hip_perform_covariant_displacement_vector(&E[k], &E[k - 1], &lp->gauge, dir, sign, lp->commDim, lp->stream))) return st;
   }
-  h.posted = true;
-  h.entryPacksFrom = -1;
-  return MUGIQ_HIP_SUCCESS;
+  if (!e.buildGaugeFromLinks) return MUGIQ_HIP_SUCCESS;
+  std::vector<const void *> lk;
+  for (int k = 1; k <= stop; k++) lk.push_back(E[k].data);
+  if ((st = scratch_alloc(lp, G, (size_t)e.gaugeBytes, false))) return st;
+  return build_axial_gauge(*G, lp->eVecs[0], lk.data(), stop, dir, sign, lp->stream);
 }
 
-// step 2: block b of every posted entry -- packed on the pack stream, handed to the transport on the halo stream (the entries
-// of one block inside one transfer group: different axes, different links).  which: -1 every posted entry | 0 only those whose
-// block b is packed by mugiq_hip_pack_face_layers | 1 only those whose block b the first entry has written (the pack stream
-// waits for that entry; see mugiq_hip_loop_compute)
-static bool entry_packs_block(const MugiqHipLoop::HaloPost &h, int b) { return h.entryPacksFrom >= 0 && b * h.blockN >= h.entryPacksFrom; }
-static int send_halo_block(MugiqHipLoop *lp, int b, bool grouped, int which = -1) {
+// Block b of every posted entry (buffers: prepare_halos) -- packed on the pack stream, handed to the transport on the halo stream
+// (the entries of one block inside one transfer group: different axes, different links).  which: -1 every posted entry | 0 only those
+// whose block b is packed by mugiq_hip_pack_face_layers | 1 only those whose block b the first entry has written (the pack stream
+// waits for that entry; see post_halos_entry_packs)
+static bool entry_packs_block(const EntryPlan &e, int b) { return e.entryPacksFrom >= 0 && b * e.blockN >= e.entryPacksFrom; }
+static int send_halo_block(MugiqHipLoop *lp, int b, int which = -1) {
   int st = MUGIQ_HIP_SUCCESS;
-  auto takes = [&](const MugiqHipLoop::HaloPost &h) {
-    return h.posted && b < h.nBlocks && (which < 0 || (which == 1) == entry_packs_block(h, b));
-  };
+  std::vector<int> ids;  // the entries that take part, and whether any of them sends a message
+  bool grouped = false;
   for (int id = 0; id < lp->nDispEntries; id++) {
-    MugiqHipLoop::HaloPost &h = lp->halo[id];
-    if (!takes(h)) continue;
-    const int dir = lp->dispDir[id], sign = lp->dispSign[id], stop = lp->dispStop[id];
-    const int n0 = b * h.blockN, nv = std::min(h.blockN, lp->nEv - n0);
-    const size_t perVec = halo_bytes(lp, id) / (size_t)lp->nEv;
-    const int high = (sign == MUGIQ_HIP_DISP_SIGN_PLUS) ? 0 : 1;
-    if (!entry_packs_block(h, b) &&
-        (st = mugiq_hip_pack_face_layers(static_cast<char *>(h.gsend) + perVec * n0, &lp->eVecs[n0], nv, dir, high, stop, lp->packStream)))
-      return st;
-    MUGIQ_CHECK_HIP(hipEventRecord(h.evPackedBlk[b], lp->packStream));
-    MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->commStream, h.evPackedBlk[b], 0));
+    const EntryPlan &e = lp->plan.entry[id];
+    if (!e.ahead || b >= e.nBlocks || (which >= 0 && (which == 1) != entry_packs_block(e, b))) continue;
+    ids.push_back(id);
+    grouped = grouped || (lp->plan.grouped && !e.selfAlias);
   }
-  bool anyMessage = false;
-  for (int id = 0; id < lp->nDispEntries; id++) anyMessage = anyMessage || (takes(lp->halo[id]) && !lp->halo[id].selfAlias);
-  grouped = grouped && anyMessage;
+  for (int id : ids) {
+    const EntryPlan &e = lp->plan.entry[id];
+    const int n0 = b * e.blockN, nv = std::min(e.blockN, lp->nEv - n0);
+    char *send = static_cast<char *>(lp->halo[id].gsend) + (size_t)e.perVecHaloBytes * n0;
+    if (!entry_packs_block(e, b) && (st = mugiq_hip_pack_face_layers(send, &lp->eVecs[n0], nv, lp->dispDir[id], e.high, lp->dispStop[id], lp->packStream)))
+      return st;
+    MUGIQ_CHECK_HIP(hipEventRecord(lp->halo[id].evPackedBlk[b], lp->packStream));
+    MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->commStream, lp->halo[id].evPackedBlk[b], 0));
+  }
   if (grouped && (st = lp->comm.group_begin(lp->comm.ctx))) return set_error(MUGIQ_HIP_ERROR_HIP, "group_begin callback failed with status %d", st);
-  for (int id = 0; id < lp->nDispEntries && !st; id++) {
-    MugiqHipLoop::HaloPost &h = lp->halo[id];
-    if (!takes(h) || h.selfAlias) continue;
-    const int n0 = b * h.blockN, nv = std::min(h.blockN, lp->nEv - n0);
-    const size_t perVec = halo_bytes(lp, id) / (size_t)lp->nEv;
-    const int high = (lp->dispSign[id] == MUGIQ_HIP_DISP_SIGN_PLUS) ? 0 : 1;
-    const int rc = lp->comm.sendrecv(lp->comm.ctx, static_cast<char *>(h.gsend) + perVec * n0, static_cast<char *>(h.grecv) + perVec * n0,
-                                     perVec * nv, lp->dispDir[id], high ? +1 : -1, lp->commStream);
-    if (rc) st = set_error(MUGIQ_HIP_ERROR_HIP, "halo sendrecv callback failed with status %d", rc);
+  for (int id : ids) {
+    const EntryPlan &e = lp->plan.entry[id];
+    if (e.selfAlias || st) continue;
+    const int n0 = b * e.blockN, nv = std::min(e.blockN, lp->nEv - n0);
+    const size_t off = (size_t)e.perVecHaloBytes * n0;
+    st = halo_sendrecv(lp, static_cast<char *>(lp->halo[id].gsend) + off, static_cast<char *>(lp->halo[id].grecv) + off,
+                       (size_t)e.perVecHaloBytes * nv, lp->dispDir[id], e.high, lp->commStream);
   }
   if (grouped) {
     const int st2 = lp->comm.group_end(lp->comm.ctx, lp->commStream);
     if (!st && st2) st = set_error(MUGIQ_HIP_ERROR_HIP, "group_end callback failed with status %d", st2);
   }
   if (st) return st;
-  for (int id = 0; id < lp->nDispEntries; id++) {
-    MugiqHipLoop::HaloPost &h = lp->halo[id];
-    if (takes(h)) MUGIQ_CHECK_HIP(hipEventRecord(h.evBlock[b], lp->commStream));
-  }
+  for (int id : ids) MUGIQ_CHECK_HIP(hipEventRecord(lp->halo[id].evBlock[b], lp->commStream));
   return MUGIQ_HIP_SUCCESS;
 }
 
@@ -645,13 +498,10 @@ static int send_halo_block(MugiqHipLoop *lp, int b, bool grouped, int which = -1
 // is still work that needs none).  pack / nPack / packed: face layers of posted halos for the entry to write (FusedEntryPlan)
 static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0, const EntryPackTarget *pack = nullptr, int nPack = 0,
                        bool *packed = nullptr) {
+  const EntryPlan &e = lp->plan.entry[id];
   const int dir = lp->dispDir[id], sign = lp->dispSign[id];
-  const bool part = lp->commDim[dir] != 0;
   const int stop = lp->dispStop[id], start = lp->dispStart[id];
   int st;
-  // a displacement longer than the local extent of a partitioned dimension reaches past the nearest neighbour: the
-  // multi-layer halo cannot serve it, the step-by-step sequence (one face per step) can
-  if (entry_stepwise(lp, id)) return entry_stepwise_blocked(lp, id, slot0);
   const MugiqHipSpinorField *evL = lp->twoSided ? lp->eVecsL.data() : nullptr;  // (two-sided: the left set of the tile)
   int kernel = -1;
   struct KernelRecord {  // what produced the entry, on every way out
@@ -662,24 +512,22 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0, 
       if (*k >= 0) lp->entryKernel[id] = *k;
     }
   } kernelRecord{lp, id, &kernel};
-  const bool ahead = part && lp->halo[id].posted;
-  std::vector<int> kv;
-  for (int k = start; k <= stop; k++) kv.push_back(k);
   // the entry's gauge and link fields: built here, or by prepare_halo when its halo was posted ahead
   void *gauge = nullptr;
   std::vector<MugiqHipSpinorField> Elocal;
-  if (!ahead && (st = build_entry_links(lp, id, false, &gauge, Elocal))) return st;
-  const std::vector<MugiqHipSpinorField> &E = ahead ? lp->halo[id].E : Elocal;
+  if (!e.ahead && (st = build_entry_links(lp, id, &gauge, Elocal))) return st;
+  const std::vector<MugiqHipSpinorField> &E = e.ahead ? lp->halo[id].E : Elocal;
   std::vector<const void *> links;  // W_start .. W_stop (none: the gauge came straight from the gauge field)
   for (int k = start; k <= stop && !E.empty(); k++) links.push_back(E[k].data);
   // the tile only if the pre-pass allowed it
-  const FusedEntryPlan plan{entry_tile_allowed(lp, id) ? 1 : 0, ahead ? lp->halo[id].axialGauge : gauge, pack, nPack, packed};
+  const FusedEntryPlan plan{e.tile, e.ahead ? lp->halo[id].axialGauge : gauge, pack, nPack, packed};
   auto fused = [&](int n0, int nv, const void *ghost, int region, void *ultra, int *carried) {
     return fused_contraction(slot0, lp->loopPrecision, evL ? evL + n0 : nullptr, &lp->eVecs[n0], &lp->sigma[n0], nv,
-                             links.empty() ? nullptr : links.data(), kv.data(), (int)kv.size(), dir, sign, lp->commDim, ghost, ghost ? stop : 0,
+                             links.empty() ? nullptr : links.data(), e.kv.data(), e.nK, dir, sign, lp->commDim, ghost, ghost ? stop : 0,
                              region, ultra, carried, lp->stream, &kernel, &plan);
   };
-  if (ahead) {
+  const size_t perVec = (size_t)e.perVecHaloBytes;
+  if (e.ahead) {
     // the halo of all eigenvectors was posted at the start of the compute: interior tiles, then (once it has landed) the
     // boundary tiles
     MugiqHipLoop::HaloPost &h = lp->halo[id];
@@ -691,9 +539,8 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0, 
     }
     if (part_sel == 1) return MUGIQ_HIP_SUCCESS;
     // boundary tiles, block of eigenvectors by block as the halo lands: the first block writes the boundary sites, the others add
-    const size_t perVec = halo_bytes(lp, id) / (size_t)lp->nEv;
-    for (int b = 0; b < h.nBlocks; b++) {
-      const int n0 = b * h.blockN, nv = std::min(h.blockN, lp->nEv - n0);
+    for (int b = 0; b < e.nBlocks; b++) {
+      const int n0 = b * e.blockN, nv = std::min(e.blockN, lp->nEv - n0);
       ph = phase_begin(lp, MUGIQ_HIP_PHASE_HALO_WAIT, id, lp->stream);  // idle time of the compute stream: what the overlap did not hide
       MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->stream, h.evBlock[b], 0));
       phase_end(lp, ph, lp->stream);
@@ -706,26 +553,22 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0, 
     return MUGIQ_HIP_SUCCESS;
   }
   // eigenvector blocks: bounded by the ghost-layer buffers when the dimension is partitioned
-  int nb = lp->nEv;
+  const int nb = e.blockN;
   void *gsend = nullptr, *grecv = nullptr;
-  size_t perVec = 0;
-  if (part) {
-    perVec = (size_t)stop * 24 * (lp->volumeCB / lp->localL[dir]) * lp->cplxBytes();
-    const size_t budget = (size_t)4 << 30;  // 4 GiB per direction buffer
-    nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)lp->nEv, budget / perVec));
+  if (e.part) {
     if ((st = scratch_alloc(lp, &grecv, perVec * nb, false))) return st;
-    if (self_neighbour_alias(lp, dir)) gsend = grecv;  // packed straight into the ghost buffer, no message
+    if (e.selfAlias) gsend = grecv;  // packed straight into the ghost buffer, no message
     else if ((st = scratch_alloc(lp, &gsend, perVec * nb, false))) return st;
   }
-  if (part && (st = ensure_comm_stream(lp))) return st;
+  if (e.part && (st = ensure_comm_stream(lp))) return st;
   for (int n0 = 0; n0 < lp->nEv; n0 += nb) {
     const int nv = std::min(nb, lp->nEv - n0);
-    // the slots were not zeroed (see mugiq_hip_loop_compute): the first eigenvector block writes them, later ones add
+    // the slots were not zeroed (see run_entry): the first eigenvector block writes them, later ones add
     const int ow = n0 == 0 ? MUGIQ_HIP_REGION_OVERWRITE : 0;
-    if (!part) {
+    if (!e.part) {
       // (one block here: nb = nEv.)  The first such entry also takes the ultra-local loop along, if the kernel has room
       int carried = 0;
-      void *ultra = (lp->carryUltra && !lp->ultraCarried && nb == lp->nEv) ? lp->dataPos_d : nullptr;
+      void *ultra = (lp->plan.carryUltra && !lp->ultraCarried && nb == lp->nEv) ? lp->dataPos_d : nullptr;
       if ((st = fused(n0, nv, nullptr, MUGIQ_HIP_REGION_ALL | ow, ultra, &carried))) return st;
       if (carried) {
         lp->ultraCarried = true;
@@ -734,15 +577,11 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0, 
       continue;
     }
     // pack the face layers -> [comm stream] exchange them  ||  [compute stream] interior sites -> boundary sites
-    const int high = (sign == MUGIQ_HIP_DISP_SIGN_PLUS) ? 0 : 1;
-    if ((st = mugiq_hip_pack_face_layers(gsend, &lp->eVecs[n0], nv, dir, high, stop, lp->stream))) return st;
+    if ((st = mugiq_hip_pack_face_layers(gsend, &lp->eVecs[n0], nv, dir, e.high, stop, lp->stream))) return st;
     MUGIQ_CHECK_HIP(hipEventRecord(lp->evPacked, lp->stream));
     MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->commStream, lp->evPacked, 0));
     int ph = phase_begin(lp, MUGIQ_HIP_PHASE_HALO_TRANSFER, id, lp->commStream, (double)(perVec * nv));
-    if (gsend != grecv) {
-      st = lp->comm.sendrecv(lp->comm.ctx, gsend, grecv, perVec * nv, dir, high ? +1 : -1, lp->commStream);
-      if (st) return set_error(MUGIQ_HIP_ERROR_HIP, "halo sendrecv callback failed with status %d", st);
-    }
+    if (gsend != grecv && (st = halo_sendrecv(lp, gsend, grecv, perVec * nv, dir, e.high, lp->commStream))) return st;
     phase_end(lp, ph, lp->commStream);
     MUGIQ_CHECK_HIP(hipEventRecord(lp->evHalo, lp->commStream));
     ph = phase_begin(lp, MUGIQ_HIP_PHASE_ENTRY_INTERIOR, id, lp->stream);
@@ -758,47 +597,31 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0, 
   return MUGIQ_HIP_SUCCESS;
 }
 
-// Reflected entries (csrc/reflect.hip): entry `id` can be derived from an entry `jd` computed earlier in this run if jd
-// has the same direction, the opposite sign and covers id's lengths.  Returns the source entry or -1.
-static int reflection_source(const MugiqHipLoop *lp, int id) {
-  if (lp->twoSided) return -1;  // (L^-(x) = eta conj L^+(x - k mu) rests on the left and right vectors being the same)
-  if (const char *e = getenv("MUGIQ_HIP_REFLECT"))
-    if (atoi(e) == 0) return -1;
-  // a length that reaches past the nearest neighbour cannot be served by one halo of the source slot
-  if (lp->commDim[lp->dispDir[id]] && lp->dispStop[id] > lp->localL[lp->dispDir[id]]) return -1;
-  for (int jd = 0; jd < id; jd++)
-    if (lp->dispDir[jd] == lp->dispDir[id] && lp->dispSign[jd] != lp->dispSign[id] && lp->dispStart[jd] <= lp->dispStart[id] &&
-        lp->dispStop[id] <= lp->dispStop[jd] && lp->derivedFrom[jd] < 0)
-      return jd;
-  return -1;
-}
-
+// A reflected entry (csrc/reflect.hip): entry `id` from the complete slots of entry `jd`, computed earlier in this run.
 static int entry_reflected(MugiqHipLoop *lp, int id, int jd, void *slot0) {
+  const EntryPlan &e = lp->plan.entry[id];
   const int dir = lp->dispDir[id], sign = lp->dispSign[id];
-  const bool part = lp->commDim[dir] != 0;
   const size_t slotBytes = (size_t)lp->nElemPosLocPerLoop * lp->loopBytes();
-  const char *src0 = static_cast<const char *>(lp->dataPos_d) + slotBytes * (size_t)lp->nLoopOffset[jd];
+  const char *src0 = static_cast<const char *>(entry_slot(lp, jd));
   const int faceCB = lp->volumeCB / lp->localL[dir];
   int st;
   lp->entryKernel[id] = MUGIQ_HIP_ENTRY_KERNEL_REFLECTED;
-  // a length that reaches past the nearest neighbour cannot be served by one halo: nothing is written, the caller
-  // computes the entry from the eigenvectors
-  if (part && lp->dispStop[id] > lp->localL[dir]) return -1;
+  // (a length past the nearest neighbour cannot be served by one halo of the source slot: the plan never reflects such an entry)
+  if (e.route != MUGIQ_HIP_LOOP_ROUTE_REFLECTED || (e.part && lp->dispStop[id] > lp->localL[dir]))
+    return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "computeCoarseLoop: entry %d cannot be reflected from entry %d (internal)", id, jd);
   for (int k = lp->dispStart[id]; k <= lp->dispStop[id]; k++) {
     void *dst = static_cast<char *>(slot0) + slotBytes * (size_t)(k - lp->dispStart[id]);
     const void *src = src0 + slotBytes * (size_t)(k - lp->dispStart[jd]);
     void *grecv = nullptr;
-    if (part) {
+    if (e.part) {
       // dst "-": the source sites x - k mu below my block are the backward neighbour's top k layers, so every rank sends its
       // top layers forward; dst "+": bottom layers backward
-      const int high = sign == MUGIQ_HIP_DISP_SIGN_MINUS ? 1 : 0;
       const size_t bytes = (size_t)32 * k * faceCB * lp->loopBytes();
       void *gsend = nullptr;
       if ((st = scratch_alloc(lp, &gsend, bytes, false))) return st;
       if ((st = scratch_alloc(lp, &grecv, bytes, false))) return st;
-      if ((st = mugiq_hip_pack_loop_layers(gsend, src, lp->localL, dir, high, k, lp->loopPrecision, lp->stream))) return st;
-      st = lp->comm.sendrecv(lp->comm.ctx, gsend, grecv, bytes, dir, high ? +1 : -1, lp->stream);
-      if (st) return set_error(MUGIQ_HIP_ERROR_HIP, "halo sendrecv callback failed with status %d", st);
+      if ((st = mugiq_hip_pack_loop_layers(gsend, src, lp->localL, dir, e.high, k, lp->loopPrecision, lp->stream))) return st;
+      if ((st = halo_sendrecv(lp, gsend, grecv, bytes, dir, e.high, lp->stream))) return st;
     }
     if ((st = mugiq_hip_reflect_displaced_loop(dst, src, grecv, lp->localL, dir, sign, k, lp->commDim, lp->loopPrecision, lp->stream)))
       return st;
@@ -806,42 +629,20 @@ static int entry_reflected(MugiqHipLoop *lp, int id, int jd, void *slot0) {
   return MUGIQ_HIP_SUCCESS;
 }
 
-// hand the current entry's buffers back to the pool (the stream has been synchronised by the caller)
-static void free_scratch(MugiqHipLoop *lp) {
-  for (void *p : lp->scratch)
-    for (auto &b : lp->pool)
-      if (b.ptr == p) b.inUse = false;
-  lp->scratch.clear();
-}
-static void destroy_pool(MugiqHipLoop *lp) {
-  for (auto &b : lp->pool) (void)hipFree(b.ptr);
-  lp->pool.clear();
-  lp->scratch.clear();
-}
-
 // the position-space slots of the reflected entries a compute left out (momentum-space reflection): produced on first request
 static int materialise_reflected(MugiqHipLoop *lp) {
   if (!lp->posReflectPending) return MUGIQ_HIP_SUCCESS;
-  const size_t cb = lp->loopBytes();
   int st = MUGIQ_HIP_SUCCESS;
   for (int id = 0; id < lp->nDispEntries && !st; id++) {
-    if (lp->derivedFrom[id] < 0) continue;
-    void *slot0 = static_cast<char *>(lp->dataPos_d) + (size_t)lp->nElemPosLocPerLoop * lp->nLoopOffset[id] * cb;
-    st = entry_reflected(lp, id, lp->derivedFrom[id], slot0);
-    free_scratch(lp);
+    const int jd = lp->plan.entry[id].derivedFrom;
+    if (jd < 0) continue;
+    st = entry_reflected(lp, id, jd, entry_slot(lp, id));
+    release_buffers(lp, lp->scratch);
   }
   hipError_t e = hipStreamSynchronize(lp->stream);
   if (!st && e != hipSuccess) st = set_error(MUGIQ_HIP_ERROR_HIP, "dataPos: %s", hipGetErrorString(e));
   if (!st) lp->posReflectPending = false;
   return st;
-}
-
-// can the fused reorder + x step take this lattice?  (else: reorder, then the three separable steps)
-static bool fused_projection_applies(const MugiqHipLoop *lp) {
-  std::vector<int> px;
-  for (int n = 0; n < lp->Nmom; n++)
-    if (std::find(px.begin(), px.end(), lp->momMatrix[3 * n]) == px.end()) px.push_back(lp->momMatrix[3 * n]);
-  return eo_dft_x_time_chunk(lp->loopPrecision, lp->localL, (int)px.size()) >= 1 && lp->localL[2] <= 65535 && lp->nData <= 65535;
 }
 
 // Loop_Mugiq::performMomentumProjection  lib/loop_mugiq.cpp:322-434
@@ -864,10 +665,10 @@ static int momentum_projection(MugiqHipLoop *lp) {
     int coord[4] = {0, 0, 0, 0};
     if (lp->haveComm)
       for (int d = 0; d < 4; d++) coord[d] = lp->comm.coord[d];
-    if (lp->momReflect) {
+    if (lp->plan.momReflect) {
       // only the slots computed from the eigenvectors are transformed; the reflected ones follow on the gathered array below
       for (int id = -1; id < lp->nDispEntries; id++) {
-        if (id >= 0 && lp->derivedFrom[id] >= 0) continue;
+        if (id >= 0 && lp->plan.entry[id].derivedFrom >= 0) continue;
         const int first = id < 0 ? 0 : lp->nLoopOffset[id], cnt = id < 0 ? 1 : lp->nLoopPerEntry[id];
         for (int i = 0; i < cnt; i++) activeSlots.push_back(first + i);
       }
@@ -876,7 +677,7 @@ static int momentum_projection(MugiqHipLoop *lp) {
                                                     lp->momMatrix.data(), lp->Nmom, lp->FTSign, lp->localL, lp->totalL, coord,
                                                     lp->loopPrecision, nullptr, 0, lp->stream)))
         return st;
-    } else if (fused_projection_applies(lp)) {
+    } else if (fused_projection_applies(lp->loopPrecision, lp->localL, lp->nData, lp->momMatrix.data(), lp->Nmom)) {
       if ((st = mugiq_hip_convert_and_project(lp->dataMom_d, lp->dataPos_d, lp->nData, lp->nLoop, lp->momMatrix.data(), lp->Nmom, lp->FTSign,
                                               lp->localL, lp->totalL, coord, lp->loopPrecision, nullptr, 0, lp->stream)))
         return st;
@@ -909,7 +710,7 @@ static int momentum_projection(MugiqHipLoop *lp) {
   }  // (one process: dataMom and dataMom_bcast alias dataMom_h)
   phase_host(lp, MUGIQ_HIP_PHASE_MOMENTUM_REDUCE, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tRed0).count(),
              2.0 * (double)lp->nElemMomLoc * lp->loopPrecision);
-  if (lp->momReflect) {
+  if (lp->plan.momReflect) {
     // the reflected entries, on the gathered array (every rank holds it after the broadcast): csrc/reflect_mom.cpp
     const auto tRef0 = std::chrono::steady_clock::now();
     struct Task {
@@ -917,7 +718,7 @@ static int momentum_projection(MugiqHipLoop *lp) {
     };
     std::vector<Task> tasks;
     for (int id = 0; id < lp->nDispEntries; id++) {
-      const int jd = lp->derivedFrom[id];
+      const int jd = lp->plan.entry[id].derivedFrom;
       if (jd < 0) continue;
       for (int k = lp->dispStart[id]; k <= lp->dispStop[id]; k++)
         tasks.push_back({lp->nLoopOffset[id] + k - lp->dispStart[id], lp->nLoopOffset[jd] + k - lp->dispStart[jd], lp->dispDir[id], lp->dispSign[id], k});
@@ -945,6 +746,221 @@ static int momentum_projection(MugiqHipLoop *lp) {
     phase_host(lp, MUGIQ_HIP_PHASE_MOMENTUM_REFLECT, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tRef0).count());
   }
   lp->momProjDone = true;
+  return MUGIQ_HIP_SUCCESS;
+}
+
+// ---- mugiq_hip_loop_compute, step by step --------------------------------------------------------------------------
+struct ComputeState {
+  std::vector<int> pendingBoundary;  // entries whose interior tiles are out and whose boundary tiles wait for their halo
+  int phPack = -1, phHalo = -1;      // the HALO_PREPARE / HALO_TRANSFER phases of the posted halos
+  int maxBlocks = 0;                 // the most blocks any posted halo travels in
+};
+
+// coarse eigenvectors -> the fine ones the entries read (MG path)
+static int prolong_inputs(MugiqHipLoop *lp) {
+  int st;
+  if (lp->coarseMode && lp->levelVecs.size() > 1) {
+    // coarsest level -> level 1 through the upper transfer operators (lib/loop_mugiq.cpp:306-311), all eigenvectors per launch
+    const int ph = phase_begin(lp, MUGIQ_HIP_PHASE_PROLONGATION, -1, lp->stream);
+    for (int l = (int)lp->levelVecs.size() - 1; l >= 1; l--)
+      if ((st = mugiq_hip_prolongate_coarse_batched(lp->levelVecs[l - 1].data(), lp->levelVecs[l].data(), lp->nEv, &lp->upper[l - 1], lp->stream)))
+        return st;
+    phase_end(lp, ph, lp->stream);
+  }
+  if (lp->coarseMode && lp->fineStore) {
+    // prolongateEvec for every eigenvector, once (the reference repeats it per displacement entry, lib/loop_mugiq.cpp:482)
+    const int ph = phase_begin(lp, MUGIQ_HIP_PHASE_PROLONGATION, -1, lp->stream);
+    if ((st = mugiq_hip_prolongate_batched(lp->eVecs.data(), lp->coarseVecs.data(), lp->nEv, &lp->transfer, lp->stream))) return st;
+    phase_end(lp, ph, lp->stream);
+  }
+  return MUGIQ_HIP_SUCCESS;
+}
+
+// the plan of this compute: the caller's gauge may have changed since the last one, so the pre-pass runs again
+static int plan_compute(MugiqHipLoop *lp) {
+  if (lp->calcType != MUGIQ_HIP_LOOP_CALC_TYPE_BASIC_KERNEL && lp->nDispEntries > 0) {
+    const int ph = phase_begin(lp, MUGIQ_HIP_PHASE_AXIAL_CHECK, -1, lp->stream);
+    if (int st = check_axial_gauge(lp)) return st;
+    phase_end(lp, ph, lp->stream);
+  }
+  lp->halo.resize(lp->nDispEntries);
+  lp->ultraCarried = lp->posReflectPending = false;
+  lp->ultraCarrier = -1;
+  lp->halosPackedInEntry = 0;
+  return make_plan(lp);
+}
+
+// One entry of the order (-1: the ultra-local loop).  holdScratch: its buffers stay out of the pool until the compute ends.
+static int run_entry(MugiqHipLoop *lp, ComputeState &cs, int id, bool holdScratch = false, const std::vector<EntryPackTarget> &pack = {},
+                     bool *packed = nullptr) {
+  const bool basic = lp->calcType == MUGIQ_HIP_LOOP_CALC_TYPE_BASIC_KERNEL;
+  const EntryPlan *e = id >= 0 ? &lp->plan.entry[id] : nullptr;
+  if (!e && lp->plan.carryUltra && lp->ultraCarried) return MUGIQ_HIP_SUCCESS;  // produced by a displaced entry's pass
+  if (e && lp->plan.momReflect && e->derivedFrom >= 0) {  // derived in momentum space; position space on request
+    lp->posReflectPending = true;
+    lp->entryKernel[id] = MUGIQ_HIP_ENTRY_KERNEL_REFLECTED;
+    return MUGIQ_HIP_SUCCESS;
+  }
+  void *slot0 = entry_slot(lp, id);  // :465-474
+  // cudaMemset :476 -- needed where kernels accumulate into the slots: the ultra-local loop, the BASIC plan, and an OPT entry that
+  // goes step by step.  Reflected entries and the fused displaced contraction write every site of their slots
+  // (MUGIQ_HIP_REGION_OVERWRITE).
+  if (!e || e->needsMemset)
+    MUGIQ_CHECK_HIP(hipMemsetAsync(slot0, 0, lp->loopBytes() * (size_t)lp->nElemPosLocPerLoop * (e ? lp->nLoopPerEntry[id] : 1), lp->stream));
+  const bool split = e && e->route == MUGIQ_HIP_LOOP_ROUTE_FUSED && e->part;  // entry_fused opens its own phases
+  const int ph = split ? -1
+                       : phase_begin(lp, !e ? MUGIQ_HIP_PHASE_ULTRA_LOCAL
+                                            : e->route == MUGIQ_HIP_LOOP_ROUTE_REFLECTED  ? MUGIQ_HIP_PHASE_ENTRY_REFLECTED
+                                              : e->route == MUGIQ_HIP_LOOP_ROUTE_STEPWISE ? MUGIQ_HIP_PHASE_ENTRY_STEPWISE
+                                                                                          : MUGIQ_HIP_PHASE_ENTRY_FUSED,
+                                     id, lp->stream);
+  int st = MUGIQ_HIP_SUCCESS;
+  if (!e && lp->coarseMode && !lp->fineStore) {
+    // MG ultra-local loop without materialising the fine vectors
+    st = mugiq_hip_prolongate_contract_batched(slot0, lp->loopPrecision, lp->coarseVecs.data(), lp->sigma.data(), lp->nEv, &lp->transfer,
+                                               lp->stream);
+  } else if (!e) {
+    const int step = basic ? 1 : lp->nEv;  // BASIC: one launch per eigenvector (:501-502)
+    for (int n = 0; n < lp->nEv && !st; n += step)
+      st = mugiq_hip_perform_loop_contraction_batched_mixed(slot0, lp->loopPrecision, lp->left() + n, &lp->eVecs[n], &lp->sigma[n], step, lp->stream);
+  } else {
+    if (basic) st = entry_basic(lp, id, slot0);
+    else if (e->route == MUGIQ_HIP_LOOP_ROUTE_REFLECTED) st = entry_reflected(lp, id, e->derivedFrom, slot0);
+    else if (e->route == MUGIQ_HIP_LOOP_ROUTE_STEPWISE) st = entry_stepwise_blocked(lp, id, slot0);
+    else if (e->ahead) {
+      st = entry_fused(lp, id, slot0, 1);  // interior tiles now; the boundary tiles once every entry's interior is through
+      cs.pendingBoundary.push_back(id);
+    } else st = entry_fused(lp, id, slot0, 0, pack.data(), (int)pack.size(), packed);
+    // No host synchronisation between entries: every user of this entry's scratch is ordered on lp->stream (the halo
+    // stream's part was waited for by the boundary kernels), so the next entry may take the buffers over at once.
+    // The exception is the entry that runs BEFORE the halos are posted: the pack and halo streams start from an event
+    // recorded ahead of it, so a buffer it hands back could be given to prepare_halo as gsend / grecv and be written by the
+    // pack kernels while this entry's kernels still read it.  Its scratch stays out of the pool until the compute ends.
+    if (holdScratch) hold_scratch(lp);
+    else release_buffers(lp, lp->scratch);
+  }
+  phase_end(lp, ph, lp->stream);
+  return st;
+}
+
+// the boundary tiles of the posted entries whose interior tiles are out
+static int run_boundaries(MugiqHipLoop *lp, ComputeState &cs) {
+  for (int id : cs.pendingBoundary) {
+    if (int st = entry_fused(lp, id, entry_slot(lp, id), 2)) return st;
+    release_buffers(lp, lp->scratch);
+  }
+  cs.pendingBoundary.clear();
+  return MUGIQ_HIP_SUCCESS;
+}
+
+// ---- the halos of the plan: link fields, packed face layers, one transfer group per block on the halo stream
+static int prepare_halos(MugiqHipLoop *lp, ComputeState &cs) {
+  double haloBytes = 0;
+  for (int id = 0; id < lp->nDispEntries; id++) {
+    const EntryPlan &e = lp->plan.entry[id];
+    if (!e.ahead) continue;
+    // its links (the small face exchanges of the link fields happen here, at once), ghost buffers for ALL eigenvectors, and the events
+    // of the blocks of eigenvectors the halo travels in: all of these outlive the entries processed in between
+    MugiqHipLoop::HaloPost &h = lp->halo[id];
+    int st;
+    if ((st = build_entry_links(lp, id, &h.axialGauge, h.E)) || (st = scratch_alloc(lp, &h.grecv, (size_t)e.haloBytes, false))) return st;
+    if (e.selfAlias) h.gsend = h.grecv;
+    else if ((st = scratch_alloc(lp, &h.gsend, (size_t)e.haloBytes, false))) return st;
+    hold_scratch(lp);
+    for (auto *ev : {&h.evPackedBlk, &h.evBlock})
+      while ((int)ev->size() < e.nBlocks) {
+        ev->push_back(nullptr);
+        MUGIQ_CHECK_HIP(hipEventCreateWithFlags(&ev->back(), hipEventDisableTiming));
+      }
+    haloBytes += (double)e.haloBytes;
+    cs.maxBlocks = std::max(cs.maxBlocks, e.nBlocks);
+  }
+  // the pack stream starts where the halo stream starts (behind what the compute stream held when the compute began)
+  MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->packStream, lp->evPacked, 0));
+  cs.phPack = phase_begin(lp, MUGIQ_HIP_PHASE_HALO_PREPARE, -1, lp->packStream, haloBytes);
+  cs.phHalo = phase_begin(lp, MUGIQ_HIP_PHASE_HALO_TRANSFER, -1, lp->commStream, haloBytes);
+  return MUGIQ_HIP_SUCCESS;
+}
+static int send_halos(MugiqHipLoop *lp, ComputeState &cs, int bFirst) {  // blocks bFirst .. of every posted entry
+  for (int b = bFirst; b < cs.maxBlocks; b++)
+    if (int st = send_halo_block(lp, b)) return st;
+  phase_end(lp, cs.phPack, lp->packStream);
+  phase_end(lp, cs.phHalo, lp->commStream);
+  return MUGIQ_HIP_SUCCESS;
+}
+
+// Who packs?  Pack kernels beside a tile kernel that fills every CU's registers and LDS do not overlap with it, they take turns
+// (configs[2] per-GPU job: 12.6 ms of packing made the first entry 10 ms longer).  Variant 1: the early entry writes the face layers of
+// plan.packTargets itself -- every raw eigenvector passes through its registers anyway -- and the pack kernels read nothing a second
+// time.  The first blocks that are packed by their kernels are on their way before the entry starts: the link must not wait for it.
+static int post_halos_entry_packs(MugiqHipLoop *lp, ComputeState &cs) {
+  const int early = lp->plan.earlyEntry;
+  std::vector<EntryPackTarget> targets;
+  for (int id : lp->plan.packTargets)
+    targets.push_back(EntryPackTarget{lp->halo[id].gsend, lp->dispDir[id], lp->plan.entry[id].high, lp->dispStop[id], lp->plan.entry[id].entryPacksFrom});
+  bool taken = false;
+  int st = send_halo_block(lp, 0, 0);
+  if (st || (st = run_entry(lp, cs, early, true, targets, &taken))) return st;
+  if (!taken)
+    return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "computeCoarseLoop: entry %d was to write the face layers of the posted halos and did not (internal)", early);
+  lp->halosPackedInEntry = (int)targets.size();
+  MUGIQ_CHECK_HIP(hipEventRecord(lp->evEntryPacked, lp->stream));
+  MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->packStream, lp->evEntryPacked, 0));
+  if ((st = send_halo_block(lp, 0, 1))) return st;
+  return send_halos(lp, cs, 1);
+}
+
+// The halos posted ahead, and the entry that needs none and goes FIRST: a pack kernel launched ahead of it fills the device and the
+// entry's kernels queue up behind it (measured: the compute stream made no progress during the 12 ms of packing even with the packs on
+// the halo stream); launched behind a tiled kernel that is already resident -- one workgroup per CU, LDS-bound occupancy -- the packs
+// and the transfer run in its shadow instead.  Variant 2: the early entry runs, then the pack kernels (the halos prepared before it
+// where it could have taken pack targets and got none, else behind it).  Variant 3: no early entry.
+static int post_halos(MugiqHipLoop *lp, ComputeState &cs) {
+  const LoopPlan &P = lp->plan;
+  if (!P.postHalos) return MUGIQ_HIP_SUCCESS;
+  int st = ensure_comm_stream(lp);
+  if (st) return st;
+  // the halo stream starts behind what the compute stream holds so far (e.g. the prolongation that writes the eigenvectors)
+  MUGIQ_CHECK_HIP(hipEventRecord(lp->evPacked, lp->stream));
+  MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->commStream, lp->evPacked, 0));
+  const bool prepareFirst = P.earlyEntry < 0 || P.earlyPackRoom > 0;
+  if (prepareFirst && (st = prepare_halos(lp, cs))) return st;
+  if (!P.packTargets.empty()) return post_halos_entry_packs(lp, cs);
+  if (P.earlyEntry >= 0 && (st = run_entry(lp, cs, P.earlyEntry, true))) return st;
+  if (!prepareFirst && (st = prepare_halos(lp, cs))) return st;
+  return send_halos(lp, cs, 0);
+}
+
+// the entries in the order of the plan, then the device part is complete
+static int run_entries(MugiqHipLoop *lp, ComputeState &cs) {
+  int st = post_halos(lp, cs);
+  for (int id : lp->plan.order) {
+    if (st) break;
+    if (id == lp->plan.earlyEntry) continue;
+    // reflected entries and the ultra-local loop come after the computed ones: the boundary tiles go before them (a reflected
+    // entry reads the complete slots of its source)
+    if (!cs.pendingBoundary.empty() && (id < 0 || lp->plan.entry[id].derivedFrom >= 0)) st = run_boundaries(lp, cs);
+    if (!st) st = run_entry(lp, cs, id);
+  }
+  if (!st) st = run_boundaries(lp, cs);
+  hipError_t e = hipStreamSynchronize(lp->stream);
+  if (!st && e != hipSuccess) st = set_error(MUGIQ_HIP_ERROR_HIP, "computeCoarseLoop: %s", hipGetErrorString(e));
+  return st;
+}
+
+// performMomentumProjection :517-520, and the end of the compute
+static int project_and_finish(MugiqHipLoop *lp, std::chrono::steady_clock::time_point tWall0) {
+  lp->dataPosCopied = false;
+  if (lp->doMomProj)
+    if (int st = momentum_projection(lp)) return st;
+  MUGIQ_CHECK_HIP(hipStreamSynchronize(lp->stream));
+  if (lp->profiling) {
+    if (lp->packStream) MUGIQ_CHECK_HIP(hipStreamSynchronize(lp->packStream));  // HALO_PREPARE's end event is recorded there
+    if (lp->commStream) MUGIQ_CHECK_HIP(hipStreamSynchronize(lp->commStream));
+    phases_resolve(lp);
+    phase_host(lp, MUGIQ_HIP_PHASE_TOTAL_WALL, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall0).count());
+  }
+  lp->computed = true;
   return MUGIQ_HIP_SUCCESS;
 }
 
@@ -1115,7 +1131,6 @@ static int loop_create(MugiqHipLoop **out, const MugiqHipLoopParam *p, const Mug
       if ((st = parse_displacement(lp->dispString[id].c_str(), &dir, &sign))) return fail(st);  // Displace::setupDisplacement
       lp->dispDir.push_back(dir);
       lp->dispSign.push_back(sign);
-      lp->derivedFrom.push_back(-1);
       lp->entryKernel.push_back(-1);
     }
     lp->nLoop += 1;  // Don't forget ultra-local case!!
@@ -1125,7 +1140,6 @@ static int loop_create(MugiqHipLoop **out, const MugiqHipLoopParam *p, const Mug
         return fail(MUGIQ_HIP_ERROR_INVALID_ARGUMENT);
       }
       lp->gauge = *p->gauge;
-      lp->haveGauge = true;
       for (int d = 0; d < 4; d++)
         if (lp->commDim[d] && lp->gauge.R[d] < 1) {
           set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "%s: dim %d is partitioned but the gauge border R[%d] = %d (the reference uses 2, lib/displace.cpp:16)", who, d, d, lp->gauge.R[d]);
@@ -1180,8 +1194,9 @@ static int loop_create(MugiqHipLoop **out, const MugiqHipLoopParam *p, const Mug
                                             lp->totalL, cc, lp->loopPrecision, lp->stream)))
       return fail(st);
   }
-  // the buffers the OPT plan will hold for the halos it posts ahead (the large allocations of a partitioned run)
-  if (lp->haveGauge && (st = reserve_plan_buffers(lp))) return fail(st);
+  // the plan as it stands now, and the buffers it will hold for the halos it posts ahead
+  if (lp->calcType != MUGIQ_HIP_LOOP_CALC_TYPE_BASIC_KERNEL && lp->nDispEntries > 0 && (st = check_axial_gauge(lp))) return fail(st);
+  if ((st = make_plan(lp)) || (st = reserve_plan_buffers(lp))) return fail(st);
   *out = lp;
   return MUGIQ_HIP_SUCCESS;
 }
@@ -1296,286 +1311,20 @@ int mugiq_hip_loop_create_coarse(MugiqHipLoop **out, const MugiqHipLoopParam *p,
 
 int mugiq_hip_loop_compute(MugiqHipLoop *lp) {
   MUGIQ_REQUIRE(lp != nullptr, "computeCoarseLoop: NULL loop handle");
-  int st = MUGIQ_HIP_SUCCESS;
-  const size_t cb = lp->loopBytes();
-  const bool basic = lp->calcType == MUGIQ_HIP_LOOP_CALC_TYPE_BASIC_KERNEL;
   lp->phases.clear();
   lp->eventsUsed = 0;
-  lp->carryUltra = lp->ultraCarried = false;
-  lp->ultraCarrier = -1;
   std::fill(lp->entryKernel.begin(), lp->entryKernel.end(), -1);
   const auto tWall0 = std::chrono::steady_clock::now();
-  if (lp->coarseMode && lp->levelVecs.size() > 1) {
-    // coarsest level -> level 1 through the upper transfer operators (lib/loop_mugiq.cpp:306-311), all eigenvectors per launch
-    const int ph = phase_begin(lp, MUGIQ_HIP_PHASE_PROLONGATION, -1, lp->stream);
-    for (int l = (int)lp->levelVecs.size() - 1; l >= 1; l--)
-      if ((st = mugiq_hip_prolongate_coarse_batched(lp->levelVecs[l - 1].data(), lp->levelVecs[l].data(), lp->nEv, &lp->upper[l - 1], lp->stream)))
-        return st;
-    phase_end(lp, ph, lp->stream);
-  }
-  if (lp->coarseMode && lp->fineStore) {
-    // prolongateEvec for every eigenvector, once (the reference repeats it per displacement entry, lib/loop_mugiq.cpp:482)
-    const int ph = phase_begin(lp, MUGIQ_HIP_PHASE_PROLONGATION, -1, lp->stream);
-    if ((st = mugiq_hip_prolongate_batched(lp->eVecs.data(), lp->coarseVecs.data(), lp->nEv, &lp->transfer, lp->stream))) return st;
-    phase_end(lp, ph, lp->stream);
-  }
-  // ---- plan (OPT): which entries are reflected from which, and in what order things run.  The slots are independent,
-  // so the order of lib/loop_mugiq.cpp:455 is kept for BASIC only; OPT posts the eigenvector halos of all partitioned
-  // entries first, runs the ultra-local loop and the entries of unpartitioned directions while they travel, then the
-  // partitioned entries (interior tiles before the halo is waited for), and the reflected entries last.
-  std::vector<int> order;
-  order.push_back(-1);
-  int earlyEntry = -2;        // OPT plan with halos to post: the entry that runs before they are packed (-2: none)
-  bool postHalos = false;
-  bool grouped = false;
-  std::vector<char> aheadFlags;
-  if (basic) {
-    for (int id = 0; id < lp->nDispEntries; id++) {
-      lp->derivedFrom[id] = -1;
-      order.push_back(id);
-    }
-  } else {
-    lp->halo.resize(lp->nDispEntries);
-    if (lp->nDispEntries > 0) {
-      const int ph = phase_begin(lp, MUGIQ_HIP_PHASE_AXIAL_CHECK, -1, lp->stream);
-      if ((st = check_axial_gauge(lp))) return st;
-      phase_end(lp, ph, lp->stream);
-    }
-    std::vector<char> ahead;
-    if ((st = plan_opt(lp, ahead))) return st;
-    bool any = false;
-    for (int id = 0; id < lp->nDispEntries; id++) {
-      lp->halo[id].posted = false;
-      any = any || ahead[id];
-    }
-    // momentum-space output only needs the reflected entries in momentum space (csrc/reflect_mom.cpp): when the momentum list
-    // holds -p for every p they are left out of position space, of the reorder and of the Fourier kernels, and derived on the
-    // gathered array; dataPos materialises them on first request (MUGIQ_HIP_REFLECT_MOM=0: always in position space)
-    lp->momReflect = false;
-    if (lp->doMomProj && !lp->momProjDone) {
-      bool anyDerived = false;
-      for (int id = 0; id < lp->nDispEntries; id++) anyDerived = anyDerived || lp->derivedFrom[id] >= 0;
-      std::vector<int> neg;
-      bool on = true;
-      if (const char *e = getenv("MUGIQ_HIP_REFLECT_MOM")) on = atoi(e) != 0;
-      lp->momReflect = on && anyDerived && fused_projection_applies(lp) && momenta_negation_table(lp->momMatrix.data(), lp->Nmom, neg);
-    }
-    grouped = lp->haveComm && lp->comm.group_begin && lp->comm.group_end;
-    for (int pass = 0; pass < 3; pass++)
-      for (int id = 0; id < lp->nDispEntries; id++) {
-        const bool derived = lp->derivedFrom[id] >= 0, part = lp->commDim[lp->dispDir[id]] != 0;
-        if ((pass == 0 && !derived && !part) || (pass == 1 && !derived && part) || (pass == 2 && derived)) order.push_back(id);
-      }
-    // the ultra-local loop may ride along with a displaced entry (MUGIQ_HIP_CARRY_ULTRALOCAL=0: never): it then moves to the end
-    // of the order and is skipped if some entry has taken it along
-    lp->carryUltra = lp->nDispEntries > 0 && !lp->coarseMode;
-    if (const char *e = getenv("MUGIQ_HIP_CARRY_ULTRALOCAL")) lp->carryUltra = lp->carryUltra && atoi(e) != 0;
-    lp->ultraCarried = false;
-    if (lp->carryUltra) {
-      order.erase(order.begin());
-      order.push_back(-1);
-    }
-    earlyEntry = -2;  // (the halos are posted further down, once the order is known)
-    if (any) {
-      if ((st = ensure_comm_stream(lp))) return st;
-      // the halo stream starts behind what the compute stream holds so far (e.g. the prolongation that writes the eigenvectors)
-      MUGIQ_CHECK_HIP(hipEventRecord(lp->evPacked, lp->stream));
-      MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->commStream, lp->evPacked, 0));
-      // One entry that needs no halo goes FIRST, before the halos are packed: a pack kernel launched ahead of it fills the
-      // device and the entry's kernels queue up behind it (measured: the compute stream made no progress during the 12 ms of
-      // packing even with the packs on the halo stream); launched behind a tiled kernel that is already resident -- one
-      // workgroup per CU, LDS-bound occupancy -- the packs and the transfer run in its shadow instead.
-      for (int id : order)
-        if (id >= 0 && lp->derivedFrom[id] < 0 && !lp->commDim[lp->dispDir[id]]) {
-          earlyEntry = id;
-          break;
-        }
-    }
-    postHalos = any;
-    aheadFlags = ahead;
-  }
-  lp->posReflectPending = false;
-  std::vector<int> pendingBoundary;  // entries whose interior tiles are out and whose boundary tiles wait for their halo
-  auto run_boundaries = [&]() -> int {
-    for (int id : pendingBoundary) {
-      void *slot0 = static_cast<char *>(lp->dataPos_d) + (size_t)lp->nElemPosLocPerLoop * lp->nLoopOffset[id] * cb;
-      if ((st = entry_fused(lp, id, slot0, 2))) return st;
-      free_scratch(lp);
-    }
-    pendingBoundary.clear();
-    return MUGIQ_HIP_SUCCESS;
-  };
-  auto run_one = [&](int id, bool holdScratch = false, const std::vector<EntryPackTarget> &pack = {}, bool *packed = nullptr) -> int {
-    if (id == -1 && !basic && lp->carryUltra && lp->ultraCarried) return MUGIQ_HIP_SUCCESS;  // produced by a displaced entry's pass
-    if (id >= 0 && !basic && lp->momReflect && lp->derivedFrom[id] >= 0) {   // derived in momentum space; position space on request
-      lp->posReflectPending = true;
-      lp->entryKernel[id] = MUGIQ_HIP_ENTRY_KERNEL_REFLECTED;
-      return MUGIQ_HIP_SUCCESS;
-    }
-    long long bufOffset;
-    size_t bufByteSize;
-    if (id != -1) {  // :465-474
-      bufOffset = lp->nElemPosLocPerLoop * lp->nLoopOffset[id];
-      bufByteSize = cb * (size_t)lp->nElemPosLocPerLoop * lp->nLoopPerEntry[id];
-    } else {
-      bufOffset = 0;
-      bufByteSize = cb * (size_t)lp->nElemPosLocPerLoop;
-    }
-    void *slot0 = static_cast<char *>(lp->dataPos_d) + (size_t)bufOffset * cb;
-    // cudaMemset :476 -- needed where kernels accumulate into the slots: the ultra-local loop, the BASIC plan, and an OPT
-    // entry that falls back to the step-by-step sequence (length beyond the neighbour).  Reflected entries and the fused
-    // displaced contraction write every site of their slots (MUGIQ_HIP_REGION_OVERWRITE).
-    const bool stepByStep = id >= 0 && entry_stepwise(lp, id);
-    if (id == -1 || basic || (lp->derivedFrom[id] < 0 && stepByStep)) MUGIQ_CHECK_HIP(hipMemsetAsync(slot0, 0, bufByteSize, lp->stream));
-    const bool reflected = id >= 0 && !basic && lp->derivedFrom[id] >= 0;
-    const bool split = id >= 0 && !basic && !reflected && !stepByStep && lp->commDim[lp->dispDir[id]];  // entry_fused opens its own phases
-    const int ph = split ? -1
-                         : phase_begin(lp, id < 0 ? MUGIQ_HIP_PHASE_ULTRA_LOCAL
-                                                  : reflected ? MUGIQ_HIP_PHASE_ENTRY_REFLECTED
-                                                              : (basic || stepByStep) ? MUGIQ_HIP_PHASE_ENTRY_STEPWISE : MUGIQ_HIP_PHASE_ENTRY_FUSED,
-                                       id, lp->stream);
-    if (id == -1 && lp->coarseMode && !lp->fineStore) {
-      // MG ultra-local loop without materialising the fine vectors
-      st = mugiq_hip_prolongate_contract_batched(slot0, lp->loopPrecision, lp->coarseVecs.data(), lp->sigma.data(), lp->nEv,
-                                                 &lp->transfer, lp->stream);
-    } else if (id == -1) {
-      if (basic) {
-        for (int n = 0; n < lp->nEv && !st; n++)  // :501-502
-          st = mugiq_hip_perform_loop_contraction_batched_mixed(slot0, lp->loopPrecision, lp->left() + n, &lp->eVecs[n], &lp->sigma[n], 1,
-                                                                lp->stream);
-      } else {
-        st = mugiq_hip_perform_loop_contraction_batched_mixed(slot0, lp->loopPrecision, lp->left(), lp->eVecs.data(),
-                                                              lp->sigma.data(), lp->nEv, lp->stream);
-      }
-    } else {
-      if (basic) st = entry_basic(lp, id, slot0);
-      else if (lp->derivedFrom[id] >= 0) st = entry_reflected(lp, id, lp->derivedFrom[id], slot0);
-      else if (split && lp->halo[id].posted) {
-        st = entry_fused(lp, id, slot0, 1);  // interior tiles now; the boundary tiles once every entry's interior is through
-        pendingBoundary.push_back(id);
-      } else st = entry_fused(lp, id, slot0, 0, pack.data(), (int)pack.size(), packed);
-      // No host synchronisation between entries: every user of this entry's scratch is ordered on lp->stream (the halo
-      // stream's part was waited for by the boundary kernels), so the next entry may take the buffers over at once.
-      // The exception is the entry that runs BEFORE the halos are posted: the pack and halo streams start from an event
-      // recorded ahead of it, so a buffer it hands back could be given to prepare_halo as gsend / grecv and be written by the
-      // pack kernels while this entry's kernels still read it.  Its scratch stays out of the pool until the compute ends.
-      if (holdScratch) {
-        for (void *q : lp->scratch) lp->held.push_back(q);
-        lp->scratch.clear();
-      } else {
-        free_scratch(lp);
-      }
-    }
-    phase_end(lp, ph, lp->stream);
-    return st;
-  };
-  // the halos of the plan: link fields, packed face layers, one transfer group on the halo stream
-  int phPack = -1, phHalo = -1, maxBlocks = 0;
-  bool halosPrepared = false;
-  auto prepare_halos = [&]() -> int {
-    for (int id = 0; id < lp->nDispEntries; id++)
-      if (aheadFlags[id] && (st = prepare_halo(lp, id))) return st;
-    double haloBytes = 0;
-    for (int id = 0; id < lp->nDispEntries; id++)
-      if (lp->halo[id].posted) {
-        haloBytes += (double)halo_bytes(lp, id);
-        maxBlocks = std::max(maxBlocks, lp->halo[id].nBlocks);
-      }
-    // the pack stream starts where the halo stream starts (behind what the compute stream held when the compute began)
-    MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->packStream, lp->evPacked, 0));
-    phPack = phase_begin(lp, MUGIQ_HIP_PHASE_HALO_PREPARE, -1, lp->packStream, haloBytes);
-    phHalo = phase_begin(lp, MUGIQ_HIP_PHASE_HALO_TRANSFER, -1, lp->commStream, haloBytes);
-    halosPrepared = true;
-    return MUGIQ_HIP_SUCCESS;
-  };
-  auto send_halos = [&](int bFirst, int whichFirst) -> int {
-    for (int b = bFirst; b < maxBlocks; b++)
-      if ((st = send_halo_block(lp, b, grouped, b == bFirst ? whichFirst : -1))) return st;
-    phase_end(lp, phPack, lp->packStream);
-    phase_end(lp, phHalo, lp->commStream);
-    return MUGIQ_HIP_SUCCESS;
-  };
-  // Who packs?  Pack kernels beside a tile kernel that fills every CU's registers and LDS do not overlap with it, they take turns
-  // (configs[2] per-GPU job: 12.6 ms of packing made the first entry 10 ms longer).  Where the entry that runs first is a mu = x
-  // entry on the row tile of csrc/fused_mfma.hip and the partitioned axes are z / t, that entry writes the face layers itself -- every
-  // raw eigenvector passes through its registers anyway -- and the pack kernels read nothing a second time.  The first block of a
-  // halo that really travels still goes out ahead, packed by its own kernel: the link must not wait for the entry to end.
-  // MUGIQ_HIP_PACK_IN_ENTRY = 0: pack kernels for everything.
-  std::vector<EntryPackTarget> packTargets;
-  lp->halosPackedInEntry = 0;
-  if (postHalos && earlyEntry >= 0 && lp->dispDir[earlyEntry] == 0 && lp->loopPrecision == lp->precision && !lp->twoSided) {  // (two-sided: pack kernels)
-    std::vector<int> kv;
-    for (int k = lp->dispStart[earlyEntry]; k <= lp->dispStop[earlyEntry]; k++) kv.push_back(k);
-    const int room = entry_tile_allowed(lp, earlyEntry) ? entry_pack_capacity(lp->eVecs[0], kv.data(), (int)kv.size()) : 0;
-    if (room > 0 && !(st = prepare_halos())) {
-      for (int id = 0; id < lp->nDispEntries && (int)packTargets.size() < room; id++) {
-        MugiqHipLoop::HaloPost &h = lp->halo[id];
-        if (!h.posted || lp->dispDir[id] < 2) continue;
-        const int from = h.selfAlias ? 0 : h.blockN;  // (a halo that travels in ONE block is packed by its kernel, ahead of the entry)
-        if (from >= lp->nEv) continue;
-        h.entryPacksFrom = from;
-        packTargets.push_back(EntryPackTarget{h.gsend, lp->dispDir[id], lp->dispSign[id] == MUGIQ_HIP_DISP_SIGN_PLUS ? 0 : 1, lp->dispStop[id], from});
-      }
-      if (packTargets.empty()) {  // nothing for the entry to do: the order of round 3 (entry first, pack kernels in its shadow)
-        st = run_one(earlyEntry, true);
-        if (!st) st = send_halos(0, -1);
-      } else {
-        st = send_halo_block(lp, 0, grouped, 0);  // first blocks that are packed by their kernels: on their way before the entry starts
-        if (!st) {
-          bool taken = false;
-          st = run_one(earlyEntry, true, packTargets, &taken);
-          if (!st && taken) lp->halosPackedInEntry = (int)packTargets.size();
-          if (!st && !taken) st = set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "computeCoarseLoop: entry %d was to write the face layers of the posted halos and did not (internal)", earlyEntry);
-        }
-        if (!st) {
-          MUGIQ_CHECK_HIP(hipEventRecord(lp->evEntryPacked, lp->stream));
-          MUGIQ_CHECK_HIP(hipStreamWaitEvent(lp->packStream, lp->evEntryPacked, 0));
-          st = send_halo_block(lp, 0, grouped, 1);
-        }
-        if (!st) st = send_halos(1, -1);
-      }
-    }
-  }
-  if (!halosPrepared && !st) {
-    if (earlyEntry >= 0) st = run_one(earlyEntry, postHalos);
-    if (!st && postHalos) st = prepare_halos();
-    if (!st && postHalos) st = send_halos(0, -1);
-  }
-  for (int id : order) {
-    if (st) break;
-    if (id == earlyEntry) continue;
-    // reflected entries and the ultra-local loop come after the computed ones: the boundary tiles go before them (a reflected
-    // entry reads the complete slots of its source)
-    if (!pendingBoundary.empty() && (id < 0 || lp->derivedFrom[id] >= 0)) st = run_boundaries();
-    if (!st) st = run_one(id);
-  }
-  if (!st && !pendingBoundary.empty()) st = run_boundaries();
-  {
-    hipError_t e = hipStreamSynchronize(lp->stream);
-    if (!st && e != hipSuccess) st = set_error(MUGIQ_HIP_ERROR_HIP, "computeCoarseLoop: %s", hipGetErrorString(e));
-  }
-  // hand the buffers of the posted halos back (their transfers were waited for by the entries that used them; after an
-  // error drain the halo stream first)
-  if (!lp->held.empty()) {
-    if (st && lp->packStream) (void)hipStreamSynchronize(lp->packStream);
-    if (st && lp->commStream) (void)hipStreamSynchronize(lp->commStream);
-    for (void *p : lp->held)
-      for (auto &b : lp->pool)
-        if (b.ptr == p) b.inUse = false;
-    lp->held.clear();
-  }
-  if (st) return st;
-  lp->dataPosCopied = false;
-  if (lp->doMomProj && (st = momentum_projection(lp))) return st;  // :517-520
-  MUGIQ_CHECK_HIP(hipStreamSynchronize(lp->stream));
-  if (lp->profiling) {
-    if (lp->packStream) MUGIQ_CHECK_HIP(hipStreamSynchronize(lp->packStream));  // HALO_PREPARE's end event is recorded there
-    if (lp->commStream) MUGIQ_CHECK_HIP(hipStreamSynchronize(lp->commStream));
-    phases_resolve(lp);
-    phase_host(lp, MUGIQ_HIP_PHASE_TOTAL_WALL, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall0).count());
-  }
-  lp->computed = true;
-  return MUGIQ_HIP_SUCCESS;
+  ComputeState cs;
+  int st = prolong_inputs(lp);
+  if (st || (st = plan_compute(lp))) return st;
+  st = run_entries(lp, cs);
+  // the buffers of the posted halos go back (their transfers were waited for by the entries that used them; after an error drain the
+  // halo streams first)
+  if (st && !lp->held.empty() && lp->packStream) (void)hipStreamSynchronize(lp->packStream);
+  if (st && !lp->held.empty() && lp->commStream) (void)hipStreamSynchronize(lp->commStream);
+  release_buffers(lp, lp->held);
+  return st ? st : project_and_finish(lp, tWall0);
 }
 
 int mugiq_hip_loop_set_profiling(MugiqHipLoop *lp, int on) {
@@ -1658,7 +1407,7 @@ int mugiq_hip_loop_get_entry_kernel(const MugiqHipLoop *lp, int id) {
 
 int mugiq_hip_loop_entry_derived_from(const MugiqHipLoop *lp, int id) {
   if (!lp || id < 0 || id >= lp->nDispEntries) return -2;
-  return lp->derivedFrom[id];
+  return lp->plan.entry[id].derivedFrom;
 }
 
 const void *mugiq_hip_loop_data_pos_d(const MugiqHipLoop *lp) {
@@ -1737,7 +1486,7 @@ int mugiq_hip_loop_write_hdf5(MugiqHipLoop *lp) {
 
 int mugiq_hip_loop_destroy(MugiqHipLoop *lp) {  // freeDataMemory, lib/loop_mugiq.cpp:182-229
   if (!lp) return MUGIQ_HIP_SUCCESS;
-  destroy_pool(lp);
+  for (auto &b : lp->pool) (void)hipFree(b.ptr);
   if (lp->dataMom_bcast != lp->dataMom_h) free(lp->dataMom_bcast);
   if (lp->dataMom_h) (void)hipHostFree(lp->dataMom_h);
   if (lp->dataMom != lp->dataMom_h) free(lp->dataMom);
@@ -1747,8 +1496,6 @@ int mugiq_hip_loop_destroy(MugiqHipLoop *lp) {  // freeDataMemory, lib/loop_mugi
   for (void *q : lp->levelStore)
     if (q) (void)hipFree(q);
   for (auto &h : lp->halo) {
-    if (h.evPacked) (void)hipEventDestroy(h.evPacked);
-    if (h.evHalo) (void)hipEventDestroy(h.evHalo);
     for (hipEvent_t e : h.evPackedBlk) (void)hipEventDestroy(e);
     for (hipEvent_t e : h.evBlock) (void)hipEventDestroy(e);
   }

@@ -1,4 +1,4 @@
-"""Python face of the C++ driver (csrc/loop_driver.cpp): MugiqLoopParam + Loop_Mugiq of the reference
+"""Python face of the C++ driver (csrc/loop_driver.cpp, its plan: csrc/loop_plan.cpp): MugiqLoopParam + Loop_Mugiq of the reference
 (include/mugiq.h:28-47, include/loop_mugiq.h:123-134), same member names."""
 import ctypes
 from dataclasses import dataclass, field
@@ -128,6 +128,90 @@ def reflectMomentumSpace(dataMom_bcast, momMatrix, FTSign, totalL, nLoop, locT, 
     return a
 
 
+def _c_loop_param(loopParams, keep, gauge_desc=None):
+    """MugiqLoopParam -> MugiqHipLoopParam; what the pointers of the C struct refer to is appended to `keep`."""
+    p = _CLoopParam()
+    n_mom = int(loopParams.Nmom) if loopParams.Nmom else len(loopParams.momMatrix)
+    mom = np.ascontiguousarray(np.asarray(loopParams.momMatrix, dtype=np.int32).reshape(-1)) if n_mom else np.zeros(0, np.int32)
+    p.Nmom = n_mom
+    p.momMatrix = mom.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if n_mom else None
+    p.FTSign = int(loopParams.FTSign)
+    p.calcType = int(loopParams.calcType)
+    p.writeMomSpaceHDF5 = int(bool(loopParams.writeMomSpaceHDF5))
+    p.writePosSpaceHDF5 = int(bool(loopParams.writePosSpaceHDF5))
+    p.doMomProj = int(bool(loopParams.doMomProj))
+    p.doNonLocal = int(bool(loopParams.doNonLocal))
+    ne = len(loopParams.disp_str)
+    if not (ne == len(loopParams.disp_start) == len(loopParams.disp_stop)):
+        raise _lib.MugiqHipError("Displacement string length not compatible with displacement limits length")
+    p.nDispEntries = ne
+    ent = (ctypes.c_char_p * max(ne, 1))(*[(loopParams.disp_entry[i] if i < len(loopParams.disp_entry) else "").encode() for i in range(ne)])
+    dst = (ctypes.c_char_p * max(ne, 1))(*[s.encode() for s in loopParams.disp_str])
+    a = (ctypes.c_int * max(ne, 1))(*[int(x) for x in loopParams.disp_start])
+    b = (ctypes.c_int * max(ne, 1))(*[int(x) for x in loopParams.disp_stop])
+    p.disp_entry, p.disp_str, p.disp_start, p.disp_stop = ent, dst, a, b
+    p.fname_mom_h5 = loopParams.fname_mom_h5.encode()
+    p.fname_pos_h5 = loopParams.fname_pos_h5.encode()
+    if gauge_desc is None and loopParams.gauge is not None:
+        gauge_desc = loopParams.gauge.desc()
+        keep.append(loopParams.gauge)
+    if gauge_desc is not None:
+        p.gauge = ctypes.pointer(gauge_desc)
+    p.loopPrecision = int(loopParams.loopPrecision)
+    keep += [mom, ent, dst, a, b, gauge_desc]
+    return p
+
+
+def loopPlan(loopParams, eVec, nEv, comm=None, twoSided=False, coarseMode=False, axialOk=(1, 1, 1, 1), deviceBytes=0, gauge=None):
+    """What computeCoarseLoop would do with every displacement entry (mugiq_hip_loop_plan): the plan the driver itself makes, as dicts.
+    Host only, no GPU is touched, so descriptors will do: eVec a SpinorField or (X, precision, order[, pad]); gauge (default
+    loopParams.gauge) a GaugeField or (precision, R); comm a GridComm / RcclComm or {"grid", "partitioned", "group"} (group: the
+    transport has group_begin / group_end).  axialOk: the outcome of the unitarity pre-pass per direction; deviceBytes: the device's
+    total memory."""
+    keep = []
+    if isinstance(eVec, SpinorField):
+        ev = eVec.desc()
+    else:
+        X, prec, order = eVec[:3]
+        ev = _lib.SpinorDesc()
+        ev.precision, ev.field_order, ev.nParity = int(prec), int(order), 2
+        ev.volumeCB = int(np.prod(X)) // 2
+        ev.stride = ev.volumeCB + (int(eVec[3]) if len(eVec) > 3 else 0)
+        ev.parity_offset = 12 * ev.stride
+        for d in range(4):
+            ev.X[d] = int(X[d])
+    gauge = loopParams.gauge if gauge is None else gauge
+    g = None
+    if gauge is not None and not isinstance(gauge, GaugeField):
+        g = _lib.GaugeDesc()
+        g.precision = int(gauge[0])
+        for d in range(4):
+            g.X[d], g.R[d] = ev.X[d], int(gauge[1][d])
+    elif gauge is not None:
+        g = gauge.desc()
+    if isinstance(comm, dict):
+        from .comm import _CCommRaw
+        c = _CCommRaw()
+        c.size = int(np.prod(comm["grid"]))
+        for d in range(4):
+            c.grid[d] = int(comm["grid"][d])
+            c.partitioned[d] = int(comm.get("partitioned", (0, 0, 0, 0))[d])
+        c.group_begin = c.group_end = 1 if comm.get("group") else None     # (never called: only looked at)
+    else:
+        c = comm.c_struct() if comm is not None else None
+    p = _c_loop_param(loopParams, keep, g)
+    out = _lib.LoopPlan()
+    _lib.check(_lib.load().mugiq_hip_loop_plan(ctypes.byref(p), ctypes.byref(ev), int(nEv), int(bool(twoSided)), int(bool(coarseMode)),
+                                               ctypes.byref(c) if c is not None else None, _lib.int4(axialOk), int(deviceBytes),
+                                               ctypes.byref(out)))
+    entries = [{n: getattr(out.entry[i], n) for n, _ in _lib.LoopEntryPlan._fields_} for i in range(out.nEntries)]
+    for e in entries:
+        e["kv"] = list(range(e["kStart"], e["kStart"] + e["nK"]))
+    return {"entries": entries, "order": list(out.order[:out.nOrder]), "earlyEntry": out.earlyEntry, "carryUltra": out.carryUltra,
+            "momReflect": out.momReflect, "grouped": out.grouped, "entryPacksFrom": list(out.packTargets[:out.nPackTargets]),
+            "reserve": list(out.reserve[:out.nReserve])}
+
+
 class Loop_Mugiq:
     """Loop_Mugiq<Float, order>(loopParams, eigsolve): Float/order come from the eigenvector fields;
     `eVecs` / `eVals_sigma` are what the reference reads out of Eigsolve_Mugiq (lib/loop_mugiq.cpp:442,479)."""
@@ -148,35 +232,7 @@ class Loop_Mugiq:
         lib = _lib.load()
         self._keep = []
         self._params, self._transfer = loopParams, transfer
-        p = _CLoopParam()
-        n_mom = int(loopParams.Nmom) if loopParams.Nmom else len(loopParams.momMatrix)
-        mom = np.ascontiguousarray(np.asarray(loopParams.momMatrix, dtype=np.int32).reshape(-1)) if n_mom else np.zeros(0, np.int32)
-        self._keep.append(mom)
-        p.Nmom = n_mom
-        p.momMatrix = mom.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if n_mom else None
-        p.FTSign = int(loopParams.FTSign)
-        p.calcType = int(loopParams.calcType)
-        p.writeMomSpaceHDF5 = int(bool(loopParams.writeMomSpaceHDF5))
-        p.writePosSpaceHDF5 = int(bool(loopParams.writePosSpaceHDF5))
-        p.doMomProj = int(bool(loopParams.doMomProj))
-        p.doNonLocal = int(bool(loopParams.doNonLocal))
-        ne = len(loopParams.disp_str)
-        if not (ne == len(loopParams.disp_start) == len(loopParams.disp_stop)):
-            raise _lib.MugiqHipError("Displacement string length not compatible with displacement limits length")
-        p.nDispEntries = ne
-        ent = (ctypes.c_char_p * max(ne, 1))(*[(loopParams.disp_entry[i] if i < len(loopParams.disp_entry) else "").encode() for i in range(ne)])
-        dst = (ctypes.c_char_p * max(ne, 1))(*[s.encode() for s in loopParams.disp_str])
-        a = (ctypes.c_int * max(ne, 1))(*[int(x) for x in loopParams.disp_start])
-        b = (ctypes.c_int * max(ne, 1))(*[int(x) for x in loopParams.disp_stop])
-        self._keep += [ent, dst, a, b]
-        p.disp_entry, p.disp_str, p.disp_start, p.disp_stop = ent, dst, a, b
-        p.fname_mom_h5 = loopParams.fname_mom_h5.encode()
-        p.fname_pos_h5 = loopParams.fname_pos_h5.encode()
-        if loopParams.gauge is not None:
-            g = loopParams.gauge.desc()
-            self._keep += [g, loopParams.gauge]
-            p.gauge = ctypes.pointer(g)
-        p.loopPrecision = int(loopParams.loopPrecision)
+        p = _c_loop_param(loopParams, self._keep)
         self.eVecs = list(eVecs)
         sg = (ctypes.c_double * len(self.eVecs))(*[float(s) for s in eVals_sigma])
         self.comm = comm

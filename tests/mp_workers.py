@@ -390,3 +390,59 @@ def native_rccl_worker(rank, world, port):
     pos2, mom2, _ = run(g_grid, grid)
     assert torch.equal(pos2, pos), "loops differ between the native and the torch transport"
     native.close()
+
+
+def plan_worker(rank, world, port, G, case, alloc_first, alloc_second):
+    """One rank, z and t partitioned with the rank as its own neighbour, the entries of gpu_worker's `case`: what loopPlan says before
+    the compute is what computeCoarseLoop then does (tests/test_gpu_loop_plan.py), and the scratch it allocates inside the first and
+    the second compute is the given list of byte counts."""
+    import torch
+    from util import orc, momenta_p2_le, rel_err
+    dist = _init(rank, world, port)
+    torch.cuda.set_device(0)
+    import mugiq_amd as hip
+    nev, force, prec = 4, (0, 0, 1, 1), 8
+    disp = {"pack": (["+x", "+t", "-z", "+z", "-t", "+y"], [1, 1, 1, 2, 2, 1], [2, 3, 2, 3, 4, 1]),
+            "pool_tie": (["+x", "+t", "-z", "+y", "-t"], [1, 1, 1, 2, 2], [3, 2, 2, 2, 2])}[case]
+    moms = momenta_p2_le(2)
+    ev_lex, U_lex, sg = _global_problem(G, nev, 1234)
+    cprm, pos_g, mom_g = _single_domain_reference(orc, G, ev_lex, U_lex, sg, disp, moms, 1)
+    comm = hip.GridComm((1, 1, 1, 1), device="cuda:0", force_partitioned=force)
+    brd = [2 * f for f in force]
+    U_loc = np.stack([orc.lex_to_eo(U_lex[mu], G) for mu in range(4)])
+    gauge = hip.GaugeField(G, brd, prec).set_from_qdp_host(orc.gauge_to_qdp_host(U_loc), comm)
+    f = [hip.SpinorField(G, prec, 2).set_logical(orc.lex_to_eo(v, G)) for v in ev_lex]
+    prm = hip.MugiqLoopParam(Nmom=len(moms), momMatrix=[list(m) for m in moms], FTSign=1, calcType=hip.LOOP_CALC_TYPE_OPT_KERNEL,
+                             doMomProj=True, doNonLocal=True, disp_entry=[], disp_str=disp[0], disp_start=disp[1], disp_stop=disp[2],
+                             gauge=gauge)
+    # the real inputs of the driver's own plan: a random SU(3) gauge passes the pre-pass along every direction
+    plan = hip.loopPlan(prm, f[0], nev, comm=comm, axialOk=(1, 1, 1, 1), deviceBytes=torch.cuda.mem_get_info(0)[1])
+    loop = hip.Loop_Mugiq(prm, f, sg, comm).setProfiling()
+    loop.computeCoarseLoop()
+    phases = loop.phases()
+    print("plan", plan, "\nscratch_alloc (first)", [int(p["bytes"]) for p in phases if p["kind"] == "scratch_alloc"], flush=True)
+    E, n = plan["entries"], len(disp[0])
+    assert [loop.derivedFrom(i) for i in range(n)] == [e["derivedFrom"] for e in E]
+    tiles = (hip.ENTRY_KERNEL_MFMA_ROW, hip.ENTRY_KERNEL_MFMA_COLUMN)
+    for i, e in enumerate(E):
+        want = {0: (hip.ENTRY_KERNEL_REFLECTED,), 1: (hip.ENTRY_KERNEL_STEPWISE,),
+                2: tiles if e["tile"] and e["gaugeBytes"] > 0 else (hip.ENTRY_KERNEL_VECTOR_TILE, hip.ENTRY_KERNEL_STREAMING)}[e["route"]]
+        assert loop.entryKernel(i) in want, (i, loop.entryKernel(i), e)
+    assert loop.halosPackedInEntry() == len(plan["entryPacksFrom"])
+    assert {p["entry"] for p in phases if p["kind"] == "entry_interior"} == {i for i, e in enumerate(E) if e["route"] == 2 and e["part"]}
+    _check_pos(orc, comm.coord, (1, 1, 1, 1), G, G, cprm, loop.dataPos_d.cpu().numpy().astype(np.complex128), pos_g, 1e-12)
+    e = rel_err(loop.dataMom_global(), mom_g)
+    assert e < 1e-12, ("dataMom", e)
+    assert [int(p["bytes"]) for p in phases if p["kind"] == "scratch_alloc"] == alloc_first
+    # a second compute on the same object: its position-space part runs (the projection is refused: not more than once)
+    try:
+        loop.computeCoarseLoop()
+        raise AssertionError("the second momentum projection was not refused")
+    except hip.MugiqHipError as err:
+        assert "more than once" in str(err), err
+    second = [int(p["bytes"]) for p in loop.phases() if p["kind"] == "scratch_alloc"]
+    print("scratch_alloc (second)", second, flush=True)
+    assert second == alloc_second
+    loop.close()
+    dist.barrier()
+    dist.destroy_process_group()
