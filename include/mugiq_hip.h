@@ -761,6 +761,7 @@ typedef struct MugiqHipLoopEntryPlan_s {
   int nBlocks, blockN;     /* the blocks of eigenvectors it is processed (ahead: its halo travels) in */
   int needsMemset;         /* its slots are accumulated into */
   int entryPacksFrom;      /* >= 0: the entry that runs first writes its face layers from this eigenvector on; -1: pack kernels */
+  int kernel;              /* MUGIQ_HIP_ENTRY_KERNEL_* that mugiq_hip_loop_get_entry_kernel reports after the compute */
   long long faceBytes, haloBytes, perVecHaloBytes, gaugeBytes;
 } MugiqHipLoopEntryPlan;
 typedef struct MugiqHipLoopPlan_s {
@@ -774,6 +775,30 @@ typedef struct MugiqHipLoopPlan_s {
 } MugiqHipLoopPlan;
 int mugiq_hip_loop_plan(const MugiqHipLoopParam *param, const MugiqHipSpinorField *eVec, int nEv, int twoSided, int coarseMode,
                         const MugiqHipComm *comm, const int axialOk[4], size_t deviceBytes, MugiqHipLoopPlan *out);
+/* The kernel form of one fused displaced entry (new; host only): what mugiq_hip_displaced_loop_contraction_fused* and the loop driver
+ * select for it (csrc/fused_form.cpp, the one place that decides), under the same environment switches, and the geometry of its first
+ * launch.  ev: the geometry, precision and order of the eigenvectors (no data pointer is read); partitioned: along dispDir;
+ * gaugeGiven: the caller holds the axial gauge (the driver: always); loopPrecision 0: that of ev. */
+#define MUGIQ_HIP_FUSED_FAMILY_NONE 0        /* two-sided and no matrix-pipe tile: the step-by-step sequence */
+#define MUGIQ_HIP_FUSED_FAMILY_MFMA_COLUMN 1 /* matrix-pipe column tile */
+#define MUGIQ_HIP_FUSED_FAMILY_MFMA_ROW 2    /* matrix-pipe row tile */
+#define MUGIQ_HIP_FUSED_FAMILY_TILE32 3      /* 32-line vector tile (csrc/fused_tile.hip) */
+#define MUGIQ_HIP_FUSED_FAMILY_TILE16 4      /* 16-line vector tile (csrc/fused_tile16.hip) */
+#define MUGIQ_HIP_FUSED_FAMILY_STREAMING 5   /* streaming kernel (csrc/fused.hip) */
+typedef struct MugiqHipFusedForm_s {
+  int kernel, family;               /* MUGIQ_HIP_ENTRY_KERNEL_*, MUGIQ_HIP_FUSED_FAMILY_* */
+  int slotsPerLaunch, packCapacity; /* displaced slots per launch at most; face-layer targets a mu = x entry can write on its way */
+  long long gaugeBytes;             /* its axial gauge (0: no matrix-pipe tile) */
+  /* the first launch: its slots, its longest length, and per family (0 where it does not apply) */
+  int nSlots, kmax, waves, staged;  /* staged: positions along mu held in LDS */
+  int tj, lines;                    /* positions along mu and lines per tile */
+  int rowGroups, rows, rowChunk, leftBufElems; /* matrix-pipe: row tile geometry; two-sided left image */
+  int ph, glds;                     /* vector tiles: staged global -> LDS; 32-line: bound of positions staged per lane */
+  int npc, np, m, phl;              /* 16-line: computed / staged positions, pieces per parity, bound of staging loads per lane */
+  long long ldsBytes;
+} MugiqHipFusedForm;
+int mugiq_hip_fused_form(const MugiqHipSpinorField *ev, int twoSided, int dispDir, const int *kValues, int nK, int partitioned,
+                         int gaugeGiven, int loopPrecision, MugiqHipFusedForm *out);
 /* Phase timing of a compute (measurement aid; off by default).  When switched on, mugiq_hip_loop_compute brackets each
  * phase with a pair of HIP events on the stream the phase runs on and, after its final synchronisation, reports the
  * device time between them.  Phases of different streams overlap in time (that is the point of the halo stream). */

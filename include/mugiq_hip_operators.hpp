@@ -578,6 +578,14 @@ public:
   const std::complex<Float> *dataMom_bcast() const { return static_cast<const std::complex<Float> *>(mugiq_hip_loop_data_mom_bcast_h(h_)); }
 };
 
+// The kernel form a fused displaced entry runs on, and the geometry of its first launch (mugiq_hip_fused_form; host only)
+inline MugiqHipFusedForm fusedForm(const ColorSpinorField &ev, int dispDir, const std::vector<int> &kValues, bool twoSided = false,
+                                   bool partitioned = false, bool gaugeGiven = true, int loopPrecision = 0) {
+  MugiqHipFusedForm out;
+  check(mugiq_hip_fused_form(&ev, twoSided, dispDir, kValues.data(), (int)kValues.size(), partitioned, gaugeGiven, loopPrecision, &out));
+  return out;
+}
+
 // lib/interface_mugiq.cpp:158-172: computeLoop<Float,fieldOrder>(loopParams, eigsolve)
 template <typename Float, int fieldOrder>
 inline void computeLoop(MugiqLoopParam loopParams, const std::vector<ColorSpinorField> &eVecs, const std::vector<double> &eVals_sigma,

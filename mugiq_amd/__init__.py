@@ -20,8 +20,9 @@ from .operators import (  # noqa: E402
 )
 from ._lib import MugiqHipError, LIB_PATH  # noqa: E402
 from .loop import (  # noqa: E402
-    MugiqLoopParam, Loop_Mugiq, loopPlan, parseDisplaceEntryString, parseDisplacement, read_momenta_file, writeLoopsHDF5_Mom, reflectMomentumSpace,
+    MugiqLoopParam, Loop_Mugiq, loopPlan, fusedForm, parseDisplaceEntryString, parseDisplacement, read_momenta_file, writeLoopsHDF5_Mom, reflectMomentumSpace,
     LOOP_CALC_TYPE_BLAS, LOOP_CALC_TYPE_OPT_KERNEL, LOOP_CALC_TYPE_BASIC_KERNEL,
+    FUSED_FAMILY_NONE, FUSED_FAMILY_MFMA_COLUMN, FUSED_FAMILY_MFMA_ROW, FUSED_FAMILY_TILE32, FUSED_FAMILY_TILE16, FUSED_FAMILY_STREAMING,
 )
 from .comm import GridComm, RcclComm  # noqa: E402
 from .displace import Displace, DISPLACE_TYPE_COVARIANT  # noqa: E402

@@ -72,8 +72,16 @@ LOOP_PLAN_MAX_ENTRIES, LOOP_PLAN_MAX_BUFFERS = 64, 512
 class LoopEntryPlan(ctypes.Structure):
     """MugiqHipLoopEntryPlan (include/mugiq_hip.h)."""
     _fields_ = [(n, ctypes.c_int) for n in ("derivedFrom", "route", "part", "high", "kStart", "nK", "tile", "gaugeFromField", "nLinkFields",
-                                            "buildGaugeFromLinks", "ahead", "selfAlias", "nBlocks", "blockN", "needsMemset", "entryPacksFrom")] + \
+                                            "buildGaugeFromLinks", "ahead", "selfAlias", "nBlocks", "blockN", "needsMemset", "entryPacksFrom",
+                                            "kernel")] + \
                [(n, ctypes.c_longlong) for n in ("faceBytes", "haloBytes", "perVecHaloBytes", "gaugeBytes")]
+
+
+class FusedForm(ctypes.Structure):
+    """MugiqHipFusedForm (include/mugiq_hip.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("kernel", "family", "slotsPerLaunch", "packCapacity")] + [("gaugeBytes", ctypes.c_longlong)] + \
+               [(n, ctypes.c_int) for n in ("nSlots", "kmax", "waves", "staged", "tj", "lines", "rowGroups", "rows", "rowChunk", "leftBufElems",
+                                            "ph", "glds", "npc", "np", "m", "phl")] + [("ldsBytes", ctypes.c_longlong)]
 
 
 class LoopPlan(ctypes.Structure):
@@ -198,6 +206,8 @@ SIGNATURES = {
     "mugiq_hip_loop_create_two_sided": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _VP, _SP, _SP, ctypes.POINTER(ctypes.c_double),
                                                        ctypes.c_int, _VP, _VP]),
     "mugiq_hip_loop_compute": (ctypes.c_int, [_VP]),
+    "mugiq_hip_fused_form": (ctypes.c_int, [_SP, ctypes.c_int, ctypes.c_int, _I4, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(FusedForm)]),
     "mugiq_hip_loop_plan": (ctypes.c_int, [_VP, _SP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _I4, ctypes.c_size_t, ctypes.POINTER(LoopPlan)]),
     "mugiq_hip_loop_deflate": (ctypes.c_int, [_VP, _SP, _SP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "mugiq_hip_loop_get_info": (ctypes.c_int, [_VP, _VP]),

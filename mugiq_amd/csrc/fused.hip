@@ -16,12 +16,9 @@
 // entry and eigenvector block (pack_layers_kernel), instead of one exchange per step.
 #include "internal.h"
 
-#include <cstdlib>
 #include <vector>
 
 namespace mugiq {
-
-constexpr int kFusedMaxSlots = 4;
 
 // F = storage type of eigenvectors / links, A = arithmetic and loop-buffer type (F, or double over float storage)
 template <typename F, typename A> struct FusedArgs {
@@ -227,11 +224,11 @@ __global__ __launch_bounds__(256) void pack_layers_kernel(PackLayersArgs<F> g) {
 }
 
 template <typename F, typename A, int ORDER>
-static int launch_fused(FusedArgs<F, A> a, int dir, int sign, hipStream_t stream) {
+static int launch_fused(FusedArgs<F, A> a, int dir, int sign, const FusedSwitches &sw, hipStream_t stream) {
   const int V = 2 * a.volumeCB;
   const dim3 grid((V + 63) / 64), block(64, a.nslot);
-  int nt = 1, swz = 1, remap = 1;  // MUGIQ_HIP_FUSED_TUNE = "nt,swizzle,remap" overrides (profiles/r01_fused_tune.txt)
-  if (const char *e = getenv("MUGIQ_HIP_FUSED_TUNE")) sscanf(e, "%d,%d,%d", &nt, &swz, &remap);
+  int nt = sw.tuneNt;
+  const int swz = sw.tuneSwizzle, remap = sw.tuneRemap;
   a.xcdSwizzle = (swz && grid.x % 8 == 0) ? 1 : 0;
   long long strideMu = 1;
   for (int d = 0; d < dir; d++) strideMu *= a.X[d];
@@ -258,83 +255,64 @@ static int launch_fused(FusedArgs<F, A> a, int dir, int sign, hipStream_t stream
   return MUGIQ_HIP_SUCCESS;
 }
 
-// third-generation (16-line tiles, two items per wave), csrc/fused_tile16.hip
-bool tile16_applicable(const MugiqHipSpinorField &ev, int dir, int kmax, int precision, int partitioned, bool secondGenerationApplies);
+// the vector tiles of an entry whose form is one: 16-line (csrc/fused_tile16.hip) and 32-line (csrc/fused_tile.hip)
 template <typename F, typename A, int ORDER>
-int tile16_entry(void *loop_d, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d, const int *kvals,
-                 int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers, int region, hipStream_t stream);
-// second-generation (LDS-tiled) kernel, csrc/fused_tile.hip
-bool tile_applicable(const MugiqHipSpinorField &ev, int dir, int kmax, int precision, int partitioned);
+int tile16_entry(const FusedForm &form, void *loop_d, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
+                 const int *kvals, int nK, int sign, const void *ghost_d, int layers, int region, hipStream_t stream);
 template <typename F, typename A, int ORDER>
-int tile_entry(void *loop_d, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d, const int *kvals,
-               int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers, int region, hipStream_t stream,
-               void *ultra_d, int *carried);
+int tile_entry(const FusedForm &form, void *loop_d, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
+               const int *kvals, int nK, int sign, const void *ghost_d, int layers, int region, hipStream_t stream, void *ultra_d, int *carried);
+// (the matrix-pipe tile of csrc/fused_mfma.hip: internal.h)
 
-// (fourth generation, the matrix-pipe tile of csrc/fused_mfma.hip: internal.h)
-
+// Dispatches on the form select_fused_form (csrc/fused_form.cpp) chose, or the driver's plan chose with it
 template <typename F, typename A, int ORDER>
 static int fused_entry(void *loop_d, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
                        const int *kvals, int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers,
                        int region, hipStream_t stream, void *ultra_d, int *carried, const MugiqHipSpinorField *evL, int *kernel,
-                       const FusedEntryPlan *plan) {
+                       const FusedEntryPlan *plan, const FusedSwitches &sw) {
   if (carried) *carried = 0;
-  {
-    const FusedEntryPlan p = plan ? *plan : FusedEntryPlan{};
-    int kmax = 0;
-    for (int i = 0; i < nK; i++) kmax = kvals[i] > kmax ? kvals[i] : kmax;
-    // (every storage type: the tile converts on the way into LDS and works in double; float slots are rounded once, on the way out)
-    const void *gauge = p.axialGauge;
-    bool tile = p.tile != 0 && mfma_tile_applicable(ev[0], dir, kvals, nK, partitioned, gauge != nullptr, evL != nullptr);
-    // a call with the caller's gauge may come without link fields: no other kernel may take it (the driver decides before it builds one)
-    if (gauge && !tile)
-      return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "fused contraction: an axial gauge was built for direction %d, but the "
-                       "matrix-pipe tile does not take the entry (internal)", dir);
-    if (tile && p.tile < 0 && !gauge) {  // free call: the tile only where the gauge of these links is unitary (and then on that gauge)
-      void *checkedGauge = nullptr;
-      double dev = 0.0;
-      if (int st = build_axial_gauge_checked(&checkedGauge, &dev, ev[0], E_d, kmax, dir, sign, stream)) return st;
-      tile = dev <= axial_gauge_tolerance(ev[0].precision);
-      gauge = checkedGauge;
-    }
-    if (tile) {
-      *kernel = dir == 0 ? MUGIQ_HIP_ENTRY_KERNEL_MFMA_ROW : MUGIQ_HIP_ENTRY_KERNEL_MFMA_COLUMN;
-      return mfma_tile_entry(loop_d, (int)sizeof(A), ev, sigma, nVec, E_d, kvals, nK, dir, sign, partitioned, ghost_d, layers, region, stream,
-                             ultra_d, carried, evL, gauge, p.pack, p.nPack, p.packed);
-    }
-    if (evL)  // (no two-sided form of the vector tiles or of the streaming kernel)
-      return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "mugiq_hip_displaced_loop_contraction_fused_two_sided: the matrix-pipe tile does not take this entry "
-                       "(direction %d, lengths %d .. %d, partitioned %d, precision %d, order %d, or links that are not unitary): use the step-by-step "
-                       "sequence", dir, kvals[0], kvals[nK - 1], partitioned, ev[0].precision, ev[0].field_order);
-    *kernel = MUGIQ_HIP_ENTRY_KERNEL_VECTOR_TILE;
-    const bool gen2 = tile_applicable(ev[0], dir, kmax, ev[0].precision, partitioned);
-    if (tile16_applicable(ev[0], dir, kmax, ev[0].precision, partitioned, gen2))
-      return tile16_entry<F, A, ORDER>(loop_d, ev, sigma, nVec, E_d, kvals, nK, dir, sign, partitioned, ghost_d, layers, region, stream);
-    if (gen2)
-      return tile_entry<F, A, ORDER>(loop_d, ev, sigma, nVec, E_d, kvals, nK, dir, sign, partitioned, ghost_d, layers, region, stream, ultra_d, carried);
+  const FusedEntryPlan p = plan ? *plan : FusedEntryPlan{};
+  const void *gauge = p.axialGauge;
+  auto select = [&](bool allowMatrixPipe) {
+    return select_fused_form(ev[0], dir, kvals, nK, partitioned, gauge != nullptr, evL != nullptr, (int)sizeof(A), sw, allowMatrixPipe);
+  };
+  FusedForm form = p.form ? *p.form : select(p.tile != 0);
+  // a call with the caller's gauge may come without link fields: no other kernel may take it (the driver decides before it builds one)
+  if (gauge && !fused_form_is_mfma(form))
+    return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "fused contraction: an axial gauge was built for direction %d, but the "
+                     "matrix-pipe tile does not take the entry (internal)", dir);
+  if (fused_form_is_mfma(form) && p.tile < 0 && !gauge) {  // free call: the tile only where the gauge of these links is unitary (and then on that gauge)
+    void *checkedGauge = nullptr;
+    double dev = 0.0;
+    if (int st = build_axial_gauge_checked(&checkedGauge, &dev, ev[0], E_d, form.kmax, dir, sign, stream)) return st;
+    if (dev > axial_gauge_tolerance(ev[0].precision)) form = select(false);
+    gauge = checkedGauge;
   }
-  *kernel = MUGIQ_HIP_ENTRY_KERNEL_STREAMING;
+  if (form.family == MUGIQ_HIP_FUSED_FAMILY_NONE)  // (no two-sided form of the vector tiles or of the streaming kernel)
+    return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "mugiq_hip_displaced_loop_contraction_fused_two_sided: the matrix-pipe tile does not take this entry "
+                     "(direction %d, lengths %d .. %d, partitioned %d, precision %d, order %d, or links that are not unitary): use the step-by-step "
+                     "sequence", dir, kvals[0], kvals[nK - 1], partitioned, ev[0].precision, ev[0].field_order);
+  *kernel = form.kernel;
+  // (the matrix-pipe tile takes every storage type: it converts on the way into LDS and works in double; float slots are rounded once, on the way out)
+  if (fused_form_is_mfma(form))
+    return mfma_tile_entry(form, loop_d, ev, sigma, nVec, E_d, kvals, nK, sign, ghost_d, layers, region, stream, ultra_d, carried, evL, gauge,
+                           p.pack, p.nPack, p.packed);
+  if (form.family == MUGIQ_HIP_FUSED_FAMILY_TILE16)
+    return tile16_entry<F, A, ORDER>(form, loop_d, ev, sigma, nVec, E_d, kvals, nK, sign, ghost_d, layers, region, stream);
+  if (form.family == MUGIQ_HIP_FUSED_FAMILY_TILE32)
+    return tile_entry<F, A, ORDER>(form, loop_d, ev, sigma, nVec, E_d, kvals, nK, sign, ghost_d, layers, region, stream, ultra_d, carried);
   // the streaming kernel has no interior / boundary split: when the dimension is partitioned it counts as boundary
   const int overwrite = (region & MUGIQ_HIP_REGION_OVERWRITE) ? 1 : 0;
   region &= 0xff;
   if (region == MUGIQ_HIP_REGION_INTERIOR && partitioned) return MUGIQ_HIP_SUCCESS;
   if (region == MUGIQ_HIP_REGION_BOUNDARY && !partitioned) return MUGIQ_HIP_SUCCESS;
-  const size_t ptr_bytes = sizeof(void *) * (size_t)nVec;
-  std::vector<unsigned char> host(ptr_bytes + sizeof(A) * (size_t)nVec);
-  const void **hl = reinterpret_cast<const void **>(host.data());
-  A *hs = reinterpret_cast<A *>(host.data() + ptr_bytes);
-  for (int n = 0; n < nVec; n++) {
-    hl[n] = ev[n].data;
-    const F sg = static_cast<F>(sigma[n]);
-    hs[n] = static_cast<A>(1.0 / sg);
-  }
-  void *dev = nullptr;
-  int st = upload_table(&dev, host.data(), host.size(), stream);
-  if (st) return st;
   FusedArgs<F, A> a;
+  const void *invSigma = nullptr;
+  int st = upload_vector_table(&a.L, &invSigma, ev, nullptr, sigma, nVec, (int)sizeof(F), (int)sizeof(A), stream);
+  if (st) return st;
   a.slot_stride = (int64_t)16 * 2 * ev[0].volumeCB;
   a.overwrite = overwrite;
-  a.L = reinterpret_cast<const void *const *>(dev);
-  a.inv_sigma = reinterpret_cast<const A *>(static_cast<unsigned char *>(dev) + ptr_bytes);
+  a.inv_sigma = static_cast<const A *>(invSigma);
   a.nVec = nVec;
   for (int d = 0; d < 4; d++) a.X[d] = ev[0].X[d];
   a.volumeCB = ev[0].volumeCB;
@@ -342,8 +320,9 @@ static int fused_entry(void *loop_d, const MugiqHipSpinorField *ev, const double
   a.parity_offset = ev[0].parity_offset;
   a.partitioned = partitioned;
   a.ghost = static_cast<const F *>(ghost_d);
-  a.faceCB = ev[0].volumeCB / ev[0].X[dir];
-  a.ghost_vec_stride = (int64_t)layers * 24 * a.faceCB;
+  const LineGeometry lines = line_geometry(ev[0], dir, layers);
+  a.faceCB = lines.faceCB;
+  a.ghost_vec_stride = lines.ghost_vec_stride;
   for (int k0 = 0; k0 < nK; k0 += kFusedMaxSlots) {
     a.nslot = (nK - k0 < kFusedMaxSlots) ? nK - k0 : kFusedMaxSlots;
     a.loop = static_cast<Cplx<A> *>(loop_d) + (int64_t)k0 * a.slot_stride;
@@ -351,7 +330,7 @@ static int fused_entry(void *loop_d, const MugiqHipSpinorField *ev, const double
       a.E[s] = static_cast<const F *>(E_d[k0 + (s < a.nslot ? s : 0)]);
       a.k[s] = kvals[k0 + (s < a.nslot ? s : 0)];
     }
-    st = launch_fused<F, A, ORDER>(a, dir, sign, stream);
+    st = launch_fused<F, A, ORDER>(a, dir, sign, form.sw, stream);
     if (st) return st;
   }
   return MUGIQ_HIP_SUCCESS;
@@ -451,12 +430,13 @@ int mugiq::fused_contraction(void *loopData_d, int loopPrecision, const MugiqHip
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int p = eVecs_h[0].precision, o = eVecs_h[0].field_order;
+  const FusedSwitches sw = fused_switches_from_env();  // (once per public call; the driver's plan carries its own in plan->form)
   if (loopPrecision == 0) loopPrecision = p;
   MUGIQ_REQUIRE(loopPrecision == p || (loopPrecision == 8 && p == 4),
                 "%s: loop precision %d with field precision %d is not supported", who, loopPrecision, p);
 #define MUGIQ_FUSED_GO(F, A, O)                                                                                                 \
   return fused_entry<F, A, O>(loopData_d, eVecs_h, sigma_h, nVec, pathLinkFields_h, kValues_h, nK, dispDir, dispSign, part,   \
-                              ghostLayers_d, layers, region, s, ultraLocalSlot_d, carried, eVecL_h, kernel, plan)
+                              ghostLayers_d, layers, region, s, ultraLocalSlot_d, carried, eVecL_h, kernel, plan, sw)
   if (p == 8 && o == 2) MUGIQ_FUSED_GO(double, double, 2);
   if (p == 8 && o == 4) MUGIQ_FUSED_GO(double, double, 4);
   if (loopPrecision == 8 && o == 2) MUGIQ_FUSED_GO(float, double, 2);

@@ -31,7 +31,6 @@
 #include "fused_mfma_kernel.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 #include <vector>
@@ -227,113 +226,17 @@ template <typename F> __global__ __launch_bounds__(64) void axial_gauge_from_lin
   }
 }
 
-// The tile geometry for an entry: the first TJ of {8, 12, 4} that divides the extent and keeps TJ + Kmax within the staged
-// positions of its line count (MUGIQ_HIP_MFMA_TJ = 4 | 8 | 12 fixes it); 0 = none.
-// (two-sided: 8 or 4 only -- a 12-position left image next to the right one exceeds the LDS of a workgroup)
-static int mfma_tile_tj(int extent, int kmax, int nSlots = kMT_MaxSlots, bool partitioned = true, bool reduced = false, bool two = false) {
-  int want = 0;
-  if (const char *e = getenv("MUGIQ_HIP_MFMA_TJ")) want = atoi(e);
-  // 12 x 16 sites (1 + K/12 units staged per site) where it keeps its registers -- three groups per wave: up to three slots -- and the
-  // line is not partitioned (of 24 / 12 = 2 tiles along the line one would be a boundary tile): "+z:1,3;+t:1,3" N_ev 200 32.6 against
-  // 33.4 ms.  Else 8 x 16, then 12 x 16 (spills with four slots), then 4 x 32 (512-byte runs, but 1 + K/4 units).
-  const int first = (!partitioned && nSlots < kMT_MaxSlots) ? 12 : 8;
-  for (int tj : {first, 8, 12, 4}) {
-    if (want && tj != want) continue;
-    if (reduced && tj == 4) continue;  // (storage types other than fp64 FLOAT2 come with the 16-line tiles only)
-    if (two && tj == 12) continue;
-    if (extent % tj != 0 || tj + kmax > (tj == 4 ? 8 : 16)) continue;
-    return tj;
-  }
-  return 0;
-}
-
-// mu = x: R whole rows per workgroup of W waves, G = 2 | 3 groups of 4 sites per wave: R X0 = 16 G W sites.  Two workgroups of 8
-// waves per CU where the rows allow, else one of 16 (MUGIQ_HIP_MFMA_ROW_WAVES = 8 | 16 fixes it).
-static bool mfma_reduced(const MugiqHipSpinorField &ev) { return !(ev.precision == 8 && ev.field_order == 2); }
-static bool mfma_row_geometry(const MugiqHipSpinorField &ev, int *groups, int *rows, int *waves, bool two = false) {
-  const int epr = ev.X[0] / 2, nRows = ev.volumeCB / epr;
-  if (epr % 4 != 0) return false;
-  int want = 0;
-  if (const char *e = getenv("MUGIQ_HIP_MFMA_ROW_WAVES")) want = atoi(e);
-  for (int w : {8, 16}) {  // (X0 = 48, N_ev 200, spill-free kernels: two workgroups of 8 waves per CU 13.1 ms per entry, one of 16 13.6)
-    if (want && w != want) continue;
-    if ((mfma_reduced(ev) || two) && w != 8) continue;  // (... and with the 8-wave row tile only; so are the two-sided tiles)
-    for (int g : {3, 2}) {
-      if (two && mfma_reduced(ev) && g != 2) continue;  // (two-sided, storage other than fp64 FLOAT2: 3 groups per wave spill)
-      if ((2 * g * w) % epr != 0) continue;
-      const int r = 2 * g * w / epr;
-      if (nRows % r != 0 || r * 8 * (epr + kMT_MaxLength / 2) > 64 * w) continue;
-      if (24 * ((r * (epr + kMT_MaxLength / 2) + 12) / 16 * 16 + 4) > (w == 8 ? kMT_BufElems / 2 : kMT_BufElems)) continue;  // the LDS image of a tile buffer
-      *groups = g;
-      *rows = r;
-      *waves = w;
-      return true;
-    }
-  }
-  return false;
-}
-
-// Can the axial-gauge tile take this entry?  fp64 FLOAT2 storage and loops, mu = y, z, t, lengths 1 .. Kmax (the gauge is
-// built from W_1 .. W_Kmax).  MUGIQ_HIP_TILE_MFMA = 0 switches it off (the vector tiles of csrc/fused_tile.hip /
-// fused_tile16.hip take over).
-bool mfma_tile_applicable(const MugiqHipSpinorField &ev, int dir, const int *kvals, int nK, int partitioned, bool gaugeGiven, bool two) {
-  if (const char *e = getenv("MUGIQ_HIP_TILE_MFMA"))
-    if (atoi(e) == 0) return false;
-  if (const char *e = getenv("MUGIQ_HIP_FUSED_TILE"))
-    if (atoi(e) == 0) return false;  // streaming kernel only
-  if (const char *e = getenv("MUGIQ_HIP_TILE_COLS"))
-    if (atoi(e) != 0) return false;  // a vector-tile generation was asked for by name
-  if (const char *e = getenv("MUGIQ_HIP_TILE_GLDS"))
-    if (atoi(e) == 0) return false;  // register-staged vector tile asked for
-  if ((ev.precision != 8 && ev.precision != 4) || (ev.field_order != 2 && ev.field_order != 4)) return false;
-  if (const char *e = getenv("MUGIQ_HIP_MFMA_STORAGE"))
-    if (atoi(e) == 0 && mfma_reduced(ev)) return false;  // fp64 FLOAT2 only, as before
-  if (2 * (int64_t)ev.parity_offset >= (1LL << 31)) return false;  // the kernel keeps 32-bit element offsets
-  // lengths ascending; from 1 without a gap where the tile has to build the gauge itself (from W_1 .. W_Kmax = the links it is
-  // handed); any ascending list where the caller has built the gauge (the driver holds W_1 .. W_stop whatever the entry starts at)
-  for (int i = 0; i < nK; i++)
-    if (kvals[i] < 1 || (i > 0 && kvals[i] <= kvals[i - 1]) || (!gaugeGiven && kvals[i] != i + 1)) return false;
-  const int kmax = kvals[nK - 1];
-  if (kmax > kMT_MaxLength || kmax > ev.X[dir]) return false;
-  if (dir == 0) {  // whole x rows: no ghost handling
-    int g, r, w;
-    if (const char *e = getenv("MUGIQ_HIP_MFMA_ROW"))
-      if (atoi(e) == 0) return false;
-    if (2 * (int64_t)ev.parity_offset >= (1LL << 28)) return false;  // (the row tile keeps 32-bit BYTE offsets)
-    return !partitioned && mfma_row_geometry(ev, &g, &r, &w, two);
-  }
-  return mfma_tile_tj(ev.X[dir], kmax, kMT_MaxSlots, true, mfma_reduced(ev), two) != 0;
-}
-
-static int launch_mfma_tile(const MTileArgs &a, int precision, int order, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream) {
+static int launch_mfma_tile(const MTileArgs &a, int precision, int order, int dir, int sign, int ns, const MfmaLaunch &g, hipStream_t stream) {
   if (a.VL) {  // two-sided
-    if (precision == 8 && order == 2) return launch_mfma_tile_two_d2(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
-    if (precision == 8) return launch_mfma_tile_two_d4(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
-    if (order == 2) return launch_mfma_tile_two_f2(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
-    return launch_mfma_tile_two_f4(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
+    if (precision == 8 && order == 2) return launch_mfma_tile_two_d2(a, dir, sign, ns, g, stream);
+    if (precision == 8) return launch_mfma_tile_two_d4(a, dir, sign, ns, g, stream);
+    if (order == 2) return launch_mfma_tile_two_f2(a, dir, sign, ns, g, stream);
+    return launch_mfma_tile_two_f4(a, dir, sign, ns, g, stream);
   }
-  if (precision == 8 && order == 2) return launch_mfma_tile_t<double, 2, true>(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
-  if (precision == 8) return launch_mfma_tile_d4(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
-  if (order == 2) return launch_mfma_tile_f2(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
-  return launch_mfma_tile_f4(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
-}
-
-// Face layers a mu = x entry writes on its way through the eigenvectors (see MTileArgs::pack).  entry_pack_capacity: how many
-// targets such an entry can take (0: it cannot -- not the row tile, or rows of a workgroup would straddle a z / t coordinate)
-int entry_pack_capacity(const MugiqHipSpinorField &ev, const int *kvals, int nK) {
-  if (const char *e = getenv("MUGIQ_HIP_PACK_IN_ENTRY"))
-    if (atoi(e) == 0) return 0;
-  if (mfma_reduced(ev)) return 0;
-  if (!mfma_tile_applicable(ev, 0, kvals, nK, 0, true)) return 0;  // (the driver builds the gauge where the lengths do not start at 1)
-  int g, r, w;
-  if (!mfma_row_geometry(ev, &g, &r, &w) || ev.X[1] % r != 0) return 0;
-  if ((int64_t)ev.X[1] * (ev.X[0] / 2) >= (1 << 20)) return 0;  // (face entry within its (z | t) slice: 20 bits in the kernel)
-  return kMT_MaxPack;
-}
-
-size_t axial_gauge_bytes(const MugiqHipSpinorField &ev, int dir, const int *kvals, int nK, int partitioned) {
-  if (!mfma_tile_applicable(ev, dir, kvals, nK, partitioned, true)) return 0;
-  return (size_t)9 * (ev.X[dir] + kvals[nK - 1]) * (size_t)(2 * ev.volumeCB / ev.X[dir]) * sizeof(Cplx<double>);
+  if (precision == 8 && order == 2) return launch_mfma_tile_t<double, 2, true>(a, dir, sign, ns, g, stream);
+  if (precision == 8) return launch_mfma_tile_d4(a, dir, sign, ns, g, stream);
+  if (order == 2) return launch_mfma_tile_f2(a, dir, sign, ns, g, stream);
+  return launch_mfma_tile_f4(a, dir, sign, ns, g, stream);
 }
 
 template <typename F>
@@ -343,14 +246,13 @@ static int build_axial_gauge_t(void *G_d, const MugiqHipSpinorField &ev, const v
   g.G = static_cast<Cplx<double> *>(G_d);
   g.dev = dev_d;
   for (int l = 0; l < kMT_MaxLength; l++) g.E[l] = static_cast<const Cplx<F> *>(E_d[l < kmax ? l : 0]);
-  long long strideMu = 1;
-  for (int d = 0; d < dir; d++) strideMu *= ev.X[d];
+  const LineGeometry lines = line_geometry(ev, dir);
   g.kmax = kmax;
   g.sign = sign;
   g.J = ev.X[dir];
-  g.strideMu = dir == 0 ? 1 : (int)(strideMu / 2);
-  g.H = (int)(ev.volumeCB / ((long long)ev.X[dir] * g.strideMu));
-  g.numCols = 2 * ev.volumeCB / ev.X[dir];
+  g.strideMu = lines.strideMu;
+  g.H = lines.H;
+  g.numCols = lines.numCols;
   g.volumeCB = ev.volumeCB;
   g.rowMode = dir == 0;
   g.X1 = ev.X[1];
@@ -376,7 +278,7 @@ static double deviation_from_bits(unsigned long long b) {
 // The free fused call: the gauge from the links of the call into the stream's workspace, and its largest deviation (host-blocking)
 int build_axial_gauge_checked(void **G_out, double *deviation, const MugiqHipSpinorField &ev, const void *const *E_d, int kmax, int dir, int sign,
                               hipStream_t stream) {
-  const size_t gb = (size_t)9 * (ev.X[dir] + kmax) * (size_t)(2 * ev.volumeCB / ev.X[dir]) * sizeof(Cplx<double>);
+  const size_t gb = axial_gauge_bytes_of(ev, dir, kmax);
   void *ws = nullptr;
   int st = stream_workspace(&ws, gb + 256, stream);
   if (st) return st;
@@ -502,36 +404,25 @@ static int build_axial_gauge_links_t(void *G_d, const MugiqHipSpinorField &ev, c
   g.U = static_cast<const Cplx<F> *>(U.data);
   g.Upo = U.parity_offset;
   g.Ustride = U.stride;
-  long long strideMu = 1;
   for (int d = 0; d < 4; d++) {
     g.X[d] = ev.X[d];
     g.R[d] = U.R[d];
-    if (d < dir) strideMu *= ev.X[d];
   }
+  const LineGeometry lines = line_geometry(ev, dir);
   g.dir = dir;
   g.kmax = kmax;
   g.sign = sign;
   g.J = ev.X[dir];
-  g.strideMu = dir == 0 ? 1 : (int)(strideMu / 2);
-  g.H = (int)(ev.volumeCB / ((long long)ev.X[dir] * g.strideMu));
-  g.numCols = 2 * ev.volumeCB / ev.X[dir];
+  g.strideMu = lines.strideMu;
+  g.H = lines.H;
+  g.numCols = lines.numCols;
   g.rowMode = dir == 0;
   hipLaunchKernelGGL(axial_gauge_from_links_kernel<F>, dim3((g.numCols + 63) / 64), dim3(64), 0, stream, g);
   MUGIQ_CHECK_HIP(hipGetLastError());
   return MUGIQ_HIP_SUCCESS;
 }
-// Can the gauge of (dir, sign) with lengths up to kmax be taken from the gauge field?  Always along a direction that is not partitioned
-// (border 0: periodic line); along a partitioned one as far as the border of the extended field reaches: the continued positions need the
-// links at J .. J + kmax - 2 (sign +) or -1 .. -kmax (sign -).
-bool axial_gauge_from_links_possible(const MugiqHipSpinorField &ev, const MugiqHipGaugeField &U, int kmax, int dir, int sign) {
-  if (U.precision != ev.precision) return false;
-  if (const char *e = getenv("MUGIQ_HIP_GAUGE_FROM_LINKS"))
-    if (atoi(e) == 0) return false;
-  const int R = U.R[dir];
-  return R == 0 || (sign == MUGIQ_HIP_DISP_SIGN_PLUS ? kmax <= R + 1 : kmax <= R);
-}
 int build_axial_gauge_from_links(void *G_d, const MugiqHipSpinorField &ev, const MugiqHipGaugeField &U, int kmax, int dir, int sign, hipStream_t stream) {
-  MUGIQ_REQUIRE(axial_gauge_from_links_possible(ev, U, kmax, dir, sign), "axial gauge from the links: precision %d / border %d along %d, lengths up to %d (internal)", U.precision, U.R[dir], dir, kmax);
+  MUGIQ_REQUIRE(axial_gauge_from_links_possible(ev, U, kmax, dir, sign, FusedSwitches{}), "axial gauge from the links: precision %d / border %d along %d, lengths up to %d (internal)", U.precision, U.R[dir], dir, kmax);
   return ev.precision == 8 ? build_axial_gauge_links_t<double>(G_d, ev, U, kmax, dir, sign, stream)
                            : build_axial_gauge_links_t<float>(G_d, ev, U, kmax, dir, sign, stream);
 }
@@ -539,75 +430,47 @@ int build_axial_gauge_from_links(void *G_d, const MugiqHipSpinorField &ev, const
 // ultra_d != NULL: also produce the ultra-local loop (k = 0) into ultra_d as one more slot; *carried says whether that
 // happened (only a launch over the whole lattice may: see csrc/fused_tile.hip).  evL != NULL: the two-sided tile, evL the left set
 // and ev the right (displaced) one
-int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
-                    const int *kvals, int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers, int region,
+int mfma_tile_entry(const FusedForm &form, void *loop_d, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
+                    const int *kvals, int nK, int sign, const void *ghost_d, int layers, int region,
                     hipStream_t stream, void *ultra_d, int *carried, const MugiqHipSpinorField *evL, const void *G_d,
                     const EntryPackTarget *pack, int nPack, bool *packed) {
   MUGIQ_REQUIRE(nPack <= kMT_MaxPack && (nPack == 0 || packed), "mfma tile: %d pack targets (internal)", nPack);
+  const int dir = form.dir, partitioned = form.partitioned, loopPrecision = form.loopPrecision;
   const bool two = evL != nullptr;
-  const size_t ptr_bytes = sizeof(void *) * (size_t)nVec * (two ? 2 : 1);
-  std::vector<unsigned char> host(ptr_bytes + sizeof(double) * (size_t)nVec);
-  const void **hl = reinterpret_cast<const void **>(host.data());
-  double *hs = reinterpret_cast<double *>(host.data() + ptr_bytes);
-  for (int n = 0; n < nVec; n++) {
-    hl[n] = ev[n].data;
-    if (two) hl[nVec + n] = evL[n].data;
-    hs[n] = 1.0 / sigma[n];
-  }
-  void *dev = nullptr;
-  int st = upload_table(&dev, host.data(), host.size(), stream);
-  if (st) return st;
   MTileArgs a;
+  const void *invSigma = nullptr;
+  int st = upload_vector_table(&a.L, &invSigma, ev, evL, sigma, nVec, 8, 8, stream);  // (1/sigma in double whatever the storage)
+  if (st) return st;
   const int64_t slot_stride = (int64_t)16 * 2 * ev[0].volumeCB * 2 * loopPrecision;  // bytes
   a.outFloat = loopPrecision == 4;
   if (carried) *carried = 0;
-  a.L = reinterpret_cast<const void *const *>(dev);
   a.VL = two ? a.L + nVec : nullptr;
-  a.leftBufElems = 0;
-  a.inv_sigma = reinterpret_cast<const double *>(static_cast<unsigned char *>(dev) + ptr_bytes);
+  a.inv_sigma = static_cast<const double *>(invSigma);
   a.nVec = nVec;
-  long long strideMu = 1;
-  for (int d = 0; d < 4; d++) {
-    a.X[d] = ev[0].X[d];
-    if (d < dir) strideMu *= ev[0].X[d];
-  }
-  strideMu = dir == 0 ? 1 : strideMu / 2;  // (unused by the row tile: a step along x is half a checkerboard entry)
+  for (int d = 0; d < 4; d++) a.X[d] = ev[0].X[d];
   a.volumeCB = ev[0].volumeCB;
   a.stride = ev[0].stride;
   a.parity_offset = ev[0].parity_offset;
   a.partitioned = partitioned;
   a.ghost = ghost_d;
-  a.faceCB = ev[0].volumeCB / ev[0].X[dir];
-  a.ghost_vec_stride = (int64_t)layers * 24 * a.faceCB;
-  a.strideMu = (int)strideMu;
-  a.H = (int)(ev[0].volumeCB / (ev[0].X[dir] * strideMu));
-  a.numCols = 2 * ev[0].volumeCB / ev[0].X[dir];
-  int tj = 0, rowGroups = 0, rowWaves = 0;
-  a.rowsPerTile = a.rowChunk = 0;
-  if (dir == 0) {
-    MUGIQ_REQUIRE(mfma_row_geometry(ev[0], &rowGroups, &a.rowsPerTile, &rowWaves, two), "mfma tile: no row geometry for X0 = %d (internal)", ev[0].X[0]);
-    a.rowChunk = (a.rowsPerTile * (ev[0].X[0] / 2 + kMT_MaxLength / 2) + 12) / 16 * 16 + 4;  // > R (X0/2 + 4) (the entry behind the rows holds the zero of the padded operand lanes), and 4 mod 16 entries: 16 banks of phase per component
-    MUGIQ_REQUIRE(24 * a.rowChunk <= (rowWaves == 8 ? kMT_BufElems / 2 : kMT_BufElems), "mfma tile: row image of %d entries per chunk does not fit (internal)", a.rowChunk);
-    if (two) a.leftBufElems = 24 * a.rowChunk;  // (the left image has the layout of the right one)
-    ultra_d = nullptr;  // (the row tile takes no fourth slot)
-    tj = ev[0].X[0];    // one "tile" along mu
-  } else {
-    tj = mfma_tile_tj(ev[0].X[dir], kvals[nK - 1], kMT_MaxSlots, true, mfma_reduced(ev[0]), two);
-    MUGIQ_REQUIRE(tj != 0, "mfma tile: no tile geometry for extent %d, lengths up to %d (internal)", ev[0].X[dir], kvals[nK - 1]);
-  }
-  const int nJT = ev[0].X[dir] / tj;
+  const LineGeometry lines = line_geometry(ev[0], dir, layers);
+  a.faceCB = lines.faceCB;
+  a.ghost_vec_stride = lines.ghost_vec_stride;
+  a.strideMu = lines.strideMu;
+  a.H = lines.H;
+  a.numCols = lines.numCols;
+  if (dir == 0) ultra_d = nullptr;  // (the row tile takes no fourth slot)
   a.overwrite = (region & MUGIQ_HIP_REGION_OVERWRITE) ? 1 : 0;
   region &= 0xff;
   if (region != MUGIQ_HIP_REGION_ALL) ultra_d = nullptr;
-  a.kmaxG = kvals[nK - 1];  // (mfma_tile_applicable: ascending; 1 .. nK unless the caller's gauge is at hand)
+  a.kmaxG = kvals[nK - 1];  // (select_fused_form: ascending; 1 .. nK unless the caller's gauge is at hand)
   // the axial gauge of this (direction, sign): the caller's, if it has built one; else rebuilt into the stream's workspace (one
   // pass over W_1)
   if (G_d) {
     a.G = static_cast<const Cplx<double> *>(G_d);
   } else {
-    MUGIQ_REQUIRE(a.kmaxG == nK, "mfma tile: lengths %d .. %d without the caller's axial gauge (internal)", kvals[0], a.kmaxG);
     void *gbuf = nullptr;
-    if ((st = stream_workspace(&gbuf, (size_t)9 * (ev[0].X[dir] + a.kmaxG) * a.numCols * sizeof(Cplx<double>), stream))) return st;
+    if ((st = stream_workspace(&gbuf, form.gaugeBytes, stream))) return st;
     if ((st = build_axial_gauge(gbuf, ev[0], E_d, a.kmaxG, dir, sign, stream))) return st;
     a.G = static_cast<const Cplx<double> *>(gbuf);
   }
@@ -615,9 +478,7 @@ int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *
   // k0 .. k1 stages the TJ + k1 positions its sites and their shifted partners live on
   for (int first = 0, ns = 0; first < nK; first += ns) {
     const bool takesUltra = ultra_d && first == 0;
-    const int room = two ? mt_two_max_slots(dir, !mfma_reduced(ev[0])) : dir == 0 ? kMT_MaxSlots - 1 : kMT_MaxSlots;  // (the row tile has no four-slot instance)
-    const int slotsLeft = nK - first + (takesUltra ? 1 : 0), launchesLeft = (slotsLeft + room - 1) / room;
-    ns = (slotsLeft + launchesLeft - 1) / launchesLeft - (takesUltra ? 1 : 0);  // evenly: 1 .. 8 with the ultra-local loop = 3 + 3 + 3 slots
+    ns = fused_even_slots(nK - first + (takesUltra ? 1 : 0), form.slotsPerLaunch) - (takesUltra ? 1 : 0);  // 1 .. 8 with the ultra-local loop = 3 + 3 + 3 slots
     a.kmax = kvals[first + ns - 1];
     for (int s = 0; s < kMT_MaxSlots; s++) {
       const int i = first + (s < ns ? s : 0);
@@ -633,15 +494,10 @@ int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *
       withUltra = true;
     }
     // the tile of THIS launch (its slots and the positions it stages; the gauge does not depend on it)
-    int tjL = tj, nJTL = nJT;
-    if (dir != 0) {
-      const int t2 = mfma_tile_tj(ev[0].X[dir], a.kmax, nSlots, partitioned != 0, mfma_reduced(ev[0]), two);
-      if (t2) tjL = t2;
-      nJTL = ev[0].X[dir] / tjL;
-      if (two) a.leftBufElems = mt_left_buf_elems(tjL);
-    }
-    // region 0: everything | 1: tiles whose shifted reads stay inside the local lattice | 2: tiles that read ghost layers
-    // (the split is by the ENTRY's longest length, so that the interior and the boundary launch of a slot cover complementary tiles)
+    const MfmaLaunch g = mfma_launch_geometry(form, nSlots, a.kmax);
+    a.leftBufElems = g.leftBufElems;
+    a.rowsPerTile = g.rows;
+    a.rowChunk = g.rowChunk;
     a.nPack = 0;
     if (!two && dir == 0 && first == 0 && nPack > 0 && !*packed && ev[0].X[1] % a.rowsPerTile == 0) {  // the first launch of the entry packs
       a.nPack = nPack;
@@ -657,20 +513,10 @@ int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *
       }
       *packed = true;
     }
-    a.jtBegin = 0;
-    a.jtCount = nJTL;
-    if (region != MUGIQ_HIP_REGION_ALL) {
-      const int nb = partitioned ? std::min(nJTL, (a.kmaxG + tjL - 1) / tjL) : 0;  // boundary tiles
-      if (region == MUGIQ_HIP_REGION_INTERIOR) {
-        a.jtBegin = sign == MUGIQ_HIP_DISP_SIGN_PLUS ? 0 : nb;
-        a.jtCount = nJTL - nb;
-      } else {
-        a.jtBegin = sign == MUGIQ_HIP_DISP_SIGN_PLUS ? nJTL - nb : 0;
-        a.jtCount = nb;
-      }
-    }
+    // (the split is by the ENTRY's longest length, so that the interior and the boundary launch of a slot cover complementary tiles)
+    tile_range(region, partitioned, sign, ev[0].X[dir] / g.tj, a.kmaxG, g.tj, a.jtBegin, a.jtCount);
     if (a.jtCount > 0) {
-      st = launch_mfma_tile(a, ev[0].precision, ev[0].field_order, dir, sign, nSlots, tjL, rowGroups, rowWaves, stream);
+      st = launch_mfma_tile(a, ev[0].precision, ev[0].field_order, dir, sign, nSlots, g, stream);
       if (st) return st;
       if (withUltra && carried) *carried = 1;
     }

@@ -5,29 +5,11 @@
 #include "internal.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 namespace mugiq {
 
-// Tile geometries (TJ positions along mu x LN lines per workgroup; 16 waves = 1024 threads each):
-//   TJ =  4, LN = 32: 128 sites, 4 + Kmax <=  8 staged positions, 1 + Kmax/4  units requested per site (the tile of csrc/fused_tile.hip)
-//   TJ =  8, LN = 16: 128 sites, 8 + Kmax <= 16 staged positions, 1 + Kmax/8
-//   TJ = 12, LN = 16: 192 sites, 12 + Kmax <= 16 staged positions, 1 + Kmax/12
-// 4-site groups: TJ LN / 4, an equal share per wave (2 | 2 | 3), group -> (position, 4 consecutive lines).
-constexpr int kMT_Waves = 16;
-constexpr int kMT_MaxSlots = 4;   // 3 displaced slots + the ultra-local loop riding along (k = 0) per launch
-constexpr int kMT_MaxLength = 8;  // lengths 1 .. 8 per entry (launches of three lengths; 4 x 32 tiles: 1 .. 4)
-constexpr int kMT_MaxPack = 4;   // face-layer targets a row-tile launch can fill on the way (z and t, low and high side)
-constexpr int kMT_Chunk = 68;     // complex elements per chunk: 64 + 4 of bank phase
-constexpr int kMT_Chunks = 4 * 12;  // chunks of a tile buffer: 64 / LN positions each, 12 components, <= 4 * 64 / LN staged positions
-constexpr int kMT_BufElems = kMT_Chunks * kMT_Chunk;
-constexpr size_t kMT_MaxLds = 160 * 1024;  // LDS of one workgroup (gfx950)
-// two-sided column tiles: one buffer of the left image holds the TJ own positions (TJ / (64 / LN) position chunks of 12 components)
-constexpr int mt_left_buf_elems(int tj) { return tj / (64 / (tj == 4 ? 32 : 16)) * 12 * kMT_Chunk; }
-// slots per two-sided launch that compile without scratch (128 VGPRs): 3 on the fp64 FLOAT2 column tiles, else 2
-constexpr int mt_two_max_slots(int dir, bool full) { return dir != 0 && full ? 3 : 2; }
-
+// (the tile geometries and the kMT_* limits: csrc/fused_form.h)
 struct MTileArgs {
   void *out[kMT_MaxSlots];  // Cplx<double> | Cplx<float> (outFloat)
   int outFloat;
@@ -182,7 +164,7 @@ __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile
     commits = valid;
     commitsL = TWO && valid && mm >= rOff && mm < rOff + EPR;  // (the same layout as the right image; own positions only)
     wIdxL = wIdx;
-    sByte = (unsigned)soff * (unsigned)sizeof(Cplx<F>);  // (< 2^32: mfma_tile_applicable)
+    sByte = (unsigned)soff * (unsigned)sizeof(Cplx<F>);  // (< 2^32: select_fused_form)
     if constexpr (PACK) {  // the R rows of a workgroup share z and t (X1 % R == 0, checked by the launcher)
       const int m = mm - rOff;  // a real position of the row (not a continued one): this thread owns the site
       if (valid && m >= 0 && m < EPR) pkAB = ((parity * 12 + 3 * spin) << 20) | ((rowG % a.X[1]) * EPR + m);
@@ -502,21 +484,18 @@ __global__ __launch_bounds__(64 * (DIR == 0 ? TJ : kMT_Waves), 4) void mfma_tile
 // F, ORDER: the eigenvectors' storage.  FULL: every tile geometry and the face-layer packing (fp64 FLOAT2); else the 16-line column tiles
 // and the 8-wave row tile only (a sixth of the instances per storage type).  TWO: the two-sided tile (a.VL = the left set; no 12-position
 // column tile -- its two images would not fit the LDS of a workgroup -- and no face layers)
+// g: mfma_launch_geometry of this launch (csrc/fused_form.cpp)
 template <typename F, int ORDER, bool FULL, bool TWO = false>
-inline int launch_mfma_tile_t(MTileArgs a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream) {
-  const int ln = tj == 4 ? 32 : 16;
-  const size_t bufElems = dir == 0 && rowWaves == 8 ? kMT_BufElems / 2 : kMT_BufElems;
-  const size_t imageElems = 2 * bufElems + (TWO ? 2 * (size_t)a.leftBufElems : 0);
-  const size_t shmem = std::max(imageElems, (size_t)16 * (dir == 0 ? 4 * rowGroups * rowWaves : tj * ln)) * sizeof(Cplx<double>);
+inline int launch_mfma_tile_t(MTileArgs a, int dir, int sign, int ns, const MfmaLaunch &g, hipStream_t stream) {
+  const int tj = g.tj, ln = g.lines, rowGroups = g.rowGroups, rowWaves = g.waves;
+  const size_t shmem = g.ldsBytes;
   if (TWO) {
     MUGIQ_REQUIRE(a.VL != nullptr && a.nPack == 0 && (dir == 0 || tj != 12) && (dir != 0 || (rowWaves == 8 && (FULL || rowGroups == 2))) && ns <= mt_two_max_slots(dir, FULL) && shmem <= kMT_MaxLds,
                   "mfma tile: two-sided geometry %d / %d waves / %d slots / %d pack targets / %zu bytes of LDS not built (internal)", tj, rowWaves, ns, a.nPack, shmem);
   }
   const unsigned nblocks = dir == 0 ? (unsigned)(a.numCols / a.rowsPerTile) : (unsigned)(((a.numCols + ln - 1) / ln) * a.jtCount);
-  a.blockOrder = 2;
-  if (const char *e = getenv("MUGIQ_HIP_TILE_ORDER")) a.blockOrder = atoi(e) & 2;
-  if (nblocks % 8 != 0 || dir == 0) a.blockOrder = 0;
-  const dim3 grid(nblocks), block(64 * (dir == 0 ? rowWaves : kMT_Waves));
+  a.blockOrder = g.block_order(nblocks);
+  const dim3 grid(nblocks), block(64 * g.waves);
   if (!FULL) {
     MUGIQ_REQUIRE(a.nPack == 0 && tj != 4 && (dir != 0 || rowWaves == 8), "mfma tile: geometry %d / %d waves / %d pack targets not built for this storage type (internal)", tj, rowWaves, a.nPack);
   }
@@ -572,13 +551,13 @@ inline int launch_mfma_tile_t(MTileArgs a, int dir, int sign, int ns, int tj, in
 }
 
 // the reduced sets (fused_mfma_d4.hip, fused_mfma_f2.hip, fused_mfma_f4.hip)
-int launch_mfma_tile_d4(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
-int launch_mfma_tile_f2(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
-int launch_mfma_tile_f4(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
+int launch_mfma_tile_d4(const MTileArgs &a, int dir, int sign, int ns, const MfmaLaunch &g, hipStream_t stream);
+int launch_mfma_tile_f2(const MTileArgs &a, int dir, int sign, int ns, const MfmaLaunch &g, hipStream_t stream);
+int launch_mfma_tile_f4(const MTileArgs &a, int dir, int sign, int ns, const MfmaLaunch &g, hipStream_t stream);
 // the two-sided tiles, one translation unit per storage type (fused_mfma_two.hip: fp64 FLOAT2; fused_mfma_two_d4 / _f2 / _f4.hip)
-int launch_mfma_tile_two_d2(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
-int launch_mfma_tile_two_d4(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
-int launch_mfma_tile_two_f2(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
-int launch_mfma_tile_two_f4(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream);
+int launch_mfma_tile_two_d2(const MTileArgs &a, int dir, int sign, int ns, const MfmaLaunch &g, hipStream_t stream);
+int launch_mfma_tile_two_d4(const MTileArgs &a, int dir, int sign, int ns, const MfmaLaunch &g, hipStream_t stream);
+int launch_mfma_tile_two_f2(const MTileArgs &a, int dir, int sign, int ns, const MfmaLaunch &g, hipStream_t stream);
+int launch_mfma_tile_two_f4(const MTileArgs &a, int dir, int sign, int ns, const MfmaLaunch &g, hipStream_t stream);
 
 }  // namespace mugiq

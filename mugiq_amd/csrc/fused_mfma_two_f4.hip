@@ -2,7 +2,7 @@
 #include "fused_mfma_kernel.h"
 
 namespace mugiq {
-int launch_mfma_tile_two_f4(const MTileArgs &a, int dir, int sign, int ns, int tj, int rowGroups, int rowWaves, hipStream_t stream) {
-  return launch_mfma_tile_t<float, 4, false, true>(a, dir, sign, ns, tj, rowGroups, rowWaves, stream);
+int launch_mfma_tile_two_f4(const MTileArgs &a, int dir, int sign, int ns, const MfmaLaunch &g, hipStream_t stream) {
+  return launch_mfma_tile_t<float, 4, false, true>(a, dir, sign, ns, g, stream);
 }
 }  // namespace mugiq

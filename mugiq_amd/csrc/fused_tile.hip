@@ -19,18 +19,11 @@
 #include "internal.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
-#include <vector>
 
 namespace mugiq {
 
-constexpr int kTileTJ = 4;        // positions along mu per workgroup
-constexpr int kTileMaxSlots = 3;  // displaced slots per launch: waves = kTileTJ * nslot <= 12
-constexpr int kTileCarry = kTileMaxSlots + 1;  // + the ultra-local loop riding along as a slot with k = 0 (16 waves; GLDS form only)
-constexpr int kTileMaxPos = 16;   // TJ + Kmax upper bound
-constexpr int kTileCols = 32;     // lines per workgroup (each line is held by two lanes: one per spin half)
-
+// (kTileTJ, kTileMaxSlots, kTileCarry, kTileMaxPos, kTileCols: csrc/fused_form.h)
 template <typename F, typename A> struct TileArgs {
   Cplx<A> *out[kTileCarry];  // where every slot goes
   const void *const *L;
@@ -435,21 +428,12 @@ __global__ __launch_bounds__(64 * NW) void tile_displaced_contract_kernel(TileAr
 #undef MUGIQ_TILE_BODY
 #undef MUGIQ_TILE_SIGMA
 
-// global -> LDS staging with three buffers: fp64 FLOAT2 column tiles of at most 8 positions (MUGIQ_HIP_TILE_GLDS=0: off)
-template <typename F, int ORDER> static bool tile_glds(int dir, int kmax) {
-  bool glds = std::is_same<F, double>::value && ORDER == 2 && dir >= 1 && kTileTJ + kmax <= 8;
-  if (const char *e = getenv("MUGIQ_HIP_TILE_GLDS")) glds = glds && atoi(e) != 0;
-  return glds;
-}
-
-template <typename F, typename A, int ORDER> static int launch_tile(TileArgs<F, A> a, int dir, int sign, hipStream_t stream) {
-  const int NP = dir >= 1 ? kTileTJ + a.kmax : kTileTJ;
-  const int PHsel = NP <= 8 ? 4 : kTileMaxPos / 2;
-  const bool glds = tile_glds<F, ORDER>(dir, a.kmax);
-  const bool carry = a.nslot == kTileCarry;  // (tile_entry adds the fourth slot only where glds holds)
-  const size_t tileBytes = (glds ? 3 : 2) * sizeof(Cplx<F>) * (size_t)(2 * PHsel) * 12 * kTileCols;  // padded positions
-  const size_t shmem = tileBytes;  // the staging tiles
-  a.tileBytes = (int)tileBytes;
+// g: tile32_launch_geometry of this launch (csrc/fused_form.cpp)
+template <typename F, typename A, int ORDER> static int launch_tile(TileArgs<F, A> a, int dir, int sign, const Tile32Launch &g, hipStream_t stream) {
+  const int NP = g.staged;
+  const bool glds = g.glds, carry = g.waves == 16;  // (tile_entry adds the fourth slot only where glds holds)
+  const size_t shmem = g.ldsBytes;  // the staging tiles
+  a.tileBytes = (int)shmem;
   unsigned nblocks = ((a.numCols + kTileCols - 1) / kTileCols) * a.jtCount;
   if (dir == 0) {  // row tile: 2 groups of kTileCols/(X0/2) whole x-rows per workgroup
     const int ePR = a.X[0] / 2, rpg = kTileCols / ePR;
@@ -457,10 +441,8 @@ template <typename F, typename A, int ORDER> static int launch_tile(TileArgs<F, 
   }
   // workgroup order, measured on MI355X (48.48.24.24, 100 eigenvectors): XCD-contiguous with the tiles along mu as the
   // fastest index is 2.5 % (fp64) / 1.5 % (fp32) faster than the plain order
-  a.blockOrder = 2;
-  if (const char *e = getenv("MUGIQ_HIP_TILE_ORDER")) a.blockOrder = atoi(e) & 3;
-  if (nblocks % 8 != 0) a.blockOrder &= 1;
-  const dim3 grid(nblocks), block(64 * (carry ? 16 : 12));
+  a.blockOrder = g.block_order(nblocks);
+  const dim3 grid(nblocks), block(64 * g.waves);
 #define MUGIQ_TILE_LAUNCH(D, S, P, G, W)                                                                              \
   {                                                                                                                   \
     auto kern = tile_displaced_contract_kernel<F, A, ORDER, D, S, P, G, W>;                                           \
@@ -488,68 +470,32 @@ template <typename F, typename A, int ORDER> static int launch_tile(TileArgs<F, 
   return MUGIQ_HIP_SUCCESS;
 }
 
-// Can the tiled kernel take this entry?  (otherwise the caller uses the first-generation streaming kernel)
-bool tile_applicable(const MugiqHipSpinorField &ev, int dir, int kmax, int precision, int partitioned) {
-  int mode = 1;  // MUGIQ_HIP_FUSED_TILE: 0 = streaming kernel only, 2 = column tile only (no row tile), default both
-  if (const char *e = getenv("MUGIQ_HIP_FUSED_TILE")) mode = atoi(e);
-  if (mode == 0 || (mode == 2 && dir == 0)) return false;
-  if (2 * (int64_t)ev.parity_offset >= (1LL << 31)) return false;  // the kernel keeps 32-bit element offsets
-  if (dir == 0) {  // row tile: whole x-rows in LDS, no ghost handling
-    const int ePR = ev.X[0] / 2;
-    if (partitioned || ePR > kTileCols || kmax >= ev.X[0]) return false;
-    const int rpg = kTileCols / ePR;
-    if ((ev.volumeCB / ePR) % (2 * rpg) != 0) return false;
-    return true;
-  }
-  if (ev.X[dir] % kTileTJ != 0) return false;
-  if (kmax > ev.X[dir]) return false;  // the staged window wraps at most once around the lattice
-  if (kTileTJ + kmax > kTileMaxPos) return false;
-  const int PHsel = kTileTJ + kmax <= 8 ? 4 : kTileMaxPos / 2;
-  const size_t lds = (size_t)2 * 2 * precision * (2 * PHsel) * 12 * kTileCols;
-  return lds <= 160 * 1024;
-}
-
 // ultra_d != NULL: also produce the ultra-local loop (k = 0, W = 1) into ultra_d, as a fourth slot of the 16-wave form; *carried
 // says whether that was possible (fp64 FLOAT2 column tiles staged global -> LDS, at most three displaced slots)
 template <typename F, typename A, int ORDER>
-int tile_entry(void *loop_d, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d, const int *kvals,
-               int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers, int region, hipStream_t stream,
-               void *ultra_d, int *carried) {
-  const size_t ptr_bytes = sizeof(void *) * (size_t)nVec;
-  std::vector<unsigned char> host(ptr_bytes + sizeof(A) * (size_t)nVec);
-  const void **hl = reinterpret_cast<const void **>(host.data());
-  A *hs = reinterpret_cast<A *>(host.data() + ptr_bytes);
-  for (int n = 0; n < nVec; n++) {
-    hl[n] = ev[n].data;
-    const F sg = static_cast<F>(sigma[n]);
-    hs[n] = static_cast<A>(1.0 / sg);
-  }
-  void *dev = nullptr;
-  int st = upload_table(&dev, host.data(), host.size(), stream);
-  if (st) return st;
+int tile_entry(const FusedForm &form, void *loop_d, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
+               const int *kvals, int nK, int sign, const void *ghost_d, int layers, int region, hipStream_t stream, void *ultra_d, int *carried) {
+  const int dir = form.dir, partitioned = form.partitioned;
   TileArgs<F, A> a;
+  const void *invSigma = nullptr;
+  int st = upload_vector_table(&a.L, &invSigma, ev, nullptr, sigma, nVec, (int)sizeof(F), (int)sizeof(A), stream);
+  if (st) return st;
   const int64_t slot_stride = (int64_t)16 * 2 * ev[0].volumeCB;
   if (carried) *carried = 0;
-  a.L = reinterpret_cast<const void *const *>(dev);
-  a.inv_sigma = reinterpret_cast<const A *>(static_cast<unsigned char *>(dev) + ptr_bytes);
+  a.inv_sigma = static_cast<const A *>(invSigma);
   a.nVec = nVec;
-  long long strideMu = 1;
-  for (int d = 0; d < 4; d++) {
-    a.X[d] = ev[0].X[d];
-    if (d < dir) strideMu *= ev[0].X[d];
-  }
-  strideMu /= 2;
+  for (int d = 0; d < 4; d++) a.X[d] = ev[0].X[d];
   a.volumeCB = ev[0].volumeCB;
   a.stride = ev[0].stride;
   a.parity_offset = ev[0].parity_offset;
   a.partitioned = partitioned;
   a.ghost = static_cast<const F *>(ghost_d);
-  a.faceCB = ev[0].volumeCB / ev[0].X[dir];
-  a.ghost_vec_stride = (int64_t)layers * 24 * a.faceCB;
-  if (dir == 0) strideMu = 1;  // unused by the row tile (a step along x is half a checkerboard entry)
-  a.strideMu = (int)strideMu;
-  a.H = (int)(ev[0].volumeCB / (ev[0].X[dir] * strideMu));
-  a.numCols = 2 * ev[0].volumeCB / ev[0].X[dir];
+  const LineGeometry lines = line_geometry(ev[0], dir, layers);
+  a.faceCB = lines.faceCB;
+  a.ghost_vec_stride = lines.ghost_vec_stride;
+  a.strideMu = lines.strideMu;
+  a.H = lines.H;
+  a.numCols = lines.numCols;
   a.nJT = dir == 0 ? 1 : ev[0].X[dir] / kTileTJ;  // (the row tile is not cut along x: one "tile", or X0 = 2 would launch nothing)
   a.overwrite = (region & MUGIQ_HIP_REGION_OVERWRITE) ? 1 : 0;
   region &= 0xff;
@@ -568,30 +514,16 @@ int tile_entry(void *loop_d, const MugiqHipSpinorField *ev, const double *sigma,
       if (s < a.nslot && kvals[i] > a.kmax) a.kmax = kvals[i];
     }
     // room for it: a free slot of the 12-wave forms, or the fourth slot of the 16-wave form (global -> LDS staging only)
-    if (ultra_d && k0 == 0 && nK <= kTileMaxSlots && (nK < kTileMaxSlots || tile_glds<F, ORDER>(dir, a.kmax))) {
+    if (ultra_d && k0 == 0 && nK <= kTileMaxSlots && (nK < kTileMaxSlots || tile32_launch_geometry(form, nK, a.kmax).glds)) {
       a.E[a.nslot] = nullptr;
       a.k[a.nslot] = 0;
       a.out[a.nslot] = static_cast<Cplx<A> *>(ultra_d);
       a.nslot++;
       withUltra = true;
     }
-    // region 0: everything | 1: tiles whose shifted reads stay inside the local lattice | 2: tiles that read ghost layers
-    a.jtBegin = 0;
-    a.jtCount = a.nJT;
-    if (region != MUGIQ_HIP_REGION_ALL && dir >= 1) {
-      const int nb = partitioned ? std::min(a.nJT, (a.kmax + kTileTJ - 1) / kTileTJ) : 0;  // boundary tiles
-      if (region == MUGIQ_HIP_REGION_INTERIOR) {
-        a.jtBegin = sign == MUGIQ_HIP_DISP_SIGN_PLUS ? 0 : nb;
-        a.jtCount = a.nJT - nb;
-      } else {
-        a.jtBegin = sign == MUGIQ_HIP_DISP_SIGN_PLUS ? a.nJT - nb : 0;
-        a.jtCount = nb;
-      }
-    } else if (region == MUGIQ_HIP_REGION_BOUNDARY) {
-      a.jtCount = 0;  // the row tile (x, never partitioned here) has no boundary part
-    }
+    tile_range(region, partitioned, sign, a.nJT, a.kmax, kTileTJ, a.jtBegin, a.jtCount);
     if (a.jtCount > 0) {
-      st = launch_tile<F, A, ORDER>(a, dir, sign, stream);
+      st = launch_tile<F, A, ORDER>(a, dir, sign, tile32_launch_geometry(form, a.nslot, a.kmax), stream);
       if (st) return st;
       if (withUltra && carried) *carried = 1;  // only now: a launch that covers the whole lattice did write the slot
     }
@@ -600,8 +532,8 @@ int tile_entry(void *loop_d, const MugiqHipSpinorField *ev, const double *sigma,
 }
 
 #define MUGIQ_TILE_INST(F, A, O)                                                                                                 \
-  template int tile_entry<F, A, O>(void *, const MugiqHipSpinorField *, const double *, int, const void *const *, const int *, int, \
-                                   int, int, int, const void *, int, int, hipStream_t, void *, int *);
+  template int tile_entry<F, A, O>(const FusedForm &, void *, const MugiqHipSpinorField *, const double *, int, const void *const *, const int *, \
+                                   int, int, const void *, int, int, hipStream_t, void *, int *);
 MUGIQ_TILE_INST(double, double, 2)
 MUGIQ_TILE_INST(double, double, 4)
 MUGIQ_TILE_INST(float, float, 2)

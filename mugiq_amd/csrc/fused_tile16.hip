@@ -7,26 +7,15 @@
 //   * column tile (mu = y, z, t): 4 positions x 3 slots = 12 items = 6 waves, 2 x 21.5 KB of LDS, two workgroups per CU.
 // Staging is by linear element index (element e of the [position][12][16] tile <-> thread e mod #threads), so any number of
 // waves stages any tile.  Arithmetic, prefetch depth, barrier discipline and the ghost / wrap handling are those of
-// csrc/fused_tile.hip.  Which generation takes what is decided by measurement (tile16_applicable below).
+// csrc/fused_tile.hip.  Which generation takes what is decided by measurement (tile16_admits in csrc/fused_form.cpp).
 #include "internal.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
-#include <vector>
 
 namespace mugiq {
 
-constexpr int kT16Cols = 16;       // lines per item (each line is held by two lanes: one per spin half)
-static int t16_tj() {              // positions along mu per column tile (MUGIQ_HIP_TILE16_TJ = 4 | 8)
-  if (const char *e = getenv("MUGIQ_HIP_TILE16_TJ")) return atoi(e) == 8 ? 8 : 4;
-  return 4;
-}
-constexpr int kT16MaxSlots = 3;
-constexpr int kT16MaxItems = 24;   // 12 waves
-constexpr int kT16MaxPos = 16;     // staged positions: TJ + Kmax upper bound
-constexpr int kT16Row = 12 * kT16Cols;  // elements of one staged position
-
+// (kT16Cols, kT16MaxSlots, kT16MaxItems, kT16MaxPos, kT16Row: csrc/fused_form.h)
 template <typename F, typename A> struct Tile16Args {
   Cplx<A> *loop;
   int64_t slot_stride;
@@ -383,74 +372,14 @@ __global__ __launch_bounds__(64 * 12) void tile16_displaced_contract_kernel(Tile
 #undef MUGIQ_T16_SIGMA
 #undef MUGIQ_T16_BARRIER
 
-static int gcd_int(int x, int y) { return y == 0 ? x : gcd_int(y, x % y); }
-
-// geometry of a launch: computed / staged positions, threads, loads per lane; false if the tile does not apply
-struct Tile16Plan {
-  int npc, np, m, maxSlots, minWaves;
-};
-static bool tile16_plan(const MugiqHipSpinorField &ev, int dir, int kmax, int partitioned, Tile16Plan &p) {
-  if (2 * (int64_t)ev.parity_offset >= (1LL << 31)) return false;  // the kernel keeps 32-bit element offsets
-  if (dir == 0) {  // row tile: whole x rows in LDS, no ghost handling
-    const int ePR = ev.X[0] / 2;
-    if (partitioned || kmax >= ev.X[0]) return false;
-    p.m = ePR / gcd_int(kT16Cols, ePR);  // lcm(16, ePR) / 16
-    p.npc = p.np = 2 * p.m;
-    if (p.npc > kT16MaxItems) return false;
-    if (ev.volumeCB % (p.m * kT16Cols) != 0) return false;
-    p.maxSlots = std::min(kT16MaxSlots, kT16MaxItems / p.npc);
-    p.minWaves = 2;
-    return true;
-  }
-  const int tj = t16_tj();
-  if (ev.X[dir] % tj != 0) return false;
-  if (kmax > ev.X[dir]) return false;  // the staged window wraps at most once around the lattice
-  if (tj + kmax > kT16MaxPos) return false;
-  p.m = 0;
-  p.npc = tj;
-  p.np = tj + kmax;
-  p.maxSlots = kT16MaxSlots;
-  p.minWaves = 6 * tj / 4;  // idle waves of a launch with fewer slots still stage
-  return true;
-}
-
-// Measured (48.48.24.24 fp64, 100 eigenvectors, three slots): row tile 9.3 ms here against 11.3 ms with 32-line positions
-// (24 of 32 lanes busy at X0 = 48); column tiles 10.6-10.9 ms here against 8.9 ms (256-byte instead of 512-byte runs per
-// load instruction; the two workgroups per CU did not buy the overlap hoped for).  So by default this kernel takes the ROW
-// tiles whose rows do not fill 32-line positions (32 % (X0/2) != 0) and whatever the second generation cannot take;
-// MUGIQ_HIP_TILE_COLS = 16 | 32 forces one generation for everything it can take.
-bool tile16_applicable(const MugiqHipSpinorField &ev, int dir, int kmax, int precision, int partitioned, bool secondGenerationApplies) {
-  int cols = 0;
-  if (const char *e = getenv("MUGIQ_HIP_TILE_COLS")) cols = atoi(e);
-  if (cols == 32) return false;
-  if (cols != 16 && secondGenerationApplies && !(dir == 0 && 32 % (ev.X[0] / 2) != 0)) return false;
-  int mode = 1;  // MUGIQ_HIP_FUSED_TILE: 0 = streaming kernel only, 2 = column tile only (no row tile), default both
-  if (const char *e = getenv("MUGIQ_HIP_FUSED_TILE")) mode = atoi(e);
-  if (mode == 0 || (mode == 2 && dir == 0)) return false;
-  Tile16Plan p;
-  if (!tile16_plan(ev, dir, kmax, partitioned, p)) return false;
-  // staging loads per lane with the fewest threads a launch may have (one slot)
-  const int waves = std::max(p.minWaves, (p.npc + 1) / 2);
-  const int phl = (p.np * kT16Row + 64 * waves - 1) / (64 * waves);
-  const int phlSel = phl <= 2 ? 2 : (phl <= 4 ? 4 : 8);
-  return phl <= 8 && (size_t)2 * 2 * precision * phlSel * 64 * waves <= 160 * 1024;  // two staging tiles (three when they fit: launch_tile16)
-}
-
-template <typename F, typename A, int ORDER> static int launch_tile16(Tile16Args<F, A> a, int dir, int sign, int minWaves, hipStream_t stream) {
-  const int items = a.npc * a.nslot;
-  const int waves = std::max(minWaves, (items + 1) / 2);
-  const int nthreads = 64 * waves;
-  const int phl = (a.np * kT16Row + nthreads - 1) / nthreads;
-  const int PHLsel = phl <= 2 ? 2 : (phl <= 4 ? 4 : 8);
-  // global -> LDS staging with three buffers: fp64 FLOAT2 storage (MUGIQ_HIP_TILE16_GLDS=0: register staging, two buffers)
-  bool glds = std::is_same<F, double>::value && ORDER == 2 && 3 * sizeof(Cplx<F>) * (size_t)PHLsel * nthreads <= 160 * 1024;
-  if (const char *e = getenv("MUGIQ_HIP_TILE16_GLDS")) glds = glds && atoi(e) != 0;
-  const size_t shmem = (glds ? 3 : 2) * sizeof(Cplx<F>) * (size_t)PHLsel * nthreads;
+// g: tile16_launch_geometry of this launch (csrc/fused_form.cpp)
+template <typename F, typename A, int ORDER> static int launch_tile16(Tile16Args<F, A> a, int dir, int sign, const Tile16Launch &g, hipStream_t stream) {
+  const int PHLsel = g.phlSel;
+  const bool glds = g.glds;  // global -> LDS staging with three buffers, else register staging with two
+  const size_t shmem = g.ldsBytes;
   unsigned nblocks = dir == 0 ? (unsigned)(a.volumeCB / (a.m * kT16Cols)) : (unsigned)(((a.numCols + kT16Cols - 1) / kT16Cols) * a.jtCount);
-  a.blockOrder = 2;
-  if (const char *e = getenv("MUGIQ_HIP_TILE_ORDER")) a.blockOrder = atoi(e) & 2;
-  if (nblocks % 8 != 0) a.blockOrder = 0;
-  const dim3 grid(nblocks), block(nthreads);
+  a.blockOrder = g.block_order(nblocks);
+  const dim3 grid(nblocks), block(64 * g.waves);
 #define MUGIQ_T16_LAUNCH(D, S, P) \
   if constexpr (std::is_same<F, double>::value && ORDER == 2) { \
     if (glds) MUGIQ_T16_LAUNCH_G(D, S, P, true) else MUGIQ_T16_LAUNCH_G(D, S, P, false) \
@@ -478,53 +407,35 @@ template <typename F, typename A, int ORDER> static int launch_tile16(Tile16Args
 }
 
 template <typename F, typename A, int ORDER>
-int tile16_entry(void *loop_d, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d, const int *kvals,
-                 int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers, int region, hipStream_t stream) {
-  const size_t ptr_bytes = sizeof(void *) * (size_t)nVec;
-  std::vector<unsigned char> host(ptr_bytes + sizeof(A) * (size_t)nVec);
-  const void **hl = reinterpret_cast<const void **>(host.data());
-  A *hs = reinterpret_cast<A *>(host.data() + ptr_bytes);
-  for (int n = 0; n < nVec; n++) {
-    hl[n] = ev[n].data;
-    const F sg = static_cast<F>(sigma[n]);
-    hs[n] = static_cast<A>(1.0 / sg);
-  }
-  void *dev = nullptr;
-  int st = upload_table(&dev, host.data(), host.size(), stream);
-  if (st) return st;
+int tile16_entry(const FusedForm &form, void *loop_d, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
+                 const int *kvals, int nK, int sign, const void *ghost_d, int layers, int region, hipStream_t stream) {
+  const int dir = form.dir, partitioned = form.partitioned;
   Tile16Args<F, A> a;
+  const void *invSigma = nullptr;
+  int st = upload_vector_table(&a.L, &invSigma, ev, nullptr, sigma, nVec, (int)sizeof(F), (int)sizeof(A), stream);
+  if (st) return st;
   a.slot_stride = (int64_t)16 * 2 * ev[0].volumeCB;
-  a.L = reinterpret_cast<const void *const *>(dev);
-  a.inv_sigma = reinterpret_cast<const A *>(static_cast<unsigned char *>(dev) + ptr_bytes);
+  a.inv_sigma = static_cast<const A *>(invSigma);
   a.nVec = nVec;
-  long long strideMu = 1;
-  for (int d = 0; d < 4; d++) {
-    a.X[d] = ev[0].X[d];
-    if (d < dir) strideMu *= ev[0].X[d];
-  }
-  strideMu /= 2;
+  for (int d = 0; d < 4; d++) a.X[d] = ev[0].X[d];
   a.volumeCB = ev[0].volumeCB;
   a.stride = ev[0].stride;
   a.parity_offset = ev[0].parity_offset;
   a.partitioned = partitioned;
   a.ghost = static_cast<const F *>(ghost_d);
-  a.faceCB = ev[0].volumeCB / ev[0].X[dir];
-  a.ghost_vec_stride = (int64_t)layers * 24 * a.faceCB;
-  if (dir == 0) strideMu = 1;  // unused by the row tile
-  a.strideMu = (int)strideMu;
-  a.H = (int)(ev[0].volumeCB / (ev[0].X[dir] * strideMu));
-  a.numCols = 2 * ev[0].volumeCB / ev[0].X[dir];
-  const int tj = t16_tj();
+  const LineGeometry lines = line_geometry(ev[0], dir, layers);
+  a.faceCB = lines.faceCB;
+  a.ghost_vec_stride = lines.ghost_vec_stride;
+  a.strideMu = lines.strideMu;
+  a.H = lines.H;
+  a.numCols = lines.numCols;
+  const int tj = form.sw.tile16Tj;
   a.tj = tj;
   const int nJT = dir == 0 ? 1 : ev[0].X[dir] / tj;
   a.overwrite = (region & MUGIQ_HIP_REGION_OVERWRITE) ? 1 : 0;
   region &= 0xff;
-  int kmaxAll = 0;
-  for (int i = 0; i < nK; i++) kmaxAll = std::max(kmaxAll, kvals[i]);
-  Tile16Plan plan;
-  MUGIQ_REQUIRE(tile16_plan(ev[0], dir, kmaxAll, partitioned, plan), "displacedLoopContraction: the 16-line tile does not apply (internal)");
-  for (int k0 = 0; k0 < nK; k0 += plan.maxSlots) {
-    a.nslot = std::min(nK - k0, plan.maxSlots);
+  for (int k0 = 0; k0 < nK; k0 += form.slotsPerLaunch) {
+    a.nslot = std::min(nK - k0, form.slotsPerLaunch);
     a.loop = static_cast<Cplx<A> *>(loop_d) + (int64_t)k0 * a.slot_stride;
     a.kmax = 0;
     for (int s = 0; s < kT16MaxSlots; s++) {
@@ -533,26 +444,13 @@ int tile16_entry(void *loop_d, const MugiqHipSpinorField *ev, const double *sigm
       a.k[s] = kvals[i];
       if (s < a.nslot && kvals[i] > a.kmax) a.kmax = kvals[i];
     }
-    a.m = plan.m;
-    a.npc = plan.npc;
-    a.np = dir == 0 ? plan.np : tj + a.kmax;
-    // region 0: everything | 1: tiles whose shifted reads stay inside the local lattice | 2: tiles that read ghost layers
-    a.jtBegin = 0;
-    a.jtCount = nJT;
-    if (region != MUGIQ_HIP_REGION_ALL && dir >= 1) {
-      const int nb = partitioned ? std::min(nJT, (a.kmax + tj - 1) / tj) : 0;  // boundary tiles
-      if (region == MUGIQ_HIP_REGION_INTERIOR) {
-        a.jtBegin = sign == MUGIQ_HIP_DISP_SIGN_PLUS ? 0 : nb;
-        a.jtCount = nJT - nb;
-      } else {
-        a.jtBegin = sign == MUGIQ_HIP_DISP_SIGN_PLUS ? nJT - nb : 0;
-        a.jtCount = nb;
-      }
-    } else if (region == MUGIQ_HIP_REGION_BOUNDARY) {
-      a.jtCount = 0;  // the row tile (x, never partitioned here) has no boundary part
-    }
+    const Tile16Launch g = tile16_launch_geometry(form, a.nslot, a.kmax);
+    a.m = g.m;
+    a.npc = g.npc;
+    a.np = g.np;
+    tile_range(region, partitioned, sign, nJT, a.kmax, tj, a.jtBegin, a.jtCount);
     if (a.jtCount > 0) {
-      st = launch_tile16<F, A, ORDER>(a, dir, sign, plan.minWaves, stream);
+      st = launch_tile16<F, A, ORDER>(a, dir, sign, g, stream);
       if (st) return st;
     }
   }
@@ -560,8 +458,8 @@ int tile16_entry(void *loop_d, const MugiqHipSpinorField *ev, const double *sigm
 }
 
 #define MUGIQ_T16_INST(F, A, O)                                                                                                    \
-  template int tile16_entry<F, A, O>(void *, const MugiqHipSpinorField *, const double *, int, const void *const *, const int *, int, \
-                                     int, int, int, const void *, int, int, hipStream_t);
+  template int tile16_entry<F, A, O>(const FusedForm &, void *, const MugiqHipSpinorField *, const double *, int, const void *const *, const int *, \
+                                     int, int, const void *, int, int, hipStream_t);
 MUGIQ_T16_INST(double, double, 2)
 MUGIQ_T16_INST(double, double, 4)
 MUGIQ_T16_INST(float, float, 2)

@@ -3,6 +3,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "internal.h"
 
@@ -117,6 +118,25 @@ int upload_table(void **dev_out, const void *host, size_t bytes, hipStream_t str
   MUGIQ_CHECK_HIP(hipMemcpyAsync(a.tab, a.pinned[i], bytes, hipMemcpyHostToDevice, stream));
   MUGIQ_CHECK_HIP(hipEventRecord(a.staged[i], stream));
   *dev_out = a.tab;
+  return MUGIQ_HIP_SUCCESS;
+}
+
+int upload_vector_table(const void *const **L, const void **invSigma, const MugiqHipSpinorField *ev, const MugiqHipSpinorField *evL,
+                        const double *sigma, int nVec, int sigmaPrecision, int tablePrecision, hipStream_t stream) {
+  const size_t ptr_bytes = sizeof(void *) * (size_t)nVec * (evL ? 2 : 1);
+  std::vector<unsigned char> host(ptr_bytes + (size_t)tablePrecision * nVec);
+  const void **hl = reinterpret_cast<const void **>(host.data());
+  for (int n = 0; n < nVec; n++) {
+    hl[n] = ev[n].data;
+    if (evL) hl[nVec + n] = evL[n].data;
+    const double inv = 1.0 / (sigmaPrecision == 4 ? (double)static_cast<float>(sigma[n]) : sigma[n]);
+    if (tablePrecision == 4) reinterpret_cast<float *>(host.data() + ptr_bytes)[n] = static_cast<float>(inv);
+    else reinterpret_cast<double *>(host.data() + ptr_bytes)[n] = inv;
+  }
+  void *dev = nullptr;
+  if (int st = upload_table(&dev, host.data(), host.size(), stream)) return st;
+  *L = reinterpret_cast<const void *const *>(dev);
+  *invSigma = static_cast<unsigned char *>(dev) + ptr_bytes;
   return MUGIQ_HIP_SUCCESS;
 }
 

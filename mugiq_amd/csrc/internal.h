@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "fused_form.h"
 #include "mugiq_hip.h"
 
 namespace mugiq {
@@ -33,6 +34,10 @@ int set_error(int status, const char *fmt, ...);
 int stream_scratch(void **ptr, size_t bytes, hipStream_t stream);
 int stream_workspace(void **ptr, size_t bytes, hipStream_t stream);
 int upload_table(void **dev, const void *host, size_t bytes, hipStream_t stream);
+// ... the table every fused entry reads: the bodies of ev[0 .. nVec) (then, two-sided, of evL), and behind them 1/sigma as float or
+// double (tablePrecision 4 | 8).  sigmaPrecision 4: sigma rounded to float before it is inverted (the vector kernels over fp32 storage)
+int upload_vector_table(const void *const **L, const void **invSigma, const MugiqHipSpinorField *ev, const MugiqHipSpinorField *evL,
+                        const double *sigma, int nVec, int sigmaPrecision, int tablePrecision, hipStream_t stream);
 // a third buffer of the arena, for the Wilson operator (csrc/wilson.hip): intermediate and solver vectors that must survive the
 // calls of the deflation and halo code in between, which use stream_workspace themselves
 int stream_operator_workspace(void **ptr, size_t bytes, hipStream_t stream);
@@ -45,13 +50,9 @@ int fill_identity_links(const MugiqHipSpinorField *f, hipStream_t stream);  // d
 int debug_poison_lds_if_asked(hipStream_t stream);
 // csrc/fused_mfma.hip.  The axial gauge of a (direction, sign) is rebuilt by every call of the matrix-pipe tile (one pass over
 // W_1, 0.2 ms) -- unless the caller, who calls the same entry several times (the driver: interior tiles, then the boundary tiles
-// block by block), has built it once and hands it over (FusedEntryPlan::axialGauge): axial_gauge_bytes = 0 where that tile does
-// not apply.
-size_t axial_gauge_bytes(const MugiqHipSpinorField &ev, int dir, const int *kvals, int nK, int partitioned);
+// block by block), has built it once and hands it over (FusedEntryPlan::axialGauge; FusedForm::gaugeBytes large).
 int build_axial_gauge(void *G_d, const MugiqHipSpinorField &ev, const void *const *E_d, int kmax, int dir, int sign, hipStream_t stream);
-// ... straight from the gauge field (no path-link fields needed at all): along a direction that is not partitioned, or as far as the border
-// of the extended field reaches along a partitioned one
-bool axial_gauge_from_links_possible(const MugiqHipSpinorField &ev, const MugiqHipGaugeField &U, int kmax, int dir, int sign);
+// ... straight from the gauge field (no path-link fields needed at all): where axial_gauge_from_links_possible (csrc/fused_form.h)
 int build_axial_gauge_from_links(void *G_d, const MugiqHipSpinorField &ev, const MugiqHipGaugeField &U, int kmax, int dir, int sign, hipStream_t stream);
 // The tile is exact only where g^dag g = 1.  axial_gauge_tolerance: the largest deviation max |g^dag g - 1| it is taken with
 // (per storage precision).  axial_line_deviation: the driver's pre-pass, D[mu] over the lines of the local gauge field out to reach[mu]
@@ -79,21 +80,21 @@ struct FusedEntryPlan {
                                      // -1 no decision (a free call: fused_entry checks the gauge of W_1 .. W_kmax itself)
   const void *axialGauge = nullptr;  // the gauge the caller built for (dir, sign, kmax of the call): the tile must take the call, and the
                                      // link fields are not read (pathLinkFields_h may be NULL)
-  const EntryPackTarget *pack = nullptr;  // face layers for the first launch of the row tile to write (at most entry_pack_capacity)
+  const EntryPackTarget *pack = nullptr;  // face layers for the first launch of the row tile to write (at most FusedForm::packCapacity)
   int nPack = 0;
   bool *packed = nullptr;  // with pack: set once a launch has taken the targets (later calls of the entry leave them alone)
+  const FusedForm *form = nullptr;  // the kernel form the driver's plan chose for the entry (NULL: fused_entry selects)
 };
-// The matrix-pipe tile (fourth generation, any storage type, ascending lengths up to 8).  two: the two-sided tile (left set evL != NULL
-// in mfma_tile_entry; no 12-position column tile, 8-wave row tile only).  G_d: the axial gauge of the call (NULL: built here from
-// E_d); pack / nPack / packed: as in FusedEntryPlan
-bool mfma_tile_applicable(const MugiqHipSpinorField &ev, int dir, const int *kvals, int nK, int partitioned, bool gaugeGiven, bool two = false);
-int mfma_tile_entry(void *loop_d, int loopPrecision, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
-                    const int *kvals, int nK, int dir, int sign, int partitioned, const void *ghost_d, int layers, int region,
+// The matrix-pipe tile (fourth generation, any storage type, ascending lengths up to 8) of an entry whose form is one.  evL != NULL: the
+// two-sided tile (no 12-position column tile, 8-wave row tile only).  G_d: the axial gauge of the call (NULL: built here from E_d);
+// pack / nPack / packed: as in FusedEntryPlan
+int mfma_tile_entry(const FusedForm &form, void *loop_d, const MugiqHipSpinorField *ev, const double *sigma, int nVec, const void *const *E_d,
+                    const int *kvals, int nK, int sign, const void *ghost_d, int layers, int region,
                     hipStream_t stream, void *ultra_d, int *carried, const MugiqHipSpinorField *evL, const void *G_d,
                     const EntryPackTarget *pack, int nPack, bool *packed);
 // csrc/fused.hip: what mugiq_hip_displaced_loop_contraction_fused_carry (eVecL_h = NULL) and ..._fused_two_sided do, and which kernel
 // did it (*kernel = MUGIQ_HIP_ENTRY_KERNEL_*; may be NULL).  The two-sided form runs on the matrix-pipe tile only: where that does not
-// apply it fails with MUGIQ_HIP_ERROR_UNSUPPORTED (the driver checks mfma_tile_applicable first and takes the step-by-step sequence)
+// apply it fails with MUGIQ_HIP_ERROR_UNSUPPORTED (the driver's plan asks select_fused_form first and takes the step-by-step sequence)
 int fused_contraction(void *loopData_d, int loopPrecision, const MugiqHipSpinorField *eVecL_h, const MugiqHipSpinorField *eVecR_h,
                       const double *sigma_h, int nVec, const void *const *pathLinkFields_h, const int *kValues_h, int nK, int dispDir,
                       int dispSign, const int commDim[4], const void *ghostLayers_d, int layers, int region, void *ultraLocalSlot_d,
@@ -102,7 +103,6 @@ int fused_contraction(void *loopData_d, int loopPrecision, const MugiqHipSpinorF
 int deflate_low_modes(const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int nVec, const MugiqHipSpinorField *ev,
                       const double *sigma, int nEv, int gamma5, double *overlaps_h, const MugiqHipComm *comm, hipStream_t stream,
                       const char *who);
-int entry_pack_capacity(const MugiqHipSpinorField &ev, const int *kvals, int nK);
 // csrc/wilson.hip: the gauge field of an operator call against the local dims X and the partitioned axes; comm -> part[4]
 int check_gauge(const MugiqHipGaugeField *U, const int X[4], const int part[4], const char *who);
 int check_comm(const MugiqHipComm *comm, int part[4], bool needSums, const char *who);

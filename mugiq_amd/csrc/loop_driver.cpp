@@ -519,8 +519,8 @@ static int entry_fused(MugiqHipLoop *lp, int id, void *slot0, int part_sel = 0, 
   const std::vector<MugiqHipSpinorField> &E = e.ahead ? lp->halo[id].E : Elocal;
   std::vector<const void *> links;  // W_start .. W_stop (none: the gauge came straight from the gauge field)
   for (int k = start; k <= stop && !E.empty(); k++) links.push_back(E[k].data);
-  // the tile only if the pre-pass allowed it
-  const FusedEntryPlan plan{e.tile, e.ahead ? lp->halo[id].axialGauge : gauge, pack, nPack, packed};
+  // the kernel form the plan chose (the tile only if the pre-pass allowed it): the fused calls do not select a second time
+  const FusedEntryPlan plan{e.tile, e.ahead ? lp->halo[id].axialGauge : gauge, pack, nPack, packed, &e.form};
   auto fused = [&](int n0, int nv, const void *ghost, int region, void *ultra, int *carried) {
     return fused_contraction(slot0, lp->loopPrecision, evL ? evL + n0 : nullptr, &lp->eVecs[n0], &lp->sigma[n0], nv,
                              links.empty() ? nullptr : links.data(), e.kv.data(), e.nK, dir, sign, lp->commDim, ghost, ghost ? stop : 0,

@@ -24,7 +24,7 @@ bool fused_projection_applies(int loopPrecision, const int localL[4], int nData,
 }
 
 // One OPT entry.  budget: what is left of the quarter of the device memory the ghost-layer buffers posted ahead may take.
-static void plan_opt_entry(const LoopPlanInput &in, LoopPlan &P, int id, size_t &budget) {
+static void plan_opt_entry(const LoopPlanInput &in, LoopPlan &P, int id, size_t &budget, const FusedSwitches &sw) {
   EntryPlan &e = P.entry[id];
   const MugiqHipSpinorField &ev = *in.ev;
   const int dir = in.dir[id], sign = in.sign[id], start = in.start[id], stop = in.stop[id];
@@ -35,18 +35,20 @@ static void plan_opt_entry(const LoopPlanInput &in, LoopPlan &P, int id, size_t 
   if (!in.twoSided && !past && !env_is("MUGIQ_HIP_REFLECT", true))
     for (int jd = 0; jd < id && e.derivedFrom < 0; jd++)
       if (in.dir[jd] == dir && in.sign[jd] != sign && in.start[jd] <= start && stop <= in.stop[jd] && P.entry[jd].derivedFrom < 0) e.derivedFrom = jd;
-  e.route = MUGIQ_HIP_LOOP_ROUTE_REFLECTED;
+  e.route = MUGIQ_HIP_LOOP_ROUTE_REFLECTED, e.kernel = MUGIQ_HIP_ENTRY_KERNEL_REFLECTED;
   if (e.derivedFrom >= 0) return;
+  // the kernel form of its fused calls (the driver holds the gauge of a matrix-pipe entry, or its lengths start at 1)
+  e.form = select_fused_form(ev, dir, e.kv.data(), e.nK, e.part, true, in.twoSided, in.loopPrecision, sw, e.tile != 0);
   // Step by step: a length past the nearest neighbour (the multi-layer halo cannot reach there, single steps can); for two-sided loops
   // also every entry the two-sided matrix-pipe tile does not take (lengths > 8, a partitioned x axis, no tile geometry, tile refused)
-  if (past || (in.twoSided && (!e.tile || !mfma_tile_applicable(ev, dir, e.kv.data(), e.nK, e.part, true, true)))) {
-    e.route = MUGIQ_HIP_LOOP_ROUTE_STEPWISE, e.needsMemset = 1;
+  if (past || e.form.family == MUGIQ_HIP_FUSED_FAMILY_NONE) {
+    e.route = MUGIQ_HIP_LOOP_ROUTE_STEPWISE, e.kernel = MUGIQ_HIP_ENTRY_KERNEL_STEPWISE, e.needsMemset = 1;
     const size_t fieldB = (size_t)2 * ev.parity_offset * 2 * (size_t)in.precision, aux = (size_t)8 << 30;  // two auxiliary fields per eigenvector
     e.blockN = (int)std::max<size_t>(1, std::min<size_t>((size_t)in.nEv, aux / (2 * fieldB)));
     e.nBlocks = ceil_div(in.nEv, e.blockN);
     return;
   }
-  e.route = MUGIQ_HIP_LOOP_ROUTE_FUSED;
+  e.route = MUGIQ_HIP_LOOP_ROUTE_FUSED, e.kernel = e.form.kernel;
   // an axis of extent 1 that is partitioned all the same: the rank is its own neighbour, the face layers are packed straight into the
   // ghost buffer -- no send buffer, no message (MUGIQ_HIP_SELF_HALO_COPY=1: keep them)
   e.selfAlias = e.part && in.haveComm && in.grid[dir] == 1 && !env_is("MUGIQ_HIP_SELF_HALO_COPY", false);
@@ -55,8 +57,8 @@ static void plan_opt_entry(const LoopPlanInput &in, LoopPlan &P, int id, size_t 
   // Its links: the axial gauge (csrc/fused_mfma.hip) straight from the gauge field where that reaches far enough -- a partitioned entry
   // only when its halo is posted -- else the path-link fields W_0 .. W_stop, and from them the gauge once for all launches of a posted
   // entry, and where the lengths do not start at 1 (the links of the call then do not hold W_1); otherwise every fused call builds its own
-  e.gaugeBytes = e.tile ? (long long)axial_gauge_bytes(ev, dir, e.kv.data(), e.nK, e.part) : 0;
-  e.gaugeFromField = e.gaugeBytes && (e.ahead || !e.part) && axial_gauge_from_links_possible(ev, *in.gauge, stop, dir, sign);
+  e.gaugeBytes = (long long)e.form.gaugeBytes;
+  e.gaugeFromField = e.gaugeBytes && (e.ahead || !e.part) && axial_gauge_from_links_possible(ev, *in.gauge, stop, dir, sign, sw);
   if (!e.gaugeFromField) {
     e.nLinkFields = stop + 1;
     e.buildGaugeFromLinks = e.gaugeBytes && (e.ahead || start > 1);
@@ -83,6 +85,7 @@ LoopPlan make_loop_plan(const LoopPlanInput &in) {
   const size_t cplx = 2 * (size_t)in.precision;
   P.entry.resize(n);
   size_t budget = env_is("MUGIQ_HIP_HALO_AHEAD", true) ? 0 : in.deviceBytes / 4;
+  const FusedSwitches sw = fused_switches_from_env();
   bool anyDerived = false;
   for (int id = 0; id < n; id++) {
     EntryPlan &e = P.entry[id];  // (zeroed by resize)
@@ -96,8 +99,8 @@ LoopPlan make_loop_plan(const LoopPlanInput &in) {
     e.faceBytes = (long long)((size_t)24 * (in.ev->volumeCB / in.ev->X[dir]) * cplx);
     e.perVecHaloBytes = in.stop[id] * e.faceBytes;  // `stop` face layers of one eigenvector
     e.haloBytes = e.perVecHaloBytes * in.nEv;
-    if (basic) e.route = MUGIQ_HIP_LOOP_ROUTE_STEPWISE, e.needsMemset = 1;  // the reference's own sequence: nothing derived, nothing posted
-    else plan_opt_entry(in, P, id, budget);
+    if (basic) e.route = MUGIQ_HIP_LOOP_ROUTE_STEPWISE, e.kernel = MUGIQ_HIP_ENTRY_KERNEL_STEPWISE, e.needsMemset = 1;  // the reference's own sequence: nothing derived, nothing posted
+    else plan_opt_entry(in, P, id, budget, sw);
     anyDerived = anyDerived || e.derivedFrom >= 0;
     P.postHalos = P.postHalos || e.ahead;
   }
@@ -132,7 +135,7 @@ LoopPlan make_loop_plan(const LoopPlanInput &in) {
   // layers itself (two-sided: pack kernels), but for the first block of a halo that really travels: that goes out ahead
   if (P.earlyEntry >= 0 && in.dir[P.earlyEntry] == 0 && in.loopPrecision == in.precision && !in.twoSided) {
     const EntryPlan &early = P.entry[P.earlyEntry];
-    P.earlyPackRoom = early.tile ? entry_pack_capacity(*in.ev, early.kv.data(), early.nK) : 0;
+    P.earlyPackRoom = early.form.packCapacity;
     for (int id = 0; id < n && (int)P.packTargets.size() < P.earlyPackRoom; id++) {
       EntryPlan &e = P.entry[id];
       const int from = e.selfAlias ? 0 : e.blockN;

@@ -26,6 +26,7 @@ struct LoopPlanInput {
 
 struct EntryPlan : MugiqHipLoopEntryPlan {  // (the members of include/mugiq_hip.h)
   std::vector<int> kv;                      // the lengths start .. stop
+  FusedForm form;                           // route FUSED: the kernel form of its fused calls (csrc/fused_form.h)
 };
 
 struct LoopPlan {

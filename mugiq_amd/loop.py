@@ -162,6 +162,33 @@ def _c_loop_param(loopParams, keep, gauge_desc=None):
     return p
 
 
+FUSED_FAMILY_NONE, FUSED_FAMILY_MFMA_COLUMN, FUSED_FAMILY_MFMA_ROW, FUSED_FAMILY_TILE32, FUSED_FAMILY_TILE16, FUSED_FAMILY_STREAMING = range(6)
+
+
+def _spinor_desc(eVec):
+    """The descriptor of a SpinorField, or of (X, precision, order[, pad]) without memory"""
+    if isinstance(eVec, SpinorField):
+        return eVec.desc()
+    X, prec, order = eVec[:3]
+    ev = _lib.SpinorDesc()
+    ev.precision, ev.field_order, ev.nParity = int(prec), int(order), 2
+    ev.volumeCB = int(np.prod(X)) // 2
+    ev.stride = ev.volumeCB + (int(eVec[3]) if len(eVec) > 3 else 0)
+    ev.parity_offset = 12 * ev.stride
+    for d in range(4):
+        ev.X[d] = int(X[d])
+    return ev
+
+
+def fusedForm(eVec, dispDir, kValues, twoSided=False, partitioned=False, gaugeGiven=True, loopPrecision=0):
+    """The kernel form a fused displaced entry runs on and the geometry of its first launch (mugiq_hip_fused_form), as a dict: what
+    the fused calls and the driver's plan select, under the same MUGIQ_HIP_* switches.  Host only; eVec as for loopPlan."""
+    ev, out = _spinor_desc(eVec), _lib.FusedForm()
+    _lib.check(_lib.load().mugiq_hip_fused_form(ctypes.byref(ev), int(bool(twoSided)), int(dispDir), (ctypes.c_int * len(kValues))(*[int(k) for k in kValues]), len(kValues),
+                                                int(bool(partitioned)), int(bool(gaugeGiven)), int(loopPrecision), ctypes.byref(out)))
+    return {n: getattr(out, n) for n, _ in _lib.FusedForm._fields_}
+
+
 def loopPlan(loopParams, eVec, nEv, comm=None, twoSided=False, coarseMode=False, axialOk=(1, 1, 1, 1), deviceBytes=0, gauge=None):
     """What computeCoarseLoop would do with every displacement entry (mugiq_hip_loop_plan): the plan the driver itself makes, as dicts.
     Host only, no GPU is touched, so descriptors will do: eVec a SpinorField or (X, precision, order[, pad]); gauge (default
@@ -169,17 +196,7 @@ def loopPlan(loopParams, eVec, nEv, comm=None, twoSided=False, coarseMode=False,
     transport has group_begin / group_end).  axialOk: the outcome of the unitarity pre-pass per direction; deviceBytes: the device's
     total memory."""
     keep = []
-    if isinstance(eVec, SpinorField):
-        ev = eVec.desc()
-    else:
-        X, prec, order = eVec[:3]
-        ev = _lib.SpinorDesc()
-        ev.precision, ev.field_order, ev.nParity = int(prec), int(order), 2
-        ev.volumeCB = int(np.prod(X)) // 2
-        ev.stride = ev.volumeCB + (int(eVec[3]) if len(eVec) > 3 else 0)
-        ev.parity_offset = 12 * ev.stride
-        for d in range(4):
-            ev.X[d] = int(X[d])
+    ev = _spinor_desc(eVec)
     gauge = loopParams.gauge if gauge is None else gauge
     g = None
     if gauge is not None and not isinstance(gauge, GaugeField):

@@ -423,11 +423,8 @@ def plan_worker(rank, world, port, G, case, alloc_first, alloc_second):
     print("plan", plan, "\nscratch_alloc (first)", [int(p["bytes"]) for p in phases if p["kind"] == "scratch_alloc"], flush=True)
     E, n = plan["entries"], len(disp[0])
     assert [loop.derivedFrom(i) for i in range(n)] == [e["derivedFrom"] for e in E]
-    tiles = (hip.ENTRY_KERNEL_MFMA_ROW, hip.ENTRY_KERNEL_MFMA_COLUMN)
     for i, e in enumerate(E):
-        want = {0: (hip.ENTRY_KERNEL_REFLECTED,), 1: (hip.ENTRY_KERNEL_STEPWISE,),
-                2: tiles if e["tile"] and e["gaugeBytes"] > 0 else (hip.ENTRY_KERNEL_VECTOR_TILE, hip.ENTRY_KERNEL_STREAMING)}[e["route"]]
-        assert loop.entryKernel(i) in want, (i, loop.entryKernel(i), e)
+        assert loop.entryKernel(i) == e["kernel"], (i, loop.entryKernel(i), e)
     assert loop.halosPackedInEntry() == len(plan["entryPacksFrom"])
     assert {p["entry"] for p in phases if p["kind"] == "entry_interior"} == {i for i, e in enumerate(E) if e["route"] == 2 and e["part"]}
     _check_pos(orc, comm.coord, (1, 1, 1, 1), G, G, cprm, loop.dataPos_d.cpu().numpy().astype(np.complex128), pos_g, 1e-12)

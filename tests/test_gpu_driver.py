@@ -27,6 +27,14 @@ def _setup(hip, X, nev, prec, order, seed, pad=0, gpad=0):
     return ev, Uo, f, U
 
 
+def _assert_plan_names_kernels(hip, loop, prm, f0, nev):
+    """Every entry of the compute ran on the kernel the plan names under the same environment (a random SU(3) gauge passes the
+    unitarity pre-pass along every direction)."""
+    E = hip.loopPlan(prm, f0, nev, axialOk=(1, 1, 1, 1), deviceBytes=torch.cuda.mem_get_info(0)[1])["entries"]
+    got = [loop.entryKernel(i) for i in range(len(E))]
+    assert got == [e["kernel"] for e in E], (got, E)
+
+
 @pytest.mark.parametrize("prec,order", [(8, 2), (4, 4)])
 def test_reference_loop_nest_through_displace_class(hip, prec, order):
     """The loop nest of Loop_Mugiq::computeCoarseLoop (lib/loop_mugiq.cpp:455-509) written down call for call with the
@@ -535,6 +543,7 @@ def test_fused_plans_agree_tiled_and_streaming(hip, tile, X, monkeypatch):
     _, s, a, b = orc.parse_disp_entry_string(entry)
     ref = orc.compute_loop_position_space(ev, sg, orc.LoopComputeParam(s, a, b), Uo, X)
     assert rel_err(loop.dataPos_d.cpu().numpy(), ref) < 1e-12
+    _assert_plan_names_kernels(hip, loop, prm, f[0], nev)
     loop.close()
 
 
@@ -588,6 +597,7 @@ def test_driver_random_shapes_both_fused_plans(hip, seed, monkeypatch, record_ma
         loop.computeCoarseLoop()
         err = rel_err(loop.dataPos_d.cpu().numpy(), ref)
         err_mom = rel_err(loop.dataMom_bcast, ref_mom)
+        _assert_plan_names_kernels(hip, loop, prm, f[0], nev)
         loop.close()
         record_max("driver_sweep_pos_%s" % tag, err)
         record_max("driver_sweep_mom_%s" % tag, err_mom)
@@ -793,11 +803,13 @@ def test_axial_gauge_matrix_pipe_tile_geometries(hip, monkeypatch):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
-        loop = hip.Loop_Mugiq(hip.MugiqLoopParam(gauge=U).set_displace_entry_string(entry), f, sg)
+        prm = hip.MugiqLoopParam(gauge=U).set_displace_entry_string(entry)
+        loop = hip.Loop_Mugiq(prm, f, sg)
         loop.computeCoarseLoop()
         tag = "%s=%s" % next(iter(env.items()))
         got[tag] = loop.dataPos_d.cpu().numpy()
         assert rel_err(got[tag], ref) < 1e-12, tag
+        _assert_plan_names_kernels(hip, loop, prm, f[0], nev)
         if "CARRY" not in tag and "TILE_MFMA" not in tag:
             assert loop.ultraLocalCarrier() >= 0, tag          # an unpartitioned column entry took the ultra-local loop along
         loop.close()

@@ -8,6 +8,7 @@ from util import momenta_p2_le
 
 GiB = 1 << 30
 REFLECTED, STEPWISE, FUSED = 0, 1, 2
+K_REFLECTED, K_MFMA_COLUMN, K_MFMA_ROW, K_VECTOR_TILE, K_STREAMING, K_STEPWISE = range(6)      # MUGIQ_HIP_ENTRY_KERNEL_*
 CFG2 = "+x:1,3;-x:1,3;+y:1,3;-y:1,3;+z:1,3;-z:1,3;+t:1,3;-t:1,3"
 X_CFG2 = (48, 48, 24, 24)
 HALO_CFG2 = 3 * 24 * 27648 * 16 * 400          # stop * 24 * faceCB * sizeof(complex double) * nEv = 12,740,198,400
@@ -18,7 +19,8 @@ GAUGE_X = 9 * 51 * 27648 * 16                  # 203,046,912
 @pytest.fixture(autouse=True)
 def _no_switches(monkeypatch):
     for k in ("HALO_AHEAD", "REFLECT", "REFLECT_MOM", "SELF_HALO_COPY", "HALO_BLOCKS", "CARRY_ULTRALOCAL", "TILE_MFMA", "FUSED_TILE",
-              "TILE_COLS", "TILE_GLDS", "MFMA_STORAGE", "MFMA_ROW", "MFMA_ROW_WAVES", "PACK_IN_ENTRY", "GAUGE_FROM_LINKS"):
+              "TILE_COLS", "TILE_GLDS", "MFMA_STORAGE", "MFMA_ROW", "MFMA_ROW_WAVES", "PACK_IN_ENTRY", "GAUGE_FROM_LINKS", "MFMA_TJ",
+              "TILE16_TJ"):
         monkeypatch.delenv("MUGIQ_HIP_" + k, raising=False)
 
 
@@ -55,6 +57,8 @@ def test_configs2_as_one_gpu_sees_it(hip):
     E = p["entries"]
     assert [e["derivedFrom"] for e in E] == [-1, 0, -1, 2, -1, 4, -1, 6]
     assert [e["route"] for e in E] == [FUSED, REFLECTED] * 4
+    # X0 = 48: rows of 24 entries, 2 per 8-wave workgroup; 8 | 48 and 8 | 24: the 8 x 16 column tile (8 + 3 <= 16 positions)
+    assert [e["kernel"] for e in E] == [K_MFMA_ROW, K_REFLECTED] + [K_MFMA_COLUMN, K_REFLECTED] * 3
     assert [i for i, e in enumerate(E) if e["ahead"]] == [4, 6]
     for i in (4, 6):
         assert E[i]["haloBytes"] == HALO_CFG2 == 12740198400 and E[i]["perVecHaloBytes"] * 400 == HALO_CFG2
@@ -96,6 +100,9 @@ def test_own_neighbour_needs_one_halo_buffer(hip, monkeypatch):
         assert E[1]["haloBytes"] == E[2]["haloBytes"] == 2 * 24 * 64 * 16 * 4 == 24 * 512 * 16          # as large as a link field
         assert p["reserve"] == _reserve_of(p, X)
         assert p["earlyEntry"] == 0 and E[0]["high"] == 0 and E[2]["high"] == 1
+        # X0 = 4: rows of 2 entries, no matrix-pipe row tile (2 % 4), 16 rows fill a 32-line position; 8 | 8 along z, t; "+y:2" on
+        # Y = 4 takes the 4 x 32 tile (4 + 2 <= 8) with the driver's gauge
+        assert [e["kernel"] for e in E] == [K_VECTOR_TILE, K_MFMA_COLUMN, K_MFMA_COLUMN, K_MFMA_COLUMN, K_REFLECTED]
         lens.append(len(p["reserve"]))
     assert lens[1] == lens[0] + 2                                   # one more buffer for each of the two posted entries
 
@@ -117,6 +124,7 @@ def test_past_the_neighbour_goes_step_by_step(hip):
     p = _plan(hip, "+t:1,5;-t:1,5", (4, 4, 4, 4), 3, grid=(1, 1, 1, 4), R=(0, 0, 0, 2))
     for e in p["entries"]:
         assert (e["route"], e["derivedFrom"], e["ahead"], e["needsMemset"], e["nLinkFields"]) == (STEPWISE, -1, 0, 1, 0)
+        assert e["kernel"] == K_STEPWISE
     assert p["order"] == [0, 1, -1] and p["reserve"] == [] and p["momReflect"] == 0
 
 
@@ -125,23 +133,26 @@ def test_tile_refused_along_z(hip):
     E = p["entries"]
     assert all((E[i]["tile"], E[i]["gaugeBytes"]) == (0, 0) for i in (4, 5)) and E[4]["nLinkFields"] == 4
     assert E[4]["route"] == FUSED and E[4]["ahead"] == 1 and E[6]["gaugeFromField"] == 1
+    assert [e["kernel"] for e in E] == [K_MFMA_ROW, K_REFLECTED, K_MFMA_COLUMN, K_REFLECTED, K_VECTOR_TILE, K_REFLECTED, K_MFMA_COLUMN, K_REFLECTED]
     assert p["reserve"] == [24 * 663552 * 16] * 4 + [24 * 27648 * 16] * 2 + [HALO_CFG2] * 2 + [HALO_CFG2, HALO_CFG2, GAUGE_ZT, GAUGE_X]
     p = _cfg2(hip, axialOk=(1, 1, 0, 1), twoSided=True)
     E = p["entries"]
     assert all(e["derivedFrom"] == -1 for e in E) and p["momReflect"] == 0
     assert [E[i]["route"] for i in (4, 5)] == [STEPWISE, STEPWISE] and all(E[i]["needsMemset"] and not E[i]["ahead"] for i in (4, 5))
+    assert [e["kernel"] for e in E] == [K_MFMA_ROW] * 2 + [K_MFMA_COLUMN] * 2 + [K_STEPWISE] * 2 + [K_MFMA_COLUMN] * 2
 
 
 def test_two_sided_length_nine_goes_step_by_step(hip):
     p = _plan(hip, "+z:1,9", (8, 8, 16, 8), 4, twoSided=True)
-    assert p["entries"][0]["route"] == STEPWISE and p["entries"][0]["needsMemset"] == 1
-    assert _plan(hip, "+z:1,8", (8, 8, 16, 8), 4, twoSided=True)["entries"][0]["route"] == FUSED
+    assert p["entries"][0]["route"] == STEPWISE and p["entries"][0]["needsMemset"] == 1 and p["entries"][0]["kernel"] == K_STEPWISE
+    e = _plan(hip, "+z:1,8", (8, 8, 16, 8), 4, twoSided=True)["entries"][0]
+    assert e["route"] == FUSED and e["kernel"] == K_MFMA_COLUMN                                # 8 | 16, 8 + 8 <= 16 positions
 
 
 def test_basic_keeps_the_reference_order(hip):
     p = _cfg2(hip, calcType=hip.LOOP_CALC_TYPE_BASIC_KERNEL)
     assert p["order"] == [-1, 0, 1, 2, 3, 4, 5, 6, 7] and p["earlyEntry"] == -2 and p["reserve"] == []
-    assert all((e["derivedFrom"], e["ahead"], e["needsMemset"], e["route"]) == (-1, 0, 1, STEPWISE) for e in p["entries"])
+    assert all((e["derivedFrom"], e["ahead"], e["needsMemset"], e["route"], e["kernel"]) == (-1, 0, 1, STEPWISE, K_STEPWISE) for e in p["entries"])
     assert (p["carryUltra"], p["momReflect"], p["grouped"]) == (0, 0, 0)
 
 
@@ -152,6 +163,7 @@ def test_pack_targets_of_the_early_entry(hip, monkeypatch):
     kw = dict(grid=(1, 1, 1, 1), partitioned=(0, 0, 1, 1), R=(0, 0, 2, 2))
     p = _plan(hip, ent, (8, 16, 8, 8), 4, **kw)
     assert p["earlyEntry"] == 0 and p["entryPacksFrom"] == [1, 2, 3, 4] and all(p["entries"][i]["entryPacksFrom"] == 0 for i in (1, 2, 3, 4))
+    assert [e["kernel"] for e in p["entries"]] == [K_MFMA_ROW] + [K_MFMA_COLUMN] * 5     # X0 = 8: 8 rows of 4 entries per 8-wave workgroup
     monkeypatch.setenv("MUGIQ_HIP_SELF_HALO_COPY", "1")            # one block per halo: from = blockN = nEv
     p = _plan(hip, ent, (8, 16, 8, 8), 4, **kw)
     assert p["entryPacksFrom"] == [] and all(e["entryPacksFrom"] == -1 for e in p["entries"])

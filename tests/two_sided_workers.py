@@ -12,8 +12,8 @@ DEFAULT_SEEDS = 24                     # test_two_sided_random_shapes; MUGIQ_TES
 EXTENTS = (2, 4, 6, 8, 12, 16, 24)
 
 # ---- the single-domain decision of the OPT plan for a two-sided entry, restated from the C++:
-#   loop_plan.cpp plan_opt_entry -> fused_mfma.hip mfma_tile_applicable(..., two = true) -> mfma_tile_tj / mfma_row_geometry
-# (constants of fused_mfma_kernel.h: kMT_MaxLength = 8, kMT_MaxSlots = 4, kMT_BufElems = 4 * 12 * 68).  No MUGIQ_HIP_* switch set.
+#   loop_plan.cpp plan_opt_entry -> fused_form.cpp select_fused_form(..., two = true) -> mfma_tile_tj / mfma_row_geometry
+# (constants of fused_form.h: kMT_MaxLength = 8, kMT_MaxSlots = 4, kMT_BufElems = 4 * 12 * 68).  No MUGIQ_HIP_* switch set.
 KMT_MAX_LENGTH = 8
 KMT_BUF_ELEMS = 4 * 12 * 68
 
