@@ -411,6 +411,21 @@ int mugiq_hip_prolongate_contract_batched(void *loopData_d, int loopPrecision, c
                                           const double *sigma_h, int nVec, const MugiqHipTransfer *transfer,
                                           void *stream);
 
+/* ---- restriction R = P^dag (new): QUDA's Transfer::R, the adjoint of Transfer::P above.  The reference never calls it itself: its
+ * computeCoarse mode (lib/eigsolve_mugiq.cpp:27-33) works on mg_env->diracCoarse, which QUDA builds from it. ------------------------ */
+/* coarse_h[n](X; S, j) = sum_{x in aggregate X} sum_{s: s/spinBlockSize = S} sum_c conj(V(x; s, c, j)) g(s) fine_h[n](x; s, c) for all
+ * n < nVec; g = 1, or for gamma5 != 0 the diagonal of g5 = Gamma_15 (mugiq_hip_get_gamma_tables).  Layouts, aggregate map and the
+ * checks on `transfer` are those of mugiq_hip_prolongate_batched.  fine_h: one precision (4 | 8), FLOAT2 | FLOAT4, any stride; V and
+ * the coarse fields share the transfer's precision, which may differ from the fine one.  Products and sums in fp64, one rounding on
+ * the store, no atomics, a summation order fixed by the transfer alone: bitwise reproducible, and a vector restricted alone equals
+ * the same vector restricted in any batch.  V is read once per block of 8 vectors. */
+int mugiq_hip_restrict_batched(const MugiqHipCoarseField *coarse_h, const MugiqHipSpinorField *fine_h, int nVec,
+                               const MugiqHipTransfer *transfer, int gamma5, void *stream);
+/* The adjoint of mugiq_hip_prolongate_coarse_batched for one COARSE -> COARSE level (`transfer` as described there):
+ * coarser_h[n](X; s, j) = sum_{x in X} sum_c conj(V(x; s, c, j)) finer_h[n](x; s, c).  Same numerics as above. */
+int mugiq_hip_restrict_coarse_batched(const MugiqHipCoarseField *coarser_h, const MugiqHipCoarseField *finer_h, int nVec,
+                                      const MugiqHipTransfer *transfer, void *stream);
+
 /* ==== host-side driver: the Loop_Mugiq / Displace classes of the reference ========================================= */
 
 /* include/enum_mugiq.h:35-41.  calcType is parsed but never read by the reference's live code; here it selects
@@ -510,6 +525,20 @@ int mugiq_hip_exchange_ghost_vec(const MugiqHipSpinorField *v, const MugiqHipCom
 int mugiq_hip_deflate_low_modes(const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec,
                                 const MugiqHipSpinorField *eVecs_h, const double *sigma_h, int nEv, int gamma5,
                                 double *overlaps_h, const MugiqHipComm *comm, void *stream);
+/* mugiq_hip_deflate_low_modes for an eigenvector set that lives on the coarsest level of the MG hierarchy (computeCoarse),
+ * without ever storing v_n = P w_n:  dst_r <- dst_r - P [ sum_n w_n sigma_n^-1 c_nr ],  c_nr = <w_n, R(G src_r)>, which equals the
+ * fine-level result for any V.  transfers_h[0 .. nCoarseLevels): as for mugiq_hip_loop_create_coarse_levels, finest first;
+ * coarseEvecs_h: nEv fields on the coarsest level, of the transfers' precision.  sigma_h, overlaps_h ([nEv][nVec]), comm, aliasing
+ * of src and dst, blocking and reproducibility: the contract of mugiq_hip_deflate_low_modes (aggregates never straddle ranks: R and
+ * P need no communication).  One restriction, the overlaps and the combination on the coarsest level, the prolongation through the
+ * coarse levels, and one last pass that reads V, reads and writes dst and subtracts (no fine intermediate).  Work memory (per-stream
+ * workspace): nVec coarse vectors on every level, at least sum_l nVec * 4 * n_vec_l * volumeCB_l complex of the transfers' precision (each
+ * rounded up to 256 bytes; on the coarsest level with the eigenvectors' own stride and parity offset, pads included), plus
+ * 2 * nEv * nVec complex doubles. */
+int mugiq_hip_deflate_low_modes_coarse(const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec,
+                                       const MugiqHipCoarseField *coarseEvecs_h, const double *sigma_h, int nEv,
+                                       const MugiqHipTransfer *transfers_h, int nCoarseLevels, int gamma5, double *overlaps_h,
+                                       const MugiqHipComm *comm, void *stream);
 
 /* ==== the Wilson and Wilson-clover operators, the eigenpair check and a deflated CG (csrc/wilson.hip, csrc/clover.hip) ========= */
 /* MuGiqEigOperator, include/enum_mugiq.h:22-25 (values identical), plus H = g5 M, which the reference does not have */
@@ -625,6 +654,19 @@ int mugiq_hip_wilson_clover_apply(const MugiqHipSpinorField *dst_h, const MugiqH
 int mugiq_hip_compute_evals_clover(const MugiqHipSpinorField *eVecs_h, int nEv, const MugiqHipGaugeField *gauge,
                                    const MugiqHipCloverField *clover, double kappa, int opType, int massNormalization, double *lambda_h,
                                    double *residual_h, double *sigma_h, const MugiqHipComm *comm, void *stream);
+/* Eigsolve_Mugiq::computeEvals (lib/eigsolve_mugiq.cpp:289-315) for the computeCoarse branch (:27-33), where the reference runs the same
+ * check on mg_env->diracCoarse: the eigenvectors w_n live on the coarsest level (coarseEvecs_h, transfers_h[0 .. nCoarseLevels) as for
+ * mugiq_hip_deflate_low_modes_coarse) and the coarse operator is the Galerkin operator M_c = R M P, M_c^dag = R M^dag P, with M the
+ * Wilson (clover NULL) or Wilson-clover operator above.  Forms: M, Mdag, MdagM = M_c^dag M_c and MMdag = M_c M_c^dag (QUDA's DiracMdagM on
+ * DiracCoarse, not R MdagM P), H = R g5 M P.  lambda_n = w_n^dag A_c w_n / ||w_n||, r_n = ||lambda_n w_n - A_c w_n||, sigma and
+ * massNormalization as for mugiq_hip_compute_evals.  Blocks of 8: prolongation, one call of the batched stencil with its halo exchange,
+ * restriction; scalars are fixed-order fp64 sums, summed over the ranks as mugiq_hip_deflate_low_modes does.  Work memory (per-stream
+ * workspace): 16 fine vectors of the transfers' precision (FLOAT2, with ghost zones on partitioned axes), 16 coarse vectors on every
+ * level, and room for 8 packed level-1 vectors in fp64.  Blocks the host (two reads per block). */
+int mugiq_hip_compute_evals_coarse(const MugiqHipCoarseField *coarseEvecs_h, int nEv, const MugiqHipTransfer *transfers_h, int nCoarseLevels,
+                                   const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover, double kappa, int opType,
+                                   int massNormalization, double *lambda_h, double *residual_h, double *sigma_h, const MugiqHipComm *comm,
+                                   void *stream);
 int mugiq_hip_wilson_clover_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
                                   const MugiqHipCloverField *clover, double kappa, const MugiqHipSpinorField *eVecs_h, const double *sigma_h,
                                   int nEv, double tol, int maxIter, int *iters_out, double *relres_out, const MugiqHipComm *comm,
@@ -854,6 +896,10 @@ int mugiq_hip_write_loops_hdf5_mom(const char *filename, const void *dataMom_bca
  * MUGIQ_HIP_ERROR_UNSUPPORTED for two-sided and coarse (MG) loop objects. */
 int mugiq_hip_loop_deflate(MugiqHipLoop *loop, const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h,
                            int nVec, int gamma5, double *overlaps_h);
+/* mugiq_hip_deflate_low_modes_coarse with the coarse eigenvectors, sigma, transfers, comm and stream of a coarse (MG) loop object.
+ * MUGIQ_HIP_ERROR_UNSUPPORTED for fine-level and two-sided loop objects. */
+int mugiq_hip_loop_deflate_coarse(MugiqHipLoop *loop, const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h,
+                                  int nVec, int gamma5, double *overlaps_h);
 /* Loop_Mugiq::~Loop_Mugiq */
 int mugiq_hip_loop_destroy(MugiqHipLoop *loop);
 

@@ -95,6 +95,32 @@ inline void deflateLowModes(const std::vector<ColorSpinorField> &dst, const std:
                                     comm, stream));
 }
 
+// QUDA Transfer::R = P^dag for all vectors in one launch (mugiq_hip_restrict_batched; new): coarse_n = V^dag G fine_n per aggregate
+inline void restrictVecs(const std::vector<MugiqHipCoarseField> &coarse, const std::vector<ColorSpinorField> &fine, const MugiqHipTransfer &transfer,
+                         bool gamma5 = false, void *stream = nullptr) {
+  if (fine.empty() || coarse.size() != fine.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "restrictVecs: size mismatch");
+  check(mugiq_hip_restrict_batched(coarse.data(), fine.data(), (int)fine.size(), &transfer, gamma5 ? 1 : 0, stream));
+}
+// ... and for one coarse -> coarse level (mugiq_hip_restrict_coarse_batched), the adjoint of transfer[lev-1]->P
+inline void restrictCoarseVecs(const std::vector<MugiqHipCoarseField> &coarser, const std::vector<MugiqHipCoarseField> &finer,
+                               const MugiqHipTransfer &transfer, void *stream = nullptr) {
+  if (finer.empty() || coarser.size() != finer.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "restrictCoarseVecs: size mismatch");
+  check(mugiq_hip_restrict_coarse_batched(coarser.data(), finer.data(), (int)finer.size(), &transfer, stream));
+}
+// deflateLowModes for eigenvectors on the coarsest MG level, v_n = P w_n never stored (mugiq_hip_deflate_low_modes_coarse; new);
+// transfers: finest first
+inline void deflateLowModesCoarse(const std::vector<ColorSpinorField> &dst, const std::vector<ColorSpinorField> &src,
+                                  const std::vector<MugiqHipCoarseField> &coarseEvecs, const std::vector<MugiqHipTransfer> &transfers,
+                                  const std::vector<double> &sigma = {}, bool gamma5 = true, std::vector<std::complex<double>> *overlaps = nullptr,
+                                  const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (src.empty() || dst.size() != src.size() || coarseEvecs.empty() || transfers.empty() || (!sigma.empty() && sigma.size() != coarseEvecs.size()))
+    throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "deflateLowModesCoarse: size mismatch");
+  if (overlaps) overlaps->assign(coarseEvecs.size() * src.size(), std::complex<double>(0.0, 0.0));
+  check(mugiq_hip_deflate_low_modes_coarse(dst.data(), src.data(), (int)src.size(), coarseEvecs.data(), sigma.empty() ? nullptr : sigma.data(),
+                                           (int)coarseEvecs.size(), transfers.data(), (int)transfers.size(), gamma5 ? 1 : 0,
+                                           overlaps ? reinterpret_cast<double *>(overlaps->data()) : nullptr, comm, stream));
+}
+
 // ---- the Wilson operator and what Eigsolve_Mugiq does with it (csrc/wilson.hip; new) -------------------------------------------
 // MuGiqEigOperator of include/enum_mugiq.h:22-25 comes from the enums header; H = g5 M is this library's extension
 constexpr int EIG_OPERATOR_H = MUGIQ_HIP_EIG_OPERATOR_H;
@@ -114,6 +140,21 @@ inline void computeEvals(const std::vector<ColorSpinorField> &eVecs, const Gauge
   sigma.assign(eVecs.size(), 0.0);
   check(mugiq_hip_compute_evals(eVecs.data(), (int)eVecs.size(), &gauge, kappa, opType, massNormalization ? 1 : 0,
                                 reinterpret_cast<double *>(lambda.data()), residual.data(), sigma.data(), comm, stream));
+  if (opType == MUGIQ_HIP_EIG_OPERATOR_M || opType == MUGIQ_HIP_EIG_OPERATOR_MDAG) sigma.clear();
+}
+// computeEvals for the computeCoarse branch (lib/eigsolve_mugiq.cpp:27-33; mugiq_hip_compute_evals_coarse; new): coarse eigenvectors, the
+// Galerkin operator R M P through `transfers` (finest first); clover NULL: the unimproved operator
+inline void computeEvalsCoarse(const std::vector<MugiqHipCoarseField> &coarseEvecs, const std::vector<MugiqHipTransfer> &transfers,
+                               const GaugeField &gauge, const MugiqHipCloverField *clover, double kappa, int opType, bool massNormalization,
+                               std::vector<std::complex<double>> &lambda, std::vector<double> &residual, std::vector<double> &sigma,
+                               const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (coarseEvecs.empty() || transfers.empty()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "computeEvalsCoarse: no eigenvectors / transfers");
+  lambda.assign(coarseEvecs.size(), std::complex<double>(0.0, 0.0));
+  residual.assign(coarseEvecs.size(), 0.0);
+  sigma.assign(coarseEvecs.size(), 0.0);
+  check(mugiq_hip_compute_evals_coarse(coarseEvecs.data(), (int)coarseEvecs.size(), transfers.data(), (int)transfers.size(), &gauge, clover, kappa,
+                                       opType, massNormalization ? 1 : 0, reinterpret_cast<double *>(lambda.data()), residual.data(), sigma.data(),
+                                       comm, stream));
   if (opType == MUGIQ_HIP_EIG_OPERATOR_M || opType == MUGIQ_HIP_EIG_OPERATOR_MDAG) sigma.clear();
 }
 // Eigsolve_Mugiq::projectVector, lib/eigsolve_mugiq.cpp:340-348
@@ -443,7 +484,7 @@ public:
 // `eVecs` / `eVals_sigma` are what the reference reads from Eigsolve_Mugiq as a friend (lib/loop_mugiq.cpp:442,479).
 template <typename Float, int fieldOrder> class Loop_Mugiq {
   MugiqHipLoop *h_ = nullptr;
-  int nEv_ = 0;  // eigenvectors of a one-sided fine-level loop (what deflate reads); 0 for the other forms
+  int nEv_ = 0;  // eigenvectors of a one-sided loop, fine-level or coarse (what deflate / deflateCoarse read); 0 for two-sided loops
   GaugeField ownGauge_{};  // Displace::gaugeField when built here from loopParams.gauge[4]
 
   // everything the C parameter block points into, alive for the duration of the create call
@@ -547,6 +588,7 @@ public:
       mugiq_hip_free_extended_gauge(&ownGauge_);
       check(st);
     }
+    nEv_ = (int)coarseEvecs.size();
   }
   Loop_Mugiq(const Loop_Mugiq &) = delete;
   Loop_Mugiq &operator=(const Loop_Mugiq &) = delete;
@@ -571,6 +613,14 @@ public:
     if (overlaps) overlaps->assign((size_t)nEv_ * src.size(), std::complex<double>(0.0, 0.0));
     check(mugiq_hip_loop_deflate(h_, dst.data(), src.data(), (int)src.size(), gamma5 ? 1 : 0,
                                  overlaps ? reinterpret_cast<double *>(overlaps->data()) : nullptr));
+  }
+  // deflateLowModesCoarse with this loop's coarse eigenvectors, sigma, transfers, comm and stream (coarse loops; mugiq_hip_loop_deflate_coarse)
+  void deflateCoarse(const std::vector<ColorSpinorField> &dst, const std::vector<ColorSpinorField> &src, bool gamma5 = true,
+                     std::vector<std::complex<double>> *overlaps = nullptr) {
+    if (src.empty() || dst.size() != src.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "Loop_Mugiq::deflateCoarse: size mismatch");
+    if (overlaps) overlaps->assign((size_t)nEv_ * src.size(), std::complex<double>(0.0, 0.0));
+    check(mugiq_hip_loop_deflate_coarse(h_, dst.data(), src.data(), (int)src.size(), gamma5 ? 1 : 0,
+                                        overlaps ? reinterpret_cast<double *>(overlaps->data()) : nullptr));
   }
   int entryKernel(int id) const { return mugiq_hip_loop_get_entry_kernel(h_, id); }  // MUGIQ_HIP_ENTRY_KERNEL_* of the last compute
   const std::complex<Float> *dataPos_d() const { return static_cast<const std::complex<Float> *>(mugiq_hip_loop_data_pos_d(h_)); }

@@ -12,7 +12,7 @@ from .operators import (  # noqa: E402
     copyGammaCoeffStructToSymbol, copyGammaMapStructToSymbol, gammaTables, GammaName,
     performLoopContraction, performLoopContractionBatched, performCovariantDisplacementVector, packFace, exchangeGhostVec,
     createPhaseMatrixGPU, convertIdxOrder_mapGamma, momentumProjection, momentumProjectionSeparable, convertAndProject, convertAndProjectSlots, convertAndProjectPlan, packFaceLayers, displacedLoopContractionFused, displacedLoopContractionFusedTwoSided, reflectDisplacedLoop, packLoopLayers, probeReadBandwidth, prolongateEvecs, prolongateCoarseEvecs, prolongateContractBatched,
-    deflateLowModes,
+    deflateLowModes, restrictVecs, restrictCoarseVecs, deflateLowModesCoarse,
     DispDir, DispSignMinus, DispSignPlus, LOOP_FT_SIGN_MINUS, LOOP_FT_SIGN_PLUS, DisplaceFlagArray,
     REGION_ALL, REGION_INTERIOR, REGION_BOUNDARY, REGION_OVERWRITE, ENTRY_KERNEL_REFLECTED, ENTRY_KERNEL_MFMA_COLUMN, ENTRY_KERNEL_MFMA_ROW,
     ENTRY_KERNEL_VECTOR_TILE, ENTRY_KERNEL_STREAMING, ENTRY_KERNEL_STEPWISE,
@@ -27,7 +27,7 @@ from .loop import (  # noqa: E402
 from .comm import GridComm, RcclComm  # noqa: E402
 from .displace import Displace, DISPLACE_TYPE_COVARIANT  # noqa: E402
 from .eigsolve import (  # noqa: E402
-    Eigsolve_Mugiq, wilsonApply, computeEvals, projectVector, wilsonSolve, SolveInfo,
+    Eigsolve_Mugiq, wilsonApply, computeEvals, computeEvalsCoarse, projectVector, wilsonSolve, SolveInfo,
     MUGIQ_EIG_OPERATOR_M, MUGIQ_EIG_OPERATOR_Mdag, MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H,
 )
 

@@ -187,11 +187,20 @@ SIGNATURES = {
     "mugiq_hip_compute_evals_clover": (ctypes.c_int, [_SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                                       ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                       ctypes.POINTER(ctypes.c_double), _VP, _VP]),
+    "mugiq_hip_compute_evals_coarse": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(TransferDesc), ctypes.c_int, _GP, _CP,
+                                                      ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                                      ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _VP, _VP]),
     "mugiq_hip_wilson_clover_solve": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, _SP, ctypes.POINTER(ctypes.c_double),
                                                      ctypes.c_int, ctypes.c_double, ctypes.c_int, _I4, ctypes.POINTER(ctypes.c_double), _VP, _VP]),
     "mugiq_hip_prolongate_batched": (ctypes.c_int, [_SP, ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),
     "mugiq_hip_prolongate_contract_batched": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(CoarseDesc), ctypes.POINTER(ctypes.c_double),
                                                              ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),
+    "mugiq_hip_restrict_batched": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), _SP, ctypes.c_int, ctypes.POINTER(TransferDesc), ctypes.c_int, _VP]),
+    "mugiq_hip_restrict_coarse_batched": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.POINTER(CoarseDesc), ctypes.c_int,
+                                                         ctypes.POINTER(TransferDesc), _VP]),
+    "mugiq_hip_deflate_low_modes_coarse": (ctypes.c_int, [_SP, _SP, ctypes.c_int, ctypes.POINTER(CoarseDesc), ctypes.POINTER(ctypes.c_double),
+                                                          ctypes.c_int, ctypes.POINTER(TransferDesc), ctypes.c_int, ctypes.c_int,
+                                                          ctypes.POINTER(ctypes.c_double), _VP, _VP]),
     # driver (struct pointers are passed with ctypes.byref; see mugiq_amd/loop.py for the struct definitions)
     "mugiq_hip_loop_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _VP, _SP, ctypes.POINTER(ctypes.c_double),
                                              ctypes.c_int, _VP, _VP]),
@@ -210,6 +219,7 @@ SIGNATURES = {
                                             ctypes.POINTER(FusedForm)]),
     "mugiq_hip_loop_plan": (ctypes.c_int, [_VP, _SP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _I4, ctypes.c_size_t, ctypes.POINTER(LoopPlan)]),
     "mugiq_hip_loop_deflate": (ctypes.c_int, [_VP, _SP, _SP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
+    "mugiq_hip_loop_deflate_coarse": (ctypes.c_int, [_VP, _SP, _SP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "mugiq_hip_loop_get_info": (ctypes.c_int, [_VP, _VP]),
     "mugiq_hip_loop_set_profiling": (ctypes.c_int, [_VP, ctypes.c_int]),
     "mugiq_hip_loop_get_phases": (ctypes.c_int, [_VP, _VP, ctypes.c_int]),

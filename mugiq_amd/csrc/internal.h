@@ -103,6 +103,17 @@ int fused_contraction(void *loopData_d, int loopPrecision, const MugiqHipSpinorF
 int deflate_low_modes(const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int nVec, const MugiqHipSpinorField *ev,
                       const double *sigma, int nEv, int gamma5, double *overlaps_h, const MugiqHipComm *comm, hipStream_t stream,
                       const char *who);
+// csrc/prolong.hip: a finest-level transfer against the first coarse field of a call; one coarse -> coarse level against the nVec
+// fields of its finer and coarser side (both shared with the restriction, csrc/restrict.hip)
+int validate_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseField *c0, const char *who);
+int validate_coarse_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseField *finer_h, const MugiqHipCoarseField *coarser_h, int nVec,
+                             const char *who);
+size_t prolong_workspace_bytes(const MugiqHipTransfer *T, int nVec);  // csrc/prolong.hip: the head of the per-stream workspace the prolongator may use
+// csrc/restrict.hip: mugiq_hip_deflate_low_modes_coarse with the caller's name in the messages (mugiq_hip_loop_deflate_coarse passes the
+// loop's coarse set and transfers)
+int deflate_low_modes_coarse(const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int nVec, const MugiqHipCoarseField *ev,
+                             const double *sigma, int nEv, const MugiqHipTransfer *transfers, int nLevels, int gamma5, double *overlaps_h,
+                             const MugiqHipComm *comm, hipStream_t stream, const char *who);
 // csrc/wilson.hip: the gauge field of an operator call against the local dims X and the partitioned axes; comm -> part[4]
 int check_gauge(const MugiqHipGaugeField *U, const int X[4], const int part[4], const char *who);
 int check_comm(const MugiqHipComm *comm, int part[4], bool needSums, const char *who);
@@ -248,6 +259,14 @@ template <typename F, int G0> __device__ inline void traces_range(Cplx<F> out[4]
     for (int s2 = 0; s2 < 4; s2++) add_phase(t, kGammaPhase[G0 + i][s2], acc[s2 * 4 + kGammaColumn[G0 + i][s2]]);
     out[i] = t;
   }
+}
+
+// ---- workgroup order -------------------------------------------------------------------------------------------
+// Workgroups are dealt round-robin over the 8 XCDs.  Where neighbouring blocks of a grid share cache lines (x-adjacent aggregates
+// of the MG kernels), XCD k walks the k-th contiguous eighth of the blocks instead, so the sharers run side by side on one L2.
+__device__ inline int xcd_contiguous_block(int blk, int nblk) {
+  if (nblk & 7) return blk;
+  return (blk & 7) * (nblk >> 3) + (blk >> 3);
 }
 
 // ---- QUDA even-odd index helpers (upstream QUDA index_helper.cuh) --------------

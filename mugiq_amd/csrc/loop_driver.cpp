@@ -1400,6 +1400,19 @@ int mugiq_hip_loop_deflate(MugiqHipLoop *lp, const MugiqHipSpinorField *dst_h, c
                            lp->haveComm ? &lp->comm : nullptr, lp->stream, who);
 }
 
+int mugiq_hip_loop_deflate_coarse(MugiqHipLoop *lp, const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec, int gamma5,
+                                  double *overlaps_h) {
+  const char *who = "Loop_Mugiq::deflateCoarse";
+  MUGIQ_REQUIRE(lp != nullptr, "%s: loop is NULL", who);
+  if (lp->twoSided || !lp->coarseMode)
+    return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "%s: only loop objects over coarse (MG) eigenvectors hold a coarse low-mode set (%s)", who,
+                     lp->twoSided ? "two-sided loop" : "fine-level eigenvectors");
+  std::vector<MugiqHipTransfer> transfers(1, lp->transfer);
+  transfers.insert(transfers.end(), lp->upper.begin(), lp->upper.end());
+  return deflate_low_modes_coarse(dst_h, src_h, nVec, lp->levelVecs.back().data(), lp->sigma.data(), lp->nEv, transfers.data(),
+                                  (int)transfers.size(), gamma5, overlaps_h, lp->haveComm ? &lp->comm : nullptr, lp->stream, who);
+}
+
 int mugiq_hip_loop_get_entry_kernel(const MugiqHipLoop *lp, int id) {
   if (!lp || !lp->computed || id < 0 || id >= lp->nDispEntries) return -1;
   return lp->entryKernel[id];

@@ -190,7 +190,7 @@ __global__ __launch_bounds__(kPrTile *kPrGroups) void prolong_kernel(ProlongArgs
   }
 }
 
-static int validate_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseField *c0, const char *who) {
+int validate_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseField *c0, const char *who) {
   MUGIQ_REQUIRE(T && T->V, "%s: transfer / null vectors are NULL", who);
   MUGIQ_REQUIRE(T->precision == 4 || T->precision == 8, "%s: transfer precision %d", who, T->precision);
   MUGIQ_REQUIRE(T->nVec >= 1 && T->nVec <= 64, "%s: n_vec = %d must be in [1, 64]", who, T->nVec);
@@ -377,8 +377,6 @@ template <typename F, typename A> struct CoarseOuterArgs {
 constexpr int kCoEvecs = 8;   // eigenvectors staged per barrier
 constexpr int kCoMaxNC = 64;  // 2 * n_vec handled by the coarse path
 
-__device__ inline int xcd_contiguous_block(int blk, int nblk);
-
 // One workgroup per coarse site; the 256 threads tile C as 16 x 16 blocks of B x B entries (B = ceil(NC / 16)), so a
 // thread reads 2B components from LDS per B^2 complex multiply-adds.
 // A workgroup reads ONE 16-byte element of every (eigenvector, component) plane; the eight coarse sites of a 128-byte line are
@@ -445,10 +443,7 @@ template <typename F, typename A, int B> __global__ __launch_bounds__(256) void 
 // aggregate = blockIdx the four sharers sit on four XCDs and each pulls the line into its own L2.  Here XCD k walks the k-th
 // contiguous eighth of the lexicographic aggregate order, so the sharers run side by side on one XCD (measured: -8 % on both
 // congruence kernels at 32^4, n_vec 24).
-__device__ inline int xcd_contiguous_block(int blk, int nblk) {
-  if (nblk & 7) return blk;
-  return (blk & 7) * (nblk >> 3) + (blk >> 3);
-}
+// (xcd_contiguous_block: internal.h)
 
 template <typename F, typename A> struct FineCongruenceArgs {
   const Cplx<F> *V;       // [parity][(3s+c)*NV + j][x_cb]
@@ -1182,7 +1177,7 @@ static int prolong_mfma_plan(const MugiqHipTransfer *T, const MugiqHipCoarseFiel
   if (st) return st;
   a.table = reinterpret_cast<const void *const *>(dev);
   void *ws = nullptr;
-  const size_t packBytes = sizeof(Cplx<double>) * (size_t)volc * 2 * NV * (size_t)a.nVec8;
+  const size_t packBytes = prolong_workspace_bytes(T, nVec);
   if ((st = stream_workspace(&ws, packBytes, stream))) return st;
   a.packed = static_cast<const Cplx<double> *>(ws);
   const int nVec16 = (a.nVec8 + 15) / 16;  // (tiles of 16 eigenvectors; the last one may be half empty)
@@ -1213,6 +1208,46 @@ static int prolong_mfma_plan(const MugiqHipTransfer *T, const MugiqHipCoarseFiel
 #undef MUGIQ_PM_LAUNCH
     MUGIQ_CHECK_HIP(hipGetLastError());
   }
+  return MUGIQ_HIP_SUCCESS;
+}
+
+// what mugiq_hip_prolongate_batched may take from the HEAD of the per-stream workspace (the packed coarse vectors of the matrix-pipe form):
+// a caller that keeps data of its own in that workspace across the call leaves this much room in front of it
+size_t prolong_workspace_bytes(const MugiqHipTransfer *T, int nVec) {
+  size_t volc = 1;
+  for (int d = 0; d < 4; d++) volc *= (size_t)(T->X[d] / T->geoBlockSize[d]);
+  return sizeof(Cplx<double>) * volc * 2 * (size_t)T->nVec * (size_t)((nVec + 7) / 8 * 8);
+}
+
+// one coarse -> coarse level: `T` against the nVec fields of its finer (out_h) and coarser (in_h) side; shared with csrc/restrict.hip
+int validate_coarse_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseField *out_h, const MugiqHipCoarseField *in_h, int nVec, const char *who) {
+  MUGIQ_REQUIRE(out_h && in_h && nVec >= 1, "%s: NULL / empty argument", who);
+  MUGIQ_REQUIRE(T && T->V, "%s: Transfer operator for this level does not exist!", who);  // lib/loop_mugiq.cpp:309
+  MUGIQ_REQUIRE(T->precision == 4 || T->precision == 8, "%s: transfer precision %d", who, T->precision);
+  MUGIQ_REQUIRE(T->nVec >= 1 && T->nVec <= 96, "%s: n_vec = %d must be in [1, 96]", who, T->nVec);
+  MUGIQ_REQUIRE(T->spinBlockSize == 1, "%s: spin_block_size = %d: a coarse level keeps both chiralities (1)", who, T->spinBlockSize);
+  const MugiqHipCoarseField &o = out_h[0], &i = in_h[0];
+  MUGIQ_REQUIRE(o.nSpin == 2 && i.nSpin == 2 && i.nColor == T->nVec && o.nColor >= 1 && o.nColor <= 96, "%s: fields must have nSpin 2; coarser nColor = n_vec = %d", who, T->nVec);
+  long long vol = 1, volc = 1;
+  for (int d = 0; d < 4; d++) {
+    MUGIQ_REQUIRE(T->X[d] > 0 && (T->X[d] & 1) == 0 && o.X[d] == T->X[d], "%s: finer lattice X[%d] = %d (field: %d) must be positive, even and equal", who, d, T->X[d], o.X[d]);
+    MUGIQ_REQUIRE(T->geoBlockSize[d] >= 1 && T->X[d] % T->geoBlockSize[d] == 0, "%s: geo_block_size[%d] = %d does not divide X = %d", who, d, T->geoBlockSize[d], T->X[d]);
+    const int xc = T->X[d] / T->geoBlockSize[d];
+    MUGIQ_REQUIRE((xc & 1) == 0 && i.X[d] == xc, "%s: coarser extent in dim %d must be even and equal X/block = %d (field: %d)", who, d, xc, i.X[d]);
+    vol *= T->X[d];
+    volc *= xc;
+  }
+  MUGIQ_REQUIRE(o.volumeCB == vol / 2 && i.volumeCB == volc / 2, "%s: volumeCB mismatch", who);
+  MUGIQ_REQUIRE(T->stride >= vol / 2 && T->parity_offset >= (int64_t)2 * o.nColor * T->nVec * T->stride, "%s: V stride / parity_offset too small", who);
+  for (int n = 0; n < nVec; n++) {
+    MUGIQ_REQUIRE(out_h[n].data && in_h[n].data && out_h[n].data != in_h[n].data, "%s: field %d is NULL or aliased", who, n);
+    MUGIQ_REQUIRE(out_h[n].precision == T->precision && in_h[n].precision == T->precision, "%s: field %d: precision differs from the transfer's", who, n);
+    MUGIQ_REQUIRE(out_h[n].stride == o.stride && out_h[n].parity_offset == o.parity_offset && out_h[n].nColor == o.nColor &&
+                      in_h[n].stride == i.stride && in_h[n].parity_offset == i.parity_offset && in_h[n].nColor == i.nColor,
+                  "%s: field %d differs in layout from field 0", who, n);
+  }
+  MUGIQ_REQUIRE(o.stride >= o.volumeCB && o.parity_offset >= (int64_t)2 * o.nColor * o.stride && i.stride >= i.volumeCB &&
+                    i.parity_offset >= (int64_t)2 * i.nColor * i.stride, "%s: field stride / parity_offset too small", who);
   return MUGIQ_HIP_SUCCESS;
 }
 
@@ -1253,33 +1288,7 @@ int mugiq_hip_prolongate_coarse_batched(const MugiqHipCoarseField *out_h, const 
                                         const MugiqHipTransfer *T, void *stream) {
   if (int dbg_ = mugiq::debug_poison_lds_if_asked(static_cast<hipStream_t>(stream))) return dbg_;
   const char *who = "prolongateEvec(coarse level)";
-  MUGIQ_REQUIRE(out_h && in_h && nVec >= 1, "%s: NULL / empty argument", who);
-  MUGIQ_REQUIRE(T && T->V, "%s: Transfer operator for this level does not exist!", who);  // lib/loop_mugiq.cpp:309
-  MUGIQ_REQUIRE(T->precision == 4 || T->precision == 8, "%s: transfer precision %d", who, T->precision);
-  MUGIQ_REQUIRE(T->nVec >= 1 && T->nVec <= 96, "%s: n_vec = %d must be in [1, 96]", who, T->nVec);
-  MUGIQ_REQUIRE(T->spinBlockSize == 1, "%s: spin_block_size = %d: a coarse level keeps both chiralities (1)", who, T->spinBlockSize);
-  const MugiqHipCoarseField &o = out_h[0], &i = in_h[0];
-  MUGIQ_REQUIRE(o.nSpin == 2 && i.nSpin == 2 && i.nColor == T->nVec && o.nColor >= 1 && o.nColor <= 96, "%s: fields must have nSpin 2; coarser nColor = n_vec = %d", who, T->nVec);
-  long long vol = 1, volc = 1;
-  for (int d = 0; d < 4; d++) {
-    MUGIQ_REQUIRE(T->X[d] > 0 && (T->X[d] & 1) == 0 && o.X[d] == T->X[d], "%s: finer lattice X[%d] = %d (field: %d) must be positive, even and equal", who, d, T->X[d], o.X[d]);
-    MUGIQ_REQUIRE(T->geoBlockSize[d] >= 1 && T->X[d] % T->geoBlockSize[d] == 0, "%s: geo_block_size[%d] = %d does not divide X = %d", who, d, T->geoBlockSize[d], T->X[d]);
-    const int xc = T->X[d] / T->geoBlockSize[d];
-    MUGIQ_REQUIRE((xc & 1) == 0 && i.X[d] == xc, "%s: coarser extent in dim %d must be even and equal X/block = %d (field: %d)", who, d, xc, i.X[d]);
-    vol *= T->X[d];
-    volc *= xc;
-  }
-  MUGIQ_REQUIRE(o.volumeCB == vol / 2 && i.volumeCB == volc / 2, "%s: volumeCB mismatch", who);
-  MUGIQ_REQUIRE(T->stride >= vol / 2 && T->parity_offset >= (int64_t)2 * o.nColor * T->nVec * T->stride, "%s: V stride / parity_offset too small", who);
-  for (int n = 0; n < nVec; n++) {
-    MUGIQ_REQUIRE(out_h[n].data && in_h[n].data && out_h[n].data != in_h[n].data, "%s: field %d is NULL or aliased", who, n);
-    MUGIQ_REQUIRE(out_h[n].precision == T->precision && in_h[n].precision == T->precision, "%s: field %d: precision differs from the transfer's", who, n);
-    MUGIQ_REQUIRE(out_h[n].stride == o.stride && out_h[n].parity_offset == o.parity_offset && out_h[n].nColor == o.nColor &&
-                      in_h[n].stride == i.stride && in_h[n].parity_offset == i.parity_offset && in_h[n].nColor == i.nColor,
-                  "%s: field %d differs in layout from field 0", who, n);
-  }
-  MUGIQ_REQUIRE(o.stride >= o.volumeCB && o.parity_offset >= (int64_t)2 * o.nColor * o.stride && i.stride >= i.volumeCB &&
-                    i.parity_offset >= (int64_t)2 * i.nColor * i.stride, "%s: field stride / parity_offset too small", who);
+  if (int st = validate_coarse_transfer(T, out_h, in_h, nVec, who)) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (T->precision == 8) return launch_prolong_coarse<double>(out_h, in_h, nVec, T, s);
   return launch_prolong_coarse<float>(out_h, in_h, nVec, T, s);

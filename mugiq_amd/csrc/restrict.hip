@@ -1,0 +1,870 @@
+// Restriction R = P^dag, the adjoint of the prolongator of csrc/prolong.hip (QUDA Transfer::R), batched over right-hand sides, and
+// the low-mode deflation of fine vectors THROUGH the coarse space of the MG hierarchy (eigsolve->computeCoarse: the eigenvectors
+// w_n live on the coarsest level, v_n = P w_n is never stored):
+//     coarse(X; S, j) = sum_{x in aggregate X} sum_{s: s / spin_bs = S} sum_c conj(V(x; s, c, j)) g(s) fine(x; s, c),   g = 1 | diag(g5)
+//     dst_r <- dst_r - P [ sum_n w_n sigma_n^-1 c_nr ],   c_nr = <w_n, R(G src_r)>          (v_n^dag G src = w_n^dag R G src, exactly)
+//
+// Numerics (as csrc/deflate.hip): products and sums in fp64 whatever the storage, one rounding on the store, no atomics, and a
+// summation order that depends on nothing but the shape of the transfer -- not on nVec, not on a vector's place in the batch.
+//
+// Finest level, restrict_kernel: a workgroup owns ONE aggregate and a block of kRsRB = 8 right-hand sides; V is read once per
+// block and every element loaded is used for all eight.  256 lanes = 32 site slots x 8 null-vector groups: lane (slot, jg) walks
+// the aggregate's sites slot, slot + 32, ... (coordinates -> parity, x_cb: odd block extents mix the parities site by site) and
+// carries 3 null vectors j = jg, jg + 8, jg + 16 (more: further passes over the aggregate) x 8 right-hand sides = 24 fp64 complex
+// accumulators per chirality.  The 32 slot partials of an output leave through LDS and are added in slot order by one lane.
+// By the byte model HBM bound: 18 kflop per 4.6 KB of V at n_vec 24 is 4 flop/B, below the fp64 ridge -- the vector pipe, no MFMA.
+// (Measured, DESIGN.md 4.4a: 3.4 x one read of V; the right-hand sides are re-loaded by all 8 groups of a site, V comes in 32-byte pieces.)
+// Workgroups follow xcd_contiguous_block: x-adjacent aggregates share the 128-byte lines of a V row and run on one XCD.
+// Coarse -> coarse levels (256 x smaller): restrict_coarse_kernel, one lane per coarse site, output component and eight vectors.
+#include "internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+namespace mugiq {
+namespace {
+
+constexpr int kRsSlots = 32;  // fine sites of the aggregate in flight
+constexpr int kRsJG = 8;      // null-vector groups (lanes per site)
+constexpr int kRsJC = 3;      // null vectors per lane and pass
+constexpr int kRsRB = 8;      // right-hand sides per workgroup
+constexpr int kRsHalf = 4;    // right-hand sides per trip through LDS
+
+// diag(g5), g5 = Gamma_15 of the DeGrand-Rossi tables (internal.h): diagonal with real entries
+template <int S> constexpr double gamma5_entry() {
+  static_assert(kGammaColumn[15][S] == S && (kGammaPhase[15][S] == 0 || kGammaPhase[15][S] == 2), "gamma5 must be diagonal and real");
+  return kGammaPhase[15][S] == 0 ? 1.0 : -1.0;
+}
+__device__ inline double gamma5_diag(int s) {
+  return s == 0 ? gamma5_entry<0>() : s == 1 ? gamma5_entry<1>() : s == 2 ? gamma5_entry<2>() : gamma5_entry<3>();
+}
+
+template <typename F> __device__ inline Cplx<double> ld_wide(const void *base, int64_t i) {
+  typedef F vec2 __attribute__((ext_vector_type(2)));
+  const vec2 t = *as_global(reinterpret_cast<const vec2 *>(base) + i);
+  return Cplx<double>{(double)t.x, (double)t.y};
+}
+template <typename F> __device__ inline void st_round(void *base, int64_t i, const Cplx<double> &v) {
+  typedef F vec2 __attribute__((ext_vector_type(2)));
+  vec2 t;
+  t.x = (F)v.re;
+  t.y = (F)v.im;
+  *as_global(reinterpret_cast<vec2 *>(base) + i) = t;
+}
+// complex element of component k = 3 s + c of a fine field body (SpinorView, internal.h)
+template <int ORDER> __device__ inline int64_t fine_elem(int k, int pty, int x_cb, int stride, int64_t po) {
+  if constexpr (ORDER == 2) return pty * po + (int64_t)k * stride + x_cb;
+  else return pty * po + 2 * ((int64_t)(k >> 1) * stride + x_cb) + (k & 1);
+}
+
+struct LevelGeom {
+  int X[4], Xc[4], bs[4];
+  int aggVol, volumeCB, volumeCBc;
+};
+LevelGeom level_geom(const MugiqHipTransfer *T) {
+  LevelGeom g;
+  long long vol = 1, volc = 1;
+  g.aggVol = 1;
+  for (int d = 0; d < 4; d++) {
+    g.X[d] = T->X[d];
+    g.bs[d] = T->geoBlockSize[d];
+    g.Xc[d] = T->X[d] / T->geoBlockSize[d];
+    g.aggVol *= g.bs[d];
+    vol *= g.X[d];
+    volc *= g.Xc[d];
+  }
+  g.volumeCB = (int)(vol / 2);
+  g.volumeCBc = (int)(volc / 2);
+  return g;
+}
+// member k (lexicographic inside the block) of the aggregate at coarse coordinates cc
+__device__ inline void aggregate_member(const LevelGeom &g, const int cc[4], int k, int *pty, int *x_cb) {
+  int x[4];
+#pragma unroll
+  for (int d = 0; d < 4; d++) {
+    x[d] = cc[d] * g.bs[d] + k % g.bs[d];
+    k /= g.bs[d];
+  }
+  *pty = (x[0] + x[1] + x[2] + x[3]) & 1;
+  *x_cb = lex_index(x, g.X) >> 1;
+}
+
+struct RestrictArgs {
+  const void *V;  // [parity][(3s+c)*NV + j][x_cb]
+  int64_t Vpo;
+  int Vstride, NV;
+  LevelGeom g;
+  const void *const *tab;  // device table: nVec fine bodies, then nVec coarse bodies
+  int Fstride, Cstride;
+  int64_t Fpo, Cpo;
+  int nVec, gamma5;
+};
+
+template <typename FV, typename FS, int ORDER> __global__ __launch_bounds__(kRsSlots *kRsJG) void restrict_kernel(RestrictArgs a) {
+  __shared__ Cplx<double> red[kRsJG * kRsJC * kRsHalf][kRsSlots + 1];
+  const int t = threadIdx.x, slot = t & (kRsSlots - 1), jg = t / kRsSlots;
+  int cc[4], r = xcd_contiguous_block(blockIdx.x, gridDim.x);
+#pragma unroll
+  for (int d = 0; d < 4; d++) {
+    cc[d] = r % a.g.Xc[d];
+    r /= a.g.Xc[d];
+  }
+  const int64_t coff = (int64_t)((cc[0] + cc[1] + cc[2] + cc[3]) & 1) * a.Cpo + (lex_index(cc, a.g.Xc) >> 1);
+  const int n0 = blockIdx.y * kRsRB;
+  const auto *tab = as_constant(a.tab);
+  const void *fp[kRsRB];  // (vectors past the end shadow the last one; their sums are not stored)
+#pragma unroll
+  for (int i = 0; i < kRsRB; i++) fp[i] = tab[min(n0 + i, a.nVec - 1)];
+
+  for (int j0 = 0; j0 < a.NV; j0 += kRsJG * kRsJC) {
+    for (int chi = 0; chi < 2; chi++) {
+      Cplx<double> acc[kRsJC][kRsRB];
+#pragma unroll
+      for (int i = 0; i < kRsJC; i++)
+#pragma unroll
+        for (int n = 0; n < kRsRB; n++) acc[i][n] = Cplx<double>{0.0, 0.0};
+      for (int k = slot; k < a.g.aggVol; k += kRsSlots) {
+        int pty, x_cb;
+        aggregate_member(a.g, cc, k, &pty, &x_cb);
+        const int64_t voff = pty * a.Vpo + x_cb;
+        for (int sc = 0; sc < 6; sc++) {
+          const int comp = chi * 6 + sc;
+          const double gs = a.gamma5 ? gamma5_diag(comp / 3) : 1.0;
+          const int64_t fe = fine_elem<ORDER>(comp, pty, x_cb, a.Fstride, a.Fpo);
+          Cplx<double> psi[kRsRB];
+#pragma unroll
+          for (int n = 0; n < kRsRB; n++) {
+            const Cplx<double> p = ld_wide<FS>(fp[n], fe);
+            psi[n] = Cplx<double>{gs * p.re, gs * p.im};
+          }
+#pragma unroll
+          for (int i = 0; i < kRsJC; i++) {
+            const int j = j0 + jg + kRsJG * i;
+            if (j < a.NV) {
+              const Cplx<double> v = ld_wide<FV>(a.V, voff + (int64_t)(comp * a.NV + j) * a.Vstride);
+#pragma unroll
+              for (int n = 0; n < kRsRB; n++) cmadd_conj(acc[i][n], v, psi[n]);
+            }
+          }
+        }
+      }
+      // the 32 slot partials of every output, added in slot order
+#pragma unroll
+      for (int h = 0; h < kRsRB / kRsHalf; h++) {
+        __syncthreads();  // the previous trip has been read
+#pragma unroll
+        for (int i = 0; i < kRsJC; i++)
+#pragma unroll
+          for (int nn = 0; nn < kRsHalf; nn++) red[(jg * kRsJC + i) * kRsHalf + nn][slot] = acc[i][h * kRsHalf + nn];
+        __syncthreads();
+        if (t < kRsJG * kRsJC * kRsHalf) {
+          Cplx<double> s{0.0, 0.0};
+          for (int q = 0; q < kRsSlots; q++) {
+            s.re += red[t][q].re;
+            s.im += red[t][q].im;
+          }
+          const int nn = t % kRsHalf, i = (t / kRsHalf) % kRsJC, jgo = t / (kRsHalf * kRsJC);
+          const int j = j0 + jgo + kRsJG * i, n = n0 + h * kRsHalf + nn;
+          if (j < a.NV && n < a.nVec) st_round<FV>(const_cast<void *>(tab[a.nVec + n]), coff + (int64_t)(chi * a.NV + j) * a.Cstride, s);
+        }
+      }
+    }
+  }
+}
+
+template <typename FV, typename FS, int ORDER>
+int launch_restrict(const MugiqHipCoarseField *coarse, const MugiqHipSpinorField *fine, int nVec, const MugiqHipTransfer *T, int gamma5,
+                    hipStream_t stream) {
+  std::vector<const void *> host(2 * (size_t)nVec);
+  for (int n = 0; n < nVec; n++) {
+    host[n] = fine[n].data;
+    host[nVec + n] = coarse[n].data;
+  }
+  void *dev = nullptr;
+  if (int st = upload_table(&dev, host.data(), host.size() * sizeof(void *), stream)) return st;
+  RestrictArgs a;
+  a.V = T->V;
+  a.Vpo = T->parity_offset;
+  a.Vstride = T->stride;
+  a.NV = T->nVec;
+  a.g = level_geom(T);
+  a.tab = static_cast<const void *const *>(dev);
+  a.Fstride = fine[0].stride;
+  a.Fpo = fine[0].parity_offset;
+  a.Cstride = coarse[0].stride;
+  a.Cpo = coarse[0].parity_offset;
+  a.nVec = nVec;
+  a.gamma5 = gamma5 ? 1 : 0;
+  const dim3 grid(2 * a.g.volumeCBc, (nVec + kRsRB - 1) / kRsRB);
+  hipLaunchKernelGGL((restrict_kernel<FV, FS, ORDER>), grid, dim3(kRsSlots * kRsJG), 0, stream, a);
+  MUGIQ_CHECK_HIP(hipGetLastError());
+  return MUGIQ_HIP_SUCCESS;
+}
+
+int validate_restrict(const MugiqHipCoarseField *coarse_h, const MugiqHipSpinorField *fine_h, int nVec, const MugiqHipTransfer *T, const char *who) {
+  MUGIQ_REQUIRE(fine_h && coarse_h && nVec >= 1, "%s: NULL / empty argument", who);
+  int st = validate_transfer(T, &coarse_h[0], who);
+  if (st) return st;
+  for (int n = 0; n < nVec; n++) {
+    if ((st = validate_spinor(&fine_h[n], who, "fine"))) return st;
+    MUGIQ_REQUIRE(same_geometry(fine_h[n], fine_h[0]), "%s: fine field %d differs in precision, field order or geometry from field 0", who, n);
+    MUGIQ_REQUIRE(coarse_h[n].data && coarse_h[n].stride == coarse_h[0].stride && coarse_h[n].parity_offset == coarse_h[0].parity_offset &&
+                      coarse_h[n].precision == coarse_h[0].precision && coarse_h[n].nColor == coarse_h[0].nColor,
+                  "%s: coarse field %d differs from field 0", who, n);
+  }
+  for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(fine_h[0].X[d] == T->X[d], "%s: fine X[%d] = %d, the transfer's is %d", who, d, fine_h[0].X[d], T->X[d]);
+  return MUGIQ_HIP_SUCCESS;
+}
+
+int restrict_batched(const MugiqHipCoarseField *coarse, const MugiqHipSpinorField *fine, int nVec, const MugiqHipTransfer *T, int gamma5,
+                     hipStream_t s) {
+  const int pv = T->precision, pf = fine[0].precision, o = fine[0].field_order;
+#define MUGIQ_RS_CASE(PV_, PF_, O_, FV_, FS_) \
+  if (pv == PV_ && pf == PF_ && o == O_) return launch_restrict<FV_, FS_, O_>(coarse, fine, nVec, T, gamma5, s);
+  MUGIQ_RS_CASE(8, 8, 2, double, double)
+  MUGIQ_RS_CASE(8, 8, 4, double, double)
+  MUGIQ_RS_CASE(8, 4, 2, double, float)
+  MUGIQ_RS_CASE(8, 4, 4, double, float)
+  MUGIQ_RS_CASE(4, 8, 2, float, double)
+  MUGIQ_RS_CASE(4, 8, 4, float, double)
+  MUGIQ_RS_CASE(4, 4, 2, float, float)
+  MUGIQ_RS_CASE(4, 4, 4, float, float)
+#undef MUGIQ_RS_CASE
+  return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "restrictVecs: precision %d / %d, field order %d", pv, pf, o);
+}
+
+// ---- coarse -> coarse levels ------------------------------------------------------------------------------------------------
+// coarser(X; s, j) = sum_{x in X} sum_{c < nColor(finer)} conj(V(x; s, c, j)) finer(x; s, c): sites of the block in lexicographic
+// order, colours ascending inside a site
+struct RestrictCoarseArgs {
+  const void *V;  // [parity][(NCf*s + c)*NV + j][x_cb]
+  int64_t Vpo;
+  int Vstride, NV, NCf;
+  LevelGeom g;
+  const void *const *tab;  // device table: nVec finer bodies, then nVec coarser bodies
+  int Istride, Ostride;
+  int64_t Ipo, Opo;
+  int nVec;
+};
+
+template <typename F> __global__ __launch_bounds__(128) void restrict_coarse_kernel(RestrictCoarseArgs a) {
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (tid >= 2 * a.g.volumeCBc) return;
+  const int cpar = tid / a.g.volumeCBc, xc_cb = tid - cpar * a.g.volumeCBc;
+  const int k = blockIdx.y, s = k / a.NV, j = k - s * a.NV;  // output component (s, j)
+  const int n0 = blockIdx.z * kRsRB;
+  int cc[4];
+  get_coords(cc, xc_cb, a.g.Xc, cpar);
+  const auto *tab = as_constant(a.tab);
+  const void *ip[kRsRB];
+#pragma unroll
+  for (int i = 0; i < kRsRB; i++) ip[i] = tab[min(n0 + i, a.nVec - 1)];
+  Cplx<double> acc[kRsRB];
+#pragma unroll
+  for (int i = 0; i < kRsRB; i++) acc[i] = Cplx<double>{0.0, 0.0};
+  for (int m = 0; m < a.g.aggVol; m++) {
+    int pty, x_cb;
+    aggregate_member(a.g, cc, m, &pty, &x_cb);
+    for (int c = 0; c < a.NCf; c++) {
+      const int plane = s * a.NCf + c;
+      const Cplx<double> v = ld_wide<F>(a.V, pty * a.Vpo + (int64_t)(plane * a.NV + j) * a.Vstride + x_cb);
+      const int64_t ie = pty * a.Ipo + (int64_t)plane * a.Istride + x_cb;
+#pragma unroll
+      for (int i = 0; i < kRsRB; i++) cmadd_conj(acc[i], v, ld_wide<F>(ip[i], ie));
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kRsRB; i++)
+    if (n0 + i < a.nVec) st_round<F>(const_cast<void *>(tab[a.nVec + n0 + i]), cpar * a.Opo + (int64_t)k * a.Ostride + xc_cb, acc[i]);
+}
+
+template <typename F>
+int launch_restrict_coarse(const MugiqHipCoarseField *coarser, const MugiqHipCoarseField *finer, int nVec, const MugiqHipTransfer *T,
+                           hipStream_t stream) {
+  std::vector<const void *> host(2 * (size_t)nVec);
+  for (int n = 0; n < nVec; n++) {
+    host[n] = finer[n].data;
+    host[nVec + n] = coarser[n].data;
+  }
+  void *dev = nullptr;
+  if (int st = upload_table(&dev, host.data(), host.size() * sizeof(void *), stream)) return st;
+  RestrictCoarseArgs a;
+  a.V = T->V;
+  a.Vpo = T->parity_offset;
+  a.Vstride = T->stride;
+  a.NV = T->nVec;
+  a.NCf = finer[0].nColor;
+  a.g = level_geom(T);
+  a.tab = static_cast<const void *const *>(dev);
+  a.Istride = finer[0].stride;
+  a.Ipo = finer[0].parity_offset;
+  a.Ostride = coarser[0].stride;
+  a.Opo = coarser[0].parity_offset;
+  a.nVec = nVec;
+  const dim3 grid((2 * a.g.volumeCBc + 127) / 128, 2 * a.NV, (nVec + kRsRB - 1) / kRsRB);
+  hipLaunchKernelGGL((restrict_coarse_kernel<F>), grid, dim3(128), 0, stream, a);
+  MUGIQ_CHECK_HIP(hipGetLastError());
+  return MUGIQ_HIP_SUCCESS;
+}
+
+int restrict_coarse_batched(const MugiqHipCoarseField *coarser, const MugiqHipCoarseField *finer, int nVec, const MugiqHipTransfer *T,
+                            hipStream_t s) {
+  if (T->precision == 8) return launch_restrict_coarse<double>(coarser, finer, nVec, T, s);
+  return launch_restrict_coarse<float>(coarser, finer, nVec, T, s);
+}
+
+// ---- deflation through the coarse space ---------------------------------------------------------------------------------------
+// Elements of a coarse field without its pads: e -> (parity, plane, x_cb), e < 2 * planes * volumeCB
+struct CoarseGeom {
+  int planes, volumeCB, stride;
+  int64_t po;
+  int nElem;
+};
+__device__ inline int64_t coarse_elem(const CoarseGeom &g, int e) {
+  const int q = e / g.volumeCB, x = e - q * g.volumeCB;
+  const int parity = q / g.planes, plane = q - parity * g.planes;
+  return parity * g.po + (int64_t)plane * g.stride + x;
+}
+
+constexpr int kCoThreads = 256;
+// C[n][r] = sum_e conj(w_n[e]) y_r[e] for the block r = r0 .. r0 + 7 of blockIdx.y: lane t adds e = t, t + 256, ... in ascending order,
+// then the 256 lane sums are folded by a fixed halving tree in LDS.  D = C / sigma.
+template <typename F>
+__global__ __launch_bounds__(kCoThreads) void coarse_overlap_kernel(const void *const *W, const void *const *Y, int nVec, CoarseGeom g,
+                                                                    const double *invSigma, Cplx<double> *C, Cplx<double> *D) {
+  __shared__ Cplx<double> red[kRsRB][kCoThreads];
+  const int n = blockIdx.x, r0 = blockIdx.y * kRsRB, t = threadIdx.x;
+  const void *w = as_constant(W)[n];
+  const void *yp[kRsRB];
+#pragma unroll
+  for (int i = 0; i < kRsRB; i++) yp[i] = as_constant(Y)[min(r0 + i, nVec - 1)];
+  Cplx<double> acc[kRsRB];
+#pragma unroll
+  for (int i = 0; i < kRsRB; i++) acc[i] = Cplx<double>{0.0, 0.0};
+  for (int e = t; e < g.nElem; e += kCoThreads) {
+    const int64_t off = coarse_elem(g, e);
+    const Cplx<double> wv = ld_wide<F>(w, off);
+#pragma unroll
+    for (int i = 0; i < kRsRB; i++) cmadd_conj(acc[i], wv, ld_wide<F>(yp[i], off));
+  }
+#pragma unroll
+  for (int i = 0; i < kRsRB; i++) red[i][t] = acc[i];
+  for (int s = kCoThreads / 2; s > 0; s >>= 1) {
+    __syncthreads();
+    if (t < s) {
+#pragma unroll
+      for (int i = 0; i < kRsRB; i++) {
+        red[i][t].re += red[i][t + s].re;
+        red[i][t].im += red[i][t + s].im;
+      }
+    }
+  }
+  if (t < kRsRB && r0 + t < nVec) {
+    const Cplx<double> c = red[t][0];
+    C[(int64_t)n * nVec + r0 + t] = c;
+    D[(int64_t)n * nVec + r0 + t] = Cplx<double>{c.re * invSigma[n], c.im * invSigma[n]};
+  }
+}
+
+// z_r[e] = sum_n w_n[e] D[n][r], n ascending, for the block r = r0 .. r0 + 7 of blockIdx.y
+template <typename F>
+__global__ __launch_bounds__(kCoThreads) void coarse_combine_kernel(const void *const *W, void *const *Z, int nEv, int nVec, CoarseGeom g,
+                                                                    const Cplx<double> *D) {
+  const int e = blockIdx.x * kCoThreads + threadIdx.x, r0 = blockIdx.y * kRsRB;
+  if (e >= g.nElem) return;
+  const int64_t off = coarse_elem(g, e);
+  Cplx<double> acc[kRsRB];
+#pragma unroll
+  for (int i = 0; i < kRsRB; i++) acc[i] = Cplx<double>{0.0, 0.0};
+  for (int n = 0; n < nEv; n++) {
+    const Cplx<double> wv = ld_wide<F>(as_constant(W)[n], off);
+#pragma unroll
+    for (int i = 0; i < kRsRB; i++) {
+      typedef double vec2 __attribute__((ext_vector_type(2)));
+      const vec2 d = *as_constant(reinterpret_cast<const vec2 *>(D) + (int64_t)n * nVec + min(r0 + i, nVec - 1));
+      cmadd(acc[i], wv, Cplx<double>{d.x, d.y});
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kRsRB; i++)
+    if (r0 + i < nVec) st_round<F>(as_constant(Z)[r0 + i], off, acc[i]);
+}
+
+// dst_r(x; s, c) -= sum_j V(x; s, c, j) z_r(X(x); s / 2, j), j ascending: the last prolongation and the update in one pass.  Lane =
+// fine site (V rows coalesced along x_cb), blockIdx.y = component 3 s + c, blockIdx.z = block of eight right-hand sides: every V element
+// is read once per block, every dst element read and written once
+struct ProlongSubtractArgs {
+  const void *V;
+  int64_t Vpo;
+  int Vstride, NV;
+  LevelGeom g;
+  const void *const *tab;  // device table: nVec coarse bodies (z), then nVec dst bodies
+  int Fstride, Cstride;
+  int64_t Fpo, Cpo;
+  int nVec;
+};
+template <typename FV, typename FS, int ORDER> __global__ __launch_bounds__(128) void prolong_subtract_kernel(ProlongSubtractArgs a) {
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (tid >= 2 * a.g.volumeCB) return;
+  const int pty = tid / a.g.volumeCB, x_cb = tid - pty * a.g.volumeCB;
+  const int comp = blockIdx.y, chi = comp / 6, n0 = blockIdx.z * kRsRB;
+  int c[4], cc[4];
+  get_coords(c, x_cb, a.g.X, pty);
+#pragma unroll
+  for (int d = 0; d < 4; d++) cc[d] = c[d] / a.g.bs[d];
+  const int64_t coff = (int64_t)((cc[0] + cc[1] + cc[2] + cc[3]) & 1) * a.Cpo + (lex_index(cc, a.g.Xc) >> 1) + (int64_t)(chi * a.NV) * a.Cstride;
+  const auto *tab = as_constant(a.tab);
+  const void *zp[kRsRB];
+#pragma unroll
+  for (int i = 0; i < kRsRB; i++) zp[i] = tab[min(n0 + i, a.nVec - 1)];
+  Cplx<double> acc[kRsRB];
+#pragma unroll
+  for (int i = 0; i < kRsRB; i++) acc[i] = Cplx<double>{0.0, 0.0};
+  const int64_t voff = pty * a.Vpo + (int64_t)comp * a.NV * a.Vstride + x_cb;
+  for (int j = 0; j < a.NV; j++) {
+    const Cplx<double> v = ld_wide<FV>(a.V, voff + (int64_t)j * a.Vstride);
+#pragma unroll
+    for (int i = 0; i < kRsRB; i++) cmadd(acc[i], v, ld_wide<FV>(zp[i], coff + (int64_t)j * a.Cstride));
+  }
+  const int64_t fe = fine_elem<ORDER>(comp, pty, x_cb, a.Fstride, a.Fpo);
+#pragma unroll
+  for (int i = 0; i < kRsRB; i++)
+    if (n0 + i < a.nVec) {
+      void *q = const_cast<void *>(tab[a.nVec + n0 + i]);
+      const Cplx<double> d = ld_wide<FS>(q, fe);
+      st_round<FS>(q, fe, Cplx<double>{d.re - acc[i].re, d.im - acc[i].im});
+    }
+}
+
+template <typename FV, typename FS, int ORDER>
+int launch_prolong_subtract(const MugiqHipSpinorField *dst, const MugiqHipCoarseField *z, int nVec, const MugiqHipTransfer *T, hipStream_t stream) {
+  std::vector<const void *> host(2 * (size_t)nVec);
+  for (int n = 0; n < nVec; n++) {
+    host[n] = z[n].data;
+    host[nVec + n] = dst[n].data;
+  }
+  void *dev = nullptr;
+  if (int st = upload_table(&dev, host.data(), host.size() * sizeof(void *), stream)) return st;
+  ProlongSubtractArgs a;
+  a.V = T->V;
+  a.Vpo = T->parity_offset;
+  a.Vstride = T->stride;
+  a.NV = T->nVec;
+  a.g = level_geom(T);
+  a.tab = static_cast<const void *const *>(dev);
+  a.Fstride = dst[0].stride;
+  a.Fpo = dst[0].parity_offset;
+  a.Cstride = z[0].stride;
+  a.Cpo = z[0].parity_offset;
+  a.nVec = nVec;
+  const dim3 grid((2 * a.g.volumeCB + 127) / 128, 12, (nVec + kRsRB - 1) / kRsRB);
+  hipLaunchKernelGGL((prolong_subtract_kernel<FV, FS, ORDER>), grid, dim3(128), 0, stream, a);
+  MUGIQ_CHECK_HIP(hipGetLastError());
+  return MUGIQ_HIP_SUCCESS;
+}
+
+int prolong_subtract(const MugiqHipSpinorField *dst, const MugiqHipCoarseField *z, int nVec, const MugiqHipTransfer *T, hipStream_t s) {
+  const int pv = T->precision, pf = dst[0].precision, o = dst[0].field_order;
+#define MUGIQ_PS_CASE(PV_, PF_, O_, FV_, FS_) \
+  if (pv == PV_ && pf == PF_ && o == O_) return launch_prolong_subtract<FV_, FS_, O_>(dst, z, nVec, T, s);
+  MUGIQ_PS_CASE(8, 8, 2, double, double)
+  MUGIQ_PS_CASE(8, 8, 4, double, double)
+  MUGIQ_PS_CASE(8, 4, 2, double, float)
+  MUGIQ_PS_CASE(8, 4, 4, double, float)
+  MUGIQ_PS_CASE(4, 8, 2, float, double)
+  MUGIQ_PS_CASE(4, 8, 4, float, double)
+  MUGIQ_PS_CASE(4, 4, 2, float, float)
+  MUGIQ_PS_CASE(4, 4, 4, float, float)
+#undef MUGIQ_PS_CASE
+  return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "deflateLowModesCoarse: precision %d / %d, field order %d", pv, pf, o);
+}
+
+// [first, last) byte range a fine field's kernels may touch
+void fine_span(const MugiqHipSpinorField &f, uintptr_t *a, uintptr_t *b) {
+  *a = reinterpret_cast<uintptr_t>(f.data);
+  *b = *a + (uintptr_t)(f.parity_offset + (int64_t)12 * f.stride) * 2 * f.precision;
+}
+
+// The hierarchy of a call on coarse eigenvectors: transfers[0 .. nLevels) (finest first) fit together and the nEv eigenvectors live on
+// the coarsest level.  lev[l]: the layout of the work vectors on level l + 1 (the coarser side of transfers[l]), without a body; the
+// coarsest one takes the eigenvectors' stride and parity offset, so that one element offset serves both
+int validate_hierarchy(const MugiqHipTransfer *transfers, int nLevels, const MugiqHipCoarseField *ev, int nEv, std::vector<MugiqHipCoarseField> *levOut,
+                       const char *who) {
+  int st;
+  std::vector<MugiqHipCoarseField> &lev = *levOut;
+  lev.assign(nLevels, MugiqHipCoarseField{});
+  // level l + 1 fields (the coarser side of transfers[l]) as descriptors without data; lev[nLevels - 1] describes the eigenvectors
+  for (int l = 0; l < nLevels; l++) {
+    const MugiqHipTransfer &T = transfers[l];
+    MUGIQ_REQUIRE(T.V != nullptr && T.nVec >= 1, "%s: transfer %d is empty", who, l);
+    MUGIQ_REQUIRE(T.precision == ev[0].precision, "%s: transfer %d has precision %d, the eigenvectors %d", who, l, T.precision, ev[0].precision);
+    MugiqHipCoarseField f{};
+    f.data = reinterpret_cast<void *>(uintptr_t(16) * (l + 1));  // geometry only: the validators want distinct non-NULL bodies and never read them
+    f.precision = T.precision, f.nSpin = 2, f.nColor = T.nVec;
+    long long volc = 1;
+    for (int d = 0; d < 4; d++) {
+      MUGIQ_REQUIRE(T.X[d] > 0 && T.geoBlockSize[d] >= 1, "%s: transfer %d: X / geo_block_size[%d]", who, l, d);
+      f.X[d] = T.X[d] / T.geoBlockSize[d];
+      volc *= f.X[d];
+    }
+    f.volumeCB = f.stride = (int)(volc / 2);
+    f.parity_offset = (int64_t)2 * f.nColor * f.stride;
+    lev[l] = f;
+    if (l == 0) st = validate_transfer(&T, &lev[0], who);
+    else st = validate_coarse_transfer(&T, &lev[l - 1], &lev[l], 1, who);
+    if (st) return st;
+  }
+  const MugiqHipCoarseField top = lev[nLevels - 1];
+  for (int n = 0; n < nEv; n++) {
+    const MugiqHipCoarseField &w = ev[n];
+    MUGIQ_REQUIRE(w.data && w.precision == top.precision && w.nSpin == 2 && w.nColor == top.nColor && w.volumeCB == top.volumeCB,
+                  "%s: coarse eigenvector %d does not live on the coarsest level (precision %d, nSpin 2, nColor %d, volumeCB %d)", who, n,
+                  top.precision, top.nColor, top.volumeCB);
+    for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(w.X[d] == top.X[d], "%s: coarse eigenvector %d: X[%d] = %d, expected %d", who, n, d, w.X[d], top.X[d]);
+    MUGIQ_REQUIRE(w.stride >= w.volumeCB && w.parity_offset >= (int64_t)2 * w.nColor * w.stride && w.stride == ev[0].stride &&
+                      w.parity_offset == ev[0].parity_offset, "%s: coarse eigenvector %d: stride / parity_offset", who, n);
+  }
+  lev[nLevels - 1].stride = ev[0].stride;  // the coarsest work vectors take the eigenvectors' layout: one element offset for both
+  lev[nLevels - 1].parity_offset = ev[0].parity_offset;
+  return MUGIQ_HIP_SUCCESS;
+}
+
+}  // namespace
+
+int deflate_low_modes_coarse(const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int nVec, const MugiqHipCoarseField *ev,
+                             const double *sigma, int nEv, const MugiqHipTransfer *transfers, int nLevels, int gamma5, double *overlaps_h,
+                             const MugiqHipComm *comm, hipStream_t stream, const char *who) {
+  // ---- validation, before any device work
+  MUGIQ_REQUIRE(dst != nullptr && src != nullptr && ev != nullptr && transfers != nullptr, "%s: NULL argument", who);
+  MUGIQ_REQUIRE(nVec >= 1, "%s: nVec = %d must be >= 1", who, nVec);
+  MUGIQ_REQUIRE(nEv >= 1, "%s: nEv = %d must be >= 1", who, nEv);
+  MUGIQ_REQUIRE(nLevels >= 1 && nLevels <= 8, "%s: nCoarseLevels = %d must be in [1, 8]", who, nLevels);
+  int st;
+  std::vector<MugiqHipCoarseField> lev;
+  if ((st = validate_hierarchy(transfers, nLevels, ev, nEv, &lev, who))) return st;
+  const MugiqHipCoarseField top = lev[nLevels - 1];
+  for (int n = 0; n < nEv; n++) MUGIQ_REQUIRE(sigma == nullptr || sigma[n] != 0.0, "%s: sigma[%d] is zero", who, n);
+  for (int r = 0; r < nVec; r++) {
+    if ((st = validate_spinor(&src[r], who, "src"))) return st;
+    if ((st = validate_spinor(&dst[r], who, "dst"))) return st;
+    MUGIQ_REQUIRE(same_geometry(src[r], src[0]) && same_geometry(dst[r], src[0]),
+                  "%s: src / dst vector %d differs in precision, field order or geometry from src vector 0", who, r);
+  }
+  for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(src[0].X[d] == transfers[0].X[d], "%s: src X[%d] = %d, the finest transfer's is %d", who, d, src[0].X[d], transfers[0].X[d]);
+  for (int r = 0; r < nVec; r++) {
+    uintptr_t a0, a1;
+    fine_span(dst[r], &a0, &a1);
+    for (int q = 0; q < nVec; q++) {
+      uintptr_t b0, b1;
+      fine_span(src[q], &b0, &b1);
+      const bool overlap = a0 < b1 && b0 < a1;
+      MUGIQ_REQUIRE(!overlap || (q == r && dst[r].data == src[r].data), "%s: dst vector %d overlaps src vector %d without being identical to it", who, r, q);
+    }
+  }
+  const bool multi = comm != nullptr && comm->size > 1;
+  if (comm) {
+    MUGIQ_REQUIRE(comm->size >= 1 && comm->grid[3] >= 1, "%s: invalid comm (size %d)", who, comm->size);
+    MUGIQ_REQUIRE(!multi || (comm->reduce_space && comm->gather_time && comm->bcast), "%s: a comm callback is NULL", who);
+  }
+
+  // ---- setup.  Workspace: nVec coarse vectors on every level, then C and D ([nEv][nVec] complex doubles each)
+  if ((st = debug_poison_lds_if_asked(stream))) return st;
+  const size_t P = (size_t)top.precision;
+  std::vector<size_t> levOff(nLevels);
+  size_t bytes = 0;
+  for (int l = 0; l < nLevels; l++) {
+    levOff[l] = bytes;
+    bytes += ((size_t)2 * lev[l].parity_offset * 2 * P * nVec + 255) / 256 * 256;
+  }
+  const size_t cN = (size_t)nEv * nVec, cOff = bytes;
+  bytes += 2 * cN * sizeof(Cplx<double>);
+  void *ws = nullptr;
+  if ((st = stream_workspace(&ws, bytes, stream))) return st;
+  std::vector<std::vector<MugiqHipCoarseField>> y(nLevels, std::vector<MugiqHipCoarseField>(nVec));
+  for (int l = 0; l < nLevels; l++)
+    for (int r = 0; r < nVec; r++) {
+      y[l][r] = lev[l];
+      y[l][r].data = static_cast<unsigned char *>(ws) + levOff[l] + (size_t)r * 2 * lev[l].parity_offset * 2 * P;
+    }
+  Cplx<double> *C = reinterpret_cast<Cplx<double> *>(static_cast<unsigned char *>(ws) + cOff), *D = C + cN;
+
+  // ---- c = <w, R G src>: all of src is read before any dst is written (src may alias dst)
+  if ((st = restrict_batched(y[0].data(), src, nVec, &transfers[0], gamma5, stream))) return st;
+  for (int l = 1; l < nLevels; l++)
+    if ((st = restrict_coarse_batched(y[l].data(), y[l - 1].data(), nVec, &transfers[l], stream))) return st;
+  // device tables: [eigenvector pointers][coarsest work vectors][1/sigma]
+  const size_t pv = sizeof(void *) * (size_t)nEv, py = sizeof(void *) * (size_t)nVec;
+  std::vector<unsigned char> host(pv + py + sizeof(double) * (size_t)nEv);
+  const void **hw = reinterpret_cast<const void **>(host.data());
+  void **hy = reinterpret_cast<void **>(host.data() + pv);
+  double *hi = reinterpret_cast<double *>(host.data() + pv + py);
+  for (int n = 0; n < nEv; n++) {
+    hw[n] = ev[n].data;
+    hi[n] = sigma ? 1.0 / sigma[n] : 1.0;
+  }
+  const std::vector<MugiqHipCoarseField> &yt = y[nLevels - 1];
+  for (int r = 0; r < nVec; r++) hy[r] = yt[r].data;
+  void *tab = nullptr;
+  if ((st = upload_table(&tab, host.data(), host.size(), stream))) return st;
+  const void *const *W_d = static_cast<const void *const *>(tab);
+  void *const *Y_d = reinterpret_cast<void *const *>(static_cast<unsigned char *>(tab) + pv);
+  const double *inv_d = reinterpret_cast<const double *>(static_cast<unsigned char *>(tab) + pv + py);
+  const CoarseGeom g{2 * top.nColor, top.volumeCB, ev[0].stride, ev[0].parity_offset, 2 * 2 * top.nColor * top.volumeCB};
+  const int nBlocks = (nVec + kRsRB - 1) / kRsRB;
+  if (P == 8) hipLaunchKernelGGL((coarse_overlap_kernel<double>), dim3(nEv, nBlocks), dim3(kCoThreads), 0, stream, W_d, Y_d, nVec, g, inv_d, C, D);
+  else hipLaunchKernelGGL((coarse_overlap_kernel<float>), dim3(nEv, nBlocks), dim3(kCoThreads), 0, stream, W_d, Y_d, nVec, g, inv_d, C, D);
+  MUGIQ_CHECK_HIP(hipGetLastError());
+  // ---- global overlaps: one synchronisation when they leave the device
+  if (multi || overlaps_h) {
+    std::vector<double> c(2 * cN);
+    MUGIQ_CHECK_HIP(hipMemcpyAsync(c.data(), C, sizeof(Cplx<double>) * cN, hipMemcpyDeviceToHost, stream));
+    MUGIQ_CHECK_HIP(hipStreamSynchronize(stream));
+    if (multi) {
+      if ((st = sum_over_ranks(comm, c))) return st;
+      std::vector<double> d(2 * cN);
+      for (int n = 0; n < nEv; n++)
+        for (int r = 0; r < 2 * nVec; r++) d[(size_t)n * 2 * nVec + r] = c[(size_t)n * 2 * nVec + r] * hi[n];
+      MUGIQ_CHECK_HIP(hipMemcpyAsync(D, d.data(), sizeof(Cplx<double>) * cN, hipMemcpyHostToDevice, stream));
+      MUGIQ_CHECK_HIP(hipStreamSynchronize(stream));  // d is pageable and goes out of scope
+    }
+    if (overlaps_h) std::copy(c.begin(), c.end(), overlaps_h);
+  }
+  // ---- z = sum_n w_n sigma_n^-1 c_n on the coarsest level (over the restricted vectors), up the hierarchy, off dst
+  const dim3 cgrid((g.nElem + kCoThreads - 1) / kCoThreads, nBlocks);
+  if (P == 8) hipLaunchKernelGGL((coarse_combine_kernel<double>), cgrid, dim3(kCoThreads), 0, stream, W_d, Y_d, nEv, nVec, g, D);
+  else hipLaunchKernelGGL((coarse_combine_kernel<float>), cgrid, dim3(kCoThreads), 0, stream, W_d, Y_d, nEv, nVec, g, D);
+  MUGIQ_CHECK_HIP(hipGetLastError());
+  for (int l = nLevels - 1; l >= 1; l--)
+    if ((st = mugiq_hip_prolongate_coarse_batched(y[l - 1].data(), y[l].data(), nVec, &transfers[l], stream))) return st;
+  return prolong_subtract(dst, y[0].data(), nVec, &transfers[0], stream);
+}
+
+// ---- the eigenpair check on the coarsest level ----------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kEvBlock = 8;  // eigenvectors per block: the block of the batched stencil and of the restriction
+
+// MODE 0: out[i] = (Re, Im <w_i, y_i>, |w_i|^2);  MODE 1: out[i] = (|lambda_i w_i - y_i|^2, 0, 0).  One workgroup per vector: lane t adds
+// the elements t, t + 256, ... in ascending order, then a fixed halving tree in LDS
+template <typename F, int MODE>
+__global__ __launch_bounds__(kCoThreads) void coarse_scalar_kernel(const void *const *W, const void *const *Y, CoarseGeom g, const double *lambda,
+                                                                   double *out) {
+  __shared__ double red[3][kCoThreads];
+  const int i = blockIdx.x, t = threadIdx.x;
+  const void *w = as_constant(W)[i], *y = as_constant(Y)[i];
+  const double lr = MODE == 1 ? lambda[2 * i] : 0.0, li = MODE == 1 ? lambda[2 * i + 1] : 0.0;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  for (int e = t; e < g.nElem; e += kCoThreads) {
+    const int64_t off = coarse_elem(g, e);
+    const Cplx<double> wv = ld_wide<F>(w, off), yv = ld_wide<F>(y, off);
+    if constexpr (MODE == 0) {
+      a0 = fma(wv.re, yv.re, a0);
+      a0 = fma(wv.im, yv.im, a0);
+      a1 = fma(wv.re, yv.im, a1);
+      a1 = fma(-wv.im, yv.re, a1);
+      a2 = fma(wv.re, wv.re, a2);
+      a2 = fma(wv.im, wv.im, a2);
+    } else {
+      const double dr = fma(lr, wv.re, fma(-li, wv.im, -yv.re)), di = fma(lr, wv.im, fma(li, wv.re, -yv.im));
+      a0 = fma(dr, dr, a0);
+      a0 = fma(di, di, a0);
+    }
+  }
+  red[0][t] = a0, red[1][t] = a1, red[2][t] = a2;
+  for (int s = kCoThreads / 2; s > 0; s >>= 1) {
+    __syncthreads();
+    if (t < s)
+#pragma unroll
+      for (int k = 0; k < 3; k++) red[k][t] += red[k][t + s];
+  }
+  if (t < 3) out[3 * i + t] = red[t][0];
+}
+
+size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+}  // namespace
+
+int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipTransfer *transfers, int nLevels, const MugiqHipGaugeField *gauge,
+                         const MugiqHipCloverField *clover, double kappa, int opType, int massNormalization, double *lambda_h, double *residual_h,
+                         double *sigma_h, const MugiqHipComm *comm, hipStream_t stream) {
+  const char *who = "computeEvalsCoarse";
+  // ---- validation, before any device work
+  MUGIQ_REQUIRE(ev != nullptr && transfers != nullptr && lambda_h != nullptr && residual_h != nullptr, "%s: NULL argument", who);
+  MUGIQ_REQUIRE(nEv >= 1, "%s: nEv = %d must be >= 1", who, nEv);
+  MUGIQ_REQUIRE(nLevels >= 1 && nLevels <= 8, "%s: nCoarseLevels = %d must be in [1, 8]", who, nLevels);
+  MUGIQ_REQUIRE(opType >= MUGIQ_HIP_EIG_OPERATOR_M && opType <= MUGIQ_HIP_EIG_OPERATOR_H, "%s: opType %d is none of M, Mdag, MdagM, MMdag, H", who, opType);
+  const bool normal = opType == MUGIQ_HIP_EIG_OPERATOR_MDAGM || opType == MUGIQ_HIP_EIG_OPERATOR_MMDAG;
+  MUGIQ_REQUIRE(!(normal || opType == MUGIQ_HIP_EIG_OPERATOR_H) || sigma_h != nullptr, "%s: sigma_h is NULL", who);
+  MUGIQ_REQUIRE(!massNormalization || kappa != 0.0, "%s: mass normalisation with kappa = 0", who);
+  int st, part[4];
+  std::vector<MugiqHipCoarseField> lev;
+  if ((st = validate_hierarchy(transfers, nLevels, ev, nEv, &lev, who))) return st;
+  const MugiqHipTransfer &T0 = transfers[0];
+  if ((st = check_comm(comm, part, true, who))) return st;
+  if ((st = check_gauge(gauge, T0.X, part, who))) return st;
+  const LevelGeom g0 = level_geom(&T0);
+  if (clover) {
+    if ((st = validate_clover(clover, T0.X, g0.volumeCB, who))) return st;
+    MUGIQ_REQUIRE(clover->precision == gauge->precision, "%s: clover precision %d differs from the gauge precision %d", who, clover->precision, gauge->precision);
+  }
+  if ((st = debug_poison_lds_if_asked(stream))) return st;
+
+  // ---- work memory (per-stream workspace): [room for the prolongator's packed coarse vectors][2 x 8 fine vectors with ghost zones]
+  // [2 x 8 coarse vectors on every level][lambda and sums]
+  const size_t P = (size_t)T0.precision;
+  const size_t head = align256(prolong_workspace_bytes(&T0, kEvBlock));
+  const size_t fineBody = align256((size_t)24 * g0.volumeCB * 2 * P);
+  size_t zone[4], fineBytes = fineBody;
+  for (int d = 0; d < 4; d++) {
+    zone[d] = part[d] ? align256((size_t)24 * (g0.volumeCB / T0.X[d]) * 2 * P) : 0;
+    fineBytes += 2 * zone[d];
+  }
+  std::vector<size_t> levBytes(nLevels);
+  size_t bytes = head + 2 * kEvBlock * fineBytes;
+  for (int l = 0; l < nLevels; l++) {
+    levBytes[l] = align256((size_t)2 * lev[l].parity_offset * 2 * P);
+    bytes += 2 * kEvBlock * levBytes[l];
+  }
+  const size_t scalOff = bytes;
+  bytes += sizeof(double) * 5 * kEvBlock;
+  void *ws = nullptr;
+  if ((st = stream_workspace(&ws, bytes, stream))) return st;  // (later, smaller requests of the prolongator get the same buffer)
+  unsigned char *cur = static_cast<unsigned char *>(ws) + head;
+  MugiqHipSpinorField F[2][kEvBlock];
+  for (int k = 0; k < 2; k++)
+    for (int i = 0; i < kEvBlock; i++) {
+      MugiqHipSpinorField f{};
+      f.data = cur;
+      cur += fineBody;
+      f.precision = (int)P, f.field_order = 2, f.nParity = 2, f.volumeCB = f.stride = g0.volumeCB, f.parity_offset = (int64_t)12 * g0.volumeCB;
+      for (int d = 0; d < 4; d++) {
+        f.X[d] = T0.X[d];
+        for (int b = 0; b < 2; b++) {
+          f.ghost[d][b] = part[d] ? cur : nullptr;
+          cur += zone[d];
+        }
+      }
+      F[k][i] = f;
+    }
+  // C[l][0]: the vectors in transit on level l + 1; on the coarsest level C[..][0] = A_c w and C[..][1] = the intermediate of a normal form
+  std::vector<std::vector<MugiqHipCoarseField>> C(nLevels, std::vector<MugiqHipCoarseField>(2 * kEvBlock));
+  for (int l = 0; l < nLevels; l++)
+    for (int i = 0; i < 2 * kEvBlock; i++) {
+      C[l][i] = lev[l];
+      C[l][i].data = cur;
+      cur += levBytes[l];
+    }
+  double *lambda_d = reinterpret_cast<double *>(static_cast<unsigned char *>(ws) + scalOff), *sums_d = lambda_d + 2 * kEvBlock;
+  const int L = nLevels;
+  const MugiqHipCoarseField *Y = C[L - 1].data(), *Tm = C[L - 1].data() + kEvBlock;
+  const CoarseGeom cg{2 * lev[L - 1].nColor, lev[L - 1].volumeCB, lev[L - 1].stride, lev[L - 1].parity_offset, 2 * 2 * lev[L - 1].nColor * lev[L - 1].volumeCB};
+  const double scale = massNormalization ? 0.25 / (kappa * kappa) : 1.0;  // lib/eigsolve_mugiq.cpp:302
+
+  // out = s R [g5] M^(dag) P in: up through the levels, one batched stencil call (its halo exchange included), down again
+  auto apply = [&](const MugiqHipCoarseField *out, const MugiqHipCoarseField *in, int n, int dagger, int gamma5, double s) -> int {
+    int rc;
+    const MugiqHipCoarseField *c = in;
+    for (int l = L - 1; l >= 1; l--) {
+      if ((rc = mugiq_hip_prolongate_coarse_batched(C[l - 1].data(), c, n, &transfers[l], stream))) return rc;
+      c = C[l - 1].data();
+    }
+    if ((rc = mugiq_hip_prolongate_batched(F[0], c, n, &T0, stream))) return rc;
+    if ((rc = mugiq_hip_wilson_clover_apply(F[1], F[0], n, gauge, clover, kappa, dagger ? MUGIQ_HIP_EIG_OPERATOR_MDAG : MUGIQ_HIP_EIG_OPERATOR_M, s, comm,
+                                            stream)))
+      return rc;
+    if ((rc = restrict_batched(L == 1 ? out : C[0].data(), F[1], n, &T0, gamma5, stream))) return rc;
+    for (int l = 1; l < L; l++)
+      if ((rc = restrict_coarse_batched(l == L - 1 ? out : C[l].data(), C[l - 1].data(), n, &transfers[l], stream))) return rc;
+    return MUGIQ_HIP_SUCCESS;
+  };
+  auto scalars = [&](int mode, const MugiqHipCoarseField *w, int n, double out[3 * kEvBlock]) -> int {
+    std::vector<const void *> host(2 * (size_t)n);
+    for (int i = 0; i < n; i++) host[i] = w[i].data, host[n + i] = Y[i].data;
+    void *tab = nullptr;
+    if (int rc = upload_table(&tab, host.data(), host.size() * sizeof(void *), stream)) return rc;
+    const void *const *W_d = static_cast<const void *const *>(tab);
+    if (P == 8 && mode == 0) hipLaunchKernelGGL((coarse_scalar_kernel<double, 0>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
+    else if (P == 8) hipLaunchKernelGGL((coarse_scalar_kernel<double, 1>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
+    else if (mode == 0) hipLaunchKernelGGL((coarse_scalar_kernel<float, 0>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
+    else hipLaunchKernelGGL((coarse_scalar_kernel<float, 1>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
+    MUGIQ_CHECK_HIP(hipGetLastError());
+    MUGIQ_CHECK_HIP(hipMemcpyAsync(out, sums_d, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, stream));
+    MUGIQ_CHECK_HIP(hipStreamSynchronize(stream));
+    if (comm && comm->size > 1) {
+      std::vector<double> v(out, out + 3 * n);
+      if (int rc = sum_over_ranks(comm, v)) return rc;
+      std::copy(v.begin(), v.end(), out);
+    }
+    return MUGIQ_HIP_SUCCESS;
+  };
+
+  for (int v0 = 0; v0 < nEv; v0 += kEvBlock) {
+    const int n = std::min(kEvBlock, nEv - v0);
+    const MugiqHipCoarseField *w = ev + v0;
+    switch (opType) {  // QUDA's DiracMdagM / DiracMMdag on DiracCoarse: products of the coarse operators, not R MdagM P
+    case MUGIQ_HIP_EIG_OPERATOR_M: st = apply(Y, w, n, 0, 0, scale); break;
+    case MUGIQ_HIP_EIG_OPERATOR_MDAG: st = apply(Y, w, n, 1, 0, scale); break;
+    case MUGIQ_HIP_EIG_OPERATOR_H: st = apply(Y, w, n, 0, 1, scale); break;
+    case MUGIQ_HIP_EIG_OPERATOR_MDAGM:
+      if (!(st = apply(Tm, w, n, 0, 0, 1.0))) st = apply(Y, Tm, n, 1, 0, scale);
+      break;
+    default:
+      if (!(st = apply(Tm, w, n, 1, 0, 1.0))) st = apply(Y, Tm, n, 0, 0, scale);
+    }
+    if (st) return st;
+    double sums[3 * kEvBlock];
+    if ((st = scalars(0, w, n, sums))) return st;
+    for (int i = 0; i < n; i++) {
+      const double nrm = std::sqrt(sums[3 * i + 2]);  // lambda = w^dag A_c w / ||w||   (:303, not ||w||^2)
+      lambda_h[2 * (v0 + i)] = sums[3 * i] / nrm;
+      lambda_h[2 * (v0 + i) + 1] = sums[3 * i + 1] / nrm;
+    }
+    MUGIQ_CHECK_HIP(hipMemcpyAsync(lambda_d, lambda_h + 2 * v0, sizeof(double) * 2 * n, hipMemcpyHostToDevice, stream));
+    if ((st = scalars(1, w, n, sums))) return st;  // (synchronises: lambda_h may be read again)
+    for (int i = 0; i < n; i++) {
+      residual_h[v0 + i] = std::sqrt(sums[3 * i]);  // r = ||lambda w - A_c w||   (:305-306)
+      if (normal) sigma_h[v0 + i] = std::sqrt(lambda_h[2 * (v0 + i)]);  // :311
+      else if (opType == MUGIQ_HIP_EIG_OPERATOR_H) sigma_h[v0 + i] = lambda_h[2 * (v0 + i)];
+    }
+  }
+  return MUGIQ_HIP_SUCCESS;
+}
+
+}  // namespace mugiq
+
+using namespace mugiq;
+
+extern "C" {
+
+int mugiq_hip_restrict_batched(const MugiqHipCoarseField *coarse_h, const MugiqHipSpinorField *fine_h, int nVec, const MugiqHipTransfer *transfer,
+                               int gamma5, void *stream) {
+  if (int st = validate_restrict(coarse_h, fine_h, nVec, transfer, "restrictVecs")) return st;
+  if (int dbg_ = debug_poison_lds_if_asked(static_cast<hipStream_t>(stream))) return dbg_;
+  return restrict_batched(coarse_h, fine_h, nVec, transfer, gamma5, static_cast<hipStream_t>(stream));
+}
+
+int mugiq_hip_restrict_coarse_batched(const MugiqHipCoarseField *coarser_h, const MugiqHipCoarseField *finer_h, int nVec,
+                                      const MugiqHipTransfer *transfer, void *stream) {
+  if (int st = validate_coarse_transfer(transfer, finer_h, coarser_h, nVec, "restrictVecs(coarse level)")) return st;
+  if (int dbg_ = debug_poison_lds_if_asked(static_cast<hipStream_t>(stream))) return dbg_;
+  return restrict_coarse_batched(coarser_h, finer_h, nVec, transfer, static_cast<hipStream_t>(stream));
+}
+
+int mugiq_hip_deflate_low_modes_coarse(const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec,
+                                       const MugiqHipCoarseField *coarseEvecs_h, const double *sigma_h, int nEv,
+                                       const MugiqHipTransfer *transfers_h, int nCoarseLevels, int gamma5, double *overlaps_h,
+                                       const MugiqHipComm *comm, void *stream) {
+  return deflate_low_modes_coarse(dst_h, src_h, nVec, coarseEvecs_h, sigma_h, nEv, transfers_h, nCoarseLevels, gamma5, overlaps_h, comm,
+                                  static_cast<hipStream_t>(stream), "deflateLowModesCoarse");
+}
+
+int mugiq_hip_compute_evals_coarse(const MugiqHipCoarseField *coarseEvecs_h, int nEv, const MugiqHipTransfer *transfers_h, int nCoarseLevels,
+                                   const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover, double kappa, int opType,
+                                   int massNormalization, double *lambda_h, double *residual_h, double *sigma_h, const MugiqHipComm *comm,
+                                   void *stream) {
+  return compute_evals_coarse(coarseEvecs_h, nEv, transfers_h, nCoarseLevels, gauge, clover, kappa, opType, massNormalization, lambda_h, residual_h,
+                              sigma_h, comm, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

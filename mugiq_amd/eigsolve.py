@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .fields import SpinorField, desc_array
+from .fields import SpinorField, desc_array, coarse_desc_array, transfer_desc_array
 
 # MuGiqEigOperator (include/enum_mugiq.h:22-25 of the reference, values identical) and the extension H = g5 M
 MUGIQ_EIG_OPERATOR_M, MUGIQ_EIG_OPERATOR_Mdag, MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H = range(5)
@@ -85,6 +85,24 @@ def computeEvals(eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, massNorma
     return np.array(lam).view(np.complex128).copy(), np.array(res), (np.array(sig) if has_sigma else None)
 
 
+def computeEvalsCoarse(coarseEvecs, transfer, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, massNormalization=False, comm=None, clover=None):
+    """computeEvals for eigenvectors on the coarsest level of an MG hierarchy (mugiq_hip_compute_evals_coarse): the operator is the Galerkin
+    operator R M P (MdagM / MMdag: products of the coarse operators; H: R g5 M P).  transfer: a Transfer, or the list [finest, ...]."""
+    ev = list(coarseEvecs)
+    tr = list(transfer) if isinstance(transfer, (list, tuple)) else [transfer]
+    n = len(ev)
+    lam = (ctypes.c_double * (2 * max(n, 1)))()
+    res = (ctypes.c_double * max(n, 1))()
+    sig = (ctypes.c_double * max(n, 1))()
+    keep = []
+    g = gauge.desc()
+    _lib.check(_lib.load().mugiq_hip_compute_evals_coarse(coarse_desc_array(ev) if ev else None, n, transfer_desc_array(tr) if tr else None, len(tr),
+                                                          ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), int(opType),
+                                                          int(bool(massNormalization)), lam, res, sig, _comm_ptr(comm, keep), _stream()))
+    has_sigma = int(opType) in (MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H)
+    return np.array(lam).view(np.complex128)[:n].copy(), np.array(res)[:n], (np.array(sig)[:n] if has_sigma else None)
+
+
 def projectVector(out, inp, eVecs, comm=None):
     """out = sum_i v_i <v_i, in>   (lib/eigsolve_mugiq.cpp:340-348; mugiq_hip_project_vector)"""
     ev = list(eVecs)
@@ -142,17 +160,24 @@ def format_evals(evals, evals_quda, residuals, sigmas=None):
 class Eigsolve_Mugiq:
     """The part of the reference's Eigsolve_Mugiq that runs on eigenvectors somebody else computed: eVecs (SpinorFields), the gauge
     field they belong to, kappa and the form of the operator they are eigenvectors of.  evals_quda: what the eigensolver reported
-    (printed beside the recomputed values; zero if not given).  clover: the CloverField of a Wilson-clover operator (None: Wilson)."""
+    (printed beside the recomputed values; zero if not given).  clover: the CloverField of a Wilson-clover operator (None: Wilson).
+    transfer (a Transfer or the list [finest, ...]): the computeCoarse branch -- eVecs are CoarseFields on the coarsest level and the
+    operator is the Galerkin operator (computeEvalsCoarse); projectVector and solve stay fine-level."""
 
-    def __init__(self, eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, comm=None, massNormalization=False, evals_quda=None, clover=None):
+    def __init__(self, eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, comm=None, massNormalization=False, evals_quda=None, clover=None,
+                 transfer=None):
         self.eVecs, self.gauge, self.kappa, self.opType, self.comm = list(eVecs), gauge, float(kappa), int(opType), comm
-        self.clover = clover
+        self.clover, self.transfer = clover, transfer
         self.massNormalization = bool(massNormalization)
         n = len(self.eVecs)
         self.eVals_quda = np.zeros(n, np.complex128) if evals_quda is None else np.asarray(evals_quda, np.complex128)
         self.eVals, self.evals_res, self.eVals_sigma = np.zeros(n, np.complex128), np.zeros(n), None
 
     def computeEvals(self):
+        if self.transfer is not None:
+            self.eVals, self.evals_res, self.eVals_sigma = computeEvalsCoarse(self.eVecs, self.transfer, self.gauge, self.kappa, self.opType,
+                                                                               self.massNormalization, self.comm, self.clover)
+            return self.eVals, self.evals_res, self.eVals_sigma
         self.eVals, self.evals_res, self.eVals_sigma = computeEvals(self.eVecs, self.gauge, self.kappa, self.opType, self.massNormalization,
                                                                      self.comm, self.clover)
         return self.eVals, self.evals_res, self.eVals_sigma
@@ -165,10 +190,14 @@ class Eigsolve_Mugiq:
         return lines
 
     def projectVector(self, out, inp):
+        if self.transfer is not None:
+            raise _lib.MugiqHipError("status 2: Eigsolve_Mugiq.projectVector: coarse (MG) eigenvectors are not supported")
         projectVector(out, inp, self.eVecs, self.comm)
 
     def solve(self, b, tol=1e-10, maxIter=1000, sigmas=None, x=None, allow_unconverged=False):
         """M^-1 b.  With opType H the eigenvectors (and sigmas, default: the computeEvals ones) deflate the start vector."""
+        if self.transfer is not None:
+            raise _lib.MugiqHipError("status 2: Eigsolve_Mugiq.solve: coarse (MG) eigenvectors are not supported")
         ev, sg = (), ()
         if self.opType == MUGIQ_EIG_OPERATOR_H:
             sg = self.eVals_sigma if sigmas is None else sigmas

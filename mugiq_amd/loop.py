@@ -372,6 +372,16 @@ class Loop_Mugiq:
         _lib.check(_lib.load().mugiq_hip_loop_deflate(self._handle, dd, ds, nVec, int(bool(gamma5)), buf))
         return _overlap_array(buf, nEv, nVec) if overlaps else None
 
+    def deflateCoarse(self, dst, src, gamma5=True, overlaps=False):
+        """deflateLowModesCoarse with this loop's coarse eigenvectors, sigmas, transfers, comm and stream (mugiq_hip_loop_deflate_coarse):
+        coarse (MG) loop objects only (MugiqHipError, status 2 = UNSUPPORTED, for fine-level and two-sided ones)."""
+        from .operators import _deflate_args, _overlap_buffer, _overlap_array
+        dst, src, dd, ds = _deflate_args(dst, src)
+        nEv, nVec = len(self.eVecs), len(src)
+        buf = _overlap_buffer(overlaps, nEv, nVec)
+        _lib.check(_lib.load().mugiq_hip_loop_deflate_coarse(self._handle, dd, ds, nVec, int(bool(gamma5)), buf))
+        return _overlap_array(buf, nEv, nVec) if overlaps else None
+
     def solve(self, b, kappa, tol=1e-10, maxIter=1000, x=None, allow_unconverged=False, clover=None):
         """x_r = M^-1 b_r (wilsonSolve) with this loop's gauge field, comm and stream, started from the low-mode part of its
         eigenvectors and sigmas, which must be eigenpairs of H = g5 M at this kappa (M the Wilson-clover operator with clover=CloverField).  Returns the list x; the iteration counts and true

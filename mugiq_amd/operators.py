@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .fields import SpinorField, GaugeField, desc_array, coarse_desc_array
+from .fields import SpinorField, GaugeField, desc_array, coarse_desc_array, transfer_desc_array
 
 N_GAMMA = 16
 DispDir = {"x": 0, "y": 1, "z": 2, "t": 3}          # include/enum_mugiq.h:72-78
@@ -316,3 +316,44 @@ def prolongateContractBatched(loopData_d, coarseEvecs, sigmas, transfer):
     sg = (ctypes.c_double * n)(*[float(s) for s in sigmas])
     _lib.check(_lib.load().mugiq_hip_prolongate_contract_batched(loopData_d.data_ptr(), _prec_of(loopData_d), coarse_desc_array(coarseEvecs),
                                                                  sg, n, ctypes.byref(t), _stream()))
+
+
+def restrictVecs(coarseVecs, fineVecs, transfer, gamma5=False):
+    """QUDA Transfer::R = P^dag for all vectors in one launch (mugiq_hip_restrict_batched): coarse_n = V^dag G fine_n summed over each
+    aggregate, G = g5 (gamma5) or 1.  The fine fields may differ in precision from the transfer; the coarse ones share it."""
+    n = len(fineVecs)
+    assert len(coarseVecs) == n and n >= 1
+    t = transfer.desc()
+    _lib.check(_lib.load().mugiq_hip_restrict_batched(coarse_desc_array(coarseVecs), desc_array(fineVecs), n, ctypes.byref(t),
+                                                      int(bool(gamma5)), _stream()))
+
+
+def restrictCoarseVecs(coarserVecs, finerVecs, transfer):
+    """The adjoint of prolongateCoarseEvecs for one coarse -> coarse level (mugiq_hip_restrict_coarse_batched)."""
+    n = len(finerVecs)
+    assert len(coarserVecs) == n and n >= 1
+    t = transfer.desc()
+    _lib.check(_lib.load().mugiq_hip_restrict_coarse_batched(coarse_desc_array(coarserVecs), coarse_desc_array(finerVecs), n,
+                                                             ctypes.byref(t), _stream()))
+
+
+def _transfer_list(transfer):
+    return list(transfer) if isinstance(transfer, (list, tuple)) else [transfer]
+
+
+def deflateLowModesCoarse(dst, src, coarseEvecs, transfer, sigmas=None, gamma5=True, comm=None, overlaps=False):
+    """deflateLowModes for eigenvectors on the coarsest level of an MG hierarchy, v_n = P w_n never stored
+    (mugiq_hip_deflate_low_modes_coarse): dst_r <- dst_r - P sum_n w_n sigma_n^-1 c_nr,  c_nr = <w_n, R G src_r>.
+    transfer: a Transfer, or the list [finest, level 1 -> 2, ...] as for Loop_Mugiq.  Everything else as deflateLowModes."""
+    dst, src, dd, ds = _deflate_args(dst, src)
+    ev, tr = list(coarseEvecs), _transfer_list(transfer)
+    nEv, nVec = len(ev), len(src)
+    if sigmas is not None and len(sigmas) != nEv:
+        raise _lib.MugiqHipError("deflateLowModesCoarse: %d sigmas for %d eigenvectors" % (len(sigmas), nEv))
+    sg = (ctypes.c_double * nEv)(*[float(s) for s in sigmas]) if sigmas is not None else None
+    c = comm.c_struct() if comm is not None else None
+    buf = _overlap_buffer(overlaps, nEv, nVec)
+    _lib.check(_lib.load().mugiq_hip_deflate_low_modes_coarse(
+        dd, ds, nVec, coarse_desc_array(ev) if ev else None, sg, nEv, transfer_desc_array(tr) if tr else None, len(tr), int(bool(gamma5)), buf,
+        ctypes.cast(ctypes.byref(c), ctypes.c_void_p) if c is not None else None, _stream()))
+    return _overlap_array(buf, nEv, nVec) if overlaps else None
