@@ -45,10 +45,14 @@ template <typename F, typename A> struct ProlongArgs {
   Cplx<A> *loop;                // (CONTRACT) [16][V]
 };
 
-template <typename F, typename A, int ORDER, bool WRITE, bool CONTRACT>
+// STAGED: the V tile of the workgroup's 16 sites is copied to the LDS once and read from there by all 16 eigenvector groups.  An fp64 tile
+// of more than 53 null vectors (12 n_vec 16 sites x 16 B) does not fit the 160 KB of a workgroup: those transfers take the kernel with
+// STAGED = false, which reads V(x; :, j) from global memory (L2) in the same place of the pipeline.  Same sums in the same order.
+constexpr size_t kPrMaxLds = 160 * 1024;
+template <typename F, typename A, int ORDER, bool WRITE, bool CONTRACT, bool STAGED>
 __global__ __launch_bounds__(kPrTile *kPrGroups) void prolong_kernel(ProlongArgs<F, A> a) {
   extern __shared__ __align__(16) unsigned char smem[];
-  Cplx<F> *Vt = reinterpret_cast<Cplx<F> *>(smem);  // [12*NV][16 sites]
+  Cplx<F> *Vt = reinterpret_cast<Cplx<F> *>(smem);  // [12*NV][16 sites]  (STAGED)
   const int tilesPerParity = (a.volumeCB + kPrTile - 1) / kPrTile;
   const int pty = blockIdx.x / tilesPerParity;
   const int x0 = (blockIdx.x - pty * tilesPerParity) * kPrTile;
@@ -56,10 +60,13 @@ __global__ __launch_bounds__(kPrTile *kPrGroups) void prolong_kernel(ProlongArgs
   const int x_cb = x0 + site;
   const bool valid = x_cb < a.volumeCB;
 
-  const int nPl = 12 * a.NV;
-  for (int k = g; k < nPl; k += kPrGroups)
-    Vt[k * kPrTile + site] = valid ? a.V[pty * a.Vpo + (int64_t)k * a.Vstride + x_cb] : Cplx<F>{F(0), F(0)};
-  __syncthreads();
+  if constexpr (STAGED) {
+    const int nPl = 12 * a.NV;
+    for (int k = g; k < nPl; k += kPrGroups)
+      Vt[k * kPrTile + site] = valid ? a.V[pty * a.Vpo + (int64_t)k * a.Vstride + x_cb] : Cplx<F>{F(0), F(0)};
+    __syncthreads();
+  }
+  const Cplx<F> *Vg = a.V + pty * a.Vpo + (valid ? x_cb : a.volumeCB - 1);  // (!STAGED; a lane past the end reads the last site and stores nothing)
 
   // aggregate of this fine site: coarse coordinates = fine / block, even-odd on the coarse lattice
   int c[4] = {0, 0, 0, 0};
@@ -99,7 +106,10 @@ __global__ __launch_bounds__(kPrTile *kPrGroups) void prolong_kernel(ProlongArgs
       sp[chi] = *as_global(reinterpret_cast<const vec2 *>(c0 + (int64_t)(chi * a.NV + j_) * a.Cstride));               \
       sp[2 + chi] = *as_global(reinterpret_cast<const vec2 *>(c1 + (int64_t)(chi * a.NV + j_) * a.Cstride));           \
     }                                                                                                                  \
-    _Pragma("unroll") for (int sc = 0; sc < 12; sc++) sv[sc] = Vt[(sc * a.NV + j_) * kPrTile + site];                  \
+    _Pragma("unroll") for (int sc = 0; sc < 12; sc++) {                                                                \
+      if constexpr (STAGED) sv[sc] = Vt[(sc * a.NV + j_) * kPrTile + site];                                            \
+      else sv[sc] = Vg[(int64_t)(sc * a.NV + j_) * a.Vstride];                                                         \
+    }                                                                                                                  \
   }
 #define MUGIQ_PR_COMPUTE(sv, sp)                                                                                       \
   {                                                                                                                    \
@@ -250,13 +260,21 @@ static int launch_prolong(const MugiqHipTransfer *T, const MugiqHipCoarseField *
   a.nVec = nVec;
   a.inv_sigma = reinterpret_cast<const A *>(static_cast<unsigned char *>(dev) + 2 * pb);
   a.loop = static_cast<Cplx<A> *>(loop_d);
-  size_t shmem = sizeof(Cplx<F>) * 12 * (size_t)T->nVec * kPrTile;
-  const size_t redBytes = sizeof(A) * 16 * kPrGroups * kPrTile;
-  if (CONTRACT && shmem < redBytes) shmem = redBytes;
-  auto kern = prolong_kernel<F, A, ORDER, WRITE, CONTRACT>;
+  const size_t tileBytes = sizeof(Cplx<F>) * 12 * (size_t)T->nVec * kPrTile;
+  const size_t redBytes = CONTRACT ? sizeof(A) * 16 * kPrGroups * kPrTile : 0;
+  const int tiles = 2 * ((a.volumeCB + kPrTile - 1) / kPrTile);
+  if (tileBytes > kPrMaxLds) {  // the V tile does not fit the LDS (fp64, n_vec > 53)
+    if constexpr (sizeof(F) == 8) {
+      hipLaunchKernelGGL((prolong_kernel<F, A, ORDER, WRITE, CONTRACT, false>), dim3(tiles), dim3(kPrTile * kPrGroups), redBytes, stream, a);
+      MUGIQ_CHECK_HIP(hipGetLastError());
+      return MUGIQ_HIP_SUCCESS;
+    }
+    return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "prolongateEvec: n_vec = %d needs %zu bytes of LDS", T->nVec, tileBytes);
+  }
+  const size_t shmem = std::max(tileBytes, redBytes);
+  auto kern = prolong_kernel<F, A, ORDER, WRITE, CONTRACT, true>;
   if (shmem > 64 * 1024)
     MUGIQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  const int tiles = 2 * ((a.volumeCB + kPrTile - 1) / kPrTile);
   hipLaunchKernelGGL(kern, dim3(tiles), dim3(kPrTile * kPrGroups), shmem, stream, a);
   MUGIQ_CHECK_HIP(hipGetLastError());
   return MUGIQ_HIP_SUCCESS;

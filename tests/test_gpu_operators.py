@@ -468,7 +468,10 @@ def _mg_problem(X, bs, nvec, nev, seed):
                                            # shapes the matrix-pipe form takes for fp64 FLOAT2 (n_vec 8 | 16 | 24, aggregates of 16 k sites):
                                            # ragged eigenvector counts, every wave with blocks, two passes (> 192 eigenvectors)
                                            ((8, 8, 4, 4), (4, 4, 2, 2), 16, 19), ((4, 4, 8, 8), (2, 2, 4, 4), 8, 70), ((4, 4, 4, 4), (2, 2, 2, 2), 8, 203),
-                                           ((8, 8, 4, 4), (4, 2, 2, 2), 24, 66)])
+                                           ((8, 8, 4, 4), (4, 2, 2, 2), 24, 66),
+                                           # n_vec 64, the largest a transfer may have: an fp64 V tile of 16 sites (192 KB) exceeds the LDS of a
+                                           # workgroup, the vector kernel reads V from global memory; more than 32 eigenvectors: a second round
+                                           ((4, 4, 4, 4), (2, 2, 2, 2), 64, 35)])
 def test_prolongator_matches_oracle(hip, prec, order, X, bs, nvec, nev, monkeypatch):
     V, phis, Xc = _mg_problem(X, bs, nvec, nev, 71)
     cdt = _np_c(prec)
@@ -520,7 +523,8 @@ def test_coarse_to_coarse_prolongator_matches_oracle(hip, prec, X, bs, ncf, nvec
 @pytest.mark.parametrize("prec,lprec", [(8, 8), (4, 4), (4, 8)])
 @pytest.mark.parametrize("X,bs,nvec,nev", [((8, 8, 8, 8), (4, 4, 4, 4), 24, 37), ((4, 4, 4, 6), (2, 2, 2, 1), 3, 2),
                                            ((4, 4, 4, 4), (2, 2, 2, 2), 32, 9), ((8, 8, 4, 4), (4, 4, 2, 2), 12, 5),
-                                           ((8, 4, 12, 4), (2, 2, 3, 2), 16, 11), ((4, 8, 4, 4), (2, 4, 2, 1), 8, 3)])
+                                           ((8, 4, 12, 4), (2, 2, 3, 2), 16, 11), ((4, 8, 4, 4), (2, 4, 2, 1), 8, 3),
+                                           ((4, 4, 4, 4), (2, 2, 2, 2), 64, 5)])      # direct kernel only; fp64: V tile larger than the LDS
 def test_fused_prolong_contract_matches_oracle(hip, prec, lprec, X, bs, nvec, nev, plan, monkeypatch):
     """MG ultra-local loop: (P c_n)^dag G (P c_n) summed over n, fine vectors never written.  Two plans behind one entry
     point: "coarse" = outer product of the eigenvectors on the coarse grid + one congruence per fine site (n_vec 8, 12,

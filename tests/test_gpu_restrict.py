@@ -1,7 +1,9 @@
 """GPU tests of the restriction R = P^dag (mugiq_hip_restrict_batched, mugiq_hip_restrict_coarse_batched) and of the low-mode deflation
 through the coarse space (mugiq_hip_deflate_low_modes_coarse, mugiq_hip_loop_deflate_coarse) against the numpy reference of
-tests/restrict_ref.py, the library's own prolongator and the fine-level deflation.  Tolerances: relative in the max norm (util.rel_err),
-1e-13 for fp64 and 2e-6 for fp32 storage, the bounds of the stencil and the prolongator."""
+tests/restrict_ref.py, the library's own prolongator and the fine-level deflation, and of the eigenpair check on the coarsest level
+(mugiq_hip_compute_evals_coarse) against the same reference through the whole hierarchy and against true eigenvectors of the dense
+Galerkin operator.  Tolerances: relative in the max norm (util.rel_err), 1e-13 for fp64 and 2e-6 for fp32 storage, the bounds of the
+stencil and the prolongator."""
 import functools
 
 import numpy as np
@@ -18,6 +20,11 @@ pytestmark = pytest.mark.gpu
 
 TOL = {8: 1e-13, 4: 2e-6}
 SHAPES = [((8, 8, 8, 8), (4, 4, 4, 4), 24), ((8, 4, 12, 4), (2, 2, 3, 2), 6), ((4, 4, 4, 6), (2, 2, 2, 1), 3), ((8, 8, 4, 4), (4, 2, 2, 2), 24)]
+# restrict_kernel walks the null vectors in passes of 24 and the sites of an aggregate in strides of 32 slots: n_vec 25 (a second pass with
+# one live lane group), 48 (two full passes), 64 (three, the last ragged; the largest validate_transfer admits); aggregates of 48 and 72
+# sites (some slots make one trip more than others); both at once
+RAGGED_SHAPES = [((4, 4, 4, 4), (2, 2, 2, 2), 25), ((4, 4, 4, 4), (2, 2, 2, 2), 48), ((4, 4, 4, 4), (2, 2, 2, 2), 64), ((12, 4, 4, 4), (6, 2, 2, 2), 6),
+                 ((12, 12, 4, 4), (6, 6, 2, 1), 25)]
 COUNTS = (1, 5, 9, 19)         # ragged against the block of 8 right-hand sides
 NMAX = max(COUNTS)
 
@@ -49,7 +56,7 @@ def _finest_problem(X, bs, nvec, pv, pf):
 @pytest.mark.parametrize("gamma5", [False, True])
 @pytest.mark.parametrize("order", [2, 4])
 @pytest.mark.parametrize("prec", [8, 4])
-@pytest.mark.parametrize("X,bs,nvec", SHAPES)
+@pytest.mark.parametrize("X,bs,nvec", SHAPES + RAGGED_SHAPES)
 def test_restrict_matches_numpy(hip, X, bs, nvec, prec, order, gamma5, record_max):
     V, psi, ref = _finest_problem(X, bs, nvec, prec, prec)
     T = hip.Transfer(X, nvec, bs, 2, prec).set_logical(V)
@@ -107,12 +114,7 @@ def test_coarse_to_coarse_restriction_matches_numpy(hip, prec, X, bs, ncf, nvec,
         hip.restrictCoarseVecs(out, fin, hip.Transfer(X, nvec, bs, 2, prec, fine_spin=2, fine_color=ncf))
 
 
-@pytest.mark.parametrize("mfma", ["0", "1"])
-def test_adjoint_of_the_library_prolongator(hip, mfma, monkeypatch, record_max):
-    """<R psi, phi> = <psi, P phi> with the library's prolongator in both of its forms, to 1e-13 of |psi| |P phi|; R P phi = phi for a
-    block-orthonormal V.  8 8 4 4 with 4 4 2 2 aggregates and n_vec 16: a shape the matrix-pipe prolongator takes."""
-    monkeypatch.setenv("MUGIQ_HIP_PROLONG_MFMA", mfma)
-    X, bs, nvec, n = (8, 8, 4, 4), (4, 4, 2, 2), 16, 5
+def _check_adjoint_of_the_prolongator(hip, X, bs, nvec, n, record_max):
     rng = np.random.default_rng(77)
     vcb = int(np.prod(X)) // 2
     V = rr.block_orthonormal(_c(rng, (2, vcb, 4, 3, nvec)), X, bs)
@@ -137,12 +139,22 @@ def test_adjoint_of_the_library_prolongator(hip, mfma, monkeypatch, record_max):
         assert e < 1e-13, (k, e)
 
 
-@pytest.mark.parametrize("poison", [False, True])
-@pytest.mark.parametrize("prec,order", [(8, 2), (4, 4)])
-def test_restrict_is_bitwise_reproducible_and_batch_independent(hip, prec, order, poison, monkeypatch):
-    if poison:
-        monkeypatch.setenv("MUGIQ_HIP_DEBUG_POISON_LDS", "1")
-    X, bs, nvec = (8, 8, 4, 4), (4, 2, 2, 2), 24
+@pytest.mark.parametrize("mfma", ["0", "1"])
+def test_adjoint_of_the_library_prolongator(hip, mfma, monkeypatch, record_max):
+    """<R psi, phi> = <psi, P phi> with the library's prolongator in both of its forms, to 1e-13 of |psi| |P phi|; R P phi = phi for a
+    block-orthonormal V.  8 8 4 4 with 4 4 2 2 aggregates and n_vec 16: a shape the matrix-pipe prolongator takes."""
+    monkeypatch.setenv("MUGIQ_HIP_PROLONG_MFMA", mfma)
+    _check_adjoint_of_the_prolongator(hip, (8, 8, 4, 4), (4, 4, 2, 2), 16, 5, record_max)
+
+
+@pytest.mark.parametrize("X,bs,nvec", RAGGED_SHAPES)
+def test_adjoint_of_the_vector_prolongator_beyond_one_pass(hip, X, bs, nvec, record_max):
+    """The same two properties where restrict_kernel makes more than one null-vector pass or a ragged slot walk.  None of these n_vec is
+    8, 16 or 24, so the prolongator is the library's vector kernel (prolong_mfma_plan returns -1), which loops over j in one piece."""
+    _check_adjoint_of_the_prolongator(hip, X, bs, nvec, 9, record_max)
+
+
+def _check_bitwise_and_batch_independent(hip, X, bs, nvec, prec, order):
     V, psi, _ = _finest_problem(X, bs, nvec, prec, prec)
     T = hip.Transfer(X, nvec, bs, 2, prec).set_logical(V)
     ff = [hip.SpinorField(X, prec, order).set_logical(p) for p in psi]
@@ -158,11 +170,32 @@ def test_restrict_is_bitwise_reproducible_and_batch_independent(hip, prec, order
         assert torch.equal(_bits(alone[0].data), _bits(a[k].data)), k
 
 
+@pytest.mark.parametrize("poison", [False, True])
+@pytest.mark.parametrize("prec,order", [(8, 2), (4, 4)])
+def test_restrict_is_bitwise_reproducible_and_batch_independent(hip, prec, order, poison, monkeypatch):
+    if poison:
+        monkeypatch.setenv("MUGIQ_HIP_DEBUG_POISON_LDS", "1")
+    _check_bitwise_and_batch_independent(hip, (8, 8, 4, 4), (4, 2, 2, 2), 24, prec, order)
+
+
+@pytest.mark.parametrize("poison", [False, True])
+@pytest.mark.parametrize("prec,order", [(8, 2), (4, 4)])
+@pytest.mark.parametrize("X,bs,nvec", [RAGGED_SHAPES[0], RAGGED_SHAPES[4]])
+def test_restrict_beyond_one_pass_is_bitwise_reproducible_and_batch_independent(hip, X, bs, nvec, prec, order, poison, monkeypatch):
+    """n_vec 25: the accumulators are zeroed again and the LDS rows reused for the second pass, with stale first-pass sums (or the poison)
+    in the rows of the lanes that have no null vector left; with 72-site aggregates the slots also differ in their trip count."""
+    if poison:
+        monkeypatch.setenv("MUGIQ_HIP_DEBUG_POISON_LDS", "1")
+    _check_bitwise_and_batch_independent(hip, X, bs, nvec, prec, order)
+
+
 # ---- deflation through the coarse space -------------------------------------------------------------------------------------------
-def _hierarchy(hip, levels, rng, orthonormal=False, prec=8, pad=0):
+def _hierarchy(hip, levels, rng, orthonormal=False, prec=8, pad=0, shape=None):
     """levels = 1: 8 8 4 4 with 4 2 2 2 aggregates, n_vec 8.  levels = 2: the hierarchy of test_driver_mg_multilevel_hierarchy,
-    8^3 x 16 -> 4^3 x 8 -> 2^3 x 4 with n_vec 8 / 6."""
-    if levels == 1:
+    8^3 x 16 -> 4^3 x 8 -> 2^3 x 4 with n_vec 8 / 6.  shape = (X0, aggregates per level, n_vec per level): that hierarchy instead."""
+    if shape is not None:
+        X0, bss, nvecs = shape
+    elif levels == 1:
         X0, bss, nvecs = (8, 8, 4, 4), [(4, 2, 2, 2)], [8]
     else:
         X0, bss, nvecs = (8, 8, 8, 16), [(2, 2, 2, 2), (2, 2, 2, 2)], [8, 6]
@@ -318,28 +351,6 @@ def test_coarse_deflation_process_grids(grid, force, tmp_path):
 
 
 # ---- the eigenpair check on the coarsest level ------------------------------------------------------------------------------------
-def _coarse_evals_reference(ws, V, X, bs, Uo, A_eo, kappa, op, scale):
-    """lambda, r, sigma of Eigsolve_Mugiq::computeEvals for A_c built from orc.prolongate, the numpy Wilson(-clover) operator and
-    restrict_ref: M_c = R M P, M_c^dag = R M^dag P, MdagM = M_c^dag M_c, MMdag = M_c M_c^dag, H = R g5 M P."""
-    import clover_ref as cr
-    import wilson_ref as wr
-
-    def Mc(w, dagger=False, gamma5=False):
-        f = orc.prolongate(w, V, X, bs)
-        f = cr.clover_M(f, Uo, A_eo, kappa, X, dagger=dagger) if A_eo is not None else wr.wilson_M(f, Uo, kappa, X, dagger=dagger)
-        return rr.restrict(f, V, X, bs, 2, gamma5)
-    lam, res = [], []
-    for w in ws:
-        y = {0: lambda: Mc(w), 1: lambda: Mc(w, True), 2: lambda: Mc(Mc(w), True), 3: lambda: Mc(Mc(w, True)), 4: lambda: Mc(w, gamma5=True)}[op]()
-        y = scale * y
-        l = np.vdot(w, y) / np.linalg.norm(w)
-        lam.append(l)
-        res.append(np.linalg.norm(l * w - y))
-    lam, res = np.array(lam), np.array(res)
-    sig = np.sqrt(lam.real) if op in (2, 3) else lam.real if op == 4 else None
-    return lam, res, sig
-
-
 @functools.lru_cache(maxsize=None)
 def _evals_problem(nvec, with_clover):
     import clover_ref as cr
@@ -377,7 +388,7 @@ def test_coarse_evals_match_numpy(hip, nvec, with_clover, mass_norm, record_max)
     scale = 0.25 / kappa ** 2 if mass_norm else 1.0
     for op in range(5):
         lam, res, sig = hip.computeEvalsCoarse(cw, T, gauge, kappa, op, mass_norm, clover=C)
-        wl, wr_, wsg = _coarse_evals_reference(ws, V, X, bs, Uo, A_eo, kappa, op, scale)
+        wl, wr_, wsg = rr.coarse_evals_reference(ws, [V], [X], [bs], Uo, A_eo, kappa, op, scale)
         e = max(rel_err(lam, wl), rel_err(res, wr_), 0.0 if wsg is None else rel_err(sig, wsg))
         record_max("coarse_evals", e)
         assert e < 1e-12, (op, e)
@@ -430,3 +441,279 @@ def test_eigsolve_with_transfer_prints_the_reference_lines(hip, capsys):
     assert re.fullmatch(r"Mugiq-Quda: Eval\[0000\] = [+-]\d\.\d{16}e[+-]\d\d [+-]\d\.\d{16}e[+-]\d\d , .* , Residual = \+\d\.\d{16}e[+-]\d\d", lines[2])
     with pytest.raises(hip.MugiqHipError, match="status 2"):
         es.solve([])
+
+
+# ---- the eigenpair check beyond one level, one rank, fp64 and unpadded fields ---------------------------------------------------------
+KAPPA = 0.12
+# 4 4 4 8 -> 2 2 2 4 -> 2 2 2 2 (n_vec 8: 16-site aggregates, the matrix-pipe prolongator on the fp64 FLOAT2 work vectors; then n_vec 6) and
+# 4 4 4 8 -> 2 2 2 4 -> 2 2 2 4 -> 2 2 2 2 with n_vec 4 / 5 / 3
+MULTI_LEVEL = {2: ((4, 4, 4, 8), [(2, 2, 2, 2), (1, 1, 1, 2)], [8, 6]), 3: ((4, 4, 4, 8), [(2, 2, 2, 2), (1, 1, 1, 1), (1, 1, 1, 2)], [4, 5, 3])}
+# 4^4 with 2^4 aggregates and n_vec 4 (coarse dimension 16 * 2 * 4 = 128), and one more level with 1 1 1 1 aggregates and n_vec 3 (96)
+GALERKIN = {1: ((4, 4, 4, 4), [(2, 2, 2, 2)], [4]), 2: ((4, 4, 4, 4), [(2, 2, 2, 2), (1, 1, 1, 1)], [4, 3])}
+
+
+@functools.lru_cache(maxsize=None)
+def _links(X, with_clover):
+    """random SU(3) links on the single periodic domain X and, with clover, the blocks of the clover term at coefficient 0.17"""
+    import clover_ref as cr
+    from util import random_gauge_lex
+    U_lex = random_gauge_lex(np.random.default_rng(4400 + sum(X)), X)
+    return orc.extended_gauge_from_global(U_lex, (0, 0, 0, 0), (1, 1, 1, 1), (0, 0, 0, 0)), (cr.clover_blocks_eo(U_lex, 0.17, X) if with_clover else None)
+
+
+def _device_operator(hip, X, with_clover, prec=8):
+    """the gauge and clover fields of the operator, and the links and dense 12 x 12 clover blocks as the device stores them"""
+    Uo, blocks = _links(tuple(X), with_clover)
+    gauge = hip.GaugeField(X, (0, 0, 0, 0), prec).set_logical(Uo)
+    C = hip.CloverField(X, prec).set_logical(blocks) if with_clover else None
+    return gauge, C, gauge.get_logical().astype(np.complex128), (_dense12(C.get_logical().astype(np.complex128)) if with_clover else None)
+
+
+def _evals_hierarchy(hip, shape, prec=8, nev=9):
+    """the hierarchy `shape` with random null vectors, and nev random coarse vectors on its coarsest level, all as stored"""
+    rng = np.random.default_rng(700 + len(shape[1]))
+    Xs, bss, nvecs, Vs, Ts = _hierarchy(hip, len(shape[1]), rng, prec=prec, shape=shape)
+    ws = [_c(rng, (2, int(np.prod(Xs[-1])) // 2, 2, nvecs[-1])).astype(_cdt(prec)).astype(np.complex128) for _ in range(nev)]
+    cw = [hip.CoarseField(Xs[-1], nvecs[-1], prec).set_logical(w) for w in ws]
+    return Xs, bss, Vs, Ts, ws, cw
+
+
+def _evals_err(got, want):
+    """the largest relative deviation (max norm over the vectors) of lambda, r and sigma"""
+    assert (got[2] is None) == (want[2] is None)
+    return max(rel_err(got[0], want[0]), rel_err(got[1], want[1]), 0.0 if want[2] is None else rel_err(got[2], want[2]))
+
+
+def _same_bits(a, b):
+    return all((x is None and y is None) or np.array_equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("mass_norm", [False, True])
+@pytest.mark.parametrize("with_clover", [False, True])
+@pytest.mark.parametrize("levels", [2, 3])
+def test_coarse_evals_multilevel_match_numpy(hip, levels, with_clover, mass_norm, record_max):
+    """Two and three levels on 4 4 4 8, 9 random vectors on the coarsest level (two blocks, the second of one vector): lambda, r and sigma
+    of all five forms against the numpy reference through the whole hierarchy, to the 1e-12 of the one-level test."""
+    shape = MULTI_LEVEL[levels]
+    gauge, C, Us, A_eo = _device_operator(hip, shape[0], with_clover)
+    Xs, bss, Vs, Ts, ws, cw = _evals_hierarchy(hip, shape)
+    scale = 0.25 / KAPPA ** 2 if mass_norm else 1.0
+    for op in range(5):
+        got = hip.computeEvalsCoarse(cw, Ts, gauge, KAPPA, op, mass_norm, clover=C)
+        e = _evals_err(got, rr.coarse_evals_reference(ws, Vs, Xs[:-1], bss, Us, A_eo, KAPPA, op, scale))
+        record_max("coarse_evals_levels%d" % levels, e)
+        assert e < 1e-12, (op, e)
+
+
+@pytest.mark.parametrize("with_clover", [False, True])
+def test_coarse_evals_two_levels_agree_without_the_matrix_pipe_prolongator(hip, with_clover, monkeypatch, record_max):
+    """The two-level case (n_vec 8 on 16-site aggregates: prolong_mfma_plan takes the fp64 FLOAT2 work vectors) against the same calls with
+    MUGIQ_HIP_PROLONG_MFMA=0, the vector prolongator: 1e-13."""
+    shape = MULTI_LEVEL[2]
+    gauge, C, _, _ = _device_operator(hip, shape[0], with_clover)
+    Xs, bss, Vs, Ts, ws, cw = _evals_hierarchy(hip, shape)
+    for mass_norm in (False, True):
+        for op in range(5):
+            monkeypatch.delenv("MUGIQ_HIP_PROLONG_MFMA", raising=False)
+            default = hip.computeEvalsCoarse(cw, Ts, gauge, KAPPA, op, mass_norm, clover=C)
+            monkeypatch.setenv("MUGIQ_HIP_PROLONG_MFMA", "0")
+            vector = hip.computeEvalsCoarse(cw, Ts, gauge, KAPPA, op, mass_norm, clover=C)
+            e = _evals_err(vector, default)
+            record_max("coarse_evals_mfma_vs_vector", e)
+            assert e < 1e-13, (mass_norm, op, e)
+
+
+def _hermitian_from_lower(B):
+    """6 x 6 blocks as a CloverField keeps them: the real part of the diagonal and the strictly lower triangle, the upper one implied"""
+    L = np.tril(B, -1)
+    return L + np.conj(np.swapaxes(L, -1, -2)) + np.real(np.diagonal(B, axis1=-2, axis2=-1))[..., None] * np.eye(6)
+
+
+@functools.lru_cache(maxsize=None)
+def _dense_galerkin(levels, with_clover, gamma5):
+    """R [g5] M P of the hierarchy GALERKIN[levels] as a dense matrix on the (parity, x_cb, spin, colour) index of its coarsest level, column
+    by column from unit vectors through the numpy reference; with the hierarchy (host arrays only, fp64: what the device will store).
+    The null vectors of the finest level are random and not orthonormal (R P is not the identity); those of a coarser level are
+    block-orthonormal, because random ones there make M_c^dag M_c span six orders of magnitude, and a relative bound on its lowest
+    eigenvalues would then measure fp64 rounding (1e-16 of the largest one), in numpy as on the device, instead of the operator."""
+    X0, bss, nvecs = GALERKIN[levels]
+    rng = np.random.default_rng(8100 + levels)
+    Xs, Vs = [X0], []
+    for l in range(levels):
+        ns, nc = (4, 3) if l == 0 else (2, nvecs[l - 1])
+        V = _c(rng, (2, int(np.prod(Xs[l])) // 2, ns, nc, nvecs[l])) / np.sqrt(ns * nc * nvecs[l])
+        Vs.append(V if l == 0 else rr.block_orthonormal(V, Xs[l], bss[l], 1))
+        Xs.append(tuple(Xs[l][d] // bss[l][d] for d in range(4)))
+    Uo, blocks = _links(X0, with_clover)
+    A_eo = _dense12(_hermitian_from_lower(blocks)) if with_clover else None
+    shape = (2, int(np.prod(Xs[-1])) // 2, 2, nvecs[-1])
+    N = int(np.prod(shape))
+    A = np.zeros((N, N), dtype=np.complex128)
+    for i in range(N):
+        e = np.zeros(N, dtype=np.complex128)
+        e[i] = 1.0
+        A[:, i] = rr.galerkin_apply(e.reshape(shape), Vs, Xs[:-1], bss, Uo, A_eo, KAPPA, gamma5=gamma5).reshape(N)
+    return A, Xs, bss, nvecs, Vs, shape
+
+
+def _galerkin_fields(hip, levels, with_clover, gamma5, vectors):
+    A, Xs, bss, nvecs, Vs, shape = _dense_galerkin(levels, with_clover, gamma5)
+    Ts = [hip.Transfer(Xs[l], nvecs[l], bss[l], 2 if l == 0 else 1, 8, fine_spin=Vs[l].shape[2], fine_color=Vs[l].shape[3]).set_logical(Vs[l])
+          for l in range(levels)]
+    Uo, blocks = _links(Xs[0], with_clover)
+    gauge = hip.GaugeField(Xs[0], (0, 0, 0, 0), 8).set_logical(Uo)
+    C = hip.CloverField(Xs[0], 8).set_logical(blocks) if with_clover else None
+    cw = [hip.CoarseField(Xs[-1], nvecs[-1], 8).set_logical(v.reshape(shape)) for v in vectors]
+    return cw, Ts, gauge, C
+
+
+@pytest.mark.parametrize("with_clover", [False, True])
+def test_coarse_evals_of_true_eigenvectors_of_the_hermitian_galerkin_operator(hip, with_clover, record_max):
+    """H_c = R g5 M P built densely in numpy (128 x 128) is Hermitian to 1e-13 of its largest entry; its 9 eigenvectors of smallest
+    |lambda| (numpy eigh, unit norm) are eigenpairs for computeEvalsCoarse too: lambda to 1e-12 relative, sigma = lambda, and
+    r < 1e-12 max |eigenvalue| (the spectral norm: the scale of the rounding of H_c w, about 10^3 operations of eps 1e-16 each)."""
+    H = _dense_galerkin(1, with_clover, True)[0]
+    assert np.max(np.abs(H - H.conj().T)) < 1e-13 * np.max(np.abs(H))
+    ev, Q = np.linalg.eigh(H)
+    pick = np.argsort(np.abs(ev))[:9]
+    cw, Ts, gauge, C = _galerkin_fields(hip, 1, with_clover, True, [Q[:, i] for i in pick])
+    lam, res, sig = hip.computeEvalsCoarse(cw, Ts, gauge, KAPPA, hip.MUGIQ_EIG_OPERATOR_H, clover=C)
+    el, er = np.max(np.abs(lam - ev[pick]) / np.abs(ev[pick])), np.max(res) / np.max(np.abs(ev))
+    print("H_c eigenpairs: lambda %.3e, residual / norm %.3e, smallest / largest |eigenvalue| %.3e" % (el, er, np.min(np.abs(ev)) / np.max(np.abs(ev))))
+    record_max("coarse_evals_galerkin_lambda", el)
+    record_max("coarse_evals_galerkin_residual", er)
+    assert el < 1e-12, el
+    assert np.array_equal(sig, lam.real) and np.max(np.abs(sig - ev[pick]) / np.abs(ev[pick])) < 1e-12
+    assert er < 1e-12, er
+
+
+@pytest.mark.parametrize("with_clover", [False, True])
+@pytest.mark.parametrize("levels", [1, 2])
+def test_coarse_evals_of_true_eigenvectors_of_the_normal_galerkin_operator(hip, levels, with_clover, record_max):
+    """M_c = R M P built densely in numpy; the 9 lowest eigenvectors of M_c^dag M_c are eigenpairs of the library's MdagM form (which
+    applies R M P and then R M^dag P: that this is (R M P)^dag is part of what is tested): lambda to 1e-12 relative, sigma = sqrt(lambda),
+    r < 1e-12 max eigenvalue."""
+    Mc = _dense_galerkin(levels, with_clover, False)[0]
+    ev, Q = np.linalg.eigh(Mc.conj().T @ Mc)
+    pick = np.argsort(np.abs(ev))[:9]
+    cw, Ts, gauge, C = _galerkin_fields(hip, levels, with_clover, False, [Q[:, i] for i in pick])
+    lam, res, sig = hip.computeEvalsCoarse(cw, Ts, gauge, KAPPA, hip.MUGIQ_EIG_OPERATOR_MdagM, clover=C)
+    el, er = np.max(np.abs(lam - ev[pick]) / np.abs(ev[pick])), np.max(res) / np.max(np.abs(ev))
+    print("M_c^dag M_c eigenpairs, %d level(s): lambda %.3e, residual / norm %.3e, smallest / largest eigenvalue %.3e" % (levels, el, er, ev[0] / ev[-1]))
+    record_max("coarse_evals_galerkin_lambda", el)
+    record_max("coarse_evals_galerkin_residual", er)
+    assert el < 1e-12, el
+    assert np.array_equal(sig, np.sqrt(lam.real)) and np.max(np.abs(sig - np.sqrt(ev[pick])) / np.sqrt(ev[pick])) < 1e-12
+    assert er < 1e-12, er
+
+
+@pytest.mark.parametrize("grid,force", [((1, 1, 1, 1), (0, 0, 1, 1)), ((1, 1, 1, 2), (0, 0, 0, 0))])
+def test_coarse_evals_process_grids(grid, force, tmp_path):
+    """Forced partitioning of z and t on one rank (fine work vectors with ghost zones, the stencil's halo exchange) and 2 ranks (t split)
+    on the one GPU through gloo, two levels, clover on, forms M, MdagM and H: every rank's lambda, r and sigma equal the single-domain
+    numpy result to 1e-12 and, forced, the unpartitioned call to 1e-13 (asserted in the worker); they are bitwise identical on every rank."""
+    world = int(np.prod(grid))
+    prefix = str(tmp_path / "evals")
+    mp.spawn(restrict_workers.coarse_evals_worker, args=(world, free_port(), grid, force, (4, 4, 4, 8), prefix), nprocs=world, join=True)
+    outs = [np.load("%s_%d.npy" % (prefix, r)) for r in range(world)]
+    assert len(outs) == world and np.all(np.isfinite(outs[0]))
+    for o in outs[1:]:
+        assert np.array_equal(o, outs[0])
+
+
+def test_coarse_evals_fp32_hierarchy(hip, record_max):
+    """The two-level hierarchy in precision 4 (fp32 null vectors, coarse vectors and fine work vectors: coarse_scalar_kernel<float>, the
+    vector prolongator), fp32 gauge and clover fields, against the complex128 reference on the inputs rounded to fp32.  The bound is not
+    chosen: a second reference rounds every intermediate to complex64 where the library stores it (after each P, after the stencil, after
+    each R); its largest relative deviation from the unrounded reference over the five forms is the scale, 4 x that the tolerance (the 4
+    for the device's own summation order inside a storage step).
+    Measured on an MI355X: scale 3.68e-08 (set by form H, whose lambda are sums that cancel), worst deviation of the library 5.33e-08."""
+    shape = MULTI_LEVEL[2]
+    gauge, C, Us, A_eo = _device_operator(hip, shape[0], True, prec=4)
+    Xs, bss, Vs, Ts, ws, cw = _evals_hierarchy(hip, shape, prec=4)
+
+    def stored(f):
+        return f.astype(np.complex64).astype(np.complex128)
+    scale, worst = 0.0, 0.0
+    for op in range(5):
+        want = rr.coarse_evals_reference(ws, Vs, Xs[:-1], bss, Us, A_eo, KAPPA, op, 1.0)
+        scale = max(scale, _evals_err(rr.coarse_evals_reference(ws, Vs, Xs[:-1], bss, Us, A_eo, KAPPA, op, 1.0, stored=stored), want))
+        worst = max(worst, _evals_err(hip.computeEvalsCoarse(cw, Ts, gauge, KAPPA, op, clover=C), want))
+    print("fp32 coarse evals: scale of the rounded reference %.3e, worst deviation of the library %.3e" % (scale, worst))
+    record_max("coarse_evals_fp32_reference_scale", scale)
+    record_max("coarse_evals_fp32", worst)
+    assert worst < 4.0 * scale, (worst, scale)
+
+
+def _poison_pads(f):
+    nan = complex(float("nan"), float("nan"))
+    f.data.view(2, 2 * f.n_vec, f.stride)[:, :, f.volumeCB:] = nan
+    return f
+
+
+@pytest.mark.parametrize("mass_norm", [False, True])
+def test_coarse_evals_padded_strides(hip, mass_norm, record_max):
+    """One level, fp64: a transfer with pad 5 and eigenvectors with pad 7 (the work vectors of the coarsest level take their stride and
+    parity offset) against the unpadded call, 1e-13, and finite.  The eigenvector buffers are NaN before set_logical; set_logical writes
+    the whole buffer, so the pads are filled with NaN again after it."""
+    X, bs, Uo, V, ws, blocks = _evals_problem(8, True)
+    gauge = hip.GaugeField(X, (0, 0, 0, 0), 8).set_logical(Uo)
+    C = hip.CloverField(X, 8).set_logical(blocks)
+    T, Tp = hip.Transfer(X, 8, bs, 2, 8).set_logical(V), hip.Transfer(X, 8, bs, 2, 8, pad=5).set_logical(V)
+    cw = [hip.CoarseField(T.Xc, 8, 8).set_logical(w) for w in ws]
+    cp = []
+    for w in ws:
+        f = hip.CoarseField(T.Xc, 8, 8, pad=7)
+        f.data.fill_(complex(float("nan"), float("nan")))
+        cp.append(_poison_pads(f.set_logical(w)))
+    assert cp[0].stride == cw[0].stride + 7 and bool(torch.isnan(cp[0].data.real).any())
+    for op in range(5):
+        plain = hip.computeEvalsCoarse(cw, T, gauge, KAPPA, op, mass_norm, clover=C)
+        padded = hip.computeEvalsCoarse(cp, Tp, gauge, KAPPA, op, mass_norm, clover=C)
+        assert all(np.all(np.isfinite(a)) for a in padded if a is not None), op
+        e = _evals_err(padded, plain)
+        record_max("coarse_evals_padded", e)
+        assert e < 1e-13, (op, e)
+
+
+def test_coarse_evals_are_reproducible_and_independent_of_the_batch(hip, record_max):
+    """Two calls on equal inputs return the same bits.  Vector 8 (alone in the second block of the 9-vector call) evaluated in a call of its
+    own agrees to 1e-13, and so does vector 3 (inside the first block there, alone here); the library and DESIGN.md promise a summation
+    order independent of the batch for the restriction only, not for the whole chain, so this is not asserted bitwise."""
+    shape = MULTI_LEVEL[2]
+    gauge, C, _, _ = _device_operator(hip, shape[0], True)
+    Xs, bss, Vs, Ts, ws, cw = _evals_hierarchy(hip, shape)
+    for op in range(5):
+        a = hip.computeEvalsCoarse(cw, Ts, gauge, KAPPA, op, clover=C)
+        b = hip.computeEvalsCoarse(cw, Ts, gauge, KAPPA, op, clover=C)
+        assert _same_bits(a, b), op
+        for k in (8, 3):
+            alone = hip.computeEvalsCoarse([cw[k]], Ts, gauge, KAPPA, op, clover=C)
+            e = _evals_err(alone, tuple(None if x is None else x[k:k + 1] for x in a))
+            record_max("coarse_evals_alone_vs_batch", e)
+            assert e < 1e-13, (op, k, e)
+
+
+def test_coarse_deflation_with_more_than_one_null_vector_pass(hip, record_max):
+    """deflateLowModesCoarse on one level with n_vec 25 against numpy: the restriction makes a second pass and prolong_subtract_kernel
+    sums over more than 24 null vectors."""
+    rng = np.random.default_rng(925)
+    Xs, bss, nvecs, Vs, Ts = _hierarchy(hip, 1, rng, shape=((4, 4, 4, 4), [(2, 2, 2, 2)], [25]))
+    X0, nev, nvec = Xs[0], 7, 3
+    vcb, vcbc = int(np.prod(X0)) // 2, int(np.prod(Xs[-1])) // 2
+    ws = [_c(rng, (2, vcbc, 2, 25)) for _ in range(nev)]
+    sg = list((0.5 + rng.random(nev)) * np.where(np.arange(nev) % 2, -1.0, 1.0))
+    src = [_c(rng, (2, vcb, 4, 3)) for _ in range(nvec)]
+    dst = [_c(rng, (2, vcb, 4, 3)) for _ in range(nvec)]
+    cw = [hip.CoarseField(Xs[-1], 25, 8).set_logical(w) for w in ws]
+    fs = [hip.SpinorField(X0, 8, 2).set_logical(s) for s in src]
+    fd = [hip.SpinorField(X0, 8, 2).set_logical(d) for d in dst]
+    ov = hip.deflateLowModesCoarse(fd, fs, cw, Ts[0], sg, gamma5=True, overlaps=True)
+    want, C = _reference(dst, src, [orc.prolongate_levels(w, Vs, Xs[:-1], bss) for w in ws], sg, True)
+    e = rel_err(ov, C)
+    record_max("deflate_coarse_overlaps", e)
+    assert e < 1e-13, e
+    for r in range(nvec):
+        e = rel_err(fd[r].get_logical(), want[r])
+        record_max("deflate_coarse_dst", e)
+        assert e < 1e-13, (r, e)
