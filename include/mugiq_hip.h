@@ -426,6 +426,37 @@ int mugiq_hip_restrict_batched(const MugiqHipCoarseField *coarse_h, const MugiqH
 int mugiq_hip_restrict_coarse_batched(const MugiqHipCoarseField *coarser_h, const MugiqHipCoarseField *finer_h, int nVec,
                                       const MugiqHipTransfer *transfer, void *stream);
 
+/* The kernel forms of a finest-level transfer (new; host only, no device work): what mugiq_hip_prolongate_batched and
+ * mugiq_hip_prolongate_contract_batched select for it (csrc/transfer_form.cpp, the one place that decides), under the same environment
+ * switches, with their launch geometry, and the level geometry every MG kernel is handed.  transfer: checked as by the compute calls;
+ * V is not read (any non-NULL value).  finePrecision / fineOrder: of the fine fields of the prolongation (0: the transfer's precision);
+ * loopPrecision 0: the transfer's; nVec: the eigenvectors of the call. */
+#define MUGIQ_HIP_PROLONG_FAMILY_MFMA 1            /* matrix pipe, one workgroup per aggregate (prolong_mfma_kernel) */
+#define MUGIQ_HIP_PROLONG_FAMILY_VECTOR_STAGED 2   /* vector kernel, the V tile of 16 sites staged in LDS */
+#define MUGIQ_HIP_PROLONG_FAMILY_VECTOR_GLOBAL 3   /* vector kernel, V read from global memory (fp64, n_vec > 53) */
+#define MUGIQ_HIP_CONTRACT_FAMILY_COARSE_MFMA 1    /* coarse-grid plan V C V^dag, congruence on the matrix pipe */
+#define MUGIQ_HIP_CONTRACT_FAMILY_COARSE_VECTOR 2  /* coarse-grid plan, congruence on the vector pipe */
+#define MUGIQ_HIP_CONTRACT_FAMILY_DIRECT_STAGED 3  /* per-eigenvector kernel (prolong and contract on the spot), V tile in LDS */
+#define MUGIQ_HIP_CONTRACT_FAMILY_DIRECT_GLOBAL 4  /* ... V read from global memory */
+typedef struct MugiqHipTransferForm_s {
+  int X[4], Xc[4], bs[4];           /* finer lattice, coarser lattice, aggregate */
+  int aggVol, volumeCB, volumeCBc;
+  int coarseNColor, coarseStride;   /* the coarser side's fields where the library lays them out itself (no pad) */
+  long long coarseParityOffset;
+  /* mugiq_hip_prolongate_batched */
+  int prolongFamily, prolongThreads, prolongWorkgroups;
+  int prolongPasses, prolongBlocksPerPass; /* matrix pipe: launches, blocks of eight eigenvectors per launch */
+  long long prolongLdsBytes;
+  long long prolongWorkspaceBytes;  /* the head of the per-stream workspace the call may take (whatever the family) */
+  /* mugiq_hip_prolongate_contract_batched; 0 where the family does not use it */
+  int contractFamily, contractThreads, contractWorkgroups; /* of the congruence (coarse plan) or the per-eigenvector kernel */
+  int JC, SPR, NH;                  /* vector congruence: columns per lane chunk, sites per round, chunks per (site, chi, chi') */
+  int outerB, glds;                 /* coarse plan: outer-product kernel instance; matrix-pipe congruence staged global -> LDS */
+  long long contractLdsBytes, contractScratchBytes; /* scratch: pointer table, 1/sigma and C(X) of the coarse plan */
+} MugiqHipTransferForm;
+int mugiq_hip_transfer_form(const MugiqHipTransfer *transfer, int finePrecision, int fineOrder, int loopPrecision, int nVec,
+                            MugiqHipTransferForm *out);
+
 /* ==== host-side driver: the Loop_Mugiq / Displace classes of the reference ========================================= */
 
 /* include/enum_mugiq.h:35-41.  calcType is parsed but never read by the reference's live code; here it selects

@@ -636,6 +636,13 @@ inline MugiqHipFusedForm fusedForm(const ColorSpinorField &ev, int dispDir, cons
   return out;
 }
 
+// The kernel forms a finest-level MG transfer runs on, their launch geometry and the level geometry (mugiq_hip_transfer_form; host only)
+inline MugiqHipTransferForm transferForm(const MugiqHipTransfer &transfer, int nVec, int fineOrder = 2, int loopPrecision = 0) {
+  MugiqHipTransferForm out;
+  check(mugiq_hip_transfer_form(&transfer, 0, fineOrder, loopPrecision, nVec, &out));
+  return out;
+}
+
 // lib/interface_mugiq.cpp:158-172: computeLoop<Float,fieldOrder>(loopParams, eigsolve)
 template <typename Float, int fieldOrder>
 inline void computeLoop(MugiqLoopParam loopParams, const std::vector<ColorSpinorField> &eVecs, const std::vector<double> &eVals_sigma,

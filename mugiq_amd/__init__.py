@@ -12,7 +12,9 @@ from .operators import (  # noqa: E402
     copyGammaCoeffStructToSymbol, copyGammaMapStructToSymbol, gammaTables, GammaName,
     performLoopContraction, performLoopContractionBatched, performCovariantDisplacementVector, packFace, exchangeGhostVec,
     createPhaseMatrixGPU, convertIdxOrder_mapGamma, momentumProjection, momentumProjectionSeparable, convertAndProject, convertAndProjectSlots, convertAndProjectPlan, packFaceLayers, displacedLoopContractionFused, displacedLoopContractionFusedTwoSided, reflectDisplacedLoop, packLoopLayers, probeReadBandwidth, prolongateEvecs, prolongateCoarseEvecs, prolongateContractBatched,
-    deflateLowModes, restrictVecs, restrictCoarseVecs, deflateLowModesCoarse,
+    deflateLowModes, restrictVecs, restrictCoarseVecs, deflateLowModesCoarse, transferForm,
+    PROLONG_FAMILY_MFMA, PROLONG_FAMILY_VECTOR_STAGED, PROLONG_FAMILY_VECTOR_GLOBAL,
+    CONTRACT_FAMILY_COARSE_MFMA, CONTRACT_FAMILY_COARSE_VECTOR, CONTRACT_FAMILY_DIRECT_STAGED, CONTRACT_FAMILY_DIRECT_GLOBAL,
     DispDir, DispSignMinus, DispSignPlus, LOOP_FT_SIGN_MINUS, LOOP_FT_SIGN_PLUS, DisplaceFlagArray,
     REGION_ALL, REGION_INTERIOR, REGION_BOUNDARY, REGION_OVERWRITE, ENTRY_KERNEL_REFLECTED, ENTRY_KERNEL_MFMA_COLUMN, ENTRY_KERNEL_MFMA_ROW,
     ENTRY_KERNEL_VECTOR_TILE, ENTRY_KERNEL_STREAMING, ENTRY_KERNEL_STEPWISE,

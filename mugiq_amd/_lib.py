@@ -84,6 +84,16 @@ class FusedForm(ctypes.Structure):
                                             "ph", "glds", "npc", "np", "m", "phl")] + [("ldsBytes", ctypes.c_longlong)]
 
 
+class TransferForm(ctypes.Structure):
+    """MugiqHipTransferForm (include/mugiq_hip.h)."""
+    _fields_ = [(n, ctypes.c_int * 4) for n in ("X", "Xc", "bs")] + \
+               [(n, ctypes.c_int) for n in ("aggVol", "volumeCB", "volumeCBc", "coarseNColor", "coarseStride")] + [("coarseParityOffset", ctypes.c_longlong)] + \
+               [(n, ctypes.c_int) for n in ("prolongFamily", "prolongThreads", "prolongWorkgroups", "prolongPasses", "prolongBlocksPerPass")] + \
+               [(n, ctypes.c_longlong) for n in ("prolongLdsBytes", "prolongWorkspaceBytes")] + \
+               [(n, ctypes.c_int) for n in ("contractFamily", "contractThreads", "contractWorkgroups", "JC", "SPR", "NH", "outerB", "glds")] + \
+               [(n, ctypes.c_longlong) for n in ("contractLdsBytes", "contractScratchBytes")]
+
+
 class LoopPlan(ctypes.Structure):
     """MugiqHipLoopPlan (include/mugiq_hip.h)."""
     _fields_ = [(n, ctypes.c_int) for n in ("nEntries", "nOrder", "nPackTargets", "nReserve", "earlyEntry", "carryUltra", "momReflect", "grouped")] + \
@@ -198,6 +208,8 @@ SIGNATURES = {
     "mugiq_hip_restrict_batched": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), _SP, ctypes.c_int, ctypes.POINTER(TransferDesc), ctypes.c_int, _VP]),
     "mugiq_hip_restrict_coarse_batched": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.POINTER(CoarseDesc), ctypes.c_int,
                                                          ctypes.POINTER(TransferDesc), _VP]),
+    "mugiq_hip_transfer_form": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.POINTER(TransferForm)]),
     "mugiq_hip_deflate_low_modes_coarse": (ctypes.c_int, [_SP, _SP, ctypes.c_int, ctypes.POINTER(CoarseDesc), ctypes.POINTER(ctypes.c_double),
                                                           ctypes.c_int, ctypes.POINTER(TransferDesc), ctypes.c_int, ctypes.c_int,
                                                           ctypes.POINTER(ctypes.c_double), _VP, _VP]),

@@ -251,12 +251,6 @@ void launch_any(int precV, int precS, bool update, int RB, const void *const *V,
   else launch_pass<float, float>(update, RB, V, S, Dst, nEv, nR, g, nNB, nChunks, segsPerChunk, gamma5, partial, D, stream);
 }
 
-// [first, last) byte range a field's kernels may touch
-void field_span(const MugiqHipSpinorField &f, uintptr_t *a, uintptr_t *b) {
-  *a = reinterpret_cast<uintptr_t>(f.data);
-  *b = *a + (uintptr_t)(f.parity_offset + (int64_t)12 * f.stride) * 2 * f.precision;
-}
-
 bool same_layout(const MugiqHipSpinorField &a, const MugiqHipSpinorField &b) {
   return a.field_order == b.field_order && a.volumeCB == b.volumeCB && a.stride == b.stride && a.parity_offset == b.parity_offset &&
          a.X[0] == b.X[0] && a.X[1] == b.X[1] && a.X[2] == b.X[2] && a.X[3] == b.X[3];
@@ -304,10 +298,10 @@ int deflate_low_modes(const MugiqHipSpinorField *dst, const MugiqHipSpinorField 
                 who);
   for (int r = 0; r < nVec; r++) {
     uintptr_t a0, a1;
-    field_span(dst[r], &a0, &a1);
+    spinor_span(dst[r], &a0, &a1);
     for (int q = 0; q < nVec; q++) {
       uintptr_t b0, b1;
-      field_span(src[q], &b0, &b1);
+      spinor_span(src[q], &b0, &b1);
       const bool overlap = a0 < b1 && b0 < a1;
       MUGIQ_REQUIRE(!overlap || (q == r && dst[r].data == src[r].data),
                     "%s: dst vector %d overlaps src vector %d without being identical to it", who, r, q);

@@ -8,6 +8,7 @@
 
 #include "fused_form.h"
 #include "mugiq_hip.h"
+#include "transfer_form.h"
 
 namespace mugiq {
 
@@ -108,7 +109,6 @@ int deflate_low_modes(const MugiqHipSpinorField *dst, const MugiqHipSpinorField 
 int validate_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseField *c0, const char *who);
 int validate_coarse_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseField *finer_h, const MugiqHipCoarseField *coarser_h, int nVec,
                              const char *who);
-size_t prolong_workspace_bytes(const MugiqHipTransfer *T, int nVec);  // csrc/prolong.hip: the head of the per-stream workspace the prolongator may use
 // csrc/restrict.hip: mugiq_hip_deflate_low_modes_coarse with the caller's name in the messages (mugiq_hip_loop_deflate_coarse passes the
 // loop's coarse set and transfers)
 int deflate_low_modes_coarse(const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int nVec, const MugiqHipCoarseField *ev,
@@ -366,5 +366,11 @@ int validate_spinor(const MugiqHipSpinorField *f, const char *who, const char *n
 // on an axis of extent 1 (the rank is then its own neighbour; QUDA's comm_dim_partitioned_set)
 inline bool comm_partitioned(const MugiqHipComm *c, int d) { return c != nullptr && (c->grid[d] > 1 || c->partitioned[d] != 0); }
 bool same_geometry(const MugiqHipSpinorField &a, const MugiqHipSpinorField &b);
+// [first, last) byte range a spinor's kernels may touch
+inline void spinor_span(const MugiqHipSpinorField &f, uintptr_t *a, uintptr_t *b) {
+  *a = reinterpret_cast<uintptr_t>(f.data);
+  *b = *a + (uintptr_t)(f.parity_offset + (int64_t)12 * f.stride) * 2 * f.precision;
+}
+inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }  // sub-buffers of the per-stream arenas
 
 }  // namespace mugiq

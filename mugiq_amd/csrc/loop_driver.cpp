@@ -1234,12 +1234,9 @@ int mugiq_hip_loop_create_coarse_levels(MugiqHipLoop **out, const MugiqHipLoopPa
                     "%s: transfer level %d: X[%d] = %d is not level %d's X / geo_block_size", who, l, d, transfers_h[l].X[d], l - 1);
   }
   *out = nullptr;
-  long long vol = 1;
-  for (int d = 0; d < 4; d++) {
+  for (int d = 0; d < 4; d++)
     MUGIQ_REQUIRE(transfer->X[d] > 0 && (transfer->X[d] & 1) == 0, "%s: fine X[%d] = %d must be positive and even", who, d, transfer->X[d]);
-    vol *= transfer->X[d];
-  }
-  const int volumeCB = (int)(vol / 2);
+  const int volumeCB = transfer_geom(*transfer).volumeCB;
   const bool needFine = (p->doNonLocal && p->nDispEntries > 0) || p->calcType == MUGIQ_HIP_LOOP_CALC_TYPE_BASIC_KERNEL;
   const size_t fieldBytes = (size_t)24 * volumeCB * 2 * (size_t)transfer->precision;
   void *store = nullptr;
@@ -1276,18 +1273,7 @@ int mugiq_hip_loop_create_coarse_levels(MugiqHipLoop **out, const MugiqHipLoopPa
   for (int l = nCoarseLevels - 2; l >= 0; l--) {
     const MugiqHipTransfer &T = transfers_h[l + 1];  // between level l+1 (finer side, dims T.X) and level l+2
     lp->upper.insert(lp->upper.begin(), T);
-    MugiqHipCoarseField f{};
-    f.precision = T.precision;
-    f.nSpin = 2;
-    f.nColor = transfers_h[l].nVec;
-    long long v = 1;
-    for (int d = 0; d < 4; d++) {
-      f.X[d] = T.X[d];
-      v *= T.X[d];
-    }
-    f.volumeCB = (int)(v / 2);
-    f.stride = f.volumeCB;
-    f.parity_offset = (int64_t)2 * f.nColor * f.stride;
+    MugiqHipCoarseField f = coarse_side_layout(transfers_h[l]);  // level l + 1 is the coarser side of transfers_h[l] (checked above)
     const size_t bytes = (size_t)2 * f.parity_offset * 2 * (size_t)T.precision;
     if (hipMalloc(&lp->levelStore[l], bytes * (size_t)nEv) != hipSuccess) {
       mugiq_hip_loop_destroy(lp);

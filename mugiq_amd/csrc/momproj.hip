@@ -738,7 +738,7 @@ static int launch_separable(void *C, const void *A, const void *dataPosEO, int n
   }
   const size_t slotOff = ints.size();
   if (slotMap_h) ints.insert(ints.end(), slotMap_h, slotMap_h + nData / 16);
-  const size_t phBytes = (ph.size() * sizeof(Cplx<F>) + 255) / 256 * 256;
+  const size_t phBytes = align256(ph.size() * sizeof(Cplx<F>));
   std::vector<unsigned char> host(phBytes + ints.size() * sizeof(int));
   memcpy(host.data(), ph.data(), ph.size() * sizeof(Cplx<F>));
   memcpy(host.data() + phBytes, ints.data(), ints.size() * sizeof(int));

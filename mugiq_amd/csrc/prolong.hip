@@ -17,15 +17,11 @@
 #include "internal.h"
 
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 
 namespace mugiq {
 
-constexpr int kPrTile = 16;    // sites per workgroup
-constexpr int kPrGroups = 16;  // eigenvector groups per workgroup
-
+// (kPrTile = 16 sites and kPrGroups = 16 eigenvector groups per workgroup: csrc/transfer_form.h, with the other tile constants)
 template <typename F, typename A> struct ProlongArgs {
   const Cplx<F> *V;             // [parity][(3s+c)*NV + j][x_cb]
   int64_t Vpo;
@@ -48,7 +44,7 @@ template <typename F, typename A> struct ProlongArgs {
 // STAGED: the V tile of the workgroup's 16 sites is copied to the LDS once and read from there by all 16 eigenvector groups.  An fp64 tile
 // of more than 53 null vectors (12 n_vec 16 sites x 16 B) does not fit the 160 KB of a workgroup: those transfers take the kernel with
 // STAGED = false, which reads V(x; :, j) from global memory (L2) in the same place of the pipeline.  Same sums in the same order.
-constexpr size_t kPrMaxLds = 160 * 1024;
+// (Which of the two: select_prolong_form / select_prolong_contract_form, csrc/transfer_form.cpp.)
 template <typename F, typename A, int ORDER, bool WRITE, bool CONTRACT, bool STAGED>
 __global__ __launch_bounds__(kPrTile *kPrGroups) void prolong_kernel(ProlongArgs<F, A> a) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -221,8 +217,27 @@ int validate_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseField *c0, 
   return MUGIQ_HIP_SUCCESS;
 }
 
-template <typename F, typename A, int ORDER, bool WRITE, bool CONTRACT>
-static int launch_prolong(const MugiqHipTransfer *T, const MugiqHipCoarseField *coarse, const MugiqHipSpinorField *fine,
+// fills X, Xc, bs (and the volumes, where the struct has them) of a kernel's arguments from the level geometry
+template <typename Args> static void set_lattices(Args &a, const TransferGeom &g) {
+  for (int d = 0; d < 4; d++) a.X[d] = g.X[d], a.Xc[d] = g.Xc[d], a.bs[d] = g.bs[d];
+}
+template <typename Args> static void set_geometry(Args &a, const TransferGeom &g) {
+  set_lattices(a, g);
+  a.volumeCB = g.volumeCB, a.volumeCBc = g.volumeCBc, a.aggVol = g.aggVol;
+}
+// a launch with the dynamic LDS its form asks for
+template <typename Kernel, typename Args>
+static int launch_with_lds(Kernel kern, int workgroups, int threads, size_t ldsBytes, hipStream_t stream, const Args &a) {
+  if (ldsBytes > 64 * 1024)
+    MUGIQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
+  hipLaunchKernelGGL(kern, dim3((unsigned)workgroups), dim3(threads), ldsBytes, stream, a);
+  MUGIQ_CHECK_HIP(hipGetLastError());
+  return MUGIQ_HIP_SUCCESS;
+}
+
+// the vector kernel of a form (ProlongForm or ContractForm); staged: the family with the V tile in LDS
+template <typename F, typename A, int ORDER, bool WRITE, bool CONTRACT, typename Form>
+static int launch_prolong(const Form &form, bool staged, const MugiqHipTransfer *T, const MugiqHipCoarseField *coarse, const MugiqHipSpinorField *fine,
                           const double *sigma, void *loop_d, int nVec, hipStream_t stream) {
   const size_t pb = sizeof(void *) * (size_t)nVec;
   std::vector<unsigned char> host(2 * pb + sizeof(A) * (size_t)nVec);
@@ -242,15 +257,9 @@ static int launch_prolong(const MugiqHipTransfer *T, const MugiqHipCoarseField *
   a.Vpo = T->parity_offset;
   a.Vstride = T->stride;
   a.NV = T->nVec;
-  long long vol = 1;
-  for (int d = 0; d < 4; d++) {
-    a.X[d] = T->X[d];
-    a.bs[d] = T->geoBlockSize[d];
-    a.Xc[d] = T->X[d] / T->geoBlockSize[d];
-    vol *= T->X[d];
-  }
+  set_lattices(a, form.geom);
   a.spinBs = T->spinBlockSize;
-  a.volumeCB = (int)(vol / 2);
+  a.volumeCB = form.geom.volumeCB;
   a.coarse = reinterpret_cast<const void *const *>(dev);
   a.Cpo = coarse[0].parity_offset;
   a.Cstride = coarse[0].stride;
@@ -260,24 +269,10 @@ static int launch_prolong(const MugiqHipTransfer *T, const MugiqHipCoarseField *
   a.nVec = nVec;
   a.inv_sigma = reinterpret_cast<const A *>(static_cast<unsigned char *>(dev) + 2 * pb);
   a.loop = static_cast<Cplx<A> *>(loop_d);
-  const size_t tileBytes = sizeof(Cplx<F>) * 12 * (size_t)T->nVec * kPrTile;
-  const size_t redBytes = CONTRACT ? sizeof(A) * 16 * kPrGroups * kPrTile : 0;
-  const int tiles = 2 * ((a.volumeCB + kPrTile - 1) / kPrTile);
-  if (tileBytes > kPrMaxLds) {  // the V tile does not fit the LDS (fp64, n_vec > 53)
-    if constexpr (sizeof(F) == 8) {
-      hipLaunchKernelGGL((prolong_kernel<F, A, ORDER, WRITE, CONTRACT, false>), dim3(tiles), dim3(kPrTile * kPrGroups), redBytes, stream, a);
-      MUGIQ_CHECK_HIP(hipGetLastError());
-      return MUGIQ_HIP_SUCCESS;
-    }
-    return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "prolongateEvec: n_vec = %d needs %zu bytes of LDS", T->nVec, tileBytes);
-  }
-  const size_t shmem = std::max(tileBytes, redBytes);
-  auto kern = prolong_kernel<F, A, ORDER, WRITE, CONTRACT, true>;
-  if (shmem > 64 * 1024)
-    MUGIQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  hipLaunchKernelGGL(kern, dim3(tiles), dim3(kPrTile * kPrGroups), shmem, stream, a);
-  MUGIQ_CHECK_HIP(hipGetLastError());
-  return MUGIQ_HIP_SUCCESS;
+  // (an fp32 V tile always fits the LDS -- the static_assert of csrc/transfer_form.h -- so the kernel without staging exists for fp64 only)
+  if constexpr (sizeof(F) == 8)
+    if (!staged) return launch_with_lds(prolong_kernel<F, A, ORDER, WRITE, CONTRACT, false>, form.workgroups, form.threads, form.ldsBytes, stream, a);
+  return launch_with_lds(prolong_kernel<F, A, ORDER, WRITE, CONTRACT, true>, form.workgroups, form.threads, form.ldsBytes, stream, a);
 }
 
 
@@ -358,11 +353,7 @@ static int launch_prolong_coarse(const MugiqHipCoarseField *out, const MugiqHipC
   a.Vstride = T->stride;
   a.NV = T->nVec;
   a.NCf = out[0].nColor;
-  for (int d = 0; d < 4; d++) {
-    a.X[d] = T->X[d];
-    a.bs[d] = T->geoBlockSize[d];
-    a.Xc[d] = T->X[d] / T->geoBlockSize[d];
-  }
+  set_lattices(a, transfer_geom(*T));
   a.volumeCB = out[0].volumeCB;
   a.in = reinterpret_cast<const void *const *>(dev);
   a.Ipo = in[0].parity_offset;
@@ -619,8 +610,7 @@ template <typename F> struct CongruenceMfmaArgs {
   Cplx<double> *loop;     // [16][V]
 };
 
-constexpr int kCmS = 16;  // sites per round = columns of one MFMA
-
+// (kCmS = 16 sites per round = columns of one MFMA: csrc/transfer_form.h)
 // GLDS (fp64 storage, two tiles fit the LDS): the next round's tile goes global -> LDS directly (global_load_lds_dwordx4, no
 // registers, no ds_write pass) into the other buffer while this round is consumed; otherwise (fp32 storage: the tile is
 // widened to double on the way; n_vec = 32: one buffer only) the next round waits in registers.
@@ -816,60 +806,23 @@ template <typename F, int NV, bool GLDS> __global__ __launch_bounds__(64 * (NV /
   }
 }
 
-template <typename F, int NV> static int launch_congruence_mfma(const CongruenceMfmaArgs<F> &a, hipStream_t stream) {
-  constexpr int NW = NV / 2;
-  constexpr size_t tileB = sizeof(Cplx<double>) * (size_t)12 * NV * kCmS, redB = sizeof(double) * (size_t)NW * kCmS * 8;
-  constexpr bool GLDS = sizeof(F) == 8 && 2 * tileB + redB <= 160 * 1024;
-  const size_t shmem = (GLDS ? 2 : 1) * tileB + redB;
-  auto kern = fine_congruence_mfma_kernel<F, NV, GLDS>;
-  if (shmem > 64 * 1024)
-    MUGIQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  hipLaunchKernelGGL(kern, dim3(2 * a.volumeCBc), dim3(64 * NW), shmem, stream, a);
-  MUGIQ_CHECK_HIP(hipGetLastError());
-  return MUGIQ_HIP_SUCCESS;
+template <typename F, int NV> static int launch_congruence_mfma(const ContractForm &form, const CongruenceMfmaArgs<F> &a, hipStream_t stream) {
+  return launch_with_lds(fine_congruence_mfma_kernel<F, NV, congruence_mfma_glds(sizeof(F), NV)>, form.workgroups, form.threads, form.ldsBytes, stream, a);
 }
 
-// LDS bytes of the congruence kernel; 0 if this (n_vec, precision) does not fit
-template <typename F, typename A> static size_t congruence_lds(int NV, int SPR) {
-  const size_t NC = 2 * (size_t)NV;
-  return sizeof(Cplx<A>) * (NC * NC + (size_t)SPR * 16) + sizeof(Cplx<F>) * 4 * NV * (size_t)SPR;
-}
-
-template <typename F, typename A, int JC, int SPR, int NH> static int launch_congruence(const FineCongruenceArgs<F, A> &a, size_t shmem, hipStream_t stream) {
-  auto kern = fine_congruence_kernel<F, A, JC, SPR, NH>;
-  if (shmem > 64 * 1024)
-    MUGIQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  hipLaunchKernelGGL(kern, dim3(2 * a.volumeCBc), dim3(4 * NH * SPR), shmem, stream, a);
-  MUGIQ_CHECK_HIP(hipGetLastError());
-  return MUGIQ_HIP_SUCCESS;
-}
-
-// returns -1 if the coarse-grid plan does not apply (caller falls back to the per-eigenvector kernel)
+// The coarse-grid plan of a ContractForm of that family: C(X) by coarse_outer_kernel, then the congruence the form names
 template <typename F, typename A>
-static int coarse_plan(const MugiqHipTransfer *T, const MugiqHipCoarseField *coarse, const double *sigma, void *loop_d, int nVec,
-                       hipStream_t stream) {
-  const int NV = T->nVec, NC = 2 * NV;
-  // supported shapes: n_vec = 8, 16, 32 (chunks of 8 columns) and 12, 24 (chunks of 12); NH = n_vec / chunk lanes per
-  // (site, chi, chi') must be a power of two (shuffle reduction) and 4 * NH * SPR <= 1024 threads
-  if (!(NV == 8 || NV == 16 || NV == 32 || NV == 12 || NV == 24)) return -1;
-  const int JC = NV % 12 == 0 ? 12 : 8, NH = NV / JC;  // (6-column chunks on 16 lanes per site measured 8 % slower)
-  int SPR = 64;
-  if (congruence_lds<F, A>(NV, SPR) > 150 * 1024 || 4 * NH * SPR > 1024) SPR = 32;
-  if (congruence_lds<F, A>(NV, SPR) > 150 * 1024) return -1;
-  long long volc = 1, aggVol = 1;
-  for (int d = 0; d < 4; d++) {
-    volc *= T->X[d] / T->geoBlockSize[d];
-    aggVol *= T->geoBlockSize[d];
-  }
+static int coarse_plan(const ContractForm &form, const MugiqHipTransfer *T, const MugiqHipCoarseField *coarse, const double *sigma, void *loop_d,
+                       int nVec, hipStream_t stream) {
+  const int NV = T->nVec;
+  const TransferGeom &g = form.geom;
   const size_t pb = sizeof(void *) * (size_t)nVec;
-  const size_t tabBytes = (pb + sizeof(A) * (size_t)nVec + 255) / 256 * 256;
-  const size_t cBytes = sizeof(Cplx<A>) * (size_t)volc * NC * NC;
   // one scratch region holds [pointer table | 1/sigma | C]: reserve it in full first, so that the table upload below
   // (which draws on the same per-stream scratch) cannot move it
   void *base = nullptr;
-  int st = stream_scratch(&base, tabBytes + cBytes, stream);
+  int st = stream_scratch(&base, form.scratchBytes, stream);
   if (st) return st;
-  std::vector<unsigned char> host(tabBytes, 0);
+  std::vector<unsigned char> host(form.tableBytes, 0);
   const void **hc = reinterpret_cast<const void **>(host.data());
   A *hs = reinterpret_cast<A *>(host.data() + pb);
   for (int n = 0; n < nVec; n++) {
@@ -877,52 +830,40 @@ static int coarse_plan(const MugiqHipTransfer *T, const MugiqHipCoarseField *coa
     hs[n] = static_cast<A>(1.0 / static_cast<F>(sigma[n]));
   }
   void *dev = nullptr;
-  if ((st = upload_table(&dev, host.data(), tabBytes, stream))) return st;
+  if ((st = upload_table(&dev, host.data(), form.tableBytes, stream))) return st;
   MUGIQ_REQUIRE(dev == base, "prolongateContract: scratch moved under the coarse-grid plan");
   CoarseOuterArgs<F, A> o;
   o.coarse = reinterpret_cast<const void *const *>(dev);
   o.inv_sigma = reinterpret_cast<const A *>(static_cast<unsigned char *>(dev) + pb);
   o.nVec = nVec;
   o.NV = NV;
-  o.volumeCBc = (int)(volc / 2);
+  o.volumeCBc = g.volumeCBc;
   o.Cstride = coarse[0].stride;
   o.Cpo = coarse[0].parity_offset;
-  o.C = reinterpret_cast<Cplx<A> *>(static_cast<unsigned char *>(dev) + tabBytes);
-  switch ((NC + 15) / 16) {
-  case 1: hipLaunchKernelGGL((coarse_outer_kernel<F, A, 1>), dim3((unsigned)volc), dim3(256), 0, stream, o); break;
-  case 2: hipLaunchKernelGGL((coarse_outer_kernel<F, A, 2>), dim3((unsigned)volc), dim3(256), 0, stream, o); break;
-  case 3: hipLaunchKernelGGL((coarse_outer_kernel<F, A, 3>), dim3((unsigned)volc), dim3(256), 0, stream, o); break;
-  default: hipLaunchKernelGGL((coarse_outer_kernel<F, A, 4>), dim3((unsigned)volc), dim3(256), 0, stream, o); break;
+  o.C = reinterpret_cast<Cplx<A> *>(static_cast<unsigned char *>(dev) + form.tableBytes);
+  const dim3 sites((unsigned)form.workgroups);  // one workgroup per coarse site
+  switch (form.outerB) {
+  case 1: hipLaunchKernelGGL((coarse_outer_kernel<F, A, 1>), sites, dim3(256), 0, stream, o); break;
+  case 2: hipLaunchKernelGGL((coarse_outer_kernel<F, A, 2>), sites, dim3(256), 0, stream, o); break;
+  case 3: hipLaunchKernelGGL((coarse_outer_kernel<F, A, 3>), sites, dim3(256), 0, stream, o); break;
+  default: hipLaunchKernelGGL((coarse_outer_kernel<F, A, 4>), sites, dim3(256), 0, stream, o); break;
   }
   MUGIQ_CHECK_HIP(hipGetLastError());
 
-  // fp64 accumulation, n_vec = 8, 16, 24, 32, aggregates of a multiple of 16 sites: the congruence on the matrix pipe
-  // (MUGIQ_HIP_MG_MFMA=0 keeps the vector kernel)
-  if constexpr (sizeof(A) == 8) {
-    bool mfma = (NV == 8 || NV == 16 || NV == 24 || NV == 32) && aggVol % kCmS == 0;
-    if (const char *e = getenv("MUGIQ_HIP_MG_MFMA")) mfma = mfma && atoi(e) != 0;
-    if (mfma) {
+  if constexpr (sizeof(A) == 8) {  // (the matrix-pipe congruence accumulates in fp64)
+    if (form.family == MUGIQ_HIP_CONTRACT_FAMILY_COARSE_MFMA) {
       CongruenceMfmaArgs<F> m;
       m.V = static_cast<const Cplx<F> *>(T->V);
       m.Vpo = T->parity_offset;
       m.Vstride = T->stride;
-      long long volf = 1;
-      for (int d = 0; d < 4; d++) {
-        m.X[d] = T->X[d];
-        m.bs[d] = T->geoBlockSize[d];
-        m.Xc[d] = T->X[d] / T->geoBlockSize[d];
-        volf *= T->X[d];
-      }
-      m.volumeCB = (int)(volf / 2);
-      m.volumeCBc = (int)(volc / 2);
-      m.aggVol = (int)aggVol;
+      set_geometry(m, g);
       m.C = reinterpret_cast<const Cplx<double> *>(o.C);
       m.loop = static_cast<Cplx<double> *>(loop_d);
       switch (NV) {
-      case 8: return launch_congruence_mfma<F, 8>(m, stream);
-      case 16: return launch_congruence_mfma<F, 16>(m, stream);
-      case 24: return launch_congruence_mfma<F, 24>(m, stream);
-      default: return launch_congruence_mfma<F, 32>(m, stream);
+      case 8: return launch_congruence_mfma<F, 8>(form, m, stream);
+      case 16: return launch_congruence_mfma<F, 16>(form, m, stream);
+      case 24: return launch_congruence_mfma<F, 24>(form, m, stream);
+      default: return launch_congruence_mfma<F, 32>(form, m, stream);
       }
     }
   }
@@ -931,26 +872,18 @@ static int coarse_plan(const MugiqHipTransfer *T, const MugiqHipCoarseField *coa
   a.Vpo = T->parity_offset;
   a.Vstride = T->stride;
   a.NV = NV;
-  long long vol = 1;
-  for (int d = 0; d < 4; d++) {
-    a.X[d] = T->X[d];
-    a.bs[d] = T->geoBlockSize[d];
-    a.Xc[d] = T->X[d] / T->geoBlockSize[d];
-    vol *= T->X[d];
-  }
-  a.volumeCB = (int)(vol / 2);
-  a.volumeCBc = (int)(volc / 2);
-  a.aggVol = (int)aggVol;
+  set_geometry(a, g);
   a.C = o.C;
   a.loop = static_cast<Cplx<A> *>(loop_d);
-  const size_t shmem = congruence_lds<F, A>(NV, SPR);
+  switch (100 * form.JC + form.SPR + form.NH) {  // the kernel instance of the form's (JC, SPR, NH)
 #define MUGIQ_CONGRUENCE_CASE(J, S, H) \
-  if (JC == J && SPR == S && NH == H) return launch_congruence<F, A, J, S, H>(a, shmem, stream);
-  MUGIQ_CONGRUENCE_CASE(12, 64, 2) MUGIQ_CONGRUENCE_CASE(12, 32, 2) MUGIQ_CONGRUENCE_CASE(12, 64, 1) MUGIQ_CONGRUENCE_CASE(12, 32, 1)
-  MUGIQ_CONGRUENCE_CASE(8, 64, 1) MUGIQ_CONGRUENCE_CASE(8, 32, 1) MUGIQ_CONGRUENCE_CASE(8, 64, 2) MUGIQ_CONGRUENCE_CASE(8, 32, 2)
-  MUGIQ_CONGRUENCE_CASE(8, 64, 4) MUGIQ_CONGRUENCE_CASE(8, 32, 4)
+  case 100 * J + S + H: return launch_with_lds(fine_congruence_kernel<F, A, J, S, H>, form.workgroups, form.threads, form.ldsBytes, stream, a);
+    MUGIQ_CONGRUENCE_CASE(12, 64, 2) MUGIQ_CONGRUENCE_CASE(12, 32, 2) MUGIQ_CONGRUENCE_CASE(12, 64, 1) MUGIQ_CONGRUENCE_CASE(12, 32, 1)
+    MUGIQ_CONGRUENCE_CASE(8, 64, 1) MUGIQ_CONGRUENCE_CASE(8, 32, 1) MUGIQ_CONGRUENCE_CASE(8, 64, 2) MUGIQ_CONGRUENCE_CASE(8, 32, 2)
+    MUGIQ_CONGRUENCE_CASE(8, 64, 4) MUGIQ_CONGRUENCE_CASE(8, 32, 4)
 #undef MUGIQ_CONGRUENCE_CASE
-  return -1;
+  }
+  return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "prolongateContract: no congruence kernel with %d columns, %d sites, %d chunks", form.JC, form.SPR, form.NH);
 }
 
 
@@ -975,8 +908,7 @@ static int coarse_plan(const MugiqHipTransfer *T, const MugiqHipCoarseField *coa
 // workgroup tile by tile (51 ms); aggregate pairs per wave with the 64-byte sector completed inside the store instruction
 // by a quad permutation (39.9 ms).  Every wait in the loop is vmcnt(0): loads and stores share that counter and are not
 // documented to complete in order with respect to each other, so no counted wait is used while stores are in flight.
-constexpr int kPmWaves = 8;  // waves per workgroup: even ones take chirality 0, odd ones chirality 1
-constexpr int kPmPairs = 4;  // eight-eigenvector blocks a wave keeps resident (measured: 12-16 blocks per pass beat 24 and 8)
+// (kPmWaves = 8 waves per workgroup, kPmPairs = 4 resident blocks per wave: csrc/transfer_form.h)
 
 struct ProlongMfmaArgs {
   const Cplx<double> *V;  // [parity][(3s+c)*NV + j][x_cb]
@@ -1152,33 +1084,15 @@ template <int NV> __global__ __launch_bounds__(64 * kPmWaves) void prolong_mfma_
   }
 }
 
-// The fine fields must be FLOAT2 fp64, n_vec 8 | 16 | 24 (two V tiles fit the LDS), aggregates of a multiple of 16 sites.
-// Returns -1 if the shape is not covered (the caller uses the vector kernel); MUGIQ_HIP_PROLONG_MFMA=0 switches it off.
-static int prolong_mfma_plan(const MugiqHipTransfer *T, const MugiqHipCoarseField *coarse, const MugiqHipSpinorField *fine, int nVec,
-                             hipStream_t stream) {
+// The matrix-pipe form of a ProlongForm of that family (fp64 FLOAT2 fine fields, n_vec 8 | 16 | 24, aggregates of a multiple of 16 sites)
+static int launch_prolong_mfma(const ProlongForm &form, const MugiqHipTransfer *T, const MugiqHipCoarseField *coarse, const MugiqHipSpinorField *fine,
+                               int nVec, hipStream_t stream) {
   const int NV = T->nVec;
-  if (!(NV == 8 || NV == 16 || NV == 24)) return -1;
-  if (const char *e = getenv("MUGIQ_HIP_PROLONG_MFMA"))
-    if (atoi(e) == 0) return -1;
-  long long vol = 1, volc = 1, aggVol = 1;
-  for (int d = 0; d < 4; d++) {
-    vol *= T->X[d];
-    volc *= T->X[d] / T->geoBlockSize[d];
-    aggVol *= T->geoBlockSize[d];
-  }
-  if (aggVol % kCmS != 0) return -1;
   ProlongMfmaArgs a;
   a.V = static_cast<const Cplx<double> *>(T->V);
   a.Vpo = T->parity_offset;
   a.Vstride = T->stride;
-  for (int d = 0; d < 4; d++) {
-    a.X[d] = T->X[d];
-    a.bs[d] = T->geoBlockSize[d];
-    a.Xc[d] = T->X[d] / T->geoBlockSize[d];
-  }
-  a.volumeCB = (int)(vol / 2);
-  a.volumeCBc = (int)(volc / 2);
-  a.aggVol = (int)aggVol;
+  set_geometry(a, form.geom);
   a.Cpo = coarse[0].parity_offset;
   a.Cstride = coarse[0].stride;
   a.Fstride = fine[0].stride;
@@ -1195,46 +1109,21 @@ static int prolong_mfma_plan(const MugiqHipTransfer *T, const MugiqHipCoarseFiel
   if (st) return st;
   a.table = reinterpret_cast<const void *const *>(dev);
   void *ws = nullptr;
-  const size_t packBytes = prolong_workspace_bytes(T, nVec);
-  if ((st = stream_workspace(&ws, packBytes, stream))) return st;
+  if ((st = stream_workspace(&ws, form.workspaceBytes, stream))) return st;  // the packed coarse vectors
   a.packed = static_cast<const Cplx<double> *>(ws);
   const int nVec16 = (a.nVec8 + 15) / 16;  // (tiles of 16 eigenvectors; the last one may be half empty)
   hipLaunchKernelGGL(coarse_pack_kernel, dim3((unsigned)((a.volumeCBc + 15) / 16), (unsigned)(2 * NV), (unsigned)(2 * nVec16)), dim3(256), 0, stream, a, NV);
   MUGIQ_CHECK_HIP(hipGetLastError());
-  // passes: a workgroup keeps 4 * kPmPairs blocks of eight eigenvectors per chirality resident; more eigenvectors than that
-  // are split evenly (V is staged once per pass: 12 n_vec 16 B per site against 192 B per site and eigenvector written)
-  int cap = 4 * kPmPairs;
-  if (const char *e = getenv("MUGIQ_HIP_PROLONG_PASS_BLOCKS")) {  // experiments: blocks of eight eigenvectors per pass (<= 4 kPmPairs)
-    const int c = atoi(e);
-    if (c >= 1 && c <= 4 * kPmPairs) cap = c;
-  }
   const int blocks = a.nVec8 / 8;
-  const int passes = (blocks + cap - 1) / cap;
-  const int blocksPerPass = (blocks + passes - 1) / passes;
-  const size_t shmem = 2 * sizeof(Cplx<double>) * (size_t)12 * NV * kCmS;
-  for (int b = 0; b < blocks; b += blocksPerPass) {
+  for (int b = 0; b < blocks; b += form.blocksPerPass) {  // form.passes launches
     a.blkBegin = b;
-    a.blkCount = std::min(blocksPerPass, blocks - b);
-#define MUGIQ_PM_LAUNCH(N_)                                                                                             \
-  {                                                                                                                     \
-    auto kern = prolong_mfma_kernel<N_>;                                                                                \
-    if (shmem > 64 * 1024)                                                                                              \
-      MUGIQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-    hipLaunchKernelGGL(kern, dim3((unsigned)volc), dim3(64 * kPmWaves), shmem, stream, a);                              \
-  }
-    if (NV == 8) MUGIQ_PM_LAUNCH(8) else if (NV == 16) MUGIQ_PM_LAUNCH(16) else MUGIQ_PM_LAUNCH(24)
-#undef MUGIQ_PM_LAUNCH
-    MUGIQ_CHECK_HIP(hipGetLastError());
+    a.blkCount = std::min(form.blocksPerPass, blocks - b);
+    void (*kern)(ProlongMfmaArgs) = prolong_mfma_kernel<8>;
+    if (NV == 16) kern = prolong_mfma_kernel<16>;
+    else if (NV == 24) kern = prolong_mfma_kernel<24>;
+    if ((st = launch_with_lds(kern, form.workgroups, form.threads, form.ldsBytes, stream, a))) return st;
   }
   return MUGIQ_HIP_SUCCESS;
-}
-
-// what mugiq_hip_prolongate_batched may take from the HEAD of the per-stream workspace (the packed coarse vectors of the matrix-pipe form):
-// a caller that keeps data of its own in that workspace across the call leaves this much room in front of it
-size_t prolong_workspace_bytes(const MugiqHipTransfer *T, int nVec) {
-  size_t volc = 1;
-  for (int d = 0; d < 4; d++) volc *= (size_t)(T->X[d] / T->geoBlockSize[d]);
-  return sizeof(Cplx<double>) * volc * 2 * (size_t)T->nVec * (size_t)((nVec + 7) / 8 * 8);
 }
 
 // one coarse -> coarse level: `T` against the nVec fields of its finer (out_h) and coarser (in_h) side; shared with csrc/restrict.hip
@@ -1291,15 +1180,15 @@ int mugiq_hip_prolongate_batched(const MugiqHipSpinorField *fine_h, const MugiqH
   MUGIQ_REQUIRE(fine_h[0].precision == transfer->precision, "%s: fine precision %d != transfer precision %d", who, fine_h[0].precision, transfer->precision);
   for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(fine_h[0].X[d] == transfer->X[d], "%s: fine X[%d] mismatch", who, d);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int p = transfer->precision, o = fine_h[0].field_order;
-  if (p == 8 && o == 2) {
-    const int rc = prolong_mfma_plan(transfer, coarse_h, fine_h, nVec, s);  // the matrix-pipe form where the shape allows
-    if (rc >= 0) return rc;
-    return launch_prolong<double, double, 2, true, false>(transfer, coarse_h, fine_h, nullptr, nullptr, nVec, s);
+  const ProlongForm form = select_prolong_form(*transfer, transfer->precision, fine_h[0].field_order, nVec, transfer_switches_from_env());
+  if (form.family == MUGIQ_HIP_PROLONG_FAMILY_MFMA) return launch_prolong_mfma(form, transfer, coarse_h, fine_h, nVec, s);
+  const bool staged = form.family == MUGIQ_HIP_PROLONG_FAMILY_VECTOR_STAGED;
+  switch (10 * form.precision + form.order) {
+  case 82: return launch_prolong<double, double, 2, true, false>(form, staged, transfer, coarse_h, fine_h, nullptr, nullptr, nVec, s);
+  case 84: return launch_prolong<double, double, 4, true, false>(form, staged, transfer, coarse_h, fine_h, nullptr, nullptr, nVec, s);
+  case 42: return launch_prolong<float, float, 2, true, false>(form, staged, transfer, coarse_h, fine_h, nullptr, nullptr, nVec, s);
+  default: return launch_prolong<float, float, 4, true, false>(form, staged, transfer, coarse_h, fine_h, nullptr, nullptr, nVec, s);
   }
-  if (p == 8 && o == 4) return launch_prolong<double, double, 4, true, false>(transfer, coarse_h, fine_h, nullptr, nullptr, nVec, s);
-  if (p == 4 && o == 2) return launch_prolong<float, float, 2, true, false>(transfer, coarse_h, fine_h, nullptr, nullptr, nVec, s);
-  return launch_prolong<float, float, 4, true, false>(transfer, coarse_h, fine_h, nullptr, nullptr, nVec, s);
 }
 
 int mugiq_hip_prolongate_coarse_batched(const MugiqHipCoarseField *out_h, const MugiqHipCoarseField *in_h, int nVec,
@@ -1328,18 +1217,20 @@ int mugiq_hip_prolongate_contract_batched(void *loopData_d, int loopPrecision, c
   if (loopPrecision == 0) loopPrecision = p;
   MUGIQ_REQUIRE(loopPrecision == p || (loopPrecision == 8 && p == 4), "%s: loop precision %d with field precision %d is not supported", who, loopPrecision, p);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // MUGIQ_HIP_MG_PLAN=direct keeps the per-eigenvector kernel (prolong every eigenvector, contract on the spot)
-  const char *plan = getenv("MUGIQ_HIP_MG_PLAN");
-  if (!(plan && strcmp(plan, "direct") == 0)) {
-    int rc;
-    if (p == 8) rc = coarse_plan<double, double>(transfer, coarse_h, sigma_h, loopData_d, nVec, s);
-    else if (loopPrecision == 8) rc = coarse_plan<float, double>(transfer, coarse_h, sigma_h, loopData_d, nVec, s);
-    else rc = coarse_plan<float, float>(transfer, coarse_h, sigma_h, loopData_d, nVec, s);
-    if (rc >= 0) return rc;
+  const ContractForm form = select_prolong_contract_form(*transfer, loopPrecision, nVec, transfer_switches_from_env());
+  const bool coarse = form.family == MUGIQ_HIP_CONTRACT_FAMILY_COARSE_MFMA || form.family == MUGIQ_HIP_CONTRACT_FAMILY_COARSE_VECTOR;
+  const bool staged = form.family == MUGIQ_HIP_CONTRACT_FAMILY_DIRECT_STAGED;
+  auto run = [&](auto f, auto a) {  // storage F, accumulation A
+    using F = decltype(f);
+    using A = decltype(a);
+    if (coarse) return coarse_plan<F, A>(form, transfer, coarse_h, sigma_h, loopData_d, nVec, s);
+    return launch_prolong<F, A, 2, false, true>(form, staged, transfer, coarse_h, nullptr, sigma_h, loopData_d, nVec, s);
+  };
+  switch (10 * form.precision + form.loopPrecision) {
+  case 88: return run(double(), double());
+  case 48: return run(float(), double());
+  default: return run(float(), float());
   }
-  if (p == 8) return launch_prolong<double, double, 2, false, true>(transfer, coarse_h, nullptr, sigma_h, loopData_d, nVec, s);
-  if (loopPrecision == 8) return launch_prolong<float, double, 2, false, true>(transfer, coarse_h, nullptr, sigma_h, loopData_d, nVec, s);
-  return launch_prolong<float, float, 2, false, true>(transfer, coarse_h, nullptr, sigma_h, loopData_d, nVec, s);
 }
 
 }  // extern "C"

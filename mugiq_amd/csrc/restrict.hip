@@ -58,28 +58,8 @@ template <int ORDER> __device__ inline int64_t fine_elem(int k, int pty, int x_c
   else return pty * po + 2 * ((int64_t)(k >> 1) * stride + x_cb) + (k & 1);
 }
 
-struct LevelGeom {
-  int X[4], Xc[4], bs[4];
-  int aggVol, volumeCB, volumeCBc;
-};
-LevelGeom level_geom(const MugiqHipTransfer *T) {
-  LevelGeom g;
-  long long vol = 1, volc = 1;
-  g.aggVol = 1;
-  for (int d = 0; d < 4; d++) {
-    g.X[d] = T->X[d];
-    g.bs[d] = T->geoBlockSize[d];
-    g.Xc[d] = T->X[d] / T->geoBlockSize[d];
-    g.aggVol *= g.bs[d];
-    vol *= g.X[d];
-    volc *= g.Xc[d];
-  }
-  g.volumeCB = (int)(vol / 2);
-  g.volumeCBc = (int)(volc / 2);
-  return g;
-}
 // member k (lexicographic inside the block) of the aggregate at coarse coordinates cc
-__device__ inline void aggregate_member(const LevelGeom &g, const int cc[4], int k, int *pty, int *x_cb) {
+__device__ inline void aggregate_member(const TransferGeom &g, const int cc[4], int k, int *pty, int *x_cb) {
   int x[4];
 #pragma unroll
   for (int d = 0; d < 4; d++) {
@@ -94,7 +74,7 @@ struct RestrictArgs {
   const void *V;  // [parity][(3s+c)*NV + j][x_cb]
   int64_t Vpo;
   int Vstride, NV;
-  LevelGeom g;
+  TransferGeom g;
   const void *const *tab;  // device table: nVec fine bodies, then nVec coarse bodies
   int Fstride, Cstride;
   int64_t Fpo, Cpo;
@@ -188,7 +168,7 @@ int launch_restrict(const MugiqHipCoarseField *coarse, const MugiqHipSpinorField
   a.Vpo = T->parity_offset;
   a.Vstride = T->stride;
   a.NV = T->nVec;
-  a.g = level_geom(T);
+  a.g = transfer_geom(*T);
   a.tab = static_cast<const void *const *>(dev);
   a.Fstride = fine[0].stride;
   a.Fpo = fine[0].parity_offset;
@@ -241,7 +221,7 @@ struct RestrictCoarseArgs {
   const void *V;  // [parity][(NCf*s + c)*NV + j][x_cb]
   int64_t Vpo;
   int Vstride, NV, NCf;
-  LevelGeom g;
+  TransferGeom g;
   const void *const *tab;  // device table: nVec finer bodies, then nVec coarser bodies
   int Istride, Ostride;
   int64_t Ipo, Opo;
@@ -295,7 +275,7 @@ int launch_restrict_coarse(const MugiqHipCoarseField *coarser, const MugiqHipCoa
   a.Vstride = T->stride;
   a.NV = T->nVec;
   a.NCf = finer[0].nColor;
-  a.g = level_geom(T);
+  a.g = transfer_geom(*T);
   a.tab = static_cast<const void *const *>(dev);
   a.Istride = finer[0].stride;
   a.Ipo = finer[0].parity_offset;
@@ -398,7 +378,7 @@ struct ProlongSubtractArgs {
   const void *V;
   int64_t Vpo;
   int Vstride, NV;
-  LevelGeom g;
+  TransferGeom g;
   const void *const *tab;  // device table: nVec coarse bodies (z), then nVec dst bodies
   int Fstride, Cstride;
   int64_t Fpo, Cpo;
@@ -451,7 +431,7 @@ int launch_prolong_subtract(const MugiqHipSpinorField *dst, const MugiqHipCoarse
   a.Vpo = T->parity_offset;
   a.Vstride = T->stride;
   a.NV = T->nVec;
-  a.g = level_geom(T);
+  a.g = transfer_geom(*T);
   a.tab = static_cast<const void *const *>(dev);
   a.Fstride = dst[0].stride;
   a.Fpo = dst[0].parity_offset;
@@ -480,12 +460,6 @@ int prolong_subtract(const MugiqHipSpinorField *dst, const MugiqHipCoarseField *
   return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "deflateLowModesCoarse: precision %d / %d, field order %d", pv, pf, o);
 }
 
-// [first, last) byte range a fine field's kernels may touch
-void fine_span(const MugiqHipSpinorField &f, uintptr_t *a, uintptr_t *b) {
-  *a = reinterpret_cast<uintptr_t>(f.data);
-  *b = *a + (uintptr_t)(f.parity_offset + (int64_t)12 * f.stride) * 2 * f.precision;
-}
-
 // The hierarchy of a call on coarse eigenvectors: transfers[0 .. nLevels) (finest first) fit together and the nEv eigenvectors live on
 // the coarsest level.  lev[l]: the layout of the work vectors on level l + 1 (the coarser side of transfers[l]), without a body; the
 // coarsest one takes the eigenvectors' stride and parity offset, so that one element offset serves both
@@ -499,18 +473,9 @@ int validate_hierarchy(const MugiqHipTransfer *transfers, int nLevels, const Mug
     const MugiqHipTransfer &T = transfers[l];
     MUGIQ_REQUIRE(T.V != nullptr && T.nVec >= 1, "%s: transfer %d is empty", who, l);
     MUGIQ_REQUIRE(T.precision == ev[0].precision, "%s: transfer %d has precision %d, the eigenvectors %d", who, l, T.precision, ev[0].precision);
-    MugiqHipCoarseField f{};
-    f.data = reinterpret_cast<void *>(uintptr_t(16) * (l + 1));  // geometry only: the validators want distinct non-NULL bodies and never read them
-    f.precision = T.precision, f.nSpin = 2, f.nColor = T.nVec;
-    long long volc = 1;
-    for (int d = 0; d < 4; d++) {
-      MUGIQ_REQUIRE(T.X[d] > 0 && T.geoBlockSize[d] >= 1, "%s: transfer %d: X / geo_block_size[%d]", who, l, d);
-      f.X[d] = T.X[d] / T.geoBlockSize[d];
-      volc *= f.X[d];
-    }
-    f.volumeCB = f.stride = (int)(volc / 2);
-    f.parity_offset = (int64_t)2 * f.nColor * f.stride;
-    lev[l] = f;
+    for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(T.X[d] > 0 && T.geoBlockSize[d] >= 1, "%s: transfer %d: X / geo_block_size[%d]", who, l, d);
+    lev[l] = coarse_side_layout(T);
+    lev[l].data = reinterpret_cast<void *>(uintptr_t(16) * (l + 1));  // geometry only: the validators want distinct non-NULL bodies and never read them
     if (l == 0) st = validate_transfer(&T, &lev[0], who);
     else st = validate_coarse_transfer(&T, &lev[l - 1], &lev[l], 1, who);
     if (st) return st;
@@ -554,10 +519,10 @@ int deflate_low_modes_coarse(const MugiqHipSpinorField *dst, const MugiqHipSpino
   for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(src[0].X[d] == transfers[0].X[d], "%s: src X[%d] = %d, the finest transfer's is %d", who, d, src[0].X[d], transfers[0].X[d]);
   for (int r = 0; r < nVec; r++) {
     uintptr_t a0, a1;
-    fine_span(dst[r], &a0, &a1);
+    spinor_span(dst[r], &a0, &a1);
     for (int q = 0; q < nVec; q++) {
       uintptr_t b0, b1;
-      fine_span(src[q], &b0, &b1);
+      spinor_span(src[q], &b0, &b1);
       const bool overlap = a0 < b1 && b0 < a1;
       MUGIQ_REQUIRE(!overlap || (q == r && dst[r].data == src[r].data), "%s: dst vector %d overlaps src vector %d without being identical to it", who, r, q);
     }
@@ -575,7 +540,7 @@ int deflate_low_modes_coarse(const MugiqHipSpinorField *dst, const MugiqHipSpino
   size_t bytes = 0;
   for (int l = 0; l < nLevels; l++) {
     levOff[l] = bytes;
-    bytes += ((size_t)2 * lev[l].parity_offset * 2 * P * nVec + 255) / 256 * 256;
+    bytes += align256((size_t)2 * lev[l].parity_offset * 2 * P * nVec);
   }
   const size_t cN = (size_t)nEv * nVec, cOff = bytes;
   bytes += 2 * cN * sizeof(Cplx<double>);
@@ -681,8 +646,6 @@ __global__ __launch_bounds__(kCoThreads) void coarse_scalar_kernel(const void *c
   if (t < 3) out[3 * i + t] = red[t][0];
 }
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace
 
 int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipTransfer *transfers, int nLevels, const MugiqHipGaugeField *gauge,
@@ -703,7 +666,7 @@ int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipT
   const MugiqHipTransfer &T0 = transfers[0];
   if ((st = check_comm(comm, part, true, who))) return st;
   if ((st = check_gauge(gauge, T0.X, part, who))) return st;
-  const LevelGeom g0 = level_geom(&T0);
+  const TransferGeom g0 = transfer_geom(T0);
   if (clover) {
     if ((st = validate_clover(clover, T0.X, g0.volumeCB, who))) return st;
     MUGIQ_REQUIRE(clover->precision == gauge->precision, "%s: clover precision %d differs from the gauge precision %d", who, clover->precision, gauge->precision);
@@ -713,7 +676,7 @@ int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipT
   // ---- work memory (per-stream workspace): [room for the prolongator's packed coarse vectors][2 x 8 fine vectors with ghost zones]
   // [2 x 8 coarse vectors on every level][lambda and sums]
   const size_t P = (size_t)T0.precision;
-  const size_t head = align256(prolong_workspace_bytes(&T0, kEvBlock));
+  const size_t head = align256(select_prolong_form(T0, T0.precision, 2, kEvBlock, TransferSwitches{}).workspaceBytes);  // (the same under every switch)
   const size_t fineBody = align256((size_t)24 * g0.volumeCB * 2 * P);
   size_t zone[4], fineBytes = fineBody;
   for (int d = 0; d < 4; d++) {

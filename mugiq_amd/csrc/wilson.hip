@@ -401,7 +401,6 @@ __global__ void wilson_final_sum_kernel(const double *partial, int nGroups, unsi
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 size_t body_bytes(const MugiqHipSpinorField &f, int prec) { return align256((size_t)2 * (size_t)f.parity_offset * 2 * (size_t)prec); }
 size_t zone_bytes(const MugiqHipSpinorField &f, int prec, int d) { return (size_t)24 * (size_t)(f.volumeCB / f.X[d]) * 2 * (size_t)prec; }
 size_t ghost_bytes(const MugiqHipSpinorField &f, int prec, const int part[4]) {
@@ -441,10 +440,6 @@ struct OpContext {
 
 bool same_layout(const MugiqHipSpinorField &a, const MugiqHipSpinorField &b) {
   return same_geometry(a, b) && a.stride == b.stride && a.parity_offset == b.parity_offset;
-}
-void span_of(const MugiqHipSpinorField &f, uintptr_t *a, uintptr_t *b) {
-  *a = reinterpret_cast<uintptr_t>(f.data);
-  *b = *a + (uintptr_t)(f.parity_offset + (int64_t)12 * f.stride) * 2 * f.precision;
 }
 
 }  // namespace
@@ -690,10 +685,10 @@ static int wilson_apply_impl(const MugiqHipSpinorField *dst_h, const MugiqHipSpi
   MUGIQ_REQUIRE(same_layout(dst_h[0], src_h[0]), "%s: dst and src differ in precision, field order, geometry, stride or parity offset", who);
   for (int i = 0; i < nVec; i++) {
     uintptr_t a0, a1;
-    span_of(dst_h[i], &a0, &a1);
+    spinor_span(dst_h[i], &a0, &a1);
     for (int j = 0; j < nVec; j++) {
       uintptr_t b0, b1;
-      span_of(src_h[j], &b0, &b1);
+      spinor_span(src_h[j], &b0, &b1);
       MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: dst vector %d overlaps src vector %d (the kernel reads neighbours of src)", who, i, j);
     }
   }
@@ -822,10 +817,10 @@ static int wilson_solve_impl(const MugiqHipSpinorField *x_h, const MugiqHipSpino
   MUGIQ_REQUIRE(same_layout(x_h[0], b_h[0]), "%s: x and b differ in precision, field order, geometry, stride or parity offset", who);
   for (int i = 0; i < nVec; i++) {
     uintptr_t a0, a1;
-    span_of(x_h[i], &a0, &a1);
+    spinor_span(x_h[i], &a0, &a1);
     for (int j = 0; j < nVec; j++) {
       uintptr_t b0, b1;
-      span_of(b_h[j], &b0, &b1);
+      spinor_span(b_h[j], &b0, &b1);
       MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: x vector %d overlaps b vector %d", who, i, j);
     }
   }

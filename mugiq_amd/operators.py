@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .fields import SpinorField, GaugeField, desc_array, coarse_desc_array, transfer_desc_array
+from .fields import SpinorField, GaugeField, Transfer, desc_array, coarse_desc_array, transfer_desc_array
 
 N_GAMMA = 16
 DispDir = {"x": 0, "y": 1, "z": 2, "t": 3}          # include/enum_mugiq.h:72-78
@@ -23,6 +23,9 @@ REGION_ALL, REGION_INTERIOR, REGION_BOUNDARY, REGION_OVERWRITE = 0, 1, 2, 0x100 
 # mugiq_hip_convert_and_project_plan: the kernel form of the fused reorder + x step (MUGIQ_HIP_PROJECT_FORM_*)
 PROJECT_FORM_GENERAL, PROJECT_FORM_PIPELINED, PROJECT_FORM_MFMA = range(3)
 ENTRY_KERNEL_REFLECTED, ENTRY_KERNEL_MFMA_COLUMN, ENTRY_KERNEL_MFMA_ROW, ENTRY_KERNEL_VECTOR_TILE, ENTRY_KERNEL_STREAMING, ENTRY_KERNEL_STEPWISE = range(6)
+# mugiq_hip_transfer_form: the kernel forms of an MG transfer (MUGIQ_HIP_PROLONG_FAMILY_*, MUGIQ_HIP_CONTRACT_FAMILY_*)
+PROLONG_FAMILY_MFMA, PROLONG_FAMILY_VECTOR_STAGED, PROLONG_FAMILY_VECTOR_GLOBAL = 1, 2, 3
+CONTRACT_FAMILY_COARSE_MFMA, CONTRACT_FAMILY_COARSE_VECTOR, CONTRACT_FAMILY_DIRECT_STAGED, CONTRACT_FAMILY_DIRECT_GLOBAL = 1, 2, 3, 4
 
 
 def _stream():
@@ -316,6 +319,25 @@ def prolongateContractBatched(loopData_d, coarseEvecs, sigmas, transfer):
     sg = (ctypes.c_double * n)(*[float(s) for s in sigmas])
     _lib.check(_lib.load().mugiq_hip_prolongate_contract_batched(loopData_d.data_ptr(), _prec_of(loopData_d), coarse_desc_array(coarseEvecs),
                                                                  sg, n, ctypes.byref(t), _stream()))
+
+
+def transferForm(transfer, nVec, fineOrder=2, loopPrecision=0):
+    """The kernel forms prolongateEvecs and prolongateContractBatched run on for this finest-level transfer and nVec eigenvectors, with their
+    launch geometry and the level geometry (mugiq_hip_transfer_form), as a dict: what the compute calls select, under the same MUGIQ_HIP_*
+    switches.  Host only, no GPU is touched, so a descriptor will do: transfer a Transfer or (X, geo_block_size, n_vec, precision[, pad])."""
+    if isinstance(transfer, Transfer):
+        t = transfer.desc()
+    else:
+        X, bs, n_vec, prec = transfer[:4]
+        t = _lib.TransferDesc()
+        t.V, t.precision, t.nVec, t.spinBlockSize = 16, int(prec), int(n_vec), 2
+        t.stride = int(np.prod(X)) // 2 + (int(transfer[4]) if len(transfer) > 4 else 0)
+        t.parity_offset = 12 * t.nVec * t.stride
+        for d in range(4):
+            t.X[d], t.geoBlockSize[d] = int(X[d]), int(bs[d])
+    out = _lib.TransferForm()
+    _lib.check(_lib.load().mugiq_hip_transfer_form(ctypes.byref(t), 0, int(fineOrder), int(loopPrecision), int(nVec), ctypes.byref(out)))
+    return {n: list(getattr(out, n)) if n in ("X", "Xc", "bs") else getattr(out, n) for n, _ in _lib.TransferForm._fields_}
 
 
 def restrictVecs(coarseVecs, fineVecs, transfer, gamma5=False):

@@ -480,12 +480,20 @@ def test_prolongator_matches_oracle(hip, prec, order, X, bs, nvec, nev, monkeypa
     T = hip.Transfer(X, nvec, bs, 2, prec).set_logical(V)
     cf = [hip.CoarseField(Xc, nvec, prec).set_logical(p) for p in phis]
     ff = [hip.SpinorField(X, prec, order) for _ in range(nev)]
+    # the kernel each shape runs on (hip.transferForm: the selector of the call itself): the matrix pipe for fp64 FLOAT2, n_vec 8 | 16 | 24,
+    # aggregates of 16 k sites; else the vector kernel, with the V tile in LDS unless an fp64 tile is larger than it (n_vec > 53)
+    monkeypatch.delenv("MUGIQ_HIP_PROLONG_MFMA", raising=False)
+    vector = hip.PROLONG_FAMILY_VECTOR_GLOBAL if (prec, nvec) == (8, 64) else hip.PROLONG_FAMILY_VECTOR_STAGED
+    mfma = prec == 8 and order == 2 and nvec in (8, 16, 24) and int(np.prod(bs)) % 16 == 0
+    assert mfma == ((X, nvec) not in (((8, 4, 12, 4), 6), ((4, 4, 4, 6), 3), ((4, 4, 4, 4), 64)) and (prec, order) == (8, 2))
+    assert hip.transferForm(T, nev, fineOrder=order)["prolongFamily"] == (hip.PROLONG_FAMILY_MFMA if mfma else vector)
     hip.prolongateEvecs(ff, cf, T)
     exps = [orc.prolongate(phis[n].astype(np.complex128), V.astype(np.complex128), X, bs) for n in range(nev)]
     for n in range(nev):
         assert rel_err(ff[n].get_logical(), exps[n]) < (1e-14 if prec == 8 else 2e-6), n
     if prec == 8 and order == 2:                      # the vector kernel on the same input (MUGIQ_HIP_PROLONG_MFMA=0)
         monkeypatch.setenv("MUGIQ_HIP_PROLONG_MFMA", "0")
+        assert hip.transferForm(T, nev, fineOrder=order)["prolongFamily"] == vector
         for f in ff:
             f.data.zero_()
         hip.prolongateEvecs(ff, cf, T)
@@ -542,6 +550,13 @@ def test_fused_prolong_contract_matches_oracle(hip, prec, lprec, X, bs, nvec, ne
     cf = [hip.CoarseField(Xc, nvec, prec).set_logical(p) for p in phis]
     Vt = int(np.prod(X))
     loop = torch.zeros(16 * Vt, dtype=torch.complex128 if lprec == 8 else torch.complex64, device="cuda")
+    # the kernels the call runs on (hip.transferForm: the selector of the call itself)
+    monkeypatch.delenv("MUGIQ_HIP_MG_MFMA", raising=False)
+    if plan == "coarse" and nvec in (8, 12, 16, 24, 32):
+        want = hip.CONTRACT_FAMILY_COARSE_MFMA if lprec == 8 and nvec != 12 and int(np.prod(bs)) % 16 == 0 else hip.CONTRACT_FAMILY_COARSE_VECTOR
+    else:
+        want = hip.CONTRACT_FAMILY_DIRECT_GLOBAL if (prec, nvec) == (8, 64) else hip.CONTRACT_FAMILY_DIRECT_STAGED
+    assert hip.transferForm(T, nev, loopPrecision=lprec)["contractFamily"] == want
     hip.prolongateContractBatched(loop, cf, sg, T)
     ref = np.zeros(16 * Vt, dtype=np.complex128)
     for n in range(nev):

@@ -144,13 +144,17 @@ def test_adjoint_of_the_library_prolongator(hip, mfma, monkeypatch, record_max):
     """<R psi, phi> = <psi, P phi> with the library's prolongator in both of its forms, to 1e-13 of |psi| |P phi|; R P phi = phi for a
     block-orthonormal V.  8 8 4 4 with 4 4 2 2 aggregates and n_vec 16: a shape the matrix-pipe prolongator takes."""
     monkeypatch.setenv("MUGIQ_HIP_PROLONG_MFMA", mfma)
+    family = hip.transferForm(((8, 8, 4, 4), (4, 4, 2, 2), 16, 8), 5)["prolongFamily"]
+    assert family == (hip.PROLONG_FAMILY_MFMA if mfma == "1" else hip.PROLONG_FAMILY_VECTOR_STAGED)
     _check_adjoint_of_the_prolongator(hip, (8, 8, 4, 4), (4, 4, 2, 2), 16, 5, record_max)
 
 
 @pytest.mark.parametrize("X,bs,nvec", RAGGED_SHAPES)
 def test_adjoint_of_the_vector_prolongator_beyond_one_pass(hip, X, bs, nvec, record_max):
     """The same two properties where restrict_kernel makes more than one null-vector pass or a ragged slot walk.  None of these n_vec is
-    8, 16 or 24, so the prolongator is the library's vector kernel (prolong_mfma_plan returns -1), which loops over j in one piece."""
+    8, 16 or 24, so the prolongator is the library's vector kernel (what hip.transferForm reports), which loops over j in one piece."""
+    vector = hip.PROLONG_FAMILY_VECTOR_STAGED if nvec <= 53 else hip.PROLONG_FAMILY_VECTOR_GLOBAL      # (an fp64 V tile of 16 sites in LDS, or not)
+    assert hip.transferForm((X, bs, nvec, 8), 9)["prolongFamily"] == vector
     _check_adjoint_of_the_prolongator(hip, X, bs, nvec, 9, record_max)
 
 
@@ -507,16 +511,18 @@ def test_coarse_evals_multilevel_match_numpy(hip, levels, with_clover, mass_norm
 
 @pytest.mark.parametrize("with_clover", [False, True])
 def test_coarse_evals_two_levels_agree_without_the_matrix_pipe_prolongator(hip, with_clover, monkeypatch, record_max):
-    """The two-level case (n_vec 8 on 16-site aggregates: prolong_mfma_plan takes the fp64 FLOAT2 work vectors) against the same calls with
-    MUGIQ_HIP_PROLONG_MFMA=0, the vector prolongator: 1e-13."""
+    """The two-level case (n_vec 8 on 16-site aggregates: the matrix-pipe prolongator takes the fp64 FLOAT2 work vectors) against the same
+    calls with MUGIQ_HIP_PROLONG_MFMA=0, the vector prolongator: 1e-13."""
     shape = MULTI_LEVEL[2]
     gauge, C, _, _ = _device_operator(hip, shape[0], with_clover)
     Xs, bss, Vs, Ts, ws, cw = _evals_hierarchy(hip, shape)
     for mass_norm in (False, True):
         for op in range(5):
             monkeypatch.delenv("MUGIQ_HIP_PROLONG_MFMA", raising=False)
+            assert hip.transferForm(Ts[0], 8)["prolongFamily"] == hip.PROLONG_FAMILY_MFMA      # (blocks of 8 eigenvectors)
             default = hip.computeEvalsCoarse(cw, Ts, gauge, KAPPA, op, mass_norm, clover=C)
             monkeypatch.setenv("MUGIQ_HIP_PROLONG_MFMA", "0")
+            assert hip.transferForm(Ts[0], 8)["prolongFamily"] == hip.PROLONG_FAMILY_VECTOR_STAGED
             vector = hip.computeEvalsCoarse(cw, Ts, gauge, KAPPA, op, mass_norm, clover=C)
             e = _evals_err(vector, default)
             record_max("coarse_evals_mfma_vs_vector", e)
