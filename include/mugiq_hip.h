@@ -949,6 +949,52 @@ int mugiq_hip_free_extended_gauge(MugiqHipGaugeField *gauge);
 int mugiq_hip_create_extended_gauge(const MugiqHipGaugeField *gauge, const void *const qdpLinks_h[4], int cpuPrecision,
                                     const MugiqHipComm *comm, void *stream);
 
+/* ---- stout smearing of the extended gauge field, its border refresh and the plaquette (csrc/smear.hip; new) ---------------------------
+ * Displaced loops run on a second gauge field (--loop-gauge-filename, tests/loop.cpp:902-918), in production a smeared copy of the
+ * configuration; the reference prints the plaquette of what it loaded (tests/loop.cpp:895-898).  One stout step (Morningstar and
+ * Peardon, hep-lat/0311018) of a link U_mu(x) that is smeared, S the set of smeared directions:
+ *   C_mu(x)  = sum_{nu in S, nu != mu} [ U_nu(x) U_mu(x+nu) U_nu^dag(x+mu)  +  U_nu^dag(x-nu) U_mu(x-nu) U_nu(x-nu+mu) ]
+ *   Omega    = rho C_mu(x) U_mu^dag(x)
+ *   Q        = (i/2) (Omega^dag - Omega) - (i/6) tr(Omega^dag - Omega) 1              (Hermitian, traceless)
+ *   U'_mu(x) = exp(iQ) U_mu(x)
+ * smearDims = 3: S = {x, y, z}; the spatial links are smeared with spatial staples and the t links are copied unchanged.
+ * smearDims = 4: S = all four directions, every link is smeared.  U^dag is the conjugate transpose of the link as stored, as everywhere
+ * else in the library.  exp(iQ) = f0 + f1 Q + f2 Q^2 analytically (Cayley-Hamilton) from c0 = det Q and c1 = tr Q^2 / 2 in the
+ * (u, w, xi0(w)) form of that paper, with the series of xi0 for small w and the symmetry c0 -> -c0.  Q = 0 (rho = 0, pure-gauge links, a
+ * constant abelian field) has c1 = 0, where the closed form is 0/0: for c1 <= 1e-14 (Q^3/6 below 1e-21) the series 1 + iQ - Q^2/2 is
+ * taken, which is exact to rounding there and gives U' = U without a NaN.  Every step reads the field of the step before: smearing is out of place, with a
+ * ping-pong between two fields.  fp64 arithmetic whatever the storage, rounded once per step on the store.
+ *
+ * Plaquette:
+ *   P_mn(x)  = Re tr [ U_m(x) U_n(x+m) U_m^dag(x+n) U_n^dag(x) ] / 3
+ *   spatial  = mean over the local sites of all ranks and the planes xy, xz, yz
+ *   temporal = mean over the local sites of all ranks and the planes xt, yt, zt
+ *   plaq[0]  = (spatial + temporal) / 2,  plaq[1] = spatial,  plaq[2] = temporal
+ * This is the normalisation ASSUMED for QUDA's plaqQuda (1 for unit links); QUDA is not available to this project, so it has not
+ * been compared against it.
+ *
+ * Links are addressed in the extended field as mugiq_hip_compute_clover addresses them: x +- nu across a face comes from the border
+ * where R >= 1 and wraps where R = 0, x - nu + mu from the edge regions.  A partitioned dimension (comm) with R[d] = 0, or without
+ * comm->sendrecv, is MUGIQ_HIP_ERROR_INVALID_ARGUMENT for all three calls, as are a NULL descriptor or data, a precision other than
+ * 4 | 8, odd local dims and an odd sum of the borders; all of it is checked before any device work. */
+/* Refresh the R-deep borders of a device-resident field from its interior: the device counterpart of the border half of
+ * mugiq_hip_create_extended_gauge (the reference's exchangeExtendedGhost, lib/displace.cpp:127).  One dimension after the other, later
+ * ones carrying the borders of earlier ones (edges and corners); a dimension that is not partitioned is wrapped on the device, a
+ * partitioned one goes pack kernel -> comm->sendrecv -> unpack kernel.  The result equals, bit for bit, what
+ * mugiq_hip_create_extended_gauge builds from the same interior.  Pads are not written. */
+int mugiq_hip_exchange_extended_gauge(const MugiqHipGaugeField *gauge, const MugiqHipComm *comm, void *stream);
+/* nSteps stout steps of `in` into `out` (same X, R and precision; strides may differ; the buffers must not overlap:
+ * MUGIQ_HIP_ERROR_INVALID_ARGUMENT otherwise, and for nSteps < 0, smearDims not 3 | 4, rho not finite).  The borders of `in` must be
+ * valid (mugiq_hip_create_extended_gauge or mugiq_hip_exchange_extended_gauge).  One kernel per step and a border refresh after every
+ * step: `out` ends complete, borders included; `in` is never written.  nSteps >= 2 allocates one temporary field inside the call and
+ * frees it (set-up-time code); nSteps = 0 copies `in` to `out`.  Pads are not written. */
+int mugiq_hip_stout_smear(const MugiqHipGaugeField *out, const MugiqHipGaugeField *in, double rho, int nSteps, int smearDims,
+                          const MugiqHipComm *comm, void *stream);
+/* plaq_h[3] = {mean, spatial, temporal} of the definition above, summed over the ranks of comm (NULL: one process; otherwise
+ * reduce_space, gather_time and bcast must be set when size > 1).  One local site per lane, a fixed-order fp64 reduction: bitwise
+ * reproducible, and identical on every rank.  Blocks the host. */
+int mugiq_hip_plaquette(const MugiqHipGaugeField *gauge, double plaq_h[3], const MugiqHipComm *comm, void *stream);
+
 /* ---- user syntax (tests/loop.cpp:607-705) -------------------------------------------------------------------------- */
 /* Parse "+z:1,8;-x:3;+y:2,5".  Returns the number of entries (<= max_entries) or a negative MugiqHipStatus.
  * disp_str_out: max_entries x 4 chars ("+z\0"); start/stop as in setLoopParam. */

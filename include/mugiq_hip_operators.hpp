@@ -12,6 +12,7 @@
 #ifndef MUGIQ_HIP_OPERATORS_HPP
 #define MUGIQ_HIP_OPERATORS_HPP
 
+#include <array>
 #include <climits>
 #include <complex>
 #include <cstdio>
@@ -177,6 +178,22 @@ inline bool wilsonSolve(const std::vector<ColorSpinorField> &x, const std::vecto
   if (st == MUGIQ_HIP_ERROR_NOT_CONVERGED) return false;
   check(st);
   return true;
+}
+// ---- stout smearing, border refresh and plaquette of the border-extended gauge field (csrc/smear.hip; new) ----
+// the R-deep borders of a device-resident field from its interior (exchangeExtendedGhost, lib/displace.cpp:127)
+inline void exchangeExtendedGauge(const GaugeField &gauge, const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  check(mugiq_hip_exchange_extended_gauge(&gauge, comm, stream));
+}
+// nSteps stout steps of `in` into `out` (same geometry and precision, no overlap); smearDims 3: spatial links and staples only, 4: all
+inline void stoutSmear(const GaugeField &out, const GaugeField &in, double rho, int nSteps, int smearDims = 3, const MugiqHipComm *comm = nullptr,
+                       void *stream = nullptr) {
+  check(mugiq_hip_stout_smear(&out, &in, rho, nSteps, smearDims, comm, stream));
+}
+// {mean, spatial, temporal} of Re tr P / 3 over all ranks, what the reference prints after plaqQuda (tests/loop.cpp:895-898)
+inline std::array<double, 3> plaquette(const GaugeField &gauge, const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  std::array<double, 3> plaq{};
+  check(mugiq_hip_plaquette(&gauge, plaq.data(), comm, stream));
+  return plaq;
 }
 // ---- the clover term (csrc/clover.hip; new): a device field the holder owns, and the three calls above for the Wilson-clover operator ----
 class CloverField {

@@ -193,6 +193,9 @@ SIGNATURES = {
     "mugiq_hip_alloc_clover": (ctypes.c_int, [_CP, _I4, ctypes.c_int]),
     "mugiq_hip_free_clover": (ctypes.c_int, [_CP]),
     "mugiq_hip_compute_clover": (ctypes.c_int, [_CP, _GP, ctypes.c_double, _VP, _VP]),
+    "mugiq_hip_exchange_extended_gauge": (ctypes.c_int, [_GP, _VP, _VP]),
+    "mugiq_hip_stout_smear": (ctypes.c_int, [_GP, _GP, ctypes.c_double, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    "mugiq_hip_plaquette": (ctypes.c_int, [_GP, ctypes.POINTER(ctypes.c_double), _VP, _VP]),
     "mugiq_hip_wilson_clover_apply": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.c_int, ctypes.c_double, _VP, _VP]),
     "mugiq_hip_compute_evals_clover": (ctypes.c_int, [_SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                                       ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),

@@ -151,6 +151,40 @@ class GaugeField:
             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return self
 
+    @staticmethod
+    def _comm_ptr(comm):
+        c = comm.c_struct() if comm is not None else None
+        return c, (ctypes.cast(ctypes.byref(c), ctypes.c_void_p) if c is not None else None)
+
+    def exchangeBorders(self, comm=None):
+        """Refresh the R-deep borders from the interior on the device (mugiq_hip_exchange_extended_gauge): neighbour slabs through
+        `comm` (a GridComm) along its partitioned dimensions, a periodic wrap along the others."""
+        d = self.desc()
+        c, cp = self._comm_ptr(comm)
+        _lib.check(_lib.load().mugiq_hip_exchange_extended_gauge(ctypes.byref(d), cp, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return self
+
+    def stoutSmear(self, rho, nSteps, smearDims=3, comm=None, out=None):
+        """nSteps stout steps (mugiq_hip_stout_smear; smearDims 3: spatial links and staples only, 4: all) into `out`, a new field of
+        the same geometry unless one is given.  This field, whose borders must be valid, is not written.  Returns `out`."""
+        if out is None:
+            out = GaugeField(self.X, self.R, self.precision, pad=self.stride - self.volumeExCB, device=self.device)
+        if not isinstance(out, GaugeField):
+            raise _lib.MugiqHipError("stoutSmear: out must be a GaugeField")
+        i, o = self.desc(), out.desc()
+        c, cp = self._comm_ptr(comm)
+        _lib.check(_lib.load().mugiq_hip_stout_smear(ctypes.byref(o), ctypes.byref(i), float(rho), int(nSteps), int(smearDims), cp,
+                                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return out
+
+    def plaquette(self, comm=None):
+        """(mean, spatial, temporal) of Re tr P / 3 over all ranks of `comm` (mugiq_hip_plaquette); 1 for unit links."""
+        d = self.desc()
+        c, cp = self._comm_ptr(comm)
+        plaq = (ctypes.c_double * 3)()
+        _lib.check(_lib.load().mugiq_hip_plaquette(ctypes.byref(d), plaq, cp, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return plaq[0], plaq[1], plaq[2]
+
     def get_logical(self):
         d = np.arange(4).reshape(4, 1, 1, 1, 1)
         p = np.arange(2).reshape(1, 2, 1, 1, 1)

@@ -33,6 +33,26 @@ def _choice(mapping):
     return conv
 
 
+def _nonneg_int(s):
+    try:
+        v = int(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected an integer, got %r" % s)
+    if v < 0:
+        raise argparse.ArgumentTypeError("must not be negative")
+    return v
+
+
+def _finite_float(s):
+    try:
+        v = float(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected a number, got %r" % s)
+    if not np.isfinite(v):
+        raise argparse.ArgumentTypeError("must be finite")
+    return v
+
+
 def add_loop_option_mugiq(parser):
     """add_loop_option_mugiq (tests/test_params_mugiq.cpp:77-112): same names, same defaults (tests/test_params_mugiq.cpp:12-24)."""
     g = parser.add_argument_group("Loop-MuGiq", "Loop Options within MuGiq")
@@ -117,6 +137,15 @@ def build_parser():
     ap.add_argument("--check-evals", action="store_true",
                     help="print the printEvals lines (lambda = v^dag MdagM v / ||v||, residual, sigma) of the eigenvectors the loop runs on; "
                          "needs the gauge field of a displaced loop")
+    # stout smearing of the displacement links and the plaquette: this project's own flags, the reference has none
+    ap.add_argument("--loop-gauge-stout-steps", type=_nonneg_int, default=0, metavar="N",
+                    help="stout-smear the gauge field of the displacements N times before the loops run on it (default 0: as loaded); "
+                         "--check-evals keeps the field as loaded")
+    ap.add_argument("--loop-gauge-stout-rho", type=_finite_float, default=0.1, metavar="R", help="stout weight rho (default 0.1)")
+    ap.add_argument("--loop-gauge-stout-dims", type=int, choices=[3, 4], default=3,
+                    help="3: spatial links with spatial staples, t links unchanged (default); 4: every link")
+    ap.add_argument("--compute-plaquette", action="store_true",
+                    help="print the plaquette of the gauge field of the displacements, as the reference does after plaqQuda")
     add_loop_option_mugiq(ap)
     return ap
 
@@ -175,7 +204,21 @@ def main(argv=None):
         raise SystemExit("--gridsize %s needs %d processes (torchrun)" % (args.gridsize, int(np.prod(args.gridsize))))
     rank = dist.get_rank() if world > 1 else 0
     fields, sigma, gauge = synthetic_inputs(args, rank, comm)
-    prm = setLoopParam(args, gauge)
+    # the links of the displacements: the loaded field, or a stout-smeared copy of it (the operator of --check-evals keeps the loaded one)
+    loop_gauge = gauge
+    if args.loop_gauge_stout_steps > 0 or args.compute_plaquette:
+        if gauge is None:
+            raise SystemExit("--loop-gauge-stout-steps / --compute-plaquette need a gauge field: set --loop-do-nonlocal yes and --displace-entry-string")
+
+        def print_plaquette(g):
+            plaq = g.plaquette(comm)
+            if rank == 0:
+                print("Computed plaquette is %e (spatial = %e, temporal = %e)" % tuple(plaq), file=sys.stderr)   # tests/loop.cpp:898
+        print_plaquette(gauge)
+        if args.loop_gauge_stout_steps > 0:
+            loop_gauge = gauge.stoutSmear(args.loop_gauge_stout_rho, args.loop_gauge_stout_steps, args.loop_gauge_stout_dims, comm)
+            print_plaquette(loop_gauge)
+    prm = setLoopParam(args, loop_gauge)
     if args.loop_prec == "double":
         prm.loopPrecision = 8
 
