@@ -146,8 +146,8 @@ __global__ __launch_bounds__(BLOCK) void loop_contract_kernel(ContractArgs<A> a)
   trace_and_store(a.loop, acc, V, site);
 }
 
-// Launch configuration.  Defaults were picked by sweeping on MI355X (profiles/); MUGIQ_HIP_CONTRACT_TUNE="block,depth,nt"
-// overrides them for experiments (e.g. "512,3,1").
+// Launch configuration.  Defaults were picked by sweeping on MI355X (profiles/); MUGIQ_HIP_CONTRACT_TUNE="block,depth,nt,swz"
+// overrides them for experiments (e.g. "512,3,1,1"; three fields, "block,depth,nt", leave swz at 0: XCD swizzle off).
 struct ContractTune {
   int block, depth, nt, swz;
 };
@@ -188,10 +188,15 @@ static void launch_depth(const ContractArgs<A> &a, const ContractTune &t, hipStr
   else launch_variant<F, A, ORDER, SAME, BLOCK, (SAME ? 3 : 2)>(a, t.nt, stream);
 }
 
+// the block size launch_block launches for a tune: the mixed mode is built for the default block size only
+template <typename F, typename A> static int launched_block(const ContractTune &t) {
+  return std::is_same<F, A>::value ? t.block : 256;
+}
+
 template <typename F, typename A, int ORDER, bool SAME>
 static void launch_block(const ContractArgs<A> &a, const ContractTune &t, hipStream_t stream) {
   if constexpr (std::is_same<F, A>::value) {
-    switch (t.block) {
+    switch (launched_block<F, A>(t)) {
     case 64: launch_depth<F, A, ORDER, SAME, 64>(a, t, stream); return;
     case 128: launch_depth<F, A, ORDER, SAME, 128>(a, t, stream); return;
     case 512: launch_depth<F, A, ORDER, SAME, 512>(a, t, stream); return;
@@ -231,7 +236,10 @@ static int launch_contract(void *loop_d, const MugiqHipSpinorField *L, const Mug
   a.stride = L[0].stride;
   a.parity_offset = L[0].parity_offset;
   const ContractTune t = contract_tune(same, std::is_same<F, double>::value && std::is_same<A, double>::value);
-  a.xcdSwizzle = (t.swz && (((2 * a.volumeCB + t.block - 1) / t.block) % 8 == 0)) ? 1 : 0;
+  // the swizzle is a permutation of the workgroups only where the grid LAUNCHED is a multiple of 8: decide from the block size
+  // launch_block takes (the mixed mode runs on 256 whatever t.block says), not from the one asked for
+  const int block = launched_block<F, A>(t);
+  a.xcdSwizzle = (t.swz && (((2 * a.volumeCB + block - 1) / block) % 8 == 0)) ? 1 : 0;
   if (same) launch_block<F, A, ORDER, true>(a, t, stream);
   else launch_block<F, A, ORDER, false>(a, t, stream);
   MUGIQ_CHECK_HIP(hipGetLastError());

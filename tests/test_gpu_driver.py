@@ -10,6 +10,7 @@ import torch
 import torch.multiprocessing as mp
 
 import mp_workers
+from fused_cases import fused_two_domains_along_t
 from test_multi_rank_cpu import free_port
 from util import orc, random_gauge_lex, random_spinor_lex, sigmas, momenta_p2_le, rel_err
 
@@ -150,54 +151,7 @@ def test_driver_ultralocal_only_and_errors(hip):
 def test_fused_operator_with_ghost_layers(hip, order):
     """Operator-level check of the fused kernel across a domain boundary (2 domains emulated on one GPU):
     path links from E_k = D^k E_0 per domain, 3 ghost layers packed by pack_face_layers."""
-    G = (4, 4, 4, 8)
-    grid = (1, 1, 1, 2)
-    l = (4, 4, 4, 4)
-    comm = (0, 0, 0, 1)
-    brd = (0, 0, 0, 2)
-    rng = np.random.default_rng(8)
-    nev = 3
-    ev_lex = [random_spinor_lex(rng, G) for _ in range(nev)]
-    U_lex = random_gauge_lex(rng, G)
-    sg = sigmas(nev)
-    ranks = [(0, 0, 0, 0), (0, 0, 0, 1)]
-    for dispstr in ("+t", "-t"):
-        dirn, sign = orc.parse_displacement(dispstr)
-        cprm = orc.LoopComputeParam([dispstr], [1], [3])
-        ref = orc.compute_loop_position_space([orc.lex_to_eo(v, G) for v in ev_lex], sg, cprm,
-                                              orc.extended_gauge_from_global(U_lex, (0, 0, 0, 0), (1, 1, 1, 1), (0, 0, 0, 0)), G)
-        f = {r: [hip.SpinorField(l, 8, order).set_logical(orc.lex_to_eo(orc.local_block(v, r, grid), l)) for v in ev_lex] for r in ranks}
-        Ue = {r: hip.GaugeField(l, brd, 8).set_logical(orc.extended_gauge_from_global(U_lex, r, grid, brd)) for r in ranks}
-        high = 0 if sign == hip.DispSignPlus else 1
-        # path links per rank (needs the depth-1 face of E_{k-1} from the neighbour at every step)
-        E = {r: [hip.SpinorField(l, 8, 2) for _ in range(4)] for r in ranks}
-        ident = np.zeros((2, 128, 4, 3), dtype=np.complex128)
-        for s in range(3):
-            ident[:, :, s, s] = 1.0
-        for r in ranks:
-            E[r][0].set_logical(ident)
-        for k in range(1, 4):
-            faces = {}
-            for r in ranks:
-                faces[r] = torch.zeros(24 * E[r][k - 1].face_cb(3), dtype=torch.complex128, device="cuda")
-                hip.packFace(faces[r], E[r][k - 1], 3, high)
-            for i, r in enumerate(ranks):
-                E[r][k - 1].ghost[3][1 - high] = faces[ranks[1 - i]]
-                hip.performCovariantDisplacementVector(E[r][k], E[r][k - 1], Ue[r], dirn, sign, comm)
-        layers = {}
-        for r in ranks:
-            layers[r] = torch.zeros(nev * 3 * 24 * f[r][0].face_cb(3), dtype=torch.complex128, device="cuda")
-            hip.packFaceLayers(layers[r], f[r], 3, high, 3)
-        Vl, Vg = 256, 512
-        for i, r in enumerate(ranks):
-            out = torch.zeros(3 * 16 * Vl, dtype=torch.complex128, device="cuda")
-            hip.displacedLoopContractionFused(out, f[r], sg, E[r][1:], [1, 2, 3], dirn, sign, comm, layers[ranks[1 - i]], 3)
-            got = out.cpu().numpy()
-            for k in range(3):
-                for ig in range(16):
-                    gl = orc.eo_to_lex(ref[Vg * (16 * (1 + k) + ig):Vg * (16 * (1 + k) + ig + 1)].reshape(2, Vg // 2), G)
-                    lo = orc.eo_to_lex(got[Vl * (16 * k + ig):Vl * (16 * k + ig + 1)].reshape(2, Vl // 2), l)
-                    assert rel_err(lo, orc.local_block(gl, r, grid)) < 1e-13, (dispstr, r, k, ig)
+    fused_two_domains_along_t(hip, order, (4, 4, 4, 8), 1e-13)
 
 
 @pytest.mark.parametrize("prec,order,lengths", [(8, 2, [1, 2, 3]), (8, 2, [2]), (8, 4, [1, 2]), (4, 4, [1, 3]), (4, 2, [1, 2, 3]), (8, 4, [1, 2, 3])])

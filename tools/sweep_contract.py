@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sweep the launch variants of loop_contract_kernel (MUGIQ_HIP_CONTRACT_TUNE = "block,depth,nt") on the bench
+"""Sweep the launch variants of loop_contract_kernel (MUGIQ_HIP_CONTRACT_TUNE = "block,depth,nt,swz") on the bench
 workload, interleaved rounds in ONE process (cdna_hip_programming.md rule 24), median + min per variant."""
 import argparse
 import itertools
