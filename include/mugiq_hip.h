@@ -412,7 +412,8 @@ int mugiq_hip_prolongate_contract_batched(void *loopData_d, int loopPrecision, c
                                           void *stream);
 
 /* ---- restriction R = P^dag (new): QUDA's Transfer::R, the adjoint of Transfer::P above.  The reference never calls it itself: its
- * computeCoarse mode (lib/eigsolve_mugiq.cpp:27-33) works on mg_env->diracCoarse, which QUDA builds from it. ------------------------ */
+ * computeCoarse mode (lib/eigsolve_mugiq.cpp:27-33) works on mg_env->diracCoarse, which QUDA builds from it (here:
+ * mugiq_hip_compute_coarse_operator, below). ---------------------------------------------------------------------------------------- */
 /* coarse_h[n](X; S, j) = sum_{x in aggregate X} sum_{s: s/spinBlockSize = S} sum_c conj(V(x; s, c, j)) g(s) fine_h[n](x; s, c) for all
  * n < nVec; g = 1, or for gamma5 != 0 the diagonal of g5 = Gamma_15 (mugiq_hip_get_gamma_tables).  Layouts, aggregate map and the
  * checks on `transfer` are those of mugiq_hip_prolongate_batched.  fine_h: one precision (4 | 8), FLOAT2 | FLOAT4, any stride; V and
@@ -702,6 +703,73 @@ int mugiq_hip_wilson_clover_solve(const MugiqHipSpinorField *x_h, const MugiqHip
                                   const MugiqHipCloverField *clover, double kappa, const MugiqHipSpinorField *eVecs_h, const double *sigma_h,
                                   int nEv, double tol, int maxIter, int *iters_out, double *relres_out, const MugiqHipComm *comm,
                                   void *stream);
+
+/* ---- the explicit Galerkin coarse operator (new; csrc/coarse_op.hip): what QUDA's DiracCoarse is to the reference's computeCoarse branch
+ * (lib/eigsolve_mugiq.cpp:27-33) -- nine dense N x N matrices per coarse site, N = 2 n_vec, built once per configuration, so that an
+ * application of M_c = R M P reads those matrices and never walks the fine lattice.
+ *
+ * Definitions.  M is the fine operator of mugiq_hip_wilson_clover_apply,
+ *   M = A(x) - kappa sum_mu [ (1 - g_mu) U_mu(x) delta_{x+mu} + (1 + g_mu) U_mu^dag(x-mu) delta_{x-mu} ],   A = 1 without a clover field,
+ * links applied as stored (U^dag: the conjugate transpose), and V the null vectors of a FINEST-level MugiqHipTransfer (spinBlockSize 2).
+ * Row index r = S*n_vec + j, the coarse field's (s*nColor + c).  With V^dag(x) = sum_{s: s/2 = S} sum_c conj V(x; s, c, j) ... and
+ * V(x') = V(x'; s', c', j'), s'/2 = S', for the coarse site X (an aggregate):
+ *   Xd(X)    = sum_{x in X} V^dag(x) A(x) V(x)
+ *              - kappa sum_mu sum_{x in X, x+mu in X} V^dag(x) (1 - g_mu) U_mu(x) V(x+mu)
+ *              - kappa sum_mu sum_{x in X, x-mu in X} V^dag(x) (1 + g_mu) U_mu^dag(x-mu) V(x-mu)
+ *   Y+_mu(X) = - kappa sum_{x in X, x+mu not in X} V^dag(x) (1 - g_mu) U_mu(x) V(x+mu)
+ *   Y-_mu(X) = - kappa sum_{x in X, x-mu not in X} V^dag(x) (1 + g_mu) U_mu^dag(x-mu) V(x-mu)
+ *   (M_c in)(X) = Xd(X) in(X) + sum_mu [ Y+_mu(X) in(X+mu) + Y-_mu(X) in(X-mu) ]
+ * Membership is by aggregate, after the periodic wrap; coarse extents are even (>= 2), so a hop that leaves the block lands in another
+ * aggregate.  With coarse extent 2, X+mu = X-mu: Y+ and Y- stay separate matrices, defined by the direction of the hop.  kappa is
+ * folded in: a new kappa means a new build.
+ *   M_c^dag: the explicit adjoint of the stored matrices,
+ *     (M_c^dag in)(X) = Xd(X)^dag in(X) + sum_mu [ Y-_mu(X+mu)^dag in(X+mu) + Y+_mu(X-mu)^dag in(X-mu) ]  = R M^dag P for ANY V (no
+ *     block-orthonormality assumed);
+ *   H_c = R g5 M P = G5 M_c, G5 = diag(g5(S)): +1 on chirality 0, -1 on chirality 1;
+ *   MdagM = M_c^dag M_c and MMdag = M_c M_c^dag: products of the coarse operators, as in mugiq_hip_compute_evals_coarse.
+ *
+ * Storage: matrix-contiguous, no pad.  The complex element (m, r, c) of site (parity, x_cb) is at
+ *   ((parity*volumeCB + x_cb)*9 + m)*N*N + r*N + c,       m = 0: Xd,  m = 1 + 2 mu: Y+_mu,  m = 2 + 2 mu: Y-_mu
+ * (32^4 with 4^4 aggregates and n_vec 24 in fp64: 1.36 GB).
+ *
+ * Limits: a SINGLE DOMAIN (a comm with size > 1 or any partitioned axis: MUGIQ_HIP_ERROR_UNSUPPORTED, before any device work) and ONE
+ * coarse level (the operator of a coarse -> coarse transfer is not built).  Deeper hierarchies and partitioned grids stay on the route of
+ * mugiq_hip_compute_evals_coarse, which applies R M P through the fine lattice. */
+typedef struct MugiqHipCoarseOperator_s {
+  void *data;
+  int precision; /* 4 | 8: the transfer's (and the coarse fields') */
+  int nVec;      /* n_vec of the transfer; N = 2*nVec */
+  int X[4];      /* coarse lattice dims, all even */
+  int volumeCB;
+  double kappa;  /* of the last build (informational) */
+  int hasClover; /* the last build had a clover field */
+} MugiqHipCoarseOperator;
+
+/* bytes of the nine matrices of every site: volume * 9 * N^2 complex of `precision` */
+size_t mugiq_hip_coarse_operator_bytes(const int X[4], int nVec, int precision);
+/* allocate (zeroed) and describe; release with mugiq_hip_free_coarse_operator */
+int mugiq_hip_alloc_coarse_operator(MugiqHipCoarseOperator *op, const int X[4], int nVec, int precision);
+int mugiq_hip_free_coarse_operator(MugiqHipCoarseOperator *op);
+/* Fill `op` from the definitions above.  transfer: a finest-level one, whose precision and n_vec are the operator's and whose coarse
+ * lattice is op->X; gauge (either precision; R[d] = 0 wraps, links addressed as by the stencil) and clover (NULL | the gauge field's
+ * precision) as for mugiq_hip_wilson_clover_apply.  fp64 arithmetic whatever the storages, one rounding on the store, no atomics, a
+ * summation order fixed by the transfer alone: two builds give identical bits.  One workgroup per aggregate and matrix, V(x) and
+ * K(x) V(x') staged in LDS; a once-per-configuration cost.  Sets op->kappa and op->hasClover. */
+int mugiq_hip_compute_coarse_operator(MugiqHipCoarseOperator *op, const MugiqHipTransfer *transfer, const MugiqHipGaugeField *gauge,
+                                      const MugiqHipCloverField *clover, double kappa, const MugiqHipComm *comm, void *stream);
+/* dst_i = scale * A_c src_i, i < nVec, A_c the form opType (MUGIQ_HIP_EIG_OPERATOR_*) of the coarse operator.  Coarse fields of the
+ * operator's precision and lattice, any stride (one for all src, one for all dst); pads are neither read nor written; no dst may overlap
+ * any src.  Blocks of 8 vectors: the matrices are read once per block.  Sums in fp64, one rounding on the store; a vector applied alone
+ * equals the same vector applied in any batch, bit for bit.  The intermediate of MdagM / MMdag (8 vectors) lives in the per-stream
+ * workspace. */
+int mugiq_hip_coarse_apply(const MugiqHipCoarseField *dst_h, const MugiqHipCoarseField *src_h, int nVec, const MugiqHipCoarseOperator *op,
+                           int opType, double scale, const MugiqHipComm *comm, void *stream);
+/* lambda, r and sigma of mugiq_hip_compute_evals_coarse (lib/eigsolve_mugiq.cpp:289-315) with A_c applied by mugiq_hip_coarse_apply:
+ * massNormalization scales by 0.25 / op->kappa^2.  The same fixed-order fp64 scalar kernels; work memory: 8 coarse vectors and the
+ * scalars in the operator workspace of the stream.  Blocks the host (two reads per block of 8). */
+int mugiq_hip_compute_evals_coarse_operator(const MugiqHipCoarseField *coarseEvecs_h, int nEv, const MugiqHipCoarseOperator *op, int opType,
+                                            int massNormalization, double *lambda_h, double *residual_h, double *sigma_h,
+                                            const MugiqHipComm *comm, void *stream);
 
 /* What Displace asks of QUDA's ColorSpinorField for its auxiliary vector (lib/displace.cpp:26-30: ColorSpinorField::Create
  * with QUDA_ZERO_FIELD_CREATE and setPrecision(coarsePrec_); :42,:50-51: operator=; :59: blas::zero), for hosts that do not

@@ -158,6 +158,43 @@ inline void computeEvalsCoarse(const std::vector<MugiqHipCoarseField> &coarseEve
                                        comm, stream));
   if (opType == MUGIQ_HIP_EIG_OPERATOR_M || opType == MUGIQ_HIP_EIG_OPERATOR_MDAG) sigma.clear();
 }
+// ---- the explicit Galerkin coarse operator (MugiqHipCoarseOperator; csrc/coarse_op.hip; new): one level, one domain ------------------
+// Owns the nine matrices per coarse site of a finest-level transfer
+class CoarseOperator {
+public:
+  CoarseOperator(const int Xc[4], int nVec, int precision) { check(mugiq_hip_alloc_coarse_operator(&op_, Xc, nVec, precision)); }
+  ~CoarseOperator() { mugiq_hip_free_coarse_operator(&op_); }
+  CoarseOperator(const CoarseOperator &) = delete;
+  CoarseOperator &operator=(const CoarseOperator &) = delete;
+  MugiqHipCoarseOperator *desc() { return &op_; }
+  const MugiqHipCoarseOperator *desc() const { return &op_; }
+
+private:
+  MugiqHipCoarseOperator op_{};
+};
+// Xd and Y+-_mu of every coarse site from V, the links and the clover term (NULL: Wilson), kappa folded in (mugiq_hip_compute_coarse_operator)
+inline void computeCoarseOperator(CoarseOperator &op, const MugiqHipTransfer &transfer, const GaugeField &gauge, const MugiqHipCloverField *clover,
+                                  double kappa, const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  check(mugiq_hip_compute_coarse_operator(op.desc(), &transfer, &gauge, clover, kappa, comm, stream));
+}
+// dst_i = scale * A_c src_i on the coarse grid (mugiq_hip_coarse_apply)
+inline void coarseApply(const std::vector<MugiqHipCoarseField> &dst, const std::vector<MugiqHipCoarseField> &src, const CoarseOperator &op,
+                        int opType = MUGIQ_HIP_EIG_OPERATOR_M, double scale = 1.0, const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (src.empty() || dst.size() != src.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "coarseApply: size mismatch");
+  check(mugiq_hip_coarse_apply(dst.data(), src.data(), (int)src.size(), op.desc(), opType, scale, comm, stream));
+}
+// computeEvalsCoarse on the explicit operator (mugiq_hip_compute_evals_coarse_operator): no pass over the fine lattice
+inline void computeEvalsCoarse(const std::vector<MugiqHipCoarseField> &coarseEvecs, const CoarseOperator &coarseOp, int opType, bool massNormalization,
+                               std::vector<std::complex<double>> &lambda, std::vector<double> &residual, std::vector<double> &sigma,
+                               const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (coarseEvecs.empty()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "computeEvalsCoarse: no eigenvectors");
+  lambda.assign(coarseEvecs.size(), std::complex<double>(0.0, 0.0));
+  residual.assign(coarseEvecs.size(), 0.0);
+  sigma.assign(coarseEvecs.size(), 0.0);
+  check(mugiq_hip_compute_evals_coarse_operator(coarseEvecs.data(), (int)coarseEvecs.size(), coarseOp.desc(), opType, massNormalization ? 1 : 0,
+                                                reinterpret_cast<double *>(lambda.data()), residual.data(), sigma.data(), comm, stream));
+  if (opType == MUGIQ_HIP_EIG_OPERATOR_M || opType == MUGIQ_HIP_EIG_OPERATOR_MDAG) sigma.clear();
+}
 // Eigsolve_Mugiq::projectVector, lib/eigsolve_mugiq.cpp:340-348
 inline void projectVector(ColorSpinorField &out, ColorSpinorField &in, const std::vector<ColorSpinorField> &eVecs, const MugiqHipComm *comm = nullptr,
                           void *stream = nullptr) {

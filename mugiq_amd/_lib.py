@@ -59,6 +59,12 @@ class TransferDesc(ctypes.Structure):
                 ("spinBlockSize", ctypes.c_int), ("X", ctypes.c_int * 4), ("stride", ctypes.c_int), ("parity_offset", ctypes.c_int64)]
 
 
+class CoarseOperatorDesc(ctypes.Structure):
+    """MugiqHipCoarseOperator (include/mugiq_hip.h)."""
+    _fields_ = [("data", ctypes.c_void_p), ("precision", ctypes.c_int), ("nVec", ctypes.c_int), ("X", ctypes.c_int * 4), ("volumeCB", ctypes.c_int),
+                ("kappa", ctypes.c_double), ("hasClover", ctypes.c_int)]
+
+
 class ProjectPlan(ctypes.Structure):
     """MugiqHipProjectPlan (include/mugiq_hip.h)."""
     _fields_ = [(n, ctypes.c_int) for n in ("form", "nks", "mb", "nPx", "tChunk", "nChunks", "lastChunk", "tiles", "tilesPerWg",
@@ -203,6 +209,16 @@ SIGNATURES = {
     "mugiq_hip_compute_evals_coarse": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(TransferDesc), ctypes.c_int, _GP, _CP,
                                                       ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                                       ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _VP, _VP]),
+    "mugiq_hip_coarse_operator_bytes": (ctypes.c_size_t, [_I4, ctypes.c_int, ctypes.c_int]),
+    "mugiq_hip_alloc_coarse_operator": (ctypes.c_int, [ctypes.POINTER(CoarseOperatorDesc), _I4, ctypes.c_int, ctypes.c_int]),
+    "mugiq_hip_free_coarse_operator": (ctypes.c_int, [ctypes.POINTER(CoarseOperatorDesc)]),
+    "mugiq_hip_compute_coarse_operator": (ctypes.c_int, [ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(TransferDesc), _GP, _CP, ctypes.c_double,
+                                                         _VP, _VP]),
+    "mugiq_hip_coarse_apply": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(CoarseOperatorDesc),
+                                              ctypes.c_int, ctypes.c_double, _VP, _VP]),
+    "mugiq_hip_compute_evals_coarse_operator": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int,
+                                                               ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                               ctypes.POINTER(ctypes.c_double), _VP, _VP]),
     "mugiq_hip_wilson_clover_solve": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, _SP, ctypes.POINTER(ctypes.c_double),
                                                      ctypes.c_int, ctypes.c_double, ctypes.c_int, _I4, ctypes.POINTER(ctypes.c_double), _VP, _VP]),
     "mugiq_hip_prolongate_batched": (ctypes.c_int, [_SP, ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),

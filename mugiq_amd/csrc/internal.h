@@ -114,6 +114,14 @@ int validate_coarse_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseFiel
 int deflate_low_modes_coarse(const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int nVec, const MugiqHipCoarseField *ev,
                              const double *sigma, int nEv, const MugiqHipTransfer *transfers, int nLevels, int gamma5, double *overlaps_h,
                              const MugiqHipComm *comm, hipStream_t stream, const char *who);
+// csrc/coarse_op.hip: the explicit coarse operator.  check_single_domain: MUGIQ_HIP_ERROR_UNSUPPORTED for a comm with more than one rank
+// or a partitioned axis; validate_coarse_vectors: n fields the operator can act on, of one stride and parity offset; coarse_apply:
+// mugiq_hip_coarse_apply behind its validation (the eigenpair check of csrc/restrict.hip calls it block by block)
+int check_single_domain(const MugiqHipComm *comm, const char *who);
+int validate_coarse_operator(const MugiqHipCoarseOperator *op, const char *who);
+int validate_coarse_vectors(const MugiqHipCoarseField *f, int n, const MugiqHipCoarseOperator *op, const char *who, const char *name);
+int coarse_apply(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src, int nVec, const MugiqHipCoarseOperator *op, int opType, double scale,
+                 hipStream_t stream);
 // csrc/wilson.hip: the gauge field of an operator call against the local dims X and the partitioned axes; comm -> part[4]
 int check_gauge(const MugiqHipGaugeField *U, const int X[4], const int part[4], const char *who);
 int check_comm(const MugiqHipComm *comm, int part[4], bool needSums, const char *who);

@@ -794,6 +794,75 @@ int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipT
   return MUGIQ_HIP_SUCCESS;
 }
 
+// The same check with A_c applied by the explicit coarse operator (csrc/coarse_op.hip) instead of R M P through the fine lattice: one
+// level, one domain.  Work memory (operator workspace of the stream; coarse_apply keeps its intermediate in stream_workspace): 8 coarse
+// vectors laid out like the eigenvectors, lambda and the sums
+int compute_evals_coarse_operator(const MugiqHipCoarseField *ev, int nEv, const MugiqHipCoarseOperator *op, int opType, int massNormalization,
+                                  double *lambda_h, double *residual_h, double *sigma_h, const MugiqHipComm *comm, hipStream_t stream) {
+  const char *who = "computeEvalsCoarse(coarseOp)";
+  // ---- validation, before any device work
+  MUGIQ_REQUIRE(ev != nullptr && lambda_h != nullptr && residual_h != nullptr, "%s: NULL argument", who);
+  MUGIQ_REQUIRE(nEv >= 1, "%s: nEv = %d must be >= 1", who, nEv);
+  int st;
+  if ((st = check_single_domain(comm, who))) return st;
+  if ((st = validate_coarse_operator(op, who))) return st;
+  MUGIQ_REQUIRE(opType >= MUGIQ_HIP_EIG_OPERATOR_M && opType <= MUGIQ_HIP_EIG_OPERATOR_H, "%s: opType %d is none of M, Mdag, MdagM, MMdag, H", who, opType);
+  const bool normal = opType == MUGIQ_HIP_EIG_OPERATOR_MDAGM || opType == MUGIQ_HIP_EIG_OPERATOR_MMDAG;
+  MUGIQ_REQUIRE(!(normal || opType == MUGIQ_HIP_EIG_OPERATOR_H) || sigma_h != nullptr, "%s: sigma_h is NULL", who);
+  MUGIQ_REQUIRE(!massNormalization || op->kappa != 0.0, "%s: mass normalisation with kappa = 0", who);
+  if ((st = validate_coarse_vectors(ev, nEv, op, who, "coarse eigen"))) return st;
+  if ((st = debug_poison_lds_if_asked(stream))) return st;
+
+  const size_t P = (size_t)op->precision, one = align256((size_t)2 * ev[0].parity_offset * 2 * P);
+  void *ws = nullptr;
+  if ((st = stream_operator_workspace(&ws, kEvBlock * one + sizeof(double) * 5 * kEvBlock, stream))) return st;
+  MugiqHipCoarseField Y[kEvBlock];
+  for (int i = 0; i < kEvBlock; i++) {
+    Y[i] = ev[0];
+    Y[i].data = static_cast<unsigned char *>(ws) + i * one;
+  }
+  double *lambda_d = reinterpret_cast<double *>(static_cast<unsigned char *>(ws) + kEvBlock * one), *sums_d = lambda_d + 2 * kEvBlock;
+  const CoarseGeom cg{2 * op->nVec, op->volumeCB, ev[0].stride, ev[0].parity_offset, 2 * 2 * op->nVec * op->volumeCB};
+  const double scale = massNormalization ? 0.25 / (op->kappa * op->kappa) : 1.0;  // lib/eigsolve_mugiq.cpp:302
+
+  auto scalars = [&](int mode, const MugiqHipCoarseField *w, int n, double out[3 * kEvBlock]) -> int {
+    std::vector<const void *> host(2 * (size_t)n);
+    for (int i = 0; i < n; i++) host[i] = w[i].data, host[n + i] = Y[i].data;
+    void *tab = nullptr;
+    if (int rc = upload_table(&tab, host.data(), host.size() * sizeof(void *), stream)) return rc;
+    const void *const *W_d = static_cast<const void *const *>(tab);
+    if (P == 8 && mode == 0) hipLaunchKernelGGL((coarse_scalar_kernel<double, 0>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
+    else if (P == 8) hipLaunchKernelGGL((coarse_scalar_kernel<double, 1>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
+    else if (mode == 0) hipLaunchKernelGGL((coarse_scalar_kernel<float, 0>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
+    else hipLaunchKernelGGL((coarse_scalar_kernel<float, 1>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
+    MUGIQ_CHECK_HIP(hipGetLastError());
+    MUGIQ_CHECK_HIP(hipMemcpyAsync(out, sums_d, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, stream));
+    MUGIQ_CHECK_HIP(hipStreamSynchronize(stream));
+    return MUGIQ_HIP_SUCCESS;
+  };
+
+  for (int v0 = 0; v0 < nEv; v0 += kEvBlock) {
+    const int n = std::min(kEvBlock, nEv - v0);
+    const MugiqHipCoarseField *w = ev + v0;
+    if ((st = coarse_apply(Y, w, n, op, opType, scale, stream))) return st;
+    double sums[3 * kEvBlock];
+    if ((st = scalars(0, w, n, sums))) return st;
+    for (int i = 0; i < n; i++) {
+      const double nrm = std::sqrt(sums[3 * i + 2]);  // lambda = w^dag A_c w / ||w||   (:303, not ||w||^2)
+      lambda_h[2 * (v0 + i)] = sums[3 * i] / nrm;
+      lambda_h[2 * (v0 + i) + 1] = sums[3 * i + 1] / nrm;
+    }
+    MUGIQ_CHECK_HIP(hipMemcpyAsync(lambda_d, lambda_h + 2 * v0, sizeof(double) * 2 * n, hipMemcpyHostToDevice, stream));
+    if ((st = scalars(1, w, n, sums))) return st;  // (synchronises: lambda_h may be read again)
+    for (int i = 0; i < n; i++) {
+      residual_h[v0 + i] = std::sqrt(sums[3 * i]);  // r = ||lambda w - A_c w||   (:305-306)
+      if (normal) sigma_h[v0 + i] = std::sqrt(lambda_h[2 * (v0 + i)]);  // :311
+      else if (opType == MUGIQ_HIP_EIG_OPERATOR_H) sigma_h[v0 + i] = lambda_h[2 * (v0 + i)];
+    }
+  }
+  return MUGIQ_HIP_SUCCESS;
+}
+
 }  // namespace mugiq
 
 using namespace mugiq;
@@ -828,6 +897,13 @@ int mugiq_hip_compute_evals_coarse(const MugiqHipCoarseField *coarseEvecs_h, int
                                    void *stream) {
   return compute_evals_coarse(coarseEvecs_h, nEv, transfers_h, nCoarseLevels, gauge, clover, kappa, opType, massNormalization, lambda_h, residual_h,
                               sigma_h, comm, static_cast<hipStream_t>(stream));
+}
+
+int mugiq_hip_compute_evals_coarse_operator(const MugiqHipCoarseField *coarseEvecs_h, int nEv, const MugiqHipCoarseOperator *op, int opType,
+                                            int massNormalization, double *lambda_h, double *residual_h, double *sigma_h,
+                                            const MugiqHipComm *comm, void *stream) {
+  return compute_evals_coarse_operator(coarseEvecs_h, nEv, op, opType, massNormalization, lambda_h, residual_h, sigma_h, comm,
+                                       static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

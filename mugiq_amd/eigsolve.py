@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .fields import SpinorField, desc_array, coarse_desc_array, transfer_desc_array
+from .fields import SpinorField, CoarseOperator, desc_array, coarse_desc_array, transfer_desc_array
 
 # MuGiqEigOperator (include/enum_mugiq.h:22-25 of the reference, values identical) and the extension H = g5 M
 MUGIQ_EIG_OPERATOR_M, MUGIQ_EIG_OPERATOR_Mdag, MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H = range(5)
@@ -85,10 +85,52 @@ def computeEvals(eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, massNorma
     return np.array(lam).view(np.complex128).copy(), np.array(res), (np.array(sig) if has_sigma else None)
 
 
-def computeEvalsCoarse(coarseEvecs, transfer, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, massNormalization=False, comm=None, clover=None):
+def computeCoarseOperator(transfer, gauge, kappa, clover=None, comm=None, op=None):
+    """The explicit Galerkin coarse operator of a finest-level Transfer (mugiq_hip_compute_coarse_operator): Xd and Y+-_mu of every coarse
+    site, kappa folded in.  Built into `op` (a CoarseOperator of the transfer's coarse lattice, n_vec and precision) or a new one; a
+    single domain only (a comm with more than one rank or a partitioned axis: status 2).  Returns the operator."""
+    if op is None:
+        op = CoarseOperator(transfer.Xc, transfer.n_vec, transfer.precision, device=transfer.device)
+    if not isinstance(op, CoarseOperator):
+        raise _lib.MugiqHipError("computeCoarseOperator: op must be a CoarseOperator")
+    keep = []
+    d, t, g = op.desc(), transfer.desc(), gauge.desc()
+    _lib.check(_lib.load().mugiq_hip_compute_coarse_operator(ctypes.byref(d), ctypes.byref(t), ctypes.byref(g), _clover_ptr(clover, keep), float(kappa),
+                                                             _comm_ptr(comm, keep), _stream()))
+    op.kappa, op.hasClover = float(d.kappa), bool(d.hasClover)
+    return op
+
+
+def coarseApply(dst, src, op, opType=MUGIQ_EIG_OPERATOR_M, scale=1.0, comm=None):
+    """dst_i = scale * A_c src_i for lists of CoarseFields, A_c the form opType of the explicit coarse operator (mugiq_hip_coarse_apply)."""
+    dst, src = list(dst), list(src)
+    if len(dst) != len(src) or not src:
+        raise _lib.MugiqHipError("coarseApply: %d dst and %d src vectors (need the same number, at least one)" % (len(dst), len(src)))
+    keep = []
+    d = op.desc()
+    _lib.check(_lib.load().mugiq_hip_coarse_apply(coarse_desc_array(dst), coarse_desc_array(src), len(src), ctypes.byref(d), int(opType), float(scale),
+                                                  _comm_ptr(comm, keep), _stream()))
+
+
+def computeEvalsCoarse(coarseEvecs, transfer=None, gauge=None, kappa=None, opType=MUGIQ_EIG_OPERATOR_MdagM, massNormalization=False, comm=None,
+                       clover=None, coarseOp=None):
     """computeEvals for eigenvectors on the coarsest level of an MG hierarchy (mugiq_hip_compute_evals_coarse): the operator is the Galerkin
-    operator R M P (MdagM / MMdag: products of the coarse operators; H: R g5 M P).  transfer: a Transfer, or the list [finest, ...]."""
+    operator R M P (MdagM / MMdag: products of the coarse operators; H: R g5 M P).  transfer: a Transfer, or the list [finest, ...].
+    coarseOp (a CoarseOperator of computeCoarseOperator): the same check on the explicit operator, without a pass over the fine lattice
+    (mugiq_hip_compute_evals_coarse_operator; one level, one domain); transfer, gauge, kappa and clover are then not looked at -- they are
+    in the operator."""
     ev = list(coarseEvecs)
+    if coarseOp is not None:
+        n = len(ev)
+        lam = (ctypes.c_double * (2 * max(n, 1)))()
+        res = (ctypes.c_double * max(n, 1))()
+        sig = (ctypes.c_double * max(n, 1))()
+        keep = []
+        d = coarseOp.desc()
+        _lib.check(_lib.load().mugiq_hip_compute_evals_coarse_operator(coarse_desc_array(ev) if ev else None, n, ctypes.byref(d), int(opType),
+                                                                       int(bool(massNormalization)), lam, res, sig, _comm_ptr(comm, keep), _stream()))
+        has_sigma = int(opType) in (MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H)
+        return np.array(lam).view(np.complex128)[:n].copy(), np.array(res)[:n], (np.array(sig)[:n] if has_sigma else None)
     tr = list(transfer) if isinstance(transfer, (list, tuple)) else [transfer]
     n = len(ev)
     lam = (ctypes.c_double * (2 * max(n, 1)))()
@@ -162,12 +204,15 @@ class Eigsolve_Mugiq:
     field they belong to, kappa and the form of the operator they are eigenvectors of.  evals_quda: what the eigensolver reported
     (printed beside the recomputed values; zero if not given).  clover: the CloverField of a Wilson-clover operator (None: Wilson).
     transfer (a Transfer or the list [finest, ...]): the computeCoarse branch -- eVecs are CoarseFields on the coarsest level and the
-    operator is the Galerkin operator (computeEvalsCoarse); projectVector and solve stay fine-level."""
+    operator is the Galerkin operator (computeEvalsCoarse); projectVector and solve stay fine-level.  coarseOp (with transfer): the
+    CoarseOperator built for this transfer, gauge, clover and kappa -- computeEvals then runs on it, on the coarse grid alone."""
 
     def __init__(self, eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, comm=None, massNormalization=False, evals_quda=None, clover=None,
-                 transfer=None):
+                 transfer=None, coarseOp=None):
         self.eVecs, self.gauge, self.kappa, self.opType, self.comm = list(eVecs), gauge, float(kappa), int(opType), comm
-        self.clover, self.transfer = clover, transfer
+        self.clover, self.transfer, self.coarseOp = clover, transfer, coarseOp
+        if coarseOp is not None and transfer is None:
+            raise _lib.MugiqHipError("Eigsolve_Mugiq: coarseOp needs the transfer it was built from")
         self.massNormalization = bool(massNormalization)
         n = len(self.eVecs)
         self.eVals_quda = np.zeros(n, np.complex128) if evals_quda is None else np.asarray(evals_quda, np.complex128)
@@ -176,7 +221,7 @@ class Eigsolve_Mugiq:
     def computeEvals(self):
         if self.transfer is not None:
             self.eVals, self.evals_res, self.eVals_sigma = computeEvalsCoarse(self.eVecs, self.transfer, self.gauge, self.kappa, self.opType,
-                                                                               self.massNormalization, self.comm, self.clover)
+                                                                               self.massNormalization, self.comm, self.clover, self.coarseOp)
             return self.eVals, self.evals_res, self.eVals_sigma
         self.eVals, self.evals_res, self.eVals_sigma = computeEvals(self.eVecs, self.gauge, self.kappa, self.opType, self.massNormalization,
                                                                      self.comm, self.clover)

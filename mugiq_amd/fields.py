@@ -331,6 +331,36 @@ class CoarseField:
         return self.data.cpu().numpy()[p * self.parity_offset + (s * self.n_vec + c) * self.stride + x]
 
 
+class CoarseOperator:
+    """The explicit Galerkin coarse operator of a finest-level transfer (MugiqHipCoarseOperator in mugiq_hip.h): nine dense N x N
+    matrices per coarse site, N = 2 n_vec -- Xd, then Y+_mu and Y-_mu for mu = x, y, z, t -- matrix-contiguous and without pad.
+    eigsolve.computeCoarseOperator fills it; kappa and hasClover are those of the last build."""
+
+    def __init__(self, Xc, n_vec, precision=8, device="cuda"):
+        self.X = tuple(int(x) for x in Xc)
+        assert all(x > 0 and x % 2 == 0 for x in self.X), "coarse dims must be even"
+        self.n_vec = int(n_vec)
+        self.N = 2 * self.n_vec
+        self.precision = int(precision)
+        self.volumeCB = int(np.prod(self.X)) // 2
+        self.kappa, self.hasClover = 0.0, False
+        self.device = torch.device(device)
+        self.data = torch.zeros(2 * self.volumeCB * 9 * self.N * self.N, dtype=_cdtype(precision), device=self.device)
+
+    def desc(self):
+        d = _lib.CoarseOperatorDesc()
+        d.data = self.data.data_ptr()
+        d.precision, d.nVec, d.volumeCB = self.precision, self.n_vec, self.volumeCB
+        d.kappa, d.hasClover = float(self.kappa), int(self.hasClover)
+        for i in range(4):
+            d.X[i] = self.X[i]
+        return d
+
+    def get_logical(self):
+        """[2, volCB_c, 9, N, N] (parity, x_cb, matrix, row, column)"""
+        return self.data.cpu().numpy().reshape(2, self.volumeCB, 9, self.N, self.N)
+
+
 class Transfer:
     """One level of QUDA's Transfer as the hot path sees it: the block-orthonormal null vectors V on the finer grid of
     the level (packed vector index), the aggregate size and the spin blocking.  Finest level: the finer side is the
