@@ -771,6 +771,67 @@ int mugiq_hip_compute_evals_coarse_operator(const MugiqHipCoarseField *coarseEve
                                             int massNormalization, double *lambda_h, double *residual_h, double *sigma_h,
                                             const MugiqHipComm *comm, void *stream);
 
+/* ---- a two-grid preconditioned flexible GCR on the fine operator (new; csrc/mg_solve.hip): the solve of the deflated recipe for every
+ * stochastic source, for hosts that hold an MG hierarchy (V of a finest-level transfer and its explicit coarse operator).
+ *
+ * Definitions.  M is the operator of mugiq_hip_wilson_clover_apply (clover NULL: unimproved); M_c, P = mugiq_hip_prolongate_batched and
+ * R = P^dag = mugiq_hip_restrict_batched those of the coarse-operator section above.  All inner products <a, b> = sum conj(a) b are fp64
+ * fixed-order sums.
+ *   MR step on (z, s):  t = M s,  d = <t, t>,  alpha = omega <t, s> / d if d > 0, else 0;  z += alpha s,  s -= alpha t.
+ *   GCRfix(A, b, n):  x = 0, r = b; for k = 0 .. n-1:  p = r, q = A p;  c_j = <q_j, q> for all j < k, taken from the un-updated q
+ *     (classical Gram-Schmidt, one pass);  p -= sum c_j p_j,  q -= sum c_j q_j;  nu = ||q||: if nu = 0 the step contributes nothing and
+ *     stores a zero direction, otherwise p /= nu, q /= nu;  alpha = <q, r>,  x += alpha p,  r -= alpha q.  Returns x.
+ *   K(r), the preconditioner:  z = 0, s = r;  nuPre MR steps;  if coarseIters > 0: e = GCRfix(M_c, R s, coarseIters), z += P e,
+ *     s = r - M z (one application);  nuPost MR steps;  returns z.  K is homogeneous: K(c r) = c K(r) for real c > 0.
+ *   Outer solve of M x = b:  x = 0, r = b; the recurrence of GCRfix with p = K(r), q = M p, the directions cleared after every nKrylov
+ *     steps; stops at the first iteration with recursive ||r|| <= tol ||b||.  relres is the TRUE ||b - M x|| / ||b|| from one more
+ *     application, history[i] the recursive relative residual after iteration i + 1;  b = 0 gives x = 0 in 0 iterations.
+ * (alpha = <q, r> is formed as <q, r> / nu from the orthogonalised q before its normalisation, in the pass that orthogonalises it.)
+ * Right-hand sides advance in blocks of at most 8 through the batched operators, each with its own scalars; a converged one is no longer
+ * touched, and one solved alone equals the same one in any batch, bit for bit.
+ *
+ * Inside K nothing is read back: K is a fixed sequence of launches whose scalars (Gram-Schmidt coefficients, nu, alpha) stay in device
+ * memory.  The outer loop blocks the host once per iteration (the residual norms of the block) and twice more per block (||b|| and the
+ * true residual); *hostReads_out counts these reads.  No atomics: two runs give identical bits, iteration counts and histories.
+ *
+ * The defaults are first guesses that converge on the test fields; they are NOT tuned. */
+typedef struct MugiqHipMgSolveParam_s {
+  double tol;      /* > 0: recursive ||r|| <= tol ||b|| */
+  int maxIter;     /* >= 0 outer iterations per right-hand side */
+  int nKrylov;     /* 1 .. 16 stored directions of the outer GCR before a restart */
+  int nuPre;       /* 0 .. 16 MR steps before the coarse-grid correction */
+  int nuPost;      /* 0 .. 16 MR steps after it */
+  double omega;    /* MR relaxation */
+  int coarseIters; /* 0 .. 16 GCR steps on M_c; 0: no coarse-grid correction */
+} MugiqHipMgSolveParam;
+/* tol 1e-10, maxIter 1000, nKrylov 16, nuPre 0, nuPost 4, omega 1.0, coarseIters 8 */
+int mugiq_hip_mg_solve_param_default(MugiqHipMgSolveParam *param);
+/* z_i = K(r_i), i < nVec.  z_h, r_h: fp64 fields of one layout (FLOAT2 | FLOAT4, any stride; pads are neither read nor written), no z
+ * overlapping any r; they need no ghost zones.  transfer: a finest-level one of precision 8 on the fields' lattice; coarseOp: the operator
+ * built from it for this gauge field, clover field and kappa (precision 8).  tol and maxIter of `param` are checked but not used.
+ * Limits, each refused before any device work: a single domain and one level (MUGIQ_HIP_ERROR_UNSUPPORTED, as for the coarse operator);
+ * precision 4 anywhere in transfer, coarse operator or fields (MUGIQ_HIP_ERROR_UNSUPPORTED); parameters out of range, geometry mismatches
+ * between fields, transfer and operator, a coarse operator built for another kappa or without / with the clover term of the call
+ * (op->kappa, op->hasClover), a z overlapping an r or another z (MUGIQ_HIP_ERROR_INVALID_ARGUMENT).
+ * Work memory, all from the per-stream operator workspace: 3 min(nVec, 8) fine vectors, (2 coarseIters + 2) min(nVec, 8) coarse vectors
+ * and 0.6 MB of scalars; an allocation that fails is MUGIQ_HIP_ERROR_HIP, not an abort.  The workspace grows to 1.5 x a request that
+ * does not fit and is kept for the stream (mugiq_hip_release_stream frees it). */
+int mugiq_hip_mg_precondition(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
+                              const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer,
+                              const MugiqHipCoarseOperator *coarseOp, const MugiqHipMgSolveParam *param, const MugiqHipComm *comm, void *stream);
+/* x_i = M^-1 b_i, i < nVec, by the outer solve above.  Fields and limits as for mugiq_hip_mg_precondition (x for z, b for r).
+ * iters_out[nVec], relres_out[nVec]; history_out (may be NULL): history_out[i*historyStride + k] for k < iters_out[i], entries behind
+ * that are not written, historyStride >= maxIter; hostReads_out (may be NULL): the blocking reads of this call, max(iters of the block)
+ * + 2 per block of 8.  MUGIQ_HIP_ERROR_NOT_CONVERGED if a right-hand side reaches maxIter first: x and all outputs are filled all the same.
+ * Work memory (per-stream operator workspace): (2 nKrylov + 4) min(nVec, 8) fine vectors -- the directions p_j and q_j, r, s, t and one
+ * for P e -- (2 coarseIters + 2) min(nVec, 8) coarse vectors and 0.6 MB of scalars.  32^4, nKrylov 16, 8 right-hand sides: 58 GB are
+ * used, and because the workspace grows to 1.5 x a request that does not fit, a first call on a stream allocates 87 GB (nKrylov 8: 32 GB
+ * used, 48 GB allocated).  Size nKrylov from the allocation. */
+int mugiq_hip_mg_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                       const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *coarseOp,
+                       const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out, double *history_out, int historyStride,
+                       int *hostReads_out, const MugiqHipComm *comm, void *stream);
+
 /* What Displace asks of QUDA's ColorSpinorField for its auxiliary vector (lib/displace.cpp:26-30: ColorSpinorField::Create
  * with QUDA_ZERO_FIELD_CREATE and setPrecision(coarsePrec_); :42,:50-51: operator=; :59: blas::zero), for hosts that do not
  * manage device memory themselves.  alloc: geometry, order, stride of `like`, `precision` (0 = like's), zeroed; ghost zones

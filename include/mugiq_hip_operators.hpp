@@ -201,6 +201,39 @@ inline void projectVector(ColorSpinorField &out, ColorSpinorField &in, const std
   if (eVecs.empty()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "projectVector: no eigenvectors");
   check(mugiq_hip_project_vector(&out, &in, eVecs.data(), (int)eVecs.size(), comm, stream));
 }
+// ---- the two-grid preconditioned GCR (csrc/mg_solve.hip; new) ----
+// MugiqHipMgSolveParam with the defaults of mugiq_hip_mg_solve_param_default (first guesses, not tuned)
+struct MgSolveParam : MugiqHipMgSolveParam {
+  MgSolveParam() { check(mugiq_hip_mg_solve_param_default(this)); }
+};
+// z_i = K(r_i): one two-grid cycle (mugiq_hip_mg_precondition); clover NULL: the unimproved operator
+inline void mgPrecondition(const std::vector<ColorSpinorField> &z, const std::vector<ColorSpinorField> &r, const GaugeField &gauge,
+                           const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer &transfer, const CoarseOperator &coarseOp,
+                           const MgSolveParam &param = MgSolveParam(), const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (r.empty() || z.size() != r.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgPrecondition: size mismatch");
+  check(mugiq_hip_mg_precondition(z.data(), r.data(), (int)r.size(), &gauge, clover, kappa, &transfer, coarseOp.desc(), &param, comm, stream));
+}
+// x_r = M^-1 b_r by the flexible GCR preconditioned with that cycle (mugiq_hip_mg_solve).  history[r]: the recursive relative residuals of
+// right-hand side r; hostReads: the blocking reads of the call.  Returns false where a right-hand side did not reach tol within maxIter
+// (every output is filled all the same); every other failure throws.
+inline bool mgSolve(const std::vector<ColorSpinorField> &x, const std::vector<ColorSpinorField> &b, const GaugeField &gauge,
+                    const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer &transfer, const CoarseOperator &coarseOp,
+                    const MgSolveParam &param, std::vector<int> &iters, std::vector<double> &relres, std::vector<std::vector<double>> *history = nullptr,
+                    int *hostReads = nullptr, const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (b.empty() || x.size() != b.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgSolve: size mismatch");
+  iters.assign(b.size(), 0);
+  relres.assign(b.size(), 0.0);
+  const int stride = param.maxIter > 0 ? param.maxIter : 1;
+  std::vector<double> hist(history ? b.size() * (size_t)stride : 0);
+  const int st = mugiq_hip_mg_solve(x.data(), b.data(), (int)b.size(), &gauge, clover, kappa, &transfer, coarseOp.desc(), &param, iters.data(),
+                                    relres.data(), history ? hist.data() : nullptr, stride, hostReads, comm, stream);
+  if (st != MUGIQ_HIP_ERROR_NOT_CONVERGED) check(st);
+  if (history) {
+    history->clear();
+    for (size_t i = 0; i < b.size(); i++) history->emplace_back(hist.begin() + i * stride, hist.begin() + i * stride + iters[i]);
+  }
+  return st == 0;
+}
 // x_r = M^-1 b_r by CG on the normal equations from the low-mode start (mugiq_hip_wilson_solve).  Returns false where a right-hand
 // side did not reach tol within maxIter (x, iters and relres are filled all the same); every other failure throws.
 inline bool wilsonSolve(const std::vector<ColorSpinorField> &x, const std::vector<ColorSpinorField> &b, const GaugeField &gauge, double kappa,

@@ -65,6 +65,12 @@ class CoarseOperatorDesc(ctypes.Structure):
                 ("kappa", ctypes.c_double), ("hasClover", ctypes.c_int)]
 
 
+class MgSolveParam(ctypes.Structure):
+    """MugiqHipMgSolveParam (include/mugiq_hip.h)."""
+    _fields_ = [("tol", ctypes.c_double), ("maxIter", ctypes.c_int), ("nKrylov", ctypes.c_int), ("nuPre", ctypes.c_int), ("nuPost", ctypes.c_int),
+                ("omega", ctypes.c_double), ("coarseIters", ctypes.c_int)]
+
+
 class ProjectPlan(ctypes.Structure):
     """MugiqHipProjectPlan (include/mugiq_hip.h)."""
     _fields_ = [(n, ctypes.c_int) for n in ("form", "nks", "mb", "nPx", "tChunk", "nChunks", "lastChunk", "tiles", "tilesPerWg",
@@ -221,6 +227,12 @@ SIGNATURES = {
                                                                ctypes.POINTER(ctypes.c_double), _VP, _VP]),
     "mugiq_hip_wilson_clover_solve": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, _SP, ctypes.POINTER(ctypes.c_double),
                                                      ctypes.c_int, ctypes.c_double, ctypes.c_int, _I4, ctypes.POINTER(ctypes.c_double), _VP, _VP]),
+    "mugiq_hip_mg_solve_param_default": (ctypes.c_int, [ctypes.POINTER(MgSolveParam)]),
+    "mugiq_hip_mg_precondition": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
+                                                 ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(MgSolveParam), _VP, _VP]),
+    "mugiq_hip_mg_solve": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
+                                          ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(MgSolveParam), _I4, ctypes.POINTER(ctypes.c_double),
+                                          ctypes.POINTER(ctypes.c_double), ctypes.c_int, _I4, _VP, _VP]),
     "mugiq_hip_prolongate_batched": (ctypes.c_int, [_SP, ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),
     "mugiq_hip_prolongate_contract_batched": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(CoarseDesc), ctypes.POINTER(ctypes.c_double),
                                                              ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),

@@ -1,0 +1,734 @@
+// A flexible GCR on the fine Wilson(-clover) operator, preconditioned by one two-grid cycle K: MR smoothing and a coarse-grid correction
+// through R, a fixed number of GCR steps on the explicit coarse operator, and P.  Definitions (MR step, GCRfix, K, the outer solve), limits
+// and work memory: mugiq_hip_mg_solve in include/mugiq_hip.h.  The stencil, R, P and the coarse application are the library's own entry
+// points, called as they are; what is new here are the Krylov kernels between them, on both levels.
+//
+// One set of kernels serves both levels: a field is a list of rows of complex fp64 numbers (MgLayout; fine FLOAT2: 12 rows of volumeCB per
+// parity, fine FLOAT4: 6 rows of 2 volumeCB, coarse: 2 n_vec rows of volumeCB_c), every lane takes whole complex numbers (16-byte accesses,
+// consecutive along a row), pads are never touched.  blockIdx.y is the right-hand side; a right-hand side whose `active` bit is clear is not
+// touched.  Every sum is taken per lane over its elements in ascending order, over the wave by shuffles, over the workgroup's four waves
+// and then over the workgroups by mg_final_sum_kernel, each in a fixed order that depends on the shape of the field alone: no atomics, two
+// runs give the same bits, and a right-hand side has the same sums wherever it stands in a block.
+//
+// The Krylov directions of a level lie behind one base pointer, direction j of right-hand side v at (j nb + v) vecElems, so that a kernel
+// reaches all of them without a pointer table.  Scalars never leave the device inside K: mg_final_sum_kernel turns the partial sums into
+// the Gram-Schmidt coefficients, into (nu, alpha) of a GCR step or into alpha of an MR step, and the next kernel reads them from memory.
+// The host reads only the squared residual norms of the outer iteration (and ||b||^2 and the true residual, once per block each).
+#include "internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+namespace mugiq {
+namespace {
+
+constexpr int kMgBlock = 8;       // right-hand sides per block
+constexpr int kMgMaxDir = 16;     // stored directions of a level
+constexpr int kMgThreads = 256;
+constexpr int kMgMaxGroups = 256; // workgroups of a pass per right-hand side: the partial sums mg_final_sum_kernel adds up
+constexpr int kMgSlots = 32;      // doubles per right-hand side and workgroup: up to 15 complex coefficients, or 3 sums
+static_assert(2 * (kMgMaxDir - 1) <= kMgSlots && kMgBlock * kMgSlots == kMgThreads, "mg_final_sum_kernel: one lane per (right-hand side, slot)");
+
+typedef Cplx<double> Z;
+
+struct MgLayout {
+  int nRows;
+  int64_t rowLen, rowStride, po, total;  // complex elements; total = 2 nRows rowLen
+};
+
+// complex offset of element e of a field: (parity, row, position in the row), rows in ascending order.  I: uint32_t where total < 2^31
+template <typename I> __device__ inline int64_t mg_offset(const MgLayout &L, I e) {
+  const I rowLen = (I)L.rowLen, per = (I)L.nRows * rowLen;
+  const int pty = e >= per ? 1 : 0;
+  const I rem = e - (pty ? per : (I)0), row = rem / rowLen;
+  return pty * L.po + (int64_t)row * L.rowStride + (int64_t)(rem - row * rowLen);
+}
+
+typedef double mg_vec2 __attribute__((ext_vector_type(2)));
+__device__ inline Z ldz(const Z *p, int64_t i) {
+  const mg_vec2 t = *as_global(reinterpret_cast<const mg_vec2 *>(p) + i);
+  return Z{t.x, t.y};
+}
+__device__ inline void stz(Z *p, int64_t i, const Z &v) {
+  mg_vec2 t;
+  t.x = v.re;
+  t.y = v.im;
+  *as_global(reinterpret_cast<mg_vec2 *>(p) + i) = t;
+}
+
+// v[0 .. nUsed) summed over the workgroup -> out[0 .. nUsed): down the wave by shuffles, then the four waves in ascending order
+template <int NS> __device__ inline void mg_group_sum(double (&v)[NS], int nUsed, double *out) {
+  __shared__ double sh[kMgThreads / 64][NS];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+#pragma unroll
+  for (int s = 0; s < NS; s++) {
+    if (s < nUsed) {
+      double x = v[s];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+      if (lane == 0) sh[w][s] = x;
+    }
+  }
+  __syncthreads();
+  if (t < nUsed) out[t] = ((sh[0][t] + sh[1][t]) + sh[2][t]) + sh[3][t];
+}
+
+struct MgVecs {
+  Z *p[kMgBlock];
+};
+
+// multi-dot: c_j = <q_j, q_k> for all j < k, from the q_k the operator left (classical Gram-Schmidt): slots (2j, 2j + 1)
+template <typename I>
+__global__ __launch_bounds__(kMgThreads) void mg_multidot_kernel(const Z *Q, int64_t vecElems, int nb, int k, MgLayout L, unsigned active, double *partial) {
+  const int v = blockIdx.y;
+  if (!((active >> v) & 1u)) return;
+  double acc[kMgSlots];
+#pragma unroll
+  for (int s = 0; s < kMgSlots; s++) acc[s] = 0.0;
+  const Z *qk = Q + ((int64_t)k * nb + v) * vecElems;
+  for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
+    const int64_t off = mg_offset<I>(L, e);
+    const Z q = ldz(qk, off);
+#pragma unroll
+    for (int j = 0; j < kMgMaxDir - 1; j++) {
+      if (j < k) {
+        const Z a = ldz(Q + ((int64_t)j * nb + v) * vecElems, off);
+        acc[2 * j] = fma(a.re, q.re, acc[2 * j]);
+        acc[2 * j] = fma(a.im, q.im, acc[2 * j]);
+        acc[2 * j + 1] = fma(a.re, q.im, acc[2 * j + 1]);
+        acc[2 * j + 1] = fma(-a.im, q.re, acc[2 * j + 1]);
+      }
+    }
+  }
+  mg_group_sum<kMgSlots>(acc, 2 * k, partial + ((size_t)v * gridDim.x + blockIdx.x) * kMgSlots);
+}
+
+// multi-axpy: p_k -= sum_j c_j p_j, q_k -= sum_j c_j q_j with c from device memory; in the same pass ||q_k||^2 (slot 0) and <q_k, r>
+// (slots 1, 2) of the orthogonalised q_k
+template <typename I>
+__global__ __launch_bounds__(kMgThreads) void mg_multiaxpy_kernel(Z *P, Z *Q, int64_t vecElems, int nb, int k, MgVecs R, const double *coef, MgLayout L,
+                                                                 unsigned active, double *partial) {
+  const int v = blockIdx.y;
+  if (!((active >> v) & 1u)) return;
+  double c[2 * (kMgMaxDir - 1)];
+#pragma unroll
+  for (int s = 0; s < 2 * (kMgMaxDir - 1); s++) c[s] = s < 2 * k ? coef[v * kMgSlots + s] : 0.0;
+  double acc[3] = {0.0, 0.0, 0.0};
+  Z *pk = P + ((int64_t)k * nb + v) * vecElems, *qk = Q + ((int64_t)k * nb + v) * vecElems;
+  for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
+    const int64_t off = mg_offset<I>(L, e);
+    Z q = ldz(qk, off);
+    if (k > 0) {
+      Z p = ldz(pk, off);
+#pragma unroll
+      for (int j = 0; j < kMgMaxDir - 1; j++) {
+        if (j < k) {
+          const Z cj{-c[2 * j], -c[2 * j + 1]};
+          cmadd(p, cj, ldz(P + ((int64_t)j * nb + v) * vecElems, off));
+          cmadd(q, cj, ldz(Q + ((int64_t)j * nb + v) * vecElems, off));
+        }
+      }
+      stz(pk, off, p);
+      stz(qk, off, q);
+    }
+    const Z r = ldz(R.p[v], off);
+    acc[0] = fma(q.re, q.re, acc[0]);
+    acc[0] = fma(q.im, q.im, acc[0]);
+    acc[1] = fma(q.re, r.re, acc[1]);
+    acc[1] = fma(q.im, r.im, acc[1]);
+    acc[2] = fma(q.re, r.im, acc[2]);
+    acc[2] = fma(-q.im, r.re, acc[2]);
+  }
+  mg_group_sum<3>(acc, 3, partial + ((size_t)v * gridDim.x + blockIdx.x) * kMgSlots);
+}
+
+// update: p_k /= nu, q_k /= nu (nu = 0: a zero direction), x += alpha p_k (xZero: x = alpha p_k), r -= alpha q_k, ||r||^2 into slot 0;
+// sc[4 v] = (nu, Re alpha, Im alpha) from mg_final_sum_kernel.  Pnext != NULL: the new r is also the next direction p_{k+1} (GCRfix)
+template <typename I>
+__global__ __launch_bounds__(kMgThreads) void mg_update_kernel(Z *P, Z *Q, int64_t vecElems, int nb, int k, MgVecs X, MgVecs R, const double *sc, int xZero,
+                                                              Z *Pnext, MgLayout L, unsigned active, double *partial) {
+  const int v = blockIdx.y;
+  if (!((active >> v) & 1u)) return;
+  const double nu = sc[4 * v];
+  const Z alpha{sc[4 * v + 1], sc[4 * v + 2]}, malpha{-alpha.re, -alpha.im};
+  double acc[1] = {0.0};
+  Z *pk = P + ((int64_t)k * nb + v) * vecElems, *qk = Q + ((int64_t)k * nb + v) * vecElems;
+  Z *pn = Pnext ? Pnext + ((int64_t)(k + 1) * nb + v) * vecElems : nullptr;
+  for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
+    const int64_t off = mg_offset<I>(L, e);
+    Z p = ldz(pk, off), q = ldz(qk, off);
+    if (nu > 0.0) {
+      p = Z{p.re / nu, p.im / nu};
+      q = Z{q.re / nu, q.im / nu};
+    } else {
+      p = q = Z{0.0, 0.0};
+    }
+    stz(pk, off, p);
+    stz(qk, off, q);
+    Z x = xZero ? Z{0.0, 0.0} : ldz(X.p[v], off);
+    cmadd(x, alpha, p);
+    stz(X.p[v], off, x);
+    Z r = ldz(R.p[v], off);
+    cmadd(r, malpha, q);
+    stz(R.p[v], off, r);
+    if (pn) stz(pn, off, r);
+    acc[0] = fma(r.re, r.re, acc[0]);
+    acc[0] = fma(r.im, r.im, acc[0]);
+  }
+  mg_group_sum<1>(acc, 1, partial + ((size_t)v * gridDim.x + blockIdx.x) * kMgSlots);
+}
+
+// <t, s> into slots 0, 1 and <t, t> into slot 2 (an MR step; with t = s: a norm)
+template <typename I> __global__ __launch_bounds__(kMgThreads) void mg_dot2_kernel(MgVecs T, MgVecs S, MgLayout L, unsigned active, double *partial) {
+  const int v = blockIdx.y;
+  if (!((active >> v) & 1u)) return;
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
+    const int64_t off = mg_offset<I>(L, e);
+    const Z t = ldz(T.p[v], off), s = ldz(S.p[v], off);
+    acc[0] = fma(t.re, s.re, acc[0]);
+    acc[0] = fma(t.im, s.im, acc[0]);
+    acc[1] = fma(t.re, s.im, acc[1]);
+    acc[1] = fma(-t.im, s.re, acc[1]);
+    acc[2] = fma(t.re, t.re, acc[2]);
+    acc[2] = fma(t.im, t.im, acc[2]);
+  }
+  mg_group_sum<3>(acc, 3, partial + ((size_t)v * gridDim.x + blockIdx.x) * kMgSlots);
+}
+
+// the update of an MR step: z += alpha s (zZero: z = alpha s), sOut = s - alpha t (sOut NULL: the last step of K, s is not needed again);
+// sc[4 v] = (Re alpha, Im alpha) from mg_final_sum_kernel.  sOut may be s
+template <typename I>
+__global__ __launch_bounds__(kMgThreads) void mg_mr_update_kernel(MgVecs Zv, MgVecs S, MgVecs T, MgVecs SOut, const double *sc, int zZero, int writeS,
+                                                                 MgLayout L, unsigned active) {
+  const int v = blockIdx.y;
+  if (!((active >> v) & 1u)) return;
+  const Z alpha{sc[4 * v], sc[4 * v + 1]}, malpha{-alpha.re, -alpha.im};
+  for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
+    const int64_t off = mg_offset<I>(L, e);
+    Z s = ldz(S.p[v], off);
+    Z z = zZero ? Z{0.0, 0.0} : ldz(Zv.p[v], off);
+    cmadd(z, alpha, s);
+    stz(Zv.p[v], off, z);
+    if (writeS) {
+      cmadd(s, malpha, ldz(T.p[v], off));
+      stz(SOut.p[v], off, s);
+    }
+  }
+}
+
+// c = sa a + sb b on the elements (a or b NULL: that term is zero; c may be a or b)
+template <typename I>
+__global__ __launch_bounds__(kMgThreads) void mg_axpby_kernel(MgVecs C, MgVecs A, double sa, MgVecs B, double sb, MgLayout L, unsigned active) {
+  const int v = blockIdx.y;
+  if (!((active >> v) & 1u)) return;
+  for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
+    const int64_t off = mg_offset<I>(L, e);
+    Z o{0.0, 0.0};
+    if (A.p[v]) {
+      const Z a = ldz(A.p[v], off);
+      o = Z{sa * a.re, sa * a.im};
+    }
+    if (B.p[v]) {
+      const Z b = ldz(B.p[v], off);
+      o.re = fma(sb, b.re, o.re);
+      o.im = fma(sb, b.im, o.im);
+    }
+    stz(C.p[v], off, o);
+  }
+}
+
+// The sums of the last pass over its workgroups, in ascending order, one lane per (right-hand side, slot), and what the next kernel needs
+// of them.  kMgFinRaw: res[4 v + s] = sum s, s < 4 (what the host reads);  kMgFinCoef: coef[32 v + s] = sum s;
+// kMgFinNorm (after mg_multiaxpy_kernel): sc[4 v] = (nu = sqrt ||q||^2, <q, r> / nu), zero for nu = 0;
+// kMgFinMr (after mg_dot2_kernel): sc[4 v] = omega <t, s> / <t, t>, zero for <t, t> = 0
+enum { kMgFinRaw = 0, kMgFinCoef = 1, kMgFinNorm = 2, kMgFinMr = 3 };
+__global__ __launch_bounds__(kMgThreads) void mg_final_sum_kernel(const double *partial, int nGroups, int nUsed, unsigned active, int mode, double omega,
+                                                                 double *coef, double *sc, double *res) {
+  __shared__ double sum[kMgBlock][kMgSlots];
+  const int t = threadIdx.x, v = t / kMgSlots, s = t - v * kMgSlots;
+  double a = 0.0;
+  if (((active >> v) & 1u) && s < nUsed)
+    for (int g = 0; g < nGroups; g++) a += partial[((size_t)v * nGroups + g) * kMgSlots + s];
+  sum[v][s] = a;
+  __syncthreads();
+  if (mode == kMgFinCoef) {
+    coef[t] = a;
+  } else if (mode == kMgFinRaw) {
+    if (s < 4) res[4 * v + s] = a;
+  } else if (s == 0) {
+    if (mode == kMgFinNorm) {
+      const double nu = sqrt(sum[v][0]);
+      sc[4 * v] = nu;
+      sc[4 * v + 1] = nu > 0.0 ? sum[v][1] / nu : 0.0;
+      sc[4 * v + 2] = nu > 0.0 ? sum[v][2] / nu : 0.0;
+    } else {
+      const double d = sum[v][2];
+      sc[4 * v] = d > 0.0 ? omega * sum[v][0] / d : 0.0;
+      sc[4 * v + 1] = d > 0.0 ? omega * sum[v][1] / d : 0.0;
+    }
+  }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------------
+MgLayout fine_layout(const MugiqHipSpinorField &f) {
+  MgLayout L;
+  const bool f2 = f.field_order == 2;
+  L.nRows = f2 ? 12 : 6;
+  L.rowLen = f2 ? f.volumeCB : (int64_t)2 * f.volumeCB;
+  L.rowStride = f2 ? f.stride : (int64_t)2 * f.stride;
+  L.po = f.parity_offset;
+  L.total = 2 * L.nRows * L.rowLen;
+  return L;
+}
+MgLayout coarse_layout(const MugiqHipCoarseField &f) {
+  MgLayout L;
+  L.nRows = f.nSpin * f.nColor;
+  L.rowLen = f.volumeCB;
+  L.rowStride = f.stride;
+  L.po = f.parity_offset;
+  L.total = 2 * L.nRows * L.rowLen;
+  return L;
+}
+size_t fine_bytes(const MugiqHipSpinorField &f) { return align256((size_t)2 * (size_t)f.parity_offset * sizeof(Z)); }
+size_t coarse_bytes(const MugiqHipCoarseField &f) { return align256((size_t)2 * (size_t)f.parity_offset * sizeof(Z)); }
+size_t scalar_bytes() { return align256(sizeof(double) * ((size_t)kMgBlock * kMgMaxGroups * kMgSlots + kMgBlock * kMgSlots + 2 * 4 * kMgBlock)); }
+
+// one level's Krylov state in the workspace and the launches on it
+struct MgLevel {
+  MgLayout L;
+  int nb = 0, nGroups = 0;
+  int64_t vecElems = 0;
+  Z *P = nullptr, *Q = nullptr;  // nDir x nb vectors each
+  double *partial = nullptr, *coef = nullptr, *sc = nullptr, *res = nullptr;  // shared by both levels: the stream orders their passes
+  hipStream_t stream = nullptr;
+
+  void set_layout(const MgLayout &l) {
+    L = l;
+    nGroups = (int)std::min<int64_t>(kMgMaxGroups, (L.total + kMgThreads - 1) / kMgThreads);
+  }
+  void set_scalars(unsigned char *base) {
+    partial = reinterpret_cast<double *>(base);
+    coef = partial + (size_t)kMgBlock * kMgMaxGroups * kMgSlots;
+    sc = coef + kMgBlock * kMgSlots;
+    res = sc + 4 * kMgBlock;
+  }
+  Z *dir(Z *base, int j, int v) const { return base + ((int64_t)j * nb + v) * vecElems; }
+  bool narrow() const { return L.total < (int64_t(1) << 31); }
+  dim3 grid(int n) const { return dim3(nGroups, n); }
+
+  int final_sum(int nUsed, unsigned active, int mode, double omega) const {
+    hipLaunchKernelGGL(mg_final_sum_kernel, dim3(1), dim3(kMgThreads), 0, stream, partial, nGroups, nUsed, active, mode, omega, coef, sc, res);
+    MUGIQ_CHECK_HIP(hipGetLastError());
+    return MUGIQ_HIP_SUCCESS;
+  }
+#define MUGIQ_MG_LAUNCH(kernel, n, ...)                                                                                   \
+  do {                                                                                                                    \
+    if (narrow()) hipLaunchKernelGGL(kernel<uint32_t>, grid(n), dim3(kMgThreads), 0, stream, __VA_ARGS__);                \
+    else hipLaunchKernelGGL(kernel<int64_t>, grid(n), dim3(kMgThreads), 0, stream, __VA_ARGS__);                          \
+    MUGIQ_CHECK_HIP(hipGetLastError());                                                                                   \
+  } while (0)
+
+  int axpby(const MgVecs &c, const MgVecs *a, double sa, const MgVecs *b, double sb, int n, unsigned active) const {
+    const MgVecs none{};
+    MUGIQ_MG_LAUNCH(mg_axpby_kernel, n, c, a ? *a : none, sa, b ? *b : none, sb, L, active);
+    return MUGIQ_HIP_SUCCESS;
+  }
+  // <t, s> and <t, t> -> mode kMgFinMr: alpha of an MR step in sc; kMgFinRaw: the sums in res
+  int dot2(const MgVecs &t, const MgVecs &s, int n, unsigned active, int mode, double omega) const {
+    MUGIQ_MG_LAUNCH(mg_dot2_kernel, n, t, s, L, active, partial);
+    return final_sum(3, active, mode, omega);
+  }
+  int mr_update(const MgVecs &z, const MgVecs &s, const MgVecs &t, const MgVecs *sOut, bool zZero, int n, unsigned active) const {
+    const MgVecs none{};
+    MUGIQ_MG_LAUNCH(mg_mr_update_kernel, n, z, s, t, sOut ? *sOut : none, sc, zZero ? 1 : 0, sOut ? 1 : 0, L, active);
+    return MUGIQ_HIP_SUCCESS;
+  }
+  // step k of the GCR recurrence once q_k = A p_k is there: orthogonalise against the k stored directions, normalise, update x and r.
+  // Leaves ||r||^2 of the step in res (wantNorm) for the host to fetch
+  int gcr_step(int k, const MgVecs &x, const MgVecs &r, bool xZero, bool copyNext, bool wantNorm, int n, unsigned active) const {
+    if (k > 0) {
+      MUGIQ_MG_LAUNCH(mg_multidot_kernel, n, Q, vecElems, nb, k, L, active, partial);
+      if (int st = final_sum(2 * k, active, kMgFinCoef, 0.0)) return st;
+    }
+    MUGIQ_MG_LAUNCH(mg_multiaxpy_kernel, n, P, Q, vecElems, nb, k, r, coef, L, active, partial);
+    if (int st = final_sum(3, active, kMgFinNorm, 0.0)) return st;
+    MUGIQ_MG_LAUNCH(mg_update_kernel, n, P, Q, vecElems, nb, k, x, r, sc, xZero ? 1 : 0, copyNext ? P : (Z *)nullptr, L, active, partial);
+    return wantNorm ? final_sum(1, active, kMgFinRaw, 0.0) : MUGIQ_HIP_SUCCESS;
+  }
+#undef MUGIQ_MG_LAUNCH
+};
+
+struct MgSolver {
+  const MugiqHipGaugeField *gauge;
+  const MugiqHipCloverField *clover;
+  double kappa;
+  const MugiqHipTransfer *transfer;
+  const MugiqHipCoarseOperator *op;
+  MugiqHipMgSolveParam prm;
+  hipStream_t stream;
+  int nb;
+  MgLevel fine, coarse;
+  MugiqHipSpinorField s[kMgBlock], t[kMgBlock], w[kMgBlock], r[kMgBlock];  // r: the solver's recursive residual
+  MugiqHipCoarseField xc[kMgBlock], rc[kMgBlock];
+  MugiqHipSpinorField fineLike;
+  MugiqHipCoarseField coarseLike;
+
+  static MgVecs vecs(const MugiqHipSpinorField *f, int n) {
+    MgVecs m{};
+    for (int i = 0; i < n; i++) m.p[i] = static_cast<Z *>(f[i].data);
+    return m;
+  }
+  static MgVecs vecs(const MugiqHipCoarseField *f, int n) {
+    MgVecs m{};
+    for (int i = 0; i < n; i++) m.p[i] = static_cast<Z *>(f[i].data);
+    return m;
+  }
+  MugiqHipSpinorField fine_dir(Z *base, int j, int v) const {
+    MugiqHipSpinorField f = fineLike;
+    f.data = fine.dir(base, j, v);
+    return f;
+  }
+  MugiqHipCoarseField coarse_dir(Z *base, int j, int v) const {
+    MugiqHipCoarseField f = coarseLike;
+    f.data = coarse.dir(base, j, v);
+    return f;
+  }
+  template <typename F> static int gather(const F *set, int n, unsigned mask, F *out) {
+    int m = 0;
+    for (int i = 0; i < n; i++)
+      if ((mask >> i) & 1u) out[m++] = set[i];
+    return m;
+  }
+  // dst_i = M src_i for the active i: the batched stencil as it is
+  int apply_M(const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int n, unsigned active) const {
+    MugiqHipSpinorField d[kMgBlock], sr[kMgBlock];
+    const int m = gather(dst, n, active, d);
+    gather(src, n, active, sr);
+    return mugiq_hip_wilson_clover_apply(d, sr, m, gauge, clover, kappa, MUGIQ_HIP_EIG_OPERATOR_M, 1.0, nullptr, stream);
+  }
+
+  // the work memory, carved from the stream's operator workspace: the scalars, then per right-hand side of a block 2 nDirFine fine
+  // directions, s, t, w (and r for the solver), and on the coarse level 2 coarseIters directions, xc, rc.
+  // apply_M calls the public stencil entry, which reserves the SAME arena for itself (csrc/wilson.hip, wilson_apply_impl) and takes its
+  // start as the send buffer of its halo exchange.  That is safe here for two reasons, both of which this file depends on: on a single
+  // domain with the form M its request is 256 bytes, so the arena, which only ever grows, neither moves nor is freed under us; and
+  // without a partitioned axis nothing is packed into that send buffer.  The first kStencilHead bytes are left unused all the same, so
+  // that a send buffer that did get written would not land in `partial`.
+  int reserve(const MugiqHipSpinorField &like, int nDirFine, int nVecRhs, bool withR) {
+    nb = std::min(nVecRhs, kMgBlock);
+    fineLike = like;
+    for (int d = 0; d < 4; d++)
+      for (int b = 0; b < 2; b++) fineLike.ghost[d][b] = nullptr;
+    coarseLike = coarse_side_layout(*transfer);
+    const size_t fb = fine_bytes(like), cb = coarse_bytes(coarseLike);
+    const int nC = prm.coarseIters;
+    constexpr size_t kStencilHead = 4096;
+    const size_t bytes = kStencilHead + scalar_bytes() + (size_t)(2 * nDirFine + (withR ? 4 : 3)) * nb * fb + (size_t)(nC > 0 ? 2 * nC + 2 : 0) * nb * cb + 256;
+    void *ws = nullptr;
+    if (int st = stream_operator_workspace(&ws, bytes, stream)) return st;
+    unsigned char *cur = static_cast<unsigned char *>(ws) + kStencilHead;
+    fine.set_scalars(cur);
+    coarse.set_scalars(cur);
+    cur += scalar_bytes();
+    fine.stream = coarse.stream = stream;
+    fine.nb = coarse.nb = nb;
+    fine.set_layout(fine_layout(like));
+    fine.vecElems = (int64_t)(fb / sizeof(Z));
+    fine.P = reinterpret_cast<Z *>(cur);
+    cur += (size_t)nDirFine * nb * fb;
+    fine.Q = reinterpret_cast<Z *>(cur);
+    cur += (size_t)nDirFine * nb * fb;
+    MugiqHipSpinorField *sets[4] = {s, t, w, r};
+    for (int k = 0; k < (withR ? 4 : 3); k++)
+      for (int i = 0; i < nb; i++) {
+        MugiqHipSpinorField *set = sets[k];
+        set[i] = fineLike;
+        set[i].data = cur;
+        cur += fb;
+      }
+    coarse.set_layout(coarse_layout(coarseLike));
+    coarse.vecElems = (int64_t)(cb / sizeof(Z));
+    if (nC > 0) {
+      coarse.P = reinterpret_cast<Z *>(cur);
+      cur += (size_t)nC * nb * cb;
+      coarse.Q = reinterpret_cast<Z *>(cur);
+      cur += (size_t)nC * nb * cb;
+      MugiqHipCoarseField *csets[2] = {xc, rc};
+      for (auto *set : csets)
+        for (int i = 0; i < nb; i++) {
+          set[i] = coarseLike;
+          set[i].data = cur;
+          cur += cb;
+        }
+    }
+    return MUGIQ_HIP_SUCCESS;
+  }
+
+  // one MR step on (z, sIn): t = M sIn, alpha on the device, z += alpha sIn, s = sIn - alpha t (last: s is not needed again)
+  int mr_step(const MugiqHipSpinorField *z, const MugiqHipSpinorField *sIn, bool zZero, bool last, int n, unsigned active) const {
+    if (int st = apply_M(t, sIn, n, active)) return st;
+    const MgVecs tv = vecs(t, n), sv = vecs(sIn, n), so = vecs(s, n);
+    if (int st = fine.dot2(tv, sv, n, active, kMgFinMr, prm.omega)) return st;
+    return fine.mr_update(vecs(z, n), sv, tv, last ? nullptr : &so, zZero, n, active);
+  }
+
+  // xc = GCRfix(M_c, rc, coarseIters) for the active right-hand sides; rc is used up
+  int coarse_solve(int n, unsigned active) const {
+    const int nC = prm.coarseIters;
+    MugiqHipCoarseField p0[kMgBlock];
+    for (int i = 0; i < n; i++) p0[i] = coarse_dir(coarse.P, 0, i);
+    const MgVecs rv = vecs(rc, n), xv = vecs(xc, n), pv = vecs(p0, n);
+    if (int st = coarse.axpby(pv, &rv, 1.0, nullptr, 0.0, n, active)) return st;
+    for (int k = 0; k < nC; k++) {
+      MugiqHipCoarseField p[kMgBlock], q[kMgBlock], pa[kMgBlock], qa[kMgBlock];
+      for (int i = 0; i < n; i++) {
+        p[i] = coarse_dir(coarse.P, k, i);
+        q[i] = coarse_dir(coarse.Q, k, i);
+      }
+      const int m = gather(p, n, active, pa);
+      gather(q, n, active, qa);
+      if (int st = coarse_apply(qa, pa, m, op, MUGIQ_HIP_EIG_OPERATOR_M, 1.0, stream)) return st;
+      if (int st = coarse.gcr_step(k, xv, rv, k == 0, k + 1 < nC, false, n, active)) return st;
+    }
+    return MUGIQ_HIP_SUCCESS;
+  }
+
+  // z_i = K(r_i) for the active i: a fixed sequence of launches, nothing read back.  z and r are not touched elsewhere; r is only read
+  int precondition(const MugiqHipSpinorField *z, const MugiqHipSpinorField *r, int n, unsigned active) const {
+    bool zZero = true;
+    const MugiqHipSpinorField *sIn = r;  // where s lives: r itself until the first update
+    const bool coarseStep = prm.coarseIters > 0;
+    int st;
+    for (int i = 0; i < prm.nuPre; i++) {
+      if ((st = mr_step(z, sIn, zZero, !coarseStep && prm.nuPost == 0 && i == prm.nuPre - 1, n, active))) return st;
+      zZero = false;
+      sIn = s;
+    }
+    if (coarseStep) {
+      MugiqHipSpinorField fa[kMgBlock];
+      MugiqHipCoarseField ca[kMgBlock];
+      int m = gather(sIn, n, active, fa);
+      gather(rc, n, active, ca);
+      if ((st = mugiq_hip_restrict_batched(ca, fa, m, transfer, 0, stream))) return st;
+      if ((st = coarse_solve(n, active))) return st;
+      gather(xc, n, active, ca);
+      gather(zZero ? z : w, n, active, fa);
+      if ((st = mugiq_hip_prolongate_batched(fa, ca, m, transfer, stream))) return st;
+      const MgVecs zv = vecs(z, n), wv = vecs(w, n);
+      if (!zZero && (st = fine.axpby(zv, &zv, 1.0, &wv, 1.0, n, active))) return st;
+      zZero = false;
+      if (prm.nuPost > 0) {  // s = r - M z, one application
+        if ((st = apply_M(t, z, n, active))) return st;
+        const MgVecs rv = vecs(r, n), tv = vecs(t, n);
+        if ((st = fine.axpby(vecs(s, n), &rv, 1.0, &tv, -1.0, n, active))) return st;
+        sIn = s;
+      }
+    }
+    for (int i = 0; i < prm.nuPost; i++) {
+      if ((st = mr_step(z, sIn, zZero, i == prm.nuPost - 1, n, active))) return st;
+      zZero = false;
+      sIn = s;
+    }
+    if (zZero) return fine.axpby(vecs(z, n), nullptr, 0.0, nullptr, 0.0, n, active);  // no step at all: K = 0
+    return MUGIQ_HIP_SUCCESS;
+  }
+
+  // res[4 i + ..] of the last final sum, on the host: the one blocking read
+  int fetch(double out[4 * kMgBlock], int *reads) const {
+    MUGIQ_CHECK_HIP(hipMemcpyAsync(out, fine.res, sizeof(double) * 4 * kMgBlock, hipMemcpyDeviceToHost, stream));
+    MUGIQ_CHECK_HIP(hipStreamSynchronize(stream));
+    ++*reads;
+    return MUGIQ_HIP_SUCCESS;
+  }
+};
+
+bool same_layout(const MugiqHipSpinorField &a, const MugiqHipSpinorField &b) {
+  return same_geometry(a, b) && a.stride == b.stride && a.parity_offset == b.parity_offset;
+}
+
+int check_param(const MugiqHipMgSolveParam *p, const char *who) {
+  MUGIQ_REQUIRE(p != nullptr, "%s: param is NULL", who);
+  MUGIQ_REQUIRE(p->tol > 0.0 && p->maxIter >= 0, "%s: tol = %g must be positive and maxIter = %d non-negative", who, p->tol, p->maxIter);
+  MUGIQ_REQUIRE(p->nKrylov >= 1 && p->nKrylov <= kMgMaxDir, "%s: nKrylov = %d must be in [1, %d]", who, p->nKrylov, kMgMaxDir);
+  MUGIQ_REQUIRE(p->nuPre >= 0 && p->nuPre <= 16 && p->nuPost >= 0 && p->nuPost <= 16, "%s: nuPre = %d and nuPost = %d must be in [0, 16]", who, p->nuPre,
+                p->nuPost);
+  MUGIQ_REQUIRE(p->coarseIters >= 0 && p->coarseIters <= kMgMaxDir, "%s: coarseIters = %d must be in [0, %d]", who, p->coarseIters, kMgMaxDir);
+  MUGIQ_REQUIRE(std::isfinite(p->omega), "%s: omega = %g", who, p->omega);
+  return MUGIQ_HIP_SUCCESS;
+}
+
+// everything the two entry points share, before any device work: out (written) and in (read) are nVec fp64 fields of one layout
+int check_problem(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in, int nVec, const char *outName, const char *inName,
+                  const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *op,
+                  const MugiqHipMgSolveParam *param, double kappa, const MugiqHipComm *comm, const char *who) {
+  MUGIQ_REQUIRE(out != nullptr && in != nullptr && transfer != nullptr && op != nullptr && gauge != nullptr, "%s: NULL argument", who);
+  MUGIQ_REQUIRE(nVec >= 1, "%s: nVec = %d must be >= 1", who, nVec);
+  int st;
+  if ((st = check_param(param, who))) return st;
+  if ((st = check_single_domain(comm, who))) return st;
+  if ((st = validate_coarse_operator(op, who))) return st;
+  MUGIQ_REQUIRE(transfer->V != nullptr, "%s: transfer / null vectors are NULL", who);
+  for (int i = 0; i < nVec; i++) {
+    if ((st = validate_spinor(&out[i], who, outName))) return st;
+    if ((st = validate_spinor(&in[i], who, inName))) return st;
+  }
+  if (transfer->precision != 8 || op->precision != 8 || out[0].precision != 8 || in[0].precision != 8)
+    return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "%s: fp64 only: the transfer has precision %d, the coarse operator %d, %s %d and %s %d", who,
+                     transfer->precision, op->precision, outName, out[0].precision, inName, in[0].precision);
+  for (int i = 0; i < nVec; i++)
+    MUGIQ_REQUIRE(same_layout(out[i], out[0]) && same_layout(in[i], out[0]),
+                  "%s: vector %d of %s or %s differs in precision, field order, geometry, stride or parity offset from %s vector 0", who, i, outName, inName,
+                  outName);
+  for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(transfer->X[d] > 0 && transfer->geoBlockSize[d] >= 1, "%s: transfer X / geo_block_size[%d]", who, d);
+  MugiqHipCoarseField c0 = coarse_side_layout(*transfer);
+  c0.data = reinterpret_cast<void *>(uintptr_t(16));  // geometry only: never read
+  if ((st = validate_transfer(transfer, &c0, who))) return st;
+  MUGIQ_REQUIRE(op->nVec == transfer->nVec, "%s: the coarse operator has n_vec %d, the transfer %d", who, op->nVec, transfer->nVec);
+  for (int d = 0; d < 4; d++) {
+    MUGIQ_REQUIRE(op->X[d] == c0.X[d], "%s: coarse operator X[%d] = %d, the transfer's coarse lattice has %d", who, d, op->X[d], c0.X[d]);
+    MUGIQ_REQUIRE(in[0].X[d] == transfer->X[d], "%s: the fields have X[%d] = %d, the transfer %d", who, d, in[0].X[d], transfer->X[d]);
+  }
+  const int part[4] = {0, 0, 0, 0};
+  if ((st = check_gauge(gauge, in[0].X, part, who))) return st;
+  if (clover) {
+    if ((st = validate_clover(clover, in[0].X, in[0].volumeCB, who))) return st;
+    MUGIQ_REQUIRE(clover->precision == gauge->precision, "%s: clover precision %d differs from the gauge precision %d", who, clover->precision, gauge->precision);
+  }
+  // the operator must be the one of this M: a coarse operator of another kappa or clover term would still converge, only slowly and silently
+  MUGIQ_REQUIRE(op->kappa == kappa, "%s: the coarse operator was built for kappa = %.17g, the call has kappa = %.17g", who, op->kappa, kappa);
+  MUGIQ_REQUIRE((op->hasClover != 0) == (clover != nullptr), "%s: the coarse operator was built %s a clover field, the call is %s one", who,
+                op->hasClover ? "with" : "without", clover ? "with" : "without");
+  for (int i = 0; i < nVec; i++) {
+    uintptr_t a0, a1;
+    spinor_span(out[i], &a0, &a1);
+    for (int j = 0; j < i; j++) {
+      uintptr_t b0, b1;
+      spinor_span(out[j], &b0, &b1);
+      MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: %s vector %d overlaps %s vector %d", who, outName, i, outName, j);
+    }
+    for (int j = 0; j < nVec; j++) {
+      uintptr_t b0, b1;
+      spinor_span(in[j], &b0, &b1);
+      MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: %s vector %d overlaps %s vector %d", who, outName, i, inName, j);
+    }
+  }
+  return MUGIQ_HIP_SUCCESS;
+}
+
+}  // namespace
+}  // namespace mugiq
+
+using namespace mugiq;
+
+extern "C" {
+
+int mugiq_hip_mg_solve_param_default(MugiqHipMgSolveParam *param) {
+  MUGIQ_REQUIRE(param != nullptr, "mgSolveParamDefault: param is NULL");
+  param->tol = 1e-10;
+  param->maxIter = 1000;
+  param->nKrylov = 16;
+  param->nuPre = 0;
+  param->nuPost = 4;
+  param->omega = 1.0;
+  param->coarseIters = 8;
+  return MUGIQ_HIP_SUCCESS;
+}
+
+int mugiq_hip_mg_precondition(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
+                              const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *coarseOp,
+                              const MugiqHipMgSolveParam *param, const MugiqHipComm *comm, void *stream) {
+  const char *who = "mgPrecondition";
+  int st;
+  if ((st = check_problem(z_h, r_h, nVec, "z", "r", gauge, clover, transfer, coarseOp, param, kappa, comm, who))) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((st = debug_poison_lds_if_asked(s))) return st;
+  MgSolver S{gauge, clover, kappa, transfer, coarseOp, *param, s};
+  if ((st = S.reserve(r_h[0], 0, nVec, false))) return st;
+  for (int v0 = 0; v0 < nVec; v0 += kMgBlock) {
+    const int n = std::min(kMgBlock, nVec - v0);
+    if ((st = S.precondition(z_h + v0, r_h + v0, n, (1u << n) - 1u))) return st;
+  }
+  return MUGIQ_HIP_SUCCESS;
+}
+
+int mugiq_hip_mg_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                       const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *coarseOp,
+                       const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out, double *history_out, int historyStride, int *hostReads_out,
+                       const MugiqHipComm *comm, void *stream) {
+  const char *who = "mgSolve";
+  MUGIQ_REQUIRE(iters_out != nullptr && relres_out != nullptr, "%s: NULL argument", who);
+  int st;
+  if ((st = check_problem(x_h, b_h, nVec, "x", "b", gauge, clover, transfer, coarseOp, param, kappa, comm, who))) return st;
+  MUGIQ_REQUIRE(history_out == nullptr || historyStride >= param->maxIter, "%s: historyStride = %d is smaller than maxIter = %d", who, historyStride,
+                param->maxIter);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((st = debug_poison_lds_if_asked(s))) return st;
+  MgSolver S{gauge, clover, kappa, transfer, coarseOp, *param, s};
+  const int nK = param->nKrylov;
+  if ((st = S.reserve(b_h[0], nK, nVec, true))) return st;
+  const MugiqHipSpinorField *r = S.r;
+  const double tol2 = param->tol * param->tol;
+  bool allConverged = true;
+  int reads = 0;
+  double sums[4 * kMgBlock];
+  for (int v0 = 0; v0 < nVec; v0 += kMgBlock) {
+    const int n = std::min(kMgBlock, nVec - v0);
+    const unsigned all = (1u << n) - 1u;
+    const MugiqHipSpinorField *x = x_h + v0, *b = b_h + v0;
+    const MgVecs xv = MgSolver::vecs(x, n), bv = MgSolver::vecs(b, n), rv = MgSolver::vecs(r, n);
+    double bn2[kMgBlock], rr[kMgBlock];
+    // x = 0, r = b, ||b||^2
+    if ((st = S.fine.axpby(xv, nullptr, 0.0, nullptr, 0.0, n, all))) return st;
+    if ((st = S.fine.axpby(rv, &bv, 1.0, nullptr, 0.0, n, all))) return st;
+    if ((st = S.fine.dot2(bv, bv, n, all, kMgFinRaw, 0.0))) return st;
+    if ((st = S.fetch(sums, &reads))) return st;
+    unsigned active = 0;
+    for (int i = 0; i < n; i++) {
+      bn2[i] = rr[i] = sums[4 * i + 2];
+      iters_out[v0 + i] = 0;
+      if (bn2[i] > 0.0 && !(rr[i] <= tol2 * bn2[i])) active |= 1u << i;
+    }
+    int k = 0;
+    for (int it = 0; it < param->maxIter && active; it++) {
+      MugiqHipSpinorField p[kMgBlock], q[kMgBlock];
+      for (int i = 0; i < n; i++) {
+        p[i] = S.fine_dir(S.fine.P, k, i);
+        q[i] = S.fine_dir(S.fine.Q, k, i);
+      }
+      if ((st = S.precondition(p, r, n, active))) return st;
+      if ((st = S.apply_M(q, p, n, active))) return st;
+      if ((st = S.fine.gcr_step(k, xv, rv, false, false, true, n, active))) return st;
+      if ((st = S.fetch(sums, &reads))) return st;
+      unsigned next = active;
+      for (int i = 0; i < n; i++) {
+        if (!((active >> i) & 1u)) continue;
+        rr[i] = sums[4 * i];
+        if (history_out) history_out[(size_t)(v0 + i) * historyStride + iters_out[v0 + i]] = std::sqrt(rr[i] / bn2[i]);
+        iters_out[v0 + i]++;
+        if (rr[i] <= tol2 * bn2[i]) next &= ~(1u << i);
+      }
+      active = next;
+      if (++k == nK) k = 0;  // restart: the directions are cleared
+    }
+    // the true residual ||b - M x|| / ||b||, with one more application
+    if ((st = S.apply_M(S.t, x, n, all))) return st;
+    const MgVecs tv = MgSolver::vecs(S.t, n);
+    if ((st = S.fine.axpby(tv, &bv, 1.0, &tv, -1.0, n, all))) return st;
+    if ((st = S.fine.dot2(tv, tv, n, all, kMgFinRaw, 0.0))) return st;
+    if ((st = S.fetch(sums, &reads))) return st;
+    for (int i = 0; i < n; i++) {
+      relres_out[v0 + i] = bn2[i] > 0.0 ? std::sqrt(sums[4 * i + 2] / bn2[i]) : 0.0;
+      if (bn2[i] > 0.0 && !(rr[i] <= tol2 * bn2[i])) allConverged = false;
+    }
+  }
+  if (hostReads_out) *hostReads_out = reads;
+  if (!allConverged)
+    return set_error(MUGIQ_HIP_ERROR_NOT_CONVERGED,
+                     "%s: not every right-hand side reached tol = %g within maxIter = %d (x, iters_out, relres_out and history_out are filled)", who, param->tol,
+                     param->maxIter);
+  return MUGIQ_HIP_SUCCESS;
+}
+
+}  // extern "C"

@@ -18,6 +18,7 @@ MUGIQ_EIG_OPERATOR_M, MUGIQ_EIG_OPERATOR_Mdag, MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_E
 STATUS_NOT_CONVERGED = 5  # MUGIQ_HIP_ERROR_NOT_CONVERGED
 
 SolveInfo = collections.namedtuple("SolveInfo", "iters relres converged")
+MgSolveInfo = collections.namedtuple("MgSolveInfo", "iters relres converged history hostReads")
 
 
 def _stream():
@@ -186,6 +187,64 @@ def wilsonSolve(b, gauge, kappa, eVecs=(), sigmas=(), tol=1e-10, maxIter=1000, c
     return x, SolveInfo(np.array(iters), np.array(relres), st == 0)
 
 
+def mgSolveParam(**param):
+    """MugiqHipMgSolveParam: the defaults of mugiq_hip_mg_solve_param_default (tol 1e-10, maxIter 1000, nKrylov 16, nuPre 0, nuPost 4,
+    omega 1.0, coarseIters 8 -- first guesses, not tuned) with the given members replaced."""
+    p = _lib.MgSolveParam()
+    _lib.check(_lib.load().mugiq_hip_mg_solve_param_default(ctypes.byref(p)))
+    names = [n for n, _ in _lib.MgSolveParam._fields_]
+    for k, v in param.items():
+        if k not in names:
+            raise _lib.MugiqHipError("mgSolveParam: no parameter %r (have %s)" % (k, ", ".join(names)))
+        setattr(p, k, float(v) if k in ("tol", "omega") else int(v))
+    return p
+
+
+def mgPrecondition(z, r, gauge, kappa, transfer, coarseOp, clover=None, comm=None, **param):
+    """z_i = K(r_i): one two-grid cycle (MR smoothing, coarse-grid correction by GCR on the explicit coarse operator) for lists of fp64
+    SpinorFields (mugiq_hip_mg_precondition).  param: members of MugiqHipMgSolveParam (nuPre, nuPost, omega, coarseIters)."""
+    z, r = list(z), list(r)
+    if len(z) != len(r) or not r:
+        raise _lib.MugiqHipError("mgPrecondition: %d z and %d r vectors (need the same number, at least one)" % (len(z), len(r)))
+    keep = []
+    p, g, t, o = mgSolveParam(**param), gauge.desc(), transfer.desc(), coarseOp.desc()
+    _lib.check(_lib.load().mugiq_hip_mg_precondition(desc_array(z), desc_array(r), len(r), ctypes.byref(g), _clover_ptr(clover, keep), float(kappa),
+                                                     ctypes.byref(t), ctypes.byref(o), ctypes.byref(p), _comm_ptr(comm, keep), _stream()))
+
+
+def mgSolve(b, gauge, kappa, transfer, coarseOp, clover=None, x=None, allow_unconverged=False, comm=None, **param):
+    """x_r = M^-1 b_r by flexible GCR preconditioned with the two-grid cycle of mgPrecondition (mugiq_hip_mg_solve); transfer: the
+    finest-level Transfer, coarseOp: the CoarseOperator computeCoarseOperator built from it for this gauge, clover and kappa.  param:
+    members of MugiqHipMgSolveParam (tol, maxIter, nKrylov, nuPre, nuPost, omega, coarseIters).  Returns (x, MgSolveInfo(iters, relres,
+    converged, history, hostReads)): history[r] the recursive relative residuals of right-hand side r, one per iteration; hostReads the
+    blocking reads the call made.  x: new fp64 fields laid out like b unless given.  A right-hand side that does not reach tol within
+    maxIter raises MugiqHipError (status 5) unless allow_unconverged."""
+    b = list(b)
+    if not b:
+        raise _lib.MugiqHipError("mgSolve: no right-hand side")
+    if x is None:
+        x = [SpinorField(f.X, 8, f.order, f.stride - f.volumeCB, device=f.device) for f in b]
+    x = list(x)
+    n = len(b)
+    if len(x) != n:
+        raise _lib.MugiqHipError("mgSolve: %d x and %d b vectors" % (len(x), n))
+    keep = []
+    p, g, t, o = mgSolveParam(**param), gauge.desc(), transfer.desc(), coarseOp.desc()
+    stride = max(int(p.maxIter), 1)
+    iters = (ctypes.c_int * n)()
+    relres = (ctypes.c_double * n)()
+    hist = (ctypes.c_double * (n * stride))()
+    reads = ctypes.c_int(0)
+    st = _lib.load().mugiq_hip_mg_solve(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), ctypes.byref(t),
+                                        ctypes.byref(o), ctypes.byref(p), iters, relres, hist, stride, ctypes.byref(reads), _comm_ptr(comm, keep),
+                                        _stream())
+    if st != 0 and not (st == STATUS_NOT_CONVERGED and allow_unconverged):
+        _lib.check(st)
+    it = np.array(iters)
+    h = np.array(hist).reshape(n, stride)
+    return x, MgSolveInfo(it, np.array(relres), st == 0, [h[i, :it[i]].copy() for i in range(n)], int(reads.value))
+
+
 def format_evals(evals, evals_quda, residuals, sigmas=None):
     """The lines of Eigsolve_Mugiq::printEvals (lib/eigsolve_mugiq.cpp:325-333), character for character."""
     lines = ["", "Eigsolve_Mugiq - Eigenvalues:"]
@@ -250,3 +309,10 @@ class Eigsolve_Mugiq:
                 raise _lib.MugiqHipError("Eigsolve_Mugiq.solve: no sigmas (call computeEvals first or pass them)")
             ev = self.eVecs
         return wilsonSolve(b, self.gauge, self.kappa, ev, sg, tol, maxIter, self.comm, x, allow_unconverged, self.clover)
+
+    def solveMG(self, b, x=None, allow_unconverged=False, **param):
+        """M^-1 b by the two-grid preconditioned GCR (mgSolve) for objects built with transfer= and coarseOp=: their gauge field, clover
+        field, kappa, transfer and coarse operator.  Returns (x, MgSolveInfo)."""
+        if self.transfer is None or self.coarseOp is None or isinstance(self.transfer, (list, tuple)):
+            raise _lib.MugiqHipError("status 2: Eigsolve_Mugiq.solveMG: needs an object built with one finest-level transfer= and its coarseOp=")
+        return mgSolve(b, self.gauge, self.kappa, self.transfer, self.coarseOp, self.clover, x, allow_unconverged, self.comm, **param)

@@ -397,6 +397,25 @@ class Loop_Mugiq:
                                         allow_unconverged, clover)
         return x
 
+    def solveMG(self, b, kappa, coarseOp, clover=None, x=None, allow_unconverged=False, **param):
+        """x_r = M^-1 b_r by the two-grid preconditioned GCR (mgSolve) with this coarse loop object's gauge field, transfer and stream;
+        coarseOp: the CoarseOperator of that transfer at this kappa (and clover).  Returns the list x; iteration counts, true residuals,
+        histories and host reads are kept in self.lastSolve.  Status 2 (UNSUPPORTED) for fine-level and two-sided loop objects and for
+        hierarchies of more than one level, status 1 for a loop object created without a gauge field.  An MG set then reads
+        x = loop.solveMG(xi, kappa, coarseOp); loop.deflateCoarse(x, xi)."""
+        from .eigsolve import mgSolve
+        if self._transfer is None or self.eVecsLeft is not None:
+            raise _lib.MugiqHipError("status 2: Loop_Mugiq.solveMG: coarse (MG) loop objects only")
+        tr = self._transfer
+        if isinstance(tr, (list, tuple)):
+            if len(tr) != 1:
+                raise _lib.MugiqHipError("status 2: Loop_Mugiq.solveMG: one coarse level only (the loop has %d transfers)" % len(tr))
+            tr = tr[0]
+        if self._params.gauge is None:
+            raise _lib.MugiqHipError("status 1: Loop_Mugiq.solveMG: the loop object was created without a gauge field")
+        x, self.lastSolve = mgSolve(b, self._params.gauge, kappa, tr, coarseOp, clover, x, allow_unconverged, self.comm, **param)
+        return x
+
     def computeCoarseLoop(self):
         """lib/loop_mugiq.cpp:439-525"""
         _lib.check(_lib.load().mugiq_hip_loop_compute(self._handle))
