@@ -299,6 +299,7 @@ size_t scalar_bytes() { return align256(sizeof(double) * ((size_t)kMgBlock * kMg
 struct MgLevel {
   MgLayout L;
   int nb = 0, nGroups = 0;
+  bool wide = false;  // MUGIQ_HIP_DEBUG_WIDE_INDEX, as the call found it (MgSolver::reserve)
   int64_t vecElems = 0;
   Z *P = nullptr, *Q = nullptr;  // nDir x nb vectors each
   double *partial = nullptr, *coef = nullptr, *sc = nullptr, *res = nullptr;  // shared by both levels: the stream orders their passes
@@ -315,7 +316,7 @@ struct MgLevel {
     res = sc + 4 * kMgBlock;
   }
   Z *dir(Z *base, int j, int v) const { return base + ((int64_t)j * nb + v) * vecElems; }
-  bool narrow() const { return L.total < (int64_t(1) << 31); }
+  bool narrow() const { return !wide && L.total < (int64_t(1) << 31); }
   dim3 grid(int n) const { return dim3(nGroups, n); }
 
   int final_sum(int nUsed, unsigned active, int mode, double omega) const {
@@ -434,6 +435,7 @@ struct MgSolver {
     cur += scalar_bytes();
     fine.stream = coarse.stream = stream;
     fine.nb = coarse.nb = nb;
+    fine.wide = coarse.wide = debug_wide_index_asked();
     fine.set_layout(fine_layout(like));
     fine.vecElems = (int64_t)(fb / sizeof(Z));
     fine.P = reinterpret_cast<Z *>(cur);

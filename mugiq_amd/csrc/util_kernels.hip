@@ -181,6 +181,10 @@ int debug_poison_lds_if_asked(hipStream_t stream) {
   if (!e || atoi(e) == 0) return MUGIQ_HIP_SUCCESS;
   return mugiq_hip_debug_poison_lds(stream);
 }
+bool debug_wide_index_asked() {
+  const char *e = getenv("MUGIQ_HIP_DEBUG_WIDE_INDEX");
+  return e && atoi(e) != 0;
+}
 }  // namespace mugiq
 
 extern "C" {

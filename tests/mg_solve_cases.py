@@ -5,6 +5,7 @@ import functools
 
 import numpy as np
 
+import coarse_op_cases as coc
 import mg_solve_ref as mgr
 import restrict_ref as rr
 import wilson_ref as wr
@@ -23,6 +24,17 @@ SOLVES = [("hot", 16, 4), ("smooth", 16, 4), ("hot", 4, 2), ("smooth", 4, 4)]
 # right-hand side: with null vectors from the low modes and with random ones, as recorded on the machine that wrote this (another BLAS may
 # move a count by one; test_coarse_space_condition asserts low <= 0.7 random and prints what it finds)
 SMOOTH_COUNTS = {"low": 45, "random": 90}
+# (nuPre, nuPost, coarseIters) of the K comparisons on the device, and the sets beyond them (tests/test_gpu_mg_solve_scale.py): omega
+# other than 1, 16 coarse steps (15 coefficients of the multi-dot), a single coarse step, no coarse step
+K_PARAMS = [dict(nuPre=0, nuPost=2, coarseIters=4), dict(nuPre=1, nuPost=1, coarseIters=8), dict(nuPre=0, nuPost=0, coarseIters=4),
+            dict(nuPre=2, nuPost=0, coarseIters=0)]
+EDGE_PARAMS = [dict(nuPre=1, nuPost=1, omega=0.85, coarseIters=16), dict(nuPre=3, nuPost=0, omega=1.3, coarseIters=1),
+               dict(nuPre=0, nuPost=2, omega=0.5, coarseIters=0)]
+# fine X, aggregate, n_vec on the fields of coarse_op_cases.  LARGE: 98 304 complex elements per vector, so that the first 128 of the 256
+# workgroups of a Krylov kernel make a second trip of their grid-stride loop.  RAGGED: volumeCB 432, 10 368 = 40.5 x 256 elements, rows
+# of 432 (FLOAT2: 6.75 waves) and 864
+LARGE = ((16, 8, 8, 8), (4, 4, 4, 4), 8)
+RAGGED = ((6, 6, 6, 4), (3, 3, 3, 2), 4)
 
 
 def _c(rng, shape):
@@ -106,6 +118,20 @@ def rhs(field, n=3):
 def dense_solution(field, i):
     b = rhs(field)[i]
     return np.linalg.solve(dense_M(field), b.reshape(-1)).reshape(b.shape)
+
+
+@functools.lru_cache(maxsize=None)
+def shape_problem(X, bs, nvec, clover=False, chain=False):
+    """the problem on the links, clover blocks and (random) null vectors of coarse_op_cases; chain: A_c = R M P, nothing is built"""
+    Uo, blocks = coc.links(X)
+    cls = mgr.ChainProblem if chain else mgr.Problem
+    return cls(X, Uo, coc.KAPPA, coc.null_vectors(X, bs, nvec)[0], bs, coc.dense12(blocks) if clover else None)
+
+
+@functools.lru_cache(maxsize=None)
+def shape_rhs(X, n=9):
+    rng = np.random.default_rng(7900 + sum(X))
+    return tuple(_c(rng, (2, int(np.prod(X)) // 2, 4, 3)) for _ in range(n))
 
 
 def _margin_ok(hist, tol):

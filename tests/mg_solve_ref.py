@@ -37,6 +37,19 @@ class Problem:
         return cor.apply_Mc(self.Mc, w, self.Xc)
 
 
+class ChainProblem(Problem):
+    """The same problem with A_c w = R M P w applied as that chain, so that no coarse matrices are built (coarse_op_ref.build takes
+    seconds beyond 8^4).  test_coarse_op_cpu.py pins the explicit matrices to this chain; test_mg_solve_cpu.py holds the K of both."""
+
+    def __init__(self, X, Uo, kappa, V, bs, A_eo=None):
+        self.X, self.Uo, self.kappa, self.V, self.bs, self.A_eo = tuple(X), Uo, kappa, V, tuple(bs), A_eo
+        self.Xc = tuple(X[d] // bs[d] for d in range(4))
+        self.Mc = None
+
+    def A_c(self, w):
+        return self.R(self.M(self.P(w)))
+
+
 def mr_step(M, z, s, omega):
     t = M(s)
     d = np.vdot(t, t).real

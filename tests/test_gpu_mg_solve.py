@@ -8,12 +8,12 @@ import functools
 
 import numpy as np
 import pytest
-import torch
 
 import coarse_op_cases as cases
 import coarse_op_ref as cor
 import mg_solve_cases as mgc
 import mg_solve_ref as mgr
+from mg_solve_fields import field as _field, pads_are_nan as _pads_are_nan, same as _same
 from util import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -21,44 +21,12 @@ pytestmark = pytest.mark.gpu
 KAPPA = cases.KAPPA
 K_SHAPES = [cases.SHAPES[0], cases.SHAPES[1], cases.SHAPES[2], cases.SHAPES[5],
             ((8, 8, 8, 8), (4, 4, 4, 4), 8)]            # reductions over several workgroups on the fine level, one on the coarse level
-K_PARAMS = [dict(nuPre=0, nuPost=2, coarseIters=4), dict(nuPre=1, nuPost=1, coarseIters=8), dict(nuPre=0, nuPost=0, coarseIters=4),
-            dict(nuPre=2, nuPost=0, coarseIters=0)]
+K_PARAMS = mgc.K_PARAMS
 NRHS = 9                                                 # a block of 8 and one more
-
-
-def _bits(t):
-    return t.view(torch.float64).view(torch.int64)
-
-
-def _same(a, b):
-    return bool(torch.equal(_bits(a.data), _bits(b.data)))
 
 
 def _c(rng, shape):
     return rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
-
-
-NAN = complex(float("nan"), float("nan"))
-
-
-def _pads(f):
-    return f.data.view(2, 12, f.stride)[:, :, f.volumeCB:] if f.order == 2 else f.data.view(2, 6, f.stride, 2)[:, :, f.volumeCB:]
-
-
-def _field(hip, X, v=None, order=2, pad=0):
-    """a field holding v with NaN pads, or (v None) an output field: zero without pads, NaN everywhere with them"""
-    f = hip.SpinorField(X, 8, order, pad)
-    if v is not None:
-        f.set_logical(v)
-        if pad:
-            _pads(f)[...] = NAN
-    elif pad:
-        f.data.fill_(NAN)
-    return f
-
-
-def _pads_are_nan(f):
-    return bool(torch.isnan(_pads(f).real).all()) and bool(torch.isnan(_pads(f).imag).all())
 
 
 @functools.lru_cache(maxsize=None)

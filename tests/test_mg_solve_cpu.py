@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import coarse_op_cases as coc
 import mg_solve_cases as cases
 import mg_solve_ref as mgr
 import wilson_ref as wr
@@ -64,6 +65,51 @@ def test_K_is_homogeneous(param):
         assert rel_err(mgr.K(P, c * r, **param), c * z) < 1e-13
     assert max(rel_err(mgr.K(P, mgr.ulp_perturbed(r, s), **param), z) for s in (1, 2, 3)) < 1e-14
     assert not np.any(mgr.K(P, np.zeros_like(r), **param))               # the guards: no 0 / 0
+
+
+@pytest.mark.parametrize("shape", [cases.RAGGED, coc.SHAPES[0]], ids=["ragged", "4x4x4x4"])
+@pytest.mark.parametrize("clover", [False, True])
+def test_chain_variant_has_the_K_of_the_explicit_matrices(shape, clover):
+    """mg_solve_ref.ChainProblem (A_c = R M P applied as a chain, what the GPU tests compare with where the matrices take too long to
+    build) against mg_solve_ref.Problem on the explicit matrices: K of every parameter set the GPU tests use, to 1e-13 of the max norm
+    (measured 9e-16: the two coarse operators differ by rounding, and K moves by less than 1e-14 under 1-ulp perturbations); and K(0) = 0
+    exactly in both -- d > 0.0 fails in the MR step, nu == 0.0 in the GCR step."""
+    pe, pc = cases.shape_problem(*shape, clover=clover), cases.shape_problem(*shape, clover=clover, chain=True)
+    assert pc.Mc is None and pe.Xc == pc.Xc
+    r = cases.shape_rhs(shape[0])[0]
+    for prm in cases.K_PARAMS + cases.EDGE_PARAMS:
+        z = mgr.K(pe, r, **prm)
+        e = rel_err(mgr.K(pc, r, **prm), z)
+        assert np.all(np.isfinite(z)) and e < 1e-13, (prm, e)
+        assert max(rel_err(mgr.K(pc, mgr.ulp_perturbed(r, s), **prm), z) for s in (1, 2, 3)) < 1e-14
+        for p in (pe, pc):
+            z0 = mgr.K(p, np.zeros_like(r), **prm)
+            assert np.all(z0 == 0.0), prm                                  # (a NaN is != 0.0)
+
+
+def test_new_shapes_launch_as_the_scale_tests_say():
+    """The arithmetic the shapes of tests/test_gpu_mg_solve_scale.py were chosen by, against the constants of csrc/mg_solve.hip."""
+    src = open(os.path.join(ROOT, "mugiq_amd", "csrc", "mg_solve.hip")).read()
+    assert "constexpr int kMgThreads = 256;" in src and "constexpr int kMgMaxGroups = 256;" in src and "constexpr int kMgSlots = 32;" in src
+    total = lambda X: 24 * int(np.prod(X)) // 2                          # noqa: E731  complex elements of a fine vector
+    assert total(cases.LARGE[0]) == 98304 and 256 * 256 < total(cases.LARGE[0]) < 2 * 256 * 256      # a second trip for some workgroups only
+    assert total((8, 8, 8, 8)) < 256 * 256                                # the largest field of test_gpu_mg_solve.py: one trip
+    vcb = int(np.prod(cases.RAGGED[0])) // 2
+    assert vcb == 432 and total(cases.RAGGED[0]) % 256 == 128 and vcb % 64 != 0 and (2 * vcb) % 64 != 0
+    X, bs, nvec = coc.SHAPES[5]
+    assert 2 * 2 * nvec * (int(np.prod(X)) // int(np.prod(bs)) // 2) == 1536 and 2 * 15 <= 32
+
+
+def test_wide_index_switch_is_read_and_documented(hip):
+    """MUGIQ_HIP_DEBUG_WIDE_INDEX: the built library holds the name (it calls getenv with it), narrow() of csrc/mg_solve.hip depends on it,
+    and internal.h, DESIGN.md and README.md name it."""
+    name = "MUGIQ_HIP_DEBUG_WIDE_INDEX"
+    hip._lib.load()
+    assert name.encode() in open(hip._lib.LIB_PATH, "rb").read()
+    src = open(os.path.join(ROOT, "mugiq_amd", "csrc", "mg_solve.hip")).read()
+    assert "debug_wide_index_asked()" in src and "return !wide && L.total < (int64_t(1) << 31);" in src
+    for doc in (os.path.join("mugiq_amd", "csrc", "internal.h"), "DESIGN.md", "README.md"):
+        assert name in open(os.path.join(ROOT, doc)).read(), doc
 
 
 def test_coarse_space_condition():
