@@ -381,7 +381,9 @@ typedef struct MugiqHipCoarseField_s {
 /* One level of QUDA's Transfer: the block-orthonormal null vectors V as a field of the FINER side with a packed vector
  * index.  Finest level: FieldOrderCB<Float,4,3,n_vec,FLOAT2>, complex index of V(parity, x_cb; s, c, j) =
  * parity*parity_offset + ((3*s + c)*nVec + j)*stride + x_cb, spinBlockSize 2.  Coarse -> coarse levels: see
- * mugiq_hip_prolongate_coarse_batched.  (Producing V is QUDA's MG setup: out of scope.) */
+ * mugiq_hip_prolongate_coarse_batched.  V comes from QUDA's MG setup or from the engine's own (mugiq_hip_mg_setup, below: null vectors
+ * by an early-stopped CG, packed by mugiq_hip_transfer_set_vectors and made block-orthonormal by mugiq_hip_block_orthonormalize); the
+ * two are interchangeable, and mugiq_hip_transfer_orthonormality checks either. */
 typedef struct MugiqHipTransfer_s {
   const void *V;
   int precision;       /* 4 | 8 */
@@ -831,6 +833,82 @@ int mugiq_hip_mg_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField
                        const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *coarseOp,
                        const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out, double *history_out, int historyStride,
                        int *hostReads_out, const MugiqHipComm *comm, void *stream);
+
+/* ---- MG setup (new; csrc/mg_setup.hip): what QUDA's newMultigridQuda does before MG_Mugiq / Eigsolve_Mugiq see a transfer
+ * (tests/loop.cpp:347-365: setup_inv, setup_maxiter, setup_tol, num_setup_iter, n_block_ortho) -- from a gauge field to V and M_c.
+ *
+ * Block orthonormalisation, in place on V (QUDA's BlockOrthogonalize).  For every aggregate and every coarse spin S (finest level: the
+ * chirality s / spinBlockSize) let B be the m x n_vec block of V whose rows are all (x in the aggregate; s with s / spinBlockSize = S; c):
+ * m = 6 aggVol on the finest level, m = nColor aggVol on a coarse -> coarse level.  For pass < nPasses, for j = 0 .. n_vec - 1:
+ *   c_i = <q_i, b_j> for all i < j, taken from the un-updated b_j (classical Gram-Schmidt, one reduction round per 16 columns: the idiom
+ *   of GCRfix above);  b_j -= sum_i c_i q_i;  nu_j = ||b_j||;  q_j = b_j / nu_j;  nu_j = 0: the column is stored as exact zeros and counted.
+ * The result is the Q of the thin QR with positive real diagonal, columns in their given order.  nPasses: 1 .. 4 (QUDA's n_block_ortho
+ * defaults to 1; one classical pass loses orthogonality as kappa(B)^2 eps, the second restores it: "twice is enough").
+ * Arithmetic and sums in fp64 for either storage precision of V, one rounding on the store of a column (every pass stores; the finished
+ * columns q_i are read as stored).  No atomics; the order of every sum is fixed by the level geometry alone (rows in the lexicographic
+ * order of the LOCAL site coordinates in the aggregate, x fastest, spin-colour rows outermost): the call is bitwise reproducible, and the
+ * bits of a block depend neither on the other blocks nor on the lattice the aggregate sits in.  Pads are never read or written.
+ * info (may be NULL): minPivotRatio = the minimum over blocks and columns of the FIRST pass's nu_j / ||b_j as given|| (0 for a zero
+ * column), zeroColumns = the columns stored as zeros; one host read at the end.  minPivotRatio < rankTol: MUGIQ_HIP_ERROR_INVALID_ARGUMENT
+ * after filling V and info all the same; rankTol = 0 never fails.  A NaN is not turned into a zero column: it spreads through its own
+ * column and the later columns of its block, which come back as NaN, minPivotRatio is NaN (which fails every rankTol > 0), and
+ * zeroColumns does not count it.
+ * transfer: either layout MugiqHipTransfer describes, checked before any device work as mugiq_hip_prolongate_batched (spinBlockSize 2)
+ * or mugiq_hip_prolongate_coarse_batched (spinBlockSize 1) check it.  The colours of the finer side of a coarse -> coarse V are not in
+ * the descriptor: they are taken from parity_offset = 2 nColor n_vec stride, which must hold exactly.  n_vec <= m;  a column of m rows
+ * in fp64 and the row table (24 m bytes) must fit the LDS of a workgroup (m <= 6 600 or so; MUGIQ_HIP_ERROR_UNSUPPORTED beyond). */
+typedef struct MugiqHipBlockOrthoInfo_s {
+  double minPivotRatio;
+  int zeroColumns;
+} MugiqHipBlockOrthoInfo;
+int mugiq_hip_block_orthonormalize(const MugiqHipTransfer *transfer /* V is written */, int nPasses, double rankTol,
+                                   MugiqHipBlockOrthoInfo *info, void *stream);
+/* out[0] = max over the blocks of max_ij |(B^dag B - 1)_ij|, by the same fixed-order fp64 sums: the check a user runs on a V they were
+ * handed (in the spirit of computeEvals and the plaquette).  One host read. */
+int mugiq_hip_transfer_orthonormality(const MugiqHipTransfer *transfer, double *out, void *stream);
+/* V(x; s, c, j) = vecs_h[j](x; s, c) for all j < nVec = transfer->nVec, and its inverse for one column.  transfer: a finest-level one;
+ * the vectors: its lattice, either precision (converted on the way if it differs from V's), FLOAT2 | FLOAT4, any stride; pads of
+ * neither side are read or written. */
+int mugiq_hip_transfer_set_vectors(const MugiqHipTransfer *transfer /* V is written */, const MugiqHipSpinorField *vecs_h, int nVec, void *stream);
+int mugiq_hip_transfer_get_vector(const MugiqHipSpinorField *vec, const MugiqHipTransfer *transfer, int j, void *stream);
+
+/* The setup driver: host code over the entry points above and below.  start_h: nVec = transfer->nVec fp64 start vectors the caller
+ * fills (e.g. seeded Gaussian noise; there is no device RNG).  Null vector j is QUDA's "M x = 0 from a random guess":
+ *   b = M start_j;  e = mugiq_hip_wilson_clover_solve(b) stopped at setupMaxIter or setupTol (MUGIQ_HIP_ERROR_NOT_CONVERGED is expected
+ *   and absorbed);  v_j = start_j - e,
+ * in blocks of 8.  Then V = pack(v), mugiq_hip_block_orthonormalize(nBlockOrtho, rankTol) and, if coarseOp is given,
+ * mugiq_hip_compute_coarse_operator.  refineCycles > 0 (QUDA's num_setup_iter > 1; needs coarseOp, MUGIQ_HIP_ERROR_INVALID_ARGUMENT
+ * otherwise, and fp64): each cycle v_j -= mugiq_hip_mg_solve(M v_j) with the current V and M_c, stopped after refineIters outer
+ * iterations (defaults of mugiq_hip_mg_solve_param_default otherwise; tol = setupTol, nKrylov = refineIters), then repack,
+ * re-orthonormalise and rebuild M_c.  A rank failure of the orthonormalisation ends the setup with its status, V and info filled.
+ * One level and one domain, as for the coarse operator: a comm with more than one rank or a partitioned axis is
+ * MUGIQ_HIP_ERROR_UNSUPPORTED before any device work.  The start vectors are only read.  Work memory: nVec + 16 fine fp64 vectors,
+ * allocated for the call and freed, plus what the calls it makes take from the per-stream workspace.
+ * Defaults: setupMaxIter 500 and setupTol 5e-6 mirror tests/loop.cpp:349-350;  nBlockOrtho 2, rankTol 1e-8, refineCycles 0 and
+ * refineIters 4 are first guesses, NOT tuned. */
+typedef struct MugiqHipMgSetupParam_s {
+  int setupMaxIter;  /* >= 0 CG iterations per null vector */
+  double setupTol;   /* > 0: tolerance of the CG (and of the refinement solves) */
+  int nBlockOrtho;   /* 1 .. 4 passes of the block orthonormalisation */
+  double rankTol;    /* 0 .. 1: see mugiq_hip_block_orthonormalize */
+  int refineCycles;  /* 0 .. 16 */
+  int refineIters;   /* 1 .. 16 outer iterations of a refinement solve */
+} MugiqHipMgSetupParam;
+typedef struct MugiqHipMgSetupInfo_s {
+  int cgIters[64];        /* CG iterations of null vector j */
+  double minPivotRatio;   /* of the last orthonormalisation */
+  int zeroColumns;
+  double orthonormality;  /* mugiq_hip_transfer_orthonormality of the final V */
+  int hostReads;          /* blocking reads the call COUNTED: one per orthonormalisation, one for the final check, and those
+                             mugiq_hip_mg_solve reports for the refinement solves.  The CG's reads are not in it */
+  int cgHostReadsEstimate; /* NOT counted: mugiq_hip_wilson_clover_solve reports no reads, so this is what its source makes for the
+                             iteration counts above -- 2 max(cgIters) + 3 per block of 8 -- and goes stale if that solver changes */
+} MugiqHipMgSetupInfo;
+int mugiq_hip_mg_setup_param_default(MugiqHipMgSetupParam *p);
+int mugiq_hip_mg_setup(const MugiqHipTransfer *transfer /* V is written */, MugiqHipCoarseOperator *coarseOp /* may be NULL */,
+                       const MugiqHipSpinorField *start_h, int nVec, const MugiqHipGaugeField *gauge,
+                       const MugiqHipCloverField *clover /* may be NULL */, double kappa, const MugiqHipMgSetupParam *p,
+                       MugiqHipMgSetupInfo *info, const MugiqHipComm *comm /* NULL: one domain */, void *stream);
 
 /* What Displace asks of QUDA's ColorSpinorField for its auxiliary vector (lib/displace.cpp:26-30: ColorSpinorField::Create
  * with QUDA_ZERO_FIELD_CREATE and setPrecision(coarsePrec_); :42,:50-51: operator=; :59: blas::zero), for hosts that do not

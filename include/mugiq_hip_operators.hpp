@@ -234,6 +234,36 @@ inline bool mgSolve(const std::vector<ColorSpinorField> &x, const std::vector<Co
   }
   return st == 0;
 }
+// ---- the MG setup (csrc/mg_setup.hip; new) ----
+// Orthonormalise the columns of V inside every (aggregate, coarse spin) block, in place (mugiq_hip_block_orthonormalize).  Returns the
+// info; a minPivotRatio below rankTol throws (status 1) with V filled all the same
+inline MugiqHipBlockOrthoInfo blockOrthonormalize(const MugiqHipTransfer &transfer, int nPasses = 2, double rankTol = 0.0, void *stream = nullptr) {
+  MugiqHipBlockOrthoInfo info{};
+  check(mugiq_hip_block_orthonormalize(&transfer, nPasses, rankTol, &info, stream));
+  return info;
+}
+// max over the blocks of max |B^dag B - 1| (mugiq_hip_transfer_orthonormality)
+inline double transferOrthonormality(const MugiqHipTransfer &transfer, void *stream = nullptr) {
+  double out = 0.0;
+  check(mugiq_hip_transfer_orthonormality(&transfer, &out, stream));
+  return out;
+}
+// MugiqHipMgSetupParam with the defaults of mugiq_hip_mg_setup_param_default (setupMaxIter and setupTol as in tests/loop.cpp, the rest
+// first guesses)
+struct MgSetupParam : MugiqHipMgSetupParam {
+  MgSetupParam() { check(mugiq_hip_mg_setup_param_default(this)); }
+};
+// V of `transfer` (written in place) and, if coarseOp is given, its coarse operator from the gauge field and the caller's start vectors
+// (mugiq_hip_mg_setup)
+inline MugiqHipMgSetupInfo mgSetup(const MugiqHipTransfer &transfer, CoarseOperator *coarseOp, const std::vector<ColorSpinorField> &start,
+                                   const GaugeField &gauge, const MugiqHipCloverField *clover, double kappa, const MgSetupParam &param = MgSetupParam(),
+                                   const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (start.empty()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgSetup: no start vectors");
+  MugiqHipMgSetupInfo info{};
+  check(mugiq_hip_mg_setup(&transfer, coarseOp ? coarseOp->desc() : nullptr, start.data(), (int)start.size(), &gauge, clover, kappa, &param, &info, comm,
+                           stream));
+  return info;
+}
 // x_r = M^-1 b_r by CG on the normal equations from the low-mode start (mugiq_hip_wilson_solve).  Returns false where a right-hand
 // side did not reach tol within maxIter (x, iters and relres are filled all the same); every other failure throws.
 inline bool wilsonSolve(const std::vector<ColorSpinorField> &x, const std::vector<ColorSpinorField> &b, const GaugeField &gauge, double kappa,

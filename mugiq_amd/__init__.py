@@ -30,7 +30,7 @@ from .comm import GridComm, RcclComm  # noqa: E402
 from .displace import Displace, DISPLACE_TYPE_COVARIANT  # noqa: E402
 from .eigsolve import (  # noqa: E402
     Eigsolve_Mugiq, wilsonApply, computeEvals, computeEvalsCoarse, computeCoarseOperator, coarseApply, projectVector, wilsonSolve, SolveInfo,
-    mgSolve, mgPrecondition, mgSolveParam, MgSolveInfo,
+    mgSolve, mgPrecondition, mgSolveParam, MgSolveInfo, mgSetup, mgSetupParam, mgStartVectors, MgSetupInfo,
     MUGIQ_EIG_OPERATOR_M, MUGIQ_EIG_OPERATOR_Mdag, MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H,
 )
 

@@ -71,6 +71,23 @@ class MgSolveParam(ctypes.Structure):
                 ("omega", ctypes.c_double), ("coarseIters", ctypes.c_int)]
 
 
+class BlockOrthoInfo(ctypes.Structure):
+    """MugiqHipBlockOrthoInfo (include/mugiq_hip.h)."""
+    _fields_ = [("minPivotRatio", ctypes.c_double), ("zeroColumns", ctypes.c_int)]
+
+
+class MgSetupParam(ctypes.Structure):
+    """MugiqHipMgSetupParam (include/mugiq_hip.h)."""
+    _fields_ = [("setupMaxIter", ctypes.c_int), ("setupTol", ctypes.c_double), ("nBlockOrtho", ctypes.c_int), ("rankTol", ctypes.c_double),
+                ("refineCycles", ctypes.c_int), ("refineIters", ctypes.c_int)]
+
+
+class MgSetupInfo(ctypes.Structure):
+    """MugiqHipMgSetupInfo (include/mugiq_hip.h)."""
+    _fields_ = [("cgIters", ctypes.c_int * 64), ("minPivotRatio", ctypes.c_double), ("zeroColumns", ctypes.c_int), ("orthonormality", ctypes.c_double),
+                ("hostReads", ctypes.c_int), ("cgHostReadsEstimate", ctypes.c_int)]
+
+
 class ProjectPlan(ctypes.Structure):
     """MugiqHipProjectPlan (include/mugiq_hip.h)."""
     _fields_ = [(n, ctypes.c_int) for n in ("form", "nks", "mb", "nPx", "tChunk", "nChunks", "lastChunk", "tiles", "tilesPerWg",
@@ -233,6 +250,13 @@ SIGNATURES = {
     "mugiq_hip_mg_solve": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
                                           ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(MgSolveParam), _I4, ctypes.POINTER(ctypes.c_double),
                                           ctypes.POINTER(ctypes.c_double), ctypes.c_int, _I4, _VP, _VP]),
+    "mugiq_hip_block_orthonormalize": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.c_int, ctypes.c_double, ctypes.POINTER(BlockOrthoInfo), _VP]),
+    "mugiq_hip_transfer_orthonormality": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.POINTER(ctypes.c_double), _VP]),
+    "mugiq_hip_transfer_set_vectors": (ctypes.c_int, [ctypes.POINTER(TransferDesc), _SP, ctypes.c_int, _VP]),
+    "mugiq_hip_transfer_get_vector": (ctypes.c_int, [_SP, ctypes.POINTER(TransferDesc), ctypes.c_int, _VP]),
+    "mugiq_hip_mg_setup_param_default": (ctypes.c_int, [ctypes.POINTER(MgSetupParam)]),
+    "mugiq_hip_mg_setup": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.POINTER(CoarseOperatorDesc), _SP, ctypes.c_int, _GP, _CP, ctypes.c_double,
+                                          ctypes.POINTER(MgSetupParam), ctypes.POINTER(MgSetupInfo), _VP, _VP]),
     "mugiq_hip_prolongate_batched": (ctypes.c_int, [_SP, ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),
     "mugiq_hip_prolongate_contract_batched": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(CoarseDesc), ctypes.POINTER(ctypes.c_double),
                                                              ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .fields import SpinorField, CoarseOperator, desc_array, coarse_desc_array, transfer_desc_array
+from .fields import SpinorField, CoarseOperator, Transfer, desc_array, coarse_desc_array, transfer_desc_array
 
 # MuGiqEigOperator (include/enum_mugiq.h:22-25 of the reference, values identical) and the extension H = g5 M
 MUGIQ_EIG_OPERATOR_M, MUGIQ_EIG_OPERATOR_Mdag, MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H = range(5)
@@ -19,6 +19,7 @@ STATUS_NOT_CONVERGED = 5  # MUGIQ_HIP_ERROR_NOT_CONVERGED
 
 SolveInfo = collections.namedtuple("SolveInfo", "iters relres converged")
 MgSolveInfo = collections.namedtuple("MgSolveInfo", "iters relres converged history hostReads")
+MgSetupInfo = collections.namedtuple("MgSetupInfo", "cgIters minPivotRatio zeroColumns orthonormality hostReads cgHostReadsEstimate")
 
 
 def _stream():
@@ -245,6 +246,65 @@ def mgSolve(b, gauge, kappa, transfer, coarseOp, clover=None, x=None, allow_unco
     return x, MgSolveInfo(it, np.array(relres), st == 0, [h[i, :it[i]].copy() for i in range(n)], int(reads.value))
 
 
+def mgSetupParam(**param):
+    """MugiqHipMgSetupParam: the defaults of mugiq_hip_mg_setup_param_default (setupMaxIter 500 and setupTol 5e-6 as in the reference's
+    tests/loop.cpp; nBlockOrtho 2, rankTol 1e-8, refineCycles 0, refineIters 4 -- first guesses, not tuned) with the given members replaced."""
+    p = _lib.MgSetupParam()
+    _lib.check(_lib.load().mugiq_hip_mg_setup_param_default(ctypes.byref(p)))
+    names = [n for n, _ in _lib.MgSetupParam._fields_]
+    for k, v in param.items():
+        if k not in names:
+            raise _lib.MugiqHipError("mgSetupParam: no parameter %r (have %s)" % (k, ", ".join(names)))
+        setattr(p, k, float(v) if k in ("setupTol", "rankTol") else int(v))
+    return p
+
+
+def mgStartVectors(X, n_vec, seed=0, order=2, pad=0, device="cuda"):
+    """n_vec fp64 SpinorFields of seeded Gaussian noise (torch.randn with its own generator): the start vectors of mgSetup"""
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    out = []
+    for _ in range(int(n_vec)):
+        f = SpinorField(X, 8, order, pad, device=device)
+        f.data.copy_(torch.view_as_complex(torch.randn(f.data.numel(), 2, dtype=torch.float64, device=f.device, generator=gen)))
+        out.append(f)
+    return out
+
+
+def mgSetup(gauge, kappa, n_vec=24, geo_block_size=(4, 4, 4, 4), start=None, seed=0, clover=None, transfer=None, coarseOp=True, comm=None,
+            **param):
+    """The MG setup on the device (mugiq_hip_mg_setup): null vectors from the start vectors by an early-stopped CG on the normal
+    equations, packed into V, block-orthonormalised, then the explicit coarse operator and, with refineCycles > 0, adaptive refinement by
+    the two-grid solve.  start: n_vec fp64 SpinorFields (default: mgStartVectors(gauge.X, n_vec, seed)); transfer: the finest-level
+    Transfer to fill (default: a new fp64 one on gauge.X with n_vec and geo_block_size); coarseOp: True builds a new CoarseOperator, a
+    CoarseOperator is filled, None / False skips it.  param: members of MugiqHipMgSetupParam.  Returns (Transfer, CoarseOperator or
+    None, MgSetupInfo(cgIters, minPivotRatio, zeroColumns, orthonormality, hostReads, cgHostReadsEstimate)): hostReads are the blocking
+    reads the call counted, cgHostReadsEstimate what the CG, which reports none, makes by its source.  A rank failure (minPivotRatio < rankTol) raises
+    MugiqHipError (status 1)."""
+    if transfer is None:
+        transfer = Transfer(gauge.X, n_vec, geo_block_size, 2, 8, device=gauge.device)
+    if start is None:
+        start = mgStartVectors(transfer.X, transfer.n_vec, seed, device=transfer.device)
+    start = list(start)
+    if coarseOp is True:
+        coarseOp = CoarseOperator(transfer.Xc, transfer.n_vec, transfer.precision, device=transfer.device)
+    elif coarseOp is False:
+        coarseOp = None
+    if coarseOp is not None and not isinstance(coarseOp, CoarseOperator):
+        raise _lib.MugiqHipError("mgSetup: coarseOp must be a CoarseOperator, True or None")
+    keep = []
+    p, g, t = mgSetupParam(**param), gauge.desc(), transfer.desc()
+    o = coarseOp.desc() if coarseOp is not None else None
+    info = _lib.MgSetupInfo()
+    _lib.check(_lib.load().mugiq_hip_mg_setup(ctypes.byref(t), ctypes.byref(o) if o is not None else None, desc_array(start) if start else None,
+                                              len(start), ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), ctypes.byref(p),
+                                              ctypes.byref(info), _comm_ptr(comm, keep), _stream()))
+    if coarseOp is not None:
+        coarseOp.kappa, coarseOp.hasClover = float(o.kappa), bool(o.hasClover)
+    return transfer, coarseOp, MgSetupInfo(np.array(info.cgIters[:len(start)]), float(info.minPivotRatio), int(info.zeroColumns),
+                                           float(info.orthonormality), int(info.hostReads), int(info.cgHostReadsEstimate))
+
+
 def format_evals(evals, evals_quda, residuals, sigmas=None):
     """The lines of Eigsolve_Mugiq::printEvals (lib/eigsolve_mugiq.cpp:325-333), character for character."""
     lines = ["", "Eigsolve_Mugiq - Eigenvalues:"]
@@ -270,6 +330,7 @@ class Eigsolve_Mugiq:
                  transfer=None, coarseOp=None):
         self.eVecs, self.gauge, self.kappa, self.opType, self.comm = list(eVecs), gauge, float(kappa), int(opType), comm
         self.clover, self.transfer, self.coarseOp = clover, transfer, coarseOp
+        self.mgTransfer, self.mgCoarseOp, self.lastSetup = None, None, None   # of setupMG
         if coarseOp is not None and transfer is None:
             raise _lib.MugiqHipError("Eigsolve_Mugiq: coarseOp needs the transfer it was built from")
         self.massNormalization = bool(massNormalization)
@@ -313,6 +374,17 @@ class Eigsolve_Mugiq:
     def solveMG(self, b, x=None, allow_unconverged=False, **param):
         """M^-1 b by the two-grid preconditioned GCR (mgSolve) for objects built with transfer= and coarseOp=: their gauge field, clover
         field, kappa, transfer and coarse operator.  Returns (x, MgSolveInfo)."""
-        if self.transfer is None or self.coarseOp is None or isinstance(self.transfer, (list, tuple)):
+        tr, op = self.transfer, self.coarseOp
+        if tr is None and op is None and self.mgTransfer is not None:   # the hierarchy setupMG made
+            tr, op = self.mgTransfer, self.mgCoarseOp
+        if tr is None or op is None or isinstance(tr, (list, tuple)):
             raise _lib.MugiqHipError("status 2: Eigsolve_Mugiq.solveMG: needs an object built with one finest-level transfer= and its coarseOp=")
-        return mgSolve(b, self.gauge, self.kappa, self.transfer, self.coarseOp, self.clover, x, allow_unconverged, self.comm, **param)
+        return mgSolve(b, self.gauge, self.kappa, tr, op, self.clover, x, allow_unconverged, self.comm, **param)
+
+    def setupMG(self, n_vec=24, geo_block_size=(4, 4, 4, 4), start=None, seed=0, **param):
+        """Make an MG hierarchy from this object's own gauge field, clover field and kappa (mgSetup) and keep it in self.mgTransfer and
+        self.mgCoarseOp: solveMG then works on an object that was built without transfer= and coarseOp= (what the eigenvectors are, and
+        so computeEvals and projectVector, does not change).  Returns the MgSetupInfo (also in self.lastSetup)."""
+        self.mgTransfer, self.mgCoarseOp, self.lastSetup = mgSetup(self.gauge, self.kappa, n_vec, geo_block_size, start, seed, self.clover,
+                                                                   comm=self.comm, **param)
+        return self.lastSetup

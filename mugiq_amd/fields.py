@@ -407,6 +407,37 @@ class Transfer:
         self.V.copy_(torch.from_numpy(buf))
         return self
 
+    # ---- MG setup on the device (csrc/mg_setup.hip) ------------------------------------------------------------------------------
+    def setVectors(self, vecs):
+        """V(x; s, c, j) = vecs[j](x; s, c) for n_vec fine SpinorFields of either precision and order (mugiq_hip_transfer_set_vectors);
+        a finest-level transfer only."""
+        vecs = list(vecs)
+        d = self.desc()
+        _lib.check(_lib.load().mugiq_hip_transfer_set_vectors(ctypes.byref(d), desc_array(vecs) if vecs else None, len(vecs), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return self
+
+    def getVector(self, j, out=None):
+        """column j of V as a fine SpinorField (mugiq_hip_transfer_get_vector): `out`, or a new FLOAT2 field of the transfer's precision"""
+        if out is None:
+            out = SpinorField(self.X, self.precision, FLOAT2, device=self.device)
+        d, o = self.desc(), out.desc()
+        _lib.check(_lib.load().mugiq_hip_transfer_get_vector(ctypes.byref(o), ctypes.byref(d), int(j), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return out
+
+    def blockOrthonormalize(self, nPasses=2, rankTol=0.0):
+        """Orthonormalise the n_vec columns inside every (aggregate, coarse spin) block of V, in place: nPasses of classical Gram-Schmidt
+        in fp64 (mugiq_hip_block_orthonormalize; the second pass is what restores orthonormality for ill-conditioned blocks).  Returns
+        (minPivotRatio, zeroColumns); a minPivotRatio below rankTol raises MugiqHipError (status 1) with V filled all the same."""
+        d, info = self.desc(), _lib.BlockOrthoInfo()
+        _lib.check(_lib.load().mugiq_hip_block_orthonormalize(ctypes.byref(d), int(nPasses), float(rankTol), ctypes.byref(info), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return float(info.minPivotRatio), int(info.zeroColumns)
+
+    def orthonormality(self):
+        """max over the blocks of max |B^dag B - 1| (mugiq_hip_transfer_orthonormality)"""
+        d, out = self.desc(), (ctypes.c_double * 1)()
+        _lib.check(_lib.load().mugiq_hip_transfer_orthonormality(ctypes.byref(d), out, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return float(out[0])
+
 
 def transfer_desc_array(transfers):
     arr = (_lib.TransferDesc * len(transfers))()

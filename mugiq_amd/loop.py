@@ -249,6 +249,8 @@ class Loop_Mugiq:
         lib = _lib.load()
         self._keep = []
         self._params, self._transfer = loopParams, transfer
+        self.coarseOp, self.lastSetup = None, None   # of setupMG
+        self._setupReplacedV = False
         p = _c_loop_param(loopParams, self._keep)
         self.eVecs = list(eVecs)
         sg = (ctypes.c_double * len(self.eVecs))(*[float(s) for s in eVals_sigma])
@@ -376,6 +378,7 @@ class Loop_Mugiq:
         """deflateLowModesCoarse with this loop's coarse eigenvectors, sigmas, transfers, comm and stream (mugiq_hip_loop_deflate_coarse):
         coarse (MG) loop objects only (MugiqHipError, status 2 = UNSUPPORTED, for fine-level and two-sided ones)."""
         from .operators import _deflate_args, _overlap_buffer, _overlap_array
+        self._refuse_after_setup("deflateCoarse")
         dst, src, dd, ds = _deflate_args(dst, src)
         nEv, nVec = len(self.eVecs), len(src)
         buf = _overlap_buffer(overlaps, nEv, nVec)
@@ -397,7 +400,29 @@ class Loop_Mugiq:
                                         allow_unconverged, clover)
         return x
 
-    def solveMG(self, b, kappa, coarseOp, clover=None, x=None, allow_unconverged=False, **param):
+    def setupMG(self, kappa, start=None, seed=0, clover=None, **param):
+        """Fill this coarse loop object's (single, finest-level) transfer in place by the MG setup (mgSetup) on its gauge field, and keep
+        the coarse operator built with it in self.coarseOp, which solveMG then uses when it is given none.  The coarse eigenvectors
+        the loop was created with belong to the V it had then, so computeCoarseLoop and deflateCoarse refuse (status 1) from here on:
+        loops and deflation with the new V need a new loop object with eigenvectors of the new hierarchy.  solveMG, which uses no
+        eigenvectors, reads V at the time of the call.
+        Returns the MgSetupInfo (also in self.lastSetup)."""
+        from .eigsolve import mgSetup
+        if self._transfer is None or self.eVecsLeft is not None:
+            raise _lib.MugiqHipError("status 2: Loop_Mugiq.setupMG: coarse (MG) loop objects only")
+        tr = self._transfer
+        if isinstance(tr, (list, tuple)):
+            if len(tr) != 1:
+                raise _lib.MugiqHipError("status 2: Loop_Mugiq.setupMG: one coarse level only (the loop has %d transfers)" % len(tr))
+            tr = tr[0]
+        if self._params.gauge is None:
+            raise _lib.MugiqHipError("status 1: Loop_Mugiq.setupMG: the loop object was created without a gauge field")
+        self._setupReplacedV = True
+        _, self.coarseOp, self.lastSetup = mgSetup(self._params.gauge, kappa, start=start, seed=seed, clover=clover, transfer=tr,
+                                                   comm=self.comm, **param)
+        return self.lastSetup
+
+    def solveMG(self, b, kappa, coarseOp=None, clover=None, x=None, allow_unconverged=False, **param):
         """x_r = M^-1 b_r by the two-grid preconditioned GCR (mgSolve) with this coarse loop object's gauge field, transfer and stream;
         coarseOp: the CoarseOperator of that transfer at this kappa (and clover).  Returns the list x; iteration counts, true residuals,
         histories and host reads are kept in self.lastSolve.  Status 2 (UNSUPPORTED) for fine-level and two-sided loop objects and for
@@ -413,12 +438,22 @@ class Loop_Mugiq:
             tr = tr[0]
         if self._params.gauge is None:
             raise _lib.MugiqHipError("status 1: Loop_Mugiq.solveMG: the loop object was created without a gauge field")
+        if coarseOp is None:
+            coarseOp = self.coarseOp
+            if coarseOp is None:
+                raise _lib.MugiqHipError("status 1: Loop_Mugiq.solveMG: no coarse operator (pass one or call setupMG first)")
         x, self.lastSolve = mgSolve(b, self._params.gauge, kappa, tr, coarseOp, clover, x, allow_unconverged, self.comm, **param)
         return x
 
     def computeCoarseLoop(self):
         """lib/loop_mugiq.cpp:439-525"""
+        self._refuse_after_setup("computeCoarseLoop")
         _lib.check(_lib.load().mugiq_hip_loop_compute(self._handle))
+
+    def _refuse_after_setup(self, who):
+        if self._setupReplacedV:
+            raise _lib.MugiqHipError("status 1: Loop_Mugiq.%s: setupMG replaced the V this loop's coarse eigenvectors belong to; "
+                                     "create a loop object with eigenvectors of the new hierarchy" % who)
 
     @property
     def dataPos_d(self):
