@@ -910,6 +910,102 @@ int mugiq_hip_mg_setup(const MugiqHipTransfer *transfer /* V is written */, Mugi
                        const MugiqHipCloverField *clover /* may be NULL */, double kappa, const MugiqHipMgSetupParam *p,
                        MugiqHipMgSetupInfo *info, const MugiqHipComm *comm /* NULL: one domain */, void *stream);
 
+/* ---- the coarse-grid eigensolver (new; csrc/coarse_eig.hip, csrc/dense_herm.cpp): Eigsolve_Mugiq::computeEvecs
+ * (lib/eigsolve_mugiq.cpp:278-287) in the computeCoarse branch (:27-33), where the reference hands mg_env->diracCoarse to QUDA's
+ * eigensolver with the QudaEigParam members tests/eigensolve.cpp:251-289 fills from the command line (nConv, nKr, tol, max_restarts,
+ * use_norm_op, use_poly_acc, poly_deg, a_min, a_max): in production the normal operator MdagM, the smallest real part of the spectrum,
+ * Chebyshev acceleration on.  Here: a Chebyshev-filtered block subspace iteration, shaped by
+ * mugiq_hip_coarse_apply, which reads the matrices once per 8 vectors.  tests/coarse_eig_ref.py restates it in numpy, step for step.
+ *
+ * Definitions.  A = MdagM | MMdag of the coarse operator (Hermitian, positive); Q a basis of m = nKr coarse vectors; <a, b> = sum conj(a) b
+ * in fp64 fixed-order sums.
+ *   Bounds.  aMax > 0 is taken as given; aMax <= 0: 20 power steps of A on the first 8 start vectors, each vector normalised after each
+ *     step, then aMax = 1.1 max_j <x_j, A x_j> from one more application.  After every Rayleigh-Ritz step, if the largest Ritz value
+ *     exceeds aMax: aMax = 1.1 x that value (a Ritz value never exceeds lambda_max, so this only repairs an underestimate).  The first time
+ *     this happens to a GIVEN aMax, the bound has been shown wrong, and a Ritz value repairs it only as far as the basis reaches (a filter
+ *     whose aMax is still below lambda_max amplifies the top of the spectrum): the power estimate above then runs once after all, 21
+ *     block applications and 21 host reads, and aMax is the larger of the two.
+ *   orth(Y): nOrtho rounds of Cholesky QR -- G = Y^dag Y (mugiq_hip_coarse_gram), G = R^dag R and R^-1 on the host, Y <- Y R^-1
+ *     (mugiq_hip_coarse_rotate).  A pivot <= rankTol max diag G ends the call with MUGIQ_HIP_ERROR_INVALID_ARGUMENT, outputs and info
+ *     filled from the basis as it stands (the convention of mugiq_hip_block_orthonormalize).
+ *   Rayleigh-Ritz: W = A Q in blocks of 8, H = Q^dag W Hermitised as (H + H^dag) / 2, H = Z Theta Z^dag with Theta ascending
+ *     (mugiq_hip_hermitian_eigh), Q <- Q Z and W <- W Z (A is not applied again), r_i = ||W_i - theta_i Q_i||.  Pair i is converged when
+ *     r_i <= tol aMax; nLocked = the largest multiple of 8 such that every i < nLocked is converged.
+ *   Filter: for the columns i >= nLocked in blocks of 8, Q_i <- T_d(A) Q_i by QUDA's unscaled recurrence with a = aMin, b = aMax,
+ *     d1 = 2 / (b - a), d2 = -(b + a) / (b - a), d = polyDeg:  t_0 = q,  t_1 = d1 A q + d2 q,  t_{k+1} = 2 (d1 A t_k + d2 t_k) - t_{k-1}.
+ *     aMin > 0 is fixed (the reference's eig_amin); aMin <= 0 is adaptive: before each filter, the largest Ritz value of the previous
+ *     Rayleigh-Ritz step.  Locked columns are not filtered; they stay in Q for orth and Rayleigh-Ritz.  A non-finite Gram diagonal after
+ *     a filter is MUGIQ_HIP_ERROR_HIP with a message, not an abort.
+ *   Driver: Q = orth(start), Rayleigh-Ritz; then filter, orth, Rayleigh-Ritz, iters++ until the first nConv pairs are converged or
+ *     iters = maxIter (MUGIQ_HIP_ERROR_NOT_CONVERGED, all outputs filled, as mugiq_hip_mg_solve does).  Returned: the first nConv columns,
+ *     theta, r and sigma_i = sqrt(theta_i).
+ * The 20 power steps (QUDA: 100), tol, polyDeg, nOrtho and rankTol are first guesses, NOT tuned; the 1.1 is QUDA's. */
+
+/* G_h[i*mB + j] = <a_i, b_j> (complex, row-major, HOST memory: one blocking read per call) for mA x mB coarse vectors of one lattice and
+ * n_vec, precision 8 (4: MUGIQ_HIP_ERROR_UNSUPPORTED), any stride (one for all a, one for all b; pads are not read), a comm of more than
+ * one rank or with a partitioned axis MUGIQ_HIP_ERROR_UNSUPPORTED.  A tall-skinny complex GEMM on v_mfma_f64_16x16x4_f64; the vector is
+ * cut into chunks of 4096 complex elements, the partial of a chunk is written and the chunks are added in ascending order by a second
+ * kernel: no atomics.  The bits of G[i][j] depend on a_i, b_j and the field geometry alone -- not on mA, mB or where i and j stand in
+ * the batch.  (G[j][i] of a = b is the conjugate of G[i][j] only to rounding: the imaginary part adds its two products in another order.)
+ * Work memory (per-stream workspace): (chunks + 1) mA mB complex. */
+int mugiq_hip_coarse_gram(double *G_h, const MugiqHipCoarseField *a_h, int mA, const MugiqHipCoarseField *b_h, int mB, const MugiqHipComm *comm,
+                          void *stream);
+/* out_j = sum_i in_i Z[i][j], i < mIn, j < mOut; Z_h[i*mOut + j] complex, row-major, on the host, copied by the call.  Out of place: an
+ * out overlapping an in or another out is MUGIQ_HIP_ERROR_INVALID_ARGUMENT.  Fields as above, one stride for all in and one for all out;
+ * pads are neither read nor written.  The same instruction; the sum over i runs in ascending order, four to an instruction, whatever
+ * mOut.  An in_i with Z[i][j] = 0 still enters as 0 x in_i: a NaN or Inf there reaches every output. */
+int mugiq_hip_coarse_rotate(const MugiqHipCoarseField *out_h, int mOut, const MugiqHipCoarseField *in_h, int mIn, const double *Z_h,
+                            const MugiqHipComm *comm, void *stream);
+/* Host-side dense algebra, no device and no LAPACK behind it; matrices are row-major n x n complex (re, im interleaved), n <= 512.
+ * eigh: (H + H^dag) / 2 = Z diag(theta) Z^dag, theta ascending, column j of Z the eigenvector of theta_j -- Householder
+ *   tridiagonalisation, implicit-shift QL; a non-finite H is MUGIQ_HIP_ERROR_INVALID_ARGUMENT.
+ * cholesky_upper: G = R^dag R, R upper triangular with a positive diagonal, from the upper triangle of G.  The first pivot <= rankTol max
+ *   diag G, or not finite, is MUGIQ_HIP_ERROR_INVALID_ARGUMENT with *badPivot = its column and *pivot its value (either may be NULL;
+ *   *badPivot = -1 on success): reported, never a NaN in R.
+ * upper_triangular_inverse: Rinv = R^-1 (upper triangular); a zero or non-finite diagonal entry is MUGIQ_HIP_ERROR_INVALID_ARGUMENT. */
+int mugiq_hip_hermitian_eigh(int n, const double *H, double *theta, double *Z);
+int mugiq_hip_cholesky_upper(int n, const double *G, double *R, double rankTol, int *badPivot, double *pivot);
+int mugiq_hip_upper_triangular_inverse(int n, const double *R, double *Rinv);
+
+typedef struct MugiqHipCoarseEigParam_s {
+  int nConv;      /* eig_nConv: 1 <= nConv < nKr */
+  int nKr;        /* eig_nKr: a multiple of 8, <= min(512, dimension of the coarse space) */
+  double tol;     /* > 0: pair i is converged when r_i <= tol aMax */
+  int maxIter;    /* eig_max_restarts: >= 0 filter / orth / Rayleigh-Ritz rounds */
+  int polyDeg;    /* eig_poly_deg: >= 1 */
+  double aMin;    /* eig_amin; <= 0: adaptive */
+  double aMax;    /* eig_amax; <= 0: estimated */
+  int nOrtho;     /* 1 .. 3 rounds of Cholesky QR */
+  double rankTol; /* 0 .. 1 */
+} MugiqHipCoarseEigParam;
+typedef struct MugiqHipCoarseEigInfo_s {
+  int iters;               /* filter / orth / Rayleigh-Ritz rounds made */
+  int nConverged;          /* of the first nConv pairs */
+  int opBlocks;            /* applications of A to a block of (at most) 8 vectors */
+  double aMaxUsed;         /* the upper bound at the end (estimated or given, then repaired) */
+  double aMinLast;         /* the lower bound of the last filter (the given aMin if none ran) */
+  double orthonormality;   /* max |E^dag E - 1| of the returned vectors, from one last Gram matrix */
+  int hostReads;           /* blocking reads, COUNTED by the call: one per Gram matrix and one per set of residual norms */
+  double hostDenseSeconds; /* wall time of the host's eigendecompositions, Cholesky factors and inverses */
+} MugiqHipCoarseEigInfo;
+/* The members are those tests/eigensolve.cpp:251-289 fills from QUDA's flags; it fixes no values.  nConv 200 is the N_ev of this
+ * project's flagship workload, nKr 256 the next multiple of 8 with a quarter to spare; maxIter 100, tol 1e-10, polyDeg 20, aMin 0
+ * (adaptive), aMax 0 (estimated), nOrtho 2, rankTol 1e-14: first guesses, NOT tuned. */
+int mugiq_hip_coarse_eig_param_default(MugiqHipCoarseEigParam *param);
+/* The solver above.  evecs_h[nConv] (written), start_h[nKr] (only read; the caller fills them, e.g. with seeded Gaussian noise: there is
+ * no device RNG, as in mugiq_hip_mg_setup): coarse fields of the operator's lattice and n_vec, any stride (one for all evecs, one for all
+ * start), no overlaps.  op: an operator of precision 8; opType MdagM | MMdag.  theta_h, residual_h, sigma_h: [nConv].
+ * Refusals, each before any device work: parameters out of range (MUGIQ_HIP_ERROR_INVALID_ARGUMENT); a comm of more than one rank or
+ * with a partitioned axis (MUGIQ_HIP_ERROR_UNSUPPORTED, as for the coarse operator); opType M | Mdag | H (MUGIQ_HIP_ERROR_UNSUPPORTED);
+ * precision 4 in the operator or a field (MUGIQ_HIP_ERROR_UNSUPPORTED); geometry mismatches, nKr above the dimension 4 n_vec volumeCB,
+ * overlaps (MUGIQ_HIP_ERROR_INVALID_ARGUMENT).
+ * Work memory: three bases of nKr packed vectors plus 24 vectors (and nKr (chunks + 2) doubles), allocated for the call and freed -- a
+ * failed allocation is MUGIQ_HIP_ERROR_HIP -- plus what mugiq_hip_coarse_apply, mugiq_hip_coarse_gram and mugiq_hip_coarse_rotate take
+ * from the per-stream arenas.  No atomics: two runs give identical bits, counts and info, apart from the seconds. */
+int mugiq_hip_coarse_eigensolve(const MugiqHipCoarseField *evecs_h, const MugiqHipCoarseField *start_h, const MugiqHipCoarseOperator *op,
+                                int opType, const MugiqHipCoarseEigParam *param, double *theta_h, double *residual_h, double *sigma_h,
+                                MugiqHipCoarseEigInfo *info, const MugiqHipComm *comm, void *stream);
+
 /* What Displace asks of QUDA's ColorSpinorField for its auxiliary vector (lib/displace.cpp:26-30: ColorSpinorField::Create
  * with QUDA_ZERO_FIELD_CREATE and setPrecision(coarsePrec_); :42,:50-51: operator=; :59: blas::zero), for hosts that do not
  * manage device memory themselves.  alloc: geometry, order, stride of `like`, `precision` (0 = like's), zeroed; ghost zones

@@ -264,6 +264,62 @@ inline MugiqHipMgSetupInfo mgSetup(const MugiqHipTransfer &transfer, CoarseOpera
                            stream));
   return info;
 }
+// ---- the coarse-grid eigensolver (csrc/coarse_eig.hip, csrc/dense_herm.cpp; new) ----
+// G[i * b.size() + j] = <a_i, b_j> on the matrix pipe, fixed-order sums, one blocking read (mugiq_hip_coarse_gram)
+inline std::vector<std::complex<double>> coarseGram(const std::vector<MugiqHipCoarseField> &a, const std::vector<MugiqHipCoarseField> &b,
+                                                    const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (a.empty() || b.empty()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "coarseGram: no vectors");
+  std::vector<std::complex<double>> G(a.size() * b.size());
+  check(mugiq_hip_coarse_gram(reinterpret_cast<double *>(G.data()), a.data(), (int)a.size(), b.data(), (int)b.size(), comm, stream));
+  return G;
+}
+// out_j = sum_i in_i Z[i * out.size() + j], out of place (mugiq_hip_coarse_rotate)
+inline void coarseRotate(const std::vector<MugiqHipCoarseField> &out, const std::vector<MugiqHipCoarseField> &in, const std::vector<std::complex<double>> &Z,
+                         const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (in.empty() || out.empty() || Z.size() != in.size() * out.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "coarseRotate: size mismatch");
+  check(mugiq_hip_coarse_rotate(out.data(), (int)out.size(), in.data(), (int)in.size(), reinterpret_cast<const double *>(Z.data()), comm, stream));
+}
+// (H + H^dag) / 2 = Z diag(theta) Z^dag on the host, theta ascending; H and Z row-major n x n (mugiq_hip_hermitian_eigh)
+inline void hermitianEigh(int n, const std::vector<std::complex<double>> &H, std::vector<double> &theta, std::vector<std::complex<double>> &Z) {
+  if (n < 1 || H.size() < (size_t)n * n) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "hermitianEigh: size mismatch");
+  theta.assign(n, 0.0);
+  Z.assign((size_t)n * n, std::complex<double>(0.0, 0.0));
+  check(mugiq_hip_hermitian_eigh(n, reinterpret_cast<const double *>(H.data()), theta.data(), reinterpret_cast<double *>(Z.data())));
+}
+// R with G = R^dag R, and R^-1 (mugiq_hip_cholesky_upper, mugiq_hip_upper_triangular_inverse); a pivot <= rankTol max diag G throws (status 1)
+inline void choleskyUpper(int n, const std::vector<std::complex<double>> &G, std::vector<std::complex<double>> &R, double rankTol = 0.0) {
+  if (n < 1 || G.size() < (size_t)n * n) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "choleskyUpper: size mismatch");
+  R.assign((size_t)n * n, std::complex<double>(0.0, 0.0));
+  check(mugiq_hip_cholesky_upper(n, reinterpret_cast<const double *>(G.data()), reinterpret_cast<double *>(R.data()), rankTol, nullptr, nullptr));
+}
+inline void upperTriangularInverse(int n, const std::vector<std::complex<double>> &R, std::vector<std::complex<double>> &Rinv) {
+  if (n < 1 || R.size() < (size_t)n * n) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "upperTriangularInverse: size mismatch");
+  Rinv.assign((size_t)n * n, std::complex<double>(0.0, 0.0));
+  check(mugiq_hip_upper_triangular_inverse(n, reinterpret_cast<const double *>(R.data()), reinterpret_cast<double *>(Rinv.data())));
+}
+// MugiqHipCoarseEigParam with the defaults of mugiq_hip_coarse_eig_param_default (the members the reference's tests/eigensolve.cpp
+// fills from QUDA's flags; the values are first guesses, not tuned)
+struct CoarseEigParam : MugiqHipCoarseEigParam {
+  CoarseEigParam() { check(mugiq_hip_coarse_eig_param_default(this)); }
+};
+// The param.nConv lowest eigenpairs of A = MdagM | MMdag of the explicit coarse operator into eVecs (param.nConv fields), from the
+// caller's param.nKr start vectors (mugiq_hip_coarse_eigensolve).  maxIter exhausted throws (status 5) unless allowUnconverged: the
+// outputs are filled all the same, and info.nConverged says how far it got
+inline MugiqHipCoarseEigInfo coarseEigensolve(const std::vector<MugiqHipCoarseField> &eVecs, const std::vector<MugiqHipCoarseField> &start,
+                                              const CoarseOperator &op, int opType, const CoarseEigParam &param, std::vector<double> &theta,
+                                              std::vector<double> &residual, std::vector<double> &sigma, bool allowUnconverged = false,
+                                              const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if ((int)eVecs.size() != param.nConv || (int)start.size() != param.nKr || eVecs.empty())
+    throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "coarseEigensolve: nConv eigenvector fields and nKr start vectors are needed");
+  theta.assign(eVecs.size(), 0.0);
+  residual.assign(eVecs.size(), 0.0);
+  sigma.assign(eVecs.size(), 0.0);
+  MugiqHipCoarseEigInfo info{};
+  const int st = mugiq_hip_coarse_eigensolve(eVecs.data(), start.data(), op.desc(), opType, &param, theta.data(), residual.data(), sigma.data(), &info,
+                                             comm, stream);
+  if (!(st == MUGIQ_HIP_ERROR_NOT_CONVERGED && allowUnconverged)) check(st);
+  return info;
+}
 // x_r = M^-1 b_r by CG on the normal equations from the low-mode start (mugiq_hip_wilson_solve).  Returns false where a right-hand
 // side did not reach tol within maxIter (x, iters and relres are filled all the same); every other failure throws.
 inline bool wilsonSolve(const std::vector<ColorSpinorField> &x, const std::vector<ColorSpinorField> &b, const GaugeField &gauge, double kappa,
@@ -371,7 +427,39 @@ public:
                  bool massNormalization = false, void *stream = nullptr)
       : eVecs_(std::move(eVecs)), gauge_(gauge), kappa_(kappa), opType_(opType), comm_(comm), mass_(massNormalization), stream_(stream),
         eVals_quda_(eVecs_.size()) {}
-  void computeEvals() { detail::computeEvals(eVecs_, gauge_, clover_, kappa_, opType_, mass_, eVals_, evals_res_, eVals_sigma_, comm_, stream_); }
+  // the computeCoarse branch (lib/eigsolve_mugiq.cpp:27-33) on the explicit coarse operator: coarse eigenvectors (may be empty until
+  // computeEvecs has run), the finest-level transfer and the operator built from it for this gauge field, clover field (NULL: Wilson) and
+  // kappa.  `coarseOp` must outlive the object.  computeEvals, computeEvecs and printEvals work; projectVector and solve are fine-level
+  Eigsolve_Mugiq(std::vector<MugiqHipCoarseField> coarseEvecs, const MugiqHipTransfer &transfer, const CoarseOperator &coarseOp, const GaugeField &gauge,
+                 const MugiqHipCloverField *clover, double kappa, int opType = MUGIQ_HIP_EIG_OPERATOR_MDAGM, const MugiqHipComm *comm = nullptr,
+                 bool massNormalization = false, void *stream = nullptr)
+      : gauge_(gauge), clover_(clover), kappa_(kappa), opType_(opType), comm_(comm), mass_(massNormalization), stream_(stream),
+        eVals_quda_(coarseEvecs.size()), coarseEvecs_(std::move(coarseEvecs)), coarseOp_(&coarseOp) {
+    (void)transfer;  // named for the reader: the operator was built from it and carries everything the calls below need
+  }
+  void computeEvals() {
+    if (coarseOp_) {
+      mugiq_hip::computeEvalsCoarse(coarseEvecs_, *coarseOp_, opType_, mass_, eVals_, evals_res_, eVals_sigma_, comm_, stream_);
+      return;
+    }
+    detail::computeEvals(eVecs_, gauge_, clover_, kappa_, opType_, mass_, eVals_, evals_res_, eVals_sigma_, comm_, stream_);
+  }
+  // Eigsolve_Mugiq::computeEvecs (lib/eigsolve_mugiq.cpp:278-287) for the coarse-operator constructor: the param.nConv lowest eigenpairs of
+  // this object's operator (MdagM | MMdag) by coarseEigensolve, into the caller's fields eVecs, which become the object's eigenvectors;
+  // eVals_quda takes the solver's theta, so that printEvals shows it beside what computeEvals recomputes
+  MugiqHipCoarseEigInfo computeEvecs(const std::vector<MugiqHipCoarseField> &eVecs, const std::vector<MugiqHipCoarseField> &start,
+                                     const CoarseEigParam &param = CoarseEigParam(), bool allowUnconverged = false) {
+    if (!coarseOp_) throw Error(MUGIQ_HIP_ERROR_UNSUPPORTED, "Eigsolve_Mugiq::computeEvecs: needs the coarse-operator constructor (fine-operator eigensolves are out of scope)");
+    std::vector<double> theta, res, sig;
+    const MugiqHipCoarseEigInfo info = coarseEigensolve(eVecs, start, *coarseOp_, opType_, param, theta, res, sig, allowUnconverged, comm_, stream_);
+    coarseEvecs_ = eVecs;
+    eVals_quda_.assign(theta.begin(), theta.end());
+    eVals_.assign(theta.size(), std::complex<double>(0.0, 0.0));
+    evals_res_.assign(theta.size(), 0.0);
+    eVals_sigma_.clear();
+    return info;
+  }
+  std::vector<MugiqHipCoarseField> &getCoarseEvecs() { return coarseEvecs_; }
   // lib/eigsolve_mugiq.cpp:317-337, the two line formats character for character (the interface contract of its log)
   void printEvals(FILE *out = stdout) const {
     if (comm_ && comm_->rank != 0) return;
@@ -411,6 +499,8 @@ private:
   void *stream_;
   std::vector<std::complex<double>> eVals_, eVals_quda_;
   std::vector<double> evals_res_, eVals_sigma_;
+  std::vector<MugiqHipCoarseField> coarseEvecs_;  // the computeCoarse branch
+  const CoarseOperator *coarseOp_ = nullptr;
 };
 
 // lib/contract_wrappers.cu:133-156

@@ -88,6 +88,18 @@ class MgSetupInfo(ctypes.Structure):
                 ("hostReads", ctypes.c_int), ("cgHostReadsEstimate", ctypes.c_int)]
 
 
+class CoarseEigParam(ctypes.Structure):
+    """MugiqHipCoarseEigParam (include/mugiq_hip.h)."""
+    _fields_ = [("nConv", ctypes.c_int), ("nKr", ctypes.c_int), ("tol", ctypes.c_double), ("maxIter", ctypes.c_int), ("polyDeg", ctypes.c_int),
+                ("aMin", ctypes.c_double), ("aMax", ctypes.c_double), ("nOrtho", ctypes.c_int), ("rankTol", ctypes.c_double)]
+
+
+class CoarseEigInfo(ctypes.Structure):
+    """MugiqHipCoarseEigInfo (include/mugiq_hip.h)."""
+    _fields_ = [("iters", ctypes.c_int), ("nConverged", ctypes.c_int), ("opBlocks", ctypes.c_int), ("aMaxUsed", ctypes.c_double),
+                ("aMinLast", ctypes.c_double), ("orthonormality", ctypes.c_double), ("hostReads", ctypes.c_int), ("hostDenseSeconds", ctypes.c_double)]
+
+
 class ProjectPlan(ctypes.Structure):
     """MugiqHipProjectPlan (include/mugiq_hip.h)."""
     _fields_ = [(n, ctypes.c_int) for n in ("form", "nks", "mb", "nPx", "tChunk", "nChunks", "lastChunk", "tiles", "tilesPerWg",
@@ -257,6 +269,19 @@ SIGNATURES = {
     "mugiq_hip_mg_setup_param_default": (ctypes.c_int, [ctypes.POINTER(MgSetupParam)]),
     "mugiq_hip_mg_setup": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.POINTER(CoarseOperatorDesc), _SP, ctypes.c_int, _GP, _CP, ctypes.c_double,
                                           ctypes.POINTER(MgSetupParam), ctypes.POINTER(MgSetupInfo), _VP, _VP]),
+    "mugiq_hip_coarse_gram": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(CoarseDesc),
+                                             ctypes.c_int, _VP, _VP]),
+    "mugiq_hip_coarse_rotate": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(CoarseDesc), ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_double), _VP, _VP]),
+    "mugiq_hip_hermitian_eigh": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                ctypes.POINTER(ctypes.c_double)]),
+    "mugiq_hip_cholesky_upper": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_double, _I4,
+                                                ctypes.POINTER(ctypes.c_double)]),
+    "mugiq_hip_upper_triangular_inverse": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "mugiq_hip_coarse_eig_param_default": (ctypes.c_int, [ctypes.POINTER(CoarseEigParam)]),
+    "mugiq_hip_coarse_eigensolve": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.POINTER(CoarseDesc), ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int,
+                                                   ctypes.POINTER(CoarseEigParam), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(CoarseEigInfo), _VP, _VP]),
     "mugiq_hip_prolongate_batched": (ctypes.c_int, [_SP, ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),
     "mugiq_hip_prolongate_contract_batched": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(CoarseDesc), ctypes.POINTER(ctypes.c_double),
                                                              ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),

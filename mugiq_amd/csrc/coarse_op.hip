@@ -380,12 +380,6 @@ size_t operator_elems(const int Xc[4], int nVec) {
   return vol * 9 * (size_t)(2 * nVec) * (size_t)(2 * nVec);
 }
 
-// [first, last) bytes of a coarse field's body
-void coarse_span(const MugiqHipCoarseField &f, uintptr_t *a, uintptr_t *b) {
-  *a = reinterpret_cast<uintptr_t>(f.data);
-  *b = *a + (uintptr_t)(f.parity_offset + (int64_t)2 * f.nColor * f.stride) * 2 * f.precision;
-}
-
 }  // namespace
 
 int check_single_domain(const MugiqHipComm *comm, const char *who) {

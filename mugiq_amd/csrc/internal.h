@@ -383,6 +383,11 @@ inline void spinor_span(const MugiqHipSpinorField &f, uintptr_t *a, uintptr_t *b
   *a = reinterpret_cast<uintptr_t>(f.data);
   *b = *a + (uintptr_t)(f.parity_offset + (int64_t)12 * f.stride) * 2 * f.precision;
 }
+// [first, last) bytes of a coarse field's body (csrc/coarse_op.hip, csrc/coarse_eig.hip)
+inline void coarse_span(const MugiqHipCoarseField &f, uintptr_t *a, uintptr_t *b) {
+  *a = reinterpret_cast<uintptr_t>(f.data);
+  *b = *a + (uintptr_t)(f.parity_offset + (int64_t)2 * f.nColor * f.stride) * 2 * f.precision;
+}
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }  // sub-buffers of the per-stream arenas
 
 }  // namespace mugiq

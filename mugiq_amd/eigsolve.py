@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .fields import SpinorField, CoarseOperator, Transfer, desc_array, coarse_desc_array, transfer_desc_array
+from .fields import SpinorField, CoarseField, CoarseOperator, Transfer, desc_array, coarse_desc_array, transfer_desc_array
 
 # MuGiqEigOperator (include/enum_mugiq.h:22-25 of the reference, values identical) and the extension H = g5 M
 MUGIQ_EIG_OPERATOR_M, MUGIQ_EIG_OPERATOR_Mdag, MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H = range(5)
@@ -20,6 +20,7 @@ STATUS_NOT_CONVERGED = 5  # MUGIQ_HIP_ERROR_NOT_CONVERGED
 SolveInfo = collections.namedtuple("SolveInfo", "iters relres converged")
 MgSolveInfo = collections.namedtuple("MgSolveInfo", "iters relres converged history hostReads")
 MgSetupInfo = collections.namedtuple("MgSetupInfo", "cgIters minPivotRatio zeroColumns orthonormality hostReads cgHostReadsEstimate")
+CoarseEigInfo = collections.namedtuple("CoarseEigInfo", "iters nConverged opBlocks aMaxUsed aMinLast orthonormality hostReads hostDenseSeconds converged")
 
 
 def _stream():
@@ -305,6 +306,136 @@ def mgSetup(gauge, kappa, n_vec=24, geo_block_size=(4, 4, 4, 4), start=None, see
                                            float(info.orthonormality), int(info.hostReads), int(info.cgHostReadsEstimate))
 
 
+def _dptr(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+def _square(M, who):
+    M = np.ascontiguousarray(M, dtype=np.complex128)
+    if M.ndim != 2 or M.shape[0] != M.shape[1] or M.shape[0] < 1:
+        raise _lib.MugiqHipError("%s: a square matrix is needed, got shape %s" % (who, M.shape))
+    return M
+
+
+def hermitianEigh(H):
+    """(theta ascending, Z) with (H + H^dag) / 2 = Z diag(theta) Z^dag: the host eigensolver of the coarse eigensolve
+    (mugiq_hip_hermitian_eigh; Householder tridiagonalisation and implicit-shift QL, n <= 512, no device, no LAPACK)."""
+    H = _square(H, "hermitianEigh")
+    n = H.shape[0]
+    theta, Z = np.zeros(n), np.zeros((n, n), np.complex128)
+    _lib.check(_lib.load().mugiq_hip_hermitian_eigh(n, _dptr(H), _dptr(theta), _dptr(Z)))
+    return theta, Z
+
+
+def choleskyUpper(G, rankTol=0.0):
+    """R upper triangular with G = R^dag R (mugiq_hip_cholesky_upper).  A pivot <= rankTol max diag G, or not finite, raises MugiqHipError
+    (status 1) whose badPivot and pivot attributes say where and what."""
+    G = _square(G, "choleskyUpper")
+    n = G.shape[0]
+    R = np.zeros((n, n), np.complex128)
+    bad, piv = ctypes.c_int(-1), ctypes.c_double(0.0)
+    st = _lib.load().mugiq_hip_cholesky_upper(n, _dptr(G), _dptr(R), float(rankTol), ctypes.byref(bad), ctypes.byref(piv))
+    if st != 0:
+        try:
+            _lib.check(st)
+        except _lib.MugiqHipError as e:
+            e.badPivot, e.pivot = int(bad.value), float(piv.value)
+            raise
+    return R
+
+
+def upperTriangularInverse(R):
+    """R^-1 of an upper triangular R (mugiq_hip_upper_triangular_inverse)"""
+    R = _square(R, "upperTriangularInverse")
+    X = np.zeros_like(R)
+    _lib.check(_lib.load().mugiq_hip_upper_triangular_inverse(R.shape[0], _dptr(R), _dptr(X)))
+    return X
+
+
+def coarseGram(a, b=None, comm=None):
+    """G[i][j] = <a_i, b_j> for lists of fp64 CoarseFields (b: a itself if not given), as a complex numpy array
+    (mugiq_hip_coarse_gram: the matrix pipe, fixed-order sums, one blocking read)."""
+    a = list(a)
+    b = a if b is None else list(b)
+    if not a or not b:
+        raise _lib.MugiqHipError("coarseGram: no vectors")
+    G = np.zeros((len(a), len(b)), np.complex128)
+    keep = []
+    _lib.check(_lib.load().mugiq_hip_coarse_gram(_dptr(G), coarse_desc_array(a), len(a), coarse_desc_array(b), len(b), _comm_ptr(comm, keep), _stream()))
+    return G
+
+
+def coarseRotate(out, inp, Z, comm=None):
+    """out_j = sum_i in_i Z[i][j] for lists of fp64 CoarseFields and a len(in) x len(out) matrix (mugiq_hip_coarse_rotate); out of place."""
+    out, inp = list(out), list(inp)
+    Z = np.ascontiguousarray(Z, dtype=np.complex128)
+    if not out or not inp or Z.shape != (len(inp), len(out)):
+        raise _lib.MugiqHipError("coarseRotate: %d in and %d out vectors need a %d x %d matrix, got %s" % (len(inp), len(out), len(inp), len(out), Z.shape))
+    keep = []
+    _lib.check(_lib.load().mugiq_hip_coarse_rotate(coarse_desc_array(out), len(out), coarse_desc_array(inp), len(inp), _dptr(Z), _comm_ptr(comm, keep), _stream()))
+
+
+def coarseEigParam(**param):
+    """MugiqHipCoarseEigParam: the defaults of mugiq_hip_coarse_eig_param_default (nConv 200, nKr 256, maxIter 100, tol 1e-10,
+    polyDeg 20, aMin 0 = adaptive, aMax 0 = estimated, nOrtho 2, rankTol 1e-14 -- first guesses, not tuned; the members are those the
+    reference's tests/eigensolve.cpp fills from QUDA's flags) with the given members replaced."""
+    p = _lib.CoarseEigParam()
+    _lib.check(_lib.load().mugiq_hip_coarse_eig_param_default(ctypes.byref(p)))
+    names = [n for n, _ in _lib.CoarseEigParam._fields_]
+    for k, v in param.items():
+        if k not in names:
+            raise _lib.MugiqHipError("coarseEigParam: no parameter %r (have %s)" % (k, ", ".join(names)))
+        setattr(p, k, float(v) if k in ("tol", "aMin", "aMax", "rankTol") else int(v))
+    return p
+
+
+def coarseStartVectors(Xc, n_vec, nKr, seed=0, pad=0, device="cuda"):
+    """nKr fp64 CoarseFields of seeded Gaussian noise (torch.randn with its own generator): the start vectors of coarseEigensolve.
+    Pads, if any, are left zero."""
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    out = []
+    for _ in range(int(nKr)):
+        f = CoarseField(Xc, n_vec, 8, pad, device=device)
+        body = f.data.view(2, 2 * f.n_vec, f.stride)[:, :, :f.volumeCB]
+        body.copy_(torch.view_as_complex(torch.randn(body.shape + (2,), dtype=torch.float64, device=f.device, generator=gen)))
+        out.append(f)
+    return out
+
+
+def coarseEigensolve(op, opType=MUGIQ_EIG_OPERATOR_MdagM, start=None, seed=0, eVecs=None, allow_unconverged=False, comm=None, **param):
+    """The nConv lowest eigenpairs of A = MdagM | MMdag of the explicit coarse operator `op` by Chebyshev-filtered block subspace iteration
+    (mugiq_hip_coarse_eigensolve).  start: nKr fp64 CoarseFields (default: coarseStartVectors(op.X, op.n_vec, nKr, seed)); eVecs: nConv
+    CoarseFields to fill (default: new ones); param: members of MugiqHipCoarseEigParam.  Returns (eVecs, theta, residual, sigma,
+    CoarseEigInfo(iters, nConverged, opBlocks, aMaxUsed, aMinLast, orthonormality, hostReads, hostDenseSeconds, converged)).  maxIter
+    exhausted raises MugiqHipError (status 5) unless allow_unconverged; a dependent basis raises status 1."""
+    p = coarseEigParam(**param)
+    if start is None:
+        start = coarseStartVectors(op.X, op.n_vec, p.nKr, seed, device=op.device)
+    start = list(start)
+    if len(start) != p.nKr:
+        raise _lib.MugiqHipError("coarseEigensolve: %d start vectors for nKr = %d" % (len(start), p.nKr))
+    if eVecs is None:
+        eVecs = [CoarseField(op.X, op.n_vec, 8, device=op.device) for _ in range(max(int(p.nConv), 0))]
+    eVecs = list(eVecs)
+    if len(eVecs) != p.nConv:
+        raise _lib.MugiqHipError("coarseEigensolve: %d eigenvector fields for nConv = %d" % (len(eVecs), p.nConv))
+    n = max(int(p.nConv), 1)
+    theta, res, sig = np.zeros(n), np.zeros(n), np.zeros(n)
+    info = _lib.CoarseEigInfo()
+    keep = []
+    d = op.desc()
+    st = _lib.load().mugiq_hip_coarse_eigensolve(coarse_desc_array(eVecs) if eVecs else None, coarse_desc_array(start) if start else None, ctypes.byref(d),
+                                                 int(opType), ctypes.byref(p), _dptr(theta), _dptr(res), _dptr(sig), ctypes.byref(info),
+                                                 _comm_ptr(comm, keep), _stream())
+    if st != 0 and not (st == STATUS_NOT_CONVERGED and allow_unconverged):
+        _lib.check(st)
+    nc = int(p.nConv)
+    return eVecs, theta[:nc], res[:nc], sig[:nc], CoarseEigInfo(int(info.iters), int(info.nConverged), int(info.opBlocks), float(info.aMaxUsed),
+                                                                 float(info.aMinLast), float(info.orthonormality), int(info.hostReads),
+                                                                 float(info.hostDenseSeconds), st == 0)
+
+
 def format_evals(evals, evals_quda, residuals, sigmas=None):
     """The lines of Eigsolve_Mugiq::printEvals (lib/eigsolve_mugiq.cpp:325-333), character for character."""
     lines = ["", "Eigsolve_Mugiq - Eigenvalues:"]
@@ -324,7 +455,8 @@ class Eigsolve_Mugiq:
     (printed beside the recomputed values; zero if not given).  clover: the CloverField of a Wilson-clover operator (None: Wilson).
     transfer (a Transfer or the list [finest, ...]): the computeCoarse branch -- eVecs are CoarseFields on the coarsest level and the
     operator is the Galerkin operator (computeEvalsCoarse); projectVector and solve stay fine-level.  coarseOp (with transfer): the
-    CoarseOperator built for this transfer, gauge, clover and kappa -- computeEvals then runs on it, on the coarse grid alone."""
+    CoarseOperator built for this transfer, gauge, clover and kappa -- computeEvals then runs on it, on the coarse grid alone, and
+    computeEvecs computes the eigenvectors themselves (eVecs may be empty until then): the one eigensolve this class owns."""
 
     def __init__(self, eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, comm=None, massNormalization=False, evals_quda=None, clover=None,
                  transfer=None, coarseOp=None):
@@ -346,6 +478,23 @@ class Eigsolve_Mugiq:
         self.eVals, self.evals_res, self.eVals_sigma = computeEvals(self.eVecs, self.gauge, self.kappa, self.opType, self.massNormalization,
                                                                      self.comm, self.clover)
         return self.eVals, self.evals_res, self.eVals_sigma
+
+    def computeEvecs(self, nConv, nKr, start=None, seed=0, allow_unconverged=False, **param):
+        """Eigsolve_Mugiq::computeEvecs (lib/eigsolve_mugiq.cpp:278-287) in the computeCoarse branch: the nConv lowest eigenpairs of this
+        object's operator (MdagM | MMdag) on its explicit coarse operator, by coarseEigensolve.  For objects built with one finest-level
+        transfer= and its coarseOp=.  Fills eVecs, and eVals_quda with the solver's theta (printEvals then prints it beside what
+        computeEvals recomputes); the solver's residuals, sigmas and CoarseEigInfo are kept in evecs_res, evecs_sigma and lastEigensolve.
+        Returns sigma."""
+        if self.transfer is None or self.coarseOp is None or isinstance(self.transfer, (list, tuple)):
+            raise _lib.MugiqHipError("status 2: Eigsolve_Mugiq.computeEvecs: needs an object built with one finest-level transfer= and its coarseOp= "
+                                     "(fine-operator eigensolves are out of scope)")
+        ev, theta, res, sig, info = coarseEigensolve(self.coarseOp, self.opType, start, seed, None, allow_unconverged, self.comm, nConv=nConv, nKr=nKr,
+                                                     **param)
+        n = len(ev)
+        self.eVecs, self.eVals_quda = ev, theta.astype(np.complex128)
+        self.eVals, self.evals_res, self.eVals_sigma = np.zeros(n, np.complex128), np.zeros(n), None
+        self.evecs_res, self.evecs_sigma, self.lastEigensolve = res, sig, info
+        return sig
 
     def printEvals(self, file=None):
         sig = self.eVals_sigma if self.opType in (MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag) else None

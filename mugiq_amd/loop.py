@@ -445,6 +445,29 @@ class Loop_Mugiq:
         x, self.lastSolve = mgSolve(b, self._params.gauge, kappa, tr, coarseOp, clover, x, allow_unconverged, self.comm, **param)
         return x
 
+    def computeEvecs(self, kappa, nConv, nKr, coarseOp=None, opType=None, start=None, seed=0, allow_unconverged=False, **param):
+        """The nConv lowest eigenpairs of MdagM (or opType) of the explicit coarse operator of this coarse loop object's transfer, by
+        coarseEigensolve: what Eigsolve_Mugiq::computeEvecs gives the reference's computeCoarse branch.  coarseOp: the CoarseOperator of
+        that transfer at this kappa (default: self.coarseOp, which setupMG keeps).  The vectors go to self.coarseEvecs, the sigmas to
+        self.coarseSigma and the CoarseEigInfo to self.lastEigensolve; the loop object keeps contracting the eigenvectors it was created
+        with -- loops with the new ones need a new loop object, Loop_Mugiq(params, loop.coarseEvecs, sigma, transfer=...).  Returns
+        sigma.  Status 2 for fine-level and two-sided loop objects and for hierarchies of more than one level."""
+        from .eigsolve import coarseEigensolve, MUGIQ_EIG_OPERATOR_MdagM
+        if self._transfer is None or self.eVecsLeft is not None:
+            raise _lib.MugiqHipError("status 2: Loop_Mugiq.computeEvecs: coarse (MG) loop objects only")
+        if isinstance(self._transfer, (list, tuple)) and len(self._transfer) != 1:
+            raise _lib.MugiqHipError("status 2: Loop_Mugiq.computeEvecs: one coarse level only (the loop has %d transfers)" % len(self._transfer))
+        if coarseOp is None:
+            coarseOp = self.coarseOp
+            if coarseOp is None:
+                raise _lib.MugiqHipError("status 1: Loop_Mugiq.computeEvecs: no coarse operator (pass one or call setupMG first)")
+        if float(coarseOp.kappa) != float(kappa):
+            raise _lib.MugiqHipError("status 1: Loop_Mugiq.computeEvecs: the coarse operator was built for kappa = %r, not %r" % (coarseOp.kappa, kappa))
+        ev, _, _, sigma, self.lastEigensolve = coarseEigensolve(coarseOp, MUGIQ_EIG_OPERATOR_MdagM if opType is None else opType, start, seed, None,
+                                                                allow_unconverged, self.comm, nConv=nConv, nKr=nKr, **param)
+        self.coarseEvecs, self.coarseSigma = ev, sigma
+        return sigma
+
     def computeCoarseLoop(self):
         """lib/loop_mugiq.cpp:439-525"""
         self._refuse_after_setup("computeCoarseLoop")

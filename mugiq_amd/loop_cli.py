@@ -1,12 +1,18 @@
 """The loop options of the reference's drivers, under the same flag names (tests/test_params_mugiq.cpp:77-112), and the
 `setLoopParam` filler of tests/loop.cpp:620-748 -- so a command line written for `tests/loop` carries over unchanged.
 
-The reference's driver then runs QUDA's eigensolver; that part is out of scope here (eigenvectors and sigma are the
-INPUTS of the loop engine), so `main()` feeds the engine synthetic eigenvectors of the requested shape:
+The reference's driver then runs QUDA's eigensolver.  For the fine operator that part is out of scope here (eigenvectors and
+sigma are the INPUTS of the loop engine), so by default `main()` feeds the engine synthetic eigenvectors of the requested shape:
 
     python -m mugiq_amd.loop_cli --dim 8 8 8 8 --prec double --n-ev 4 \\
         --loop-ft-sign minus --loop-calc-type opt --momenta-filename momenta.txt \\
         --displace-entry-string "+z:1,2;-x:3" --loop-mom-space-filename loops.h5
+
+The computeCoarse branch is covered: --eig-compute-coarse runs the MG setup on the gauge field, computes the lowest eigenpairs of MdagM
+of the coarse operator on the device (QUDA's flag names: --eig-nConv, --eig-nKr, --eig-tol, --eig-poly-deg, --eig-amin, --eig-amax,
+--eig-max-restarts, --mg-nvec, --mg-block-size), prints the printEvals lines and runs the MG ultra-local loop on the result:
+
+    python -m mugiq_amd.loop_cli --dim 8 8 8 8 --eig-compute-coarse --eig-nConv 16 --eig-nKr 32 --mg-nvec 8 --mg-block-size 4 4 4 4
 
 Multi-GPU: launch with torchrun and pass --gridsize gx gy gz gt (QUDA's --gridsize); one process per GPU.
 """
@@ -147,7 +153,77 @@ def build_parser():
     ap.add_argument("--compute-plaquette", action="store_true",
                     help="print the plaquette of the gauge field of the displacements, as the reference does after plaqQuda")
     add_loop_option_mugiq(ap)
+    add_eig_option_mugiq(ap)
     return ap
+
+
+def _random_su3_qdp(vcb, gen):
+    """seeded random SU(3) links of the local lattice in QDP order, [4][V*18] reals"""
+    import torch
+    m = torch.complex(torch.randn(4 * 2 * vcb, 3, 3, dtype=torch.float64, device="cuda", generator=gen),
+                      torch.randn(4 * 2 * vcb, 3, 3, dtype=torch.float64, device="cuda", generator=gen))
+    r0 = m[:, 0] / torch.linalg.vector_norm(m[:, 0], dim=-1, keepdim=True)
+    r1 = m[:, 1] - (r0.conj() * m[:, 1]).sum(-1, keepdim=True) * r0
+    r1 = r1 / torch.linalg.vector_norm(r1, dim=-1, keepdim=True)
+    r2 = torch.linalg.cross(r0.conj(), r1.conj())                                  # det = 1
+    u = torch.stack([r0, r1, r2], dim=1).reshape(4, 2 * vcb, 9)
+    return torch.view_as_real(u).reshape(4, 2 * vcb * 18).cpu().numpy()
+
+
+def add_eig_option_mugiq(parser):
+    """The eigensolver and MG flags of QUDA's command line that --eig-compute-coarse reads (tests/eigensolve.cpp:251-289 of the reference
+    sets the matching QudaEigParam members; tests/loop.cpp:471,492 the MG ones).  Defaults: those of mugiq_hip_coarse_eig_param_default
+    where this project has one (first guesses, not tuned), QUDA's names throughout."""
+    g = parser.add_argument_group("Eigensolver", "the computeCoarse branch: MG setup and coarse eigensolve on the device")
+    g.add_argument("--eig-compute-coarse", action="store_true",
+                   help="compute the eigenvectors instead of using synthetic ones: MG setup on the gauge field, then the lowest eigenpairs of MdagM "
+                        "of the coarse operator, then the MG ultra-local loop on them (one process, double precision)")
+    g.add_argument("--eig-nConv", dest="eig_nConv", type=int, default=None, help="eigenpairs wanted (default: --n-ev)")
+    g.add_argument("--eig-nKr", dest="eig_nKr", type=int, default=None, help="size of the search space, a multiple of 8 (default: nConv + 8 rounded up)")
+    g.add_argument("--eig-tol", dest="eig_tol", type=_finite_float, default=1e-10, help="r_i <= tol x aMax")
+    g.add_argument("--eig-poly-deg", dest="eig_poly_deg", type=int, default=20, help="degree of the Chebyshev filter")
+    g.add_argument("--eig-amin", dest="eig_amin", type=_finite_float, default=0.0, help="lower end of the filter interval (<= 0: adaptive)")
+    g.add_argument("--eig-amax", dest="eig_amax", type=_finite_float, default=0.0, help="upper end of the filter interval (<= 0: estimated)")
+    g.add_argument("--eig-max-restarts", dest="eig_max_restarts", type=_nonneg_int, default=100, help="filter / orthonormalise / Rayleigh-Ritz rounds")
+    g.add_argument("--mg-nvec", dest="mg_nvec", type=int, default=24, help="null vectors of the MG setup")
+    g.add_argument("--mg-block-size", dest="mg_block_size", type=int, nargs=4, default=[4, 4, 4, 4], metavar=("X", "Y", "Z", "T"), help="aggregate")
+    return g
+
+
+def compute_coarse_main(args):
+    """--eig-compute-coarse: gauge field -> mgSetup -> coarse eigenpairs -> Loop_Mugiq(transfer=), nothing from outside.  Prints the
+    reference's printEvals lines (the solver's theta in the second column) and one JSON line."""
+    import torch
+    from . import CloverField, GaugeField, Loop_Mugiq
+    from .eigsolve import Eigsolve_Mugiq, MUGIQ_EIG_OPERATOR_MdagM, mgSetup
+    if int(np.prod(args.gridsize)) != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--eig-compute-coarse runs on one process: the explicit coarse operator is a single-domain object")
+    if args.prec != "double":
+        raise SystemExit("--eig-compute-coarse needs --prec double: the MG setup and the eigensolve are fp64")
+    X = tuple(args.dim)
+    gen = torch.Generator(device="cuda").manual_seed(args.seed)
+    gauge = GaugeField(X, (0, 0, 0, 0), 8)
+    qdp = np.load(args.loop_gauge_filename, allow_pickle=False) if args.loop_gauge_filename else _random_su3_qdp(int(np.prod(X)) // 2, gen)
+    gauge.set_from_qdp_host(qdp, None)
+    clover = CloverField(X, 8).compute(gauge, args.clover_coeff, None) if args.dslash_type == "clover" else None
+    transfer, coarseOp, setup = mgSetup(gauge, args.kappa, args.mg_nvec, tuple(args.mg_block_size), seed=args.seed, clover=clover)
+    nConv = args.eig_nConv if args.eig_nConv is not None else args.n_ev
+    nKr = args.eig_nKr if args.eig_nKr is not None else (nConv + 8 + 7) // 8 * 8
+    es = Eigsolve_Mugiq([], gauge, args.kappa, MUGIQ_EIG_OPERATOR_MdagM, clover=clover, transfer=transfer, coarseOp=coarseOp)
+    sigma = es.computeEvecs(nConv, nKr, seed=args.seed, tol=args.eig_tol, polyDeg=args.eig_poly_deg, aMin=args.eig_amin, aMax=args.eig_amax,
+                            maxIter=args.eig_max_restarts)
+    es.computeEvals()
+    es.printEvals()
+    loop = Loop_Mugiq(MugiqLoopParam(gauge=gauge), es.eVecs, sigma, transfer=transfer)
+    loop.computeCoarseLoop()
+    norm = float(torch.linalg.vector_norm(loop.dataPos_d))
+    info = es.lastEigensolve
+    print(json.dumps({"local_dim": list(args.dim), "mg_nvec": args.mg_nvec, "mg_block_size": list(args.mg_block_size), "nConv": nConv, "nKr": nKr,
+                      "iters": info.iters, "opBlocks": info.opBlocks, "aMax": info.aMaxUsed, "hostReads": info.hostReads,
+                      "hostDenseSeconds": info.hostDenseSeconds, "setupOrthonormality": setup.orthonormality, "nLoop": loop.nLoop,
+                      "loop_norm": norm, "data": "computed: MG setup on the device, coarse eigenpairs of MdagM, MG ultra-local loop"}))
+    loop.close()
+    return 0
 
 
 def synthetic_inputs(args, rank=0, comm=None):
@@ -168,14 +244,7 @@ def synthetic_inputs(args, rank=0, comm=None):
         if args.loop_gauge_filename:
             qdp = np.load(args.loop_gauge_filename, allow_pickle=False)                    # [4][V*18] reals, QDP order
         else:
-            m = torch.complex(torch.randn(4 * 2 * vcb, 3, 3, dtype=torch.float64, device="cuda", generator=gen),
-                              torch.randn(4 * 2 * vcb, 3, 3, dtype=torch.float64, device="cuda", generator=gen))
-            r0 = m[:, 0] / torch.linalg.vector_norm(m[:, 0], dim=-1, keepdim=True)
-            r1 = m[:, 1] - (r0.conj() * m[:, 1]).sum(-1, keepdim=True) * r0
-            r1 = r1 / torch.linalg.vector_norm(r1, dim=-1, keepdim=True)
-            r2 = torch.linalg.cross(r0.conj(), r1.conj())                                  # det = 1
-            u = torch.stack([r0, r1, r2], dim=1).reshape(4, 2 * vcb, 9)
-            qdp = torch.view_as_real(u).reshape(4, 2 * vcb * 18).cpu().numpy()
+            qdp = _random_su3_qdp(vcb, gen)
         gauge.set_from_qdp_host(qdp, comm)
     fields = []
     for n in range(args.n_ev):
@@ -190,6 +259,8 @@ def synthetic_inputs(args, rank=0, comm=None):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.eig_compute_coarse:
+        return compute_coarse_main(args)
     import torch
     import torch.distributed as dist
     from . import GridComm, Loop_Mugiq
