@@ -734,8 +734,9 @@ int mugiq_hip_wilson_clover_solve(const MugiqHipSpinorField *x_h, const MugiqHip
  *   ((parity*volumeCB + x_cb)*9 + m)*N*N + r*N + c,       m = 0: Xd,  m = 1 + 2 mu: Y+_mu,  m = 2 + 2 mu: Y-_mu
  * (32^4 with 4^4 aggregates and n_vec 24 in fp64: 1.36 GB).
  *
- * Limits: a SINGLE DOMAIN (a comm with size > 1 or any partitioned axis: MUGIQ_HIP_ERROR_UNSUPPORTED, before any device work) and ONE
- * coarse level (the operator of a coarse -> coarse transfer is not built).  Deeper hierarchies and partitioned grids stay on the route of
+ * Limits: a SINGLE DOMAIN (a comm with size > 1 or any partitioned axis: MUGIQ_HIP_ERROR_UNSUPPORTED, before any device work).  The
+ * operator of a coarse -> coarse transfer is built from this one by mugiq_hip_compute_coarse_operator_coarse (below) and lives in the same
+ * struct: application, eigenpair check and eigensolver do not know the level.  Partitioned grids stay on the route of
  * mugiq_hip_compute_evals_coarse, which applies R M P through the fine lattice. */
 typedef struct MugiqHipCoarseOperator_s {
   void *data;
@@ -772,6 +773,37 @@ int mugiq_hip_coarse_apply(const MugiqHipCoarseField *dst_h, const MugiqHipCoars
 int mugiq_hip_compute_evals_coarse_operator(const MugiqHipCoarseField *coarseEvecs_h, int nEv, const MugiqHipCoarseOperator *op, int opType,
                                             int massNormalization, double *lambda_h, double *residual_h, double *sigma_h,
                                             const MugiqHipComm *comm, void *stream);
+
+/* ---- the operator of a coarse -> coarse transfer (new; csrc/coarse_op2.hip): the coarsest level of a three-level hierarchy, where the
+ * reference's Eigsolve_Mugiq computes its eigenvectors (MG_Mugiq takes n_level 2, 3 or 4: include/mg_mugiq.h:40-53;
+ * lib/eigsolve_mugiq.cpp:135-152).
+ *
+ * Definition.  Let K_m(x), m = 0 .. 8, be the matrices of a coarse operator on the lattice X1 (m = 0: Xd, 1 + 2 mu: Y+_mu, 2 + 2 mu: Y-_mu),
+ * of size N0 x N0, N0 = 2 nc, and V the null vectors of a coarse -> coarse MugiqHipTransfer on X1 (spinBlockSize 1, nc colours on its finer
+ * side, nVec = nv, complex index ((nc*s + c)*nv + j)*stride + x_cb).  N1 = 2 nv, row index S*nv + j; E(x) is the N0 x N1 embedding
+ * E[(s, c), (S', j')] = delta_{s S'} V(x; s, c, j'): the chirality is kept.  For the coarsest site X (an aggregate of geoBlockSize):
+ *   Xd'(X)   = sum_{x in X} E(x)^dag K_0(x) E(x)
+ *              + sum_mu sum_{x in X, x+mu in X} E(x)^dag K_{1+2mu}(x) E(x+mu)
+ *              + sum_mu sum_{x in X, x-mu in X} E(x)^dag K_{2+2mu}(x) E(x-mu)
+ *   Y'+_mu(X) = sum_{x in X, x+mu not in X} E(x)^dag K_{1+2mu}(x) E(x+mu)
+ *   Y'-_mu(X) = sum_{x in X, x-mu not in X} E(x)^dag K_{2+2mu}(x) E(x-mu)
+ * Membership is by aggregate, after the periodic wrap.  The forward and the backward term stay separate even where x+mu = x-mu (extent 2
+ * on X1, or on the coarsest lattice).  Storage and application of the result are those of MugiqHipCoarseOperator; kappa and hasClover
+ * are inherited from the input operator.  Nothing assumes that V is block-orthonormal.  By construction the result is R_1 M_c P_1
+ * (= R_1 R_0 M P_0 P_1), its explicit adjoint R_1 M_c^dag P_1, and G5 M' = R_1 R_0 g5 M P_0 P_1.
+ *
+ * Checks, all before any device work: NULL arguments; a single domain (MUGIQ_HIP_ERROR_UNSUPPORTED); transfer->spinBlockSize == 1;
+ * transfer->X == finerOp->X; stride >= volumeCB; parity_offset == 2 finerOp->nVec nVec stride exactly (the rule of
+ * mugiq_hip_block_orthonormalize for the colours of a coarse V); the block sizes divide the extents and the coarsest extents are even;
+ * op->X, op->nVec and op->precision are the transfer's; the three precisions are equal; op->data does not overlap finerOp->data.
+ * Every nc <= 64 and nv <= 64 (the limits of the struct) is served.
+ * Numerics: fp64 products and sums for either storage, one rounding on the store, no atomics, and a summation order fixed by the
+ * transfer geometry alone (sites of the aggregate in lexicographic order; per site K_0, then +x, -x, ... -t): two builds give the same
+ * bits on any stream.  Every K_m(x) is read from memory once per build: the four workgroups of a matrix own its chirality quadrants,
+ * and a quadrant of the result needs that quadrant of K alone.  The input can itself be a result of this call (a fourth level); nothing
+ * tests that. */
+int mugiq_hip_compute_coarse_operator_coarse(MugiqHipCoarseOperator *op, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *finerOp,
+                                             const MugiqHipComm *comm, void *stream);
 
 /* ---- a two-grid preconditioned flexible GCR on the fine operator (new; csrc/mg_solve.hip): the solve of the deflated recipe for every
  * stochastic source, for hosts that hold an MG hierarchy (V of a finest-level transfer and its explicit coarse operator).
@@ -811,7 +843,7 @@ int mugiq_hip_mg_solve_param_default(MugiqHipMgSolveParam *param);
 /* z_i = K(r_i), i < nVec.  z_h, r_h: fp64 fields of one layout (FLOAT2 | FLOAT4, any stride; pads are neither read nor written), no z
  * overlapping any r; they need no ghost zones.  transfer: a finest-level one of precision 8 on the fields' lattice; coarseOp: the operator
  * built from it for this gauge field, clover field and kappa (precision 8).  tol and maxIter of `param` are checked but not used.
- * Limits, each refused before any device work: a single domain and one level (MUGIQ_HIP_ERROR_UNSUPPORTED, as for the coarse operator);
+ * Limits, each refused before any device work: a single domain (MUGIQ_HIP_ERROR_UNSUPPORTED, as for the coarse operator) and a two-grid cycle;
  * precision 4 anywhere in transfer, coarse operator or fields (MUGIQ_HIP_ERROR_UNSUPPORTED); parameters out of range, geometry mismatches
  * between fields, transfer and operator, a coarse operator built for another kappa or without / with the clover term of the call
  * (op->kappa, op->hasClover), a z overlapping an r or another z (MUGIQ_HIP_ERROR_INVALID_ARGUMENT).
@@ -871,6 +903,11 @@ int mugiq_hip_transfer_orthonormality(const MugiqHipTransfer *transfer, double *
  * neither side are read or written. */
 int mugiq_hip_transfer_set_vectors(const MugiqHipTransfer *transfer /* V is written */, const MugiqHipSpinorField *vecs_h, int nVec, void *stream);
 int mugiq_hip_transfer_get_vector(const MugiqHipSpinorField *vec, const MugiqHipTransfer *transfer, int j, void *stream);
+/* The same for a coarse -> coarse transfer (spinBlockSize 1; csrc/coarse_op2.hip): V(x; s, c, j) = vecs_h[j](x; s, c) for coarse vectors
+ * on its finer lattice with nColor = the colours of that side (parity_offset = 2 nColor n_vec stride, exactly), and its inverse for one
+ * column.  Either precision on each side (converted on the way), any strides (one for all vectors); pads are neither read nor written. */
+int mugiq_hip_transfer_set_coarse_vectors(const MugiqHipTransfer *transfer /* V is written */, const MugiqHipCoarseField *vecs_h, int nVec, void *stream);
+int mugiq_hip_transfer_get_coarse_vector(const MugiqHipCoarseField *vec, const MugiqHipTransfer *transfer, int j, void *stream);
 
 /* The setup driver: host code over the entry points above and below.  start_h: nVec = transfer->nVec fp64 start vectors the caller
  * fills (e.g. seeded Gaussian noise; there is no device RNG).  Null vector j is QUDA's "M x = 0 from a random guess":
@@ -881,7 +918,7 @@ int mugiq_hip_transfer_get_vector(const MugiqHipSpinorField *vec, const MugiqHip
  * otherwise, and fp64): each cycle v_j -= mugiq_hip_mg_solve(M v_j) with the current V and M_c, stopped after refineIters outer
  * iterations (defaults of mugiq_hip_mg_solve_param_default otherwise; tol = setupTol, nKrylov = refineIters), then repack,
  * re-orthonormalise and rebuild M_c.  A rank failure of the orthonormalisation ends the setup with its status, V and info filled.
- * One level and one domain, as for the coarse operator: a comm with more than one rank or a partitioned axis is
+ * The finest level only (a second one: mugiq_hip_compute_coarse_operator_coarse) and one domain: a comm with more than one rank or a partitioned axis is
  * MUGIQ_HIP_ERROR_UNSUPPORTED before any device work.  The start vectors are only read.  Work memory: nVec + 16 fine fp64 vectors,
  * allocated for the call and freed, plus what the calls it makes take from the per-stream workspace.
  * Defaults: setupMaxIter 500 and setupTol 5e-6 mirror tests/loop.cpp:349-350;  nBlockOrtho 2, rankTol 1e-8, refineCycles 0 and

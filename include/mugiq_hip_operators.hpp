@@ -158,8 +158,8 @@ inline void computeEvalsCoarse(const std::vector<MugiqHipCoarseField> &coarseEve
                                        comm, stream));
   if (opType == MUGIQ_HIP_EIG_OPERATOR_M || opType == MUGIQ_HIP_EIG_OPERATOR_MDAG) sigma.clear();
 }
-// ---- the explicit Galerkin coarse operator (MugiqHipCoarseOperator; csrc/coarse_op.hip; new): one level, one domain ------------------
-// Owns the nine matrices per coarse site of a finest-level transfer
+// ---- the explicit Galerkin coarse operator (MugiqHipCoarseOperator; csrc/coarse_op.hip, csrc/coarse_op2.hip; new): one domain -----------
+// Owns the nine matrices per coarse site of a transfer (any level)
 class CoarseOperator {
 public:
   CoarseOperator(const int Xc[4], int nVec, int precision) { check(mugiq_hip_alloc_coarse_operator(&op_, Xc, nVec, precision)); }
@@ -176,6 +176,19 @@ private:
 inline void computeCoarseOperator(CoarseOperator &op, const MugiqHipTransfer &transfer, const GaugeField &gauge, const MugiqHipCloverField *clover,
                                   double kappa, const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
   check(mugiq_hip_compute_coarse_operator(op.desc(), &transfer, &gauge, clover, kappa, comm, stream));
+}
+// The operator of a coarse -> coarse transfer from the operator of its finer lattice (mugiq_hip_compute_coarse_operator_coarse): the
+// coarsest level of a three-level hierarchy, in the same CoarseOperator; kappa and hasClover are inherited
+inline void computeCoarseOperatorCoarse(CoarseOperator &op, const MugiqHipTransfer &transfer, const CoarseOperator &finerOp,
+                                        const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  check(mugiq_hip_compute_coarse_operator_coarse(op.desc(), &transfer, finerOp.desc(), comm, stream));
+}
+// V(x; s, c, j) = vecs[j](x; s, c) of a coarse -> coarse transfer, and one column back (mugiq_hip_transfer_set_coarse_vectors / _get_coarse_vector)
+inline void setCoarseVectors(const MugiqHipTransfer &transfer, const std::vector<MugiqHipCoarseField> &vecs, void *stream = nullptr) {
+  check(mugiq_hip_transfer_set_coarse_vectors(&transfer, vecs.data(), (int)vecs.size(), stream));
+}
+inline void getCoarseVector(const MugiqHipCoarseField &vec, const MugiqHipTransfer &transfer, int j, void *stream = nullptr) {
+  check(mugiq_hip_transfer_get_coarse_vector(&vec, &transfer, j, stream));
 }
 // dst_i = scale * A_c src_i on the coarse grid (mugiq_hip_coarse_apply)
 inline void coarseApply(const std::vector<MugiqHipCoarseField> &dst, const std::vector<MugiqHipCoarseField> &src, const CoarseOperator &op,

@@ -254,6 +254,10 @@ SIGNATURES = {
     "mugiq_hip_compute_evals_coarse_operator": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int,
                                                                ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                                ctypes.POINTER(ctypes.c_double), _VP, _VP]),
+    "mugiq_hip_compute_coarse_operator_coarse": (ctypes.c_int, [ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(TransferDesc),
+                                                                ctypes.POINTER(CoarseOperatorDesc), _VP, _VP]),
+    "mugiq_hip_transfer_set_coarse_vectors": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.POINTER(CoarseDesc), ctypes.c_int, _VP]),
+    "mugiq_hip_transfer_get_coarse_vector": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.POINTER(TransferDesc), ctypes.c_int, _VP]),
     "mugiq_hip_wilson_clover_solve": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, _SP, ctypes.POINTER(ctypes.c_double),
                                                      ctypes.c_int, ctypes.c_double, ctypes.c_int, _I4, ctypes.POINTER(ctypes.c_double), _VP, _VP]),
     "mugiq_hip_mg_solve_param_default": (ctypes.c_int, [ctypes.POINTER(MgSolveParam)]),

@@ -20,6 +20,7 @@ STATUS_NOT_CONVERGED = 5  # MUGIQ_HIP_ERROR_NOT_CONVERGED
 SolveInfo = collections.namedtuple("SolveInfo", "iters relres converged")
 MgSolveInfo = collections.namedtuple("MgSolveInfo", "iters relres converged history hostReads")
 MgSetupInfo = collections.namedtuple("MgSetupInfo", "cgIters minPivotRatio zeroColumns orthonormality hostReads cgHostReadsEstimate")
+MgSetupCoarseInfo = collections.namedtuple("MgSetupCoarseInfo", "theta residual eigensolve minPivotRatio zeroColumns orthonormality")
 CoarseEigInfo = collections.namedtuple("CoarseEigInfo", "iters nConverged opBlocks aMaxUsed aMinLast orthonormality hostReads hostDenseSeconds converged")
 
 
@@ -104,6 +105,24 @@ def computeCoarseOperator(transfer, gauge, kappa, clover=None, comm=None, op=Non
     return op
 
 
+def computeCoarseOperatorCoarse(transfer, finerOp, comm=None, op=None):
+    """The Galerkin operator of a coarse -> coarse Transfer (spin_block_size 1) from the CoarseOperator `finerOp` of its finer lattice
+    (mugiq_hip_compute_coarse_operator_coarse): R_1 M_c P_1, in the storage of every CoarseOperator, so that coarseApply,
+    computeEvalsCoarse(coarseOp=) and coarseEigensolve serve it as they stand.  Built into `op` (a CoarseOperator of the transfer's coarse
+    lattice, n_vec and precision) or a new one; kappa and hasClover are inherited.  A single domain only.  Returns the operator."""
+    if not isinstance(transfer, Transfer) or not isinstance(finerOp, CoarseOperator):
+        raise _lib.MugiqHipError("computeCoarseOperatorCoarse: needs a Transfer and the CoarseOperator of its finer lattice")
+    if op is None:
+        op = CoarseOperator(transfer.Xc, transfer.n_vec, transfer.precision, device=transfer.device)
+    if not isinstance(op, CoarseOperator):
+        raise _lib.MugiqHipError("computeCoarseOperatorCoarse: op must be a CoarseOperator")
+    keep = []
+    d, t, f = op.desc(), transfer.desc(), finerOp.desc()
+    _lib.check(_lib.load().mugiq_hip_compute_coarse_operator_coarse(ctypes.byref(d), ctypes.byref(t), ctypes.byref(f), _comm_ptr(comm, keep), _stream()))
+    op.kappa, op.hasClover = float(d.kappa), bool(d.hasClover)
+    return op
+
+
 def coarseApply(dst, src, op, opType=MUGIQ_EIG_OPERATOR_M, scale=1.0, comm=None):
     """dst_i = scale * A_c src_i for lists of CoarseFields, A_c the form opType of the explicit coarse operator (mugiq_hip_coarse_apply)."""
     dst, src = list(dst), list(src)
@@ -120,7 +139,7 @@ def computeEvalsCoarse(coarseEvecs, transfer=None, gauge=None, kappa=None, opTyp
     """computeEvals for eigenvectors on the coarsest level of an MG hierarchy (mugiq_hip_compute_evals_coarse): the operator is the Galerkin
     operator R M P (MdagM / MMdag: products of the coarse operators; H: R g5 M P).  transfer: a Transfer, or the list [finest, ...].
     coarseOp (a CoarseOperator of computeCoarseOperator): the same check on the explicit operator, without a pass over the fine lattice
-    (mugiq_hip_compute_evals_coarse_operator; one level, one domain); transfer, gauge, kappa and clover are then not looked at -- they are
+    (mugiq_hip_compute_evals_coarse_operator; the operator of any level, one domain); transfer, gauge, kappa and clover are then not looked at -- they are
     in the operator."""
     ev = list(coarseEvecs)
     if coarseOp is not None:
@@ -306,6 +325,41 @@ def mgSetup(gauge, kappa, n_vec=24, geo_block_size=(4, 4, 4, 4), start=None, see
                                            float(info.orthonormality), int(info.hostReads), int(info.cgHostReadsEstimate))
 
 
+def mgSetupCoarse(coarseOp, n_vec, geo_block_size, vectors=None, seed=0, nBlockOrtho=2, rankTol=1e-8, **eigParam):
+    """The second level of an MG hierarchy from the first with nothing from outside: a coarse -> coarse Transfer on the lattice of
+    `coarseOp` and its Galerkin operator.  vectors: n_vec CoarseFields on that lattice (default: the n_vec lowest eigenvectors of MdagM
+    of coarseOp, by coarseEigensolve with eigParam over nKr = max(2 n_vec, n_vec + 8) rounded up to a multiple of 8 and tol = 1e-8 -- first guesses, NOT
+    tuned).  They
+    are packed into V (Transfer.setCoarseVectors), made block-orthonormal (nBlockOrtho passes, rankTol) and followed by
+    computeCoarseOperatorCoarse.  What is exact: H_c = G5 M_c is Hermitian, so an eigenvector w of MdagM can be taken as one of H_c; the
+    blocks of V split by chirality, so w and G5 w lie in the range of P_1, and R_1 w is an eigenvector of the coarsest MdagM with the same
+    eigenvalue.  That holds for the n_vec vectors that went in and for nothing else: how good the other coarsest modes are for loops is
+    not known.  Returns (Transfer, CoarseOperator, MgSetupCoarseInfo(theta, residual, eigensolve, minPivotRatio, zeroColumns,
+    orthonormality)); theta, residual and eigensolve (a CoarseEigInfo) are None when the vectors were given."""
+    if not isinstance(coarseOp, CoarseOperator):
+        raise _lib.MugiqHipError("mgSetupCoarse: coarseOp must be a CoarseOperator")
+    n_vec, bs = int(n_vec), tuple(int(b) for b in geo_block_size)
+    if len(bs) != 4 or any(b < 1 or coarseOp.X[d] % b or (coarseOp.X[d] // b) % 2 for d, b in enumerate(bs)):
+        raise _lib.MugiqHipError("mgSetupCoarse: geo_block_size %s must divide the lattice %s of coarseOp into even extents" % (bs, coarseOp.X))
+    if n_vec < 1 or n_vec > 64:
+        raise _lib.MugiqHipError("mgSetupCoarse: n_vec = %d must be in [1, 64]" % n_vec)
+    theta = res = einfo = None
+    if vectors is None:
+        eigParam.setdefault("nKr", (max(2 * n_vec, n_vec + 8) + 7) // 8 * 8)
+        eigParam.setdefault("tol", 1e-8)
+        vectors, theta, res, _, einfo = coarseEigensolve(coarseOp, MUGIQ_EIG_OPERATOR_MdagM, seed=seed, nConv=n_vec, **eigParam)
+    elif eigParam:
+        raise _lib.MugiqHipError("mgSetupCoarse: eigensolver parameters %s given together with vectors" % sorted(eigParam))
+    vectors = list(vectors)
+    if len(vectors) != n_vec:
+        raise _lib.MugiqHipError("mgSetupCoarse: %d vectors for n_vec = %d" % (len(vectors), n_vec))
+    T = Transfer(coarseOp.X, n_vec, bs, 1, coarseOp.precision, device=coarseOp.device, fine_spin=2, fine_color=coarseOp.n_vec)
+    T.setCoarseVectors(vectors)
+    ratio, zeros = T.blockOrthonormalize(nBlockOrtho, rankTol)
+    op = computeCoarseOperatorCoarse(T, coarseOp)
+    return T, op, MgSetupCoarseInfo(theta, res, einfo, ratio, zeros, T.orthonormality())
+
+
 def _dptr(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
@@ -455,7 +509,7 @@ class Eigsolve_Mugiq:
     (printed beside the recomputed values; zero if not given).  clover: the CloverField of a Wilson-clover operator (None: Wilson).
     transfer (a Transfer or the list [finest, ...]): the computeCoarse branch -- eVecs are CoarseFields on the coarsest level and the
     operator is the Galerkin operator (computeEvalsCoarse); projectVector and solve stay fine-level.  coarseOp (with transfer): the
-    CoarseOperator built for this transfer, gauge, clover and kappa -- computeEvals then runs on it, on the coarse grid alone, and
+    CoarseOperator built for this transfer (for a list: of its last level, by computeCoarseOperatorCoarse), gauge, clover and kappa -- computeEvals then runs on it, on the coarse grid alone, and
     computeEvecs computes the eigenvectors themselves (eVecs may be empty until then): the one eigensolve this class owns."""
 
     def __init__(self, eVecs, gauge, kappa, opType=MUGIQ_EIG_OPERATOR_MdagM, comm=None, massNormalization=False, evals_quda=None, clover=None,
@@ -482,12 +536,19 @@ class Eigsolve_Mugiq:
     def computeEvecs(self, nConv, nKr, start=None, seed=0, allow_unconverged=False, **param):
         """Eigsolve_Mugiq::computeEvecs (lib/eigsolve_mugiq.cpp:278-287) in the computeCoarse branch: the nConv lowest eigenpairs of this
         object's operator (MdagM | MMdag) on its explicit coarse operator, by coarseEigensolve.  For objects built with one finest-level
-        transfer= and its coarseOp=.  Fills eVecs, and eVals_quda with the solver's theta (printEvals then prints it beside what
+        transfer= and its coarseOp=, or with the list transfer=[T0, T1] and the coarseOp of the LAST transfer's coarse lattice (the
+        coarsest level, where the reference computes them).  Fills eVecs, and eVals_quda with the solver's theta (printEvals then prints it beside what
         computeEvals recomputes); the solver's residuals, sigmas and CoarseEigInfo are kept in evecs_res, evecs_sigma and lastEigensolve.
         Returns sigma."""
-        if self.transfer is None or self.coarseOp is None or isinstance(self.transfer, (list, tuple)):
-            raise _lib.MugiqHipError("status 2: Eigsolve_Mugiq.computeEvecs: needs an object built with one finest-level transfer= and its coarseOp= "
+        if self.transfer is None or self.coarseOp is None:
+            raise _lib.MugiqHipError("status 2: Eigsolve_Mugiq.computeEvecs: needs an object built with transfer= and its coarseOp= "
                                      "(fine-operator eigensolves are out of scope)")
+        last = self.transfer[-1] if isinstance(self.transfer, (list, tuple)) and self.transfer else self.transfer
+        if not isinstance(last, Transfer):
+            raise _lib.MugiqHipError("status 2: Eigsolve_Mugiq.computeEvecs: transfer= must be a Transfer or a non-empty list of them")
+        if tuple(self.coarseOp.X) != tuple(last.Xc) or self.coarseOp.n_vec != last.n_vec:
+            raise _lib.MugiqHipError("status 1: Eigsolve_Mugiq.computeEvecs: coarseOp lives on the lattice %s with n_vec %d, the last transfer's coarse "
+                                     "lattice is %s with n_vec %d" % (tuple(self.coarseOp.X), self.coarseOp.n_vec, tuple(last.Xc), last.n_vec))
         ev, theta, res, sig, info = coarseEigensolve(self.coarseOp, self.opType, start, seed, None, allow_unconverged, self.comm, nConv=nConv, nKr=nKr,
                                                      **param)
         n = len(ev)

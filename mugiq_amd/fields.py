@@ -332,9 +332,10 @@ class CoarseField:
 
 
 class CoarseOperator:
-    """The explicit Galerkin coarse operator of a finest-level transfer (MugiqHipCoarseOperator in mugiq_hip.h): nine dense N x N
-    matrices per coarse site, N = 2 n_vec -- Xd, then Y+_mu and Y-_mu for mu = x, y, z, t -- matrix-contiguous and without pad.
-    eigsolve.computeCoarseOperator fills it; kappa and hasClover are those of the last build."""
+    """The explicit Galerkin coarse operator of a transfer (MugiqHipCoarseOperator in mugiq_hip.h): nine dense N x N matrices per coarse
+    site, N = 2 n_vec -- Xd, then Y+_mu and Y-_mu for mu = x, y, z, t -- matrix-contiguous and without pad.
+    eigsolve.computeCoarseOperator fills it from a finest-level transfer, eigsolve.computeCoarseOperatorCoarse from a coarse -> coarse
+    transfer and the operator of the level above; kappa and hasClover are those of the last build."""
 
     def __init__(self, Xc, n_vec, precision=8, device="cuda"):
         self.X = tuple(int(x) for x in Xc)
@@ -422,6 +423,24 @@ class Transfer:
             out = SpinorField(self.X, self.precision, FLOAT2, device=self.device)
         d, o = self.desc(), out.desc()
         _lib.check(_lib.load().mugiq_hip_transfer_get_vector(ctypes.byref(o), ctypes.byref(d), int(j), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return out
+
+    def setCoarseVectors(self, vecs):
+        """V(x; s, c, j) = vecs[j](x; s, c) for n_vec CoarseFields (either precision) on the finer lattice of a coarse -> coarse transfer
+        (spin_block_size 1), with fine_color colours (mugiq_hip_transfer_set_coarse_vectors)."""
+        vecs = list(vecs)
+        d = self.desc()
+        _lib.check(_lib.load().mugiq_hip_transfer_set_coarse_vectors(ctypes.byref(d), coarse_desc_array(vecs) if vecs else None, len(vecs),
+                                                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return self
+
+    def getCoarseVector(self, j, out=None):
+        """column j of the V of a coarse -> coarse transfer as a CoarseField on its finer lattice (mugiq_hip_transfer_get_coarse_vector):
+        `out`, or a new field of the transfer's precision"""
+        if out is None:
+            out = CoarseField(self.X, self.fine_color, self.precision, device=self.device)
+        d, o = self.desc(), out.desc()
+        _lib.check(_lib.load().mugiq_hip_transfer_get_coarse_vector(ctypes.byref(o), ctypes.byref(d), int(j), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return out
 
     def blockOrthonormalize(self, nPasses=2, rankTol=0.0):

@@ -187,6 +187,12 @@ def add_eig_option_mugiq(parser):
     g.add_argument("--eig-max-restarts", dest="eig_max_restarts", type=_nonneg_int, default=100, help="filter / orthonormalise / Rayleigh-Ritz rounds")
     g.add_argument("--mg-nvec", dest="mg_nvec", type=int, default=24, help="null vectors of the MG setup")
     g.add_argument("--mg-block-size", dest="mg_block_size", type=int, nargs=4, default=[4, 4, 4, 4], metavar=("X", "Y", "Z", "T"), help="aggregate")
+    # a second coarse level: this project's own flag names (QUDA's per-level syntax is not mirrored, as for the two flags above)
+    g.add_argument("--mg-coarse-nvec", dest="mg_coarse_nvec", type=int, default=None, metavar="N",
+                   help="with --mg-coarse-block-size: a third level -- N vectors of a coarse -> coarse transfer (the lowest eigenvectors of MdagM "
+                        "of the first coarse operator); the eigensolve then runs on the coarsest operator")
+    g.add_argument("--mg-coarse-block-size", dest="mg_coarse_block_size", type=int, nargs=4, default=None, metavar=("X", "Y", "Z", "T"),
+                   help="aggregate of the second level, on the first coarse lattice")
     return g
 
 
@@ -195,7 +201,9 @@ def compute_coarse_main(args):
     reference's printEvals lines (the solver's theta in the second column) and one JSON line."""
     import torch
     from . import CloverField, GaugeField, Loop_Mugiq
-    from .eigsolve import Eigsolve_Mugiq, MUGIQ_EIG_OPERATOR_MdagM, mgSetup
+    from .eigsolve import Eigsolve_Mugiq, MUGIQ_EIG_OPERATOR_MdagM, mgSetup, mgSetupCoarse
+    if (args.mg_coarse_nvec is None) != (args.mg_coarse_block_size is None):
+        raise SystemExit("--mg-coarse-nvec and --mg-coarse-block-size go together")
     if int(np.prod(args.gridsize)) != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
         raise SystemExit("--eig-compute-coarse runs on one process: the explicit coarse operator is a single-domain object")
     if args.prec != "double":
@@ -209,6 +217,13 @@ def compute_coarse_main(args):
     transfer, coarseOp, setup = mgSetup(gauge, args.kappa, args.mg_nvec, tuple(args.mg_block_size), seed=args.seed, clover=clover)
     nConv = args.eig_nConv if args.eig_nConv is not None else args.n_ev
     nKr = args.eig_nKr if args.eig_nKr is not None else (nConv + 8 + 7) // 8 * 8
+    levels = None
+    if args.mg_coarse_nvec is not None:                                                     # a third level, from the second alone
+        transfer1, coarseOp, setup1 = mgSetupCoarse(coarseOp, args.mg_coarse_nvec, tuple(args.mg_coarse_block_size), seed=args.seed)
+        transfer = [transfer, transfer1]
+        levels = {"mg_coarse_nvec": args.mg_coarse_nvec, "mg_coarse_block_size": list(args.mg_coarse_block_size),
+                  "coarsest_dim": list(coarseOp.X), "setupCoarseOrthonormality": setup1.orthonormality,
+                  "setupCoarseIters": setup1.eigensolve.iters, "setupCoarseOpBlocks": setup1.eigensolve.opBlocks}
     es = Eigsolve_Mugiq([], gauge, args.kappa, MUGIQ_EIG_OPERATOR_MdagM, clover=clover, transfer=transfer, coarseOp=coarseOp)
     sigma = es.computeEvecs(nConv, nKr, seed=args.seed, tol=args.eig_tol, polyDeg=args.eig_poly_deg, aMin=args.eig_amin, aMax=args.eig_amax,
                             maxIter=args.eig_max_restarts)
@@ -218,10 +233,14 @@ def compute_coarse_main(args):
     loop.computeCoarseLoop()
     norm = float(torch.linalg.vector_norm(loop.dataPos_d))
     info = es.lastEigensolve
-    print(json.dumps({"local_dim": list(args.dim), "mg_nvec": args.mg_nvec, "mg_block_size": list(args.mg_block_size), "nConv": nConv, "nKr": nKr,
-                      "iters": info.iters, "opBlocks": info.opBlocks, "aMax": info.aMaxUsed, "hostReads": info.hostReads,
-                      "hostDenseSeconds": info.hostDenseSeconds, "setupOrthonormality": setup.orthonormality, "nLoop": loop.nLoop,
-                      "loop_norm": norm, "data": "computed: MG setup on the device, coarse eigenpairs of MdagM, MG ultra-local loop"}))
+    out = {"local_dim": list(args.dim), "mg_nvec": args.mg_nvec, "mg_block_size": list(args.mg_block_size), "nConv": nConv, "nKr": nKr,
+           "iters": info.iters, "opBlocks": info.opBlocks, "aMax": info.aMaxUsed, "hostReads": info.hostReads,
+           "hostDenseSeconds": info.hostDenseSeconds, "setupOrthonormality": setup.orthonormality, "nLoop": loop.nLoop,
+           "loop_norm": norm, "data": "computed: MG setup on the device, coarse eigenpairs of MdagM, MG ultra-local loop"}
+    if levels is not None:
+        out.update(levels)
+        out["data"] = "computed: MG setup on the device over two coarse levels, eigenpairs of MdagM of the coarsest operator, MG ultra-local loop"
+    print(json.dumps(out))
     loop.close()
     return 0
 
