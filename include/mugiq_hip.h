@@ -866,6 +866,62 @@ int mugiq_hip_mg_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField
                        const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out, double *history_out, int historyStride,
                        int *hostReads_out, const MugiqHipComm *comm, void *stream);
 
+/* ---- the mixed-precision solve (new; csrc/mg_solve.hip): the cycle K in fp32 storage under the fp64 outer GCR, what QUDA's
+ * --prec-sloppy / --prec-precondition give the reference's MG solve.  mugiq_hip_mg_precondition and mugiq_hip_mg_solve above do not
+ * change: they keep refusing precision 4.
+ *
+ * Definitions.  K32 is K of the section above with every vector it stores -- s, t, w, the coarse directions, xc, rc, its input and its
+ * result -- in fp32 storage, on a transfer and a coarse operator of precision 4, in the same sequence of launches.  The Krylov kernels
+ * widen every load to fp64, form all products and sums in fp64 and round once on the store; the scalars (Gram-Schmidt coefficients, nu,
+ * alpha, the partial sums) stay fp64 in device memory.  The stencil computes in the fields' precision (fp32), R, P and M_c sum in fp64.
+ * Every promise of the fp64 path holds: a fixed summation order, no atomics, identical bits from two runs, a right-hand side alone equal
+ * to the same one in any batch, pads neither read nor written; and K32(2^k r) = 2^k K32(r) bit for bit while nothing under- or overflows.
+ *   Mixed solve of M x = b:  the outer solve above, unchanged and in fp64 -- operator applications, directions, residual, tol, history and
+ *   the true residual -- with  p = widen(K32(round(r)))  in place of  p = K(r):  r is rounded to nearest into fp32, and the fp32 result is
+ *   widened (exactly) straight into the direction slot.  r is not scaled: K is homogeneous, and a residual of 1e-10 ||b|| is far inside
+ *   fp32's exponent range.  The outer GCR is flexible, so the rounding costs iterations at most, never accuracy: relres and x meet the
+ *   bounds of mugiq_hip_mg_solve.
+ * Nothing assumes that a V rounded to fp32 is block-orthonormal to better than fp32: the sloppy coarse operator is built from the rounded
+ * V (mugiq_hip_transfer_convert, then mugiq_hip_compute_coarse_operator), so it is the Galerkin operator of that V. */
+
+/* z_i = K32(r_i), i < nVec.  Arguments as for mugiq_hip_mg_precondition with z_h, r_h, transfer and coarseOp ALL of precision 4; gauge of
+ * either precision, clover (NULL | of the gauge field's precision) as the stencil requires.  Refused before any device work: a process
+ * grid or a partitioned axis (MUGIQ_HIP_ERROR_UNSUPPORTED); precision 8 in any of the four objects (MUGIQ_HIP_ERROR_INVALID_ARGUMENT: that is
+ * mugiq_hip_mg_precondition); and everything else mugiq_hip_mg_precondition refuses (parameters, geometry, kappa, hasClover, overlaps).
+ * Work memory (per-stream operator workspace): 3 min(nVec, 8) fine vectors and (2 coarseIters + 2) min(nVec, 8) coarse vectors, all fp32
+ * -- half the bytes of mugiq_hip_mg_precondition per vector -- and the same 0.6 MB of fp64 scalars; an allocation that fails is
+ * MUGIQ_HIP_ERROR_HIP, not an abort. */
+int mugiq_hip_mg_precondition_sloppy(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
+                                     const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer,
+                                     const MugiqHipCoarseOperator *coarseOp, const MugiqHipMgSolveParam *param, const MugiqHipComm *comm,
+                                     void *stream);
+/* x_i = M^-1 b_i, i < nVec, by the mixed solve above.  x_h, b_h, gauge, clover, kappa, param and every output as for mugiq_hip_mg_solve
+ * (fp64 fields; hostReads: max(iters of the block) + 2 per block of 8, nothing is read back inside K32; MUGIQ_HIP_ERROR_NOT_CONVERGED with
+ * all outputs filled).  transferSloppy and coarseOpSloppy: the hierarchy in precision 4 (anything else: MUGIQ_HIP_ERROR_INVALID_ARGUMENT),
+ * coarseOpSloppy built from transferSloppy for this kappa and clover term.  gaugeSloppy, cloverSloppy: the fields the cycle's stencil
+ * reads, e.g. fp32 copies; both NULL: the cycle reads gauge and clover (the stencil takes fp32 spinors on fp64 links).  With a clover
+ * field in the call they are given both or neither; without one cloverSloppy is NULL and gaugeSloppy optional; anything else is
+ * MUGIQ_HIP_ERROR_INVALID_ARGUMENT.  The other limits are those of mugiq_hip_mg_solve.
+ * Work memory (per-stream operator workspace): (2 nKrylov + 2) min(nVec, 8) fine vectors in fp64 -- the directions p_j and q_j, r and
+ * one for the true residual -- which dominate; 5 min(nVec, 8) fine vectors (r and z rounded, s, t, w) and (2 coarseIters + 2) min(nVec, 8)
+ * coarse vectors in fp32, half of what the cycle takes in mugiq_hip_mg_solve; 0.6 MB of scalars.  32^4, nKrylov 16, 8 right-hand sides:
+ * 59 GB are used, as many as by mugiq_hip_mg_solve (58 GB): the two vectors of the hand-over take what the halved cycle saves.  The growth
+ * rule of the workspace is the same. */
+int mugiq_hip_mg_solve_mixed(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                             const MugiqHipCloverField *clover, double kappa, const MugiqHipGaugeField *gaugeSloppy,
+                             const MugiqHipCloverField *cloverSloppy, const MugiqHipTransfer *transferSloppy,
+                             const MugiqHipCoarseOperator *coarseOpSloppy, const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out,
+                             double *history_out, int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream);
+/* dst_i = src_i, i < nVec, between spinor fields of either precision: the two conversions of the mixed solve as an entry point.  One
+ * geometry and field order for all; dst and src each with their own stride and parity offset; no dst overlapping any src.  fp64 -> fp32
+ * rounds to nearest even, once; fp32 -> fp64 is exact; equal precisions copy.  Blocks of 8, pads neither read nor written. */
+int mugiq_hip_mg_convert_precision(const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec, void *stream);
+/* dst->V = src->V between two transfers of equal geometry (X, geoBlockSize, nVec, spinBlockSize, and for a coarse -> coarse transfer the
+ * colours of its finer side) and either precision, each with its own stride and parity offset: a sloppy hierarchy without a round trip
+ * through the host.  One rounding on the store, pads neither read nor written; finest-level and coarse -> coarse transfers alike.
+ * Different geometries, a NULL V or overlapping buffers: MUGIQ_HIP_ERROR_INVALID_ARGUMENT, before any device work. */
+int mugiq_hip_transfer_convert(const MugiqHipTransfer *dst, const MugiqHipTransfer *src, void *stream);
+
 /* ---- MG setup (new; csrc/mg_setup.hip): what QUDA's newMultigridQuda does before MG_Mugiq / Eigsolve_Mugiq see a transfer
  * (tests/loop.cpp:347-365: setup_inv, setup_maxiter, setup_tol, num_setup_iter, n_block_ortho) -- from a gauge field to V and M_c.
  *

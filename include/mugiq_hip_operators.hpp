@@ -247,6 +247,45 @@ inline bool mgSolve(const std::vector<ColorSpinorField> &x, const std::vector<Co
   }
   return st == 0;
 }
+// ---- the mixed-precision solve (csrc/mg_solve.hip; new): the cycle in fp32 storage under the fp64 outer GCR ----
+// z_i = K(r_i) with z, r, transfer and coarseOp all of precision 4 (mugiq_hip_mg_precondition_sloppy)
+inline void mgPreconditionSloppy(const std::vector<ColorSpinorField> &z, const std::vector<ColorSpinorField> &r, const GaugeField &gauge,
+                                 const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer &transfer, const CoarseOperator &coarseOp,
+                                 const MgSolveParam &param = MgSolveParam(), const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (r.empty() || z.size() != r.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgPreconditionSloppy: size mismatch");
+  check(mugiq_hip_mg_precondition_sloppy(z.data(), r.data(), (int)r.size(), &gauge, clover, kappa, &transfer, coarseOp.desc(), &param, comm, stream));
+}
+// mgSolve with p = K(r) in fp32 storage on the sloppy hierarchy (mugiq_hip_mg_solve_mixed); x and b stay fp64.  gaugeSloppy and
+// cloverSloppy NULL: the cycle reads gauge and clover.  Outputs and the return value as for mgSolve
+inline bool mgSolveMixed(const std::vector<ColorSpinorField> &x, const std::vector<ColorSpinorField> &b, const GaugeField &gauge,
+                         const MugiqHipCloverField *clover, double kappa, const GaugeField *gaugeSloppy, const MugiqHipCloverField *cloverSloppy,
+                         const MugiqHipTransfer &transferSloppy, const CoarseOperator &coarseOpSloppy, const MgSolveParam &param, std::vector<int> &iters,
+                         std::vector<double> &relres, std::vector<std::vector<double>> *history = nullptr, int *hostReads = nullptr,
+                         const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (b.empty() || x.size() != b.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgSolveMixed: size mismatch");
+  iters.assign(b.size(), 0);
+  relres.assign(b.size(), 0.0);
+  const int stride = param.maxIter > 0 ? param.maxIter : 1;
+  std::vector<double> hist(history ? b.size() * (size_t)stride : 0);
+  const int st = mugiq_hip_mg_solve_mixed(x.data(), b.data(), (int)b.size(), &gauge, clover, kappa, gaugeSloppy, cloverSloppy, &transferSloppy,
+                                          coarseOpSloppy.desc(), &param, iters.data(), relres.data(), history ? hist.data() : nullptr, stride, hostReads,
+                                          comm, stream);
+  if (st != MUGIQ_HIP_ERROR_NOT_CONVERGED) check(st);
+  if (history) {
+    history->clear();
+    for (size_t i = 0; i < b.size(); i++) history->emplace_back(hist.begin() + i * stride, hist.begin() + i * stride + iters[i]);
+  }
+  return st == 0;
+}
+// dst_i = src_i between spinor fields of either precision (mugiq_hip_mg_convert_precision)
+inline void mgConvertPrecision(const std::vector<ColorSpinorField> &dst, const std::vector<ColorSpinorField> &src, void *stream = nullptr) {
+  if (src.empty() || dst.size() != src.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgConvertPrecision: size mismatch");
+  check(mugiq_hip_mg_convert_precision(dst.data(), src.data(), (int)src.size(), stream));
+}
+// dst.V = src.V between two transfers of equal geometry and either precision (mugiq_hip_transfer_convert): the sloppy hierarchy's V
+inline void transferConvert(const MugiqHipTransfer &dst, const MugiqHipTransfer &src, void *stream = nullptr) {
+  check(mugiq_hip_transfer_convert(&dst, &src, stream));
+}
 // ---- the MG setup (csrc/mg_setup.hip; new) ----
 // Orthonormalise the columns of V inside every (aggregate, coarse spin) block, in place (mugiq_hip_block_orthonormalize).  Returns the
 // info; a minPivotRatio below rankTol throws (status 1) with V filled all the same

@@ -266,6 +266,13 @@ SIGNATURES = {
     "mugiq_hip_mg_solve": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
                                           ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(MgSolveParam), _I4, ctypes.POINTER(ctypes.c_double),
                                           ctypes.POINTER(ctypes.c_double), ctypes.c_int, _I4, _VP, _VP]),
+    "mugiq_hip_mg_precondition_sloppy": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
+                                                        ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(MgSolveParam), _VP, _VP]),
+    "mugiq_hip_mg_solve_mixed": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, _GP, _CP, ctypes.POINTER(TransferDesc),
+                                                ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(MgSolveParam), _I4, ctypes.POINTER(ctypes.c_double),
+                                                ctypes.POINTER(ctypes.c_double), ctypes.c_int, _I4, _VP, _VP]),
+    "mugiq_hip_mg_convert_precision": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _VP]),
+    "mugiq_hip_transfer_convert": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.POINTER(TransferDesc), _VP]),
     "mugiq_hip_block_orthonormalize": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.c_int, ctypes.c_double, ctypes.POINTER(BlockOrthoInfo), _VP]),
     "mugiq_hip_transfer_orthonormality": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.POINTER(ctypes.c_double), _VP]),
     "mugiq_hip_transfer_set_vectors": (ctypes.c_int, [ctypes.POINTER(TransferDesc), _SP, ctypes.c_int, _VP]),

@@ -51,7 +51,7 @@ int fill_identity_links(const MugiqHipSpinorField *f, hipStream_t stream);  // d
 int debug_poison_lds_if_asked(hipStream_t stream);
 // MUGIQ_HIP_DEBUG_WIDE_INDEX=1 (test aid): the Krylov kernels of csrc/mg_solve.hip run in their int64_t instantiation whatever the size
 // of the field (otherwise only from 2^31 complex elements per vector on, 32 GiB, which no test reaches).  Read by every call of
-// mugiq_hip_mg_solve / mugiq_hip_mg_precondition; the order of every sum depends on the shape alone, so the results are the same bits.
+// mugiq_hip_mg_solve / mugiq_hip_mg_precondition, of their mixed-precision twins and of the two conversions; the order of every sum depends on the shape alone, so the results are the same bits.
 bool debug_wide_index_asked();
 // csrc/fused_mfma.hip.  The axial gauge of a (direction, sign) is rebuilt by every call of the matrix-pipe tile (one pass over
 // W_1, 0.2 ms) -- unless the caller, who calls the same entry several times (the driver: interior tiles, then the boundary tiles

@@ -3,11 +3,15 @@
 // and work memory: mugiq_hip_mg_solve in include/mugiq_hip.h.  The stencil, R, P and the coarse application are the library's own entry
 // points, called as they are; what is new here are the Krylov kernels between them, on both levels.
 //
-// One set of kernels serves both levels: a field is a list of rows of complex fp64 numbers (MgLayout; fine FLOAT2: 12 rows of volumeCB per
-// parity, fine FLOAT4: 6 rows of 2 volumeCB, coarse: 2 n_vec rows of volumeCB_c), every lane takes whole complex numbers (16-byte accesses,
-// consecutive along a row), pads are never touched.  blockIdx.y is the right-hand side; a right-hand side whose `active` bit is clear is not
-// touched.  Every sum is taken per lane over its elements in ascending order, over the wave by shuffles, over the workgroup's four waves
-// and then over the workgroups by mg_final_sum_kernel, each in a fixed order that depends on the shape of the field alone: no atomics, two
+// One set of kernels serves both levels and both storages: a field is a list of rows of complex numbers (MgLayout; fine FLOAT2: 12 rows of
+// volumeCB per parity, fine FLOAT4: 6 rows of 2 volumeCB, coarse: 2 n_vec rows of volumeCB_c) stored as Cplx<F>, F = double or float.  Every
+// lane takes one whole complex number per access (16 bytes in fp64, 8 bytes in fp32, consecutive along a row: a wave's access is one
+// contiguous run of 1 KiB or 512 B), widens it to fp64 on the load (ldz), forms every product and every sum in fp64 and rounds once on the
+// store (stz); the scalars -- partial sums, Gram-Schmidt coefficients, nu, alpha -- are fp64 in device memory for either storage.  The
+// element a lane takes does not depend on F, so the order of every sum is the same in both storages, and no alignment beyond that of one
+// complex number is asked of a row (an odd stride or a row that cuts a wave needs no peeling).  Pads are never touched.  blockIdx.y is
+// the right-hand side; a right-hand side whose `active` bit is clear is not touched.  Every sum is taken per lane over its elements in
+// ascending order, over the wave by shuffles, over the workgroup's four waves and then over the workgroups by mg_final_sum_kernel, each in a fixed order that depends on the shape of the field alone: no atomics, two
 // runs give the same bits, and a right-hand side has the same sums wherever it stands in a block.
 //
 // The Krylov directions of a level lie behind one base pointer, direction j of right-hand side v at (j nb + v) vecElems, so that a kernel
@@ -45,16 +49,18 @@ template <typename I> __device__ inline int64_t mg_offset(const MgLayout &L, I e
   return pty * L.po + (int64_t)row * L.rowStride + (int64_t)(rem - row * rowLen);
 }
 
-typedef double mg_vec2 __attribute__((ext_vector_type(2)));
-__device__ inline Z ldz(const Z *p, int64_t i) {
-  const mg_vec2 t = *as_global(reinterpret_cast<const mg_vec2 *>(p) + i);
-  return Z{t.x, t.y};
+// one complex number of storage F, widened to fp64 / rounded once from fp64 (F = double: the same bits both ways)
+template <typename F> __device__ inline Z ldz(const Cplx<F> *p, int64_t i) {
+  typedef F vec2 __attribute__((ext_vector_type(2)));
+  const vec2 t = *as_global(reinterpret_cast<const vec2 *>(p) + i);
+  return Z{(double)t.x, (double)t.y};
 }
-__device__ inline void stz(Z *p, int64_t i, const Z &v) {
-  mg_vec2 t;
-  t.x = v.re;
-  t.y = v.im;
-  *as_global(reinterpret_cast<mg_vec2 *>(p) + i) = t;
+template <typename F> __device__ inline void stz(Cplx<F> *p, int64_t i, const Z &v) {
+  typedef F vec2 __attribute__((ext_vector_type(2)));
+  vec2 t;
+  t.x = (F)v.re;
+  t.y = (F)v.im;
+  *as_global(reinterpret_cast<vec2 *>(p) + i) = t;
 }
 
 // v[0 .. nUsed) summed over the workgroup -> out[0 .. nUsed): down the wave by shuffles, then the four waves in ascending order
@@ -74,19 +80,19 @@ template <int NS> __device__ inline void mg_group_sum(double (&v)[NS], int nUsed
   if (t < nUsed) out[t] = ((sh[0][t] + sh[1][t]) + sh[2][t]) + sh[3][t];
 }
 
-struct MgVecs {
-  Z *p[kMgBlock];
+template <typename F> struct MgVecs {
+  Cplx<F> *p[kMgBlock];
 };
 
 // multi-dot: c_j = <q_j, q_k> for all j < k, from the q_k the operator left (classical Gram-Schmidt): slots (2j, 2j + 1)
-template <typename I>
-__global__ __launch_bounds__(kMgThreads) void mg_multidot_kernel(const Z *Q, int64_t vecElems, int nb, int k, MgLayout L, unsigned active, double *partial) {
+template <typename F, typename I>
+__global__ __launch_bounds__(kMgThreads) void mg_multidot_kernel(const Cplx<F> *Q, int64_t vecElems, int nb, int k, MgLayout L, unsigned active, double *partial) {
   const int v = blockIdx.y;
   if (!((active >> v) & 1u)) return;
   double acc[kMgSlots];
 #pragma unroll
   for (int s = 0; s < kMgSlots; s++) acc[s] = 0.0;
-  const Z *qk = Q + ((int64_t)k * nb + v) * vecElems;
+  const Cplx<F> *qk = Q + ((int64_t)k * nb + v) * vecElems;
   for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
     const int64_t off = mg_offset<I>(L, e);
     const Z q = ldz(qk, off);
@@ -106,8 +112,8 @@ __global__ __launch_bounds__(kMgThreads) void mg_multidot_kernel(const Z *Q, int
 
 // multi-axpy: p_k -= sum_j c_j p_j, q_k -= sum_j c_j q_j with c from device memory; in the same pass ||q_k||^2 (slot 0) and <q_k, r>
 // (slots 1, 2) of the orthogonalised q_k
-template <typename I>
-__global__ __launch_bounds__(kMgThreads) void mg_multiaxpy_kernel(Z *P, Z *Q, int64_t vecElems, int nb, int k, MgVecs R, const double *coef, MgLayout L,
+template <typename F, typename I>
+__global__ __launch_bounds__(kMgThreads) void mg_multiaxpy_kernel(Cplx<F> *P, Cplx<F> *Q, int64_t vecElems, int nb, int k, MgVecs<F> R, const double *coef, MgLayout L,
                                                                  unsigned active, double *partial) {
   const int v = blockIdx.y;
   if (!((active >> v) & 1u)) return;
@@ -115,7 +121,7 @@ __global__ __launch_bounds__(kMgThreads) void mg_multiaxpy_kernel(Z *P, Z *Q, in
 #pragma unroll
   for (int s = 0; s < 2 * (kMgMaxDir - 1); s++) c[s] = s < 2 * k ? coef[v * kMgSlots + s] : 0.0;
   double acc[3] = {0.0, 0.0, 0.0};
-  Z *pk = P + ((int64_t)k * nb + v) * vecElems, *qk = Q + ((int64_t)k * nb + v) * vecElems;
+  Cplx<F> *pk = P + ((int64_t)k * nb + v) * vecElems, *qk = Q + ((int64_t)k * nb + v) * vecElems;
   for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
     const int64_t off = mg_offset<I>(L, e);
     Z q = ldz(qk, off);
@@ -145,16 +151,16 @@ __global__ __launch_bounds__(kMgThreads) void mg_multiaxpy_kernel(Z *P, Z *Q, in
 
 // update: p_k /= nu, q_k /= nu (nu = 0: a zero direction), x += alpha p_k (xZero: x = alpha p_k), r -= alpha q_k, ||r||^2 into slot 0;
 // sc[4 v] = (nu, Re alpha, Im alpha) from mg_final_sum_kernel.  Pnext != NULL: the new r is also the next direction p_{k+1} (GCRfix)
-template <typename I>
-__global__ __launch_bounds__(kMgThreads) void mg_update_kernel(Z *P, Z *Q, int64_t vecElems, int nb, int k, MgVecs X, MgVecs R, const double *sc, int xZero,
-                                                              Z *Pnext, MgLayout L, unsigned active, double *partial) {
+template <typename F, typename I>
+__global__ __launch_bounds__(kMgThreads) void mg_update_kernel(Cplx<F> *P, Cplx<F> *Q, int64_t vecElems, int nb, int k, MgVecs<F> X, MgVecs<F> R, const double *sc, int xZero,
+                                                              Cplx<F> *Pnext, MgLayout L, unsigned active, double *partial) {
   const int v = blockIdx.y;
   if (!((active >> v) & 1u)) return;
   const double nu = sc[4 * v];
   const Z alpha{sc[4 * v + 1], sc[4 * v + 2]}, malpha{-alpha.re, -alpha.im};
   double acc[1] = {0.0};
-  Z *pk = P + ((int64_t)k * nb + v) * vecElems, *qk = Q + ((int64_t)k * nb + v) * vecElems;
-  Z *pn = Pnext ? Pnext + ((int64_t)(k + 1) * nb + v) * vecElems : nullptr;
+  Cplx<F> *pk = P + ((int64_t)k * nb + v) * vecElems, *qk = Q + ((int64_t)k * nb + v) * vecElems;
+  Cplx<F> *pn = Pnext ? Pnext + ((int64_t)(k + 1) * nb + v) * vecElems : nullptr;
   for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
     const int64_t off = mg_offset<I>(L, e);
     Z p = ldz(pk, off), q = ldz(qk, off);
@@ -180,7 +186,7 @@ __global__ __launch_bounds__(kMgThreads) void mg_update_kernel(Z *P, Z *Q, int64
 }
 
 // <t, s> into slots 0, 1 and <t, t> into slot 2 (an MR step; with t = s: a norm)
-template <typename I> __global__ __launch_bounds__(kMgThreads) void mg_dot2_kernel(MgVecs T, MgVecs S, MgLayout L, unsigned active, double *partial) {
+template <typename F, typename I> __global__ __launch_bounds__(kMgThreads) void mg_dot2_kernel(MgVecs<F> T, MgVecs<F> S, MgLayout L, unsigned active, double *partial) {
   const int v = blockIdx.y;
   if (!((active >> v) & 1u)) return;
   double acc[3] = {0.0, 0.0, 0.0};
@@ -199,8 +205,8 @@ template <typename I> __global__ __launch_bounds__(kMgThreads) void mg_dot2_kern
 
 // the update of an MR step: z += alpha s (zZero: z = alpha s), sOut = s - alpha t (sOut NULL: the last step of K, s is not needed again);
 // sc[4 v] = (Re alpha, Im alpha) from mg_final_sum_kernel.  sOut may be s
-template <typename I>
-__global__ __launch_bounds__(kMgThreads) void mg_mr_update_kernel(MgVecs Zv, MgVecs S, MgVecs T, MgVecs SOut, const double *sc, int zZero, int writeS,
+template <typename F, typename I>
+__global__ __launch_bounds__(kMgThreads) void mg_mr_update_kernel(MgVecs<F> Zv, MgVecs<F> S, MgVecs<F> T, MgVecs<F> SOut, const double *sc, int zZero, int writeS,
                                                                  MgLayout L, unsigned active) {
   const int v = blockIdx.y;
   if (!((active >> v) & 1u)) return;
@@ -219,8 +225,8 @@ __global__ __launch_bounds__(kMgThreads) void mg_mr_update_kernel(MgVecs Zv, MgV
 }
 
 // c = sa a + sb b on the elements (a or b NULL: that term is zero; c may be a or b)
-template <typename I>
-__global__ __launch_bounds__(kMgThreads) void mg_axpby_kernel(MgVecs C, MgVecs A, double sa, MgVecs B, double sb, MgLayout L, unsigned active) {
+template <typename F, typename I>
+__global__ __launch_bounds__(kMgThreads) void mg_axpby_kernel(MgVecs<F> C, MgVecs<F> A, double sa, MgVecs<F> B, double sb, MgLayout L, unsigned active) {
   const int v = blockIdx.y;
   if (!((active >> v) & 1u)) return;
   for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
@@ -237,6 +243,17 @@ __global__ __launch_bounds__(kMgThreads) void mg_axpby_kernel(MgVecs C, MgVecs A
     }
     stz(C.p[v], off, o);
   }
+}
+
+// d = s on the elements, between two storages and two layouts of the same rows (Ld.nRows == Ls.nRows, Ld.rowLen == Ls.rowLen): the
+// precision hand-over of the mixed solve, and the copy of V between two transfers.  fp64 -> fp32 rounds to nearest even, once (what
+// numpy's astype(complex64) does); fp32 -> fp64 is exact.  Pads of neither side are touched
+template <typename FD, typename FS, typename I>
+__global__ __launch_bounds__(kMgThreads) void mg_convert_kernel(MgVecs<FD> D, MgVecs<FS> S, MgLayout Ld, MgLayout Ls, unsigned active) {
+  const int v = blockIdx.y;
+  if (!((active >> v) & 1u)) return;
+  for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)Ls.total; e += (I)gridDim.x * kMgThreads)
+    stz(D.p[v], mg_offset<I>(Ld, e), ldz(S.p[v], mg_offset<I>(Ls, e)));
 }
 
 // The sums of the last pass over its workgroups, in ascending order, one lane per (right-hand side, slot), and what the next kernel needs
@@ -291,17 +308,39 @@ MgLayout coarse_layout(const MugiqHipCoarseField &f) {
   L.total = 2 * L.nRows * L.rowLen;
   return L;
 }
-size_t fine_bytes(const MugiqHipSpinorField &f) { return align256((size_t)2 * (size_t)f.parity_offset * sizeof(Z)); }
-size_t coarse_bytes(const MugiqHipCoarseField &f) { return align256((size_t)2 * (size_t)f.parity_offset * sizeof(Z)); }
+// rows of V: a finest-level transfer has 12 n_vec of them per parity, a coarse -> coarse one parity_offset / stride (2 nc n_vec, no gap)
+MgLayout transfer_layout(const MugiqHipTransfer &T) {
+  MgLayout L;
+  L.nRows = T.spinBlockSize == 2 ? 12 * T.nVec : (int)(T.parity_offset / T.stride);
+  L.rowLen = ((int64_t)T.X[0] * T.X[1] * T.X[2] * T.X[3]) / 2;
+  L.rowStride = T.stride;
+  L.po = T.parity_offset;
+  L.total = 2 * L.nRows * L.rowLen;
+  return L;
+}
+template <typename F> size_t fine_bytes(const MugiqHipSpinorField &f) { return align256((size_t)2 * (size_t)f.parity_offset * sizeof(Cplx<F>)); }
+template <typename F> size_t coarse_bytes(const MugiqHipCoarseField &f) { return align256((size_t)2 * (size_t)f.parity_offset * sizeof(Cplx<F>)); }
 size_t scalar_bytes() { return align256(sizeof(double) * ((size_t)kMgBlock * kMgMaxGroups * kMgSlots + kMgBlock * kMgSlots + 2 * 4 * kMgBlock)); }
 
-// one level's Krylov state in the workspace and the launches on it
-struct MgLevel {
+// D_i = S_i for the active i < n, from storage FS in layout Ls to storage FD in layout Ld (mg_convert_kernel)
+template <typename FD, typename FS>
+int mg_convert(const MgVecs<FD> &D, const MgVecs<FS> &S, const MgLayout &Ld, const MgLayout &Ls, int n, unsigned active, bool wide, hipStream_t stream) {
+  const dim3 grid((unsigned)std::min<int64_t>(kMgMaxGroups, (Ls.total + kMgThreads - 1) / kMgThreads), n);
+  if (!wide && Ls.total < (int64_t(1) << 31)) hipLaunchKernelGGL((mg_convert_kernel<FD, FS, uint32_t>), grid, dim3(kMgThreads), 0, stream, D, S, Ld, Ls, active);
+  else hipLaunchKernelGGL((mg_convert_kernel<FD, FS, int64_t>), grid, dim3(kMgThreads), 0, stream, D, S, Ld, Ls, active);
+  MUGIQ_CHECK_HIP(hipGetLastError());
+  return MUGIQ_HIP_SUCCESS;
+}
+
+// one level's Krylov state in the workspace and the launches on it, for vectors stored as Cplx<F>
+template <typename F> struct MgLevel {
+  typedef Cplx<F> C;
+  typedef MgVecs<F> Vecs;
   MgLayout L;
   int nb = 0, nGroups = 0;
-  bool wide = false;  // MUGIQ_HIP_DEBUG_WIDE_INDEX, as the call found it (MgSolver::reserve)
+  bool wide = false;  // MUGIQ_HIP_DEBUG_WIDE_INDEX, as the call found it (MgSolver::init)
   int64_t vecElems = 0;
-  Z *P = nullptr, *Q = nullptr;  // nDir x nb vectors each
+  C *P = nullptr, *Q = nullptr;  // nDir x nb vectors each
   double *partial = nullptr, *coef = nullptr, *sc = nullptr, *res = nullptr;  // shared by both levels: the stream orders their passes
   hipStream_t stream = nullptr;
 
@@ -315,7 +354,7 @@ struct MgLevel {
     sc = coef + kMgBlock * kMgSlots;
     res = sc + 4 * kMgBlock;
   }
-  Z *dir(Z *base, int j, int v) const { return base + ((int64_t)j * nb + v) * vecElems; }
+  C *dir(C *base, int j, int v) const { return base + ((int64_t)j * nb + v) * vecElems; }
   bool narrow() const { return !wide && L.total < (int64_t(1) << 31); }
   dim3 grid(int n) const { return dim3(nGroups, n); }
 
@@ -326,42 +365,49 @@ struct MgLevel {
   }
 #define MUGIQ_MG_LAUNCH(kernel, n, ...)                                                                                   \
   do {                                                                                                                    \
-    if (narrow()) hipLaunchKernelGGL(kernel<uint32_t>, grid(n), dim3(kMgThreads), 0, stream, __VA_ARGS__);                \
-    else hipLaunchKernelGGL(kernel<int64_t>, grid(n), dim3(kMgThreads), 0, stream, __VA_ARGS__);                          \
+    if (narrow()) hipLaunchKernelGGL((kernel<F, uint32_t>), grid(n), dim3(kMgThreads), 0, stream, __VA_ARGS__);                \
+    else hipLaunchKernelGGL((kernel<F, int64_t>), grid(n), dim3(kMgThreads), 0, stream, __VA_ARGS__);                          \
     MUGIQ_CHECK_HIP(hipGetLastError());                                                                                   \
   } while (0)
 
-  int axpby(const MgVecs &c, const MgVecs *a, double sa, const MgVecs *b, double sb, int n, unsigned active) const {
-    const MgVecs none{};
+  int axpby(const Vecs &c, const Vecs *a, double sa, const Vecs *b, double sb, int n, unsigned active) const {
+    const Vecs none{};
     MUGIQ_MG_LAUNCH(mg_axpby_kernel, n, c, a ? *a : none, sa, b ? *b : none, sb, L, active);
     return MUGIQ_HIP_SUCCESS;
   }
   // <t, s> and <t, t> -> mode kMgFinMr: alpha of an MR step in sc; kMgFinRaw: the sums in res
-  int dot2(const MgVecs &t, const MgVecs &s, int n, unsigned active, int mode, double omega) const {
+  int dot2(const Vecs &t, const Vecs &s, int n, unsigned active, int mode, double omega) const {
     MUGIQ_MG_LAUNCH(mg_dot2_kernel, n, t, s, L, active, partial);
     return final_sum(3, active, mode, omega);
   }
-  int mr_update(const MgVecs &z, const MgVecs &s, const MgVecs &t, const MgVecs *sOut, bool zZero, int n, unsigned active) const {
-    const MgVecs none{};
+  int mr_update(const Vecs &z, const Vecs &s, const Vecs &t, const Vecs *sOut, bool zZero, int n, unsigned active) const {
+    const Vecs none{};
     MUGIQ_MG_LAUNCH(mg_mr_update_kernel, n, z, s, t, sOut ? *sOut : none, sc, zZero ? 1 : 0, sOut ? 1 : 0, L, active);
     return MUGIQ_HIP_SUCCESS;
   }
   // step k of the GCR recurrence once q_k = A p_k is there: orthogonalise against the k stored directions, normalise, update x and r.
   // Leaves ||r||^2 of the step in res (wantNorm) for the host to fetch
-  int gcr_step(int k, const MgVecs &x, const MgVecs &r, bool xZero, bool copyNext, bool wantNorm, int n, unsigned active) const {
+  int gcr_step(int k, const Vecs &x, const Vecs &r, bool xZero, bool copyNext, bool wantNorm, int n, unsigned active) const {
     if (k > 0) {
       MUGIQ_MG_LAUNCH(mg_multidot_kernel, n, Q, vecElems, nb, k, L, active, partial);
       if (int st = final_sum(2 * k, active, kMgFinCoef, 0.0)) return st;
     }
     MUGIQ_MG_LAUNCH(mg_multiaxpy_kernel, n, P, Q, vecElems, nb, k, r, coef, L, active, partial);
     if (int st = final_sum(3, active, kMgFinNorm, 0.0)) return st;
-    MUGIQ_MG_LAUNCH(mg_update_kernel, n, P, Q, vecElems, nb, k, x, r, sc, xZero ? 1 : 0, copyNext ? P : (Z *)nullptr, L, active, partial);
+    MUGIQ_MG_LAUNCH(mg_update_kernel, n, P, Q, vecElems, nb, k, x, r, sc, xZero ? 1 : 0, copyNext ? P : (C *)nullptr, L, active, partial);
     return wantNorm ? final_sum(1, active, kMgFinRaw, 0.0) : MUGIQ_HIP_SUCCESS;
   }
 #undef MUGIQ_MG_LAUNCH
 };
 
-struct MgSolver {
+// which fine vectors of a block a solver keeps in the workspace
+enum { kMgSetS = 1, kMgSetT = 2, kMgSetW = 4, kMgSetR = 8, kMgSetZ = 16, kMgSetsOfK = kMgSetS | kMgSetT | kMgSetW };
+
+// the operators, the parameters and the workspace vectors of one storage F: with F = double the whole solve, or the outer iteration of
+// the mixed solve; with F = float the cycle K of the mixed solve, on the sloppy fields
+template <typename F> struct MgSolver {
+  typedef Cplx<F> C;
+  typedef MgVecs<F> Vecs;
   const MugiqHipGaugeField *gauge;
   const MugiqHipCloverField *clover;
   double kappa;
@@ -369,34 +415,37 @@ struct MgSolver {
   const MugiqHipCoarseOperator *op;
   MugiqHipMgSolveParam prm;
   hipStream_t stream;
-  int nb;
-  MgLevel fine, coarse;
-  MugiqHipSpinorField s[kMgBlock], t[kMgBlock], w[kMgBlock], r[kMgBlock];  // r: the solver's recursive residual
+  int nb, nDirFine, sets;
+  bool withCoarse;
+  size_t fb, cb;
+  MgLevel<F> fine, coarse;
+  // r: the solver's recursive residual (mixed solve, F = float: its rounded copy); zk: K's result before it is widened (mixed solve only)
+  MugiqHipSpinorField s[kMgBlock], t[kMgBlock], w[kMgBlock], r[kMgBlock], zk[kMgBlock];
   MugiqHipCoarseField xc[kMgBlock], rc[kMgBlock];
   MugiqHipSpinorField fineLike;
   MugiqHipCoarseField coarseLike;
 
-  static MgVecs vecs(const MugiqHipSpinorField *f, int n) {
-    MgVecs m{};
-    for (int i = 0; i < n; i++) m.p[i] = static_cast<Z *>(f[i].data);
+  static Vecs vecs(const MugiqHipSpinorField *f, int n) {
+    Vecs m{};
+    for (int i = 0; i < n; i++) m.p[i] = static_cast<C *>(f[i].data);
     return m;
   }
-  static MgVecs vecs(const MugiqHipCoarseField *f, int n) {
-    MgVecs m{};
-    for (int i = 0; i < n; i++) m.p[i] = static_cast<Z *>(f[i].data);
+  static Vecs vecs(const MugiqHipCoarseField *f, int n) {
+    Vecs m{};
+    for (int i = 0; i < n; i++) m.p[i] = static_cast<C *>(f[i].data);
     return m;
   }
-  MugiqHipSpinorField fine_dir(Z *base, int j, int v) const {
+  MugiqHipSpinorField fine_dir(C *base, int j, int v) const {
     MugiqHipSpinorField f = fineLike;
     f.data = fine.dir(base, j, v);
     return f;
   }
-  MugiqHipCoarseField coarse_dir(Z *base, int j, int v) const {
+  MugiqHipCoarseField coarse_dir(C *base, int j, int v) const {
     MugiqHipCoarseField f = coarseLike;
     f.data = coarse.dir(base, j, v);
     return f;
   }
-  template <typename F> static int gather(const F *set, int n, unsigned mask, F *out) {
+  template <typename T> static int gather(const T *set, int n, unsigned mask, T *out) {
     int m = 0;
     for (int i = 0; i < n; i++)
       if ((mask >> i) & 1u) out[m++] = set[i];
@@ -410,52 +459,55 @@ struct MgSolver {
     return mugiq_hip_wilson_clover_apply(d, sr, m, gauge, clover, kappa, MUGIQ_HIP_EIG_OPERATOR_M, 1.0, nullptr, stream);
   }
 
-  // the work memory, carved from the stream's operator workspace: the scalars, then per right-hand side of a block 2 nDirFine fine
-  // directions, s, t, w (and r for the solver), and on the coarse level 2 coarseIters directions, xc, rc.
+  // The work memory is carved from the stream's operator workspace: the scalars, then per right-hand side of a block 2 nDirFine fine
+  // directions and the fine vectors of `sets` (K: s, t, w; the solver: r as well), and with the coarse level 2 coarseIters directions,
+  // xc, rc.  init() fixes the layouts and sizes (vectors laid out like `like`, stored as Cplx<F>), vector_bytes() is this solver's share
+  // and carve() places it; the mixed solve carves two solvers from one reservation.
   // apply_M calls the public stencil entry, which reserves the SAME arena for itself (csrc/wilson.hip, wilson_apply_impl) and takes its
   // start as the send buffer of its halo exchange.  That is safe here for two reasons, both of which this file depends on: on a single
   // domain with the form M its request is 256 bytes, so the arena, which only ever grows, neither moves nor is freed under us; and
   // without a partitioned axis nothing is packed into that send buffer.  The first kStencilHead bytes are left unused all the same, so
   // that a send buffer that did get written would not land in `partial`.
-  int reserve(const MugiqHipSpinorField &like, int nDirFine, int nVecRhs, bool withR) {
+  static constexpr size_t kStencilHead = 4096;
+  void init(const MugiqHipSpinorField &like, int nDirFine_, int nVecRhs, int sets_, bool withCoarse_) {
     nb = std::min(nVecRhs, kMgBlock);
+    nDirFine = nDirFine_, sets = sets_, withCoarse = withCoarse_ && prm.coarseIters > 0;
     fineLike = like;
+    fineLike.precision = (int)sizeof(F);
+    fineLike.data = nullptr;
     for (int d = 0; d < 4; d++)
       for (int b = 0; b < 2; b++) fineLike.ghost[d][b] = nullptr;
     coarseLike = coarse_side_layout(*transfer);
-    const size_t fb = fine_bytes(like), cb = coarse_bytes(coarseLike);
-    const int nC = prm.coarseIters;
-    constexpr size_t kStencilHead = 4096;
-    const size_t bytes = kStencilHead + scalar_bytes() + (size_t)(2 * nDirFine + (withR ? 4 : 3)) * nb * fb + (size_t)(nC > 0 ? 2 * nC + 2 : 0) * nb * cb + 256;
-    void *ws = nullptr;
-    if (int st = stream_operator_workspace(&ws, bytes, stream)) return st;
-    unsigned char *cur = static_cast<unsigned char *>(ws) + kStencilHead;
-    fine.set_scalars(cur);
-    coarse.set_scalars(cur);
-    cur += scalar_bytes();
+    fb = fine_bytes<F>(like), cb = coarse_bytes<F>(coarseLike);
     fine.stream = coarse.stream = stream;
     fine.nb = coarse.nb = nb;
     fine.wide = coarse.wide = debug_wide_index_asked();
     fine.set_layout(fine_layout(like));
-    fine.vecElems = (int64_t)(fb / sizeof(Z));
-    fine.P = reinterpret_cast<Z *>(cur);
+    fine.vecElems = (int64_t)(fb / sizeof(C));
+    coarse.set_layout(coarse_layout(coarseLike));
+    coarse.vecElems = (int64_t)(cb / sizeof(C));
+  }
+  int n_sets() const { return __builtin_popcount((unsigned)sets); }
+  size_t vector_bytes() const { return (size_t)(2 * nDirFine + n_sets()) * nb * fb + (size_t)(withCoarse ? 2 * prm.coarseIters + 2 : 0) * nb * cb; }
+  unsigned char *carve(unsigned char *scalars, unsigned char *cur) {
+    fine.set_scalars(scalars);
+    coarse.set_scalars(scalars);
+    fine.P = reinterpret_cast<C *>(cur);
     cur += (size_t)nDirFine * nb * fb;
-    fine.Q = reinterpret_cast<Z *>(cur);
+    fine.Q = reinterpret_cast<C *>(cur);
     cur += (size_t)nDirFine * nb * fb;
-    MugiqHipSpinorField *sets[4] = {s, t, w, r};
-    for (int k = 0; k < (withR ? 4 : 3); k++)
-      for (int i = 0; i < nb; i++) {
-        MugiqHipSpinorField *set = sets[k];
-        set[i] = fineLike;
-        set[i].data = cur;
+    MugiqHipSpinorField *all[5] = {s, t, w, r, zk};
+    for (int k = 0; k < 5; k++)
+      for (int i = 0; i < nb && ((sets >> k) & 1); i++) {
+        all[k][i] = fineLike;
+        all[k][i].data = cur;
         cur += fb;
       }
-    coarse.set_layout(coarse_layout(coarseLike));
-    coarse.vecElems = (int64_t)(cb / sizeof(Z));
-    if (nC > 0) {
-      coarse.P = reinterpret_cast<Z *>(cur);
+    if (withCoarse) {
+      const int nC = prm.coarseIters;
+      coarse.P = reinterpret_cast<C *>(cur);
       cur += (size_t)nC * nb * cb;
-      coarse.Q = reinterpret_cast<Z *>(cur);
+      coarse.Q = reinterpret_cast<C *>(cur);
       cur += (size_t)nC * nb * cb;
       MugiqHipCoarseField *csets[2] = {xc, rc};
       for (auto *set : csets)
@@ -465,13 +517,22 @@ struct MgSolver {
           cur += cb;
         }
     }
+    return cur;
+  }
+  // one solver alone on the workspace
+  int reserve(const MugiqHipSpinorField &like, int nDirFine_, int nVecRhs, bool withR) {
+    init(like, nDirFine_, nVecRhs, kMgSetsOfK | (withR ? kMgSetR : 0), true);
+    void *ws = nullptr;
+    if (int st = stream_operator_workspace(&ws, kStencilHead + scalar_bytes() + vector_bytes() + 256, stream)) return st;
+    unsigned char *cur = static_cast<unsigned char *>(ws) + kStencilHead;
+    carve(cur, cur + scalar_bytes());
     return MUGIQ_HIP_SUCCESS;
   }
 
   // one MR step on (z, sIn): t = M sIn, alpha on the device, z += alpha sIn, s = sIn - alpha t (last: s is not needed again)
   int mr_step(const MugiqHipSpinorField *z, const MugiqHipSpinorField *sIn, bool zZero, bool last, int n, unsigned active) const {
     if (int st = apply_M(t, sIn, n, active)) return st;
-    const MgVecs tv = vecs(t, n), sv = vecs(sIn, n), so = vecs(s, n);
+    const Vecs tv = vecs(t, n), sv = vecs(sIn, n), so = vecs(s, n);
     if (int st = fine.dot2(tv, sv, n, active, kMgFinMr, prm.omega)) return st;
     return fine.mr_update(vecs(z, n), sv, tv, last ? nullptr : &so, zZero, n, active);
   }
@@ -481,7 +542,7 @@ struct MgSolver {
     const int nC = prm.coarseIters;
     MugiqHipCoarseField p0[kMgBlock];
     for (int i = 0; i < n; i++) p0[i] = coarse_dir(coarse.P, 0, i);
-    const MgVecs rv = vecs(rc, n), xv = vecs(xc, n), pv = vecs(p0, n);
+    const Vecs rv = vecs(rc, n), xv = vecs(xc, n), pv = vecs(p0, n);
     if (int st = coarse.axpby(pv, &rv, 1.0, nullptr, 0.0, n, active)) return st;
     for (int k = 0; k < nC; k++) {
       MugiqHipCoarseField p[kMgBlock], q[kMgBlock], pa[kMgBlock], qa[kMgBlock];
@@ -518,12 +579,12 @@ struct MgSolver {
       gather(xc, n, active, ca);
       gather(zZero ? z : w, n, active, fa);
       if ((st = mugiq_hip_prolongate_batched(fa, ca, m, transfer, stream))) return st;
-      const MgVecs zv = vecs(z, n), wv = vecs(w, n);
+      const Vecs zv = vecs(z, n), wv = vecs(w, n);
       if (!zZero && (st = fine.axpby(zv, &zv, 1.0, &wv, 1.0, n, active))) return st;
       zZero = false;
       if (prm.nuPost > 0) {  // s = r - M z, one application
         if ((st = apply_M(t, z, n, active))) return st;
-        const MgVecs rv = vecs(r, n), tv = vecs(t, n);
+        const Vecs rv = vecs(r, n), tv = vecs(t, n);
         if ((st = fine.axpby(vecs(s, n), &rv, 1.0, &tv, -1.0, n, active))) return st;
         sIn = s;
       }
@@ -561,10 +622,12 @@ int check_param(const MugiqHipMgSolveParam *p, const char *who) {
   return MUGIQ_HIP_SUCCESS;
 }
 
-// everything the two entry points share, before any device work: out (written) and in (read) are nVec fp64 fields of one layout
+// everything the entry points share, before any device work: out (written) and in (read) are nVec fields of one layout and of precision
+// fieldPrec, the transfer and the coarse operator of precision hierPrec.  (8, 8): the fp64 entries, which refuse anything else as
+// UNSUPPORTED; (4, 4): the sloppy cycle; (8, 4): the mixed solve
 int check_problem(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in, int nVec, const char *outName, const char *inName,
                   const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *op,
-                  const MugiqHipMgSolveParam *param, double kappa, const MugiqHipComm *comm, const char *who) {
+                  const MugiqHipMgSolveParam *param, double kappa, const MugiqHipComm *comm, const char *who, int fieldPrec = 8, int hierPrec = 8) {
   MUGIQ_REQUIRE(out != nullptr && in != nullptr && transfer != nullptr && op != nullptr && gauge != nullptr, "%s: NULL argument", who);
   MUGIQ_REQUIRE(nVec >= 1, "%s: nVec = %d must be >= 1", who, nVec);
   int st;
@@ -576,9 +639,20 @@ int check_problem(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in,
     if ((st = validate_spinor(&out[i], who, outName))) return st;
     if ((st = validate_spinor(&in[i], who, inName))) return st;
   }
-  if (transfer->precision != 8 || op->precision != 8 || out[0].precision != 8 || in[0].precision != 8)
-    return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "%s: fp64 only: the transfer has precision %d, the coarse operator %d, %s %d and %s %d", who,
-                     transfer->precision, op->precision, outName, out[0].precision, inName, in[0].precision);
+  if (fieldPrec == 8 && hierPrec == 8) {
+    if (transfer->precision != 8 || op->precision != 8 || out[0].precision != 8 || in[0].precision != 8)
+      return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "%s: fp64 only: the transfer has precision %d, the coarse operator %d, %s %d and %s %d", who,
+                       transfer->precision, op->precision, outName, out[0].precision, inName, in[0].precision);
+  } else if (fieldPrec == 4) {
+    MUGIQ_REQUIRE(transfer->precision == 4 && op->precision == 4 && out[0].precision == 4 && in[0].precision == 4,
+                  "%s: fp32 storage only (mugiq_hip_mg_precondition serves precision 8): the transfer has precision %d, the coarse operator %d, %s %d and %s %d",
+                  who, transfer->precision, op->precision, outName, out[0].precision, inName, in[0].precision);
+  } else {
+    MUGIQ_REQUIRE(transfer->precision == 4 && op->precision == 4 && out[0].precision == 8 && in[0].precision == 8,
+                  "%s: %s and %s are fp64 and the sloppy hierarchy is fp32 (mugiq_hip_mg_solve serves an fp64 hierarchy): the sloppy transfer has precision %d, "
+                  "the sloppy coarse operator %d, %s %d and %s %d",
+                  who, outName, inName, transfer->precision, op->precision, outName, out[0].precision, inName, in[0].precision);
+  }
   for (int i = 0; i < nVec; i++)
     MUGIQ_REQUIRE(same_layout(out[i], out[0]) && same_layout(in[i], out[0]),
                   "%s: vector %d of %s or %s differs in precision, field order, geometry, stride or parity offset from %s vector 0", who, i, outName, inName,
@@ -619,6 +693,86 @@ int check_problem(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in,
   return MUGIQ_HIP_SUCCESS;
 }
 
+// The outer flexible GCR of mugiq_hip_mg_solve on the vectors of S (fp64).  K32 NULL: p = K(r) is S's own cycle; otherwise the cycle of
+// K32 in fp32 storage, between two conversions.  Everything else -- operator applications, directions, residual, tol, the history and the
+// true residual -- is the same code for both
+int outer_solve(MgSolver<double> &S, const MgSolver<float> *K32, const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec,
+                const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out, double *history_out, int historyStride, int *hostReads_out,
+                const char *who) {
+  const int nK = param->nKrylov;
+  int st;
+  const MugiqHipSpinorField *r = S.r;
+  const double tol2 = param->tol * param->tol;
+  bool allConverged = true;
+  int reads = 0;
+  double sums[4 * kMgBlock];
+  for (int v0 = 0; v0 < nVec; v0 += kMgBlock) {
+    const int n = std::min(kMgBlock, nVec - v0);
+    const unsigned all = (1u << n) - 1u;
+    const MugiqHipSpinorField *x = x_h + v0, *b = b_h + v0;
+    const MgVecs<double> xv = MgSolver<double>::vecs(x, n), bv = MgSolver<double>::vecs(b, n), rv = MgSolver<double>::vecs(r, n);
+    double bn2[kMgBlock], rr[kMgBlock];
+    // x = 0, r = b, ||b||^2
+    if ((st = S.fine.axpby(xv, nullptr, 0.0, nullptr, 0.0, n, all))) return st;
+    if ((st = S.fine.axpby(rv, &bv, 1.0, nullptr, 0.0, n, all))) return st;
+    if ((st = S.fine.dot2(bv, bv, n, all, kMgFinRaw, 0.0))) return st;
+    if ((st = S.fetch(sums, &reads))) return st;
+    unsigned active = 0;
+    for (int i = 0; i < n; i++) {
+      bn2[i] = rr[i] = sums[4 * i + 2];
+      iters_out[v0 + i] = 0;
+      if (bn2[i] > 0.0 && !(rr[i] <= tol2 * bn2[i])) active |= 1u << i;
+    }
+    int k = 0;
+    for (int it = 0; it < param->maxIter && active; it++) {
+      MugiqHipSpinorField p[kMgBlock], q[kMgBlock];
+      for (int i = 0; i < n; i++) {
+        p[i] = S.fine_dir(S.fine.P, k, i);
+        q[i] = S.fine_dir(S.fine.Q, k, i);
+      }
+      if (K32) {
+        // p = K(r) with the cycle in fp32 storage: r rounded to fp32, K, z widened straight into the direction slot.  No scaling of r
+        // is needed: K is homogeneous, and a residual of 1e-10 ||b|| is far inside fp32's exponent range (2^-126 = 1e-38)
+        const MgVecs<float> r32 = MgSolver<float>::vecs(K32->r, n), z32 = MgSolver<float>::vecs(K32->zk, n);
+        if ((st = mg_convert(r32, rv, K32->fine.L, S.fine.L, n, active, S.fine.wide, S.stream))) return st;
+        if ((st = K32->precondition(K32->zk, K32->r, n, active))) return st;
+        if ((st = mg_convert(MgSolver<double>::vecs(p, n), z32, S.fine.L, K32->fine.L, n, active, S.fine.wide, S.stream))) return st;
+      } else if ((st = S.precondition(p, r, n, active))) {
+        return st;
+      }
+      if ((st = S.apply_M(q, p, n, active))) return st;
+      if ((st = S.fine.gcr_step(k, xv, rv, false, false, true, n, active))) return st;
+      if ((st = S.fetch(sums, &reads))) return st;
+      unsigned next = active;
+      for (int i = 0; i < n; i++) {
+        if (!((active >> i) & 1u)) continue;
+        rr[i] = sums[4 * i];
+        if (history_out) history_out[(size_t)(v0 + i) * historyStride + iters_out[v0 + i]] = std::sqrt(rr[i] / bn2[i]);
+        iters_out[v0 + i]++;
+        if (rr[i] <= tol2 * bn2[i]) next &= ~(1u << i);
+      }
+      active = next;
+      if (++k == nK) k = 0;  // restart: the directions are cleared
+    }
+    // the true residual ||b - M x|| / ||b||, with one more application
+    if ((st = S.apply_M(S.t, x, n, all))) return st;
+    const MgVecs<double> tv = MgSolver<double>::vecs(S.t, n);
+    if ((st = S.fine.axpby(tv, &bv, 1.0, &tv, -1.0, n, all))) return st;
+    if ((st = S.fine.dot2(tv, tv, n, all, kMgFinRaw, 0.0))) return st;
+    if ((st = S.fetch(sums, &reads))) return st;
+    for (int i = 0; i < n; i++) {
+      relres_out[v0 + i] = bn2[i] > 0.0 ? std::sqrt(sums[4 * i + 2] / bn2[i]) : 0.0;
+      if (bn2[i] > 0.0 && !(rr[i] <= tol2 * bn2[i])) allConverged = false;
+    }
+  }
+  if (hostReads_out) *hostReads_out = reads;
+  if (!allConverged)
+    return set_error(MUGIQ_HIP_ERROR_NOT_CONVERGED,
+                     "%s: not every right-hand side reached tol = %g within maxIter = %d (x, iters_out, relres_out and history_out are filled)", who, param->tol,
+                     param->maxIter);
+  return MUGIQ_HIP_SUCCESS;
+}
+
 }  // namespace
 }  // namespace mugiq
 
@@ -646,7 +800,7 @@ int mugiq_hip_mg_precondition(const MugiqHipSpinorField *z_h, const MugiqHipSpin
   if ((st = check_problem(z_h, r_h, nVec, "z", "r", gauge, clover, transfer, coarseOp, param, kappa, comm, who))) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
-  MgSolver S{gauge, clover, kappa, transfer, coarseOp, *param, s};
+  MgSolver<double> S{gauge, clover, kappa, transfer, coarseOp, *param, s};
   if ((st = S.reserve(r_h[0], 0, nVec, false))) return st;
   for (int v0 = 0; v0 < nVec; v0 += kMgBlock) {
     const int n = std::min(kMgBlock, nVec - v0);
@@ -667,70 +821,148 @@ int mugiq_hip_mg_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField
                 param->maxIter);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
-  MgSolver S{gauge, clover, kappa, transfer, coarseOp, *param, s};
+  MgSolver<double> S{gauge, clover, kappa, transfer, coarseOp, *param, s};
   const int nK = param->nKrylov;
   if ((st = S.reserve(b_h[0], nK, nVec, true))) return st;
-  const MugiqHipSpinorField *r = S.r;
-  const double tol2 = param->tol * param->tol;
-  bool allConverged = true;
-  int reads = 0;
-  double sums[4 * kMgBlock];
+  return outer_solve(S, nullptr, x_h, b_h, nVec, param, iters_out, relres_out, history_out, historyStride, hostReads_out, who);
+}
+
+int mugiq_hip_mg_precondition_sloppy(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
+                                     const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer,
+                                     const MugiqHipCoarseOperator *coarseOp, const MugiqHipMgSolveParam *param, const MugiqHipComm *comm, void *stream) {
+  const char *who = "mgPreconditionSloppy";
+  int st;
+  if ((st = check_problem(z_h, r_h, nVec, "z", "r", gauge, clover, transfer, coarseOp, param, kappa, comm, who, 4, 4))) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((st = debug_poison_lds_if_asked(s))) return st;
+  MgSolver<float> S{gauge, clover, kappa, transfer, coarseOp, *param, s};
+  if ((st = S.reserve(r_h[0], 0, nVec, false))) return st;
+  for (int v0 = 0; v0 < nVec; v0 += kMgBlock) {
+    const int n = std::min(kMgBlock, nVec - v0);
+    if ((st = S.precondition(z_h + v0, r_h + v0, n, (1u << n) - 1u))) return st;
+  }
+  return MUGIQ_HIP_SUCCESS;
+}
+
+int mugiq_hip_mg_solve_mixed(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                             const MugiqHipCloverField *clover, double kappa, const MugiqHipGaugeField *gaugeSloppy,
+                             const MugiqHipCloverField *cloverSloppy, const MugiqHipTransfer *transferSloppy, const MugiqHipCoarseOperator *coarseOpSloppy,
+                             const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out, double *history_out, int historyStride,
+                             int *hostReads_out, const MugiqHipComm *comm, void *stream) {
+  const char *who = "mgSolveMixed";
+  MUGIQ_REQUIRE(iters_out != nullptr && relres_out != nullptr, "%s: NULL argument", who);
+  int st;
+  if ((st = check_problem(x_h, b_h, nVec, "x", "b", gauge, clover, transferSloppy, coarseOpSloppy, param, kappa, comm, who, 8, 4))) return st;
+  MUGIQ_REQUIRE(history_out == nullptr || historyStride >= param->maxIter, "%s: historyStride = %d is smaller than maxIter = %d", who, historyStride,
+                param->maxIter);
+  // the cycle's own fields: both or neither where the operator has a clover term; without one only gaugeSloppy can be given
+  MUGIQ_REQUIRE(!(cloverSloppy != nullptr && gaugeSloppy == nullptr), "%s: cloverSloppy without gaugeSloppy (give both, or neither to use gauge and clover)", who);
+  MUGIQ_REQUIRE(!(gaugeSloppy != nullptr && (cloverSloppy != nullptr) != (clover != nullptr)),
+                "%s: gaugeSloppy %s cloverSloppy, but the call is %s a clover field (give both, or neither to use gauge and clover)", who,
+                cloverSloppy ? "with" : "without", clover ? "with" : "without");
+  if (gaugeSloppy) {
+    const int part[4] = {0, 0, 0, 0};
+    if ((st = check_gauge(gaugeSloppy, b_h[0].X, part, who))) return st;
+    if (cloverSloppy) {
+      if ((st = validate_clover(cloverSloppy, b_h[0].X, b_h[0].volumeCB, who))) return st;
+      MUGIQ_REQUIRE(cloverSloppy->precision == gaugeSloppy->precision, "%s: cloverSloppy precision %d differs from the gaugeSloppy precision %d", who,
+                    cloverSloppy->precision, gaugeSloppy->precision);
+    }
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((st = debug_poison_lds_if_asked(s))) return st;
+  // the outer iteration: 2 nKrylov directions, r and t (for the true residual) in fp64; the cycle: r and z rounded, s, t, w and the coarse
+  // level in fp32.  One reservation, the scalars shared: the stream orders every pass
+  MgSolver<double> S{gauge, clover, kappa, transferSloppy, coarseOpSloppy, *param, s};
+  MgSolver<float> K{gaugeSloppy ? gaugeSloppy : gauge, gaugeSloppy ? cloverSloppy : clover, kappa, transferSloppy, coarseOpSloppy, *param, s};
+  S.init(b_h[0], param->nKrylov, nVec, kMgSetT | kMgSetR, false);
+  K.init(b_h[0], 0, nVec, kMgSetsOfK | kMgSetR | kMgSetZ, true);
+  void *ws = nullptr;
+  if ((st = stream_operator_workspace(&ws, MgSolver<double>::kStencilHead + scalar_bytes() + S.vector_bytes() + K.vector_bytes() + 256, s))) return st;
+  unsigned char *scalars = static_cast<unsigned char *>(ws) + MgSolver<double>::kStencilHead;
+  K.carve(scalars, S.carve(scalars, scalars + scalar_bytes()));
+  return outer_solve(S, &K, x_h, b_h, nVec, param, iters_out, relres_out, history_out, historyStride, hostReads_out, who);
+}
+
+/* dst_i = src_i between two precisions: fields of one geometry and field order, each set with its own stride and parity offset */
+int mugiq_hip_mg_convert_precision(const MugiqHipSpinorField *dst_h, const MugiqHipSpinorField *src_h, int nVec, void *stream) {
+  const char *who = "mgConvertPrecision";
+  MUGIQ_REQUIRE(dst_h != nullptr && src_h != nullptr, "%s: NULL argument", who);
+  MUGIQ_REQUIRE(nVec >= 1, "%s: nVec = %d must be >= 1", who, nVec);
+  int st;
+  for (int i = 0; i < nVec; i++) {
+    if ((st = validate_spinor(&dst_h[i], who, "dst"))) return st;
+    if ((st = validate_spinor(&src_h[i], who, "src"))) return st;
+    MUGIQ_REQUIRE(same_layout(dst_h[i], dst_h[0]) && same_layout(src_h[i], src_h[0]), "%s: vector %d differs from vector 0 of its set", who, i);
+  }
+  MUGIQ_REQUIRE(dst_h[0].field_order == src_h[0].field_order && dst_h[0].volumeCB == src_h[0].volumeCB && dst_h[0].nParity == src_h[0].nParity,
+                "%s: dst and src differ in field order or geometry", who);
+  for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(dst_h[0].X[d] == src_h[0].X[d], "%s: dst X[%d] = %d, src %d", who, d, dst_h[0].X[d], src_h[0].X[d]);
+  for (int i = 0; i < nVec; i++) {
+    uintptr_t a0, a1;
+    spinor_span(dst_h[i], &a0, &a1);
+    for (int j = 0; j < nVec; j++) {
+      uintptr_t b0, b1;
+      spinor_span(src_h[j], &b0, &b1);
+      MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: dst vector %d overlaps src vector %d", who, i, j);
+    }
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const MgLayout Ld = fine_layout(dst_h[0]), Ls = fine_layout(src_h[0]);
+  const bool wide = debug_wide_index_asked();
+  const int pd = dst_h[0].precision, ps = src_h[0].precision;
   for (int v0 = 0; v0 < nVec; v0 += kMgBlock) {
     const int n = std::min(kMgBlock, nVec - v0);
     const unsigned all = (1u << n) - 1u;
-    const MugiqHipSpinorField *x = x_h + v0, *b = b_h + v0;
-    const MgVecs xv = MgSolver::vecs(x, n), bv = MgSolver::vecs(b, n), rv = MgSolver::vecs(r, n);
-    double bn2[kMgBlock], rr[kMgBlock];
-    // x = 0, r = b, ||b||^2
-    if ((st = S.fine.axpby(xv, nullptr, 0.0, nullptr, 0.0, n, all))) return st;
-    if ((st = S.fine.axpby(rv, &bv, 1.0, nullptr, 0.0, n, all))) return st;
-    if ((st = S.fine.dot2(bv, bv, n, all, kMgFinRaw, 0.0))) return st;
-    if ((st = S.fetch(sums, &reads))) return st;
-    unsigned active = 0;
-    for (int i = 0; i < n; i++) {
-      bn2[i] = rr[i] = sums[4 * i + 2];
-      iters_out[v0 + i] = 0;
-      if (bn2[i] > 0.0 && !(rr[i] <= tol2 * bn2[i])) active |= 1u << i;
-    }
-    int k = 0;
-    for (int it = 0; it < param->maxIter && active; it++) {
-      MugiqHipSpinorField p[kMgBlock], q[kMgBlock];
-      for (int i = 0; i < n; i++) {
-        p[i] = S.fine_dir(S.fine.P, k, i);
-        q[i] = S.fine_dir(S.fine.Q, k, i);
-      }
-      if ((st = S.precondition(p, r, n, active))) return st;
-      if ((st = S.apply_M(q, p, n, active))) return st;
-      if ((st = S.fine.gcr_step(k, xv, rv, false, false, true, n, active))) return st;
-      if ((st = S.fetch(sums, &reads))) return st;
-      unsigned next = active;
-      for (int i = 0; i < n; i++) {
-        if (!((active >> i) & 1u)) continue;
-        rr[i] = sums[4 * i];
-        if (history_out) history_out[(size_t)(v0 + i) * historyStride + iters_out[v0 + i]] = std::sqrt(rr[i] / bn2[i]);
-        iters_out[v0 + i]++;
-        if (rr[i] <= tol2 * bn2[i]) next &= ~(1u << i);
-      }
-      active = next;
-      if (++k == nK) k = 0;  // restart: the directions are cleared
-    }
-    // the true residual ||b - M x|| / ||b||, with one more application
-    if ((st = S.apply_M(S.t, x, n, all))) return st;
-    const MgVecs tv = MgSolver::vecs(S.t, n);
-    if ((st = S.fine.axpby(tv, &bv, 1.0, &tv, -1.0, n, all))) return st;
-    if ((st = S.fine.dot2(tv, tv, n, all, kMgFinRaw, 0.0))) return st;
-    if ((st = S.fetch(sums, &reads))) return st;
-    for (int i = 0; i < n; i++) {
-      relres_out[v0 + i] = bn2[i] > 0.0 ? std::sqrt(sums[4 * i + 2] / bn2[i]) : 0.0;
-      if (bn2[i] > 0.0 && !(rr[i] <= tol2 * bn2[i])) allConverged = false;
-    }
+    if (pd == 4 && ps == 8) st = mg_convert(MgSolver<float>::vecs(dst_h + v0, n), MgSolver<double>::vecs(src_h + v0, n), Ld, Ls, n, all, wide, s);
+    else if (pd == 8 && ps == 4) st = mg_convert(MgSolver<double>::vecs(dst_h + v0, n), MgSolver<float>::vecs(src_h + v0, n), Ld, Ls, n, all, wide, s);
+    else if (pd == 8) st = mg_convert(MgSolver<double>::vecs(dst_h + v0, n), MgSolver<double>::vecs(src_h + v0, n), Ld, Ls, n, all, wide, s);
+    else st = mg_convert(MgSolver<float>::vecs(dst_h + v0, n), MgSolver<float>::vecs(src_h + v0, n), Ld, Ls, n, all, wide, s);
+    if (st) return st;
   }
-  if (hostReads_out) *hostReads_out = reads;
-  if (!allConverged)
-    return set_error(MUGIQ_HIP_ERROR_NOT_CONVERGED,
-                     "%s: not every right-hand side reached tol = %g within maxIter = %d (x, iters_out, relres_out and history_out are filled)", who, param->tol,
-                     param->maxIter);
   return MUGIQ_HIP_SUCCESS;
+}
+
+int mugiq_hip_transfer_convert(const MugiqHipTransfer *dst, const MugiqHipTransfer *src, void *stream) {
+  const char *who = "transferConvert";
+  MUGIQ_REQUIRE(dst != nullptr && src != nullptr && dst->V != nullptr && src->V != nullptr, "%s: NULL argument", who);
+  for (const MugiqHipTransfer *T : {dst, src}) {
+    MUGIQ_REQUIRE(T->precision == 4 || T->precision == 8, "%s: precision %d", who, T->precision);
+    MUGIQ_REQUIRE(T->nVec >= 1 && (T->spinBlockSize == 1 || T->spinBlockSize == 2), "%s: nVec = %d, spinBlockSize = %d", who, T->nVec, T->spinBlockSize);
+    int64_t vol = 1;
+    for (int d = 0; d < 4; d++) {
+      MUGIQ_REQUIRE(T->X[d] > 0 && T->geoBlockSize[d] >= 1, "%s: transfer X / geo_block_size[%d]", who, d);
+      vol *= T->X[d];
+    }
+    MUGIQ_REQUIRE(vol % 2 == 0 && T->stride >= vol / 2, "%s: stride = %d is smaller than volumeCB = %lld", who, T->stride, (long long)(vol / 2));
+    if (T->spinBlockSize == 2)
+      MUGIQ_REQUIRE(T->parity_offset >= (int64_t)12 * T->nVec * T->stride, "%s: parity_offset = %lld is smaller than 12 nVec stride", who,
+                    (long long)T->parity_offset);
+    else
+      MUGIQ_REQUIRE(T->parity_offset > 0 && T->parity_offset % ((int64_t)2 * T->nVec * T->stride) == 0,
+                    "%s: a coarse -> coarse transfer needs parity_offset = 2 nc nVec stride exactly, not %lld", who, (long long)T->parity_offset);
+  }
+  MUGIQ_REQUIRE(dst->nVec == src->nVec && dst->spinBlockSize == src->spinBlockSize, "%s: dst has n_vec %d and spin block %d, src %d and %d", who, dst->nVec,
+                dst->spinBlockSize, src->nVec, src->spinBlockSize);
+  for (int d = 0; d < 4; d++)
+    MUGIQ_REQUIRE(dst->X[d] == src->X[d] && dst->geoBlockSize[d] == src->geoBlockSize[d], "%s: dst has X[%d] = %d and block %d, src %d and %d", who, d,
+                  dst->X[d], dst->geoBlockSize[d], src->X[d], src->geoBlockSize[d]);
+  const MgLayout Ld = transfer_layout(*dst), Ls = transfer_layout(*src);
+  MUGIQ_REQUIRE(Ld.nRows == Ls.nRows, "%s: dst has %d rows per parity, src %d (the colours of the finer side differ)", who, Ld.nRows, Ls.nRows);
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(dst->V), a1 = a0 + (uintptr_t)2 * dst->parity_offset * 2 * dst->precision;
+  const uintptr_t b0 = reinterpret_cast<uintptr_t>(src->V), b1 = b0 + (uintptr_t)2 * src->parity_offset * 2 * src->precision;
+  MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: dst overlaps src", who);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool wide = debug_wide_index_asked();
+  void *dv = const_cast<void *>(dst->V), *sv = const_cast<void *>(src->V);
+  MgVecs<double> d8{}, s8{};
+  MgVecs<float> d4{}, s4{};
+  d8.p[0] = static_cast<Cplx<double> *>(dv), s8.p[0] = static_cast<Cplx<double> *>(sv);
+  d4.p[0] = static_cast<Cplx<float> *>(dv), s4.p[0] = static_cast<Cplx<float> *>(sv);
+  if (dst->precision == 4 && src->precision == 8) return mg_convert(d4, s8, Ld, Ls, 1, 1u, wide, s);
+  if (dst->precision == 8 && src->precision == 4) return mg_convert(d8, s4, Ld, Ls, 1, 1u, wide, s);
+  if (dst->precision == 8) return mg_convert(d8, s8, Ld, Ls, 1, 1u, wide, s);
+  return mg_convert(d4, s4, Ld, Ls, 1, 1u, wide, s);
 }
 
 }  // extern "C"

@@ -266,6 +266,64 @@ def mgSolve(b, gauge, kappa, transfer, coarseOp, clover=None, x=None, allow_unco
     return x, MgSolveInfo(it, np.array(relres), st == 0, [h[i, :it[i]].copy() for i in range(n)], int(reads.value))
 
 
+def mgConvertPrecision(dst, src):
+    """dst_i = src_i between lists of SpinorFields of one geometry and order and either precision (mugiq_hip_mg_convert_precision):
+    fp64 -> fp32 rounds to nearest, once; fp32 -> fp64 is exact.  The conversions of mgSolveMixed as they run inside it."""
+    dst, src = list(dst), list(src)
+    if len(dst) != len(src) or not src:
+        raise _lib.MugiqHipError("mgConvertPrecision: %d dst and %d src vectors (need the same number, at least one)" % (len(dst), len(src)))
+    _lib.check(_lib.load().mugiq_hip_mg_convert_precision(desc_array(dst), desc_array(src), len(src), _stream()))
+
+
+def mgPreconditionSloppy(z, r, gauge, kappa, transfer, coarseOp, clover=None, comm=None, **param):
+    """z_i = K(r_i) with every vector of the cycle in fp32 storage (mugiq_hip_mg_precondition_sloppy): z, r, transfer and coarseOp all of
+    precision 4, gauge (and clover) of either.  Sums are fp64 and in a fixed order, as in mgPrecondition.  param: as for mgPrecondition."""
+    z, r = list(z), list(r)
+    if len(z) != len(r) or not r:
+        raise _lib.MugiqHipError("mgPreconditionSloppy: %d z and %d r vectors (need the same number, at least one)" % (len(z), len(r)))
+    keep = []
+    p, g, t, o = mgSolveParam(**param), gauge.desc(), transfer.desc(), coarseOp.desc()
+    _lib.check(_lib.load().mugiq_hip_mg_precondition_sloppy(desc_array(z), desc_array(r), len(r), ctypes.byref(g), _clover_ptr(clover, keep), float(kappa),
+                                                            ctypes.byref(t), ctypes.byref(o), ctypes.byref(p), _comm_ptr(comm, keep), _stream()))
+
+
+def mgSolveMixed(b, gauge, kappa, transferSloppy, coarseOpSloppy, clover=None, gaugeSloppy=None, cloverSloppy=None, x=None, allow_unconverged=False,
+                 comm=None, **param):
+    """x_r = M^-1 b_r by the fp64 flexible GCR of mgSolve with the two-grid cycle in fp32 storage (mugiq_hip_mg_solve_mixed).  b, x, gauge and
+    clover as for mgSolve; transferSloppy: the Transfer in precision 4 (Transfer.astype(4)), coarseOpSloppy: the CoarseOperator
+    computeCoarseOperator built from it; gaugeSloppy / cloverSloppy: the fields the cycle's stencil reads (e.g. fp32 copies), both None:
+    gauge and clover.  Returns (x, MgSolveInfo) as mgSolve does; relres is the true fp64 residual."""
+    b = list(b)
+    if not b:
+        raise _lib.MugiqHipError("mgSolveMixed: no right-hand side")
+    if x is None:
+        x = [SpinorField(f.X, 8, f.order, f.stride - f.volumeCB, device=f.device) for f in b]
+    x = list(x)
+    n = len(b)
+    if len(x) != n:
+        raise _lib.MugiqHipError("mgSolveMixed: %d x and %d b vectors" % (len(x), n))
+    keep = []
+    p, g, t, o = mgSolveParam(**param), gauge.desc(), transferSloppy.desc(), coarseOpSloppy.desc()
+    gs = None
+    if gaugeSloppy is not None:
+        gd = gaugeSloppy.desc()
+        keep.append(gd)
+        gs = ctypes.byref(gd)
+    stride = max(int(p.maxIter), 1)
+    iters = (ctypes.c_int * n)()
+    relres = (ctypes.c_double * n)()
+    hist = (ctypes.c_double * (n * stride))()
+    reads = ctypes.c_int(0)
+    st = _lib.load().mugiq_hip_mg_solve_mixed(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), gs,
+                                              _clover_ptr(cloverSloppy, keep), ctypes.byref(t), ctypes.byref(o), ctypes.byref(p), iters, relres, hist,
+                                              stride, ctypes.byref(reads), _comm_ptr(comm, keep), _stream())
+    if st != 0 and not (st == STATUS_NOT_CONVERGED and allow_unconverged):
+        _lib.check(st)
+    it = np.array(iters)
+    h = np.array(hist).reshape(n, stride)
+    return x, MgSolveInfo(it, np.array(relres), st == 0, [h[i, :it[i]].copy() for i in range(n)], int(reads.value))
+
+
 def mgSetupParam(**param):
     """MugiqHipMgSetupParam: the defaults of mugiq_hip_mg_setup_param_default (setupMaxIter 500 and setupTol 5e-6 as in the reference's
     tests/loop.cpp; nBlockOrtho 2, rankTol 1e-8, refineCycles 0, refineIters 4 -- first guesses, not tuned) with the given members replaced."""
@@ -581,9 +639,13 @@ class Eigsolve_Mugiq:
             ev = self.eVecs
         return wilsonSolve(b, self.gauge, self.kappa, ev, sg, tol, maxIter, self.comm, x, allow_unconverged, self.clover)
 
-    def solveMG(self, b, x=None, allow_unconverged=False, **param):
+    def solveMG(self, b, x=None, allow_unconverged=False, sloppy=None, **param):
         """M^-1 b by the two-grid preconditioned GCR (mgSolve) for objects built with transfer= and coarseOp=: their gauge field, clover
-        field, kappa, transfer and coarse operator.  Returns (x, MgSolveInfo)."""
+        field, kappa, transfer and coarse operator.  sloppy=(T32, op32): the mixed solve (mgSolveMixed) with that fp32 hierarchy, on this
+        object's gauge and clover fields.  Returns (x, MgSolveInfo)."""
+        if sloppy is not None:
+            T32, op32 = sloppy
+            return mgSolveMixed(b, self.gauge, self.kappa, T32, op32, self.clover, x=x, allow_unconverged=allow_unconverged, comm=self.comm, **param)
         tr, op = self.transfer, self.coarseOp
         if tr is None and op is None and self.mgTransfer is not None:   # the hierarchy setupMG made
             tr, op = self.mgTransfer, self.mgCoarseOp

@@ -408,6 +408,16 @@ class Transfer:
         self.V.copy_(torch.from_numpy(buf))
         return self
 
+    def astype(self, precision, pad=None):
+        """A new Transfer of the same geometry in `precision` (4 | 8) with V copied on the device (mugiq_hip_transfer_convert): one
+        rounding on the store, no trip through the host.  pad: of the new V (default: this one's).  The fp32 hierarchy of mgSolveMixed is
+        T32 = T.astype(4); op32 = computeCoarseOperator(T32, gauge, kappa, clover=...)."""
+        out = Transfer(self.X, self.n_vec, self.geo_block_size, self.spin_block_size, int(precision), self.stride - self.volumeCB if pad is None else pad,
+                       self.device, self.fine_spin, self.fine_color)
+        d, s = out.desc(), self.desc()
+        _lib.check(_lib.load().mugiq_hip_transfer_convert(ctypes.byref(d), ctypes.byref(s), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return out
+
     # ---- MG setup on the device (csrc/mg_setup.hip) ------------------------------------------------------------------------------
     def setVectors(self, vecs):
         """V(x; s, c, j) = vecs[j](x; s, c) for n_vec fine SpinorFields of either precision and order (mugiq_hip_transfer_set_vectors);

@@ -422,13 +422,14 @@ class Loop_Mugiq:
                                                    comm=self.comm, **param)
         return self.lastSetup
 
-    def solveMG(self, b, kappa, coarseOp=None, clover=None, x=None, allow_unconverged=False, **param):
+    def solveMG(self, b, kappa, coarseOp=None, clover=None, x=None, allow_unconverged=False, sloppy=None, **param):
         """x_r = M^-1 b_r by the two-grid preconditioned GCR (mgSolve) with this coarse loop object's gauge field, transfer and stream;
         coarseOp: the CoarseOperator of that transfer at this kappa (and clover).  Returns the list x; iteration counts, true residuals,
         histories and host reads are kept in self.lastSolve.  Status 2 (UNSUPPORTED) for fine-level and two-sided loop objects and for
         hierarchies of more than one level, status 1 for a loop object created without a gauge field.  An MG set then reads
-        x = loop.solveMG(xi, kappa, coarseOp); loop.deflateCoarse(x, xi)."""
-        from .eigsolve import mgSolve
+        x = loop.solveMG(xi, kappa, coarseOp); loop.deflateCoarse(x, xi).  sloppy=(T32, op32): the mixed solve (mgSolveMixed) with that
+        fp32 hierarchy in place of this object's transfer and coarseOp; the checks of the object stay."""
+        from .eigsolve import mgSolve, mgSolveMixed
         if self._transfer is None or self.eVecsLeft is not None:
             raise _lib.MugiqHipError("status 2: Loop_Mugiq.solveMG: coarse (MG) loop objects only")
         tr = self._transfer
@@ -438,6 +439,11 @@ class Loop_Mugiq:
             tr = tr[0]
         if self._params.gauge is None:
             raise _lib.MugiqHipError("status 1: Loop_Mugiq.solveMG: the loop object was created without a gauge field")
+        if sloppy is not None:
+            T32, op32 = sloppy
+            x, self.lastSolve = mgSolveMixed(b, self._params.gauge, kappa, T32, op32, clover, x=x, allow_unconverged=allow_unconverged, comm=self.comm,
+                                             **param)
+            return x
         if coarseOp is None:
             coarseOp = self.coarseOp
             if coarseOp is None:
