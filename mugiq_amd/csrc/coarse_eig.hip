@@ -12,9 +12,10 @@
 // coarse_gram_kernel: G[i][j] = <a_i, b_j>.  The k index of the instruction runs over vector elements: a wave owns a 16 x 16 tile of G
 // and walks a chunk of kGramChunk elements eight at a time -- lane (i, k) reads elements 2 k and 2 k + 1 of the eight, so the four lanes
 // of a row read one 128-byte line -- with Re G and Im G in one accumulator each, updated in a fixed order (re re, im im | re im, -im re).
-// Sums are kept short: 256 elements make one chain, the chains of a chunk are added in order, and coarse_gram_sum_kernel adds the chunks
-// eight to a run (a single chain over 4096 positive terms, the diagonal of a Gram matrix, was measured 9 eps off, past the 4 eps
-// sum |a| |b| the tests hold it to).
+// Sums are kept short: 16 elements make one chain (a leaf), the 16 leaves of a run of 256 elements are added in order, the 16 runs of a
+// chunk in order, and coarse_gram_sum_kernel adds the chunks eight to a run (a single chain over 4096 positive terms, the diagonal of a
+// Gram matrix, was measured 9 eps off, and chains of 256 elements 6.8 eps on short vectors, past the 4 eps sum |a| |b| the tests hold it
+// to: gram_walk).
 // The partial of a chunk goes to memory, coarse_gram_sum_kernel adds the chunks in ascending order.  The chunk depends on nothing, the
 // walk on L alone, and an entry of the tile on its own row and column alone: the bits of G[i][j] are those of (a_i, b_j) in any batch.
 //
@@ -40,7 +41,8 @@ constexpr int kEigBlock = 8;         // vectors per call of the batched operator
 constexpr int kEigMaxKr = 512;
 constexpr int kGramChunk = 4096;     // complex elements of a vector per partial Gram matrix
 constexpr int kGramStep = 8;         // ... per trip of a wave
-constexpr int kGramRun = 256;        // ... summed in one chain before they join the chunk's sum (divides kGramChunk)
+constexpr int kGramLeaf = 16;        // ... summed in one chain before they join the run's sum (divides 32, which divides every vector)
+constexpr int kGramRun = 256;        // ... whose leaves are added in one chain before they join the chunk's sum (divides kGramChunk)
 constexpr int kGramFan = 8;          // chunks added in one chain by coarse_gram_sum_kernel before they join the total
 constexpr int kRotElems = 32;        // rotate: elements per wave,
 constexpr int kRotOut = 64;          // ... outputs per wave,
@@ -87,27 +89,38 @@ struct GramArgs {
 };
 
 __device__ inline void gram_walk(const void *pa, const void *pb, const VecGeom &ga, const VecGeom &gb, int64_t e0, int64_t e1, int k, d4 &re, d4 &im) {
-  // two levels: a run of kGramRun elements is summed on its own and then added to the chunk's sum, so that no accumulator takes more than
-  // 4 kGramRun / kGramStep = 128 instructions in a row (a sum of 4096 positive terms in one chain drifts past 4 eps of its value).
-  // L is a multiple of 32 (VecGeom), so the last run of a vector may be short but no trip of 8 elements is
+  // three levels: a leaf of kGramLeaf elements is summed on its own (8 instructions, 32 products to an accumulator), the leaves of a run
+  // of kGramRun elements are added in order, and the runs in order to the chunk's sum.  The instruction adds its four products one after
+  // the other, each sum rounded, so a chain of n elements is a chain of 2 n roundings: on the diagonal of a Gram matrix (all terms
+  // positive) a single chain over 4096 elements was measured 9 eps off, and runs of 256 without leaves reached 6.8 eps among the 264
+  // diagonal entries of vectors of 320 elements, which have only two runs to average over -- past the 4 eps sum |a| |b| the tests hold
+  // the kernel to.  With leaves no level adds more than 32 terms in a row (1.9 eps at most over the shapes of
+  // tests/test_coarse_eig_cpu.py, which restates this tree in numpy).
+  // L is a multiple of 32 (VecGeom), so the last run of a vector may be short but no leaf and no trip of 8 elements is
   for (int64_t s0 = e0; s0 < e1; s0 += kGramRun) {
     const int64_t s1 = min(s0 + (int64_t)kGramRun, e1);
     d4 rr = {0.0, 0.0, 0.0, 0.0}, ri = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t b = s0; b < s1; b += kGramStep) {
-      Z x[2], y[2];
+    for (int64_t l0 = s0; l0 < s1; l0 += kGramLeaf) {
+      d4 lr = {0.0, 0.0, 0.0, 0.0}, li = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-      for (int u = 0; u < 2; u++) {
-        const int64_t e = b + 2 * k + u;
-        x[u] = ce_ld(pa, ce_offset(ga, e));
-        y[u] = ce_ld(pb, ce_offset(gb, e));
-      }
+      for (int64_t b = l0; b < l0 + kGramLeaf; b += kGramStep) {
+        Z x[2], y[2];
 #pragma unroll
-      for (int u = 0; u < 2; u++) {
-        rr = __builtin_amdgcn_mfma_f64_16x16x4f64(x[u].re, y[u].re, rr, 0, 0, 0);
-        rr = __builtin_amdgcn_mfma_f64_16x16x4f64(x[u].im, y[u].im, rr, 0, 0, 0);
-        ri = __builtin_amdgcn_mfma_f64_16x16x4f64(x[u].re, y[u].im, ri, 0, 0, 0);
-        ri = __builtin_amdgcn_mfma_f64_16x16x4f64(-x[u].im, y[u].re, ri, 0, 0, 0);
+        for (int u = 0; u < 2; u++) {
+          const int64_t e = b + 2 * k + u;
+          x[u] = ce_ld(pa, ce_offset(ga, e));
+          y[u] = ce_ld(pb, ce_offset(gb, e));
+        }
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+          lr = __builtin_amdgcn_mfma_f64_16x16x4f64(x[u].re, y[u].re, lr, 0, 0, 0);
+          lr = __builtin_amdgcn_mfma_f64_16x16x4f64(x[u].im, y[u].im, lr, 0, 0, 0);
+          li = __builtin_amdgcn_mfma_f64_16x16x4f64(x[u].re, y[u].im, li, 0, 0, 0);
+          li = __builtin_amdgcn_mfma_f64_16x16x4f64(-x[u].im, y[u].re, li, 0, 0, 0);
+        }
       }
+      rr += lr;
+      ri += li;
     }
     re += rr;
     im += ri;

@@ -259,6 +259,79 @@ def test_golden_fine_spectrum_is_what_numpy_gives():
     assert gold.shape == (32,) and np.max(np.abs(gold - lam[:32])) <= 3072 * EPS * lam[-1]
 
 
+# ---- what tests/test_gpu_coarse_eig_scale.py stands on ---------------------------------------------------------------------------------
+def test_apply_block_is_apply_Mc_column_by_column():
+    """coarse_eig_cases.apply_block (numpy.matmul on a block of columns) against coarse_op_ref.apply_Mc on each column, plain and dagger, on
+    the synthetic operator of the solver-scale test: 1e-14 of the max norm (two orders of summing 9 x 22 terms)"""
+    M, Xc = cec.scale_operator(), cec.SCALE_XC
+    vcb, N = int(np.prod(Xc)) // 2, 2 * cec.SCALE_NVEC
+    W = _c(np.random.default_rng(5600), (2, vcb, N, 5))
+    for dagger in (False, True):
+        got = cec.apply_block(M, W, Xc, dagger)
+        want = np.stack([cor.apply_Mc(M, W[..., k].reshape(cec.scale_field_shape()), Xc, dagger=dagger).reshape(2, vcb, N) for k in range(5)], axis=-1)
+        err = float(np.max(np.abs(got - want)) / np.max(np.abs(want)))
+        print("dagger %s: %.2e" % (dagger, err))
+        assert got.shape == W.shape and err <= 1e-14
+
+
+@pytest.mark.parametrize("nConv,nKr,polyDeg,maxIter", cec.SCALE_CASES)
+def test_scale_restatement_is_a_sound_reference(nConv, nKr, polyDeg, maxIter):
+    """The two runs the device is compared with at 4224 elements per vector: one round, status 5, nothing locked (so opBlocks is the power
+    estimate, two Rayleigh-Ritz steps and one filter of the whole basis), every residual far above rounding (nothing converged: a wrong
+    residual cannot hide behind a floor), and theta and r well conditioned: a shift of the start vectors by one unit in the last place
+    moves them by less than 1e-13 relative"""
+    res = cec.scale_restatement(nConv, nKr, polyDeg, maxIter)
+    assert res.status == cer.STATUS_NOT_CONVERGED and res.iters == 1 and res.nConverged == 0 and res.locked == [0, 0]
+    assert res.opBlocks == 21 + nKr // 8 * (2 + polyDeg) and res.opBlocks == {72: 111, 264: 153}[nKr]
+    assert res.evecs.shape == (cec.scale_dimension(), nConv) and np.all(np.isfinite(res.evecs)) and res.orthonormality <= 100 * EPS * np.sqrt(cec.scale_dimension())
+    assert np.all(res.residual > 1e-3) and np.all(np.diff(res.theta) >= 0.0)
+    moved = cec.scale_restatement(nConv, nKr, polyDeg, maxIter, ulp=1)
+    d_theta = float(np.max(np.abs(moved.theta - res.theta) / res.theta))
+    d_res = float(np.max(np.abs(moved.residual - res.residual) / res.residual))
+    print("nKr %d: r in [%.3f, %.3f], theta in [%.3f, %.3f]; one ulp of the start vectors moves theta by %.1e, r by %.1e"
+          % (nKr, res.residual.min(), res.residual.max(), res.theta.min(), res.theta.max(), d_theta, d_res))
+    assert (moved.iters, moved.opBlocks, moved.status) == (res.iters, res.opBlocks, res.status)
+    assert d_theta < 1e-13 and d_res < 1e-13
+
+
+def _exact_squares(x):
+    """x^2 as an unevaluated sum p + e of two doubles (Veltkamp split, Dekker product): p = fl(x^2), e the rounding error, exactly"""
+    t = 134217729.0 * x
+    hi = t - (t - x)
+    lo = x - hi
+    p = x * x
+    return p, ((hi * hi - p) + 2.0 * hi * lo) + lo * lo
+
+
+def _exact_norms(a):
+    import math
+    return np.array([math.fsum(np.concatenate(_exact_squares(x.real) + _exact_squares(x.imag))) for x in a])
+
+
+# 16 vectors of 8, 10 and 17 chunks; 264 vectors (the diagonal of the widest Gram matrix of the GPU tests) of 128, 320 and 18 432 elements
+TREE_CASES = [(16, Xc, nvec) for Xc, nvec in cec.LONG_SHAPES] + [(264, Xc, nvec) for Xc, nvec in cec.GRAM_SHAPES]
+
+
+@pytest.mark.parametrize("case", range(len(TREE_CASES)))
+def test_gram_summation_tree_stays_within_the_bound(case):
+    """The tree of coarse_gram_kernel and coarse_gram_sum_kernel as documented (4 products per step, leaves of 16 elements, 16 leaves per
+    run, 16 runs per chunk, chunks 8 to a fan run) on the diagonal of a Gram matrix -- all terms positive, the worst case for drift: within
+    4 eps of the exact sum (math.fsum over the exact squares), which is what entitles the GPU tests to hold the device to 4 eps sum |a| |b|
+    at these lengths and widths.  Long vectors are the easy side: the errors of many runs average out.  Short vectors with many entries are
+    the hard one, and there the tree WITHOUT the leaf level (one chain per 256 elements, as the kernel was first written) misses the bound:
+    6.75 eps among 264 vectors of 320 elements, which the device showed bit for bit (7.5 eps against numpy's own 2.4 eps)"""
+    m, Xc, nvec = TREE_CASES[case]
+    L = int(np.prod(Xc)) * 2 * nvec
+    a = _c(np.random.default_rng(5700 + case), (m, L))
+    exact = _exact_norms(a)
+    worst = float(np.max(np.abs(cec.gram_tree_diagonal(a) - exact) / (EPS * exact)))
+    flat = float(np.max(np.abs(cec.gram_tree_diagonal(a, leaf=cec.GRAM_RUN) - exact) / (EPS * exact)))
+    print("%d vectors of %d elements: tree within %.2f eps of the exact sum (without leaves: %.2f eps)" % (m, L, worst, flat))
+    assert worst <= 4.0
+    if (m, L) == (264, 320):
+        assert flat > 4.0
+
+
 # ---- refusals, without a device -------------------------------------------------------------------------------------------------------
 def _coarse_descs(hip, n, Xc=(2, 2, 2, 2), nvec=4, precision=8, base=1 << 20, pad=0):
     arr = (hip._lib.CoarseDesc * n)()
