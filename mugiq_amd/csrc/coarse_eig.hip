@@ -22,7 +22,7 @@
 // coarse_rotate_kernel: out_j = sum_i in_i Z[i][j], computed transposed, D[j][e] = sum_i Z^T[j][i] in_i[e], so that the element stays on the lane and a
 // store is 16 consecutive complex numbers.  k runs over the input vectors, four to an instruction, in ascending order; a wave owns 32
 // elements x 64 outputs (16 accumulators).  Z comes zero-padded to multiples of (4, 64) behind the pointer table.
-#include "internal.h"
+#include "mg_common.h"
 
 #include <algorithm>
 #include <chrono>
@@ -53,7 +53,6 @@ constexpr double kAmaxMargin = 1.1;  // QUDA's
 
 typedef Cplx<double> Z;
 typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double ce_vec2 __attribute__((ext_vector_type(2)));
 
 // total = 2 rows rowLen = 4 n_vec volumeCB is a multiple of 32 for every field check_fields admits (four even extents: volumeCB is a
 // multiple of 8); the kernels rely on it: a wave's 8 (Gram) or 32 (rotation) elements are all there or none is
@@ -68,16 +67,6 @@ __device__ inline int64_t ce_offset(const VecGeom &g, int64_t e) {
   const int64_t row = e / g.rowLen;
   const int pty = row >= g.rows ? 1 : 0;
   return pty * g.po + (row - pty * g.rows) * (int64_t)g.stride + (e - row * g.rowLen);
-}
-__device__ inline Z ce_ld(const void *p, int64_t i) {
-  const ce_vec2 t = *as_global(static_cast<const ce_vec2 *>(p) + i);
-  return Z{t.x, t.y};
-}
-__device__ inline void ce_st(void *p, int64_t i, const Z &v) {
-  ce_vec2 t;
-  t.x = v.re;
-  t.y = v.im;
-  *as_global(static_cast<ce_vec2 *>(p) + i) = t;
 }
 
 // ---- Gram ------------------------------------------------------------------------------------------------------------------------------
@@ -108,8 +97,8 @@ __device__ inline void gram_walk(const void *pa, const void *pb, const VecGeom &
 #pragma unroll
         for (int u = 0; u < 2; u++) {
           const int64_t e = b + 2 * k + u;
-          x[u] = ce_ld(pa, ce_offset(ga, e));
-          y[u] = ce_ld(pb, ce_offset(gb, e));
+          x[u] = ld_wide<double>(pa, ce_offset(ga, e));
+          y[u] = ld_wide<double>(pb, ce_offset(gb, e));
         }
 #pragma unroll
         for (int u = 0; u < 2; u++) {
@@ -141,7 +130,7 @@ __global__ __launch_bounds__(256) void coarse_gram_kernel(GramArgs a) {
 #pragma unroll
   for (int q = 0; q < 4; q++) {
     const int i = i0 + k + 4 * q, j = j0 + r;
-    if (i < a.mA && j < a.mB) ce_st(out, (int64_t)i * a.mB + j, Z{re[q], im[q]});
+    if (i < a.mA && j < a.mB) st_round<double>(out, (int64_t)i * a.mB + j, Z{re[q], im[q]});
   }
 }
 
@@ -151,16 +140,16 @@ __global__ __launch_bounds__(256) void coarse_gram_sum_kernel(const Z *partial, 
   // chunks in ascending order, kGramFan to a run, the runs in ascending order
   Z s{0.0, 0.0};
   for (int c0 = 0; c0 < nChunks; c0 += kGramFan) {
-    Z run = ce_ld(partial, (int64_t)c0 * nEntries + idx);
+    Z run = ld_wide<double>(partial, (int64_t)c0 * nEntries + idx);
     for (int c = c0 + 1; c < min(c0 + kGramFan, nChunks); c++) {
-      const Z p = ce_ld(partial, (int64_t)c * nEntries + idx);
+      const Z p = ld_wide<double>(partial, (int64_t)c * nEntries + idx);
       run.re += p.re;
       run.im += p.im;
     }
     s.re += run.re;
     s.im += run.im;
   }
-  ce_st(G, idx, s);
+  st_round<double>(G, idx, s);
 }
 
 // ---- rotation --------------------------------------------------------------------------------------------------------------------------
@@ -191,7 +180,7 @@ __global__ __launch_bounds__(64 * kRotWaves) void coarse_rotate_kernel(RotArgs a
     const void *p = as_global(a.tab)[min(i, a.mIn - 1)];
     Z x[EB];
 #pragma unroll
-    for (int eb = 0; eb < EB; eb++) x[eb] = i < a.mIn ? ce_ld(p, offIn[eb]) : Z{0.0, 0.0};
+    for (int eb = 0; eb < EB; eb++) x[eb] = i < a.mIn ? ld_wide<double>(p, offIn[eb]) : Z{0.0, 0.0};
     double zr[JB], zi[JB];
 #pragma unroll
     for (int jb = 0; jb < JB; jb++) {
@@ -217,7 +206,7 @@ __global__ __launch_bounds__(64 * kRotWaves) void coarse_rotate_kernel(RotArgs a
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const int j = jBase + 16 * jb + k + 4 * r;
-        if (j < a.mOut) ce_st(const_cast<void *>(as_global(a.tab)[a.mIn + j]), off, Z{accRe[eb][jb][r], accIm[eb][jb][r]});
+        if (j < a.mOut) st_round<double>(const_cast<void *>(as_global(a.tab)[a.mIn + j]), off, Z{accRe[eb][jb][r], accIm[eb][jb][r]});
       }
   }
 }
@@ -233,14 +222,14 @@ struct ChebArgs {
 __global__ __launch_bounds__(kEwThreads) void chebyshev_step_kernel(ChebArgs a) {
   const int64_t base = (int64_t)blockIdx.y * a.pitch;
   for (int64_t e = (int64_t)blockIdx.x * kEwThreads + threadIdx.x; e < a.total; e += (int64_t)gridDim.x * kEwThreads) {
-    const Z y = ce_ld(a.y, base + e), t = ce_ld(a.t, base + e);
+    const Z y = ld_wide<double>(a.y, base + e), t = ld_wide<double>(a.t, base + e);
     Z o{fma(a.alpha, y.re, a.beta * t.re), fma(a.alpha, y.im, a.beta * t.im)};
     if (a.prev) {
-      const Z p = ce_ld(a.prev, base + e);
+      const Z p = ld_wide<double>(a.prev, base + e);
       o.re -= p.re;
       o.im -= p.im;
     }
-    ce_st(a.out, base + e, o);
+    st_round<double>(a.out, base + e, o);
   }
 }
 
@@ -253,7 +242,7 @@ __global__ __launch_bounds__(kEwThreads) void residual_partial_kernel(const Z *W
   const int64_t base = (int64_t)v * pitch, e0 = (int64_t)blockIdx.x * kGramChunk, e1 = min(e0 + (int64_t)kGramChunk, total);
   double s = 0.0;
   for (int64_t e = e0 + t; e < e1; e += kEwThreads) {
-    const Z w = ce_ld(W, base + e), q = ce_ld(Q, base + e);
+    const Z w = ld_wide<double>(W, base + e), q = ld_wide<double>(Q, base + e);
     const double dr = fma(-th, q.re, w.re), di = fma(-th, q.im, w.im);
     s = fma(dr, dr, s);
     s = fma(di, di, s);

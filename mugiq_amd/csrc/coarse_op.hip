@@ -3,7 +3,7 @@
 // configuration from V, the links and the clover term, and applied on the coarse grid without touching a fine vector.  Definitions, storage
 // and limits: MugiqHipCoarseOperator in include/mugiq_hip.h.
 //
-// Numerics (as csrc/restrict.hip): products and sums in fp64 whatever the storage, one rounding on the store, no atomics, and a
+// Numerics (csrc/mg_common.h): products and sums in fp64 whatever the storage, one rounding on the store, no atomics, and a
 // summation order fixed by the shape of the transfer (build) or by N (apply) alone.
 //
 // coarse_build_kernel: a workgroup owns one matrix m of one aggregate X (and, for N^2 > 4096, one chunk of 4096 of its elements); lane t
@@ -20,7 +20,7 @@
 // adjoint: the matrices of the neighbour sites, conjugate-transposed) reads the same runs and adds the rows g, g + 16, ... into its
 // columns l + 16 k.  The 16 partial sums of an output meet in LDS and are added in a fixed order by one lane.  Every vector has its own
 // accumulators and the same order wherever it stands in the batch.
-#include "internal.h"
+#include "mg_common.h"
 
 #include <algorithm>
 #include <vector>
@@ -37,18 +37,6 @@ constexpr int kCaOut = 64;       // ... output components per workgroup (4 per g
 static_assert(kGammaColumn[15][0] == 0 && kGammaColumn[15][3] == 3 && kGammaPhase[15][0] == 0 && kGammaPhase[15][1] == 0 && kGammaPhase[15][2] == 2 &&
                   kGammaPhase[15][3] == 2, "g5 = diag(1, 1, -1, -1): G5 of the coarse operator is +1 on chirality 0 and -1 on chirality 1");
 
-template <typename F> __device__ inline Cplx<double> ld_wide(const void *base, int64_t i) {
-  typedef F vec2 __attribute__((ext_vector_type(2)));
-  const vec2 t = *as_global(reinterpret_cast<const vec2 *>(base) + i);
-  return Cplx<double>{(double)t.x, (double)t.y};
-}
-template <typename F> __device__ inline void st_round(void *base, int64_t i, const Cplx<double> &v) {
-  typedef F vec2 __attribute__((ext_vector_type(2)));
-  vec2 t;
-  t.x = (F)v.re;
-  t.y = (F)v.im;
-  *as_global(reinterpret_cast<vec2 *>(base) + i) = t;
-}
 // i^ph * z
 __device__ inline Cplx<double> mul_phase(int ph, const Cplx<double> &z) {
   switch (ph & 3) {
@@ -407,6 +395,18 @@ int validate_coarse_operator(const MugiqHipCoarseOperator *op, const char *who) 
   return MUGIQ_HIP_SUCCESS;
 }
 
+int validate_transfer_operator(const MugiqHipTransfer *T, const MugiqHipCoarseOperator *op, const char *who) {
+  for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(T->X[d] > 0 && T->geoBlockSize[d] >= 1, "%s: transfer X / geo_block_size[%d]", who, d);
+  MugiqHipCoarseField c0 = coarse_side_layout(*T);
+  c0.data = reinterpret_cast<void *>(uintptr_t(16));  // geometry only: never read
+  if (int st = validate_transfer(T, &c0, who)) return st;  // a finest-level transfer (spin_block_size 2), even coarse dims
+  MUGIQ_REQUIRE(op->precision == T->precision, "%s: the coarse operator has precision %d, the transfer %d", who, op->precision, T->precision);
+  MUGIQ_REQUIRE(op->nVec == T->nVec, "%s: the coarse operator has n_vec %d, the transfer %d", who, op->nVec, T->nVec);
+  for (int d = 0; d < 4; d++)
+    MUGIQ_REQUIRE(op->X[d] == c0.X[d], "%s: coarse operator X[%d] = %d, the transfer's coarse lattice has %d", who, d, op->X[d], c0.X[d]);
+  return MUGIQ_HIP_SUCCESS;
+}
+
 int validate_coarse_vectors(const MugiqHipCoarseField *f, int n, const MugiqHipCoarseOperator *op, const char *who, const char *name) {
   for (int i = 0; i < n; i++) {
     const MugiqHipCoarseField &w = f[i];
@@ -499,14 +499,7 @@ int mugiq_hip_compute_coarse_operator(MugiqHipCoarseOperator *op, const MugiqHip
   if ((st = check_single_domain(comm, who))) return st;
   if ((st = validate_coarse_operator(op, who))) return st;
   MUGIQ_REQUIRE(transfer->V != nullptr, "%s: transfer / null vectors are NULL", who);
-  for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(transfer->X[d] > 0 && transfer->geoBlockSize[d] >= 1, "%s: transfer X / geo_block_size[%d]", who, d);
-  MugiqHipCoarseField c0 = coarse_side_layout(*transfer);
-  c0.data = reinterpret_cast<void *>(uintptr_t(16));  // geometry only: never read
-  if ((st = validate_transfer(transfer, &c0, who))) return st;  // a finest-level transfer (spin_block_size 2), even coarse dims
-  MUGIQ_REQUIRE(op->precision == transfer->precision, "%s: the coarse operator has precision %d, the transfer %d", who, op->precision, transfer->precision);
-  MUGIQ_REQUIRE(op->nVec == transfer->nVec, "%s: the coarse operator has n_vec %d, the transfer %d", who, op->nVec, transfer->nVec);
-  for (int d = 0; d < 4; d++)
-    MUGIQ_REQUIRE(op->X[d] == c0.X[d], "%s: coarse operator X[%d] = %d, the transfer's coarse lattice has %d", who, d, op->X[d], c0.X[d]);
+  if ((st = validate_transfer_operator(transfer, op, who))) return st;
   const int part[4] = {0, 0, 0, 0};
   if ((st = check_gauge(gauge, transfer->X, part, who))) return st;
   const TransferGeom g = transfer_geom(*transfer);
@@ -516,11 +509,9 @@ int mugiq_hip_compute_coarse_operator(MugiqHipCoarseOperator *op, const MugiqHip
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
-  const int pv = transfer->precision, pg = gauge->precision;
-  if (pv == 8 && pg == 8) st = launch_build<double, double>(op, transfer, gauge, clover, kappa, s);
-  else if (pv == 8) st = launch_build<double, float>(op, transfer, gauge, clover, kappa, s);
-  else if (pg == 8) st = launch_build<float, double>(op, transfer, gauge, clover, kappa, s);
-  else st = launch_build<float, float>(op, transfer, gauge, clover, kappa, s);
+  st = with_storage(transfer->precision, gauge->precision, [&](auto fv, auto fg) {
+    return launch_build<decltype(fv), decltype(fg)>(op, transfer, gauge, clover, kappa, s);
+  });
   if (st) return st;
   op->kappa = kappa;
   op->hasClover = clover ? 1 : 0;

@@ -3,7 +3,7 @@
 // eigenpair check and the eigensolver serve it as they stand).  Definition: "the operator of a coarse -> coarse transfer" in
 // include/mugiq_hip.h.  Also here: V of such a transfer <-> coarse vectors (the counterparts of csrc/mg_setup.hip's pack kernels).
 //
-// Numerics (as csrc/coarse_op.hip): products and sums in fp64 whatever the storage, one rounding on the store, no atomics, a summation
+// Numerics (csrc/mg_common.h): products and sums in fp64 whatever the storage, one rounding on the store, no atomics, a summation
 // order fixed by the transfer geometry alone -- sites of the aggregate in lexicographic order, per site the terms K_0, +x, -x, ... -t, per
 // term the colours of the finer side ascending.
 //
@@ -14,7 +14,7 @@
 // (nv x nv, k = nc) from LDS.  16 x 16 lanes carry 4 x 4 micro-tiles of T and of the output: 8 LDS reads per 16 complex products.
 // LDS: (2 nc nv + pk (nc + nv)) complex doubles, 144 KB at nc = nv = 64 with pk = 8.  The vector pipe: a once-per-configuration cost
 // (DESIGN.md 4.4f says what the matrix pipe would have bought).
-#include "internal.h"
+#include "mg_common.h"
 
 #include <algorithm>
 #include <vector>
@@ -29,19 +29,6 @@ constexpr int kC2MinPanel = 8;   // columns of K per panel where LDS is short
 constexpr int kC2LdsTarget = 4096;  // complex doubles (64 KB): panels grow up to here, for whole rows of K per read and 2+ workgroups per CU
 static_assert(16 * kC2Tile == kC2MaxN && kC2MaxN == kTransferMaxNV, "a quadrant of the largest operator is one micro-tile per lane");
 static_assert(sizeof(Cplx<double>) * (size_t)(2 * kC2MaxN * kC2MaxN + kC2MinPanel * 2 * kC2MaxN) <= kTransferMaxLds, "the largest shape fits the LDS of a workgroup");
-
-template <typename F> __device__ inline Cplx<double> ld2(const void *base, int64_t i) {
-  typedef F vec2 __attribute__((ext_vector_type(2)));
-  const vec2 t = *as_global(reinterpret_cast<const vec2 *>(base) + i);
-  return Cplx<double>{(double)t.x, (double)t.y};
-}
-template <typename F> __device__ inline void st2(void *base, int64_t i, const Cplx<double> &v) {
-  typedef F vec2 __attribute__((ext_vector_type(2)));
-  vec2 t;
-  t.x = (F)v.re;
-  t.y = (F)v.im;
-  *as_global(reinterpret_cast<vec2 *>(base) + i) = t;
-}
 
 struct CoarseBuild2Args {
   const void *V;  // [parity][(nc S + c) nv + j][x_cb]
@@ -103,7 +90,7 @@ template <typename F> __global__ __launch_bounds__(kC2Threads) void coarse_build
       }
       __syncthreads();  // the products of the previous term have been taken
       if (!staged) {
-        for (int i = t; i < nc * nv; i += kC2Threads) Vx[i] = ld2<F>(a.V, pty * a.Vpo + (int64_t)(nc * S * nv + i) * a.Vstride + x_cb);
+        for (int i = t; i < nc * nv; i += kC2Threads) Vx[i] = ld_wide<F>(a.V, pty * a.Vpo + (int64_t)(nc * S * nv + i) * a.Vstride + x_cb);
         staged = true;
       }
       // T = K(S, S') V(x'; S'), the colours c' of the neighbour ascending, panel by panel
@@ -118,9 +105,9 @@ template <typename F> __global__ __launch_bounds__(kC2Threads) void coarse_build
         if (p0 > 0) __syncthreads();  // the previous panel is through
         for (int i = t; i < nc * w; i += kC2Threads) {
           const int c0 = i / w, c1 = i - c0 * w;
-          Kp[c0 * pk + c1] = ld2<F>(a.K, kbase + (int64_t)c0 * N0 + p0 + c1);
+          Kp[c0 * pk + c1] = ld_wide<F>(a.K, kbase + (int64_t)c0 * N0 + p0 + c1);
         }
-        for (int i = t; i < w * nv; i += kC2Threads) Vp[i] = ld2<F>(a.V, npty * a.Vpo + (int64_t)((nc * Sp + p0) * nv + i) * a.Vstride + nidx);
+        for (int i = t; i < w * nv; i += kC2Threads) Vp[i] = ld_wide<F>(a.V, npty * a.Vpo + (int64_t)((nc * Sp + p0) * nv + i) * a.Vstride + nidx);
         __syncthreads();
 #pragma unroll 2
         for (int c1 = 0; c1 < w; c1++) {
@@ -163,7 +150,7 @@ template <typename F> __global__ __launch_bounds__(kC2Threads) void coarse_build
   for (int i = 0; i < kC2Tile; i++)
 #pragma unroll
     for (int k = 0; k < kC2Tile; k++)
-      if (kC2Tile * tr + i < nv && kC2Tile * tc + k < nv) st2<F>(a.out, obase + (int64_t)(kC2Tile * tr + i) * N1 + kC2Tile * tc + k, acc[i][k]);
+      if (kC2Tile * tr + i < nv && kC2Tile * tc + k < nv) st_round<F>(a.out, obase + (int64_t)(kC2Tile * tr + i) * N1 + kC2Tile * tc + k, acc[i][k]);
 }
 
 template <typename F> int launch_build2(const MugiqHipCoarseOperator *op, const MugiqHipTransfer *T, const MugiqHipCoarseOperator *finer, hipStream_t stream) {
@@ -180,11 +167,7 @@ template <typename F> int launch_build2(const MugiqHipCoarseOperator *op, const 
   const size_t lds = sizeof(Cplx<double>) * build2_lds_elems(a.nc, a.nv, a.pk);
   if (lds > kTransferMaxLds)  // (not reachable for nc, nv <= 64: the static_assert above)
     return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "computeCoarseOperatorCoarse: %zu bytes of LDS for nc = %d, n_vec = %d", lds, a.nc, a.nv);
-  if (lds > 64 * 1024)
-    MUGIQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(coarse_build2_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((coarse_build2_kernel<F>), dim3((unsigned)(2 * a.g.volumeCBc), 9, 4), dim3(kC2Threads), lds, stream, a);
-  MUGIQ_CHECK_HIP(hipGetLastError());
-  return MUGIQ_HIP_SUCCESS;
+  return launch_with_lds(coarse_build2_kernel<F>, dim3((unsigned)(2 * a.g.volumeCBc), 9, 4), kC2Threads, lds, stream, a);
 }
 
 // ---- V of a coarse -> coarse transfer <-> coarse vectors.  One lane per (parity, plane k = nc s + c, x_cb) ---------------------------
@@ -201,12 +184,12 @@ template <typename FV, typename FS> __global__ __launch_bounds__(256) void pack_
   const int x = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y, parity = blockIdx.z;
   if (x >= A.volumeCB) return;
   const int64_t src = parity * A.fPo + (int64_t)k * A.fStride + x, dst = parity * A.po + (int64_t)k * A.nVec * A.stride + x;
-  for (int j = 0; j < A.nVec; j++) st2<FV>(A.V, dst + (int64_t)j * A.stride, ld2<FS>(as_constant(A.vecs)[j], src));
+  for (int j = 0; j < A.nVec; j++) st_round<FV>(A.V, dst + (int64_t)j * A.stride, ld_wide<FS>(as_constant(A.vecs)[j], src));
 }
 template <typename FV, typename FS> __global__ __launch_bounds__(256) void unpack_coarse_vector_kernel(Pack2Args A) {
   const int x = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y, parity = blockIdx.z;
   if (x >= A.volumeCB) return;
-  st2<FS>(A.vec, parity * A.fPo + (int64_t)k * A.fStride + x, ld2<FV>(A.V, parity * A.po + ((int64_t)k * A.nVec + A.j) * A.stride + x));
+  st_round<FS>(A.vec, parity * A.fPo + (int64_t)k * A.fStride + x, ld_wide<FV>(A.V, parity * A.po + ((int64_t)k * A.nVec + A.j) * A.stride + x));
 }
 
 // the transfer of a coarse -> coarse level on its own: geometry, and the colours nc of its finer side from parity_offset = 2 nc n_vec stride
@@ -318,12 +301,9 @@ int mugiq_hip_transfer_set_coarse_vectors(const MugiqHipTransfer *transfer, cons
   if (int st = upload_table(&table, host.data(), sizeof(void *) * host.size(), s)) return st;
   Pack2Args A = pack2_args(transfer, vecs_h[0]);
   A.vecs = static_cast<const void *const *>(table);
-  const dim3 grid = pack2_grid(A, nc);
-  const int pv = transfer->precision, pf = vecs_h[0].precision;
-  if (pv == 8 && pf == 8) hipLaunchKernelGGL((pack_coarse_vectors_kernel<double, double>), grid, dim3(256), 0, s, A);
-  else if (pv == 8) hipLaunchKernelGGL((pack_coarse_vectors_kernel<double, float>), grid, dim3(256), 0, s, A);
-  else if (pf == 8) hipLaunchKernelGGL((pack_coarse_vectors_kernel<float, double>), grid, dim3(256), 0, s, A);
-  else hipLaunchKernelGGL((pack_coarse_vectors_kernel<float, float>), grid, dim3(256), 0, s, A);
+  with_storage(transfer->precision, vecs_h[0].precision, [&](auto fv, auto fs) {
+    hipLaunchKernelGGL((pack_coarse_vectors_kernel<decltype(fv), decltype(fs)>), pack2_grid(A, nc), dim3(256), 0, s, A);
+  });
   MUGIQ_CHECK_HIP(hipGetLastError());
   return MUGIQ_HIP_SUCCESS;
 }
@@ -336,12 +316,9 @@ int mugiq_hip_transfer_get_coarse_vector(const MugiqHipCoarseField *vec, const M
   hipStream_t s = static_cast<hipStream_t>(stream);
   Pack2Args A = pack2_args(transfer, *vec);
   A.vec = vec->data, A.j = j;
-  const dim3 grid = pack2_grid(A, nc);
-  const int pv = transfer->precision, pf = vec->precision;
-  if (pv == 8 && pf == 8) hipLaunchKernelGGL((unpack_coarse_vector_kernel<double, double>), grid, dim3(256), 0, s, A);
-  else if (pv == 8) hipLaunchKernelGGL((unpack_coarse_vector_kernel<double, float>), grid, dim3(256), 0, s, A);
-  else if (pf == 8) hipLaunchKernelGGL((unpack_coarse_vector_kernel<float, double>), grid, dim3(256), 0, s, A);
-  else hipLaunchKernelGGL((unpack_coarse_vector_kernel<float, float>), grid, dim3(256), 0, s, A);
+  with_storage(transfer->precision, vec->precision, [&](auto fv, auto fs) {
+    hipLaunchKernelGGL((unpack_coarse_vector_kernel<decltype(fv), decltype(fs)>), pack2_grid(A, nc), dim3(256), 0, s, A);
+  });
   MUGIQ_CHECK_HIP(hipGetLastError());
   return MUGIQ_HIP_SUCCESS;
 }

@@ -1,4 +1,5 @@
-// Internal helpers shared by the HIP translation units of libmugiq_hip.so (gfx950 only).
+// Internal helpers shared by the HIP translation units of libmugiq_hip.so (gfx950 only).  What only the multigrid translation units
+// share (storage access, the aggregate and Galerkin term walks, launch helpers) is in csrc/mg_common.h, on top of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -113,6 +114,9 @@ int deflate_low_modes(const MugiqHipSpinorField *dst, const MugiqHipSpinorField 
 int validate_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseField *c0, const char *who);
 int validate_coarse_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseField *finer_h, const MugiqHipCoarseField *coarser_h, int nVec,
                              const char *who);
+// csrc/coarse_op.hip: a finest-level transfer (validate_transfer against the coarse side it lays out itself) and the coarse operator built
+// from it: one precision, one n_vec, the operator on the transfer's coarse lattice.  T->V and op are the caller's to check first
+int validate_transfer_operator(const MugiqHipTransfer *T, const MugiqHipCoarseOperator *op, const char *who);
 // csrc/restrict.hip: mugiq_hip_deflate_low_modes_coarse with the caller's name in the messages (mugiq_hip_loop_deflate_coarse passes the
 // loop's coarse set and transfers)
 int deflate_low_modes_coarse(const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int nVec, const MugiqHipCoarseField *ev,

@@ -10,7 +10,7 @@
 // re-read from global memory, 16 of them per reduction round (the block is 590 KB at m = 1536 and n_vec = 24 in fp64; with four workgroups
 // on every CU the blocks in flight exceed the caches at 32^4, so these re-reads are what the kernel's time goes into: DESIGN.md 4.4d).
 // Every sum runs per lane over its rows in ascending order, down the wave by shuffles and over the four waves in ascending order: the order depends on m alone, so a block has the same bits in every lattice and beside any other blocks.
-#include "internal.h"
+#include "mg_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -39,18 +39,6 @@ struct BoArgs {
   int *blockZeros;     // [blocks] columns stored as zeros
   double *blockDev;    // [blocks] max |B^dag B - 1| (ortho_check_kernel)
 };
-
-template <typename F> using bo_vec2 = F __attribute__((ext_vector_type(2)));
-template <typename F> __device__ inline Z ldv(const void *V, int64_t i) {
-  const bo_vec2<F> t = *as_global(static_cast<const bo_vec2<F> *>(V) + i);
-  return Z{(double)t.x, (double)t.y};
-}
-template <typename F> __device__ inline void stv(void *V, int64_t i, const Z &z) {
-  bo_vec2<F> t;
-  t.x = (F)z.re;
-  t.y = (F)z.im;
-  *as_global(static_cast<bo_vec2<F> *>(V) + i) = t;
-}
 
 // v[0 .. nUsed) summed over the workgroup -> out[0 .. nUsed) in LDS, visible to every lane on return
 __device__ inline void bo_group_sum(double (&v)[kBoSlots], int nUsed, double (*red)[kBoSlots], double *out) {
@@ -105,7 +93,7 @@ template <typename F> __device__ inline void bo_dots(const BoArgs &A, const int6
 #pragma unroll
     for (int ii = 0; ii < kBoChunk; ii++) {
       if (ii < nc) {
-        const Z q = ldv<F>(A.V, base + (int64_t)ii * A.stride);
+        const Z q = ld_wide<F>(A.V, base + (int64_t)ii * A.stride);
         acc[2 * ii] = fma(q.re, b.re, acc[2 * ii]);
         acc[2 * ii] = fma(q.im, b.im, acc[2 * ii]);
         acc[2 * ii + 1] = fma(q.re, b.im, acc[2 * ii + 1]);
@@ -132,7 +120,7 @@ template <typename F> __global__ __launch_bounds__(kBoThreads) void block_ortho_
 #pragma unroll
       for (int s = 0; s < kBoSlots; s++) acc[s] = 0.0;
       for (int r = t; r < A.m; r += kBoThreads) {
-        const Z b = ldv<F>(A.V, rowBase[r] + (int64_t)j * A.stride);
+        const Z b = ld_wide<F>(A.V, rowBase[r] + (int64_t)j * A.stride);
         col[r] = b;
         acc[2 * kBoChunk] = fma(b.re, b.re, acc[2 * kBoChunk]);
         acc[2 * kBoChunk] = fma(b.im, b.im, acc[2 * kBoChunk]);
@@ -157,7 +145,7 @@ template <typename F> __global__ __launch_bounds__(kBoThreads) void block_ortho_
         const int64_t base = rowBase[r];
         for (int i = 0; i < j; i++) {
           const Z c = coef[i], mc{-c.re, -c.im};
-          cmadd(b, mc, ldv<F>(A.V, base + (int64_t)i * A.stride));
+          cmadd(b, mc, ld_wide<F>(A.V, base + (int64_t)i * A.stride));
         }
         col[r] = b;
         acc[0] = fma(b.re, b.re, acc[0]);
@@ -170,7 +158,7 @@ template <typename F> __global__ __launch_bounds__(kBoThreads) void block_ortho_
       // q_j = b_j / nu (nu = 0: exact zeros; a NaN in the column stays one), one rounding on the store
       for (int r = t; r < A.m; r += kBoThreads) {
         const Z b = col[r];
-        stv<F>(A.V, rowBase[r] + (int64_t)j * A.stride, nu != 0.0 ? Z{b.re / nu, b.im / nu} : Z{0.0, 0.0});
+        st_round<F>(A.V, rowBase[r] + (int64_t)j * A.stride, nu != 0.0 ? Z{b.re / nu, b.im / nu} : Z{0.0, 0.0});
       }
       __threadfence_block();
       __syncthreads();  // q_j is in memory before a lane of another wave reads it as a finished column
@@ -192,7 +180,7 @@ template <typename F> __global__ __launch_bounds__(kBoThreads) void ortho_check_
   bo_row_table(A, blk, rowBase);
   double dev = 0.0;
   for (int j = 0; j < A.nVec; j++) {
-    for (int r = t; r < A.m; r += kBoThreads) col[r] = ldv<F>(A.V, rowBase[r] + (int64_t)j * A.stride);
+    for (int r = t; r < A.m; r += kBoThreads) col[r] = ld_wide<F>(A.V, rowBase[r] + (int64_t)j * A.stride);
     for (int i0 = 0; i0 <= j; i0 += kBoChunk) {
       const int nc = min(kBoChunk, j + 1 - i0);
       double acc[kBoSlots];
@@ -266,12 +254,12 @@ template <typename FV, typename FS, int ORDER> __global__ __launch_bounds__(256)
   if (x >= A.volumeCB) return;
   const int64_t src = spinor_elem<ORDER>(parity, k, x, A.vStride, A.vPo);
   const int64_t dst = parity * A.po + (int64_t)k * A.nVec * A.stride + x;
-  for (int j = 0; j < A.nVec; j++) stv<FV>(A.V, dst + (int64_t)j * A.stride, ldv<FS>(as_constant(A.vecs)[j], src));
+  for (int j = 0; j < A.nVec; j++) st_round<FV>(A.V, dst + (int64_t)j * A.stride, ld_wide<FS>(as_constant(A.vecs)[j], src));
 }
 template <typename FV, typename FS, int ORDER> __global__ __launch_bounds__(256) void unpack_vector_kernel(PackArgs A) {
   const int x = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y, parity = blockIdx.z;
   if (x >= A.volumeCB) return;
-  stv<FS>(A.vec, spinor_elem<ORDER>(parity, k, x, A.vStride, A.vPo), ldv<FV>(A.V, parity * A.po + ((int64_t)k * A.nVec + A.j) * A.stride + x));
+  st_round<FS>(A.vec, spinor_elem<ORDER>(parity, k, x, A.vStride, A.vPo), ld_wide<FV>(A.V, parity * A.po + ((int64_t)k * A.nVec + A.j) * A.stride + x));
 }
 
 // dst = a - b on the bodies of fp64 fields of one layout (rows of rowLen complex numbers rowStride apart; pads are not touched)
@@ -287,8 +275,8 @@ __global__ __launch_bounds__(256) void field_sub_kernel(SubArgs A) {
     const int pty = e >= per ? 1 : 0;
     const int64_t rem = e - pty * per, row = rem / A.rowLen;
     const int64_t off = pty * A.po + row * A.rowStride + (rem - row * A.rowLen);
-    const Z x = ldv<double>(A.a, off), y = ldv<double>(A.b, off);
-    stv<double>(A.dst, off, Z{x.re - y.re, x.im - y.im});
+    const Z x = ld_wide<double>(A.a, off), y = ld_wide<double>(A.b, off);
+    st_round<double>(A.dst, off, Z{x.re - y.re, x.im - y.im});
   }
 }
 
@@ -352,11 +340,7 @@ BoArgs bo_args(const MugiqHipTransfer *T, const BoLevel &L, int nPasses) {
 }
 
 template <typename Kernel> int bo_launch(Kernel kern, const BoLevel &L, const BoArgs &A, hipStream_t s) {
-  if (L.ldsBytes > 48 * 1024)
-    MUGIQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.ldsBytes));
-  hipLaunchKernelGGL(kern, dim3((unsigned)L.nBlocks), dim3(kBoThreads), L.ldsBytes, s, A);
-  MUGIQ_CHECK_HIP(hipGetLastError());
-  return MUGIQ_HIP_SUCCESS;
+  return launch_with_lds(kern, dim3((unsigned)L.nBlocks), kBoThreads, L.ldsBytes, s, A);
 }
 
 // the per-block outputs in the stream's workspace: [ratio | dev | zeros | result]
@@ -438,29 +422,18 @@ int check_pack(const MugiqHipTransfer *T, const MugiqHipSpinorField *v, int n, c
   return MUGIQ_HIP_SUCCESS;
 }
 
-template <template <typename, typename, int> class Launch> int pack_dispatch(int vPrec, int sPrec, int order, const PackArgs &A, hipStream_t s) {
-  if (vPrec == 8) {
-    if (sPrec == 8) return order == 2 ? Launch<double, double, 2>::run(A, s) : Launch<double, double, 4>::run(A, s);
-    return order == 2 ? Launch<double, float, 2>::run(A, s) : Launch<double, float, 4>::run(A, s);
-  }
-  if (sPrec == 8) return order == 2 ? Launch<float, double, 2>::run(A, s) : Launch<float, double, 4>::run(A, s);
-  return order == 2 ? Launch<float, float, 2>::run(A, s) : Launch<float, float, 4>::run(A, s);
+// vectors of precision sPrec and field order `order` into V of precision vPrec (pack: A.vecs), or column A.j of V into A.vec
+int launch_pack(bool pack, int vPrec, int sPrec, int order, const PackArgs &A, hipStream_t s) {
+  with_storage(vPrec, sPrec, [&](auto fv, auto fs) {
+    using FV = decltype(fv);
+    using FS = decltype(fs);
+    const auto kern = pack ? (order == 2 ? pack_vectors_kernel<FV, FS, 2> : pack_vectors_kernel<FV, FS, 4>)
+                           : (order == 2 ? unpack_vector_kernel<FV, FS, 2> : unpack_vector_kernel<FV, FS, 4>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((A.volumeCB + 255) / 256), 12, 2), dim3(256), 0, s, A);
+  });
+  MUGIQ_CHECK_HIP(hipGetLastError());
+  return MUGIQ_HIP_SUCCESS;
 }
-inline dim3 pack_grid(const PackArgs &A) { return dim3((unsigned)((A.volumeCB + 255) / 256), 12, 2); }
-template <typename FV, typename FS, int ORDER> struct PackLaunch {
-  static int run(const PackArgs &A, hipStream_t s) {
-    hipLaunchKernelGGL((pack_vectors_kernel<FV, FS, ORDER>), pack_grid(A), dim3(256), 0, s, A);
-    MUGIQ_CHECK_HIP(hipGetLastError());
-    return MUGIQ_HIP_SUCCESS;
-  }
-};
-template <typename FV, typename FS, int ORDER> struct UnpackLaunch {
-  static int run(const PackArgs &A, hipStream_t s) {
-    hipLaunchKernelGGL((unpack_vector_kernel<FV, FS, ORDER>), pack_grid(A), dim3(256), 0, s, A);
-    MUGIQ_CHECK_HIP(hipGetLastError());
-    return MUGIQ_HIP_SUCCESS;
-  }
-};
 
 PackArgs pack_args(const MugiqHipTransfer *T, const MugiqHipSpinorField &v) {
   PackArgs A{};
@@ -478,7 +451,7 @@ int set_vectors(const MugiqHipTransfer *T, const MugiqHipSpinorField *v, hipStre
   if (int st = upload_table(&table, host.data(), sizeof(void *) * host.size(), s)) return st;
   PackArgs A = pack_args(T, v[0]);
   A.vecs = static_cast<const void *const *>(table);
-  return pack_dispatch<PackLaunch>(T->precision, v[0].precision, v[0].field_order, A, s);
+  return launch_pack(true, T->precision, v[0].precision, v[0].field_order, A, s);
 }
 
 int field_sub(const MugiqHipSpinorField &dst, const MugiqHipSpinorField &a, const MugiqHipSpinorField &b, hipStream_t s) {
@@ -556,7 +529,7 @@ int mugiq_hip_transfer_get_vector(const MugiqHipSpinorField *vec, const MugiqHip
   MUGIQ_REQUIRE(j >= 0 && j < transfer->nVec, "%s: j = %d is not in [0, n_vec = %d)", who, j, transfer->nVec);
   PackArgs A = pack_args(transfer, *vec);
   A.vec = vec->data, A.j = j;
-  return pack_dispatch<UnpackLaunch>(transfer->precision, vec->precision, vec->field_order, A, static_cast<hipStream_t>(stream));
+  return launch_pack(false, transfer->precision, vec->precision, vec->field_order, A, static_cast<hipStream_t>(stream));
 }
 
 int mugiq_hip_mg_setup_param_default(MugiqHipMgSetupParam *p) {

@@ -6,8 +6,8 @@
 // One set of kernels serves both levels and both storages: a field is a list of rows of complex numbers (MgLayout; fine FLOAT2: 12 rows of
 // volumeCB per parity, fine FLOAT4: 6 rows of 2 volumeCB, coarse: 2 n_vec rows of volumeCB_c) stored as Cplx<F>, F = double or float.  Every
 // lane takes one whole complex number per access (16 bytes in fp64, 8 bytes in fp32, consecutive along a row: a wave's access is one
-// contiguous run of 1 KiB or 512 B), widens it to fp64 on the load (ldz), forms every product and every sum in fp64 and rounds once on the
-// store (stz); the scalars -- partial sums, Gram-Schmidt coefficients, nu, alpha -- are fp64 in device memory for either storage.  The
+// contiguous run of 1 KiB or 512 B), widens it to fp64 on the load (ld_wide, csrc/mg_common.h), forms every product and every sum in fp64 and
+// rounds once on the store (st_round); the scalars -- partial sums, Gram-Schmidt coefficients, nu, alpha -- are fp64 in device memory for either storage.  The
 // element a lane takes does not depend on F, so the order of every sum is the same in both storages, and no alignment beyond that of one
 // complex number is asked of a row (an odd stride or a row that cuts a wave needs no peeling).  Pads are never touched.  blockIdx.y is
 // the right-hand side; a right-hand side whose `active` bit is clear is not touched.  Every sum is taken per lane over its elements in
@@ -18,7 +18,7 @@
 // reaches all of them without a pointer table.  Scalars never leave the device inside K: mg_final_sum_kernel turns the partial sums into
 // the Gram-Schmidt coefficients, into (nu, alpha) of a GCR step or into alpha of an MR step, and the next kernel reads them from memory.
 // The host reads only the squared residual norms of the outer iteration (and ||b||^2 and the true residual, once per block each).
-#include "internal.h"
+#include "mg_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -47,20 +47,6 @@ template <typename I> __device__ inline int64_t mg_offset(const MgLayout &L, I e
   const int pty = e >= per ? 1 : 0;
   const I rem = e - (pty ? per : (I)0), row = rem / rowLen;
   return pty * L.po + (int64_t)row * L.rowStride + (int64_t)(rem - row * rowLen);
-}
-
-// one complex number of storage F, widened to fp64 / rounded once from fp64 (F = double: the same bits both ways)
-template <typename F> __device__ inline Z ldz(const Cplx<F> *p, int64_t i) {
-  typedef F vec2 __attribute__((ext_vector_type(2)));
-  const vec2 t = *as_global(reinterpret_cast<const vec2 *>(p) + i);
-  return Z{(double)t.x, (double)t.y};
-}
-template <typename F> __device__ inline void stz(Cplx<F> *p, int64_t i, const Z &v) {
-  typedef F vec2 __attribute__((ext_vector_type(2)));
-  vec2 t;
-  t.x = (F)v.re;
-  t.y = (F)v.im;
-  *as_global(reinterpret_cast<vec2 *>(p) + i) = t;
 }
 
 // v[0 .. nUsed) summed over the workgroup -> out[0 .. nUsed): down the wave by shuffles, then the four waves in ascending order
@@ -95,11 +81,11 @@ __global__ __launch_bounds__(kMgThreads) void mg_multidot_kernel(const Cplx<F> *
   const Cplx<F> *qk = Q + ((int64_t)k * nb + v) * vecElems;
   for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
     const int64_t off = mg_offset<I>(L, e);
-    const Z q = ldz(qk, off);
+    const Z q = ld_wide(qk, off);
 #pragma unroll
     for (int j = 0; j < kMgMaxDir - 1; j++) {
       if (j < k) {
-        const Z a = ldz(Q + ((int64_t)j * nb + v) * vecElems, off);
+        const Z a = ld_wide(Q + ((int64_t)j * nb + v) * vecElems, off);
         acc[2 * j] = fma(a.re, q.re, acc[2 * j]);
         acc[2 * j] = fma(a.im, q.im, acc[2 * j]);
         acc[2 * j + 1] = fma(a.re, q.im, acc[2 * j + 1]);
@@ -124,21 +110,21 @@ __global__ __launch_bounds__(kMgThreads) void mg_multiaxpy_kernel(Cplx<F> *P, Cp
   Cplx<F> *pk = P + ((int64_t)k * nb + v) * vecElems, *qk = Q + ((int64_t)k * nb + v) * vecElems;
   for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
     const int64_t off = mg_offset<I>(L, e);
-    Z q = ldz(qk, off);
+    Z q = ld_wide(qk, off);
     if (k > 0) {
-      Z p = ldz(pk, off);
+      Z p = ld_wide(pk, off);
 #pragma unroll
       for (int j = 0; j < kMgMaxDir - 1; j++) {
         if (j < k) {
           const Z cj{-c[2 * j], -c[2 * j + 1]};
-          cmadd(p, cj, ldz(P + ((int64_t)j * nb + v) * vecElems, off));
-          cmadd(q, cj, ldz(Q + ((int64_t)j * nb + v) * vecElems, off));
+          cmadd(p, cj, ld_wide(P + ((int64_t)j * nb + v) * vecElems, off));
+          cmadd(q, cj, ld_wide(Q + ((int64_t)j * nb + v) * vecElems, off));
         }
       }
-      stz(pk, off, p);
-      stz(qk, off, q);
+      st_round(pk, off, p);
+      st_round(qk, off, q);
     }
-    const Z r = ldz(R.p[v], off);
+    const Z r = ld_wide(R.p[v], off);
     acc[0] = fma(q.re, q.re, acc[0]);
     acc[0] = fma(q.im, q.im, acc[0]);
     acc[1] = fma(q.re, r.re, acc[1]);
@@ -163,22 +149,22 @@ __global__ __launch_bounds__(kMgThreads) void mg_update_kernel(Cplx<F> *P, Cplx<
   Cplx<F> *pn = Pnext ? Pnext + ((int64_t)(k + 1) * nb + v) * vecElems : nullptr;
   for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
     const int64_t off = mg_offset<I>(L, e);
-    Z p = ldz(pk, off), q = ldz(qk, off);
+    Z p = ld_wide(pk, off), q = ld_wide(qk, off);
     if (nu > 0.0) {
       p = Z{p.re / nu, p.im / nu};
       q = Z{q.re / nu, q.im / nu};
     } else {
       p = q = Z{0.0, 0.0};
     }
-    stz(pk, off, p);
-    stz(qk, off, q);
-    Z x = xZero ? Z{0.0, 0.0} : ldz(X.p[v], off);
+    st_round(pk, off, p);
+    st_round(qk, off, q);
+    Z x = xZero ? Z{0.0, 0.0} : ld_wide(X.p[v], off);
     cmadd(x, alpha, p);
-    stz(X.p[v], off, x);
-    Z r = ldz(R.p[v], off);
+    st_round(X.p[v], off, x);
+    Z r = ld_wide(R.p[v], off);
     cmadd(r, malpha, q);
-    stz(R.p[v], off, r);
-    if (pn) stz(pn, off, r);
+    st_round(R.p[v], off, r);
+    if (pn) st_round(pn, off, r);
     acc[0] = fma(r.re, r.re, acc[0]);
     acc[0] = fma(r.im, r.im, acc[0]);
   }
@@ -192,7 +178,7 @@ template <typename F, typename I> __global__ __launch_bounds__(kMgThreads) void 
   double acc[3] = {0.0, 0.0, 0.0};
   for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
     const int64_t off = mg_offset<I>(L, e);
-    const Z t = ldz(T.p[v], off), s = ldz(S.p[v], off);
+    const Z t = ld_wide(T.p[v], off), s = ld_wide(S.p[v], off);
     acc[0] = fma(t.re, s.re, acc[0]);
     acc[0] = fma(t.im, s.im, acc[0]);
     acc[1] = fma(t.re, s.im, acc[1]);
@@ -213,13 +199,13 @@ __global__ __launch_bounds__(kMgThreads) void mg_mr_update_kernel(MgVecs<F> Zv, 
   const Z alpha{sc[4 * v], sc[4 * v + 1]}, malpha{-alpha.re, -alpha.im};
   for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)L.total; e += (I)gridDim.x * kMgThreads) {
     const int64_t off = mg_offset<I>(L, e);
-    Z s = ldz(S.p[v], off);
-    Z z = zZero ? Z{0.0, 0.0} : ldz(Zv.p[v], off);
+    Z s = ld_wide(S.p[v], off);
+    Z z = zZero ? Z{0.0, 0.0} : ld_wide(Zv.p[v], off);
     cmadd(z, alpha, s);
-    stz(Zv.p[v], off, z);
+    st_round(Zv.p[v], off, z);
     if (writeS) {
-      cmadd(s, malpha, ldz(T.p[v], off));
-      stz(SOut.p[v], off, s);
+      cmadd(s, malpha, ld_wide(T.p[v], off));
+      st_round(SOut.p[v], off, s);
     }
   }
 }
@@ -233,15 +219,15 @@ __global__ __launch_bounds__(kMgThreads) void mg_axpby_kernel(MgVecs<F> C, MgVec
     const int64_t off = mg_offset<I>(L, e);
     Z o{0.0, 0.0};
     if (A.p[v]) {
-      const Z a = ldz(A.p[v], off);
+      const Z a = ld_wide(A.p[v], off);
       o = Z{sa * a.re, sa * a.im};
     }
     if (B.p[v]) {
-      const Z b = ldz(B.p[v], off);
+      const Z b = ld_wide(B.p[v], off);
       o.re = fma(sb, b.re, o.re);
       o.im = fma(sb, b.im, o.im);
     }
-    stz(C.p[v], off, o);
+    st_round(C.p[v], off, o);
   }
 }
 
@@ -253,7 +239,7 @@ __global__ __launch_bounds__(kMgThreads) void mg_convert_kernel(MgVecs<FD> D, Mg
   const int v = blockIdx.y;
   if (!((active >> v) & 1u)) return;
   for (I e = (I)blockIdx.x * kMgThreads + threadIdx.x; e < (I)Ls.total; e += (I)gridDim.x * kMgThreads)
-    stz(D.p[v], mg_offset<I>(Ld, e), ldz(S.p[v], mg_offset<I>(Ls, e)));
+    st_round(D.p[v], mg_offset<I>(Ld, e), ld_wide(S.p[v], mg_offset<I>(Ls, e)));
 }
 
 // The sums of the last pass over its workgroups, in ascending order, one lane per (right-hand side, slot), and what the next kernel needs
@@ -657,15 +643,9 @@ int check_problem(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in,
     MUGIQ_REQUIRE(same_layout(out[i], out[0]) && same_layout(in[i], out[0]),
                   "%s: vector %d of %s or %s differs in precision, field order, geometry, stride or parity offset from %s vector 0", who, i, outName, inName,
                   outName);
-  for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(transfer->X[d] > 0 && transfer->geoBlockSize[d] >= 1, "%s: transfer X / geo_block_size[%d]", who, d);
-  MugiqHipCoarseField c0 = coarse_side_layout(*transfer);
-  c0.data = reinterpret_cast<void *>(uintptr_t(16));  // geometry only: never read
-  if ((st = validate_transfer(transfer, &c0, who))) return st;
-  MUGIQ_REQUIRE(op->nVec == transfer->nVec, "%s: the coarse operator has n_vec %d, the transfer %d", who, op->nVec, transfer->nVec);
-  for (int d = 0; d < 4; d++) {
-    MUGIQ_REQUIRE(op->X[d] == c0.X[d], "%s: coarse operator X[%d] = %d, the transfer's coarse lattice has %d", who, d, op->X[d], c0.X[d]);
+  if ((st = validate_transfer_operator(transfer, op, who))) return st;  // (the precisions agree by the checks above)
+  for (int d = 0; d < 4; d++)
     MUGIQ_REQUIRE(in[0].X[d] == transfer->X[d], "%s: the fields have X[%d] = %d, the transfer %d", who, d, in[0].X[d], transfer->X[d]);
-  }
   const int part[4] = {0, 0, 0, 0};
   if ((st = check_gauge(gauge, in[0].X, part, who))) return st;
   if (clover) {

@@ -14,7 +14,7 @@
 // (3 MB each) are served by L2.  V is read from HBM exactly once per call (the reference re-reads it N_ev times).
 // With CONTRACT the prolonged vectors are consumed on the spot by the Hermitian 16-gamma accumulation and never
 // written: the ultra-local loop of the MG path costs one pass over V instead of N_ev fine-vector writes + reads.
-#include "internal.h"
+#include "mg_common.h"
 
 #include <algorithm>
 #include <vector>
@@ -224,15 +224,6 @@ template <typename Args> static void set_lattices(Args &a, const TransferGeom &g
 template <typename Args> static void set_geometry(Args &a, const TransferGeom &g) {
   set_lattices(a, g);
   a.volumeCB = g.volumeCB, a.volumeCBc = g.volumeCBc, a.aggVol = g.aggVol;
-}
-// a launch with the dynamic LDS its form asks for
-template <typename Kernel, typename Args>
-static int launch_with_lds(Kernel kern, int workgroups, int threads, size_t ldsBytes, hipStream_t stream, const Args &a) {
-  if (ldsBytes > 64 * 1024)
-    MUGIQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
-  hipLaunchKernelGGL(kern, dim3((unsigned)workgroups), dim3(threads), ldsBytes, stream, a);
-  MUGIQ_CHECK_HIP(hipGetLastError());
-  return MUGIQ_HIP_SUCCESS;
 }
 
 // the vector kernel of a form (ProlongForm or ContractForm); staged: the family with the V tile in LDS
@@ -491,17 +482,7 @@ __global__ __launch_bounds__(4 * NH * SPR) void fine_congruence_kernel(FineCongr
   for (int i = t; i < NC * NC; i += NT) Cs[i] = Cg[i];
 
   // fine site (parity, x_cb) of aggregate member k (lexicographic inside the block); k >= aggVol shadows the last one
-  auto member = [&](int k, int &pty, int &x_cb) {
-    if (k >= a.aggVol) k = a.aggVol - 1;
-    int x[4];
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-      x[d] = cc[d] * a.bs[d] + k % a.bs[d];
-      k /= a.bs[d];
-    }
-    pty = (x[0] + x[1] + x[2] + x[3]) & 1;
-    x_cb = lex_index(x, a.X) >> 1;
-  };
+  auto member = [&](int k, int &pty, int &x_cb) { aggregate_member(a.bs, a.X, cc, min(k, a.aggVol - 1), &pty, &x_cb); };
 
   const int rounds = (a.aggVol + SPR - 1) / SPR;
   const int stSite = t % SPR, stRow0 = t / SPR;  // staging: this lane always fetches site stSite, rows stRow0 + LPS*i
@@ -647,16 +628,7 @@ template <typename F, int NV, bool GLDS> __global__ __launch_bounds__(64 * (NV /
     cfrag[2 * m + 1] = (site & 1) == 0 ? -cv.im : cv.re;  // V_im contributes -Im C to T_re,  Re C to T_im
   }
   // fine site (parity, x_cb) of aggregate member k (lexicographic inside the block)
-  auto member = [&](int k, int &pty, int &x_cb) {
-    int x[4];
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-      x[d] = cc[d] * a.bs[d] + k % a.bs[d];
-      k /= a.bs[d];
-    }
-    pty = (x[0] + x[1] + x[2] + x[3]) & 1;
-    x_cb = lex_index(x, a.X) >> 1;
-  };
+  auto member = [&](int k, int &pty, int &x_cb) { aggregate_member(a.bs, a.X, cc, k, &pty, &x_cb); };
   // staging: element e = row * 16 + site of the round's tile, e = t + NT * q (six per lane for every n_vec); consecutive lanes
   // take the 16 sites of a row, a wave instruction four consecutive rows = 1 KiB of the LDS image
   vec2 u[GLDS ? 1 : NLD];
@@ -1001,16 +973,7 @@ template <int NV> __global__ __launch_bounds__(64 * kPmWaves) void prolong_mfma_
     }
   }
   // fine site (parity, x_cb) of aggregate member k (lexicographic inside the block)
-  auto member = [&](int k, int &pty, int &x_cb) {
-    int x[4];
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-      x[d] = cc[d] * a.bs[d] + k % a.bs[d];
-      k /= a.bs[d];
-    }
-    pty = (x[0] + x[1] + x[2] + x[3]) & 1;
-    x_cb = lex_index(x, a.X) >> 1;
-  };
+  auto member = [&](int k, int &pty, int &x_cb) { aggregate_member(a.bs, a.X, cc, k, &pty, &x_cb); };
   const int stSite = t & 15;
   auto fetch = [&](int rd, Cplx<double> *buf) {
     int pty, x_cb;

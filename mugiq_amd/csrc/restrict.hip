@@ -16,7 +16,7 @@
 // (Measured, DESIGN.md 4.4a: 3.4 x one read of V; the right-hand sides are re-loaded by all 8 groups of a site, V comes in 32-byte pieces.)
 // Workgroups follow xcd_contiguous_block: x-adjacent aggregates share the 128-byte lines of a V row and run on one XCD.
 // Coarse -> coarse levels (256 x smaller): restrict_coarse_kernel, one lane per coarse site, output component and eight vectors.
-#include "internal.h"
+#include "mg_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -40,34 +40,10 @@ __device__ inline double gamma5_diag(int s) {
   return s == 0 ? gamma5_entry<0>() : s == 1 ? gamma5_entry<1>() : s == 2 ? gamma5_entry<2>() : gamma5_entry<3>();
 }
 
-template <typename F> __device__ inline Cplx<double> ld_wide(const void *base, int64_t i) {
-  typedef F vec2 __attribute__((ext_vector_type(2)));
-  const vec2 t = *as_global(reinterpret_cast<const vec2 *>(base) + i);
-  return Cplx<double>{(double)t.x, (double)t.y};
-}
-template <typename F> __device__ inline void st_round(void *base, int64_t i, const Cplx<double> &v) {
-  typedef F vec2 __attribute__((ext_vector_type(2)));
-  vec2 t;
-  t.x = (F)v.re;
-  t.y = (F)v.im;
-  *as_global(reinterpret_cast<vec2 *>(base) + i) = t;
-}
 // complex element of component k = 3 s + c of a fine field body (SpinorView, internal.h)
 template <int ORDER> __device__ inline int64_t fine_elem(int k, int pty, int x_cb, int stride, int64_t po) {
   if constexpr (ORDER == 2) return pty * po + (int64_t)k * stride + x_cb;
   else return pty * po + 2 * ((int64_t)(k >> 1) * stride + x_cb) + (k & 1);
-}
-
-// member k (lexicographic inside the block) of the aggregate at coarse coordinates cc
-__device__ inline void aggregate_member(const TransferGeom &g, const int cc[4], int k, int *pty, int *x_cb) {
-  int x[4];
-#pragma unroll
-  for (int d = 0; d < 4; d++) {
-    x[d] = cc[d] * g.bs[d] + k % g.bs[d];
-    k /= g.bs[d];
-  }
-  *pty = (x[0] + x[1] + x[2] + x[3]) & 1;
-  *x_cb = lex_index(x, g.X) >> 1;
 }
 
 struct RestrictArgs {
@@ -106,7 +82,7 @@ template <typename FV, typename FS, int ORDER> __global__ __launch_bounds__(kRsS
         for (int n = 0; n < kRsRB; n++) acc[i][n] = Cplx<double>{0.0, 0.0};
       for (int k = slot; k < a.g.aggVol; k += kRsSlots) {
         int pty, x_cb;
-        aggregate_member(a.g, cc, k, &pty, &x_cb);
+        aggregate_member(a.g.bs, a.g.X, cc, k, &pty, &x_cb);
         const int64_t voff = pty * a.Vpo + x_cb;
         for (int sc = 0; sc < 6; sc++) {
           const int comp = chi * 6 + sc;
@@ -245,7 +221,7 @@ template <typename F> __global__ __launch_bounds__(128) void restrict_coarse_ker
   for (int i = 0; i < kRsRB; i++) acc[i] = Cplx<double>{0.0, 0.0};
   for (int m = 0; m < a.g.aggVol; m++) {
     int pty, x_cb;
-    aggregate_member(a.g, cc, m, &pty, &x_cb);
+    aggregate_member(a.g.bs, a.g.X, cc, m, &pty, &x_cb);
     for (int c = 0; c < a.NCf; c++) {
       const int plane = s * a.NCf + c;
       const Cplx<double> v = ld_wide<F>(a.V, pty * a.Vpo + (int64_t)(plane * a.NV + j) * a.Vstride + x_cb);
