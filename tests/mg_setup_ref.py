@@ -1,10 +1,11 @@
 """numpy restatement of the MG setup (mugiq_hip_block_orthonormalize, mugiq_hip_transfer_orthonormality and mugiq_hip_mg_setup in
 include/mugiq_hip.h), written from the contracts there: classical Gram-Schmidt per (aggregate, coarse spin) block with every coefficient
 of a column taken from the un-updated column, repeated nPasses times; the null-vector recipe v = start - CG(M start); packing; refinement
-by the two-grid solve.  The operators, the CG and the solve are the tests' own (wilson_ref, mg_solve_ref).  It shares no code with the
+by the two-grid solve.  The operators, the CG and the solve are the tests' own (wilson_ref, clover_ref, mg_solve_ref).  It shares no code with the
 product, and its blocks are gathered with the oracle's aggregate map, not with the kernel's site table."""
 import numpy as np
 
+import clover_ref as cr
 import mg_solve_ref as mgr
 import wilson_ref as wr
 from util import orc
@@ -95,21 +96,21 @@ def pack(vectors):
 
 
 def setup(X, Uo, kappa, bs, starts, setupMaxIter=500, setupTol=5e-6, nBlockOrtho=2, refineCycles=0, refineIters=4, A_eo=None):
-    """(V, [CG iterations], minPivotRatio of the last orthonormalisation) of mugiq_hip_mg_setup"""
+    """(V, [CG iterations], minPivotRatio of the last orthonormalisation) of mugiq_hip_mg_setup.  A_eo [2, volCB, 12, 12]: the clover term,
+    which then stands in M and M^dag of the null-vector CG, in the coarse operator and in the M of the refinement solve."""
     def M(v):
-        return wr.wilson_M(v, Uo, kappa, X)
+        return wr.wilson_M(v, Uo, kappa, X) if A_eo is None else cr.clover_M(v, Uo, A_eo, kappa, X)
 
     def Mdag(v):
-        return wr.wilson_M(v, Uo, kappa, X, dagger=True)
+        return wr.wilson_M(v, Uo, kappa, X, dagger=True) if A_eo is None else cr.clover_M(v, Uo, A_eo, kappa, X, dagger=True)
 
-    assert A_eo is None
     vs, its = [], []
     for s in starts:
         v, it = null_vector(M, Mdag, np.asarray(s, dtype=np.complex128), setupTol, setupMaxIter)
         vs.append(v), its.append(it)
     V, ratio, _ = block_orthonormalize(pack(vs), X, bs, 2, nBlockOrtho)
     for _ in range(refineCycles):
-        prob = mgr.Problem(X, Uo, kappa, V, bs)
+        prob = mgr.Problem(X, Uo, kappa, V, bs, A_eo)
         vs = [v - mgr.solve(prob, M(v), tol=setupTol, maxIter=refineIters, nKrylov=refineIters)[0] for v in vs]
         V, ratio, _ = block_orthonormalize(pack(vs), X, bs, 2, nBlockOrtho)
     return V, its, ratio

@@ -1,6 +1,7 @@
 """CPU tests of the MG setup: the numpy restatement of the block orthonormalisation (tests/mg_setup_ref.py) against numpy.linalg.qr, one
 pass against two on a near-dependent block, the null-vector recipe, the packing of V, the solve iteration counts with setup-made null
-vectors, and every refusal of the new entry points, which come before any device work (no GPU is there)."""
+vectors, the restatement's setup with a clover term (at coefficient 0 against the Wilson run, and the numbers the device is held to),
+and every refusal of the new entry points, which come before any device work (no GPU is there)."""
 import ctypes
 import os
 import subprocess
@@ -16,11 +17,11 @@ from util import ROOT
 
 
 # ---- the restatement against QR -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(msc.ORTHO_SHAPES))
+@pytest.mark.parametrize("name", list(msc.FINEST_SHAPES))
 def test_restatement_against_qr(name, record_max):
     """Two passes of the contract on random blocks: max |B^dag B - 1| and the distance to the Q of numpy's QR (positive diagonal) stay
     below the numbers written into mg_setup_cases.py, which the device is held to 100 x of."""
-    X, bs, nvec = msc.ORTHO_SHAPES[name]
+    X, bs, nvec = msc.FINEST_SHAPES[name]
     V, ratio, zeros = msc.reference(name)
     orth = msr.orthonormality(V, X, bs)
     dist = float(np.max(np.abs(V - msc.qr_reference(name))))
@@ -40,6 +41,21 @@ def test_restatement_against_qr_coarse_layout(record_max):
     record_max("mg_setup_restatement_orthonormality", orth)
     record_max("mg_setup_restatement_vs_qr", dist)
     assert zeros == 0 and orth <= msc.RESTATEMENT["coarse"][0] and dist <= msc.RESTATEMENT["coarse"][1]
+
+
+@pytest.mark.parametrize("name", ["coarse96", "coarse7"])
+def test_restatement_against_qr_coarse_scale(name, record_max):
+    """The same on the coarse -> coarse inputs of tests/test_gpu_mg_setup_scale.py: n_vec 96 on nColor 24, and nColor 7 on aggregates
+    with an odd extent."""
+    X, bs, nc, nvec = msc.COARSE_SHAPES[name]
+    V, ratio, zeros, qr = msc.coarse_reference(name)
+    assert msr.to_blocks(V, X, bs, 1).shape[1:] == (2, nc * int(np.prod(bs)), nvec)
+    orth, dist = msr.orthonormality(V, X, bs, 1), float(np.max(np.abs(V - qr)))
+    print("%s: restatement |B^dag B - 1| = %.3e, distance to QR = %.3e, minPivotRatio = %.3e" % (name, orth, dist, ratio))
+    record_max("mg_setup_restatement_orthonormality", orth)
+    record_max("mg_setup_restatement_vs_qr", dist)
+    assert zeros == 0 and 0.0 < ratio <= 1.0
+    assert orth <= msc.RESTATEMENT[name][0] and dist <= msc.RESTATEMENT[name][1]
 
 
 def test_blocks_round_trip_and_are_the_aggregates():
@@ -139,6 +155,43 @@ def test_setup_counts(field, refineCycles):
     assert count == msc.SETUP_COUNTS[(field, refineCycles)]
     if field == "smooth":
         assert count < mgc.SMOOTH_COUNTS["random"]
+
+
+# ---- the driver with a clover term ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("refineCycles", [0, 1])
+def test_clover_setup_at_coefficient_zero_is_the_wilson_setup(refineCycles, record_max):
+    """At clover coefficient 0 the term is A = 1 (clover_ref.clover_dense gives exactly that), and M = (M_wilson - 1) + A differs from
+    M_wilson by one rounding per entry: the setup with that A_eo -- CG, coarse operator and refinement solve all through the clover
+    path -- has the CG counts of the Wilson run, and its V within 100 x the Wilson run's own deviation under 1-ulp perturbations of the
+    start vectors, the measure the device is held to."""
+    import clover_ref as cr
+    from util import random_gauge_lex
+    one = np.zeros((2, int(np.prod(mgc.RAGGED[0])) // 2, 12, 12), dtype=np.complex128)
+    one[...] = np.eye(12)
+    assert np.array_equal(cr.clover_dense(random_gauge_lex(np.random.default_rng(5), (2, 2, 2, 2)), 0.0)[0, 0, 0, 0], np.eye(12))
+    v = msc.ragged_starts()[0]
+    assert np.array_equal(cr.apply_A(one, v), v)
+    V, its, ratio = msc.ragged_reference_setup(False, refineCycles)
+    V0, its0, ratio0 = msc.ragged_setup(True, refineCycles, msc.ragged_starts(), A_eo=one)
+    dev, scale = float(np.max(np.abs(V0 - V)) / np.max(np.abs(V))), msc.ragged_setup_sensitivity(False, refineCycles)
+    print("%d cycles: A = 1 moves V by %.3e, 1-ulp perturbations by %.3e" % (refineCycles, dev, scale))
+    record_max("mg_setup_clover_zero_vs_wilson", dev)
+    assert its0 == its and abs(ratio0 - ratio) <= 1e-6 * ratio
+    assert dev <= msc.FACTOR * scale
+
+
+@pytest.mark.parametrize("clover,refineCycles", list(msc.RAGGED_PIVOTS))
+def test_clover_setup_pins(clover, refineCycles):
+    """What tests/test_gpu_mg_setup_scale.py holds the device to at mg_solve_cases.RAGGED: every CG stops at its 10 iterations, the
+    pinned minPivotRatio, a rounding-sized orthonormality; and the clover term moves V by far more than any bound there."""
+    X, bs, nvec = mgc.RAGGED
+    V, its, ratio = msc.ragged_reference_setup(clover, refineCycles)
+    pin = msc.RAGGED_PIVOTS[(clover, refineCycles)]
+    print("clover %s, %d cycles: minPivotRatio %.10f (pinned %.10f)" % (clover, refineCycles, ratio, pin))
+    assert its == [msc.SETUP["setupMaxIter"]] * nvec and abs(ratio - pin) <= 1e-6 * pin
+    assert msr.orthonormality(V, X, bs) < 20 * np.finfo(np.float64).eps          # rounding-sized after two passes (m = 324)
+    other = msc.ragged_reference_setup(not clover, refineCycles)[0]
+    assert np.max(np.abs(V - other)) > 1e-3
 
 
 # ---- refusals -------------------------------------------------------------------------------------------------------------------------
