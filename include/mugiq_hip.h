@@ -843,7 +843,8 @@ int mugiq_hip_mg_solve_param_default(MugiqHipMgSolveParam *param);
 /* z_i = K(r_i), i < nVec.  z_h, r_h: fp64 fields of one layout (FLOAT2 | FLOAT4, any stride; pads are neither read nor written), no z
  * overlapping any r; they need no ghost zones.  transfer: a finest-level one of precision 8 on the fields' lattice; coarseOp: the operator
  * built from it for this gauge field, clover field and kappa (precision 8).  tol and maxIter of `param` are checked but not used.
- * Limits, each refused before any device work: a single domain (MUGIQ_HIP_ERROR_UNSUPPORTED, as for the coarse operator) and a two-grid cycle;
+ * Limits, each refused before any device work: a single domain (MUGIQ_HIP_ERROR_UNSUPPORTED, as for the coarse operator) and a two-grid cycle
+ * (three levels: mugiq_hip_mg_precondition_levels, below);
  * precision 4 anywhere in transfer, coarse operator or fields (MUGIQ_HIP_ERROR_UNSUPPORTED); parameters out of range, geometry mismatches
  * between fields, transfer and operator, a coarse operator built for another kappa or without / with the clover term of the call
  * (op->kappa, op->hasClover), a z overlapping an r or another z (MUGIQ_HIP_ERROR_INVALID_ARGUMENT).
@@ -921,6 +922,58 @@ int mugiq_hip_mg_convert_precision(const MugiqHipSpinorField *dst_h, const Mugiq
  * through the host.  One rounding on the store, pads neither read nor written; finest-level and coarse -> coarse transfers alike.
  * Different geometries, a NULL V or overlapping buffers: MUGIQ_HIP_ERROR_INVALID_ARGUMENT, before any device work. */
 int mugiq_hip_transfer_convert(const MugiqHipTransfer *dst, const MugiqHipTransfer *src, void *stream);
+
+/* ---- the three-level solve (new; csrc/mg_solve.hip): the K-cycle through the coarsest operator, what the reference's MG_Mugiq runs with
+ * n_level 3.  The eight entry points above do not change, in bits or in refusals; they are these with nCoarseLevels = 1.
+ *
+ * Levels.  Level 0 is the fine lattice with M.  Level l >= 1 carries the explicit operator M_l = coarseOps_h[l-1]; T_l = transfers_h[l]
+ * connects level l and l + 1; R_l and P_l are the batched restriction and prolongation (finest-level for l = 0, coarse -> coarse for
+ * l >= 1).  L = nCoarseLevels in {1, 2}.
+ *   Cyc(A, R, P, S; nuPre, nuPost, omega)(r):  z = 0, s = r;  nuPre MR steps on A;  if S is given: z += P S(R s), s = r - A z (one
+ *     application);  nuPost MR steps;  returns z.  Word for word the K of mugiq_hip_mg_solve, with the same elisions of copies.
+ *   GCRflex(A, C, b, n):  x = 0, r = b; for k < n:  p = C(r), q = A p, then the step of GCRfix (classical Gram-Schmidt in one pass, the
+ *     nu = 0 guard, alpha = <q, r> / nu taken in the orthogonalising pass).  Returns x.
+ *   K_1   = Cyc(M_1, R_1, P_1, GCRfix(M_2, ., params[1].coarseIters); params[1])        (S absent for params[1].coarseIters = 0)
+ *   K^(3) = Cyc(M,   R_0, P_0, GCRflex(M_1, K_1, ., params[0].coarseIters); params[0])  (S absent for params[0].coarseIters = 0)
+ * With L = 1 the level-1 solve is GCRfix(M_1, ., params[0].coarseIters) and the cycle IS K.  The outer solve is that of
+ * mugiq_hip_mg_solve with p = K^(3)(r).
+ * Parameters.  params_h[0] is the whole MugiqHipMgSolveParam of the two-grid calls: tol, maxIter and nKrylov of the outer solve and the
+ * cycle on level 0.  Of params_h[1] only nuPre, nuPost, omega and coarseIters are used; the rest is range-checked and ignored.
+ * nuPre + nuPost + coarseIters = 0 in params_h[1] would make K_1 = 0 and is MUGIQ_HIP_ERROR_INVALID_ARGUMENT.  params_h[0].coarseIters = 0
+ * is allowed: levels 1 and 2 are then never touched (but still checked).  The struct defaults are NOT tuned for level 1.
+ * Promises, as for the two-grid calls: blocks of 8 right-hand sides with a mask, a converged one is not touched, one solved alone equals
+ * the same one in any batch bit for bit, no atomics and fixed summation orders, identical bits, counts and histories from two runs, pads
+ * neither read nor written, K^(3)(2^k r) = 2^k K^(3)(r) bit for bit; in fp32 storage every load is widened, sums are fp64 and the store
+ * rounds once.  Nothing is read back inside K^(3): hostReads stays max(iters of the block) + 2 per block of 8.
+ * Refused before any device work: nCoarseLevels outside 1 .. 2 (MUGIQ_HIP_ERROR_UNSUPPORTED); a process grid or a partitioned axis
+ * (UNSUPPORTED); the precision rules of the twin for EVERY object of the hierarchy (mixed precisions inside one hierarchy: UNSUPPORTED in
+ * the fp64 calls, INVALID_ARGUMENT in the sloppy and mixed ones); transfers_h[1] not a spinBlockSize 1 transfer on the lattice of
+ * coarseOps_h[0] with parity_offset = 2 coarseOps_h[0].nVec nVec stride; coarseOps_h[1] not on the coarse side of transfers_h[1] with its
+ * nVec; kappa or hasClover mismatches of either operator; overlapping fields or operators; parameter ranges per level.
+ * Work memory (per-stream operator workspace), beyond that of the twin: per right-hand side of a block 3 level-1 vectors (s, t, w of K_1)
+ * and 2 params[1].coarseIters + 2 level-2 vectors; the result of K_1 goes straight into the direction slot p_k of level 1.  In all for
+ * mugiq_hip_mg_precondition_levels: 3 min(nVec, 8) fine, (2 params[0].coarseIters + 5) min(nVec, 8) level-1 and
+ * (2 params[1].coarseIters + 2) min(nVec, 8) level-2 vectors and 0.6 MB of scalars; the solves add the fine vectors of their twins. */
+int mugiq_hip_mg_precondition_levels(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
+                                     const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfers_h,
+                                     const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h,
+                                     const MugiqHipComm *comm, void *stream);
+int mugiq_hip_mg_solve_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                              const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfers_h,
+                              const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h, int *iters_out,
+                              double *relres_out, double *history_out, int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream);
+/* everything in precision 4, as mugiq_hip_mg_precondition_sloppy */
+int mugiq_hip_mg_precondition_sloppy_levels(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
+                                            const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfers_h,
+                                            const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h,
+                                            const MugiqHipComm *comm, void *stream);
+/* fp64 fields and outer GCR, the whole hierarchy in precision 4, as mugiq_hip_mg_solve_mixed */
+int mugiq_hip_mg_solve_mixed_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                                    const MugiqHipCloverField *clover, double kappa, const MugiqHipGaugeField *gaugeSloppy,
+                                    const MugiqHipCloverField *cloverSloppy, const MugiqHipTransfer *transfersSloppy_h,
+                                    const MugiqHipCoarseOperator *coarseOpsSloppy_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h,
+                                    int *iters_out, double *relres_out, double *history_out, int historyStride, int *hostReads_out,
+                                    const MugiqHipComm *comm, void *stream);
 
 /* ---- MG setup (new; csrc/mg_setup.hip): what QUDA's newMultigridQuda does before MG_Mugiq / Eigsolve_Mugiq see a transfer
  * (tests/loop.cpp:347-365: setup_inv, setup_maxiter, setup_tol, num_setup_iter, n_block_ortho) -- from a gauge field to V and M_c.

@@ -277,6 +277,76 @@ inline bool mgSolveMixed(const std::vector<ColorSpinorField> &x, const std::vect
   }
   return st == 0;
 }
+// ---- the three-level solve (csrc/mg_solve.hip; new): the same four calls on a hierarchy, transfers[l] and coarseOps[l] (descriptors, e.g.
+// *CoarseOperator::desc()) per coarse level and params[l] per level; one of each is the two-grid call.  params[1]: nuPre, nuPost, omega and
+// coarseIters of the level-1 cycle, whose defaults are not tuned ----
+namespace detail {
+static_assert(sizeof(MgSolveParam) == sizeof(MugiqHipMgSolveParam), "std::vector<MgSolveParam> is handed over as an array of the C struct");
+inline int mgLevels(const std::vector<MugiqHipTransfer> &transfers, const std::vector<MugiqHipCoarseOperator> &coarseOps, const std::vector<MgSolveParam> &params,
+                    const char *who) {
+  if (transfers.empty() || transfers.size() != coarseOps.size() || transfers.size() != params.size())
+    throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, std::string(who) + ": one transfer, coarse operator and MgSolveParam per coarse level");
+  return (int)transfers.size();
+}
+inline bool mgHistory(int st, const std::vector<double> &hist, int stride, const std::vector<int> &iters, std::vector<std::vector<double>> *history) {
+  if (st != MUGIQ_HIP_ERROR_NOT_CONVERGED) check(st);
+  if (history) {
+    history->clear();
+    for (size_t i = 0; i < iters.size(); i++) history->emplace_back(hist.begin() + i * stride, hist.begin() + i * stride + iters[i]);
+  }
+  return st == 0;
+}
+}  // namespace detail
+inline void mgPrecondition(const std::vector<ColorSpinorField> &z, const std::vector<ColorSpinorField> &r, const GaugeField &gauge,
+                           const MugiqHipCloverField *clover, double kappa, const std::vector<MugiqHipTransfer> &transfers,
+                           const std::vector<MugiqHipCoarseOperator> &coarseOps, const std::vector<MgSolveParam> &params, const MugiqHipComm *comm = nullptr,
+                           void *stream = nullptr) {
+  if (r.empty() || z.size() != r.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgPrecondition: size mismatch");
+  const int L = detail::mgLevels(transfers, coarseOps, params, "mgPrecondition");
+  check(mugiq_hip_mg_precondition_levels(z.data(), r.data(), (int)r.size(), &gauge, clover, kappa, transfers.data(), coarseOps.data(), L, params.data(), comm,
+                                         stream));
+}
+inline void mgPreconditionSloppy(const std::vector<ColorSpinorField> &z, const std::vector<ColorSpinorField> &r, const GaugeField &gauge,
+                                 const MugiqHipCloverField *clover, double kappa, const std::vector<MugiqHipTransfer> &transfers,
+                                 const std::vector<MugiqHipCoarseOperator> &coarseOps, const std::vector<MgSolveParam> &params,
+                                 const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (r.empty() || z.size() != r.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgPreconditionSloppy: size mismatch");
+  const int L = detail::mgLevels(transfers, coarseOps, params, "mgPreconditionSloppy");
+  check(mugiq_hip_mg_precondition_sloppy_levels(z.data(), r.data(), (int)r.size(), &gauge, clover, kappa, transfers.data(), coarseOps.data(), L, params.data(),
+                                                comm, stream));
+}
+inline bool mgSolve(const std::vector<ColorSpinorField> &x, const std::vector<ColorSpinorField> &b, const GaugeField &gauge,
+                    const MugiqHipCloverField *clover, double kappa, const std::vector<MugiqHipTransfer> &transfers,
+                    const std::vector<MugiqHipCoarseOperator> &coarseOps, const std::vector<MgSolveParam> &params, std::vector<int> &iters,
+                    std::vector<double> &relres, std::vector<std::vector<double>> *history = nullptr, int *hostReads = nullptr,
+                    const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
+  if (b.empty() || x.size() != b.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgSolve: size mismatch");
+  const int L = detail::mgLevels(transfers, coarseOps, params, "mgSolve");
+  iters.assign(b.size(), 0);
+  relres.assign(b.size(), 0.0);
+  const int stride = params[0].maxIter > 0 ? params[0].maxIter : 1;
+  std::vector<double> hist(history ? b.size() * (size_t)stride : 0);
+  const int st = mugiq_hip_mg_solve_levels(x.data(), b.data(), (int)b.size(), &gauge, clover, kappa, transfers.data(), coarseOps.data(), L, params.data(),
+                                           iters.data(), relres.data(), history ? hist.data() : nullptr, stride, hostReads, comm, stream);
+  return detail::mgHistory(st, hist, stride, iters, history);
+}
+inline bool mgSolveMixed(const std::vector<ColorSpinorField> &x, const std::vector<ColorSpinorField> &b, const GaugeField &gauge,
+                         const MugiqHipCloverField *clover, double kappa, const GaugeField *gaugeSloppy, const MugiqHipCloverField *cloverSloppy,
+                         const std::vector<MugiqHipTransfer> &transfersSloppy, const std::vector<MugiqHipCoarseOperator> &coarseOpsSloppy,
+                         const std::vector<MgSolveParam> &params, std::vector<int> &iters, std::vector<double> &relres,
+                         std::vector<std::vector<double>> *history = nullptr, int *hostReads = nullptr, const MugiqHipComm *comm = nullptr,
+                         void *stream = nullptr) {
+  if (b.empty() || x.size() != b.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgSolveMixed: size mismatch");
+  const int L = detail::mgLevels(transfersSloppy, coarseOpsSloppy, params, "mgSolveMixed");
+  iters.assign(b.size(), 0);
+  relres.assign(b.size(), 0.0);
+  const int stride = params[0].maxIter > 0 ? params[0].maxIter : 1;
+  std::vector<double> hist(history ? b.size() * (size_t)stride : 0);
+  const int st = mugiq_hip_mg_solve_mixed_levels(x.data(), b.data(), (int)b.size(), &gauge, clover, kappa, gaugeSloppy, cloverSloppy, transfersSloppy.data(),
+                                                 coarseOpsSloppy.data(), L, params.data(), iters.data(), relres.data(), history ? hist.data() : nullptr,
+                                                 stride, hostReads, comm, stream);
+  return detail::mgHistory(st, hist, stride, iters, history);
+}
 // dst_i = src_i between spinor fields of either precision (mugiq_hip_mg_convert_precision)
 inline void mgConvertPrecision(const std::vector<ColorSpinorField> &dst, const std::vector<ColorSpinorField> &src, void *stream = nullptr) {
   if (src.empty() || dst.size() != src.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgConvertPrecision: size mismatch");

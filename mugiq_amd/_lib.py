@@ -271,6 +271,16 @@ SIGNATURES = {
     "mugiq_hip_mg_solve_mixed": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, _GP, _CP, ctypes.POINTER(TransferDesc),
                                                 ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(MgSolveParam), _I4, ctypes.POINTER(ctypes.c_double),
                                                 ctypes.POINTER(ctypes.c_double), ctypes.c_int, _I4, _VP, _VP]),
+    "mugiq_hip_mg_precondition_levels": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
+                                                        ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int, ctypes.POINTER(MgSolveParam), _VP, _VP]),
+    "mugiq_hip_mg_solve_levels": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
+                                                 ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int, ctypes.POINTER(MgSolveParam), _I4,
+                                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_int, _I4, _VP, _VP]),
+    "mugiq_hip_mg_precondition_sloppy_levels": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
+                                                               ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int, ctypes.POINTER(MgSolveParam), _VP, _VP]),
+    "mugiq_hip_mg_solve_mixed_levels": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, _GP, _CP, ctypes.POINTER(TransferDesc),
+                                                       ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int, ctypes.POINTER(MgSolveParam), _I4,
+                                                       ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_int, _I4, _VP, _VP]),
     "mugiq_hip_mg_convert_precision": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _VP]),
     "mugiq_hip_transfer_convert": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.POINTER(TransferDesc), _VP]),
     "mugiq_hip_block_orthonormalize": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.c_int, ctypes.c_double, ctypes.POINTER(BlockOrthoInfo), _VP]),

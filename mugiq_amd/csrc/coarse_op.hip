@@ -32,7 +32,7 @@ constexpr int kCbThreads = 256;  // build: lanes of a workgroup
 constexpr int kCbEPT = 16;       // ... matrix elements a lane carries
 constexpr int kCaThreads = 256;  // apply: 16 groups x 16 lanes
 constexpr int kCaRB = 8;         // ... vectors per workgroup
-constexpr int kCaOut = 64;       // ... output components per workgroup (4 per group or lane)
+constexpr int kCaOut = 64;       // ... output components per workgroup (4 per group or lane); the small-lattice forms take 32 or 16
 
 static_assert(kGammaColumn[15][0] == 0 && kGammaColumn[15][3] == 3 && kGammaPhase[15][0] == 0 && kGammaPhase[15][1] == 0 && kGammaPhase[15][2] == 2 &&
                   kGammaPhase[15][3] == 2, "g5 = diag(1, 1, -1, -1): G5 of the coarse operator is +1 on chirality 0 and -1 on chirality 1");
@@ -244,18 +244,24 @@ struct CoarseApplyArgs {
   double scale;
 };
 
-template <typename F, int DAG> __global__ __launch_bounds__(kCaThreads) void coarse_apply_kernel(CoarseApplyArgs a) {
+// OUT = 64 | 32 | 16 output components per workgroup: every 16-lane group (M) or lane (M^dag) owns OUT / 16 of them, and blockIdx.z walks
+// N / OUT chunks.  What one output is made of does not depend on OUT -- the 9 matrices in order, lane l over c = l, l + 16, ..., then
+// the 16 partial sums in ascending order, every product an explicit fma -- so all three give the same bits; a smaller OUT only spreads a
+// small lattice over more workgroups (launch_apply chooses)
+template <typename F, int DAG, int OUT> __global__ __launch_bounds__(kCaThreads) void coarse_apply_kernel(CoarseApplyArgs a) {
+  static_assert(OUT == 16 || OUT == 32 || OUT == 64, "outputs per workgroup");
+  constexpr int NI = OUT / 16;                     // outputs per group or lane
   extern __shared__ Cplx<double> in_s[];           // [8][N]: the input vectors at the neighbour of the current matrix
   __shared__ Cplx<double> red[16][kCaRB][16 + 1];  // the 16 partial sums of 16 outputs x 8 vectors
   const int NV = a.NV, N = 2 * NV, t = threadIdx.x, l = t & 15, g = t >> 4;
-  const int site = blockIdx.x, n0 = blockIdx.y * kCaRB, o0 = blockIdx.z * kCaOut;
+  const int site = blockIdx.x, n0 = blockIdx.y * kCaRB, o0 = blockIdx.z * OUT;
   const int cpar = site / a.volumeCBc, xc_cb = site - cpar * a.volumeCBc;
   int cc[4];
   get_coords(cc, xc_cb, a.Xc, cpar);
   const auto *tab = as_constant(a.tab);
-  Cplx<double> acc[4][kCaRB];
+  Cplx<double> acc[NI][kCaRB];
 #pragma unroll
-  for (int i = 0; i < 4; i++)
+  for (int i = 0; i < NI; i++)
 #pragma unroll
     for (int v = 0; v < kCaRB; v++) acc[i][v] = Cplx<double>{0.0, 0.0};
 
@@ -280,7 +286,7 @@ template <typename F, int DAG> __global__ __launch_bounds__(kCaThreads) void coa
 #pragma unroll
         for (int v = 0; v < kCaRB; v++) x[v] = in_s[v * N + c];
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
+        for (int i = 0; i < NI; i++) {
           const int r = o0 + g + 16 * i;
           if (r < N) {
             const Cplx<double> e = ld_wide<F>(a.op, mbase + (int64_t)r * N + c);
@@ -295,7 +301,7 @@ template <typename F, int DAG> __global__ __launch_bounds__(kCaThreads) void coa
 #pragma unroll
         for (int v = 0; v < kCaRB; v++) x[v] = in_s[v * N + r];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
+        for (int k = 0; k < NI; k++) {
           const int c = o0 + l + 16 * k;
           if (c < N) {
             const Cplx<double> e = ld_wide<F>(a.op, mbase + (int64_t)r * N + c);
@@ -308,7 +314,7 @@ template <typename F, int DAG> __global__ __launch_bounds__(kCaThreads) void coa
   }
   // output o0 + p + 16 i, p = g (M) | l (M^dag): its 16 partial sums, added in ascending order by one lane
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
+  for (int i = 0; i < NI; i++) {
     __syncthreads();  // the previous trip has been read
 #pragma unroll
     for (int v = 0; v < kCaRB; v++) red[DAG ? l : g][v][DAG ? g : l] = acc[i][v];
@@ -326,6 +332,28 @@ template <typename F, int DAG> __global__ __launch_bounds__(kCaThreads) void coa
       }
     }
   }
+}
+
+// The outputs per workgroup of coarse_apply_kernel, decided here and nowhere else, on the host: from the workgroups the 64-output grid
+// would have.  With one workgroup per coarse site (256 at 4^4 with N = 64, one per compute unit) the 64-output form leaves the device short
+// of waves; the 32-output form, twice as many workgroups that each read the same inputs and half of the matrix rows, took 0.69 x its time
+// there and 1.18 x at 512 workgroups (the 16-output form: 0.83 x and 1.26 x).  MUGIQ_HIP_COARSE_APPLY_OUT = 16 | 32 | 64
+// overrides the rule (anything else is ignored); the bits do not depend on it
+constexpr int64_t kCaSmallGrid = 512;
+int apply_outputs_per_workgroup(int64_t workgroups64) {
+  if (const char *e = getenv("MUGIQ_HIP_COARSE_APPLY_OUT")) {
+    const int o = atoi(e);
+    if (o == 16 || o == 32 || o == 64) return o;
+  }
+  return workgroups64 < kCaSmallGrid ? 32 : kCaOut;
+}
+
+template <typename F, int DAG>
+void launch_apply_form(int out, dim3 grid, size_t lds, hipStream_t stream, const CoarseApplyArgs &a, int N) {
+  grid.z = (N + out - 1) / out;
+  if (out == 16) hipLaunchKernelGGL((coarse_apply_kernel<F, DAG, 16>), grid, dim3(kCaThreads), lds, stream, a);
+  else if (out == 32) hipLaunchKernelGGL((coarse_apply_kernel<F, DAG, 32>), grid, dim3(kCaThreads), lds, stream, a);
+  else hipLaunchKernelGGL((coarse_apply_kernel<F, DAG, 64>), grid, dim3(kCaThreads), lds, stream, a);
 }
 
 // dst_i = scale [G5] M_c^(dag) src_i, i < n
@@ -353,11 +381,12 @@ int launch_apply(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src,
   a.scale = scale;
   const int N = 2 * op->nVec;
   const dim3 grid(2 * op->volumeCB, (n + kCaRB - 1) / kCaRB, (N + kCaOut - 1) / kCaOut);
+  const int out = apply_outputs_per_workgroup((int64_t)grid.x * grid.y * grid.z);
   const size_t lds = sizeof(Cplx<double>) * (size_t)kCaRB * N;
-  if (op->precision == 8 && !dagger) hipLaunchKernelGGL((coarse_apply_kernel<double, 0>), grid, dim3(kCaThreads), lds, stream, a);
-  else if (op->precision == 8) hipLaunchKernelGGL((coarse_apply_kernel<double, 1>), grid, dim3(kCaThreads), lds, stream, a);
-  else if (!dagger) hipLaunchKernelGGL((coarse_apply_kernel<float, 0>), grid, dim3(kCaThreads), lds, stream, a);
-  else hipLaunchKernelGGL((coarse_apply_kernel<float, 1>), grid, dim3(kCaThreads), lds, stream, a);
+  if (op->precision == 8 && !dagger) launch_apply_form<double, 0>(out, grid, lds, stream, a, N);
+  else if (op->precision == 8) launch_apply_form<double, 1>(out, grid, lds, stream, a, N);
+  else if (!dagger) launch_apply_form<float, 0>(out, grid, lds, stream, a, N);
+  else launch_apply_form<float, 1>(out, grid, lds, stream, a, N);
   MUGIQ_CHECK_HIP(hipGetLastError());
   return MUGIQ_HIP_SUCCESS;
 }

@@ -1,7 +1,9 @@
 // A flexible GCR on the fine Wilson(-clover) operator, preconditioned by one two-grid cycle K: MR smoothing and a coarse-grid correction
 // through R, a fixed number of GCR steps on the explicit coarse operator, and P.  Definitions (MR step, GCRfix, K, the outer solve), limits
 // and work memory: mugiq_hip_mg_solve in include/mugiq_hip.h.  The stencil, R, P and the coarse application are the library's own entry
-// points, called as they are; what is new here are the Krylov kernels between them, on both levels.
+// points, called as they are; what is new here are the Krylov kernels between them, on every level.  With a second coarse level the
+// level-1 solve becomes a flexible GCR preconditioned by a cycle of its own through the coarsest operator (K^(3), the *_levels entry
+// points: MgSolver::cycle is K with the level abstracted, MgSolver::coarse_solve the level-1 solve of either depth).
 //
 // One set of kernels serves both levels and both storages: a field is a list of rows of complex numbers (MgLayout; fine FLOAT2: 12 rows of
 // volumeCB per parity, fine FLOAT4: 6 rows of 2 volumeCB, coarse: 2 n_vec rows of volumeCB_c) stored as Cplx<F>, F = double or float.  Every
@@ -327,7 +329,7 @@ template <typename F> struct MgLevel {
   bool wide = false;  // MUGIQ_HIP_DEBUG_WIDE_INDEX, as the call found it (MgSolver::init)
   int64_t vecElems = 0;
   C *P = nullptr, *Q = nullptr;  // nDir x nb vectors each
-  double *partial = nullptr, *coef = nullptr, *sc = nullptr, *res = nullptr;  // shared by both levels: the stream orders their passes
+  double *partial = nullptr, *coef = nullptr, *sc = nullptr, *res = nullptr;  // shared by all levels: the stream orders their passes (MgSolver::carve)
   hipStream_t stream = nullptr;
 
   void set_layout(const MgLayout &l) {
@@ -401,15 +403,23 @@ template <typename F> struct MgSolver {
   const MugiqHipCoarseOperator *op;
   MugiqHipMgSolveParam prm;
   hipStream_t stream;
+  // the second coarse level of a three-level cycle (transfer1 NULL: two-grid): T_1, M_2 and params[1], set by set_coarsest() before init()
+  const MugiqHipTransfer *transfer1 = nullptr;
+  const MugiqHipCoarseOperator *op2 = nullptr;
+  MugiqHipMgSolveParam prm1{};
   int nb, nDirFine, sets;
-  bool withCoarse;
-  size_t fb, cb;
-  MgLevel<F> fine, coarse;
+  bool withCoarse, withCoarse2;
+  size_t fb, cb, cb2;
+  MgLevel<F> fine, coarse, coarse2;
   // r: the solver's recursive residual (mixed solve, F = float: its rounded copy); zk: K's result before it is widened (mixed solve only)
   MugiqHipSpinorField s[kMgBlock], t[kMgBlock], w[kMgBlock], r[kMgBlock], zk[kMgBlock];
   MugiqHipCoarseField xc[kMgBlock], rc[kMgBlock];
+  // K_1's own vectors on level 1 and the coarsest solve's on level 2 (three levels only)
+  MugiqHipCoarseField s1[kMgBlock], t1[kMgBlock], w1[kMgBlock], xc2[kMgBlock], rc2[kMgBlock];
   MugiqHipSpinorField fineLike;
-  MugiqHipCoarseField coarseLike;
+  MugiqHipCoarseField coarseLike, coarse2Like;
+
+  void set_coarsest(const MugiqHipTransfer *T1, const MugiqHipCoarseOperator *M2, const MugiqHipMgSolveParam &p1) { transfer1 = T1, op2 = M2, prm1 = p1; }
 
   static Vecs vecs(const MugiqHipSpinorField *f, int n) {
     Vecs m{};
@@ -431,6 +441,11 @@ template <typename F> struct MgSolver {
     f.data = coarse.dir(base, j, v);
     return f;
   }
+  MugiqHipCoarseField coarse2_dir(C *base, int j, int v) const {
+    MugiqHipCoarseField f = coarse2Like;
+    f.data = coarse2.dir(base, j, v);
+    return f;
+  }
   template <typename T> static int gather(const T *set, int n, unsigned mask, T *out) {
     int m = 0;
     for (int i = 0; i < n; i++)
@@ -444,10 +459,18 @@ template <typename F> struct MgSolver {
     gather(src, n, active, sr);
     return mugiq_hip_wilson_clover_apply(d, sr, m, gauge, clover, kappa, MUGIQ_HIP_EIG_OPERATOR_M, 1.0, nullptr, stream);
   }
+  // dst_i = A src_i for the active i, A an explicit coarse operator (M_1 or M_2)
+  int apply_coarse(const MugiqHipCoarseOperator *A, const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src, int n, unsigned active) const {
+    MugiqHipCoarseField d[kMgBlock], sr[kMgBlock];
+    const int m = gather(dst, n, active, d);
+    gather(src, n, active, sr);
+    return coarse_apply(d, sr, m, A, MUGIQ_HIP_EIG_OPERATOR_M, 1.0, stream);
+  }
 
   // The work memory is carved from the stream's operator workspace: the scalars, then per right-hand side of a block 2 nDirFine fine
   // directions and the fine vectors of `sets` (K: s, t, w; the solver: r as well), and with the coarse level 2 coarseIters directions,
-  // xc, rc.  init() fixes the layouts and sizes (vectors laid out like `like`, stored as Cplx<F>), vector_bytes() is this solver's share
+  // xc, rc; with three levels also s, t, w of K_1 on level 1 and, for params[1].coarseIters > 0, 2 params[1].coarseIters directions, xc
+  // and rc on level 2.  init() fixes the layouts and sizes (vectors laid out like `like`, stored as Cplx<F>), vector_bytes() is this solver's share
   // and carve() places it; the mixed solve carves two solvers from one reservation.
   // apply_M calls the public stencil entry, which reserves the SAME arena for itself (csrc/wilson.hip, wilson_apply_impl) and takes its
   // start as the send buffer of its halo exchange.  That is safe here for two reasons, both of which this file depends on: on a single
@@ -472,12 +495,31 @@ template <typename F> struct MgSolver {
     fine.vecElems = (int64_t)(fb / sizeof(C));
     coarse.set_layout(coarse_layout(coarseLike));
     coarse.vecElems = (int64_t)(cb / sizeof(C));
+    withCoarse2 = false, cb2 = 0;
+    if (transfer1 && withCoarse) {
+      coarse2Like = coarse_side_layout(*transfer1);
+      cb2 = coarse_bytes<F>(coarse2Like);
+      withCoarse2 = prm1.coarseIters > 0;
+      coarse2.stream = stream, coarse2.nb = nb, coarse2.wide = fine.wide;
+      coarse2.set_layout(coarse_layout(coarse2Like));
+      coarse2.vecElems = (int64_t)(cb2 / sizeof(C));
+    }
   }
   int n_sets() const { return __builtin_popcount((unsigned)sets); }
-  size_t vector_bytes() const { return (size_t)(2 * nDirFine + n_sets()) * nb * fb + (size_t)(withCoarse ? 2 * prm.coarseIters + 2 : 0) * nb * cb; }
+  bool three_level() const { return transfer1 != nullptr && withCoarse; }
+  size_t vector_bytes() const {
+    return (size_t)(2 * nDirFine + n_sets()) * nb * fb + (size_t)((withCoarse ? 2 * prm.coarseIters + 2 : 0) + (three_level() ? 3 : 0)) * nb * cb +
+           (size_t)(withCoarse2 ? 2 * prm1.coarseIters + 2 : 0) * nb * cb2;
+  }
   unsigned char *carve(unsigned char *scalars, unsigned char *cur) {
+    // One set of scalars serves every level because the stream orders the passes and every scalar lives for one launch: a final sum
+    // writes coef, (nu, alpha) or an MR alpha, and the very next launch of that level's step (multi-axpy, update, MR update) is its
+    // only reader.  Nesting K_1 inside a GCR step of level 1 does not change that: p_k = K_1(r) and q_k = M_1 p_k are complete launches
+    // that come BEFORE the step's own multi-dot, so no scalar of the step exists yet while K_1 and the coarsest solve overwrite them,
+    // and K_1's last alpha was consumed by its last update.  Only `res` is read by the host, straight after the final sum that wrote it.
     fine.set_scalars(scalars);
     coarse.set_scalars(scalars);
+    coarse2.set_scalars(scalars);
     fine.P = reinterpret_cast<C *>(cur);
     cur += (size_t)nDirFine * nb * fb;
     fine.Q = reinterpret_cast<C *>(cur);
@@ -495,12 +537,26 @@ template <typename F> struct MgSolver {
       cur += (size_t)nC * nb * cb;
       coarse.Q = reinterpret_cast<C *>(cur);
       cur += (size_t)nC * nb * cb;
-      MugiqHipCoarseField *csets[2] = {xc, rc};
+      MugiqHipCoarseField *csets[5] = {xc, rc, s1, t1, w1};
+      for (int k = 0; k < (three_level() ? 5 : 2); k++)
+        for (int i = 0; i < nb; i++) {
+          csets[k][i] = coarseLike;
+          csets[k][i].data = cur;
+          cur += cb;
+        }
+    }
+    if (withCoarse2) {
+      const int nC = prm1.coarseIters;
+      coarse2.P = reinterpret_cast<C *>(cur);
+      cur += (size_t)nC * nb * cb2;
+      coarse2.Q = reinterpret_cast<C *>(cur);
+      cur += (size_t)nC * nb * cb2;
+      MugiqHipCoarseField *csets[2] = {xc2, rc2};
       for (auto *set : csets)
         for (int i = 0; i < nb; i++) {
-          set[i] = coarseLike;
+          set[i] = coarse2Like;
           set[i].data = cur;
-          cur += cb;
+          cur += cb2;
         }
     }
     return cur;
@@ -515,73 +571,118 @@ template <typename F> struct MgSolver {
     return MUGIQ_HIP_SUCCESS;
   }
 
-  // one MR step on (z, sIn): t = M sIn, alpha on the device, z += alpha sIn, s = sIn - alpha t (last: s is not needed again)
-  int mr_step(const MugiqHipSpinorField *z, const MugiqHipSpinorField *sIn, bool zZero, bool last, int n, unsigned active) const {
-    if (int st = apply_M(t, sIn, n, active)) return st;
-    const Vecs tv = vecs(t, n), sv = vecs(sIn, n), so = vecs(s, n);
-    if (int st = fine.dot2(tv, sv, n, active, kMgFinMr, prm.omega)) return st;
-    return fine.mr_update(vecs(z, n), sv, tv, last ? nullptr : &so, zZero, n, active);
+  // x = GCRfix(A, r, nC) on level `lv` (directions P, Q of that level) for the active right-hand sides; r is used up
+  int gcr_fixed(const MgLevel<F> &lv, const MugiqHipCoarseField &like, const MugiqHipCoarseOperator *A, int nC, const MugiqHipCoarseField *x,
+                const MugiqHipCoarseField *r, int n, unsigned active) const {
+    MugiqHipCoarseField p[kMgBlock], q[kMgBlock];
+    for (int i = 0; i < n; i++) {
+      p[i] = like;
+      p[i].data = lv.dir(lv.P, 0, i);
+    }
+    const Vecs rv = vecs(r, n), xv = vecs(x, n), pv = vecs(p, n);
+    if (int st = lv.axpby(pv, &rv, 1.0, nullptr, 0.0, n, active)) return st;
+    for (int k = 0; k < nC; k++) {
+      for (int i = 0; i < n; i++) {
+        p[i] = q[i] = like;
+        p[i].data = lv.dir(lv.P, k, i);
+        q[i].data = lv.dir(lv.Q, k, i);
+      }
+      if (int st = apply_coarse(A, q, p, n, active)) return st;
+      if (int st = lv.gcr_step(k, xv, rv, k == 0, k + 1 < nC, false, n, active)) return st;
+    }
+    return MUGIQ_HIP_SUCCESS;
   }
 
-  // xc = GCRfix(M_c, rc, coarseIters) for the active right-hand sides; rc is used up
+  // xc = the level-1 solve of rc for the active right-hand sides; rc is used up.  Two-grid: GCRfix(M_1, rc, coarseIters).  Three levels:
+  // GCRflex(M_1, K_1, rc, coarseIters), where K_1 writes its result straight into the direction slot p_k
   int coarse_solve(int n, unsigned active) const {
     const int nC = prm.coarseIters;
-    MugiqHipCoarseField p0[kMgBlock];
-    for (int i = 0; i < n; i++) p0[i] = coarse_dir(coarse.P, 0, i);
-    const Vecs rv = vecs(rc, n), xv = vecs(xc, n), pv = vecs(p0, n);
-    if (int st = coarse.axpby(pv, &rv, 1.0, nullptr, 0.0, n, active)) return st;
+    if (!three_level()) return gcr_fixed(coarse, coarseLike, op, nC, xc, rc, n, active);
+    const Vecs rv = vecs(rc, n), xv = vecs(xc, n);
     for (int k = 0; k < nC; k++) {
-      MugiqHipCoarseField p[kMgBlock], q[kMgBlock], pa[kMgBlock], qa[kMgBlock];
+      MugiqHipCoarseField p[kMgBlock], q[kMgBlock];
       for (int i = 0; i < n; i++) {
         p[i] = coarse_dir(coarse.P, k, i);
         q[i] = coarse_dir(coarse.Q, k, i);
       }
-      const int m = gather(p, n, active, pa);
-      gather(q, n, active, qa);
-      if (int st = coarse_apply(qa, pa, m, op, MUGIQ_HIP_EIG_OPERATOR_M, 1.0, stream)) return st;
-      if (int st = coarse.gcr_step(k, xv, rv, k == 0, k + 1 < nC, false, n, active)) return st;
+      if (int st = precondition1(p, rc, n, active)) return st;
+      if (int st = apply_coarse(op, q, p, n, active)) return st;
+      if (int st = coarse.gcr_step(k, xv, rv, k == 0, false, false, n, active)) return st;
     }
     return MUGIQ_HIP_SUCCESS;
   }
 
-  // z_i = K(r_i) for the active i: a fixed sequence of launches, nothing read back.  z and r are not touched elsewhere; r is only read
-  int precondition(const MugiqHipSpinorField *z, const MugiqHipSpinorField *r, int n, unsigned active) const {
+  // z_i = Cyc(A, R, P, S; p)(r_i) for the active i on level `lv`, with the level's own vectors s, t, w: a fixed sequence of launches,
+  // nothing read back.  applyA(dst, src, n, active): dst = A src; correct(dst, src, n, active): dst = P S(R src), called for
+  // p.coarseIters > 0 only.  z and r are not touched elsewhere; r is only read
+  template <typename Fld, typename ApplyA, typename Correct>
+  int cycle(const MgLevel<F> &lv, const MugiqHipMgSolveParam &p, const ApplyA &applyA, const Correct &correct, const Fld *z, const Fld *r, const Fld *s_,
+            const Fld *t_, const Fld *w_, int n, unsigned active) const {
     bool zZero = true;
-    const MugiqHipSpinorField *sIn = r;  // where s lives: r itself until the first update
-    const bool coarseStep = prm.coarseIters > 0;
+    const Fld *sIn = r;  // where s lives: r itself until the first update
+    const bool coarseStep = p.coarseIters > 0;
     int st;
-    for (int i = 0; i < prm.nuPre; i++) {
-      if ((st = mr_step(z, sIn, zZero, !coarseStep && prm.nuPost == 0 && i == prm.nuPre - 1, n, active))) return st;
+    // one MR step on (z, sIn): t = A sIn, alpha on the device, z += alpha sIn, s = sIn - alpha t (last: s is not needed again)
+    auto mr_step = [&](bool last) {
+      if (int e = applyA(t_, sIn, n, active)) return e;
+      const Vecs tv = vecs(t_, n), sv = vecs(sIn, n), so = vecs(s_, n);
+      if (int e = lv.dot2(tv, sv, n, active, kMgFinMr, p.omega)) return e;
+      const int e = lv.mr_update(vecs(z, n), sv, tv, last ? nullptr : &so, zZero, n, active);
       zZero = false;
-      sIn = s;
-    }
+      sIn = s_;
+      return e;
+    };
+    for (int i = 0; i < p.nuPre; i++)
+      if ((st = mr_step(!coarseStep && p.nuPost == 0 && i == p.nuPre - 1))) return st;
     if (coarseStep) {
-      MugiqHipSpinorField fa[kMgBlock];
-      MugiqHipCoarseField ca[kMgBlock];
-      int m = gather(sIn, n, active, fa);
-      gather(rc, n, active, ca);
-      if ((st = mugiq_hip_restrict_batched(ca, fa, m, transfer, 0, stream))) return st;
-      if ((st = coarse_solve(n, active))) return st;
-      gather(xc, n, active, ca);
-      gather(zZero ? z : w, n, active, fa);
-      if ((st = mugiq_hip_prolongate_batched(fa, ca, m, transfer, stream))) return st;
-      const Vecs zv = vecs(z, n), wv = vecs(w, n);
-      if (!zZero && (st = fine.axpby(zv, &zv, 1.0, &wv, 1.0, n, active))) return st;
+      if ((st = correct(zZero ? z : w_, sIn, n, active))) return st;
+      const Vecs zv = vecs(z, n), wv = vecs(w_, n);
+      if (!zZero && (st = lv.axpby(zv, &zv, 1.0, &wv, 1.0, n, active))) return st;
       zZero = false;
-      if (prm.nuPost > 0) {  // s = r - M z, one application
-        if ((st = apply_M(t, z, n, active))) return st;
-        const Vecs rv = vecs(r, n), tv = vecs(t, n);
-        if ((st = fine.axpby(vecs(s, n), &rv, 1.0, &tv, -1.0, n, active))) return st;
-        sIn = s;
+      if (p.nuPost > 0) {  // s = r - A z, one application
+        if ((st = applyA(t_, z, n, active))) return st;
+        const Vecs rv = vecs(r, n), tv = vecs(t_, n);
+        if ((st = lv.axpby(vecs(s_, n), &rv, 1.0, &tv, -1.0, n, active))) return st;
+        sIn = s_;
       }
     }
-    for (int i = 0; i < prm.nuPost; i++) {
-      if ((st = mr_step(z, sIn, zZero, i == prm.nuPost - 1, n, active))) return st;
-      zZero = false;
-      sIn = s;
-    }
-    if (zZero) return fine.axpby(vecs(z, n), nullptr, 0.0, nullptr, 0.0, n, active);  // no step at all: K = 0
+    for (int i = 0; i < p.nuPost; i++)
+      if ((st = mr_step(i == p.nuPost - 1))) return st;
+    if (zZero) return lv.axpby(vecs(z, n), nullptr, 0.0, nullptr, 0.0, n, active);  // no step at all: the cycle is 0
     return MUGIQ_HIP_SUCCESS;
+  }
+
+  // z_i = K_1(r_i) on level 1: Cyc(M_1, R_1, P_1, GCRfix(M_2, ., params[1].coarseIters); params[1])
+  int precondition1(const MugiqHipCoarseField *z, const MugiqHipCoarseField *r, int n, unsigned active) const {
+    auto applyA = [this](const MugiqHipCoarseField *d, const MugiqHipCoarseField *sr, int m, unsigned act) { return apply_coarse(op, d, sr, m, act); };
+    auto correct = [this](const MugiqHipCoarseField *d, const MugiqHipCoarseField *sr, int m, unsigned act) {
+      MugiqHipCoarseField fa[kMgBlock], ca[kMgBlock];
+      const int na = gather(sr, m, act, fa);
+      gather(rc2, m, act, ca);
+      if (int e = mugiq_hip_restrict_coarse_batched(ca, fa, na, transfer1, stream)) return e;
+      if (int e = gcr_fixed(coarse2, coarse2Like, op2, prm1.coarseIters, xc2, rc2, m, act)) return e;
+      gather(xc2, m, act, ca);
+      gather(d, m, act, fa);
+      return mugiq_hip_prolongate_coarse_batched(fa, ca, na, transfer1, stream);
+    };
+    return cycle(coarse, prm1, applyA, correct, z, r, s1, t1, w1, n, active);
+  }
+
+  // z_i = K(r_i) (three levels: K^(3)) for the active i
+  int precondition(const MugiqHipSpinorField *z, const MugiqHipSpinorField *r, int n, unsigned active) const {
+    auto applyA = [this](const MugiqHipSpinorField *d, const MugiqHipSpinorField *sr, int m, unsigned act) { return apply_M(d, sr, m, act); };
+    auto correct = [this](const MugiqHipSpinorField *d, const MugiqHipSpinorField *sr, int m, unsigned act) {
+      MugiqHipSpinorField fa[kMgBlock];
+      MugiqHipCoarseField ca[kMgBlock];
+      const int na = gather(sr, m, act, fa);
+      gather(rc, m, act, ca);
+      if (int e = mugiq_hip_restrict_batched(ca, fa, na, transfer, 0, stream)) return e;
+      if (int e = coarse_solve(m, act)) return e;
+      gather(xc, m, act, ca);
+      gather(d, m, act, fa);
+      return mugiq_hip_prolongate_batched(fa, ca, na, transfer, stream);
+    };
+    return cycle(fine, prm, applyA, correct, z, r, s, t, w, n, active);
   }
 
   // res[4 i + ..] of the last final sum, on the host: the one blocking read
@@ -673,6 +774,49 @@ int check_problem(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in,
   return MUGIQ_HIP_SUCCESS;
 }
 
+// check_problem for a hierarchy of L = nCoarseLevels coarse levels: level 0 as above with params_h[0]; for L = 2 also T_1 = transfers_h[1]
+// (a coarse -> coarse transfer on the lattice and with the colours of M_1), M_2 = coarseOps_h[1] (on its coarse side) and params_h[1].
+// Everything before any device work; a NULL array is refused by check_problem, which sees its element 0
+int check_levels(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in, int nVec, const char *outName, const char *inName,
+                 const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover, const MugiqHipTransfer *transfers_h, const MugiqHipCoarseOperator *coarseOps_h,
+                 int nCoarseLevels, const MugiqHipMgSolveParam *params_h, double kappa, const MugiqHipComm *comm, const char *who, int fieldPrec = 8,
+                 int hierPrec = 8) {
+  if (nCoarseLevels < 1 || nCoarseLevels > 2)
+    return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "%s: nCoarseLevels = %d: a two-grid (1) or a three-level (2) cycle", who, nCoarseLevels);
+  int st;
+  if ((st = check_problem(out, in, nVec, outName, inName, gauge, clover, transfers_h, coarseOps_h, params_h, kappa, comm, who, fieldPrec, hierPrec))) return st;
+  if (nCoarseLevels == 1) return MUGIQ_HIP_SUCCESS;
+  const MugiqHipTransfer *T1 = &transfers_h[1];
+  const MugiqHipCoarseOperator *M1 = &coarseOps_h[0], *M2 = &coarseOps_h[1];
+  const MugiqHipMgSolveParam *p1 = &params_h[1];
+  if ((st = check_param(p1, who))) return st;
+  MUGIQ_REQUIRE(p1->nuPre + p1->nuPost + p1->coarseIters > 0, "%s: params[1] has nuPre = nuPost = coarseIters = 0: the level-1 cycle would be zero", who);
+  if ((st = validate_coarse_operator(M2, who))) return st;
+  MUGIQ_REQUIRE(T1->V != nullptr, "%s: transfer 1 / null vectors are NULL", who);
+  if (T1->precision != hierPrec || M2->precision != hierPrec)
+    return set_error(fieldPrec == 8 && hierPrec == 8 ? MUGIQ_HIP_ERROR_UNSUPPORTED : MUGIQ_HIP_ERROR_INVALID_ARGUMENT,
+                     "%s: one precision per hierarchy: transfer 0 has precision %d, transfer 1 %d and coarse operator 1 %d", who, hierPrec, T1->precision,
+                     M2->precision);
+  for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(T1->X[d] > 0 && T1->geoBlockSize[d] >= 1, "%s: transfer 1: X / geo_block_size[%d]", who, d);
+  MugiqHipCoarseField lev1 = coarse_side_layout(transfers_h[0]), lev2 = coarse_side_layout(*T1);
+  lev1.data = reinterpret_cast<void *>(uintptr_t(16));  // geometry only: the validator wants distinct non-NULL bodies and never reads them
+  lev2.data = reinterpret_cast<void *>(uintptr_t(32));
+  if ((st = validate_coarse_transfer(T1, &lev1, &lev2, 1, who))) return st;  // spin_block_size 1, on the lattice of M_1, even coarsest dims
+  MUGIQ_REQUIRE(T1->parity_offset == (int64_t)2 * M1->nVec * T1->nVec * T1->stride,
+                "%s: transfer 1 must have parity_offset = 2 nColor n_vec stride with the nColor = %d of coarse operator 0, not %lld", who, M1->nVec,
+                (long long)T1->parity_offset);
+  MUGIQ_REQUIRE(M2->nVec == T1->nVec, "%s: coarse operator 1 has n_vec %d, transfer 1 %d", who, M2->nVec, T1->nVec);
+  for (int d = 0; d < 4; d++)
+    MUGIQ_REQUIRE(M2->X[d] == lev2.X[d], "%s: coarse operator 1 X[%d] = %d, the coarse lattice of transfer 1 has %d", who, d, M2->X[d], lev2.X[d]);
+  MUGIQ_REQUIRE(M2->kappa == kappa, "%s: coarse operator 1 was built for kappa = %.17g, the call has kappa = %.17g", who, M2->kappa, kappa);
+  MUGIQ_REQUIRE((M2->hasClover != 0) == (clover != nullptr), "%s: coarse operator 1 was built %s a clover field, the call is %s one", who,
+                M2->hasClover ? "with" : "without", clover ? "with" : "without");
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(M1->data), a1 = a0 + mugiq_hip_coarse_operator_bytes(M1->X, M1->nVec, M1->precision);
+  const uintptr_t b0 = reinterpret_cast<uintptr_t>(M2->data), b1 = b0 + mugiq_hip_coarse_operator_bytes(M2->X, M2->nVec, M2->precision);
+  MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: coarse operator 1 overlaps coarse operator 0", who);
+  return MUGIQ_HIP_SUCCESS;
+}
+
 // The outer flexible GCR of mugiq_hip_mg_solve on the vectors of S (fp64).  K32 NULL: p = K(r) is S's own cycle; otherwise the cycle of
 // K32 in fp32 storage, between two conversions.  Everything else -- operator applications, directions, residual, tol, the history and the
 // true residual -- is the same code for both
@@ -753,6 +897,86 @@ int outer_solve(MgSolver<double> &S, const MgSolver<float> *K32, const MugiqHipS
   return MUGIQ_HIP_SUCCESS;
 }
 
+// the four entry points, for either number of levels; `who` names the caller in every message
+template <typename F>
+int precondition_levels(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover,
+                        double kappa, const MugiqHipTransfer *transfers_h, const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels,
+                        const MugiqHipMgSolveParam *params_h, const MugiqHipComm *comm, void *stream, const char *who) {
+  const int prec = (int)sizeof(F);
+  int st;
+  if ((st = check_levels(z_h, r_h, nVec, "z", "r", gauge, clover, transfers_h, coarseOps_h, nCoarseLevels, params_h, kappa, comm, who, prec, prec))) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((st = debug_poison_lds_if_asked(s))) return st;
+  MgSolver<F> S{gauge, clover, kappa, &transfers_h[0], &coarseOps_h[0], params_h[0], s};
+  if (nCoarseLevels == 2) S.set_coarsest(&transfers_h[1], &coarseOps_h[1], params_h[1]);
+  if ((st = S.reserve(r_h[0], 0, nVec, false))) return st;
+  for (int v0 = 0; v0 < nVec; v0 += kMgBlock) {
+    const int n = std::min(kMgBlock, nVec - v0);
+    if ((st = S.precondition(z_h + v0, r_h + v0, n, (1u << n) - 1u))) return st;
+  }
+  return MUGIQ_HIP_SUCCESS;
+}
+
+int solve_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover,
+                 double kappa, const MugiqHipTransfer *transfers_h, const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels,
+                 const MugiqHipMgSolveParam *params_h, int *iters_out, double *relres_out, double *history_out, int historyStride, int *hostReads_out,
+                 const MugiqHipComm *comm, void *stream, const char *who) {
+  MUGIQ_REQUIRE(iters_out != nullptr && relres_out != nullptr, "%s: NULL argument", who);
+  int st;
+  if ((st = check_levels(x_h, b_h, nVec, "x", "b", gauge, clover, transfers_h, coarseOps_h, nCoarseLevels, params_h, kappa, comm, who))) return st;
+  const MugiqHipMgSolveParam *param = &params_h[0];
+  MUGIQ_REQUIRE(history_out == nullptr || historyStride >= param->maxIter, "%s: historyStride = %d is smaller than maxIter = %d", who, historyStride,
+                param->maxIter);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((st = debug_poison_lds_if_asked(s))) return st;
+  MgSolver<double> S{gauge, clover, kappa, &transfers_h[0], &coarseOps_h[0], *param, s};
+  if (nCoarseLevels == 2) S.set_coarsest(&transfers_h[1], &coarseOps_h[1], params_h[1]);
+  if ((st = S.reserve(b_h[0], param->nKrylov, nVec, true))) return st;
+  return outer_solve(S, nullptr, x_h, b_h, nVec, param, iters_out, relres_out, history_out, historyStride, hostReads_out, who);
+}
+
+int solve_mixed_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                       const MugiqHipCloverField *clover, double kappa, const MugiqHipGaugeField *gaugeSloppy, const MugiqHipCloverField *cloverSloppy,
+                       const MugiqHipTransfer *transfersSloppy_h, const MugiqHipCoarseOperator *coarseOpsSloppy_h, int nCoarseLevels,
+                       const MugiqHipMgSolveParam *params_h, int *iters_out, double *relres_out, double *history_out, int historyStride, int *hostReads_out,
+                       const MugiqHipComm *comm, void *stream, const char *who) {
+  MUGIQ_REQUIRE(iters_out != nullptr && relres_out != nullptr, "%s: NULL argument", who);
+  int st;
+  if ((st = check_levels(x_h, b_h, nVec, "x", "b", gauge, clover, transfersSloppy_h, coarseOpsSloppy_h, nCoarseLevels, params_h, kappa, comm, who, 8, 4)))
+    return st;
+  const MugiqHipMgSolveParam *param = &params_h[0];
+  MUGIQ_REQUIRE(history_out == nullptr || historyStride >= param->maxIter, "%s: historyStride = %d is smaller than maxIter = %d", who, historyStride,
+                param->maxIter);
+  // the cycle's own fields: both or neither where the operator has a clover term; without one only gaugeSloppy can be given
+  MUGIQ_REQUIRE(!(cloverSloppy != nullptr && gaugeSloppy == nullptr), "%s: cloverSloppy without gaugeSloppy (give both, or neither to use gauge and clover)", who);
+  MUGIQ_REQUIRE(!(gaugeSloppy != nullptr && (cloverSloppy != nullptr) != (clover != nullptr)),
+                "%s: gaugeSloppy %s cloverSloppy, but the call is %s a clover field (give both, or neither to use gauge and clover)", who,
+                cloverSloppy ? "with" : "without", clover ? "with" : "without");
+  if (gaugeSloppy) {
+    const int part[4] = {0, 0, 0, 0};
+    if ((st = check_gauge(gaugeSloppy, b_h[0].X, part, who))) return st;
+    if (cloverSloppy) {
+      if ((st = validate_clover(cloverSloppy, b_h[0].X, b_h[0].volumeCB, who))) return st;
+      MUGIQ_REQUIRE(cloverSloppy->precision == gaugeSloppy->precision, "%s: cloverSloppy precision %d differs from the gaugeSloppy precision %d", who,
+                    cloverSloppy->precision, gaugeSloppy->precision);
+    }
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((st = debug_poison_lds_if_asked(s))) return st;
+  // the outer iteration: 2 nKrylov directions, r and t (for the true residual) in fp64; the cycle: r and z rounded, s, t, w and the coarse
+  // levels in fp32.  One reservation, the scalars shared: the stream orders every pass
+  MgSolver<double> S{gauge, clover, kappa, &transfersSloppy_h[0], &coarseOpsSloppy_h[0], *param, s};
+  MgSolver<float> K{gaugeSloppy ? gaugeSloppy : gauge, gaugeSloppy ? cloverSloppy : clover, kappa, &transfersSloppy_h[0], &coarseOpsSloppy_h[0], *param, s};
+  if (nCoarseLevels == 2) K.set_coarsest(&transfersSloppy_h[1], &coarseOpsSloppy_h[1], params_h[1]);
+  S.init(b_h[0], param->nKrylov, nVec, kMgSetT | kMgSetR, false);
+  K.init(b_h[0], 0, nVec, kMgSetsOfK | kMgSetR | kMgSetZ, true);
+  void *ws = nullptr;
+  if ((st = stream_operator_workspace(&ws, MgSolver<double>::kStencilHead + scalar_bytes() + S.vector_bytes() + K.vector_bytes() + 256, s))) return st;
+  unsigned char *scalars = static_cast<unsigned char *>(ws) + MgSolver<double>::kStencilHead;
+  K.carve(scalars, S.carve(scalars, scalars + scalar_bytes()));
+  return outer_solve(S, &K, x_h, b_h, nVec, param, iters_out, relres_out, history_out, historyStride, hostReads_out, who);
+}
+
 }  // namespace
 }  // namespace mugiq
 
@@ -775,53 +999,21 @@ int mugiq_hip_mg_solve_param_default(MugiqHipMgSolveParam *param) {
 int mugiq_hip_mg_precondition(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
                               const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *coarseOp,
                               const MugiqHipMgSolveParam *param, const MugiqHipComm *comm, void *stream) {
-  const char *who = "mgPrecondition";
-  int st;
-  if ((st = check_problem(z_h, r_h, nVec, "z", "r", gauge, clover, transfer, coarseOp, param, kappa, comm, who))) return st;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if ((st = debug_poison_lds_if_asked(s))) return st;
-  MgSolver<double> S{gauge, clover, kappa, transfer, coarseOp, *param, s};
-  if ((st = S.reserve(r_h[0], 0, nVec, false))) return st;
-  for (int v0 = 0; v0 < nVec; v0 += kMgBlock) {
-    const int n = std::min(kMgBlock, nVec - v0);
-    if ((st = S.precondition(z_h + v0, r_h + v0, n, (1u << n) - 1u))) return st;
-  }
-  return MUGIQ_HIP_SUCCESS;
+  return precondition_levels<double>(z_h, r_h, nVec, gauge, clover, kappa, transfer, coarseOp, 1, param, comm, stream, "mgPrecondition");
 }
 
 int mugiq_hip_mg_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
                        const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *coarseOp,
                        const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out, double *history_out, int historyStride, int *hostReads_out,
                        const MugiqHipComm *comm, void *stream) {
-  const char *who = "mgSolve";
-  MUGIQ_REQUIRE(iters_out != nullptr && relres_out != nullptr, "%s: NULL argument", who);
-  int st;
-  if ((st = check_problem(x_h, b_h, nVec, "x", "b", gauge, clover, transfer, coarseOp, param, kappa, comm, who))) return st;
-  MUGIQ_REQUIRE(history_out == nullptr || historyStride >= param->maxIter, "%s: historyStride = %d is smaller than maxIter = %d", who, historyStride,
-                param->maxIter);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if ((st = debug_poison_lds_if_asked(s))) return st;
-  MgSolver<double> S{gauge, clover, kappa, transfer, coarseOp, *param, s};
-  const int nK = param->nKrylov;
-  if ((st = S.reserve(b_h[0], nK, nVec, true))) return st;
-  return outer_solve(S, nullptr, x_h, b_h, nVec, param, iters_out, relres_out, history_out, historyStride, hostReads_out, who);
+  return solve_levels(x_h, b_h, nVec, gauge, clover, kappa, transfer, coarseOp, 1, param, iters_out, relres_out, history_out, historyStride, hostReads_out, comm,
+                      stream, "mgSolve");
 }
 
 int mugiq_hip_mg_precondition_sloppy(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
                                      const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer,
                                      const MugiqHipCoarseOperator *coarseOp, const MugiqHipMgSolveParam *param, const MugiqHipComm *comm, void *stream) {
-  const char *who = "mgPreconditionSloppy";
-  int st;
-  if ((st = check_problem(z_h, r_h, nVec, "z", "r", gauge, clover, transfer, coarseOp, param, kappa, comm, who, 4, 4))) return st;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if ((st = debug_poison_lds_if_asked(s))) return st;
-  MgSolver<float> S{gauge, clover, kappa, transfer, coarseOp, *param, s};
-  if ((st = S.reserve(r_h[0], 0, nVec, false))) return st;
-  for (int v0 = 0; v0 < nVec; v0 += kMgBlock) {
-    const int n = std::min(kMgBlock, nVec - v0);
-    if ((st = S.precondition(z_h + v0, r_h + v0, n, (1u << n) - 1u))) return st;
-  }
-  return MUGIQ_HIP_SUCCESS;
+  return precondition_levels<float>(z_h, r_h, nVec, gauge, clover, kappa, transfer, coarseOp, 1, param, comm, stream, "mgPreconditionSloppy");
 }
 
 int mugiq_hip_mg_solve_mixed(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
@@ -829,39 +1021,41 @@ int mugiq_hip_mg_solve_mixed(const MugiqHipSpinorField *x_h, const MugiqHipSpino
                              const MugiqHipCloverField *cloverSloppy, const MugiqHipTransfer *transferSloppy, const MugiqHipCoarseOperator *coarseOpSloppy,
                              const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out, double *history_out, int historyStride,
                              int *hostReads_out, const MugiqHipComm *comm, void *stream) {
-  const char *who = "mgSolveMixed";
-  MUGIQ_REQUIRE(iters_out != nullptr && relres_out != nullptr, "%s: NULL argument", who);
-  int st;
-  if ((st = check_problem(x_h, b_h, nVec, "x", "b", gauge, clover, transferSloppy, coarseOpSloppy, param, kappa, comm, who, 8, 4))) return st;
-  MUGIQ_REQUIRE(history_out == nullptr || historyStride >= param->maxIter, "%s: historyStride = %d is smaller than maxIter = %d", who, historyStride,
-                param->maxIter);
-  // the cycle's own fields: both or neither where the operator has a clover term; without one only gaugeSloppy can be given
-  MUGIQ_REQUIRE(!(cloverSloppy != nullptr && gaugeSloppy == nullptr), "%s: cloverSloppy without gaugeSloppy (give both, or neither to use gauge and clover)", who);
-  MUGIQ_REQUIRE(!(gaugeSloppy != nullptr && (cloverSloppy != nullptr) != (clover != nullptr)),
-                "%s: gaugeSloppy %s cloverSloppy, but the call is %s a clover field (give both, or neither to use gauge and clover)", who,
-                cloverSloppy ? "with" : "without", clover ? "with" : "without");
-  if (gaugeSloppy) {
-    const int part[4] = {0, 0, 0, 0};
-    if ((st = check_gauge(gaugeSloppy, b_h[0].X, part, who))) return st;
-    if (cloverSloppy) {
-      if ((st = validate_clover(cloverSloppy, b_h[0].X, b_h[0].volumeCB, who))) return st;
-      MUGIQ_REQUIRE(cloverSloppy->precision == gaugeSloppy->precision, "%s: cloverSloppy precision %d differs from the gaugeSloppy precision %d", who,
-                    cloverSloppy->precision, gaugeSloppy->precision);
-    }
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if ((st = debug_poison_lds_if_asked(s))) return st;
-  // the outer iteration: 2 nKrylov directions, r and t (for the true residual) in fp64; the cycle: r and z rounded, s, t, w and the coarse
-  // level in fp32.  One reservation, the scalars shared: the stream orders every pass
-  MgSolver<double> S{gauge, clover, kappa, transferSloppy, coarseOpSloppy, *param, s};
-  MgSolver<float> K{gaugeSloppy ? gaugeSloppy : gauge, gaugeSloppy ? cloverSloppy : clover, kappa, transferSloppy, coarseOpSloppy, *param, s};
-  S.init(b_h[0], param->nKrylov, nVec, kMgSetT | kMgSetR, false);
-  K.init(b_h[0], 0, nVec, kMgSetsOfK | kMgSetR | kMgSetZ, true);
-  void *ws = nullptr;
-  if ((st = stream_operator_workspace(&ws, MgSolver<double>::kStencilHead + scalar_bytes() + S.vector_bytes() + K.vector_bytes() + 256, s))) return st;
-  unsigned char *scalars = static_cast<unsigned char *>(ws) + MgSolver<double>::kStencilHead;
-  K.carve(scalars, S.carve(scalars, scalars + scalar_bytes()));
-  return outer_solve(S, &K, x_h, b_h, nVec, param, iters_out, relres_out, history_out, historyStride, hostReads_out, who);
+  return solve_mixed_levels(x_h, b_h, nVec, gauge, clover, kappa, gaugeSloppy, cloverSloppy, transferSloppy, coarseOpSloppy, 1, param, iters_out, relres_out,
+                            history_out, historyStride, hostReads_out, comm, stream, "mgSolveMixed");
+}
+
+int mugiq_hip_mg_precondition_levels(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
+                                     const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfers_h,
+                                     const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h,
+                                     const MugiqHipComm *comm, void *stream) {
+  return precondition_levels<double>(z_h, r_h, nVec, gauge, clover, kappa, transfers_h, coarseOps_h, nCoarseLevels, params_h, comm, stream,
+                                     "mgPrecondition(levels)");
+}
+
+int mugiq_hip_mg_solve_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                              const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfers_h, const MugiqHipCoarseOperator *coarseOps_h,
+                              int nCoarseLevels, const MugiqHipMgSolveParam *params_h, int *iters_out, double *relres_out, double *history_out,
+                              int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream) {
+  return solve_levels(x_h, b_h, nVec, gauge, clover, kappa, transfers_h, coarseOps_h, nCoarseLevels, params_h, iters_out, relres_out, history_out,
+                      historyStride, hostReads_out, comm, stream, "mgSolve(levels)");
+}
+
+int mugiq_hip_mg_precondition_sloppy_levels(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
+                                            const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfers_h,
+                                            const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h,
+                                            const MugiqHipComm *comm, void *stream) {
+  return precondition_levels<float>(z_h, r_h, nVec, gauge, clover, kappa, transfers_h, coarseOps_h, nCoarseLevels, params_h, comm, stream,
+                                    "mgPreconditionSloppy(levels)");
+}
+
+int mugiq_hip_mg_solve_mixed_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                                    const MugiqHipCloverField *clover, double kappa, const MugiqHipGaugeField *gaugeSloppy,
+                                    const MugiqHipCloverField *cloverSloppy, const MugiqHipTransfer *transfersSloppy_h,
+                                    const MugiqHipCoarseOperator *coarseOpsSloppy_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h, int *iters_out,
+                                    double *relres_out, double *history_out, int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream) {
+  return solve_mixed_levels(x_h, b_h, nVec, gauge, clover, kappa, gaugeSloppy, cloverSloppy, transfersSloppy_h, coarseOpsSloppy_h, nCoarseLevels, params_h,
+                            iters_out, relres_out, history_out, historyStride, hostReads_out, comm, stream, "mgSolveMixed(levels)");
 }
 
 /* dst_i = src_i between two precisions: fields of one geometry and field order, each set with its own stride and parity offset */

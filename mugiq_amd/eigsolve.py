@@ -221,25 +221,58 @@ def mgSolveParam(**param):
     return p
 
 
-def mgPrecondition(z, r, gauge, kappa, transfer, coarseOp, clover=None, comm=None, **param):
+def _mg_levels(who, transfer, coarseOp, coarseParam, param):
+    """The hierarchy arguments of the MG calls.  A single Transfer and CoarseOperator: None (the two-grid entry points).  Lists
+    [T0, T1] and [op1, op2] (or of one each): (transfer descs, operator descs, nCoarseLevels, params) for the *_levels entry points, with
+    params[0] from `param` and params[1] the struct defaults with the members of coarseParam replaced."""
+    lists = isinstance(transfer, (list, tuple)), isinstance(coarseOp, (list, tuple))
+    if not any(lists):
+        if coarseParam is not None:
+            raise _lib.MugiqHipError("%s: coarseParam belongs to a three-level hierarchy (transfer=[T0, T1], coarseOp=[op1, op2])" % who)
+        return None
+    if not all(lists) or len(transfer) != len(coarseOp) or not transfer:
+        raise _lib.MugiqHipError("%s: transfer and coarseOp must be lists of the same length (one per coarse level)" % who)
+    L = len(transfer)
+    if coarseParam is not None and L < 2:
+        raise _lib.MugiqHipError("%s: coarseParam without a second coarse level" % who)
+    t = transfer_desc_array(list(transfer))
+    o = (_lib.CoarseOperatorDesc * L)(*[c.desc() for c in coarseOp])
+    params = (_lib.MgSolveParam * L)()
+    params[0] = mgSolveParam(**param)
+    for l in range(1, L):
+        params[l] = mgSolveParam(**dict(coarseParam or {}))
+    return t, o, L, params
+
+
+def mgPrecondition(z, r, gauge, kappa, transfer, coarseOp, clover=None, comm=None, coarseParam=None, **param):
     """z_i = K(r_i): one two-grid cycle (MR smoothing, coarse-grid correction by GCR on the explicit coarse operator) for lists of fp64
-    SpinorFields (mugiq_hip_mg_precondition).  param: members of MugiqHipMgSolveParam (nuPre, nuPost, omega, coarseIters)."""
+    SpinorFields (mugiq_hip_mg_precondition).  param: members of MugiqHipMgSolveParam (nuPre, nuPost, omega, coarseIters).
+    transfer=[T0, T1], coarseOp=[op1, op2]: the three-level cycle K^(3) (mugiq_hip_mg_precondition_levels), whose level-1 solve is a GCR
+    preconditioned by a cycle through op2; coarseParam: dict of the level-1 members (nuPre, nuPost, omega, coarseIters), default: the
+    struct defaults, which are not tuned."""
     z, r = list(z), list(r)
     if len(z) != len(r) or not r:
         raise _lib.MugiqHipError("mgPrecondition: %d z and %d r vectors (need the same number, at least one)" % (len(z), len(r)))
     keep = []
+    lev = _mg_levels("mgPrecondition", transfer, coarseOp, coarseParam, param)
+    if lev is not None:
+        g = gauge.desc()
+        _lib.check(_lib.load().mugiq_hip_mg_precondition_levels(desc_array(z), desc_array(r), len(r), ctypes.byref(g), _clover_ptr(clover, keep),
+                                                                float(kappa), lev[0], lev[1], lev[2], lev[3], _comm_ptr(comm, keep), _stream()))
+        return
     p, g, t, o = mgSolveParam(**param), gauge.desc(), transfer.desc(), coarseOp.desc()
     _lib.check(_lib.load().mugiq_hip_mg_precondition(desc_array(z), desc_array(r), len(r), ctypes.byref(g), _clover_ptr(clover, keep), float(kappa),
                                                      ctypes.byref(t), ctypes.byref(o), ctypes.byref(p), _comm_ptr(comm, keep), _stream()))
 
 
-def mgSolve(b, gauge, kappa, transfer, coarseOp, clover=None, x=None, allow_unconverged=False, comm=None, **param):
+def mgSolve(b, gauge, kappa, transfer, coarseOp, clover=None, x=None, allow_unconverged=False, comm=None, coarseParam=None, **param):
     """x_r = M^-1 b_r by flexible GCR preconditioned with the two-grid cycle of mgPrecondition (mugiq_hip_mg_solve); transfer: the
     finest-level Transfer, coarseOp: the CoarseOperator computeCoarseOperator built from it for this gauge, clover and kappa.  param:
     members of MugiqHipMgSolveParam (tol, maxIter, nKrylov, nuPre, nuPost, omega, coarseIters).  Returns (x, MgSolveInfo(iters, relres,
     converged, history, hostReads)): history[r] the recursive relative residuals of right-hand side r, one per iteration; hostReads the
     blocking reads the call made.  x: new fp64 fields laid out like b unless given.  A right-hand side that does not reach tol within
-    maxIter raises MugiqHipError (status 5) unless allow_unconverged."""
+    maxIter raises MugiqHipError (status 5) unless allow_unconverged.  transfer=[T0, T1], coarseOp=[op1, op2] and coarseParam: the
+    three-level cycle, as for mgPrecondition (mugiq_hip_mg_solve_levels)."""
     b = list(b)
     if not b:
         raise _lib.MugiqHipError("mgSolve: no right-hand side")
@@ -250,15 +283,22 @@ def mgSolve(b, gauge, kappa, transfer, coarseOp, clover=None, x=None, allow_unco
     if len(x) != n:
         raise _lib.MugiqHipError("mgSolve: %d x and %d b vectors" % (len(x), n))
     keep = []
-    p, g, t, o = mgSolveParam(**param), gauge.desc(), transfer.desc(), coarseOp.desc()
+    lev = _mg_levels("mgSolve", transfer, coarseOp, coarseParam, param)
+    p, g = mgSolveParam(**param), gauge.desc()
     stride = max(int(p.maxIter), 1)
     iters = (ctypes.c_int * n)()
     relres = (ctypes.c_double * n)()
     hist = (ctypes.c_double * (n * stride))()
     reads = ctypes.c_int(0)
-    st = _lib.load().mugiq_hip_mg_solve(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), ctypes.byref(t),
-                                        ctypes.byref(o), ctypes.byref(p), iters, relres, hist, stride, ctypes.byref(reads), _comm_ptr(comm, keep),
-                                        _stream())
+    if lev is not None:
+        st = _lib.load().mugiq_hip_mg_solve_levels(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), lev[0],
+                                                   lev[1], lev[2], lev[3], iters, relres, hist, stride, ctypes.byref(reads), _comm_ptr(comm, keep),
+                                                   _stream())
+    else:
+        t, o = transfer.desc(), coarseOp.desc()
+        st = _lib.load().mugiq_hip_mg_solve(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), ctypes.byref(t),
+                                            ctypes.byref(o), ctypes.byref(p), iters, relres, hist, stride, ctypes.byref(reads), _comm_ptr(comm, keep),
+                                            _stream())
     if st != 0 and not (st == STATUS_NOT_CONVERGED and allow_unconverged):
         _lib.check(st)
     it = np.array(iters)
@@ -275,24 +315,32 @@ def mgConvertPrecision(dst, src):
     _lib.check(_lib.load().mugiq_hip_mg_convert_precision(desc_array(dst), desc_array(src), len(src), _stream()))
 
 
-def mgPreconditionSloppy(z, r, gauge, kappa, transfer, coarseOp, clover=None, comm=None, **param):
+def mgPreconditionSloppy(z, r, gauge, kappa, transfer, coarseOp, clover=None, comm=None, coarseParam=None, **param):
     """z_i = K(r_i) with every vector of the cycle in fp32 storage (mugiq_hip_mg_precondition_sloppy): z, r, transfer and coarseOp all of
-    precision 4, gauge (and clover) of either.  Sums are fp64 and in a fixed order, as in mgPrecondition.  param: as for mgPrecondition."""
+    precision 4, gauge (and clover) of either.  Sums are fp64 and in a fixed order, as in mgPrecondition.  param, and the lists and
+    coarseParam of a three-level hierarchy (mugiq_hip_mg_precondition_sloppy_levels): as for mgPrecondition."""
     z, r = list(z), list(r)
     if len(z) != len(r) or not r:
         raise _lib.MugiqHipError("mgPreconditionSloppy: %d z and %d r vectors (need the same number, at least one)" % (len(z), len(r)))
     keep = []
+    lev = _mg_levels("mgPreconditionSloppy", transfer, coarseOp, coarseParam, param)
+    if lev is not None:
+        g = gauge.desc()
+        _lib.check(_lib.load().mugiq_hip_mg_precondition_sloppy_levels(desc_array(z), desc_array(r), len(r), ctypes.byref(g), _clover_ptr(clover, keep),
+                                                                       float(kappa), lev[0], lev[1], lev[2], lev[3], _comm_ptr(comm, keep), _stream()))
+        return
     p, g, t, o = mgSolveParam(**param), gauge.desc(), transfer.desc(), coarseOp.desc()
     _lib.check(_lib.load().mugiq_hip_mg_precondition_sloppy(desc_array(z), desc_array(r), len(r), ctypes.byref(g), _clover_ptr(clover, keep), float(kappa),
                                                             ctypes.byref(t), ctypes.byref(o), ctypes.byref(p), _comm_ptr(comm, keep), _stream()))
 
 
 def mgSolveMixed(b, gauge, kappa, transferSloppy, coarseOpSloppy, clover=None, gaugeSloppy=None, cloverSloppy=None, x=None, allow_unconverged=False,
-                 comm=None, **param):
+                 comm=None, coarseParam=None, **param):
     """x_r = M^-1 b_r by the fp64 flexible GCR of mgSolve with the two-grid cycle in fp32 storage (mugiq_hip_mg_solve_mixed).  b, x, gauge and
     clover as for mgSolve; transferSloppy: the Transfer in precision 4 (Transfer.astype(4)), coarseOpSloppy: the CoarseOperator
     computeCoarseOperator built from it; gaugeSloppy / cloverSloppy: the fields the cycle's stencil reads (e.g. fp32 copies), both None:
-    gauge and clover.  Returns (x, MgSolveInfo) as mgSolve does; relres is the true fp64 residual."""
+    gauge and clover.  Returns (x, MgSolveInfo) as mgSolve does; relres is the true fp64 residual.  transferSloppy=[T0_32, T1_32],
+    coarseOpSloppy=[op1_32, op2_32] and coarseParam: the three-level cycle in fp32 storage (mugiq_hip_mg_solve_mixed_levels)."""
     b = list(b)
     if not b:
         raise _lib.MugiqHipError("mgSolveMixed: no right-hand side")
@@ -303,7 +351,8 @@ def mgSolveMixed(b, gauge, kappa, transferSloppy, coarseOpSloppy, clover=None, g
     if len(x) != n:
         raise _lib.MugiqHipError("mgSolveMixed: %d x and %d b vectors" % (len(x), n))
     keep = []
-    p, g, t, o = mgSolveParam(**param), gauge.desc(), transferSloppy.desc(), coarseOpSloppy.desc()
+    lev = _mg_levels("mgSolveMixed", transferSloppy, coarseOpSloppy, coarseParam, param)
+    p, g = mgSolveParam(**param), gauge.desc()
     gs = None
     if gaugeSloppy is not None:
         gd = gaugeSloppy.desc()
@@ -314,9 +363,15 @@ def mgSolveMixed(b, gauge, kappa, transferSloppy, coarseOpSloppy, clover=None, g
     relres = (ctypes.c_double * n)()
     hist = (ctypes.c_double * (n * stride))()
     reads = ctypes.c_int(0)
-    st = _lib.load().mugiq_hip_mg_solve_mixed(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), gs,
-                                              _clover_ptr(cloverSloppy, keep), ctypes.byref(t), ctypes.byref(o), ctypes.byref(p), iters, relres, hist,
-                                              stride, ctypes.byref(reads), _comm_ptr(comm, keep), _stream())
+    if lev is not None:
+        st = _lib.load().mugiq_hip_mg_solve_mixed_levels(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), gs,
+                                                         _clover_ptr(cloverSloppy, keep), lev[0], lev[1], lev[2], lev[3], iters, relres, hist, stride,
+                                                         ctypes.byref(reads), _comm_ptr(comm, keep), _stream())
+    else:
+        t, o = transferSloppy.desc(), coarseOpSloppy.desc()
+        st = _lib.load().mugiq_hip_mg_solve_mixed(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), gs,
+                                                  _clover_ptr(cloverSloppy, keep), ctypes.byref(t), ctypes.byref(o), ctypes.byref(p), iters, relres, hist,
+                                                  stride, ctypes.byref(reads), _comm_ptr(comm, keep), _stream())
     if st != 0 and not (st == STATUS_NOT_CONVERGED and allow_unconverged):
         _lib.check(st)
     it = np.array(iters)
@@ -639,19 +694,23 @@ class Eigsolve_Mugiq:
             ev = self.eVecs
         return wilsonSolve(b, self.gauge, self.kappa, ev, sg, tol, maxIter, self.comm, x, allow_unconverged, self.clover)
 
-    def solveMG(self, b, x=None, allow_unconverged=False, sloppy=None, **param):
+    def solveMG(self, b, x=None, allow_unconverged=False, sloppy=None, coarseOp=None, coarseParam=None, **param):
         """M^-1 b by the two-grid preconditioned GCR (mgSolve) for objects built with transfer= and coarseOp=: their gauge field, clover
         field, kappa, transfer and coarse operator.  sloppy=(T32, op32): the mixed solve (mgSolveMixed) with that fp32 hierarchy, on this
-        object's gauge and clover fields.  Returns (x, MgSolveInfo)."""
+        object's gauge and clover fields.  An object built with transfer=[T0, T1] holds only the coarsest operator, so the three-level
+        solve takes coarseOp=[op1, op2] here (and coarseParam, the level-1 cycle); its sloppy= is ([T0_32, T1_32], [op1_32, op2_32]).
+        Returns (x, MgSolveInfo)."""
         if sloppy is not None:
             T32, op32 = sloppy
-            return mgSolveMixed(b, self.gauge, self.kappa, T32, op32, self.clover, x=x, allow_unconverged=allow_unconverged, comm=self.comm, **param)
-        tr, op = self.transfer, self.coarseOp
+            return mgSolveMixed(b, self.gauge, self.kappa, T32, op32, self.clover, x=x, allow_unconverged=allow_unconverged, comm=self.comm,
+                                coarseParam=coarseParam, **param)
+        tr, op = self.transfer, self.coarseOp if coarseOp is None else coarseOp
         if tr is None and op is None and self.mgTransfer is not None:   # the hierarchy setupMG made
             tr, op = self.mgTransfer, self.mgCoarseOp
-        if tr is None or op is None or isinstance(tr, (list, tuple)):
-            raise _lib.MugiqHipError("status 2: Eigsolve_Mugiq.solveMG: needs an object built with one finest-level transfer= and its coarseOp=")
-        return mgSolve(b, self.gauge, self.kappa, tr, op, self.clover, x, allow_unconverged, self.comm, **param)
+        if tr is None or op is None or isinstance(tr, (list, tuple)) != isinstance(op, (list, tuple)):
+            raise _lib.MugiqHipError("status 2: Eigsolve_Mugiq.solveMG: needs an object built with one finest-level transfer= and its coarseOp=, or "
+                                     "with transfer=[T0, T1] and coarseOp=[op1, op2] in the call")
+        return mgSolve(b, self.gauge, self.kappa, tr, op, self.clover, x, allow_unconverged, self.comm, coarseParam=coarseParam, **param)
 
     def setupMG(self, n_vec=24, geo_block_size=(4, 4, 4, 4), start=None, seed=0, **param):
         """Make an MG hierarchy from this object's own gauge field, clover field and kappa (mgSetup) and keep it in self.mgTransfer and

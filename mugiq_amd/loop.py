@@ -422,33 +422,40 @@ class Loop_Mugiq:
                                                    comm=self.comm, **param)
         return self.lastSetup
 
-    def solveMG(self, b, kappa, coarseOp=None, clover=None, x=None, allow_unconverged=False, sloppy=None, **param):
+    def solveMG(self, b, kappa, coarseOp=None, clover=None, x=None, allow_unconverged=False, sloppy=None, coarseParam=None, **param):
         """x_r = M^-1 b_r by the two-grid preconditioned GCR (mgSolve) with this coarse loop object's gauge field, transfer and stream;
         coarseOp: the CoarseOperator of that transfer at this kappa (and clover).  Returns the list x; iteration counts, true residuals,
         histories and host reads are kept in self.lastSolve.  Status 2 (UNSUPPORTED) for fine-level and two-sided loop objects and for
-        hierarchies of more than one level, status 1 for a loop object created without a gauge field.  An MG set then reads
+        hierarchies of more than two coarse levels, status 1 for a loop object created without a gauge field.  An MG set then reads
         x = loop.solveMG(xi, kappa, coarseOp); loop.deflateCoarse(x, xi).  sloppy=(T32, op32): the mixed solve (mgSolveMixed) with that
-        fp32 hierarchy in place of this object's transfer and coarseOp; the checks of the object stay."""
+        fp32 hierarchy in place of this object's transfer and coarseOp; the checks of the object stay.  A loop object made with
+        transfer=[T0, T1] supplies both transfers and takes coarseOp=[op1, op2] (and coarseParam, the level-1 cycle): the three-level
+        solve; its sloppy= is ([T0_32, T1_32], [op1_32, op2_32])."""
         from .eigsolve import mgSolve, mgSolveMixed
         if self._transfer is None or self.eVecsLeft is not None:
             raise _lib.MugiqHipError("status 2: Loop_Mugiq.solveMG: coarse (MG) loop objects only")
         tr = self._transfer
         if isinstance(tr, (list, tuple)):
-            if len(tr) != 1:
-                raise _lib.MugiqHipError("status 2: Loop_Mugiq.solveMG: one coarse level only (the loop has %d transfers)" % len(tr))
-            tr = tr[0]
+            if len(tr) > 2:
+                raise _lib.MugiqHipError("status 2: Loop_Mugiq.solveMG: at most two coarse levels (the loop has %d transfers)" % len(tr))
+            if len(tr) == 1:
+                tr = tr[0]
+            elif sloppy is None and not (isinstance(coarseOp, (list, tuple)) and len(coarseOp) == 2):
+                raise _lib.MugiqHipError("status 1: Loop_Mugiq.solveMG: a loop of two coarse levels needs coarseOp=[op1, op2]")
+            else:
+                tr = list(tr)
         if self._params.gauge is None:
             raise _lib.MugiqHipError("status 1: Loop_Mugiq.solveMG: the loop object was created without a gauge field")
         if sloppy is not None:
             T32, op32 = sloppy
             x, self.lastSolve = mgSolveMixed(b, self._params.gauge, kappa, T32, op32, clover, x=x, allow_unconverged=allow_unconverged, comm=self.comm,
-                                             **param)
+                                             coarseParam=coarseParam, **param)
             return x
         if coarseOp is None:
             coarseOp = self.coarseOp
             if coarseOp is None:
                 raise _lib.MugiqHipError("status 1: Loop_Mugiq.solveMG: no coarse operator (pass one or call setupMG first)")
-        x, self.lastSolve = mgSolve(b, self._params.gauge, kappa, tr, coarseOp, clover, x, allow_unconverged, self.comm, **param)
+        x, self.lastSolve = mgSolve(b, self._params.gauge, kappa, tr, coarseOp, clover, x, allow_unconverged, self.comm, coarseParam=coarseParam, **param)
         return x
 
     def computeEvecs(self, kappa, nConv, nKr, coarseOp=None, opType=None, start=None, seed=0, allow_unconverged=False, **param):
