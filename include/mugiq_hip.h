@@ -767,6 +767,12 @@ int mugiq_hip_compute_coarse_operator(MugiqHipCoarseOperator *op, const MugiqHip
  * workspace. */
 int mugiq_hip_coarse_apply(const MugiqHipCoarseField *dst_h, const MugiqHipCoarseField *src_h, int nVec, const MugiqHipCoarseOperator *op,
                            int opType, double scale, const MugiqHipComm *comm, void *stream);
+/* The output components per workgroup -- 16, 32 or 64 -- one launch of the application's kernel takes for nVec vectors on this operator: the
+ * answer of the one rule every launch asks (32 where the 64-output grid, 2 volumeCB x ceil(nVec / 8) x ceil(2 n_vec / 64) workgroups, would
+ * have fewer than 512, else 64), under MUGIQ_HIP_COARSE_APPLY_OUT as the launches read it.  Host only: no device work, no launch; op->data
+ * is not read, so a described geometry will do.  The results do not depend on the form, bit for bit.  0 with the last error set for an
+ * operator mugiq_hip_coarse_apply would refuse or nVec < 1.  (A normal form applies in blocks of 8; the MG solvers pass at most 8.) */
+int mugiq_hip_coarse_apply_outputs(const MugiqHipCoarseOperator *op, int nVec);
 /* lambda, r and sigma of mugiq_hip_compute_evals_coarse (lib/eigsolve_mugiq.cpp:289-315) with A_c applied by mugiq_hip_coarse_apply:
  * massNormalization scales by 0.25 / op->kappa^2.  The same fixed-order fp64 scalar kernels; work memory: 8 coarse vectors and the
  * scalars in the operator workspace of the stream.  Blocks the host (two reads per block of 8). */

@@ -196,6 +196,12 @@ inline void coarseApply(const std::vector<MugiqHipCoarseField> &dst, const std::
   if (src.empty() || dst.size() != src.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "coarseApply: size mismatch");
   check(mugiq_hip_coarse_apply(dst.data(), src.data(), (int)src.size(), op.desc(), opType, scale, comm, stream));
 }
+// 16, 32 or 64: the output components per workgroup coarseApply takes for nVec vectors on this operator (mugiq_hip_coarse_apply_outputs; host only)
+inline int coarseApplyForm(const MugiqHipCoarseOperator &op, int nVec) {
+  const int out = mugiq_hip_coarse_apply_outputs(&op, nVec);
+  if (out == 0) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, mugiq_hip_last_error());
+  return out;
+}
 // computeEvalsCoarse on the explicit operator (mugiq_hip_compute_evals_coarse_operator): no pass over the fine lattice
 inline void computeEvalsCoarse(const std::vector<MugiqHipCoarseField> &coarseEvecs, const CoarseOperator &coarseOp, int opType, bool massNormalization,
                                std::vector<std::complex<double>> &lambda, std::vector<double> &residual, std::vector<double> &sigma,

@@ -29,7 +29,7 @@ from .loop import (  # noqa: E402
 from .comm import GridComm, RcclComm  # noqa: E402
 from .displace import Displace, DISPLACE_TYPE_COVARIANT  # noqa: E402
 from .eigsolve import (  # noqa: E402
-    Eigsolve_Mugiq, wilsonApply, computeEvals, computeEvalsCoarse, computeCoarseOperator, computeCoarseOperatorCoarse, coarseApply, projectVector, wilsonSolve, SolveInfo,
+    Eigsolve_Mugiq, wilsonApply, computeEvals, computeEvalsCoarse, computeCoarseOperator, computeCoarseOperatorCoarse, coarseApply, coarseApplyForm, projectVector, wilsonSolve, SolveInfo,
     mgSolve, mgPrecondition, mgSolveMixed, mgPreconditionSloppy, mgConvertPrecision, mgSolveParam, MgSolveInfo, mgSetup, mgSetupCoarse, MgSetupCoarseInfo, mgSetupParam, mgStartVectors, MgSetupInfo,
     coarseGram, coarseRotate, hermitianEigh, choleskyUpper, upperTriangularInverse, coarseEigensolve, coarseEigParam, coarseStartVectors, CoarseEigInfo,
     MUGIQ_EIG_OPERATOR_M, MUGIQ_EIG_OPERATOR_Mdag, MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H,

@@ -251,6 +251,7 @@ SIGNATURES = {
                                                          _VP, _VP]),
     "mugiq_hip_coarse_apply": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(CoarseOperatorDesc),
                                               ctypes.c_int, ctypes.c_double, _VP, _VP]),
+    "mugiq_hip_coarse_apply_outputs": (ctypes.c_int, [ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int]),
     "mugiq_hip_compute_evals_coarse_operator": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int,
                                                                ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                                ctypes.POINTER(ctypes.c_double), _VP, _VP]),

@@ -334,18 +334,23 @@ template <typename F, int DAG, int OUT> __global__ __launch_bounds__(kCaThreads)
   }
 }
 
-// The outputs per workgroup of coarse_apply_kernel, decided here and nowhere else, on the host: from the workgroups the 64-output grid
-// would have.  With one workgroup per coarse site (256 at 4^4 with N = 64, one per compute unit) the 64-output form leaves the device short
-// of waves; the 32-output form, twice as many workgroups that each read the same inputs and half of the matrix rows, took 0.69 x its time
-// there and 1.18 x at 512 workgroups (the 16-output form: 0.83 x and 1.26 x).  MUGIQ_HIP_COARSE_APPLY_OUT = 16 | 32 | 64
-// overrides the rule (anything else is ignored); the bits do not depend on it
+// The outputs per workgroup of coarse_apply_kernel for one launch on n vectors, decided here and nowhere else, on the host: from the
+// workgroups the 64-output grid would have, 2 volumeCB sites x ceil(n / 8) blocks of vectors x ceil(N / 64) chunks.  With one workgroup per
+// coarse site (256 at 4^4 with N = 64, one per compute unit) the 64-output form leaves the device short of waves; the 32-output form, twice
+// as many workgroups that each read the same inputs and half of the matrix rows, took 0.69 x its time there and 1.18 x at 512 workgroups
+// (the 16-output form: 0.83 x and 1.26 x).  MUGIQ_HIP_COARSE_APPLY_OUT = 16 | 32 | 64 overrides the rule (anything else is
+// ignored); the bits do not depend on it.  launch_apply and the host query mugiq_hip_coarse_apply_outputs both ask here
 constexpr int64_t kCaSmallGrid = 512;
-int apply_outputs_per_workgroup(int64_t workgroups64) {
+dim3 apply_grid64(const MugiqHipCoarseOperator *op, int n) {
+  return dim3(2 * op->volumeCB, (n + kCaRB - 1) / kCaRB, (2 * op->nVec + kCaOut - 1) / kCaOut);
+}
+int apply_outputs_per_workgroup(const MugiqHipCoarseOperator *op, int n) {
   if (const char *e = getenv("MUGIQ_HIP_COARSE_APPLY_OUT")) {
     const int o = atoi(e);
     if (o == 16 || o == 32 || o == 64) return o;
   }
-  return workgroups64 < kCaSmallGrid ? 32 : kCaOut;
+  const dim3 g = apply_grid64(op, n);
+  return (int64_t)g.x * g.y * g.z < kCaSmallGrid ? 32 : kCaOut;
 }
 
 template <typename F, int DAG>
@@ -380,8 +385,8 @@ int launch_apply(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src,
   a.gamma5 = gamma5 ? 1 : 0;
   a.scale = scale;
   const int N = 2 * op->nVec;
-  const dim3 grid(2 * op->volumeCB, (n + kCaRB - 1) / kCaRB, (N + kCaOut - 1) / kCaOut);
-  const int out = apply_outputs_per_workgroup((int64_t)grid.x * grid.y * grid.z);
+  const dim3 grid = apply_grid64(op, n);
+  const int out = apply_outputs_per_workgroup(op, n);
   const size_t lds = sizeof(Cplx<double>) * (size_t)kCaRB * N;
   if (op->precision == 8 && !dagger) launch_apply_form<double, 0>(out, grid, lds, stream, a, N);
   else if (op->precision == 8) launch_apply_form<double, 1>(out, grid, lds, stream, a, N);
@@ -569,6 +574,16 @@ int mugiq_hip_coarse_apply(const MugiqHipCoarseField *dst_h, const MugiqHipCoars
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
   return coarse_apply(dst_h, src_h, nVec, op, opType, scale, s);
+}
+
+int mugiq_hip_coarse_apply_outputs(const MugiqHipCoarseOperator *op, int nVec) {
+  const char *who = "coarseApplyOutputs";
+  if (validate_coarse_operator(op, who)) return 0;
+  if (nVec < 1) {
+    set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "%s: nVec = %d must be at least 1", who, nVec);
+    return 0;
+  }
+  return apply_outputs_per_workgroup(op, nVec);
 }
 
 }  // extern "C"

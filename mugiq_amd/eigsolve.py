@@ -134,6 +134,24 @@ def coarseApply(dst, src, op, opType=MUGIQ_EIG_OPERATOR_M, scale=1.0, comm=None)
                                                   _comm_ptr(comm, keep), _stream()))
 
 
+def coarseApplyForm(op, nVec):
+    """16, 32 or 64: the output components per workgroup one launch of coarseApply's kernel takes for nVec vectors on this operator
+    (mugiq_hip_coarse_apply_outputs) -- what every launch selects, under the same MUGIQ_HIP_COARSE_APPLY_OUT.  Host only, no GPU is touched,
+    so a description will do: op a CoarseOperator or (X, n_vec[, precision]).  The MG solvers apply at most 8 vectors at a time."""
+    if isinstance(op, CoarseOperator):
+        d = op.desc()
+    else:
+        X, n_vec = op[:2]
+        d = _lib.CoarseOperatorDesc()
+        d.data, d.precision, d.nVec, d.volumeCB = 16, int(op[2]) if len(op) > 2 else 8, int(n_vec), int(np.prod(X)) // 2
+        for i in range(4):
+            d.X[i] = int(X[i])
+    out = _lib.load().mugiq_hip_coarse_apply_outputs(ctypes.byref(d), int(nVec))
+    if out == 0:
+        _lib.check(1)
+    return out
+
+
 def computeEvalsCoarse(coarseEvecs, transfer=None, gauge=None, kappa=None, opType=MUGIQ_EIG_OPERATOR_MdagM, massNormalization=False, comm=None,
                        clover=None, coarseOp=None):
     """computeEvals for eigenvectors on the coarsest level of an MG hierarchy (mugiq_hip_compute_evals_coarse): the operator is the Galerkin
