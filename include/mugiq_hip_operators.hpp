@@ -225,6 +225,32 @@ inline void projectVector(ColorSpinorField &out, ColorSpinorField &in, const std
 struct MgSolveParam : MugiqHipMgSolveParam {
   MgSolveParam() { check(mugiq_hip_mg_solve_param_default(this)); }
 };
+namespace detail {
+static_assert(sizeof(MgSolveParam) == sizeof(MugiqHipMgSolveParam), "std::vector<MgSolveParam> is handed over as an array of the C struct");
+inline int mgLevels(const std::vector<MugiqHipTransfer> &transfers, const std::vector<MugiqHipCoarseOperator> &coarseOps, const std::vector<MgSolveParam> &params,
+                    const char *who) {
+  if (transfers.empty() || transfers.size() != coarseOps.size() || transfers.size() != params.size())
+    throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, std::string(who) + ": one transfer, coarse operator and MgSolveParam per coarse level");
+  return (int)transfers.size();
+}
+// the outputs of a solve before the call: iters and relres sized for n right-hand sides, *stride = max(maxIter, 1); returns the history
+// buffer of n * stride entries (empty where no history is asked for)
+inline std::vector<double> mgOutputs(size_t n, int maxIter, bool wantHistory, std::vector<int> &iters, std::vector<double> &relres, int *stride) {
+  iters.assign(n, 0);
+  relres.assign(n, 0.0);
+  *stride = maxIter > 0 ? maxIter : 1;
+  return std::vector<double>(wantHistory ? n * (size_t)*stride : 0);
+}
+// and after it: NOT_CONVERGED is the return value false, every other failure throws; history[r] = the iters[r] entries of right-hand side r
+inline bool mgHistory(int st, const std::vector<double> &hist, int stride, const std::vector<int> &iters, std::vector<std::vector<double>> *history) {
+  if (st != MUGIQ_HIP_ERROR_NOT_CONVERGED) check(st);
+  if (history) {
+    history->clear();
+    for (size_t i = 0; i < iters.size(); i++) history->emplace_back(hist.begin() + i * stride, hist.begin() + i * stride + iters[i]);
+  }
+  return st == 0;
+}
+}  // namespace detail
 // z_i = K(r_i): one two-grid cycle (mugiq_hip_mg_precondition); clover NULL: the unimproved operator
 inline void mgPrecondition(const std::vector<ColorSpinorField> &z, const std::vector<ColorSpinorField> &r, const GaugeField &gauge,
                            const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer &transfer, const CoarseOperator &coarseOp,
@@ -240,18 +266,11 @@ inline bool mgSolve(const std::vector<ColorSpinorField> &x, const std::vector<Co
                     const MgSolveParam &param, std::vector<int> &iters, std::vector<double> &relres, std::vector<std::vector<double>> *history = nullptr,
                     int *hostReads = nullptr, const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
   if (b.empty() || x.size() != b.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgSolve: size mismatch");
-  iters.assign(b.size(), 0);
-  relres.assign(b.size(), 0.0);
-  const int stride = param.maxIter > 0 ? param.maxIter : 1;
-  std::vector<double> hist(history ? b.size() * (size_t)stride : 0);
+  int stride;
+  std::vector<double> hist = detail::mgOutputs(b.size(), param.maxIter, history != nullptr, iters, relres, &stride);
   const int st = mugiq_hip_mg_solve(x.data(), b.data(), (int)b.size(), &gauge, clover, kappa, &transfer, coarseOp.desc(), &param, iters.data(),
                                     relres.data(), history ? hist.data() : nullptr, stride, hostReads, comm, stream);
-  if (st != MUGIQ_HIP_ERROR_NOT_CONVERGED) check(st);
-  if (history) {
-    history->clear();
-    for (size_t i = 0; i < b.size(); i++) history->emplace_back(hist.begin() + i * stride, hist.begin() + i * stride + iters[i]);
-  }
-  return st == 0;
+  return detail::mgHistory(st, hist, stride, iters, history);
 }
 // ---- the mixed-precision solve (csrc/mg_solve.hip; new): the cycle in fp32 storage under the fp64 outer GCR ----
 // z_i = K(r_i) with z, r, transfer and coarseOp all of precision 4 (mugiq_hip_mg_precondition_sloppy)
@@ -269,40 +288,16 @@ inline bool mgSolveMixed(const std::vector<ColorSpinorField> &x, const std::vect
                          std::vector<double> &relres, std::vector<std::vector<double>> *history = nullptr, int *hostReads = nullptr,
                          const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
   if (b.empty() || x.size() != b.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgSolveMixed: size mismatch");
-  iters.assign(b.size(), 0);
-  relres.assign(b.size(), 0.0);
-  const int stride = param.maxIter > 0 ? param.maxIter : 1;
-  std::vector<double> hist(history ? b.size() * (size_t)stride : 0);
+  int stride;
+  std::vector<double> hist = detail::mgOutputs(b.size(), param.maxIter, history != nullptr, iters, relres, &stride);
   const int st = mugiq_hip_mg_solve_mixed(x.data(), b.data(), (int)b.size(), &gauge, clover, kappa, gaugeSloppy, cloverSloppy, &transferSloppy,
                                           coarseOpSloppy.desc(), &param, iters.data(), relres.data(), history ? hist.data() : nullptr, stride, hostReads,
                                           comm, stream);
-  if (st != MUGIQ_HIP_ERROR_NOT_CONVERGED) check(st);
-  if (history) {
-    history->clear();
-    for (size_t i = 0; i < b.size(); i++) history->emplace_back(hist.begin() + i * stride, hist.begin() + i * stride + iters[i]);
-  }
-  return st == 0;
+  return detail::mgHistory(st, hist, stride, iters, history);
 }
 // ---- the three-level solve (csrc/mg_solve.hip; new): the same four calls on a hierarchy, transfers[l] and coarseOps[l] (descriptors, e.g.
 // *CoarseOperator::desc()) per coarse level and params[l] per level; one of each is the two-grid call.  params[1]: nuPre, nuPost, omega and
 // coarseIters of the level-1 cycle, whose defaults are not tuned ----
-namespace detail {
-static_assert(sizeof(MgSolveParam) == sizeof(MugiqHipMgSolveParam), "std::vector<MgSolveParam> is handed over as an array of the C struct");
-inline int mgLevels(const std::vector<MugiqHipTransfer> &transfers, const std::vector<MugiqHipCoarseOperator> &coarseOps, const std::vector<MgSolveParam> &params,
-                    const char *who) {
-  if (transfers.empty() || transfers.size() != coarseOps.size() || transfers.size() != params.size())
-    throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, std::string(who) + ": one transfer, coarse operator and MgSolveParam per coarse level");
-  return (int)transfers.size();
-}
-inline bool mgHistory(int st, const std::vector<double> &hist, int stride, const std::vector<int> &iters, std::vector<std::vector<double>> *history) {
-  if (st != MUGIQ_HIP_ERROR_NOT_CONVERGED) check(st);
-  if (history) {
-    history->clear();
-    for (size_t i = 0; i < iters.size(); i++) history->emplace_back(hist.begin() + i * stride, hist.begin() + i * stride + iters[i]);
-  }
-  return st == 0;
-}
-}  // namespace detail
 inline void mgPrecondition(const std::vector<ColorSpinorField> &z, const std::vector<ColorSpinorField> &r, const GaugeField &gauge,
                            const MugiqHipCloverField *clover, double kappa, const std::vector<MugiqHipTransfer> &transfers,
                            const std::vector<MugiqHipCoarseOperator> &coarseOps, const std::vector<MgSolveParam> &params, const MugiqHipComm *comm = nullptr,
@@ -328,10 +323,8 @@ inline bool mgSolve(const std::vector<ColorSpinorField> &x, const std::vector<Co
                     const MugiqHipComm *comm = nullptr, void *stream = nullptr) {
   if (b.empty() || x.size() != b.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgSolve: size mismatch");
   const int L = detail::mgLevels(transfers, coarseOps, params, "mgSolve");
-  iters.assign(b.size(), 0);
-  relres.assign(b.size(), 0.0);
-  const int stride = params[0].maxIter > 0 ? params[0].maxIter : 1;
-  std::vector<double> hist(history ? b.size() * (size_t)stride : 0);
+  int stride;
+  std::vector<double> hist = detail::mgOutputs(b.size(), params[0].maxIter, history != nullptr, iters, relres, &stride);
   const int st = mugiq_hip_mg_solve_levels(x.data(), b.data(), (int)b.size(), &gauge, clover, kappa, transfers.data(), coarseOps.data(), L, params.data(),
                                            iters.data(), relres.data(), history ? hist.data() : nullptr, stride, hostReads, comm, stream);
   return detail::mgHistory(st, hist, stride, iters, history);
@@ -344,10 +337,8 @@ inline bool mgSolveMixed(const std::vector<ColorSpinorField> &x, const std::vect
                          void *stream = nullptr) {
   if (b.empty() || x.size() != b.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgSolveMixed: size mismatch");
   const int L = detail::mgLevels(transfersSloppy, coarseOpsSloppy, params, "mgSolveMixed");
-  iters.assign(b.size(), 0);
-  relres.assign(b.size(), 0.0);
-  const int stride = params[0].maxIter > 0 ? params[0].maxIter : 1;
-  std::vector<double> hist(history ? b.size() * (size_t)stride : 0);
+  int stride;
+  std::vector<double> hist = detail::mgOutputs(b.size(), params[0].maxIter, history != nullptr, iters, relres, &stride);
   const int st = mugiq_hip_mg_solve_mixed_levels(x.data(), b.data(), (int)b.size(), &gauge, clover, kappa, gaugeSloppy, cloverSloppy, transfersSloppy.data(),
                                                  coarseOpsSloppy.data(), L, params.data(), iters.data(), relres.data(), history ? hist.data() : nullptr,
                                                  stride, hostReads, comm, stream);

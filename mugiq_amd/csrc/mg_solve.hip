@@ -3,7 +3,8 @@
 // and work memory: mugiq_hip_mg_solve in include/mugiq_hip.h.  The stencil, R, P and the coarse application are the library's own entry
 // points, called as they are; what is new here are the Krylov kernels between them, on every level.  With a second coarse level the
 // level-1 solve becomes a flexible GCR preconditioned by a cycle of its own through the coarsest operator (K^(3), the *_levels entry
-// points: MgSolver::cycle is K with the level abstracted, MgSolver::coarse_solve the level-1 solve of either depth).
+// points).  The coarse levels are a chain (MgCoarse, MgSolver::coarse): MgSolver::cycle is K with the level abstracted, its correction
+// restricts to the next level, solves there (MgSolver::solve: GCRfix on the last level, the flexible GCR above it) and prolongs back.
 //
 // One set of kernels serves both levels and both storages: a field is a list of rows of complex numbers (MgLayout; fine FLOAT2: 12 rows of
 // volumeCB per parity, fine FLOAT4: 6 rows of 2 volumeCB, coarse: 2 n_vec rows of volumeCB_c) stored as Cplx<F>, F = double or float.  Every
@@ -332,9 +333,10 @@ template <typename F> struct MgLevel {
   double *partial = nullptr, *coef = nullptr, *sc = nullptr, *res = nullptr;  // shared by all levels: the stream orders their passes (MgSolver::carve)
   hipStream_t stream = nullptr;
 
-  void set_layout(const MgLayout &l) {
-    L = l;
+  void set(hipStream_t stream_, int nb_, bool wide_, const MgLayout &l, size_t vecBytes) {
+    stream = stream_, nb = nb_, wide = wide_, L = l;
     nGroups = (int)std::min<int64_t>(kMgMaxGroups, (L.total + kMgThreads - 1) / kMgThreads);
+    vecElems = (int64_t)(vecBytes / sizeof(C));
   }
   void set_scalars(unsigned char *base) {
     partial = reinterpret_cast<double *>(base);
@@ -391,35 +393,52 @@ template <typename F> struct MgLevel {
 // which fine vectors of a block a solver keeps in the workspace
 enum { kMgSetS = 1, kMgSetT = 2, kMgSetW = 4, kMgSetR = 8, kMgSetZ = 16, kMgSetsOfK = kMgSetS | kMgSetT | kMgSetW };
 
+// the coarse levels a hierarchy may have (nCoarseLevels).  Lifting the limit is this constant and the wording of check_levels' refusal;
+// it needs a reference and tests of its own first
+constexpr int kMgMaxCoarse = 2;
+
+// coarse level l >= 1 of a solver (MgSolver::coarse[l - 1]): what leads into it, its operator, and its vectors in the workspace
+template <typename F> struct MgCoarse {
+  const MugiqHipTransfer *transfer = nullptr;  // T_{l-1}, between level l - 1 and this one
+  const MugiqHipCoarseOperator *op = nullptr;  // M_l
+  MgLevel<F> lv;                               // P, Q: nDir x nb directions each
+  MugiqHipCoarseField like;                    // a vector of the level, without a body
+  size_t bytes = 0;                            // of one vector
+  int nDir = 0;                                // stored directions: coarseIters of the cycle one level up
+  bool deeper = false;                         // a level l + 1 was given: the solve here is flexible, preconditioned by the level's own cycle K_l
+  MugiqHipMgSolveParam prm{};                  // the parameters of K_l (deeper only)
+  MugiqHipCoarseField x[kMgBlock], r[kMgBlock];               // the solve's result and its right-hand side
+  MugiqHipCoarseField s[kMgBlock], t[kMgBlock], w[kMgBlock];  // K_l's own vectors (deeper only)
+
+  MugiqHipCoarseField dir(Cplx<F> *base, int j, int v) const {
+    MugiqHipCoarseField f = like;
+    f.data = lv.dir(base, j, v);
+    return f;
+  }
+};
+
 // the operators, the parameters and the workspace vectors of one storage F: with F = double the whole solve, or the outer iteration of
-// the mixed solve; with F = float the cycle K of the mixed solve, on the sloppy fields
+// the mixed solve; with F = float the cycle K of the mixed solve, on the sloppy fields.  The hierarchy is the caller's arrays of nGiven
+// coarse levels: transfers[l] = T_l, ops[l] = M_{l+1}, params[l] = the cycle on level l (nGiven = 1: two-grid)
 template <typename F> struct MgSolver {
   typedef Cplx<F> C;
   typedef MgVecs<F> Vecs;
   const MugiqHipGaugeField *gauge;
   const MugiqHipCloverField *clover;
   double kappa;
-  const MugiqHipTransfer *transfer;
-  const MugiqHipCoarseOperator *op;
-  MugiqHipMgSolveParam prm;
+  const MugiqHipTransfer *transfers;
+  const MugiqHipCoarseOperator *ops;
+  const MugiqHipMgSolveParam *params;
+  int nGiven;
   hipStream_t stream;
-  // the second coarse level of a three-level cycle (transfer1 NULL: two-grid): T_1, M_2 and params[1], set by set_coarsest() before init()
-  const MugiqHipTransfer *transfer1 = nullptr;
-  const MugiqHipCoarseOperator *op2 = nullptr;
-  MugiqHipMgSolveParam prm1{};
   int nb, nDirFine, sets;
-  bool withCoarse, withCoarse2;
-  size_t fb, cb, cb2;
-  MgLevel<F> fine, coarse, coarse2;
+  int nCoarse;  // coarse levels in use (init): level l is, when every cycle above it takes its coarse step
+  size_t fb;
+  MgLevel<F> fine;
+  MgCoarse<F> coarse[kMgMaxCoarse];
   // r: the solver's recursive residual (mixed solve, F = float: its rounded copy); zk: K's result before it is widened (mixed solve only)
   MugiqHipSpinorField s[kMgBlock], t[kMgBlock], w[kMgBlock], r[kMgBlock], zk[kMgBlock];
-  MugiqHipCoarseField xc[kMgBlock], rc[kMgBlock];
-  // K_1's own vectors on level 1 and the coarsest solve's on level 2 (three levels only)
-  MugiqHipCoarseField s1[kMgBlock], t1[kMgBlock], w1[kMgBlock], xc2[kMgBlock], rc2[kMgBlock];
   MugiqHipSpinorField fineLike;
-  MugiqHipCoarseField coarseLike, coarse2Like;
-
-  void set_coarsest(const MugiqHipTransfer *T1, const MugiqHipCoarseOperator *M2, const MugiqHipMgSolveParam &p1) { transfer1 = T1, op2 = M2, prm1 = p1; }
 
   static Vecs vecs(const MugiqHipSpinorField *f, int n) {
     Vecs m{};
@@ -436,16 +455,6 @@ template <typename F> struct MgSolver {
     f.data = fine.dir(base, j, v);
     return f;
   }
-  MugiqHipCoarseField coarse_dir(C *base, int j, int v) const {
-    MugiqHipCoarseField f = coarseLike;
-    f.data = coarse.dir(base, j, v);
-    return f;
-  }
-  MugiqHipCoarseField coarse2_dir(C *base, int j, int v) const {
-    MugiqHipCoarseField f = coarse2Like;
-    f.data = coarse2.dir(base, j, v);
-    return f;
-  }
   template <typename T> static int gather(const T *set, int n, unsigned mask, T *out) {
     int m = 0;
     for (int i = 0; i < n; i++)
@@ -459,165 +468,153 @@ template <typename F> struct MgSolver {
     gather(src, n, active, sr);
     return mugiq_hip_wilson_clover_apply(d, sr, m, gauge, clover, kappa, MUGIQ_HIP_EIG_OPERATOR_M, 1.0, nullptr, stream);
   }
-  // dst_i = A src_i for the active i, A an explicit coarse operator (M_1 or M_2)
+  // dst_i = A src_i for the active i, A the explicit operator of a coarse level
   int apply_coarse(const MugiqHipCoarseOperator *A, const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src, int n, unsigned active) const {
     MugiqHipCoarseField d[kMgBlock], sr[kMgBlock];
     const int m = gather(dst, n, active, d);
     gather(src, n, active, sr);
     return coarse_apply(d, sr, m, A, MUGIQ_HIP_EIG_OPERATOR_M, 1.0, stream);
   }
+  // c_i = R f_i and f_i = P c_i through T, from and into the fine level or a coarse one: all that tells level 0 from the others in a cycle
+  int restrict_to(const MugiqHipCoarseField *c, const MugiqHipSpinorField *f, int n, const MugiqHipTransfer *T) const {
+    return mugiq_hip_restrict_batched(c, f, n, T, 0, stream);
+  }
+  int restrict_to(const MugiqHipCoarseField *c, const MugiqHipCoarseField *f, int n, const MugiqHipTransfer *T) const {
+    return mugiq_hip_restrict_coarse_batched(c, f, n, T, stream);
+  }
+  int prolong_from(const MugiqHipSpinorField *f, const MugiqHipCoarseField *c, int n, const MugiqHipTransfer *T) const {
+    return mugiq_hip_prolongate_batched(f, c, n, T, stream);
+  }
+  int prolong_from(const MugiqHipCoarseField *f, const MugiqHipCoarseField *c, int n, const MugiqHipTransfer *T) const {
+    return mugiq_hip_prolongate_coarse_batched(f, c, n, T, stream);
+  }
 
   // The work memory is carved from the stream's operator workspace: the scalars, then per right-hand side of a block 2 nDirFine fine
-  // directions and the fine vectors of `sets` (K: s, t, w; the solver: r as well), and with the coarse level 2 coarseIters directions,
-  // xc, rc; with three levels also s, t, w of K_1 on level 1 and, for params[1].coarseIters > 0, 2 params[1].coarseIters directions, xc
-  // and rc on level 2.  init() fixes the layouts and sizes (vectors laid out like `like`, stored as Cplx<F>), vector_bytes() is this solver's share
-  // and carve() places it; the mixed solve carves two solvers from one reservation.
+  // directions and the fine vectors of `sets` (K: s, t, w; the solver: r as well), and per coarse level in use 2 nDir directions, x and
+  // r, and s, t, w of the level's own cycle where a deeper level follows (three levels: s, t, w of K_1 on level 1; level 2 only for
+  // params[1].coarseIters > 0).  init() fixes the layouts and sizes (vectors laid out like `like`, stored as Cplx<F>); carve() is the one
+  // statement of the layout: it places this solver's share, and run without a workspace it counts it (place()).  The mixed solve carves
+  // two solvers from one reservation.
   // apply_M calls the public stencil entry, which reserves the SAME arena for itself (csrc/wilson.hip, wilson_apply_impl) and takes its
   // start as the send buffer of its halo exchange.  That is safe here for two reasons, both of which this file depends on: on a single
   // domain with the form M its request is 256 bytes, so the arena, which only ever grows, neither moves nor is freed under us; and
   // without a partitioned axis nothing is packed into that send buffer.  The first kStencilHead bytes are left unused all the same, so
   // that a send buffer that did get written would not land in `partial`.
   static constexpr size_t kStencilHead = 4096;
-  void init(const MugiqHipSpinorField &like, int nDirFine_, int nVecRhs, int sets_, bool withCoarse_) {
+  void init(const MugiqHipSpinorField &like, int nDirFine_, int nVecRhs, int sets_, bool withCoarse) {
     nb = std::min(nVecRhs, kMgBlock);
-    nDirFine = nDirFine_, sets = sets_, withCoarse = withCoarse_ && prm.coarseIters > 0;
+    nDirFine = nDirFine_, sets = sets_;
     fineLike = like;
     fineLike.precision = (int)sizeof(F);
     fineLike.data = nullptr;
     for (int d = 0; d < 4; d++)
       for (int b = 0; b < 2; b++) fineLike.ghost[d][b] = nullptr;
-    coarseLike = coarse_side_layout(*transfer);
-    fb = fine_bytes<F>(like), cb = coarse_bytes<F>(coarseLike);
-    fine.stream = coarse.stream = stream;
-    fine.nb = coarse.nb = nb;
-    fine.wide = coarse.wide = debug_wide_index_asked();
-    fine.set_layout(fine_layout(like));
-    fine.vecElems = (int64_t)(fb / sizeof(C));
-    coarse.set_layout(coarse_layout(coarseLike));
-    coarse.vecElems = (int64_t)(cb / sizeof(C));
-    withCoarse2 = false, cb2 = 0;
-    if (transfer1 && withCoarse) {
-      coarse2Like = coarse_side_layout(*transfer1);
-      cb2 = coarse_bytes<F>(coarse2Like);
-      withCoarse2 = prm1.coarseIters > 0;
-      coarse2.stream = stream, coarse2.nb = nb, coarse2.wide = fine.wide;
-      coarse2.set_layout(coarse_layout(coarse2Like));
-      coarse2.vecElems = (int64_t)(cb2 / sizeof(C));
+    const bool wide = debug_wide_index_asked();
+    fb = fine_bytes<F>(like);
+    fine.set(stream, nb, wide, fine_layout(like), fb);
+    nCoarse = 0;
+    for (int l = 0; l < nGiven && withCoarse && params[l].coarseIters > 0; l++) {
+      MgCoarse<F> &c = coarse[nCoarse++];
+      c.transfer = &transfers[l], c.op = &ops[l], c.nDir = params[l].coarseIters;
+      c.deeper = l + 1 < nGiven;
+      if (c.deeper) c.prm = params[l + 1];
+      c.like = coarse_side_layout(*c.transfer);
+      c.bytes = coarse_bytes<F>(c.like);
+      c.lv.set(stream, nb, wide, coarse_layout(c.like), c.bytes);
     }
   }
-  int n_sets() const { return __builtin_popcount((unsigned)sets); }
-  bool three_level() const { return transfer1 != nullptr && withCoarse; }
-  size_t vector_bytes() const {
-    return (size_t)(2 * nDirFine + n_sets()) * nb * fb + (size_t)((withCoarse ? 2 * prm.coarseIters + 2 : 0) + (three_level() ? 3 : 0)) * nb * cb +
-           (size_t)(withCoarse2 ? 2 * prm1.coarseIters + 2 : 0) * nb * cb2;
-  }
-  unsigned char *carve(unsigned char *scalars, unsigned char *cur) {
+  // this solver's vectors from ws + off on, ws the start of the scalars; returns the offset behind them.  ws NULL: nothing is placed,
+  // the offsets are the same
+  size_t carve(unsigned char *ws, size_t off) {
     // One set of scalars serves every level because the stream orders the passes and every scalar lives for one launch: a final sum
     // writes coef, (nu, alpha) or an MR alpha, and the very next launch of that level's step (multi-axpy, update, MR update) is its
     // only reader.  Nesting K_1 inside a GCR step of level 1 does not change that: p_k = K_1(r) and q_k = M_1 p_k are complete launches
     // that come BEFORE the step's own multi-dot, so no scalar of the step exists yet while K_1 and the coarsest solve overwrite them,
     // and K_1's last alpha was consumed by its last update.  Only `res` is read by the host, straight after the final sum that wrote it.
-    fine.set_scalars(scalars);
-    coarse.set_scalars(scalars);
-    coarse2.set_scalars(scalars);
-    fine.P = reinterpret_cast<C *>(cur);
-    cur += (size_t)nDirFine * nb * fb;
-    fine.Q = reinterpret_cast<C *>(cur);
-    cur += (size_t)nDirFine * nb * fb;
+    auto take = [&](size_t bytes) {
+      unsigned char *p = ws ? ws + off : nullptr;
+      off += bytes;
+      return p;
+    };
+    if (ws) fine.set_scalars(ws);
+    fine.P = reinterpret_cast<C *>(take((size_t)nDirFine * nb * fb));
+    fine.Q = reinterpret_cast<C *>(take((size_t)nDirFine * nb * fb));
     MugiqHipSpinorField *all[5] = {s, t, w, r, zk};
     for (int k = 0; k < 5; k++)
       for (int i = 0; i < nb && ((sets >> k) & 1); i++) {
         all[k][i] = fineLike;
-        all[k][i].data = cur;
-        cur += fb;
+        all[k][i].data = take(fb);
       }
-    if (withCoarse) {
-      const int nC = prm.coarseIters;
-      coarse.P = reinterpret_cast<C *>(cur);
-      cur += (size_t)nC * nb * cb;
-      coarse.Q = reinterpret_cast<C *>(cur);
-      cur += (size_t)nC * nb * cb;
-      MugiqHipCoarseField *csets[5] = {xc, rc, s1, t1, w1};
-      for (int k = 0; k < (three_level() ? 5 : 2); k++)
+    for (int l = 0; l < nCoarse; l++) {
+      MgCoarse<F> &c = coarse[l];
+      if (ws) c.lv.set_scalars(ws);
+      c.lv.P = reinterpret_cast<C *>(take((size_t)c.nDir * nb * c.bytes));
+      c.lv.Q = reinterpret_cast<C *>(take((size_t)c.nDir * nb * c.bytes));
+      MugiqHipCoarseField *csets[5] = {c.x, c.r, c.s, c.t, c.w};
+      for (int k = 0; k < (c.deeper ? 5 : 2); k++)
         for (int i = 0; i < nb; i++) {
-          csets[k][i] = coarseLike;
-          csets[k][i].data = cur;
-          cur += cb;
+          csets[k][i] = c.like;
+          csets[k][i].data = take(c.bytes);
         }
     }
-    if (withCoarse2) {
-      const int nC = prm1.coarseIters;
-      coarse2.P = reinterpret_cast<C *>(cur);
-      cur += (size_t)nC * nb * cb2;
-      coarse2.Q = reinterpret_cast<C *>(cur);
-      cur += (size_t)nC * nb * cb2;
-      MugiqHipCoarseField *csets[2] = {xc2, rc2};
-      for (auto *set : csets)
-        for (int i = 0; i < nb; i++) {
-          set[i] = coarse2Like;
-          set[i].data = cur;
-          cur += cb2;
-        }
-    }
-    return cur;
+    return off;
+  }
+  // walk(ws) carves the solvers of a call behind the scalars at ws and returns the bytes it walked: once without a workspace for the
+  // size of the reservation, once on it
+  template <typename Walk> static int place(hipStream_t stream, const Walk &walk) {
+    void *ws = nullptr;
+    if (int st = stream_operator_workspace(&ws, kStencilHead + walk(nullptr) + 256, stream)) return st;
+    walk(static_cast<unsigned char *>(ws) + kStencilHead);
+    return MUGIQ_HIP_SUCCESS;
   }
   // one solver alone on the workspace
   int reserve(const MugiqHipSpinorField &like, int nDirFine_, int nVecRhs, bool withR) {
     init(like, nDirFine_, nVecRhs, kMgSetsOfK | (withR ? kMgSetR : 0), true);
-    void *ws = nullptr;
-    if (int st = stream_operator_workspace(&ws, kStencilHead + scalar_bytes() + vector_bytes() + 256, stream)) return st;
-    unsigned char *cur = static_cast<unsigned char *>(ws) + kStencilHead;
-    carve(cur, cur + scalar_bytes());
-    return MUGIQ_HIP_SUCCESS;
+    return place(stream, [this](unsigned char *ws) { return carve(ws, scalar_bytes()); });
   }
 
-  // x = GCRfix(A, r, nC) on level `lv` (directions P, Q of that level) for the active right-hand sides; r is used up
-  int gcr_fixed(const MgLevel<F> &lv, const MugiqHipCoarseField &like, const MugiqHipCoarseOperator *A, int nC, const MugiqHipCoarseField *x,
-                const MugiqHipCoarseField *r, int n, unsigned active) const {
+  // x = GCRfix(M_l, r, nDir) on the coarse level c for the active right-hand sides; r is used up
+  int gcr_fixed(const MgCoarse<F> &c, int n, unsigned active) const {
     MugiqHipCoarseField p[kMgBlock], q[kMgBlock];
-    for (int i = 0; i < n; i++) {
-      p[i] = like;
-      p[i].data = lv.dir(lv.P, 0, i);
-    }
-    const Vecs rv = vecs(r, n), xv = vecs(x, n), pv = vecs(p, n);
-    if (int st = lv.axpby(pv, &rv, 1.0, nullptr, 0.0, n, active)) return st;
-    for (int k = 0; k < nC; k++) {
+    for (int i = 0; i < n; i++) p[i] = c.dir(c.lv.P, 0, i);
+    const Vecs rv = vecs(c.r, n), xv = vecs(c.x, n), pv = vecs(p, n);
+    if (int st = c.lv.axpby(pv, &rv, 1.0, nullptr, 0.0, n, active)) return st;
+    for (int k = 0; k < c.nDir; k++) {
       for (int i = 0; i < n; i++) {
-        p[i] = q[i] = like;
-        p[i].data = lv.dir(lv.P, k, i);
-        q[i].data = lv.dir(lv.Q, k, i);
+        p[i] = c.dir(c.lv.P, k, i);
+        q[i] = c.dir(c.lv.Q, k, i);
       }
-      if (int st = apply_coarse(A, q, p, n, active)) return st;
-      if (int st = lv.gcr_step(k, xv, rv, k == 0, k + 1 < nC, false, n, active)) return st;
+      if (int st = apply_coarse(c.op, q, p, n, active)) return st;
+      if (int st = c.lv.gcr_step(k, xv, rv, k == 0, k + 1 < c.nDir, false, n, active)) return st;
     }
     return MUGIQ_HIP_SUCCESS;
   }
 
-  // xc = the level-1 solve of rc for the active right-hand sides; rc is used up.  Two-grid: GCRfix(M_1, rc, coarseIters).  Three levels:
-  // GCRflex(M_1, K_1, rc, coarseIters), where K_1 writes its result straight into the direction slot p_k
-  int coarse_solve(int n, unsigned active) const {
-    const int nC = prm.coarseIters;
-    if (!three_level()) return gcr_fixed(coarse, coarseLike, op, nC, xc, rc, n, active);
-    const Vecs rv = vecs(rc, n), xv = vecs(xc, n);
-    for (int k = 0; k < nC; k++) {
+  // x = the solve on level l >= 1 of r (the level's own x and r) for the active right-hand sides; r is used up.  The last level:
+  // GCRfix(M_l, r, nDir).  Above it: GCRflex(M_l, K_l, r, nDir), where K_l writes its result straight into the direction slot p_k
+  int solve(int l, int n, unsigned active) const {
+    const MgCoarse<F> &c = coarse[l - 1];
+    if (!c.deeper) return gcr_fixed(c, n, active);
+    const Vecs rv = vecs(c.r, n), xv = vecs(c.x, n);
+    for (int k = 0; k < c.nDir; k++) {
       MugiqHipCoarseField p[kMgBlock], q[kMgBlock];
       for (int i = 0; i < n; i++) {
-        p[i] = coarse_dir(coarse.P, k, i);
-        q[i] = coarse_dir(coarse.Q, k, i);
+        p[i] = c.dir(c.lv.P, k, i);
+        q[i] = c.dir(c.lv.Q, k, i);
       }
-      if (int st = precondition1(p, rc, n, active)) return st;
-      if (int st = apply_coarse(op, q, p, n, active)) return st;
-      if (int st = coarse.gcr_step(k, xv, rv, k == 0, false, false, n, active)) return st;
+      if (int st = cycle_on(l, p, c.r, n, active)) return st;
+      if (int st = apply_coarse(c.op, q, p, n, active)) return st;
+      if (int st = c.lv.gcr_step(k, xv, rv, k == 0, false, false, n, active)) return st;
     }
     return MUGIQ_HIP_SUCCESS;
   }
 
   // z_i = Cyc(A, R, P, S; p)(r_i) for the active i on level `lv`, with the level's own vectors s, t, w: a fixed sequence of launches,
-  // nothing read back.  applyA(dst, src, n, active): dst = A src; correct(dst, src, n, active): dst = P S(R src), called for
-  // p.coarseIters > 0 only.  z and r are not touched elsewhere; r is only read
-  template <typename Fld, typename ApplyA, typename Correct>
-  int cycle(const MgLevel<F> &lv, const MugiqHipMgSolveParam &p, const ApplyA &applyA, const Correct &correct, const Fld *z, const Fld *r, const Fld *s_,
-            const Fld *t_, const Fld *w_, int n, unsigned active) const {
+  // nothing read back.  applyA(dst, src, n, active): dst = A src; the correction dst = P S(R src) goes through level l + 1 (correct(),
+  // below) and is taken for p.coarseIters > 0 only.  z and r are not touched elsewhere; r is only read
+  template <typename Fld, typename ApplyA>
+  int cycle(int l, const MgLevel<F> &lv, const MugiqHipMgSolveParam &p, const ApplyA &applyA, const Fld *z, const Fld *r, const Fld *s_, const Fld *t_,
+            const Fld *w_, int n, unsigned active) const {
     bool zZero = true;
     const Fld *sIn = r;  // where s lives: r itself until the first update
     const bool coarseStep = p.coarseIters > 0;
@@ -635,7 +632,7 @@ template <typename F> struct MgSolver {
     for (int i = 0; i < p.nuPre; i++)
       if ((st = mr_step(!coarseStep && p.nuPost == 0 && i == p.nuPre - 1))) return st;
     if (coarseStep) {
-      if ((st = correct(zZero ? z : w_, sIn, n, active))) return st;
+      if ((st = correct(l, zZero ? z : w_, sIn, n, active))) return st;
       const Vecs zv = vecs(z, n), wv = vecs(w_, n);
       if (!zZero && (st = lv.axpby(zv, &zv, 1.0, &wv, 1.0, n, active))) return st;
       zZero = false;
@@ -651,38 +648,30 @@ template <typename F> struct MgSolver {
     if (zZero) return lv.axpby(vecs(z, n), nullptr, 0.0, nullptr, 0.0, n, active);  // no step at all: the cycle is 0
     return MUGIQ_HIP_SUCCESS;
   }
-
-  // z_i = K_1(r_i) on level 1: Cyc(M_1, R_1, P_1, GCRfix(M_2, ., params[1].coarseIters); params[1])
-  int precondition1(const MugiqHipCoarseField *z, const MugiqHipCoarseField *r, int n, unsigned active) const {
-    auto applyA = [this](const MugiqHipCoarseField *d, const MugiqHipCoarseField *sr, int m, unsigned act) { return apply_coarse(op, d, sr, m, act); };
-    auto correct = [this](const MugiqHipCoarseField *d, const MugiqHipCoarseField *sr, int m, unsigned act) {
-      MugiqHipCoarseField fa[kMgBlock], ca[kMgBlock];
-      const int na = gather(sr, m, act, fa);
-      gather(rc2, m, act, ca);
-      if (int e = mugiq_hip_restrict_coarse_batched(ca, fa, na, transfer1, stream)) return e;
-      if (int e = gcr_fixed(coarse2, coarse2Like, op2, prm1.coarseIters, xc2, rc2, m, act)) return e;
-      gather(xc2, m, act, ca);
-      gather(d, m, act, fa);
-      return mugiq_hip_prolongate_coarse_batched(fa, ca, na, transfer1, stream);
-    };
-    return cycle(coarse, prm1, applyA, correct, z, r, s1, t1, w1, n, active);
+  // d_i = P S(R src_i) for the active i, from level l through level l + 1: restrict into its r, solve there, prolong its x
+  template <typename Fld> int correct(int l, const Fld *d, const Fld *src, int n, unsigned active) const {
+    const MgCoarse<F> &c = coarse[l];
+    Fld fa[kMgBlock];
+    MugiqHipCoarseField ca[kMgBlock];
+    const int na = gather(src, n, active, fa);
+    gather(c.r, n, active, ca);
+    if (int e = restrict_to(ca, fa, na, c.transfer)) return e;
+    if (int e = solve(l + 1, n, active)) return e;
+    gather(c.x, n, active, ca);
+    gather(d, n, active, fa);
+    return prolong_from(fa, ca, na, c.transfer);
   }
 
-  // z_i = K(r_i) (three levels: K^(3)) for the active i
-  int precondition(const MugiqHipSpinorField *z, const MugiqHipSpinorField *r, int n, unsigned active) const {
+  // z_i = K_l(r_i) on the coarse level l >= 1 with a deeper one: Cyc(M_l, R_l, P_l, the solve on level l + 1; params[l])
+  int cycle_on(int l, const MugiqHipCoarseField *z, const MugiqHipCoarseField *r_, int n, unsigned active) const {
+    const MgCoarse<F> &c = coarse[l - 1];
+    auto applyA = [&](const MugiqHipCoarseField *d, const MugiqHipCoarseField *sr, int m, unsigned act) { return apply_coarse(c.op, d, sr, m, act); };
+    return cycle(l, c.lv, c.prm, applyA, z, r_, c.s, c.t, c.w, n, active);
+  }
+  // z_i = K(r_i) (three levels: K^(3)) for the active i: the same on level 0, Cyc(M, R_0, P_0, the solve on level 1; params[0])
+  int precondition(const MugiqHipSpinorField *z, const MugiqHipSpinorField *r_, int n, unsigned active) const {
     auto applyA = [this](const MugiqHipSpinorField *d, const MugiqHipSpinorField *sr, int m, unsigned act) { return apply_M(d, sr, m, act); };
-    auto correct = [this](const MugiqHipSpinorField *d, const MugiqHipSpinorField *sr, int m, unsigned act) {
-      MugiqHipSpinorField fa[kMgBlock];
-      MugiqHipCoarseField ca[kMgBlock];
-      const int na = gather(sr, m, act, fa);
-      gather(rc, m, act, ca);
-      if (int e = mugiq_hip_restrict_batched(ca, fa, na, transfer, 0, stream)) return e;
-      if (int e = coarse_solve(m, act)) return e;
-      gather(xc, m, act, ca);
-      gather(d, m, act, fa);
-      return mugiq_hip_prolongate_batched(fa, ca, na, transfer, stream);
-    };
-    return cycle(fine, prm, applyA, correct, z, r, s, t, w, n, active);
+    return cycle(0, fine, params[0], applyA, z, r_, s, t, w, n, active);
   }
 
   // res[4 i + ..] of the last final sum, on the host: the one blocking read
@@ -774,46 +763,48 @@ int check_problem(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in,
   return MUGIQ_HIP_SUCCESS;
 }
 
-// check_problem for a hierarchy of L = nCoarseLevels coarse levels: level 0 as above with params_h[0]; for L = 2 also T_1 = transfers_h[1]
-// (a coarse -> coarse transfer on the lattice and with the colours of M_1), M_2 = coarseOps_h[1] (on its coarse side) and params_h[1].
-// Everything before any device work; a NULL array is refused by check_problem, which sees its element 0
+// check_problem for a hierarchy of L = nCoarseLevels coarse levels: level 0 as above with params_h[0]; for every l >= 1 also
+// T_l = transfers_h[l] (a coarse -> coarse transfer on the lattice and with the colours of M_l), M_{l+1} = coarseOps_h[l] (on its coarse
+// side) and params_h[l].  Everything before any device work; a NULL array is refused by check_problem, which sees its element 0
 int check_levels(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in, int nVec, const char *outName, const char *inName,
                  const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover, const MugiqHipTransfer *transfers_h, const MugiqHipCoarseOperator *coarseOps_h,
                  int nCoarseLevels, const MugiqHipMgSolveParam *params_h, double kappa, const MugiqHipComm *comm, const char *who, int fieldPrec = 8,
                  int hierPrec = 8) {
-  if (nCoarseLevels < 1 || nCoarseLevels > 2)
+  static_assert(kMgMaxCoarse == 2, "the message below names the cycles that exist");
+  if (nCoarseLevels < 1 || nCoarseLevels > kMgMaxCoarse)
     return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "%s: nCoarseLevels = %d: a two-grid (1) or a three-level (2) cycle", who, nCoarseLevels);
   int st;
   if ((st = check_problem(out, in, nVec, outName, inName, gauge, clover, transfers_h, coarseOps_h, params_h, kappa, comm, who, fieldPrec, hierPrec))) return st;
-  if (nCoarseLevels == 1) return MUGIQ_HIP_SUCCESS;
-  const MugiqHipTransfer *T1 = &transfers_h[1];
-  const MugiqHipCoarseOperator *M1 = &coarseOps_h[0], *M2 = &coarseOps_h[1];
-  const MugiqHipMgSolveParam *p1 = &params_h[1];
-  if ((st = check_param(p1, who))) return st;
-  MUGIQ_REQUIRE(p1->nuPre + p1->nuPost + p1->coarseIters > 0, "%s: params[1] has nuPre = nuPost = coarseIters = 0: the level-1 cycle would be zero", who);
-  if ((st = validate_coarse_operator(M2, who))) return st;
-  MUGIQ_REQUIRE(T1->V != nullptr, "%s: transfer 1 / null vectors are NULL", who);
-  if (T1->precision != hierPrec || M2->precision != hierPrec)
-    return set_error(fieldPrec == 8 && hierPrec == 8 ? MUGIQ_HIP_ERROR_UNSUPPORTED : MUGIQ_HIP_ERROR_INVALID_ARGUMENT,
-                     "%s: one precision per hierarchy: transfer 0 has precision %d, transfer 1 %d and coarse operator 1 %d", who, hierPrec, T1->precision,
-                     M2->precision);
-  for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(T1->X[d] > 0 && T1->geoBlockSize[d] >= 1, "%s: transfer 1: X / geo_block_size[%d]", who, d);
-  MugiqHipCoarseField lev1 = coarse_side_layout(transfers_h[0]), lev2 = coarse_side_layout(*T1);
-  lev1.data = reinterpret_cast<void *>(uintptr_t(16));  // geometry only: the validator wants distinct non-NULL bodies and never reads them
-  lev2.data = reinterpret_cast<void *>(uintptr_t(32));
-  if ((st = validate_coarse_transfer(T1, &lev1, &lev2, 1, who))) return st;  // spin_block_size 1, on the lattice of M_1, even coarsest dims
-  MUGIQ_REQUIRE(T1->parity_offset == (int64_t)2 * M1->nVec * T1->nVec * T1->stride,
-                "%s: transfer 1 must have parity_offset = 2 nColor n_vec stride with the nColor = %d of coarse operator 0, not %lld", who, M1->nVec,
-                (long long)T1->parity_offset);
-  MUGIQ_REQUIRE(M2->nVec == T1->nVec, "%s: coarse operator 1 has n_vec %d, transfer 1 %d", who, M2->nVec, T1->nVec);
-  for (int d = 0; d < 4; d++)
-    MUGIQ_REQUIRE(M2->X[d] == lev2.X[d], "%s: coarse operator 1 X[%d] = %d, the coarse lattice of transfer 1 has %d", who, d, M2->X[d], lev2.X[d]);
-  MUGIQ_REQUIRE(M2->kappa == kappa, "%s: coarse operator 1 was built for kappa = %.17g, the call has kappa = %.17g", who, M2->kappa, kappa);
-  MUGIQ_REQUIRE((M2->hasClover != 0) == (clover != nullptr), "%s: coarse operator 1 was built %s a clover field, the call is %s one", who,
-                M2->hasClover ? "with" : "without", clover ? "with" : "without");
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(M1->data), a1 = a0 + mugiq_hip_coarse_operator_bytes(M1->X, M1->nVec, M1->precision);
-  const uintptr_t b0 = reinterpret_cast<uintptr_t>(M2->data), b1 = b0 + mugiq_hip_coarse_operator_bytes(M2->X, M2->nVec, M2->precision);
-  MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: coarse operator 1 overlaps coarse operator 0", who);
+  for (int l = 1; l < nCoarseLevels; l++) {
+    const MugiqHipTransfer *T = &transfers_h[l];
+    const MugiqHipCoarseOperator *Ma = &coarseOps_h[l - 1], *Mb = &coarseOps_h[l];  // M_l above the transfer, M_{l+1} below it
+    const MugiqHipMgSolveParam *p = &params_h[l];
+    if ((st = check_param(p, who))) return st;
+    MUGIQ_REQUIRE(p->nuPre + p->nuPost + p->coarseIters > 0, "%s: params[%d] has nuPre = nuPost = coarseIters = 0: the level-%d cycle would be zero", who, l, l);
+    if ((st = validate_coarse_operator(Mb, who))) return st;
+    MUGIQ_REQUIRE(T->V != nullptr, "%s: transfer %d / null vectors are NULL", who, l);
+    if (T->precision != hierPrec || Mb->precision != hierPrec)
+      return set_error(fieldPrec == 8 && hierPrec == 8 ? MUGIQ_HIP_ERROR_UNSUPPORTED : MUGIQ_HIP_ERROR_INVALID_ARGUMENT,
+                       "%s: one precision per hierarchy: transfer 0 has precision %d, transfer %d %d and coarse operator %d %d", who, hierPrec, l, T->precision, l,
+                       Mb->precision);
+    for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(T->X[d] > 0 && T->geoBlockSize[d] >= 1, "%s: transfer %d: X / geo_block_size[%d]", who, l, d);
+    MugiqHipCoarseField above = coarse_side_layout(transfers_h[l - 1]), below = coarse_side_layout(*T);
+    above.data = reinterpret_cast<void *>(uintptr_t(16));  // geometry only: the validator wants distinct non-NULL bodies and never reads them
+    below.data = reinterpret_cast<void *>(uintptr_t(32));
+    if ((st = validate_coarse_transfer(T, &above, &below, 1, who))) return st;  // spin_block_size 1, on the lattice of M_l, even coarsest dims
+    MUGIQ_REQUIRE(T->parity_offset == (int64_t)2 * Ma->nVec * T->nVec * T->stride,
+                  "%s: transfer %d must have parity_offset = 2 nColor n_vec stride with the nColor = %d of coarse operator %d, not %lld", who, l, Ma->nVec, l - 1,
+                  (long long)T->parity_offset);
+    MUGIQ_REQUIRE(Mb->nVec == T->nVec, "%s: coarse operator %d has n_vec %d, transfer %d %d", who, l, Mb->nVec, l, T->nVec);
+    for (int d = 0; d < 4; d++)
+      MUGIQ_REQUIRE(Mb->X[d] == below.X[d], "%s: coarse operator %d X[%d] = %d, the coarse lattice of transfer %d has %d", who, l, d, Mb->X[d], l, below.X[d]);
+    MUGIQ_REQUIRE(Mb->kappa == kappa, "%s: coarse operator %d was built for kappa = %.17g, the call has kappa = %.17g", who, l, Mb->kappa, kappa);
+    MUGIQ_REQUIRE((Mb->hasClover != 0) == (clover != nullptr), "%s: coarse operator %d was built %s a clover field, the call is %s one", who, l,
+                  Mb->hasClover ? "with" : "without", clover ? "with" : "without");
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(Ma->data), a1 = a0 + mugiq_hip_coarse_operator_bytes(Ma->X, Ma->nVec, Ma->precision);
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(Mb->data), b1 = b0 + mugiq_hip_coarse_operator_bytes(Mb->X, Mb->nVec, Mb->precision);
+    MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: coarse operator %d overlaps coarse operator %d", who, l, l - 1);
+  }
   return MUGIQ_HIP_SUCCESS;
 }
 
@@ -907,8 +898,7 @@ int precondition_levels(const MugiqHipSpinorField *z_h, const MugiqHipSpinorFiel
   if ((st = check_levels(z_h, r_h, nVec, "z", "r", gauge, clover, transfers_h, coarseOps_h, nCoarseLevels, params_h, kappa, comm, who, prec, prec))) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
-  MgSolver<F> S{gauge, clover, kappa, &transfers_h[0], &coarseOps_h[0], params_h[0], s};
-  if (nCoarseLevels == 2) S.set_coarsest(&transfers_h[1], &coarseOps_h[1], params_h[1]);
+  MgSolver<F> S{gauge, clover, kappa, transfers_h, coarseOps_h, params_h, nCoarseLevels, s};
   if ((st = S.reserve(r_h[0], 0, nVec, false))) return st;
   for (int v0 = 0; v0 < nVec; v0 += kMgBlock) {
     const int n = std::min(kMgBlock, nVec - v0);
@@ -929,8 +919,7 @@ int solve_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h,
                 param->maxIter);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
-  MgSolver<double> S{gauge, clover, kappa, &transfers_h[0], &coarseOps_h[0], *param, s};
-  if (nCoarseLevels == 2) S.set_coarsest(&transfers_h[1], &coarseOps_h[1], params_h[1]);
+  MgSolver<double> S{gauge, clover, kappa, transfers_h, coarseOps_h, params_h, nCoarseLevels, s};
   if ((st = S.reserve(b_h[0], param->nKrylov, nVec, true))) return st;
   return outer_solve(S, nullptr, x_h, b_h, nVec, param, iters_out, relres_out, history_out, historyStride, hostReads_out, who);
 }
@@ -965,15 +954,11 @@ int solve_mixed_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField
   if ((st = debug_poison_lds_if_asked(s))) return st;
   // the outer iteration: 2 nKrylov directions, r and t (for the true residual) in fp64; the cycle: r and z rounded, s, t, w and the coarse
   // levels in fp32.  One reservation, the scalars shared: the stream orders every pass
-  MgSolver<double> S{gauge, clover, kappa, &transfersSloppy_h[0], &coarseOpsSloppy_h[0], *param, s};
-  MgSolver<float> K{gaugeSloppy ? gaugeSloppy : gauge, gaugeSloppy ? cloverSloppy : clover, kappa, &transfersSloppy_h[0], &coarseOpsSloppy_h[0], *param, s};
-  if (nCoarseLevels == 2) K.set_coarsest(&transfersSloppy_h[1], &coarseOpsSloppy_h[1], params_h[1]);
+  MgSolver<double> S{gauge, clover, kappa, transfersSloppy_h, coarseOpsSloppy_h, params_h, nCoarseLevels, s};
+  MgSolver<float> K{gaugeSloppy ? gaugeSloppy : gauge, gaugeSloppy ? cloverSloppy : clover, kappa, transfersSloppy_h, coarseOpsSloppy_h, params_h, nCoarseLevels, s};
   S.init(b_h[0], param->nKrylov, nVec, kMgSetT | kMgSetR, false);
   K.init(b_h[0], 0, nVec, kMgSetsOfK | kMgSetR | kMgSetZ, true);
-  void *ws = nullptr;
-  if ((st = stream_operator_workspace(&ws, MgSolver<double>::kStencilHead + scalar_bytes() + S.vector_bytes() + K.vector_bytes() + 256, s))) return st;
-  unsigned char *scalars = static_cast<unsigned char *>(ws) + MgSolver<double>::kStencilHead;
-  K.carve(scalars, S.carve(scalars, scalars + scalar_bytes()));
+  if ((st = MgSolver<double>::place(s, [&](unsigned char *ws) { return K.carve(ws, S.carve(ws, scalar_bytes())); }))) return st;
   return outer_solve(S, &K, x_h, b_h, nVec, param, iters_out, relres_out, history_out, historyStride, hostReads_out, who);
 }
 

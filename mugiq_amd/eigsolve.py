@@ -262,25 +262,73 @@ def _mg_levels(who, transfer, coarseOp, coarseParam, param):
     return t, o, L, params
 
 
+def _mg_hierarchy(who, transfer, coarseOp, coarseParam, param):
+    """(suffix of the entry point, its transfer / operator / parameter arguments, params[0]) of an MG call: "_levels" and the arrays of
+    _mg_levels for lists, "" and the three descriptors by reference for a single Transfer and CoarseOperator (the two-grid entry points)."""
+    lev = _mg_levels(who, transfer, coarseOp, coarseParam, param)
+    if lev is not None:
+        return "_levels", lev, lev[3][0]
+    p, t, o = mgSolveParam(**param), transfer.desc(), coarseOp.desc()
+    return "", (ctypes.byref(t), ctypes.byref(o), ctypes.byref(p)), p
+
+
+def _mg_precondition(who, entry, z, r, gauge, kappa, transfer, coarseOp, clover, comm, coarseParam, param):
+    """mgPrecondition and mgPreconditionSloppy: `entry` (two-grid) or entry + "_levels" (lists)."""
+    z, r = list(z), list(r)
+    if len(z) != len(r) or not r:
+        raise _lib.MugiqHipError("%s: %d z and %d r vectors (need the same number, at least one)" % (who, len(z), len(r)))
+    keep = []
+    suffix, hierarchy, _ = _mg_hierarchy(who, transfer, coarseOp, coarseParam, param)
+    g = gauge.desc()
+    _lib.check(getattr(_lib.load(), entry + suffix)(desc_array(z), desc_array(r), len(r), ctypes.byref(g), _clover_ptr(clover, keep), float(kappa),
+                                                    *hierarchy, _comm_ptr(comm, keep), _stream()))
+
+
+def _mg_solve(who, entry, b, gauge, kappa, transfer, coarseOp, clover, sloppyFields, x, allow_unconverged, comm, coarseParam, param):
+    """mgSolve and mgSolveMixed: `entry` (two-grid) or entry + "_levels" (lists).  sloppyFields: None, or (gaugeSloppy, cloverSloppy),
+    which the mixed entries take in front of the hierarchy."""
+    b = list(b)
+    if not b:
+        raise _lib.MugiqHipError("%s: no right-hand side" % who)
+    if x is None:
+        x = [SpinorField(f.X, 8, f.order, f.stride - f.volumeCB, device=f.device) for f in b]
+    x = list(x)
+    n = len(b)
+    if len(x) != n:
+        raise _lib.MugiqHipError("%s: %d x and %d b vectors" % (who, len(x), n))
+    keep = []
+    suffix, hierarchy, p = _mg_hierarchy(who, transfer, coarseOp, coarseParam, param)
+    g = gauge.desc()
+    sloppy = ()
+    if sloppyFields is not None:
+        gaugeSloppy, cloverSloppy = sloppyFields
+        gs = None
+        if gaugeSloppy is not None:
+            gd = gaugeSloppy.desc()
+            keep.append(gd)
+            gs = ctypes.byref(gd)
+        sloppy = (gs, _clover_ptr(cloverSloppy, keep))
+    stride = max(int(p.maxIter), 1)
+    iters = (ctypes.c_int * n)()
+    relres = (ctypes.c_double * n)()
+    hist = (ctypes.c_double * (n * stride))()
+    reads = ctypes.c_int(0)
+    st = getattr(_lib.load(), entry + suffix)(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), *sloppy,
+                                              *hierarchy, iters, relres, hist, stride, ctypes.byref(reads), _comm_ptr(comm, keep), _stream())
+    if st != 0 and not (st == STATUS_NOT_CONVERGED and allow_unconverged):
+        _lib.check(st)
+    it = np.array(iters)
+    h = np.array(hist).reshape(n, stride)
+    return x, MgSolveInfo(it, np.array(relres), st == 0, [h[i, :it[i]].copy() for i in range(n)], int(reads.value))
+
+
 def mgPrecondition(z, r, gauge, kappa, transfer, coarseOp, clover=None, comm=None, coarseParam=None, **param):
     """z_i = K(r_i): one two-grid cycle (MR smoothing, coarse-grid correction by GCR on the explicit coarse operator) for lists of fp64
     SpinorFields (mugiq_hip_mg_precondition).  param: members of MugiqHipMgSolveParam (nuPre, nuPost, omega, coarseIters).
     transfer=[T0, T1], coarseOp=[op1, op2]: the three-level cycle K^(3) (mugiq_hip_mg_precondition_levels), whose level-1 solve is a GCR
     preconditioned by a cycle through op2; coarseParam: dict of the level-1 members (nuPre, nuPost, omega, coarseIters), default: the
     struct defaults, which are not tuned."""
-    z, r = list(z), list(r)
-    if len(z) != len(r) or not r:
-        raise _lib.MugiqHipError("mgPrecondition: %d z and %d r vectors (need the same number, at least one)" % (len(z), len(r)))
-    keep = []
-    lev = _mg_levels("mgPrecondition", transfer, coarseOp, coarseParam, param)
-    if lev is not None:
-        g = gauge.desc()
-        _lib.check(_lib.load().mugiq_hip_mg_precondition_levels(desc_array(z), desc_array(r), len(r), ctypes.byref(g), _clover_ptr(clover, keep),
-                                                                float(kappa), lev[0], lev[1], lev[2], lev[3], _comm_ptr(comm, keep), _stream()))
-        return
-    p, g, t, o = mgSolveParam(**param), gauge.desc(), transfer.desc(), coarseOp.desc()
-    _lib.check(_lib.load().mugiq_hip_mg_precondition(desc_array(z), desc_array(r), len(r), ctypes.byref(g), _clover_ptr(clover, keep), float(kappa),
-                                                     ctypes.byref(t), ctypes.byref(o), ctypes.byref(p), _comm_ptr(comm, keep), _stream()))
+    _mg_precondition("mgPrecondition", "mugiq_hip_mg_precondition", z, r, gauge, kappa, transfer, coarseOp, clover, comm, coarseParam, param)
 
 
 def mgSolve(b, gauge, kappa, transfer, coarseOp, clover=None, x=None, allow_unconverged=False, comm=None, coarseParam=None, **param):
@@ -291,37 +339,7 @@ def mgSolve(b, gauge, kappa, transfer, coarseOp, clover=None, x=None, allow_unco
     blocking reads the call made.  x: new fp64 fields laid out like b unless given.  A right-hand side that does not reach tol within
     maxIter raises MugiqHipError (status 5) unless allow_unconverged.  transfer=[T0, T1], coarseOp=[op1, op2] and coarseParam: the
     three-level cycle, as for mgPrecondition (mugiq_hip_mg_solve_levels)."""
-    b = list(b)
-    if not b:
-        raise _lib.MugiqHipError("mgSolve: no right-hand side")
-    if x is None:
-        x = [SpinorField(f.X, 8, f.order, f.stride - f.volumeCB, device=f.device) for f in b]
-    x = list(x)
-    n = len(b)
-    if len(x) != n:
-        raise _lib.MugiqHipError("mgSolve: %d x and %d b vectors" % (len(x), n))
-    keep = []
-    lev = _mg_levels("mgSolve", transfer, coarseOp, coarseParam, param)
-    p, g = mgSolveParam(**param), gauge.desc()
-    stride = max(int(p.maxIter), 1)
-    iters = (ctypes.c_int * n)()
-    relres = (ctypes.c_double * n)()
-    hist = (ctypes.c_double * (n * stride))()
-    reads = ctypes.c_int(0)
-    if lev is not None:
-        st = _lib.load().mugiq_hip_mg_solve_levels(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), lev[0],
-                                                   lev[1], lev[2], lev[3], iters, relres, hist, stride, ctypes.byref(reads), _comm_ptr(comm, keep),
-                                                   _stream())
-    else:
-        t, o = transfer.desc(), coarseOp.desc()
-        st = _lib.load().mugiq_hip_mg_solve(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), ctypes.byref(t),
-                                            ctypes.byref(o), ctypes.byref(p), iters, relres, hist, stride, ctypes.byref(reads), _comm_ptr(comm, keep),
-                                            _stream())
-    if st != 0 and not (st == STATUS_NOT_CONVERGED and allow_unconverged):
-        _lib.check(st)
-    it = np.array(iters)
-    h = np.array(hist).reshape(n, stride)
-    return x, MgSolveInfo(it, np.array(relres), st == 0, [h[i, :it[i]].copy() for i in range(n)], int(reads.value))
+    return _mg_solve("mgSolve", "mugiq_hip_mg_solve", b, gauge, kappa, transfer, coarseOp, clover, None, x, allow_unconverged, comm, coarseParam, param)
 
 
 def mgConvertPrecision(dst, src):
@@ -337,19 +355,8 @@ def mgPreconditionSloppy(z, r, gauge, kappa, transfer, coarseOp, clover=None, co
     """z_i = K(r_i) with every vector of the cycle in fp32 storage (mugiq_hip_mg_precondition_sloppy): z, r, transfer and coarseOp all of
     precision 4, gauge (and clover) of either.  Sums are fp64 and in a fixed order, as in mgPrecondition.  param, and the lists and
     coarseParam of a three-level hierarchy (mugiq_hip_mg_precondition_sloppy_levels): as for mgPrecondition."""
-    z, r = list(z), list(r)
-    if len(z) != len(r) or not r:
-        raise _lib.MugiqHipError("mgPreconditionSloppy: %d z and %d r vectors (need the same number, at least one)" % (len(z), len(r)))
-    keep = []
-    lev = _mg_levels("mgPreconditionSloppy", transfer, coarseOp, coarseParam, param)
-    if lev is not None:
-        g = gauge.desc()
-        _lib.check(_lib.load().mugiq_hip_mg_precondition_sloppy_levels(desc_array(z), desc_array(r), len(r), ctypes.byref(g), _clover_ptr(clover, keep),
-                                                                       float(kappa), lev[0], lev[1], lev[2], lev[3], _comm_ptr(comm, keep), _stream()))
-        return
-    p, g, t, o = mgSolveParam(**param), gauge.desc(), transfer.desc(), coarseOp.desc()
-    _lib.check(_lib.load().mugiq_hip_mg_precondition_sloppy(desc_array(z), desc_array(r), len(r), ctypes.byref(g), _clover_ptr(clover, keep), float(kappa),
-                                                            ctypes.byref(t), ctypes.byref(o), ctypes.byref(p), _comm_ptr(comm, keep), _stream()))
+    _mg_precondition("mgPreconditionSloppy", "mugiq_hip_mg_precondition_sloppy", z, r, gauge, kappa, transfer, coarseOp, clover, comm, coarseParam,
+                     param)
 
 
 def mgSolveMixed(b, gauge, kappa, transferSloppy, coarseOpSloppy, clover=None, gaugeSloppy=None, cloverSloppy=None, x=None, allow_unconverged=False,
@@ -359,42 +366,8 @@ def mgSolveMixed(b, gauge, kappa, transferSloppy, coarseOpSloppy, clover=None, g
     computeCoarseOperator built from it; gaugeSloppy / cloverSloppy: the fields the cycle's stencil reads (e.g. fp32 copies), both None:
     gauge and clover.  Returns (x, MgSolveInfo) as mgSolve does; relres is the true fp64 residual.  transferSloppy=[T0_32, T1_32],
     coarseOpSloppy=[op1_32, op2_32] and coarseParam: the three-level cycle in fp32 storage (mugiq_hip_mg_solve_mixed_levels)."""
-    b = list(b)
-    if not b:
-        raise _lib.MugiqHipError("mgSolveMixed: no right-hand side")
-    if x is None:
-        x = [SpinorField(f.X, 8, f.order, f.stride - f.volumeCB, device=f.device) for f in b]
-    x = list(x)
-    n = len(b)
-    if len(x) != n:
-        raise _lib.MugiqHipError("mgSolveMixed: %d x and %d b vectors" % (len(x), n))
-    keep = []
-    lev = _mg_levels("mgSolveMixed", transferSloppy, coarseOpSloppy, coarseParam, param)
-    p, g = mgSolveParam(**param), gauge.desc()
-    gs = None
-    if gaugeSloppy is not None:
-        gd = gaugeSloppy.desc()
-        keep.append(gd)
-        gs = ctypes.byref(gd)
-    stride = max(int(p.maxIter), 1)
-    iters = (ctypes.c_int * n)()
-    relres = (ctypes.c_double * n)()
-    hist = (ctypes.c_double * (n * stride))()
-    reads = ctypes.c_int(0)
-    if lev is not None:
-        st = _lib.load().mugiq_hip_mg_solve_mixed_levels(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), gs,
-                                                         _clover_ptr(cloverSloppy, keep), lev[0], lev[1], lev[2], lev[3], iters, relres, hist, stride,
-                                                         ctypes.byref(reads), _comm_ptr(comm, keep), _stream())
-    else:
-        t, o = transferSloppy.desc(), coarseOpSloppy.desc()
-        st = _lib.load().mugiq_hip_mg_solve_mixed(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), gs,
-                                                  _clover_ptr(cloverSloppy, keep), ctypes.byref(t), ctypes.byref(o), ctypes.byref(p), iters, relres, hist,
-                                                  stride, ctypes.byref(reads), _comm_ptr(comm, keep), _stream())
-    if st != 0 and not (st == STATUS_NOT_CONVERGED and allow_unconverged):
-        _lib.check(st)
-    it = np.array(iters)
-    h = np.array(hist).reshape(n, stride)
-    return x, MgSolveInfo(it, np.array(relres), st == 0, [h[i, :it[i]].copy() for i in range(n)], int(reads.value))
+    return _mg_solve("mgSolveMixed", "mugiq_hip_mg_solve_mixed", b, gauge, kappa, transferSloppy, coarseOpSloppy, clover, (gaugeSloppy, cloverSloppy), x,
+                     allow_unconverged, comm, coarseParam, param)
 
 
 def mgSetupParam(**param):
