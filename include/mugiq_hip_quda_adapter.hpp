@@ -7,7 +7,9 @@
 // declaration-only stand-ins for the QUDA / MPI / Eigsolve_Mugiq names it touches (tests/quda_stub/) and, where the reference
 // tree is mounted, against the reference's own include/mugiq.h + include/enum_mugiq.h -- that pins templates, signatures and
 // C-ABI calls, and nothing about layouts (see 5. below).
-// Everything QUDA-independent that it calls IS built and tested here (include/mugiq_hip_operators.hpp, tests/cpp/loop.cpp).
+// Everything QUDA-independent that it calls IS built and executed here: include/mugiq_hip_operators.hpp runs on the GPU in
+// tests/cpp/loop.cpp (the loop classes) and tests/cpp/operators.cpp (every other wrapper and class, against the Python binding bit
+// for bit), and tests/test_cpp_operators_cpu.py fails for a name of that header that neither program executes.
 // The QUDA accessors used below are those of QUDA develop, early-to-mid 2020 (the reference's vintage);
 // a maintainer on another QUDA version adjusts the few lines marked [QUDA-API].
 //

@@ -1,6 +1,7 @@
 """The C++ host-side mirror (include/mugiq_hip_operators.hpp) compiles against the C ABI (CPU check) and the C++
 driver program tests/cpp/loop.cpp -- the computeLoop flow of the reference's tests/loop.cpp for configs[0] --
-runs green on the GPU with the reference's own flag names."""
+runs green on the GPU with the reference's own flag names.  The operator part of the header (everything beside the loop classes) is
+executed by a second program, tests/cpp/operators.cpp: tests/test_cpp_operators_cpu.py and tests/test_gpu_cpp_operators.py."""
 import os
 import subprocess
 
