@@ -23,6 +23,7 @@
 // store is 16 consecutive complex numbers.  k runs over the input vectors, four to an instruction, in ascending order; a wave owns 32
 // elements x 64 outputs (16 accumulators).  Z comes zero-padded to multiples of (4, 64) behind the pointer table.
 #include "mg_common.h"
+#include "op_forms.h"
 
 #include <algorithm>
 #include <chrono>
@@ -613,8 +614,8 @@ int mugiq_hip_coarse_eigensolve(const MugiqHipCoarseField *evecs_h, const MugiqH
   if ((st = check_eig_param(param, who))) return st;
   if ((st = check_single_domain(comm, who))) return st;
   if ((st = validate_coarse_operator(op, who))) return st;
-  MUGIQ_REQUIRE(opType >= MUGIQ_HIP_EIG_OPERATOR_M && opType <= MUGIQ_HIP_EIG_OPERATOR_H, "%s: opType %d is none of M, Mdag, MdagM, MMdag, H", who, opType);
-  if (opType != MUGIQ_HIP_EIG_OPERATOR_MDAGM && opType != MUGIQ_HIP_EIG_OPERATOR_MMDAG)
+  MUGIQ_REQUIRE(valid_op(opType), "%s: opType %d is none of M, Mdag, MdagM, MMdag, H", who, opType);
+  if (!normal_op(opType))
     return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "%s: opType %d: the solver needs a Hermitian positive operator, MdagM or MMdag", who, opType);
   if (op->precision != 8) return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "%s: the coarse operator has precision %d: the eigensolver is fp64 only", who, op->precision);
   const int nKr = param->nKr, nConv = param->nConv;

@@ -21,6 +21,7 @@
 // columns l + 16 k.  The 16 partial sums of an output meet in LDS and are added in a fixed order by one lane.  Every vector has its own
 // accumulators and the same order wherever it stands in the batch.
 #include "mg_common.h"
+#include "op_forms.h"
 
 #include <algorithm>
 #include <vector>
@@ -459,10 +460,11 @@ int validate_coarse_vectors(const MugiqHipCoarseField *f, int n, const MugiqHipC
 // validated arguments; the intermediate of a normal form: 8 unpadded vectors in the per-stream workspace
 int coarse_apply(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src, int nVec, const MugiqHipCoarseOperator *op, int opType, double scale,
                  hipStream_t stream) {
-  const bool normal = opType == MUGIQ_HIP_EIG_OPERATOR_MDAGM || opType == MUGIQ_HIP_EIG_OPERATOR_MMDAG;
-  if (!normal)
-    return launch_apply(dst, src, nVec, op, opType == MUGIQ_HIP_EIG_OPERATOR_MDAG, opType == MUGIQ_HIP_EIG_OPERATOR_H, scale, stream);
+  auto simple = [&](const MugiqHipCoarseField *d, const MugiqHipCoarseField *s, int n, int dagger, int gamma5, double f) {
+    return launch_apply(d, s, n, op, dagger, gamma5, f, stream);
+  };
   MugiqHipCoarseField tmp[kCaRB];
+  if (!normal_op(opType)) return apply_form(opType, simple, dst, src, tmp, nVec, scale);  // (one launch sequence for all nVec, no intermediate)
   const size_t one = align256((size_t)2 * 2 * op->nVec * op->volumeCB * 2 * op->precision);
   void *ws = nullptr;
   if (int st = stream_workspace(&ws, kCaRB * one, stream)) return st;
@@ -472,12 +474,8 @@ int coarse_apply(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src,
     tmp[i].stride = op->volumeCB;
     tmp[i].parity_offset = (int64_t)2 * op->nVec * op->volumeCB;
   }
-  const int first = opType == MUGIQ_HIP_EIG_OPERATOR_MMDAG;  // MMdag = M_c M_c^dag: the adjoint first
-  for (int v0 = 0; v0 < nVec; v0 += kCaRB) {
-    const int n = std::min(kCaRB, nVec - v0);
-    if (int st = launch_apply(tmp, src + v0, n, op, first, 0, 1.0, stream)) return st;
-    if (int st = launch_apply(dst + v0, tmp, n, op, !first, 0, scale, stream)) return st;
-  }
+  for (int v0 = 0; v0 < nVec; v0 += kCaRB)
+    if (int st = apply_form(opType, simple, dst + v0, src + v0, tmp, std::min(kCaRB, nVec - v0), scale)) return st;
   return MUGIQ_HIP_SUCCESS;
 }
 
@@ -559,7 +557,7 @@ int mugiq_hip_coarse_apply(const MugiqHipCoarseField *dst_h, const MugiqHipCoars
   int st;
   if ((st = check_single_domain(comm, who))) return st;
   if ((st = validate_coarse_operator(op, who))) return st;
-  MUGIQ_REQUIRE(opType >= MUGIQ_HIP_EIG_OPERATOR_M && opType <= MUGIQ_HIP_EIG_OPERATOR_H, "%s: opType %d is none of M, Mdag, MdagM, MMdag, H", who, opType);
+  MUGIQ_REQUIRE(valid_op(opType), "%s: opType %d is none of M, Mdag, MdagM, MMdag, H", who, opType);
   if ((st = validate_coarse_vectors(src_h, nVec, op, who, "src"))) return st;
   if ((st = validate_coarse_vectors(dst_h, nVec, op, who, "dst"))) return st;
   for (int r = 0; r < nVec; r++) {

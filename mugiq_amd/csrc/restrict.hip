@@ -17,6 +17,7 @@
 // Workgroups follow xcd_contiguous_block: x-adjacent aggregates share the 128-byte lines of a V row and run on one XCD.
 // Coarse -> coarse levels (256 x smaller): restrict_coarse_kernel, one lane per coarse site, output component and eight vectors.
 #include "mg_common.h"
+#include "op_forms.h"
 
 #include <algorithm>
 #include <cmath>
@@ -581,10 +582,8 @@ int deflate_low_modes_coarse(const MugiqHipSpinorField *dst, const MugiqHipSpino
   return prolong_subtract(dst, y[0].data(), nVec, &transfers[0], stream);
 }
 
-// ---- the eigenpair check on the coarsest level ----------------------------------------------------------------------------------------
+// ---- the eigenpair check on the coarsest level (check_eigenpairs of csrc/op_forms.h with the scalars below) ---------------------------
 namespace {
-
-constexpr int kEvBlock = 8;  // eigenvectors per block: the block of the batched stencil and of the restriction
 
 // MODE 0: out[i] = (Re, Im <w_i, y_i>, |w_i|^2);  MODE 1: out[i] = (|lambda_i w_i - y_i|^2, 0, 0).  One workgroup per vector: lane t adds
 // the elements t, t + 256, ... in ascending order, then a fixed halving tree in LDS
@@ -622,6 +621,47 @@ __global__ __launch_bounds__(kCoThreads) void coarse_scalar_kernel(const void *c
   if (t < 3) out[3 * i + t] = red[t][0];
 }
 
+// The sums of coarse_scalar_kernel<.., mode> over the pairs (w_i, y_i), i < n, of one layout, on the host and over all ranks of comm (NULL:
+// this rank's).  scal_d: lambda of the block [2 kEvBlock], then the sums [3 kEvBlock].  Synchronises the stream
+int coarse_scalars(int mode, const MugiqHipCoarseField *w, const MugiqHipCoarseField *y, int n, double *scal_d, const MugiqHipComm *comm,
+                   hipStream_t stream, double out[3 * kEvBlock]) {
+  std::vector<const void *> host(2 * (size_t)n);
+  for (int i = 0; i < n; i++) host[i] = w[i].data, host[n + i] = y[i].data;
+  void *tab = nullptr;
+  if (int rc = upload_table(&tab, host.data(), host.size() * sizeof(void *), stream)) return rc;
+  const void *const *W_d = static_cast<const void *const *>(tab);
+  const CoarseGeom cg{2 * w[0].nColor, w[0].volumeCB, w[0].stride, w[0].parity_offset, 2 * 2 * w[0].nColor * w[0].volumeCB};
+  double *sums_d = scal_d + 2 * kEvBlock;
+  with_storage(w[0].precision, [&](auto f) {
+    using F = decltype(f);
+    hipLaunchKernelGGL((mode == 0 ? coarse_scalar_kernel<F, 0> : coarse_scalar_kernel<F, 1>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg,
+                       scal_d, sums_d);
+  });
+  MUGIQ_CHECK_HIP(hipGetLastError());
+  MUGIQ_CHECK_HIP(hipMemcpyAsync(out, sums_d, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, stream));
+  MUGIQ_CHECK_HIP(hipStreamSynchronize(stream));
+  if (comm && comm->size > 1) {
+    std::vector<double> v(out, out + 3 * n);
+    if (int rc = sum_over_ranks(comm, v)) return rc;
+    std::copy(v.begin(), v.end(), out);
+  }
+  return MUGIQ_HIP_SUCCESS;
+}
+
+// The check of ev[0 .. nEv) with y_i = A_c w_i from apply(Y, w, n), block by block.  Y: kEvBlock work vectors laid out like the
+// eigenvectors; scal_d: as above
+template <typename Apply>
+int check_coarse_eigenpairs(const MugiqHipCoarseField *ev, int nEv, int opType, const MugiqHipCoarseField *Y, double *scal_d, double *lambda_h,
+                            double *residual_h, double *sigma_h, const MugiqHipComm *comm, hipStream_t stream, Apply &&apply) {
+  return check_eigenpairs(
+      nEv, opType, lambda_h, residual_h, sigma_h, [&](int v0, int n) { return apply(Y, ev + v0, n); },
+      [&](int v0, int n, double *sums) { return coarse_scalars(0, ev + v0, Y, n, scal_d, comm, stream, sums); },
+      [&](int v0, int n, const double *lambda, double *sums) -> int {
+        MUGIQ_CHECK_HIP(hipMemcpyAsync(scal_d, lambda, sizeof(double) * 2 * n, hipMemcpyHostToDevice, stream));
+        return coarse_scalars(1, ev + v0, Y, n, scal_d, comm, stream, sums);
+      });
+}
+
 }  // namespace
 
 int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipTransfer *transfers, int nLevels, const MugiqHipGaugeField *gauge,
@@ -632,11 +672,8 @@ int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipT
   MUGIQ_REQUIRE(ev != nullptr && transfers != nullptr && lambda_h != nullptr && residual_h != nullptr, "%s: NULL argument", who);
   MUGIQ_REQUIRE(nEv >= 1, "%s: nEv = %d must be >= 1", who, nEv);
   MUGIQ_REQUIRE(nLevels >= 1 && nLevels <= 8, "%s: nCoarseLevels = %d must be in [1, 8]", who, nLevels);
-  MUGIQ_REQUIRE(opType >= MUGIQ_HIP_EIG_OPERATOR_M && opType <= MUGIQ_HIP_EIG_OPERATOR_H, "%s: opType %d is none of M, Mdag, MdagM, MMdag, H", who, opType);
-  const bool normal = opType == MUGIQ_HIP_EIG_OPERATOR_MDAGM || opType == MUGIQ_HIP_EIG_OPERATOR_MMDAG;
-  MUGIQ_REQUIRE(!(normal || opType == MUGIQ_HIP_EIG_OPERATOR_H) || sigma_h != nullptr, "%s: sigma_h is NULL", who);
-  MUGIQ_REQUIRE(!massNormalization || kappa != 0.0, "%s: mass normalisation with kappa = 0", who);
   int st, part[4];
+  if ((st = check_evals_request(opType, sigma_h, massNormalization, kappa, who))) return st;
   std::vector<MugiqHipCoarseField> lev;
   if ((st = validate_hierarchy(transfers, nLevels, ev, nEv, &lev, who))) return st;
   const MugiqHipTransfer &T0 = transfers[0];
@@ -694,14 +731,11 @@ int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipT
       C[l][i].data = cur;
       cur += levBytes[l];
     }
-  double *lambda_d = reinterpret_cast<double *>(static_cast<unsigned char *>(ws) + scalOff), *sums_d = lambda_d + 2 * kEvBlock;
   const int L = nLevels;
-  const MugiqHipCoarseField *Y = C[L - 1].data(), *Tm = C[L - 1].data() + kEvBlock;
-  const CoarseGeom cg{2 * lev[L - 1].nColor, lev[L - 1].volumeCB, lev[L - 1].stride, lev[L - 1].parity_offset, 2 * 2 * lev[L - 1].nColor * lev[L - 1].volumeCB};
-  const double scale = massNormalization ? 0.25 / (kappa * kappa) : 1.0;  // lib/eigsolve_mugiq.cpp:302
+  const double scale = mass_scale(massNormalization, kappa);
 
   // out = s R [g5] M^(dag) P in: up through the levels, one batched stencil call (its halo exchange included), down again
-  auto apply = [&](const MugiqHipCoarseField *out, const MugiqHipCoarseField *in, int n, int dagger, int gamma5, double s) -> int {
+  auto simple = [&](const MugiqHipCoarseField *out, const MugiqHipCoarseField *in, int n, int dagger, int gamma5, double s) -> int {
     int rc;
     const MugiqHipCoarseField *c = in;
     for (int l = L - 1; l >= 1; l--) {
@@ -717,62 +751,18 @@ int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipT
       if ((rc = restrict_coarse_batched(l == L - 1 ? out : C[l].data(), C[l - 1].data(), n, &transfers[l], stream))) return rc;
     return MUGIQ_HIP_SUCCESS;
   };
-  auto scalars = [&](int mode, const MugiqHipCoarseField *w, int n, double out[3 * kEvBlock]) -> int {
-    std::vector<const void *> host(2 * (size_t)n);
-    for (int i = 0; i < n; i++) host[i] = w[i].data, host[n + i] = Y[i].data;
-    void *tab = nullptr;
-    if (int rc = upload_table(&tab, host.data(), host.size() * sizeof(void *), stream)) return rc;
-    const void *const *W_d = static_cast<const void *const *>(tab);
-    if (P == 8 && mode == 0) hipLaunchKernelGGL((coarse_scalar_kernel<double, 0>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
-    else if (P == 8) hipLaunchKernelGGL((coarse_scalar_kernel<double, 1>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
-    else if (mode == 0) hipLaunchKernelGGL((coarse_scalar_kernel<float, 0>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
-    else hipLaunchKernelGGL((coarse_scalar_kernel<float, 1>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
-    MUGIQ_CHECK_HIP(hipGetLastError());
-    MUGIQ_CHECK_HIP(hipMemcpyAsync(out, sums_d, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, stream));
-    MUGIQ_CHECK_HIP(hipStreamSynchronize(stream));
-    if (comm && comm->size > 1) {
-      std::vector<double> v(out, out + 3 * n);
-      if (int rc = sum_over_ranks(comm, v)) return rc;
-      std::copy(v.begin(), v.end(), out);
-    }
-    return MUGIQ_HIP_SUCCESS;
-  };
-
-  for (int v0 = 0; v0 < nEv; v0 += kEvBlock) {
-    const int n = std::min(kEvBlock, nEv - v0);
-    const MugiqHipCoarseField *w = ev + v0;
-    switch (opType) {  // QUDA's DiracMdagM / DiracMMdag on DiracCoarse: products of the coarse operators, not R MdagM P
-    case MUGIQ_HIP_EIG_OPERATOR_M: st = apply(Y, w, n, 0, 0, scale); break;
-    case MUGIQ_HIP_EIG_OPERATOR_MDAG: st = apply(Y, w, n, 1, 0, scale); break;
-    case MUGIQ_HIP_EIG_OPERATOR_H: st = apply(Y, w, n, 0, 1, scale); break;
-    case MUGIQ_HIP_EIG_OPERATOR_MDAGM:
-      if (!(st = apply(Tm, w, n, 0, 0, 1.0))) st = apply(Y, Tm, n, 1, 0, scale);
-      break;
-    default:
-      if (!(st = apply(Tm, w, n, 1, 0, 1.0))) st = apply(Y, Tm, n, 0, 0, scale);
-    }
-    if (st) return st;
-    double sums[3 * kEvBlock];
-    if ((st = scalars(0, w, n, sums))) return st;
-    for (int i = 0; i < n; i++) {
-      const double nrm = std::sqrt(sums[3 * i + 2]);  // lambda = w^dag A_c w / ||w||   (:303, not ||w||^2)
-      lambda_h[2 * (v0 + i)] = sums[3 * i] / nrm;
-      lambda_h[2 * (v0 + i) + 1] = sums[3 * i + 1] / nrm;
-    }
-    MUGIQ_CHECK_HIP(hipMemcpyAsync(lambda_d, lambda_h + 2 * v0, sizeof(double) * 2 * n, hipMemcpyHostToDevice, stream));
-    if ((st = scalars(1, w, n, sums))) return st;  // (synchronises: lambda_h may be read again)
-    for (int i = 0; i < n; i++) {
-      residual_h[v0 + i] = std::sqrt(sums[3 * i]);  // r = ||lambda w - A_c w||   (:305-306)
-      if (normal) sigma_h[v0 + i] = std::sqrt(lambda_h[2 * (v0 + i)]);  // :311
-      else if (opType == MUGIQ_HIP_EIG_OPERATOR_H) sigma_h[v0 + i] = lambda_h[2 * (v0 + i)];
-    }
-  }
-  return MUGIQ_HIP_SUCCESS;
+  // (QUDA's DiracMdagM / DiracMMdag on DiracCoarse: products of the coarse operators, not R MdagM P)
+  const MugiqHipCoarseField *Tm = C[L - 1].data() + kEvBlock;
+  return check_coarse_eigenpairs(ev, nEv, opType, C[L - 1].data(), reinterpret_cast<double *>(static_cast<unsigned char *>(ws) + scalOff), lambda_h,
+                                 residual_h, sigma_h, comm, stream, [&](const MugiqHipCoarseField *y, const MugiqHipCoarseField *w, int n) {
+                                   return apply_form(opType, simple, y, w, Tm, n, scale);
+                                 });
 }
 
 // The same check with A_c applied by the explicit coarse operator (csrc/coarse_op.hip) instead of R M P through the fine lattice: one
-// level, one domain.  Work memory (operator workspace of the stream; coarse_apply keeps its intermediate in stream_workspace): 8 coarse
-// vectors laid out like the eigenvectors, lambda and the sums
+// level, one domain (an unpartitioned comm of several ranks passes check_single_domain: every rank checks its own vectors, nothing is
+// summed).  Work memory (operator workspace of the stream; coarse_apply keeps its intermediate in stream_workspace): 8 coarse vectors laid
+// out like the eigenvectors, lambda and the sums
 int compute_evals_coarse_operator(const MugiqHipCoarseField *ev, int nEv, const MugiqHipCoarseOperator *op, int opType, int massNormalization,
                                   double *lambda_h, double *residual_h, double *sigma_h, const MugiqHipComm *comm, hipStream_t stream) {
   const char *who = "computeEvalsCoarse(coarseOp)";
@@ -782,14 +772,11 @@ int compute_evals_coarse_operator(const MugiqHipCoarseField *ev, int nEv, const 
   int st;
   if ((st = check_single_domain(comm, who))) return st;
   if ((st = validate_coarse_operator(op, who))) return st;
-  MUGIQ_REQUIRE(opType >= MUGIQ_HIP_EIG_OPERATOR_M && opType <= MUGIQ_HIP_EIG_OPERATOR_H, "%s: opType %d is none of M, Mdag, MdagM, MMdag, H", who, opType);
-  const bool normal = opType == MUGIQ_HIP_EIG_OPERATOR_MDAGM || opType == MUGIQ_HIP_EIG_OPERATOR_MMDAG;
-  MUGIQ_REQUIRE(!(normal || opType == MUGIQ_HIP_EIG_OPERATOR_H) || sigma_h != nullptr, "%s: sigma_h is NULL", who);
-  MUGIQ_REQUIRE(!massNormalization || op->kappa != 0.0, "%s: mass normalisation with kappa = 0", who);
+  if ((st = check_evals_request(opType, sigma_h, massNormalization, op->kappa, who))) return st;
   if ((st = validate_coarse_vectors(ev, nEv, op, who, "coarse eigen"))) return st;
   if ((st = debug_poison_lds_if_asked(stream))) return st;
 
-  const size_t P = (size_t)op->precision, one = align256((size_t)2 * ev[0].parity_offset * 2 * P);
+  const size_t one = align256((size_t)2 * ev[0].parity_offset * 2 * (size_t)op->precision);
   void *ws = nullptr;
   if ((st = stream_operator_workspace(&ws, kEvBlock * one + sizeof(double) * 5 * kEvBlock, stream))) return st;
   MugiqHipCoarseField Y[kEvBlock];
@@ -797,46 +784,11 @@ int compute_evals_coarse_operator(const MugiqHipCoarseField *ev, int nEv, const 
     Y[i] = ev[0];
     Y[i].data = static_cast<unsigned char *>(ws) + i * one;
   }
-  double *lambda_d = reinterpret_cast<double *>(static_cast<unsigned char *>(ws) + kEvBlock * one), *sums_d = lambda_d + 2 * kEvBlock;
-  const CoarseGeom cg{2 * op->nVec, op->volumeCB, ev[0].stride, ev[0].parity_offset, 2 * 2 * op->nVec * op->volumeCB};
-  const double scale = massNormalization ? 0.25 / (op->kappa * op->kappa) : 1.0;  // lib/eigsolve_mugiq.cpp:302
-
-  auto scalars = [&](int mode, const MugiqHipCoarseField *w, int n, double out[3 * kEvBlock]) -> int {
-    std::vector<const void *> host(2 * (size_t)n);
-    for (int i = 0; i < n; i++) host[i] = w[i].data, host[n + i] = Y[i].data;
-    void *tab = nullptr;
-    if (int rc = upload_table(&tab, host.data(), host.size() * sizeof(void *), stream)) return rc;
-    const void *const *W_d = static_cast<const void *const *>(tab);
-    if (P == 8 && mode == 0) hipLaunchKernelGGL((coarse_scalar_kernel<double, 0>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
-    else if (P == 8) hipLaunchKernelGGL((coarse_scalar_kernel<double, 1>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
-    else if (mode == 0) hipLaunchKernelGGL((coarse_scalar_kernel<float, 0>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
-    else hipLaunchKernelGGL((coarse_scalar_kernel<float, 1>), dim3(n), dim3(kCoThreads), 0, stream, W_d, W_d + n, cg, lambda_d, sums_d);
-    MUGIQ_CHECK_HIP(hipGetLastError());
-    MUGIQ_CHECK_HIP(hipMemcpyAsync(out, sums_d, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, stream));
-    MUGIQ_CHECK_HIP(hipStreamSynchronize(stream));
-    return MUGIQ_HIP_SUCCESS;
-  };
-
-  for (int v0 = 0; v0 < nEv; v0 += kEvBlock) {
-    const int n = std::min(kEvBlock, nEv - v0);
-    const MugiqHipCoarseField *w = ev + v0;
-    if ((st = coarse_apply(Y, w, n, op, opType, scale, stream))) return st;
-    double sums[3 * kEvBlock];
-    if ((st = scalars(0, w, n, sums))) return st;
-    for (int i = 0; i < n; i++) {
-      const double nrm = std::sqrt(sums[3 * i + 2]);  // lambda = w^dag A_c w / ||w||   (:303, not ||w||^2)
-      lambda_h[2 * (v0 + i)] = sums[3 * i] / nrm;
-      lambda_h[2 * (v0 + i) + 1] = sums[3 * i + 1] / nrm;
-    }
-    MUGIQ_CHECK_HIP(hipMemcpyAsync(lambda_d, lambda_h + 2 * v0, sizeof(double) * 2 * n, hipMemcpyHostToDevice, stream));
-    if ((st = scalars(1, w, n, sums))) return st;  // (synchronises: lambda_h may be read again)
-    for (int i = 0; i < n; i++) {
-      residual_h[v0 + i] = std::sqrt(sums[3 * i]);  // r = ||lambda w - A_c w||   (:305-306)
-      if (normal) sigma_h[v0 + i] = std::sqrt(lambda_h[2 * (v0 + i)]);  // :311
-      else if (opType == MUGIQ_HIP_EIG_OPERATOR_H) sigma_h[v0 + i] = lambda_h[2 * (v0 + i)];
-    }
-  }
-  return MUGIQ_HIP_SUCCESS;
+  const double scale = mass_scale(massNormalization, op->kappa);
+  return check_coarse_eigenpairs(ev, nEv, opType, Y, reinterpret_cast<double *>(static_cast<unsigned char *>(ws) + kEvBlock * one), lambda_h, residual_h,
+                                 sigma_h, nullptr, stream, [&](const MugiqHipCoarseField *y, const MugiqHipCoarseField *w, int n) {
+                                   return coarse_apply(y, w, n, op, opType, scale, stream);
+                                 });
 }
 
 }  // namespace mugiq

@@ -1,6 +1,6 @@
 // The Wilson and Wilson-clover operators on the fields this library already holds, and what rests on them: the eigenpair check of
-// Eigsolve_Mugiq::computeEvals (lib/eigsolve_mugiq.cpp:289-315), projectVector (:340-348) and a CG on the normal equations started
-// from the low-mode part.  Twisted-mass terms, the inverse clover term, even-odd preconditioning and mixed precision are out of scope.
+// Eigsolve_Mugiq::computeEvals (host procedure and the five forms: csrc/op_forms.h), projectVector (lib/eigsolve_mugiq.cpp:340-348) and a
+// CG on the normal equations started from the low-mode part.  Twisted-mass terms, the inverse clover term, even-odd preconditioning and mixed precision are out of scope.
 //
 //   M psi(x) = A(x) psi(x) - kappa sum_mu [ (1 - g_mu) U_mu(x) psi(x+mu) + (1 + g_mu) U_mu^dag(x-mu) psi(x-mu) ]
 //   A = 1 (Wilson) | the clover term of a MugiqHipCloverField (csrc/clover.hip): two Hermitian 6 x 6 blocks per site, which commute with g5
@@ -18,7 +18,7 @@
 // without scratch (checked with -Rpass-analysis=kernel-resource-usage).
 // CLOVER: the accumulators start as A(x) psi_v(x) instead of psi_v(x).  One packed block (36 reals) is loaded at a time and applied to the
 // NB vectors; it is dead before the hops start.  A is Hermitian and commutes with g5, so the dagger and gamma5 flags need nothing more.
-#include "internal.h"
+#include "op_forms.h"
 
 #include <algorithm>
 #include <cmath>
@@ -572,22 +572,8 @@ int apply_simple(const OpContext &c, const MugiqHipSpinorField *dst, const Mugiq
 // any form; tmp: n fields with ghost zones for the intermediate of the two normal operators
 int apply_op(const OpContext &c, const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int n, int opType, double scale,
              const MugiqHipSpinorField *tmp) {
-  int st;
-  switch (opType) {
-  case MUGIQ_HIP_EIG_OPERATOR_M: return apply_simple(c, dst, src, n, 0, 0, scale);
-  case MUGIQ_HIP_EIG_OPERATOR_MDAG: return apply_simple(c, dst, src, n, 1, 0, scale);
-  case MUGIQ_HIP_EIG_OPERATOR_H: return apply_simple(c, dst, src, n, 0, 1, scale);
-  case MUGIQ_HIP_EIG_OPERATOR_MDAGM:
-    if ((st = apply_simple(c, tmp, src, n, 0, 0, 1.0))) return st;
-    return apply_simple(c, dst, tmp, n, 1, 0, scale);
-  default:
-    if ((st = apply_simple(c, tmp, src, n, 1, 0, 1.0))) return st;
-    return apply_simple(c, dst, tmp, n, 0, 0, scale);
-  }
+  return apply_form(opType, [&c](auto... a) { return apply_simple(c, a...); }, dst, src, tmp, n, scale);
 }
-
-bool valid_op(int opType) { return opType >= MUGIQ_HIP_EIG_OPERATOR_M && opType <= MUGIQ_HIP_EIG_OPERATOR_H; }
-bool normal_op(int opType) { return opType == MUGIQ_HIP_EIG_OPERATOR_MDAGM || opType == MUGIQ_HIP_EIG_OPERATOR_MMDAG; }
 
 int reduction_groups(const MugiqHipSpinorField &f) { return std::min(kRedMaxGroups, (2 * f.volumeCB + kRedThreads - 1) / kRedThreads); }
 size_t reduction_bytes(const MugiqHipSpinorField &f) { return align256(sizeof(double) * 3 * kOpBlock * ((size_t)reduction_groups(f) + 1)); }
@@ -722,10 +708,7 @@ static int compute_evals_impl(const MugiqHipSpinorField *eVecs_h, int nEv, const
   const char *who = "computeEvals";
   MUGIQ_REQUIRE(eVecs_h != nullptr && lambda_h != nullptr && residual_h != nullptr, "%s: NULL argument", who);
   MUGIQ_REQUIRE(nEv >= 1, "%s: nEv = %d must be >= 1", who, nEv);
-  MUGIQ_REQUIRE(valid_op(opType), "%s: opType %d is none of M, Mdag, MdagM, MMdag, H", who, opType);
-  const bool wantSigma = normal_op(opType) || opType == MUGIQ_HIP_EIG_OPERATOR_H;
-  MUGIQ_REQUIRE(!wantSigma || sigma_h != nullptr, "%s: sigma_h is NULL", who);
-  MUGIQ_REQUIRE(!massNormalization || kappa != 0.0, "%s: mass normalisation with kappa = 0", who);
+  if (int rq = check_evals_request(opType, sigma_h, massNormalization, kappa, who)) return rq;
   int st, part[4];
   if ((st = check_vector_set(eVecs_h, nEv, who, "eVecs"))) return st;
   if ((st = check_comm(comm, part, true, who))) return st;
@@ -748,35 +731,28 @@ static int compute_evals_impl(const MugiqHipSpinorField *eVecs_h, int nEv, const
   carve_fields(&cur, e0, prec, part, kOpBlock, w);
   carve_fields(&cur, e0, prec, part, kOpBlock, tmp);
   double *red_d = reinterpret_cast<double *>(cur);
-  const double scale = massNormalization ? 0.25 / (kappa * kappa) : 1.0;  // lib/eigsolve_mugiq.cpp:302
-  for (int v0 = 0; v0 < nEv; v0 += kOpBlock) {
-    const int n = std::min(kOpBlock, nEv - v0);
-    const unsigned active = (1u << n) - 1u;
-    for (int i = 0; i < n; i++)
-      if ((st = copy_body(vc[i], eVecs_h[v0 + i], s))) return st;
-    if ((st = apply_op(c, w, vc, n, opType, scale, tmp))) return st;
-    double sums[kOpBlock * 3];
-    if ((st = dot_norm(c, vc, w, n, active, red_d, sums))) return st;
-    VecArgs A{};
-    for (int i = 0; i < n; i++) {
-      const double nrm = std::sqrt(sums[3 * i + 2]);  // lambda = v^dag A v / ||v||   (:303, not ||v||^2)
-      lambda_h[2 * (v0 + i)] = sums[3 * i] / nrm;
-      lambda_h[2 * (v0 + i) + 1] = sums[3 * i + 1] / nrm;
-      A.a[i] = vc[i].data;
-      A.b[i] = w[i].data;
-      A.s[i] = lambda_h[2 * (v0 + i)];
-      A.s2[i] = lambda_h[2 * (v0 + i) + 1];
-    }
-    A.active = active;
-    if ((st = launch_reduce<1>(c, A, vc[0], n, red_d))) return st;
-    if ((st = fetch_sums(c, red_d, reduction_groups(vc[0]), active, sums))) return st;
-    for (int i = 0; i < n; i++) {
-      residual_h[v0 + i] = std::sqrt(sums[3 * i]);  // r = ||lambda v - A v||   (:305-306)
-      if (normal_op(opType)) sigma_h[v0 + i] = std::sqrt(lambda_h[2 * (v0 + i)]);  // :311
-      else if (opType == MUGIQ_HIP_EIG_OPERATOR_H) sigma_h[v0 + i] = lambda_h[2 * (v0 + i)];
-    }
-  }
-  return MUGIQ_HIP_SUCCESS;
+  const double scale = mass_scale(massNormalization, kappa);
+  static_assert(kEvBlock == kOpBlock, "a block of the check is a block of the stencil and of the reductions");
+  return check_eigenpairs(
+      nEv, opType, lambda_h, residual_h, sigma_h,
+      [&](int v0, int n) -> int {
+        for (int i = 0; i < n; i++)
+          if (int rc = copy_body(vc[i], eVecs_h[v0 + i], s)) return rc;
+        return apply_op(c, w, vc, n, opType, scale, tmp);
+      },
+      [&](int, int n, double *sums) { return dot_norm(c, vc, w, n, (1u << n) - 1u, red_d, sums); },
+      [&](int, int n, const double *lambda, double *sums) -> int {
+        VecArgs A{};
+        for (int i = 0; i < n; i++) {
+          A.a[i] = vc[i].data;
+          A.b[i] = w[i].data;
+          A.s[i] = lambda[2 * i];
+          A.s2[i] = lambda[2 * i + 1];
+        }
+        A.active = (1u << n) - 1u;
+        if (int rc = launch_reduce<1>(c, A, vc[0], n, red_d)) return rc;
+        return fetch_sums(c, red_d, reduction_groups(vc[0]), A.active, sums);
+      });
 }
 
 extern "C" {
