@@ -296,17 +296,7 @@ int deflate_low_modes(const MugiqHipSpinorField *dst, const MugiqHipSpinorField 
   }
   MUGIQ_REQUIRE(same_layout(src[0], ev[0]), "%s: src / dst and the eigenvectors differ in field order, geometry, stride or parity offset",
                 who);
-  for (int r = 0; r < nVec; r++) {
-    uintptr_t a0, a1;
-    spinor_span(dst[r], &a0, &a1);
-    for (int q = 0; q < nVec; q++) {
-      uintptr_t b0, b1;
-      spinor_span(src[q], &b0, &b1);
-      const bool overlap = a0 < b1 && b0 < a1;
-      MUGIQ_REQUIRE(!overlap || (q == r && dst[r].data == src[r].data),
-                    "%s: dst vector %d overlaps src vector %d without being identical to it", who, r, q);
-    }
-  }
+  if ((st = check_disjoint(dst, nVec, "dst", src, nVec, "src", who, true, " without being identical to it"))) return st;
   const bool multi = comm != nullptr && comm->size > 1;
   if (comm) {
     MUGIQ_REQUIRE(comm->size >= 1 && comm->grid[3] >= 1, "%s: invalid comm (size %d)", who, comm->size);

@@ -33,6 +33,11 @@ int set_error(int status, const char *fmt, ...);
 // behind the previous kernel; calls on different streams (or threads, or Loop objects) never share one.
 // stream_scratch returns the table buffer itself (at least `bytes` large; the next upload_table of at most that size
 // on the same stream lands at the same address); stream_workspace is a second, independent buffer of the same arena.
+// Who may hold which: a reservation is good until the next request for the same buffer on the stream (a larger one moves it).  So a
+// solver or a check reserves once, before its first launch, and calls internal entries only: the stencil, the restrictions and the
+// prolongations below (stencil_apply, restrict_*, prolong_*) take their work memory from the caller and reserve nothing; they upload
+// tables, which live for the launches that follow.  coarse_apply alone keeps the intermediate of a normal form in stream_workspace: its
+// callers keep their own vectors in the operator workspace.
 int stream_scratch(void **ptr, size_t bytes, hipStream_t stream);
 int stream_workspace(void **ptr, size_t bytes, hipStream_t stream);
 int upload_table(void **dev, const void *host, size_t bytes, hipStream_t stream);
@@ -40,15 +45,17 @@ int upload_table(void **dev, const void *host, size_t bytes, hipStream_t stream)
 // double (tablePrecision 4 | 8).  sigmaPrecision 4: sigma rounded to float before it is inverted (the vector kernels over fp32 storage)
 int upload_vector_table(const void *const **L, const void **invSigma, const MugiqHipSpinorField *ev, const MugiqHipSpinorField *evL,
                         const double *sigma, int nVec, int sigmaPrecision, int tablePrecision, hipStream_t stream);
-// a third buffer of the arena, for the Wilson operator (csrc/wilson.hip): intermediate and solver vectors that must survive the
-// calls of the deflation and halo code in between, which use stream_workspace themselves
+// a third buffer of the arena, for the operators and solvers (csrc/wilson.hip, csrc/mg_solve.hip, the explicit coarse check of
+// csrc/restrict.hip): intermediate and solver vectors that must survive the calls of the deflation and halo code and of coarse_apply in
+// between, which use stream_workspace themselves.  Held by one public call at a time, which calls no other holder while it holds it
 int stream_operator_workspace(void **ptr, size_t bytes, hipStream_t stream);
 int release_stream_scratch(hipStream_t stream);
 size_t eo_dft_x_lds_bytes(int precision, const int localL[4], int nPx, int *redOffsetElems);  // momproj.hip
 int eo_dft_x_time_chunk(int precision, const int localL[4], int nPx);                            // momproj.hip: 0 = the fused x step does not apply
 int fill_identity_links(const MugiqHipSpinorField *f, hipStream_t stream);  // displace.hip
 // MUGIQ_HIP_DEBUG_POISON_LDS=1 (test aid): every compute entry point of the C ABI first overwrites the LDS of all CUs with NaN bit
-// patterns (mugiq_hip_debug_poison_lds), so that a kernel reading a cell it never wrote shows it in its result.
+// patterns (mugiq_hip_debug_poison_lds), so that a kernel reading a cell it never wrote shows it in its result.  A solver or a check
+// does the same in front of every stencil, restriction and prolongation of its own (the internal entries below do not)
 int debug_poison_lds_if_asked(hipStream_t stream);
 // MUGIQ_HIP_DEBUG_WIDE_INDEX=1 (test aid): the Krylov kernels of csrc/mg_solve.hip run in their int64_t instantiation whatever the size
 // of the field (otherwise only from 2^31 complex elements per vector on, 32 GiB, which no test reaches).  Read by every call of
@@ -114,6 +121,14 @@ int deflate_low_modes(const MugiqHipSpinorField *dst, const MugiqHipSpinorField 
 int validate_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseField *c0, const char *who);
 int validate_coarse_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseField *finer_h, const MugiqHipCoarseField *coarser_h, int nVec,
                              const char *who);
+// The transfers behind the validation of their extern "C" entries (mugiq_hip_prolongate_batched, ..._coarse_batched, csrc/prolong.hip;
+// mugiq_hip_restrict_batched, ..._coarse_batched, csrc/restrict.hip), for callers that validated their hierarchy up front.
+// prolong_batched runs the form select_prolong_form gives for `sw`; packed_ws: that form's workspaceBytes, the caller's
+int prolong_batched(const MugiqHipSpinorField *fine, const MugiqHipCoarseField *coarse, int nVec, const MugiqHipTransfer *T, const TransferSwitches &sw,
+                    void *packed_ws, hipStream_t stream);
+int prolong_coarse_batched(const MugiqHipCoarseField *out, const MugiqHipCoarseField *in, int nVec, const MugiqHipTransfer *T, hipStream_t stream);
+int restrict_batched(const MugiqHipCoarseField *coarse, const MugiqHipSpinorField *fine, int nVec, const MugiqHipTransfer *T, int gamma5, hipStream_t stream);
+int restrict_coarse_batched(const MugiqHipCoarseField *coarser, const MugiqHipCoarseField *finer, int nVec, const MugiqHipTransfer *T, hipStream_t stream);
 // csrc/coarse_op.hip: a finest-level transfer (validate_transfer against the coarse side it lays out itself) and the coarse operator built
 // from it: one precision, one n_vec, the operator on the transfer's coarse lattice.  T->V and op are the caller's to check first
 int validate_transfer_operator(const MugiqHipTransfer *T, const MugiqHipCoarseOperator *op, const char *who);
@@ -133,6 +148,21 @@ int coarse_apply(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src,
 // csrc/wilson.hip: the gauge field of an operator call against the local dims X and the partitioned axes; comm -> part[4]
 int check_gauge(const MugiqHipGaugeField *U, const int X[4], const int part[4], const char *who);
 int check_comm(const MugiqHipComm *comm, int part[4], bool needSums, const char *who);
+// ... and the stencil behind those checks.  OpContext: the operator of a call and where its halo exchange packs: stencil_send_bytes for
+// the most fields one stencil_apply of the call takes, laid out like `like` in precision prec (0 on a single domain: send may be NULL).
+// stencil_apply: dst_i = scale [g5] M^(dag) src_i for n fields of one layout; the ghost zones of src are exchanged first
+struct OpContext {
+  const MugiqHipGaugeField *U;
+  const MugiqHipComm *comm;
+  int part[4];
+  double kappa;
+  hipStream_t stream;
+  unsigned char *send;
+  const char *who;
+  const MugiqHipCloverField *clover = nullptr;  // NULL: the unimproved operator
+};
+size_t stencil_send_bytes(const MugiqHipSpinorField &like, int prec, const int part[4], int n);
+int stencil_apply(const OpContext &c, const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int n, int dagger, int gamma5, double scale);
 // csrc/clover.hip: descriptor bounds; X != NULL: and the geometry of the fields it is applied to
 int validate_clover(const MugiqHipCloverField *C, const int X[4], int volumeCB, const char *who);
 }  // namespace mugiq
@@ -386,6 +416,23 @@ bool same_geometry(const MugiqHipSpinorField &a, const MugiqHipSpinorField &b);
 inline void spinor_span(const MugiqHipSpinorField &f, uintptr_t *a, uintptr_t *b) {
   *a = reinterpret_cast<uintptr_t>(f.data);
   *b = *a + (uintptr_t)(f.parity_offset + (int64_t)12 * f.stride) * 2 * f.precision;
+}
+// no a_i shares a byte with a b_j (b NULL: with an a_j, j < i).  identicalOk: a_i may be b_i itself, body on body.  The message names
+// the two sets and ends in `note`
+inline int check_disjoint(const MugiqHipSpinorField *a, int na, const char *aName, const MugiqHipSpinorField *b, int nb, const char *bName,
+                          const char *who, bool identicalOk = false, const char *note = "") {
+  for (int i = 0; i < na; i++) {
+    uintptr_t a0, a1;
+    spinor_span(a[i], &a0, &a1);
+    for (int j = 0; j < (b ? nb : i); j++) {
+      const MugiqHipSpinorField &o = b ? b[j] : a[j];
+      uintptr_t b0, b1;
+      spinor_span(o, &b0, &b1);
+      MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1) || (identicalOk && j == i && a[i].data == o.data), "%s: %s vector %d overlaps %s vector %d%s", who, aName, i,
+                    bName, j, note);
+    }
+  }
+  return MUGIQ_HIP_SUCCESS;
 }
 // [first, last) bytes of a coarse field's body (csrc/coarse_op.hip, csrc/coarse_eig.hip)
 inline void coarse_span(const MugiqHipCoarseField &f, uintptr_t *a, uintptr_t *b) {

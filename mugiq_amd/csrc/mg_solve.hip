@@ -1,7 +1,7 @@
 // A flexible GCR on the fine Wilson(-clover) operator, preconditioned by one two-grid cycle K: MR smoothing and a coarse-grid correction
 // through R, a fixed number of GCR steps on the explicit coarse operator, and P.  Definitions (MR step, GCRfix, K, the outer solve), limits
-// and work memory: mugiq_hip_mg_solve in include/mugiq_hip.h.  The stencil, R, P and the coarse application are the library's own entry
-// points, called as they are; what is new here are the Krylov kernels between them, on every level.  With a second coarse level the
+// and work memory: mugiq_hip_mg_solve in include/mugiq_hip.h.  The stencil, R, P and the coarse application are the library's own, called
+// below their C entries (csrc/internal.h) on arguments checked once, up front; what is new here are the Krylov kernels between them, on every level.  With a second coarse level the
 // level-1 solve becomes a flexible GCR preconditioned by a cycle of its own through the coarsest operator (K^(3), the *_levels entry
 // points).  The coarse levels are a chain (MgCoarse, MgSolver::coarse): MgSolver::cycle is K with the level abstracted, its correction
 // restricts to the next level, solves there (MgSolver::solve: GCRfix on the last level, the flexible GCR above it) and prolongs back.
@@ -431,9 +431,14 @@ template <typename F> struct MgSolver {
   const MugiqHipMgSolveParam *params;
   int nGiven;
   hipStream_t stream;
+  const char *who;
   int nb, nDirFine, sets;
   int nCoarse;  // coarse levels in use (init): level l is, when every cycle above it takes its coarse step
   size_t fb;
+  OpContext stencil;          // M of this solver on the single domain check_problem admits: no halo exchange, no send buffer
+  TransferSwitches switches;  // as the call found them (init)
+  size_t packedBytes;         // of `packed`, the packed coarse vectors of P_0 for nb vectors (ProlongForm::workspaceBytes)
+  void *packed;
   MgLevel<F> fine;
   MgCoarse<F> coarse[kMgMaxCoarse];
   // r: the solver's recursive residual (mixed solve, F = float: its rounded copy); zk: K's result before it is widened (mixed solve only)
@@ -461,12 +466,13 @@ template <typename F> struct MgSolver {
       if ((mask >> i) & 1u) out[m++] = set[i];
     return m;
   }
-  // dst_i = M src_i for the active i: the batched stencil as it is
+  // dst_i = M src_i for the active i: the batched stencil as it is.  (This, R and P: the LDS poisoned in front, where asked)
   int apply_M(const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int n, unsigned active) const {
     MugiqHipSpinorField d[kMgBlock], sr[kMgBlock];
     const int m = gather(dst, n, active, d);
     gather(src, n, active, sr);
-    return mugiq_hip_wilson_clover_apply(d, sr, m, gauge, clover, kappa, MUGIQ_HIP_EIG_OPERATOR_M, 1.0, nullptr, stream);
+    if (int e = debug_poison_lds_if_asked(stream)) return e;
+    return stencil_apply(stencil, d, sr, m, 0, 0, 1.0);
   }
   // dst_i = A src_i for the active i, A the explicit operator of a coarse level
   int apply_coarse(const MugiqHipCoarseOperator *A, const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src, int n, unsigned active) const {
@@ -477,33 +483,35 @@ template <typename F> struct MgSolver {
   }
   // c_i = R f_i and f_i = P c_i through T, from and into the fine level or a coarse one: all that tells level 0 from the others in a cycle
   int restrict_to(const MugiqHipCoarseField *c, const MugiqHipSpinorField *f, int n, const MugiqHipTransfer *T) const {
-    return mugiq_hip_restrict_batched(c, f, n, T, 0, stream);
+    if (int e = debug_poison_lds_if_asked(stream)) return e;
+    return restrict_batched(c, f, n, T, 0, stream);
   }
   int restrict_to(const MugiqHipCoarseField *c, const MugiqHipCoarseField *f, int n, const MugiqHipTransfer *T) const {
-    return mugiq_hip_restrict_coarse_batched(c, f, n, T, stream);
+    if (int e = debug_poison_lds_if_asked(stream)) return e;
+    return restrict_coarse_batched(c, f, n, T, stream);
   }
   int prolong_from(const MugiqHipSpinorField *f, const MugiqHipCoarseField *c, int n, const MugiqHipTransfer *T) const {
-    return mugiq_hip_prolongate_batched(f, c, n, T, stream);
+    if (int e = debug_poison_lds_if_asked(stream)) return e;
+    return prolong_batched(f, c, n, T, switches, packed, stream);
   }
   int prolong_from(const MugiqHipCoarseField *f, const MugiqHipCoarseField *c, int n, const MugiqHipTransfer *T) const {
-    return mugiq_hip_prolongate_coarse_batched(f, c, n, T, stream);
+    if (int e = debug_poison_lds_if_asked(stream)) return e;
+    return prolong_coarse_batched(f, c, n, T, stream);
   }
 
-  // The work memory is carved from the stream's operator workspace: the scalars, then per right-hand side of a block 2 nDirFine fine
+  // The work memory is carved from the stream's operator workspace: the scalars, the prolongator's packed coarse vectors (where a coarse
+  // level is in use), then per right-hand side of a block 2 nDirFine fine
   // directions and the fine vectors of `sets` (K: s, t, w; the solver: r as well), and per coarse level in use 2 nDir directions, x and
   // r, and s, t, w of the level's own cycle where a deeper level follows (three levels: s, t, w of K_1 on level 1; level 2 only for
   // params[1].coarseIters > 0).  init() fixes the layouts and sizes (vectors laid out like `like`, stored as Cplx<F>); carve() is the one
   // statement of the layout: it places this solver's share, and run without a workspace it counts it (place()).  The mixed solve carves
-  // two solvers from one reservation.
-  // apply_M calls the public stencil entry, which reserves the SAME arena for itself (csrc/wilson.hip, wilson_apply_impl) and takes its
-  // start as the send buffer of its halo exchange.  That is safe here for two reasons, both of which this file depends on: on a single
-  // domain with the form M its request is 256 bytes, so the arena, which only ever grows, neither moves nor is freed under us; and
-  // without a partitioned axis nothing is packed into that send buffer.  The first kStencilHead bytes are left unused all the same, so
-  // that a send buffer that did get written would not land in `partial`.
-  static constexpr size_t kStencilHead = 4096;
+  // two solvers from one reservation.  Nothing the solver calls reserves the arena again: the stencil and the transfers are the internal
+  // entries, which work in what they are handed (the prolongator in `packed`), and coarse_apply with the form M takes no work memory.
   void init(const MugiqHipSpinorField &like, int nDirFine_, int nVecRhs, int sets_, bool withCoarse) {
     nb = std::min(nVecRhs, kMgBlock);
     nDirFine = nDirFine_, sets = sets_;
+    stencil = OpContext{gauge, nullptr, {0, 0, 0, 0}, kappa, stream, nullptr, who, clover};
+    switches = transfer_switches_from_env();
     fineLike = like;
     fineLike.precision = (int)sizeof(F);
     fineLike.data = nullptr;
@@ -522,6 +530,8 @@ template <typename F> struct MgSolver {
       c.bytes = coarse_bytes<F>(c.like);
       c.lv.set(stream, nb, wide, coarse_layout(c.like), c.bytes);
     }
+    // (only the finest transfer has a packed form: the coarse -> coarse prolongator takes no work memory)
+    packedBytes = nCoarse ? align256(select_prolong_form(transfers[0], (int)sizeof(F), like.field_order, nb, switches).workspaceBytes) : 0;
   }
   // this solver's vectors from ws + off on, ws the start of the scalars; returns the offset behind them.  ws NULL: nothing is placed,
   // the offsets are the same
@@ -537,6 +547,7 @@ template <typename F> struct MgSolver {
       return p;
     };
     if (ws) fine.set_scalars(ws);
+    packed = take(packedBytes);
     fine.P = reinterpret_cast<C *>(take((size_t)nDirFine * nb * fb));
     fine.Q = reinterpret_cast<C *>(take((size_t)nDirFine * nb * fb));
     MugiqHipSpinorField *all[5] = {s, t, w, r, zk};
@@ -563,8 +574,8 @@ template <typename F> struct MgSolver {
   // size of the reservation, once on it
   template <typename Walk> static int place(hipStream_t stream, const Walk &walk) {
     void *ws = nullptr;
-    if (int st = stream_operator_workspace(&ws, kStencilHead + walk(nullptr) + 256, stream)) return st;
-    walk(static_cast<unsigned char *>(ws) + kStencilHead);
+    if (int st = stream_operator_workspace(&ws, walk(nullptr) + 256, stream)) return st;
+    walk(static_cast<unsigned char *>(ws));
     return MUGIQ_HIP_SUCCESS;
   }
   // one solver alone on the workspace
@@ -746,21 +757,8 @@ int check_problem(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in,
   MUGIQ_REQUIRE(op->kappa == kappa, "%s: the coarse operator was built for kappa = %.17g, the call has kappa = %.17g", who, op->kappa, kappa);
   MUGIQ_REQUIRE((op->hasClover != 0) == (clover != nullptr), "%s: the coarse operator was built %s a clover field, the call is %s one", who,
                 op->hasClover ? "with" : "without", clover ? "with" : "without");
-  for (int i = 0; i < nVec; i++) {
-    uintptr_t a0, a1;
-    spinor_span(out[i], &a0, &a1);
-    for (int j = 0; j < i; j++) {
-      uintptr_t b0, b1;
-      spinor_span(out[j], &b0, &b1);
-      MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: %s vector %d overlaps %s vector %d", who, outName, i, outName, j);
-    }
-    for (int j = 0; j < nVec; j++) {
-      uintptr_t b0, b1;
-      spinor_span(in[j], &b0, &b1);
-      MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: %s vector %d overlaps %s vector %d", who, outName, i, inName, j);
-    }
-  }
-  return MUGIQ_HIP_SUCCESS;
+  if ((st = check_disjoint(out, nVec, outName, nullptr, 0, outName, who))) return st;
+  return check_disjoint(out, nVec, outName, in, nVec, inName, who);
 }
 
 // check_problem for a hierarchy of L = nCoarseLevels coarse levels: level 0 as above with params_h[0]; for every l >= 1 also
@@ -898,7 +896,7 @@ int precondition_levels(const MugiqHipSpinorField *z_h, const MugiqHipSpinorFiel
   if ((st = check_levels(z_h, r_h, nVec, "z", "r", gauge, clover, transfers_h, coarseOps_h, nCoarseLevels, params_h, kappa, comm, who, prec, prec))) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
-  MgSolver<F> S{gauge, clover, kappa, transfers_h, coarseOps_h, params_h, nCoarseLevels, s};
+  MgSolver<F> S{gauge, clover, kappa, transfers_h, coarseOps_h, params_h, nCoarseLevels, s, who};
   if ((st = S.reserve(r_h[0], 0, nVec, false))) return st;
   for (int v0 = 0; v0 < nVec; v0 += kMgBlock) {
     const int n = std::min(kMgBlock, nVec - v0);
@@ -919,7 +917,7 @@ int solve_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h,
                 param->maxIter);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
-  MgSolver<double> S{gauge, clover, kappa, transfers_h, coarseOps_h, params_h, nCoarseLevels, s};
+  MgSolver<double> S{gauge, clover, kappa, transfers_h, coarseOps_h, params_h, nCoarseLevels, s, who};
   if ((st = S.reserve(b_h[0], param->nKrylov, nVec, true))) return st;
   return outer_solve(S, nullptr, x_h, b_h, nVec, param, iters_out, relres_out, history_out, historyStride, hostReads_out, who);
 }
@@ -954,8 +952,8 @@ int solve_mixed_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField
   if ((st = debug_poison_lds_if_asked(s))) return st;
   // the outer iteration: 2 nKrylov directions, r and t (for the true residual) in fp64; the cycle: r and z rounded, s, t, w and the coarse
   // levels in fp32.  One reservation, the scalars shared: the stream orders every pass
-  MgSolver<double> S{gauge, clover, kappa, transfersSloppy_h, coarseOpsSloppy_h, params_h, nCoarseLevels, s};
-  MgSolver<float> K{gaugeSloppy ? gaugeSloppy : gauge, gaugeSloppy ? cloverSloppy : clover, kappa, transfersSloppy_h, coarseOpsSloppy_h, params_h, nCoarseLevels, s};
+  MgSolver<double> S{gauge, clover, kappa, transfersSloppy_h, coarseOpsSloppy_h, params_h, nCoarseLevels, s, who};
+  MgSolver<float> K{gaugeSloppy ? gaugeSloppy : gauge, gaugeSloppy ? cloverSloppy : clover, kappa, transfersSloppy_h, coarseOpsSloppy_h, params_h, nCoarseLevels, s, who};
   S.init(b_h[0], param->nKrylov, nVec, kMgSetT | kMgSetR, false);
   K.init(b_h[0], 0, nVec, kMgSetsOfK | kMgSetR | kMgSetZ, true);
   if ((st = MgSolver<double>::place(s, [&](unsigned char *ws) { return K.carve(ws, S.carve(ws, scalar_bytes())); }))) return st;
@@ -1057,15 +1055,7 @@ int mugiq_hip_mg_convert_precision(const MugiqHipSpinorField *dst_h, const Mugiq
   MUGIQ_REQUIRE(dst_h[0].field_order == src_h[0].field_order && dst_h[0].volumeCB == src_h[0].volumeCB && dst_h[0].nParity == src_h[0].nParity,
                 "%s: dst and src differ in field order or geometry", who);
   for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(dst_h[0].X[d] == src_h[0].X[d], "%s: dst X[%d] = %d, src %d", who, d, dst_h[0].X[d], src_h[0].X[d]);
-  for (int i = 0; i < nVec; i++) {
-    uintptr_t a0, a1;
-    spinor_span(dst_h[i], &a0, &a1);
-    for (int j = 0; j < nVec; j++) {
-      uintptr_t b0, b1;
-      spinor_span(src_h[j], &b0, &b1);
-      MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: dst vector %d overlaps src vector %d", who, i, j);
-    }
-  }
+  if ((st = check_disjoint(dst_h, nVec, "dst", src_h, nVec, "src", who))) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const MgLayout Ld = fine_layout(dst_h[0]), Ls = fine_layout(src_h[0]);
   const bool wide = debug_wide_index_asked();

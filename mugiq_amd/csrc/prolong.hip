@@ -1047,9 +1047,10 @@ template <int NV> __global__ __launch_bounds__(64 * kPmWaves) void prolong_mfma_
   }
 }
 
-// The matrix-pipe form of a ProlongForm of that family (fp64 FLOAT2 fine fields, n_vec 8 | 16 | 24, aggregates of a multiple of 16 sites)
+// The matrix-pipe form of a ProlongForm of that family (fp64 FLOAT2 fine fields, n_vec 8 | 16 | 24, aggregates of a multiple of 16 sites);
+// packed_ws: form.workspaceBytes for the packed coarse vectors
 static int launch_prolong_mfma(const ProlongForm &form, const MugiqHipTransfer *T, const MugiqHipCoarseField *coarse, const MugiqHipSpinorField *fine,
-                               int nVec, hipStream_t stream) {
+                               int nVec, void *packed_ws, hipStream_t stream) {
   const int NV = T->nVec;
   ProlongMfmaArgs a;
   a.V = static_cast<const Cplx<double> *>(T->V);
@@ -1071,9 +1072,7 @@ static int launch_prolong_mfma(const ProlongForm &form, const MugiqHipTransfer *
   int st = upload_table(&dev, host.data(), sizeof(void *) * host.size(), stream);
   if (st) return st;
   a.table = reinterpret_cast<const void *const *>(dev);
-  void *ws = nullptr;
-  if ((st = stream_workspace(&ws, form.workspaceBytes, stream))) return st;  // the packed coarse vectors
-  a.packed = static_cast<const Cplx<double> *>(ws);
+  a.packed = static_cast<const Cplx<double> *>(packed_ws);
   const int nVec16 = (a.nVec8 + 15) / 16;  // (tiles of 16 eigenvectors; the last one may be half empty)
   hipLaunchKernelGGL(coarse_pack_kernel, dim3((unsigned)((a.volumeCBc + 15) / 16), (unsigned)(2 * NV), (unsigned)(2 * nVec16)), dim3(256), 0, stream, a, NV);
   MUGIQ_CHECK_HIP(hipGetLastError());
@@ -1121,6 +1120,24 @@ int validate_coarse_transfer(const MugiqHipTransfer *T, const MugiqHipCoarseFiel
   return MUGIQ_HIP_SUCCESS;
 }
 
+int prolong_batched(const MugiqHipSpinorField *fine, const MugiqHipCoarseField *coarse, int nVec, const MugiqHipTransfer *T, const TransferSwitches &sw,
+                    void *packed_ws, hipStream_t s) {
+  const ProlongForm form = select_prolong_form(*T, T->precision, fine[0].field_order, nVec, sw);
+  if (form.family == MUGIQ_HIP_PROLONG_FAMILY_MFMA) return launch_prolong_mfma(form, T, coarse, fine, nVec, packed_ws, s);
+  const bool staged = form.family == MUGIQ_HIP_PROLONG_FAMILY_VECTOR_STAGED;
+  switch (10 * form.precision + form.order) {
+  case 82: return launch_prolong<double, double, 2, true, false>(form, staged, T, coarse, fine, nullptr, nullptr, nVec, s);
+  case 84: return launch_prolong<double, double, 4, true, false>(form, staged, T, coarse, fine, nullptr, nullptr, nVec, s);
+  case 42: return launch_prolong<float, float, 2, true, false>(form, staged, T, coarse, fine, nullptr, nullptr, nVec, s);
+  default: return launch_prolong<float, float, 4, true, false>(form, staged, T, coarse, fine, nullptr, nullptr, nVec, s);
+  }
+}
+
+int prolong_coarse_batched(const MugiqHipCoarseField *out, const MugiqHipCoarseField *in, int nVec, const MugiqHipTransfer *T, hipStream_t s) {
+  if (T->precision == 8) return launch_prolong_coarse<double>(out, in, nVec, T, s);
+  return launch_prolong_coarse<float>(out, in, nVec, T, s);
+}
+
 }  // namespace mugiq
 
 using namespace mugiq;
@@ -1143,15 +1160,12 @@ int mugiq_hip_prolongate_batched(const MugiqHipSpinorField *fine_h, const MugiqH
   MUGIQ_REQUIRE(fine_h[0].precision == transfer->precision, "%s: fine precision %d != transfer precision %d", who, fine_h[0].precision, transfer->precision);
   for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(fine_h[0].X[d] == transfer->X[d], "%s: fine X[%d] mismatch", who, d);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const ProlongForm form = select_prolong_form(*transfer, transfer->precision, fine_h[0].field_order, nVec, transfer_switches_from_env());
-  if (form.family == MUGIQ_HIP_PROLONG_FAMILY_MFMA) return launch_prolong_mfma(form, transfer, coarse_h, fine_h, nVec, s);
-  const bool staged = form.family == MUGIQ_HIP_PROLONG_FAMILY_VECTOR_STAGED;
-  switch (10 * form.precision + form.order) {
-  case 82: return launch_prolong<double, double, 2, true, false>(form, staged, transfer, coarse_h, fine_h, nullptr, nullptr, nVec, s);
-  case 84: return launch_prolong<double, double, 4, true, false>(form, staged, transfer, coarse_h, fine_h, nullptr, nullptr, nVec, s);
-  case 42: return launch_prolong<float, float, 2, true, false>(form, staged, transfer, coarse_h, fine_h, nullptr, nullptr, nVec, s);
-  default: return launch_prolong<float, float, 4, true, false>(form, staged, transfer, coarse_h, fine_h, nullptr, nullptr, nVec, s);
-  }
+  // the packed coarse vectors of the matrix pipe: the head of the stream's workspace (the other families take none)
+  const TransferSwitches sw = transfer_switches_from_env();
+  const ProlongForm form = select_prolong_form(*transfer, transfer->precision, fine_h[0].field_order, nVec, sw);
+  void *packed = nullptr;
+  if (form.family == MUGIQ_HIP_PROLONG_FAMILY_MFMA && (st = stream_workspace(&packed, form.workspaceBytes, s))) return st;
+  return prolong_batched(fine_h, coarse_h, nVec, transfer, sw, packed, s);
 }
 
 int mugiq_hip_prolongate_coarse_batched(const MugiqHipCoarseField *out_h, const MugiqHipCoarseField *in_h, int nVec,
@@ -1159,9 +1173,7 @@ int mugiq_hip_prolongate_coarse_batched(const MugiqHipCoarseField *out_h, const 
   if (int dbg_ = mugiq::debug_poison_lds_if_asked(static_cast<hipStream_t>(stream))) return dbg_;
   const char *who = "prolongateEvec(coarse level)";
   if (int st = validate_coarse_transfer(T, out_h, in_h, nVec, who)) return st;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (T->precision == 8) return launch_prolong_coarse<double>(out_h, in_h, nVec, T, s);
-  return launch_prolong_coarse<float>(out_h, in_h, nVec, T, s);
+  return prolong_coarse_batched(out_h, in_h, nVec, T, static_cast<hipStream_t>(stream));
 }
 
 int mugiq_hip_prolongate_contract_batched(void *loopData_d, int loopPrecision, const MugiqHipCoarseField *coarse_h,

@@ -174,23 +174,6 @@ int validate_restrict(const MugiqHipCoarseField *coarse_h, const MugiqHipSpinorF
   return MUGIQ_HIP_SUCCESS;
 }
 
-int restrict_batched(const MugiqHipCoarseField *coarse, const MugiqHipSpinorField *fine, int nVec, const MugiqHipTransfer *T, int gamma5,
-                     hipStream_t s) {
-  const int pv = T->precision, pf = fine[0].precision, o = fine[0].field_order;
-#define MUGIQ_RS_CASE(PV_, PF_, O_, FV_, FS_) \
-  if (pv == PV_ && pf == PF_ && o == O_) return launch_restrict<FV_, FS_, O_>(coarse, fine, nVec, T, gamma5, s);
-  MUGIQ_RS_CASE(8, 8, 2, double, double)
-  MUGIQ_RS_CASE(8, 8, 4, double, double)
-  MUGIQ_RS_CASE(8, 4, 2, double, float)
-  MUGIQ_RS_CASE(8, 4, 4, double, float)
-  MUGIQ_RS_CASE(4, 8, 2, float, double)
-  MUGIQ_RS_CASE(4, 8, 4, float, double)
-  MUGIQ_RS_CASE(4, 4, 2, float, float)
-  MUGIQ_RS_CASE(4, 4, 4, float, float)
-#undef MUGIQ_RS_CASE
-  return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "restrictVecs: precision %d / %d, field order %d", pv, pf, o);
-}
-
 // ---- coarse -> coarse levels ------------------------------------------------------------------------------------------------
 // coarser(X; s, j) = sum_{x in X} sum_{c < nColor(finer)} conj(V(x; s, c, j)) finer(x; s, c): sites of the block in lexicographic
 // order, colours ascending inside a site
@@ -263,12 +246,6 @@ int launch_restrict_coarse(const MugiqHipCoarseField *coarser, const MugiqHipCoa
   hipLaunchKernelGGL((restrict_coarse_kernel<F>), grid, dim3(128), 0, stream, a);
   MUGIQ_CHECK_HIP(hipGetLastError());
   return MUGIQ_HIP_SUCCESS;
-}
-
-int restrict_coarse_batched(const MugiqHipCoarseField *coarser, const MugiqHipCoarseField *finer, int nVec, const MugiqHipTransfer *T,
-                            hipStream_t s) {
-  if (T->precision == 8) return launch_restrict_coarse<double>(coarser, finer, nVec, T, s);
-  return launch_restrict_coarse<float>(coarser, finer, nVec, T, s);
 }
 
 // ---- deflation through the coarse space ---------------------------------------------------------------------------------------
@@ -474,6 +451,29 @@ int validate_hierarchy(const MugiqHipTransfer *transfers, int nLevels, const Mug
 
 }  // namespace
 
+int restrict_batched(const MugiqHipCoarseField *coarse, const MugiqHipSpinorField *fine, int nVec, const MugiqHipTransfer *T, int gamma5,
+                     hipStream_t s) {
+  const int pv = T->precision, pf = fine[0].precision, o = fine[0].field_order;
+#define MUGIQ_RS_CASE(PV_, PF_, O_, FV_, FS_) \
+  if (pv == PV_ && pf == PF_ && o == O_) return launch_restrict<FV_, FS_, O_>(coarse, fine, nVec, T, gamma5, s);
+  MUGIQ_RS_CASE(8, 8, 2, double, double)
+  MUGIQ_RS_CASE(8, 8, 4, double, double)
+  MUGIQ_RS_CASE(8, 4, 2, double, float)
+  MUGIQ_RS_CASE(8, 4, 4, double, float)
+  MUGIQ_RS_CASE(4, 8, 2, float, double)
+  MUGIQ_RS_CASE(4, 8, 4, float, double)
+  MUGIQ_RS_CASE(4, 4, 2, float, float)
+  MUGIQ_RS_CASE(4, 4, 4, float, float)
+#undef MUGIQ_RS_CASE
+  return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "restrictVecs: precision %d / %d, field order %d", pv, pf, o);
+}
+
+int restrict_coarse_batched(const MugiqHipCoarseField *coarser, const MugiqHipCoarseField *finer, int nVec, const MugiqHipTransfer *T,
+                            hipStream_t s) {
+  if (T->precision == 8) return launch_restrict_coarse<double>(coarser, finer, nVec, T, s);
+  return launch_restrict_coarse<float>(coarser, finer, nVec, T, s);
+}
+
 int deflate_low_modes_coarse(const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int nVec, const MugiqHipCoarseField *ev,
                              const double *sigma, int nEv, const MugiqHipTransfer *transfers, int nLevels, int gamma5, double *overlaps_h,
                              const MugiqHipComm *comm, hipStream_t stream, const char *who) {
@@ -494,16 +494,7 @@ int deflate_low_modes_coarse(const MugiqHipSpinorField *dst, const MugiqHipSpino
                   "%s: src / dst vector %d differs in precision, field order or geometry from src vector 0", who, r);
   }
   for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(src[0].X[d] == transfers[0].X[d], "%s: src X[%d] = %d, the finest transfer's is %d", who, d, src[0].X[d], transfers[0].X[d]);
-  for (int r = 0; r < nVec; r++) {
-    uintptr_t a0, a1;
-    spinor_span(dst[r], &a0, &a1);
-    for (int q = 0; q < nVec; q++) {
-      uintptr_t b0, b1;
-      spinor_span(src[q], &b0, &b1);
-      const bool overlap = a0 < b1 && b0 < a1;
-      MUGIQ_REQUIRE(!overlap || (q == r && dst[r].data == src[r].data), "%s: dst vector %d overlaps src vector %d without being identical to it", who, r, q);
-    }
-  }
+  if ((st = check_disjoint(dst, nVec, "dst", src, nVec, "src", who, true, " without being identical to it"))) return st;
   const bool multi = comm != nullptr && comm->size > 1;
   if (comm) {
     MUGIQ_REQUIRE(comm->size >= 1 && comm->grid[3] >= 1, "%s: invalid comm (size %d)", who, comm->size);
@@ -577,8 +568,10 @@ int deflate_low_modes_coarse(const MugiqHipSpinorField *dst, const MugiqHipSpino
   if (P == 8) hipLaunchKernelGGL((coarse_combine_kernel<double>), cgrid, dim3(kCoThreads), 0, stream, W_d, Y_d, nEv, nVec, g, D);
   else hipLaunchKernelGGL((coarse_combine_kernel<float>), cgrid, dim3(kCoThreads), 0, stream, W_d, Y_d, nEv, nVec, g, D);
   MUGIQ_CHECK_HIP(hipGetLastError());
-  for (int l = nLevels - 1; l >= 1; l--)
-    if ((st = mugiq_hip_prolongate_coarse_batched(y[l - 1].data(), y[l].data(), nVec, &transfers[l], stream))) return st;
+  for (int l = nLevels - 1; l >= 1; l--) {
+    if ((st = debug_poison_lds_if_asked(stream))) return st;
+    if ((st = prolong_coarse_batched(y[l - 1].data(), y[l].data(), nVec, &transfers[l], stream))) return st;
+  }
   return prolong_subtract(dst, y[0].data(), nVec, &transfers[0], stream);
 }
 
@@ -686,10 +679,15 @@ int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipT
   }
   if ((st = debug_poison_lds_if_asked(stream))) return st;
 
-  // ---- work memory (per-stream workspace): [room for the prolongator's packed coarse vectors][2 x 8 fine vectors with ghost zones]
-  // [2 x 8 coarse vectors on every level][lambda and sums]
+  // ---- work memory (per-stream workspace): [the prolongator's packed coarse vectors][the send buffer of the stencil's halo exchange]
+  // [2 x 8 fine vectors with ghost zones][2 x 8 coarse vectors on every level][lambda and sums]
   const size_t P = (size_t)T0.precision;
-  const size_t head = align256(select_prolong_form(T0, T0.precision, 2, kEvBlock, TransferSwitches{}).workspaceBytes);  // (the same under every switch)
+  const TransferSwitches sw = transfer_switches_from_env();
+  MugiqHipSpinorField like{};  // a fine work vector, without a body
+  like.precision = (int)P, like.field_order = 2, like.nParity = 2, like.volumeCB = like.stride = g0.volumeCB, like.parity_offset = (int64_t)12 * g0.volumeCB;
+  for (int d = 0; d < 4; d++) like.X[d] = T0.X[d];
+  const size_t packedBytes = align256(select_prolong_form(T0, T0.precision, like.field_order, kEvBlock, sw).workspaceBytes);
+  const size_t sendBytes = align256(stencil_send_bytes(like, (int)P, part, kEvBlock));
   const size_t fineBody = align256((size_t)24 * g0.volumeCB * 2 * P);
   size_t zone[4], fineBytes = fineBody;
   for (int d = 0; d < 4; d++) {
@@ -697,7 +695,7 @@ int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipT
     fineBytes += 2 * zone[d];
   }
   std::vector<size_t> levBytes(nLevels);
-  size_t bytes = head + 2 * kEvBlock * fineBytes;
+  size_t bytes = packedBytes + sendBytes + 2 * kEvBlock * fineBytes;
   for (int l = 0; l < nLevels; l++) {
     levBytes[l] = align256((size_t)2 * lev[l].parity_offset * 2 * P);
     bytes += 2 * kEvBlock * levBytes[l];
@@ -705,22 +703,20 @@ int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipT
   const size_t scalOff = bytes;
   bytes += sizeof(double) * 5 * kEvBlock;
   void *ws = nullptr;
-  if ((st = stream_workspace(&ws, bytes, stream))) return st;  // (later, smaller requests of the prolongator get the same buffer)
-  unsigned char *cur = static_cast<unsigned char *>(ws) + head;
+  if ((st = stream_workspace(&ws, bytes, stream))) return st;
+  unsigned char *const packed = static_cast<unsigned char *>(ws), *cur = packed + packedBytes + sendBytes;
+  const OpContext stencil{gauge, comm, {part[0], part[1], part[2], part[3]}, kappa, stream, packed + packedBytes, who, clover};
   MugiqHipSpinorField F[2][kEvBlock];
   for (int k = 0; k < 2; k++)
     for (int i = 0; i < kEvBlock; i++) {
-      MugiqHipSpinorField f{};
+      MugiqHipSpinorField f = like;
       f.data = cur;
       cur += fineBody;
-      f.precision = (int)P, f.field_order = 2, f.nParity = 2, f.volumeCB = f.stride = g0.volumeCB, f.parity_offset = (int64_t)12 * g0.volumeCB;
-      for (int d = 0; d < 4; d++) {
-        f.X[d] = T0.X[d];
+      for (int d = 0; d < 4; d++)
         for (int b = 0; b < 2; b++) {
           f.ghost[d][b] = part[d] ? cur : nullptr;
           cur += zone[d];
         }
-      }
       F[k][i] = f;
     }
   // C[l][0]: the vectors in transit on level l + 1; on the coarsest level C[..][0] = A_c w and C[..][1] = the intermediate of a normal form
@@ -734,18 +730,20 @@ int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipT
   const int L = nLevels;
   const double scale = mass_scale(massNormalization, kappa);
 
-  // out = s R [g5] M^(dag) P in: up through the levels, one batched stencil call (its halo exchange included), down again
+  // out = s R [g5] M^(dag) P in: up through the levels, one batched stencil (its halo exchange included), down again.  The LDS is
+  // poisoned (where asked) in front of every step up and of the stencil
   auto simple = [&](const MugiqHipCoarseField *out, const MugiqHipCoarseField *in, int n, int dagger, int gamma5, double s) -> int {
     int rc;
     const MugiqHipCoarseField *c = in;
     for (int l = L - 1; l >= 1; l--) {
-      if ((rc = mugiq_hip_prolongate_coarse_batched(C[l - 1].data(), c, n, &transfers[l], stream))) return rc;
+      if ((rc = debug_poison_lds_if_asked(stream))) return rc;
+      if ((rc = prolong_coarse_batched(C[l - 1].data(), c, n, &transfers[l], stream))) return rc;
       c = C[l - 1].data();
     }
-    if ((rc = mugiq_hip_prolongate_batched(F[0], c, n, &T0, stream))) return rc;
-    if ((rc = mugiq_hip_wilson_clover_apply(F[1], F[0], n, gauge, clover, kappa, dagger ? MUGIQ_HIP_EIG_OPERATOR_MDAG : MUGIQ_HIP_EIG_OPERATOR_M, s, comm,
-                                            stream)))
-      return rc;
+    if ((rc = debug_poison_lds_if_asked(stream))) return rc;
+    if ((rc = prolong_batched(F[0], c, n, &T0, sw, packed, stream))) return rc;
+    if ((rc = debug_poison_lds_if_asked(stream))) return rc;
+    if ((rc = stencil_apply(stencil, F[1], F[0], n, dagger, 0, s))) return rc;
     if ((rc = restrict_batched(L == 1 ? out : C[0].data(), F[1], n, &T0, gamma5, stream))) return rc;
     for (int l = 1; l < L; l++)
       if ((rc = restrict_coarse_batched(l == L - 1 ? out : C[l].data(), C[l - 1].data(), n, &transfers[l], stream))) return rc;

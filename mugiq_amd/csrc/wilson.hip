@@ -427,22 +427,13 @@ void carve_fields(unsigned char **cur, const MugiqHipSpinorField &like, int prec
   }
 }
 
-struct OpContext {
-  const MugiqHipGaugeField *U;
-  const MugiqHipComm *comm;
-  int part[4];
-  double kappa;
-  hipStream_t stream;
-  unsigned char *send;  // kOpBlock * ghost_bytes
-  const char *who;
-  const MugiqHipCloverField *clover = nullptr;  // NULL: the unimproved operator
-};
-
 bool same_layout(const MugiqHipSpinorField &a, const MugiqHipSpinorField &b) {
   return same_geometry(a, b) && a.stride == b.stride && a.parity_offset == b.parity_offset;
 }
 
 }  // namespace
+
+size_t stencil_send_bytes(const MugiqHipSpinorField &like, int prec, const int part[4], int n) { return (size_t)n * ghost_bytes(like, prec, part); }
 
 int check_gauge(const MugiqHipGaugeField *U, const int X[4], const int part[4], const char *who) {
   MUGIQ_REQUIRE(U != nullptr && U->data != nullptr, "%s: gauge field is NULL", who);
@@ -546,8 +537,9 @@ int launch_stencil(const OpContext &c, const MugiqHipSpinorField *dst, const Mug
   return MUGIQ_HIP_SUCCESS;
 }
 
-// dst_i = scale [g5] M^(dag) src_i for n <= kOpBlock fields of one layout; the ghost zones of src are exchanged first
-int apply_simple(const OpContext &c, const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int n, int dagger, int gamma5, double scale) {
+}  // namespace
+
+int stencil_apply(const OpContext &c, const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int n, int dagger, int gamma5, double scale) {
   if (n <= 0) return MUGIQ_HIP_SUCCESS;
   int st = exchange_block(c, src, n);
   if (st) return st;
@@ -569,10 +561,12 @@ int apply_simple(const OpContext &c, const MugiqHipSpinorField *dst, const Mugiq
   return set_error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "%s: precision %d / field order %d", c.who, prec, order);
 }
 
+namespace {
+
 // any form; tmp: n fields with ghost zones for the intermediate of the two normal operators
 int apply_op(const OpContext &c, const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int n, int opType, double scale,
              const MugiqHipSpinorField *tmp) {
-  return apply_form(opType, [&c](auto... a) { return apply_simple(c, a...); }, dst, src, tmp, n, scale);
+  return apply_form(opType, [&c](auto... a) { return stencil_apply(c, a...); }, dst, src, tmp, n, scale);
 }
 
 int reduction_groups(const MugiqHipSpinorField &f) { return std::min(kRedMaxGroups, (2 * f.volumeCB + kRedThreads - 1) / kRedThreads); }
@@ -669,15 +663,7 @@ static int wilson_apply_impl(const MugiqHipSpinorField *dst_h, const MugiqHipSpi
   if ((st = check_vector_set(src_h, nVec, who, "src"))) return st;
   if ((st = check_vector_set(dst_h, nVec, who, "dst"))) return st;
   MUGIQ_REQUIRE(same_layout(dst_h[0], src_h[0]), "%s: dst and src differ in precision, field order, geometry, stride or parity offset", who);
-  for (int i = 0; i < nVec; i++) {
-    uintptr_t a0, a1;
-    spinor_span(dst_h[i], &a0, &a1);
-    for (int j = 0; j < nVec; j++) {
-      uintptr_t b0, b1;
-      spinor_span(src_h[j], &b0, &b1);
-      MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: dst vector %d overlaps src vector %d (the kernel reads neighbours of src)", who, i, j);
-    }
-  }
+  if ((st = check_disjoint(dst_h, nVec, "dst", src_h, nVec, "src", who, false, " (the kernel reads neighbours of src)"))) return st;
   if ((st = check_comm(comm, part, false, who))) return st;
   if ((st = check_gauge(gauge, src_h[0].X, part, who))) return st;
   if ((st = check_clover(clover, src_h[0], gauge, who))) return st;
@@ -689,7 +675,7 @@ static int wilson_apply_impl(const MugiqHipSpinorField *dst_h, const MugiqHipSpi
   if ((st = debug_poison_lds_if_asked(s))) return st;
   // workspace: [send buffers of a block][intermediate fields of a block, for the two normal operators]
   const int prec = src_h[0].precision;
-  const size_t sendB = (size_t)kOpBlock * ghost_bytes(src_h[0], prec, part);
+  const size_t sendB = stencil_send_bytes(src_h[0], prec, part, kOpBlock);
   const size_t tmpB = normal_op(opType) ? (size_t)kOpBlock * (body_bytes(src_h[0], prec) + ghost_bytes(src_h[0], prec, part)) : 0;
   void *ws = nullptr;
   if ((st = stream_operator_workspace(&ws, sendB + tmpB + 256, s))) return st;
@@ -720,7 +706,7 @@ static int compute_evals_impl(const MugiqHipSpinorField *eVecs_h, int nEv, const
   // normal operator), whatever nEv
   const MugiqHipSpinorField &e0 = eVecs_h[0];
   const int prec = e0.precision;
-  const size_t sendB = (size_t)kOpBlock * ghost_bytes(e0, prec, part);
+  const size_t sendB = stencil_send_bytes(e0, prec, part, kOpBlock);
   const size_t fieldB = body_bytes(e0, prec) + ghost_bytes(e0, prec, part);
   void *ws = nullptr;
   if ((st = stream_operator_workspace(&ws, sendB + 3 * kOpBlock * fieldB + reduction_bytes(e0) + 256, s))) return st;
@@ -791,15 +777,7 @@ static int wilson_solve_impl(const MugiqHipSpinorField *x_h, const MugiqHipSpino
   if ((st = check_vector_set(x_h, nVec, who, "x"))) return st;
   MUGIQ_REQUIRE(b_h[0].precision == 8, "%s: x and b must be fp64 fields", who);
   MUGIQ_REQUIRE(same_layout(x_h[0], b_h[0]), "%s: x and b differ in precision, field order, geometry, stride or parity offset", who);
-  for (int i = 0; i < nVec; i++) {
-    uintptr_t a0, a1;
-    spinor_span(x_h[i], &a0, &a1);
-    for (int j = 0; j < nVec; j++) {
-      uintptr_t b0, b1;
-      spinor_span(b_h[j], &b0, &b1);
-      MUGIQ_REQUIRE(!(a0 < b1 && b0 < a1), "%s: x vector %d overlaps b vector %d", who, i, j);
-    }
-  }
+  if ((st = check_disjoint(x_h, nVec, "x", b_h, nVec, "b", who))) return st;
   std::vector<double> negSigma((size_t)nEv);
   for (int n = 0; n < nEv; n++) {
     MUGIQ_REQUIRE(sigma_h[n] != 0.0, "%s: sigma[%d] is zero", who, n);
@@ -813,7 +791,7 @@ static int wilson_solve_impl(const MugiqHipSpinorField *x_h, const MugiqHipSpino
   if ((st = debug_poison_lds_if_asked(s))) return st;
   // work memory: r, p, t = M p, q = M^dag t for a block of kOpBlock right-hand sides (fp64, with ghost zones), whatever nVec
   const MugiqHipSpinorField &b0 = b_h[0];
-  const size_t sendB = (size_t)kOpBlock * ghost_bytes(b0, 8, part);
+  const size_t sendB = stencil_send_bytes(b0, 8, part, kOpBlock);
   const size_t fieldB = body_bytes(b0, 8) + ghost_bytes(b0, 8, part);
   void *ws = nullptr;
   if ((st = stream_operator_workspace(&ws, sendB + 4 * kOpBlock * fieldB + reduction_bytes(b0) + 256, s))) return st;
@@ -844,8 +822,8 @@ static int wilson_solve_impl(const MugiqHipSpinorField *x_h, const MugiqHipSpino
     const int m = gather(p, n, mask, pa);
     gather(t, n, mask, ta);
     gather(q, n, mask, qa);
-    if (int e = apply_simple(c, ta, pa, m, 0, 0, 1.0)) return e;
-    return apply_simple(c, qa, ta, m, 1, 0, 1.0);
+    if (int e = stencil_apply(c, ta, pa, m, 0, 0, 1.0)) return e;
+    return stencil_apply(c, qa, ta, m, 1, 0, 1.0);
   };
 
   for (int v0 = 0; v0 < nVec; v0 += kOpBlock) {
@@ -859,7 +837,7 @@ static int wilson_solve_impl(const MugiqHipSpinorField *x_h, const MugiqHipSpino
       bnorm2[i] = sums[3 * i + 2];
       if ((st = copy_body(p[i], b[i], s))) return st;
     }
-    if ((st = apply_simple(c, r, p, n, 1, 0, 1.0))) return st;
+    if ((st = stencil_apply(c, r, p, n, 1, 0, 1.0))) return st;
     if ((st = dot_norm(c, r, r, n, all, red_d, sums))) return st;
     for (int i = 0; i < n; i++) rhs2[i] = sums[3 * i + 2];
     // start vector: zero, or the low-mode part x0 = sum_n v_n sigma_n^-1 (v_n^dag g5 b), and then r -= M^dag M x0
@@ -919,7 +897,7 @@ static int wilson_solve_impl(const MugiqHipSpinorField *x_h, const MugiqHipSpino
     // the true residual ||b - M x|| / ||b||, with one more application
     for (int i = 0; i < n; i++)
       if ((st = copy_body(p[i], x[i], s))) return st;
-    if ((st = apply_simple(c, t, p, n, 0, 0, 1.0))) return st;
+    if ((st = stencil_apply(c, t, p, n, 0, 0, 1.0))) return st;
     if ((st = lincomb(c, t, b, one, t, minus, n, all))) return st;
     if ((st = dot_norm(c, t, t, n, all, red_d, sums))) return st;
     for (int i = 0; i < n; i++) {
