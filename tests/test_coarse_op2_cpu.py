@@ -2,7 +2,10 @@
 R_1 R_0 [g5] M^(dag) P_0 P_1 of tests/restrict_ref.py, the normal forms to products of these, the recipe of mgSetupCoarse to its exact
 property (P_1 R_1 w = w, and the coarsest MdagM keeps the eigenvalues of the vectors that went into V); the three new entry points are
 declared and exported, return every validation error before any device work (the descriptors point at nothing), the Python layer
-checks its arguments and the C++ mirror compiles against the C ABI."""
+checks its arguments and the C++ mirror compiles against the C ABI.  The launch geometry of coarse_build2_kernel (panels of K, their
+widths, the LDS) is restated in tests/coarse_op2_cases.py: here the restatement is held to the text of csrc/coarse_op2.hip, every kernel
+case to the regimes it is there for, the case table to the combinations of regimes that matter, and the reference of every case beyond
+one panel to the chain R_1 M_c P_1."""
 import ctypes
 import os
 import subprocess
@@ -47,10 +50,139 @@ def test_reference_normal_forms_are_products():
 
 def test_reference_keeps_forward_and_backward_apart():
     """coarsest extent 2 everywhere and extent 2 on the input lattice: Y'+ and Y'- are different matrices, both needed"""
-    X, bs, nc, nv = cases.KERNEL_CASES[0]
+    X, bs, nc, nv = cases.KERNEL_CASES[0][:4]
     M = cases.kernel_reference(X, bs, nc, nv)
     for mu in range(4):
         assert np.max(np.abs(M[:, :, 1 + 2 * mu] - M[:, :, 2 + 2 * mu])) > 1e-3 * np.max(np.abs(M))
+
+
+# ---- the launch geometry of coarse_build2_kernel: the restatement, the case table and what it reaches -----------------------------------
+# the cases beyond one panel of K, with the widths worked out by hand from the panel rule: (X1, bs, nc, nv) -> pk, panels, LDS bytes
+MULTI_PANEL = {((4, 2, 2, 2), (2, 1, 1, 1), 40, 24): (34, [34, 6], 65536),
+               ((4, 2, 2, 2), (2, 1, 1, 1), 37, 35): (20, [20, 17], 64480),
+               ((4, 2, 2, 2), (2, 1, 1, 1), 40, 40): (11, [11, 11, 11, 7], 65280),
+               ((4, 2, 2, 2), (2, 1, 1, 1), 32, 48): (12, [12, 12, 8], 64512),
+               ((8, 2, 2, 2), (4, 1, 1, 1), 48, 48): (8, [8] * 6, 86016),
+               ((4, 4, 2, 2), (2, 2, 1, 1), 64, 64): (8, [8] * 8, 147456),
+               ((2, 2, 2, 2), (1, 1, 1, 1), 64, 64): (8, [8] * 8, 147456)}
+SINGLE_PANEL = {((4, 2, 2, 2), (2, 1, 1, 1), 4, 3): 4, ((8, 2, 2, 2), (4, 1, 1, 1), 2, 3): 2, ((8, 4, 2, 2), (2, 2, 1, 1), 5, 6): 5,
+                ((4, 4, 4, 4), (2, 2, 2, 2), 24, 32): 24, ((4, 2, 2, 2), (2, 1, 1, 1), 33, 4): 33, ((4, 2, 2, 2), (2, 1, 1, 1), 5, 33): 5}
+
+
+def _source():
+    return open(os.path.join(ROOT, "mugiq_amd", "csrc", "coarse_op2.hip")).read()
+
+
+def pin_to_source(text):
+    """the constants and the panel rule of the kernel's source text against the restatement in tests/coarse_op2_cases.py"""
+    import re
+    consts = {k: int(v) for k, v in re.findall(r"^constexpr int (kC2\w+) = (\d+);", text, flags=re.M)}
+    assert consts == dict(kC2Threads=cases.C2_THREADS, kC2Tile=cases.C2_TILE, kC2MaxN=cases.C2_MAX_N, kC2MinPanel=cases.C2_MIN_PANEL,
+                          kC2LdsTarget=cases.C2_LDS_TARGET), consts
+    rule = re.findall(r"^int build2_panel\(int nc, int nv\) \{ return (.*); \}$", text, flags=re.M)
+    assert rule == [cases.BUILD2_PANEL_EXPR], rule
+    lds = re.findall(r"^size_t build2_lds_elems\(int nc, int nv, int pk\) \{ return (.*); \}$", text, flags=re.M)
+    assert lds == ["(size_t)2 * nc * nv + (size_t)pk * (nc + nv)"], lds
+    assert "a.pk = build2_panel(a.nc, a.nv);" in text and "sizeof(Cplx<double>) * build2_lds_elems(a.nc, a.nv, a.pk)" in text
+    assert "if (ldsBytes > 64 * 1024)" in open(os.path.join(ROOT, "mugiq_amd", "csrc", "mg_common.h")).read()
+
+
+def test_geometry_restatement_is_the_kernels():
+    """kC2Threads, kC2Tile, kC2MaxN, kC2MinPanel, kC2LdsTarget, the expression of build2_panel and of the LDS size as csrc/coarse_op2.hip
+    has them; an edit of any of them in a copy of the text is noticed (so a change of the panel rule fails here and the case table is
+    looked at again)"""
+    text = _source()
+    pin_to_source(text)
+    for old, new in (("kC2LdsTarget = 4096;", "kC2LdsTarget = 8192;"), ("kC2MinPanel = 8;", "kC2MinPanel = 4;"),
+                     ("(kC2LdsTarget - 2 * nc * nv) / (nc + nv)", "(kC2LdsTarget - 2 * nc * nv) / (nc + nv) & ~3")):
+        assert old in text
+        with pytest.raises(AssertionError):
+            pin_to_source(text.replace(old, new))
+
+
+def test_geometry_restatement_by_hand():
+    """build2_geometry against widths worked out by hand; more than one panel exactly when nc^2 + 3 nc nv > 4096, over the whole range;
+    the panels tile [0, nc) and the LDS stays under the 160 KB of a workgroup"""
+    for (X, bs, nc, nv), (pk, panels, lds) in MULTI_PANEL.items():
+        g = cases.build2_geometry(X, bs, nc, nv)
+        assert (g["pk"], g["panels"], g["lds"]) == (pk, panels, lds), (nc, nv, g)
+    for (X, bs, nc, nv), pk in SINGLE_PANEL.items():
+        g = cases.build2_geometry(X, bs, nc, nv)
+        assert (g["pk"], g["panels"]) == (pk, [pk]) and pk == nc, (nc, nv, g)
+    assert cases.build2_geometry((8, 4, 4, 4), (2, 1, 1, 1), 36, 36)["panels"] == [20, 16]          # the wide chain of the GPU tests
+    for nc in range(1, 65):
+        for nv in range(1, 65):
+            g = cases.build2_geometry((4, 2, 2, 2), (2, 1, 1, 1), nc, nv)
+            assert sum(g["panels"]) == nc and all(0 < w <= g["pk"] for w in g["panels"]) and g["lds"] <= 160 * 1024
+            assert (len(g["panels"]) > 1) == (nc * nc + 3 * nc * nv > 4096), (nc, nv, g)
+            assert g["single_panel"] + g["even_panels"] + g["ragged_last_panel"] == 1
+    for nc, nv in ((33, 33), (32, 48), (40, 24), (48, 16)):
+        assert not cases.build2_geometry((4, 2, 2, 2), (2, 1, 1, 1), nc, nv)["single_panel"]
+    assert cases.build2_geometry((4, 2, 2, 2), (2, 1, 1, 1), 32, 32)["single_panel"]
+
+
+@pytest.mark.parametrize("case", cases.KERNEL_CASES, ids=lambda c: "%s-%s-%d-%d" % ("x".join(map(str, c[0])), "x".join(map(str, c[1])), c[2], c[3]))
+def test_each_case_reaches_what_it_is_there_for(case):
+    X, bs, nc, nv, purpose = case
+    assert purpose and purpose <= cases.regimes(X, bs, nc, nv), (purpose - cases.regimes(X, bs, nc, nv), cases.build2_geometry(X, bs, nc, nv))
+    # the lattice is one the entry point takes: even coarsest extents
+    assert all(X[d] % bs[d] == 0 and (X[d] // bs[d]) % 2 == 0 for d in range(4))
+
+
+def _reached(table, *names, also=lambda X, bs, nc, nv, g: True):
+    """the cases of the table that are THERE FOR every regime of names (and whose geometry satisfies `also`)"""
+    return [c[:4] for c in table if set(names) <= c[4] and also(*c[:4], cases.build2_geometry(*c[:4]))]
+
+
+def check_table(table, fp32):
+    """The regimes that meet in one launch: a ragged last panel and even panels, each with several terms and several sites per workgroup;
+    a ragged panel with nc no multiple of 4, with nc > nv and with nv > nc; the raised LDS attribute with several sites; both neighbours
+    inside with several panels; a ragged panel after more than one full one; the same ragged regime in fp32 storage.  And every case
+    beyond one panel that the widths were worked out for is in the table."""
+    assert _reached(table, "ragged_last_panel", "multi_term", "multi_site")
+    assert _reached(table, "even_panels", "multi_term", "multi_site")
+    assert _reached(table, "ragged_last_panel", "shadow_rows", also=lambda X, bs, nc, nv, g: nc % 4 != 0)
+    assert _reached(table, "ragged_last_panel", "cols_gt_rows")
+    assert _reached(table, "ragged_last_panel", "rows_gt_cols")
+    assert _reached(table, "lds_over_64k", "multi_site")
+    assert _reached(table, "both_neighbours_inside", also=lambda X, bs, nc, nv, g: len(g["panels"]) > 1)
+    assert _reached(table, "ragged_last_panel", also=lambda X, bs, nc, nv, g: len(g["panels"]) >= 4)
+    assert _reached(fp32, "ragged_last_panel", "multi_term", "multi_site")
+    assert _reached(fp32, "ragged_last_panel", "shadow_rows", also=lambda X, bs, nc, nv, g: nc % 4 != 0)
+    assert _reached(fp32, "single_panel")
+    have = {c[:4] for c in table}
+    assert set(MULTI_PANEL) | set(SINGLE_PANEL) <= have, (set(MULTI_PANEL) | set(SINGLE_PANEL)) - have
+    assert all(c in table for c in fp32)
+
+
+def test_the_table_reaches_every_combination():
+    """check_table on the tables as they are; without any one of the cases beyond one panel, or without the ragged fp32 cases, it fails"""
+    check_table(cases.KERNEL_CASES, cases.FP32_CASES)
+    for gone in MULTI_PANEL:
+        with pytest.raises(AssertionError):
+            check_table([c for c in cases.KERNEL_CASES if c[:4] != gone], [c for c in cases.FP32_CASES if c[:4] != gone])
+    with pytest.raises(AssertionError):
+        check_table(cases.KERNEL_CASES, cases.FP32_CASES[:2])
+
+
+@pytest.mark.parametrize("case", cases.KERNEL_CASES[:1] + [c for c in cases.KERNEL_CASES if c[:4] in MULTI_PANEL],
+                         ids=lambda c: "%s-%s-%d-%d" % ("x".join(map(str, c[0])), "x".join(map(str, c[1])), c[2], c[3]))
+def test_kernel_reference_equals_the_chain(case):
+    """coarse_op2_ref.build on the random dense K of a kernel case against the chain R_1 M_c P_1 (orc.prolongate, coarse_op_ref.apply_Mc,
+    restrict_ref.restrict) on random coarsest vectors, also daggered: 1e-13 relative in the max norm, the bound of the hierarchies above.
+    The numpy side is not trusted blindly at the widths of the multi-panel cases."""
+    X, bs, nc, nv = case[:4]
+    K, V = cases.kernel_inputs(X, bs, nc, nv)
+    M = cases.kernel_reference(X, bs, nc, nv)
+    Xc = cases.coarse_dims(X, bs)
+    rng = np.random.default_rng(31 + nc + nv)
+    for _ in range(2):
+        w = rng.standard_normal((2, M.shape[1], 2, nv)) + 1j * rng.standard_normal((2, M.shape[1], 2, nv))
+        for dagger in (False, True):
+            chain = rr.restrict(cor.apply_Mc(K, orc.prolongate(w, V, X, bs, 1), X, dagger=dagger), V, X, bs, 1)
+            e = rel_err(cor.apply_Mc(M, w, Xc, dagger=dagger), chain)
+            print("case %s dagger %d: %.2e" % (case[:4], dagger, e))
+            assert e < 1e-13, (dagger, e)
 
 
 def test_setup_recipe_preserves_the_eigenpairs_that_went_in():

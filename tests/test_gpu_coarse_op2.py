@@ -3,7 +3,9 @@ mugiq_hip_transfer_get_coarse_vector, eigsolve.mgSetupCoarse): the matrices agai
 pinned to the chain R_1 R_0 M P_0 P_1 in tests/test_coarse_op2_cpu.py) on random dense input operators, two known answers that need no
 numpy, the bitwise promises, the whole chain from a gauge field, the eigensolver on a second-level operator, the exact property of
 the setup recipe, and the end-to-end run.  Tolerances: 1e-12 relative in the max norm for fp64 (the bound of tests/test_gpu_coarse_op.py),
-2e-12 between two device routes; the fp32 bound is measured, not chosen."""
+2e-12 between two device routes; the fp32 bound is measured, not chosen.  coarse_build2_kernel passes K through LDS in panels whose
+width and number depend on the sizes at run time: every case says on the host which regime of coarse_op2_cases.build2_geometry it
+reaches before anything runs (the table's purposes are asserted in tests/test_coarse_op2_cpu.py)."""
 import functools
 import json
 import subprocess
@@ -72,24 +74,38 @@ def _v_logical(T):
     return T.V.cpu().numpy()[p * T.parity_offset + ((nc * s + c) * T.n_vec + j) * T.stride + x]
 
 
+def _case_id(c):
+    return "%s-%s-%d-%d" % ("x".join(map(str, c[0])), "x".join(map(str, c[1])), c[2], c[3])
+
+
+def _assert_regime(case):
+    """the case reaches what it is there for, said on the host before anything runs"""
+    X, bs, nc, nv, purpose = case
+    reached = cases.regimes(X, bs, nc, nv)
+    assert purpose <= reached, (case, purpose - reached)
+    return cases.build2_geometry(X, bs, nc, nv)
+
+
 def _kernel_problem(hip, case, prec=8, pad=0):
-    X, bs, nc, nv = case
+    X, bs, nc, nv = case[:4]
     K, V = cases.kernel_inputs(X, bs, nc, nv)
     return _operator_from(hip, K, X, nc, prec), _transfer_from(hip, V, X, bs, prec, pad)
 
 
 # ---- the matrices ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", cases.KERNEL_CASES, ids=lambda c: "%s-%s-%d-%d" % ("x".join(map(str, c[0])), "x".join(map(str, c[1])), c[2], c[3]))
+@pytest.mark.parametrize("case", cases.KERNEL_CASES, ids=_case_id)
 def test_matrices_match_numpy(hip, case, record_max):
     """Xd' and Y'+-_mu of every coarsest site from random dense matrices and a random V, fp64, to 1e-12 of the largest entry"""
-    X, bs, nc, nv = case
+    X, bs, nc, nv = case[:4]
+    g = _assert_regime(case)
+    print("case %s: panels %s, %d bytes of LDS, there for %s" % (case[:4], g["panels"], g["lds"], sorted(case[4])))
     finer, T = _kernel_problem(hip, case)
     op = hip.computeCoarseOperatorCoarse(T, finer)
     assert op.kappa == finer.kappa and op.hasClover == finer.hasClover and op.X == cases.coarse_dims(X, bs) and op.n_vec == nv
     got, want = op.get_logical(), cases.kernel_reference(X, bs, nc, nv)
     assert got.shape == want.shape == (2, op.volumeCB, 9, 2 * nv, 2 * nv)
     e = np.max(np.abs(got - want)) / np.max(np.abs(want))
-    print("case %s: %.3e" % (case, e))
+    print("case %s: %.3e" % (case[:4], e))
     record_max("coarse_op2_matrices", e)
     assert e < 1e-12, e
     for m in range(9):                                                            # every matrix against its own largest entry as well
@@ -97,18 +113,19 @@ def test_matrices_match_numpy(hip, case, record_max):
         assert em < 1e-12, (m, em)
 
 
-@pytest.mark.parametrize("case", cases.FP32_CASES, ids=["small", "production"])
+@pytest.mark.parametrize("case", cases.FP32_CASES, ids=["small", "production", "ragged-40-24", "ragged-37-35"])
 def test_matrices_fp32(hip, case, record_max):
     """Everything in precision 4 against the complex128 reference on the inputs as stored.  The bound is not chosen: 4 x the rounding of the
     stored reference (the project's margin for the device's own summation order, as test_fp32_hierarchy of tests/test_gpu_coarse_op.py)."""
-    X, bs, nc, nv = case
+    X, bs, nc, nv = case[:4]
+    _assert_regime(case)
     finer, T = _kernel_problem(hip, case, prec=4)
     op = hip.computeCoarseOperatorCoarse(T, finer)
     assert op.precision == 4 and op.data.dtype == torch.complex64
     M = cases.kernel_reference(X, bs, nc, nv, 4)
     em = np.max(np.abs(op.get_logical() - M)) / np.max(np.abs(M))
     scale = np.max(np.abs(M.astype(np.complex64).astype(np.complex128) - M)) / np.max(np.abs(M))
-    print("fp32 case %s: deviation %.3e, rounding of the stored reference %.3e" % (case, em, scale))
+    print("fp32 case %s: deviation %.3e, rounding of the stored reference %.3e" % (case[:4], em, scale))
     record_max("coarse_op2_matrices_fp32", em)
     record_max("coarse_op2_matrices_fp32_reference_scale", scale)
     assert em < 4.0 * scale, (em, scale)
@@ -117,8 +134,24 @@ def test_matrices_fp32(hip, case, record_max):
 # ---- two known answers that need no numpy -----------------------------------------------------------------------------------------------
 def test_identity_transfer_returns_the_input_bit_for_bit(hip):
     """Aggregate (1,1,1,1), nv = nc, V(x) the identity: every sum has one non-zero term, so the result is the input operator, bit for bit"""
-    X, bs, nc, _ = cases.KERNEL_CASES[2]
-    K, _ = cases.kernel_inputs(*cases.KERNEL_CASES[2])
+    X, bs, nc, _ = cases.KERNEL_CASES[2][:4]
+    K, _ = cases.kernel_inputs(*cases.KERNEL_CASES[2][:4])
+    finer = _operator_from(hip, K, X, nc)
+    V = np.zeros((2, int(np.prod(X)) // 2, 2, nc, nc), dtype=np.complex128)
+    V[..., np.arange(nc), np.arange(nc)] = 1.0
+    T = _transfer_from(hip, V, X, (1, 1, 1, 1), pad=3)
+    op = hip.computeCoarseOperatorCoarse(T, finer)
+    assert op.X == finer.X and _same(op.data, finer.data)
+
+
+def test_identity_transfer_across_panels(hip):
+    """The same known answer where K passes through LDS in four panels, the last one ragged: lattice 8.4.2.2, aggregate (1,1,1,1),
+    nc = nv = 40 (panels of 11, 11, 11 and 7 columns).  Every panel but the one that holds the column adds exact zeros, so the result is
+    still the input operator, bit for bit (its zeros included: the input has none that are negative)."""
+    X, nc = (8, 4, 2, 2), 40
+    g = cases.build2_geometry(X, (1, 1, 1, 1), nc, nc)
+    assert g["panels"] == [11, 11, 11, 7] and g["ragged_last_panel"] and not g["multi_site"] and not g["multi_term"]
+    K, _ = cases.kernel_inputs(X, (1, 1, 1, 1), nc, nc)
     finer = _operator_from(hip, K, X, nc)
     V = np.zeros((2, int(np.prod(X)) // 2, 2, nc, nc), dtype=np.complex128)
     V[..., np.arange(nc), np.arange(nc)] = 1.0
@@ -130,8 +163,8 @@ def test_identity_transfer_returns_the_input_bit_for_bit(hip):
 def test_unitary_transfer_keeps_the_eigenpair_check(hip, record_max):
     """Aggregate (1,1,1,1), nv = nc and a random unitary per site and chirality: M' = P^dag M_c P with P unitary, so computeEvalsCoarse of
     P^dag w on M' equals that of w on the input operator (2e-12: two device routes)"""
-    X, bs, nc, _ = cases.KERNEL_CASES[2]
-    K, _ = cases.kernel_inputs(*cases.KERNEL_CASES[2])
+    X, bs, nc, _ = cases.KERNEL_CASES[2][:4]
+    K, _ = cases.kernel_inputs(*cases.KERNEL_CASES[2][:4])
     finer = _operator_from(hip, K, X, nc)
     rng = np.random.default_rng(4242)
     vcb = int(np.prod(X)) // 2
@@ -178,6 +211,35 @@ def test_bitwise_promises(hip, monkeypatch):
     monkeypatch.setenv("MUGIQ_HIP_DEBUG_POISON_LDS", "1")
     g = hip.computeCoarseOperatorCoarse(T, finer)
     assert _same(f.data, g.data)
+
+
+@pytest.mark.parametrize("X,bs,nc,nv,regime", [((4, 2, 2, 2), (2, 1, 1, 1), 40, 24, "ragged_last_panel"), ((8, 2, 2, 2), (4, 1, 1, 1), 48, 48, "even_panels")],
+                         ids=["ragged-40-24", "even-48-48"])
+def test_bitwise_promises_across_panels(hip, monkeypatch, X, bs, nc, nv, regime):
+    """The same promises where a workgroup takes several panels, several terms and several sites: a ragged last panel ([34, 6]) and six
+    even ones above 64 KB of LDS.  Poisoned LDS is what would show a read of a stale column of the K panel or a stale row of the V panel
+    beyond the width of the last one; a race between terms would show as two builds that differ."""
+    g = cases.build2_geometry(X, bs, nc, nv)
+    assert g[regime] and g["multi_term"] and g["multi_site"] and len(g["panels"]) > 1, g
+    case = (X, bs, nc, nv)
+    finer, T = _kernel_problem(hip, case)
+    a = hip.computeCoarseOperatorCoarse(T, finer)
+    b = hip.computeCoarseOperatorCoarse(T, finer)
+    assert _same(a.data, b.data)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        c = hip.computeCoarseOperatorCoarse(T, finer)
+    s.synchronize()
+    assert _same(a.data, c.data)
+    _, Tp = _kernel_problem(hip, case, pad=5)
+    d = hip.computeCoarseOperatorCoarse(Tp, finer)
+    assert _same(a.data, d.data) and bool(torch.isfinite(torch.view_as_real(d.data)).all())
+    pads = _v_pads(Tp)
+    assert bool(torch.isnan(pads.real).all()) and bool(torch.isnan(pads.imag).all())
+    monkeypatch.setenv("MUGIQ_HIP_DEBUG_POISON_LDS", "1")
+    e = hip.computeCoarseOperatorCoarse(T, finer)
+    assert _same(a.data, e.data)
 
 
 # ---- V <-> coarse vectors ---------------------------------------------------------------------------------------------------------------
@@ -254,6 +316,33 @@ def test_chain_from_the_gauge_field(hip, clover, record_max):
         b = hip.computeEvalsCoarse(cw, [T0, T1], gauge, KAPPA, opType, clover=C)
         big = np.max(np.abs(b[0]))
         e = max(np.max(np.abs(a[0] - b[0])), np.max(np.abs(a[1] - b[1]))) / big
+        record_max("coarse_op2_chain_evals_vs_fine_route", e)
+        assert e < 2e-12, (opType, e)
+
+
+def test_chain_at_multi_panel_widths(hip, record_max):
+    """Fine 8.4.4.4, 2^4 aggregates with n_vec 36, then (2,1,1,1) with n_vec 36, Wilson-clover: the input of the second build is a real
+    Galerkin operator with its chirality structure, 72 x 72, and passes through LDS in panels of 20 and 16 columns, two sites and two terms
+    per workgroup of Xd'.  computeEvalsCoarse(coarseOp=op2) against the fine route computeEvalsCoarse(ev, [T0, T1], gauge, ...), which
+    uses neither explicit operator, in all five forms on 9 coarsest vectors (2e-12: two device routes)."""
+    h = cases.wide_chain()
+    g = cases.build2_geometry(h["X1"], h["bs1"], h["nv0"], h["nv1"])
+    assert g["panels"] == [20, 16] and g["ragged_last_panel"] and g["multi_term"] and g["multi_site"], g
+    gauge = hip.GaugeField(h["X"], (0, 0, 0, 0), 8).set_logical(h["Uo"])
+    C = hip.CloverField(h["X"], 8).set_logical(h["blocks"])
+    T0 = hip.Transfer(h["X"], h["nv0"], h["bs0"], 2, 8).set_logical(h["V0"])
+    T1 = _transfer_from(hip, h["V1"], h["X1"], h["bs1"])
+    op1 = hip.computeCoarseOperator(T0, gauge, KAPPA, clover=C)
+    op2 = hip.computeCoarseOperatorCoarse(T1, op1)
+    assert op2.X == h["X2"] and op2.n_vec == h["nv1"] and op2.kappa == KAPPA and op2.hasClover
+    cw = [hip.CoarseField(h["X2"], h["nv1"], 8).set_logical(w) for w in h["ws"]]
+    assert len(cw) == 9
+    for opType in range(5):
+        a = hip.computeEvalsCoarse(cw, opType=opType, coarseOp=op2)
+        b = hip.computeEvalsCoarse(cw, [T0, T1], gauge, KAPPA, opType, clover=C)
+        big = np.max(np.abs(b[0]))
+        e = max(np.max(np.abs(a[0] - b[0])), np.max(np.abs(a[1] - b[1]))) / big
+        print("opType %d: %.3e" % (opType, e))
         record_max("coarse_op2_chain_evals_vs_fine_route", e)
         assert e < 2e-12, (opType, e)
 
