@@ -981,6 +981,82 @@ int mugiq_hip_mg_solve_mixed_levels(const MugiqHipSpinorField *x_h, const MugiqH
                                     int *iters_out, double *relres_out, double *history_out, int historyStride, int *hostReads_out,
                                     const MugiqHipComm *comm, void *stream);
 
+/* ---- the deflated coarsest solve (new; csrc/mg_deflate.hip): the coarsest level of the MG solve seeded with the lowest eigenvectors of
+ * M_L^dag M_L, the vectors mugiq_hip_coarse_eigensolve computes on that level for the loops.  What QUDA's multigrid does with
+ * mg_param.use_eig_solver on its coarsest level (tests/loop.cpp:474, 813-820) and coarse_guess (tests/loop.cpp:592).  M_L is the explicit
+ * operator of the LAST coarse level given to a call, coarseOps_h[nCoarseLevels - 1]; only that level is deflated, the levels above it
+ * keep their flexible GCR.  It pays where the coarsest solve is the weak link of the cycle.
+ *
+ * The space.  w_n: orthonormal, the nEv lowest eigenvectors of M_L^dag M_L; u_n = M_L w_n / sigma_n with sigma_n = ||M_L w_n|| > 0, so
+ * that (sigma_n, u_n, w_n) are the lowest singular triplets of M_L.  mugiq_hip_coarse_deflation_build makes U and sigma from W.
+ *   GCRdefl(A, D, b, n):  c_n = <u_n, b>;  x0 = sum_n w_n (c_n / sigma_n);  r0 = b - sum_n u_n c_n  (n ascending in both);
+ *                         x = x0 + GCRfix(A, r0, n): the recurrence of mugiq_hip_mg_solve started from (x0, r0), its first update
+ *                         accumulating into x instead of assigning it.
+ * r0 is NOT recomputed as b - A x0: with exact triplets the two are equal, with approximate ones they differ by the order of the
+ * eigensolver's residual, and the outer GCR is flexible -- a preconditioner that is slightly off costs iterations, never accuracy.  So the
+ * projection applies no operator (x0 = W Theta^-1 W^dag A^dag b, r0 = b - A x0 would apply two).
+ * With a space, the last-level solve GCRfix(M_L, ., coarseIters) of every cycle above becomes GCRdefl(M_L, D, ., coarseIters); nothing else
+ * changes.  Where that level is never reached (params_h[0].coarseIters = 0, or params_h[1].coarseIters = 0 with two coarse levels) the space
+ * is checked but not read.
+ *
+ * The projection is two passes (csrc/mg_deflate.hip): the overlaps c[n][r] over element chunks x groups of eigenvectors, U read once per
+ * block of <= 8 right-hand sides, per-chunk partial sums added in ascending chunk order by a small kernel that also forms c_n / sigma_n;
+ * then one pass, one element per lane, that reads w_n and u_n once and writes both x0 and r0.  fp64 arithmetic in either storage, one
+ * rounding on the store, no atomics; the bits of c[n][r] depend on u_n, b_r and the field geometry alone -- not on nEv, nVec, the mask or
+ * the place in the batch.  Pads are neither read nor written; an inactive right-hand side is not touched. */
+typedef struct MugiqHipCoarseDeflation_s {
+  int nEv;                      /* 1 .. 1024, no multiple of anything */
+  const MugiqHipCoarseField *W; /* [nEv] w_n: lowest eigenvectors of M_L^dag M_L (what mugiq_hip_coarse_eigensolve returns for MdagM) */
+  const MugiqHipCoarseField *U; /* [nEv] u_n = M_L w_n / sigma_n, unit norm */
+  const double *sigma;          /* [nEv], host, sigma_n = ||M_L w_n|| > 0 */
+} MugiqHipCoarseDeflation;
+
+/* U_n = M_L W_n / sigma_n and sigma_n = ||M_L W_n|| for n < nEv: the application in blocks of 8, the norm by a fixed-order fp64 sum, one
+ * blocking read per block.  W, U and op of one precision (4 | 8); any strides, one for all W and one for all U; no U may overlap a W or
+ * another U.  A sigma_n that is 0 or not finite: MUGIQ_HIP_ERROR_INVALID_ARGUMENT with sigma_h filled (u_n is then left unscaled).  A
+ * single domain only.  Work memory: 64 KB of scalars in the per-stream operator workspace. */
+int mugiq_hip_coarse_deflation_build(const MugiqHipCoarseField *U_h, double *sigma_h, const MugiqHipCoarseField *W_h, int nEv,
+                                     const MugiqHipCoarseOperator *op, const MugiqHipComm *comm, void *stream);
+/* The projection alone: x0_i and r0_i of GCRdefl for b_i, i < nVec, in blocks of 8 -- the coarse guess, and the kernels without a solve.
+ * x0, r0 and b: 3 nVec distinct fields of the space's lattice, n_vec and precision, of one stride and parity offset; none may overlap a
+ * w_n or u_n.  A vector alone equals the same vector in any batch, bit for bit.  Work memory as below. */
+int mugiq_hip_coarse_deflate(const MugiqHipCoarseField *x0_h, const MugiqHipCoarseField *r0_h, const MugiqHipCoarseField *b_h, int nVec,
+                             const MugiqHipCoarseDeflation *space, const MugiqHipComm *comm, void *stream);
+/* The four *_levels entry points with a space: their argument lists plus `deflation` after params_h.  deflation == NULL IS the twin: the
+ * same code path, the same bits.  The space must live on the lattice and n_vec of coarseOps_h[nCoarseLevels - 1], in that hierarchy's
+ * precision (the mixed solve: the sloppy one, 4).
+ * Promises.  Every promise of the twins carries over: blocks of 8 right-hand sides with a mask, a converged one is not touched, one solved
+ * alone equals the same one in any batch bit for bit, two runs give identical bits, counts and histories, pads neither read nor written,
+ * fp64 sums in fp32 storage with one rounding on the store, K(2^k r) = 2^k K(r) bit for bit (the projection is linear and its scalars
+ * scale exactly).  Nothing is read back inside the cycle: hostReads stays max(iters of the block) + 2 per block of 8.
+ * Refused before any device work, beyond the refusals of the twins: nEv outside 1 .. 1024; NULL members; a w_n or u_n that differs from
+ * the last operator in lattice, n_vec or precision, or within its set in stride or parity offset; w_n or u_n overlapping each other or
+ * the call's fields; a sigma_n that is not positive and finite.
+ * Work memory, beyond that of the twin, in a buffer of its own carved from the per-stream operator workspace (not the Krylov scalars):
+ * sigma and the two body tables (3 nEv words), the coefficients c and c / sigma ([nEv][8] complex each) and the chunk partials
+ * ([nChunks][nEv][8] complex): 8 nEv (35 + 16 nChunks) bytes, nChunks = ceil(E / max(2048, 64 ceil(E / 16384))) <= 256 for E complex
+ * elements per vector (196 608 elements and 200 vectors: 96 chunks, 2.5 MB). */
+int mugiq_hip_mg_precondition_levels_deflated(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
+                                              const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfers_h,
+                                              const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h,
+                                              const MugiqHipCoarseDeflation *deflation, const MugiqHipComm *comm, void *stream);
+int mugiq_hip_mg_solve_levels_deflated(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                                       const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfers_h,
+                                       const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h,
+                                       const MugiqHipCoarseDeflation *deflation, int *iters_out, double *relres_out, double *history_out,
+                                       int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream);
+int mugiq_hip_mg_precondition_sloppy_levels_deflated(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec,
+                                                     const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover, double kappa,
+                                                     const MugiqHipTransfer *transfers_h, const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels,
+                                                     const MugiqHipMgSolveParam *params_h, const MugiqHipCoarseDeflation *deflation,
+                                                     const MugiqHipComm *comm, void *stream);
+int mugiq_hip_mg_solve_mixed_levels_deflated(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                                             const MugiqHipCloverField *clover, double kappa, const MugiqHipGaugeField *gaugeSloppy,
+                                             const MugiqHipCloverField *cloverSloppy, const MugiqHipTransfer *transfersSloppy_h,
+                                             const MugiqHipCoarseOperator *coarseOpsSloppy_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h,
+                                             const MugiqHipCoarseDeflation *deflation, int *iters_out, double *relres_out, double *history_out,
+                                             int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream);
+
 /* ---- MG setup (new; csrc/mg_setup.hip): what QUDA's newMultigridQuda does before MG_Mugiq / Eigsolve_Mugiq see a transfer
  * (tests/loop.cpp:347-365: setup_inv, setup_maxiter, setup_tol, num_setup_iter, n_block_ortho) -- from a gauge field to V and M_c.
  *

@@ -71,6 +71,11 @@ class MgSolveParam(ctypes.Structure):
                 ("omega", ctypes.c_double), ("coarseIters", ctypes.c_int)]
 
 
+class CoarseDeflationDesc(ctypes.Structure):
+    """MugiqHipCoarseDeflation (include/mugiq_hip.h)."""
+    _fields_ = [("nEv", ctypes.c_int), ("W", ctypes.POINTER(CoarseDesc)), ("U", ctypes.POINTER(CoarseDesc)), ("sigma", ctypes.POINTER(ctypes.c_double))]
+
+
 class BlockOrthoInfo(ctypes.Structure):
     """MugiqHipBlockOrthoInfo (include/mugiq_hip.h)."""
     _fields_ = [("minPivotRatio", ctypes.c_double), ("zeroColumns", ctypes.c_int)]
@@ -282,6 +287,24 @@ SIGNATURES = {
     "mugiq_hip_mg_solve_mixed_levels": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, _GP, _CP, ctypes.POINTER(TransferDesc),
                                                        ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int, ctypes.POINTER(MgSolveParam), _I4,
                                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_int, _I4, _VP, _VP]),
+    "mugiq_hip_coarse_deflation_build": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(CoarseDesc), ctypes.c_int,
+                                                        ctypes.POINTER(CoarseOperatorDesc), _VP, _VP]),
+    "mugiq_hip_coarse_deflate": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.POINTER(CoarseDesc), ctypes.POINTER(CoarseDesc), ctypes.c_int,
+                                                ctypes.POINTER(CoarseDeflationDesc), _VP, _VP]),
+    "mugiq_hip_mg_precondition_levels_deflated": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
+                                                                 ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int, ctypes.POINTER(MgSolveParam),
+                                                                 ctypes.POINTER(CoarseDeflationDesc), _VP, _VP]),
+    "mugiq_hip_mg_solve_levels_deflated": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
+                                                          ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int, ctypes.POINTER(MgSolveParam),
+                                                          ctypes.POINTER(CoarseDeflationDesc), _I4, ctypes.POINTER(ctypes.c_double),
+                                                          ctypes.POINTER(ctypes.c_double), ctypes.c_int, _I4, _VP, _VP]),
+    "mugiq_hip_mg_precondition_sloppy_levels_deflated": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
+                                                                        ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int, ctypes.POINTER(MgSolveParam),
+                                                                        ctypes.POINTER(CoarseDeflationDesc), _VP, _VP]),
+    "mugiq_hip_mg_solve_mixed_levels_deflated": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, _GP, _CP, ctypes.POINTER(TransferDesc),
+                                                                ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int, ctypes.POINTER(MgSolveParam),
+                                                                ctypes.POINTER(CoarseDeflationDesc), _I4, ctypes.POINTER(ctypes.c_double),
+                                                                ctypes.POINTER(ctypes.c_double), ctypes.c_int, _I4, _VP, _VP]),
     "mugiq_hip_mg_convert_precision": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _VP]),
     "mugiq_hip_transfer_convert": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.POINTER(TransferDesc), _VP]),
     "mugiq_hip_block_orthonormalize": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.c_int, ctypes.c_double, ctypes.POINTER(BlockOrthoInfo), _VP]),

@@ -5,6 +5,8 @@
 // level-1 solve becomes a flexible GCR preconditioned by a cycle of its own through the coarsest operator (K^(3), the *_levels entry
 // points).  The coarse levels are a chain (MgCoarse, MgSolver::coarse): MgSolver::cycle is K with the level abstracted, its correction
 // restricts to the next level, solves there (MgSolver::solve: GCRfix on the last level, the flexible GCR above it) and prolongs back.
+// With a deflation space for the last level (the *_levels_deflated entry points) its GCRfix starts from the projection on the space
+// (csrc/mg_deflate.hip, called through csrc/mg_common.h); without one nothing here takes another path.
 //
 // One set of kernels serves both levels and both storages: a field is a list of rows of complex numbers (MgLayout; fine FLOAT2: 12 rows of
 // volumeCB per parity, fine FLOAT4: 6 rows of 2 volumeCB, coarse: 2 n_vec rows of volumeCB_c) stored as Cplx<F>, F = double or float.  Every
@@ -30,7 +32,6 @@
 namespace mugiq {
 namespace {
 
-constexpr int kMgBlock = 8;       // right-hand sides per block
 constexpr int kMgMaxDir = 16;     // stored directions of a level
 constexpr int kMgThreads = 256;
 constexpr int kMgMaxGroups = 256; // workgroups of a pass per right-hand side: the partial sums mg_final_sum_kernel adds up
@@ -38,19 +39,6 @@ constexpr int kMgSlots = 32;      // doubles per right-hand side and workgroup: 
 static_assert(2 * (kMgMaxDir - 1) <= kMgSlots && kMgBlock * kMgSlots == kMgThreads, "mg_final_sum_kernel: one lane per (right-hand side, slot)");
 
 typedef Cplx<double> Z;
-
-struct MgLayout {
-  int nRows;
-  int64_t rowLen, rowStride, po, total;  // complex elements; total = 2 nRows rowLen
-};
-
-// complex offset of element e of a field: (parity, row, position in the row), rows in ascending order.  I: uint32_t where total < 2^31
-template <typename I> __device__ inline int64_t mg_offset(const MgLayout &L, I e) {
-  const I rowLen = (I)L.rowLen, per = (I)L.nRows * rowLen;
-  const int pty = e >= per ? 1 : 0;
-  const I rem = e - (pty ? per : (I)0), row = rem / rowLen;
-  return pty * L.po + (int64_t)row * L.rowStride + (int64_t)(rem - row * rowLen);
-}
 
 // v[0 .. nUsed) summed over the workgroup -> out[0 .. nUsed): down the wave by shuffles, then the four waves in ascending order
 template <int NS> __device__ inline void mg_group_sum(double (&v)[NS], int nUsed, double *out) {
@@ -68,10 +56,6 @@ template <int NS> __device__ inline void mg_group_sum(double (&v)[NS], int nUsed
   __syncthreads();
   if (t < nUsed) out[t] = ((sh[0][t] + sh[1][t]) + sh[2][t]) + sh[3][t];
 }
-
-template <typename F> struct MgVecs {
-  Cplx<F> *p[kMgBlock];
-};
 
 // multi-dot: c_j = <q_j, q_k> for all j < k, from the q_k the operator left (classical Gram-Schmidt): slots (2j, 2j + 1)
 template <typename F, typename I>
@@ -288,15 +272,6 @@ MgLayout fine_layout(const MugiqHipSpinorField &f) {
   L.total = 2 * L.nRows * L.rowLen;
   return L;
 }
-MgLayout coarse_layout(const MugiqHipCoarseField &f) {
-  MgLayout L;
-  L.nRows = f.nSpin * f.nColor;
-  L.rowLen = f.volumeCB;
-  L.rowStride = f.stride;
-  L.po = f.parity_offset;
-  L.total = 2 * L.nRows * L.rowLen;
-  return L;
-}
 // rows of V: a finest-level transfer has 12 n_vec of them per parity, a coarse -> coarse one parity_offset / stride (2 nc n_vec, no gap)
 MgLayout transfer_layout(const MugiqHipTransfer &T) {
   MgLayout L;
@@ -432,6 +407,7 @@ template <typename F> struct MgSolver {
   int nGiven;
   hipStream_t stream;
   const char *who;
+  const MugiqHipCoarseDeflation *deflation;  // of the last coarse level given (NULL: none); read only where that level is in use (init)
   int nb, nDirFine, sets;
   int nCoarse;  // coarse levels in use (init): level l is, when every cycle above it takes its coarse step
   size_t fb;
@@ -444,6 +420,10 @@ template <typename F> struct MgSolver {
   // r: the solver's recursive residual (mixed solve, F = float: its rounded copy); zk: K's result before it is widened (mixed solve only)
   MugiqHipSpinorField s[kMgBlock], t[kMgBlock], w[kMgBlock], r[kMgBlock], zk[kMgBlock];
   MugiqHipSpinorField fineLike;
+  bool deflated = false;     // the last-level solve is GCRdefl: a space was given and its level is in use
+  size_t deflBytes = 0;      // of deflMem, the space of this call on the device (CoarseDeflationWork, csrc/mg_common.h)
+  void *deflMem = nullptr;
+  CoarseDeflationWork defl;
 
   static Vecs vecs(const MugiqHipSpinorField *f, int n) {
     Vecs m{};
@@ -531,6 +511,8 @@ template <typename F> struct MgSolver {
       c.lv.set(stream, nb, wide, coarse_layout(c.like), c.bytes);
     }
     // (only the finest transfer has a packed form: the coarse -> coarse prolongator takes no work memory)
+    deflated = deflation != nullptr && nCoarse == nGiven;
+    deflBytes = deflated ? coarse_deflation_work_bytes(coarse[nCoarse - 1].like, deflation->nEv) : 0;
     packedBytes = nCoarse ? align256(select_prolong_form(transfers[0], (int)sizeof(F), like.field_order, nb, switches).workspaceBytes) : 0;
   }
   // this solver's vectors from ws + off on, ws the start of the scalars; returns the offset behind them.  ws NULL: nothing is placed,
@@ -568,7 +550,15 @@ template <typename F> struct MgSolver {
           csets[k][i].data = take(c.bytes);
         }
     }
+    // the deflation space of the call: sigma, the coefficients and the chunk partials live from one projection to the next launch that
+    // reads them, across the operator applications of the recurrence -- not for one launch as the scalars above, so they get a buffer of their own
+    deflMem = take(deflBytes);
     return off;
+  }
+  // once the workspace is placed: sigma and the body tables of the space go up, once per call
+  int upload_deflation() {
+    if (!deflated) return MUGIQ_HIP_SUCCESS;
+    return coarse_deflation_prepare(&defl, deflation, coarse[nCoarse - 1].like, deflMem, fine.wide, stream);
   }
   // walk(ws) carves the solvers of a call behind the scalars at ws and returns the bytes it walked: once without a workspace for the
   // size of the reservation, once on it
@@ -581,14 +571,18 @@ template <typename F> struct MgSolver {
   // one solver alone on the workspace
   int reserve(const MugiqHipSpinorField &like, int nDirFine_, int nVecRhs, bool withR) {
     init(like, nDirFine_, nVecRhs, kMgSetsOfK | (withR ? kMgSetR : 0), true);
-    return place(stream, [this](unsigned char *ws) { return carve(ws, scalar_bytes()); });
+    if (int st = place(stream, [this](unsigned char *ws) { return carve(ws, scalar_bytes()); })) return st;
+    return upload_deflation();
   }
 
-  // x = GCRfix(M_l, r, nDir) on the coarse level c for the active right-hand sides; r is used up
+  // x = GCRfix(M_l, r, nDir) on the coarse level c for the active right-hand sides; r is used up.  With a space: GCRdefl, the same
+  // recurrence started from the projection (x0, r0) of r, which takes r's place
   int gcr_fixed(const MgCoarse<F> &c, int n, unsigned active) const {
     MugiqHipCoarseField p[kMgBlock], q[kMgBlock];
     for (int i = 0; i < n; i++) p[i] = c.dir(c.lv.P, 0, i);
     const Vecs rv = vecs(c.r, n), xv = vecs(c.x, n), pv = vecs(p, n);
+    if (deflated)
+      if (int st = coarse_deflation_project(defl, c.x, c.r, c.r, n, active, (int)sizeof(F), stream)) return st;
     if (int st = c.lv.axpby(pv, &rv, 1.0, nullptr, 0.0, n, active)) return st;
     for (int k = 0; k < c.nDir; k++) {
       for (int i = 0; i < n; i++) {
@@ -596,7 +590,7 @@ template <typename F> struct MgSolver {
         q[i] = c.dir(c.lv.Q, k, i);
       }
       if (int st = apply_coarse(c.op, q, p, n, active)) return st;
-      if (int st = c.lv.gcr_step(k, xv, rv, k == 0, k + 1 < c.nDir, false, n, active)) return st;
+      if (int st = c.lv.gcr_step(k, xv, rv, k == 0 && !deflated, k + 1 < c.nDir, false, n, active)) return st;
     }
     return MUGIQ_HIP_SUCCESS;
   }
@@ -806,6 +800,20 @@ int check_levels(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in, 
   return MUGIQ_HIP_SUCCESS;
 }
 
+// the space of a *_deflated call (NULL: none, nothing to check) against the last operator of the hierarchy check_levels admitted and the
+// call's own fields, before any device work
+int check_deflation(const MugiqHipCoarseDeflation *d, const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels, const MugiqHipSpinorField *out,
+                    const MugiqHipSpinorField *in, int nVec, const char *who) {
+  if (d == nullptr) return MUGIQ_HIP_SUCCESS;
+  std::vector<uintptr_t> span(4 * (size_t)nVec);
+  uintptr_t(*fields)[2] = reinterpret_cast<uintptr_t(*)[2]>(span.data());
+  for (int i = 0; i < nVec; i++) {
+    spinor_span(out[i], &fields[i][0], &fields[i][1]);
+    spinor_span(in[i], &fields[nVec + i][0], &fields[nVec + i][1]);
+  }
+  return check_coarse_deflation(d, &coarseOps_h[nCoarseLevels - 1], fields, 2 * nVec, who);
+}
+
 // The outer flexible GCR of mugiq_hip_mg_solve on the vectors of S (fp64).  K32 NULL: p = K(r) is S's own cycle; otherwise the cycle of
 // K32 in fp32 storage, between two conversions.  Everything else -- operator applications, directions, residual, tol, the history and the
 // true residual -- is the same code for both
@@ -890,13 +898,15 @@ int outer_solve(MgSolver<double> &S, const MgSolver<float> *K32, const MugiqHipS
 template <typename F>
 int precondition_levels(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover,
                         double kappa, const MugiqHipTransfer *transfers_h, const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels,
-                        const MugiqHipMgSolveParam *params_h, const MugiqHipComm *comm, void *stream, const char *who) {
+                        const MugiqHipMgSolveParam *params_h, const MugiqHipCoarseDeflation *deflation, const MugiqHipComm *comm, void *stream,
+                        const char *who) {
   const int prec = (int)sizeof(F);
   int st;
   if ((st = check_levels(z_h, r_h, nVec, "z", "r", gauge, clover, transfers_h, coarseOps_h, nCoarseLevels, params_h, kappa, comm, who, prec, prec))) return st;
+  if ((st = check_deflation(deflation, coarseOps_h, nCoarseLevels, z_h, r_h, nVec, who))) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
-  MgSolver<F> S{gauge, clover, kappa, transfers_h, coarseOps_h, params_h, nCoarseLevels, s, who};
+  MgSolver<F> S{gauge, clover, kappa, transfers_h, coarseOps_h, params_h, nCoarseLevels, s, who, deflation};
   if ((st = S.reserve(r_h[0], 0, nVec, false))) return st;
   for (int v0 = 0; v0 < nVec; v0 += kMgBlock) {
     const int n = std::min(kMgBlock, nVec - v0);
@@ -907,17 +917,18 @@ int precondition_levels(const MugiqHipSpinorField *z_h, const MugiqHipSpinorFiel
 
 int solve_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover,
                  double kappa, const MugiqHipTransfer *transfers_h, const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels,
-                 const MugiqHipMgSolveParam *params_h, int *iters_out, double *relres_out, double *history_out, int historyStride, int *hostReads_out,
-                 const MugiqHipComm *comm, void *stream, const char *who) {
+                 const MugiqHipMgSolveParam *params_h, const MugiqHipCoarseDeflation *deflation, int *iters_out, double *relres_out, double *history_out,
+                 int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream, const char *who) {
   MUGIQ_REQUIRE(iters_out != nullptr && relres_out != nullptr, "%s: NULL argument", who);
   int st;
   if ((st = check_levels(x_h, b_h, nVec, "x", "b", gauge, clover, transfers_h, coarseOps_h, nCoarseLevels, params_h, kappa, comm, who))) return st;
+  if ((st = check_deflation(deflation, coarseOps_h, nCoarseLevels, x_h, b_h, nVec, who))) return st;
   const MugiqHipMgSolveParam *param = &params_h[0];
   MUGIQ_REQUIRE(history_out == nullptr || historyStride >= param->maxIter, "%s: historyStride = %d is smaller than maxIter = %d", who, historyStride,
                 param->maxIter);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
-  MgSolver<double> S{gauge, clover, kappa, transfers_h, coarseOps_h, params_h, nCoarseLevels, s, who};
+  MgSolver<double> S{gauge, clover, kappa, transfers_h, coarseOps_h, params_h, nCoarseLevels, s, who, deflation};
   if ((st = S.reserve(b_h[0], param->nKrylov, nVec, true))) return st;
   return outer_solve(S, nullptr, x_h, b_h, nVec, param, iters_out, relres_out, history_out, historyStride, hostReads_out, who);
 }
@@ -925,12 +936,13 @@ int solve_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h,
 int solve_mixed_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
                        const MugiqHipCloverField *clover, double kappa, const MugiqHipGaugeField *gaugeSloppy, const MugiqHipCloverField *cloverSloppy,
                        const MugiqHipTransfer *transfersSloppy_h, const MugiqHipCoarseOperator *coarseOpsSloppy_h, int nCoarseLevels,
-                       const MugiqHipMgSolveParam *params_h, int *iters_out, double *relres_out, double *history_out, int historyStride, int *hostReads_out,
-                       const MugiqHipComm *comm, void *stream, const char *who) {
+                       const MugiqHipMgSolveParam *params_h, const MugiqHipCoarseDeflation *deflation, int *iters_out, double *relres_out,
+                       double *history_out, int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream, const char *who) {
   MUGIQ_REQUIRE(iters_out != nullptr && relres_out != nullptr, "%s: NULL argument", who);
   int st;
   if ((st = check_levels(x_h, b_h, nVec, "x", "b", gauge, clover, transfersSloppy_h, coarseOpsSloppy_h, nCoarseLevels, params_h, kappa, comm, who, 8, 4)))
     return st;
+  if ((st = check_deflation(deflation, coarseOpsSloppy_h, nCoarseLevels, x_h, b_h, nVec, who))) return st;
   const MugiqHipMgSolveParam *param = &params_h[0];
   MUGIQ_REQUIRE(history_out == nullptr || historyStride >= param->maxIter, "%s: historyStride = %d is smaller than maxIter = %d", who, historyStride,
                 param->maxIter);
@@ -952,11 +964,13 @@ int solve_mixed_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField
   if ((st = debug_poison_lds_if_asked(s))) return st;
   // the outer iteration: 2 nKrylov directions, r and t (for the true residual) in fp64; the cycle: r and z rounded, s, t, w and the coarse
   // levels in fp32.  One reservation, the scalars shared: the stream orders every pass
-  MgSolver<double> S{gauge, clover, kappa, transfersSloppy_h, coarseOpsSloppy_h, params_h, nCoarseLevels, s, who};
-  MgSolver<float> K{gaugeSloppy ? gaugeSloppy : gauge, gaugeSloppy ? cloverSloppy : clover, kappa, transfersSloppy_h, coarseOpsSloppy_h, params_h, nCoarseLevels, s, who};
+  MgSolver<double> S{gauge, clover, kappa, transfersSloppy_h, coarseOpsSloppy_h, params_h, nCoarseLevels, s, who, nullptr};
+  MgSolver<float> K{gaugeSloppy ? gaugeSloppy : gauge, gaugeSloppy ? cloverSloppy : clover, kappa, transfersSloppy_h, coarseOpsSloppy_h, params_h, nCoarseLevels, s, who,
+                    deflation};
   S.init(b_h[0], param->nKrylov, nVec, kMgSetT | kMgSetR, false);
   K.init(b_h[0], 0, nVec, kMgSetsOfK | kMgSetR | kMgSetZ, true);
   if ((st = MgSolver<double>::place(s, [&](unsigned char *ws) { return K.carve(ws, S.carve(ws, scalar_bytes())); }))) return st;
+  if ((st = K.upload_deflation())) return st;
   return outer_solve(S, &K, x_h, b_h, nVec, param, iters_out, relres_out, history_out, historyStride, hostReads_out, who);
 }
 
@@ -982,21 +996,21 @@ int mugiq_hip_mg_solve_param_default(MugiqHipMgSolveParam *param) {
 int mugiq_hip_mg_precondition(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
                               const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *coarseOp,
                               const MugiqHipMgSolveParam *param, const MugiqHipComm *comm, void *stream) {
-  return precondition_levels<double>(z_h, r_h, nVec, gauge, clover, kappa, transfer, coarseOp, 1, param, comm, stream, "mgPrecondition");
+  return precondition_levels<double>(z_h, r_h, nVec, gauge, clover, kappa, transfer, coarseOp, 1, param, nullptr, comm, stream, "mgPrecondition");
 }
 
 int mugiq_hip_mg_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
                        const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *coarseOp,
                        const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out, double *history_out, int historyStride, int *hostReads_out,
                        const MugiqHipComm *comm, void *stream) {
-  return solve_levels(x_h, b_h, nVec, gauge, clover, kappa, transfer, coarseOp, 1, param, iters_out, relres_out, history_out, historyStride, hostReads_out, comm,
-                      stream, "mgSolve");
+  return solve_levels(x_h, b_h, nVec, gauge, clover, kappa, transfer, coarseOp, 1, param, nullptr, iters_out, relres_out, history_out, historyStride, hostReads_out,
+                      comm, stream, "mgSolve");
 }
 
 int mugiq_hip_mg_precondition_sloppy(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
                                      const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer,
                                      const MugiqHipCoarseOperator *coarseOp, const MugiqHipMgSolveParam *param, const MugiqHipComm *comm, void *stream) {
-  return precondition_levels<float>(z_h, r_h, nVec, gauge, clover, kappa, transfer, coarseOp, 1, param, comm, stream, "mgPreconditionSloppy");
+  return precondition_levels<float>(z_h, r_h, nVec, gauge, clover, kappa, transfer, coarseOp, 1, param, nullptr, comm, stream, "mgPreconditionSloppy");
 }
 
 int mugiq_hip_mg_solve_mixed(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
@@ -1004,7 +1018,7 @@ int mugiq_hip_mg_solve_mixed(const MugiqHipSpinorField *x_h, const MugiqHipSpino
                              const MugiqHipCloverField *cloverSloppy, const MugiqHipTransfer *transferSloppy, const MugiqHipCoarseOperator *coarseOpSloppy,
                              const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out, double *history_out, int historyStride,
                              int *hostReads_out, const MugiqHipComm *comm, void *stream) {
-  return solve_mixed_levels(x_h, b_h, nVec, gauge, clover, kappa, gaugeSloppy, cloverSloppy, transferSloppy, coarseOpSloppy, 1, param, iters_out, relres_out,
+  return solve_mixed_levels(x_h, b_h, nVec, gauge, clover, kappa, gaugeSloppy, cloverSloppy, transferSloppy, coarseOpSloppy, 1, param, nullptr, iters_out, relres_out,
                             history_out, historyStride, hostReads_out, comm, stream, "mgSolveMixed");
 }
 
@@ -1012,7 +1026,7 @@ int mugiq_hip_mg_precondition_levels(const MugiqHipSpinorField *z_h, const Mugiq
                                      const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfers_h,
                                      const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h,
                                      const MugiqHipComm *comm, void *stream) {
-  return precondition_levels<double>(z_h, r_h, nVec, gauge, clover, kappa, transfers_h, coarseOps_h, nCoarseLevels, params_h, comm, stream,
+  return precondition_levels<double>(z_h, r_h, nVec, gauge, clover, kappa, transfers_h, coarseOps_h, nCoarseLevels, params_h, nullptr, comm, stream,
                                      "mgPrecondition(levels)");
 }
 
@@ -1020,7 +1034,7 @@ int mugiq_hip_mg_solve_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpin
                               const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfers_h, const MugiqHipCoarseOperator *coarseOps_h,
                               int nCoarseLevels, const MugiqHipMgSolveParam *params_h, int *iters_out, double *relres_out, double *history_out,
                               int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream) {
-  return solve_levels(x_h, b_h, nVec, gauge, clover, kappa, transfers_h, coarseOps_h, nCoarseLevels, params_h, iters_out, relres_out, history_out,
+  return solve_levels(x_h, b_h, nVec, gauge, clover, kappa, transfers_h, coarseOps_h, nCoarseLevels, params_h, nullptr, iters_out, relres_out, history_out,
                       historyStride, hostReads_out, comm, stream, "mgSolve(levels)");
 }
 
@@ -1028,7 +1042,7 @@ int mugiq_hip_mg_precondition_sloppy_levels(const MugiqHipSpinorField *z_h, cons
                                             const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfers_h,
                                             const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h,
                                             const MugiqHipComm *comm, void *stream) {
-  return precondition_levels<float>(z_h, r_h, nVec, gauge, clover, kappa, transfers_h, coarseOps_h, nCoarseLevels, params_h, comm, stream,
+  return precondition_levels<float>(z_h, r_h, nVec, gauge, clover, kappa, transfers_h, coarseOps_h, nCoarseLevels, params_h, nullptr, comm, stream,
                                     "mgPreconditionSloppy(levels)");
 }
 
@@ -1038,7 +1052,44 @@ int mugiq_hip_mg_solve_mixed_levels(const MugiqHipSpinorField *x_h, const MugiqH
                                     const MugiqHipCoarseOperator *coarseOpsSloppy_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h, int *iters_out,
                                     double *relres_out, double *history_out, int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream) {
   return solve_mixed_levels(x_h, b_h, nVec, gauge, clover, kappa, gaugeSloppy, cloverSloppy, transfersSloppy_h, coarseOpsSloppy_h, nCoarseLevels, params_h,
-                            iters_out, relres_out, history_out, historyStride, hostReads_out, comm, stream, "mgSolveMixed(levels)");
+                            nullptr, iters_out, relres_out, history_out, historyStride, hostReads_out, comm, stream, "mgSolveMixed(levels)");
+}
+
+/* the *_levels entry points with a deflation space for the last coarse level (NULL: the twin) */
+int mugiq_hip_mg_precondition_levels_deflated(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
+                                              const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfers_h,
+                                              const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h,
+                                              const MugiqHipCoarseDeflation *deflation, const MugiqHipComm *comm, void *stream) {
+  return precondition_levels<double>(z_h, r_h, nVec, gauge, clover, kappa, transfers_h, coarseOps_h, nCoarseLevels, params_h, deflation, comm, stream,
+                                     "mgPrecondition(levels, deflated)");
+}
+
+int mugiq_hip_mg_solve_levels_deflated(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                                       const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfers_h,
+                                       const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h,
+                                       const MugiqHipCoarseDeflation *deflation, int *iters_out, double *relres_out, double *history_out,
+                                       int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream) {
+  return solve_levels(x_h, b_h, nVec, gauge, clover, kappa, transfers_h, coarseOps_h, nCoarseLevels, params_h, deflation, iters_out, relres_out, history_out,
+                      historyStride, hostReads_out, comm, stream, "mgSolve(levels, deflated)");
+}
+
+int mugiq_hip_mg_precondition_sloppy_levels_deflated(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec,
+                                                     const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover, double kappa,
+                                                     const MugiqHipTransfer *transfers_h, const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels,
+                                                     const MugiqHipMgSolveParam *params_h, const MugiqHipCoarseDeflation *deflation,
+                                                     const MugiqHipComm *comm, void *stream) {
+  return precondition_levels<float>(z_h, r_h, nVec, gauge, clover, kappa, transfers_h, coarseOps_h, nCoarseLevels, params_h, deflation, comm, stream,
+                                    "mgPreconditionSloppy(levels, deflated)");
+}
+
+int mugiq_hip_mg_solve_mixed_levels_deflated(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                                             const MugiqHipCloverField *clover, double kappa, const MugiqHipGaugeField *gaugeSloppy,
+                                             const MugiqHipCloverField *cloverSloppy, const MugiqHipTransfer *transfersSloppy_h,
+                                             const MugiqHipCoarseOperator *coarseOpsSloppy_h, int nCoarseLevels, const MugiqHipMgSolveParam *params_h,
+                                             const MugiqHipCoarseDeflation *deflation, int *iters_out, double *relres_out, double *history_out,
+                                             int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream) {
+  return solve_mixed_levels(x_h, b_h, nVec, gauge, clover, kappa, gaugeSloppy, cloverSloppy, transfersSloppy_h, coarseOpsSloppy_h, nCoarseLevels, params_h,
+                            deflation, iters_out, relres_out, history_out, historyStride, hostReads_out, comm, stream, "mgSolveMixed(levels, deflated)");
 }
 
 /* dst_i = src_i between two precisions: fields of one geometry and field order, each set with its own stride and parity offset */

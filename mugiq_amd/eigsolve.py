@@ -239,6 +239,73 @@ def mgSolveParam(**param):
     return p
 
 
+class CoarseDeflation:
+    """The deflation space of the coarsest level of an MG solve (MugiqHipCoarseDeflation): W, the lowest eigenvectors of MdagM of the
+    CoarseOperator `op` of that level (what coarseEigensolve returns), and U_n = M W_n / sigma_n with sigma_n = ||M W_n||, built here on
+    the device (mugiq_hip_coarse_deflation_build).  W and op have one precision; W is kept, not copied.  A sigma that is zero or not
+    finite raises MugiqHipError (status 1).  Pass it as deflation= to mgPrecondition, mgSolve, mgPreconditionSloppy and mgSolveMixed."""
+
+    def __init__(self, W, op, comm=None):
+        self.W, self.op, self.comm = list(W), op, comm
+        if not self.W or not isinstance(op, CoarseOperator):
+            raise _lib.MugiqHipError("CoarseDeflation: needs at least one eigenvector and the CoarseOperator of their level")
+        w0 = self.W[0]
+        self.U = [CoarseField(w0.X, w0.n_vec, w0.precision, w0.stride - w0.volumeCB, device=w0.device) for _ in self.W]
+        n = len(self.W)
+        self._sigma = (ctypes.c_double * n)()
+        keep = []
+        d = op.desc()
+        _lib.check(_lib.load().mugiq_hip_coarse_deflation_build(coarse_desc_array(self.U), self._sigma, coarse_desc_array(self.W), n, ctypes.byref(d),
+                                                                _comm_ptr(comm, keep), _stream()))
+        self.sigma = np.array(self._sigma)
+
+    @property
+    def nEv(self):
+        return len(self.W)
+
+    @property
+    def precision(self):
+        return self.W[0].precision
+
+    def desc(self, keep):
+        """the C struct; what it points to is appended to `keep`, which must outlive the call"""
+        w, u = coarse_desc_array(self.W), coarse_desc_array(self.U)
+        sg = (ctypes.c_double * self.nEv)(*[float(s) for s in self.sigma])
+        d = _lib.CoarseDeflationDesc(self.nEv, w, u, sg)
+        keep.extend([w, u, sg, d])
+        return d
+
+    def astype(self, precision, op):
+        """the space in another storage precision: W rounded (once, to nearest) on the device, U and sigma rebuilt on `op`, the
+        CoarseOperator of that precision -- for the sloppy hierarchy of mgSolveMixed, astype(4, op32).  The comm of this space is kept"""
+        if int(precision) not in (4, 8) or not isinstance(op, CoarseOperator) or op.precision != int(precision):
+            raise _lib.MugiqHipError("CoarseDeflation.astype: precision %r needs the CoarseOperator of that precision (4 | 8), got %s"
+                                     % (precision, "precision %d" % op.precision if isinstance(op, CoarseOperator) else type(op).__name__))
+        W = []
+        for w in self.W:
+            f = CoarseField(w.X, w.n_vec, int(precision), w.stride - w.volumeCB, device=w.device)
+            f.data.copy_(w.data)
+            W.append(f)
+        return CoarseDeflation(W, op, self.comm)
+
+
+def coarseDeflate(b, space, comm=None, x0=None, r0=None):
+    """(x0, r0) of the deflated coarsest solve for a list b of CoarseFields (mugiq_hip_coarse_deflate): c_n = <u_n, b>,
+    x0 = sum_n w_n c_n / sigma_n, r0 = b - sum_n u_n c_n.  x0, r0: new fields laid out like b unless given."""
+    b = list(b)
+    if not b or not isinstance(space, CoarseDeflation):
+        raise _lib.MugiqHipError("coarseDeflate: needs at least one right-hand side and a CoarseDeflation")
+    x0 = [CoarseField(f.X, f.n_vec, f.precision, f.stride - f.volumeCB, device=f.device) for f in b] if x0 is None else list(x0)
+    r0 = [CoarseField(f.X, f.n_vec, f.precision, f.stride - f.volumeCB, device=f.device) for f in b] if r0 is None else list(r0)
+    if len(x0) != len(b) or len(r0) != len(b):
+        raise _lib.MugiqHipError("coarseDeflate: %d x0 and %d r0 fields for %d right-hand sides" % (len(x0), len(r0), len(b)))
+    keep = []
+    d = space.desc(keep)
+    _lib.check(_lib.load().mugiq_hip_coarse_deflate(coarse_desc_array(x0), coarse_desc_array(r0), coarse_desc_array(b), len(b), ctypes.byref(d),
+                                                    _comm_ptr(comm, keep), _stream()))
+    return x0, r0
+
+
 def _mg_levels(who, transfer, coarseOp, coarseParam, param):
     """The hierarchy arguments of the MG calls.  A single Transfer and CoarseOperator: None (the two-grid entry points).  Lists
     [T0, T1] and [op1, op2] (or of one each): (transfer descs, operator descs, nCoarseLevels, params) for the *_levels entry points, with
@@ -262,9 +329,19 @@ def _mg_levels(who, transfer, coarseOp, coarseParam, param):
     return t, o, L, params
 
 
-def _mg_hierarchy(who, transfer, coarseOp, coarseParam, param):
+def _mg_hierarchy(who, transfer, coarseOp, coarseParam, param, deflation=None, keep=None):
     """(suffix of the entry point, its transfer / operator / parameter arguments, params[0]) of an MG call: "_levels" and the arrays of
-    _mg_levels for lists, "" and the three descriptors by reference for a single Transfer and CoarseOperator (the two-grid entry points)."""
+    _mg_levels for lists, "" and the three descriptors by reference for a single Transfer and CoarseOperator (the two-grid entry points).
+    deflation (a CoarseDeflation): "_levels_deflated" and the space behind the parameters; a single Transfer and CoarseOperator then go
+    through it as a hierarchy of one level.  What the struct points to is appended to `keep`."""
+    if deflation is not None:
+        if not isinstance(deflation, CoarseDeflation):
+            raise _lib.MugiqHipError("%s: deflation must be a CoarseDeflation" % who)
+        if not isinstance(transfer, (list, tuple)) and not isinstance(coarseOp, (list, tuple)):
+            transfer, coarseOp = [transfer], [coarseOp]
+        lev = _mg_levels(who, transfer, coarseOp, coarseParam, param)
+        d = deflation.desc(keep)
+        return "_levels_deflated", lev + (ctypes.byref(d),), lev[3][0]
     lev = _mg_levels(who, transfer, coarseOp, coarseParam, param)
     if lev is not None:
         return "_levels", lev, lev[3][0]
@@ -272,19 +349,19 @@ def _mg_hierarchy(who, transfer, coarseOp, coarseParam, param):
     return "", (ctypes.byref(t), ctypes.byref(o), ctypes.byref(p)), p
 
 
-def _mg_precondition(who, entry, z, r, gauge, kappa, transfer, coarseOp, clover, comm, coarseParam, param):
+def _mg_precondition(who, entry, z, r, gauge, kappa, transfer, coarseOp, clover, comm, coarseParam, param, deflation=None):
     """mgPrecondition and mgPreconditionSloppy: `entry` (two-grid) or entry + "_levels" (lists)."""
     z, r = list(z), list(r)
     if len(z) != len(r) or not r:
         raise _lib.MugiqHipError("%s: %d z and %d r vectors (need the same number, at least one)" % (who, len(z), len(r)))
     keep = []
-    suffix, hierarchy, _ = _mg_hierarchy(who, transfer, coarseOp, coarseParam, param)
+    suffix, hierarchy, _ = _mg_hierarchy(who, transfer, coarseOp, coarseParam, param, deflation, keep)
     g = gauge.desc()
     _lib.check(getattr(_lib.load(), entry + suffix)(desc_array(z), desc_array(r), len(r), ctypes.byref(g), _clover_ptr(clover, keep), float(kappa),
                                                     *hierarchy, _comm_ptr(comm, keep), _stream()))
 
 
-def _mg_solve(who, entry, b, gauge, kappa, transfer, coarseOp, clover, sloppyFields, x, allow_unconverged, comm, coarseParam, param):
+def _mg_solve(who, entry, b, gauge, kappa, transfer, coarseOp, clover, sloppyFields, x, allow_unconverged, comm, coarseParam, param, deflation=None):
     """mgSolve and mgSolveMixed: `entry` (two-grid) or entry + "_levels" (lists).  sloppyFields: None, or (gaugeSloppy, cloverSloppy),
     which the mixed entries take in front of the hierarchy."""
     b = list(b)
@@ -297,7 +374,7 @@ def _mg_solve(who, entry, b, gauge, kappa, transfer, coarseOp, clover, sloppyFie
     if len(x) != n:
         raise _lib.MugiqHipError("%s: %d x and %d b vectors" % (who, len(x), n))
     keep = []
-    suffix, hierarchy, p = _mg_hierarchy(who, transfer, coarseOp, coarseParam, param)
+    suffix, hierarchy, p = _mg_hierarchy(who, transfer, coarseOp, coarseParam, param, deflation, keep)
     g = gauge.desc()
     sloppy = ()
     if sloppyFields is not None:
@@ -322,24 +399,27 @@ def _mg_solve(who, entry, b, gauge, kappa, transfer, coarseOp, clover, sloppyFie
     return x, MgSolveInfo(it, np.array(relres), st == 0, [h[i, :it[i]].copy() for i in range(n)], int(reads.value))
 
 
-def mgPrecondition(z, r, gauge, kappa, transfer, coarseOp, clover=None, comm=None, coarseParam=None, **param):
+def mgPrecondition(z, r, gauge, kappa, transfer, coarseOp, clover=None, comm=None, coarseParam=None, deflation=None, **param):
     """z_i = K(r_i): one two-grid cycle (MR smoothing, coarse-grid correction by GCR on the explicit coarse operator) for lists of fp64
     SpinorFields (mugiq_hip_mg_precondition).  param: members of MugiqHipMgSolveParam (nuPre, nuPost, omega, coarseIters).
     transfer=[T0, T1], coarseOp=[op1, op2]: the three-level cycle K^(3) (mugiq_hip_mg_precondition_levels), whose level-1 solve is a GCR
     preconditioned by a cycle through op2; coarseParam: dict of the level-1 members (nuPre, nuPost, omega, coarseIters), default: the
-    struct defaults, which are not tuned."""
-    _mg_precondition("mgPrecondition", "mugiq_hip_mg_precondition", z, r, gauge, kappa, transfer, coarseOp, clover, comm, coarseParam, param)
+    struct defaults, which are not tuned.  deflation: a CoarseDeflation on the last coarse level -- its solve starts from the projection on
+    the space (mugiq_hip_mg_precondition_levels_deflated); None: the call is what it was."""
+    _mg_precondition("mgPrecondition", "mugiq_hip_mg_precondition", z, r, gauge, kappa, transfer, coarseOp, clover, comm, coarseParam, param, deflation)
 
 
-def mgSolve(b, gauge, kappa, transfer, coarseOp, clover=None, x=None, allow_unconverged=False, comm=None, coarseParam=None, **param):
+def mgSolve(b, gauge, kappa, transfer, coarseOp, clover=None, x=None, allow_unconverged=False, comm=None, coarseParam=None, deflation=None, **param):
     """x_r = M^-1 b_r by flexible GCR preconditioned with the two-grid cycle of mgPrecondition (mugiq_hip_mg_solve); transfer: the
     finest-level Transfer, coarseOp: the CoarseOperator computeCoarseOperator built from it for this gauge, clover and kappa.  param:
     members of MugiqHipMgSolveParam (tol, maxIter, nKrylov, nuPre, nuPost, omega, coarseIters).  Returns (x, MgSolveInfo(iters, relres,
     converged, history, hostReads)): history[r] the recursive relative residuals of right-hand side r, one per iteration; hostReads the
     blocking reads the call made.  x: new fp64 fields laid out like b unless given.  A right-hand side that does not reach tol within
     maxIter raises MugiqHipError (status 5) unless allow_unconverged.  transfer=[T0, T1], coarseOp=[op1, op2] and coarseParam: the
-    three-level cycle, as for mgPrecondition (mugiq_hip_mg_solve_levels)."""
-    return _mg_solve("mgSolve", "mugiq_hip_mg_solve", b, gauge, kappa, transfer, coarseOp, clover, None, x, allow_unconverged, comm, coarseParam, param)
+    three-level cycle, as for mgPrecondition (mugiq_hip_mg_solve_levels).  deflation: a CoarseDeflation on the last coarse level, as for
+    mgPrecondition (mugiq_hip_mg_solve_levels_deflated)."""
+    return _mg_solve("mgSolve", "mugiq_hip_mg_solve", b, gauge, kappa, transfer, coarseOp, clover, None, x, allow_unconverged, comm, coarseParam, param,
+                     deflation)
 
 
 def mgConvertPrecision(dst, src):
@@ -351,23 +431,25 @@ def mgConvertPrecision(dst, src):
     _lib.check(_lib.load().mugiq_hip_mg_convert_precision(desc_array(dst), desc_array(src), len(src), _stream()))
 
 
-def mgPreconditionSloppy(z, r, gauge, kappa, transfer, coarseOp, clover=None, comm=None, coarseParam=None, **param):
+def mgPreconditionSloppy(z, r, gauge, kappa, transfer, coarseOp, clover=None, comm=None, coarseParam=None, deflation=None, **param):
     """z_i = K(r_i) with every vector of the cycle in fp32 storage (mugiq_hip_mg_precondition_sloppy): z, r, transfer and coarseOp all of
     precision 4, gauge (and clover) of either.  Sums are fp64 and in a fixed order, as in mgPrecondition.  param, and the lists and
-    coarseParam of a three-level hierarchy (mugiq_hip_mg_precondition_sloppy_levels): as for mgPrecondition."""
+    coarseParam of a three-level hierarchy (mugiq_hip_mg_precondition_sloppy_levels): as for mgPrecondition.  deflation: a CoarseDeflation
+    of precision 4 (CoarseDeflation.astype(4, op32))."""
     _mg_precondition("mgPreconditionSloppy", "mugiq_hip_mg_precondition_sloppy", z, r, gauge, kappa, transfer, coarseOp, clover, comm, coarseParam,
-                     param)
+                     param, deflation)
 
 
 def mgSolveMixed(b, gauge, kappa, transferSloppy, coarseOpSloppy, clover=None, gaugeSloppy=None, cloverSloppy=None, x=None, allow_unconverged=False,
-                 comm=None, coarseParam=None, **param):
+                 comm=None, coarseParam=None, deflation=None, **param):
     """x_r = M^-1 b_r by the fp64 flexible GCR of mgSolve with the two-grid cycle in fp32 storage (mugiq_hip_mg_solve_mixed).  b, x, gauge and
     clover as for mgSolve; transferSloppy: the Transfer in precision 4 (Transfer.astype(4)), coarseOpSloppy: the CoarseOperator
     computeCoarseOperator built from it; gaugeSloppy / cloverSloppy: the fields the cycle's stencil reads (e.g. fp32 copies), both None:
     gauge and clover.  Returns (x, MgSolveInfo) as mgSolve does; relres is the true fp64 residual.  transferSloppy=[T0_32, T1_32],
-    coarseOpSloppy=[op1_32, op2_32] and coarseParam: the three-level cycle in fp32 storage (mugiq_hip_mg_solve_mixed_levels)."""
+    coarseOpSloppy=[op1_32, op2_32] and coarseParam: the three-level cycle in fp32 storage (mugiq_hip_mg_solve_mixed_levels).  deflation: the
+    space of the sloppy hierarchy, precision 4 (CoarseDeflation.astype(4, op32))."""
     return _mg_solve("mgSolveMixed", "mugiq_hip_mg_solve_mixed", b, gauge, kappa, transferSloppy, coarseOpSloppy, clover, (gaugeSloppy, cloverSloppy), x,
-                     allow_unconverged, comm, coarseParam, param)
+                     allow_unconverged, comm, coarseParam, param, deflation)
 
 
 def mgSetupParam(**param):
@@ -685,23 +767,35 @@ class Eigsolve_Mugiq:
             ev = self.eVecs
         return wilsonSolve(b, self.gauge, self.kappa, ev, sg, tol, maxIter, self.comm, x, allow_unconverged, self.clover)
 
-    def solveMG(self, b, x=None, allow_unconverged=False, sloppy=None, coarseOp=None, coarseParam=None, **param):
+    def deflationSpace(self):
+        """The CoarseDeflation of this object's own coarse eigenvectors (of MdagM, e.g. from computeEvecs) and its coarseOp: the space that
+        deflates the coarsest level of solveMG.  For objects built with transfer= and coarseOp= whose eVecs are CoarseFields."""
+        if self.transfer is None or self.coarseOp is None:
+            raise _lib.MugiqHipError("status 2: Eigsolve_Mugiq.deflationSpace: needs an object built with transfer= and its coarseOp= (the "
+                                     "eigenvectors of a fine operator do not deflate a coarse level)")
+        if self.opType != MUGIQ_EIG_OPERATOR_MdagM:
+            raise _lib.MugiqHipError("status 2: Eigsolve_Mugiq.deflationSpace: the space is made of eigenvectors of MdagM")
+        if not self.eVecs or not all(isinstance(v, CoarseField) for v in self.eVecs):
+            raise _lib.MugiqHipError("status 1: Eigsolve_Mugiq.deflationSpace: no coarse eigenvectors (call computeEvecs first)")
+        return CoarseDeflation(self.eVecs, self.coarseOp, self.comm)
+
+    def solveMG(self, b, x=None, allow_unconverged=False, sloppy=None, coarseOp=None, coarseParam=None, deflation=None, **param):
         """M^-1 b by the two-grid preconditioned GCR (mgSolve) for objects built with transfer= and coarseOp=: their gauge field, clover
         field, kappa, transfer and coarse operator.  sloppy=(T32, op32): the mixed solve (mgSolveMixed) with that fp32 hierarchy, on this
         object's gauge and clover fields.  An object built with transfer=[T0, T1] holds only the coarsest operator, so the three-level
         solve takes coarseOp=[op1, op2] here (and coarseParam, the level-1 cycle); its sloppy= is ([T0_32, T1_32], [op1_32, op2_32]).
-        Returns (x, MgSolveInfo)."""
+        deflation: a CoarseDeflation on the last coarse level (deflationSpace(); with sloppy=, its astype(4, op32)).  Returns (x, MgSolveInfo)."""
         if sloppy is not None:
             T32, op32 = sloppy
             return mgSolveMixed(b, self.gauge, self.kappa, T32, op32, self.clover, x=x, allow_unconverged=allow_unconverged, comm=self.comm,
-                                coarseParam=coarseParam, **param)
+                                coarseParam=coarseParam, deflation=deflation, **param)
         tr, op = self.transfer, self.coarseOp if coarseOp is None else coarseOp
         if tr is None and op is None and self.mgTransfer is not None:   # the hierarchy setupMG made
             tr, op = self.mgTransfer, self.mgCoarseOp
         if tr is None or op is None or isinstance(tr, (list, tuple)) != isinstance(op, (list, tuple)):
             raise _lib.MugiqHipError("status 2: Eigsolve_Mugiq.solveMG: needs an object built with one finest-level transfer= and its coarseOp=, or "
                                      "with transfer=[T0, T1] and coarseOp=[op1, op2] in the call")
-        return mgSolve(b, self.gauge, self.kappa, tr, op, self.clover, x, allow_unconverged, self.comm, coarseParam=coarseParam, **param)
+        return mgSolve(b, self.gauge, self.kappa, tr, op, self.clover, x, allow_unconverged, self.comm, coarseParam=coarseParam, deflation=deflation, **param)
 
     def setupMG(self, n_vec=24, geo_block_size=(4, 4, 4, 4), start=None, seed=0, **param):
         """Make an MG hierarchy from this object's own gauge field, clover field and kappa (mgSetup) and keep it in self.mgTransfer and

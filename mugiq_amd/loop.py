@@ -422,7 +422,7 @@ class Loop_Mugiq:
                                                    comm=self.comm, **param)
         return self.lastSetup
 
-    def solveMG(self, b, kappa, coarseOp=None, clover=None, x=None, allow_unconverged=False, sloppy=None, coarseParam=None, **param):
+    def solveMG(self, b, kappa, coarseOp=None, clover=None, x=None, allow_unconverged=False, sloppy=None, coarseParam=None, deflation=None, **param):
         """x_r = M^-1 b_r by the two-grid preconditioned GCR (mgSolve) with this coarse loop object's gauge field, transfer and stream;
         coarseOp: the CoarseOperator of that transfer at this kappa (and clover).  Returns the list x; iteration counts, true residuals,
         histories and host reads are kept in self.lastSolve.  Status 2 (UNSUPPORTED) for fine-level and two-sided loop objects and for
@@ -430,7 +430,8 @@ class Loop_Mugiq:
         x = loop.solveMG(xi, kappa, coarseOp); loop.deflateCoarse(x, xi).  sloppy=(T32, op32): the mixed solve (mgSolveMixed) with that
         fp32 hierarchy in place of this object's transfer and coarseOp; the checks of the object stay.  A loop object made with
         transfer=[T0, T1] supplies both transfers and takes coarseOp=[op1, op2] (and coarseParam, the level-1 cycle): the three-level
-        solve; its sloppy= is ([T0_32, T1_32], [op1_32, op2_32])."""
+        solve; its sloppy= is ([T0_32, T1_32], [op1_32, op2_32]).  deflation: a CoarseDeflation on the last coarse level, handed to the
+        solve as it is (with sloppy=, the space of the fp32 hierarchy)."""
         from .eigsolve import mgSolve, mgSolveMixed
         if self._transfer is None or self.eVecsLeft is not None:
             raise _lib.MugiqHipError("status 2: Loop_Mugiq.solveMG: coarse (MG) loop objects only")
@@ -449,13 +450,14 @@ class Loop_Mugiq:
         if sloppy is not None:
             T32, op32 = sloppy
             x, self.lastSolve = mgSolveMixed(b, self._params.gauge, kappa, T32, op32, clover, x=x, allow_unconverged=allow_unconverged, comm=self.comm,
-                                             coarseParam=coarseParam, **param)
+                                             coarseParam=coarseParam, deflation=deflation, **param)
             return x
         if coarseOp is None:
             coarseOp = self.coarseOp
             if coarseOp is None:
                 raise _lib.MugiqHipError("status 1: Loop_Mugiq.solveMG: no coarse operator (pass one or call setupMG first)")
-        x, self.lastSolve = mgSolve(b, self._params.gauge, kappa, tr, coarseOp, clover, x, allow_unconverged, self.comm, coarseParam=coarseParam, **param)
+        x, self.lastSolve = mgSolve(b, self._params.gauge, kappa, tr, coarseOp, clover, x, allow_unconverged, self.comm, coarseParam=coarseParam,
+                                    deflation=deflation, **param)
         return x
 
     def computeEvecs(self, kappa, nConv, nKr, coarseOp=None, opType=None, start=None, seed=0, allow_unconverged=False, **param):
