@@ -736,8 +736,9 @@ int mugiq_hip_wilson_clover_solve(const MugiqHipSpinorField *x_h, const MugiqHip
  *
  * Limits: a SINGLE DOMAIN (a comm with size > 1 or any partitioned axis: MUGIQ_HIP_ERROR_UNSUPPORTED, before any device work).  The
  * operator of a coarse -> coarse transfer is built from this one by mugiq_hip_compute_coarse_operator_coarse (below) and lives in the same
- * struct: application, eigenpair check and eigensolver do not know the level.  Partitioned grids stay on the route of
- * mugiq_hip_compute_evals_coarse, which applies R M P through the fine lattice. */
+ * struct: application, eigenpair check and eigensolver do not know the level.  Process grids are served by the entry points of their own
+ * further down -- mugiq_hip_compute_coarse_operator_grid, mugiq_hip_coarse_apply_grid and mugiq_hip_compute_evals_coarse_operator_grid,
+ * with a MugiqHipCoarseHalo beside the operator -- and, through the fine lattice, by mugiq_hip_compute_evals_coarse. */
 typedef struct MugiqHipCoarseOperator_s {
   void *data;
   int precision; /* 4 | 8: the transfer's (and the coarse fields') */
@@ -779,6 +780,67 @@ int mugiq_hip_coarse_apply_outputs(const MugiqHipCoarseOperator *op, int nVec);
 int mugiq_hip_compute_evals_coarse_operator(const MugiqHipCoarseField *coarseEvecs_h, int nEv, const MugiqHipCoarseOperator *op, int opType,
                                             int massNormalization, double *lambda_h, double *residual_h, double *sigma_h,
                                             const MugiqHipComm *comm, void *stream);
+
+/* ---- the explicit coarse operator on a process grid (new; csrc/coarse_op.hip).  Xd, Y+-_mu, M_c and M_c^dag are the definitions above on
+ * the GLOBAL lattice.  A rank owns the aggregates of its local fine lattice: local fine extents are multiples of the block size and local
+ * coarse extents are even, so rank offsets are even and local parity is global parity.  MugiqHipCoarseOperator holds the matrices of the
+ * local coarse sites, unchanged.  M_c of a site on a face reads the neighbour rank's coarse vector; M_c^dag reads the neighbour rank's
+ * MATRIX as well, Y+_mu(X-mu)^dag for X on the local low face and Y-_mu(X+mu)^dag for X on the high face.  Those matrices are kept in a
+ * MugiqHipCoarseHalo, filled once by the build.
+ *
+ * Face-site ordering (every face buffer of these calls, fine or coarse): a site with coordinates c on a face of axis mu (c[mu] = 0 or
+ * X[mu] - 1) and parity p = (c0 + c1 + c2 + c3) & 1 has the face index p*faceCB + (l >> 1), faceCB = volumeCB / X[mu], l the
+ * lexicographic index of the three other coordinates with the lowest axis fastest (QUDA's ghostFaceIndex at depth 1).  A site and the
+ * neighbour-rank site it hops to share their three other coordinates, hence (l >> 1); their parities differ.
+ *   Yback[mu]: Y+_mu of the BACKWARD neighbour's high-face sites, Yfwd[mu]: Y-_mu of the FORWARD neighbour's low-face sites; each
+ *   2*faceCB matrices of N*N complex in the operator's precision, matrix-contiguous: element (r, c) of face site f at (f*N + r)*N + c.
+ * Both NULL on an axis the halo was not built for (dims[mu] == 0).  With a rank as its own neighbour (MugiqHipComm.partitioned) the
+ * halo holds copies of the rank's own matrices.
+ *
+ * Only these three calls serve a grid.  The MG solve, mugiq_hip_mg_setup, mugiq_hip_coarse_eigensolve with mugiq_hip_coarse_gram and
+ * mugiq_hip_coarse_rotate, the coarse deflation and mugiq_hip_compute_coarse_operator_coarse stay single-domain and refuse a partitioned
+ * comm, as do the three single-domain calls above.  The exchange is not overlapped with interior work. */
+typedef struct MugiqHipCoarseHalo_s {
+  void *Yback[4], *Yfwd[4];
+  int precision; /* of the operator it belongs to */
+  int nVec;
+  int X[4];      /* local coarse lattice of that operator */
+  int volumeCB;
+  int dims[4];   /* != 0: built for a partitioned axis mu */
+} MugiqHipCoarseHalo;
+/* bytes of all face matrices: sum over dims[mu] != 0 of 2 * (volume / X[mu]) * N^2 complex of `precision`; 0 for arguments the
+ * allocation would refuse */
+size_t mugiq_hip_coarse_halo_bytes(const int X[4], int nVec, int precision, const int dims[4]);
+/* allocate (zeroed) for the geometry, n_vec and precision of `op` on the axes dims[mu] != 0; release with mugiq_hip_free_coarse_halo */
+int mugiq_hip_alloc_coarse_halo(MugiqHipCoarseHalo *halo, const MugiqHipCoarseOperator *op, const int dims[4]);
+int mugiq_hip_free_coarse_halo(MugiqHipCoarseHalo *halo);
+/* mugiq_hip_compute_coarse_operator on a process grid; collective.  gauge: border-extended with R >= 1 on every partitioned axis, as for
+ * mugiq_hip_wilson_clover_apply; clover: the local field.  On every partitioned axis the two faces of V (12 n_vec complex per face site)
+ * go to the neighbours in one transfer group, into the per-stream workspace; a hop that leaves the local lattice reads V(x +- mu) from
+ * there and its link from the border, every sum in the order of the single-domain build, so a rank's matrices are the bits of its slice
+ * of the single-domain operator.  Then Y+_mu of the high face and Y-_mu of the low face are packed and exchanged into `halo` (a second
+ * group).  Checks, before any device work: NULL op / transfer; comm->sendrecv NULL on a partitioned comm; an operator with an odd extent;
+ * halo NULL on a partitioned comm, or of another geometry, n_vec or precision than op, or not built for a partitioned axis; a gauge
+ * border of 0 on a partitioned axis; everything mugiq_hip_compute_coarse_operator checks.  With nothing partitioned (comm NULL, or one
+ * rank without a forced axis) halo may be NULL and the call is mugiq_hip_compute_coarse_operator: the same launch, the same bits. */
+int mugiq_hip_compute_coarse_operator_grid(MugiqHipCoarseOperator *op, const MugiqHipCoarseHalo *halo, const MugiqHipTransfer *transfer,
+                                           const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover, double kappa,
+                                           const MugiqHipComm *comm, void *stream);
+/* mugiq_hip_coarse_apply on a process grid; collective, all five forms.  Per kernel launch (one for M, M^dag and H on all nVec vectors;
+ * two per block of 8 for MdagM and MMdag, whose intermediate is exchanged as well) the faces of the input vectors are packed -- N complex
+ * per face site and vector, the face index fastest, then the component, the parity and the vector -- and sent in ONE message per
+ * partitioned axis and direction, inside group_begin / group_end where the comm has them; then the one launch of the application follows,
+ * whose hops off the rank read the received faces and, for M^dag, the halo's matrices.  Nothing overlaps the exchange.  The sums and
+ * their order are those of mugiq_hip_coarse_apply: the result is the bits of the rank's slice of the single-domain result.  Work memory
+ * (send and receive faces, the intermediate): the per-stream workspace; pads are neither read nor written.  Checks as above (no gauge)
+ * plus those of mugiq_hip_coarse_apply; nothing partitioned: halo may be NULL, the call is mugiq_hip_coarse_apply. */
+int mugiq_hip_coarse_apply_grid(const MugiqHipCoarseField *dst_h, const MugiqHipCoarseField *src_h, int nVec, const MugiqHipCoarseOperator *op,
+                                const MugiqHipCoarseHalo *halo, int opType, double scale, const MugiqHipComm *comm, void *stream);
+/* mugiq_hip_compute_evals_coarse_operator on a process grid: A_c by mugiq_hip_coarse_apply_grid, the fixed-order fp64 sums of every rank
+ * added over the ranks in a fixed order (reduce_space, gather_time and bcast, required with size > 1): identical values on every rank. */
+int mugiq_hip_compute_evals_coarse_operator_grid(const MugiqHipCoarseField *coarseEvecs_h, int nEv, const MugiqHipCoarseOperator *op,
+                                                 const MugiqHipCoarseHalo *halo, int opType, int massNormalization, double *lambda_h,
+                                                 double *residual_h, double *sigma_h, const MugiqHipComm *comm, void *stream);
 
 /* ---- the operator of a coarse -> coarse transfer (new; csrc/coarse_op2.hip): the coarsest level of a three-level hierarchy, where the
  * reference's Eigsolve_Mugiq computes its eigenvectors (MG_Mugiq takes n_level 2, 3 or 4: include/mg_mugiq.h:40-53;

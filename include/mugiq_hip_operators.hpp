@@ -214,6 +214,30 @@ inline void computeEvalsCoarse(const std::vector<MugiqHipCoarseField> &coarseEve
                                                 reinterpret_cast<double *>(lambda.data()), residual.data(), sigma.data(), comm, stream));
   if (opType == MUGIQ_HIP_EIG_OPERATOR_M || opType == MUGIQ_HIP_EIG_OPERATOR_MDAG) sigma.clear();
 }
+// ---- ... on a process grid (mugiq_hip_compute_coarse_operator_grid, mugiq_hip_coarse_apply_grid, mugiq_hip_compute_evals_coarse_operator_grid;
+// new): the same three names with the operator's MugiqHipCoarseHalo (mugiq_hip_alloc_coarse_halo / mugiq_hip_free_coarse_halo) behind the
+// operator; collective, comm required.  Compile-checked only (tests/test_coarse_op_grid_cpu.py): the C++ test program does not run them
+inline void computeCoarseOperator(CoarseOperator &op, const MugiqHipCoarseHalo &halo, const MugiqHipTransfer &transfer, const GaugeField &gauge,
+                                  const MugiqHipCloverField *clover, double kappa, const MugiqHipComm *comm, void *stream = nullptr) {
+  check(mugiq_hip_compute_coarse_operator_grid(op.desc(), &halo, &transfer, &gauge, clover, kappa, comm, stream));
+}
+inline void coarseApply(const std::vector<MugiqHipCoarseField> &dst, const std::vector<MugiqHipCoarseField> &src, const CoarseOperator &op,
+                        const MugiqHipCoarseHalo &halo, int opType, double scale, const MugiqHipComm *comm, void *stream = nullptr) {
+  if (src.empty() || dst.size() != src.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "coarseApply: size mismatch");
+  check(mugiq_hip_coarse_apply_grid(dst.data(), src.data(), (int)src.size(), op.desc(), &halo, opType, scale, comm, stream));
+}
+inline void computeEvalsCoarse(const std::vector<MugiqHipCoarseField> &coarseEvecs, const CoarseOperator &coarseOp, const MugiqHipCoarseHalo &halo,
+                               int opType, bool massNormalization, std::vector<std::complex<double>> &lambda, std::vector<double> &residual,
+                               std::vector<double> &sigma, const MugiqHipComm *comm, void *stream = nullptr) {
+  if (coarseEvecs.empty()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "computeEvalsCoarse: no eigenvectors");
+  lambda.assign(coarseEvecs.size(), std::complex<double>(0.0, 0.0));
+  residual.assign(coarseEvecs.size(), 0.0);
+  sigma.assign(coarseEvecs.size(), 0.0);
+  check(mugiq_hip_compute_evals_coarse_operator_grid(coarseEvecs.data(), (int)coarseEvecs.size(), coarseOp.desc(), &halo, opType,
+                                                     massNormalization ? 1 : 0, reinterpret_cast<double *>(lambda.data()), residual.data(),
+                                                     sigma.data(), comm, stream));
+  if (opType == MUGIQ_HIP_EIG_OPERATOR_M || opType == MUGIQ_HIP_EIG_OPERATOR_MDAG) sigma.clear();
+}
 // Eigsolve_Mugiq::projectVector, lib/eigsolve_mugiq.cpp:340-348
 inline void projectVector(ColorSpinorField &out, ColorSpinorField &in, const std::vector<ColorSpinorField> &eVecs, const MugiqHipComm *comm = nullptr,
                           void *stream = nullptr) {

@@ -7,7 +7,7 @@ from . import _lib
 
 _lib.load()
 
-from .fields import SpinorField, GaugeField, CloverField, CoarseField, CoarseOperator, Transfer, FLOAT2, FLOAT4  # noqa: E402
+from .fields import SpinorField, GaugeField, CloverField, CoarseField, CoarseOperator, CoarseHalo, Transfer, FLOAT2, FLOAT4  # noqa: E402
 from .operators import (  # noqa: E402
     copyGammaCoeffStructToSymbol, copyGammaMapStructToSymbol, gammaTables, GammaName,
     performLoopContraction, performLoopContractionBatched, performCovariantDisplacementVector, packFace, exchangeGhostVec,
@@ -29,7 +29,7 @@ from .loop import (  # noqa: E402
 from .comm import GridComm, RcclComm  # noqa: E402
 from .displace import Displace, DISPLACE_TYPE_COVARIANT  # noqa: E402
 from .eigsolve import (  # noqa: E402
-    Eigsolve_Mugiq, wilsonApply, computeEvals, computeEvalsCoarse, computeCoarseOperator, computeCoarseOperatorCoarse, coarseApply, coarseApplyForm, projectVector, wilsonSolve, SolveInfo,
+    Eigsolve_Mugiq, wilsonApply, computeEvals, computeEvalsCoarse, computeCoarseOperator, computeCoarseOperatorCoarse, coarseApply, coarseApplyForm, computeCoarseOperatorGrid, coarseApplyGrid, computeEvalsCoarseGrid, projectVector, wilsonSolve, SolveInfo,
     mgSolve, mgPrecondition, mgSolveMixed, mgPreconditionSloppy, mgConvertPrecision, mgSolveParam, MgSolveInfo, mgSetup, mgSetupCoarse, MgSetupCoarseInfo, mgSetupParam, mgStartVectors, MgSetupInfo,
     coarseGram, coarseRotate, hermitianEigh, choleskyUpper, upperTriangularInverse, coarseEigensolve, coarseEigParam, coarseStartVectors, CoarseEigInfo,
     CoarseDeflation, coarseDeflate,

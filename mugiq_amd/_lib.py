@@ -65,6 +65,12 @@ class CoarseOperatorDesc(ctypes.Structure):
                 ("kappa", ctypes.c_double), ("hasClover", ctypes.c_int)]
 
 
+class CoarseHaloDesc(ctypes.Structure):
+    """MugiqHipCoarseHalo (include/mugiq_hip.h)."""
+    _fields_ = [("Yback", ctypes.c_void_p * 4), ("Yfwd", ctypes.c_void_p * 4), ("precision", ctypes.c_int), ("nVec", ctypes.c_int),
+                ("X", ctypes.c_int * 4), ("volumeCB", ctypes.c_int), ("dims", ctypes.c_int * 4)]
+
+
 class MgSolveParam(ctypes.Structure):
     """MugiqHipMgSolveParam (include/mugiq_hip.h)."""
     _fields_ = [("tol", ctypes.c_double), ("maxIter", ctypes.c_int), ("nKrylov", ctypes.c_int), ("nuPre", ctypes.c_int), ("nuPost", ctypes.c_int),
@@ -260,6 +266,17 @@ SIGNATURES = {
     "mugiq_hip_compute_evals_coarse_operator": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int,
                                                                ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                                ctypes.POINTER(ctypes.c_double), _VP, _VP]),
+    "mugiq_hip_coarse_halo_bytes": (ctypes.c_size_t, [_I4, ctypes.c_int, ctypes.c_int, _I4]),
+    "mugiq_hip_alloc_coarse_halo": (ctypes.c_int, [ctypes.POINTER(CoarseHaloDesc), ctypes.POINTER(CoarseOperatorDesc), _I4]),
+    "mugiq_hip_free_coarse_halo": (ctypes.c_int, [ctypes.POINTER(CoarseHaloDesc)]),
+    "mugiq_hip_compute_coarse_operator_grid": (ctypes.c_int, [ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(CoarseHaloDesc), ctypes.POINTER(TransferDesc),
+                                                              _GP, _CP, ctypes.c_double, _VP, _VP]),
+    "mugiq_hip_coarse_apply_grid": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(CoarseOperatorDesc),
+                                                   ctypes.POINTER(CoarseHaloDesc), ctypes.c_int, ctypes.c_double, _VP, _VP]),
+    "mugiq_hip_compute_evals_coarse_operator_grid": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(CoarseOperatorDesc),
+                                                                    ctypes.POINTER(CoarseHaloDesc), ctypes.c_int, ctypes.c_int,
+                                                                    ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                                    ctypes.POINTER(ctypes.c_double), _VP, _VP]),
     "mugiq_hip_compute_coarse_operator_coarse": (ctypes.c_int, [ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(TransferDesc),
                                                                 ctypes.POINTER(CoarseOperatorDesc), _VP, _VP]),
     "mugiq_hip_transfer_set_coarse_vectors": (ctypes.c_int, [ctypes.POINTER(TransferDesc), ctypes.POINTER(CoarseDesc), ctypes.c_int, _VP]),

@@ -20,6 +20,10 @@
 // adjoint: the matrices of the neighbour sites, conjugate-transposed) reads the same runs and adds the rows g, g + 16, ... into its
 // columns l + 16 k.  The 16 partial sums of an output meet in LDS and are added in a fixed order by one lane.  Every vector has its own
 // accumulators and the same order wherever it stands in the batch.
+//
+// A process grid (the ..._grid entry points): both kernels have a ghost path as a template flag -- a hop that leaves the
+// rank reads the neighbour's rows (build) or vectors (apply) from a face the neighbour rank sent, and M^dag its matrix from the
+// MugiqHipCoarseHalo -- behind pack kernels and one transfer group per launch.  Terms, products and their order do not change.
 #include "mg_common.h"
 #include "op_forms.h"
 
@@ -78,7 +82,24 @@ struct CoarseBuildArgs {
   double kappa;
 };
 
-template <typename FV, typename FG> __global__ __launch_bounds__(kCbThreads) void coarse_build_kernel(CoarseBuildArgs a) {
+// The ghost path of a process grid, a template flag of both kernels: what a workgroup reads in place of the body when its hop leaves the
+// rank -- a condition that is uniform over the workgroup, which owns one aggregate (build) or one coarse site (apply).  Without the flag
+// the struct is empty and the kernel is the code it was.  Face indexing: MugiqHipCoarseHalo in include/mugiq_hip.h; [..][0] came from the
+// backward neighbour (its high face), [..][1] from the forward one (its low face)
+template <bool GHOST> struct BuildGhost {};
+template <> struct BuildGhost<true> {
+  const void *Vg[4][2];  // faces of V: [parity][(3s+c)*NV + j][faceCB]
+  int part[4], faceCB[4];
+};
+template <bool GHOST> struct ApplyGhost {};
+template <> struct ApplyGhost<true> {
+  const void *vec[4][2];  // faces of the input vectors of the launch: [vector][parity][N][faceCB]
+  const void *Y[4][2];    // MugiqHipCoarseHalo: Yback[mu] (Y+_mu of the backward neighbour's high face), Yfwd[mu] (Y-_mu of the forward one's low face)
+  int part[4], faceCB[4];
+};
+
+template <typename FV, typename FG, bool GHOST>
+__global__ __launch_bounds__(kCbThreads) void coarse_build_kernel(CoarseBuildArgs a, BuildGhost<GHOST> gh) {
   extern __shared__ Cplx<double> build_lds[];
   __shared__ Cplx<double> Um[9], Acl[72];
   const int NV = a.NV, N = 2 * NV, t = threadIdx.x;
@@ -168,6 +189,17 @@ template <typename FV, typename FG> __global__ __launch_bounds__(kCbThreads) voi
         dx[mu] = fwd ? 1 : -1;
         const int npty = 1 - pty, nidx = link_index_shift(x, dx, a.g.X);
         const double sg = fwd ? -1.0 : 1.0;  // (1 - g_mu) forward, (1 + g_mu) backward
+        // GHOST: the hop leaves the rank -- the neighbour's rows wait in the face the neighbour rank sent (the link comes from the border)
+        [[maybe_unused]] const void *Vn = a.V;
+        [[maybe_unused]] int nstride = a.Vstride;
+        [[maybe_unused]] int64_t nbase = npty * a.Vpo + nidx;
+        if constexpr (GHOST) {
+          if (gh.part[mu] && (fwd ? x[mu] + 1 == a.g.X[mu] : x[mu] == 0)) {
+            Vn = gh.Vg[mu][fwd];
+            nstride = gh.faceCB[mu];
+            nbase = (int64_t)npty * 12 * NV * nstride + ghost_face_index_on_face(x, a.g.X, mu);
+          }
+        }
         for (int idx = t; idx < 8 * NV; idx += kCbThreads) {
           const int s = idx / N, rem = idx - s * N, Sp = rem / NV, jp = rem - Sp * NV;
           int ph, col;
@@ -177,7 +209,9 @@ template <typename FV, typename FG> __global__ __launch_bounds__(kCbThreads) voi
           Cplx<double> T[3];
 #pragma unroll
           for (int cp = 0; cp < 3; cp++) {
-            const Cplx<double> v = ld_wide<FV>(a.V, npty * a.Vpo + (int64_t)((3 * ss + cp) * NV + jp) * a.Vstride + nidx);
+            Cplx<double> v;
+            if constexpr (!GHOST) v = ld_wide<FV>(a.V, npty * a.Vpo + (int64_t)((3 * ss + cp) * NV + jp) * a.Vstride + nidx);
+            else v = ld_wide<FV>(Vn, nbase + (int64_t)((3 * ss + cp) * NV + jp) * nstride);
             const Cplx<double> gv = mul_phase(ph, v);
             T[cp] = same ? v : Cplx<double>{sg * gv.re, sg * gv.im};
           }
@@ -207,7 +241,7 @@ template <typename FV, typename FG> __global__ __launch_bounds__(kCbThreads) voi
 
 template <typename FV, typename FG>
 int launch_build(const MugiqHipCoarseOperator *op, const MugiqHipTransfer *T, const MugiqHipGaugeField *U, const MugiqHipCloverField *C, double kappa,
-                 hipStream_t stream) {
+                 hipStream_t stream, const BuildGhost<true> *gh = nullptr) {
   CoarseBuildArgs a;
   a.V = T->V;
   a.Vpo = T->parity_offset;
@@ -229,7 +263,8 @@ int launch_build(const MugiqHipCoarseOperator *op, const MugiqHipTransfer *T, co
   const int N = 2 * a.NV, per = kCbThreads * kCbEPT;
   const dim3 grid(2 * a.g.volumeCBc, 9, (N * N + per - 1) / per);
   const size_t lds = sizeof(Cplx<double>) * (size_t)(12 * a.NV + 12 * N);
-  hipLaunchKernelGGL((coarse_build_kernel<FV, FG>), grid, dim3(kCbThreads), lds, stream, a);
+  if (gh) hipLaunchKernelGGL((coarse_build_kernel<FV, FG, true>), grid, dim3(kCbThreads), lds, stream, a, *gh);
+  else hipLaunchKernelGGL((coarse_build_kernel<FV, FG, false>), grid, dim3(kCbThreads), lds, stream, a, BuildGhost<false>{});
   MUGIQ_CHECK_HIP(hipGetLastError());
   return MUGIQ_HIP_SUCCESS;
 }
@@ -249,7 +284,8 @@ struct CoarseApplyArgs {
 // N / OUT chunks.  What one output is made of does not depend on OUT -- the 9 matrices in order, lane l over c = l, l + 16, ..., then
 // the 16 partial sums in ascending order, every product an explicit fma -- so all three give the same bits; a smaller OUT only spreads a
 // small lattice over more workgroups (launch_apply chooses)
-template <typename F, int DAG, int OUT> __global__ __launch_bounds__(kCaThreads) void coarse_apply_kernel(CoarseApplyArgs a) {
+template <typename F, int DAG, int OUT, bool GHOST>
+__global__ __launch_bounds__(kCaThreads) void coarse_apply_kernel(CoarseApplyArgs a, ApplyGhost<GHOST> gh) {
   static_assert(OUT == 16 || OUT == 32 || OUT == 64, "outputs per workgroup");
   constexpr int NI = OUT / 16;                     // outputs per group or lane
   extern __shared__ Cplx<double> in_s[];           // [8][N]: the input vectors at the neighbour of the current matrix
@@ -274,12 +310,31 @@ template <typename F, int DAG, int OUT> __global__ __launch_bounds__(kCaThreads)
     if (m > 0) nc[mu] = (cc[mu] + (fwd ? 1 : a.Xc[mu] - 1)) % a.Xc[mu];
     const int npar = m == 0 ? cpar : 1 - cpar, nx = lex_index(nc, a.Xc) >> 1;
     const int msite = DAG ? npar * a.volumeCBc + nx : site, mm = (DAG && m > 0) ? (fwd ? m + 1 : m - 1) : m;
-    const int64_t mbase = ((int64_t)msite * 9 + mm) * N * N;
+    int64_t mbase = ((int64_t)msite * 9 + mm) * N * N;
+    const void *mptr = a.op;
     __syncthreads();  // the previous matrix is through
-    for (int idx = t; idx < kCaRB * N; idx += kCaThreads) {
-      const int v = idx / N, c = idx - v * N;
-      in_s[idx] = ld_wide<F>(tab[min(n0 + v, a.nVec - 1)], npar * a.Spo + (int64_t)c * a.Sstride + nx);  // (vectors past the end shadow the last one)
+    bool staged = false;
+    if constexpr (GHOST) {
+      // the input site is on the neighbour rank: its vectors are in the face that rank sent, and the matrix M^dag wants in the halo
+      if (m > 0 && gh.part[mu] && cc[mu] == (fwd ? a.Xc[mu] - 1 : 0)) {
+        const int fcb = gh.faceCB[mu], fidx = ghost_face_index_on_face(cc, a.Xc, mu);
+        const void *face = gh.vec[mu][fwd];
+        for (int idx = t; idx < kCaRB * N; idx += kCaThreads) {
+          const int v = idx / N, c = idx - v * N;
+          in_s[idx] = ld_wide<F>(face, (((int64_t)min(n0 + v, a.nVec - 1) * 2 + npar) * N + c) * fcb + fidx);
+        }
+        if (DAG) {
+          mptr = gh.Y[mu][fwd];
+          mbase = ((int64_t)npar * fcb + fidx) * N * N;
+        }
+        staged = true;
+      }
     }
+    if (!staged)
+      for (int idx = t; idx < kCaRB * N; idx += kCaThreads) {
+        const int v = idx / N, c = idx - v * N;
+        in_s[idx] = ld_wide<F>(tab[min(n0 + v, a.nVec - 1)], npar * a.Spo + (int64_t)c * a.Sstride + nx);  // (vectors past the end shadow the last one)
+      }
     __syncthreads();
     if constexpr (!DAG) {
       for (int c = l; c < N; c += 16) {
@@ -290,7 +345,7 @@ template <typename F, int DAG, int OUT> __global__ __launch_bounds__(kCaThreads)
         for (int i = 0; i < NI; i++) {
           const int r = o0 + g + 16 * i;
           if (r < N) {
-            const Cplx<double> e = ld_wide<F>(a.op, mbase + (int64_t)r * N + c);
+            const Cplx<double> e = ld_wide<F>(mptr, mbase + (int64_t)r * N + c);
 #pragma unroll
             for (int v = 0; v < kCaRB; v++) cmadd(acc[i][v], e, x[v]);
           }
@@ -305,7 +360,7 @@ template <typename F, int DAG, int OUT> __global__ __launch_bounds__(kCaThreads)
         for (int k = 0; k < NI; k++) {
           const int c = o0 + l + 16 * k;
           if (c < N) {
-            const Cplx<double> e = ld_wide<F>(a.op, mbase + (int64_t)r * N + c);
+            const Cplx<double> e = ld_wide<F>(mptr, mbase + (int64_t)r * N + c);
 #pragma unroll
             for (int v = 0; v < kCaRB; v++) cmadd_conj(acc[k][v], e, x[v]);
           }
@@ -354,17 +409,25 @@ int apply_outputs_per_workgroup(const MugiqHipCoarseOperator *op, int n) {
   return (int64_t)g.x * g.y * g.z < kCaSmallGrid ? 32 : kCaOut;
 }
 
-template <typename F, int DAG>
-void launch_apply_form(int out, dim3 grid, size_t lds, hipStream_t stream, const CoarseApplyArgs &a, int N) {
+template <typename F, int DAG, bool GHOST>
+void launch_apply_form(int out, dim3 grid, size_t lds, hipStream_t stream, const CoarseApplyArgs &a, int N, const ApplyGhost<GHOST> &gh) {
   grid.z = (N + out - 1) / out;
-  if (out == 16) hipLaunchKernelGGL((coarse_apply_kernel<F, DAG, 16>), grid, dim3(kCaThreads), lds, stream, a);
-  else if (out == 32) hipLaunchKernelGGL((coarse_apply_kernel<F, DAG, 32>), grid, dim3(kCaThreads), lds, stream, a);
-  else hipLaunchKernelGGL((coarse_apply_kernel<F, DAG, 64>), grid, dim3(kCaThreads), lds, stream, a);
+  if (out == 16) hipLaunchKernelGGL((coarse_apply_kernel<F, DAG, 16, GHOST>), grid, dim3(kCaThreads), lds, stream, a, gh);
+  else if (out == 32) hipLaunchKernelGGL((coarse_apply_kernel<F, DAG, 32, GHOST>), grid, dim3(kCaThreads), lds, stream, a, gh);
+  else hipLaunchKernelGGL((coarse_apply_kernel<F, DAG, 64, GHOST>), grid, dim3(kCaThreads), lds, stream, a, gh);
+}
+template <bool GHOST>
+void launch_apply_storage(int precision, int dagger, int out, dim3 grid, size_t lds, hipStream_t stream, const CoarseApplyArgs &a, int N,
+                          const ApplyGhost<GHOST> &gh) {
+  if (precision == 8 && !dagger) launch_apply_form<double, 0>(out, grid, lds, stream, a, N, gh);
+  else if (precision == 8) launch_apply_form<double, 1>(out, grid, lds, stream, a, N, gh);
+  else if (!dagger) launch_apply_form<float, 0>(out, grid, lds, stream, a, N, gh);
+  else launch_apply_form<float, 1>(out, grid, lds, stream, a, N, gh);
 }
 
-// dst_i = scale [G5] M_c^(dag) src_i, i < n
+// dst_i = scale [G5] M_c^(dag) src_i, i < n;  gh: the faces and halo matrices of a process grid (NULL: one domain)
 int launch_apply(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src, int n, const MugiqHipCoarseOperator *op, int dagger, int gamma5,
-                 double scale, hipStream_t stream) {
+                 double scale, hipStream_t stream, const ApplyGhost<true> *gh = nullptr) {
   std::vector<const void *> host(2 * (size_t)n);
   for (int i = 0; i < n; i++) {
     host[i] = src[i].data;
@@ -389,13 +452,106 @@ int launch_apply(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src,
   const dim3 grid = apply_grid64(op, n);
   const int out = apply_outputs_per_workgroup(op, n);
   const size_t lds = sizeof(Cplx<double>) * (size_t)kCaRB * N;
-  if (op->precision == 8 && !dagger) launch_apply_form<double, 0>(out, grid, lds, stream, a, N);
-  else if (op->precision == 8) launch_apply_form<double, 1>(out, grid, lds, stream, a, N);
-  else if (!dagger) launch_apply_form<float, 0>(out, grid, lds, stream, a, N);
-  else launch_apply_form<float, 1>(out, grid, lds, stream, a, N);
+  if (gh) launch_apply_storage(op->precision, dagger, out, grid, lds, stream, a, N, *gh);
+  else launch_apply_storage(op->precision, dagger, out, grid, lds, stream, a, N, ApplyGhost<false>{});
   MUGIQ_CHECK_HIP(hipGetLastError());
   return MUGIQ_HIP_SUCCESS;
 }
+
+// ---- the faces of a process grid ----------------------------------------------------------------------------------------------------
+// The face site (parity par, index f < faceCB) of axis mu, low (x[mu] = 0) or high (X[mu] - 1): its checkerboard index in the body.  The
+// three other coordinates in lexicographic order, lowest axis fastest, halved (the lowest of them has an even extent, so the parity picks
+// one of the pair 2 f, 2 f + 1): the inverse of ghost_face_index_on_face
+__device__ inline int face_site_cb(const int X[4], int mu, int high, int par, int f) {
+  int c[4], q = 2 * f, low = -1, sum = 0;
+#pragma unroll
+  for (int d = 0; d < 4; d++) {
+    if (d == mu) {
+      c[d] = high ? X[d] - 1 : 0;
+    } else {
+      c[d] = q % X[d];
+      q /= X[d];
+      if (low < 0) low = d;
+    }
+    sum += c[d];
+  }
+  c[low] += (par - sum) & 1;
+  return lex_index(c, X) >> 1;
+}
+
+// Faces of fields stored as rows of sites (V: 12 n_vec rows; a coarse vector: N rows), for one body or a table of them:
+// out[vector][parity][row][f] = body_vector[parity * po + row * stride + site(parity, f)].  One lane per (row, f), f fastest on both sides
+struct FacePackArgs {
+  const void *const *tab;  // device table of bodies (NULL: the one body `body`)
+  const void *body;
+  void *out;
+  int rows, stride;
+  int64_t po;
+  int X[4], mu, high, faceCB;
+};
+template <typename F> __global__ __launch_bounds__(256) void face_pack_kernel(FacePackArgs a) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)a.rows * a.faceCB) return;
+  const int row = (int)(idx / a.faceCB), f = (int)(idx - (int64_t)row * a.faceCB), par = blockIdx.y & 1;
+  const void *src = a.tab ? as_constant(a.tab)[blockIdx.y >> 1] : a.body;
+  const Cplx<double> v = ld_wide<F>(src, par * a.po + (int64_t)row * a.stride + face_site_cb(a.X, a.mu, a.high, par, f));
+  st_round<F>(a.out, (int64_t)blockIdx.y * a.rows * a.faceCB + idx, v);
+}
+
+// Matrix m of every site of a face, matrix-contiguous: out[(parity * faceCB + f) * N^2 + e].  One workgroup per face site
+struct MatrixPackArgs {
+  const void *op;
+  void *out;
+  int NN, volumeCB, X[4], mu, high, faceCB, m;
+};
+template <typename F> __global__ __launch_bounds__(256) void matrix_face_pack_kernel(MatrixPackArgs a) {
+  const int par = blockIdx.x / a.faceCB, f = blockIdx.x - par * a.faceCB;
+  const int64_t sbase = (((int64_t)par * a.volumeCB + face_site_cb(a.X, a.mu, a.high, par, f)) * 9 + a.m) * a.NN, obase = (int64_t)blockIdx.x * a.NN;
+  for (int e = threadIdx.x; e < a.NN; e += 256) st_round<F>(a.out, obase + e, ld_wide<F>(a.op, sbase + e));
+}
+
+// The send and receive buffers of one exchange: per partitioned axis the low face [0] and the high face [1] to send, and what arrives
+// from the backward [0] and the forward [1] neighbour
+struct FaceBuffers {
+  unsigned char *send[4][2] = {}, *recv[4][2] = {};
+  size_t bytes[4] = {0, 0, 0, 0};  // of one message
+};
+// ... carved from *cur, `cap[d]` bytes each (0: the axis is not partitioned); receive buffers only where recvToo
+void carve_faces(FaceBuffers *b, unsigned char **cur, const size_t cap[4], bool recvToo) {
+  for (int d = 0; d < 4; d++)
+    for (int k = 0; k < (recvToo ? 4 : 2); k++) {
+      if (cap[d] == 0) continue;
+      (k < 2 ? b->send[d][k] : b->recv[d][k - 2]) = *cur;
+      *cur += align256(cap[d]);
+    }
+}
+// One transfer group: pack(d, high, send buffer) launches the pack kernel of a face; the high face goes forward and arrives, on the
+// forward neighbour, from the backward one
+template <typename Pack>
+int exchange_faces(const MugiqHipComm *comm, const int part[4], const FaceBuffers &b, hipStream_t stream, const char *who, Pack &&pack) {
+  int st;
+  const bool grouped = comm->group_begin && comm->group_end;
+  if (grouped && (st = comm->group_begin(comm->ctx))) return set_error(MUGIQ_HIP_ERROR_HIP, "%s: group_begin callback failed with status %d", who, st);
+  for (int d = 0; d < 4; d++) {
+    if (!part[d]) continue;
+    for (int high = 0; high < 2; high++) {
+      if ((st = pack(d, high, b.send[d][high]))) return st;
+      if ((st = comm->sendrecv(comm->ctx, b.send[d][high], b.recv[d][1 - high], b.bytes[d], d, high ? +1 : -1, stream)))
+        return set_error(MUGIQ_HIP_ERROR_HIP, "%s: halo sendrecv callback failed with status %d", who, st);
+    }
+  }
+  if (grouped && (st = comm->group_end(comm->ctx, stream))) return set_error(MUGIQ_HIP_ERROR_HIP, "%s: group_end callback failed with status %d", who, st);
+  return MUGIQ_HIP_SUCCESS;
+}
+
+template <typename F> int launch_face_pack(FacePackArgs a, int nBodies, hipStream_t stream) {
+  const int64_t per = (int64_t)a.rows * a.faceCB;
+  hipLaunchKernelGGL((face_pack_kernel<F>), dim3((unsigned)((per + 255) / 256), 2 * nBodies), dim3(256), 0, stream, a);
+  MUGIQ_CHECK_HIP(hipGetLastError());
+  return MUGIQ_HIP_SUCCESS;
+}
+
+bool any_partitioned(const int part[4]) { return part[0] || part[1] || part[2] || part[3]; }
 
 size_t operator_elems(const int Xc[4], int nVec) {
   size_t vol = 1;
@@ -479,6 +635,74 @@ int coarse_apply(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src,
   return MUGIQ_HIP_SUCCESS;
 }
 
+int check_coarse_grid(const MugiqHipComm *comm, const MugiqHipCoarseOperator *op, const MugiqHipCoarseHalo *halo, int part[4], bool needSums,
+                      const char *who) {
+  int st;
+  if ((st = check_comm(comm, part, needSums, who))) return st;
+  if ((st = validate_coarse_operator(op, who))) return st;
+  MUGIQ_REQUIRE(!any_partitioned(part) || halo != nullptr, "%s: the comm has a partitioned axis but the coarse halo is NULL", who);
+  if (halo == nullptr) return MUGIQ_HIP_SUCCESS;
+  MUGIQ_REQUIRE(halo->precision == op->precision && halo->nVec == op->nVec && halo->volumeCB == op->volumeCB,
+                "%s: the coarse halo (precision %d, n_vec %d, volumeCB %d) does not belong to the coarse operator (precision %d, n_vec %d, volumeCB %d)", who,
+                halo->precision, halo->nVec, halo->volumeCB, op->precision, op->nVec, op->volumeCB);
+  for (int d = 0; d < 4; d++) MUGIQ_REQUIRE(halo->X[d] == op->X[d], "%s: coarse halo X[%d] = %d, the coarse operator's is %d", who, d, halo->X[d], op->X[d]);
+  for (int d = 0; d < 4; d++)
+    MUGIQ_REQUIRE(!part[d] || (halo->dims[d] && halo->Yback[d] && halo->Yfwd[d]), "%s: dimension %d is partitioned but the coarse halo was not built for it",
+                  who, d);
+  return MUGIQ_HIP_SUCCESS;
+}
+
+// validated arguments.  Work memory (per-stream workspace): [the intermediate of a normal form, 8 vectors][per partitioned axis: two send
+// and two receive faces of the most vectors one launch takes].  Per launch: faces packed and exchanged (one group), then the kernel
+int coarse_apply_grid(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src, int nVec, const MugiqHipCoarseOperator *op,
+                      const MugiqHipCoarseHalo *halo, const int part[4], int opType, double scale, const MugiqHipComm *comm, hipStream_t stream) {
+  if (!any_partitioned(part)) return coarse_apply(dst, src, nVec, op, opType, scale, stream);
+  const char *who = "coarseApplyGrid";
+  const int N = 2 * op->nVec, perLaunch = normal_op(opType) ? std::min(kCaRB, nVec) : nVec;
+  const size_t cplx = 2 * (size_t)op->precision, one = normal_op(opType) ? align256((size_t)2 * N * op->volumeCB * cplx) : 0;
+  ApplyGhost<true> gh;
+  size_t cap[4], total = kCaRB * one;
+  for (int d = 0; d < 4; d++) {
+    gh.part[d] = part[d];
+    gh.faceCB[d] = op->volumeCB / op->X[d];
+    gh.Y[d][0] = part[d] ? halo->Yback[d] : nullptr;
+    gh.Y[d][1] = part[d] ? halo->Yfwd[d] : nullptr;
+    cap[d] = part[d] ? (size_t)perLaunch * 2 * N * gh.faceCB[d] * cplx : 0;
+    total += 4 * align256(cap[d]);
+  }
+  void *ws = nullptr;
+  if (int st = stream_workspace(&ws, total, stream)) return st;
+  unsigned char *cur = static_cast<unsigned char *>(ws) + kCaRB * one;
+  FaceBuffers fb;
+  carve_faces(&fb, &cur, cap, true);
+  for (int d = 0; d < 4; d++) gh.vec[d][0] = fb.recv[d][0], gh.vec[d][1] = fb.recv[d][1];
+
+  auto simple = [&](const MugiqHipCoarseField *d_, const MugiqHipCoarseField *s_, int n, int dagger, int gamma5, double f) -> int {
+    std::vector<const void *> host(2 * (size_t)n);  // (the size of launch_apply's table, so the buffer stays where it is)
+    for (int i = 0; i < n; i++) host[i] = host[n + i] = s_[i].data;
+    void *dev = nullptr;
+    if (int st = upload_table(&dev, host.data(), host.size() * sizeof(void *), stream)) return st;
+    for (int d = 0; d < 4; d++) fb.bytes[d] = part[d] ? (size_t)n * 2 * N * gh.faceCB[d] * cplx : 0;
+    int st = exchange_faces(comm, part, fb, stream, who, [&](int d, int high, unsigned char *send) {
+      FacePackArgs p{static_cast<const void *const *>(dev), nullptr, send, N, s_[0].stride, s_[0].parity_offset, {op->X[0], op->X[1], op->X[2], op->X[3]}, d, high, gh.faceCB[d]};
+      return with_storage(op->precision, [&](auto fs) { return launch_face_pack<decltype(fs)>(p, n, stream); });
+    });
+    if (st) return st;
+    return launch_apply(d_, s_, n, op, dagger, gamma5, f, stream, &gh);
+  };
+  MugiqHipCoarseField tmp[kCaRB];
+  if (!normal_op(opType)) return apply_form(opType, simple, dst, src, tmp, nVec, scale);
+  for (int i = 0; i < kCaRB; i++) {
+    tmp[i] = src[0];
+    tmp[i].data = static_cast<unsigned char *>(ws) + i * one;
+    tmp[i].stride = op->volumeCB;
+    tmp[i].parity_offset = (int64_t)2 * op->nVec * op->volumeCB;
+  }
+  for (int v0 = 0; v0 < nVec; v0 += kCaRB)
+    if (int st = apply_form(opType, simple, dst + v0, src + v0, tmp, std::min(kCaRB, nVec - v0), scale)) return st;
+  return MUGIQ_HIP_SUCCESS;
+}
+
 }  // namespace mugiq
 
 using namespace mugiq;
@@ -522,17 +746,38 @@ int mugiq_hip_free_coarse_operator(MugiqHipCoarseOperator *op) {
   return MUGIQ_HIP_SUCCESS;
 }
 
-int mugiq_hip_compute_coarse_operator(MugiqHipCoarseOperator *op, const MugiqHipTransfer *transfer, const MugiqHipGaugeField *gauge,
-                                      const MugiqHipCloverField *clover, double kappa, const MugiqHipComm *comm, void *stream) {
-  const char *who = "computeCoarseOperator";
+}  // extern "C"
+
+namespace {
+
+// The faces of V to the neighbours (one group), into ws: the ghost arguments of the build
+int exchange_transfer_faces(BuildGhost<true> *gh, FaceBuffers *fb, const MugiqHipTransfer *T, const int part[4], const MugiqHipComm *comm,
+                            hipStream_t stream, const char *who) {
+  const int rows = 12 * T->nVec;
+  for (int d = 0; d < 4; d++) {
+    gh->part[d] = part[d];
+    gh->Vg[d][0] = fb->recv[d][0], gh->Vg[d][1] = fb->recv[d][1];
+  }
+  return exchange_faces(comm, part, *fb, stream, who, [&](int d, int high, unsigned char *send) {
+    FacePackArgs p{nullptr, T->V, send, rows, T->stride, T->parity_offset, {T->X[0], T->X[1], T->X[2], T->X[3]}, d, high, gh->faceCB[d]};
+    return with_storage(T->precision, [&](auto fv) { return launch_face_pack<decltype(fv)>(p, 1, stream); });
+  });
+}
+
+// mugiq_hip_compute_coarse_operator (grid false: one domain, or MUGIQ_HIP_ERROR_UNSUPPORTED) and ..._grid
+int compute_coarse_operator(MugiqHipCoarseOperator *op, const MugiqHipCoarseHalo *halo, const MugiqHipTransfer *transfer, const MugiqHipGaugeField *gauge,
+                            const MugiqHipCloverField *clover, double kappa, const MugiqHipComm *comm, void *stream, const char *who, bool grid) {
   // ---- validation, before any device work
   MUGIQ_REQUIRE(op != nullptr && transfer != nullptr, "%s: NULL argument", who);
-  int st;
-  if ((st = check_single_domain(comm, who))) return st;
-  if ((st = validate_coarse_operator(op, who))) return st;
+  int st, part[4] = {0, 0, 0, 0};
+  if (grid) {
+    if ((st = check_coarse_grid(comm, op, halo, part, false, who))) return st;
+  } else {
+    if ((st = check_single_domain(comm, who))) return st;
+    if ((st = validate_coarse_operator(op, who))) return st;
+  }
   MUGIQ_REQUIRE(transfer->V != nullptr, "%s: transfer / null vectors are NULL", who);
   if ((st = validate_transfer_operator(transfer, op, who))) return st;
-  const int part[4] = {0, 0, 0, 0};
   if ((st = check_gauge(gauge, transfer->X, part, who))) return st;
   const TransferGeom g = transfer_geom(*transfer);
   if (clover) {
@@ -541,8 +786,50 @@ int mugiq_hip_compute_coarse_operator(MugiqHipCoarseOperator *op, const MugiqHip
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
-  st = with_storage(transfer->precision, gauge->precision, [&](auto fv, auto fg) {
-    return launch_build<decltype(fv), decltype(fg)>(op, transfer, gauge, clover, kappa, s);
+  if (!any_partitioned(part)) {
+    st = with_storage(transfer->precision, gauge->precision, [&](auto fv, auto fg) {
+      return launch_build<decltype(fv), decltype(fg)>(op, transfer, gauge, clover, kappa, s);
+    });
+    if (st) return st;
+    op->kappa = kappa;
+    op->hasClover = clover ? 1 : 0;
+    return MUGIQ_HIP_SUCCESS;
+  }
+  // ---- a process grid.  Work memory (per-stream workspace): per partitioned axis two send and two receive faces of V, two send faces of Y
+  const size_t cplx = 2 * (size_t)op->precision, NN = (size_t)4 * op->nVec * op->nVec;
+  BuildGhost<true> gh;
+  size_t capV[4], capY[4], total = 0;
+  int faceCBc[4];
+  for (int d = 0; d < 4; d++) {
+    gh.faceCB[d] = g.volumeCB / transfer->X[d];
+    faceCBc[d] = op->volumeCB / op->X[d];
+    capV[d] = part[d] ? (size_t)2 * 12 * transfer->nVec * gh.faceCB[d] * cplx : 0;
+    capY[d] = part[d] ? (size_t)2 * faceCBc[d] * NN * cplx : 0;
+    total += 4 * align256(capV[d]) + 2 * align256(capY[d]);
+  }
+  void *ws = nullptr;
+  if ((st = stream_workspace(&ws, total, s))) return st;
+  unsigned char *cur = static_cast<unsigned char *>(ws);
+  FaceBuffers fv, fy;
+  carve_faces(&fv, &cur, capV, true);
+  carve_faces(&fy, &cur, capY, false);
+  for (int d = 0; d < 4; d++) {
+    fv.bytes[d] = capV[d], fy.bytes[d] = capY[d];
+    fy.recv[d][0] = static_cast<unsigned char *>(halo->Yback[d]), fy.recv[d][1] = static_cast<unsigned char *>(halo->Yfwd[d]);
+  }
+  if ((st = exchange_transfer_faces(&gh, &fv, transfer, part, comm, s, who))) return st;
+  st = with_storage(transfer->precision, gauge->precision, [&](auto fv_, auto fg) {
+    return launch_build<decltype(fv_), decltype(fg)>(op, transfer, gauge, clover, kappa, s, &gh);
+  });
+  if (st) return st;
+  // Y+_mu of the high face goes forward (the neighbour's Yback), Y-_mu of the low face backward (its Yfwd)
+  st = exchange_faces(comm, part, fy, s, who, [&](int d, int high, unsigned char *send) -> int {
+    MatrixPackArgs p{op->data, send, (int)NN, op->volumeCB, {op->X[0], op->X[1], op->X[2], op->X[3]}, d, high, faceCBc[d], high ? 1 + 2 * d : 2 + 2 * d};
+    with_storage(op->precision, [&](auto f) {
+      hipLaunchKernelGGL((matrix_face_pack_kernel<decltype(f)>), dim3(2 * faceCBc[d]), dim3(256), 0, s, p);
+    });
+    MUGIQ_CHECK_HIP(hipGetLastError());
+    return MUGIQ_HIP_SUCCESS;
   });
   if (st) return st;
   op->kappa = kappa;
@@ -550,13 +837,90 @@ int mugiq_hip_compute_coarse_operator(MugiqHipCoarseOperator *op, const MugiqHip
   return MUGIQ_HIP_SUCCESS;
 }
 
-int mugiq_hip_coarse_apply(const MugiqHipCoarseField *dst_h, const MugiqHipCoarseField *src_h, int nVec, const MugiqHipCoarseOperator *op, int opType,
-                           double scale, const MugiqHipComm *comm, void *stream) {
-  const char *who = "coarseApply";
+size_t halo_face_elems(const int X[4], int nVec, int d) {
+  size_t vol = 1;
+  for (int k = 0; k < 4; k++) vol *= (size_t)X[k];
+  return vol / (size_t)X[d] * 4 * (size_t)nVec * (size_t)nVec;  // both parities of the face x N^2
+}
+
+}  // namespace
+
+extern "C" {
+
+int mugiq_hip_compute_coarse_operator(MugiqHipCoarseOperator *op, const MugiqHipTransfer *transfer, const MugiqHipGaugeField *gauge,
+                                      const MugiqHipCloverField *clover, double kappa, const MugiqHipComm *comm, void *stream) {
+  return compute_coarse_operator(op, nullptr, transfer, gauge, clover, kappa, comm, stream, "computeCoarseOperator", false);
+}
+
+int mugiq_hip_compute_coarse_operator_grid(MugiqHipCoarseOperator *op, const MugiqHipCoarseHalo *halo, const MugiqHipTransfer *transfer,
+                                           const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover, double kappa,
+                                           const MugiqHipComm *comm, void *stream) {
+  return compute_coarse_operator(op, halo, transfer, gauge, clover, kappa, comm, stream, "computeCoarseOperatorGrid", true);
+}
+
+size_t mugiq_hip_coarse_halo_bytes(const int X[4], int nVec, int precision, const int dims[4]) {
+  if (!X || !dims || nVec < 1 || nVec > kTransferMaxNV || (precision != 4 && precision != 8)) return 0;
+  size_t bytes = 0;
+  for (int d = 0; d < 4; d++) {
+    if (X[d] <= 0 || (X[d] & 1)) return 0;
+    if (dims[d]) bytes += 2 * halo_face_elems(X, nVec, d) * 2 * (size_t)precision;  // Yback and Yfwd
+  }
+  return bytes;
+}
+
+int mugiq_hip_alloc_coarse_halo(MugiqHipCoarseHalo *halo, const MugiqHipCoarseOperator *op, const int dims[4]) {
+  const char *who = "allocCoarseHalo";
+  MUGIQ_REQUIRE(halo && op && dims, "%s: NULL argument", who);
+  MugiqHipCoarseOperator geom = *op;
+  geom.data = reinterpret_cast<void *>(uintptr_t(16));  // geometry only: never read
+  if (int st = validate_coarse_operator(&geom, who)) return st;
+  halo->precision = op->precision, halo->nVec = op->nVec, halo->volumeCB = op->volumeCB;
+  for (int d = 0; d < 4; d++) {
+    halo->X[d] = op->X[d];
+    halo->dims[d] = dims[d] ? 1 : 0;
+    halo->Yback[d] = halo->Yfwd[d] = nullptr;
+  }
+  for (int d = 0; d < 4; d++) {
+    if (!halo->dims[d]) continue;
+    const size_t bytes = halo_face_elems(op->X, op->nVec, d) * 2 * (size_t)op->precision;
+    for (void **p : {&halo->Yback[d], &halo->Yfwd[d]}) {
+      hipError_t e = hipMalloc(p, bytes);
+      if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
+      else *p = nullptr;
+      if (e != hipSuccess) {  // the caller gets a complete halo or nothing
+        (void)mugiq_hip_free_coarse_halo(halo);
+        return set_error(MUGIQ_HIP_ERROR_HIP, "%s: allocating %zu bytes failed: %s", who, bytes, hipGetErrorString(e));
+      }
+    }
+  }
+  return MUGIQ_HIP_SUCCESS;
+}
+
+int mugiq_hip_free_coarse_halo(MugiqHipCoarseHalo *halo) {
+  if (!halo) return MUGIQ_HIP_SUCCESS;
+  for (int d = 0; d < 4; d++)
+    for (void **p : {&halo->Yback[d], &halo->Yfwd[d]}) {
+      if (*p) MUGIQ_CHECK_HIP(hipFree(*p));
+      *p = nullptr;
+    }
+  return MUGIQ_HIP_SUCCESS;
+}
+
+}  // extern "C"
+
+namespace {
+
+// mugiq_hip_coarse_apply (grid false: one domain, or MUGIQ_HIP_ERROR_UNSUPPORTED) and ..._grid
+int coarse_apply_entry(const MugiqHipCoarseField *dst_h, const MugiqHipCoarseField *src_h, int nVec, const MugiqHipCoarseOperator *op,
+                       const MugiqHipCoarseHalo *halo, int opType, double scale, const MugiqHipComm *comm, void *stream, const char *who, bool grid) {
   MUGIQ_REQUIRE(dst_h != nullptr && src_h != nullptr && nVec >= 1, "%s: NULL / empty argument", who);
-  int st;
-  if ((st = check_single_domain(comm, who))) return st;
-  if ((st = validate_coarse_operator(op, who))) return st;
+  int st, part[4] = {0, 0, 0, 0};
+  if (grid) {
+    if ((st = check_coarse_grid(comm, op, halo, part, false, who))) return st;
+  } else {
+    if ((st = check_single_domain(comm, who))) return st;
+    if ((st = validate_coarse_operator(op, who))) return st;
+  }
   MUGIQ_REQUIRE(valid_op(opType), "%s: opType %d is none of M, Mdag, MdagM, MMdag, H", who, opType);
   if ((st = validate_coarse_vectors(src_h, nVec, op, who, "src"))) return st;
   if ((st = validate_coarse_vectors(dst_h, nVec, op, who, "dst"))) return st;
@@ -571,7 +935,21 @@ int mugiq_hip_coarse_apply(const MugiqHipCoarseField *dst_h, const MugiqHipCoars
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
-  return coarse_apply(dst_h, src_h, nVec, op, opType, scale, s);
+  return coarse_apply_grid(dst_h, src_h, nVec, op, halo, part, opType, scale, comm, s);  // (nothing partitioned: coarse_apply)
+}
+
+}  // namespace
+
+extern "C" {
+
+int mugiq_hip_coarse_apply(const MugiqHipCoarseField *dst_h, const MugiqHipCoarseField *src_h, int nVec, const MugiqHipCoarseOperator *op, int opType,
+                           double scale, const MugiqHipComm *comm, void *stream) {
+  return coarse_apply_entry(dst_h, src_h, nVec, op, nullptr, opType, scale, comm, stream, "coarseApply", false);
+}
+
+int mugiq_hip_coarse_apply_grid(const MugiqHipCoarseField *dst_h, const MugiqHipCoarseField *src_h, int nVec, const MugiqHipCoarseOperator *op,
+                                const MugiqHipCoarseHalo *halo, int opType, double scale, const MugiqHipComm *comm, void *stream) {
+  return coarse_apply_entry(dst_h, src_h, nVec, op, halo, opType, scale, comm, stream, "coarseApplyGrid", true);
 }
 
 int mugiq_hip_coarse_apply_outputs(const MugiqHipCoarseOperator *op, int nVec) {

@@ -145,6 +145,13 @@ int validate_coarse_operator(const MugiqHipCoarseOperator *op, const char *who);
 int validate_coarse_vectors(const MugiqHipCoarseField *f, int n, const MugiqHipCoarseOperator *op, const char *who, const char *name);
 int coarse_apply(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src, int nVec, const MugiqHipCoarseOperator *op, int opType, double scale,
                  hipStream_t stream);
+// ... on a process grid.  check_coarse_grid: comm -> part[4] (check_comm), a valid operator, and the halo of that operator built for every
+// partitioned axis (NULL only where nothing is partitioned), before any device work; coarse_apply_grid: mugiq_hip_coarse_apply_grid behind
+// its validation.  With part all 0 it is coarse_apply
+int check_coarse_grid(const MugiqHipComm *comm, const MugiqHipCoarseOperator *op, const MugiqHipCoarseHalo *halo, int part[4], bool needSums,
+                      const char *who);
+int coarse_apply_grid(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src, int nVec, const MugiqHipCoarseOperator *op,
+                      const MugiqHipCoarseHalo *halo, const int part[4], int opType, double scale, const MugiqHipComm *comm, hipStream_t stream);
 // csrc/wilson.hip: the gauge field of an operator call against the local dims X and the partitioned axes; comm -> part[4]
 int check_gauge(const MugiqHipGaugeField *U, const int X[4], const int part[4], const char *who);
 int check_comm(const MugiqHipComm *comm, int part[4], bool needSums, const char *who);

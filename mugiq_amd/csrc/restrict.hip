@@ -761,15 +761,22 @@ int compute_evals_coarse(const MugiqHipCoarseField *ev, int nEv, const MugiqHipT
 // level, one domain (an unpartitioned comm of several ranks passes check_single_domain: every rank checks its own vectors, nothing is
 // summed).  Work memory (operator workspace of the stream; coarse_apply keeps its intermediate in stream_workspace): 8 coarse vectors laid
 // out like the eigenvectors, lambda and the sums
-int compute_evals_coarse_operator(const MugiqHipCoarseField *ev, int nEv, const MugiqHipCoarseOperator *op, int opType, int massNormalization,
-                                  double *lambda_h, double *residual_h, double *sigma_h, const MugiqHipComm *comm, hipStream_t stream) {
-  const char *who = "computeEvalsCoarse(coarseOp)";
+// grid: mugiq_hip_compute_evals_coarse_operator_grid -- A_c by coarse_apply_grid (the faces of every launch exchanged, the halo's matrices
+// for M^dag), the sums added over the ranks in their fixed order
+int compute_evals_coarse_operator(const MugiqHipCoarseField *ev, int nEv, const MugiqHipCoarseOperator *op, const MugiqHipCoarseHalo *halo, int opType,
+                                  int massNormalization, double *lambda_h, double *residual_h, double *sigma_h, const MugiqHipComm *comm,
+                                  hipStream_t stream, bool grid) {
+  const char *who = grid ? "computeEvalsCoarseGrid" : "computeEvalsCoarse(coarseOp)";
   // ---- validation, before any device work
   MUGIQ_REQUIRE(ev != nullptr && lambda_h != nullptr && residual_h != nullptr, "%s: NULL argument", who);
   MUGIQ_REQUIRE(nEv >= 1, "%s: nEv = %d must be >= 1", who, nEv);
-  int st;
-  if ((st = check_single_domain(comm, who))) return st;
-  if ((st = validate_coarse_operator(op, who))) return st;
+  int st, part[4] = {0, 0, 0, 0};
+  if (grid) {
+    if ((st = check_coarse_grid(comm, op, halo, part, true, who))) return st;
+  } else {
+    if ((st = check_single_domain(comm, who))) return st;
+    if ((st = validate_coarse_operator(op, who))) return st;
+  }
   if ((st = check_evals_request(opType, sigma_h, massNormalization, op->kappa, who))) return st;
   if ((st = validate_coarse_vectors(ev, nEv, op, who, "coarse eigen"))) return st;
   if ((st = debug_poison_lds_if_asked(stream))) return st;
@@ -784,8 +791,8 @@ int compute_evals_coarse_operator(const MugiqHipCoarseField *ev, int nEv, const 
   }
   const double scale = mass_scale(massNormalization, op->kappa);
   return check_coarse_eigenpairs(ev, nEv, opType, Y, reinterpret_cast<double *>(static_cast<unsigned char *>(ws) + kEvBlock * one), lambda_h, residual_h,
-                                 sigma_h, nullptr, stream, [&](const MugiqHipCoarseField *y, const MugiqHipCoarseField *w, int n) {
-                                   return coarse_apply(y, w, n, op, opType, scale, stream);
+                                 sigma_h, grid ? comm : nullptr, stream, [&](const MugiqHipCoarseField *y, const MugiqHipCoarseField *w, int n) {
+                                   return coarse_apply_grid(y, w, n, op, halo, part, opType, scale, comm, stream);  // (one domain: coarse_apply)
                                  });
 }
 
@@ -828,8 +835,15 @@ int mugiq_hip_compute_evals_coarse(const MugiqHipCoarseField *coarseEvecs_h, int
 int mugiq_hip_compute_evals_coarse_operator(const MugiqHipCoarseField *coarseEvecs_h, int nEv, const MugiqHipCoarseOperator *op, int opType,
                                             int massNormalization, double *lambda_h, double *residual_h, double *sigma_h,
                                             const MugiqHipComm *comm, void *stream) {
-  return compute_evals_coarse_operator(coarseEvecs_h, nEv, op, opType, massNormalization, lambda_h, residual_h, sigma_h, comm,
-                                       static_cast<hipStream_t>(stream));
+  return compute_evals_coarse_operator(coarseEvecs_h, nEv, op, nullptr, opType, massNormalization, lambda_h, residual_h, sigma_h, comm,
+                                       static_cast<hipStream_t>(stream), false);
+}
+
+int mugiq_hip_compute_evals_coarse_operator_grid(const MugiqHipCoarseField *coarseEvecs_h, int nEv, const MugiqHipCoarseOperator *op,
+                                                 const MugiqHipCoarseHalo *halo, int opType, int massNormalization, double *lambda_h,
+                                                 double *residual_h, double *sigma_h, const MugiqHipComm *comm, void *stream) {
+  return compute_evals_coarse_operator(coarseEvecs_h, nEv, op, halo, opType, massNormalization, lambda_h, residual_h, sigma_h, comm,
+                                       static_cast<hipStream_t>(stream), true);
 }
 
 }  // extern "C"

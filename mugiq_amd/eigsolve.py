@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .fields import SpinorField, CoarseField, CoarseOperator, Transfer, desc_array, coarse_desc_array, transfer_desc_array
+from .fields import SpinorField, CoarseField, CoarseOperator, CoarseHalo, Transfer, desc_array, coarse_desc_array, transfer_desc_array
 
 # MuGiqEigOperator (include/enum_mugiq.h:22-25 of the reference, values identical) and the extension H = g5 M
 MUGIQ_EIG_OPERATOR_M, MUGIQ_EIG_OPERATOR_Mdag, MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H = range(5)
@@ -183,6 +183,64 @@ def computeEvalsCoarse(coarseEvecs, transfer=None, gauge=None, kappa=None, opTyp
                                                           int(bool(massNormalization)), lam, res, sig, _comm_ptr(comm, keep), _stream()))
     has_sigma = int(opType) in (MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H)
     return np.array(lam).view(np.complex128)[:n].copy(), np.array(res)[:n], (np.array(sig)[:n] if has_sigma else None)
+
+
+def _halo_ptr(op, comm, keep):
+    """the CoarseHalo the operator carries, by reference (None where it has none: the library accepts that on an unpartitioned comm only)"""
+    if getattr(op, "halo", None) is None:
+        return None
+    h = op.halo.desc()
+    keep.append(h)
+    return ctypes.byref(h)
+
+
+def computeCoarseOperatorGrid(transfer, gauge, kappa, comm, clover=None, op=None):
+    """computeCoarseOperator on a process grid (mugiq_hip_compute_coarse_operator_grid; collective): transfer, clover and the operator are
+    the rank's local ones, gauge has a border on every partitioned axis.  Returns the CoarseOperator with its CoarseHalo in op.halo (the
+    neighbour ranks' matrices M_c^dag reads), built for the axes comm partitions; on an unpartitioned comm this is computeCoarseOperator."""
+    if comm is None:
+        raise _lib.MugiqHipError("computeCoarseOperatorGrid: comm is required")
+    if op is None:
+        op = CoarseOperator(transfer.Xc, transfer.n_vec, transfer.precision, device=transfer.device)
+    if not isinstance(op, CoarseOperator):
+        raise _lib.MugiqHipError("computeCoarseOperatorGrid: op must be a CoarseOperator")
+    dims = tuple(comm.comm_dim_partitioned(d) for d in range(4))
+    if any(dims) and (op.halo is None or op.halo.dims != dims):
+        op.halo = CoarseHalo(op, dims)
+    keep = []
+    d, t, g = op.desc(), transfer.desc(), gauge.desc()
+    _lib.check(_lib.load().mugiq_hip_compute_coarse_operator_grid(ctypes.byref(d), _halo_ptr(op, comm, keep), ctypes.byref(t), ctypes.byref(g),
+                                                                  _clover_ptr(clover, keep), float(kappa), _comm_ptr(comm, keep), _stream()))
+    op.kappa, op.hasClover = float(d.kappa), bool(d.hasClover)
+    return op
+
+
+def coarseApplyGrid(dst, src, op, comm, opType=MUGIQ_EIG_OPERATOR_M, scale=1.0):
+    """coarseApply on a process grid (mugiq_hip_coarse_apply_grid; collective): op from computeCoarseOperatorGrid, local CoarseFields."""
+    dst, src = list(dst), list(src)
+    if comm is None or len(dst) != len(src) or not src:
+        raise _lib.MugiqHipError("coarseApplyGrid: needs a comm and the same number (at least one) of dst and src vectors, got %d and %d"
+                                 % (len(dst), len(src)))
+    keep = []
+    d = op.desc()
+    _lib.check(_lib.load().mugiq_hip_coarse_apply_grid(coarse_desc_array(dst), coarse_desc_array(src), len(src), ctypes.byref(d), _halo_ptr(op, comm, keep),
+                                                       int(opType), float(scale), _comm_ptr(comm, keep), _stream()))
+
+
+def computeEvalsCoarseGrid(coarseEvecs, coarseOp, comm, opType=MUGIQ_EIG_OPERATOR_MdagM, massNormalization=False):
+    """computeEvalsCoarse(..., coarseOp=) on a process grid (mugiq_hip_compute_evals_coarse_operator_grid; collective): the local blocks of
+    the coarse eigenvectors, sums over all ranks; every rank gets the same (lambda, residual, sigma or None)."""
+    ev = list(coarseEvecs)
+    if comm is None or not ev:
+        raise _lib.MugiqHipError("computeEvalsCoarseGrid: needs a comm and at least one eigenvector")
+    n = len(ev)
+    lam, res, sig = (ctypes.c_double * (2 * n))(), (ctypes.c_double * n)(), (ctypes.c_double * n)()
+    keep = []
+    d = coarseOp.desc()
+    _lib.check(_lib.load().mugiq_hip_compute_evals_coarse_operator_grid(coarse_desc_array(ev), n, ctypes.byref(d), _halo_ptr(coarseOp, comm, keep), int(opType),
+                                                                        int(bool(massNormalization)), lam, res, sig, _comm_ptr(comm, keep), _stream()))
+    has_sigma = int(opType) in (MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H)
+    return np.array(lam).view(np.complex128).copy(), np.array(res), (np.array(sig) if has_sigma else None)
 
 
 def projectVector(out, inp, eVecs, comm=None):

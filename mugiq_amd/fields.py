@@ -345,6 +345,7 @@ class CoarseOperator:
         self.precision = int(precision)
         self.volumeCB = int(np.prod(self.X)) // 2
         self.kappa, self.hasClover = 0.0, False
+        self.halo = None  # the CoarseHalo of a build on a process grid (eigsolve.computeCoarseOperatorGrid)
         self.device = torch.device(device)
         self.data = torch.zeros(2 * self.volumeCB * 9 * self.N * self.N, dtype=_cdtype(precision), device=self.device)
 
@@ -360,6 +361,35 @@ class CoarseOperator:
     def get_logical(self):
         """[2, volCB_c, 9, N, N] (parity, x_cb, matrix, row, column)"""
         return self.data.cpu().numpy().reshape(2, self.volumeCB, 9, self.N, self.N)
+
+
+class CoarseHalo:
+    """What M_c^dag of a CoarseOperator needs from the neighbour ranks of a process grid (MugiqHipCoarseHalo in mugiq_hip.h): per axis in
+    `dims` the Y+_mu matrices of the backward neighbour's high face (Yback) and the Y-_mu matrices of the forward neighbour's low face
+    (Yfwd), [2 faceCB, N, N] each in the header's face-site order.  eigsolve.computeCoarseOperatorGrid fills it."""
+
+    def __init__(self, op, dims):
+        self.X, self.n_vec, self.N, self.precision, self.volumeCB, self.device = op.X, op.n_vec, op.N, op.precision, op.volumeCB, op.device
+        self.dims = tuple(1 if d else 0 for d in dims)
+        self.faceCB = tuple(self.volumeCB // x for x in self.X)
+
+        def face(d):
+            return torch.zeros(2 * self.faceCB[d] * self.N * self.N, dtype=_cdtype(self.precision), device=self.device) if self.dims[d] else None
+        self.Yback, self.Yfwd = [face(d) for d in range(4)], [face(d) for d in range(4)]
+
+    def desc(self):
+        d = _lib.CoarseHaloDesc()
+        d.precision, d.nVec, d.volumeCB = self.precision, self.n_vec, self.volumeCB
+        for i in range(4):
+            d.X[i], d.dims[i] = self.X[i], self.dims[i]
+            d.Yback[i] = self.Yback[i].data_ptr() if self.dims[i] else None
+            d.Yfwd[i] = self.Yfwd[i].data_ptr() if self.dims[i] else None
+        return d
+
+    def get_logical(self, mu, forward):
+        """[2, faceCB, N, N] (parity, face index, row, column) of Yfwd[mu] (forward) or Yback[mu]"""
+        t = (self.Yfwd if forward else self.Yback)[mu]
+        return t.cpu().numpy().reshape(2, self.faceCB[mu], self.N, self.N)
 
 
 class Transfer:
