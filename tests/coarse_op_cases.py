@@ -18,6 +18,10 @@ SHAPES = [((4, 4, 4, 4), (2, 2, 2, 2), 4),     # every coarse extent 2: Y+ and Y
 # beyond the table: a workgroup of coarse_apply_kernel takes 64 output components and one of coarse_build_kernel 4096 matrix elements;
 # n_vec 33 (N = 66, N^2 = 4356) gives both kernels a second, ragged chunk
 LARGE_NVEC = [((4, 4, 4, 4), (2, 2, 2, 2), 33)]
+# x, y and z pairwise distinct on the fine and on the coarse lattice, one coarse extent 6 (no power of two): in every table above y = z, so
+# a multiplier or a modulus taken from the wrong axis in get_coords, lex_index or a face index changes nothing there
+ANISO = [((4, 8, 12, 4), (2, 2, 2, 2), 5),     # coarse (2, 4, 6, 2), 96 coarse sites
+         ((12, 4, 8, 4), (2, 2, 2, 2), 4)]     # coarse (6, 2, 4, 2): the checkerboard axis carries the 6, the face of x has y != z
 KAPPA = 0.12
 CSW_COEFF = 0.17
 NW = 17                                        # coarse vectors: two blocks of 8 and one more

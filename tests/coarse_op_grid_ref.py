@@ -79,9 +79,11 @@ def halo(Mblocks, coord, grid, part, X):
     return Yb, Yf
 
 
-def apply_Mc_local(M, w, gw, Y, X, part, dagger=False, gamma5=False):
+def apply_Mc_local(M, w, gw, Y, X, part, dagger=False, gamma5=False, read_index=face_index):
     """coarse_op_ref.apply_Mc on one rank: M, w local; gw = ghost_faces of w; Y = halo(...).  A hop along a partitioned axis that leaves the
-    local lattice reads the ghost face, and for M_c^dag the neighbour's matrix from the halo; nothing else leaves the rank."""
+    local lattice reads the ghost face, and for M_c^dag the neighbour's matrix from the halo; nothing else leaves the rank.  read_index:
+    where a site looks into a face, face_index unless a test wants to know what a wrong one would do (the faces are always packed by
+    face_index)."""
     vcb, nvec = w.shape[1], w.shape[-1]
     v = w.reshape(2, vcb, 2 * nvec).astype(np.complex128)
     out = np.zeros_like(v)
@@ -97,7 +99,7 @@ def apply_Mc_local(M, w, gw, Y, X, part, dagger=False, gamma5=False):
                 A = M[1 - p, n, mm].copy() if dagger else M[p, :, (1 if fwd else 2) + 2 * mu]
                 if part[mu]:
                     off = coord[:, mu] == (X[mu] - 1 if fwd else 0)
-                    fi = face_index(coord[off], X, mu)
+                    fi = read_index(coord[off], X, mu)
                     vin[off] = gw[mu][fwd][1 - p, fi].reshape(-1, 2 * nvec)
                     if dagger:
                         A[off] = (Y[1] if fwd else Y[0])[mu][1 - p, fi]
@@ -108,16 +110,16 @@ def apply_Mc_local(M, w, gw, Y, X, part, dagger=False, gamma5=False):
     return out
 
 
-def apply_op_grid(Mg, wg, Gc, grid, op, scale=1.0, force=(0, 0, 0, 0)):
+def apply_op_grid(Mg, wg, Gc, grid, op, scale=1.0, force=(0, 0, 0, 0), read_index=face_index):
     """scale * A_c w of the form `op` on the global coarse lattice Gc, computed rank by rank on `grid`; returns ({rank coordinates: local
-    result}, the reassembled global field)"""
+    result}, the reassembled global field).  read_index: see apply_Mc_local"""
     X, part = local_dims(Gc, grid), partitioned(grid, force)
     rs = ranks(grid)
     Mb = {c: slice_eo(Mg, Gc, c, grid) for c in rs}
     Ys = {c: halo(Mb, c, grid, part, X) for c in rs}
 
     def step(blocks, dagger, gamma5):
-        return {c: apply_Mc_local(Mb[c], blocks[c], ghost_faces(blocks, c, grid, part, X), Ys[c], X, part, dagger, gamma5) for c in rs}
+        return {c: apply_Mc_local(Mb[c], blocks[c], ghost_faces(blocks, c, grid, part, X), Ys[c], X, part, dagger, gamma5, read_index) for c in rs}
     wb = {c: slice_eo(wg, Gc, c, grid) for c in rs}
     if op == cor.OP_M:
         r = step(wb, False, False)

@@ -19,7 +19,7 @@ NEW = ["mugiq_hip_coarse_operator_bytes", "mugiq_hip_alloc_coarse_operator", "mu
 
 
 @pytest.mark.parametrize("clover", [False, True])
-@pytest.mark.parametrize("X,bs,nvec", cases.SHAPES + cases.LARGE_NVEC)
+@pytest.mark.parametrize("X,bs,nvec", cases.SHAPES + cases.LARGE_NVEC + cases.ANISO)
 def test_reference_apply_equals_the_galerkin_chain(X, bs, nvec, clover):
     """M_c w, M_c^dag w (the explicit adjoint of the stored matrices) and G5 M_c w against restrict_ref.galerkin_apply -- P, the numpy
     Wilson(-clover) operator, R -- on random coarse vectors and random, NOT block-orthonormal null vectors: 1e-12 relative in the max norm."""

@@ -4,12 +4,14 @@ new entry points are declared, exported and bound; every refusal of their valida
 point at nothing); an unpartitioned comm, or none, passes the grid check without a halo; the halo byte count is the header's; and the
 C++ mirror's three overloads compile against the C ABI."""
 import ctypes
+import functools
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import coarse_op_cases as cases
 import coarse_op_grid_ref as gr
 import coarse_op_ref as cor
 from test_coarse_op_cpu import _arr, _coarse, _comm, _expect, _gauge, _op, _ptr, _transfer
@@ -23,14 +25,25 @@ GRIDS = [((4, 4, 4, 8), (2, 2, 2, 2), 4, (1, 1, 1, 2)),
          ((8, 4, 4, 8), (2, 2, 2, 2), 4, (2, 1, 1, 2)),
          ((4, 4, 4, 16), (2, 2, 2, 2), 4, (1, 1, 1, 4)),      # four distinct neighbours along t: a swapped direction shows
          ((16, 4, 4, 4), (2, 2, 2, 2), 5, (2, 1, 1, 1))]      # local coarse extent 4 along the partitioned axis
+# ranks are ordered x slowest, t fastest: a t neighbour is the next rank whatever is swapped elsewhere, so x and y get four ranks of their
+# own (z follows from the code being generic over the axis); and real messages that carry faces with pairwise distinct extents
+NEW_GRIDS = [((16, 4, 4, 4), (2, 2, 2, 2), 4, (4, 1, 1, 1)),
+             ((4, 16, 4, 4), (2, 2, 2, 2), 4, (1, 4, 1, 1)),
+             ((4, 8, 12, 8), (2, 2, 2, 2), 5, (1, 1, 1, 2))]  # local blocks 4 8 12 4, coarse 2 4 6 2
 
 
-@pytest.mark.parametrize("G,bs,nvec,grid", GRIDS)
+@functools.lru_cache(maxsize=None)
+def _reference(G, bs, nvec):
+    """gr.global_reference without the clover term, computed once per lattice; nothing writes to it"""
+    return gr.global_reference(G, bs, nvec, False)
+
+
+@pytest.mark.parametrize("G,bs,nvec,grid", GRIDS + NEW_GRIDS)
 def test_decomposition_reassembles_to_the_global_operator(G, bs, nvec, grid):
     """All five forms with scale 1.7, rank by rank from local matrices, local vectors, ghost faces and the halo: the reassembled result
     equals coarse_op_ref.apply_op on the global lattice to 1e-14 (the same products, summed in another order).  The adjoint's faces are
     in it: M_c^dag of a face site reads Y of the neighbour rank."""
-    M, ws = gr.global_reference(G, bs, nvec, False)
+    M, ws = _reference(G, bs, nvec)
     Gc = tuple(G[d] // bs[d] for d in range(4))
     for op in range(5):
         for w in ws[:2]:
@@ -44,10 +57,77 @@ def test_decomposition_with_forced_partitioning_on_one_rank():
     """grid 1 1 1 1 with every axis forced: a rank is its own neighbour, ghosts and halo are its own faces; extent 2 everywhere, so the
     forward and the backward ghost of a site are the same neighbour site while Y+ and Y- differ."""
     G, bs, nvec = (4, 4, 4, 4), (2, 2, 2, 2), 4
-    M, ws = gr.global_reference(G, bs, nvec, False)
+    M, ws = _reference(G, bs, nvec)
     for op in range(5):
         _, got = gr.apply_op_grid(M, ws[0], (2, 2, 2, 2), (1, 1, 1, 1), op, 1.7, force=(1, 1, 1, 1))
         assert rel_err(got, cor.apply_op(M, ws[0], (2, 2, 2, 2), op, 1.7)) < 1e-14, op
+
+
+@pytest.mark.parametrize("G,bs,nvec", cases.ANISO)
+def test_forced_decomposition_on_pairwise_distinct_extents(G, bs, nvec):
+    """The same with x, y and z pairwise distinct and one extent 6 (coarse 2 4 6 2 and 6 2 4 2), all four axes forced and x alone: which
+    extent multiplies which coordinate in the face index matters on every face.  1e-14 of the max norm, as above."""
+    M, ws = _reference(G, bs, nvec)
+    Gc = cases.coarse_dims(G, bs)
+    for force in ((1, 1, 1, 1), (1, 0, 0, 0)):
+        for op in range(5):
+            _, got = gr.apply_op_grid(M, ws[0], Gc, (1, 1, 1, 1), op, 1.7, force=force)
+            e = rel_err(got, cor.apply_op(M, ws[0], Gc, op, 1.7))
+            assert e < 1e-14, (force, op, e)
+
+
+@pytest.mark.parametrize("Xc", [(2, 4, 6, 2), (4, 8, 12, 4), (6, 2, 4, 2)])
+def test_face_index_is_a_bijection(Xc):
+    """every axis, parity and side: the face sites of one parity fill range(faceCB) exactly once"""
+    vcb = int(np.prod(Xc)) // 2
+    for mu in range(4):
+        for p in range(2):
+            coord = gr.orc.get_coords(np.arange(vcb), Xc, p)
+            for high in (0, 1):
+                fi = gr.face_index(coord[coord[:, mu] == (Xc[mu] - 1 if high else 0)], Xc, mu)
+                assert np.array_equal(np.sort(fi), np.arange(vcb // Xc[mu])), (mu, p, high)
+
+
+def _swapped_face_index(coord, X, mu):
+    """gr.face_index with its two multipliers swapped: the same index wherever the two lowest of the three other extents are equal"""
+    a, b, c = [d for d in range(4) if d != mu]
+    return ((coord[..., c] * X[a] + coord[..., b]) * X[b] + coord[..., a]) >> 1
+
+
+def _reproduces(M, w, Gc, grid, force, read_index):
+    """whether M_c w, rank by rank with `read_index` on the read side, is the global result to the 1e-14 of the tests above; an index past
+    the face is a no"""
+    try:
+        _, got = gr.apply_op_grid(M, w, Gc, grid, cor.OP_M, 1.7, force=force, read_index=read_index)
+    except IndexError:
+        return False, None
+    e = rel_err(got, cor.apply_op(M, w, Gc, cor.OP_M, 1.7))
+    return e < 1e-14, e
+
+
+def test_only_the_new_shapes_see_swapped_face_multipliers():
+    """A read side whose face index has its two multipliers swapped (the faces and the halo are packed as ever).  On every process grid the
+    suite had (GRIDS), on the all-forced 4^4 above and on the other lattices of the forced sweep on the device (coarse 2 2 2 4 with every
+    axis forced, coarse 4 2 2 2 on its x face) it still gives the global result: y = z everywhere, and the process grids cut x and t only,
+    with local coarse blocks 2 2 2 2 or 4 2 2 2.  (The y, z and t faces of coarse 4 2 2 2 do see it: the device sweep was blind on the x
+    face -- the face of the checkerboard axis -- and in every real message.)  On both shapes of cases.ANISO and on the 4 8 12 8 process grid it does
+    not: an index past the face, or a result that is wrong by more than 1e-3 of its max norm (a hop term taken from another site of
+    independent random data is wrong by its own size)."""
+    blind = [(G, bs, nvec, grid, (0, 0, 0, 0)) for G, bs, nvec, grid in GRIDS]
+    blind += [((4, 4, 4, 4), (2, 2, 2, 2), 4, (1, 1, 1, 1), (1, 1, 1, 1)),
+              ((8, 4, 4, 4), (2, 2, 2, 2), 5, (1, 1, 1, 1), (1, 0, 0, 0)), ((4, 4, 4, 8), (2, 2, 2, 2), 4, (1, 1, 1, 1), (1, 1, 1, 1))]
+    for G, bs, nvec, grid, force in blind:
+        M, ws = _reference(G, bs, nvec)
+        ok, e = _reproduces(M, ws[0], cases.coarse_dims(G, bs), grid, force, _swapped_face_index)
+        assert ok, (G, grid, force, e)
+    seeing = [(G, bs, nvec, (1, 1, 1, 1), force) for G, bs, nvec in cases.ANISO for force in ((1, 1, 1, 1), (1, 0, 0, 0))]
+    seeing.append(NEW_GRIDS[2] + ((0, 0, 0, 0),))
+    for G, bs, nvec, grid, force in seeing:
+        M, ws = _reference(G, bs, nvec)
+        Gc = cases.coarse_dims(G, bs)
+        assert _reproduces(M, ws[0], Gc, grid, force, gr.face_index)[0], (G, grid, force)        # the index as it is: fine
+        ok, e = _reproduces(M, ws[0], Gc, grid, force, _swapped_face_index)
+        assert not ok and (e is None or e > 1e-3), (G, grid, force, e)
 
 
 def test_slices_and_faces_are_consistent():

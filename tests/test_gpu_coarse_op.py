@@ -48,7 +48,7 @@ def _device_problem(hip, X, bs, nvec, clover, kind="su3", gprec=8, prec=8):
 
 # ---- the matrices ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("clover", [False, True])
-@pytest.mark.parametrize("X,bs,nvec", cases.SHAPES + cases.LARGE_NVEC)
+@pytest.mark.parametrize("X,bs,nvec", cases.SHAPES + cases.LARGE_NVEC + cases.ANISO)
 def test_matrices_match_numpy(hip, X, bs, nvec, clover, record_max):
     """Xd and Y+-_mu of every coarse site, fp64 everywhere, to 1e-12 of the largest entry."""
     gauge, C, T, _, _ = _device_problem(hip, X, bs, nvec, clover)
@@ -121,7 +121,7 @@ def _fine_route(hip, T, gauge, C, cw, X, opType, scale):
 
 
 @pytest.mark.parametrize("clover", [False, True])
-@pytest.mark.parametrize("X,bs,nvec", cases.SHAPES + cases.LARGE_NVEC)
+@pytest.mark.parametrize("X,bs,nvec", cases.SHAPES + cases.LARGE_NVEC + cases.ANISO)
 def test_apply_matches_numpy_and_the_fine_route(hip, X, bs, nvec, clover, record_max):
     """All five forms with scale 1.7 in batches of 1, 8, 9 and 17 vectors against coarse_op_ref, and the batch of 17 against prolongation +
     stencil + restriction on the device: 1e-12 of the result's max norm."""

@@ -1,8 +1,10 @@
 """GPU tests of the explicit coarse operator on a process grid (mugiq_hip_compute_coarse_operator_grid, mugiq_hip_coarse_apply_grid,
 mugiq_hip_compute_evals_coarse_operator_grid).  On one rank with the partitioned path forced -- ghost faces, halo matrices and messages
 with the rank as its own neighbour -- everything must be the BITS of the unpartitioned existing calls on the same fields: the sums and
-their order are the same, only where an operand is read from changes.  On 2 and 4 ranks (tests/coarse_op_grid_workers.py) a rank's
-matrices and outputs must be the bits of its slice of the single-domain ones.  The decomposition itself is pinned on the CPU
+their order are the same, only where an operand is read from changes -- on lattices with y = z and on two with x, y, z pairwise distinct
+(coarse_op_cases.ANISO), where a face index with an extent from the wrong axis shows, and in all three forms of the ghost apply kernel
+(16, 32 and 64 outputs per workgroup).  On 2 and 4 ranks (tests/coarse_op_grid_workers.py; four along x, y and t, each with four distinct
+neighbours) a rank's matrices and outputs must be the bits of its slice of the single-domain ones.  The decomposition itself is pinned on the CPU
 (tests/test_coarse_op_grid_cpu.py).  The eigenpair check: 1e-13 against the unpartitioned call (the bound tests/restrict_workers.py uses
 for the same comparison), 1e-12 against numpy (the bound of this chain)."""
 import ctypes
@@ -30,7 +32,10 @@ SHAPES = [cases.SHAPES[0],      # every coarse extent 2: both ghosts of a site c
           cases.SHAPES[2],      # coarse extent 4 along x: faces differ from the interior; n_vec no multiple of 4
           cases.SHAPES[4],      # sites with both x neighbours inside the aggregate
           cases.SHAPES[5],      # N = 48
-          cases.LARGE_NVEC[0]]  # a second, ragged chunk in both kernels
+          cases.LARGE_NVEC[0],  # a second, ragged chunk in both kernels
+          cases.ANISO[0],       # coarse 2 4 6 2: x, y, z pairwise distinct and a 6, so every face index has two different multipliers
+          cases.ANISO[1]]       # coarse 6 2 4 2: the 6 on the checkerboard axis, the face of x with y != z
+FORM_ENV = "MUGIQ_HIP_COARSE_APPLY_OUT"
 
 
 def _bits(t):
@@ -126,11 +131,8 @@ def test_forced_partitioning_reproduces_the_single_domain_bits(hip, X, bs, nvec,
         p.check(hip, force)
 
 
-def test_halo_holds_the_neighbours_matrices(hip):
-    """A rank that is its own neighbour: Yback[mu] is Y+_mu of its own high face and Yfwd[mu] Y-_mu of its own low face, in the header's
-    face order (tests/coarse_op_grid_ref.face)."""
+def _halo_is_the_own_faces(hip, X, bs, nvec):
     import coarse_op_grid_ref as gr
-    X, bs, nvec = cases.SHAPES[2]
     p = _Problem(hip, X, bs, nvec, True)
     opg = p.check(hip, (1, 1, 1, 1))
     M, Xc = p.op.get_logical(), p.T.Xc
@@ -139,10 +141,30 @@ def test_halo_holds_the_neighbours_matrices(hip):
         assert np.array_equal(opg.halo.get_logical(mu, True), gr.face(M[:, :, 2 + 2 * mu], Xc, mu, 0)), mu
 
 
+def test_halo_holds_the_neighbours_matrices(hip):
+    """A rank that is its own neighbour: Yback[mu] is Y+_mu of its own high face and Yfwd[mu] Y-_mu of its own low face, in the header's
+    face order (tests/coarse_op_grid_ref.face)."""
+    _halo_is_the_own_faces(hip, *cases.SHAPES[2])
+
+
+def test_halo_on_pairwise_distinct_extents(hip):
+    """the same on coarse 2 4 6 2: the matrix pack walks faces whose three extents all differ"""
+    _halo_is_the_own_faces(hip, *cases.ANISO[0])
+
+
 @pytest.mark.parametrize("prec,gprec", [(4, 4), (8, 4)])
 def test_forced_partitioning_in_fp32(hip, prec, gprec):
     """fp32 transfer, operator and vectors; fp32 links and clover field under an fp64 transfer"""
     X, bs, nvec = cases.SHAPES[2]
+    p = _Problem(hip, X, bs, nvec, True, prec=prec, gprec=gprec)
+    for force in ((1, 0, 0, 0), (0, 0, 1, 1), (1, 1, 1, 1)):
+        p.check(hip, force)
+
+
+@pytest.mark.parametrize("prec,gprec", [(4, 4), (8, 4)])
+def test_forced_partitioning_in_fp32_on_pairwise_distinct_extents(hip, prec, gprec):
+    """the same on coarse 2 4 6 2"""
+    X, bs, nvec = cases.ANISO[0]
     p = _Problem(hip, X, bs, nvec, True, prec=prec, gprec=gprec)
     for force in ((1, 0, 0, 0), (0, 0, 1, 1), (1, 1, 1, 1)):
         p.check(hip, force)
@@ -156,6 +178,14 @@ def test_forced_partitioning_with_padded_vectors(hip):
         p.check(hip, force)
 
 
+def test_forced_partitioning_with_padded_vectors_on_pairwise_distinct_extents(hip):
+    """the same on coarse 2 4 6 2: a face index taken with the wrong stride or extent lands in a pad or on another site"""
+    X, bs, nvec = cases.ANISO[0]
+    p = _Problem(hip, X, bs, nvec, True, pad=7)
+    for force in ((1, 0, 0, 0), (1, 1, 1, 1)):
+        p.check(hip, force)
+
+
 def test_forced_partitioning_under_poisoned_lds(hip, monkeypatch):
     """MUGIQ_HIP_DEBUG_POISON_LDS=1: no kernel of the grid path reads an LDS cell it has not written"""
     X, bs, nvec = cases.SHAPES[2]
@@ -164,11 +194,69 @@ def test_forced_partitioning_under_poisoned_lds(hip, monkeypatch):
     p.check(hip, (1, 1, 1, 1))
 
 
+# ---- 1b. every form of the ghost kernel ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("prec", [8, 4])
+@pytest.mark.parametrize("X,bs,nvec", [cases.SHAPES[2],        # N = 10: one chunk, most lanes masked
+                                       cases.LARGE_NVEC[0],    # N = 66: two ragged chunks of 64 outputs, three of 32, five of 16
+                                       cases.ANISO[0]])        # faces with pairwise distinct extents
+def test_every_form_of_the_ghost_apply_kernel(hip, X, bs, nvec, prec, monkeypatch):
+    """coarse_apply_kernel<.., GHOST = true> with 16, 32 and 64 outputs per workgroup (MUGIQ_HIP_COARSE_APPLY_OUT; the rule alone picks 32
+    on lattices this small), fp64 and fp32 storage, all four axes forced and x alone: the five forms with 1, 9 and 17 vectors and scale 1.7
+    are the bits of coarseApply on the same fields with the variable unset -- the unpartitioned call under the default rule, not the grid
+    call itself.  M and G5 M launch the M kernel, M^dag its own, the normal forms both."""
+    monkeypatch.delenv(FORM_ENV, raising=False)
+    p = _Problem(hip, X, bs, nvec, True, prec=prec, gprec=prec)
+    assert all(hip.coarseApplyForm(p.op, n) == 32 for n in (1, 9, 17))
+    for force in ((1, 1, 1, 1), (1, 0, 0, 0)):
+        comm = _comm(hip, force)
+        opg = hip.computeCoarseOperatorGrid(p.T, _gauge(hip, X, _border(force), prec), KAPPA, comm, clover=p.C)
+        assert opg.halo.dims == force and _same(opg.data, p.op.data), force
+        for form in (16, 32, 64):
+            monkeypatch.setenv(FORM_ENV, str(form))
+            assert hip.coarseApplyForm(opg, 17) == form
+            for opType in range(5):
+                for n in (1, 9, 17):
+                    out = p.outputs(hip, n)
+                    hip.coarseApplyGrid(out, p.cw[:n], opg, comm, opType, SCALE)
+                    for k in range(n):
+                        assert _same(out[k].data, p.ref[opType, n][k].data), (force, form, opType, n, k)
+            monkeypatch.delenv(FORM_ENV)
+
+
+def test_the_rule_selects_the_64_output_form_on_the_ghost_path(hip, monkeypatch):
+    """No variable set: 41 vectors on the 96 coarse sites of the first ANISO shape are 96 x 6 blocks of vectors = 576 >= 512 workgroups of
+    the 64-output grid, so the rule itself takes the 64-output form (17 vectors: 288, the 32-output form).  M, M^dag and G5 M under
+    1 1 1 1 are the bits of coarseApply.  The normal forms are not in this test: they launch 8 vectors at a time, 96 workgroups, and stay on
+    the 32-output form; test_every_form_of_the_ghost_apply_kernel forces them through the others."""
+    monkeypatch.delenv(FORM_ENV, raising=False)
+    X, bs, nvec = cases.ANISO[0]
+    p = _Problem(hip, X, bs, nvec, True)
+    assert hip.coarseApplyForm(p.op, 41) == 64 and hip.coarseApplyForm(p.op, 17) == 32
+    rng = np.random.default_rng(4100)                     # cases.NW stays 17: the other 24 vectors are this test's own
+    cw = p.cw + [hip.CoarseField(p.T.Xc, nvec, 8).set_logical(cases.c(rng, (2, p.op.volumeCB, 2, nvec))) for _ in range(41 - cases.NW)]
+    force = (1, 1, 1, 1)
+    comm = _comm(hip, force)
+    opg = hip.computeCoarseOperatorGrid(p.T, _gauge(hip, X, _border(force)), KAPPA, comm, clover=p.C)
+    assert opg.halo.dims == force and len(cw) == 41 and hip.coarseApplyForm(opg, len(cw)) == 64
+    for opType in (hip.MUGIQ_EIG_OPERATOR_M, hip.MUGIQ_EIG_OPERATOR_Mdag, hip.MUGIQ_EIG_OPERATOR_H):
+        want, got = p.outputs(hip, 41), p.outputs(hip, 41)
+        hip.coarseApply(want, cw, p.op, opType, SCALE)
+        hip.coarseApplyGrid(got, cw, opg, comm, opType, SCALE)
+        for k in range(41):
+            assert _same(got[k].data, want[k].data), (opType, k)
+        assert not _same(want[0].data, want[40].data)
+
+
 # ---- 2. two and four ranks -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("G,nvec,grid", [((4, 4, 4, 8), 4, (1, 1, 1, 2)),
                                          ((8, 4, 4, 8), 4, (2, 1, 1, 2)),
                                          ((4, 4, 4, 16), 4, (1, 1, 1, 4)),     # four distinct neighbours along t: a swapped direction shows
-                                         ((16, 4, 4, 4), 5, (2, 1, 1, 1))])    # local coarse extent 4 along the partitioned axis
+                                         ((16, 4, 4, 4), 5, (2, 1, 1, 1)),     # local coarse extent 4 along the partitioned axis
+                                         # ranks are ordered x slowest, t fastest: four distinct neighbours along x (rank +- 1 is no x
+                                         # neighbour) and along y; real messages with faces of pairwise distinct extents (coarse 2 4 6 2)
+                                         ((16, 4, 4, 4), 4, (4, 1, 1, 1)),
+                                         ((4, 16, 4, 4), 4, (1, 4, 1, 1)),
+                                         ((4, 8, 12, 8), 5, (1, 1, 1, 2))])
 def test_process_grids(G, nvec, grid, tmp_path):
     """Every rank on the one GPU through gloo: local matrices and outputs are the bits of the rank's slice of the single-domain ones and
     equal numpy to 1e-12, the eigenpair values equal numpy to 1e-12 (asserted in the worker) and are identical on all ranks."""
@@ -177,6 +265,19 @@ def test_process_grids(G, nvec, grid, tmp_path):
     mp.spawn(coarse_op_grid_workers.grid_worker, args=(world, free_port(), grid, G, (2, 2, 2, 2), nvec, prefix), nprocs=world, join=True)
     outs = [np.load("%s_%d.npy" % (prefix, r)) for r in range(world)]
     assert len(outs) == world and np.all(np.isfinite(outs[0]))
+    for o in outs[1:]:
+        assert np.array_equal(o, outs[0])
+
+
+def test_process_grid_in_fp32(tmp_path):
+    """Four ranks along x with every field in fp32 storage: local matrices and outputs are the bits of the rank's slice of the
+    single-domain device results in the same storage, and all ranks save identical eigenpair values.  Nothing is compared with numpy: the
+    project has no fp32 bound for this chain."""
+    G, nvec, grid = (16, 4, 4, 4), 4, (4, 1, 1, 1)
+    prefix = str(tmp_path / "grid")
+    mp.spawn(coarse_op_grid_workers.grid_worker, args=(4, free_port(), grid, G, (2, 2, 2, 2), nvec, prefix, 4), nprocs=4, join=True)
+    outs = [np.load("%s_%d.npy" % (prefix, r)) for r in range(4)]
+    assert np.all(np.isfinite(outs[0]))
     for o in outs[1:]:
         assert np.array_equal(o, outs[0])
 
