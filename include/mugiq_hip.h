@@ -797,9 +797,10 @@ int mugiq_hip_compute_evals_coarse_operator(const MugiqHipCoarseField *coarseEve
  * Both NULL on an axis the halo was not built for (dims[mu] == 0).  With a rank as its own neighbour (MugiqHipComm.partitioned) the
  * halo holds copies of the rank's own matrices.
  *
- * Only these three calls serve a grid.  The MG solve, mugiq_hip_mg_setup, mugiq_hip_coarse_eigensolve with mugiq_hip_coarse_gram and
- * mugiq_hip_coarse_rotate, the coarse deflation and mugiq_hip_compute_coarse_operator_coarse stay single-domain and refuse a partitioned
- * comm, as do the three single-domain calls above.  The exchange is not overlapped with interior work. */
+ * These three calls serve a grid, and on top of them mugiq_hip_coarse_gram_grid and mugiq_hip_coarse_eigensolve_grid (further down).  The
+ * MG solve, mugiq_hip_mg_setup, the coarse deflation and mugiq_hip_compute_coarse_operator_coarse stay single-domain and refuse a
+ * partitioned comm, as do the three single-domain calls above and mugiq_hip_coarse_eigensolve, mugiq_hip_coarse_gram and
+ * mugiq_hip_coarse_rotate.  The exchange is not overlapped with interior work. */
 typedef struct MugiqHipCoarseHalo_s {
   void *Yback[4], *Yfwd[4];
   int precision; /* of the operator it belongs to */
@@ -1243,7 +1244,9 @@ int mugiq_hip_coarse_gram(double *G_h, const MugiqHipCoarseField *a_h, int mA, c
 /* out_j = sum_i in_i Z[i][j], i < mIn, j < mOut; Z_h[i*mOut + j] complex, row-major, on the host, copied by the call.  Out of place: an
  * out overlapping an in or another out is MUGIQ_HIP_ERROR_INVALID_ARGUMENT.  Fields as above, one stride for all in and one for all out;
  * pads are neither read nor written.  The same instruction; the sum over i runs in ascending order, four to an instruction, whatever
- * mOut.  An in_i with Z[i][j] = 0 still enters as 0 x in_i: a NaN or Inf there reaches every output. */
+ * mOut.  An in_i with Z[i][j] = 0 still enters as 0 x in_i: a NaN or Inf there reaches every output.
+ * There is no grid twin of this call: a rotation is local to a rank (every rank rotates its block with the same Z), so the grid solver
+ * calls the kernel as it is; this entry keeps refusing a partitioned comm, like mugiq_hip_coarse_gram. */
 int mugiq_hip_coarse_rotate(const MugiqHipCoarseField *out_h, int mOut, const MugiqHipCoarseField *in_h, int mIn, const double *Z_h,
                             const MugiqHipComm *comm, void *stream);
 /* Host-side dense algebra, no device and no LAPACK behind it; matrices are row-major n x n complex (re, im interleaved), n <= 512.
@@ -1295,6 +1298,43 @@ int mugiq_hip_coarse_eig_param_default(MugiqHipCoarseEigParam *param);
 int mugiq_hip_coarse_eigensolve(const MugiqHipCoarseField *evecs_h, const MugiqHipCoarseField *start_h, const MugiqHipCoarseOperator *op,
                                 int opType, const MugiqHipCoarseEigParam *param, double *theta_h, double *residual_h, double *sigma_h,
                                 MugiqHipCoarseEigInfo *info, const MugiqHipComm *comm, void *stream);
+
+/* ---- the coarse eigensolver on a process grid (new; csrc/coarse_eig.hip; tests/coarse_eig_grid_ref.py restates it rank by rank).
+ * The solver touches the lattice in three places: the application of A, the Gram matrices and the residual sums.  On a grid A is applied
+ * by mugiq_hip_coarse_apply_grid's internals (faces exchanged per launch), and every Gram matrix and every vector of residual sums is
+ * added over the ranks in the fixed order of the eigenpair check (reduce_space, gather_time, rank-ordered sum, bcast: the same bits on
+ * every rank).  The rotations and the recurrence are local to a rank; the dense host algebra runs on every rank on identical input, so
+ * convergence, locking, the aMax repair, every count and every return status are identical on all ranks, and nothing is broadcast beyond
+ * those sums.  On ONE rank with axes forced (MugiqHipComm.partitioned) nothing is summed and the applications are the bits of
+ * mugiq_hip_coarse_apply: the call gives the bits of mugiq_hip_coarse_eigensolve.  On more ranks the Gram sums are added in another
+ * order than on one domain (per rank first), so values agree to rounding, not bit for bit.
+ *
+ * The Chebyshev step of the filter writes the send faces of the next application (chebyshev_step_pack_kernel: the element of a site on
+ * the low or high face of a partitioned axis is stored a second time, into that face's send buffer, in the layout of the face pack:
+ * [vector][parity][row][face index]), for the steps k < polyDeg of a block; the first application of a block, Rayleigh-Ritz and the
+ * power estimate pack with the pack kernel.  MUGIQ_HIP_EIG_PACK_IN_STEP=0 (read once per call) keeps the plain step kernel and separate
+ * packs everywhere; both settings give the same bits. */
+typedef struct MugiqHipCoarseEigGridInfo_s {
+  int exchanges;    /* face exchanges issued (one per kernel launch of the operator: 2 per block application on a partitioned comm) */
+  int rankSums;     /* sums over the ranks made (0 on one rank: there is nothing to add) */
+  int packLaunches; /* launches of the face pack kernel made for the solver's applications */
+  int stepPacked;   /* exchanges whose send faces were written by the recurrence kernel */
+} MugiqHipCoarseEigGridInfo;
+/* mugiq_hip_coarse_gram for a rank of a process grid; collective.  The local Gram matrix, by the same two kernels, is added over the ranks:
+ * every rank gets the same bits.  comm is required (NULL: MUGIQ_HIP_ERROR_INVALID_ARGUMENT), with reduce_space, gather_time and bcast
+ * where it has more than one rank.  On a comm of one rank the call is mugiq_hip_coarse_gram, bit for bit. */
+int mugiq_hip_coarse_gram_grid(double *G_h, const MugiqHipCoarseField *a_h, int mA, const MugiqHipCoarseField *b_h, int mB,
+                               const MugiqHipComm *comm, void *stream);
+/* mugiq_hip_coarse_eigensolve for a rank of a process grid; collective.  op and halo: from mugiq_hip_compute_coarse_operator_grid;
+ * evecs_h, start_h: the rank's local blocks.  nKr is checked against the global dimension, 4 n_vec volumeCB x ranks.  info is filled as
+ * by the single-domain call (hostReads keeps its meaning and its formula), gridInfo as above.  Checks, each before any device work:
+ * comm or gridInfo NULL; those of the grid calls (sendrecv NULL on a partitioned comm; a sum callback NULL with more than one rank;
+ * halo NULL on a partitioned comm, of another operator, or not built for a partitioned axis); those of mugiq_hip_coarse_eigensolve.
+ * With nothing partitioned (one rank, no forced axis) halo may be NULL and the call runs the existing solver: the same bits. */
+int mugiq_hip_coarse_eigensolve_grid(const MugiqHipCoarseField *evecs_h, const MugiqHipCoarseField *start_h, const MugiqHipCoarseOperator *op,
+                                     const MugiqHipCoarseHalo *halo, int opType, const MugiqHipCoarseEigParam *param, double *theta_h,
+                                     double *residual_h, double *sigma_h, MugiqHipCoarseEigInfo *info, MugiqHipCoarseEigGridInfo *gridInfo,
+                                     const MugiqHipComm *comm, void *stream);
 
 /* What Displace asks of QUDA's ColorSpinorField for its auxiliary vector (lib/displace.cpp:26-30: ColorSpinorField::Create
  * with QUDA_ZERO_FIELD_CREATE and setPrecision(coarsePrec_); :42,:50-51: operator=; :59: blas::zero), for hosts that do not

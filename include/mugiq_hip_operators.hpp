@@ -463,6 +463,32 @@ inline MugiqHipCoarseEigInfo coarseEigensolve(const std::vector<MugiqHipCoarseFi
   if (!(st == MUGIQ_HIP_ERROR_NOT_CONVERGED && allowUnconverged)) check(st);
   return info;
 }
+// ---- ... on a process grid (mugiq_hip_coarse_gram_grid, mugiq_hip_coarse_eigensolve_grid; new): the same two names with the operator's
+// MugiqHipCoarseHalo behind the vectors / the operator and a comm that is required.  The Gram matrix needs nothing of the halo; it marks
+// the vectors as the local blocks of the grid the halo was built on.  coarseRotate has no grid form: a rotation is local to a rank
+inline std::vector<std::complex<double>> coarseGram(const std::vector<MugiqHipCoarseField> &a, const std::vector<MugiqHipCoarseField> &b,
+                                                    const MugiqHipCoarseHalo &, const MugiqHipComm *comm, void *stream = nullptr) {
+  if (a.empty() || b.empty()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "coarseGram: no vectors");
+  std::vector<std::complex<double>> G(a.size() * b.size());
+  check(mugiq_hip_coarse_gram_grid(reinterpret_cast<double *>(G.data()), a.data(), (int)a.size(), b.data(), (int)b.size(), comm, stream));
+  return G;
+}
+inline MugiqHipCoarseEigInfo coarseEigensolve(const std::vector<MugiqHipCoarseField> &eVecs, const std::vector<MugiqHipCoarseField> &start,
+                                              const CoarseOperator &op, const MugiqHipCoarseHalo &halo, int opType, const CoarseEigParam &param,
+                                              std::vector<double> &theta, std::vector<double> &residual, std::vector<double> &sigma,
+                                              MugiqHipCoarseEigGridInfo &gridInfo, const MugiqHipComm *comm, bool allowUnconverged = false,
+                                              void *stream = nullptr) {
+  if ((int)eVecs.size() != param.nConv || (int)start.size() != param.nKr || eVecs.empty())
+    throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "coarseEigensolve: nConv eigenvector fields and nKr start vectors are needed");
+  theta.assign(eVecs.size(), 0.0);
+  residual.assign(eVecs.size(), 0.0);
+  sigma.assign(eVecs.size(), 0.0);
+  MugiqHipCoarseEigInfo info{};
+  const int st = mugiq_hip_coarse_eigensolve_grid(eVecs.data(), start.data(), op.desc(), &halo, opType, &param, theta.data(), residual.data(),
+                                                  sigma.data(), &info, &gridInfo, comm, stream);
+  if (!(st == MUGIQ_HIP_ERROR_NOT_CONVERGED && allowUnconverged)) check(st);
+  return info;
+}
 // x_r = M^-1 b_r by CG on the normal equations from the low-mode start (mugiq_hip_wilson_solve).  Returns false where a right-hand
 // side did not reach tol within maxIter (x, iters and relres are filled all the same); every other failure throws.
 inline bool wilsonSolve(const std::vector<ColorSpinorField> &x, const std::vector<ColorSpinorField> &b, const GaugeField &gauge, double kappa,

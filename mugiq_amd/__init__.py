@@ -32,6 +32,7 @@ from .eigsolve import (  # noqa: E402
     Eigsolve_Mugiq, wilsonApply, computeEvals, computeEvalsCoarse, computeCoarseOperator, computeCoarseOperatorCoarse, coarseApply, coarseApplyForm, computeCoarseOperatorGrid, coarseApplyGrid, computeEvalsCoarseGrid, projectVector, wilsonSolve, SolveInfo,
     mgSolve, mgPrecondition, mgSolveMixed, mgPreconditionSloppy, mgConvertPrecision, mgSolveParam, MgSolveInfo, mgSetup, mgSetupCoarse, MgSetupCoarseInfo, mgSetupParam, mgStartVectors, MgSetupInfo,
     coarseGram, coarseRotate, hermitianEigh, choleskyUpper, upperTriangularInverse, coarseEigensolve, coarseEigParam, coarseStartVectors, CoarseEigInfo,
+    coarseGramGrid, coarseStartVectorsGrid, coarseEigensolveGrid, CoarseEigGridInfo,
     CoarseDeflation, coarseDeflate,
     MUGIQ_EIG_OPERATOR_M, MUGIQ_EIG_OPERATOR_Mdag, MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H,
 )

@@ -111,6 +111,11 @@ class CoarseEigInfo(ctypes.Structure):
                 ("aMinLast", ctypes.c_double), ("orthonormality", ctypes.c_double), ("hostReads", ctypes.c_int), ("hostDenseSeconds", ctypes.c_double)]
 
 
+class CoarseEigGridInfo(ctypes.Structure):
+    """MugiqHipCoarseEigGridInfo (include/mugiq_hip.h)."""
+    _fields_ = [("exchanges", ctypes.c_int), ("rankSums", ctypes.c_int), ("packLaunches", ctypes.c_int), ("stepPacked", ctypes.c_int)]
+
+
 class ProjectPlan(ctypes.Structure):
     """MugiqHipProjectPlan (include/mugiq_hip.h)."""
     _fields_ = [(n, ctypes.c_int) for n in ("form", "nks", "mb", "nPx", "tChunk", "nChunks", "lastChunk", "tiles", "tilesPerWg",
@@ -344,6 +349,12 @@ SIGNATURES = {
     "mugiq_hip_coarse_eigensolve": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.POINTER(CoarseDesc), ctypes.POINTER(CoarseOperatorDesc), ctypes.c_int,
                                                    ctypes.POINTER(CoarseEigParam), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                    ctypes.POINTER(ctypes.c_double), ctypes.POINTER(CoarseEigInfo), _VP, _VP]),
+    "mugiq_hip_coarse_gram_grid": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(CoarseDesc),
+                                                  ctypes.c_int, _VP, _VP]),
+    "mugiq_hip_coarse_eigensolve_grid": (ctypes.c_int, [ctypes.POINTER(CoarseDesc), ctypes.POINTER(CoarseDesc), ctypes.POINTER(CoarseOperatorDesc),
+                                                        ctypes.POINTER(CoarseHaloDesc), ctypes.c_int, ctypes.POINTER(CoarseEigParam),
+                                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                        ctypes.POINTER(CoarseEigInfo), ctypes.POINTER(CoarseEigGridInfo), _VP, _VP]),
     "mugiq_hip_prolongate_batched": (ctypes.c_int, [_SP, ctypes.POINTER(CoarseDesc), ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),
     "mugiq_hip_prolongate_contract_batched": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.POINTER(CoarseDesc), ctypes.POINTER(ctypes.c_double),
                                                              ctypes.c_int, ctypes.POINTER(TransferDesc), _VP]),

@@ -1,7 +1,10 @@
 // The coarse-grid eigensolver: Chebyshev-filtered block subspace iteration on A = MdagM | MMdag of the explicit coarse operator
 // (csrc/coarse_op.hip), what Eigsolve_Mugiq::computeEvecs does on mg_env->diracCoarse in the reference's computeCoarse branch
 // (lib/eigsolve_mugiq.cpp:27-33, 278-287).  Contracts: mugiq_hip_coarse_gram, mugiq_hip_coarse_rotate and mugiq_hip_coarse_eigensolve in
-// include/mugiq_hip.h; the algorithm, step for step: tests/coarse_eig_ref.py.  fp64 only, one domain.
+// include/mugiq_hip.h; the algorithm, step for step: tests/coarse_eig_ref.py.  fp64 only.  On a process grid
+// (mugiq_hip_coarse_gram_grid, mugiq_hip_coarse_eigensolve_grid; tests/coarse_eig_grid_ref.py) the operator exchanges faces
+// (coarse_apply_grid), every Gram matrix and every residual sum is added over the ranks (sum_over_ranks), and everything else is local to
+// a rank or dense host algebra repeated on identical input; the Chebyshev step writes the send faces of the next application.
 //
 // A coarse vector is seen as the list of its L = 2 N volumeCB body elements, N = 2 n_vec, in the order (parity, row s n_vec + c, x_cb):
 // element e of a padded field sits at parity parity_offset + row stride + x_cb, of a packed one (stride = volumeCB, parity_offset =
@@ -49,6 +52,8 @@ constexpr int kRotElems = 32;        // rotate: elements per wave,
 constexpr int kRotOut = 64;          // ... outputs per wave,
 constexpr int kRotWaves = 4;         // ... waves per workgroup
 constexpr int kEwThreads = 256;
+constexpr int kStepRows = 8;         // rows a thread of chebyshev_step_pack_kernel walks at most from one set of coordinates
+constexpr bool kEigPackInStepDefault = true;  // the measurement the default follows
 constexpr int kPowerSteps = 20;      // first guess, NOT tuned (QUDA: 100)
 constexpr double kAmaxMargin = 1.1;  // QUDA's
 
@@ -220,17 +225,62 @@ struct ChebArgs {
   int64_t pitch, total;
   double alpha, beta;
 };
+// element `at` of the step: the one expression of both step kernels, so their values are the same bits by construction
+__device__ inline Z chebyshev_value(const ChebArgs &a, int64_t at) {
+  const Z y = ld_wide<double>(a.y, at), t = ld_wide<double>(a.t, at);
+  Z o{fma(a.alpha, y.re, a.beta * t.re), fma(a.alpha, y.im, a.beta * t.im)};
+  if (a.prev) {
+    const Z p = ld_wide<double>(a.prev, at);
+    o.re -= p.re;
+    o.im -= p.im;
+  }
+  return o;
+}
 __global__ __launch_bounds__(kEwThreads) void chebyshev_step_kernel(ChebArgs a) {
   const int64_t base = (int64_t)blockIdx.y * a.pitch;
-  for (int64_t e = (int64_t)blockIdx.x * kEwThreads + threadIdx.x; e < a.total; e += (int64_t)gridDim.x * kEwThreads) {
-    const Z y = ld_wide<double>(a.y, base + e), t = ld_wide<double>(a.t, base + e);
-    Z o{fma(a.alpha, y.re, a.beta * t.re), fma(a.alpha, y.im, a.beta * t.im)};
-    if (a.prev) {
-      const Z p = ld_wide<double>(a.prev, base + e);
-      o.re -= p.re;
-      o.im -= p.im;
-    }
-    st_round<double>(a.out, base + e, o);
+  for (int64_t e = (int64_t)blockIdx.x * kEwThreads + threadIdx.x; e < a.total; e += (int64_t)gridDim.x * kEwThreads)
+    st_round<double>(a.out, base + e, chebyshev_value(a, base + e));
+}
+
+// The step on a process grid: the same values, and where the site of an element lies on the low or the high face of a partitioned axis
+// the element goes to that face's send buffer as well, in the layout of face_pack_kernel (csrc/coarse_op.hip):
+// send[mu][high][((v 2 + parity) rows + row) faceCB + f], f = ghost_face_index_on_face.  A site can be on faces of several axes (with
+// extent 2 it is on one of the two faces of that axis) and then stores to each; plain vector stores, no atomics, no LDS.
+// A thread owns one site (vector v, parity, x_cb) and a subset of its rows: lane = x_cb within a tile of 64, so every load and the body
+// store of a wave are 64 consecutive complex numbers of one row; the coordinates and the face indices are worked out once per thread,
+// ahead of the rows.  The stores to a face are consecutive in f where the lanes' sites are (the x face: scattered).
+// grid (ceil(volumeCB / 64), 2 kEigBlock, row chunks), 4 waves: wave w of chunk z walks the rows 4 z + w, + 4 gridDim.z, ...
+struct ChebPackArgs {
+  ChebArgs c;
+  int X[4], volumeCB, rows;
+  int part[4], faceCB[4];
+  Z *send[4][2];
+};
+__global__ __launch_bounds__(kEwThreads) void chebyshev_step_pack_kernel(ChebPackArgs a) {
+  const int x_cb = blockIdx.x * 64 + (threadIdx.x & 63), v = blockIdx.y >> 1, par = blockIdx.y & 1;
+  if (x_cb >= a.volumeCB) return;
+  int c[4];
+  get_coords(c, x_cb, a.X, par);
+  Z *face[4];
+  int64_t fbase[4];
+#pragma unroll
+  for (int mu = 0; mu < 4; mu++) {
+    face[mu] = nullptr;
+    fbase[mu] = 0;
+    if (!a.part[mu]) continue;
+    const int high = c[mu] == a.X[mu] - 1 ? 1 : 0;
+    if (!high && c[mu] != 0) continue;
+    face[mu] = a.send[mu][high];
+    fbase[mu] = (int64_t)blockIdx.y * a.rows * a.faceCB[mu] + ghost_face_index_on_face(c, a.X, mu);
+  }
+  const int64_t base = (int64_t)v * a.c.pitch + (int64_t)par * a.rows * a.volumeCB + x_cb;
+  for (int row = blockIdx.z * (kEwThreads / 64) + (threadIdx.x >> 6); row < a.rows; row += gridDim.z * (kEwThreads / 64)) {
+    const int64_t at = base + (int64_t)row * a.volumeCB;
+    const Z o = chebyshev_value(a.c, at);
+    st_round<double>(a.c.out, at, o);
+#pragma unroll
+    for (int mu = 0; mu < 4; mu++)
+      if (face[mu]) st_round<double>(face[mu], fbase[mu] + (int64_t)row * a.faceCB[mu], o);
   }
 }
 
@@ -365,6 +415,13 @@ int check_eig_param(const MugiqHipCoarseEigParam *p, const char *who) {
   return MUGIQ_HIP_SUCCESS;
 }
 
+// MUGIQ_HIP_EIG_PACK_IN_STEP (read once per call of the grid solver): 1 the recurrence kernel writes the send faces of the next
+// application (chebyshev_step_pack_kernel), 0 the plain step kernel and a separate face_pack_kernel per face.  The same bits either way
+bool eig_pack_in_step() {
+  const char *e = getenv("MUGIQ_HIP_EIG_PACK_IN_STEP");
+  return e ? atoi(e) != 0 : kEigPackInStepDefault;
+}
+
 struct DeviceSlab {
   void *p = nullptr;
   ~DeviceSlab() {
@@ -394,16 +451,45 @@ struct EigRun {
   const MugiqHipCoarseField *start = nullptr;  // the caller's start vectors
   bool estimated = false;                      // the power estimate of aMax has run
 
+  // a rank of a process grid (mugiq_hip_coarse_eigensolve_grid; all unset: one domain).  The lattice is touched in three places: apply
+  // exchanges faces, gram and the residual norms are added over the ranks; the rest is local or repeated on identical input
+  const MugiqHipComm *comm = nullptr;
+  bool multi = false;  // more than one rank: sums go through sum_over_ranks
+  const MugiqHipCoarseHalo *halo = nullptr;
+  int part[4] = {0, 0, 0, 0};
+  bool partitioned = false;
+  bool packInStep = false;  // the recurrence kernel writes the send faces of the next application
+  bool facesPacked = false;  // ... and has done so for the vectors the next apply takes
+  CoarseGridLayout layout{};
+  unsigned char *wsBase = nullptr;  // the per-stream workspace, reserved once for the largest request of the call
+  MugiqHipCoarseEigGridInfo ginfo{};
+
   static double since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
   Z *body(const MugiqHipCoarseField &f) const { return static_cast<Z *>(f.data); }
 
+  int rank_sum(double *v, size_t n) {
+    if (!multi) return MUGIQ_HIP_SUCCESS;
+    std::vector<double> c(v, v + n);
+    ginfo.rankSums++;
+    if (int st = sum_over_ranks(comm, c)) return st;
+    std::copy(c.begin(), c.end(), v);
+    return MUGIQ_HIP_SUCCESS;
+  }
   int apply(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src, int n) {
     info->opBlocks += (n + kEigBlock - 1) / kEigBlock;
-    return coarse_apply(dst, src, n, op, opType, 1.0, s);
+    if (!partitioned) return coarse_apply(dst, src, n, op, opType, 1.0, s);
+    const bool packed = facesPacked;
+    facesPacked = false;
+    CoarseGridCounts counts;
+    const int st = coarse_apply_grid(dst, src, n, op, halo, part, opType, 1.0, comm, s, packed, &counts);
+    ginfo.exchanges += counts.exchanges, ginfo.packLaunches += counts.packLaunches;
+    if (packed) ginfo.stepPacked++;
+    return st;
   }
   int gram(const MugiqHipCoarseField *a, int mA, const MugiqHipCoarseField *b, int mB) {
     info->hostReads++;
-    return coarse_gram(G.data(), a, mA, b, mB, s);
+    if (int st = coarse_gram(G.data(), a, mA, b, mB, s)) return st;
+    return rank_sum(G.data(), (size_t)2 * mA * mB);
   }
 
   // nOrtho rounds of Cholesky QR of the nKr vectors Y (a base, or the caller's start vectors), written to the bases f0 and f1 in turn,
@@ -462,6 +548,7 @@ struct EigRun {
     MUGIQ_CHECK_HIP(hipMemcpyAsync(r.data(), r2_d, sizeof(double) * nKr, hipMemcpyDeviceToHost, s));
     MUGIQ_CHECK_HIP(hipStreamSynchronize(s));
     info->hostReads++;
+    if ((st = rank_sum(r.data(), (size_t)nKr))) return st;
     for (int i = 0; i < nKr; i++) r[i] = std::sqrt(r[i]);
     if (theta[nKr - 1] > aMax) {
       aMax = kAmaxMargin * theta[nKr - 1];
@@ -479,10 +566,26 @@ struct EigRun {
     return MUGIQ_HIP_SUCCESS;
   }
 
-  int cheb_step(const MugiqHipCoarseField *out, const MugiqHipCoarseField *y, const MugiqHipCoarseField *t, const MugiqHipCoarseField *prev, double alpha, double beta) {
+  // pack: `out` is the input of another application of this block, whose send faces the step writes (a grid with packInStep)
+  int cheb_step(const MugiqHipCoarseField *out, const MugiqHipCoarseField *y, const MugiqHipCoarseField *t, const MugiqHipCoarseField *prev, double alpha, double beta,
+                bool pack) {
     ChebArgs A;
     A.out = body(out[0]), A.y = body(y[0]), A.t = body(t[0]), A.prev = prev ? body(prev[0]) : nullptr;
     A.pitch = pitch, A.total = total, A.alpha = alpha, A.beta = beta;
+    if (pack) {
+      ChebPackArgs P;
+      P.c = A;
+      P.volumeCB = op->volumeCB, P.rows = 2 * op->nVec;
+      for (int d = 0; d < 4; d++) {
+        P.X[d] = op->X[d], P.part[d] = part[d], P.faceCB[d] = layout.faceCB[d];
+        for (int h = 0; h < 2; h++) P.send[d][h] = part[d] ? reinterpret_cast<Z *>(wsBase + layout.send[d][h]) : nullptr;
+      }
+      const int waves = kEwThreads / 64, chunks = (P.rows + waves * kStepRows - 1) / (waves * kStepRows);
+      hipLaunchKernelGGL(chebyshev_step_pack_kernel, dim3((unsigned)((P.volumeCB + 63) / 64), 2 * kEigBlock, (unsigned)chunks), dim3(kEwThreads), 0, s, P);
+      MUGIQ_CHECK_HIP(hipGetLastError());
+      facesPacked = true;
+      return MUGIQ_HIP_SUCCESS;
+    }
     hipLaunchKernelGGL(chebyshev_step_kernel, dim3((unsigned)std::min<int64_t>(1024, (total + kEwThreads - 1) / kEwThreads), kEigBlock), dim3(kEwThreads), 0, s, A);
     MUGIQ_CHECK_HIP(hipGetLastError());
     return MUGIQ_HIP_SUCCESS;
@@ -498,8 +601,9 @@ struct EigRun {
       int st;
       if ((st = apply(Y, cur, kEigBlock))) return st;
       const MugiqHipCoarseField *out = k == deg ? Qb : ring.data() + kEigBlock * ((k - 1) % 3);
-      if (k == 1) st = cheb_step(out, Y, cur, nullptr, d1, d2);
-      else st = cheb_step(out, Y, cur, prev, 2.0 * d1, 2.0 * d2);
+      const bool pack = partitioned && packInStep && k < deg;  // only a step that feeds another application of the block
+      if (k == 1) st = cheb_step(out, Y, cur, nullptr, d1, d2, pack);
+      else st = cheb_step(out, Y, cur, prev, 2.0 * d1, 2.0 * d2, pack);
       if (st) return st;
       prev = cur, cur = out;
     }
@@ -604,16 +708,24 @@ int mugiq_hip_coarse_eig_param_default(MugiqHipCoarseEigParam *p) {
   return MUGIQ_HIP_SUCCESS;
 }
 
-int mugiq_hip_coarse_eigensolve(const MugiqHipCoarseField *evecs_h, const MugiqHipCoarseField *start_h, const MugiqHipCoarseOperator *op, int opType,
-                                const MugiqHipCoarseEigParam *param, double *theta_h, double *residual_h, double *sigma_h, MugiqHipCoarseEigInfo *info,
-                                const MugiqHipComm *comm, void *stream) {
-  const char *who = "coarseEigensolve";
+// mugiq_hip_coarse_eigensolve (gridInfo NULL: one domain, halo not looked at) and mugiq_hip_coarse_eigensolve_grid
+static int coarse_eigensolve(const MugiqHipCoarseField *evecs_h, const MugiqHipCoarseField *start_h, const MugiqHipCoarseOperator *op,
+                             const MugiqHipCoarseHalo *halo, int opType, const MugiqHipCoarseEigParam *param, double *theta_h, double *residual_h,
+                             double *sigma_h, MugiqHipCoarseEigInfo *info, MugiqHipCoarseEigGridInfo *gridInfo, const MugiqHipComm *comm, void *stream) {
+  const bool grid = gridInfo != nullptr;
+  const char *who = grid ? "coarseEigensolveGrid" : "coarseEigensolve";
   MUGIQ_REQUIRE(evecs_h != nullptr && start_h != nullptr && param != nullptr && theta_h != nullptr && residual_h != nullptr && sigma_h != nullptr && info != nullptr,
                 "%s: NULL argument", who);
-  int st;
+  int st, part[4] = {0, 0, 0, 0};
   if ((st = check_eig_param(param, who))) return st;
-  if ((st = check_single_domain(comm, who))) return st;
-  if ((st = validate_coarse_operator(op, who))) return st;
+  if (grid) {
+    MUGIQ_REQUIRE(comm != nullptr, "%s: comm is NULL (the single-domain call is mugiq_hip_coarse_eigensolve)", who);
+    if ((st = check_coarse_grid(comm, op, halo, part, true, who))) return st;
+  } else {
+    if ((st = check_single_domain(comm, who))) return st;
+    if ((st = validate_coarse_operator(op, who))) return st;
+  }
+  const int nRanks = grid ? comm->size : 1;
   MUGIQ_REQUIRE(valid_op(opType), "%s: opType %d is none of M, Mdag, MdagM, MMdag, H", who, opType);
   if (!normal_op(opType))
     return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "%s: opType %d: the solver needs a Hermitian positive operator, MdagM or MMdag", who, opType);
@@ -624,7 +736,7 @@ int mugiq_hip_coarse_eigensolve(const MugiqHipCoarseField *evecs_h, const MugiqH
   if ((st = validate_coarse_vectors(start_h, nKr, op, who, "start"))) return st;
   if ((st = validate_coarse_vectors(evecs_h, nConv, op, who, "evecs"))) return st;
   const int64_t total = (int64_t)2 * 2 * op->nVec * op->volumeCB;
-  MUGIQ_REQUIRE(nKr <= total, "%s: nKr = %d exceeds the dimension %lld of the coarse space", who, nKr, (long long)total);
+  MUGIQ_REQUIRE(nKr <= total * nRanks, "%s: nKr = %d exceeds the dimension %lld of the coarse space", who, nKr, (long long)(total * nRanks));
   for (int j = 0; j < nConv; j++) {
     uintptr_t a0, a1;
     coarse_span(evecs_h[j], &a0, &a1);
@@ -643,9 +755,23 @@ int mugiq_hip_coarse_eigensolve(const MugiqHipCoarseField *evecs_h, const MugiqH
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
   *info = MugiqHipCoarseEigInfo{};
+  if (gridInfo) *gridInfo = MugiqHipCoarseEigGridInfo{};
   EigRun run;
   run.op = op, run.opType = opType, run.prm = param, run.info = info, run.s = s, run.who = who, run.nKr = nKr, run.total = total;
   run.nChunks = gram_nchunks(total);
+  if (grid) {
+    run.comm = comm, run.halo = halo, run.multi = comm->size > 1;
+    for (int d = 0; d < 4; d++) run.part[d] = part[d], run.partitioned |= part[d] != 0;
+  }
+  if (run.partitioned) {
+    // the per-stream workspace, once, for the largest request of the call (the Gram matrix of a basis; the faces and the intermediate of
+    // an application of 8 vectors): it stays where it is, so the recurrence kernel knows the send buffers of the next application
+    run.packInStep = eig_pack_in_step();
+    coarse_grid_layout(&run.layout, op, part, opType, kEigBlock);
+    void *ws = nullptr;
+    if ((st = stream_workspace(&ws, std::max(run.layout.bytes, sizeof(Z) * (size_t)nKr * nKr * ((size_t)run.nChunks + 1)), s))) return st;
+    run.wsBase = static_cast<unsigned char *>(ws);
+  }
   // work memory: three bases of nKr packed vectors, 24 vectors for the Chebyshev recurrence, and the scalars of the residual kernels
   const size_t vecBytes = align256((size_t)total * sizeof(Z)), nWork = (size_t)3 * nKr + 3 * kEigBlock;
   const size_t scalBytes = align256(sizeof(double) * (size_t)nKr * (2 + run.nChunks));
@@ -696,6 +822,7 @@ int mugiq_hip_coarse_eigensolve(const MugiqHipCoarseField *evecs_h, const MugiqH
     info->aMaxUsed = run.aMax, info->aMinLast = run.aMinLast;
     info->orthonormality = dev;
     info->hostDenseSeconds = run.dense;
+    if (gridInfo) *gridInfo = run.ginfo;
     MUGIQ_CHECK_HIP(hipStreamSynchronize(s));
     if (status == MUGIQ_HIP_ERROR_INVALID_ARGUMENT)
       return set_error(status, "%s: %s: a pivot of the Cholesky QR fell to rankTol = %.3e x the largest squared norm: the basis is dependent (outputs and info are filled)", who,
@@ -730,6 +857,41 @@ int mugiq_hip_coarse_eigensolve(const MugiqHipCoarseField *evecs_h, const MugiqH
     info->iters++;
   }
   return finish(run.base[run.q].data(), done() ? MUGIQ_HIP_SUCCESS : MUGIQ_HIP_ERROR_NOT_CONVERGED, "");
+}
+
+int mugiq_hip_coarse_eigensolve(const MugiqHipCoarseField *evecs_h, const MugiqHipCoarseField *start_h, const MugiqHipCoarseOperator *op, int opType,
+                                const MugiqHipCoarseEigParam *param, double *theta_h, double *residual_h, double *sigma_h, MugiqHipCoarseEigInfo *info,
+                                const MugiqHipComm *comm, void *stream) {
+  return coarse_eigensolve(evecs_h, start_h, op, nullptr, opType, param, theta_h, residual_h, sigma_h, info, nullptr, comm, stream);
+}
+
+int mugiq_hip_coarse_eigensolve_grid(const MugiqHipCoarseField *evecs_h, const MugiqHipCoarseField *start_h, const MugiqHipCoarseOperator *op,
+                                     const MugiqHipCoarseHalo *halo, int opType, const MugiqHipCoarseEigParam *param, double *theta_h,
+                                     double *residual_h, double *sigma_h, MugiqHipCoarseEigInfo *info, MugiqHipCoarseEigGridInfo *gridInfo,
+                                     const MugiqHipComm *comm, void *stream) {
+  MUGIQ_REQUIRE(gridInfo != nullptr, "coarseEigensolveGrid: NULL argument");
+  return coarse_eigensolve(evecs_h, start_h, op, halo, opType, param, theta_h, residual_h, sigma_h, info, gridInfo, comm, stream);
+}
+
+int mugiq_hip_coarse_gram_grid(double *G_h, const MugiqHipCoarseField *a_h, int mA, const MugiqHipCoarseField *b_h, int mB, const MugiqHipComm *comm,
+                               void *stream) {
+  const char *who = "coarseGramGrid";
+  MUGIQ_REQUIRE(G_h != nullptr && a_h != nullptr && b_h != nullptr, "%s: NULL argument", who);
+  MUGIQ_REQUIRE(comm != nullptr, "%s: comm is NULL (the single-domain call is mugiq_hip_coarse_gram)", who);
+  MUGIQ_REQUIRE(mA >= 1 && mB >= 1 && mA <= 4096 && mB <= 4096, "%s: mA = %d and mB = %d must be in [1, 4096]", who, mA, mB);
+  int st, part[4];
+  if ((st = check_comm(comm, part, true, who))) return st;
+  if ((st = check_fields(a_h, mA, nullptr, who, "a"))) return st;
+  if ((st = check_fields(b_h, mB, a_h, who, "b"))) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((st = debug_poison_lds_if_asked(s))) return st;
+  if ((st = coarse_gram(G_h, a_h, mA, b_h, mB, s))) return st;
+  if (comm->size > 1) {
+    std::vector<double> c(G_h, G_h + (size_t)2 * mA * mB);
+    if ((st = sum_over_ranks(comm, c))) return st;
+    std::copy(c.begin(), c.end(), G_h);
+  }
+  return MUGIQ_HIP_SUCCESS;
 }
 
 }  // extern "C"

@@ -652,42 +652,76 @@ int check_coarse_grid(const MugiqHipComm *comm, const MugiqHipCoarseOperator *op
   return MUGIQ_HIP_SUCCESS;
 }
 
-// validated arguments.  Work memory (per-stream workspace): [the intermediate of a normal form, 8 vectors][per partitioned axis: two send
-// and two receive faces of the most vectors one launch takes].  Per launch: faces packed and exchanged (one group), then the kernel
-int coarse_apply_grid(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src, int nVec, const MugiqHipCoarseOperator *op,
-                      const MugiqHipCoarseHalo *halo, const int part[4], int opType, double scale, const MugiqHipComm *comm, hipStream_t stream) {
-  if (!any_partitioned(part)) return coarse_apply(dst, src, nVec, op, opType, scale, stream);
-  const char *who = "coarseApplyGrid";
+// The work memory of coarse_apply_grid, from the start of the per-stream workspace: [the intermediate of a normal form, 8 vectors][per
+// partitioned axis: two send and two receive faces of the most vectors one launch takes].  A function of the operator, the partitioned
+// axes, the form and min(nVec, 8) alone
+void coarse_grid_layout(CoarseGridLayout *L, const MugiqHipCoarseOperator *op, const int part[4], int opType, int nVec) {
   const int N = 2 * op->nVec, perLaunch = normal_op(opType) ? std::min(kCaRB, nVec) : nVec;
   const size_t cplx = 2 * (size_t)op->precision, one = normal_op(opType) ? align256((size_t)2 * N * op->volumeCB * cplx) : 0;
+  *L = CoarseGridLayout{};
+  L->intermediate = one;
+  size_t at = kCaRB * one;
+  for (int d = 0; d < 4; d++) {
+    L->faceCB[d] = op->volumeCB / op->X[d];
+    L->cap[d] = part[d] ? (size_t)perLaunch * 2 * N * L->faceCB[d] * cplx : 0;
+    for (int k = 0; k < 4; k++) {  // send low, send high, receive backward, receive forward
+      if (L->cap[d] == 0) continue;
+      (k < 2 ? L->send[d][k] : L->recv[d][k - 2]) = at;
+      at += align256(L->cap[d]);
+    }
+  }
+  L->bytes = at;
+}
+
+// validated arguments.  Work memory (per-stream workspace): coarse_grid_layout.  Per launch: faces packed and exchanged (one group), then
+// the kernel.  firstPacked: the send faces of the first launch are in place already (written by the caller into the buffers of
+// coarse_grid_layout; nVec <= 8, one block): that launch exchanges without packing.  counts (may be NULL): exchanges and pack launches
+// are added
+int coarse_apply_grid(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src, int nVec, const MugiqHipCoarseOperator *op,
+                      const MugiqHipCoarseHalo *halo, const int part[4], int opType, double scale, const MugiqHipComm *comm, hipStream_t stream,
+                      bool firstPacked, CoarseGridCounts *counts) {
+  if (!any_partitioned(part)) return coarse_apply(dst, src, nVec, op, opType, scale, stream);
+  const char *who = "coarseApplyGrid";
+  const int N = 2 * op->nVec;
+  const size_t cplx = 2 * (size_t)op->precision;
+  CoarseGridLayout L;
+  coarse_grid_layout(&L, op, part, opType, nVec);
+  const size_t one = L.intermediate;
   ApplyGhost<true> gh;
-  size_t cap[4], total = kCaRB * one;
   for (int d = 0; d < 4; d++) {
     gh.part[d] = part[d];
-    gh.faceCB[d] = op->volumeCB / op->X[d];
+    gh.faceCB[d] = L.faceCB[d];
     gh.Y[d][0] = part[d] ? halo->Yback[d] : nullptr;
     gh.Y[d][1] = part[d] ? halo->Yfwd[d] : nullptr;
-    cap[d] = part[d] ? (size_t)perLaunch * 2 * N * gh.faceCB[d] * cplx : 0;
-    total += 4 * align256(cap[d]);
   }
   void *ws = nullptr;
-  if (int st = stream_workspace(&ws, total, stream)) return st;
-  unsigned char *cur = static_cast<unsigned char *>(ws) + kCaRB * one;
+  if (int st = stream_workspace(&ws, L.bytes, stream)) return st;
   FaceBuffers fb;
-  carve_faces(&fb, &cur, cap, true);
+  for (int d = 0; d < 4; d++)
+    for (int k = 0; k < 2; k++) {
+      if (L.cap[d] == 0) continue;
+      fb.send[d][k] = static_cast<unsigned char *>(ws) + L.send[d][k];
+      fb.recv[d][k] = static_cast<unsigned char *>(ws) + L.recv[d][k];
+    }
   for (int d = 0; d < 4; d++) gh.vec[d][0] = fb.recv[d][0], gh.vec[d][1] = fb.recv[d][1];
 
+  int launches = 0;
   auto simple = [&](const MugiqHipCoarseField *d_, const MugiqHipCoarseField *s_, int n, int dagger, int gamma5, double f) -> int {
     std::vector<const void *> host(2 * (size_t)n);  // (the size of launch_apply's table, so the buffer stays where it is)
     for (int i = 0; i < n; i++) host[i] = host[n + i] = s_[i].data;
     void *dev = nullptr;
     if (int st = upload_table(&dev, host.data(), host.size() * sizeof(void *), stream)) return st;
     for (int d = 0; d < 4; d++) fb.bytes[d] = part[d] ? (size_t)n * 2 * N * gh.faceCB[d] * cplx : 0;
-    int st = exchange_faces(comm, part, fb, stream, who, [&](int d, int high, unsigned char *send) {
+    const bool packed = firstPacked && launches == 0;
+    launches++;
+    int st = exchange_faces(comm, part, fb, stream, who, [&](int d, int high, unsigned char *send) -> int {
+      if (packed) return MUGIQ_HIP_SUCCESS;
+      if (counts) counts->packLaunches++;
       FacePackArgs p{static_cast<const void *const *>(dev), nullptr, send, N, s_[0].stride, s_[0].parity_offset, {op->X[0], op->X[1], op->X[2], op->X[3]}, d, high, gh.faceCB[d]};
       return with_storage(op->precision, [&](auto fs) { return launch_face_pack<decltype(fs)>(p, n, stream); });
     });
     if (st) return st;
+    if (counts) counts->exchanges++;
     return launch_apply(d_, s_, n, op, dagger, gamma5, f, stream, &gh);
   };
   MugiqHipCoarseField tmp[kCaRB];

@@ -150,8 +150,24 @@ int coarse_apply(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src,
 // its validation.  With part all 0 it is coarse_apply
 int check_coarse_grid(const MugiqHipComm *comm, const MugiqHipCoarseOperator *op, const MugiqHipCoarseHalo *halo, int part[4], bool needSums,
                       const char *who);
+// coarse_grid_layout: where coarse_apply_grid keeps its work memory, as byte offsets from the start of stream_workspace (send: the low
+// [0] and the high [1] face of a partitioned axis, in the layout of face_pack_kernel; cap: bytes of one face buffer, 0 where the axis is
+// not partitioned).  A caller that reserves `bytes` or more once (a reservation of the largest size stays where it is) knows the
+// addresses of every later call with the same operator, axes, form and min(nVec, 8): the coarse eigensolver writes the send faces of the
+// next application from its recurrence kernel and passes firstPacked, which makes the first launch exchange them as they are.
+// counts (may be NULL): the exchanges issued and the launches of face_pack_kernel made are added
+struct CoarseGridLayout {
+  size_t bytes, intermediate;
+  size_t send[4][2], recv[4][2], cap[4];
+  int faceCB[4];
+};
+struct CoarseGridCounts {
+  int exchanges = 0, packLaunches = 0;
+};
+void coarse_grid_layout(CoarseGridLayout *L, const MugiqHipCoarseOperator *op, const int part[4], int opType, int nVec);
 int coarse_apply_grid(const MugiqHipCoarseField *dst, const MugiqHipCoarseField *src, int nVec, const MugiqHipCoarseOperator *op,
-                      const MugiqHipCoarseHalo *halo, const int part[4], int opType, double scale, const MugiqHipComm *comm, hipStream_t stream);
+                      const MugiqHipCoarseHalo *halo, const int part[4], int opType, double scale, const MugiqHipComm *comm, hipStream_t stream,
+                      bool firstPacked = false, CoarseGridCounts *counts = nullptr);
 // csrc/wilson.hip: the gauge field of an operator call against the local dims X and the partitioned axes; comm -> part[4]
 int check_gauge(const MugiqHipGaugeField *U, const int X[4], const int part[4], const char *who);
 int check_comm(const MugiqHipComm *comm, int part[4], bool needSums, const char *who);

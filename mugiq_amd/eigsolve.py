@@ -22,6 +22,7 @@ MgSolveInfo = collections.namedtuple("MgSolveInfo", "iters relres converged hist
 MgSetupInfo = collections.namedtuple("MgSetupInfo", "cgIters minPivotRatio zeroColumns orthonormality hostReads cgHostReadsEstimate")
 MgSetupCoarseInfo = collections.namedtuple("MgSetupCoarseInfo", "theta residual eigensolve minPivotRatio zeroColumns orthonormality")
 CoarseEigInfo = collections.namedtuple("CoarseEigInfo", "iters nConverged opBlocks aMaxUsed aMinLast orthonormality hostReads hostDenseSeconds converged")
+CoarseEigGridInfo = collections.namedtuple("CoarseEigGridInfo", "exchanges rankSums packLaunches stepPacked")
 
 
 def _stream():
@@ -732,6 +733,67 @@ def coarseEigensolve(op, opType=MUGIQ_EIG_OPERATOR_MdagM, start=None, seed=0, eV
     return eVecs, theta[:nc], res[:nc], sig[:nc], CoarseEigInfo(int(info.iters), int(info.nConverged), int(info.opBlocks), float(info.aMaxUsed),
                                                                  float(info.aMinLast), float(info.orthonormality), int(info.hostReads),
                                                                  float(info.hostDenseSeconds), st == 0)
+
+
+def coarseGramGrid(a, b=None, comm=None):
+    """coarseGram for the local blocks of vectors on a process grid (mugiq_hip_coarse_gram_grid; collective): the local Gram matrix added
+    over the ranks in a fixed order, the same bits on every rank.  comm is required; on a comm of one rank this is coarseGram."""
+    a = list(a)
+    b = a if b is None else list(b)
+    if comm is None or not a or not b:
+        raise _lib.MugiqHipError("coarseGramGrid: needs a comm and at least one vector on each side")
+    G = np.zeros((len(a), len(b)), np.complex128)
+    keep = []
+    _lib.check(_lib.load().mugiq_hip_coarse_gram_grid(_dptr(G), coarse_desc_array(a), len(a), coarse_desc_array(b), len(b), _comm_ptr(comm, keep),
+                                                      _stream()))
+    return G
+
+
+def coarseStartVectorsGrid(Xc_local, n_vec, nKr, comm, seed=0, pad=0, device="cuda"):
+    """nKr fp64 CoarseFields of seeded Gaussian noise on the rank's local coarse lattice: the start vectors of coarseEigensolveGrid.  The
+    generator is seeded from (seed, comm.rank), so every rank draws its own block -- and the start, hence every iterate, depends on the
+    process grid: the same seed on another grid is another start space.  (For a start that does not, slice one global array.)  Pads, if
+    any, are left zero."""
+    if comm is None:
+        raise _lib.MugiqHipError("coarseStartVectorsGrid: comm is required")
+    return coarseStartVectors(Xc_local, n_vec, nKr, int(np.random.SeedSequence([int(seed), int(comm.rank)]).generate_state(1, np.uint64)[0] >> 1), pad, device)
+
+
+def coarseEigensolveGrid(op, comm, opType=MUGIQ_EIG_OPERATOR_MdagM, start=None, seed=0, eVecs=None, allow_unconverged=False, **param):
+    """coarseEigensolve on a process grid (mugiq_hip_coarse_eigensolve_grid; collective): op from computeCoarseOperatorGrid (its op.halo is
+    passed on), start and eVecs the rank's local blocks (default start: coarseStartVectorsGrid(op.X, op.n_vec, nKr, comm, seed)); nKr may
+    reach the global dimension.  Operator applications exchange faces, every Gram matrix and residual sum is added over the ranks, the
+    dense algebra is repeated on every rank: theta, residual, sigma and every count are identical on all ranks.  Returns (eVecs, theta,
+    residual, sigma, CoarseEigInfo, CoarseEigGridInfo(exchanges, rankSums, packLaunches, stepPacked)).  MUGIQ_HIP_EIG_PACK_IN_STEP=0: the
+    Chebyshev step does not write the faces of the next application (the same bits)."""
+    if comm is None:
+        raise _lib.MugiqHipError("coarseEigensolveGrid: comm is required")
+    p = coarseEigParam(**param)
+    if start is None:
+        start = coarseStartVectorsGrid(op.X, op.n_vec, p.nKr, comm, seed, device=op.device)
+    start = list(start)
+    if len(start) != p.nKr:
+        raise _lib.MugiqHipError("coarseEigensolveGrid: %d start vectors for nKr = %d" % (len(start), p.nKr))
+    if eVecs is None:
+        eVecs = [CoarseField(op.X, op.n_vec, 8, device=op.device) for _ in range(max(int(p.nConv), 0))]
+    eVecs = list(eVecs)
+    if len(eVecs) != p.nConv:
+        raise _lib.MugiqHipError("coarseEigensolveGrid: %d eigenvector fields for nConv = %d" % (len(eVecs), p.nConv))
+    n = max(int(p.nConv), 1)
+    theta, res, sig = np.zeros(n), np.zeros(n), np.zeros(n)
+    info, ginfo = _lib.CoarseEigInfo(), _lib.CoarseEigGridInfo()
+    keep = []
+    d = op.desc()
+    st = _lib.load().mugiq_hip_coarse_eigensolve_grid(coarse_desc_array(eVecs) if eVecs else None, coarse_desc_array(start) if start else None,
+                                                      ctypes.byref(d), _halo_ptr(op, comm, keep), int(opType), ctypes.byref(p), _dptr(theta), _dptr(res),
+                                                      _dptr(sig), ctypes.byref(info), ctypes.byref(ginfo), _comm_ptr(comm, keep), _stream())
+    if st != 0 and not (st == STATUS_NOT_CONVERGED and allow_unconverged):
+        _lib.check(st)
+    nc = int(p.nConv)
+    return (eVecs, theta[:nc], res[:nc], sig[:nc],
+            CoarseEigInfo(int(info.iters), int(info.nConverged), int(info.opBlocks), float(info.aMaxUsed), float(info.aMinLast),
+                          float(info.orthonormality), int(info.hostReads), float(info.hostDenseSeconds), st == 0),
+            CoarseEigGridInfo(int(ginfo.exchanges), int(ginfo.rankSums), int(ginfo.packLaunches), int(ginfo.stepPacked)))
 
 
 def format_evals(evals, evals_quda, residuals, sigmas=None):
