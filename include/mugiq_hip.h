@@ -797,8 +797,9 @@ int mugiq_hip_compute_evals_coarse_operator(const MugiqHipCoarseField *coarseEve
  * Both NULL on an axis the halo was not built for (dims[mu] == 0).  With a rank as its own neighbour (MugiqHipComm.partitioned) the
  * halo holds copies of the rank's own matrices.
  *
- * These three calls serve a grid, and on top of them mugiq_hip_coarse_gram_grid and mugiq_hip_coarse_eigensolve_grid (further down).  The
- * MG solve, mugiq_hip_mg_setup, the coarse deflation and mugiq_hip_compute_coarse_operator_coarse stay single-domain and refuse a
+ * These three calls serve a grid, and on top of them mugiq_hip_coarse_gram_grid, mugiq_hip_coarse_eigensolve_grid and the two-grid fp64
+ * mugiq_hip_mg_precondition_grid / mugiq_hip_mg_solve_grid (further down).  Every other MG solve entry point (three levels, mixed,
+ * deflated), mugiq_hip_mg_setup, the coarse deflation and mugiq_hip_compute_coarse_operator_coarse stay single-domain and refuse a
  * partitioned comm, as do the three single-domain calls above and mugiq_hip_coarse_eigensolve, mugiq_hip_coarse_gram and
  * mugiq_hip_coarse_rotate.  The exchange is not overlapped with interior work. */
 typedef struct MugiqHipCoarseHalo_s {
@@ -935,6 +936,52 @@ int mugiq_hip_mg_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField
                        const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *coarseOp,
                        const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out, double *history_out, int historyStride,
                        int *hostReads_out, const MugiqHipComm *comm, void *stream);
+
+/* ---- the two-grid cycle and solve on a process grid (new; csrc/mg_solve.hip; tests/mg_solve_grid_ref.py restates the
+ * recurrence rank by rank).  fp64, one coarse level, no deflation space.  Collective: every rank calls with its local fields.
+ *
+ * M is applied with its halo exchange (ghost zones as for mugiq_hip_wilson_clover_apply, gauge border R >= 1 on every partitioned axis),
+ * M_c by the internals of mugiq_hip_coarse_apply_grid (coarseOp and halo from mugiq_hip_compute_coarse_operator_grid); R and P are local
+ * to a rank, which owns whole aggregates.  Every inner product is the fixed-order sum of the rank, written into the rank's entry of a table
+ * [rank][8][32] doubles on the device (rank order: x slowest, t fastest); a ring gather over every axis of extent > 1, t first, completes
+ * the table on every rank -- sum_d (grid[d] - 1) calls of comm->sendrecv(.., d, +1, stream) on device buffers, straight from and into the
+ * table, no host read and no pack kernel -- and one workgroup (mg_rank_sum_kernel) adds the entries in ascending rank order and forms what
+ * the next kernel reads: the Gram-Schmidt coefficients, (nu, <q, r> / nu), the MR alpha, or the raw norms the host fetches.  The guards
+ * nu > 0 and <t, t> > 0 act on the global sums.  Every rank adds the same numbers in the same order, so all ranks hold the same bits and
+ * iteration counts, restarts, histories and statuses agree without a broadcast; the one read per outer iteration is the global value and
+ * hostReads keeps its formula.  comm->reduce_space, gather_time and bcast are not used.  The sums are added per rank first, so on more than one
+ * rank results agree with the single-domain solve to rounding, not bit for bit.  With one rank (forced axes only) no table exists,
+ * nothing is gathered, and the results are the bits of mugiq_hip_mg_precondition / mugiq_hip_mg_solve; with nothing partitioned the calls
+ * ARE those calls, launch for launch (halo may then be NULL).
+ *
+ * r_h of the cycle is read by the stencil in place: it needs ghost zones on every partitioned axis (refused otherwise, like src of
+ * mugiq_hip_wilson_apply).  z_h, x_h and b_h need none.  Checks, each before any device work: comm NULL; those of
+ * mugiq_hip_coarse_apply_grid (sendrecv NULL on a partitioned comm; halo NULL on a partitioned comm, of another operator, or not built for
+ * a partitioned axis); comm->grid, coord, rank and size that do not describe one grid; a gauge border of 0 on a partitioned axis;
+ * everything mugiq_hip_mg_precondition / mugiq_hip_mg_solve check (precision 4: MUGIQ_HIP_ERROR_UNSUPPORTED); gridInfo_out NULL.
+ * Work memory: that of the single-domain calls, every fine vector followed by its ghost zones, plus the stencil's send buffers, one more
+ * set of ghost zones per right-hand side of a block and the rank table (operator workspace), and the faces of the coarse application (the
+ * per-stream workspace, reserved once per call).  The exchanges are not overlapped with interior work. */
+typedef struct MugiqHipMgSolveGridInfo_s {
+  int fineExchanges;   /* applications of M that exchanged ghost zones (0 with nothing partitioned) */
+  int coarseExchanges; /* applications of M_c that exchanged faces */
+  int rankSums;        /* sums that went through the rank table (0 on one rank: there is nothing to add) */
+  int rankSumMessages; /* sendrecv calls made for them: rankSums * sum_d (grid[d] - 1) */
+} MugiqHipMgSolveGridInfo;
+int mugiq_hip_mg_precondition_grid(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
+                                   const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *coarseOp,
+                                   const MugiqHipCoarseHalo *halo, const MugiqHipMgSolveParam *param, const MugiqHipComm *comm, void *stream);
+int mugiq_hip_mg_solve_grid(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                            const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *coarseOp,
+                            const MugiqHipCoarseHalo *halo, const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out, double *history_out,
+                            int historyStride, int *hostReads_out, MugiqHipMgSolveGridInfo *gridInfo_out, const MugiqHipComm *comm, void *stream);
+/* The messages of the ring gather, for inspection (host only, no device): what the rank at `coord` of `grid` posts, in order.  Message m
+ * is sendrecv(table + sendEntry[m], table + recvEntry[m], entries[m] entries, dim[m], +1): it sends the run that starts at entry
+ * sendEntry[m] to the neighbour at coord[dim[m]] + 1 and receives the run at recvEntry[m] from the neighbour at coord[dim[m]] - 1 (an
+ * entry: the 8 x 32 doubles of one rank).  Returns the number of messages, sum_d (grid[d] - 1), and fills the first maxOps of each
+ * array that is not NULL; -1 for a NULL grid or coord, an extent < 1 or a coordinate outside its extent. */
+int mugiq_hip_mg_rank_sum_plan(const int grid[4], const int coord[4], int maxOps, int *dim_out, int *sendEntry_out, int *recvEntry_out,
+                               int *entries_out);
 
 /* ---- the mixed-precision solve (new; csrc/mg_solve.hip): the cycle K in fp32 storage under the fp64 outer GCR, what QUDA's
  * --prec-sloppy / --prec-precondition give the reference's MG solve.  mugiq_hip_mg_precondition and mugiq_hip_mg_solve above do not

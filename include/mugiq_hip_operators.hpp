@@ -296,6 +296,26 @@ inline bool mgSolve(const std::vector<ColorSpinorField> &x, const std::vector<Co
                                     relres.data(), history ? hist.data() : nullptr, stride, hostReads, comm, stream);
   return detail::mgHistory(st, hist, stride, iters, history);
 }
+// ---- on a process grid (mugiq_hip_mg_precondition_grid, mugiq_hip_mg_solve_grid; new): the same two calls for a rank, with the halo of
+// the coarse operator (mugiq_hip_compute_coarse_operator_grid) and a comm, which is required.  r needs ghost zones on the partitioned axes
+inline void mgPrecondition(const std::vector<ColorSpinorField> &z, const std::vector<ColorSpinorField> &r, const GaugeField &gauge,
+                           const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer &transfer, const CoarseOperator &coarseOp,
+                           const MugiqHipCoarseHalo &halo, const MgSolveParam &param, const MugiqHipComm *comm, void *stream = nullptr) {
+  if (r.empty() || z.size() != r.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgPrecondition: size mismatch");
+  check(mugiq_hip_mg_precondition_grid(z.data(), r.data(), (int)r.size(), &gauge, clover, kappa, &transfer, coarseOp.desc(), &halo, &param, comm, stream));
+}
+inline bool mgSolve(const std::vector<ColorSpinorField> &x, const std::vector<ColorSpinorField> &b, const GaugeField &gauge,
+                    const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer &transfer, const CoarseOperator &coarseOp,
+                    const MugiqHipCoarseHalo &halo, const MgSolveParam &param, std::vector<int> &iters, std::vector<double> &relres,
+                    MugiqHipMgSolveGridInfo &gridInfo, const MugiqHipComm *comm, std::vector<std::vector<double>> *history = nullptr,
+                    int *hostReads = nullptr, void *stream = nullptr) {
+  if (b.empty() || x.size() != b.size()) throw Error(MUGIQ_HIP_ERROR_INVALID_ARGUMENT, "mgSolve: size mismatch");
+  int stride;
+  std::vector<double> hist = detail::mgOutputs(b.size(), param.maxIter, history != nullptr, iters, relres, &stride);
+  const int st = mugiq_hip_mg_solve_grid(x.data(), b.data(), (int)b.size(), &gauge, clover, kappa, &transfer, coarseOp.desc(), &halo, &param, iters.data(),
+                                         relres.data(), history ? hist.data() : nullptr, stride, hostReads, &gridInfo, comm, stream);
+  return detail::mgHistory(st, hist, stride, iters, history);
+}
 // ---- the mixed-precision solve (csrc/mg_solve.hip; new): the cycle in fp32 storage under the fp64 outer GCR ----
 // z_i = K(r_i) with z, r, transfer and coarseOp all of precision 4 (mugiq_hip_mg_precondition_sloppy)
 inline void mgPreconditionSloppy(const std::vector<ColorSpinorField> &z, const std::vector<ColorSpinorField> &r, const GaugeField &gauge,

@@ -33,6 +33,7 @@ from .eigsolve import (  # noqa: E402
     mgSolve, mgPrecondition, mgSolveMixed, mgPreconditionSloppy, mgConvertPrecision, mgSolveParam, MgSolveInfo, mgSetup, mgSetupCoarse, MgSetupCoarseInfo, mgSetupParam, mgStartVectors, MgSetupInfo,
     coarseGram, coarseRotate, hermitianEigh, choleskyUpper, upperTriangularInverse, coarseEigensolve, coarseEigParam, coarseStartVectors, CoarseEigInfo,
     coarseGramGrid, coarseStartVectorsGrid, coarseEigensolveGrid, CoarseEigGridInfo,
+    mgPreconditionGrid, mgSolveGrid, mgRankSumPlan, MgSolveGridInfo,
     CoarseDeflation, coarseDeflate,
     MUGIQ_EIG_OPERATOR_M, MUGIQ_EIG_OPERATOR_Mdag, MUGIQ_EIG_OPERATOR_MdagM, MUGIQ_EIG_OPERATOR_MMdag, MUGIQ_EIG_OPERATOR_H,
 )

@@ -116,6 +116,11 @@ class CoarseEigGridInfo(ctypes.Structure):
     _fields_ = [("exchanges", ctypes.c_int), ("rankSums", ctypes.c_int), ("packLaunches", ctypes.c_int), ("stepPacked", ctypes.c_int)]
 
 
+class MgSolveGridInfo(ctypes.Structure):
+    """MugiqHipMgSolveGridInfo (include/mugiq_hip.h)."""
+    _fields_ = [("fineExchanges", ctypes.c_int), ("coarseExchanges", ctypes.c_int), ("rankSums", ctypes.c_int), ("rankSumMessages", ctypes.c_int)]
+
+
 class ProjectPlan(ctypes.Structure):
     """MugiqHipProjectPlan (include/mugiq_hip.h)."""
     _fields_ = [(n, ctypes.c_int) for n in ("form", "nks", "mb", "nPx", "tChunk", "nChunks", "lastChunk", "tiles", "tilesPerWg",
@@ -294,6 +299,14 @@ SIGNATURES = {
     "mugiq_hip_mg_solve": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
                                           ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(MgSolveParam), _I4, ctypes.POINTER(ctypes.c_double),
                                           ctypes.POINTER(ctypes.c_double), ctypes.c_int, _I4, _VP, _VP]),
+    "mugiq_hip_mg_precondition_grid": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
+                                                      ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(CoarseHaloDesc), ctypes.POINTER(MgSolveParam),
+                                                      _VP, _VP]),
+    "mugiq_hip_mg_solve_grid": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
+                                               ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(CoarseHaloDesc), ctypes.POINTER(MgSolveParam), _I4,
+                                               ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_int, _I4,
+                                               ctypes.POINTER(MgSolveGridInfo), _VP, _VP]),
+    "mugiq_hip_mg_rank_sum_plan": (ctypes.c_int, [_I4, _I4, ctypes.c_int, _I4, _I4, _I4, _I4]),
     "mugiq_hip_mg_precondition_sloppy": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, ctypes.POINTER(TransferDesc),
                                                         ctypes.POINTER(CoarseOperatorDesc), ctypes.POINTER(MgSolveParam), _VP, _VP]),
     "mugiq_hip_mg_solve_mixed": (ctypes.c_int, [_SP, _SP, ctypes.c_int, _GP, _CP, ctypes.c_double, _GP, _CP, ctypes.POINTER(TransferDesc),

@@ -185,6 +185,9 @@ struct OpContext {
   const MugiqHipCloverField *clover = nullptr;  // NULL: the unimproved operator
 };
 size_t stencil_send_bytes(const MugiqHipSpinorField &like, int prec, const int part[4], int n);
+// ... and the bytes one ghost zone of axis d takes where a caller carves the zones of a field one behind the other ([d][low, high], the
+// partitioned axes only): together the stencil_send_bytes of one field
+size_t stencil_zone_bytes(const MugiqHipSpinorField &like, int prec, int d);
 int stencil_apply(const OpContext &c, const MugiqHipSpinorField *dst, const MugiqHipSpinorField *src, int n, int dagger, int gamma5, double scale);
 // csrc/clover.hip: descriptor bounds; X != NULL: and the geometry of the fields it is applied to
 int validate_clover(const MugiqHipCloverField *C, const int X[4], int volumeCB, const char *who);

@@ -7,6 +7,8 @@
 // restricts to the next level, solves there (MgSolver::solve: GCRfix on the last level, the flexible GCR above it) and prolongs back.
 // With a deflation space for the last level (the *_levels_deflated entry points) its GCRfix starts from the projection on the space
 // (csrc/mg_deflate.hip, called through csrc/mg_common.h); without one nothing here takes another path.
+// On a process grid (the *_grid entry points: two-grid, fp64) M and M_c exchange halos and every final sum is completed over the ranks on
+// the device: the rank table, its ring gather and mg_rank_sum_kernel (MgRankSum).  One rank makes no such sum.
 //
 // One set of kernels serves both levels and both storages: a field is a list of rows of complex numbers (MgLayout; fine FLOAT2: 12 rows of
 // volumeCB per parity, fine FLOAT4: 6 rows of 2 volumeCB, coarse: 2 n_vec rows of volumeCB_c) stored as Cplx<F>, F = double or float.  Every
@@ -232,17 +234,14 @@ __global__ __launch_bounds__(kMgThreads) void mg_convert_kernel(MgVecs<FD> D, Mg
 // The sums of the last pass over its workgroups, in ascending order, one lane per (right-hand side, slot), and what the next kernel needs
 // of them.  kMgFinRaw: res[4 v + s] = sum s, s < 4 (what the host reads);  kMgFinCoef: coef[32 v + s] = sum s;
 // kMgFinNorm (after mg_multiaxpy_kernel): sc[4 v] = (nu = sqrt ||q||^2, <q, r> / nu), zero for nu = 0;
-// kMgFinMr (after mg_dot2_kernel): sc[4 v] = omega <t, s> / <t, t>, zero for <t, t> = 0
-enum { kMgFinRaw = 0, kMgFinCoef = 1, kMgFinNorm = 2, kMgFinMr = 3 };
-__global__ __launch_bounds__(kMgThreads) void mg_final_sum_kernel(const double *partial, int nGroups, int nUsed, unsigned active, int mode, double omega,
-                                                                 double *coef, double *sc, double *res) {
-  __shared__ double sum[kMgBlock][kMgSlots];
-  const int t = threadIdx.x, v = t / kMgSlots, s = t - v * kMgSlots;
-  double a = 0.0;
-  if (((active >> v) & 1u) && s < nUsed)
-    for (int g = 0; g < nGroups; g++) a += partial[((size_t)v * nGroups + g) * kMgSlots + s];
-  sum[v][s] = a;
-  __syncthreads();
+// kMgFinMr (after mg_dot2_kernel): sc[4 v] = omega <t, s> / <t, t>, zero for <t, t> = 0.
+// kMgFinTable (a rank of a process grid): the raw sums go into this rank's entry `mine` of the rank table [rank][kMgBlock][kMgSlots] and
+// nothing else is written; the entries of all ranks are then gathered and mg_rank_sum_kernel applies the mode to their sum
+enum { kMgFinRaw = 0, kMgFinCoef = 1, kMgFinNorm = 2, kMgFinMr = 3, kMgFinTable = 4 };
+// what a mode makes of the sums: lane t = (v, s) holds sum s of right-hand side v in `a`, all of them are in `sum` (after a barrier).
+// The guards nu > 0 and <t, t> > 0 act on the sums they are handed: on a process grid those over all ranks
+__device__ inline void mg_sum_epilogue(int mode, double a, const double (*sum)[kMgSlots], int t, int v, int s, double omega, double *coef, double *sc,
+                                       double *res) {
   if (mode == kMgFinCoef) {
     coef[t] = a;
   } else if (mode == kMgFinRaw) {
@@ -259,6 +258,33 @@ __global__ __launch_bounds__(kMgThreads) void mg_final_sum_kernel(const double *
       sc[4 * v + 1] = d > 0.0 ? omega * sum[v][1] / d : 0.0;
     }
   }
+}
+__global__ __launch_bounds__(kMgThreads) void mg_final_sum_kernel(const double *partial, int nGroups, int nUsed, unsigned active, int mode, double omega,
+                                                                 double *coef, double *sc, double *res, double *mine) {
+  __shared__ double sum[kMgBlock][kMgSlots];
+  const int t = threadIdx.x, v = t / kMgSlots, s = t - v * kMgSlots;
+  double a = 0.0;
+  if (((active >> v) & 1u) && s < nUsed)
+    for (int g = 0; g < nGroups; g++) a += partial[((size_t)v * nGroups + g) * kMgSlots + s];
+  if (mode == kMgFinTable) {  // (uniform over the workgroup)
+    mine[t] = a;
+    return;
+  }
+  sum[v][s] = a;
+  __syncthreads();
+  mg_sum_epilogue(mode, a, sum, t, v, s, omega, coef, sc, res);
+}
+// The sum over the ranks: one workgroup, lane t = (right-hand side, slot) adds entry t of table[0 .. size) in ascending rank order -- the
+// same additions on every rank, so every rank holds the same bits -- and applies `mode` to the sums.  A slot or a right-hand side the
+// local pass did not use is zero in every entry
+__global__ __launch_bounds__(kMgThreads) void mg_rank_sum_kernel(const double *table, int size, int mode, double omega, double *coef, double *sc, double *res) {
+  __shared__ double sum[kMgBlock][kMgSlots];
+  const int t = threadIdx.x, v = t / kMgSlots, s = t - v * kMgSlots;
+  double a = 0.0;
+  for (int r = 0; r < size; r++) a += table[(size_t)r * kMgThreads + t];
+  sum[v][s] = a;
+  __syncthreads();
+  mg_sum_epilogue(mode, a, sum, t, v, s, omega, coef, sc, res);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
@@ -286,6 +312,53 @@ template <typename F> size_t fine_bytes(const MugiqHipSpinorField &f) { return a
 template <typename F> size_t coarse_bytes(const MugiqHipCoarseField &f) { return align256((size_t)2 * (size_t)f.parity_offset * sizeof(Cplx<F>)); }
 size_t scalar_bytes() { return align256(sizeof(double) * ((size_t)kMgBlock * kMgMaxGroups * kMgSlots + kMgBlock * kMgSlots + 2 * 4 * kMgBlock)); }
 
+// The messages of the ring gather that completes a rank table (mugiq_hip_mg_rank_sum_plan): over every axis of extent n > 1, t first,
+// n - 1 calls of sendrecv(.., d, +1, ..); call k sends the run of coordinate (c - k + 1) mod n and receives that of (c - k) mod n.  A run
+// are the entries of the ranks that share the coordinates of the axes still to come: with x slowest and t fastest one contiguous piece
+int rank_sum_plan(const int grid[4], const int coord[4], int maxOps, int *dim, int *sendEntry, int *recvEntry, int *entries) {
+  int nMsg = 0, run = 1;
+  for (int d = 3; d >= 0; d--) {
+    const int n = grid[d], c = coord[d];
+    int base = 0;
+    for (int e = 0; e < 4; e++) base = base * grid[e] + (e < d ? coord[e] : 0);
+    for (int k = 1; k < n; k++, nMsg++) {
+      if (nMsg >= maxOps) continue;
+      if (dim) dim[nMsg] = d;
+      if (sendEntry) sendEntry[nMsg] = base + ((c - k + 1 + n) % n) * run;
+      if (recvEntry) recvEntry[nMsg] = base + ((c - k + n) % n) * run;
+      if (entries) entries[nMsg] = run;
+    }
+    run *= n;
+  }
+  return nMsg;
+}
+
+// the sum over the ranks of a solver on a process grid of more than one rank: the table in the workspace, the messages of this rank, and
+// the counts of MugiqHipMgSolveGridInfo
+struct MgRankSum {
+  const MugiqHipComm *comm = nullptr;
+  const char *who = "";
+  double *table = nullptr;
+  std::vector<int> dim, sendEntry, recvEntry, entries;
+  mutable int sums = 0;
+  size_t bytes() const { return align256(sizeof(double) * (size_t)comm->size * kMgThreads); }
+  void init(const MugiqHipComm *c, const char *who_) {
+    comm = c, who = who_;
+    const int n = rank_sum_plan(c->grid, c->coord, 0, nullptr, nullptr, nullptr, nullptr);
+    dim.resize(n), sendEntry.resize(n), recvEntry.resize(n), entries.resize(n);
+    rank_sum_plan(c->grid, c->coord, n, dim.data(), sendEntry.data(), recvEntry.data(), entries.data());
+  }
+  // every rank's entry into every rank's table, in stream order: no host read, no packing
+  int gather(hipStream_t stream) const {
+    for (size_t m = 0; m < dim.size(); m++)
+      if (int st = comm->sendrecv(comm->ctx, table + (size_t)sendEntry[m] * kMgThreads, table + (size_t)recvEntry[m] * kMgThreads,
+                                  sizeof(double) * (size_t)entries[m] * kMgThreads, dim[m], +1, stream))
+        return set_error(MUGIQ_HIP_ERROR_HIP, "%s: rank sum sendrecv callback failed with status %d", who, st);
+    sums++;
+    return MUGIQ_HIP_SUCCESS;
+  }
+};
+
 // D_i = S_i for the active i < n, from storage FS in layout Ls to storage FD in layout Ld (mg_convert_kernel)
 template <typename FD, typename FS>
 int mg_convert(const MgVecs<FD> &D, const MgVecs<FS> &S, const MgLayout &Ld, const MgLayout &Ls, int n, unsigned active, bool wide, hipStream_t stream) {
@@ -307,6 +380,7 @@ template <typename F> struct MgLevel {
   C *P = nullptr, *Q = nullptr;  // nDir x nb vectors each
   double *partial = nullptr, *coef = nullptr, *sc = nullptr, *res = nullptr;  // shared by all levels: the stream orders their passes (MgSolver::carve)
   hipStream_t stream = nullptr;
+  const MgRankSum *rs = nullptr;  // a process grid of more than one rank: every final sum goes through the rank table
 
   void set(hipStream_t stream_, int nb_, bool wide_, const MgLayout &l, size_t vecBytes) {
     stream = stream_, nb = nb_, wide = wide_, L = l;
@@ -324,7 +398,17 @@ template <typename F> struct MgLevel {
   dim3 grid(int n) const { return dim3(nGroups, n); }
 
   int final_sum(int nUsed, unsigned active, int mode, double omega) const {
-    hipLaunchKernelGGL(mg_final_sum_kernel, dim3(1), dim3(kMgThreads), 0, stream, partial, nGroups, nUsed, active, mode, omega, coef, sc, res);
+    if (rs) {  // local sums into this rank's entry, the gather, the sum over the ranks and the epilogue of the mode
+      hipLaunchKernelGGL(mg_final_sum_kernel, dim3(1), dim3(kMgThreads), 0, stream, partial, nGroups, nUsed, active, (int)kMgFinTable, omega, coef, sc, res,
+                         rs->table + (size_t)rs->comm->rank * kMgThreads);
+      MUGIQ_CHECK_HIP(hipGetLastError());
+      if (int st = rs->gather(stream)) return st;
+      hipLaunchKernelGGL(mg_rank_sum_kernel, dim3(1), dim3(kMgThreads), 0, stream, rs->table, rs->comm->size, mode, omega, coef, sc, res);
+      MUGIQ_CHECK_HIP(hipGetLastError());
+      return MUGIQ_HIP_SUCCESS;
+    }
+    hipLaunchKernelGGL(mg_final_sum_kernel, dim3(1), dim3(kMgThreads), 0, stream, partial, nGroups, nUsed, active, mode, omega, coef, sc, res,
+                       (double *)nullptr);
     MUGIQ_CHECK_HIP(hipGetLastError());
     return MUGIQ_HIP_SUCCESS;
   }
@@ -411,7 +495,7 @@ template <typename F> struct MgSolver {
   int nb, nDirFine, sets;
   int nCoarse;  // coarse levels in use (init): level l is, when every cycle above it takes its coarse step
   size_t fb;
-  OpContext stencil;          // M of this solver on the single domain check_problem admits: no halo exchange, no send buffer
+  OpContext stencil;          // M of this solver: on a single domain no halo exchange and no send buffer, on a process grid (set_grid) both
   TransferSwitches switches;  // as the call found them (init)
   size_t packedBytes;         // of `packed`, the packed coarse vectors of P_0 for nb vectors (ProlongForm::workspaceBytes)
   void *packed;
@@ -424,6 +508,34 @@ template <typename F> struct MgSolver {
   size_t deflBytes = 0;      // of deflMem, the space of this call on the device (CoarseDeflationWork, csrc/mg_common.h)
   void *deflMem = nullptr;
   CoarseDeflationWork defl;
+  // A rank of a process grid (set_grid, before init; the *_grid entry points, F = double, one coarse level).  part: the partitioned axes;
+  // with none of them everything below is empty and the solver is the single-domain one, launch for launch
+  const MugiqHipComm *comm = nullptr;
+  const MugiqHipCoarseHalo *halo = nullptr;
+  int part[4] = {0, 0, 0, 0};
+  bool anyPart = false;
+  size_t bodyBytes = 0, ghostBytes = 0, sendBytes = 0;  // of a fine vector's body and of its ghost zones (fb is their sum); of stencil.send
+  unsigned char *lent[kMgBlock] = {};  // ghost zones lent to an input of the stencil that the caller owns (z of K, x of the solve)
+  MgRankSum rankSum;                   // in use with more than one rank
+  mutable int fineExchanges = 0;
+  mutable CoarseGridCounts coarseCounts;
+
+  void set_grid(const MugiqHipComm *comm_, const int part_[4], const MugiqHipCoarseHalo *halo_) {
+    comm = comm_, halo = halo_;
+    for (int d = 0; d < 4; d++) anyPart |= (part[d] = part_[d]) != 0;
+  }
+  void grid_info(MugiqHipMgSolveGridInfo *g) const {
+    g->fineExchanges = fineExchanges, g->coarseExchanges = coarseCounts.exchanges;
+    g->rankSums = rankSum.sums, g->rankSumMessages = rankSum.sums * (int)rankSum.dim.size();
+  }
+  // the ghost zones of f on the partitioned axes, from `zones` on (NULL: none)
+  void set_ghosts(MugiqHipSpinorField &f, unsigned char *zones) const {
+    for (int d = 0; d < 4; d++)
+      for (int b = 0; b < 2; b++) {
+        f.ghost[d][b] = part[d] && zones ? zones : nullptr;
+        if (part[d] && zones) zones += stencil_zone_bytes(fineLike, (int)sizeof(F), d);
+      }
+  }
 
   static Vecs vecs(const MugiqHipSpinorField *f, int n) {
     Vecs m{};
@@ -438,6 +550,7 @@ template <typename F> struct MgSolver {
   MugiqHipSpinorField fine_dir(C *base, int j, int v) const {
     MugiqHipSpinorField f = fineLike;
     f.data = fine.dir(base, j, v);
+    if (anyPart) set_ghosts(f, static_cast<unsigned char *>(f.data) + bodyBytes);
     return f;
   }
   template <typename T> static int gather(const T *set, int n, unsigned mask, T *out) {
@@ -451,6 +564,15 @@ template <typename F> struct MgSolver {
     MugiqHipSpinorField d[kMgBlock], sr[kMgBlock];
     const int m = gather(dst, n, active, d);
     gather(src, n, active, sr);
+    if (anyPart) {  // the ghost zones of src are exchanged first; an input of the caller's that has none borrows the solver's
+      for (int i = 0; i < m; i++)
+        for (int dd = 0; dd < 4; dd++)
+          if (part[dd] && (sr[i].ghost[dd][0] == nullptr || sr[i].ghost[dd][1] == nullptr)) {
+            set_ghosts(sr[i], lent[i]);
+            break;
+          }
+      fineExchanges++;
+    }
     if (int e = debug_poison_lds_if_asked(stream)) return e;
     return stencil_apply(stencil, d, sr, m, 0, 0, 1.0);
   }
@@ -459,6 +581,7 @@ template <typename F> struct MgSolver {
     MugiqHipCoarseField d[kMgBlock], sr[kMgBlock];
     const int m = gather(dst, n, active, d);
     gather(src, n, active, sr);
+    if (anyPart) return coarse_apply_grid(d, sr, m, A, halo, part, MUGIQ_HIP_EIG_OPERATOR_M, 1.0, comm, stream, false, &coarseCounts);
     return coarse_apply(d, sr, m, A, MUGIQ_HIP_EIG_OPERATOR_M, 1.0, stream);
   }
   // c_i = R f_i and f_i = P c_i through T, from and into the fine level or a coarse one: all that tells level 0 from the others in a cycle
@@ -487,10 +610,20 @@ template <typename F> struct MgSolver {
   // statement of the layout: it places this solver's share, and run without a workspace it counts it (place()).  The mixed solve carves
   // two solvers from one reservation.  Nothing the solver calls reserves the arena again: the stencil and the transfers are the internal
   // entries, which work in what they are handed (the prolongator in `packed`), and coarse_apply with the form M takes no work memory.
+  //
+  // On a process grid (set_grid) two of the calls do take work memory, and the layout answers both.  The stencil packs the faces it sends
+  // into OpContext::send: stencil_send_bytes for nb fields stand at the very start of this solver's share, in front of `packed`, behind the
+  // rank table of more than one rank (MgRankSum; [rank][8][32] doubles, next to the scalars whose sums it completes).  coarse_apply_grid
+  // keeps its send and receive faces in the stream's OTHER buffer (stream_workspace, coarse_grid_layout), which nothing else of a solve
+  // uses: reserve() asks for coarse_grid_layout(M, nb).bytes there once, before the first launch, so that the reservations
+  // coarse_apply_grid makes itself are no larger, move nothing and never wait for the stream (the argument of the coarse eigensolver on a
+  // grid).  Every fine vector of the workspace -- the directions, s, t, w, r -- is followed by its ghost zones on the partitioned axes (fb
+  // counts them; the Krylov kernels walk the body alone), since any of them may be the input of a stencil; `lent` are nb more sets of
+  // zones for the inputs the caller owns.  With nothing partitioned all of these are empty and the offsets are the single-domain ones.
   void init(const MugiqHipSpinorField &like, int nDirFine_, int nVecRhs, int sets_, bool withCoarse) {
     nb = std::min(nVecRhs, kMgBlock);
     nDirFine = nDirFine_, sets = sets_;
-    stencil = OpContext{gauge, nullptr, {0, 0, 0, 0}, kappa, stream, nullptr, who, clover};
+    stencil = OpContext{gauge, comm, {part[0], part[1], part[2], part[3]}, kappa, stream, nullptr, who, clover};
     switches = transfer_switches_from_env();
     fineLike = like;
     fineLike.precision = (int)sizeof(F);
@@ -498,8 +631,14 @@ template <typename F> struct MgSolver {
     for (int d = 0; d < 4; d++)
       for (int b = 0; b < 2; b++) fineLike.ghost[d][b] = nullptr;
     const bool wide = debug_wide_index_asked();
-    fb = fine_bytes<F>(like);
+    bodyBytes = fine_bytes<F>(like);
+    ghostBytes = stencil_send_bytes(like, (int)sizeof(F), part, 1);  // (one send buffer per zone: the same bytes)
+    sendBytes = stencil_send_bytes(like, (int)sizeof(F), part, nb);
+    fb = bodyBytes + ghostBytes;
+    if (comm && comm->size > 1) rankSum.init(comm, who);
+    const MgRankSum *rs = comm && comm->size > 1 ? &rankSum : nullptr;
     fine.set(stream, nb, wide, fine_layout(like), fb);
+    fine.rs = rs;
     nCoarse = 0;
     for (int l = 0; l < nGiven && withCoarse && params[l].coarseIters > 0; l++) {
       MgCoarse<F> &c = coarse[nCoarse++];
@@ -509,6 +648,7 @@ template <typename F> struct MgSolver {
       c.like = coarse_side_layout(*c.transfer);
       c.bytes = coarse_bytes<F>(c.like);
       c.lv.set(stream, nb, wide, coarse_layout(c.like), c.bytes);
+      c.lv.rs = rs;
     }
     // (only the finest transfer has a packed form: the coarse -> coarse prolongator takes no work memory)
     deflated = deflation != nullptr && nCoarse == nGiven;
@@ -529,6 +669,9 @@ template <typename F> struct MgSolver {
       return p;
     };
     if (ws) fine.set_scalars(ws);
+    rankSum.table = reinterpret_cast<double *>(take(rankSum.comm ? rankSum.bytes() : 0));
+    stencil.send = take(sendBytes);
+    for (int i = 0; i < nb; i++) lent[i] = take(ghostBytes);
     packed = take(packedBytes);
     fine.P = reinterpret_cast<C *>(take((size_t)nDirFine * nb * fb));
     fine.Q = reinterpret_cast<C *>(take((size_t)nDirFine * nb * fb));
@@ -537,6 +680,7 @@ template <typename F> struct MgSolver {
       for (int i = 0; i < nb && ((sets >> k) & 1); i++) {
         all[k][i] = fineLike;
         all[k][i].data = take(fb);
+        if (anyPart && ws) set_ghosts(all[k][i], static_cast<unsigned char *>(all[k][i].data) + bodyBytes);
       }
     for (int l = 0; l < nCoarse; l++) {
       MgCoarse<F> &c = coarse[l];
@@ -572,6 +716,12 @@ template <typename F> struct MgSolver {
   int reserve(const MugiqHipSpinorField &like, int nDirFine_, int nVecRhs, bool withR) {
     init(like, nDirFine_, nVecRhs, kMgSetsOfK | (withR ? kMgSetR : 0), true);
     if (int st = place(stream, [this](unsigned char *ws) { return carve(ws, scalar_bytes()); })) return st;
+    if (anyPart && nCoarse) {  // the faces of coarse_apply_grid, once and for the most vectors a launch takes (the comment above init)
+      CoarseGridLayout L;
+      coarse_grid_layout(&L, coarse[0].op, part, MUGIQ_HIP_EIG_OPERATOR_M, nb);
+      void *faces = nullptr;
+      if (int st = stream_workspace(&faces, L.bytes, stream)) return st;
+    }
     return upload_deflation();
   }
 
@@ -688,6 +838,14 @@ template <typename F> struct MgSolver {
   }
 };
 
+// what a *_grid entry point adds to a call: the halo of the coarse operator, whether the input needs ghost zones, and (filled by
+// check_problem) the partitioned axes
+struct MgGridArgs {
+  const MugiqHipCoarseHalo *halo;
+  bool inNeedsGhosts;
+  mutable int part[4];
+};
+
 bool same_layout(const MugiqHipSpinorField &a, const MugiqHipSpinorField &b) {
   return same_geometry(a, b) && a.stride == b.stride && a.parity_offset == b.parity_offset;
 }
@@ -708,13 +866,31 @@ int check_param(const MugiqHipMgSolveParam *p, const char *who) {
 // UNSUPPORTED; (4, 4): the sloppy cycle; (8, 4): the mixed solve
 int check_problem(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in, int nVec, const char *outName, const char *inName,
                   const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *op,
-                  const MugiqHipMgSolveParam *param, double kappa, const MugiqHipComm *comm, const char *who, int fieldPrec = 8, int hierPrec = 8) {
+                  const MugiqHipMgSolveParam *param, double kappa, const MugiqHipComm *comm, const char *who, int fieldPrec = 8, int hierPrec = 8,
+                  const MgGridArgs *grid = nullptr) {
   MUGIQ_REQUIRE(out != nullptr && in != nullptr && transfer != nullptr && op != nullptr && gauge != nullptr, "%s: NULL argument", who);
+  MUGIQ_REQUIRE(grid == nullptr || comm != nullptr, "%s: comm is NULL (the single-domain entry points take none)", who);
   MUGIQ_REQUIRE(nVec >= 1, "%s: nVec = %d must be >= 1", who, nVec);
   int st;
   if ((st = check_param(param, who))) return st;
-  if ((st = check_single_domain(comm, who))) return st;
-  if ((st = validate_coarse_operator(op, who))) return st;
+  int part[4] = {0, 0, 0, 0};
+  if (grid) {  // comm -> part, the operator, and its halo on every partitioned axis
+    if ((st = check_coarse_grid(comm, op, grid->halo, part, false, who))) return st;
+    for (int d = 0; d < 4; d++) grid->part[d] = part[d];
+    // the rank table has comm->size entries and the plan addresses it through grid and coord: they must describe one grid
+    long long ranks = 1, me = 0;
+    for (int d = 0; d < 4; d++) {
+      MUGIQ_REQUIRE(comm->grid[d] >= 1 && comm->coord[d] >= 0 && comm->coord[d] < comm->grid[d], "%s: comm grid[%d] = %d, coord[%d] = %d", who, d,
+                    comm->grid[d], d, comm->coord[d]);
+      ranks *= comm->grid[d];
+      me = me * comm->grid[d] + comm->coord[d];
+    }
+    MUGIQ_REQUIRE(ranks == comm->size && me == comm->rank, "%s: comm grid %d x %d x %d x %d and rank %d do not match size %d (x slowest, t fastest)", who,
+                  comm->grid[0], comm->grid[1], comm->grid[2], comm->grid[3], comm->rank, comm->size);
+  } else {
+    if ((st = check_single_domain(comm, who))) return st;
+    if ((st = validate_coarse_operator(op, who))) return st;
+  }
   MUGIQ_REQUIRE(transfer->V != nullptr, "%s: transfer / null vectors are NULL", who);
   for (int i = 0; i < nVec; i++) {
     if ((st = validate_spinor(&out[i], who, outName))) return st;
@@ -741,12 +917,16 @@ int check_problem(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in,
   if ((st = validate_transfer_operator(transfer, op, who))) return st;  // (the precisions agree by the checks above)
   for (int d = 0; d < 4; d++)
     MUGIQ_REQUIRE(in[0].X[d] == transfer->X[d], "%s: the fields have X[%d] = %d, the transfer %d", who, d, in[0].X[d], transfer->X[d]);
-  const int part[4] = {0, 0, 0, 0};
   if ((st = check_gauge(gauge, in[0].X, part, who))) return st;
   if (clover) {
     if ((st = validate_clover(clover, in[0].X, in[0].volumeCB, who))) return st;
     MUGIQ_REQUIRE(clover->precision == gauge->precision, "%s: clover precision %d differs from the gauge precision %d", who, clover->precision, gauge->precision);
   }
+  // an input of the stencil that the caller owns and the solver does not copy (r of the cycle) brings its ghost zones
+  for (int d = 0; grid && grid->inNeedsGhosts && d < 4; d++)
+    for (int i = 0; part[d] && i < nVec; i++)
+      MUGIQ_REQUIRE(in[i].ghost[d][0] != nullptr && in[i].ghost[d][1] != nullptr, "%s: dimension %d is partitioned but %s vector %d has no ghost zones for it",
+                    who, d, inName, i);
   // the operator must be the one of this M: a coarse operator of another kappa or clover term would still converge, only slowly and silently
   MUGIQ_REQUIRE(op->kappa == kappa, "%s: the coarse operator was built for kappa = %.17g, the call has kappa = %.17g", who, op->kappa, kappa);
   MUGIQ_REQUIRE((op->hasClover != 0) == (clover != nullptr), "%s: the coarse operator was built %s a clover field, the call is %s one", who,
@@ -761,12 +941,12 @@ int check_problem(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in,
 int check_levels(const MugiqHipSpinorField *out, const MugiqHipSpinorField *in, int nVec, const char *outName, const char *inName,
                  const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover, const MugiqHipTransfer *transfers_h, const MugiqHipCoarseOperator *coarseOps_h,
                  int nCoarseLevels, const MugiqHipMgSolveParam *params_h, double kappa, const MugiqHipComm *comm, const char *who, int fieldPrec = 8,
-                 int hierPrec = 8) {
+                 int hierPrec = 8, const MgGridArgs *grid = nullptr) {
   static_assert(kMgMaxCoarse == 2, "the message below names the cycles that exist");
   if (nCoarseLevels < 1 || nCoarseLevels > kMgMaxCoarse)
     return set_error(MUGIQ_HIP_ERROR_UNSUPPORTED, "%s: nCoarseLevels = %d: a two-grid (1) or a three-level (2) cycle", who, nCoarseLevels);
   int st;
-  if ((st = check_problem(out, in, nVec, outName, inName, gauge, clover, transfers_h, coarseOps_h, params_h, kappa, comm, who, fieldPrec, hierPrec))) return st;
+  if ((st = check_problem(out, in, nVec, outName, inName, gauge, clover, transfers_h, coarseOps_h, params_h, kappa, comm, who, fieldPrec, hierPrec, grid))) return st;
   for (int l = 1; l < nCoarseLevels; l++) {
     const MugiqHipTransfer *T = &transfers_h[l];
     const MugiqHipCoarseOperator *Ma = &coarseOps_h[l - 1], *Mb = &coarseOps_h[l];  // M_l above the transfer, M_{l+1} below it
@@ -899,14 +1079,16 @@ template <typename F>
 int precondition_levels(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover,
                         double kappa, const MugiqHipTransfer *transfers_h, const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels,
                         const MugiqHipMgSolveParam *params_h, const MugiqHipCoarseDeflation *deflation, const MugiqHipComm *comm, void *stream,
-                        const char *who) {
+                        const char *who, const MgGridArgs *grid = nullptr) {
   const int prec = (int)sizeof(F);
   int st;
-  if ((st = check_levels(z_h, r_h, nVec, "z", "r", gauge, clover, transfers_h, coarseOps_h, nCoarseLevels, params_h, kappa, comm, who, prec, prec))) return st;
+  if ((st = check_levels(z_h, r_h, nVec, "z", "r", gauge, clover, transfers_h, coarseOps_h, nCoarseLevels, params_h, kappa, comm, who, prec, prec, grid)))
+    return st;
   if ((st = check_deflation(deflation, coarseOps_h, nCoarseLevels, z_h, r_h, nVec, who))) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
   MgSolver<F> S{gauge, clover, kappa, transfers_h, coarseOps_h, params_h, nCoarseLevels, s, who, deflation};
+  if (grid) S.set_grid(comm, grid->part, grid->halo);
   if ((st = S.reserve(r_h[0], 0, nVec, false))) return st;
   for (int v0 = 0; v0 < nVec; v0 += kMgBlock) {
     const int n = std::min(kMgBlock, nVec - v0);
@@ -918,10 +1100,11 @@ int precondition_levels(const MugiqHipSpinorField *z_h, const MugiqHipSpinorFiel
 int solve_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge, const MugiqHipCloverField *clover,
                  double kappa, const MugiqHipTransfer *transfers_h, const MugiqHipCoarseOperator *coarseOps_h, int nCoarseLevels,
                  const MugiqHipMgSolveParam *params_h, const MugiqHipCoarseDeflation *deflation, int *iters_out, double *relres_out, double *history_out,
-                 int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream, const char *who) {
-  MUGIQ_REQUIRE(iters_out != nullptr && relres_out != nullptr, "%s: NULL argument", who);
+                 int historyStride, int *hostReads_out, const MugiqHipComm *comm, void *stream, const char *who, const MgGridArgs *grid = nullptr,
+                 MugiqHipMgSolveGridInfo *gridInfo_out = nullptr) {
+  MUGIQ_REQUIRE(iters_out != nullptr && relres_out != nullptr && (grid == nullptr || gridInfo_out != nullptr), "%s: NULL argument", who);
   int st;
-  if ((st = check_levels(x_h, b_h, nVec, "x", "b", gauge, clover, transfers_h, coarseOps_h, nCoarseLevels, params_h, kappa, comm, who))) return st;
+  if ((st = check_levels(x_h, b_h, nVec, "x", "b", gauge, clover, transfers_h, coarseOps_h, nCoarseLevels, params_h, kappa, comm, who, 8, 8, grid))) return st;
   if ((st = check_deflation(deflation, coarseOps_h, nCoarseLevels, x_h, b_h, nVec, who))) return st;
   const MugiqHipMgSolveParam *param = &params_h[0];
   MUGIQ_REQUIRE(history_out == nullptr || historyStride >= param->maxIter, "%s: historyStride = %d is smaller than maxIter = %d", who, historyStride,
@@ -929,8 +1112,11 @@ int solve_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h,
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((st = debug_poison_lds_if_asked(s))) return st;
   MgSolver<double> S{gauge, clover, kappa, transfers_h, coarseOps_h, params_h, nCoarseLevels, s, who, deflation};
+  if (grid) S.set_grid(comm, grid->part, grid->halo);
   if ((st = S.reserve(b_h[0], param->nKrylov, nVec, true))) return st;
-  return outer_solve(S, nullptr, x_h, b_h, nVec, param, iters_out, relres_out, history_out, historyStride, hostReads_out, who);
+  st = outer_solve(S, nullptr, x_h, b_h, nVec, param, iters_out, relres_out, history_out, historyStride, hostReads_out, who);
+  if (gridInfo_out && (st == MUGIQ_HIP_SUCCESS || st == MUGIQ_HIP_ERROR_NOT_CONVERGED)) S.grid_info(gridInfo_out);
+  return st;
 }
 
 int solve_mixed_levels(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
@@ -1005,6 +1191,30 @@ int mugiq_hip_mg_solve(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField
                        const MugiqHipComm *comm, void *stream) {
   return solve_levels(x_h, b_h, nVec, gauge, clover, kappa, transfer, coarseOp, 1, param, nullptr, iters_out, relres_out, history_out, historyStride, hostReads_out,
                       comm, stream, "mgSolve");
+}
+
+/* the two-grid fp64 cycle and solve for a rank of a process grid.  With nothing partitioned the launches of the two calls above */
+int mugiq_hip_mg_precondition_grid(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,
+                                   const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *coarseOp,
+                                   const MugiqHipCoarseHalo *halo, const MugiqHipMgSolveParam *param, const MugiqHipComm *comm, void *stream) {
+  const MgGridArgs grid{halo, true, {0, 0, 0, 0}};
+  return precondition_levels<double>(z_h, r_h, nVec, gauge, clover, kappa, transfer, coarseOp, 1, param, nullptr, comm, stream, "mgPreconditionGrid", &grid);
+}
+
+int mugiq_hip_mg_solve_grid(const MugiqHipSpinorField *x_h, const MugiqHipSpinorField *b_h, int nVec, const MugiqHipGaugeField *gauge,
+                            const MugiqHipCloverField *clover, double kappa, const MugiqHipTransfer *transfer, const MugiqHipCoarseOperator *coarseOp,
+                            const MugiqHipCoarseHalo *halo, const MugiqHipMgSolveParam *param, int *iters_out, double *relres_out, double *history_out,
+                            int historyStride, int *hostReads_out, MugiqHipMgSolveGridInfo *gridInfo_out, const MugiqHipComm *comm, void *stream) {
+  const MgGridArgs grid{halo, false, {0, 0, 0, 0}};
+  return solve_levels(x_h, b_h, nVec, gauge, clover, kappa, transfer, coarseOp, 1, param, nullptr, iters_out, relres_out, history_out, historyStride, hostReads_out,
+                      comm, stream, "mgSolveGrid", &grid, gridInfo_out);
+}
+
+int mugiq_hip_mg_rank_sum_plan(const int grid[4], const int coord[4], int maxOps, int *dim_out, int *sendEntry_out, int *recvEntry_out, int *entries_out) {
+  if (grid == nullptr || coord == nullptr || maxOps < 0) return -1;
+  for (int d = 0; d < 4; d++)
+    if (grid[d] < 1 || coord[d] < 0 || coord[d] >= grid[d]) return -1;
+  return rank_sum_plan(grid, coord, maxOps, dim_out, sendEntry_out, recvEntry_out, entries_out);
 }
 
 int mugiq_hip_mg_precondition_sloppy(const MugiqHipSpinorField *z_h, const MugiqHipSpinorField *r_h, int nVec, const MugiqHipGaugeField *gauge,

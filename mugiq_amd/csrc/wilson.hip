@@ -434,6 +434,7 @@ bool same_layout(const MugiqHipSpinorField &a, const MugiqHipSpinorField &b) {
 }  // namespace
 
 size_t stencil_send_bytes(const MugiqHipSpinorField &like, int prec, const int part[4], int n) { return (size_t)n * ghost_bytes(like, prec, part); }
+size_t stencil_zone_bytes(const MugiqHipSpinorField &like, int prec, int d) { return align256(zone_bytes(like, prec, d)); }
 
 int check_gauge(const MugiqHipGaugeField *U, const int X[4], const int part[4], const char *who) {
   MUGIQ_REQUIRE(U != nullptr && U->data != nullptr, "%s: gauge field is NULL", who);

@@ -23,6 +23,7 @@ MgSetupInfo = collections.namedtuple("MgSetupInfo", "cgIters minPivotRatio zeroC
 MgSetupCoarseInfo = collections.namedtuple("MgSetupCoarseInfo", "theta residual eigensolve minPivotRatio zeroColumns orthonormality")
 CoarseEigInfo = collections.namedtuple("CoarseEigInfo", "iters nConverged opBlocks aMaxUsed aMinLast orthonormality hostReads hostDenseSeconds converged")
 CoarseEigGridInfo = collections.namedtuple("CoarseEigGridInfo", "exchanges rankSums packLaunches stepPacked")
+MgSolveGridInfo = collections.namedtuple("MgSolveGridInfo", "fineExchanges coarseExchanges rankSums rankSumMessages")
 
 
 def _stream():
@@ -479,6 +480,62 @@ def mgSolve(b, gauge, kappa, transfer, coarseOp, clover=None, x=None, allow_unco
     mgPrecondition (mugiq_hip_mg_solve_levels_deflated)."""
     return _mg_solve("mgSolve", "mugiq_hip_mg_solve", b, gauge, kappa, transfer, coarseOp, clover, None, x, allow_unconverged, comm, coarseParam, param,
                      deflation)
+
+
+def mgPreconditionGrid(z, r, gauge, kappa, transfer, coarseOp, comm, clover=None, **param):
+    """mgPrecondition (two-grid, fp64) on a process grid (mugiq_hip_mg_precondition_grid; collective): the rank's local fields, gauge with a
+    border on every partitioned axis, coarseOp from computeCoarseOperatorGrid (its coarseOp.halo is passed on).  r is read by the stencil
+    in place: its ghost zones on the partitioned axes are allocated here if missing.  On an unpartitioned comm this is mgPrecondition."""
+    z, r = list(z), list(r)
+    if comm is None or len(z) != len(r) or not r:
+        raise _lib.MugiqHipError("mgPreconditionGrid: needs a comm and the same number (at least one) of z and r vectors, got %d and %d" % (len(z), len(r)))
+    _alloc_ghosts(r, comm)
+    keep = []
+    p, t, o, g = mgSolveParam(**param), transfer.desc(), coarseOp.desc(), gauge.desc()
+    _lib.check(_lib.load().mugiq_hip_mg_precondition_grid(desc_array(z), desc_array(r), len(r), ctypes.byref(g), _clover_ptr(clover, keep), float(kappa),
+                                                          ctypes.byref(t), ctypes.byref(o), _halo_ptr(coarseOp, comm, keep), ctypes.byref(p),
+                                                          _comm_ptr(comm, keep), _stream()))
+
+
+def mgSolveGrid(b, gauge, kappa, transfer, coarseOp, comm, clover=None, x=None, allow_unconverged=False, **param):
+    """mgSolve (two-grid, fp64) on a process grid (mugiq_hip_mg_solve_grid; collective): arguments as for mgPreconditionGrid; b and x need
+    no ghost zones.  Every inner product is added over the ranks on the device, in rank order: iters, relres, history and hostReads are the
+    same bits on every rank.  Returns (x, MgSolveInfo, MgSolveGridInfo(fineExchanges, coarseExchanges, rankSums, rankSumMessages))."""
+    b = list(b)
+    if comm is None or not b:
+        raise _lib.MugiqHipError("mgSolveGrid: needs a comm and at least one right-hand side")
+    if x is None:
+        x = [SpinorField(f.X, 8, f.order, f.stride - f.volumeCB, device=f.device) for f in b]
+    x = list(x)
+    n = len(b)
+    if len(x) != n:
+        raise _lib.MugiqHipError("mgSolveGrid: %d x and %d b vectors" % (len(x), n))
+    keep = []
+    p, t, o, g = mgSolveParam(**param), transfer.desc(), coarseOp.desc(), gauge.desc()
+    stride = max(int(p.maxIter), 1)
+    iters, relres, hist = (ctypes.c_int * n)(), (ctypes.c_double * n)(), (ctypes.c_double * (n * stride))()
+    reads, ginfo = ctypes.c_int(0), _lib.MgSolveGridInfo()
+    st = _lib.load().mugiq_hip_mg_solve_grid(desc_array(x), desc_array(b), n, ctypes.byref(g), _clover_ptr(clover, keep), float(kappa), ctypes.byref(t),
+                                             ctypes.byref(o), _halo_ptr(coarseOp, comm, keep), ctypes.byref(p), iters, relres, hist, stride,
+                                             ctypes.byref(reads), ctypes.byref(ginfo), _comm_ptr(comm, keep), _stream())
+    if st != 0 and not (st == STATUS_NOT_CONVERGED and allow_unconverged):
+        _lib.check(st)
+    it = np.array(iters)
+    h = np.array(hist).reshape(n, stride)
+    return (x, MgSolveInfo(it, np.array(relres), st == 0, [h[i, :it[i]].copy() for i in range(n)], int(reads.value)),
+            MgSolveGridInfo(int(ginfo.fineExchanges), int(ginfo.coarseExchanges), int(ginfo.rankSums), int(ginfo.rankSumMessages)))
+
+
+def mgRankSumPlan(grid, coord):
+    """The messages the rank at `coord` of the process grid `grid` posts for one sum over the ranks of mgSolveGrid
+    (mugiq_hip_mg_rank_sum_plan; host only): a list of (dim, sendEntry, recvEntry, entries), in order."""
+    lib = _lib.load()
+    n = lib.mugiq_hip_mg_rank_sum_plan(_lib.int4(grid), _lib.int4(coord), 0, None, None, None, None)
+    if n < 0:
+        raise _lib.MugiqHipError("mgRankSumPlan: grid %r, coord %r" % (tuple(grid), tuple(coord)))
+    a = [(ctypes.c_int * max(n, 1))() for _ in range(4)]
+    lib.mugiq_hip_mg_rank_sum_plan(_lib.int4(grid), _lib.int4(coord), n, *a)
+    return [tuple(int(x[m]) for x in a) for m in range(n)]
 
 
 def mgConvertPrecision(dst, src):
